@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X-native Qwen3-TTS hot path.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times K steps, optionally dumps the last step's outputs and prints the line. --full adds what the
+  headline does not need, after the timed steps: continuous batching, the per-kernel roofline probes, the vocoder and Q8_0 legs, the
+  single-utterance / clone latency legs, the CPU baseline and the oracle parity checks of the run.
   N > 1: one rank per GPU. Under torch.distributed.run the ranks come from the environment; a plain `python bench.py --gpus N`
   starts the N rank processes itself (children, before this process touches a GPU) and relays rank 0's JSON line.
 
@@ -184,6 +187,28 @@ def batch_parity(cfg, spk, meta, outs, picks, n_frames=8):
     return rep
 
 
+DUMP_PCM_SAMPLES = 1 << 23   # 32 MB of f32: with the codes well under the 64 MB a dump may take
+
+
+def dump_outputs(path, outs, suffix=""):
+    """--dump-outputs: what the caller of the timed path received in its last step, in utterance order, as float32 / float64 .npy files.
+    codes: every utterance's codec ids stacked [sum of frames, 16] (ids < 2^24: exact in f32); n_frames: frames per utterance; with PCM,
+    pcm_rms: each utterance's full PCM reduced to its RMS (f64), pcm_sample: the concatenated PCM at DUMP_PCM_SAMPLES positions drawn with a
+    fixed seed (all of it when shorter). The workload, weights and sampler seeds are fixed, so equal arguments give equal inputs."""
+    os.makedirs(path, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(path, f"{name}{suffix}.npy"), a)
+    save("codes", np.concatenate([o.codes for o in outs]).astype(np.float32))
+    save("n_frames", np.asarray([o.n_frames for o in outs], dtype=np.float32))
+    pcms = [o.pcm if getattr(o, "pcm", None) is not None else getattr(o, "pcm_i16", None) for o in outs]
+    if all(p is not None for p in pcms):
+        pcms = [p.astype(np.float32) for p in pcms]   # (i16 from the node's gather: integers, exact in f32)
+        save("pcm_rms", np.asarray([np.sqrt(np.mean(p.astype(np.float64) ** 2)) if p.size else 0.0 for p in pcms]))
+        pcm = np.concatenate(pcms)
+        if pcm.size > DUMP_PCM_SAMPLES:
+            pcm = pcm[np.sort(np.random.default_rng(0).choice(pcm.size, DUMP_PCM_SAMPLES, replace=False))]
+        save("pcm_sample", pcm)
+
+
 def node_main(args):
     """`python bench.py --gpus N --node`: the same workload (N x batch utterances, the global list of make_workload) through the
     library's own multi-GPU entry points (q3tts_node_*, include/q3tts.h): ONE process, one engine + one host thread per GPU, requests
@@ -209,6 +234,8 @@ def node_main(args):
     elapsed = time.perf_counter() - t0
     assert all(o.status == 0 for o in outs) and [o.n_frames for o in outs] == frames
     assert all(o.pcm_i16 is not None and o.pcm_i16.size == o.n_frames * 1920 for o in outs)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs)
     audio = sum(frames) * FRAME_SEC * args.steps
     line = {"metric": "audio_sec_per_s", "value": round(audio / elapsed, 2), "unit": "audio-sec/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
@@ -284,7 +311,14 @@ def main():
     ap.add_argument("--probe-kind", type=int, default=0, help="with --probe-only talker / predictor: 0 gate/up GEMM (default), 1 QKV GEMM, 2 attention, 3 O projection, 4 down projection")
     ap.add_argument("--tiny", action="store_true", help="tests only: the small shape of the parity tests instead of the 1.7B shape (the JSON line is marked invalid)")
     ap.add_argument("--node", action="store_true", help="one process: the library's q3tts_node_* entry points drive all --gpus devices (instead of one rank process per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the informational legs: continuous batching, per-kernel roofline probes, vocoder and Q8_0 legs, "
+                         "single-utterance / clone latency, CPU baseline and the oracle parity checks (the --no-* options above skip single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (codec ids, frame counts, a seeded PCM sample, per-utterance PCM RMS) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.node:
         return node_main(args)
@@ -436,11 +470,13 @@ def main():
     assert all(o.status == 0 for o in outs)
     assert [o.n_frames for o in outs] == frames, "forced lengths not honoured"
     timed_outs = outs  # the last timed step's results: value-checked against the oracle below (batch_parity)
+    if args.dump_outputs:   # (N > 1: every rank its own utterances; with the PCM kept on the device for the gather, codes only)
+        dump_outputs(args.dump_outputs, timed_outs, f".rank{rank}" if world > 1 else "")
     # Outside the timed region, for information: the same utterances fed CONTINUOUSLY — 3 x the step's requests in one q3tts_generate_batch
     # call, so freed slots are refilled at once and the batch drains only at the very end (a step of `value` above admits its 64 utterances
     # together and runs its mixed lengths down to one live row: mean live utterances ~40 of 64). Not the contract's metric: steps overlap.
     cont = None
-    if rank == 0 and not args.no_probe and not args.tiny:
+    if rank == 0 and args.full and not args.no_probe and not args.tiny:
         t1 = time.perf_counter()
         couts = eng.generate_batch(reqs * 3)
         cdt = time.perf_counter() - t1
@@ -524,7 +560,7 @@ def main():
             line["gather_check"] = gather_check
         if args.tiny:
             line["invalid"] = "test run on the tiny shape"
-        if not args.no_probe:
+        if args.full and not args.no_probe:
             # Every kernel kind of a decoder block, measured in situ (q3tts_k_probe): the bracket also times the closing event packet; an
             # EMPTY bracket on the same stream (empty_ms) bounds that overhead from above, so a launch's own period lies in
             # [kernel_ms - empty_ms, kernel_ms]; rocprofv3 and the in-kernel timestamps of tools/chain_stamps.hip put it at the lower end
@@ -673,7 +709,7 @@ def main():
 
     # batch = 1 leg (BASELINE configs[1] / configs[4]): RTF and p50 first-chunk latency, outside the timed region
     gpu_codes = gpu_pcm = None
-    if rank == 0 and not args.no_single:
+    if rank == 0 and args.full and not args.no_single:
         eng.close()
         cfg1 = _abi.full_config_py()
         cfg1.device, cfg1.max_batch, cfg1.n_ctx, cfg1.max_steps_cap = local_rank, 1, args.n_ctx, 512
@@ -724,7 +760,7 @@ def main():
             "front_end_ms_p50": round(float(np.median(fe)), 2), "first_chunk_ms_p50": round(float(np.median(cf)), 2),
             "first_chunk_incl_front_end_ms_p50": round(float(np.median(np.asarray(fe) + np.asarray(cf))), 2)}
         e1.close()
-    if rank == 0 and not args.no_cpu_baseline:  # (rank 0 only, after the timed region and its barrier; the other ranks wait at the last barrier)
+    if rank == 0 and args.full and not args.no_cpu_baseline:  # (rank 0 only, after the timed region and its barrier; the other ranks wait at the last barrier)
         line["cpu_baseline"], parity = cpu_baseline(cfg, spk, cfg.with_vocoder, gpu_codes, gpu_pcm)
         if parity:
             line["parity_in_this_run"] = parity

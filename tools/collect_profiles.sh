@@ -48,5 +48,5 @@ else
   fi
   bash $R/tools/overlap_trace.sh > $OUT/decoder_vocoder_overlap.txt 2>&1; tail -4 $OUT/decoder_vocoder_overlap.txt
   for b in xcd_bench kernarg_bench; do (cd $R && hipcc --offload-arch=gfx950 -O3 -w -o tools/$b tools/$b.hip) && timeout -k 10 150 $R/tools/$b > $OUT/$b.txt 2>&1; done
-  cd $R && python bench.py > $OUT/bench_b64_n1.json 2> $OUT/bench_b64_n1.err; tail -c 600 $OUT/bench_b64_n1.json
+  cd $R && python bench.py --full > $OUT/bench_b64_n1.json 2> $OUT/bench_b64_n1.err; tail -c 600 $OUT/bench_b64_n1.json
 fi
