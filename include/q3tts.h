@@ -190,6 +190,70 @@ int q3tts_stream_begin(q3tts_engine* e, const q3tts_request* req, q3tts_stream**
 int q3tts_stream_poll(q3tts_stream* s, const float** chunk, int32_t* n_samples, int32_t* is_final);
 int q3tts_stream_end(q3tts_stream* s, q3tts_result* out_codes_optional);
 
+/* ---- sessions: continuous batching with per-request streaming ------------------------------------------------------------
+ * The serving form of run_inference_stream (src/tts/engine.rs:445-656) for many utterances at once: requests are submitted into a
+ * running batch at any time, each request's 4-frame chunks are delivered as they are produced, and a request can be cancelled.
+ * One worker thread per session drives the engine's max_batch slots: between 4-frame chunks it admits queued requests into free
+ * slots, retires cancelled ones, runs the frame steps and the batched vocoder, and gathers every slot's new PCM with one kernel launch
+ * and one device-to-host copy into pinned staging.
+ *
+ * Ownership: an open session owns its engine. While it is open, q3tts_generate / q3tts_generate_batch, q3tts_stream_begin, every
+ * q3tts_k_* call that takes the engine, q3tts_set_sampler / q3tts_set_max_steps / q3tts_set_device_pcm, q3tts_build_prompt, q3tts_mel,
+ * the q3tts_clone_* calls and a second q3tts_session_create return Q3TTS_ERR_STATE. After q3tts_session_close the engine is usable as
+ * before. The engine needs with_vocoder = 1.
+ *
+ * Contract:
+ *  - Per id, events come in order. Every accepted id gets exactly one final event: DONE, FAILED or CANCELLED (is_final = 1). The
+ *    last CHUNK of a DONE request has is_final = 1 (it may carry 0 samples when the utterance ends on a chunk boundary).
+ *  - A request's chunks have the sample counts q3tts_stream_poll gives for the same request (4-frame chunks, the V4 look-ahead rule
+ *    of the reference's vocoder thread, vocoder_flush_tail honoured; empty polls produce no CHUNK). Joined, they are bit-identical to
+ *    the PCM q3tts_generate_batch returns for that request: results do not depend on slot, batch size or admission time.
+ *  - A request that fails by itself (e.g. prompt + max_steps > n_ctx) gets a FAILED event with its status; other requests are
+ *    unaffected. A device error in the worker fails every open request with Q3TTS_ERR_DEVICE (other internal errors with their
+ *    status); the session then refuses new submissions. Nothing is retried.
+ *  - Memory is bounded: PCM goes through Q3TTS_SESSION_RING_DEPTH pinned staging buffers of max_batch x (4 + lookahead_frames) x
+ *    samples per frame samples each (f32: 4 bytes, i16: 2), plus one device buffer of that size. When every staging buffer still
+ *    holds chunks the consumer has not taken, the worker waits (decoding pauses) instead of allocating.
+ */
+typedef struct q3tts_session q3tts_session;
+#define Q3TTS_SESSION_RING_DEPTH 4
+#define Q3TTS_PCM_F32 0
+#define Q3TTS_PCM_I16 1   /* (x * 32767).clamp(-32768, 32767) as i16, truncation toward zero (src/utils/audio.rs:35-37) */
+#define Q3TTS_EV_NONE 0
+#define Q3TTS_EV_CHUNK 1
+#define Q3TTS_EV_DONE 2
+#define Q3TTS_EV_FAILED 3
+#define Q3TTS_EV_CANCELLED 4
+typedef struct q3tts_session_event {
+    uint64_t id;
+    int32_t kind;          /* Q3TTS_EV_* */
+    int32_t status;        /* FAILED: the request's error status; else Q3TTS_OK */
+    const void* pcm;       /* CHUNK: n_samples f32 or i16 samples (the session's format), owned by the session and valid until the next
+                            * q3tts_session_next call; NULL otherwise */
+    int32_t n_samples;
+    int32_t is_final;      /* 1 on the last CHUNK of a request and on every final event */
+    q3tts_result result;   /* final events: status, codes, n_frames, hit_eos, n_samples (delivered in chunks), sample_rate,
+                            * first_chunk_ms (submit -> first chunk ready for the consumer), total_ms (submit -> final event ready).
+                            * pcm is always NULL (the audio went out as chunks). The caller releases it with q3tts_result_free. */
+} q3tts_session_event;
+/* pcm_format: Q3TTS_PCM_F32 or Q3TTS_PCM_I16. Starts the worker thread. */
+int q3tts_session_create(q3tts_engine* e, int32_t pcm_format, q3tts_session** out);
+/* Thread-safe, any time. The request and everything it points to are copied before the call returns. req->want_pcm is ignored: a
+ * session always produces PCM, in its own format. *id receives the request's id (ids start at 1). Q3TTS_ERR_STATE after a worker
+ * failure. Requests are validated (prompt size, max_steps) at admission: failures arrive as FAILED events. */
+int q3tts_session_submit(q3tts_session* s, const q3tts_request* req, uint64_t* id);
+/* Thread-safe. Takes effect at the next chunk boundary; from the moment it returns no further CHUNK of the id is delivered, and its
+ * final event is CANCELLED. Q3TTS_ERR_INVALID for an unknown id or one whose final event was already delivered. */
+int q3tts_session_cancel(q3tts_session* s, uint64_t id);
+/* One consumer thread. Blocks until an event is ready or timeout_ms runs out (< 0: no limit); a timeout returns Q3TTS_OK with
+ * ev->kind = Q3TTS_EV_NONE. */
+int q3tts_session_next(q3tts_session* s, int32_t timeout_ms, q3tts_session_event* ev);
+/* Cancels everything queued or running, stops the worker and frees the session (events not consumed are discarded and their results
+ * freed). Must not run concurrently with q3tts_session_next. Returns the worker's error status, if it failed. */
+int q3tts_session_close(q3tts_session* s);
+/* Message of the last failing session call or of the worker's failure. */
+const char* q3tts_session_last_error(const q3tts_session* s);
+
 /* ---- one node, several GPUs ----------------------------------------------------------------------
  * The reference is one utterance at a time on one device (n_seq_max = 1, src/models/llama/mod.rs:413; `&mut self`,
  * src/tts/engine.rs:390). Utterances share nothing but read-only weights, so a batch shards over independent units:
@@ -387,6 +451,11 @@ int q3tts_k_norm_inputs(int32_t device, const float* x, int32_t rows, int32_t d,
 /* Allocator contract: device memory is handed out with its zero fill COMPLETED. Allocates `bytes` through the engine's allocator,
  * uploads a pattern into the first and last 4 KiB on the null stream at once, and reports the bytes that read back wrong (0 expected). */
 int q3tts_k_alloc_upload(q3tts_engine* e, int64_t bytes, int64_t* mismatches);
+/* The PCM gather of sessions and of the node's i16 gather (one launch): entry j copies src[row_j][first_j, first_j + count_j) to
+ * out[dst_j, dst_j + count_j); src is [rows][stride] f32 (uploaded to a fresh device buffer), n_ent <= 64; format 0: f32 out, 1: i16 by
+ * the reference's WAV rule. Windows outside src or out (out_n samples) are refused. */
+int q3tts_k_pcm_pack(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* ent_row, const int32_t* ent_first,
+                     const int32_t* ent_count, const int64_t* ent_dst, int32_t n_ent, int32_t format, void* out, int64_t out_n);
 /* rand 0.8 StdRng (ChaCha12) stream: seed_from_u64(seed) then n x gen::<f32>() */
 int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out);
 

@@ -576,6 +576,7 @@ extern "C" void q3tts_clone_default_config(q3tts_clone_config* c) {
 }
 
 extern "C" int q3tts_clone_init(q3tts_engine* e, const q3tts_clone_config* cfg) {
+    Q3_NOT_IN_SESSION(e);
     if (!e || !cfg) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     int rc = validate(e, *cfg);
     if (rc) return rc;
@@ -715,18 +716,21 @@ int audio_run(q3tts_engine* e, const float* audio, int64_t n, int64_t* codes, fl
 
 extern "C" int q3tts_clone_audio_encode(q3tts_engine* e, const float* audio, int64_t n_samples, int64_t* codes, int32_t cap_frames,
                                         int32_t* n_frames) {
+    Q3_NOT_IN_SESSION(e);
     if (!e) return Q3TTS_ERR_INVALID;
     if (!codes) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     return audio_run(e, audio, n_samples, codes, nullptr, cap_frames, n_frames);
 }
 extern "C" int q3tts_k_audio_latent(q3tts_engine* e, const float* audio, int64_t n_samples, float* latent, int32_t cap_frames,
                                     int32_t* n_frames) {
+    Q3_NOT_IN_SESSION(e);
     if (!e) return Q3TTS_ERR_INVALID;
     if (!latent) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     return audio_run(e, audio, n_samples, nullptr, latent, cap_frames, n_frames);
 }
 
 extern "C" int q3tts_clone_speaker_encode(q3tts_engine* e, const float* audio, int64_t n_samples, float* spk_emb) {
+    Q3_NOT_IN_SESSION(e);
     if (!e) return Q3TTS_ERR_INVALID;
     if (!e->clone) return not_loaded(e, "SpeakerEncoder");
     if (!spk_emb || n_samples < 0 || (n_samples > 0 && !audio)) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
@@ -738,6 +742,7 @@ extern "C" int q3tts_clone_speaker_encode(q3tts_engine* e, const float* audio, i
     return speaker_run(e, mel_dev, nf, spk_emb);
 }
 extern "C" int q3tts_k_speaker_from_mel(q3tts_engine* e, const float* mel, int32_t n_frames, float* spk_emb) {
+    Q3_NOT_IN_SESSION(e);
     if (!e) return Q3TTS_ERR_INVALID;
     Q3Clone* c = e->clone;
     if (!c) return not_loaded(e, "SpeakerEncoder");

@@ -1,6 +1,8 @@
 // q3_engine.h — internal engine state of libq3tts (host side, C++). The public surface is include/q3tts.h.
 #pragma once
 #include <algorithm>
+#include <atomic>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -106,10 +108,15 @@ struct q3tts_engine {
     int dev_pcm_on = 0; float* dev_pcm = nullptr; int dev_pcm_n = 0; size_t dev_pcm_stride = 0;
     double hp_launch = 0, hp_sync = 0;  // Q3TTS_HOST_PROF: host wall of run_chunk's launch part / of its wait (per engine: the node drives several from threads)
     float* first_chunk_host = nullptr;  // pinned landing buffer of the first 4-frame PCM chunk (first-chunk latency)
+    std::atomic<q3tts_session*> session{nullptr};  // an open session owns the engine (q3_session.hip)
+    std::mutex err_mu;                  // err is written by the session worker too
 };
 
 // helpers shared with q3_vocoder.hip
 int q3_set_err(q3tts_engine* e, int code, const std::string& msg);
+// calls that drive an engine return Q3TTS_ERR_STATE (with a message) while a session owns it
+int q3_refuse_in_session(q3tts_engine* e);
+#define Q3_NOT_IN_SESSION(e) do { if ((e) && (e)->session.load()) return q3_refuse_in_session(e); } while (0)
 #define Q3_HIP(e, call)                                                                                         \
     do {                                                                                                        \
         hipError_t err__ = (call);                                                                              \
@@ -142,3 +149,11 @@ void q3_voc_mark_last(q3tts_engine* e, int slot);
 float* q3_voc_pcm(q3tts_engine* e, int slot);
 int q3_voc_samples(q3tts_engine* e, int slot);
 int q3_voc_samples_per_frame(const q3tts_engine* e);
+size_t q3_voc_pcm_stride(const q3tts_engine* e);  // samples between the PCM buffers of consecutive slots
+
+// the scheduler steps of q3_engine.hip that the session worker (q3_session.hip) drives between 4-frame chunks
+int q3_plan_rows(q3tts_engine* e, const std::vector<int>& live);
+int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc);
+int q3_run_chunk(q3tts_engine* e, int CH);
+int q3_voc_dispatch(q3tts_engine* e, const char* live, const char* want, int* voc_frames, bool more, bool* first);
+double q3_now_ms();

@@ -15,11 +15,21 @@
 static thread_local std::string g_err;
 
 int q3_set_err(q3tts_engine* e, int code, const std::string& msg) {
-    if (e) e->err = msg;
+    if (e) { std::lock_guard<std::mutex> lk(e->err_mu); e->err = msg; }
     g_err = msg;
     return code;
 }
-extern "C" const char* q3tts_last_error(const q3tts_engine* e) { return e ? e->err.c_str() : g_err.c_str(); }
+extern "C" const char* q3tts_last_error(const q3tts_engine* e) {
+    if (!e) return g_err.c_str();
+    if (!e->session.load()) return e->err.c_str();
+    static thread_local std::string copy;  // a session worker may set e->err meanwhile: the caller reads its own copy
+    std::lock_guard<std::mutex> lk(const_cast<q3tts_engine*>(e)->err_mu);
+    copy = e->err;
+    return copy.c_str();
+}
+int q3_refuse_in_session(q3tts_engine* e) {
+    return q3_set_err(e, Q3TTS_ERR_STATE, "the engine is owned by an open session (q3tts_session_close first)");
+}
 
 // ------------------------------------------------------------------------------------------------
 // configuration
@@ -663,6 +673,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
 
 extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
     if (!e) return;
+    if (q3tts_session* ss = e->session.load()) q3tts_session_close(ss);
     hipSetDevice(e->cfg.device);
     if (e->stream) hipStreamSynchronize(e->stream);
     if (e->vstream) hipStreamSynchronize(e->vstream);
@@ -699,11 +710,13 @@ extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
 
 extern "C" int q3tts_set_sampler(q3tts_engine* e, float temperature, int32_t top_k, float top_p, int32_t has_seed, uint64_t seed) {
     if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
+    Q3_NOT_IN_SESSION(e);
     e->temperature = temperature; e->top_k = top_k; e->top_p = top_p; e->has_seed = has_seed; e->seed = seed;
     return Q3TTS_OK;
 }
 extern "C" int q3tts_set_max_steps(q3tts_engine* e, int32_t n) {
     if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
+    Q3_NOT_IN_SESSION(e);
     if (n < 0 || n > e->cfg.max_steps_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "max_steps exceeds max_steps_cap");
     e->max_steps = n;
     return Q3TTS_OK;
@@ -713,6 +726,7 @@ extern "C" void q3tts_free(void* p) { free(p); }
 // request's PCM in row i of an engine-owned device buffer [n][stride] f32 (valid until the next call); requests with want_pcm = 2
 // skip the host copy altogether.
 extern "C" int q3tts_set_device_pcm(q3tts_engine* e, int32_t enable) {
+    Q3_NOT_IN_SESSION(e);
     if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
     e->dev_pcm_on = enable ? 1 : 0;
     return Q3TTS_OK;
@@ -780,6 +794,7 @@ static int build_prompt_dev(q3tts_engine* e, const q3tts_prompt_desc* p, float* 
 }
 
 extern "C" int q3tts_build_prompt(q3tts_engine* e, const q3tts_prompt_desc* p, float** out_embd, int32_t* out_n) {
+    Q3_NOT_IN_SESSION(e);
     if (!e || !p || !out_embd || !out_n) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     int n = 0;
@@ -976,7 +991,43 @@ static double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-struct SlotRun { int req = -1; int voc_frames = 0; double t_first = 0; };
+struct SlotRun { int req = -1; double t_first = 0; };
+
+// H8: the vocoder consumes 4-frame chunks (src/tts/engine.rs:507-541). One chunk boundary of it, shared by q3tts_generate_batch and the
+// session worker (q3_session.hip): on the vocoder stream behind ev3 (the frames just decoded), batched over every slot that has a chunk
+// ready, so chunk k's PCM overlaps the decoding of chunk k+1. live[b]: slot b holds a request; want[b]: it wants PCM; voc_frames[b]:
+// its frames handed to the vocoder so far (advanced here); more: requests wait for a slot. Finished slots (live, inactive) then get
+// is_last by the reference's flush rule. *first: some slot got its first frames in this call.
+int q3_voc_dispatch(q3tts_engine* e, const char* live, const char* want, int* voc_frames, bool more, bool* first) {
+    const int B = e->B;
+    hipStream_t vs = e->vstream;
+    bool waited = false;
+    *first = false;
+    auto ensure_wait = [&]() -> int { if (!waited) { Q3_HIP(e, hipStreamWaitEvent(vs, e->ev3, 0)); waited = true; } return Q3TTS_OK; };
+    // ONE batched call per chunk: every slot with new frames runs nf = 4. A finished utterance whose tail is
+    // shorter is padded with throw-away frames: the vocoder is causal, so they cannot change the samples already
+    // due, their own samples are never reported, and the slot's vocoder state is reset at its next admission.
+    int list[64], real[64];
+    for (;;) {
+        int ns = 0;
+        for (int b = 0; b < B; ++b) {
+            if (!live[b] || !want[b]) continue;
+            const int pend = e->slots_host[b].n_frames - voc_frames[b];
+            if (pend >= 4 || (pend > 0 && !e->slots_host[b].active)) { real[ns] = std::min(pend, 4); list[ns++] = b; }
+        }
+        if (!ns) break;
+        TRY(ensure_wait());
+        int still = 0;  // slots that go on decoding while this call runs
+        for (int b = 0; b < B; ++b) if (live[b] && e->slots_host[b].active) ++still;
+        TRY(q3_voc_decode_batch(e, list, real, ns, 4, vs, (still > 0 || more) ? 1 : 0));
+        for (int i = 0; i < ns; ++i) { if (voc_frames[list[i]] == 0) *first = true; voc_frames[list[i]] += real[i]; }
+    }
+    // V4 flush: the reference sends is_last only when its final buffer is not empty, i.e. n_frames % 4 != 0 (src/tts/engine.rs:510-536,
+    // restated by q3o_chunk_plan); with lookahead_frames > 0 an utterance of n_frames % 4 == 0 keeps its withheld tail (vocoder_flush_tail = 1: always flush)
+    for (int b = 0; b < B; ++b)
+        if (live[b] && !e->slots_host[b].active && (e->cfg.vocoder_flush_tail || e->slots_host[b].n_frames % 4 != 0)) q3_voc_mark_last(e, b);
+    return Q3TTS_OK;
+}
 
 // Pinned result buffers are recycled through a small process-wide pool: hipHostMalloc / hipHostFree cost ~0.3 ms each, and a
 // batch hands out one PCM buffer per utterance. A 64-byte header in front of the payload remembers the capacity.
@@ -1063,6 +1114,7 @@ static int complete_result(q3tts_engine* e, q3tts_result* o, hipEvent_t fin_ev, 
 
 extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, int32_t n, q3tts_result* outs) {
     if (!e || !reqs || !outs || n <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null/empty argument");
+    Q3_NOT_IN_SESSION(e);
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     for (int i = 0; i < n; ++i) { memset(&outs[i], 0, sizeof(outs[i])); outs[i].status = Q3TTS_ERR_STATE; }
     for (int i = 0; i < n; ++i) {
@@ -1081,6 +1133,8 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
     const int B = e->B, CH = 4;  // 4-frame chunks: src/tts/engine.rs:509-512
     const int spf = e->voc ? q3_voc_samples_per_frame(e) : 0;
     std::vector<SlotRun> run(B);
+    std::vector<int> voc_frames(B, 0);
+    std::vector<char> live(B, 0), want(B, 0);
     const double t0 = now_ms();
     std::vector<int> pending(B, -1);  // request whose PCM copy is still in flight on the vocoder stream, per slot
     auto drain = [&](int b) -> int {
@@ -1113,7 +1167,7 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
                 TRY(admit_many(e, as.data(), ar.data(), (int)as.size(), rcs.data()));
                 for (size_t i = 0; i < as.size(); ++i) {
                     if (rcs[i] != Q3TTS_OK) { outs[ai[i]].status = rcs[i]; ++done; }
-                    else { run[as[i]] = SlotRun{}; run[as[i]].req = ai[i]; }
+                    else { run[as[i]] = SlotRun{}; run[as[i]].req = ai[i]; voc_frames[as[i]] = 0; }
                 }
             }
         }
@@ -1128,40 +1182,21 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
         dec_ms += ms; steps += CH;
         if (admitted) { hipEventElapsedTime(&ms, e->ev0, e->ev2); pre_ms += ms; }
         for (int b = 0; b < B; ++b) if (run[b].req >= 0) { ctx_tokens += (long long)e->slots_host[b].cur_pos * CH; live_slot_steps += CH; }
-        // H8: the vocoder consumes 4-frame chunks (src/tts/engine.rs:507-541). It runs on its own stream behind an
-        // event, batched over every slot that has a chunk ready, so chunk k's PCM overlaps the decoding of chunk k+1.
         if (e->voc) {
             const double tv0 = now_ms();
             hipStream_t vs = e->vstream;
-            bool waited = false, first = false;
-            auto ensure_wait = [&]() -> int { if (!waited) { Q3_HIP(e, hipStreamWaitEvent(vs, e->ev3, 0)); waited = true; } return Q3TTS_OK; };
-            // ONE batched call per chunk: every slot with new frames runs nf = 4. A finished utterance whose tail is
-            // shorter is padded with throw-away frames: the vocoder is causal, so they cannot change the samples already
-            // due, their own samples are never reported, and the slot's vocoder state is reset at its next admission.
-            int list[64], real[64];
-            for (;;) {
-                int ns = 0;
-                for (int b = 0; b < B; ++b) {
-                    if (run[b].req < 0 || !reqs[run[b].req].want_pcm) continue;
-                    const int pend = e->slots_host[b].n_frames - run[b].voc_frames;
-                    if (pend >= 4 || (pend > 0 && !e->slots_host[b].active)) { real[ns] = std::min(pend, 4); list[ns++] = b; }
-                }
-                if (!ns) break;
-                TRY(ensure_wait());
-                int still = 0;  // slots that go on decoding while this call runs
-                for (int b = 0; b < B; ++b) if (run[b].req >= 0 && e->slots_host[b].active) ++still;
-                TRY(q3_voc_decode_batch(e, list, real, ns, 4, vs, (still > 0 || next < n) ? 1 : 0));
-                for (int i = 0; i < ns; ++i) { if (run[list[i]].voc_frames == 0) first = true; run[list[i]].voc_frames += real[i]; }
-            }
+            for (int b = 0; b < B; ++b) { live[b] = run[b].req >= 0; want[b] = live[b] && reqs[run[b].req].want_pcm; }
+            bool first = false;
+            TRY(q3_voc_dispatch(e, live.data(), want.data(), voc_frames.data(), next < n, &first));
             if (first) {  // first-chunk latency: the first chunk's PCM resident on the host
                 for (int b = 0; b < B; ++b)
-                    if (run[b].req >= 0 && run[b].t_first == 0 && run[b].voc_frames > 0) {
-                        const int nsmp = std::min(run[b].voc_frames, 4) * spf;
+                    if (run[b].req >= 0 && run[b].t_first == 0 && voc_frames[b] > 0) {
+                        const int nsmp = std::min(voc_frames[b], 4) * spf;
                         Q3_HIP(e, hipMemcpyAsync(e->first_chunk_host, q3_voc_pcm(e, b), sizeof(float) * (size_t)nsmp, hipMemcpyDeviceToHost, vs));
                     }
                 Q3_HIP(e, hipStreamSynchronize(vs));
                 const double tn = now_ms();
-                for (int b = 0; b < B; ++b) if (run[b].req >= 0 && run[b].t_first == 0 && run[b].voc_frames > 0) run[b].t_first = tn;
+                for (int b = 0; b < B; ++b) if (run[b].req >= 0 && run[b].t_first == 0 && voc_frames[b] > 0) run[b].t_first = tn;
             }
             voc_ms += now_ms() - tv0;
         }
@@ -1171,9 +1206,7 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
             if (pending[j] >= 0 && hipEventQuery(e->fin_ev[j]) == hipSuccess) TRY(drain(j));
         for (int b = 0; b < B; ++b) {
             if (run[b].req < 0 || e->slots_host[b].active) continue;
-            // V4 flush: the reference sends is_last only when its final buffer is not empty, i.e. n_frames % 4 != 0 (src/tts/engine.rs:510-536,
-            // restated by q3o_chunk_plan); with lookahead_frames > 0 an utterance of n_frames % 4 == 0 keeps its withheld tail (vocoder_flush_tail = 1: always flush)
-            if (e->voc && (e->cfg.vocoder_flush_tail || e->slots_host[b].n_frames % 4 != 0)) q3_voc_mark_last(e, b);
+            // (the V4 flush rule was applied by q3_voc_dispatch)
             // hand the slot's results over without waiting for the vocoder (completed at slot reuse / at the end)
             for (int j = 0; j < B; ++j)
                 if (pending[j] >= 0 && hipEventQuery(e->fin_ev[j]) == hipSuccess) TRY(drain(j));
@@ -1212,6 +1245,12 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
     return Q3TTS_OK;
 }
 
+// the scheduler steps as the session worker drives them (q3_session.hip)
+int q3_plan_rows(q3tts_engine* e, const std::vector<int>& live) { return plan_rows(e, live); }
+int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc) { return admit_many(e, slots, reqs, count, rc); }
+int q3_run_chunk(q3tts_engine* e, int CH) { return run_chunk(e, CH, nullptr); }
+double q3_now_ms() { return now_ms(); }
+
 extern "C" int q3tts_generate(q3tts_engine* e, const q3tts_request* req, q3tts_result* out) {
     int rc = q3tts_generate_batch(e, req, 1, out);
     if (rc != Q3TTS_OK) return rc;
@@ -1241,6 +1280,7 @@ struct q3tts_stream {
 
 extern "C" int q3tts_stream_begin(q3tts_engine* e, const q3tts_request* req, q3tts_stream** out) {
     if (!e || !req || !out) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
+    Q3_NOT_IN_SESSION(e);
     if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "streaming needs with_vocoder = 1");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     q3tts_stream* st = new q3tts_stream();
@@ -1757,6 +1797,7 @@ extern "C" int q3tts_k_mfma_bf16(int32_t device, const uint16_t* a, const uint16
 }
 
 extern "C" int q3tts_k_talker_prefill(q3tts_engine* e, const float* embd, int32_t n_tok, float* hidden_out, float* logits_out) {
+    Q3_NOT_IN_SESSION(e);
     if (!e || !embd || n_tok <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     q3tts_request r{}; r.prompt_embd = embd; r.n_tok = n_tok; r.use_engine_sampler = 0; r.temperature = 0; r.max_steps = 1;
@@ -1776,6 +1817,7 @@ extern "C" int q3tts_k_talker_prefill(q3tts_engine* e, const float* embd, int32_
 }
 
 extern "C" int q3tts_k_probe(q3tts_engine* e, int32_t enable) {
+    Q3_NOT_IN_SESSION(e);
     if (!e) return Q3TTS_ERR_INVALID;
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     if (enable && e->probe_ev.empty()) {
@@ -1793,6 +1835,7 @@ extern "C" int q3tts_k_probe(q3tts_engine* e, int32_t enable) {
 // site would use), and counts the bytes that do not read back as written / as zero. An asynchronous fill on e->stream — the state
 // of rounds 1 and 2 — loses this race on large buffers.
 extern "C" int q3tts_k_alloc_upload(q3tts_engine* e, int64_t bytes, int64_t* mismatches) {
+    Q3_NOT_IN_SESSION(e);
     if (!e || !mismatches || bytes < 16384) return q3_set_err(e, Q3TTS_ERR_INVALID, "alloc hook: bytes >= 16384");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     void* q = nullptr;
@@ -1833,6 +1876,33 @@ extern "C" int q3tts_k_bgemm_pick(int32_t B, int32_t K, int32_t N, int32_t epilo
     int rt, nt, d, ntw, big;
     q3_bgemm_pick(g, &rt, &nt, &d, &ntw, &big);
     out5[0] = rt; out5[1] = nt; out5[2] = d; out5[3] = ntw; out5[4] = big;
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_pcm_pack(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* ent_row, const int32_t* ent_first,
+                                const int32_t* ent_count, const int64_t* ent_dst, int32_t n_ent, int32_t format, void* out, int64_t out_n) {
+    if (!src || !out || rows <= 0 || stride <= 0 || stride > (1 << 28) || n_ent < 0 || n_ent > Q3_PCM_MAX_ENT || (format != 0 && format != 1) || out_n < 0 ||
+        (n_ent > 0 && (!ent_row || !ent_first || !ent_count || !ent_dst)))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm pack hook: bad arguments");
+    Q3PcmPack pk{};
+    int mx = 0;
+    for (int j = 0; j < n_ent; ++j) {
+        const long long r = ent_row[j], f = ent_first[j], c = ent_count[j], d = ent_dst[j];
+        if (r < 0 || r >= rows || f < 0 || c < 0 || f + c > stride || d < 0 || d + c > out_n)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm pack hook: a window lies outside src or out");
+        pk.e[j] = Q3PcmEnt{(int32_t)r, (int32_t)f, (int32_t)c, 0, d};
+        mx = std::max(mx, (int)c);
+    }
+    const size_t es = format ? 2 : 4;
+    HK(hipSetDevice(device));
+    DevBuf s, o;
+    if (s.alloc(sizeof(float) * (size_t)rows * stride) || o.alloc(es * (size_t)std::max<int64_t>(out_n, 1))) return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
+    HK(hipMemcpy(s.p, src, sizeof(float) * (size_t)rows * stride, hipMemcpyHostToDevice));
+    if (out_n > 0) HK(hipMemcpy(o.p, out, es * (size_t)out_n, hipMemcpyHostToDevice));  // samples outside every window keep their values
+    q3_launch_pcm_pack((const float*)s.p, (size_t)stride, pk, n_ent, mx, format, o.p, nullptr);
+    HK(hipGetLastError());
+    HK(hipDeviceSynchronize());
+    if (out_n > 0) HK(hipMemcpy(out, o.p, es * (size_t)out_n, hipMemcpyDeviceToHost));
     return Q3TTS_OK;
 }
 

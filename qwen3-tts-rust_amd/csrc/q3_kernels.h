@@ -280,3 +280,12 @@ void q3_launch_copy_rows(float* dst, int ldd, const float* src, int lds, int row
 // canonical RMSNorm of rows (test hook / hidden read-back)
 void q3_launch_gather_rows(float* dst, const float* src, const int* perm, int rows, int cols, hipStream_t s);
 void q3_launch_rmsnorm_rows(const float* x, int ldx, const float* w, float eps, int d, int rows, float* out, int ldo, hipStream_t s);
+
+// PCM gather: windows of f32 sample rows -> one contiguous f32 or i16 buffer. Entry j copies src[row][first, first + count) to
+// dst[dst_off, dst_off + count); i16 follows the reference's WAV rule (src/utils/audio.rs:35-37): (x * 32767).clamp(-32768, 32767) as i16,
+// truncation toward zero. Up to Q3_PCM_MAX_ENT entries per launch (passed by value); the caller guarantees the windows lie inside
+// src and dst. i16 = 0: f32 out, 1: i16 out.
+#define Q3_PCM_MAX_ENT 64
+struct Q3PcmEnt { int32_t row, first, count, pad; long long dst_off; };
+struct Q3PcmPack { Q3PcmEnt e[Q3_PCM_MAX_ENT]; };
+void q3_launch_pcm_pack(const float* src, size_t stride, const Q3PcmPack& ents, int n_ent, int max_count, int i16, void* dst, hipStream_t s);

@@ -1531,3 +1531,38 @@ void q3_launch_rmsnorm_rows(const float* x, int ldx, const float* w, float eps, 
     else if (d == 512) hipLaunchKernelGGL((k_rmsnorm_rows<2>), grid, dim3(256), 0, s, x, ldx, w, eps, d, rows, out, ldo);
     else hipLaunchKernelGGL((k_rmsnorm_rows<0>), grid, dim3(256), 0, s, x, ldx, w, eps, d, rows, out, ldo);
 }
+
+// ---- PCM gather (sessions, the node's i16 gather) -----------------------------------------------------------------------------
+__device__ __forceinline__ void pcm_put(float* d, float v) { *d = v; }
+__device__ __forceinline__ void pcm_put(int16_t* d, float v) {
+    v = v * 32767.0f;
+    v = fminf(fmaxf(v, -32768.0f), 32767.0f);
+    *d = (int16_t)(int)truncf(v);
+}
+// grid (x, n_ent): blockIdx.y = entry. The window's head up to the first 16-byte boundary of the source row is copied element-wise,
+// the body with one float4 load per thread and iteration, the tail element-wise.
+template <typename T>
+__global__ __launch_bounds__(256) void k_pcm_pack(const float* __restrict__ src, size_t stride, const Q3PcmPack ents, T* __restrict__ dst) {
+    const Q3PcmEnt en = ents.e[blockIdx.y];
+    const int n = en.count;
+    if (n <= 0) return;
+    const float* s = src + (size_t)en.row * stride + en.first;
+    T* d = dst + en.dst_off;
+    const int head = min(n, (int)((4 - (((uintptr_t)s >> 2) & 3)) & 3));
+    const int nv = (n - head) >> 2;
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
+    if (tid < head) pcm_put(d + tid, s[tid]);
+    const float4* sv = (const float4*)(s + head);
+    for (int i = tid; i < nv; i += nth) {
+        const float4 v = sv[i];
+        T* o = d + head + 4 * i;
+        pcm_put(o, v.x); pcm_put(o + 1, v.y); pcm_put(o + 2, v.z); pcm_put(o + 3, v.w);
+    }
+    for (int i = head + 4 * nv + tid; i < n; i += nth) pcm_put(d + i, s[i]);
+}
+void q3_launch_pcm_pack(const float* src, size_t stride, const Q3PcmPack& ents, int n_ent, int max_count, int i16, void* dst, hipStream_t s) {
+    if (n_ent <= 0) return;
+    const int gx = std::max(1, std::min(64, (max_count / 4 + 255) / 256));
+    if (i16) hipLaunchKernelGGL(k_pcm_pack<int16_t>, dim3(gx, n_ent), dim3(256), 0, s, src, stride, ents, (int16_t*)dst);
+    else hipLaunchKernelGGL(k_pcm_pack<float>, dim3(gx, n_ent), dim3(256), 0, s, src, stride, ents, (float*)dst);
+}

@@ -141,6 +141,7 @@ int q3_mel_run(q3tts_engine* e, const float* audio, int64_t n_samples, int32_t* 
 }
 
 extern "C" int q3tts_mel(q3tts_engine* e, const float* audio, int64_t n_samples, float* out, int32_t cap_frames, int32_t* n_frames) {
+    Q3_NOT_IN_SESSION(e);
     if (!e || !out || !n_frames || n_samples < 0 || (n_samples > 0 && !audio)) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     int32_t nf = q3tts_mel_frames(n_samples);

@@ -43,19 +43,6 @@ struct Rccl {
 };
 static Rccl g_rccl;
 
-// f32 -> i16 exactly as the reference writes WAV samples (src/utils/audio.rs:35-37): (x * 32767).clamp(-32768, 32767) as i16 — `as`
-// truncates toward zero. Rows of the engine's packed device PCM -> one contiguous i16 buffer (utterance j at off[j]).
-__global__ __launch_bounds__(256) void k_pcm_pack_i16(const float* src, size_t stride, const int* n_samples, const long long* off, int16_t* dst) {
-    const int j = blockIdx.y, n = n_samples[j];
-    const float* s = src + (size_t)j * stride;
-    int16_t* d = dst + off[j];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        float v = s[i] * 32767.0f;
-        v = fminf(fmaxf(v, -32768.0f), 32767.0f);
-        d[i] = (int16_t)(int)truncf(v);
-    }
-}
-
 struct NodeDev {
     int device = 0;
     q3tts_engine* eng = nullptr;
@@ -66,7 +53,7 @@ struct NodeDev {
     std::vector<q3tts_result> outs;
     int rc = 0; std::string err;
     int16_t* pack = nullptr; size_t pack_cap = 0;   // this device's utterances as i16, back to back
-    int* lens_dev = nullptr; long long* off_dev = nullptr; int* all_lens_dev = nullptr; int lens_cap = 0;
+    int* lens_dev = nullptr; int* all_lens_dev = nullptr; int lens_cap = 0;
     double gen_ms = 0;
 };
 
@@ -97,7 +84,7 @@ extern "C" void q3tts_node_destroy(q3tts_node* n) {
         if (d.comm && g_rccl.CommDestroy) g_rccl.CommDestroy(d.comm);
         if (d.eng) q3tts_engine_destroy(d.eng);
         hipSetDevice(d.device);
-        hipFree(d.pack); hipFree(d.lens_dev); hipFree(d.off_dev); hipFree(d.all_lens_dev);
+        hipFree(d.pack); hipFree(d.lens_dev); hipFree(d.all_lens_dev);
         if (d.stream) hipStreamDestroy(d.stream);
     }
     if (!n->dev.empty()) hipSetDevice(n->dev[0].device);
@@ -181,20 +168,25 @@ static int node_gather(q3tts_node* n, q3tts_result* outs, int16_t** pcm_i16) {
         for (int j = 0; j < cnt; ++j) { lens[j] = (d.reqs[j].want_pcm && d.outs[j].status == Q3TTS_OK) ? d.outs[j].n_samples : 0; off[j] = (long long)tot; tot += (size_t)lens[j]; }
         pack_samples[r] = tot;
         if (d.lens_cap < maxn) {
-            hipFree(d.lens_dev); hipFree(d.off_dev); hipFree(d.all_lens_dev); d.lens_dev = nullptr; d.off_dev = nullptr; d.all_lens_dev = nullptr; d.lens_cap = 0;
-            NHIP(n, hipMalloc((void**)&d.lens_dev, sizeof(int) * maxn)); NHIP(n, hipMalloc((void**)&d.off_dev, sizeof(long long) * maxn));
+            hipFree(d.lens_dev); hipFree(d.all_lens_dev); d.lens_dev = nullptr; d.all_lens_dev = nullptr; d.lens_cap = 0;
+            NHIP(n, hipMalloc((void**)&d.lens_dev, sizeof(int) * maxn));
             NHIP(n, hipMalloc((void**)&d.all_lens_dev, sizeof(int) * (size_t)maxn * G));
             d.lens_cap = maxn;
         }
         if (d.pack_cap < tot + 1) { hipFree(d.pack); d.pack = nullptr; d.pack_cap = 0; NHIP(n, hipMalloc((void**)&d.pack, sizeof(int16_t) * (tot + 1))); d.pack_cap = tot + 1; }
         NHIP(n, hipMemcpyAsync(d.lens_dev, lens.data(), sizeof(int) * maxn, hipMemcpyHostToDevice, d.stream));
-        NHIP(n, hipMemcpyAsync(d.off_dev, off.data(), sizeof(long long) * maxn, hipMemcpyHostToDevice, d.stream));
-        NHIP(n, hipStreamSynchronize(d.stream));  // (lens / off are locals)
+        NHIP(n, hipStreamSynchronize(d.stream));  // (lens is a local)
         float* base = nullptr; int64_t stride = 0; int32_t rows = 0;
         if (cnt > 0 && tot > 0) {
             if (q3tts_get_device_pcm(d.eng, &base, &stride, &rows) != Q3TTS_OK || !base || rows < cnt) return node_err(n, Q3TTS_ERR_STATE, "node: the engine kept no device PCM");
-            hipLaunchKernelGGL(k_pcm_pack_i16, dim3(64, cnt), dim3(256), 0, d.stream, (const float*)base, (size_t)stride, (const int*)d.lens_dev, (const long long*)d.off_dev, d.pack);
-            NHIP(n, hipGetLastError());
+            // f32 -> i16 exactly as the reference writes WAV samples (src/utils/audio.rs:35-37): row j of the engine's packed device PCM
+            // -> utterance j at off[j] of one contiguous i16 buffer, in launches of up to Q3_PCM_MAX_ENT rows
+            for (int j0 = 0; j0 < cnt; j0 += Q3_PCM_MAX_ENT) {
+                Q3PcmPack pk{}; int ne = 0, mx = 0;
+                for (int j = j0; j < cnt && ne < Q3_PCM_MAX_ENT; ++j, ++ne) { pk.e[ne] = Q3PcmEnt{j, 0, lens[j], 0, off[j]}; mx = std::max(mx, lens[j]); }
+                q3_launch_pcm_pack(base, (size_t)stride, pk, ne, mx, 1, d.pack, d.stream);
+                NHIP(n, hipGetLastError());
+            }
         }
     }
     NcclGroup grp;

@@ -1,0 +1,498 @@
+// q3_session.hip — sessions (include/q3tts.h): continuous batching with per-request streaming, the serving form of
+// run_inference_stream (src/tts/engine.rs:445-656) for many utterances at once. One worker thread per session drives the engine's slots
+// between 4-frame chunks: cancellations, admissions (plan_rows + admit_many), the frame steps (run_chunk), the batched vocoder
+// (q3_voc_dispatch, shared with q3tts_generate_batch), then ONE PCM gather launch and ONE device-to-host copy of every slot's new
+// samples into a ring of pinned staging buffers. Chunk events are published when that copy's event has fired (queried, never waited
+// for while slots are decoding), so decode keeps overlapping the vocoder as in q3tts_generate_batch. DESIGN.md §"Streams".
+#include "q3_engine.h"
+
+#include <chrono>
+#include <condition_variable>
+#include <cstring>
+#include <deque>
+#include <map>
+#include <memory>
+#include <thread>
+
+namespace {
+
+#define TRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
+
+constexpr int kRing = Q3TTS_SESSION_RING_DEPTH;
+constexpr int kStopping = 1;  // (positive: the worker was told to stop while it waited for staging)
+
+// a submitted request with everything it points to copied
+struct SReq {
+    uint64_t id = 0;
+    q3tts_request r{};
+    q3tts_prompt_desc desc{};
+    std::vector<float> embd, spk;
+    std::vector<uint32_t> text, instr, ref_text;
+    std::vector<int32_t> ref_codes;
+};
+
+struct SEv {  // an event on its way to the consumer
+    uint64_t id = 0;
+    int kind = Q3TTS_EV_NONE, status = Q3TTS_OK, ring = -1, n = 0, is_final = 0;
+    size_t off = 0;      // CHUNK: first sample in the ring buffer
+    q3tts_result res{};  // final events
+};
+
+struct Batch {  // the events of one chunk boundary, published together once the copy into ring buffer `ring` has landed (-1: no copy)
+    int ring = -1;
+    std::vector<SEv> evs;
+};
+
+struct IdState {
+    bool cancelled = false, queued = true, final_ready = false;
+    double t_submit = 0, t_first = 0;
+};
+
+struct SSlot {
+    std::unique_ptr<SReq> req;  // null: the slot is free
+    int delivered = 0;          // samples handed out in chunks so far
+};
+
+}  // namespace
+
+struct q3tts_session {
+    q3tts_engine* e = nullptr;
+    int fmt = 0; size_t es = 4;
+    size_t ring_cap = 0;            // samples per staging buffer: max_batch x (4 + lookahead_frames) x samples per frame
+    void* host[kRing] = {};         // pinned staging ring
+    hipEvent_t ev[kRing] = {};      // its copies
+    int refs[kRing] = {};           // (mu) chunks of a buffer in the ready queue or held by the consumer
+    bool inflight[kRing] = {};      // (worker) its copy is not published yet
+    int ring_next = 0;
+    void* dev = nullptr;            // the gather's device output (one copy in flight at a time: stream order on the vocoder stream)
+    std::mutex mu;                  // guards everything below up to `slots`
+    std::condition_variable cv_work, cv_ev, cv_space;
+    std::deque<std::unique_ptr<SReq>> pending;
+    std::vector<uint64_t> cancels;
+    std::map<uint64_t, IdState> ids;  // accepted ids whose final event has not been delivered
+    std::deque<SEv> ready;
+    uint64_t next_id = 1;
+    bool stop = false, dead = false;
+    int held_ring = -1;             // ring buffer of the chunk the consumer holds (released at its next call)
+    int worker_rc = Q3TTS_OK;
+    std::string err;
+    // worker only
+    std::vector<SSlot> slots;
+    std::vector<int> voc_frames;
+    std::deque<Batch> flight;
+    std::thread th;
+};
+
+namespace {
+
+thread_local std::string g_serr;
+
+int serr(q3tts_session* s, int code, const std::string& m) {
+    if (s) s->err = m;
+    g_serr = m;
+    return code;
+}
+
+void copy_result_free(q3tts_result& r) { q3tts_result_free(&r); r = q3tts_result{}; }
+
+// (mu held) an event reaches the ready queue; a cancelled id's chunks are dropped and its DONE / FAILED become CANCELLED
+void deliver(q3tts_session* s, SEv& v, double t) {
+    auto it = s->ids.find(v.id);
+    if (it == s->ids.end() || it->second.final_ready) { copy_result_free(v.res); return; }
+    IdState& st = it->second;
+    if (st.cancelled) {
+        if (v.kind == Q3TTS_EV_CHUNK) return;
+        if (v.kind != Q3TTS_EV_CANCELLED) { copy_result_free(v.res); v.kind = Q3TTS_EV_CANCELLED; v.status = Q3TTS_OK; }
+    }
+    if (v.kind == Q3TTS_EV_CHUNK) {
+        if (v.ring >= 0) ++s->refs[v.ring];
+        if (st.t_first == 0) st.t_first = t;
+    } else {
+        v.is_final = 1;
+        v.res.first_chunk_ms = st.t_first > 0 ? (float)(st.t_first - st.t_submit) : 0.0f;
+        v.res.total_ms = (float)(t - st.t_submit);
+        st.final_ready = true;
+    }
+    s->ready.push_back(v);
+}
+
+SEv final_ev(uint64_t id, int kind, int status) {
+    SEv v; v.id = id; v.kind = kind; v.status = status; v.is_final = 1; v.res.status = status;
+    return v;
+}
+
+// publish finished batches in order; wait: block on the first one's copy
+int publish(q3tts_session* s, bool wait) {
+    q3tts_engine* e = s->e;
+    while (!s->flight.empty()) {
+        Batch& b = s->flight.front();
+        if (b.ring >= 0) {
+            const hipError_t q = wait ? hipEventSynchronize(s->ev[b.ring]) : hipEventQuery(s->ev[b.ring]);
+            if (q == hipErrorNotReady) break;
+            if (q != hipSuccess) return q3_set_err(e, Q3TTS_ERR_DEVICE, std::string("session: PCM copy: ") + hipGetErrorString(q));
+            s->inflight[b.ring] = false;
+        }
+        wait = false;
+        const double t = q3_now_ms();
+        {
+            std::lock_guard<std::mutex> lk(s->mu);
+            for (SEv& v : b.evs) deliver(s, v, t);
+        }
+        s->cv_ev.notify_all();
+        s->flight.pop_front();
+    }
+    return Q3TTS_OK;
+}
+
+// ring buffer k free: its copy published and every chunk in it released by the consumer (the worker waits: memory does not grow)
+int take_ring(q3tts_session* s, int k) {
+    while (s->inflight[k]) { const int rc = publish(s, true); if (rc) return rc; }
+    std::unique_lock<std::mutex> lk(s->mu);
+    s->cv_space.wait(lk, [&] { return s->stop || s->refs[k] == 0; });
+    return s->stop ? kStopping : Q3TTS_OK;
+}
+
+// upload a free state (active = 0) for slot b from the pinned staging half admissions use; its vocoder work so far precedes fin_ev[b]
+int retire_slot(q3tts_session* s, int b) {
+    q3tts_engine* e = s->e;
+    Q3Slot* st = e->slots_host + e->B + b;
+    memset(st, 0, sizeof(*st));
+    Q3_HIP(e, hipMemcpyAsync(e->slots + b, st, sizeof(Q3Slot), hipMemcpyHostToDevice, e->stream));
+    Q3_HIP(e, hipEventRecord(e->fin_ev[b], e->vstream));
+    s->slots[b].req.reset();
+    return Q3TTS_OK;
+}
+
+// one chunk boundary
+int step(q3tts_session* s) {
+    q3tts_engine* e = s->e;
+    const int B = e->B;
+    hipStream_t vs = e->vstream;
+    std::vector<uint64_t> cancels;
+    std::vector<std::unique_ptr<SReq>> adm;
+    int nfree = 0;
+    for (int b = 0; b < B; ++b) if (!s->slots[b].req) ++nfree;
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        cancels.swap(s->cancels);
+        while (nfree-- > 0 && !s->pending.empty()) {
+            s->ids[s->pending.front()->id].queued = false;
+            adm.push_back(std::move(s->pending.front()));
+            s->pending.pop_front();
+        }
+    }
+    Batch bt;
+    // 1. cancellations: the slot is retired now and admitted into again from the next boundary on
+    std::vector<char> cool(B, 0);
+    bool retired = false;
+    for (uint64_t id : cancels)
+        for (int b = 0; b < B; ++b)
+            if (s->slots[b].req && s->slots[b].req->id == id) {
+                TRY(retire_slot(s, b));
+                cool[b] = 1; retired = true;
+                bt.evs.push_back(final_ev(id, Q3TTS_EV_CANCELLED, Q3TTS_OK));
+            }
+    // 2. admissions into free slots
+    std::vector<int> as;
+    std::vector<const q3tts_request*> ar;
+    for (int b = 0; b < B && as.size() < adm.size(); ++b)
+        if (!s->slots[b].req && !cool[b]) { as.push_back(b); ar.push_back(&adm[as.size() - 1]->r); }
+    for (int b : as) Q3_HIP(e, hipEventSynchronize(e->fin_ev[b]));  // the previous occupant's vocoder work is done before the slot's reset
+    std::vector<int> live(as);
+    for (int b = 0; b < B; ++b) if (s->slots[b].req) live.push_back(b);
+    if (!live.empty()) TRY(q3_plan_rows(e, live));
+    if (!as.empty()) {
+        std::vector<int> rcs(as.size());
+        TRY(q3_admit_many(e, as.data(), ar.data(), (int)as.size(), rcs.data()));
+        bool failed = false;
+        for (int rc : rcs) failed |= rc != Q3TTS_OK;
+        if (failed) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (a refused request's uploads may still read its copy, freed below)
+        for (size_t i = 0; i < as.size(); ++i) {
+            if (rcs[i] != Q3TTS_OK) { bt.evs.push_back(final_ev(adm[i]->id, Q3TTS_EV_FAILED, rcs[i])); continue; }
+            SSlot& sl = s->slots[as[i]];
+            sl.req = std::move(adm[i]); sl.delivered = 0; s->voc_frames[as[i]] = 0;
+        }
+    }
+    std::vector<char> run(B, 0);
+    bool any = false;
+    for (int b = 0; b < B; ++b) if (s->slots[b].req) { run[b] = 1; any = true; }
+    if (!any) {
+        if (retired) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (the staging half is rewritten by the next admission)
+        if (!bt.evs.empty()) s->flight.push_back(std::move(bt));
+        return Q3TTS_OK;
+    }
+    // 3. four frame steps, 4. the vocoder
+    TRY(q3_run_chunk(e, 4));
+    bool more, first = false;
+    { std::lock_guard<std::mutex> lk(s->mu); more = !s->pending.empty(); }
+    TRY(q3_voc_dispatch(e, run.data(), run.data(), s->voc_frames.data(), more, &first));
+    // 5. every slot's new window [delivered, samples) in one gather launch and one copy
+    Q3PcmPack pk{};
+    int ne = 0, mx = 0;
+    size_t tot = 0;
+    std::vector<SEv> chunks;
+    std::vector<int> fin;
+    for (int b = 0; b < B; ++b) {
+        if (!run[b]) continue;
+        SSlot& sl = s->slots[b];
+        const int ns = q3_voc_samples(e, b), c = ns - sl.delivered;
+        const bool done = !e->slots_host[b].active;
+        if (c < 0 || tot + (size_t)std::max(c, 0) > s->ring_cap || ns > (int)q3_voc_pcm_stride(e))
+            return q3_set_err(e, Q3TTS_ERR_STATE, "session: a chunk window exceeds the staging bound");
+        if (c > 0 || done) {
+            SEv v; v.id = sl.req->id; v.kind = Q3TTS_EV_CHUNK; v.n = c; v.is_final = done ? 1 : 0; v.off = tot;
+            chunks.push_back(v);
+        }
+        if (c > 0) {
+            pk.e[ne++] = Q3PcmEnt{b, sl.delivered, c, 0, (long long)tot};
+            mx = std::max(mx, c);
+            tot += (size_t)c; sl.delivered = ns;
+        }
+        if (done) fin.push_back(b);
+    }
+    if (ne > 0) {
+        const int k = s->ring_next;
+        const int rc = take_ring(s, k);
+        if (rc) return rc;
+        q3_launch_pcm_pack(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, ne, mx, s->fmt, s->dev, vs);
+        Q3_HIP(e, hipGetLastError());
+        Q3_HIP(e, hipMemcpyAsync(s->host[k], s->dev, tot * s->es, hipMemcpyDeviceToHost, vs));
+        Q3_HIP(e, hipEventRecord(s->ev[k], vs));
+        s->inflight[k] = true;
+        s->ring_next = (k + 1) % kRing;
+        bt.ring = k;
+        for (SEv& v : chunks) if (v.n > 0) v.ring = k;
+    }
+    for (SEv& v : chunks) bt.evs.push_back(v);
+    // finished utterances: codes back on the decoder stream, the slot free from the next boundary on
+    const int ncb = e->cfg.model.n_codebooks;
+    for (int b : fin) {
+        const Q3Slot& st = e->slots_host[b];
+        SEv v = final_ev(s->slots[b].req->id, Q3TTS_EV_DONE, Q3TTS_OK);
+        q3tts_result& o = v.res;
+        o.n_frames = st.n_frames; o.hit_eos = st.hit_eos; o.n_samples = s->slots[b].delivered; o.sample_rate = e->cfg.vocoder.sample_rate;
+        o.codes = (int32_t*)malloc(sizeof(int32_t) * (size_t)std::max(1, st.n_frames * ncb));
+        if (!o.codes) return q3_set_err(e, Q3TTS_ERR_OOM, "malloc");
+        if (st.n_frames > 0)
+            Q3_HIP(e, hipMemcpyAsync(o.codes, e->codes + (size_t)b * e->cfg.max_steps_cap * ncb, sizeof(int32_t) * (size_t)st.n_frames * ncb,
+                                     hipMemcpyDeviceToHost, e->stream));
+        Q3_HIP(e, hipEventRecord(e->fin_ev[b], vs));  // (behind the gather that read the slot's PCM)
+        s->slots[b].req.reset();
+        bt.evs.push_back(v);
+    }
+    if (!fin.empty()) Q3_HIP(e, hipStreamSynchronize(e->stream));
+    s->flight.push_back(std::move(bt));
+    return Q3TTS_OK;
+}
+
+// the worker failed: every open request gets FAILED with the status; the session refuses new submissions
+void fail_all(q3tts_session* s, int rc) {
+    std::string m;
+    { std::lock_guard<std::mutex> lk(s->e->err_mu); m = s->e->err; }
+    std::lock_guard<std::mutex> lk(s->mu);
+    s->dead = true; s->worker_rc = rc; s->err = "session worker: " + m;
+    for (Batch& b : s->flight) for (SEv& v : b.evs) copy_result_free(v.res);
+    s->flight.clear();
+    s->pending.clear();
+    const double t = q3_now_ms();
+    for (auto& kv : s->ids)
+        if (!kv.second.final_ready) {
+            SEv v = final_ev(kv.first, Q3TTS_EV_FAILED, rc);
+            deliver(s, v, t);
+        }
+    s->cv_ev.notify_all();
+}
+
+void worker(q3tts_session* s) {
+    q3tts_engine* e = s->e;
+    int rc = hipSetDevice(e->cfg.device) == hipSuccess ? Q3TTS_OK : q3_set_err(e, Q3TTS_ERR_DEVICE, "session: hipSetDevice");
+    while (rc == Q3TTS_OK) {
+        bool running = false;
+        for (const SSlot& sl : s->slots) if (sl.req) running = true;
+        bool work;
+        {
+            std::unique_lock<std::mutex> lk(s->mu);
+            if (!running && s->flight.empty())  // idle: sleep until a submission, a cancel or close
+                s->cv_work.wait(lk, [&] { return s->stop || !s->pending.empty() || !s->cancels.empty(); });
+            if (s->stop) break;
+            work = !s->pending.empty() || !s->cancels.empty();
+        }
+        if (!running && !work) { rc = publish(s, true); continue; }  // only copies in flight: wait for the oldest
+        rc = step(s);
+        if (rc == Q3TTS_OK) rc = publish(s, false);
+    }
+    if (rc == kStopping) rc = Q3TTS_OK;
+    if (rc != Q3TTS_OK) fail_all(s, rc);
+    // close (or failure): retire the slots still decoding, so the engine is usable as before
+    for (int b = 0; b < e->B; ++b) if (s->slots[b].req) retire_slot(s, b);
+    hipStreamSynchronize(e->stream);
+    hipStreamSynchronize(e->vstream);
+}
+
+int copy_request(q3tts_engine* e, const q3tts_request* req, SReq* q) {
+    const q3tts_model_config& m = e->cfg.model;
+    q->r = *req;
+    q->r.want_pcm = 1;
+    q->r.prompt_embd = nullptr; q->r.prompt = nullptr;
+    if (req->prompt_embd) {
+        if (req->n_tok <= 0 || req->n_tok > e->cfg.n_ctx) return Q3TTS_ERR_INVALID;
+        q->embd.assign(req->prompt_embd, req->prompt_embd + (size_t)req->n_tok * m.d_embed);
+        q->r.prompt_embd = q->embd.data();
+    } else if (req->prompt) {
+        const q3tts_prompt_desc& p = *req->prompt;
+        auto bad = [](const void* ptr, int32_t n) { return n < 0 || (n > 0 && !ptr); };
+        if (bad(p.text_ids, p.n_text) || bad(p.instruct_ids, p.n_instruct) || bad(p.ref_codes, p.n_ref_frames) || bad(p.ref_text_ids, p.n_ref_text))
+            return Q3TTS_ERR_INVALID;
+        q->desc = p;
+        q->text.assign(p.text_ids, p.text_ids + p.n_text);
+        q->desc.text_ids = q->text.data();
+        if (p.instruct_ids) { q->instr.assign(p.instruct_ids, p.instruct_ids + p.n_instruct); q->instr.push_back(0); q->desc.instruct_ids = q->instr.data(); }
+        if (p.spk_emb) { q->spk.assign(p.spk_emb, p.spk_emb + m.d_embed); q->desc.spk_emb = q->spk.data(); }
+        if (p.ref_codes) {
+            q->ref_codes.assign(p.ref_codes, p.ref_codes + (size_t)p.n_ref_frames * 16); q->ref_codes.push_back(0); q->desc.ref_codes = q->ref_codes.data();
+            q->ref_text.assign(p.ref_text_ids ? p.ref_text_ids : nullptr, p.ref_text_ids ? p.ref_text_ids + p.n_ref_text : nullptr);
+            q->ref_text.push_back(0);
+            q->desc.ref_text_ids = q->ref_text.data();
+        } else {
+            q->desc.ref_text_ids = nullptr; q->desc.n_ref_text = 0;
+        }
+        q->r.prompt = &q->desc;
+    }
+    return Q3TTS_OK;
+}
+
+}  // namespace
+
+extern "C" int q3tts_session_create(q3tts_engine* e, int32_t pcm_format, q3tts_session** out) {
+    if (!e || !out) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
+    if (pcm_format != Q3TTS_PCM_F32 && pcm_format != Q3TTS_PCM_I16) return q3_set_err(e, Q3TTS_ERR_INVALID, "pcm_format must be 0 (f32) or 1 (i16)");
+    Q3_NOT_IN_SESSION(e);
+    if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "a session needs with_vocoder = 1");
+    Q3_HIP(e, hipSetDevice(e->cfg.device));
+    Q3_HIP(e, hipStreamSynchronize(e->stream));
+    Q3_HIP(e, hipStreamSynchronize(e->vstream));
+    std::unique_ptr<q3tts_session> s(new q3tts_session());
+    s->e = e; s->fmt = pcm_format; s->es = pcm_format ? 2 : 4;
+    s->ring_cap = (size_t)e->B * (4 + std::max(0, e->cfg.vocoder.lookahead_frames)) * q3_voc_samples_per_frame(e);
+    auto release = [&]() {
+        for (int k = 0; k < kRing; ++k) { if (s->host[k]) hipHostFree(s->host[k]); if (s->ev[k]) hipEventDestroy(s->ev[k]); }
+        if (s->dev) hipFree(s->dev);
+    };
+    for (int k = 0; k < kRing; ++k) {
+        if (hipHostMalloc(&s->host[k], s->ring_cap * s->es, hipHostMallocDefault) != hipSuccess ||
+            hipEventCreateWithFlags(&s->ev[k], hipEventDisableTiming) != hipSuccess) { release(); return q3_set_err(e, Q3TTS_ERR_OOM, "session: pinned staging"); }
+    }
+    if (hipMalloc(&s->dev, s->ring_cap * s->es) != hipSuccess) { release(); return q3_set_err(e, Q3TTS_ERR_OOM, "session: device staging"); }
+    s->slots.resize(e->B);
+    s->voc_frames.assign(e->B, 0);
+    q3tts_session* raw = s.release();
+    e->session.store(raw);
+    raw->th = std::thread(worker, raw);
+    *out = raw;
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_submit(q3tts_session* s, const q3tts_request* req, uint64_t* id) {
+    if (!s || !req || !id) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    std::unique_ptr<SReq> q(new SReq());
+    if (copy_request(s->e, req, q.get()) != Q3TTS_OK) {
+        std::lock_guard<std::mutex> lk(s->mu);
+        return serr(s, Q3TTS_ERR_INVALID, "submit: the request's prompt cannot be copied (n_tok outside 1..n_ctx or a null array with a length)");
+    }
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->stop || s->dead) return serr(s, Q3TTS_ERR_STATE, s->dead ? "submit: the session's worker failed" : "submit: the session is closing");
+        q->id = s->next_id++;
+        IdState st; st.t_submit = q3_now_ms();
+        s->ids[q->id] = st;
+        *id = q->id;
+        s->pending.push_back(std::move(q));
+    }
+    s->cv_work.notify_one();
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_cancel(q3tts_session* s, uint64_t id) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        auto it = s->ids.find(id);
+        if (it == s->ids.end()) return serr(s, Q3TTS_ERR_INVALID, "cancel: unknown id, or its final event was delivered");
+        IdState& st = it->second;
+        if (st.cancelled) return Q3TTS_OK;
+        st.cancelled = true;
+        if (st.queued) {
+            for (auto p = s->pending.begin(); p != s->pending.end(); ++p)
+                if ((*p)->id == id) { s->pending.erase(p); break; }
+            SEv v = final_ev(id, Q3TTS_EV_CANCELLED, Q3TTS_OK);
+            deliver(s, v, q3_now_ms());
+        } else {
+            for (auto r = s->ready.begin(); r != s->ready.end();) {  // no further chunk from now on; a waiting final becomes CANCELLED
+                if (r->id != id) { ++r; continue; }
+                if (r->kind == Q3TTS_EV_CHUNK) {
+                    if (r->ring >= 0 && --s->refs[r->ring] == 0) s->cv_space.notify_all();
+                    r = s->ready.erase(r);
+                    continue;
+                }
+                if (r->kind != Q3TTS_EV_CANCELLED) { copy_result_free(r->res); r->res.status = Q3TTS_OK; r->kind = Q3TTS_EV_CANCELLED; r->status = Q3TTS_OK; }
+                ++r;
+            }
+            if (!st.final_ready) s->cancels.push_back(id);
+        }
+    }
+    s->cv_work.notify_one();
+    s->cv_ev.notify_all();
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_next(q3tts_session* s, int32_t timeout_ms, q3tts_session_event* ev) {
+    if (!s || !ev) return serr(s, Q3TTS_ERR_INVALID, "null argument");
+    memset(ev, 0, sizeof(*ev));
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (s->held_ring >= 0) {
+        if (--s->refs[s->held_ring] == 0) s->cv_space.notify_all();
+        s->held_ring = -1;
+    }
+    auto ready = [&] { return !s->ready.empty() || s->stop || s->dead; };
+    if (timeout_ms < 0) s->cv_ev.wait(lk, ready);
+    else s->cv_ev.wait_for(lk, std::chrono::milliseconds(timeout_ms), ready);
+    if (s->ready.empty()) { ev->kind = Q3TTS_EV_NONE; return Q3TTS_OK; }
+    SEv v = s->ready.front();
+    s->ready.pop_front();
+    ev->id = v.id; ev->kind = v.kind; ev->status = v.status; ev->n_samples = v.n; ev->is_final = v.is_final;
+    if (v.kind == Q3TTS_EV_CHUNK) {
+        if (v.ring >= 0) { ev->pcm = (const char*)s->host[v.ring] + v.off * s->es; s->held_ring = v.ring; }  // (its reference moves to the consumer)
+    } else {
+        ev->result = v.res;
+        s->ids.erase(v.id);
+    }
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_close(q3tts_session* s) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        s->stop = true;
+    }
+    s->cv_work.notify_all(); s->cv_space.notify_all(); s->cv_ev.notify_all();
+    if (s->th.joinable()) s->th.join();
+    q3tts_engine* e = s->e;
+    hipSetDevice(e->cfg.device);
+    for (Batch& b : s->flight) for (SEv& v : b.evs) copy_result_free(v.res);
+    for (SEv& v : s->ready) copy_result_free(v.res);
+    for (int k = 0; k < kRing; ++k) { if (s->host[k]) hipHostFree(s->host[k]); if (s->ev[k]) hipEventDestroy(s->ev[k]); }
+    if (s->dev) hipFree(s->dev);
+    const int rc = s->worker_rc;
+    e->session.store(nullptr);
+    delete s;
+    return rc;
+}
+
+extern "C" const char* q3tts_session_last_error(const q3tts_session* s) {
+    if (!s) return g_serr.c_str();
+    static thread_local std::string copy;
+    std::lock_guard<std::mutex> lk(const_cast<q3tts_session*>(s)->mu);
+    copy = s->err;
+    return copy.c_str();
+}

@@ -1877,6 +1877,7 @@ int q3_voc_decode_batch(q3tts_engine* e, const int* slots, const int* real, int 
 void q3_voc_mark_last(q3tts_engine* e, int slot) { if (e->voc) e->voc->last_flag[slot] = 1; }
 
 float* q3_voc_pcm(q3tts_engine* e, int slot) { return e->voc->pcm + (size_t)slot * e->voc->pcm_stride; }
+size_t q3_voc_pcm_stride(const q3tts_engine* e) { return e->voc ? e->voc->pcm_stride : 0; }
 // V4: frames are withheld by lookahead_frames until more input arrives or the slot is flushed with is_last
 int q3_voc_samples(q3tts_engine* e, int slot) {
     Q3Voc* v = e->voc;
@@ -1886,6 +1887,7 @@ int q3_voc_samples(q3tts_engine* e, int slot) {
 }
 
 extern "C" int q3tts_k_vocoder(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, float* pcm_out, int32_t* n_samples_out) {
+    Q3_NOT_IN_SESSION(e);
     if (!e || !codes || !pcm_out || !n_samples_out || n_frames <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "engine created with with_vocoder = 0");
     if (n_frames > e->cfg.max_steps_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "n_frames exceeds max_steps_cap");
@@ -1920,6 +1922,7 @@ static void voc_print_stamps() {
 }
 #endif
 extern "C" int q3tts_k_vocoder_bench(q3tts_engine* e, int32_t n_slots, int32_t chunks, float* ms_per_chunk) {
+    Q3_NOT_IN_SESSION(e);
     if (!e || !ms_per_chunk || n_slots <= 0 || chunks <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder bench: bad argument");
     if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "engine created with with_vocoder = 0");
     if (n_slots > e->B || n_slots > VOC_MAX_NS || (chunks + 2) * 4 > e->cfg.max_steps_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder bench: shape exceeds the engine's");

@@ -87,6 +87,19 @@ class Result(C.Structure):
     ]
 
 
+class SessionEvent(C.Structure):
+    """q3tts_session_event: one event of a session (kind EV_*); pcm is f32 or i16 by the session's format."""
+    _fields_ = [
+        ("id", C.c_uint64), ("kind", C.c_int32), ("status", C.c_int32), ("pcm", C.c_void_p), ("n_samples", C.c_int32),
+        ("is_final", C.c_int32), ("result", Result),
+    ]
+
+
+EV_NONE, EV_CHUNK, EV_DONE, EV_FAILED, EV_CANCELLED = 0, 1, 2, 3, 4
+PCM_F32, PCM_I16 = 0, 1
+SESSION_RING_DEPTH = 4
+
+
 class Timings(C.Structure):
     _fields_ = [
         ("prefill_ms", C.c_float), ("decode_ms", C.c_float), ("vocoder_ms", C.c_float), ("total_ms", C.c_float),
@@ -126,6 +139,8 @@ SYMBOLS = [
     "q3tts_clone_default_config", "q3tts_clone_init", "q3tts_clone_audio_frames", "q3tts_clone_audio_encode",
     "q3tts_clone_speaker_encode", "q3tts_k_speaker_from_mel", "q3tts_k_audio_latent",
     "q3tts_node_create", "q3tts_node_destroy", "q3tts_node_generate_batch", "q3tts_node_get_timings", "q3tts_node_last_error", "q3tts_node_size", "q3tts_node_engine", "q3tts_node_shard", "q3tts_k_bgemm_q8", "q3tts_k_bgemm_q8a8", "q3tts_k_alloc_upload", "q3tts_k_bgemm_policy", "q3tts_k_attend_policy", "q3tts_k_bgemm_pick", "q3tts_k_mfma_bf16", "q3tts_k_bgemm", "q3tts_k_bgemm_voc", "q3tts_k_project", "q3tts_k_norm_inputs", "q3tts_tokenizer_load", "q3tts_tokenizer_free", "q3tts_tokenizer_vocab_size", "q3tts_tokenizer_encode", "q3tts_tokenizer_decode",
+    "q3tts_session_create", "q3tts_session_submit", "q3tts_session_cancel", "q3tts_session_next", "q3tts_session_close",
+    "q3tts_session_last_error", "q3tts_k_pcm_pack",
 ]
 
 
@@ -165,6 +180,15 @@ def load_library(path=None):
     lib.q3tts_generate_batch.argtypes = [vp, C.POINTER(Request), C.c_int32, C.POINTER(Result)]
     lib.q3tts_result_free.argtypes = [C.POINTER(Result)]
     lib.q3tts_result_free.restype = None
+    lib.q3tts_session_create.argtypes = [vp, C.c_int32, C.POINTER(vp)]
+    lib.q3tts_session_submit.argtypes = [vp, C.POINTER(Request), C.POINTER(C.c_uint64)]
+    lib.q3tts_session_cancel.argtypes = [vp, C.c_uint64]
+    lib.q3tts_session_next.argtypes = [vp, C.c_int32, C.POINTER(SessionEvent)]
+    lib.q3tts_session_close.argtypes = [vp]
+    lib.q3tts_session_last_error.argtypes = [vp]
+    lib.q3tts_session_last_error.restype = C.c_char_p
+    lib.q3tts_k_pcm_pack.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, vp,
+                                     C.c_int64]
     lib.q3tts_stream_begin.argtypes = [vp, C.POINTER(Request), C.POINTER(vp)]
     lib.q3tts_stream_poll.argtypes = [vp, C.POINTER(f32p), i32p, i32p]
     lib.q3tts_stream_end.argtypes = [vp, C.POINTER(Result)]

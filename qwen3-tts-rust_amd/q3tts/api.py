@@ -231,6 +231,23 @@ class TtsEngine:
         sr = self.cfg.vocoder.sample_rate
         return [AudioSample(o.pcm, sr, 1) for o in outs]
 
+    def stream_batch_with_voice(self, texts, voices, instructs=None, seeds=None):
+        """The streaming twin of generate_batch_with_voice: every utterance runs through one session (continuous batching over the
+        engine's slots) and its 4-frame chunks are yielded as they are produced, as (index, f32 chunk, is_final); chunks of different
+        utterances interleave, each utterance's come in order and its last has is_final = True."""
+        sc = self.sampler_config
+        with native.NativeSession(self._native) as sess:
+            index = {}
+            for i, (t, v) in enumerate(zip(texts, voices)):
+                desc, keep = self._desc(t, v, None if instructs is None else instructs[i])
+                seed = sc.seed if seeds is None else seeds[i]
+                index[sess.submit(desc=desc, temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p, seed=seed, max_steps=self.max_steps)] = i
+            for rid, kind, pcm, is_final, res in sess.events():
+                if kind == _abi.EV_CHUNK:
+                    yield index[rid], pcm, is_final
+                elif kind != _abi.EV_DONE:
+                    raise _abi.Q3Error(f"generation failed with status {res.status if res is not None else kind}")
+
     def load_clone_encoders(self, clone_config=None):
         """The reference loads onnx/qwen3_tts_codec_encoder.onnx and onnx/qwen3_tts_speaker_encoder.onnx when they exist
         (src/tts/engine.rs:105-119). Those graphs are not available; this loads the family-structure encoders with seeded

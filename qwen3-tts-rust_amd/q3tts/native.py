@@ -249,6 +249,73 @@ class NativeEngine:
         return pcm[:ns.value].copy()
 
 
+class NativeSession:
+    """q3tts_session_*: continuous batching with per-request streaming on one engine (include/q3tts.h, "sessions"). The session owns the
+    engine until close(); submit() and cancel() may be called from any thread, events() from one consumer thread."""
+
+    def __init__(self, engine: NativeEngine, pcm_format=_abi.PCM_F32):
+        self.engine, self.lib = engine, engine.lib
+        self.dtype = np.int16 if pcm_format == _abi.PCM_I16 else np.float32
+        self._ctype = C.c_int16 if pcm_format == _abi.PCM_I16 else C.c_float
+        self._open = set()   # ids without their final event yet
+        self.h = C.c_void_p()
+        engine._check(self.lib.q3tts_session_create(engine.h, pcm_format, C.byref(self.h)), "q3tts_session_create")
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise _abi.Q3Error(f"{what} failed ({rc}): {self.lib.q3tts_session_last_error(self.h).decode()}")
+
+    def submit(self, **request_kw):
+        """request_kw: NativeEngine.make_request keywords (want_pcm is ignored: a session always produces PCM). Returns the id."""
+        if not self.h:
+            raise _abi.Q3Error("q3tts_session_submit: the session is closed")
+        r, keep = NativeEngine.make_request(**request_kw)
+        rid = C.c_uint64(0)
+        self._check(self.lib.q3tts_session_submit(self.h, C.byref(r), C.byref(rid)), "q3tts_session_submit")
+        self._open.add(rid.value)
+        return rid.value
+
+    def cancel(self, rid):
+        self._check(self.lib.q3tts_session_cancel(self.h, rid), "q3tts_session_cancel")
+
+    def next(self, timeout_ms=-1):
+        """One event as (id, kind, pcm ndarray | None, is_final, GenResult | None), or None on timeout."""
+        ev = _abi.SessionEvent()
+        self._check(self.lib.q3tts_session_next(self.h, timeout_ms, C.byref(ev)), "q3tts_session_next")
+        if ev.kind == _abi.EV_NONE:
+            return None
+        pcm = res = None
+        if ev.kind == _abi.EV_CHUNK:
+            pcm = np.ctypeslib.as_array(C.cast(ev.pcm, C.POINTER(self._ctype)), shape=(ev.n_samples,)).copy() if ev.n_samples > 0 else \
+                np.zeros(0, dtype=self.dtype)
+        else:
+            res = self.engine._unpack(ev.result)
+            self._open.discard(ev.id)
+        return ev.id, ev.kind, pcm, bool(ev.is_final), res
+
+    def events(self, timeout_ms=-1):
+        """Generator over next(): ends when every submitted id has had its final event, or when timeout_ms passes without one."""
+        while self._open:
+            ev = self.next(timeout_ms)
+            if ev is None:
+                return
+            yield ev
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.q3tts_session_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
 # ---- kernel-level hooks (host arrays in / out) -------------------------------------------------
 
 class NativeNode:
@@ -497,6 +564,23 @@ def k_gguf_read(path, tensor=""):
     if not str(path).endswith(".npy"):
         shape = shape[::-1]  # ggml lists the contiguous dimension first
     return out.reshape(shape), int(ty.value)
+
+
+def k_pcm_pack(src, entries, out_n, fmt=0, device=0):
+    """q3tts_k_pcm_pack: src [rows][stride] f32, entries [(row, first, count, dst)] (<= 64); returns the f32 (fmt 0) or i16 (fmt 1) output
+    of out_n samples (zeros outside the windows)."""
+    lib = _abi.load_library()
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    rows, stride = src.shape
+    e = np.asarray(entries, dtype=np.int64).reshape(-1, 4)
+    er, ef, ec = (np.ascontiguousarray(e[:, i], dtype=np.int32) for i in range(3))
+    ed = np.ascontiguousarray(e[:, 3], dtype=np.int64)
+    out = np.zeros(max(int(out_n), 1), dtype=np.int16 if fmt else np.float32)
+    rc = lib.q3tts_k_pcm_pack(device, _ptr(src, f32p), rows, stride, _ptr(er, i32p), _ptr(ef, i32p), _ptr(ec, i32p),
+                              ed.ctypes.data_as(C.POINTER(C.c_int64)), len(e), fmt, out.ctypes.data, int(out_n))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_pcm_pack failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return out[:int(out_n)]
 
 
 def k_rng_f32(seed, n):
