@@ -378,6 +378,12 @@ int q3tts_k_gemm_exact(int32_t device, const float* x, int32_t B, int32_t K, con
 int q3tts_k_attention(int32_t device, const float* qkv /*[n][(Hq+2Hkv)*hd]*/, int32_t n_rows, int32_t pos0,
                       int32_t n_head, int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w,
                       float eps, float rope_theta, const int32_t* mrope_sections, float* out /*[n][Hq*hd]*/);
+/* decode attention as the frame step runs it: per slot, rows 0 .. lens[s] - 2 of qkv (the slots' rows back to back) prepared into a
+ * cache of n_ctx positions, then ONE fused decode launch at pos = lens[s] - 1 under decode policy `policy` (-1: the current one, as in
+ * q3tts_k_attend_policy); out_f32 [n_slots][Hq*hd]; out_bf16 (optional) the bf16 operand the same launch writes for the O projection */
+int q3tts_k_attention_decode(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t n_head,
+                             int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps, float rope_theta,
+                             const int32_t* mrope_sections, int32_t policy, float* out_f32, uint16_t* out_bf16);
 /* sampler (H4: src/models/llama/mod.rs:666-772) on n rows of logits; r_uniform[n] are the f32 draws */
 int q3tts_k_sample(int32_t device, const float* logits, int32_t n, int32_t ld, int32_t limit, float temperature,
                    int32_t top_k, float top_p, const float* r_uniform, int32_t* out_ids);
@@ -386,6 +392,9 @@ int q3tts_k_talker_prefill(q3tts_engine* e, const float* embd, int32_t n_tok, fl
 /* Vocoder: codes [n_frames][n_codebooks] -> pcm; chunk_frames frames per streaming call (0 = one call) */
 int q3tts_k_vocoder(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, float* pcm_out,
                     int32_t* n_samples_out);
+/* Vocoder transformer rows: q3tts_k_vocoder's calls on slot 0, and after each the f32 residual rows after the last layer (before the
+ * final norm) -> out [n_frames][latent_dim] */
+int q3tts_k_vocoder_latent(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, float* out);
 /* Measurement (bench.py roofline_vocoder): the batched vocoder alone, n_slots slots x `chunks` 4-frame calls with nothing else on the
  * GPU; *ms_per_chunk = mean duration of one batched call (n_slots x 4 frames of PCM) by HIP events on its stream. */
 int q3tts_k_vocoder_bench(q3tts_engine* e, int32_t n_slots, int32_t chunks, float* ms_per_chunk);

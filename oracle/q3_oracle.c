@@ -320,9 +320,9 @@ static void attend_one(const float* qh, const float* Kc, const float* Vc, int T,
     free(ou); free(sc);
 }
 
-/* rows of one sequence in order: q/k RMSNorm -> RoPE -> append bf16 K/V -> attention */
-static void attn_rows(const float* qkv, int n_rows, int pos0, int Hq, int Hkv, int hd, const float* qnw, const float* knw,
-                      float eps, const float* cs, const float* sn, float* kc, float* vc, int n_ctx, float* out) {
+/* rows of one sequence in order: q/k RMSNorm -> RoPE -> append bf16 K/V -> attention (rows before `attend_from` only append) */
+static void attn_rows_from(const float* qkv, int n_rows, int pos0, int Hq, int Hkv, int hd, const float* qnw, const float* knw,
+                           float eps, const float* cs, const float* sn, float* kc, float* vc, int n_ctx, int attend_from, float* out) {
     const int ld = (Hq + 2 * Hkv) * hd, R = Hq / Hkv, half = hd / 2;
     float* tmp = (float*)malloc((size_t)hd * 4);
     for (int r = 0; r < n_rows; ++r) {
@@ -336,15 +336,20 @@ static void attn_rows(const float* qkv, int n_rows, int pos0, int Hq, int Hkv, i
             const float* vs = row + (size_t)(Hq + Hkv + g) * hd;
             for (int d = 0; d < hd; ++d) { kd[d] = round_bf16(tmp[d]); vd[d] = round_bf16(vs[d]); }
         }
+        if (r < attend_from) continue;
         for (int h = 0; h < Hq; ++h) {
             const int g = h / R;
             q3o_rmsnorm(row + (size_t)h * hd, hd, qnw, eps, tmp);
             rope_apply(tmp, hd, cs + (size_t)pos * half, sn + (size_t)pos * half);
             attend_one(tmp, kc + (size_t)g * n_ctx * hd, vc + (size_t)g * n_ctx * hd, pos + 1, hd,
-                       out + (size_t)r * Hq * hd + (size_t)h * hd);
+                       out + (size_t)(r - attend_from) * Hq * hd + (size_t)h * hd);
         }
     }
     free(tmp);
+}
+static void attn_rows(const float* qkv, int n_rows, int pos0, int Hq, int Hkv, int hd, const float* qnw, const float* knw,
+                      float eps, const float* cs, const float* sn, float* kc, float* vc, int n_ctx, float* out) {
+    attn_rows_from(qkv, n_rows, pos0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_ctx, 0, out);
 }
 
 void q3o_attention(const float* qkv, int32_t n_rows, int32_t pos0, int32_t Hq, int32_t Hkv, int32_t hd, const float* qnw,
@@ -356,6 +361,19 @@ void q3o_attention(const float* qkv, int32_t n_rows, int32_t pos0, int32_t Hq, i
     float* kc = (float*)calloc((size_t)Hkv * n_ctx * hd, 4);
     float* vc = (float*)calloc((size_t)Hkv * n_ctx * hd, 4);
     attn_rows(qkv, n_rows, pos0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_ctx, out);
+    free(kc); free(vc); free(cs); free(sn);
+}
+/* q3o_attention's output for the LAST row only (rows 0 .. n_rows - 1 at positions 0 .. n_rows - 1, the earlier ones only appended):
+ * the decode step over long caches without the all-rows cost */
+void q3o_attention_last(const float* qkv, int32_t n_rows, int32_t Hq, int32_t Hkv, int32_t hd, const float* qnw, const float* knw,
+                        float eps, float theta, const int32_t* sections, float* out) {
+    const int half = hd / 2;
+    float* cs = (float*)malloc((size_t)n_rows * half * 4);
+    float* sn = (float*)malloc((size_t)n_rows * half * 4);
+    rope_tables(n_rows, hd, theta, sections, cs, sn);
+    float* kc = (float*)calloc((size_t)Hkv * n_rows * hd, 4);
+    float* vc = (float*)calloc((size_t)Hkv * n_rows * hd, 4);
+    attn_rows_from(qkv, n_rows, 0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_rows, n_rows - 1, out);
     free(kc); free(vc); free(cs); free(sn);
 }
 

@@ -87,6 +87,9 @@ void q3o_rmsnorm(const float* x, int32_t d, const float* w, float eps, float* y)
 void q3o_attention(const float* qkv, int32_t n_rows, int32_t pos0, int32_t n_head, int32_t n_kv_head,
                    int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps, float rope_theta,
                    const int32_t* mrope_sections, float* out);
+/* the same for the LAST of n_rows rows at positions 0 .. n_rows - 1 only: out[Hq * head_dim] */
+void q3o_attention_last(const float* qkv, int32_t n_rows, int32_t n_head, int32_t n_kv_head, int32_t head_dim, const float* q_norm_w,
+                        const float* k_norm_w, float eps, float rope_theta, const int32_t* mrope_sections, float* out);
 /* one output element of v_mfma_f32_16x16x32_bf16 (gfx950), restated in integers: a[32], b[32] bf16 bits in operand order
  * (position 8g + e = operand e of lane group g), c the accumulator. _ref: the 128-bit form the 64-bit one is tested against. */
 float q3o_mfma_bf16_dot32(const uint16_t* a, const uint16_t* b, float c);

@@ -201,7 +201,8 @@ void q3o_vocoder_set_arith_mask(q3o_vocoder* v, uint32_t mask) { (void)v; g_vf32
 
 /* whole-utterance decode of frames [0, T): returns malloc'd pcm of T*spf samples */
 /* stage / stage_out (tests): 1 the transformer's input [T][d], 2 its output after the final norm [T][d], 3 the up-sampled latent
- * [T * prod(upsample_ratios)][d], 4 the PCM before the clamp */
+ * [T * prod(upsample_ratios)][d], 4 the PCM before the clamp. A requested stage of 1..3 ends the decode there (returns NULL): the
+ * stages before it are computed exactly as in a whole decode, so their bits do not depend on where the decode stops. */
 static int g_stage = 0; static float* g_stage_out = NULL;
 #define STAGE(k, ptr, n) do { if (g_stage == (k) && g_stage_out) memcpy(g_stage_out, (ptr), (size_t)(n) * 4); } while (0)
 static float* decode_all(q3o_vocoder* v, int T) {
@@ -221,6 +222,7 @@ static float* decode_all(q3o_vocoder* v, int T) {
     float* x = malloc((size_t)T * d * 4);
     conv_fwd(&v->pre, e, T, x); free(e);
     STAGE(1, x, (size_t)T * d);
+    if (g_stage == 1) { free(x); return NULL; }
     /* V3: sliding-window transformer */
     float* xn = malloc((size_t)T * d * 4); float* q = malloc((size_t)T * HH * 4); float* k = malloc((size_t)T * HH * 4);
     float* vv = malloc((size_t)T * HH * 4); float* att = malloc((size_t)T * HH * 4); float* y = malloc((size_t)T * d * 4);
@@ -268,6 +270,7 @@ static float* decode_all(q3o_vocoder* v, int T) {
     rmsnorm_rows(x, T, d, v->final_norm, c->rms_eps, xn);
     STAGE(2, xn, (size_t)T * d);
     free(q); free(k); free(vv); free(att); free(y); free(g); free(u); free(x);
+    if (g_stage == 2) { free(xn); return NULL; }
     /* V5a: upsample stages */
     g_vgroup = 1;
     float* cur = xn; int Tc = T;
@@ -300,6 +303,7 @@ static float* decode_all(q3o_vocoder* v, int T) {
         free(dw); cur = up;
     }
     STAGE(3, cur, (size_t)Tc * d);
+    if (g_stage == 3) { free(cur); return NULL; }
     /* V5b: decoder */
     int ch = c->decoder_dim;
     float* z = malloc((size_t)Tc * ch * 4);

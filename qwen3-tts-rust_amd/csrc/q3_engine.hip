@@ -1460,6 +1460,87 @@ extern "C" int q3tts_k_attention(int32_t device, const float* qkv, int32_t n_row
     return Q3TTS_OK;
 }
 
+// Decode attention as the engine's frame step runs it: per slot, rows 0 .. len - 2 go through k_qk_prep into a cache of n_ctx positions,
+// then ONE fused decode launch (one row per slot at pos = len - 1; q/k prep and the K/V append in-kernel) through q3_launch_attend under
+// decode policy `policy` (-1: the current one). qkv holds the slots' rows back to back ([sum lens][(Hq + 2 Hkv) hd]); out_f32 [n_slots][Hq hd];
+// out_bf16 (optional): the same launch writing the A-tiled bf16 operand of the O projection, untiled here to [n_slots][Hq hd].
+extern "C" int q3tts_k_attention_decode(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq,
+                                        int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta,
+                                        const int32_t* sections, int32_t policy, float* out_f32, uint16_t* out_bf16) {
+    if (!qkv || !lens || !out_f32 || hd != 128 || n_slots <= 0 || Hkv <= 0 || Hq % Hkv || Hq / Hkv < 2 || n_ctx <= 0 || n_ctx % 64 || policy < -1 || policy > 1)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode hook: bad shape");
+    long long total = 0;
+    for (int s = 0; s < n_slots; ++s) {
+        if (lens[s] < 1 || lens[s] > n_ctx) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode hook: a length outside 1 .. n_ctx");
+        total += lens[s];
+    }
+    HK(hipSetDevice(device));
+    const int ld = (Hq + 2 * Hkv) * hd, nq = Hq * hd, npre = (int)(total - n_slots), r16 = (n_slots + 15) & ~15;
+    std::vector<float> cs, sn;
+    rope_tables(n_ctx, hd, theta, sections, cs, sn);
+    std::vector<float> last((size_t)n_slots * ld);
+    std::vector<int> pp, ps, dp(n_slots), ds(n_slots);
+    pp.reserve(npre); ps.reserve(npre);
+    {
+        size_t r0 = 0;
+        for (int s = 0; s < n_slots; ++s) {
+            for (int r = 0; r < lens[s] - 1; ++r) { pp.push_back(r); ps.push_back(s); }
+            memcpy(&last[(size_t)s * ld], qkv + (r0 + lens[s] - 1) * ld, (size_t)ld * 4);
+            dp[s] = lens[s] - 1; ds[s] = s;
+            r0 += lens[s];
+        }
+    }
+    DevBuf dpre, dlast, dout, dob, dqn, dkn, dcs, dsn, dkc, dvc, dpp, dps, ddp, dds;
+    const size_t cache = (size_t)n_slots * Hkv * n_ctx * hd * 2;
+    if (dpre.alloc((size_t)std::max(npre, 1) * ld * 4) || dlast.alloc(last.size() * 4) || dout.alloc((size_t)n_slots * nq * 4) ||
+        dob.alloc((size_t)r16 * nq * 2) || dqn.alloc(hd * 4) || dkn.alloc(hd * 4) || dcs.alloc(cs.size() * 4) || dsn.alloc(sn.size() * 4) ||
+        dkc.alloc(cache) || dvc.alloc(cache) || dpp.alloc((size_t)std::max(npre, 1) * 4) || dps.alloc((size_t)std::max(npre, 1) * 4) ||
+        ddp.alloc(n_slots * 4) || dds.alloc(n_slots * 4))
+        return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
+    {
+        size_t r0 = 0, o = 0;
+        for (int s = 0; s < n_slots; ++s) {
+            const size_t n = lens[s] - 1;
+            if (n) HK(hipMemcpy((float*)dpre.p + o * ld, qkv + r0 * ld, n * ld * 4, hipMemcpyHostToDevice));
+            o += n; r0 += lens[s];
+        }
+    }
+    HK(hipMemcpy(dqn.p, qnw, hd * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dkn.p, knw, hd * 4, hipMemcpyHostToDevice));
+    HK(hipMemcpy(dcs.p, cs.data(), cs.size() * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dsn.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+    if (npre) { HK(hipMemcpy(dpp.p, pp.data(), npre * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dps.p, ps.data(), npre * 4, hipMemcpyHostToDevice)); }
+    HK(hipMemcpy(ddp.p, dp.data(), n_slots * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dds.p, ds.data(), n_slots * 4, hipMemcpyHostToDevice));
+    Q3QkPrep qp{}; qp.qkv = (float*)dpre.p; qp.ld = ld; qp.rows = npre; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = hd; qp.qnw = (const float*)dqn.p;
+    qp.knw = (const float*)dkn.p; qp.eps = eps; qp.cs = (const float*)dcs.p; qp.sn = (const float*)dsn.p; qp.kc = (uint16_t*)dkc.p;
+    qp.vc = (uint16_t*)dvc.p; qp.n_ctx = n_ctx; qp.row_pos = (const int*)dpp.p; qp.row_slot = (const int*)dps.p;
+    if (npre) q3_launch_qk_prep(qp, nullptr);
+    int old_dec = 0, old_pre = 0;
+    q3_attend_policy_get(&old_dec, &old_pre);
+    if (policy >= 0) q3_attend_policy(policy, old_pre);
+    for (int pass = 0; pass < (out_bf16 ? 2 : 1); ++pass) {
+        // both passes start from the same cache: the fused launch's append rewrites position len - 1 with the same bits
+        HK(hipMemcpy(dlast.p, last.data(), last.size() * 4, hipMemcpyHostToDevice));
+        Q3QkPrep dq = qp; dq.qkv = (float*)dlast.p; dq.rows = n_slots; dq.row_pos = (const int*)ddp.p; dq.row_slot = (const int*)dds.p;
+        Q3Attend at{}; at.qkv = (const float*)dlast.p; at.ld = ld; at.rows = n_slots; at.ldo = nq; at.Hq = Hq; at.Hkv = Hkv; at.hd = hd;
+        at.kc = (const uint16_t*)dkc.p; at.vc = (const uint16_t*)dvc.p; at.n_ctx = n_ctx; at.row_pos = dq.row_pos; at.row_slot = dq.row_slot;
+        at.fused = 1; at.prep = dq;
+        if (pass == 0) { at.out = (float*)dout.p; at.out_bf16 = 0; }
+        else { at.out = (float*)dob.p; at.out_bf16 = 1; }
+        q3_launch_attend(at, nullptr);
+        const hipError_t er = hipDeviceSynchronize();
+        if (er != hipSuccess) { q3_attend_policy(old_dec, old_pre); return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, std::string("attention decode hook: ") + hipGetErrorString(er)); }
+    }
+    q3_attend_policy(old_dec, old_pre);
+    HK(hipGetLastError());
+    HK(hipMemcpy(out_f32, dout.p, (size_t)n_slots * nq * 4, hipMemcpyDeviceToHost));
+    if (out_bf16) {
+        std::vector<uint16_t> t((size_t)r16 * nq);
+        HK(hipMemcpy(t.data(), dob.p, t.size() * 2, hipMemcpyDeviceToHost));
+        for (int r = 0; r < n_slots; ++r)
+            for (int c = 0; c < nq; ++c) out_bf16[(size_t)r * nq + c] = t[q3_atile_off(r, c, nq >> 5)];
+    }
+    return Q3TTS_OK;
+}
+
 extern "C" int q3tts_k_sample(int32_t device, const float* logits, int32_t n, int32_t ld, int32_t limit, float temperature, int32_t top_k,
                               float top_p, const float* r, int32_t* out) {
     if (!logits || !out || n <= 0 || limit <= 0 || limit > 4096 || limit > ld) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "sample hook: bad shape");

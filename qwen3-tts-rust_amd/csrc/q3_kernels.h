@@ -223,6 +223,7 @@ struct Q3Attend {
 };
 void q3_launch_attend(const Q3Attend& a, hipStream_t s);
 void q3_attend_policy(int decode, int prefill);  // test hook (q3tts_k_attend_policy): which kernel variant serves decode / prefill attention (same bits)
+void q3_attend_policy_get(int* decode, int* prefill);
 
 // Talker sampler + frame bookkeeping (H4/H5). One workgroup per slot.
 struct Q3Sample {

@@ -946,6 +946,7 @@ static void att_policy_init() {
     });
 }
 void q3_attend_policy(int decode, int prefill) { att_policy_init(); g_att_decode = decode; g_att_prefill = prefill; }
+void q3_attend_policy_get(int* decode, int* prefill) { att_policy_init(); *decode = g_att_decode; *prefill = g_att_prefill; }
 
 void q3_launch_attend(const Q3Attend& a, hipStream_t s) {
     att_policy_init();

@@ -1908,6 +1908,31 @@ extern "C" int q3tts_k_vocoder(q3tts_engine* e, const int32_t* codes, int32_t n_
     return Q3TTS_OK;
 }
 
+// Test hook: slot 0 driven exactly as q3tts_k_vocoder drives it, and after every call the transformer's f32 residual rows v->x (after the
+// last layer, before the final norm; nothing later in the call writes them) copied to out[n_frames][latent_dim].
+extern "C" int q3tts_k_vocoder_latent(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, float* out) {
+    Q3_NOT_IN_SESSION(e);
+    if (!e || !codes || !out || n_frames <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
+    if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "engine created with with_vocoder = 0");
+    if (n_frames > e->cfg.max_steps_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "n_frames exceeds max_steps_cap");
+    Q3_HIP(e, hipSetDevice(e->cfg.device));
+    const int ncb = e->cfg.model.n_codebooks, d = e->voc->c.latent_dim;
+    hipStream_t s = e->stream;
+    Q3_HIP(e, hipMemcpyAsync(e->codes, codes, sizeof(int32_t) * (size_t)n_frames * ncb, hipMemcpyHostToDevice, s));  // slot 0
+    VTRY(q3_voc_reset(e, 0));
+    const int step = chunk_frames > 0 ? chunk_frames : n_frames;
+    for (int f = 0; f < n_frames; f += step) {
+        const int n = std::min(step, n_frames - f);
+        for (int f1 = f; f1 < f + n; f1 += VOC_FCAP) {  // q3_voc_decode's own split, one call at a time so each call's rows can be read
+            const int n1 = std::min(VOC_FCAP, f + n - f1);
+            VTRY(q3_voc_decode(e, 0, f1, n1, f1 + n1 >= n_frames, s));
+            Q3_HIP(e, hipMemcpyAsync(out + (size_t)f1 * d, e->voc->x, sizeof(float) * (size_t)n1 * d, hipMemcpyDeviceToHost, s));
+        }
+    }
+    Q3_HIP(e, hipStreamSynchronize(s));
+    return Q3TTS_OK;
+}
+
 // Measurement hook (bench.py's roofline_vocoder): the batched vocoder alone — n_slots slots x 4-frame chunks, `chunks` calls on the
 // engine's stream with nothing else on the GPU, HIP events around them. Codes are seeded pseudo-random. *ms_per_chunk = the mean
 // duration of one batched 4-frame call (n_slots x 4 frames of PCM).

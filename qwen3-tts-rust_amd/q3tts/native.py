@@ -248,6 +248,14 @@ class NativeEngine:
                     "q3tts_k_vocoder")
         return pcm[:ns.value].copy()
 
+    def vocoder_latent(self, codes, chunk_frames=0):
+        """The vocoder transformer's f32 residual rows after its last layer (before the final norm), [n_frames][latent_dim]: slot 0
+        driven as vocoder() drives it (q3tts_k_vocoder_latent)."""
+        c = np.ascontiguousarray(codes, dtype=np.int32)
+        out = np.zeros((c.shape[0], self.cfg.vocoder.latent_dim), dtype=np.float32)
+        self._check(self.lib.q3tts_k_vocoder_latent(self.h, _ptr(c, i32p), c.shape[0], chunk_frames, _ptr(out, f32p)), "q3tts_k_vocoder_latent")
+        return out
+
 
 class NativeSession:
     """q3tts_session_*: continuous batching with per-request streaming on one engine (include/q3tts.h, "sessions"). The session owns the
@@ -533,6 +541,26 @@ def k_attention(qkv, pos0, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps,
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_attention failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return out
+
+
+def k_attention_decode(qkv, lens, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, policy=-1, device=0):
+    """q3tts_k_attention_decode: qkv holds the slots' rows back to back (sum(lens) rows); returns (out_f32, out_bf16 bits), both
+    [n_slots][n_head * head_dim]: one fused decode launch per output at pos = lens[s] - 1 over a cache of n_ctx positions."""
+    lib = _abi.load_library()
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    assert qkv.shape[0] == int(ln.sum())
+    out = np.zeros((ln.size, n_head * head_dim), dtype=np.float32)
+    ob = np.zeros((ln.size, n_head * head_dim), dtype=np.uint16)
+    qn = np.ascontiguousarray(q_norm_w, dtype=np.float32)
+    kn = np.ascontiguousarray(k_norm_w, dtype=np.float32)
+    sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
+    rc = lib.q3tts_k_attention_decode(device, _ptr(qkv, f32p), ln.size, _ptr(ln, i32p), n_ctx, n_head, n_kv_head, head_dim, _ptr(qn, f32p),
+                                      _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, _ptr(out, f32p),
+                                      ob.ctypes.data_as(C.POINTER(C.c_uint16)))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_attention_decode failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return out, ob
 
 
 def k_sample(logits, limit, temperature, top_k, top_p, r=None, device=0):

@@ -19,6 +19,13 @@ ORACLE_LIB = os.path.join(ORACLE_DIR, "libq3oracle.so")
 f32p, i32p, u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
 _lib = None
 
+# The vocoder transformer's rows on the device against the bf16-input oracle (tests/test_long_gpu.py): per frame, RMS(device - oracle) /
+# RMS(oracle) after the final norm. Measured on MI355X over 160 frames: <= 2.3e-5 from position 71 on (where the window cuts), 5.9e-5 at
+# frame 0 (the noise floor of bf16 operand roundings that flip with the accumulation order). tests/test_vocoder_family_cpu.py shows that
+# a sliding window off by one moves the oracle's own rows by >= 10x VOC_LATENT_TOL at every position past the window.
+VOC_LATENT_TOL = 4e-5         # frames >= 71
+VOC_LATENT_TOL_EARLY = 1e-4   # frames < 71
+
 
 def build():
     subprocess.check_call(["make", "-C", ORACLE_DIR, "libq3oracle.so"], stdout=subprocess.DEVNULL)
@@ -52,6 +59,8 @@ def lib():
     L.q3o_attention.argtypes = [f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float,
                                 C.c_float, i32p, f32p]
     L.q3o_attention.restype = None
+    L.q3o_attention_last.argtypes = [f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float, C.c_float, i32p, f32p]
+    L.q3o_attention_last.restype = None
     L.q3o_sample.argtypes = [f32p, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_float]
     L.q3o_sample.restype = C.c_int32
     L.q3o_rng_f32.argtypes = [C.c_uint64, C.c_int32, f32p]

@@ -16,6 +16,7 @@ looks one latent step ahead: the reference's look-ahead buffer, V4) where the st
 Also reported: how far the bf16-operand arithmetic (what the device computes) is from f32 on this model. CPU only.
 """
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -23,21 +24,19 @@ import pytest
 torch = pytest.importorskip("torch")
 
 
-def test_vocoder_oracle_equals_family_code2wav(oracle):
-    O = oracle
-    from q3tts import _abi
+def _family_config(vc):
     from transformers.models.qwen3_omni_moe.configuration_qwen3_omni_moe import Qwen3OmniMoeCode2WavConfig
-    from transformers.models.qwen3_omni_moe.modeling_qwen3_omni_moe import Qwen3OmniMoeCode2Wav
-    vc = _abi.tiny_config().vocoder
-    d, H, F, W, dd = vc.latent_dim, vc.n_head * vc.head_dim, vc.d_ffn, vc.sliding_window, vc.decoder_dim
     rates = [vc.dec_rates[i] for i in range(vc.n_dec_blocks)]
     ups = [vc.upsample_ratios[i] for i in range(vc.n_upsample)]
-    cfg = Qwen3OmniMoeCode2WavConfig(codebook_size=vc.codebook_size, hidden_size=d, max_position_embeddings=8000, num_attention_heads=vc.n_head,
-                                     num_key_value_heads=vc.n_head, attention_bias=False, sliding_window=W, intermediate_size=F, hidden_act="silu",
-                                     layer_scale_initial_scale=vc.layer_scale_init, rms_norm_eps=vc.rms_eps, num_hidden_layers=vc.n_layer,
-                                     num_quantizers=vc.n_codebooks, upsample_rates=rates, upsampling_ratios=ups, decoder_dim=dd,
-                                     rope_parameters={"rope_type": "default", "rope_theta": float(vc.rope_theta)}, attn_implementation="eager")
-    net = Qwen3OmniMoeCode2Wav(cfg).eval().float()
+    return Qwen3OmniMoeCode2WavConfig(codebook_size=vc.codebook_size, hidden_size=vc.latent_dim, max_position_embeddings=8000,
+                                      num_attention_heads=vc.n_head, num_key_value_heads=vc.n_head, attention_bias=False,
+                                      sliding_window=vc.sliding_window, intermediate_size=vc.d_ffn, hidden_act="silu",
+                                      layer_scale_initial_scale=vc.layer_scale_init, rms_norm_eps=vc.rms_eps, num_hidden_layers=vc.n_layer,
+                                      num_quantizers=vc.n_codebooks, upsample_rates=rates, upsampling_ratios=ups, decoder_dim=vc.decoder_dim,
+                                      rope_parameters={"rope_type": "default", "rope_theta": float(vc.rope_theta)}, attn_implementation="eager")
+
+
+def _oracle_lib(O):
     L = O.lib()
     L.q3o_vocoder_mat.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_void_p]
     L.q3o_vocoder_mat.restype = None
@@ -45,7 +44,25 @@ def test_vocoder_oracle_equals_family_code2wav(oracle):
     L.q3o_vocoder_vec.restype = None
     L.q3o_vocoder_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     L.q3o_vocoder_stage.restype = C.c_int32
-    v = L.q3o_vocoder_create(C.byref(vc), 0, 4)
+    return L
+
+
+def _oracle_stage(L, v, codes, k, shape):
+    out = np.zeros(shape, dtype=np.float32)
+    L.q3o_vocoder_stage(v, np.ascontiguousarray(codes, dtype=np.int32).ctypes.data, codes.shape[0], k, out.ctypes.data)
+    return out
+
+
+def _load_family(L, v, vc, whole=True):
+    """The family module with the oracle `v`'s seeded synthetic weights: the whole Qwen3OmniMoeCode2Wav (whole=True) or only its
+    sliding-window transformer (Qwen3OmniMoeCode2WavTransformerModel, what Code2Wav calls pre_transformer)."""
+    from transformers.models.qwen3_omni_moe.modeling_qwen3_omni_moe import Qwen3OmniMoeCode2Wav, Qwen3OmniMoeCode2WavTransformerModel
+    cfg = _family_config(vc)
+    d, H, F, dd = vc.latent_dim, vc.n_head * vc.head_dim, vc.d_ffn, vc.decoder_dim
+    rates = [vc.dec_rates[i] for i in range(vc.n_dec_blocks)]
+    ups = [vc.upsample_ratios[i] for i in range(vc.n_upsample)]
+    net = (Qwen3OmniMoeCode2Wav(cfg) if whole else Qwen3OmniMoeCode2WavTransformerModel(cfg)).eval().float()
+    pre = net.pre_transformer if whole else net
 
     def mat(comp, which, rows, cols, fan_in, gain=1.0):
         out = np.zeros((rows, cols), dtype=np.float32)
@@ -60,57 +77,77 @@ def test_vocoder_oracle_equals_family_code2wav(oracle):
 
     def conv_w(comp, ww, ntap, cin, nout, gain=1.0):  # oracle [tap][n][ci] -> Conv1d [n][ci][tap]
         return mat(comp, ww, ntap * nout, cin, ntap * cin, gain).reshape(ntap, nout, cin).transpose(1, 2, 0)
-    try:
-        with torch.no_grad():
-            for l, blk in enumerate(net.pre_transformer.layers):
-                comp = 40 + l
-                blk.input_layernorm.weight.copy_(T_(vec(comp, 2, d, 1.0, 0.05))); blk.post_attention_layernorm.weight.copy_(T_(vec(comp, 8, d, 1.0, 0.05)))
-                blk.self_attn_layer_scale.scale.copy_(T_(vec(comp, 7, d, vc.layer_scale_init, 0.1 * vc.layer_scale_init)))
-                blk.mlp_layer_scale.scale.copy_(T_(vec(comp, 12, d, vc.layer_scale_init, 0.1 * vc.layer_scale_init)))
-                blk.self_attn.q_proj.weight.copy_(T_(mat(comp, 3, H, d, d))); blk.self_attn.k_proj.weight.copy_(T_(mat(comp, 4, H, d, d)))
-                blk.self_attn.v_proj.weight.copy_(T_(mat(comp, 5, H, d, d))); blk.self_attn.o_proj.weight.copy_(T_(mat(comp, 6, d, H, H)))
-                blk.mlp.gate_proj.weight.copy_(T_(mat(comp, 9, F, d, d))); blk.mlp.up_proj.weight.copy_(T_(mat(comp, 10, F, d, d)))
-                blk.mlp.down_proj.weight.copy_(T_(mat(comp, 11, d, F, F)))
-            net.pre_transformer.norm.weight.copy_(T_(vec(60, 0, d, 1.0, 0.05)))
-            for u, (ct, cnx) in enumerate(net.upsample):
-                comp, r = 64 + u, ups[u]
-                Wc = mat(comp, 0, r * d, d, d).reshape(r, d, d)                      # [j][o][i]
-                ct.conv.weight.copy_(T_(Wc.transpose(2, 1, 0)))                      # ConvTranspose1d [in][out][k]
-                ct.conv.bias.copy_(T_(vec(comp, 1, d, 0.0, 0.02)))
-                cnx.dwconv.conv.weight.copy_(T_(vec(comp, 13, 7 * d, 0.0, 0.3).reshape(7, d).T[:, None, :]))
-                cnx.dwconv.conv.bias.copy_(T_(vec(comp, 14, d, 0.0, 0.02)))
-                cnx.norm.weight.copy_(T_(vec(comp, 15, d, 1.0, 0.05))); cnx.norm.bias.copy_(T_(vec(comp, 16, d, 0.0, 0.02)))
-                cnx.pwconv1.weight.copy_(T_(mat(comp, 17, 4 * d, d, d))); cnx.pwconv1.bias.copy_(T_(vec(comp, 18, 4 * d, 0.0, 0.02)))
-                cnx.pwconv2.weight.copy_(T_(mat(comp, 19, d, 4 * d, 4 * d))); cnx.pwconv2.bias.copy_(T_(vec(comp, 20, d, 0.0, 0.02)))
-                cnx.gamma.copy_(T_(vec(comp, 21, d, 0.1, 0.01)))
-            dec = net.decoder
-            dec[0].conv.weight.copy_(T_(conv_w(72, 0, 7, d, dd))); dec[0].conv.bias.copy_(T_(vec(72, 1, dd, 0.0, 0.02)))
-            ch = dd
-            for b in range(vc.n_dec_blocks):
-                blk, comp, r, co = dec[1 + b].block, 80 + 4 * b, rates[b], ch // 2
-                blk[0].alpha.copy_(T_(vec(comp, 22, ch, 0.0, 0.1))); blk[0].beta.copy_(T_(vec(comp, 23, ch, 0.0, 0.1)))
-                Wt = mat(comp, 0, 2 * r * co, ch, 2 * ch).reshape(2, r, co, ch)     # [tap][j][o][i]; tap 1 = the current latent step
-                wt = np.zeros((ch, co, 2 * r), dtype=np.float32)
-                wt[:, :, :r] = Wt[1].transpose(2, 1, 0); wt[:, :, r:] = Wt[0].transpose(2, 1, 0)
-                blk[1].conv.weight.copy_(T_(wt)); blk[1].conv.bias.copy_(T_(vec(comp, 1, co, 0.0, 0.02)))
-                for u_, dil in enumerate((1, 3, 9)):
-                    ru, rc = blk[2 + u_], comp + 1 + u_
-                    ru.act1.alpha.copy_(T_(vec(rc, 22, co, 0.0, 0.1))); ru.act1.beta.copy_(T_(vec(rc, 23, co, 0.0, 0.1)))
-                    ru.conv1.conv.weight.copy_(T_(conv_w(rc, 0, 7, co, co, 0.5))); ru.conv1.conv.bias.copy_(T_(vec(rc, 1, co, 0.0, 0.02)))
-                    ru.act2.alpha.copy_(T_(vec(rc, 26, co, 0.0, 0.1))); ru.act2.beta.copy_(T_(vec(rc, 27, co, 0.0, 0.1)))
-                    ru.conv2.conv.weight.copy_(T_(conv_w(rc, 24, 1, co, co, 0.5))); ru.conv2.conv.bias.copy_(T_(vec(rc, 25, co, 0.0, 0.02)))
-                ch = co
-            dec[-2].alpha.copy_(T_(vec(120, 22, ch, 0.0, 0.1))); dec[-2].beta.copy_(T_(vec(120, 23, ch, 0.0, 0.1)))
-            dec[-1].conv.weight.copy_(T_(conv_w(120, 0, 7, ch, 1, 0.1))); dec[-1].conv.bias.copy_(T_(vec(120, 1, 1, 0.0, 0.02)))
+    with torch.no_grad():
+        for l, blk in enumerate(pre.layers):
+            comp = 40 + l
+            blk.input_layernorm.weight.copy_(T_(vec(comp, 2, d, 1.0, 0.05))); blk.post_attention_layernorm.weight.copy_(T_(vec(comp, 8, d, 1.0, 0.05)))
+            blk.self_attn_layer_scale.scale.copy_(T_(vec(comp, 7, d, vc.layer_scale_init, 0.1 * vc.layer_scale_init)))
+            blk.mlp_layer_scale.scale.copy_(T_(vec(comp, 12, d, vc.layer_scale_init, 0.1 * vc.layer_scale_init)))
+            blk.self_attn.q_proj.weight.copy_(T_(mat(comp, 3, H, d, d))); blk.self_attn.k_proj.weight.copy_(T_(mat(comp, 4, H, d, d)))
+            blk.self_attn.v_proj.weight.copy_(T_(mat(comp, 5, H, d, d))); blk.self_attn.o_proj.weight.copy_(T_(mat(comp, 6, d, H, H)))
+            blk.mlp.gate_proj.weight.copy_(T_(mat(comp, 9, F, d, d))); blk.mlp.up_proj.weight.copy_(T_(mat(comp, 10, F, d, d)))
+            blk.mlp.down_proj.weight.copy_(T_(mat(comp, 11, d, F, F)))
+        pre.norm.weight.copy_(T_(vec(60, 0, d, 1.0, 0.05)))
+        if not whole:
+            return net
+        for u, (ct, cnx) in enumerate(net.upsample):
+            comp, r = 64 + u, ups[u]
+            Wc = mat(comp, 0, r * d, d, d).reshape(r, d, d)                      # [j][o][i]
+            ct.conv.weight.copy_(T_(Wc.transpose(2, 1, 0)))                      # ConvTranspose1d [in][out][k]
+            ct.conv.bias.copy_(T_(vec(comp, 1, d, 0.0, 0.02)))
+            cnx.dwconv.conv.weight.copy_(T_(vec(comp, 13, 7 * d, 0.0, 0.3).reshape(7, d).T[:, None, :]))
+            cnx.dwconv.conv.bias.copy_(T_(vec(comp, 14, d, 0.0, 0.02)))
+            cnx.norm.weight.copy_(T_(vec(comp, 15, d, 1.0, 0.05))); cnx.norm.bias.copy_(T_(vec(comp, 16, d, 0.0, 0.02)))
+            cnx.pwconv1.weight.copy_(T_(mat(comp, 17, 4 * d, d, d))); cnx.pwconv1.bias.copy_(T_(vec(comp, 18, 4 * d, 0.0, 0.02)))
+            cnx.pwconv2.weight.copy_(T_(mat(comp, 19, d, 4 * d, 4 * d))); cnx.pwconv2.bias.copy_(T_(vec(comp, 20, d, 0.0, 0.02)))
+            cnx.gamma.copy_(T_(vec(comp, 21, d, 0.1, 0.01)))
+        dec = net.decoder
+        dec[0].conv.weight.copy_(T_(conv_w(72, 0, 7, d, dd))); dec[0].conv.bias.copy_(T_(vec(72, 1, dd, 0.0, 0.02)))
+        ch = dd
+        for b in range(vc.n_dec_blocks):
+            blk, comp, r, co = dec[1 + b].block, 80 + 4 * b, rates[b], ch // 2
+            blk[0].alpha.copy_(T_(vec(comp, 22, ch, 0.0, 0.1))); blk[0].beta.copy_(T_(vec(comp, 23, ch, 0.0, 0.1)))
+            Wt = mat(comp, 0, 2 * r * co, ch, 2 * ch).reshape(2, r, co, ch)     # [tap][j][o][i]; tap 1 = the current latent step
+            wt = np.zeros((ch, co, 2 * r), dtype=np.float32)
+            wt[:, :, :r] = Wt[1].transpose(2, 1, 0); wt[:, :, r:] = Wt[0].transpose(2, 1, 0)
+            blk[1].conv.weight.copy_(T_(wt)); blk[1].conv.bias.copy_(T_(vec(comp, 1, co, 0.0, 0.02)))
+            for u_, dil in enumerate((1, 3, 9)):
+                ru, rc = blk[2 + u_], comp + 1 + u_
+                ru.act1.alpha.copy_(T_(vec(rc, 22, co, 0.0, 0.1))); ru.act1.beta.copy_(T_(vec(rc, 23, co, 0.0, 0.1)))
+                ru.conv1.conv.weight.copy_(T_(conv_w(rc, 0, 7, co, co, 0.5))); ru.conv1.conv.bias.copy_(T_(vec(rc, 1, co, 0.0, 0.02)))
+                ru.act2.alpha.copy_(T_(vec(rc, 26, co, 0.0, 0.1))); ru.act2.beta.copy_(T_(vec(rc, 27, co, 0.0, 0.1)))
+                ru.conv2.conv.weight.copy_(T_(conv_w(rc, 24, 1, co, co, 0.5))); ru.conv2.conv.bias.copy_(T_(vec(rc, 25, co, 0.0, 0.02)))
+            ch = co
+        dec[-2].alpha.copy_(T_(vec(120, 22, ch, 0.0, 0.1))); dec[-2].beta.copy_(T_(vec(120, 23, ch, 0.0, 0.1)))
+        dec[-1].conv.weight.copy_(T_(conv_w(120, 0, 7, ch, 1, 0.1))); dec[-1].conv.bias.copy_(T_(vec(120, 1, 1, 0.0, 0.02)))
+    return net
 
-        n_frames = 10
+
+def test_vocoder_oracle_equals_family_code2wav(oracle):
+    _whole_chain_vs_family(oracle, 10)
+
+
+def test_tiny_vocoder_whole_chain_past_the_window(oracle):
+    """The whole chain at the tiny shape over 64 frames: 56 positions past its 8-frame window (the 10-frame test sees two)."""
+    _whole_chain_vs_family(oracle, 64)
+
+
+def _whole_chain_vs_family(oracle, n_frames):
+    O = oracle
+    from q3tts import _abi
+    vc = _abi.tiny_config().vocoder
+    d = vc.latent_dim
+    rates = [vc.dec_rates[i] for i in range(vc.n_dec_blocks)]
+    ups = [vc.upsample_ratios[i] for i in range(vc.n_upsample)]
+    L = _oracle_lib(O)
+    v = L.q3o_vocoder_create(C.byref(vc), 0, 4)
+    T_ = lambda a: torch.from_numpy(np.ascontiguousarray(a))
+    try:
+        net = _load_family(L, v, vc)
         codes = np.random.default_rng(7).integers(0, vc.codebook_size, size=(n_frames, 16)).astype(np.int32)
         up_total = int(np.prod(ups)); spf = up_total * int(np.prod(rates))
 
-        def stage(k, shape):
-            out = np.zeros(shape, dtype=np.float32)
-            L.q3o_vocoder_stage(v, codes.ctypes.data, n_frames, k, out.ctypes.data)
-            return out
+        stage = lambda k, shape: _oracle_stage(L, v, codes, k, shape)
         L.q3o_vocoder_set_arith(v, 1)
         try:
             s1, s2 = stage(1, (n_frames, d)), stage(2, (n_frames, d))
@@ -140,7 +177,7 @@ def test_vocoder_oracle_equals_family_code2wav(oracle):
         a, b = s4[start + shift: shift + wav.shape[0]], wav[start:]
         assert a.size > 4000 and rel(a, b) <= 1e-4, rel(a, b)
         e_bf16 = float(np.sqrt(np.mean((s4_bf16 - s4) ** 2)))
-        print(f"vocoder oracle vs transformers Code2Wav (f32): transformer {rel(s2, h2):.1e}, up-sampling {rel(s3, hid[0].T.numpy()):.1e}, decoder PCM {rel(a, b):.1e}; "
+        print(f"vocoder oracle vs transformers Code2Wav (f32), {n_frames} frames: transformer {rel(s2, h2):.1e}, up-sampling {rel(s3, hid[0].T.numpy()):.1e}, decoder PCM {rel(a, b):.1e}; "
               f"bf16-operand arithmetic vs f32 on this model: PCM RMS {e_bf16:.2e} (signal RMS {float(np.sqrt(np.mean(s4 ** 2))):.2f})")
     finally:
         L.q3o_vocoder_destroy(v)
@@ -186,3 +223,60 @@ def test_full_shape_pcm_error_budget_of_the_bf16_operand_rounding(oracle):
     assert max(errs) <= 1.6e-3 and min(errs) >= 2e-4   # no stage dominates, none is free
     assert float(np.sqrt(np.sum(np.square(errs[5:])))) <= 1.2e-3   # the HBM-bound tail holds the smaller part
     assert 2.0e-3 <= total <= 3.0e-3
+
+
+def test_full_shape_transformer_past_the_window_vs_float64_family(oracle):
+    """The f32 oracle's sliding-window transformer (stage 2) at the FULL shape (d 1024, 8 layers x 16 heads x 64, window 72) over 224
+    frames (past 2 x 76, the device's ring) against transformers' pre_transformer run in float64 on the same rows. Bound: 2e-5 of the
+    largest element: 5e-6 (measured 6.1e-7 here)."""
+    from q3tts import _abi
+    vc = _abi.full_config_py().vocoder
+    n = 224
+    L = _oracle_lib(oracle)
+    v = L.q3o_vocoder_create(C.byref(vc), 0, min(16, os.cpu_count() or 4))
+    try:
+        codes = np.random.default_rng(224).integers(0, vc.codebook_size, size=(n, 16)).astype(np.int32)
+        L.q3o_vocoder_set_arith(v, 1)
+        try:
+            s1, s2 = _oracle_stage(L, v, codes, 1, (n, vc.latent_dim)), _oracle_stage(L, v, codes, 2, (n, vc.latent_dim))
+        finally:
+            L.q3o_vocoder_set_arith(v, 0)
+        net = _load_family(L, v, vc, whole=False).double()
+    finally:
+        L.q3o_vocoder_destroy(v)
+    with torch.no_grad():
+        h = net(inputs_embeds=torch.from_numpy(s1.astype(np.float64))[None]).last_hidden_state[0].numpy()
+    err = np.abs(s2 - h).max(axis=1) / np.abs(h).max()
+    print(f"full-shape transformer, {n} frames: f32 oracle vs float64 family, worst {err.max():.1e} (frame {int(err.argmax())}); "
+          f"frames < 72 {err[:72].max():.1e}, frames >= 152 {err[152:].max():.1e}")
+    assert err.max() <= 5e-6, (int(err.argmax()), float(err.max()))
+
+
+def test_full_shape_latent_check_sees_a_window_off_by_one(oracle):
+    """Sensitivity of tests/test_long_gpu.py's latent check: oracles whose window is 71 or 73 instead of 72 (what an off-by-one in the
+    device's ring or window arithmetic would compute) give stage 2 rows equal to W = 72 bit for bit where the window has not cut
+    anything yet (positions < 71), and from the first position where the windows differ (71 for W = 71; 72 for W = 73, whose window
+    still holds key 0 there) every frame moves by >= 10 x VOC_LATENT_TOL in the device check's metric (measured over 100 frames: >= 4.35e-4, 10.9x; about
+    19x the device's own worst error there, 2.3e-5). A 20x margin over the bound is out of reach: the device's noise floor of
+    bf16 operand roundings (2-6e-5) is within 20x of the change a one-key window difference makes (4.4e-4)."""
+    from q3tts import _abi
+    import _oracle
+    n = 100
+    L = _oracle_lib(oracle)
+    codes = np.random.default_rng(100).integers(0, 2048, size=(n, 16)).astype(np.int32)
+    rows = {}
+    for W in (72, 71, 73):
+        vc = _abi.full_config_py().vocoder
+        vc.sliding_window = W
+        v = L.q3o_vocoder_create(C.byref(vc), 0, min(16, os.cpu_count() or 4))
+        try:
+            rows[W] = _oracle_stage(L, v, codes, 2, (n, vc.latent_dim))
+        finally:
+            L.q3o_vocoder_destroy(v)
+    ref = rows[72].astype(np.float64)
+    for W, first in ((71, 71), (73, 72)):
+        assert np.array_equal(rows[W][:first].view(np.uint32), rows[72][:first].view(np.uint32)), W
+        d = np.sqrt(np.mean((rows[W][first:] - ref[first:]) ** 2, axis=1) / np.mean(ref[first:] ** 2, axis=1))
+        print(f"window {W} vs 72: equal bits at positions < {first}; from {first} on the smallest per-frame change is {d.min():.2e} "
+              f"= {d.min() / _oracle.VOC_LATENT_TOL:.0f} x VOC_LATENT_TOL")
+        assert d.min() >= 10 * _oracle.VOC_LATENT_TOL, (W, int(d.argmin()) + first, float(d.min()))
