@@ -155,6 +155,7 @@ int q3tts_set_device_pcm(q3tts_engine* e, int32_t enable);
 int q3tts_get_device_pcm(q3tts_engine* e, float** base, int64_t* stride_samples, int32_t* n_rows);
 
 /* ---- generation (run_inference_stream: src/tts/engine.rs:445-656) ------------------------------ */
+typedef struct q3tts_prefix q3tts_prefix;  /* a voice prefix: see "voice prefixes" below */
 typedef struct q3tts_request {
     const float* prompt_embd; int32_t n_tok; /* [n_tok][d_embed] f32 host rows (PromptData.embd), or NULL ... */
     const q3tts_prompt_desc* prompt;         /* ... to build from ids on the device */
@@ -164,6 +165,8 @@ typedef struct q3tts_request {
     int32_t min_frames;   /* bench control: EOS logit masked while n_frames < min_frames (0 = reference) */
     int32_t force_eos_at; /* bench control: EOS forced at this step (<0 = off) */
     int32_t want_pcm;     /* 0: codec ids only; 1: PCM in host memory; 2: PCM kept on the device only (q3tts_set_device_pcm) */
+    const q3tts_prefix* prefix; /* NULL: the prompt is prompt_embd / prompt alone. Else the prompt is the prefix's rows followed by this
+                                 * request's own rows: prompt_embd / n_tok, or `prompt` as a text-only desc (see "voice prefixes") */
 } q3tts_request;
 
 typedef struct q3tts_result {
@@ -189,6 +192,30 @@ int q3tts_stream_begin(q3tts_engine* e, const q3tts_request* req, q3tts_stream**
 /* Blocks until the next chunk; *chunk is owned by the stream and valid until the next poll/end. */
 int q3tts_stream_poll(q3tts_stream* s, const float** chunk, int32_t* n_samples, int32_t* is_final);
 int q3tts_stream_end(q3tts_stream* s, q3tts_result* out_codes_optional);
+
+/* ---- voice prefixes: prefill a voice prompt once, reuse its Talker K/V ----------------------------------------------------
+ * A prompt is a voice part (the optional instruct block, the role block, the control block, the speaker row and, for a cloned voice,
+ * BOS ref_text EOS, the codec-BOS row, one row per reference frame and a PAD row) followed by a text part of n_text + 3 rows (BOS, the
+ * text, EOS, the activation row). Requests in the same voice, language and instruct share the voice part. A prefix holds the Talker's
+ * K/V of such a part on the device; a request that names it starts from a copy of them instead of running those rows again. The
+ * reference has no counterpart (it serves one request at a time and rebuilds the whole prompt each call, src/tts/engine.rs:390-466).
+ *
+ * q3tts_prefix_create: exactly one of p (its voice fields; n_text must be 0) or embd / n_tok (host rows [n_tok][d_embed]) is given;
+ * 1 <= rows < n_ctx. Refused (Q3TTS_ERR_STATE) while a session is open. Destroy every prefix before its engine.
+ * A request with prefix != NULL:
+ *  - its prompt_embd / n_tok are the rows after the prefix; otherwise `prompt` builds only the text part: text_ids are used and every
+ *    voice field must be in its None state (instruct_ids NULL, lang_id < 0, spk_id < 0, spk_emb NULL, ref_codes NULL, ref_text_ids NULL),
+ *    else Q3TTS_ERR_INVALID with a message naming the field;
+ *  - it needs P + n + max_steps <= n_ctx (P prefix rows, n own rows), else it fails by itself as any request does;
+ *  - a prefix made by another engine is Q3TTS_ERR_INVALID; q3tts_node_generate_batch refuses requests with a prefix (Q3TTS_ERR_INVALID).
+ * Contract: with a prefix made from voice desc V and a request with text T, the results (codes, hit_eos, PCM, streamed chunks) are
+ * bit-identical to those of the same request without a prefix whose desc is V with text T — in every talker_q8_0 mode, through
+ * q3tts_generate, q3tts_generate_batch, q3tts_stream_* and sessions. (Every row's arithmetic depends only on that row and the K/V at its own
+ * and earlier positions, in an order that does not depend on the batch: DESIGN.md §4.) A session keeps the pointer, not a copy: the prefix
+ * outlives it because q3tts_prefix_destroy is refused while a session is open. */
+int q3tts_prefix_create(q3tts_engine* e, const q3tts_prompt_desc* p, const float* embd, int32_t n_tok, q3tts_prefix** out);
+int32_t q3tts_prefix_rows(const q3tts_prefix* x);
+int q3tts_prefix_destroy(q3tts_prefix* x);   /* Q3TTS_ERR_STATE while a session is open on its engine */
 
 /* ---- sessions: continuous batching with per-request streaming ------------------------------------------------------------
  * The serving form of run_inference_stream (src/tts/engine.rs:445-656) for many utterances at once: requests are submitted into a
@@ -389,6 +416,9 @@ int q3tts_k_sample(int32_t device, const float* logits, int32_t n, int32_t ld, i
                    int32_t top_k, float top_p, const float* r_uniform, int32_t* out_ids);
 /* Talker forward over a prompt: hidden[d] (post final norm) and logits[t_vocab] of the LAST row */
 int q3tts_k_talker_prefill(q3tts_engine* e, const float* embd, int32_t n_tok, float* hidden_out, float* logits_out);
+/* The same behind a voice prefix: the prompt is the prefix's rows followed by embd [n_tok][d_embed] */
+int q3tts_k_talker_prefill_prefix(q3tts_engine* e, const q3tts_prefix* prefix, const float* embd, int32_t n_tok, float* hidden_out,
+                                  float* logits_out);
 /* Vocoder: codes [n_frames][n_codebooks] -> pcm; chunk_frames frames per streaming call (0 = one call) */
 int q3tts_k_vocoder(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, float* pcm_out,
                     int32_t* n_samples_out);

@@ -86,7 +86,7 @@ struct q3tts_engine {
     uint16_t* xbp = nullptr; float* sspp = nullptr;  // norm inputs of the prefill rows
     uint16_t* ascp = nullptr; int rt16p = 0;         // W8A8: block scales of xbp
     int *pf_pos = nullptr, *pf_slot = nullptr;
-    int* pf_seg = nullptr;              // the prefill launch's rows as per-slot runs {first row, n, slot} (device, 3 ints each): admit_group hands it to run_layers
+    int* pf_seg = nullptr;              // the prefill launch's rows as per-slot runs {first row, n, slot, first position} (device, 4 ints each): admit_group hands it to run_layers
     Q3PromptRow* prow_dev = nullptr; int prow_cap = 0;
     float* spk_dev = nullptr; int* refcodes_dev = nullptr;
     // sampler defaults (SamplerConfig::default: src/tts/engine.rs:25-34)
@@ -110,6 +110,14 @@ struct q3tts_engine {
     float* first_chunk_host = nullptr;  // pinned landing buffer of the first 4-frame PCM chunk (first-chunk latency)
     std::atomic<q3tts_session*> session{nullptr};  // an open session owns the engine (q3_session.hip)
     std::mutex err_mu;                  // err is written by the session worker too
+};
+
+// A voice prefix (include/q3tts.h, "voice prefixes"): the Talker's K/V of a prompt's first P rows, laid out as one slot's cache of
+// np = ceil(P / 64) * 64 positions — k / v [L][Hkv][np * hd] bf16 — and copied into a slot by k_kv_prefix at admission.
+struct q3tts_prefix {
+    q3tts_engine* e = nullptr;          // the engine that made it (and whose slots it may enter)
+    int P = 0, np = 0;
+    uint16_t *k = nullptr, *v = nullptr;
 };
 
 // helpers shared with q3_vocoder.hip

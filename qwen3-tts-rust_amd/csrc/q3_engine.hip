@@ -311,7 +311,7 @@ static int alloc_scratch(q3tts_engine* e, Q3Scratch& sc, int rows, int nqkv, int
 // Returns the number of launches the GEMM launcher refused (a shape it cannot run: stale activations would follow silently).
 static int run_layers(q3tts_engine* e, Q3Tfm& t, float* x, uint16_t* xb, float* ssp, int rows, const int* row_pos, const int* row_slot, Q3Scratch& sc,
                        hipStream_t s, bool one_row_per_slot = false, hipEvent_t* probe = nullptr, int slot_mod = 0, int pos_const = 0,
-                       const int* seg = nullptr, int n_seg = 0, int seg_max_n = 0, uint16_t* xscale = nullptr, int x_rt16 = 0) {
+                       const int* seg = nullptr, int n_seg = 0, int seg_max_n = 0, int seg_max_t = 0, uint16_t* xscale = nullptr, int x_rt16 = 0) {
     // W8A8 (t.a8: the Talker with talker_q8_0 = 2): xb / sc.att / sc.h hold Q8_0 blocks (int8 quants + the f16 scales xscale / sc.asc_att /
     // sc.asc_h) and every GEMM runs q3_launch_bgemm8: ggml's Q8_0 x Q8_0 arithmetic
     auto gemm = [&](Q3BGemm& g) { return t.a8 ? q3_launch_bgemm8(g, s) : q3_launch_bgemm(g, s); };
@@ -341,7 +341,7 @@ static int run_layers(q3tts_engine* e, Q3Tfm& t, float* x, uint16_t* xb, float* 
         at.kc = qp.kc; at.vc = qp.vc; at.n_ctx = t.n_ctx; at.row_pos = row_pos; at.row_slot = row_slot;
         at.fused = pair ? 2 : (fused ? 1 : 0); at.prep = qp; at.out_bf16 = 1; at.slot_mod = slot_mod; at.pos_const = pos_const;
         if (t.a8) { at.out_bf16 = 2; at.out_scale = sc.asc_att; at.out_rt16 = sc.rt16; }
-        if (!fused && !pair && n_seg > 0) { at.seg = seg; at.n_seg = n_seg; at.seg_max_n = seg_max_n; }  // prefill of whole prompts (admit_group): the launch's rows as per-slot runs
+        if (!fused && !pair && n_seg > 0) { at.seg = seg; at.n_seg = n_seg; at.seg_max_n = seg_max_n; at.seg_max_t = seg_max_t; }  // prefill of whole prompts (admit_group): the launch's rows as per-slot runs
         if (pk == 2) hipEventRecord(probe[0], s);
         q3_launch_attend(at, s);
         if (pk == 2) hipEventRecord(probe[1], s);
@@ -415,7 +415,7 @@ static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
     pred_next(ncb - 1);
     hipEvent_t* pt = nullptr;  // probe mode 2: the Talker's layer-0 gate/up GEMM (the largest GEMM of the frame step)
     if (e->probe == 2 && B == L.nb && e->probe_i + 2 <= 8) { pt = &e->probe_ev[e->probe_i]; e->probe_i += 2; }
-    bad += run_layers(e, e->T, L.xT, L.xbT, L.sspT, B, L.row_pos_t, L.slot_id, L.sc, s, true, pt, 0, 0, nullptr, 0, 0, L.ascT, L.rt16T);
+    bad += run_layers(e, e->T, L.xT, L.xbT, L.sspT, B, L.row_pos_t, L.slot_id, L.sc, s, true, pt, 0, 0, nullptr, 0, 0, 0, L.ascT, L.rt16T);
     Q3BGemm g{}; g.w_once = 1; g.a = L.xbT; g.B = B; g.w = e->T.head; g.wscale = e->T.q8 ? e->T.shead : nullptr; g.K = m.t_d_model; g.N = m.t_vocab;
     g.ssp = L.sspT; g.ld_ssp = m.t_d_model / 16; g.ntiles = m.t_d_model / 16; g.d_norm = m.t_d_model; g.eps = eps;
     g.epi = Q3_EPI_STORE; g.y = L.logits; g.ldy = m.t_vocab;
@@ -629,7 +629,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     TRYC(dalloc(e, &e->xbp, (((size_t)cfg->n_ctx + 15) & ~(size_t)15) * m.t_d_model)); TRYC(dalloc(e, &e->sspp, (size_t)cfg->n_ctx * (m.t_d_model / 16)));
     e->rt16p = (cfg->n_ctx + 15) / 16;
     if (e->T.a8) TRYC(dalloc(e, &e->ascp, (size_t)e->rt16p * 16 * (m.t_d_model / 32)));
-    TRYC(dalloc(e, &e->pf_pos, (size_t)cfg->n_ctx)); TRYC(dalloc(e, &e->pf_slot, (size_t)cfg->n_ctx)); TRYC(dalloc(e, &e->pf_seg, (size_t)3 * cfg->max_batch));
+    TRYC(dalloc(e, &e->pf_pos, (size_t)cfg->n_ctx)); TRYC(dalloc(e, &e->pf_slot, (size_t)cfg->n_ctx)); TRYC(dalloc(e, &e->pf_seg, (size_t)4 * cfg->max_batch));
     { std::vector<int> pp(cfg->n_ctx); for (int i = 0; i < cfg->n_ctx; ++i) pp[i] = i;
       HIPC(hipMemcpyAsync(e->pf_pos, pp.data(), pp.size() * 4, hipMemcpyHostToDevice, s)); HIPC(hipStreamSynchronize(s)); }
     e->prow_cap = cfg->n_ctx;
@@ -743,38 +743,51 @@ extern "C" int q3tts_get_device_pcm(q3tts_engine* e, float** base, int64_t* stri
 enum { PAD = 2148, BOS = 2149, THINK = 2154, NOTHINK = 2155, THINK_BOS = 2156, THINK_EOS = 2157, CODEC_BOS_ICL = 2160 };
 enum { BOS_TOKEN = 151672, EOS_TOKEN = 151673 };
 
-static int build_prompt_dev(q3tts_engine* e, const q3tts_prompt_desc* p, float* out, int max_rows, int* n_out) {
+// part: which rows to build. The voice part (instruct, role, control, speaker, clone blocks) comes first and the text part (BOS, text,
+// EOS, activation row) last, so PROMPT_VOICE ++ PROMPT_TEXT is PROMPT_WHOLE row for row (voice prefixes: include/q3tts.h).
+enum { PROMPT_WHOLE = 0, PROMPT_VOICE = 1, PROMPT_TEXT = 2 };
+static int build_prompt_dev(q3tts_engine* e, const q3tts_prompt_desc* p, float* out, int max_rows, int* n_out, int part = PROMPT_WHOLE) {
     const q3tts_model_config& m = e->cfg.model;
     if (!p || (p->n_text > 0 && !p->text_ids)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prompt: text_ids missing");
+    if (part == PROMPT_VOICE && p->n_text != 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: a voice desc has n_text == 0");
+    if (part == PROMPT_TEXT) {  // behind a prefix: the voice is the prefix's
+        const char* f = p->instruct_ids ? "instruct_ids" : p->lang_id >= 0 ? "lang_id" : p->spk_id >= 0 ? "spk_id" : p->spk_emb ? "spk_emb"
+                      : p->ref_codes ? "ref_codes" : p->ref_text_ids ? "ref_text_ids" : nullptr;
+        if (f) return q3_set_err(e, Q3TTS_ERR_INVALID, std::string("prompt: ") + f + " must be None in a request with a prefix (the voice is the prefix's)");
+    }
     const int marker = m.tts_pad_id;
     std::vector<Q3PromptRow> rows;
     int ref_row0 = -1;
     auto T1 = [&](int id) { rows.push_back({1, id, 0, 0}); };
     auto MC = [&](int cid) { rows.push_back({1, marker, 2, cid}); };       // marker + codec0[cid]
     auto TP = [&](int tid) { rows.push_back({1, tid, 2, PAD}); };          // text[tid] + codec0[PAD]
-    if (p->instruct_ids) {  // :153-169
-        T1(151644); T1(872); T1(198);
-        for (int i = 0; i < p->n_instruct; ++i) T1((int)p->instruct_ids[i]);
-        T1(151645); T1(198);
+    if (part != PROMPT_TEXT) {  // the voice part
+        if (p->instruct_ids) {  // :153-169
+            T1(151644); T1(872); T1(198);
+            for (int i = 0; i < p->n_instruct; ++i) T1((int)p->instruct_ids[i]);
+            T1(151645); T1(198);
+        }
+        T1(151644); T1(77091); T1(198);  // :171-175
+        if (p->lang_id >= 0) { MC(THINK); MC(THINK_BOS); MC(p->lang_id); MC(THINK_EOS); }  // :180-191
+        else { MC(NOTHINK); MC(THINK_BOS); MC(THINK_EOS); }                                // :192-204
+        if (p->spk_id >= 0) MC(p->spk_id);                                                 // :207-214
+        else if (p->spk_emb) rows.push_back({1, marker, -1, 0});                           // :215-222
+        if (p->ref_codes) {  // build_clone_prompt :38-106
+            TP(BOS_TOKEN);
+            for (int i = 0; i < p->n_ref_text; ++i) TP((int)p->ref_text_ids[i]);
+            TP(EOS_TOKEN);
+            MC(CODEC_BOS_ICL);
+            ref_row0 = (int)rows.size();
+            for (int i = 0; i < p->n_ref_frames; ++i) rows.push_back({-2, 0, 0, 0});  // filled by the frame kernel
+            MC(PAD);
+        }
     }
-    T1(151644); T1(77091); T1(198);  // :171-175
-    if (p->lang_id >= 0) { MC(THINK); MC(THINK_BOS); MC(p->lang_id); MC(THINK_EOS); }  // :180-191
-    else { MC(NOTHINK); MC(THINK_BOS); MC(THINK_EOS); }                                // :192-204
-    if (p->spk_id >= 0) MC(p->spk_id);                                                 // :207-214
-    else if (p->spk_emb) rows.push_back({1, marker, -1, 0});                           // :215-222
-    if (p->ref_codes) {  // build_clone_prompt :38-106
-        TP(BOS_TOKEN);
-        for (int i = 0; i < p->n_ref_text; ++i) TP((int)p->ref_text_ids[i]);
-        TP(EOS_TOKEN);
-        MC(CODEC_BOS_ICL);
-        ref_row0 = (int)rows.size();
-        for (int i = 0; i < p->n_ref_frames; ++i) rows.push_back({-2, 0, 0, 0});  // filled by the frame kernel
-        MC(PAD);
+    if (part != PROMPT_VOICE) {  // the text part
+        TP(BOS_TOKEN);                                             // :229-239
+        for (int i = 0; i < p->n_text; ++i) TP((int)p->text_ids[i]);  // :241-245
+        TP(EOS_TOKEN);                                             // :247-254
+        MC(BOS);                                                   // :256-264
     }
-    TP(BOS_TOKEN);                                             // :229-239
-    for (int i = 0; i < p->n_text; ++i) TP((int)p->text_ids[i]);  // :241-245
-    TP(EOS_TOKEN);                                             // :247-254
-    MC(BOS);                                                   // :256-264
     const int n = (int)rows.size();
     if (n > max_rows || n > e->prow_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "prompt longer than n_ctx");
     hipStream_t s = e->stream;
@@ -894,23 +907,35 @@ static uint64_t wall_seed() {
 // Talker prefill (src/tts/engine.rs:455-462) of several requests at once: their prompt rows are concatenated into one
 // batch (row -> (slot, position) maps), so the weights stream once for all of them; then per request the last row
 // seeds the slot (logits, state, sampler draws). rc[i] receives the per-request status.
-struct Adm { int b; const q3tts_request* r; int n, row0, max_steps; };
+// A request behind a voice prefix (P > 0 rows) brings only its own n rows: they sit at positions P .. P + n - 1 of its slot, whose first
+// P positions receive a copy of the prefix's K/V (k_kv_prefix, one launch for the group) before the layers run.
+struct Adm { int b; const q3tts_request* r; int n, row0, max_steps, P; };
 
 static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
     const q3tts_model_config& m = e->cfg.model;
     hipStream_t s = e->stream;
     if (grp.empty()) return Q3TTS_OK;
     std::vector<int> pos(total), slot(total);
-    for (const Adm& a : grp) for (int i = 0; i < a.n; ++i) { pos[a.row0 + i] = i; slot[a.row0 + i] = a.b; }
+    for (const Adm& a : grp) for (int i = 0; i < a.n; ++i) { pos[a.row0 + i] = a.P + i; slot[a.row0 + i] = a.b; }
     Q3_HIP(e, hipMemcpyAsync(e->pf_pos, pos.data(), (size_t)total * 4, hipMemcpyHostToDevice, s));
     Q3_HIP(e, hipMemcpyAsync(e->pf_slot, slot.data(), (size_t)total * 4, hipMemcpyHostToDevice, s));
-    std::vector<int> seg; int seg_max = 0;  // the same rows as runs: every request's rows are consecutive, positions 0 .. n - 1
-    for (const Adm& a : grp) { seg.push_back(a.row0); seg.push_back(a.n); seg.push_back(a.b); seg_max = std::max(seg_max, a.n); }
+    std::vector<int> seg; int seg_max = 0, seg_max_t = 0;  // the same rows as runs: every request's rows are consecutive, positions P .. P + n - 1
+    Q3KvPrefix kp{}; kp.kc = e->T.kc; kp.vc = e->T.vc; kp.layer_stride = e->T.layer_stride; kp.n_ctx = e->T.n_ctx; kp.L = e->T.L; kp.Hkv = e->T.Hkv; kp.hd = e->T.hd;
+    for (const Adm& a : grp) {
+        seg.push_back(a.row0); seg.push_back(a.n); seg.push_back(a.b); seg.push_back(a.P);
+        seg_max = std::max(seg_max, a.n); seg_max_t = std::max(seg_max_t, a.P + a.n);
+        if (a.P > 0) {
+            if (kp.n == Q3_KVP_MAX) { q3_launch_kv_prefix(kp, s); kp.n = 0; }  // (a group holds at most B <= 64 requests: not reached)
+            const q3tts_prefix* x = a.r->prefix;
+            kp.pk[kp.n] = x->k; kp.pv[kp.n] = x->v; kp.P[kp.n] = x->P; kp.slot[kp.n] = a.b; ++kp.n;
+        }
+    }
     Q3_HIP(e, hipMemcpyAsync(e->pf_seg, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, s));
     Q3_HIP(e, hipStreamSynchronize(s));  // pos/slot are locals
+    q3_launch_kv_prefix(kp, s);
     if (e->T.a8) q3_launch_norm_inputs_q8(e->xp, m.t_d_model, total, m.t_d_model, e->T.attn_norm[0], (int8_t*)e->xbp, e->ascp, e->rt16p, e->sspp, m.t_d_model / 16, s);
     else q3_launch_norm_inputs(e->xp, m.t_d_model, total, m.t_d_model, e->T.attn_norm[0], e->xbp, 0, e->sspp, m.t_d_model / 16, s);
-    const int rl = run_layers(e, e->T, e->xp, e->xbp, e->sspp, total, e->pf_pos, e->pf_slot, e->sc_pre, s, false, nullptr, 0, 0, e->pf_seg, (int)grp.size(), seg_max, e->ascp, e->rt16p);
+    const int rl = run_layers(e, e->T, e->xp, e->xbp, e->sspp, total, e->pf_pos, e->pf_slot, e->sc_pre, s, false, nullptr, 0, 0, e->pf_seg, (int)grp.size(), seg_max, seg_max_t, e->ascp, e->rt16p);
     if (rl) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefill: a kernel launch was refused for this model shape");
     Q3_HIP(e, hipGetLastError());
     for (const Adm& a : grp) {
@@ -937,7 +962,7 @@ static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
         }
         Q3Slot* st = e->slots_host + e->B + b;  // pinned staging half
         memset(st, 0, sizeof(*st));
-        st->active = 1; st->cur_pos = a.n; st->n_frames = 0; st->max_steps = a.max_steps; st->min_frames = r->min_frames;
+        st->active = 1; st->cur_pos = a.P + a.n; st->n_frames = 0; st->max_steps = a.max_steps; st->min_frames = r->min_frames;
         st->force_eos_at = r->force_eos_at; st->top_k = top_k; st->temperature = temperature; st->top_p = top_p;
         st->rng_base = b * e->cfg.max_steps_cap;
         Q3_HIP(e, hipMemcpyAsync(e->slots + b, st, sizeof(Q3Slot), hipMemcpyHostToDevice, s));
@@ -957,16 +982,19 @@ static int admit_many(q3tts_engine* e, const int* slots, const q3tts_request* co
         rc[i] = Q3TTS_OK;
         const int max_steps = r->max_steps > 0 ? r->max_steps : e->max_steps;
         if (max_steps > e->cfg.max_steps_cap) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "max_steps exceeds max_steps_cap"); continue; }
+        const q3tts_prefix* x = r->prefix;
+        if (x && x->e != e) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: made by another engine"); continue; }
+        const int P = x ? x->P : 0;  // the prefix's rows come first; only the request's own rows enter the prefill buffer
         int n = 0;
         for (int attempt = 0; attempt < 2; ++attempt) {
             const int room = e->cfg.n_ctx - total;
             if (r->prompt_embd) {
                 n = r->n_tok;
-                if (n <= 0 || n > e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "n_tok out of range"); break; }
+                if (n <= 0 || P + n > e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "n_tok out of range"); break; }
                 if (n > room) { if (total == 0) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "n_tok out of range"); break; } }
                 else { Q3_HIP(e, hipMemcpyAsync(e->xp + (size_t)total * m.d_embed, r->prompt_embd, (size_t)n * m.d_embed * 4, hipMemcpyHostToDevice, s)); break; }
             } else if (r->prompt) {
-                const int brc = build_prompt_dev(e, r->prompt, e->xp + (size_t)total * m.d_embed, room, &n);
+                const int brc = build_prompt_dev(e, r->prompt, e->xp + (size_t)total * m.d_embed, room, &n, x ? PROMPT_TEXT : PROMPT_WHOLE);
                 if (brc == Q3TTS_OK) break;
                 if (total == 0) { rc[i] = brc; break; }
             } else { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "request has neither prompt_embd nor prompt"); break; }
@@ -974,8 +1002,9 @@ static int admit_many(q3tts_engine* e, const int* slots, const q3tts_request* co
             grp.clear(); total = 0;
         }
         if (rc[i] != Q3TTS_OK) continue;
-        if (n + max_steps > e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prompt + max_steps exceeds n_ctx"); continue; }
-        grp.push_back(Adm{slots[i], r, n, total, max_steps});
+        if (P + n > e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix + prompt longer than n_ctx"); continue; }
+        if (P + n + max_steps > e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prompt + max_steps exceeds n_ctx"); continue; }
+        grp.push_back(Adm{slots[i], r, n, total, max_steps, P});
         total += n;
     }
     return admit_group(e, grp, total);
@@ -985,6 +1014,68 @@ static int admit(q3tts_engine* e, int b, const q3tts_request* r) {
     int rc = Q3TTS_OK;
     int st = admit_many(e, &b, &r, 1, &rc);
     return st != Q3TTS_OK ? st : rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// voice prefixes (include/q3tts.h): the Talker runs the voice rows once, at positions 0 .. P - 1, straight into the prefix store — for
+// that one run the Talker's cache fields point at the store, a cache of one slot and np = ceil(P / 64) * 64 positions — so no slot's
+// state changes. Same launches, same rows, same positions as the whole prompt's prefill: the same K/V bits.
+// ------------------------------------------------------------------------------------------------
+extern "C" int q3tts_prefix_create(q3tts_engine* e, const q3tts_prompt_desc* p, const float* embd, int32_t n_tok, q3tts_prefix** out) {
+    if (!e || !out) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
+    Q3_NOT_IN_SESSION(e);
+    *out = nullptr;
+    if ((p != nullptr) == (embd != nullptr)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: give exactly one of a voice desc or host rows");
+    Q3_HIP(e, hipSetDevice(e->cfg.device));
+    const q3tts_model_config& m = e->cfg.model;
+    hipStream_t s = e->stream;
+    const int n_ctx = e->cfg.n_ctx;
+    int n = 0;
+    if (p) TRY(build_prompt_dev(e, p, e->xp, n_ctx - 1, &n, PROMPT_VOICE));
+    else {
+        if (n_tok <= 0 || n_tok >= n_ctx) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: n_tok outside 1 .. n_ctx - 1");
+        n = n_tok;
+        Q3_HIP(e, hipMemcpyAsync(e->xp, embd, (size_t)n * m.d_embed * 4, hipMemcpyHostToDevice, s));
+    }
+    Q3Tfm& t = e->T;
+    q3tts_prefix* x = new q3tts_prefix();
+    x->e = e; x->P = n; x->np = (n + 63) & ~63;
+    const size_t per = (size_t)t.L * t.Hkv * x->np * t.hd;
+    int rc = q3_dev_alloc_zeroed(e, (void**)&x->k, per * 2);
+    if (rc == Q3TTS_OK) rc = q3_dev_alloc_zeroed(e, (void**)&x->v, per * 2);
+    if (rc != Q3TTS_OK) { hipFree(x->k); hipFree(x->v); delete x; return rc; }
+    auto fail = [&](int code, const std::string& msg) { hipStreamSynchronize(s); hipFree(x->k); hipFree(x->v); delete x; return q3_set_err(e, code, msg); };
+    std::vector<int> pos(n), zero(n, 0);
+    for (int i = 0; i < n; ++i) pos[i] = i;
+    const int seg[4] = {0, n, 0, 0};
+    hipError_t er = hipMemcpyAsync(e->pf_pos, pos.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
+    if (er == hipSuccess) er = hipMemcpyAsync(e->pf_slot, zero.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
+    if (er == hipSuccess) er = hipMemcpyAsync(e->pf_seg, seg, sizeof(seg), hipMemcpyHostToDevice, s);
+    if (er == hipSuccess) er = hipStreamSynchronize(s);  // locals
+    if (er != hipSuccess) return fail(Q3TTS_ERR_DEVICE, hipGetErrorString(er));
+    if (t.a8) q3_launch_norm_inputs_q8(e->xp, m.t_d_model, n, m.t_d_model, t.attn_norm[0], (int8_t*)e->xbp, e->ascp, e->rt16p, e->sspp, m.t_d_model / 16, s);
+    else q3_launch_norm_inputs(e->xp, m.t_d_model, n, m.t_d_model, t.attn_norm[0], e->xbp, 0, e->sspp, m.t_d_model / 16, s);
+    uint16_t *kc = t.kc, *vc = t.vc; const size_t ls = t.layer_stride; const int nc = t.n_ctx;
+    t.kc = x->k; t.vc = x->v; t.layer_stride = (size_t)t.Hkv * x->np * t.hd; t.n_ctx = x->np;
+    const int rl = run_layers(e, t, e->xp, e->xbp, e->sspp, n, e->pf_pos, e->pf_slot, e->sc_pre, s, false, nullptr, 0, 0, e->pf_seg, 1, n, n, e->ascp, e->rt16p);
+    t.kc = kc; t.vc = vc; t.layer_stride = ls; t.n_ctx = nc;
+    if (rl) return fail(Q3TTS_ERR_INVALID, "prefix: a kernel launch was refused for this model shape");
+    er = hipGetLastError();
+    if (er == hipSuccess) er = hipStreamSynchronize(s);
+    if (er != hipSuccess) return fail(Q3TTS_ERR_DEVICE, hipGetErrorString(er));
+    *out = x;
+    return Q3TTS_OK;
+}
+extern "C" int32_t q3tts_prefix_rows(const q3tts_prefix* x) { return x ? x->P : 0; }
+extern "C" int q3tts_prefix_destroy(q3tts_prefix* x) {
+    if (!x) return Q3TTS_OK;
+    q3tts_engine* e = x->e;
+    Q3_NOT_IN_SESSION(e);  // an open session may still admit requests that name it
+    hipSetDevice(e->cfg.device);
+    hipStreamSynchronize(e->stream);
+    hipFree(x->k); hipFree(x->v);
+    delete x;
+    return Q3TTS_OK;
 }
 
 static double now_ms() {
@@ -1877,11 +1968,11 @@ extern "C" int q3tts_k_mfma_bf16(int32_t device, const uint16_t* a, const uint16
     return Q3TTS_OK;
 }
 
-extern "C" int q3tts_k_talker_prefill(q3tts_engine* e, const float* embd, int32_t n_tok, float* hidden_out, float* logits_out) {
+static int talker_prefill(q3tts_engine* e, const q3tts_prefix* prefix, const float* embd, int32_t n_tok, float* hidden_out, float* logits_out) {
     Q3_NOT_IN_SESSION(e);
     if (!e || !embd || n_tok <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
-    q3tts_request r{}; r.prompt_embd = embd; r.n_tok = n_tok; r.use_engine_sampler = 0; r.temperature = 0; r.max_steps = 1;
+    q3tts_request r{}; r.prompt_embd = embd; r.n_tok = n_tok; r.use_engine_sampler = 0; r.temperature = 0; r.max_steps = 1; r.prefix = prefix;
     TRY(plan_rows(e, std::vector<int>{0}));
     TRY(admit(e, 0, &r));
     const q3tts_model_config& m = e->cfg.model;
@@ -1895,6 +1986,14 @@ extern "C" int q3tts_k_talker_prefill(q3tts_engine* e, const float* embd, int32_
     Q3_HIP(e, hipMemcpyAsync(e->slots, stage, sizeof(Q3Slot), hipMemcpyHostToDevice, s));  // retire the slot again
     Q3_HIP(e, hipStreamSynchronize(s));
     return Q3TTS_OK;
+}
+extern "C" int q3tts_k_talker_prefill(q3tts_engine* e, const float* embd, int32_t n_tok, float* hidden_out, float* logits_out) {
+    return talker_prefill(e, nullptr, embd, n_tok, hidden_out, logits_out);
+}
+extern "C" int q3tts_k_talker_prefill_prefix(q3tts_engine* e, const q3tts_prefix* prefix, const float* embd, int32_t n_tok, float* hidden_out,
+                                             float* logits_out) {
+    if (!prefix) return q3_set_err(e, Q3TTS_ERR_INVALID, "null prefix");
+    return talker_prefill(e, prefix, embd, n_tok, hidden_out, logits_out);
 }
 
 extern "C" int q3tts_k_probe(q3tts_engine* e, int32_t enable) {

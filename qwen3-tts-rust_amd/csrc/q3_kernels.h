@@ -216,12 +216,24 @@ struct Q3Attend {
     int fused;        // 1: every slot has exactly one row in this launch -> q/k prep + KV append done in-kernel (R >= 2)
                       // 2: rows b (position 0) and slot_mod + b (position 1) of every slot, nothing cached yet (R == 2, hd == 128): k_attend_pair
     Q3QkPrep prep;    // used when fused
-    // prefill (fused == 0): the launch's rows as per-slot runs of consecutive positions 0 .. n - 1 — seg[i] = {first row, n, slot}, device memory.
-    // With it (and hd = 128, two query heads per KV head, every n <= 128) one workgroup serves a whole run from LDS: k_attend_prefill
-    const int* seg; int n_seg; int seg_max_n;
+    // prefill (fused == 0): the launch's rows as per-slot runs of consecutive positions pos0 .. pos0 + n - 1 — seg[i] = {first row, n, slot,
+    // pos0}, device memory; pos0 > 0 when the slot's first pos0 positions hold a voice prefix (q3tts_prefix). seg_max_n = max n,
+    // seg_max_t = max (pos0 + n). With it (and hd = 128, two query heads per KV head, every n <= 128, every pos0 + n <= 256) one workgroup
+    // serves a whole run from LDS: k_attend_prefill
+    const int* seg; int n_seg; int seg_max_n; int seg_max_t;
     Q3_STAMP_FIELD
 };
 void q3_launch_attend(const Q3Attend& a, hipStream_t s);
+// Voice prefixes (q3tts_prefix): copy a prefix store into slots before their prefill. A store is laid out as one slot's cache of
+// np = ceil(P / 64) * 64 positions: k / v [L][Hkv][np * hd] bf16 (keys in 64-position blocks, values row-major). Entry j copies every
+// layer's whole key blocks and the values of positions < P[j] into slot[j]; keys at positions P .. np - 1 of the slot are overwritten.
+#define Q3_KVP_MAX 64
+struct Q3KvPrefix {
+    uint16_t* kc; uint16_t* vc; size_t layer_stride; int n_ctx;  // the Talker's cache: [L][slots][Hkv][n_ctx * hd]
+    int L, Hkv, hd, n;
+    const uint16_t* pk[Q3_KVP_MAX]; const uint16_t* pv[Q3_KVP_MAX]; int P[Q3_KVP_MAX]; int slot[Q3_KVP_MAX];
+};
+void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s);
 void q3_attend_policy(int decode, int prefill);  // test hook (q3tts_k_attend_policy): which kernel variant serves decode / prefill attention (same bits)
 void q3_attend_policy_get(int* decode, int* prefill);
 

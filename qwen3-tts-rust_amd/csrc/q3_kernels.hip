@@ -822,7 +822,9 @@ __global__ __launch_bounds__(256) void k_attend_pair(Q3Attend a) {
 // Prefill attention of a whole prompt run: one workgroup per (KV head, slot) keeps the run's keys (in the cache's packed block form) and
 // values in LDS and its 8 waves each take (row, query head) tasks — k_attend<2, false> starts one 8-wave workgroup per (row, KV head) that
 // fetches the same keys again (23 500 workgroups for 64 prompts: 220 us per layer). hd = 128, two query heads per KV head, runs of
-// n <= 128 rows at positions 0 .. n - 1 (what admit_group builds). The canonical order is k_attend's, element for element:
+// n <= 128 rows at positions pos0 .. pos0 + n - 1 with pos0 + n <= 256 (what admit_group builds; pos0 > 0 behind a voice prefix, whose keys
+// and values are already in the slot's cache). Row r attends to keys [0, pos0 + r]; the workgroup stages all pos0 + n of them.
+// The canonical order is k_attend's, element for element:
 //   score t: the d-ascending fmaf chain of lane t % 64 over block t / 64, times the scale; maximum over all t;
 //   weights: q3_expf(score - max); their sum: per key-block class sw = block % 4 the lanes' sums in block order, the 64-lane butterfly,
 //            then ((l0 + l1) + l2) + l3;
@@ -833,25 +835,27 @@ __global__ __launch_bounds__(256) void k_attend_pair(Q3Attend a) {
 __global__ __launch_bounds__(512) void k_attend_prefill(Q3Attend a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int g = blockIdx.x, sg = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int row0 = a.seg[3 * sg], n = a.seg[3 * sg + 1], slot = a.seg[3 * sg + 2];
+    const int row0 = a.seg[4 * sg], n = a.seg[4 * sg + 1], slot = a.seg[4 * sg + 2], pos0 = a.seg[4 * sg + 3];
     constexpr int hd = 128;
-    const int nblk = (n + 63) >> 6;
+    const int nk = pos0 + n;                                    // keys (and values) the run attends to
+    const int nblk = (nk + 63) >> 6;
+    const int pw = a.seg_max_t > 128 ? (a.seg_max_t + 63) & ~63 : 128;  // weights per wave: the launch's longest run (q3_launch_attend sizes LDS alike)
     uint4* kl = (uint4*)smem;                                  // [nblk][16 chunks][64 lanes]: a key block as the cache stores it
-    uint4* vl = kl + (size_t)nblk * 1024;                       // [n][16]: value rows
-    float* scr = (float*)(vl + (size_t)n * 16) + wave * 256;    // per wave: weights p[128] | query q[128]
-    float* p = scr; float* q = scr + 128;
+    uint4* vl = kl + (size_t)nblk * 1024;                       // [nk][16]: value rows
+    float* scr = (float*)(vl + (size_t)nk * 16) + wave * (pw + 128);  // per wave: weights p[pw] | query q[128]
+    float* p = scr; float* q = scr + pw;
     const size_t hb = ((size_t)slot * a.Hkv + g) * a.n_ctx;
     {
         const uint4* kb = (const uint4*)(a.kc + hb * hd);
         const uint4* vb = (const uint4*)(a.vc + hb * hd);
         for (int i = tid; i < nblk * 1024; i += 512) kl[i] = kb[i];
-        for (int i = tid; i < n * 16; i += 512) vl[i] = vb[i];
+        for (int i = tid; i < nk * 16; i += 512) vl[i] = vb[i];
     }
     __syncthreads();
     const float scale = 1.0f / sqrtf((float)hd);
     const int kg = lane >> 4, dl = lane & 15;
     for (int task = wave; task < 2 * n; task += 8) {
-        const int r = task >> 1, hh = task & 1, row = row0 + r, T = r + 1;
+        const int r = task >> 1, hh = task & 1, row = row0 + r, T = pos0 + r + 1;
         {
             const float2 qv = *(const float2*)(a.qkv + (size_t)row * a.ld + (size_t)(g * 2 + hh) * hd + 2 * lane);
             *(float2*)(q + 2 * lane) = qv;
@@ -987,10 +991,14 @@ void q3_launch_attend(const Q3Attend& a, hipStream_t s) {
     }
     // whole prompt runs (admit_group): keys and values once per run — when there are enough runs to occupy the chip (one workgroup per run and
     // KV head walks its rows 8 at a time: a single prompt of 31 rows took 45 us per layer on 8 workgroups against 9 us on k_attend's 248)
-    if (R == 2 && a.hd == 128 && a.seg && a.seg_max_n <= 128 && g_att_prefill != 1 && (a.n_seg * a.Hkv >= 128 || g_att_prefill == 2)) {
+    // With voice prefixes a run attends to pos0 + n keys: up to 256 of them still fit (4 key blocks of 16 KiB + 256 values of 256 B + 8 waves
+    // x (256 + 128) floats = 140 KiB); without prefixes seg_max_t = seg_max_n and the rule and the LDS size are what they were.
+    if (R == 2 && a.hd == 128 && a.seg && a.seg_max_n <= 128 && a.seg_max_t <= 256 && g_att_prefill != 1 &&
+        (a.n_seg * a.Hkv >= 128 || g_att_prefill == 2)) {
         {
-            const int nblk = (a.seg_max_n + 63) / 64;
-            const size_t lds3 = (size_t)nblk * 16384 + (size_t)a.seg_max_n * 256 + 8 * 256 * sizeof(float);
+            const int nblk = (a.seg_max_t + 63) / 64;
+            const int pw = a.seg_max_t > 128 ? (a.seg_max_t + 63) & ~63 : 128;
+            const size_t lds3 = (size_t)nblk * 16384 + (size_t)a.seg_max_t * 256 + (size_t)8 * (pw + 128) * sizeof(float);
             static Q3PerDevice pd3;
             if (lds3 > 65536) pd3.ensure(lds3, [&]() { hipFuncSetAttribute((const void*)k_attend_prefill, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3); });
             hipLaunchKernelGGL(k_attend_prefill, dim3(a.Hkv, a.n_seg), dim3(512), lds3, s, a);
@@ -1000,6 +1008,23 @@ void q3_launch_attend(const Q3Attend& a, hipStream_t s) {
     if (R == 1) hipLaunchKernelGGL((k_attend<1, false>), grid, dim3(256), lds, s, a);
     else if (R == 2) hipLaunchKernelGGL((k_attend<2, false>), grid, dim3(512), lds, s, a);
     else hipLaunchKernelGGL((k_attend<4, false>), grid, dim3(1024), lds, s, a);
+}
+
+// Voice prefixes: one workgroup per (layer, K or V, KV head) and entry copies a prefix store into its slot with 16-byte loads and stores.
+// The store is read once per entry, so its loads stay cacheable (plain loads, plain stores).
+__global__ __launch_bounds__(256) void k_kv_prefix(Q3KvPrefix a) {
+    const int j = blockIdx.y, isv = blockIdx.x & 1, lg = blockIdx.x >> 1, l = lg / a.Hkv, g = lg - l * a.Hkv;
+    const int P = a.P[j], np = (P + 63) & ~63;
+    const size_t src = ((size_t)l * a.Hkv + g) * np * a.hd;
+    const size_t dst = (size_t)l * a.layer_stride + ((size_t)a.slot[j] * a.Hkv + g) * a.n_ctx * a.hd;
+    const int n16 = (isv ? P : np) * (a.hd >> 3);  // whole key blocks; values of positions < P
+    const uint4* sp = (const uint4*)((isv ? a.pv[j] : a.pk[j]) + src);
+    uint4* dp = (uint4*)((isv ? a.vc : a.kc) + dst);
+    for (int i = threadIdx.x; i < n16; i += 256) dp[i] = sp[i];
+}
+void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s) {
+    if (a.n <= 0) return;
+    hipLaunchKernelGGL(k_kv_prefix, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -253,6 +253,8 @@ extern "C" int q3tts_node_generate_batch(q3tts_node* n, const q3tts_request* req
     const int G = (int)n->dev.size();
     const bool gather = pcm_i16 != nullptr;
     for (int i = 0; i < n_reqs; ++i) { memset(&outs[i], 0, sizeof(outs[i])); outs[i].status = Q3TTS_ERR_STATE; if (gather) pcm_i16[i] = nullptr; }
+    for (int i = 0; i < n_reqs; ++i)  // a prefix belongs to one engine (include/q3tts.h, "voice prefixes")
+        if (reqs[i].prefix) return node_err(n, Q3TTS_ERR_INVALID, "node: requests with a voice prefix are not supported (a prefix belongs to one engine)");
     if (gather) { const int rc = node_comms(n); if (rc != Q3TTS_OK) return rc; }
     const double t0 = node_now_ms();
     // ---- generation: device r runs requests {i : i mod G == r} through its own continuous-batching engine, no exchange

@@ -75,6 +75,7 @@ class Request(C.Structure):
         ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("has_seed", C.c_int32),
         ("seed", C.c_uint64),
         ("max_steps", C.c_int32), ("min_frames", C.c_int32), ("force_eos_at", C.c_int32), ("want_pcm", C.c_int32),
+        ("prefix", C.c_void_p),  # const q3tts_prefix*: NULL, or a voice prefix of the same engine (include/q3tts.h, "voice prefixes")
     ]
 
 
@@ -141,6 +142,7 @@ SYMBOLS = [
     "q3tts_node_create", "q3tts_node_destroy", "q3tts_node_generate_batch", "q3tts_node_get_timings", "q3tts_node_last_error", "q3tts_node_size", "q3tts_node_engine", "q3tts_node_shard", "q3tts_k_bgemm_q8", "q3tts_k_bgemm_q8a8", "q3tts_k_alloc_upload", "q3tts_k_bgemm_policy", "q3tts_k_attend_policy", "q3tts_k_bgemm_pick", "q3tts_k_mfma_bf16", "q3tts_k_bgemm", "q3tts_k_bgemm_voc", "q3tts_k_project", "q3tts_k_norm_inputs", "q3tts_tokenizer_load", "q3tts_tokenizer_free", "q3tts_tokenizer_vocab_size", "q3tts_tokenizer_encode", "q3tts_tokenizer_decode",
     "q3tts_session_create", "q3tts_session_submit", "q3tts_session_cancel", "q3tts_session_next", "q3tts_session_close",
     "q3tts_session_last_error", "q3tts_k_pcm_pack",
+    "q3tts_prefix_create", "q3tts_prefix_rows", "q3tts_prefix_destroy", "q3tts_k_talker_prefill_prefix",
 ]
 
 
@@ -202,6 +204,11 @@ def load_library(path=None):
     lib.q3tts_k_sample.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float,
                                    f32p, i32p]
     lib.q3tts_k_talker_prefill.argtypes = [vp, f32p, C.c_int32, f32p, f32p]
+    lib.q3tts_k_talker_prefill_prefix.argtypes = [vp, vp, f32p, C.c_int32, f32p, f32p]
+    lib.q3tts_prefix_create.argtypes = [vp, C.POINTER(PromptDesc), f32p, C.c_int32, C.POINTER(vp)]
+    lib.q3tts_prefix_rows.argtypes = [vp]
+    lib.q3tts_prefix_rows.restype = C.c_int32
+    lib.q3tts_prefix_destroy.argtypes = [vp]
     lib.q3tts_k_vocoder.argtypes = [vp, i32p, C.c_int32, C.c_int32, f32p, i32p]
     lib.q3tts_k_vocoder_latent.argtypes = [vp, i32p, C.c_int32, C.c_int32, f32p]
     lib.q3tts_k_vocoder_bench.argtypes = [vp, C.c_int32, C.c_int32, f32p]

@@ -199,31 +199,53 @@ class TtsEngine:
     def _lang(self):
         return getattr(self, "lang_id", LANG_ID_CHINESE)
 
-    def _desc(self, text, voice: VoiceFile, instruct):
-        ids = self._encode(text)
+    def _desc(self, text, voice: VoiceFile, instruct, part="whole"):
+        ids = None if part == "voice" else self._encode(text)
+        if part == "text":  # behind a voice prefix: the voice part is the prefix's
+            return native.make_prompt_desc(ids, part="text")
         ins = None if instruct is None else self._encode(instruct)
         emb = np.asarray(voice.speaker_embedding, dtype=np.float32)
         if emb.size != self.cfg.model.d_embed:
             raise _abi.Q3Error(f"speaker_embedding has {emb.size} values, expected {self.cfg.model.d_embed}")
         if len(voice.audio_codes) == 0:  # src/tts/engine.rs:398-412: x-vector-only prompt
-            return native.make_prompt_desc(ids, spk_emb=emb, lang_id=self._lang(), instruct_ids=ins)
+            return native.make_prompt_desc(ids, spk_emb=emb, lang_id=self._lang(), instruct_ids=ins, part=part)
         ref_ids = self._encode(voice.ref_text)  # :414-427: ICL clone prompt
         return native.make_prompt_desc(ids, spk_emb=emb, lang_id=self._lang(), instruct_ids=ins,
-                                       ref_codes=np.asarray(voice.audio_codes, dtype=np.int32), ref_text_ids=ref_ids)
+                                       ref_codes=np.asarray(voice.audio_codes, dtype=np.int32), ref_text_ids=ref_ids, part=part)
 
-    def generate_with_voice(self, text, voice: VoiceFile, instruct=None) -> AudioSample:
-        """src/tts/engine.rs:390-435."""
-        return self.generate_batch_with_voice([text], [voice], [instruct])[0]
+    def _prefix_key(self, voice, instruct):
+        return id(voice), None if instruct is None else tuple(int(i) for i in self._encode(instruct)), self._lang()
 
-    def generate_batch_with_voice(self, texts, voices, instructs=None, seeds=None):
+    def voice_prefix(self, voice: VoiceFile, instruct=None):
+        """A voice prefix (an extension: the reference rebuilds the whole prompt for every call): the Talker runs the voice part of the
+        prompt — instruct, language, speaker and, for a cloned voice, its reference text and frames — once and keeps its K/V on the
+        device. Pass it as prefix= with the same voice and instruct: the audio is bit-identical to a call without it. Close it (or use it
+        as a context manager) when the voice is no longer needed."""
+        desc, keep = self._desc(None, voice, instruct, part="voice")
+        x = self._native.create_prefix(desc=desc)
+        x.voice_key = self._prefix_key(voice, instruct)
+        return x
+
+    def _check_prefix(self, prefix, voice, instruct):
+        if getattr(prefix, "voice_key", None) != self._prefix_key(voice, instruct):
+            raise ValueError("prefix= was not made by voice_prefix() from this voice, instruct and language")
+
+    def generate_with_voice(self, text, voice: VoiceFile, instruct=None, *, prefix=None) -> AudioSample:
+        """src/tts/engine.rs:390-435. prefix: a voice_prefix(voice, instruct) of this engine (same audio, the voice rows are not run again)."""
+        return self.generate_batch_with_voice([text], [voice], [instruct], prefix=prefix)[0]
+
+    def generate_batch_with_voice(self, texts, voices, instructs=None, seeds=None, *, prefix=None):
         sc = self.sampler_config
         reqs, keep = [], []
         for i, (t, v) in enumerate(zip(texts, voices)):
-            desc, k = self._desc(t, v, None if instructs is None else instructs[i])
+            ins = None if instructs is None else instructs[i]
+            if prefix is not None:
+                self._check_prefix(prefix, v, ins)
+            desc, k = self._desc(t, v, ins, part="whole" if prefix is None else "text")
             keep.append(k)
             seed = sc.seed if seeds is None else seeds[i]
             reqs.append(dict(desc=desc, temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p, seed=seed, max_steps=self.max_steps,
-                             want_pcm=1))
+                             want_pcm=1, prefix=prefix))
         outs = self._native.generate_batch(reqs)
         for o in outs:
             if o.status != 0:
@@ -231,7 +253,7 @@ class TtsEngine:
         sr = self.cfg.vocoder.sample_rate
         return [AudioSample(o.pcm, sr, 1) for o in outs]
 
-    def stream_batch_with_voice(self, texts, voices, instructs=None, seeds=None):
+    def stream_batch_with_voice(self, texts, voices, instructs=None, seeds=None, *, prefix=None):
         """The streaming twin of generate_batch_with_voice: every utterance runs through one session (continuous batching over the
         engine's slots) and its 4-frame chunks are yielded as they are produced, as (index, f32 chunk, is_final); chunks of different
         utterances interleave, each utterance's come in order and its last has is_final = True."""
@@ -239,9 +261,13 @@ class TtsEngine:
         with native.NativeSession(self._native) as sess:
             index = {}
             for i, (t, v) in enumerate(zip(texts, voices)):
-                desc, keep = self._desc(t, v, None if instructs is None else instructs[i])
+                ins = None if instructs is None else instructs[i]
+                if prefix is not None:
+                    self._check_prefix(prefix, v, ins)
+                desc, keep = self._desc(t, v, ins, part="whole" if prefix is None else "text")
                 seed = sc.seed if seeds is None else seeds[i]
-                index[sess.submit(desc=desc, temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p, seed=seed, max_steps=self.max_steps)] = i
+                index[sess.submit(desc=desc, temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p, seed=seed, max_steps=self.max_steps,
+                                  prefix=prefix)] = i
             for rid, kind, pcm, is_final, res in sess.events():
                 if kind == _abi.EV_CHUNK:
                     yield index[rid], pcm, is_final

@@ -1,6 +1,7 @@
 """Thin object wrapper over the C ABI (include/q3tts.h). No arithmetic happens in Python."""
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -13,12 +14,35 @@ def _ptr(a, typ):
     return a.ctypes.data_as(typ)
 
 
-def make_prompt_desc(text_ids, spk_emb=None, lang_id=2055, spk_id=-1, instruct_ids=None, ref_codes=None,
-                     ref_text_ids=None):
-    """Returns (PromptDesc, keepalive list)."""
+_LANG_DEFAULT = object()
+
+
+def make_prompt_desc(text_ids, spk_emb=None, lang_id=_LANG_DEFAULT, spk_id=-1, instruct_ids=None, ref_codes=None,
+                     ref_text_ids=None, part="whole"):
+    """Returns (PromptDesc, keepalive list).
+
+    part: "whole" (default) describes a whole prompt; "voice" only its voice part, for NativeEngine.create_prefix (text_ids must be None or
+    empty); "text" only its text part, for a request behind a prefix (every voice field must be left unset; lang_id then defaults to None).
+    lang_id defaults to 2055 for "whole" and "voice"."""
+    if part not in ("whole", "voice", "text"):
+        raise ValueError(f"part must be 'whole', 'voice' or 'text', not {part!r}")
+    if part == "voice" and text_ids is not None and len(text_ids) > 0:
+        raise ValueError("a voice-only desc has no text: text_ids must be None or empty")
+    if part == "text":
+        given = [n for n, v in (("spk_emb", spk_emb), ("instruct_ids", instruct_ids), ("ref_codes", ref_codes),
+                                ("ref_text_ids", ref_text_ids)) if v is not None]
+        if spk_id is not None and spk_id >= 0:
+            given.append("spk_id")
+        if lang_id is not _LANG_DEFAULT and lang_id is not None and lang_id >= 0:
+            given.append("lang_id")
+        if given:
+            raise ValueError(f"a text-only desc takes its voice from the prefix: {', '.join(given)} must be unset")
+        lang_id, spk_id = None, -1
+    elif lang_id is _LANG_DEFAULT:
+        lang_id = 2055
     keep = []
     d = _abi.PromptDesc()
-    t = np.ascontiguousarray(text_ids, dtype=np.uint32)
+    t = np.ascontiguousarray([] if text_ids is None else text_ids, dtype=np.uint32)
     keep.append(t)
     d.text_ids, d.n_text = _ptr(t, u32p), len(t)
     if instruct_ids is not None:
@@ -57,12 +81,15 @@ class NativeEngine:
         self.lib = _abi.load_library()
         self.cfg = cfg
         self.h = C.c_void_p()
+        self._prefixes = weakref.WeakSet()  # destroyed before the engine
         rc = self.lib.q3tts_engine_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
             raise _abi.Q3Error(f"q3tts_engine_create failed ({rc}): {self.lib.q3tts_last_error(None).decode()}")
 
     def close(self):
         if getattr(self, "h", None):
+            for x in list(getattr(self, "_prefixes", ())):
+                x.close()
             self.lib.q3tts_engine_destroy(self.h)
             self.h = None
 
@@ -88,11 +115,31 @@ class NativeEngine:
         self.lib.q3tts_free(out)
         return arr
 
+    def create_prefix(self, desc=None, embd=None):
+        """A voice prefix (q3tts_prefix_create): the Talker's K/V of a voice part, from a voice-only desc (make_prompt_desc(part="voice"))
+        or from host rows [n][d_embed]. Requests that pass it as prefix= give the bits of the whole prompt."""
+        if (desc is None) == (embd is None):
+            raise ValueError("create_prefix: give exactly one of desc or embd")
+        h = C.c_void_p()
+        if desc is not None:
+            self._check(self.lib.q3tts_prefix_create(self.h, C.byref(desc), None, 0, C.byref(h)), "q3tts_prefix_create")
+        else:
+            e = np.ascontiguousarray(embd, dtype=np.float32)
+            self._check(self.lib.q3tts_prefix_create(self.h, None, _ptr(e, f32p), e.shape[0], C.byref(h)), "q3tts_prefix_create")
+        x = NativePrefix(self, h)
+        self._prefixes.add(x)
+        return x
+
     @staticmethod
     def make_request(embd=None, desc=None, temperature=0.0, top_k=40, top_p=0.9, seed=None, max_steps=0, min_frames=0,
-                     force_eos_at=-1, want_pcm=0, use_engine_sampler=0):
+                     force_eos_at=-1, want_pcm=0, use_engine_sampler=0, prefix=None):
         r = _abi.Request()
         keep = []
+        if prefix is not None:
+            if not prefix.h:
+                raise _abi.Q3Error("the prefix is closed")
+            keep.append(prefix)
+            r.prefix = prefix.h
         if embd is not None:
             e = np.ascontiguousarray(embd, dtype=np.float32)
             keep.append(e)
@@ -234,6 +281,15 @@ class NativeEngine:
                     "q3tts_k_talker_prefill")
         return hid, lg
 
+    def talker_prefill_prefix(self, prefix, embd):
+        """talker_prefill over prefix rows ++ embd (q3tts_k_talker_prefill_prefix)."""
+        e = np.ascontiguousarray(embd, dtype=np.float32)
+        hid = np.zeros(self.cfg.model.t_d_model, dtype=np.float32)
+        lg = np.zeros(self.cfg.model.t_vocab, dtype=np.float32)
+        self._check(self.lib.q3tts_k_talker_prefill_prefix(self.h, prefix.h, _ptr(e, f32p), e.shape[0], _ptr(hid, f32p), _ptr(lg, f32p)),
+                    "q3tts_k_talker_prefill_prefix")
+        return hid, lg
+
     def vocoder(self, codes, chunk_frames=0):
         c = np.ascontiguousarray(codes, dtype=np.int32)
         spf = 1
@@ -257,6 +313,32 @@ class NativeEngine:
         return out
 
 
+class NativePrefix:
+    """q3tts_prefix: a voice part's Talker K/V on the device of one engine (NativeEngine.create_prefix). close() is refused while a session
+    is open on the engine; the engine closes its prefixes when it closes."""
+
+    def __init__(self, engine: NativeEngine, h):
+        self.engine, self.lib, self.h = engine, engine.lib, h
+        self.n_rows = int(self.lib.q3tts_prefix_rows(h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.engine._check(self.lib.q3tts_prefix_destroy(self.h), "q3tts_prefix_destroy")
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except _abi.Q3Error:  # a session still open on the engine: the engine frees it when it closes
+            pass
+
+
 class NativeSession:
     """q3tts_session_*: continuous batching with per-request streaming on one engine (include/q3tts.h, "sessions"). The session owns the
     engine until close(); submit() and cancel() may be called from any thread, events() from one consumer thread."""
@@ -274,7 +356,8 @@ class NativeSession:
             raise _abi.Q3Error(f"{what} failed ({rc}): {self.lib.q3tts_session_last_error(self.h).decode()}")
 
     def submit(self, **request_kw):
-        """request_kw: NativeEngine.make_request keywords (want_pcm is ignored: a session always produces PCM). Returns the id."""
+        """request_kw: NativeEngine.make_request keywords, prefix= included (want_pcm is ignored: a session always produces PCM).
+        Returns the id."""
         if not self.h:
             raise _abi.Q3Error("q3tts_session_submit: the session is closed")
         r, keep = NativeEngine.make_request(**request_kw)

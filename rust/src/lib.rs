@@ -41,6 +41,7 @@ pub struct q3tts_request {
     pub prompt_embd: *const c_float, pub n_tok: i32, pub prompt: *const q3tts_prompt_desc, pub use_engine_sampler: i32,
     pub temperature: c_float, pub top_k: i32, pub top_p: c_float, pub has_seed: i32, pub seed: u64,
     pub max_steps: i32, pub min_frames: i32, pub force_eos_at: i32, pub want_pcm: i32,
+    pub prefix: *const q3tts_prefix,   // null, or a voice prefix of the same engine: the prompt is its rows followed by this request's own
 }
 #[repr(C)]
 pub struct q3tts_result {
@@ -50,6 +51,7 @@ pub struct q3tts_result {
 pub enum q3tts_engine {}
 pub enum q3tts_stream {}
 pub enum q3tts_node {}
+pub enum q3tts_prefix {}
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct q3tts_node_timings { pub generate_ms: c_float, pub gather_ms: c_float, pub total_ms: c_float, pub gathered_bytes: i64, pub n_devices: i32 }
 
@@ -69,6 +71,11 @@ extern "C" {
     pub fn q3tts_stream_poll(s: *mut q3tts_stream, chunk: *mut *const c_float, n_samples: *mut i32, is_final: *mut i32) -> c_int;
     pub fn q3tts_stream_end(s: *mut q3tts_stream, out_codes_optional: *mut q3tts_result) -> c_int;
     pub fn q3tts_free(p: *mut std::ffi::c_void);
+    // voice prefixes (no counterpart in the reference, which rebuilds the whole prompt per call): the Talker's K/V of a voice part, kept on
+    // the device; exactly one of p (n_text == 0) or embd / n_tok is given
+    pub fn q3tts_prefix_create(e: *mut q3tts_engine, p: *const q3tts_prompt_desc, embd: *const c_float, n_tok: i32, out: *mut *mut q3tts_prefix) -> c_int;
+    pub fn q3tts_prefix_rows(x: *const q3tts_prefix) -> i32;
+    pub fn q3tts_prefix_destroy(x: *mut q3tts_prefix) -> c_int;
     // one node, several GPUs (no counterpart in the reference: n_seq_max = 1, src/models/llama/mod.rs:413): one engine + host thread per device
     // inside the library, request i on device i % n_devices, optional RCCL gather of the i16 PCM to the first device
     pub fn q3tts_node_create(cfg: *const q3tts_engine_config, devices: *const i32, n_devices: i32, out: *mut *mut q3tts_node) -> c_int;
@@ -143,7 +150,7 @@ impl TtsEngine {
             prompt_embd: std::ptr::null(), n_tok: 0, prompt: &desc, use_engine_sampler: 0,
             temperature: self.sampler.temperature, top_k: self.sampler.top_k, top_p: self.sampler.top_p,
             has_seed: self.sampler.seed.is_some() as i32, seed: self.sampler.seed.unwrap_or(0),
-            max_steps: self.max_steps as i32, min_frames: 0, force_eos_at: -1, want_pcm: 1,
+            max_steps: self.max_steps as i32, min_frames: 0, force_eos_at: -1, want_pcm: 1, prefix: std::ptr::null(),
         };
         unsafe {
             let mut out: q3tts_result = std::mem::zeroed();
@@ -174,7 +181,7 @@ impl TtsEngine {
             prompt_embd: std::ptr::null(), n_tok: 0, prompt: &desc, use_engine_sampler: 0,
             temperature: self.sampler.temperature, top_k: self.sampler.top_k, top_p: self.sampler.top_p,
             has_seed: self.sampler.seed.is_some() as i32, seed: self.sampler.seed.unwrap_or(0),
-            max_steps: self.max_steps as i32, min_frames: 0, force_eos_at: -1, want_pcm: 1,
+            max_steps: self.max_steps as i32, min_frames: 0, force_eos_at: -1, want_pcm: 1, prefix: std::ptr::null(),
         };
         unsafe {
             let err = |e: *mut q3tts_engine| CStr::from_ptr(q3tts_last_error(e)).to_string_lossy().into_owned();
