@@ -425,6 +425,19 @@ int q3tts_k_vocoder(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int
 /* Vocoder transformer rows: q3tts_k_vocoder's calls on slot 0, and after each the f32 residual rows after the last layer (before the
  * final norm) -> out [n_frames][latent_dim] */
 int q3tts_k_vocoder_latent(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, float* out);
+/* Vocoder convolution half, stage by stage: q3tts_k_vocoder's calls on slot 0 (calls of <= 4 frames, numbered from 0); call `tap_call`
+ * runs eagerly with named copies of its intermediate tensors taken between the production launches, and the drive ends after it. Each
+ * tap is (hist_rows + rows) x channels elements at buf + offset, f32 (dtype 0) or bf16 bits (dtype 1), as plain rows (layout 0) or in
+ * the GEMM's A-tiled layout (layout 1: whole 16-row tiles). Names: up<u>.in / .raw / .ln / .gelu / .out (ConvTranspose input, its raw
+ * output with the depthwise history, LayerNorm output, GELU output, the stage's result), dec_in.in, b<b>.ct_in, b<b>.o_ct,
+ * b<b>.r<u>.c1_in, b<b>.r<u>.z (un-fused path only), b<b>.r<u>.o (u < 2: the last unit's sum is never stored), out.in, pcm. */
+typedef struct q3tts_voc_tap {
+    char name[32];
+    int32_t dtype, layout, hist_rows, rows, channels, reserved;
+    uint64_t offset;
+} q3tts_voc_tap;
+int q3tts_k_vocoder_taps(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, int32_t tap_call, void* buf,
+                         uint64_t buf_bytes, q3tts_voc_tap* recs, int32_t rec_cap, int32_t* n_recs);
 /* Measurement (bench.py roofline_vocoder): the batched vocoder alone, n_slots slots x `chunks` 4-frame calls with nothing else on the
  * GPU; *ms_per_chunk = mean duration of one batched call (n_slots x 4 frames of PCM) by HIP events on its stream. */
 int q3tts_k_vocoder_bench(q3tts_engine* e, int32_t n_slots, int32_t chunks, float* ms_per_chunk);

@@ -184,6 +184,13 @@ void q3o_vocoder_set_arith_mask(q3o_vocoder* v, uint32_t f32_groups_mask);  /* b
 /* tests: intermediate tensors of one whole decode (stage 1 transformer input, 2 transformer output, 3 up-sampled latent, 4 PCM before
  * the clamp) and the synthetic tensors by id, for loading the same model into the family code */
 int32_t q3o_vocoder_stage(q3o_vocoder* v, const int32_t* codes, int32_t n_frames, int32_t stage, float* out);
+/* ... the stage ids inside the convolution half are listed at STAGE() in q3_oracle_vocoder.c; _inject replaces the tensor at
+ * inject_stage by the caller's values before the decode goes on */
+int32_t q3o_vocoder_stage_inject(q3o_vocoder* v, const int32_t* codes, int32_t n_frames, int32_t stage, float* out, int32_t inject_stage,
+                                 const float* inject);
+/* one causal multi-tap convolution as a chain of q3o_mfma_bf16_dot32 in the device's K-step order (no bias): x [(ntap-1)*dil + T][cin] */
+void q3o_vconv_mfma(const uint16_t* x, int32_t T, int32_t cin, const uint16_t* w, int32_t ntap, int32_t dil, int32_t nout, int32_t chunked,
+                    float* out, int32_t threads);
 void q3o_vocoder_mat(const q3o_vocoder* v, int32_t comp, int32_t which, int64_t rows, int64_t cols, int32_t fan_in, float gain, float* out);
 void q3o_vocoder_vec(const q3o_vocoder* v, int32_t comp, int32_t which, int64_t n, float base, float std, float* out);
 /* streaming call: codes [n_frames][n_codebooks] (clamped by the caller as src/tts/engine.rs:515-519);

@@ -203,8 +203,18 @@ void q3o_vocoder_set_arith_mask(q3o_vocoder* v, uint32_t mask) { (void)v; g_vf32
 /* stage / stage_out (tests): 1 the transformer's input [T][d], 2 its output after the final norm [T][d], 3 the up-sampled latent
  * [T * prod(upsample_ratios)][d], 4 the PCM before the clamp. A requested stage of 1..3 ends the decode there (returns NULL): the
  * stages before it are computed exactly as in a whole decode, so their bits do not depend on where the decode stops. */
+/* Inside the convolution half (tests/_voc_ref.py names them; none of these ends the decode):
+ *   100 + 10 u + k, up-sampling stage u: k = 0 the ConvTranspose's input [T][d], 1 its output [T r][d], 2 the LayerNorm output, 3 the GELU
+ *     output [T r][4 d], 4 the stage's result;   200 the decoder input convolution's output [T][decoder_dim] before block 0's SnakeBeta;
+ *   300 + 20 b + k, decoder block b: k = 0 the transposed convolution's input (after SnakeBeta), 1 its output o, and for unit u = 0..2:
+ *     2 + 4 u the unit's convolution input (after SnakeBeta), 3 + 4 u the dilated convolution's output, 4 + 4 u the same after SnakeBeta 2,
+ *     5 + 4 u the residual stream o after the unit;   400 the output convolution's input (after SnakeBeta).
+ * q3o_vocoder_stage_inject: the tensor at `inject_stage` is REPLACED by the caller's values before the decode goes on (the CPU tests push a
+ * deliberately wrong stage output through the rest of the vocoder to see what the PCM checks would have made of it). */
 static int g_stage = 0; static float* g_stage_out = NULL;
-#define STAGE(k, ptr, n) do { if (g_stage == (k) && g_stage_out) memcpy(g_stage_out, (ptr), (size_t)(n) * 4); } while (0)
+static int g_inject = 0; static const float* g_inject_src = NULL;
+#define STAGE(k, ptr, n) do { if (g_inject == (k) && g_inject_src) memcpy((ptr), g_inject_src, (size_t)(n) * 4); \
+                              if (g_stage == (k) && g_stage_out) memcpy(g_stage_out, (ptr), (size_t)(n) * 4); } while (0)
 static float* decode_all(q3o_vocoder* v, int T) {
     const q3o_vocoder_config* c = &v->c;
     const int d = c->latent_dim, H = c->n_head, hd = c->head_dim, HH = H * hd, F = c->d_ffn, W = c->sliding_window;
@@ -277,8 +287,10 @@ static float* decode_all(q3o_vocoder* v, int T) {
     for (int s = 0; s < c->n_upsample; ++s) {
         vup* p = &v->U[s]; const int r = p->r;
         float* up = malloc((size_t)Tc * r * d * 4);
+        STAGE(100 + 10 * s, cur, (size_t)Tc * d);
         conv_fwd(&p->ct, cur, Tc, up); /* [Tc][r*d] == [Tc*r][d] */
         free(cur); Tc *= r;
+        STAGE(101 + 10 * s, up, (size_t)Tc * d);
         float* dw = malloc((size_t)Tc * d * 4);
         for (int t = 0; t < Tc; ++t)
             for (int i = 0; i < d; ++i) {
@@ -296,10 +308,13 @@ static float* decode_all(q3o_vocoder* v, int T) {
             for (int i = 0; i < d; ++i) dw[(size_t)t * d + i] = ((dw[(size_t)t * d + i] - mean) * rinv) * p->ln_w[i] + p->ln_b[i];
         }
         float* h1 = malloc((size_t)Tc * 4 * d * 4);
+        STAGE(102 + 10 * s, dw, (size_t)Tc * d);
         conv_fwd(&p->pw1, dw, Tc, h1);
         for (size_t i = 0; i < (size_t)Tc * 4 * d; ++i) h1[i] = 0.5f * h1[i] * (1.0f + erff(h1[i] * 0.70710678118654752f));
+        STAGE(103 + 10 * s, h1, (size_t)Tc * 4 * d);
         conv_fwd(&p->pw2, h1, Tc, dw); free(h1);
         for (int t = 0; t < Tc; ++t) for (int i = 0; i < d; ++i) up[(size_t)t * d + i] += p->gamma[i] * dw[(size_t)t * d + i];
+        STAGE(104 + 10 * s, up, (size_t)Tc * d);
         free(dw); cur = up;
     }
     STAGE(3, cur, (size_t)Tc * d);
@@ -309,27 +324,35 @@ static float* decode_all(q3o_vocoder* v, int T) {
     float* z = malloc((size_t)Tc * ch * 4);
     g_vgroup = 2;
     conv_fwd(&v->dec_in, cur, Tc, z); free(cur);
+    STAGE(200, z, (size_t)Tc * ch);
     for (int b = 0; b < c->n_dec_blocks; ++b) {
         vblk* k2 = &v->B[b];
         g_vgroup = 3 + b;
         snake(z, Tc, k2->cin, k2->ea, k2->ib);
+        STAGE(300 + 20 * b, z, (size_t)Tc * k2->cin);
         float* o = malloc((size_t)Tc * k2->r * k2->cout * 4);
         conv_fwd(&k2->ct, z, Tc, o); free(z); Tc *= k2->r; ch = k2->cout;
+        STAGE(301 + 20 * b, o, (size_t)Tc * ch);
         float* t1 = malloc((size_t)Tc * ch * 4); float* t2 = malloc((size_t)Tc * ch * 4);
         for (int s = 0; s < 3; ++s) {
             vres* rs = &k2->res[s];
             memcpy(t1, o, (size_t)Tc * ch * 4);
             snake(t1, Tc, ch, rs->ea, rs->ib);
+            STAGE(302 + 20 * b + 4 * s, t1, (size_t)Tc * ch);
             conv_fwd(&rs->c1, t1, Tc, t2);
+            STAGE(303 + 20 * b + 4 * s, t2, (size_t)Tc * ch);
             snake(t2, Tc, ch, rs->ea2, rs->ib2);
+            STAGE(304 + 20 * b + 4 * s, t2, (size_t)Tc * ch);
             conv_fwd(&rs->c2, t2, Tc, t1);
             for (size_t i = 0; i < (size_t)Tc * ch; ++i) o[i] += t1[i];
+            STAGE(305 + 20 * b + 4 * s, o, (size_t)Tc * ch);
         }
         free(t1); free(t2); z = o;
     }
     /* V6 */
     g_vgroup = 3 + c->n_dec_blocks;
     snake(z, Tc, ch, v->oea, v->oib);
+    STAGE(400, z, (size_t)Tc * ch);
     float* pcm = malloc((size_t)Tc * 4);
     conv_fwd(&v->out, z, Tc, pcm); free(z);
     STAGE(4, pcm, Tc);
@@ -348,6 +371,37 @@ int32_t q3o_vocoder_stage(q3o_vocoder* v, const int32_t* codes, int32_t n_frames
     g_stage = 0; g_stage_out = NULL;
     free(pcm); free(v->codes); v->codes = keep; v->n_frames = kn;
     return n_frames * v->spf;
+}
+
+int32_t q3o_vocoder_stage_inject(q3o_vocoder* v, const int32_t* codes, int32_t n_frames, int32_t stage, float* out, int32_t inject_stage,
+                                 const float* inject) {
+    g_inject = inject_stage; g_inject_src = inject;
+    const int32_t n = q3o_vocoder_stage(v, codes, n_frames, stage, out);
+    g_inject = 0; g_inject_src = NULL;
+    return n;
+}
+
+/* One causal multi-tap convolution on the instruction model: out[t][n] = the chain of q3o_mfma_bf16_dot32 over the 32-wide K steps in the
+ * device kernels' order (q3_vocoder.hip vstep: taps ascending with the channel steps inside a tap, or `chunked`: 32-channel chunks ascending
+ * with the taps inside a chunk), from a zero accumulator, no bias. x [hist + T][cin] bf16 bits with hist = (ntap - 1) * dil history rows in
+ * front, w [ntap][nout][cin] bf16 bits. */
+extern float q3o_mfma_bf16_dot32(const uint16_t* a, const uint16_t* b, float c);
+void q3o_vconv_mfma(const uint16_t* x, int32_t T, int32_t cin, const uint16_t* w, int32_t ntap, int32_t dil, int32_t nout, int32_t chunked,
+                    float* out, int32_t threads) {
+    const int kpt = cin / 32, steps = ntap * kpt, hist = (ntap - 1) * dil;
+#pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : 1)
+    for (int t = 0; t < T; ++t)
+        for (int n = 0; n < nout; ++n) {
+            float acc = 0.0f;
+            for (int st = 0; st < steps; ++st) {
+                int tap, k0;
+                if (chunked) { const int chn = st / ntap; tap = st - chn * ntap; k0 = chn * 32; }
+                else { tap = st / kpt; k0 = (st - tap * kpt) * 32; }
+                const uint16_t* xp = x + (size_t)(hist + t - (ntap - 1 - tap) * dil) * cin + k0;
+                acc = q3o_mfma_bf16_dot32(xp, w + ((size_t)tap * nout + n) * cin + k0, acc);
+            }
+            out[(size_t)t * nout + n] = acc;
+        }
 }
 
 int32_t q3o_vocoder_decode(q3o_vocoder* v, const int32_t* codes, int32_t n_frames, int32_t is_last, float* pcm_out, int32_t max_samples) {

@@ -48,8 +48,13 @@ struct VUp { VConv ct, pw1, pw2; float *dw_w, *dw_b, *ln_w, *ln_b, *gamma; int r
 struct VRes { float *ea, *ib, *ea2, *ib2; VConv c1, c2; VBuf c1_in; };
 struct VBlk { float *ea, *ib; VConv ct; VRes res[3]; int r, cin, cout; VBuf ct_in; };
 
+// Test taps (q3tts_k_vocoder_taps): while a sink is set, voc_call_body copies named intermediate tensors of slot 0 to the caller's host
+// buffer between its launches. nullptr in every other call: no launch, copy or branch on the device changes.
+struct VTapSink { uint8_t* buf = nullptr; size_t cap = 0, used = 0; q3tts_voc_tap* recs = nullptr; int rec_cap = 0, n = 0; bool overflow = false; };
+
 struct Q3Voc {
     q3tts_vocoder_config c;
+    VTapSink* taps = nullptr;
     int spf = 1, B = 0, RW = 0;
     std::vector<float*> cb; const float** cb_dev = nullptr;
     VConv pre; VBuf pre_in;
@@ -1664,9 +1669,27 @@ static void voc_launch_attn(hipStream_t s, const VCall* cld, Q3Voc* v, float* kr
     }
     hipLaunchKernelGGL(k_voc_attn, dim3(c.n_head, ns), dim3(64 * nf), 0, s, cld, v->qkv, kr, vr, v->rope, c.n_head, c.head_dim, v->RW, c.sliding_window, v->att, tiled);
 }
+// one tap: (H + T) rows of C elements at p, f32 (dtype 0) or bf16 (1), plain rows (layout 0) or the decoder GEMM's A-tiled layout (1: whole
+// 16-row tiles, q3_atile_off), copied in stream order, i.e. after the launches issued so far and before the next one overwrites p
+static void vtap(Q3Voc* v, hipStream_t s, const void* p, int dtype, int layout, int H, int T, int C, const char* fmt, int a = 0, int b = 0) {
+    VTapSink* k = v->taps;
+    if (!k || k->overflow) return;
+    const size_t rows = layout ? (size_t)((H + T + 15) / 16) * 16 : (size_t)(H + T), bytes = rows * C * (dtype ? 2 : 4);
+    if (k->n >= k->rec_cap || k->used + bytes > k->cap) { k->overflow = true; return; }
+    q3tts_voc_tap& r = k->recs[k->n++];
+    memset(&r, 0, sizeof(r));
+    snprintf(r.name, sizeof(r.name), fmt, a, b);
+    r.dtype = dtype; r.layout = layout; r.hist_rows = H; r.rows = T; r.channels = C; r.offset = k->used;
+    if (hipMemcpyAsync(k->buf + k->used, p, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) k->overflow = true;
+    k->used += (bytes + 15) & ~(size_t)15;
+}
+static void vtap_buf(Q3Voc* v, hipStream_t s, const VBuf& b, int T, const char* fmt, int a = 0, int c = 0) {
+    vtap(v, s, b.p, b.bf16, 0, b.H, T, b.C, fmt, a, c);
+}
 static int voc_call_body(q3tts_engine* e, const VCall& cl, hipStream_t s) {
     Q3Voc* v = e->voc;
     const VCall* cld = v->call_dev;
+    const bool tp = v->taps != nullptr;
     const q3tts_vocoder_config& c = v->c;
     const int ns = cl.ns, nf = cl.nf, d = c.latent_dim, HH = c.n_head * c.head_dim, M = ns * nf;
     hist_all(s, cl, cld, v, nf, 0);
@@ -1711,31 +1734,42 @@ static int voc_call_body(q3tts_engine* e, const VCall& cl, hipStream_t s) {
         const uint16_t* a_in = (const uint16_t*)v->xnb;
         for (size_t ui = 0; ui < v->U.size(); ++ui) {
             VUp& p = v->U[ui];
+            if (tp) vtap(v, s, a_in, 1, 1, 0, T, d, "up%d.in", (int)ui);
             Q3BGemm g{}; g.a = a_in; g.B = ns * T; g.w = p.ct_t; g.K = d; g.N = p.r * d; g.epi = Q3_EPI_STORE;  // [T][r*d] == [T*r][d]
             g.bias = p.ct.b; g.bias_n = p.ct.bias_n; g.y = p.dw_in.p + (size_t)p.dw_in.H * d; g.ldy = p.r * d; g.seg_rows = T; g.seg_stride = p.dw_in.stride();
             if (q3_launch_bgemm(g, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder: upsample ConvTranspose GEMM shape");
             T *= p.r;
+            if (tp) vtap_buf(v, s, p.dw_in, T, "up%d.raw", (int)ui);
             hipLaunchKernelGGL(k_voc_dw_ln, dim3(T, ns), dim3(64), (size_t)d * 4, s, p.dw_in.p, p.dw_in.stride(), p.dw_in.H, T, d, p.dw_w, p.dw_b, p.ln_w, p.ln_b, v->t1, 1);
+            if (tp) vtap(v, s, v->t1, 1, 1, 0, T, d, "up%d.ln", (int)ui);
             hist(s, cl, cld, p.dw_in, T, 1);  // history = the raw ConvTranspose output, saved before the in-place residual below
             Q3BGemm h{}; h.a = (const uint16_t*)v->t1; h.B = ns * T; h.w = p.pw1_t; h.K = d; h.N = 4 * d; h.epi = Q3_EPI_GELU;
             h.bias = p.pw1.b; h.bias_n = p.pw1.bias_n; h.yb = (uint16_t*)v->t2;
             if (q3_launch_bgemm(h, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder: pointwise-1 GEMM shape");
+            if (tp) vtap(v, s, v->t2, 1, 1, 0, T, 4 * d, "up%d.gelu", (int)ui);
             Q3BGemm r{}; r.a = (const uint16_t*)v->t2; r.B = ns * T; r.w = p.pw2_t; r.K = 4 * d; r.N = d; r.epi = Q3_EPI_RESID;  // residual in place
             r.bias = p.pw2.b; r.bias_n = p.pw2.bias_n; r.col_scale = p.gamma; r.y = p.dw_in.p + (size_t)p.dw_in.H * d; r.ldy = d; r.seg_rows = T; r.seg_stride = p.dw_in.stride();
             if (ui + 1 < v->U.size()) r.yb = v->upb;  // the next stage's GEMM input
             if (q3_launch_bgemm(r, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder: pointwise-2 GEMM shape");
+            if (tp) vtap_buf(v, s, p.dw_in, T, "up%d.out", (int)ui);
             a_in = v->upb;
             cur = p.dw_in.p; cur_stride = p.dw_in.stride(); cur_off = p.dw_in.H * d;
         }
     } else {
         hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, v->final_norm, c.rms_eps, d, v->xn, 0);
-        for (auto& p : v->U) {
+        for (size_t ui = 0; ui < v->U.size(); ++ui) {
+            VUp& p = v->U[ui];
+            if (tp) vtap(v, s, cur + cur_off, 0, 0, 0, T, d, "up%d.in", (int)ui);
             vgemm(s, p.ct, cur, cur_stride, cur_off, ns, T, p.dw_in.p, p.dw_in.stride(), p.dw_in.H * d);  // [T][r*d] == [T*r][d]
             T *= p.r;
+            if (tp) vtap_buf(v, s, p.dw_in, T, "up%d.raw", (int)ui);
             hipLaunchKernelGGL(k_voc_dw_ln, dim3(T, ns), dim3(64), (size_t)d * 4, s, p.dw_in.p, p.dw_in.stride(), p.dw_in.H, T, d, p.dw_w, p.dw_b, p.ln_w, p.ln_b, v->t1, 0);
+            if (tp) vtap(v, s, v->t1, 0, 0, 0, T, d, "up%d.ln", (int)ui);
             hist(s, cl, cld, p.dw_in, T, 1);  // history = the raw ConvTranspose output, saved before the in-place residual below
             vgemm(s, p.pw1, v->t1, (size_t)T * d, 0, ns, T, v->t2, (size_t)T * 4 * d, 0, 3);
+            if (tp) vtap(v, s, v->t2, 0, 0, 0, T, 4 * d, "up%d.gelu", (int)ui);
             vgemm(s, p.pw2, v->t2, (size_t)T * 4 * d, 0, ns, T, p.dw_in.p, p.dw_in.stride(), p.dw_in.H * d, 1, p.gamma, d);  // residual in place
+            if (tp) vtap_buf(v, s, p.dw_in, T, "up%d.out", (int)ui);
             cur = p.dw_in.p; cur_stride = p.dw_in.stride(); cur_off = p.dw_in.H * d;
         }
     }
@@ -1763,6 +1797,7 @@ static int voc_call_body(q3tts_engine* e, const VCall& cl, hipStream_t s) {
             vgemm(s, k.ct, k.ct_in.p, k.ct_in.stride(), k.ct_in.H * k.cin, ns, T, o, (size_t)T * k.r * k.cout, 0, 0, nullptr, 1, &sk, 1, 1);
         }
         T *= k.r; ch = k.cout;
+        if (tp) vtap(v, s, o, 0, 0, 0, T, ch, "b%d.o_ct", (int)bi);
         for (int u = 0; u < 3; ++u) {
             VRes& r = k.res[u];
             if (resunit_ok(ch)) {  // narrow blocks: the whole residual unit in one pass over HBM
@@ -1771,17 +1806,20 @@ static int voc_call_body(q3tts_engine* e, const VCall& cl, hipStream_t s) {
                 else if (bi + 1 < v->Bk.size()) { VBlk& nx = v->Bk[bi + 1]; sk = snake_into(nx.ct_in, nx.ea, nx.ib, ch); }
                 else { sk = snake_into(v->out_in, v->oea, v->oib, ch); }
                 launch_resunit(s, r, ns, T, ch, o, u < 2 ? 1 : 0, sk);
+                if (tp && u < 2) vtap(v, s, o, 0, 0, 0, T, ch, "b%d.r%d.o", (int)bi, u);  // (the last unit's sum only exists as the next SnakeBeta's input)
                 continue;
             }
             {
                 VSnake sk; sk.y2 = z; sk.stride = (size_t)T * ch; sk.off = 0; sk.ea = r.ea2; sk.ib = r.ib2; sk.n = ch; sk.bf16 = 1;  // snake2 -> z (bf16)
                 vgemm(s, r.c1, r.c1_in.p, r.c1_in.stride(), r.c1_in.H * ch, ns, T, z, (size_t)T * ch, 0, 0, nullptr, 1, &sk, 0, 1);
+                if (tp) vtap(v, s, z, 1, 0, 0, T, ch, "b%d.r%d.z", (int)bi, u);
             }
             VSnake sk;
             if (u < 2) { sk = snake_into(k.res[u + 1].c1_in, k.res[u + 1].ea, k.res[u + 1].ib, ch); }
             else if (bi + 1 < v->Bk.size()) { VBlk& nx = v->Bk[bi + 1]; sk = snake_into(nx.ct_in, nx.ea, nx.ib, ch); }
             else { sk = snake_into(v->out_in, v->oea, v->oib, ch); }
             vgemm(s, r.c2, z, (size_t)T * ch, 0, ns, T, o, (size_t)T * ch, 0, 2, nullptr, 1, &sk, u < 2 ? 1 : 0, 1);  // o += conv k1
+            if (tp && u < 2) vtap(v, s, o, 0, 0, 0, T, ch, "b%d.r%d.o", (int)bi, u);
         }
     }
     // V6
@@ -1794,6 +1832,18 @@ static int voc_call_body(q3tts_engine* e, const VCall& cl, hipStream_t s) {
     } else
         hipLaunchKernelGGL(k_voc_out, dim3((T + 63) / 64, ns), dim3(256), (size_t)(70 * (ch + 1) + 7 * ch) * 4, s, cld, v->out_in.p, v->out_in.stride(), v->out_in.H, T, ch, v->out_w, v->out_b,
                            v->pcm, v->pcm_stride, v->spf);
+    if (tp) {  // the convolutions' work buffers as the MFMAs consumed them (history rows first; each is written once per call), and the call's PCM
+        int Tb = nf; for (auto& p : v->U) Tb *= p.r;
+        vtap_buf(v, s, v->dec_in_in, Tb, "dec_in.in");
+        for (size_t bi = 0; bi < v->Bk.size(); ++bi) {
+            VBlk& k = v->Bk[bi];
+            vtap_buf(v, s, k.ct_in, Tb, "b%d.ct_in", (int)bi);
+            Tb *= k.r;
+            for (int u = 0; u < 3; ++u) vtap_buf(v, s, k.res[u].c1_in, Tb, "b%d.r%d.c1_in", (int)bi, u);
+        }
+        vtap_buf(v, s, v->out_in, Tb, "out.in");
+        vtap(v, s, v->pcm + (size_t)cl.slot[0] * v->pcm_stride + (size_t)cl.pos[0] * v->spf, 0, 0, 0, Tb, 1, "pcm");
+    }
     hist_all(s, cl, cld, v, nf, 1);
     Q3_HIP(e, hipGetLastError());
     return Q3TTS_OK;
@@ -1824,7 +1874,7 @@ static int voc_call(q3tts_engine* e, const VCall& cl, hipStream_t s) {
         Q3_HIP(e, hipEventRecord(v->call_ev[i], s));
     }
     static const bool no_graph = [] { const char* ev = getenv("Q3TTS_VOC_NO_GRAPH"); return ev && atoi(ev); }();
-    if (no_graph) return voc_call_body(e, cl, s);
+    if (no_graph || v->taps) return voc_call_body(e, cl, s);  // a tapped call runs eagerly and is never recorded or captured
     const unsigned long long key = voc_call_key(cl);
     auto it = v->call_graphs.find(key);
     if (it == v->call_graphs.end()) {
@@ -1930,6 +1980,41 @@ extern "C" int q3tts_k_vocoder_latent(q3tts_engine* e, const int32_t* codes, int
         }
     }
     Q3_HIP(e, hipStreamSynchronize(s));
+    return Q3TTS_OK;
+}
+
+// Test hook: slot 0 driven exactly as q3tts_k_vocoder drives it (same reset, same split into calls of <= VOC_FCAP frames, same launches:
+// voc_call_body itself), and call number tap_call (0-based) runs with the tap sink set — see vtap() and include/q3tts.h. The calls before
+// it go through voc_call as always (eager the first time, then the captured graph); the drive ends after the tapped call.
+extern "C" int q3tts_k_vocoder_taps(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, int32_t tap_call, void* buf,
+                                    uint64_t buf_bytes, q3tts_voc_tap* recs, int32_t rec_cap, int32_t* n_recs) {
+    Q3_NOT_IN_SESSION(e);
+    if (!e || !codes || !buf || !recs || !n_recs || n_frames <= 0 || tap_call < 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
+    if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "engine created with with_vocoder = 0");
+    if (n_frames > e->cfg.max_steps_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "n_frames exceeds max_steps_cap");
+    Q3_HIP(e, hipSetDevice(e->cfg.device));
+    const int ncb = e->cfg.model.n_codebooks;
+    hipStream_t s = e->stream;
+    Q3_HIP(e, hipMemcpyAsync(e->codes, codes, sizeof(int32_t) * (size_t)n_frames * ncb, hipMemcpyHostToDevice, s));  // slot 0
+    VTRY(q3_voc_reset(e, 0));
+    VTapSink sink; sink.buf = (uint8_t*)buf; sink.cap = (size_t)buf_bytes; sink.recs = recs; sink.rec_cap = rec_cap;
+    const int step = chunk_frames > 0 ? chunk_frames : n_frames;
+    int call = 0, rc = Q3TTS_OK; bool done = false;
+    for (int f = 0; f < n_frames && !done && rc == Q3TTS_OK; f += step) {
+        const int n = std::min(step, n_frames - f);
+        for (int f1 = f; f1 < f + n && !done && rc == Q3TTS_OK; f1 += VOC_FCAP, ++call) {  // q3_voc_decode's own split, one call at a time
+            const int n1 = std::min(VOC_FCAP, f + n - f1);
+            if (call == tap_call) { e->voc->taps = &sink; done = true; }
+            rc = q3_voc_decode(e, 0, f1, n1, f1 + n1 >= n_frames, s);
+            e->voc->taps = nullptr;
+        }
+    }
+    const hipError_t er = hipStreamSynchronize(s);  // (the copies land in the caller's buffer: nothing may outlive this call)
+    VTRY(rc);
+    Q3_HIP(e, er);
+    if (!done) return q3_set_err(e, Q3TTS_ERR_INVALID, "tap_call is past the last call of this drive");
+    if (sink.overflow) return q3_set_err(e, Q3TTS_ERR_INVALID, "tap buffer or record table too small");
+    *n_recs = sink.n;
     return Q3TTS_OK;
 }
 

@@ -312,6 +312,31 @@ class NativeEngine:
         self._check(self.lib.q3tts_k_vocoder_latent(self.h, _ptr(c, i32p), c.shape[0], chunk_frames, _ptr(out, f32p)), "q3tts_k_vocoder_latent")
         return out
 
+    def vocoder_taps(self, codes, chunk_frames=0, tap_call=0, buf_bytes=160 << 20):
+        """The convolution half of vocoder call `tap_call` (slot 0 driven as vocoder() drives it; calls of <= 4 frames numbered from 0) as
+        {name: (array[hist_rows + rows][channels], hist_rows)}: f32 taps as float32, bf16 taps as uint16 bits, A-tiled taps untiled
+        (q3tts_k_vocoder_taps; the names are listed in include/q3tts.h)."""
+        c = np.ascontiguousarray(codes, dtype=np.int32)
+        buf = np.empty(buf_bytes, dtype=np.uint8)
+        recs = (_abi.VocTap * 256)()
+        n = C.c_int32()
+        self._check(self.lib.q3tts_k_vocoder_taps(self.h, _ptr(c, i32p), c.shape[0], chunk_frames, tap_call, buf.ctypes.data, buf.size, recs, 256,
+                                                  C.byref(n)), "q3tts_k_vocoder_taps")
+        out = {}
+        for r in recs[:n.value]:
+            H, T, K = r.hist_rows, r.rows, r.channels
+            dt = np.uint16 if r.dtype else np.float32
+            if r.layout:   # q3_atile_off(row, k, K / 32), csrc/q3_kernels.h
+                flat = np.frombuffer(buf, dtype=dt, count=((H + T + 15) // 16) * 16 * K, offset=r.offset)
+                row, k = np.arange(H + T)[:, None], np.arange(K)[None, :]
+                cc = k & 31
+                off = ((((row >> 4) * (K >> 5) + (k >> 5)) * 64 + ((cc & 15) >> 2) * 16 + (row & 15)) << 3) + (cc & 3) + ((cc & 16) >> 2)
+                a = flat[off]
+            else:
+                a = np.frombuffer(buf, dtype=dt, count=(H + T) * K, offset=r.offset).reshape(H + T, K).copy()
+            out[r.name.decode()] = (a, H)
+        return out
+
 
 class NativePrefix:
     """q3tts_prefix: a voice part's Talker K/V on the device of one engine (NativeEngine.create_prefix). close() is refused while a session

@@ -26,6 +26,21 @@ _lib = None
 VOC_LATENT_TOL = 4e-5         # frames >= 71
 VOC_LATENT_TOL_EARLY = 1e-4   # frames < 71
 
+# The vocoder's convolution half, stage by stage against float64 (tests/_voc_ref.py, tests/test_vocoder_stages_{cpu,gpu}.py). R below is
+# NOT taken from device output: it is the worst error of the CPU restatement of each stage against float64 on the bf16-input oracle's
+# own activations (4 frames, random codes and one repeated frame), per element, normalised by sqrt(sum_i (x_i w_i)^2) — for the GEMM
+# stages the chain of q3o_mfma_bf16_dot32 (the pinned model of v_mfma_f32_16x16x32_bf16, which truncates) over K in the kernels' vstep
+# order, for k_voc_dw_ln and the output convolution the oracle's sequential f32 code on the scale written in _voc_ref.check_call.
+# Produced by `python tools/voc_stage_bounds.py` (CPU only, ~4 minutes). The device's bound for a stage is 4 R (VOC_STAGE_MARGIN): it
+# sums the same K in another grouping (K slices, split accumulators), so its error has this scale but not this value, while an
+# indexing error is of order 1 on it. Element-wise f32 roundings, sinf / erff and the bf16 output step are added as stated in _voc_ref.
+VOC_STAGE_MARGIN = 4.0
+VOC_STAGE_R = {
+    "tiny": {"blk_ct": 1.84e-06, "dec_in": 1.30e-06, "dw_ln": 1.17e-07, "out": 4.35e-07, "pw1": 3.93e-07, "pw2": 6.29e-07, "res_c1": 2.79e-06, "res_c2": 1.05e-06, "up_ct": 3.08e-07},
+    "narrow": {"blk_ct": 2.56e-06, "dec_in": 9.05e-07, "dw_ln": 1.17e-07, "out": 5.85e-07, "pw1": 3.93e-07, "pw2": 6.29e-07, "res_c1": 3.13e-06, "res_c2": 1.31e-06, "up_ct": 3.08e-07},
+    "full": {"blk_ct": 3.48e-06, "dec_in": 5.05e-06, "dw_ln": 2.02e-07, "out": 4.99e-07, "pw1": 1.97e-06, "pw2": 4.31e-06, "res_c1": 5.12e-06, "res_c2": 1.95e-06, "up_ct": 1.69e-06},
+}
+
 
 def build():
     subprocess.check_call(["make", "-C", ORACLE_DIR, "libq3oracle.so"], stdout=subprocess.DEVNULL)
