@@ -105,7 +105,17 @@ typedef struct q3tts_engine_config {
                                * MFMA product scaled by f32(d)) — the reference's default quantisation (gguf_q8_0,
                                * src/tts/engine.rs:91-95). Q8_0 tensors of weights_path are kept as stored; other tensor types and the
                                * synthetic weights are quantised with ggml's reference rule. 0 (default): bf16 weights. The Predictor
-                               * keeps bf16 weights either way (157 MB, Infinity-Cache resident: its launches are latency-bound). */
+                               * keeps bf16 weights either way (157 MB, Infinity-Cache resident: its launches are latency-bound).
+                               * 2: W8A8 — as 1, and every Talker GEMM's ACTIVATIONS are Q8_0 blocks too, multiplied in ggml's
+                               * Q8_0 x Q8_0 arithmetic on the int8 MFMA (exact int32 block sums x f32(d_w) * d_x): what
+                               * llama.cpp computes for a gguf_q8_0 directory, and what the Python API and the Rust shim select for
+                               * quant = "q8_0". An activation is quantised where it is produced, from the UN-normalised v = x * nw, so
+                               * its block scale carries the magnitude of the residual stream: it is d = amax / 127 rounded to f16's
+                               * 11-bit significand but stored as f32 (weight scales stay f16 as in the file). Pinned by
+                               * tests/test_q8_scales_{cpu,gpu}.py over rows scaled by 2^-24 .. 2^+24: bit-identical GEMM output under
+                               * power-of-two scaling (eps = 0), float64 accuracy within the measured margin of ggml's order
+                               * (quantise the normalised row), f16 weight scales down to 0x0001 and up to 0x7BFF. Non-finite inputs
+                               * are not defined. */
     int32_t vocoder_flush_tail; /* Only matters with vocoder.lookahead_frames > 0 (V4). 0 (default): as the reference — its vocoder thread sends
                                * is_last only with a non-empty final buffer (src/tts/engine.rs:510-536), so an utterance of n_frames % 4 == 0
                                * never flushes the withheld look-ahead tail and its audio ends lookahead_frames short (restated by the oracle's
@@ -481,13 +491,13 @@ int q3tts_k_bgemm_q8(int32_t device, const uint16_t* xb, int32_t B, int32_t K, c
                      int32_t ntiles, int32_t d_norm, float eps, int32_t epilogue, const float* nw_next, float* y, uint16_t* yb, float* ssp_out,
                      uint64_t* keys, int32_t iters, float* mean_kernel_ms);
 /* The same launch in ggml's Q8_0 x Q8_0 arithmetic (W8A8: csrc/q3_bgemm8.hip; q3tts_engine_config.talker_q8_0 = 2): the
- * ACTIVATIONS are Q8_0 blocks too — aq int8 [B][K], ad their f16 scales as bit patterns [B][K/32] — a block's product is its exact int32
- * sum times f32(d_w) * f32(d_x). epilogue 0: y = s_r * RAW; 1: y += RAW, then the consumer's operand v = y * nw_next quantised per 32
- * columns by ggml's rule -> yq int8 [B][N], yd f16 [B][N/32], and ssp_out; 2: h = swiglu(s_r * RAW_gate, s_r * RAW_up) quantised ->
- * yq [B][N/2], yd [B][N/64]. K % 512 == 0; N % 32 == 0 (1: % 64, 2: % 128). Equals oracle q3o_bgemm_q8a8 bit for bit. */
-int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const uint16_t* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N,
+ * ACTIVATIONS are Q8_0 blocks too — aq int8 [B][K], ad their block scales as f32 [B][K/32] (the producers store d = amax / 127 rounded to
+ * f16's 11-bit significand but kept in f32; any f32 is accepted) — a block's product is its exact int32 sum times f32(d_w) * d_x. epilogue 0: y = s_r * RAW; 1: y += RAW, then the consumer's operand v = y * nw_next quantised per 32
+ * columns by ggml's rule -> yq int8 [B][N], yd f32 [B][N/32], and ssp_out; 2: h = swiglu(s_r * RAW_gate, s_r * RAW_up) quantised ->
+ * yq [B][N/2], yd [B][N/64]. K % 512 == 0; N % 32 == 0 (1: % 64, 2: % 128). Equals oracle q3o_bgemm_q8a8_f32 bit for bit. */
+int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const float* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N,
                        const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epilogue, const float* nw_next, float* y, int8_t* yq,
-                       uint16_t* yd, float* ssp_out, int32_t iters, float* mean_kernel_ms);
+                       float* yd, float* ssp_out, int32_t iters, float* mean_kernel_ms);
 /* The same GEMM with the epilogue extras only the vocoder uses (nothing in the reference: its vocoder is an ONNX graph, src/models/onnx.rs:342-459):
  * bias[col % bias_n] added to RAW first; epilogue 0: y = RAW + bias; 1: y += col_scale[col] * (RAW + bias), optionally yb = bf16(y);
  * 4: yb = bf16(gelu_erf(RAW + bias)). seg_rows > 0: the f32 rows live in B / seg_rows segments separated by gap_rows rows the kernel

@@ -506,6 +506,7 @@ void q3o_permute_rows_bf16(const uint16_t* src, int32_t rows, int32_t K, uint16_
 void q3o_bgemm_raw_p(const uint16_t* xp, int32_t rows, int32_t K, const uint16_t* wp, int32_t N, float* out, int32_t ldo, int32_t threads);
 void q3o_bgemm_q8_raw_p(const uint16_t* xp, int32_t rows, int32_t K, const uint16_t* qp, const float* dsc, int32_t N, float* out, int32_t ldo, int32_t threads);
 void q3o_quantize_q8_0(const float* x, int64_t n, int8_t* q, uint16_t* d_f16);
+void q3o_quantize_q8_0_act(const float* x, int64_t n, int8_t* q, float* ds);
 void q3o_permute_rows_q8(const int8_t* src, int32_t rows, int32_t K, uint16_t* dst);
 void q3o_bgemm_q8a8_raw(const int8_t* qa, const float* da, int32_t rows, int32_t K, const uint16_t* qp, const float* dsc, int32_t N, float* out,
                         int32_t ldo, int32_t threads);
@@ -639,12 +640,10 @@ static void bgemm_rows(const uint16_t* ab, int n, int K, const uint16_t* wp, con
 /* W8A8: f32 activation rows v [n][K] -> ggml Q8_0 blocks -> RAW against a Q8_0 matrix (q3_oracle_bf16.c) */
 static void bgemm_rows_a8(const float* v, int n, int K, const uint16_t* wp, const float* dsc, int N, float* out, int ldo) {
     int8_t* qa = (int8_t*)malloc((size_t)n * K);
-    uint16_t* d16 = (uint16_t*)malloc((size_t)n * (K / 32) * 2);
-    float* da = (float*)malloc((size_t)n * (K / 32) * 4);
-    for (int r = 0; r < n; ++r) q3o_quantize_q8_0(v + (size_t)r * K, K, qa + (size_t)r * K, d16 + (size_t)r * (K / 32));
-    for (size_t i = 0; i < (size_t)n * (K / 32); ++i) da[i] = q3o_f16_to_f32(d16[i]);
+    float* da = (float*)malloc((size_t)n * (K / 32) * 4);   /* activation scales: 11-bit significand in f32 (q3o_round_sig11) */
+    for (int r = 0; r < n; ++r) q3o_quantize_q8_0_act(v + (size_t)r * K, K, qa + (size_t)r * K, da + (size_t)r * (K / 32));
     q3o_bgemm_q8a8_raw(qa, da, n, K, wp, dsc, N, out, ldo, g_threads > 0 ? g_threads : 1);
-    free(qa); free(d16); free(da);
+    free(qa); free(da);
 }
 
 /* One transformer over n rows (positions pos0.. of one sequence), canonical arithmetic. x [n][d] is the f32 residual stream,

@@ -110,6 +110,12 @@ void q3o_project_rows(const float* w, const float* bias, int32_t n_in, int32_t n
 void q3o_set_arith(q3o_model* m, int32_t arith);
 void q3o_set_talker_q8a8(q3o_model* m);  /* ... and the activations as Q8_0 blocks too: ggml's W8A8 (q3tts_engine_config.talker_q8_0 = 2; q3_oracle_bf16.c) */
 void q3o_quantize_rows_q8(const float* v, int32_t rows, int32_t K, int8_t* q, uint16_t* d_f16);
+/* an activation block's scale: d rounded to f16's 11-bit significand (nearest even), kept in f32 (no f16 exponent limit) */
+float q3o_round_sig11(float d);
+void q3o_quantize_q8_0_act(const float* x, int64_t n, int8_t* q, float* ds);  /* ggml's quantiser on an activation row: scales as above */
+void q3o_bgemm_q8a8_f32(const int8_t* aq, const float* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N, const float* ssp,
+                    int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, float* yd, float* ssp_out);
+/* ... with the activation scales as f16 bit patterns in and out (exact wherever they are normal f16) */
 void q3o_bgemm_q8a8(const int8_t* aq, const uint16_t* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N, const float* ssp,
                     int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, uint16_t* yd, float* ssp_out);
 void q3o_set_talker_q8(q3o_model* m);  /* the Talker's matrices + lm_head as ggml Q8_0 blocks, canonical Q8 order (q3tts_engine_config.talker_q8_0) */

@@ -250,6 +250,26 @@ void q3o_quantize_q8_0(const float* x, int64_t n, int8_t* q, uint16_t* d_f16) {
         for (int i = 0; i < 32; ++i) q[b * 32 + i] = (int8_t)roundf(x[b * 32 + i] * id);
     }
 }
+/* The scale of a W8A8 ACTIVATION block: d rounded to f16's 11-bit significand, nearest even — exactly what the f16
+ * conversion does to a value in f16's normal range — but kept in an f32 container, so it has f16's precision without f16's exponent
+ * range: a block of any f32 magnitude keeps a 11-bit scale (an f16 scale is subnormal below amax = 127 * 2^-14, zero below 127 * 2^-25 and
+ * infinite above 127 * 65504, and the activations here carry the magnitude of the un-normalised residual stream). Integer code: the carry
+ * runs into the exponent correctly; d <= FLT_MAX / 127 cannot overflow. Weight scales stay f16 as the file stores them. */
+float q3o_round_sig11(float d) {
+    uint32_t u = f2u(d);
+    u += 0xfffu + ((u >> 13) & 1u);
+    return u2f(u & ~0x1fffu);
+}
+/* ggml's quantiser on an activation row: as q3o_quantize_q8_0, the scale kept as q3o_round_sig11(d) in f32 */
+void q3o_quantize_q8_0_act(const float* x, int64_t n, int8_t* q, float* ds) {
+    for (int64_t b = 0; b < n / 32; ++b) {
+        float amax = 0.0f;
+        for (int i = 0; i < 32; ++i) { const float a = fabsf(x[b * 32 + i]); if (a > amax) amax = a; }
+        const float d = amax / 127.0f, id = d != 0.0f ? 1.0f / d : 0.0f;
+        ds[b] = q3o_round_sig11(d);
+        for (int i = 0; i < 32; ++i) q[b * 32 + i] = (int8_t)roundf(x[b * 32 + i] * id);
+    }
+}
 static inline uint16_t int8_bf16(int8_t v) { return (uint16_t)(f2u((float)v) >> 16); }  /* exact: |v| <= 128 */
 /* natural-order int8 rows [rows][K] -> bf16 rows in the MFMA operand order (the same permutation as q3o_permute_rows_bf16) */
 void q3o_permute_rows_q8(const int8_t* src, int32_t rows, int32_t K, uint16_t* dst) {
@@ -286,14 +306,17 @@ void q3o_bgemm_q8_raw_p(const uint16_t* xp, int32_t rows, int32_t K, const uint1
 /* ------------------------------------------------------------------------------------------ */
 /* W8A8 (q3tts_engine_config.talker_q8_0 = 2): Q8_0 weights against Q8_0 ACTIVATIONS, the arithmetic of ggml's             */
 /* vec_dot_q8_0_q8_0 — what llama.cpp computes for the reference's default gguf_q8_0 directory (src/tts/engine.rs:91-95): the f32          */
-/* activation row is quantised per block of 32 by ggml's rule (q3o_quantize_q8_0: d = amax / 127, q = roundf(x / d), d kept as f16), a      */
+/* activation row is quantised per block of 32 by ggml's rule (q3o_quantize_q8_0_act: d = amax / 127, q = roundf(x / d), d rounded to f16's */
+/* 11-bit significand and kept in f32: q3o_round_sig11), a                                                                                */
 /* block's product is the EXACT int32 sum of its 32 int8 products times (f32(d_w) * f32(d_x)) — one f32 product of the scales, one of the   */
 /* (exactly converted) integer, one f32 add, no fused multiply-add: `sumf += sumi * (dx * dy)` as ggml's scalar code spells it — blocks     */
 /* ascending inside a K slice from t = +0, the 8 slices added in order as everywhere: RAW = ((t_0 + t_1) + ...) + t_7.                      */
 /* Stated difference to ggml: the split RMSNorm stays — the quantiser sees v = x * nw and the row scale s_r multiplies RAW afterwards        */
-/* (ggml quantises s_r * x * nw; s_r > 0 commutes through amax / 127 and the rounding up to f32 rounding).                                  */
+/* (ggml quantises s_r * x * nw, whose amax is O(1) whatever the row's magnitude; here the block scale carries the magnitude of the       */
+/* residual stream, which is why it is not stored as f16: with the 11-bit scale in f32 a row scaled by 2^e gives the same quants and,     */
+/* with eps = 0, bit-identical GEMM output over the f32 range: tests/test_q8_scales_cpu.py).                                               */
 /* ------------------------------------------------------------------------------------------ */
-/* qa int8 [rows][K] and da = f32(f16 d) [rows][K/32] in natural order; qp = the weight quants as permuted bf16-coded rows (q3o_permute_rows_q8) */
+/* qa int8 [rows][K] and da = the f32 block scales [rows][K/32] in natural order; qp = the weight quants as permuted bf16-coded rows (q3o_permute_rows_q8) */
 void q3o_bgemm_q8a8_raw(const int8_t* qa, const float* da, int32_t rows, int32_t K, const uint16_t* qp, const float* dsc, int32_t N, float* out,
                         int32_t ldo, int32_t threads) {
     const int per = K / 256, kb = K / 32;
@@ -411,19 +434,17 @@ void q3o_bgemm_q8(const uint16_t* xb, int32_t B, int32_t K, const int8_t* q, con
     bgemm_epilogues(raw, B, N, ssp, ntiles, d_norm, eps, epi, nw_next, y, yb, ssp_out, keys);
     free(raw); free(dsc); free(qp); free(xp);
 }
-/* The W8A8 launch (q3tts_k_bgemm_q8a8): activations already as Q8_0 blocks (aq int8 [B][K], ad f16 bits [B][K/32]), weights q / d as in
+/* The W8A8 launch (q3tts_k_bgemm_q8a8), scales as the kernels hold them: activations already as Q8_0 blocks (aq int8 [B][K], ad f32 scales [B][K/32]), weights q / d as in
  * q3o_bgemm_q8. Epilogues: 0: y = s * RAW; 1: y += RAW, then the consumer's operand: v = y * nw_next quantised per 32 columns -> yq int8 [B][N],
- * yd f16 [B][N/32], and ssp_out; 2: h = swiglu(s * RAW_gate, s * RAW_up) (f32) quantised per 32 columns -> yq [B][N/2], yd [B][N/64]. */
-void q3o_bgemm_q8a8(const int8_t* aq, const uint16_t* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N, const float* ssp,
-                    int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, uint16_t* yd, float* ssp_out) {
+ * yd f32 [B][N/32], and ssp_out; 2: h = swiglu(s * RAW_gate, s * RAW_up) (f32) quantised per 32 columns -> yq [B][N/2], yd [B][N/64]. */
+void q3o_bgemm_q8a8_f32(const int8_t* aq, const float* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N, const float* ssp,
+                        int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, float* yd, float* ssp_out) {
     uint16_t* qp = (uint16_t*)malloc((size_t)N * K * 2);
     float* dsc = (float*)malloc((size_t)N * (K / 32) * 4);
-    float* da = (float*)malloc((size_t)B * (K / 32) * 4);
     float* raw = (float*)malloc((size_t)B * N * 4);
     q3o_permute_rows_q8(q, N, K, qp);
     for (size_t i = 0; i < (size_t)N * (K / 32); ++i) dsc[i] = q3o_f16_to_f32(d_f16[i]);
-    for (size_t i = 0; i < (size_t)B * (K / 32); ++i) da[i] = q3o_f16_to_f32(ad[i]);
-    q3o_bgemm_q8a8_raw(aq, da, B, K, qp, dsc, N, raw, N, 8);
+    q3o_bgemm_q8a8_raw(aq, ad, B, K, qp, dsc, N, raw, N, 8);
     for (int b = 0; b < B; ++b) {
         const float s = ssp ? q3o_row_scale(ssp + (size_t)b * ntiles, ntiles, d_norm, eps) : 1.0f;
         float* r = raw + (size_t)b * N;
@@ -433,18 +454,31 @@ void q3o_bgemm_q8a8(const int8_t* aq, const uint16_t* ad, int32_t B, int32_t K, 
             float* xr = y + (size_t)b * N;
             float* v = (float*)malloc((size_t)N * 4);
             for (int n = 0; n < N; ++n) { xr[n] = xr[n] + r[n]; v[n] = xr[n] * nw_next[n]; }
-            q3o_quantize_q8_0(v, N, yq + (size_t)b * N, yd + (size_t)b * (N / 32));
+            q3o_quantize_q8_0_act(v, N, yq + (size_t)b * N, yd + (size_t)b * (N / 32));
             for (int t = 0; t < N / 16; ++t) ssp_out[(size_t)b * (N / 16) + t] = q3o_tss16(xr + 16 * t);
             free(v);
         } else {
             const int F = N / 2;
             float* h = (float*)malloc((size_t)F * 4);
             for (int j = 0; j < F; ++j) h[j] = swiglu(s * r[j], s * r[F + j]);
-            q3o_quantize_q8_0(h, F, yq + (size_t)b * F, yd + (size_t)b * (F / 32));
+            q3o_quantize_q8_0_act(h, F, yq + (size_t)b * F, yd + (size_t)b * (F / 32));
             free(h);
         }
     }
-    free(raw); free(da); free(dsc); free(qp);
+    free(raw); free(dsc); free(qp);
+}
+/* The same launch with the activation scales going in and coming out as f16 bit patterns (ad [B][K/32]; yd [B][N/32] or [B][N/64]): f16
+ * scales widen exactly, and a produced scale in f16's normal range narrows exactly (it has 11 significant bits) — the form callers that keep
+ * Q8_0 blocks as ggml stores them use. Outside that range yd is the f16 rounding of the f32 scale: use q3o_bgemm_q8a8_f32 there. */
+void q3o_bgemm_q8a8(const int8_t* aq, const uint16_t* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N, const float* ssp,
+                    int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, uint16_t* yd, float* ssp_out) {
+    const size_t na = (size_t)B * (K / 32), ny = epi == 0 ? 0 : (size_t)B * ((epi == 2 ? N / 2 : N) / 32);
+    float* da = (float*)malloc(na * 4);
+    float* dy = ny ? (float*)malloc(ny * 4) : NULL;
+    for (size_t i = 0; i < na; ++i) da[i] = q3o_f16_to_f32(ad[i]);
+    q3o_bgemm_q8a8_f32(aq, da, B, K, q, d_f16, N, ssp, ntiles, d_norm, eps, epi, nw_next, y, yq, dy, ssp_out);
+    for (size_t i = 0; i < ny; ++i) yd[i] = f32_to_f16_rne(dy[i]);
+    free(dy); free(da);
 }
 static void bgemm_epilogues(float* raw, int32_t B, int32_t N, const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi,
                             const float* nw_next, float* y, uint16_t* yb, float* ssp_out, uint64_t* keys) {

@@ -9,10 +9,13 @@
 // RAW = ((t_0 + t_1) + ...) + t_7. No weight or activation is ever widened: 1.06 bytes per operand element on both sides.
 //
 // Operands: the weights in the tiled Q8 layout of q3_kernels.h (tile PAIR (n/16, k/64) = 1 KiB, f16 scales [N][K/32]); the activations
-// in the same form with rows in place of columns (q3_q8_off) and their block scales as [K/64][row tiles][4 row quads][2 blocks][4 rows] f16
-// (q3_q8_scale_idx): the 8 scales a lane needs for one (row tile, block pair) are one 16-byte load. Producers write both (this kernel's
+// in the same form with rows in place of columns (q3_q8_off) and their block scales as [K/64][row tiles][4 row quads][2 blocks][4 rows] f32
+// (q3_q8_scale_idx): the 8 scales a lane needs for one (row tile, block pair) are 32 consecutive bytes. A lane keeps only 16 of them in
+// registers — the 4 rows' scales of block (lane >> 2) & 1 of the pair — and takes the other block's from the lane 4 further in its row of
+// 16 (same rows, the other block) with one DPP move per value: the f32 scales cost the registers the f16 ones did. Producers write both (this kernel's
 // RESID / SWIGLU epilogues, the attention kernels, k_pred_next, k_norm_inputs): an activation is quantised where it is produced, from
-// its f32 value, by ggml's rule (d = amax / 127, id = d ? 1 / d : 0, q = roundf(v * id), d kept as f16).
+// its f32 value, by ggml's rule (d = amax / 127, id = d ? 1 / d : 0, q = roundf(v * id)), d rounded to f16's 11-bit significand and kept
+// in f32 (q3_q8_sig11: the activations carry the magnitude of the un-normalised residual stream, which an f16 exponent does not hold).
 //
 // Workgroup = 8 waves = the 8 K slices of one (16 RT) x (16 NT) tile, DP block pairs of operands in flight per wave; slice partials meet
 // in LDS and are added in slice order, as in q3_bgemm.hip. Epilogues: STORE (y = s_r RAW), RESID (x += RAW; the consumer's operand
@@ -23,8 +26,16 @@
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float b8_f16(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
+// as[..] of a lane holds block ((lane >> 2) & 1)'s scales; the value for block h: banks (4 lanes) of the other parity read the lane 4 further
+// round their row of 16 (row_ror:4 — the banks alternate, so either direction lands on the other block), the rest keep their own
+template <int H>
+__device__ __forceinline__ float b8_blk(float mine) {
+    const int m = __builtin_bit_cast(int, mine);
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(m, m, 0x124, 0xf, H ? 0x5 : 0xa, false));
+}
 __device__ __forceinline__ long b8_pack(uint32_t lo, uint32_t hi) { return (long)(((unsigned long)hi << 32) | (unsigned long)lo); }
 
 #define B8_PH(RT_, NT_) ((8 * (RT_) * (NT_) > 64) ? 2 : 1)  // slice-reduction phases: <= 64 KiB of LDS
@@ -41,14 +52,16 @@ __global__ __launch_bounds__(512) void k_bgemm8(Q3BGemm g) {
     }
     const int nb0 = cg * NT, row0 = rc * RT * 16, kblocks = g.K >> 5, kpairs = g.K >> 6, npair = g.K >> 9, kp0 = wave * npair;
     const int B = g.B;
-    // operand pointers: 16 bytes per lane per (tile, block pair)
-    const u32x4* ap[RT]; const u32x4* asp[RT];
+    // operands: 16 bytes per lane per (tile, block pair). The activation side as 32-bit offsets in 16-byte units from the (uniform) buffer
+    // bases — rows x K / 16 and rows x K / 128 of them: far below 2^31 — which keeps RT 64-bit pointer pairs out of the vector registers
+    const u32x4* const ab = (const u32x4*)g.a; const f32x4* const asb = (const f32x4*)g.ascale;
+    uint32_t ao[RT], aso[RT];
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
         const int R = g.a_row0 + min(row0 + 16 * i + r, B - 1);
-        ap[i] = (const u32x4*)g.a + ((size_t)(R >> 4) * kpairs + kp0) * 64 + kq * 16 + (R & 15);
+        ao[i] = (uint32_t)(((R >> 4) * kpairs + kp0) * 64 + kq * 16 + (R & 15));
         const int Rb = min(g.a_row0 + row0 + 16 * i, g.a_row0 + B - 1);   // (aligned: a_row0 is a multiple of 16; a row tile past the last row's re-reads that tile: its results are dropped)
-        asp[i] = (const u32x4*)g.ascale + ((size_t)kp0 * g.a_rt16 + (Rb >> 4)) * 4 + kq;
+        aso[i] = (uint32_t)(((kp0 * g.a_rt16 + (Rb >> 4)) * 4 + kq) * 2 + ((lane >> 2) & 1));
     }
     const u32x4* wq[NT]; const uint32_t* sq[NT];
 #pragma unroll
@@ -66,23 +79,22 @@ __global__ __launch_bounds__(512) void k_bgemm8(Q3BGemm g) {
             sp1[i] = lane + 64 < g.ntiles ? sp[lane + 64] : 0.0f;
         }
     }
-    u32x4 aq[DP][RT], as[DP][RT], bq[DP][NT]; uint32_t bs[DP][NT];
+    u32x4 aq[DP][RT], bq[DP][NT]; f32x4 as[DP][RT]; uint32_t bs[DP][NT];   // as: the scales of rows 4 kq + 0..3, block (lane >> 2) & 1 of the pair (b8_blk)
     auto load_pair = [&](int slot, int p) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) { bq[slot][j] = wq[j][(size_t)p * 64]; bs[slot][j] = sq[j][p]; }
 #pragma unroll
         for (int i = 0; i < RT; ++i) {
-            aq[slot][i] = ap[i][(size_t)p * 64];
-            if constexpr (ALIGNED) as[slot][i] = asp[i][(size_t)p * g.a_rt16 * 4];
+            aq[slot][i] = ab[ao[i] + (uint32_t)p * 64u];
+            if constexpr (ALIGNED) as[slot][i] = asb[aso[i] + (uint32_t)(p * g.a_rt16 * 8)];
             else {  // rows that do not start a tile (a single row picked out of a prefill batch): the lane's 4 rows x 2 blocks one by one
-                uint32_t sv[8];
+                float sv[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int Rr = g.a_row0 + min(row0 + 16 * i + 4 * kq + e, B - 1);
-                    const uint16_t* s8 = g.ascale + q3_q8_scale_idx(Rr, 2 * (kp0 + p), g.a_rt16);
-                    sv[e] = s8[0]; sv[4 + e] = s8[4];
+                    sv[e] = g.ascale[q3_q8_scale_idx(Rr, 2 * (kp0 + p) + ((lane >> 2) & 1), g.a_rt16)];
                 }
-                as[slot][i] = (u32x4){sv[0] | (sv[1] << 16), sv[2] | (sv[3] << 16), sv[4] | (sv[5] << 16), sv[6] | (sv[7] << 16)};
+                as[slot][i] = (f32x4){sv[0], sv[1], sv[2], sv[3]};
             }
         }
     };
@@ -133,8 +145,9 @@ __global__ __launch_bounds__(512) void k_bgemm8(Q3BGemm g) {
 #pragma unroll
                     for (int i = 0; i < RT; ++i) {
                         const long aa = h ? b8_pack(aq[dp][i].z, aq[dp][i].w) : b8_pack(aq[dp][i].x, aq[dp][i].y);
-                        const uint32_t s01 = h ? as[dp][i].z : as[dp][i].x, s23 = h ? as[dp][i].w : as[dp][i].y;  // f16 scales of rows 4 kq + 0..3
-                        const f32x2 dx01 = (f32x2){b8_f16(s01 & 0xffffu), b8_f16(s01 >> 16)}, dx23 = (f32x2){b8_f16(s23 & 0xffffu), b8_f16(s23 >> 16)};
+                        const f32x4 sm = as[dp][i];  // block h's scales of rows 4 kq + 0..3
+                        const f32x2 dx01 = h ? (f32x2){b8_blk<1>(sm.x), b8_blk<1>(sm.y)} : (f32x2){b8_blk<0>(sm.x), b8_blk<0>(sm.y)};
+                        const f32x2 dx23 = h ? (f32x2){b8_blk<1>(sm.z), b8_blk<1>(sm.w)} : (f32x2){b8_blk<0>(sm.z), b8_blk<0>(sm.w)};
 #pragma unroll
                         for (int j = 0; j < NT; ++j) {
                             const i32x4 P = __builtin_amdgcn_mfma_i32_16x16x32_i8(aa, bb[j], zero4, 0, 0, 0);
@@ -209,7 +222,7 @@ __global__ __launch_bounds__(512) void k_bgemm8(Q3BGemm g) {
                     if (live) {
                         ((int8_t*)g.yb)[q3_q8_off(row, col, g.N >> 6)] = (int8_t)(int)roundf(u[j] * id);
                         ((int8_t*)g.yb)[q3_q8_off(row, col + 16, g.N >> 6)] = (int8_t)(int)roundf(u[j + 1] * id);
-                        if (c == 0) g.yscale[q3_q8_scale_idx(row, col >> 5, g.y_rt16)] = __builtin_bit_cast(unsigned short, (_Float16)d);
+                        if (c == 0) g.yscale[q3_q8_scale_idx(row, col >> 5, g.y_rt16)] = q3_q8_sig11(d);
                     }
                 }
             } else {  // Q3_EPI_SWIGLU: gate = columns 0-7 of a tile, up = the same row 8 columns further
@@ -228,7 +241,7 @@ __global__ __launch_bounds__(512) void k_bgemm8(Q3BGemm g) {
                     if (live && c < 8) {
 #pragma unroll
                         for (int jj = 0; jj < 4; ++jj) ((int8_t*)g.yb)[q3_q8_off(row, (nb0 + j + jj) * 8 + c, g.N >> 7)] = (int8_t)(int)roundf(hv[j + jj] * id);
-                        if (c == 0) g.yscale[q3_q8_scale_idx(row, ((nb0 + j) * 8) >> 5, g.y_rt16)] = __builtin_bit_cast(unsigned short, (_Float16)d);
+                        if (c == 0) g.yscale[q3_q8_scale_idx(row, ((nb0 + j) * 8) >> 5, g.y_rt16)] = q3_q8_sig11(d);
                     }
                 }
             }

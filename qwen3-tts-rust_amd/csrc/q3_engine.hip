@@ -311,8 +311,8 @@ static int alloc_scratch(q3tts_engine* e, Q3Scratch& sc, int rows, int nqkv, int
 // Returns the number of launches the GEMM launcher refused (a shape it cannot run: stale activations would follow silently).
 static int run_layers(q3tts_engine* e, Q3Tfm& t, float* x, uint16_t* xb, float* ssp, int rows, const int* row_pos, const int* row_slot, Q3Scratch& sc,
                        hipStream_t s, bool one_row_per_slot = false, hipEvent_t* probe = nullptr, int slot_mod = 0, int pos_const = 0,
-                       const int* seg = nullptr, int n_seg = 0, int seg_max_n = 0, int seg_max_t = 0, uint16_t* xscale = nullptr, int x_rt16 = 0) {
-    // W8A8 (t.a8: the Talker with talker_q8_0 = 2): xb / sc.att / sc.h hold Q8_0 blocks (int8 quants + the f16 scales xscale / sc.asc_att /
+                       const int* seg = nullptr, int n_seg = 0, int seg_max_n = 0, int seg_max_t = 0, float* xscale = nullptr, int x_rt16 = 0) {
+    // W8A8 (t.a8: the Talker with talker_q8_0 = 2): xb / sc.att / sc.h hold Q8_0 blocks (int8 quants + the f32 block scales xscale / sc.asc_att /
     // sc.asc_h) and every GEMM runs q3_launch_bgemm8: ggml's Q8_0 x Q8_0 arithmetic
     auto gemm = [&](Q3BGemm& g) { return t.a8 ? q3_launch_bgemm8(g, s) : q3_launch_bgemm(g, s); };
     const float eps = e->cfg.model.rms_eps;
@@ -1783,8 +1783,8 @@ extern "C" int q3tts_k_bgemm_q8(int32_t device, const uint16_t* xb, int32_t B, i
 // residual result) through one hook: epi 0 (store) / 1 (residual) / 4 (GELU). y0 / y are dense [B][N]; with seg_rows > 0 the kernel
 // works on a buffer of B / seg_rows segments, each preceded by gap_rows sentinel rows that must come back untouched.
 // W8A8 (q3_bgemm8.hip): activations and weights as ggml Q8_0 blocks in natural order in / out; the hook tiles them for the device
-extern "C" int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const uint16_t* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N,
-                                  const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, uint16_t* yd,
+extern "C" int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const float* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N,
+                                  const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, float* yd,
                                   float* ssp_out, int32_t iters, float* mean_ms) {
     if (!aq || !ad || !q || !d_f16 || B <= 0 || K % 512 || K < 512 || N % 32 || epi < 0 || epi > 2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8 hook: K % 512 == 0, N % 32 == 0, epilogue 0..2");
     if (epi == Q3_EPI_SWIGLU && (N % 128 || !yq || !yd)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8 hook: swiglu needs N % 128 == 0, yq, yd");
@@ -1801,17 +1801,17 @@ extern "C" int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const uint16
             blk[0] = (uint8_t)(dd & 0xff); blk[1] = (uint8_t)(dd >> 8);
             memcpy(blk + 2, q + n * K + (size_t)b * 32, 32);
         }
-    std::vector<int8_t> at(B16 * K, 0); std::vector<uint16_t> ast((size_t)kb * B16, 0);
+    std::vector<int8_t> at(B16 * K, 0); std::vector<float> ast((size_t)kb * B16, 0.0f);
     for (int r = 0; r < B; ++r) {
         for (int k = 0; k < K; ++k) at[q3_q8_off(r, k, K >> 6)] = aq[(size_t)r * K + k];
         for (int b = 0; b < kb; ++b) ast[q3_q8_scale_idx(r, b, rt16)] = ad[(size_t)r * kb + b];
     }
     DevBuf dx, dxs, dw, dwt, dsc, ds, dn, dy, dyq, dys, dso;
-    if (dx.alloc(at.size()) || dxs.alloc(ast.size() * 2) || dw.alloc(blocks.size()) || dwt.alloc((size_t)N * K) || dsc.alloc((size_t)N * kb * 2) ||
+    if (dx.alloc(at.size()) || dxs.alloc(ast.size() * 4) || dw.alloc(blocks.size()) || dwt.alloc((size_t)N * K) || dsc.alloc((size_t)N * kb * 2) ||
         ds.alloc((size_t)B * (ntiles > 0 ? ntiles : 1) * 4) || dn.alloc((size_t)N * 4) || dy.alloc((size_t)B * N * 4) || dyq.alloc(B16 * Nout) ||
-        dys.alloc((size_t)(Nout / 32 + 2) * B16 * 2) || dso.alloc((size_t)B * (N / 16) * 4))
+        dys.alloc((size_t)(Nout / 32 + 2) * B16 * 4) || dso.alloc((size_t)B * (N / 16) * 4))
         return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    HK(hipMemcpy(dx.p, at.data(), at.size(), hipMemcpyHostToDevice)); HK(hipMemcpy(dxs.p, ast.data(), ast.size() * 2, hipMemcpyHostToDevice));
+    HK(hipMemcpy(dx.p, at.data(), at.size(), hipMemcpyHostToDevice)); HK(hipMemcpy(dxs.p, ast.data(), ast.size() * 4, hipMemcpyHostToDevice));
     HK(hipMemcpy(dw.p, blocks.data(), blocks.size(), hipMemcpyHostToDevice));
     if (ssp) HK(hipMemcpy(ds.p, ssp, (size_t)B * ntiles * 4, hipMemcpyHostToDevice));
     if (nw_next) HK(hipMemcpy(dn.p, nw_next, (size_t)N * 4, hipMemcpyHostToDevice));
@@ -1820,17 +1820,17 @@ extern "C" int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const uint16
     if (epi == Q3_EPI_SWIGLU) { f.mode = 1; f.src8_a = (const uint8_t*)dw.p; f.src8_b = (const uint8_t*)dw.p + (size_t)F * kb * 34; }
     else { f.mode = 0; f.row0 = 0; f.rows = N; f.src8_a = (const uint8_t*)dw.p; }
     q3_launch_fill_tiled_q8(f, nullptr);
-    Q3BGemm g{}; g.a = (const uint16_t*)dx.p; g.ascale = (const uint16_t*)dxs.p; g.a_rt16 = rt16; g.a_row0 = 0; g.B = B;
+    Q3BGemm g{}; g.a = (const uint16_t*)dx.p; g.ascale = (const float*)dxs.p; g.a_rt16 = rt16; g.a_row0 = 0; g.B = B;
     g.w = (const uint4*)dwt.p; g.wscale = (const uint16_t*)dsc.p; g.K = K; g.N = N;
     g.ssp = ssp ? (const float*)ds.p : nullptr; g.ld_ssp = ntiles; g.ntiles = ntiles; g.d_norm = d_norm; g.eps = eps; g.epi = epi;
-    g.y = (float*)dy.p; g.ldy = N; g.yb = (uint16_t*)dyq.p; g.yscale = (uint16_t*)dys.p; g.y_rt16 = rt16;
+    g.y = (float*)dy.p; g.ldy = N; g.yb = (uint16_t*)dyq.p; g.yscale = (float*)dys.p; g.y_rt16 = rt16;
     g.nw_next = nw_next ? (const float*)dn.p : nullptr; g.ssp_out = (float*)dso.p; g.ld_ssp_out = N / 16;
     if (q3_launch_bgemm8(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8: shape");
     HK(hipDeviceSynchronize());
     if (epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) HK(hipMemcpy(y, dy.p, (size_t)B * N * 4, hipMemcpyDeviceToHost));
     if (epi != Q3_EPI_STORE) {
-        std::vector<int8_t> qt(B16 * Nout); std::vector<uint16_t> st((size_t)(Nout / 32) * B16);
-        HK(hipMemcpy(qt.data(), dyq.p, qt.size(), hipMemcpyDeviceToHost)); HK(hipMemcpy(st.data(), dys.p, st.size() * 2, hipMemcpyDeviceToHost));
+        std::vector<int8_t> qt(B16 * Nout); std::vector<float> st((size_t)(Nout / 32) * B16);
+        HK(hipMemcpy(qt.data(), dyq.p, qt.size(), hipMemcpyDeviceToHost)); HK(hipMemcpy(st.data(), dys.p, st.size() * 4, hipMemcpyDeviceToHost));
         for (int r = 0; r < B; ++r) {
             for (int k = 0; k < Nout; ++k) yq[(size_t)r * Nout + k] = qt[q3_q8_off(r, k, Nout >> 6)];
             for (int b = 0; b < Nout / 32; ++b) yd[(size_t)r * (Nout / 32) + b] = st[q3_q8_scale_idx(r, b, rt16)];

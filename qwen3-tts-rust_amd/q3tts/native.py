@@ -571,15 +571,23 @@ def k_bgemm_q8(xb, q, d16, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=
 
 
 def k_bgemm_q8a8(aq, ad, q, d16, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=0, iters=0):
-    """The decoder's GEMM in ggml's Q8_0 x Q8_0 arithmetic (q3tts_k_bgemm_q8a8): activations aq int8 [B][K] + ad f16 bits [B][K/32], weights q / d16."""
+    """The decoder's GEMM in ggml's Q8_0 x Q8_0 arithmetic (q3tts_k_bgemm_q8a8): activations aq int8 [B][K] + their block scales ad [B][K/32], weights q / d16.
+    ad: f32 (what the W8A8 producers store: d rounded to f16's 11-bit significand, kept in f32; yd comes back as f32) or f16 bit patterns
+    (uint16: widened exactly; yd then comes back as f16 bit patterns too, exact wherever the produced scale is a normal f16)."""
     lib = _abi.load_library()
-    aq = np.ascontiguousarray(aq, dtype=np.int8); ad = np.ascontiguousarray(ad, dtype=np.uint16)
+    aq = np.ascontiguousarray(aq, dtype=np.int8); ad = np.asarray(ad)
+    as_f16 = ad.dtype == np.uint16
+    if as_f16:
+        ad = ad.view(np.float16).astype(np.float32)
+    elif ad.dtype != np.float32:
+        raise _abi.Q3Error(f"k_bgemm_q8a8: ad must be float32 or f16 bit patterns (uint16), got {ad.dtype}")
+    ad = np.ascontiguousarray(ad)
     q = np.ascontiguousarray(q, dtype=np.int8); d16 = np.ascontiguousarray(d16, dtype=np.uint16)
     B, K = aq.shape
     N = q.shape[0]
     nout = N // 2 if epi == 2 else N
     y = np.zeros((B, N), dtype=np.float32) if y0 is None else np.ascontiguousarray(y0, dtype=np.float32).copy()
-    yq = np.zeros((B, nout), dtype=np.int8); yd = np.zeros((B, nout // 32), dtype=np.uint16)
+    yq = np.zeros((B, nout), dtype=np.int8); yd = np.zeros((B, nout // 32), dtype=np.float32)
     sso = np.zeros((B, N // 16), dtype=np.float32)
     sp = None if ssp is None else np.ascontiguousarray(ssp, dtype=np.float32)
     nw = None if nw_next is None else np.ascontiguousarray(nw_next, dtype=np.float32)
@@ -589,6 +597,9 @@ def k_bgemm_q8a8(aq, ad, q, d16, ssp, d_norm, eps, epi, nw_next=None, y0=None, d
                                 yd.ctypes.data, sso.ctypes.data, iters, C.byref(ms))
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_bgemm_q8a8 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    if as_f16:
+        with np.errstate(over="ignore"):
+            yd = np.ascontiguousarray(yd.astype(np.float16)).view(np.uint16)
     return dict(y=y, yq=yq, yd=yd, ssp_out=sso, ms=ms.value)
 
 

@@ -41,6 +41,27 @@ VOC_STAGE_R = {
     "full": {"blk_ct": 3.48e-06, "dec_in": 5.05e-06, "dw_ln": 2.02e-07, "out": 4.99e-07, "pw1": 1.97e-06, "pw2": 4.31e-06, "res_c1": 5.12e-06, "res_c2": 1.95e-06, "up_ct": 1.69e-06},
 }
 
+# The Q8_0 Talker away from O(1) magnitudes (tests/_q8_scales.py, tests/test_q8_scales_{cpu,gpu}.py). W8A8 quantises an activation from the
+# UN-normalised v = x * nw; ggml quantises the normalised row. Entries are (mean, sample standard deviation) at e = 0 (rows of O(1)), taken
+# on the CPU oracle, never from device output; `python tests/_q8_scales.py` prints the table (CPU only, ~5 s).
+#   gemm / resid / swiglu: (error of this design against float64) / (error of ggml's order against float64), 8 seeds. The two orders
+#     round different f32 values to int8, so the ratio is 1 up to the sampling noise of those roundings; the producers' ratio is exactly 1
+#     (the same values are rounded) and borrows the GEMM's spread. A magnitude passes when ratio <= mean + Q8_SCALE_SIGMAS * std.
+#   talker_1 / talker_2: relative RMS of the tiny model's prefill logits in mode 1 (W8A16) / 2 (W8A8) against the bf16 mode, 5 prompts.
+#     The prompt's magnitude changes which term dominates the residual stream (rms_eps, the first block's output), so the figure moves with
+#     it in EVERY mode: the bound on a mode's figure at 2^e is Q8_TALKER_MARGIN x its e = 0 mean (a lost block or a flushed scale is an O(1)
+#     error, > 50 x the figure), and mode 2 may exceed mode 1 AT THE SAME e by no more than sqrt(2) (two independent Q8_0 roundings of equal
+#     relative size add in quadrature) times 1 + Q8_SCALE_SIGMAS x the combined relative spread below.
+Q8_SCALE_SIGMAS = 4.0
+Q8_TALKER_MARGIN = 2.0
+Q8_SCALE_RATIO = {
+    "gemm": (0.999223, 0.00143),
+    "resid": (1.0, 0.00143),
+    "swiglu": (1.0, 0.00143),
+    "talker_1": (0.0131648, 0.000192),
+    "talker_2": (0.0175642, 0.000311),
+}
+
 
 def build():
     subprocess.check_call(["make", "-C", ORACLE_DIR, "libq3oracle.so"], stdout=subprocess.DEVNULL)
@@ -122,9 +143,15 @@ def lib():
     L.q3o_bgemm_q8.restype = None
     L.q3o_quantize_q8_0.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.q3o_quantize_q8_0.restype = None
+    L.q3o_quantize_q8_0_act.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.q3o_quantize_q8_0_act.restype = None
+    L.q3o_round_sig11.argtypes = [C.c_float]
+    L.q3o_round_sig11.restype = C.c_float
     L.q3o_bgemm_q8a8.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.q3o_bgemm_q8a8.restype = None
+    L.q3o_bgemm_q8a8_f32.argtypes = L.q3o_bgemm_q8a8.argtypes
+    L.q3o_bgemm_q8a8_f32.restype = None
     L.q3o_set_talker_q8a8.argtypes = [vp]
     L.q3o_set_talker_q8a8.restype = None
     L.q3o_set_talker_q8.argtypes = [vp]
@@ -253,19 +280,32 @@ def quantize_q8_0(x):
     return q, d
 
 
+def quantize_q8_0_act(x):
+    """ggml's quantiser on ACTIVATION rows as the W8A8 producers apply it (q3o_quantize_q8_0_act): x [..., K] f32 -> (q int8 same shape,
+    d f32 [..., K/32]) with d = amax / 127 rounded to f16's 11-bit significand but kept in f32."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    q = np.zeros(x.shape, dtype=np.int8); d = np.zeros(x.shape[:-1] + (x.shape[-1] // 32,), dtype=np.float32)
+    lib().q3o_quantize_q8_0_act(x.ctypes.data, x.size, q.ctypes.data, d.ctypes.data)
+    return q, d
+
+
 def bgemm_q8a8(aq, ad, q, d16, ssp, d_norm, eps, epi, nw_next=None, y0=None):
-    """oracle/q3_oracle_bf16.c q3o_bgemm_q8a8: ggml's Q8_0 x Q8_0 arithmetic (exact int32 block sums x f32(d_w) * f32(d_x)), the quantising epilogues."""
-    aq = np.ascontiguousarray(aq, dtype=np.int8); ad = np.ascontiguousarray(ad, dtype=np.uint16)
+    """oracle/q3_oracle_bf16.c q3o_bgemm_q8a8: ggml's Q8_0 x Q8_0 arithmetic (exact int32 block sums x f32(d_w) * f32(d_x)), the quantising epilogues.
+    ad: the activation scales — f32 as the kernels hold them (q3o_bgemm_q8a8_f32; yd comes back as f32), or f16 bit patterns (uint16: widened
+    exactly, yd comes back as f16 bit patterns, exact wherever the produced scale is a normal f16)."""
+    aq = np.ascontiguousarray(aq, dtype=np.int8); ad = np.ascontiguousarray(ad)
+    assert ad.dtype in (np.uint16, np.float32), ad.dtype
+    f32 = ad.dtype == np.float32
     q = np.ascontiguousarray(q, dtype=np.int8); d16 = np.ascontiguousarray(d16, dtype=np.uint16)
     B, K = aq.shape
     N = q.shape[0]
     nout = N // 2 if epi == 2 else N
     y = np.zeros((B, N), dtype=np.float32) if y0 is None else np.ascontiguousarray(y0, dtype=np.float32).copy()
-    yq = np.zeros((B, nout), dtype=np.int8); yd = np.zeros((B, nout // 32), dtype=np.uint16)
+    yq = np.zeros((B, nout), dtype=np.int8); yd = np.zeros((B, nout // 32), dtype=np.float32 if f32 else np.uint16)
     sso = np.zeros((B, N // 16), dtype=np.float32)
     sp = None if ssp is None else np.ascontiguousarray(ssp, dtype=np.float32)
     nw = None if nw_next is None else np.ascontiguousarray(nw_next, dtype=np.float32)
-    lib().q3o_bgemm_q8a8(aq.ctypes.data, ad.ctypes.data, B, K, q.ctypes.data, d16.ctypes.data, N, None if sp is None else sp.ctypes.data,
+    (lib().q3o_bgemm_q8a8_f32 if f32 else lib().q3o_bgemm_q8a8)(aq.ctypes.data, ad.ctypes.data, B, K, q.ctypes.data, d16.ctypes.data, N, None if sp is None else sp.ctypes.data,
                          0 if sp is None else sp.shape[1], d_norm, eps, epi, None if nw is None else nw.ctypes.data, y.ctypes.data, yq.ctypes.data,
                          yd.ctypes.data, sso.ctypes.data)
     return dict(y=y, yq=yq, yd=yd, ssp_out=sso)
