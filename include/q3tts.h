@@ -97,7 +97,8 @@ typedef struct q3tts_engine_config {
                                * qwen3_tts_talker.gguf + qwen3_tts_predictor.gguf (llama.cpp qwen3 tensor names; F32, F16,
                                * BF16, Q8_0 or the K-quants Q4_K / Q5_K / Q6_K of the gguf_q5_k_m directory, converted to
                                * bf16 at load) and qwen3_assets.gguf or its NPY fallback
-                               * (src/assets_manager.rs:14-26). Shapes must match `model`; the table row counts
+                               * (src/assets_manager.rs:14-26). Shapes must match `model`: q3tts_config_from_model_dir below
+                               * fills `model` and this field from the files themselves. The table row counts
                                * (text_vocab, codec0_rows, codecq_rows) are taken from the files. The vocoder stays
                                * synthetic: the reference ships it as ONNX only. */
     int32_t talker_q8_0;      /* 1: the Talker's matrices and lm_head stay ggml Q8_0 blocks ON THE DEVICE (f16 scale + 32 int8 per block,
@@ -127,6 +128,33 @@ typedef struct q3tts_stream q3tts_stream;
 
 /* Fill cfg with the Qwen3-TTS-12Hz-1.7B shape assumed by SURVEY.md §8 (28x2048 Talker, 5x1024 Predictor). */
 void q3tts_default_config(q3tts_engine_config* cfg);
+
+/* Open a model directory: every model dimension from its files (host only, no GPU). The reference gets them from llama.cpp, which reads
+ * them from the two GGUFs (src/models/llama/mod.rs:348-353, src/tts/engine.rs:84-137); a caller of this library needs no knowledge of the
+ * architecture either. On entry cfg holds a complete configuration (typically q3tts_default_config). On success the call overwrites
+ *  - cfg->weights_path = path_buf, which receives model_dir/<quant directory> (src/tts/engine.rs:91-95: quant "q5_k_m" -> gguf_q5_k_m,
+ *    "q8_0" -> gguf_q8_0, anything else including NULL -> gguf). path_buf must stay alive while cfg is used;
+ *  - the fields of cfg->model the files determine. From the metadata of qwen3_tts_talker.gguf (t_*) and qwen3_tts_predictor.gguf (p_*),
+ *    with A = the file's general.architecture string: A.block_count -> n_layer, A.embedding_length -> d_model, A.feed_forward_length ->
+ *    d_ffn, A.attention.head_count -> n_head, A.attention.head_count_kv -> n_kv_head, A.attention.key_length -> head_dim (optional:
+ *    embedding_length / head_count, llama.cpp's rule), A.rope.freq_base -> rope_theta (optional: 10000),
+ *    A.attention.layer_norm_rms_epsilon -> rms_eps (one field: the two files must agree), A.rope.dimension_sections ->
+ *    t_mrope_sections (Talker only, required: an integer array of 1 .. 4 entries, missing entries 0, summing to head_dim / 2).
+ *    From tensor shapes: t_vocab = rows of the Talker's output.weight; n_codebooks = the number of codec_embd.N tensors of
+ *    qwen3_assets.gguf (or codec_embedding_N.npy files), contiguous from 0; codebook_size = rows of the Predictor's output.weight /
+ *    (n_codebooks - 1), exactly; d_embed = the codec tables' row length (= t_d_model); text_vocab (0 without a text table,
+ *    src/assets_manager.rs:244-249), codec0_rows, codecq_rows = the tables' row counts (tables 1 .. must agree).
+ * Everything else is left alone: device, max_batch, n_ctx, max_steps_cap, with_vocoder, synth_seed, talker_q8_0, vocoder_flush_tail,
+ * the whole vocoder block, and the protocol fields no file states (sample_limit, eos_code, tts_pad_id).
+ * Cross-checks: proj.weight is [p_d_model][d_embed], and blk.0.attn_q / attn_k / attn_output / ffn_gate / ffn_down.weight of both files
+ * have the shapes the metadata implies. What only the device path can judge, and what q3tts_engine_create checks (K % 512,
+ * t_vocab % 16, ...), is not checked here: q3tts_engine_create stays the one place for that.
+ * Errors go to err (err_cap bytes, always NUL-terminated when err_cap > 0; err may be NULL), not to q3tts_last_error, and leave cfg and
+ * path_buf unchanged: Q3TTS_ERR_INVALID for a path_buf that is too small (the message holds the needed size), a missing or mistyped key
+ * (the message names the file and the full key) and a contradiction (the key, the tensor and both numbers); Q3TTS_ERR_IO for a missing
+ * or unreadable file (named). */
+int q3tts_config_from_model_dir(const char* model_dir, const char* quant, q3tts_engine_config* cfg, char* path_buf, int32_t path_cap,
+                                char* err, int32_t err_cap);
 
 /* TtsEngine::new (reference: src/tts/engine.rs:84-169): allocates weights, KV slabs, vocoder state on the
  * device and builds the replayable frame-step graphs. */
@@ -455,6 +483,14 @@ int q3tts_k_vocoder_bench(q3tts_engine* e, int32_t n_slots, int32_t chunks, floa
  * reader the engine uses for weights_path. out may be NULL to query nelem / dims (ggml order: dims4[0] is the row length)
  * / ggml type (0 F32, 1 F16, 8 Q8_0, 30 BF16). Needs no GPU. */
 int q3tts_k_gguf_read(const char* path, const char* tensor, float* out, int64_t cap, int64_t* nelem, int64_t* dims4, int32_t* ggml_type);
+/* Host-only: one metadata value of a GGUF file through the same reader. *value_type = the GGUF value type (0 u8, 1 i8, 2 u16, 3 i16,
+ * 4 u32, 5 i32, 6 f32, 7 bool, 8 string, 9 array, 10 u64, 11 i64, 12 f64), *elem_type = an array's element type (else the value type),
+ * *count = an array's length (else 1). Numbers (scalars and arrays) go to values as doubles (values_cap elements). A string's bytes go to
+ * str (str_cap bytes, no terminator), *str_bytes = their count; a string array's elements go to str as the file stores them (each a
+ * little-endian u64 length, then its bytes). values / str may be NULL to query types, count and *str_bytes. A missing key is
+ * Q3TTS_ERR_INVALID. Needs no GPU. */
+int q3tts_k_gguf_meta(const char* path, const char* key, int32_t* value_type, int32_t* elem_type, int64_t* count, double* values,
+                      int64_t values_cap, char* str, int64_t str_cap, int64_t* str_bytes);
 /* Measurement mode for bench.py: frame steps are launched eagerly (no graph replay) and ONE launch of every frame is bracketed
  * by HIP events on its own stream. enable = model + 16 * kind; model 2: block 0 of the Talker step, model 1: block 0 of the
  * Predictor's pass 1; kind 0: the gate/up GEMM (so enable = 2 / 1 are the Talker's / Predictor's gate/up as before), 1: QKV GEMM,

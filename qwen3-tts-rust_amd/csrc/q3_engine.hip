@@ -73,7 +73,7 @@ static int validate(const q3tts_engine_config& c, std::string& why) {
     REQ(m.n_codebooks >= 2 && m.n_codebooks <= 16);
     REQ(m.sample_limit > 0 && m.sample_limit <= m.t_vocab && m.sample_limit <= 4096);
     REQ(m.t_mrope_sections[0] + m.t_mrope_sections[1] + m.t_mrope_sections[2] + m.t_mrope_sections[3] == m.t_head_dim / 2);
-    REQ(m.tts_pad_id >= 0 && m.tts_pad_id < m.text_vocab);
+    REQ(m.tts_pad_id >= 0 && (c.weights_path || m.tts_pad_id < m.text_vocab));  // with weights_path the text table's row count is the file's (0 without one: tts_pad is then zeros)
     REQ(c.max_batch >= 1 && c.max_batch <= 64);
     REQ(c.n_ctx >= 64 && c.n_ctx % 64 == 0 && c.n_ctx <= 8192);
     REQ(c.max_steps_cap >= 1 && c.max_steps_cap < c.n_ctx);

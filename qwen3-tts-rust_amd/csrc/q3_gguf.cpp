@@ -26,18 +26,36 @@ struct Cursor {
         s->assign((const char*)p + pos, (size_t)len); pos += (size_t)len;
         return true;
     }
+    bool skip_str() {  // a string that is only walked over (metadata values stay in the mapping)
+        uint64_t len = 0;
+        return get(&len) && skip_checked(len);
+    }
+    bool skip_checked(uint64_t k) { if (k > n - pos) return false; pos += (size_t)k; return true; }
 };
 
-// GGUF metadata value types
-enum { GV_U8 = 0, GV_I8, GV_U16, GV_I16, GV_U32, GV_I32, GV_F32, GV_BOOL, GV_STR, GV_ARR, GV_U64, GV_I64, GV_F64 };
 size_t scalar_size(uint32_t t) {
     switch (t) {
-        case GV_U8: case GV_I8: case GV_BOOL: return 1;
-        case GV_U16: case GV_I16: return 2;
-        case GV_U32: case GV_I32: case GV_F32: return 4;
-        case GV_U64: case GV_I64: case GV_F64: return 8;
+        case Q3_GV_U8: case Q3_GV_I8: case Q3_GV_BOOL: return 1;
+        case Q3_GV_U16: case Q3_GV_I16: return 2;
+        case Q3_GV_U32: case Q3_GV_I32: case Q3_GV_F32: return 4;
+        case Q3_GV_U64: case Q3_GV_I64: case Q3_GV_F64: return 8;
         default: return 0;
     }
+}
+bool is_int_type(uint32_t t) { return t == Q3_GV_U8 || t == Q3_GV_I8 || t == Q3_GV_U16 || t == Q3_GV_I16 || t == Q3_GV_U32 || t == Q3_GV_I32 || t == Q3_GV_U64 || t == Q3_GV_I64; }
+bool is_float_type(uint32_t t) { return t == Q3_GV_F32 || t == Q3_GV_F64; }
+// one integer (or bool) scalar at p, widened to 64 bits with its sign
+uint64_t load_int(const uint8_t* p, uint32_t t) {
+    switch (t) {
+        case Q3_GV_I8: return (uint64_t)(int64_t)(int8_t)p[0];
+        case Q3_GV_I16: { int16_t s; memcpy(&s, p, 2); return (uint64_t)(int64_t)s; }
+        case Q3_GV_I32: { int32_t s; memcpy(&s, p, 4); return (uint64_t)(int64_t)s; }
+        default: { uint64_t v = 0; memcpy(&v, p, scalar_size(t)); return v; }  // unsigned types, bool, i64 (little-endian host)
+    }
+}
+double load_float(const uint8_t* p, uint32_t t) {
+    if (t == Q3_GV_F32) { float f; memcpy(&f, p, 4); return (double)f; }
+    double d; memcpy(&d, p, 8); return d;
 }
 
 inline float f16_to_f32(uint16_t h) {
@@ -158,29 +176,36 @@ int Q3Gguf::open(const std::string& path, std::string& err) {
     }
     if (!c.get(&n_tensors) || !c.get(&n_kv) || n_tensors > (1u << 24) || n_kv > (1u << 24)) { err = path + ": corrupt GGUF header"; return -1; }
     for (uint64_t i = 0; i < n_kv; ++i) {
-        std::string key; uint32_t vt = 0;
-        if (!c.str(&key) || !c.get(&vt)) { err = path + ": truncated metadata"; return -1; }
-        if (vt == GV_STR) { std::string s; if (!c.str(&s)) { err = path + ": truncated metadata string"; return -1; } }
-        else if (vt == GV_ARR) {  // (the reference's reader gives up on arrays, :93-97; real llama.cpp files have them)
-            uint32_t et = 0; uint64_t cnt = 0;
-            if (!c.get(&et) || !c.get(&cnt)) { err = path + ": truncated metadata array"; return -1; }
-            if (et == GV_STR) { for (uint64_t j = 0; j < cnt; ++j) { std::string s; if (!c.str(&s)) { err = path + ": truncated string array"; return -1; } } }
-            else {
-                const size_t es = scalar_size(et);
-                if (!es || cnt > size_ || !c.skip((size_t)cnt * es)) { err = path + ": bad metadata array '" + key + "'"; return -1; }
+        // a length that runs past the file names the key, or the byte offset when the key itself is cut
+        const size_t key_at = c.pos;
+        std::string key; Q3GgufMeta kv;
+        if (!c.str(&key) || !c.get(&kv.type)) { err = path + ": metadata key at byte offset " + std::to_string(key_at) + " runs past the file"; return -1; }
+        const std::string what = path + ": metadata '" + key + "'";
+        kv.elem_type = kv.type; kv.off = c.pos;
+        if (kv.type == Q3_GV_STR) {
+            if (!c.skip_str()) { err = what + ": string length runs past the file"; return -1; }
+            kv.off += 8;
+        } else if (kv.type == Q3_GV_ARR) {  // (the reference's reader gives up on arrays, :93-97; real llama.cpp files have them)
+            if (!c.get(&kv.elem_type) || !c.get(&kv.count)) { err = what + ": array header runs past the file"; return -1; }
+            kv.off = c.pos;
+            if (kv.elem_type == Q3_GV_ARR) { err = what + ": nested arrays are not supported"; return -1; }
+            if (kv.elem_type == Q3_GV_STR) {
+                if (kv.count > (c.n - c.pos) / 8) { err = what + ": array length " + std::to_string(kv.count) + " runs past the file"; return -1; }
+                for (uint64_t j = 0; j < kv.count; ++j)
+                    if (!c.skip_str()) { err = what + ": string length of element " + std::to_string(j) + " runs past the file"; return -1; }
+            } else {
+                const size_t es = scalar_size(kv.elem_type);
+                if (!es) { err = what + ": unknown array element type " + std::to_string(kv.elem_type); return -1; }
+                if (kv.count > (c.n - c.pos) / es) { err = what + ": array length " + std::to_string(kv.count) + " runs past the file"; return -1; }
+                c.pos += (size_t)kv.count * es;
             }
         } else {
-            const size_t es = scalar_size(vt);
-            uint8_t buf[8] = {0};
-            if (!es || !c.take(buf, es)) { err = path + ": unknown metadata value type " + std::to_string(vt) + " for '" + key + "'"; return -1; }
-            if (vt != GV_F32 && vt != GV_F64) {
-                uint64_t v = 0; memcpy(&v, buf, es);
-                if (vt == GV_I8) v = (uint64_t)(int64_t)(int8_t)buf[0];
-                else if (vt == GV_I16) { int16_t s; memcpy(&s, buf, 2); v = (uint64_t)(int64_t)s; }
-                else if (vt == GV_I32) { int32_t s; memcpy(&s, buf, 4); v = (uint64_t)(int64_t)s; }
-                meta_[key] = v;
-            }
+            const size_t es = scalar_size(kv.type);
+            if (!es) { err = path + ": unknown metadata value type " + std::to_string(kv.type) + " for '" + key + "'"; return -1; }
+            if (!c.skip(es)) { err = what + ": value runs past the file"; return -1; }
         }
+        kv.end = c.pos;
+        meta_[key] = kv;
     }
     uint64_t al = 0;
     if (meta_u64("general.alignment", &al) && al >= 1 && al <= (1u << 20) && (al & (al - 1)) == 0) alignment_ = (uint32_t)al;
@@ -217,9 +242,69 @@ const Q3GgufTensor* Q3Gguf::find(const std::string& name) const {
 }
 bool Q3Gguf::meta_u64(const std::string& key, uint64_t* v) const {
     auto it = meta_.find(key);
-    if (it == meta_.end()) return false;
-    *v = it->second;
+    if (it == meta_.end() || !(is_int_type(it->second.type) || it->second.type == Q3_GV_BOOL)) return false;
+    *v = load_int((const uint8_t*)map_ + it->second.off, it->second.type);
     return true;
+}
+bool Q3Gguf::meta_info(const std::string& key, Q3GgufMeta* out) const {
+    auto it = meta_.find(key);
+    if (it == meta_.end()) return false;
+    if (out) *out = it->second;
+    return true;
+}
+const uint8_t* Q3Gguf::meta_raw(const std::string& key, size_t* nbytes) const {
+    auto it = meta_.find(key);
+    if (it == meta_.end()) return nullptr;
+    if (nbytes) *nbytes = it->second.end - it->second.off;
+    return (const uint8_t*)map_ + it->second.off;
+}
+int Q3Gguf::meta_int(const std::string& key, int64_t* v) const {
+    auto it = meta_.find(key);
+    if (it == meta_.end()) return Q3_META_MISSING;
+    const Q3GgufMeta& m = it->second;
+    if (!is_int_type(m.type)) return Q3_META_TYPE;
+    const uint64_t u = load_int((const uint8_t*)map_ + m.off, m.type);
+    if (m.type == Q3_GV_U64 && u > (uint64_t)INT64_MAX) return Q3_META_TYPE;
+    *v = (int64_t)u;
+    return Q3_META_OK;
+}
+int Q3Gguf::meta_float(const std::string& key, double* v) const {
+    auto it = meta_.find(key);
+    if (it == meta_.end()) return Q3_META_MISSING;
+    if (!is_float_type(it->second.type)) return Q3_META_TYPE;
+    *v = load_float((const uint8_t*)map_ + it->second.off, it->second.type);
+    return Q3_META_OK;
+}
+int Q3Gguf::meta_str(const std::string& key, std::string* v) const {
+    auto it = meta_.find(key);
+    if (it == meta_.end()) return Q3_META_MISSING;
+    if (it->second.type != Q3_GV_STR) return Q3_META_TYPE;
+    v->assign((const char*)map_ + it->second.off, it->second.end - it->second.off);
+    return Q3_META_OK;
+}
+int Q3Gguf::meta_int_array(const std::string& key, std::vector<int64_t>* v) const {
+    auto it = meta_.find(key);
+    if (it == meta_.end()) return Q3_META_MISSING;
+    const Q3GgufMeta& m = it->second;
+    if (m.type != Q3_GV_ARR || !is_int_type(m.elem_type)) return Q3_META_TYPE;
+    const size_t es = scalar_size(m.elem_type);
+    v->resize((size_t)m.count);
+    for (size_t j = 0; j < (size_t)m.count; ++j) {
+        const uint64_t u = load_int((const uint8_t*)map_ + m.off + j * es, m.elem_type);
+        if (m.elem_type == Q3_GV_U64 && u > (uint64_t)INT64_MAX) return Q3_META_TYPE;
+        (*v)[j] = (int64_t)u;
+    }
+    return Q3_META_OK;
+}
+int Q3Gguf::meta_float_array(const std::string& key, std::vector<double>* v) const {
+    auto it = meta_.find(key);
+    if (it == meta_.end()) return Q3_META_MISSING;
+    const Q3GgufMeta& m = it->second;
+    if (m.type != Q3_GV_ARR || !is_float_type(m.elem_type)) return Q3_META_TYPE;
+    const size_t es = scalar_size(m.elem_type);
+    v->resize((size_t)m.count);
+    for (size_t j = 0; j < (size_t)m.count; ++j) (*v)[j] = load_float((const uint8_t*)map_ + m.off + j * es, m.elem_type);
+    return Q3_META_OK;
 }
 
 int q3_gguf_to_f32(const Q3GgufTensor& t, float* dst, std::string& err) {
@@ -265,22 +350,22 @@ int q3_gguf_to_bf16(const Q3GgufTensor& t, uint16_t* dst, std::string& err) {
     return 0;
 }
 
-int q3_npy_load_f32(const std::string& path, std::vector<float>& out, std::vector<size_t>& shape, std::string& err) {
+// header of an NPY v1/v2 file holding little-endian f32 in C order: the shape; *fp stays open at the first data byte
+static int npy_open(const std::string& path, FILE** fp, std::vector<size_t>& shape, std::string& err) {
     FILE* f = fopen(path.c_str(), "rb");
     if (!f) { err = "cannot open " + path; return -1; }
     unsigned char magic[10];
     if (fread(magic, 1, 10, f) != 10 || memcmp(magic, "\x93NUMPY", 6) != 0) { fclose(f); err = path + ": not a numpy file"; return -1; }
-    size_t hlen = 0, hoff = 0;
-    if (magic[6] == 1) { hlen = (size_t)magic[8] | ((size_t)magic[9] << 8); hoff = 10; }
+    size_t hlen = 0;
+    if (magic[6] == 1) hlen = (size_t)magic[8] | ((size_t)magic[9] << 8);
     else if (magic[6] == 2) {
         unsigned char more[2];
         if (fread(more, 1, 2, f) != 2) { fclose(f); err = path + ": truncated header"; return -1; }
-        hlen = (size_t)magic[8] | ((size_t)magic[9] << 8) | ((size_t)more[0] << 16) | ((size_t)more[1] << 24); hoff = 12;
+        hlen = (size_t)magic[8] | ((size_t)magic[9] << 8) | ((size_t)more[0] << 16) | ((size_t)more[1] << 24);
     } else { fclose(f); err = path + ": unsupported numpy version"; return -1; }
     if (hlen > (1u << 20)) { fclose(f); err = path + ": header too long"; return -1; }
     std::string header(hlen, '\0');
     if (fread(&header[0], 1, hlen, f) != hlen) { fclose(f); err = path + ": truncated header"; return -1; }
-    (void)hoff;
     if (header.find("'<f4'") == std::string::npos && header.find("\"<f4\"") == std::string::npos) { fclose(f); err = path + ": dtype is not little-endian f32"; return -1; }
     if (header.find("'fortran_order': True") != std::string::npos) { fclose(f); err = path + ": fortran_order arrays are not supported"; return -1; }
     shape.clear();
@@ -293,10 +378,24 @@ int q3_npy_load_f32(const std::string& path, std::vector<float>& out, std::vecto
         if (ch >= '0' && ch <= '9') { v = v * 10 + (size_t)(ch - '0'); have = true; }
         else { if (have) shape.push_back(v); v = 0; have = false; }
     }
+    *fp = f;
+    return 0;
+}
+
+int q3_npy_load_f32(const std::string& path, std::vector<float>& out, std::vector<size_t>& shape, std::string& err) {
+    FILE* f = nullptr;
+    if (npy_open(path, &f, shape, err)) return -1;
     size_t n = 1;
     for (size_t d : shape) n *= d;
     out.resize(n);
     if (n && fread(out.data(), 4, n, f) != n) { fclose(f); err = path + ": truncated data"; return -1; }
+    fclose(f);
+    return 0;
+}
+
+int q3_npy_shape(const std::string& path, std::vector<size_t>& shape, std::string& err) {
+    FILE* f = nullptr;
+    if (npy_open(path, &f, shape, err)) return -1;
     fclose(f);
     return 0;
 }
@@ -329,6 +428,38 @@ extern "C" int q3tts_k_gguf_read(const char* path, const char* tensor, float* ou
     if (out) {
         if (cap < *nelem) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "output buffer too small");
         if (q3_gguf_to_f32(*t, out, err)) return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, err);
+    }
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_gguf_meta(const char* path, const char* key, int32_t* value_type, int32_t* elem_type, int64_t* count, double* values,
+                                 int64_t values_cap, char* str, int64_t str_cap, int64_t* str_bytes) {
+    if (!path || !key) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    std::string err;
+    Q3Gguf g;
+    if (g.open(path, err)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, err);
+    Q3GgufMeta m;
+    if (!g.meta_info(key, &m)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string("metadata key '") + key + "' is missing");
+    if (value_type) *value_type = (int32_t)m.type;
+    if (elem_type) *elem_type = (int32_t)m.elem_type;
+    if (count) *count = (int64_t)m.count;
+    size_t nb = 0;
+    const uint8_t* raw = g.meta_raw(key, &nb);
+    const bool text = m.elem_type == Q3_GV_STR;
+    if (str_bytes) *str_bytes = text ? (int64_t)nb : 0;
+    if (text) {
+        if (str) { if (str_cap < (int64_t)nb) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "string buffer too small"); memcpy(str, raw, nb); }
+        return Q3TTS_OK;
+    }
+    if (values) {
+        if (values_cap < (int64_t)m.count) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "value buffer too small");
+        const size_t es = scalar_size(m.elem_type);
+        for (size_t j = 0; j < (size_t)m.count; ++j) {
+            const uint8_t* p = raw + j * es;
+            if (is_float_type(m.elem_type)) values[j] = load_float(p, m.elem_type);
+            else if (m.elem_type == Q3_GV_U64) values[j] = (double)load_int(p, m.elem_type);
+            else values[j] = (double)(int64_t)load_int(p, m.elem_type);
+        }
     }
     return Q3TTS_OK;
 }

@@ -26,6 +26,16 @@ struct Q3GgufTensor {
     const uint8_t* data = nullptr;
 };
 
+// GGUF metadata value types (the file's own ids)
+enum { Q3_GV_U8 = 0, Q3_GV_I8, Q3_GV_U16, Q3_GV_I16, Q3_GV_U32, Q3_GV_I32, Q3_GV_F32, Q3_GV_BOOL, Q3_GV_STR, Q3_GV_ARR, Q3_GV_U64, Q3_GV_I64, Q3_GV_F64 };
+enum { Q3_META_OK = 0, Q3_META_MISSING = 1, Q3_META_TYPE = 2 };
+struct Q3GgufMeta {
+    uint32_t type = 0;       // Q3_GV_*
+    uint32_t elem_type = 0;  // arrays: the element type (never Q3_GV_ARR: nested arrays are refused at open); else == type
+    uint64_t count = 1;      // arrays: elements; else 1
+    size_t off = 0, end = 0; // payload [off, end) in the mapping (see Q3Gguf::meta_raw)
+};
+
 class Q3Gguf {
 public:
     Q3Gguf() = default;
@@ -38,8 +48,20 @@ public:
     const std::vector<Q3GgufTensor>& tensors() const { return tensors_; }
     uint32_t version() const { return version_; }
     uint32_t alignment() const { return alignment_; }
-    // scalar metadata that was an integer / float (arrays and strings are skipped); false when absent
+    // integer / bool scalar metadata widened to 64 bits (signed types sign-extended); false when absent or of another type
     bool meta_u64(const std::string& key, uint64_t* v) const;
+    // Typed metadata: every KV of the file is kept as (type, count, offsets into the mapping) and decoded on access, so a
+    // 150k-entry tokenizer.ggml.tokens costs one bounds-checked walk at open() and no copy. An accessor takes exactly its own class of
+    // GGUF types and never coerces: Q3_META_MISSING when the key is absent, Q3_META_TYPE when it holds another type.
+    bool meta_info(const std::string& key, Q3GgufMeta* out) const;
+    int meta_int(const std::string& key, int64_t* v) const;        // u8 .. u64, i8 .. i64 (a u64 above INT64_MAX is Q3_META_TYPE)
+    int meta_float(const std::string& key, double* v) const;       // f32, f64
+    int meta_str(const std::string& key, std::string* v) const;    // string
+    int meta_int_array(const std::string& key, std::vector<int64_t>* v) const;   // array of an integer type
+    int meta_float_array(const std::string& key, std::vector<double>* v) const;  // array of f32 / f64
+    // the payload bytes of a value inside the mapping: a scalar's bytes, a string's bytes (without its length), an array's elements as
+    // the file stores them (string elements keep their u64 length prefixes); nullptr when absent
+    const uint8_t* meta_raw(const std::string& key, size_t* nbytes) const;
 
 private:
     void* map_ = nullptr;
@@ -47,7 +69,7 @@ private:
     uint32_t version_ = 0, alignment_ = 32;
     std::vector<Q3GgufTensor> tensors_;
     std::map<std::string, size_t> index_;
-    std::map<std::string, uint64_t> meta_;
+    std::map<std::string, Q3GgufMeta> meta_;
 };
 
 // element conversions (ggml semantics: F16 -> f32 exact, Q8_0: f32(d) * q, BF16 -> f32 exact, K-quants: dequantize_row_q{4,5,6}_K)
@@ -57,3 +79,5 @@ int q3_gguf_to_bf16(const Q3GgufTensor& t, uint16_t* dst, std::string& err);
 
 // NPY v1/v2, little-endian f32, C order (the reference assumes exactly that: src/assets_manager.rs:302-377)
 int q3_npy_load_f32(const std::string& path, std::vector<float>& out, std::vector<size_t>& shape, std::string& err);
+// the same header checks, shape only (the data is not read)
+int q3_npy_shape(const std::string& path, std::vector<size_t>& shape, std::string& err);

@@ -151,6 +151,7 @@ SYMBOLS = [
     "q3tts_session_create", "q3tts_session_submit", "q3tts_session_cancel", "q3tts_session_next", "q3tts_session_close",
     "q3tts_session_last_error", "q3tts_k_pcm_pack",
     "q3tts_prefix_create", "q3tts_prefix_rows", "q3tts_prefix_destroy", "q3tts_k_talker_prefill_prefix",
+    "q3tts_config_from_model_dir", "q3tts_k_gguf_meta",
 ]
 
 
@@ -229,6 +230,9 @@ def load_library(path=None):
     lib.q3tts_mel_frames.restype = C.c_int32
     lib.q3tts_mel.argtypes = [C.c_void_p, f32p, C.c_int64, f32p, C.c_int32, C.POINTER(C.c_int32)]
     lib.q3tts_k_gguf_read.argtypes = [C.c_char_p, C.c_char_p, f32p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.q3tts_k_gguf_meta.argtypes = [C.c_char_p, C.c_char_p, i32p, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int64, C.c_char_p, C.c_int64,
+                                      C.POINTER(C.c_int64)]
+    lib.q3tts_config_from_model_dir.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(EngineConfig), C.c_char_p, C.c_int32, C.c_char_p, C.c_int32]
     lib.q3tts_clone_default_config.argtypes = [C.POINTER(CloneConfig)]
     lib.q3tts_clone_default_config.restype = None
     lib.q3tts_clone_init.argtypes = [vp, C.POINTER(CloneConfig)]
@@ -282,6 +286,14 @@ def default_config():
     cfg = EngineConfig()
     load_library().q3tts_default_config(C.byref(cfg))
     return cfg
+
+
+def copy_config(cfg):
+    """A copy of an EngineConfig that can be changed without touching the caller's object. The copy holds a reference to the original,
+    which owns whatever weights_path points to."""
+    c = EngineConfig.from_buffer_copy(cfg)
+    c._source = cfg
+    return c
 
 
 def tiny_config(max_batch=4, n_ctx=256, with_vocoder=1):

@@ -713,6 +713,53 @@ def k_gguf_read(path, tensor=""):
     return out.reshape(shape), int(ty.value)
 
 
+GGUF_VALUE_TYPES = ("u8", "i8", "u16", "i16", "u32", "i32", "f32", "bool", "str", "array", "u64", "i64", "f64")
+
+
+def k_gguf_meta(path, key):
+    """One metadata value of a GGUF file through the engine's own reader (host only): (type name, element type name, value). Numbers come
+    back as floats (the hook's doubles), a string as bytes, arrays as lists of those."""
+    lib = _abi.load_library()
+    vt, et, n, nb = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    rc = lib.q3tts_k_gguf_meta(os.fsencode(path), key.encode(), C.byref(vt), C.byref(et), C.byref(n), None, 0, None, 0, C.byref(nb))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_gguf_meta: {lib.q3tts_last_error(None).decode()} (status {rc})")
+    vals = (C.c_double * max(1, n.value))(); buf = C.create_string_buffer(max(1, nb.value))
+    rc = lib.q3tts_k_gguf_meta(os.fsencode(path), key.encode(), C.byref(vt), C.byref(et), C.byref(n), vals, n.value, buf, nb.value, C.byref(nb))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_gguf_meta: {lib.q3tts_last_error(None).decode()} (status {rc})")
+    tname, ename = GGUF_VALUE_TYPES[vt.value], GGUF_VALUE_TYPES[et.value]
+    raw = buf.raw[:nb.value]
+    if tname == "str":
+        return tname, ename, raw
+    if tname != "array":
+        return tname, ename, vals[0]
+    if ename != "str":
+        return tname, ename, list(vals[:n.value])
+    out, pos = [], 0
+    for _ in range(n.value):  # each element: little-endian u64 length, then its bytes
+        ln = int.from_bytes(raw[pos:pos + 8], "little")
+        out.append(raw[pos + 8:pos + 8 + ln])
+        pos += 8 + ln
+    return tname, ename, out
+
+
+def config_from_model_dir(model_dir, quant=None, base=None):
+    """q3tts_config_from_model_dir: a copy of `base` (default: q3tts_default_config) whose model dimensions and weights_path come from the
+    files of model_dir's quant directory. The returned config owns the path buffer weights_path points into. Host only."""
+    lib = _abi.load_library()
+    cfg = _abi.copy_config(base) if base is not None else _abi.default_config()
+    md = os.fsencode(model_dir)
+    buf = C.create_string_buffer(len(md) + 16)
+    err = C.create_string_buffer(1024)
+    q = None if quant is None else str(quant).encode()
+    rc = lib.q3tts_config_from_model_dir(md, q, C.byref(cfg), buf, len(buf), err, len(err))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_config_from_model_dir failed ({rc}): {err.value.decode('utf-8', 'replace')}")
+    cfg._path_buf = buf  # weights_path points into it
+    return cfg
+
+
 def k_pcm_pack(src, entries, out_n, fmt=0, device=0):
     """q3tts_k_pcm_pack: src [rows][stride] f32, entries [(row, first, count, dst)] (<= 64); returns the f32 (fmt 0) or i16 (fmt 1) output
     of out_n samples (zeros outside the windows)."""

@@ -58,6 +58,9 @@ pub struct q3tts_node_timings { pub generate_ms: c_float, pub gather_ms: c_float
 #[link(name = "q3tts")]
 extern "C" {
     pub fn q3tts_default_config(cfg: *mut q3tts_engine_config);
+    // every model dimension and weights_path from the files of model_dir's quant directory (host only); errors go to err, cfg is then unchanged
+    pub fn q3tts_config_from_model_dir(model_dir: *const c_char, quant: *const c_char, cfg: *mut q3tts_engine_config, path_buf: *mut c_char, path_cap: i32,
+                                       err: *mut c_char, err_cap: i32) -> c_int;
     pub fn q3tts_engine_create(cfg: *const q3tts_engine_config, out: *mut *mut q3tts_engine) -> c_int;
     pub fn q3tts_engine_destroy(e: *mut q3tts_engine);
     pub fn q3tts_last_error(e: *const q3tts_engine) -> *const c_char;
@@ -117,18 +120,24 @@ pub struct TtsEngine { raw: *mut q3tts_engine, sampler: SamplerConfig, max_steps
 
 impl TtsEngine {
     /// TtsEngine::new(model_dir, quant) — src/tts/engine.rs:84-169. `model_dir/<quant dir>` (src/tts/engine.rs:91-95) holds
-    /// qwen3_tts_talker.gguf, qwen3_tts_predictor.gguf and qwen3_assets.gguf (or the NPY assets): passed as `weights_path`.
+    /// qwen3_tts_talker.gguf, qwen3_tts_predictor.gguf and qwen3_assets.gguf (or the NPY assets). Every model dimension comes from those
+    /// files (q3tts_config_from_model_dir), as llama.cpp reads them for the reference: no shape is assumed here.
     pub fn new(model_dir: &str, quant: &str) -> Result<Self, String> {
-        let quant_dir = match quant { "q5_k_m" => "gguf_q5_k_m", "q8_0" => "gguf_q8_0", _ => "gguf" };
-        let dir = std::ffi::CString::new(format!("{}/{}", model_dir, quant_dir)).map_err(|e| e.to_string())?;
+        let dir = std::ffi::CString::new(model_dir).map_err(|e| e.to_string())?;
+        let q = std::ffi::CString::new(quant).map_err(|e| e.to_string())?;
+        let mut path_buf: Vec<c_char> = vec![0; model_dir.len() + 16];   // model_dir + '/' + the longest quant directory name + NUL
+        let mut err: Vec<c_char> = vec![0; 1024];
         unsafe {
             let mut cfg: q3tts_engine_config = std::mem::zeroed();
             q3tts_default_config(&mut cfg);
-            cfg.weights_path = dir.as_ptr();   // borrowed for the call only
+            let rc = q3tts_config_from_model_dir(dir.as_ptr(), q.as_ptr(), &mut cfg, path_buf.as_mut_ptr(), path_buf.len() as i32,
+                                                 err.as_mut_ptr(), err.len() as i32);
+            if rc != 0 { return Err(format!("q3tts_config_from_model_dir failed ({}): {}", rc, CStr::from_ptr(err.as_ptr()).to_string_lossy())); }
+            // cfg.weights_path now points into path_buf: borrowed for the call only
             cfg.talker_q8_0 = if quant == "q8_0" { 2 } else { 0 };   // gguf_q8_0: the Talker's blocks stay as stored and are multiplied as llama.cpp does (Q8_0 x Q8_0, W8A8)
             let mut raw = std::ptr::null_mut();
             let rc = q3tts_engine_create(&cfg, &mut raw);
-            if rc != 0 { return Err(format!("q3tts_engine_create failed: {}", rc)); }
+            if rc != 0 { return Err(format!("q3tts_engine_create failed ({}): {}", rc, CStr::from_ptr(q3tts_last_error(std::ptr::null())).to_string_lossy())); }
             Ok(Self { raw, sampler: SamplerConfig::default(), max_steps: 512 })
         }
     }
