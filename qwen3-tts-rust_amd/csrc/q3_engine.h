@@ -37,17 +37,22 @@ struct Q3Scratch {
     int rows = 0;
 };
 
+// a set of f32 residual rows and the operand of the GEMMs that read them: their norm inputs for the next RMSNorm weight
+struct Q3Rows {
+    float* x = nullptr;                        // [rows][d] f32
+    uint16_t* xb = nullptr;                    // bf16(x * nw), A-tiled in whole 16-row tiles (W8A8: int8 quants)
+    float* ssp = nullptr;                      // per-tile sums of squares [rows][d / 16]
+    float* ascale = nullptr; int rt16 = 0;     // W8A8: the f32 block scales of xb (null otherwise); row tiles of xb
+};
+
 // the decode rows: per-row buffers, the row -> slot map and one captured frame-step graph per row-count bucket
 struct Q3Lane {
     int nb = 0;                       // row capacity = max_batch
     hipStream_t stream = nullptr;
-    float *xT = nullptr, *logits = nullptr, *logits_tmp = nullptr, *fb = nullptr, *px = nullptr;
-    // norm inputs of the residual rows: bf16(x * nw) and the per-tile sums of squares, Talker [nb] / Predictor [2 nb]
-    uint16_t *xbT = nullptr, *xbP = nullptr;
-    float *sspT = nullptr, *sspP = nullptr;
-    float* ascT = nullptr; int rt16T = 0;   // W8A8: block scales of xbT
+    Q3Rows T, P;                      // the Talker's rows [nb] and the Predictor's [2 nb]
+    float *logits = nullptr, *logits_tmp = nullptr, *fb = nullptr;
     unsigned long long* keys = nullptr;
-    int *row_pos_t = nullptr, *slot_id = nullptr, *posA = nullptr, *slotA = nullptr, *pos_q = nullptr, *perm = nullptr;
+    int *row_pos_t = nullptr, *slot_id = nullptr, *perm = nullptr;
     Q3Scratch sc;
     std::vector<hipGraph_t> graphs;          // per bucket
     std::vector<hipGraphExec_t> execs;
@@ -79,14 +84,12 @@ struct q3tts_engine {
     Q3Slot* slots_host = nullptr;         // pinned mirror [B] + staging [B]
     int* codes = nullptr;                 // [B][max_steps_cap][ncb]
     float* rng = nullptr;                 // [B][max_steps_cap]
-    std::vector<Q3Lane> lanes;
+    Q3Lane lane;
     Q3Scratch sc_pre;
     // prefill
-    float* xp = nullptr;                  // [n_ctx][d]
-    uint16_t* xbp = nullptr; float* sspp = nullptr;  // norm inputs of the prefill rows
-    float* ascp = nullptr; int rt16p = 0;         // W8A8: block scales of xbp
+    Q3Rows pf;                            // the prefill rows [n_ctx] (x also receives the prompt builder's rows)
     int *pf_pos = nullptr, *pf_slot = nullptr;
-    int* pf_seg = nullptr;              // the prefill launch's rows as per-slot runs {first row, n, slot, first position} (device, 4 ints each): admit_group hands it to run_layers
+    int* pf_seg = nullptr;              // the prefill launch's rows as per-slot runs {first row, n, slot, first position} (device, 4 ints each): prefill_layers uploads it and hands it to run_layers
     Q3PromptRow* prow_dev = nullptr; int prow_cap = 0;
     float* spk_dev = nullptr; int* refcodes_dev = nullptr;
     // sampler defaults (SamplerConfig::default: src/tts/engine.rs:25-34)
@@ -120,7 +123,7 @@ struct q3tts_prefix {
     uint16_t *k = nullptr, *v = nullptr;
 };
 
-// helpers shared with q3_vocoder.hip
+// helpers shared with q3_vocoder.hip and the kernel-level test hooks (q3_hooks.hip)
 int q3_set_err(q3tts_engine* e, int code, const std::string& msg);
 // calls that drive an engine return Q3TTS_ERR_STATE (with a message) while a session owns it
 int q3_refuse_in_session(q3tts_engine* e);
@@ -134,6 +137,9 @@ int q3_refuse_in_session(q3tts_engine* e);
 
 // zero-filled device memory whose fill has completed on return (the one allocator of engine, vocoder, mel and clone state)
 int q3_dev_alloc_zeroed(q3tts_engine* e, void** p, size_t bytes);
+
+// RoPE tables [n_pos][hd / 2] in double on the host (q3_engine.hip; the attention hooks build their own)
+void q3_rope_tables(int n_pos, int hd, float theta, const int* sections, std::vector<float>& cs, std::vector<float>& sn);
 
 // host ChaCha12 StdRng (q3_rng.cpp)
 void q3_stdrng_f32(uint64_t seed, int n, float* out);
@@ -160,6 +166,7 @@ int q3_voc_samples_per_frame(const q3tts_engine* e);
 size_t q3_voc_pcm_stride(const q3tts_engine* e);  // samples between the PCM buffers of consecutive slots
 
 // the scheduler steps of q3_engine.hip that the session worker (q3_session.hip) drives between 4-frame chunks
+// (q3_plan_rows + q3_admit_many are also the single-request admission of the talker-prefill hook)
 int q3_plan_rows(q3tts_engine* e, const std::vector<int>& live);
 int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc);
 int q3_run_chunk(q3tts_engine* e, int CH);

@@ -1,8 +1,8 @@
-// q3_engine.hip — host side of libq3tts: weights, KV slabs, the replayable frame-step graph, the continuous
-// batching loop and the C ABI of include/q3tts.h. The loop restates run_inference_stream
-// (/root/reference/src/tts/engine.rs:445-656) with every per-frame decision on the device: one graph replay =
-// sample -> 15 predictor passes -> feedback -> Talker step, no host round trip (the reference crosses the
-// host<->backend boundary >= 33 times per frame).
+// q3_engine.hip — host side of libq3tts: weights, KV slabs, the replayable frame-step graph, batched prefill, voice prefixes,
+// the continuous batching loop and the engine part of the C ABI of include/q3tts.h (the kernel-level test hooks q3tts_k_*
+// are in q3_hooks.hip). The loop restates the reference's run_inference_stream (src/tts/engine.rs:445-656) with every
+// per-frame decision on the device: one graph replay = sample -> 15 predictor passes -> feedback -> Talker step, no host
+// round trip (the reference crosses the host<->backend boundary >= 33 times per frame).
 #include "q3_engine.h"
 #include "q3_gguf.h"
 
@@ -109,7 +109,7 @@ static int dalloc(q3tts_engine* e, T** p, size_t n) {
 #define TRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
 
 // RoPE tables in double on the host (same formula the oracle restates)
-static void rope_tables(int n_pos, int hd, float theta, const int* sections, std::vector<float>& cs, std::vector<float>& sn) {
+void q3_rope_tables(int n_pos, int hd, float theta, const int* sections, std::vector<float>& cs, std::vector<float>& sn) {
     const int half = hd / 2;
     int s3 = half;
     if (sections) s3 = sections[0] + sections[1] + sections[2];
@@ -279,7 +279,7 @@ static int init_tfm(q3tts_engine* e, Q3Tfm& t, int grp, int L, int d, int Hq, in
     t.layer_stride = (size_t)n_slots * Hkv * n_ctx * hd;
     TRY(dalloc(e, &t.kc, t.layer_stride * L)); TRY(dalloc(e, &t.vc, t.layer_stride * L));
     std::vector<float> cs, sn;
-    rope_tables(n_ctx, hd, theta, sections, cs, sn);
+    q3_rope_tables(n_ctx, hd, theta, sections, cs, sn);
     TRY(dalloc(e, &t.cs, cs.size())); TRY(dalloc(e, &t.sn, sn.size()));
     Q3_HIP(e, hipMemcpyAsync(t.cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, s));
     Q3_HIP(e, hipMemcpyAsync(t.sn, sn.data(), sn.size() * 4, hipMemcpyHostToDevice, s));
@@ -295,7 +295,7 @@ static void free_tfm(Q3Tfm& t) {
     hipFree(t.shead);
 }
 
-static int alloc_scratch(q3tts_engine* e, Q3Scratch& sc, int rows, int nqkv, int nq, int F, int dmax) {
+static int alloc_scratch(q3tts_engine* e, Q3Scratch& sc, int rows, int nqkv, int nq, int F) {
     sc.rows = rows;
     const size_t r16 = ((size_t)rows + 15) & ~(size_t)15;  // A-tiled buffers hold whole 16-row tiles
     TRY(dalloc(e, &sc.qkv, (size_t)rows * nqkv)); TRY(dalloc(e, &sc.att, r16 * nq)); TRY(dalloc(e, &sc.h, r16 * F));
@@ -303,15 +303,33 @@ static int alloc_scratch(q3tts_engine* e, Q3Scratch& sc, int rows, int nqkv, int
     if (e->T.a8) { TRY(dalloc(e, &sc.asc_att, r16 * (nq / 32))); TRY(dalloc(e, &sc.asc_h, r16 * (F / 32))); }  // W8A8: block scales of both operands
     return Q3TTS_OK;
 }
+static void free_scratch(Q3Scratch& sc) { hipFree(sc.qkv); hipFree(sc.att); hipFree(sc.h); hipFree(sc.asc_att); hipFree(sc.asc_h); }
+
+// `rows` residual rows of width d with their norm inputs (the A-tiled operand holds whole 16-row tiles); scales: the W8A8 block scales too
+static int alloc_rows(q3tts_engine* e, Q3Rows& r, size_t rows, int d, bool scales) {
+    const size_t r16 = (rows + 15) & ~(size_t)15;
+    TRY(dalloc(e, &r.x, rows * d)); TRY(dalloc(e, &r.xb, r16 * d)); TRY(dalloc(e, &r.ssp, rows * (d / 16)));
+    r.rt16 = (int)(r16 / 16);
+    if (scales) TRY(dalloc(e, &r.ascale, r16 * (d / 32)));
+    return Q3TTS_OK;
+}
+static void free_rows(Q3Rows& r) { hipFree(r.x); hipFree(r.xb); hipFree(r.ssp); hipFree(r.ascale); }
 
 // K1-K8 of SURVEY.md §8a: one decoder block per iteration, 5 launches — QKV GEMM (row scale from the producer's tile partials),
 // attention (q/k norm + RoPE + KV append fused for decode rows), O GEMM (+ residual, + the FFN norm inputs), gate/up GEMM
 // (+ SwiGLU), down GEMM (+ residual, + the next block's / the head's norm inputs). x: f32 residual rows; xb / ssp: their norm
 // inputs for attn_norm[0] on entry, for out_norm on exit. Restated by oracle/q3_oracle.c tfm_layers.
+// What one call runs them on; a zero member means "not used":
+struct Q3LayerRun {
+    int rows;                                       // the first `rows` rows of the Q3Rows
+    const int *row_pos, *row_slot;                  // per-row position / slot maps (device); null: slot = row % slot_mod, position = pos_const (+ row / slot_mod)
+    bool one_row_per_slot;                          // decode rows: q/k prep and the K/V append are fused into the attention launch
+    hipEvent_t* probe;                              // q3tts_k_probe: two events that bracket launch e->probe_kind of block 0
+    int slot_mod, pos_const;
+    const int* seg; int n_seg, seg_max_n, seg_max_t;  // prefill of whole prompts: the rows as per-slot runs (pf_seg), the longest run, the furthest position + 1
+};
 // Returns the number of launches the GEMM launcher refused (a shape it cannot run: stale activations would follow silently).
-static int run_layers(q3tts_engine* e, Q3Tfm& t, float* x, uint16_t* xb, float* ssp, int rows, const int* row_pos, const int* row_slot, Q3Scratch& sc,
-                       hipStream_t s, bool one_row_per_slot = false, hipEvent_t* probe = nullptr, int slot_mod = 0, int pos_const = 0,
-                       const int* seg = nullptr, int n_seg = 0, int seg_max_n = 0, int seg_max_t = 0, float* xscale = nullptr, int x_rt16 = 0) {
+static int run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& a, Q3Scratch& sc, hipStream_t s) {
     // W8A8 (t.a8: the Talker with talker_q8_0 = 2): xb / sc.att / sc.h hold Q8_0 blocks (int8 quants + the f32 block scales xscale / sc.asc_att /
     // sc.asc_h) and every GEMM runs q3_launch_bgemm8: ggml's Q8_0 x Q8_0 arithmetic
     auto gemm = [&](Q3BGemm& g) { return t.a8 ? q3_launch_bgemm8(g, s) : q3_launch_bgemm(g, s); };
@@ -322,47 +340,47 @@ static int run_layers(q3tts_engine* e, Q3Tfm& t, float* x, uint16_t* xb, float* 
     for (int l = 0; l < t.L; ++l) {
         Q3BGemm g{};
         g.w_once = once;
-        g.a = xb; g.B = rows; g.w = t.wqkv[l]; g.wscale = t.q8 ? t.sqkv[l] : nullptr; g.K = t.d; g.N = t.nqkv; g.ssp = ssp; g.ld_ssp = nt; g.ntiles = nt; g.d_norm = t.d; g.eps = eps;
+        g.a = r.xb; g.B = a.rows; g.w = t.wqkv[l]; g.wscale = t.q8 ? t.sqkv[l] : nullptr; g.K = t.d; g.N = t.nqkv; g.ssp = r.ssp; g.ld_ssp = nt; g.ntiles = nt; g.d_norm = t.d; g.eps = eps;
         g.epi = Q3_EPI_STORE; g.y = sc.qkv; g.ldy = t.nqkv;
-        if (t.a8) { g.ascale = xscale; g.a_rt16 = x_rt16; }
-        const int pk = (probe && l == 0) ? e->probe_kind : -1;  // which launch of block 0 the probe events bracket (q3tts_k_probe)
-        if (pk == 1) hipEventRecord(probe[0], s);
+        if (t.a8) { g.ascale = r.ascale; g.a_rt16 = r.rt16; }
+        const int pk = (a.probe && l == 0) ? e->probe_kind : -1;  // which launch of block 0 the probe events bracket (q3tts_k_probe)
+        if (pk == 1) hipEventRecord(a.probe[0], s);
         bad += gemm(g) != 0;
-        if (pk == 1) hipEventRecord(probe[1], s);
-        Q3QkPrep qp{}; qp.qkv = sc.qkv; qp.ld = t.nqkv; qp.rows = rows; qp.Hq = t.Hq; qp.Hkv = t.Hkv; qp.hd = t.hd;
+        if (pk == 1) hipEventRecord(a.probe[1], s);
+        Q3QkPrep qp{}; qp.qkv = sc.qkv; qp.ld = t.nqkv; qp.rows = a.rows; qp.Hq = t.Hq; qp.Hkv = t.Hkv; qp.hd = t.hd;
         qp.qnw = t.qn[l]; qp.knw = t.kn[l]; qp.eps = eps; qp.cs = t.cs; qp.sn = t.sn;
-        qp.kc = t.kc + l * t.layer_stride; qp.vc = t.vc + l * t.layer_stride; qp.n_ctx = t.n_ctx; qp.row_pos = row_pos; qp.row_slot = row_slot;
-        qp.slot_mod = slot_mod; qp.pos_const = pos_const;
-        const bool fused = one_row_per_slot && t.Hq / t.Hkv >= 2;
+        qp.kc = t.kc + l * t.layer_stride; qp.vc = t.vc + l * t.layer_stride; qp.n_ctx = t.n_ctx; qp.row_pos = a.row_pos; qp.row_slot = a.row_slot;
+        qp.slot_mod = a.slot_mod; qp.pos_const = a.pos_const;
+        const bool fused = a.one_row_per_slot && t.Hq / t.Hkv >= 2;
         // the Predictor's pass A: rows [0, B) at position 0 and [B, 2B) at position 1 of an empty per-frame cache: one fused launch
-        const bool pair = !one_row_per_slot && slot_mod > 0 && rows == 2 * slot_mod && pos_const == 0 && t.Hq / t.Hkv == 2 && t.hd == 128;
+        const bool pair = !a.one_row_per_slot && a.slot_mod > 0 && a.rows == 2 * a.slot_mod && a.pos_const == 0 && t.Hq / t.Hkv == 2 && t.hd == 128;
         if (!fused && !pair) q3_launch_qk_prep(qp, s);
-        Q3Attend at{}; at.qkv = sc.qkv; at.ld = t.nqkv; at.rows = rows; at.out = (float*)sc.att; at.ldo = t.nq; at.Hq = t.Hq; at.Hkv = t.Hkv; at.hd = t.hd;
-        at.kc = qp.kc; at.vc = qp.vc; at.n_ctx = t.n_ctx; at.row_pos = row_pos; at.row_slot = row_slot;
-        at.fused = pair ? 2 : (fused ? 1 : 0); at.prep = qp; at.out_bf16 = 1; at.slot_mod = slot_mod; at.pos_const = pos_const;
+        Q3Attend at{}; at.qkv = sc.qkv; at.ld = t.nqkv; at.rows = a.rows; at.out = (float*)sc.att; at.ldo = t.nq; at.Hq = t.Hq; at.Hkv = t.Hkv; at.hd = t.hd;
+        at.kc = qp.kc; at.vc = qp.vc; at.n_ctx = t.n_ctx; at.row_pos = a.row_pos; at.row_slot = a.row_slot;
+        at.fused = pair ? 2 : (fused ? 1 : 0); at.prep = qp; at.out_bf16 = 1; at.slot_mod = a.slot_mod; at.pos_const = a.pos_const;
         if (t.a8) { at.out_bf16 = 2; at.out_scale = sc.asc_att; at.out_rt16 = sc.rt16; }
-        if (!fused && !pair && n_seg > 0) { at.seg = seg; at.n_seg = n_seg; at.seg_max_n = seg_max_n; at.seg_max_t = seg_max_t; }  // prefill of whole prompts (admit_group): the launch's rows as per-slot runs
-        if (pk == 2) hipEventRecord(probe[0], s);
+        if (!fused && !pair && a.n_seg > 0) { at.seg = a.seg; at.n_seg = a.n_seg; at.seg_max_n = a.seg_max_n; at.seg_max_t = a.seg_max_t; }  // prefill of whole prompts (prefill_layers): the launch's rows as per-slot runs
+        if (pk == 2) hipEventRecord(a.probe[0], s);
         q3_launch_attend(at, s);
-        if (pk == 2) hipEventRecord(probe[1], s);
-        g = Q3BGemm{}; g.w_once = once; g.a = sc.att; g.B = rows; g.w = t.wo[l]; g.wscale = t.q8 ? t.so[l] : nullptr; g.K = t.nq; g.N = t.d; g.epi = Q3_EPI_RESID; g.y = x; g.ldy = t.d;
-        g.yb = xb; g.nw_next = t.ffn_norm[l]; g.ssp_out = ssp; g.ld_ssp_out = nt;
-        if (t.a8) { g.ascale = sc.asc_att; g.a_rt16 = sc.rt16; g.yscale = xscale; g.y_rt16 = x_rt16; }
-        if (pk == 3) hipEventRecord(probe[0], s);
+        if (pk == 2) hipEventRecord(a.probe[1], s);
+        g = Q3BGemm{}; g.w_once = once; g.a = sc.att; g.B = a.rows; g.w = t.wo[l]; g.wscale = t.q8 ? t.so[l] : nullptr; g.K = t.nq; g.N = t.d; g.epi = Q3_EPI_RESID; g.y = r.x; g.ldy = t.d;
+        g.yb = r.xb; g.nw_next = t.ffn_norm[l]; g.ssp_out = r.ssp; g.ld_ssp_out = nt;
+        if (t.a8) { g.ascale = sc.asc_att; g.a_rt16 = sc.rt16; g.yscale = r.ascale; g.y_rt16 = r.rt16; }
+        if (pk == 3) hipEventRecord(a.probe[0], s);
         bad += gemm(g) != 0;
-        if (pk == 3) hipEventRecord(probe[1], s);
-        g = Q3BGemm{}; g.w_once = once; g.a = xb; g.B = rows; g.w = t.wgu[l]; g.wscale = t.q8 ? t.sgu[l] : nullptr; g.K = t.d; g.N = 2 * t.F; g.ssp = ssp; g.ld_ssp = nt; g.ntiles = nt; g.d_norm = t.d;
+        if (pk == 3) hipEventRecord(a.probe[1], s);
+        g = Q3BGemm{}; g.w_once = once; g.a = r.xb; g.B = a.rows; g.w = t.wgu[l]; g.wscale = t.q8 ? t.sgu[l] : nullptr; g.K = t.d; g.N = 2 * t.F; g.ssp = r.ssp; g.ld_ssp = nt; g.ntiles = nt; g.d_norm = t.d;
         g.eps = eps; g.epi = Q3_EPI_SWIGLU; g.yb = sc.h;
-        if (t.a8) { g.ascale = xscale; g.a_rt16 = x_rt16; g.yscale = sc.asc_h; g.y_rt16 = sc.rt16; }
-        if (pk == 0) hipEventRecord(probe[0], s);
+        if (t.a8) { g.ascale = r.ascale; g.a_rt16 = r.rt16; g.yscale = sc.asc_h; g.y_rt16 = sc.rt16; }
+        if (pk == 0) hipEventRecord(a.probe[0], s);
         bad += gemm(g) != 0;
-        if (pk == 0) hipEventRecord(probe[1], s);
-        g = Q3BGemm{}; g.w_once = once; g.a = sc.h; g.B = rows; g.w = t.wd[l]; g.wscale = t.q8 ? t.sd[l] : nullptr; g.K = t.F; g.N = t.d; g.epi = Q3_EPI_RESID; g.y = x; g.ldy = t.d;
-        g.yb = xb; g.nw_next = l + 1 < t.L ? t.attn_norm[l + 1] : t.out_norm; g.ssp_out = ssp; g.ld_ssp_out = nt;
-        if (t.a8) { g.ascale = sc.asc_h; g.a_rt16 = sc.rt16; g.yscale = xscale; g.y_rt16 = x_rt16; }
-        if (pk == 4) hipEventRecord(probe[0], s);
+        if (pk == 0) hipEventRecord(a.probe[1], s);
+        g = Q3BGemm{}; g.w_once = once; g.a = sc.h; g.B = a.rows; g.w = t.wd[l]; g.wscale = t.q8 ? t.sd[l] : nullptr; g.K = t.F; g.N = t.d; g.epi = Q3_EPI_RESID; g.y = r.x; g.ldy = t.d;
+        g.yb = r.xb; g.nw_next = l + 1 < t.L ? t.attn_norm[l + 1] : t.out_norm; g.ssp_out = r.ssp; g.ld_ssp_out = nt;
+        if (t.a8) { g.ascale = sc.asc_h; g.a_rt16 = sc.rt16; g.yscale = r.ascale; g.y_rt16 = r.rt16; }
+        if (pk == 4) hipEventRecord(a.probe[0], s);
         bad += gemm(g) != 0;
-        if (pk == 4) hipEventRecord(probe[1], s);
+        if (pk == 4) hipEventRecord(a.probe[1], s);
     }
     return bad;
 }
@@ -378,13 +396,13 @@ static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
     int* codes = e->codes;
     Q3Sample sa{}; sa.logits = L.logits; sa.ld = m.t_vocab; sa.limit = m.sample_limit; sa.eos = m.eos_code; sa.slots = slots; sa.B = B; sa.row_slot = L.slot_id;
     sa.rng = e->rng; sa.codes = codes; sa.max_steps_cap = cap; sa.ncb = ncb;
-    Q3PredInput pi{}; pi.xT = L.xT; pi.out_norm = e->T.out_norm; pi.eps = eps; pi.d = de; pi.codec0 = e->codec[0]; pi.codec0_rows = m.codec0_rows;
-    pi.slots = slots; pi.row_slot = L.slot_id; pi.X = nullptr; pi.fb = L.fb; pi.B = B; pi.pproj0 = e->pproj[0]; pi.proj_b = e->proj_b; pi.dp = dp; pi.px = L.px;
-    pi.nw = e->P.attn_norm[0]; pi.xb = L.xbP; pi.ssp = L.sspP;
+    Q3PredInput pi{}; pi.xT = L.T.x; pi.out_norm = e->T.out_norm; pi.eps = eps; pi.d = de; pi.codec0 = e->codec[0]; pi.codec0_rows = m.codec0_rows;
+    pi.slots = slots; pi.row_slot = L.slot_id; pi.X = nullptr; pi.fb = L.fb; pi.B = B; pi.pproj0 = e->pproj[0]; pi.proj_b = e->proj_b; pi.dp = dp; pi.px = L.P.x;
+    pi.nw = e->P.attn_norm[0]; pi.xb = L.P.xb; pi.ssp = L.P.ssp;
     {   // H6 (src/assets_manager.rs:383-399) for the hidden rows only (every code embedding arrives pre-projected), in the same launch
         // as the sampler: the tiles normalise the Talker's raw output rows themselves
-        Q3Project pj{}; pj.x = L.xT; pj.ldx = de; pj.rows = B; pj.w = e->proj_w; pj.bias = e->proj_b; pj.n_in = de; pj.n_out = dp; pj.y = L.px; pj.ldy = dp;
-        pj.nw = e->P.attn_norm[0]; pj.xb = L.xbP; pj.ssp = L.sspP; pj.ld_ssp = dp / 16;  // rows [0, B) of pass A
+        Q3Project pj{}; pj.x = L.T.x; pj.ldx = de; pj.rows = B; pj.w = e->proj_w; pj.bias = e->proj_b; pj.n_in = de; pj.n_out = dp; pj.y = L.P.x; pj.ldy = dp;
+        pj.nw = e->P.attn_norm[0]; pj.xb = L.P.xb; pj.ssp = L.P.ssp; pj.ld_ssp = dp / 16;  // rows [0, B) of pass A
         pj.norm_w = e->T.out_norm; pj.eps = eps;
         bad += q3_launch_sample_input(sa, pi, pj, s) != 0;
     }
@@ -392,10 +410,10 @@ static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
     auto pred_next = [&](int q) {
         Q3PredNext pn{}; pn.keys = L.keys; pn.n_key_parts = cbs / 16; pn.q = q; pn.ncb = ncb; pn.codec_q = e->codec[q]; pn.rows_q = m.codecq_rows; pn.d = de;
         pn.slots = slots; pn.row_slot = L.slot_id; pn.B = B; pn.codes = codes; pn.max_steps_cap = cap; pn.fb = L.fb;
-        pn.tts_pad = e->tts_pad; pn.xT = L.xT; pn.row_pos_t = L.row_pos_t; pn.pproj_q = e->pproj[q]; pn.proj_b = e->proj_b; pn.dp = dp; pn.px = L.px;
+        pn.tts_pad = e->tts_pad; pn.xT = L.T.x; pn.row_pos_t = L.row_pos_t; pn.pproj_q = e->pproj[q]; pn.proj_b = e->proj_b; pn.dp = dp; pn.px = L.P.x;
         const bool last = q == ncb - 1;
-        pn.nw = last ? e->T.attn_norm[0] : e->P.attn_norm[0]; pn.xb = last ? L.xbT : L.xbP; pn.ssp = last ? L.sspT : L.sspP;
-        if (last && e->T.a8) { pn.xscale = L.ascT; pn.x_rt16 = L.rt16T; }  // W8A8 Talker: its first operand as Q8_0 blocks
+        pn.nw = last ? e->T.attn_norm[0] : e->P.attn_norm[0]; pn.xb = last ? L.T.xb : L.P.xb; pn.ssp = last ? L.T.ssp : L.P.ssp;
+        if (last && e->T.a8) { pn.xscale = L.T.ascale; pn.x_rt16 = L.T.rt16; }  // W8A8 Talker: its first operand as Q8_0 blocks
         q3_launch_pred_next(pn, s);
     };
     for (int q = 0; q < ncb - 1; ++q) {  // pass q produces code_{q+1}
@@ -405,21 +423,21 @@ static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
         if (e->probe == 1 && q == 1 && B == L.nb && e->probe_i + 2 <= 8) { pe = &e->probe_ev[e->probe_i]; e->probe_i += 2; }
         // the Predictor's cache lives for one frame (src/tts/engine.rs:575: cleared per frame), so it is indexed by ROW: slot = row % B,
         // position = (q == 0 ? row / B : q + 1) — known without a load, the attention kernels request their operands at once
-        bad += run_layers(e, e->P, L.px, L.xbP, L.sspP, rows, nullptr, nullptr, L.sc, s, q > 0, pe, B, q == 0 ? 0 : q + 1);
+        bad += run_layers(e, e->P, L.P, {.rows = rows, .one_row_per_slot = q > 0, .probe = pe, .slot_mod = B, .pos_const = q == 0 ? 0 : q + 1}, L.sc, s);
         // head q on the rows that carry the newest position (pass 0: rows [B, 2B)), argmax epilogue
-        Q3BGemm g{}; g.a = L.xbP; g.a_row0 = q == 0 ? B : 0; g.B = B; g.w = e->P.head + head_tile_stride * q; g.K = dp; g.N = cbs;
-        g.ssp = q == 0 ? L.sspP + (size_t)B * (dp / 16) : L.sspP; g.ld_ssp = dp / 16; g.ntiles = dp / 16; g.d_norm = dp; g.eps = eps;
+        Q3BGemm g{}; g.a = L.P.xb; g.a_row0 = q == 0 ? B : 0; g.B = B; g.w = e->P.head + head_tile_stride * q; g.K = dp; g.N = cbs;
+        g.ssp = q == 0 ? L.P.ssp + (size_t)B * (dp / 16) : L.P.ssp; g.ld_ssp = dp / 16; g.ntiles = dp / 16; g.d_norm = dp; g.eps = eps;
         g.epi = Q3_EPI_ARGMAX; g.keys = L.keys; g.key_stride = cbs / 16;  // per-tile maxima; k_pred_next(q + 1) reduces them
         bad += q3_launch_bgemm(g, s) != 0;
     }
     pred_next(ncb - 1);
     hipEvent_t* pt = nullptr;  // probe mode 2: the Talker's layer-0 gate/up GEMM (the largest GEMM of the frame step)
     if (e->probe == 2 && B == L.nb && e->probe_i + 2 <= 8) { pt = &e->probe_ev[e->probe_i]; e->probe_i += 2; }
-    bad += run_layers(e, e->T, L.xT, L.xbT, L.sspT, B, L.row_pos_t, L.slot_id, L.sc, s, true, pt, 0, 0, nullptr, 0, 0, 0, L.ascT, L.rt16T);
-    Q3BGemm g{}; g.w_once = 1; g.a = L.xbT; g.B = B; g.w = e->T.head; g.wscale = e->T.q8 ? e->T.shead : nullptr; g.K = m.t_d_model; g.N = m.t_vocab;
-    g.ssp = L.sspT; g.ld_ssp = m.t_d_model / 16; g.ntiles = m.t_d_model / 16; g.d_norm = m.t_d_model; g.eps = eps;
+    bad += run_layers(e, e->T, L.T, {.rows = B, .row_pos = L.row_pos_t, .row_slot = L.slot_id, .one_row_per_slot = true, .probe = pt}, L.sc, s);
+    Q3BGemm g{}; g.w_once = 1; g.a = L.T.xb; g.B = B; g.w = e->T.head; g.wscale = e->T.q8 ? e->T.shead : nullptr; g.K = m.t_d_model; g.N = m.t_vocab;
+    g.ssp = L.T.ssp; g.ld_ssp = m.t_d_model / 16; g.ntiles = m.t_d_model / 16; g.d_norm = m.t_d_model; g.eps = eps;
     g.epi = Q3_EPI_STORE; g.y = L.logits; g.ldy = m.t_vocab;
-    if (e->T.a8) { g.ascale = L.ascT; g.a_rt16 = L.rt16T; bad += q3_launch_bgemm8(g, s) != 0; }
+    if (e->T.a8) { g.ascale = L.T.ascale; g.a_rt16 = L.T.rt16; bad += q3_launch_bgemm8(g, s) != 0; }
     else bad += q3_launch_bgemm(g, s) != 0;
     return bad;
 }
@@ -590,33 +608,20 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     {
         const int nb = B;
         const int nqkv_max = std::max(e->T.nqkv, e->P.nqkv), nq_max = std::max(e->T.nq, e->P.nq), F_max = std::max(e->T.F, e->P.F);
-        e->lanes.resize(1);
-        Q3Lane& L = e->lanes[0];
+        Q3Lane& L = e->lane;
         L.nb = nb;
         HIPC(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
         HIPC(hipEventCreate(&L.ev_begin)); HIPC(hipEventCreate(&L.ev_end));
-        TRYC(dalloc(e, &L.xT, (size_t)nb * m.t_d_model)); TRYC(dalloc(e, &L.logits, (size_t)nb * m.t_vocab)); TRYC(dalloc(e, &L.logits_tmp, (size_t)nb * std::max(m.t_vocab, m.t_d_model)));
-        TRYC(dalloc(e, &L.fb, (size_t)nb * m.d_embed));
-        TRYC(dalloc(e, &L.px, (size_t)2 * nb * m.p_d_model)); TRYC(dalloc(e, &L.keys, (size_t)nb * (m.codebook_size / 16)));
-        const size_t nb16 = ((size_t)nb + 15) & ~(size_t)15, nb2_16 = ((size_t)2 * nb + 15) & ~(size_t)15;  // A-tiled buffers hold whole 16-row tiles
-        TRYC(dalloc(e, &L.xbT, nb16 * m.t_d_model)); TRYC(dalloc(e, &L.sspT, (size_t)nb * (m.t_d_model / 16)));
-        L.rt16T = (int)(nb16 / 16);
-        if (e->T.a8) TRYC(dalloc(e, &L.ascT, nb16 * (m.t_d_model / 32)));
-        TRYC(dalloc(e, &L.xbP, nb2_16 * m.p_d_model)); TRYC(dalloc(e, &L.sspP, (size_t)2 * nb * (m.p_d_model / 16)));
+        TRYC(alloc_rows(e, L.T, (size_t)nb, m.t_d_model, e->T.a8)); TRYC(alloc_rows(e, L.P, (size_t)2 * nb, m.p_d_model, false));
+        TRYC(dalloc(e, &L.logits, (size_t)nb * m.t_vocab)); TRYC(dalloc(e, &L.logits_tmp, (size_t)nb * std::max(m.t_vocab, m.t_d_model)));
+        TRYC(dalloc(e, &L.fb, (size_t)nb * m.d_embed)); TRYC(dalloc(e, &L.keys, (size_t)nb * (m.codebook_size / 16)));
         TRYC(dalloc(e, &L.row_pos_t, (size_t)nb)); TRYC(dalloc(e, &L.slot_id, (size_t)nb)); TRYC(dalloc(e, &L.perm, (size_t)nb));
-        TRYC(dalloc(e, &L.posA, (size_t)2 * nb)); TRYC(dalloc(e, &L.slotA, (size_t)2 * nb)); TRYC(dalloc(e, &L.pos_q, (size_t)m.n_codebooks * nb));
-        std::vector<int> sid(nb), pa(2 * nb), sla(2 * nb), pq((size_t)m.n_codebooks * nb), rp(nb, -1);
-        // pass A of the Predictor runs 2 rows per slot: rows [0, rows) at position 0 (the projected hidden state), rows [rows, 2 rows) at
-        // position 1 (the code row); the maps follow the current row bucket (plan_rows)
-        for (int b = 0; b < nb; ++b) { sid[b] = b; pa[b] = 0; pa[nb + b] = 1; sla[b] = sla[nb + b] = b; }
-        for (int q = 0; q < m.n_codebooks; ++q) for (int b = 0; b < nb; ++b) pq[(size_t)q * nb + b] = q + 1;  // src/tts/engine.rs:604
+        std::vector<int> sid(nb), rp(nb, -1);
+        for (int b = 0; b < nb; ++b) sid[b] = b;
         HIPC(hipMemcpyAsync(L.slot_id, sid.data(), nb * 4, hipMemcpyHostToDevice, s));
-        HIPC(hipMemcpyAsync(L.posA, pa.data(), 2 * nb * 4, hipMemcpyHostToDevice, s));
-        HIPC(hipMemcpyAsync(L.slotA, sla.data(), 2 * nb * 4, hipMemcpyHostToDevice, s));
-        HIPC(hipMemcpyAsync(L.pos_q, pq.data(), pq.size() * 4, hipMemcpyHostToDevice, s));
         HIPC(hipMemcpyAsync(L.row_pos_t, rp.data(), nb * 4, hipMemcpyHostToDevice, s));
         HIPC(hipStreamSynchronize(s));
-        TRYC(alloc_scratch(e, L.sc, 2 * nb, nqkv_max, nq_max, F_max, std::max(m.t_d_model, m.p_d_model)));
+        TRYC(alloc_scratch(e, L.sc, 2 * nb, nqkv_max, nq_max, F_max));
         // row buckets: 1, 2, 4, 8, then the multiples of 16 (the GEMM's row tiles are 16 wide: a 48-row step costs 3/4 of a 64-row one)
         for (int r = 1; r < nb && r < 16; r *= 2) e->buckets.push_back(r);
         for (int r = 16; r < nb; r += 16) e->buckets.push_back(r);
@@ -624,11 +629,8 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
         e->cur_bucket = (int)e->buckets.size() - 1;
         e->row_of_slot = sid; e->slot_of_row = sid;
     }
-    TRYC(alloc_scratch(e, e->sc_pre, cfg->n_ctx, e->T.nqkv, e->T.nq, e->T.F, m.t_d_model));
-    TRYC(dalloc(e, &e->xp, (size_t)cfg->n_ctx * m.t_d_model));
-    TRYC(dalloc(e, &e->xbp, (((size_t)cfg->n_ctx + 15) & ~(size_t)15) * m.t_d_model)); TRYC(dalloc(e, &e->sspp, (size_t)cfg->n_ctx * (m.t_d_model / 16)));
-    e->rt16p = (cfg->n_ctx + 15) / 16;
-    if (e->T.a8) TRYC(dalloc(e, &e->ascp, (size_t)e->rt16p * 16 * (m.t_d_model / 32)));
+    TRYC(alloc_scratch(e, e->sc_pre, cfg->n_ctx, e->T.nqkv, e->T.nq, e->T.F));
+    TRYC(alloc_rows(e, e->pf, (size_t)cfg->n_ctx, m.t_d_model, e->T.a8));
     TRYC(dalloc(e, &e->pf_pos, (size_t)cfg->n_ctx)); TRYC(dalloc(e, &e->pf_slot, (size_t)cfg->n_ctx)); TRYC(dalloc(e, &e->pf_seg, (size_t)4 * cfg->max_batch));
     { std::vector<int> pp(cfg->n_ctx); for (int i = 0; i < cfg->n_ctx; ++i) pp[i] = i;
       HIPC(hipMemcpyAsync(e->pf_pos, pp.data(), pp.size() * 4, hipMemcpyHostToDevice, s)); HIPC(hipStreamSynchronize(s)); }
@@ -652,7 +654,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     // for profilers)
     HIPC(hipStreamSynchronize(s));
     if (!(getenv("Q3TTS_NO_GRAPH") && atoi(getenv("Q3TTS_NO_GRAPH")))) {
-        Q3Lane& L = e->lanes[0];
+        Q3Lane& L = e->lane;
         L.graphs.resize(e->buckets.size(), nullptr); L.execs.resize(e->buckets.size(), nullptr);
         for (size_t bi = 0; bi < e->buckets.size(); ++bi) {
             HIPC(hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal));
@@ -681,15 +683,14 @@ extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
     q3_mel_destroy(e);
     q3_clone_destroy(e);
     if (e->first_chunk_host) hipHostFree(e->first_chunk_host);
-    for (auto& L : e->lanes) {
+    {
+        Q3Lane& L = e->lane;
         if (L.stream) hipStreamSynchronize(L.stream);
         for (auto ge : L.execs) if (ge) hipGraphExecDestroy(ge);
         for (auto gr : L.graphs) if (gr) hipGraphDestroy(gr);
-        hipFree(L.logits_tmp); hipFree(L.perm);
-        hipFree(L.xT); hipFree(L.logits); hipFree(L.fb); hipFree(L.px); hipFree(L.keys);
-        hipFree(L.xbT); hipFree(L.sspT); hipFree(L.xbP); hipFree(L.sspP); hipFree(L.ascT);
-        hipFree(L.row_pos_t); hipFree(L.slot_id); hipFree(L.posA); hipFree(L.slotA); hipFree(L.pos_q);
-        hipFree(L.sc.qkv); hipFree(L.sc.att); hipFree(L.sc.h); hipFree(L.sc.asc_att); hipFree(L.sc.asc_h);
+        free_rows(L.T); free_rows(L.P); free_scratch(L.sc);
+        hipFree(L.logits); hipFree(L.logits_tmp); hipFree(L.fb); hipFree(L.keys);
+        hipFree(L.row_pos_t); hipFree(L.slot_id); hipFree(L.perm);
         if (L.ev_begin) hipEventDestroy(L.ev_begin); if (L.ev_end) hipEventDestroy(L.ev_end);
         if (L.stream) hipStreamDestroy(L.stream);
     }
@@ -698,8 +699,8 @@ extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
     hipFree(e->tts_pad_own); hipFree(e->marker_row); hipFree(e->dev_pcm);
     hipFree(e->slots); if (e->slots_host) hipHostFree(e->slots_host);
     hipFree(e->codes); hipFree(e->rng);
-    hipFree(e->sc_pre.qkv); hipFree(e->sc_pre.att); hipFree(e->sc_pre.h); hipFree(e->sc_pre.asc_att); hipFree(e->sc_pre.asc_h); hipFree(e->ascp);
-    hipFree(e->xp); hipFree(e->xbp); hipFree(e->sspp); hipFree(e->pf_pos); hipFree(e->pf_slot); hipFree(e->pf_seg); hipFree(e->prow_dev); hipFree(e->spk_dev); hipFree(e->refcodes_dev);
+    free_scratch(e->sc_pre); free_rows(e->pf);
+    hipFree(e->pf_pos); hipFree(e->pf_slot); hipFree(e->pf_seg); hipFree(e->prow_dev); hipFree(e->spk_dev); hipFree(e->refcodes_dev);
     for (auto ev : e->fin_ev) if (ev) hipEventDestroy(ev);
     for (auto ev : e->probe_ev) if (ev) hipEventDestroy(ev);
     if (e->ev0) hipEventDestroy(e->ev0); if (e->ev1) hipEventDestroy(e->ev1); if (e->ev2) hipEventDestroy(e->ev2); if (e->ev3) hipEventDestroy(e->ev3);
@@ -811,11 +812,11 @@ extern "C" int q3tts_build_prompt(q3tts_engine* e, const q3tts_prompt_desc* p, f
     if (!e || !p || !out_embd || !out_n) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     int n = 0;
-    TRY(build_prompt_dev(e, p, e->xp, e->cfg.n_ctx, &n));
+    TRY(build_prompt_dev(e, p, e->pf.x, e->cfg.n_ctx, &n));
     const size_t bytes = (size_t)n * e->cfg.model.d_embed * 4;
     float* h = (float*)malloc(bytes);
     if (!h) return q3_set_err(e, Q3TTS_ERR_OOM, "malloc");
-    hipError_t er = hipMemcpyAsync(h, e->xp, bytes, hipMemcpyDeviceToHost, e->stream);
+    hipError_t er = hipMemcpyAsync(h, e->pf.x, bytes, hipMemcpyDeviceToHost, e->stream);
     if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
     if (er != hipSuccess) { free(h); return q3_set_err(e, Q3TTS_ERR_DEVICE, hipGetErrorString(er)); }
     *out_embd = h; *out_n = n;
@@ -828,7 +829,7 @@ extern "C" int q3tts_build_prompt(q3tts_engine* e, const q3tts_prompt_desc* p, f
 // Map the live slots onto rows [0, n) of the smallest bucket that holds them (idle slots fill the rest: every row keeps
 // a distinct, valid slot). Row-indexed state that outlives a frame (the Talker logits) moves with its slot.
 static int plan_rows(q3tts_engine* e, const std::vector<int>& live_in) {
-    Q3Lane& L = e->lanes[0];
+    Q3Lane& L = e->lane;
     const int B = e->B;
     std::vector<int> live(live_in);
     std::sort(live.begin(), live.end());
@@ -837,24 +838,20 @@ static int plan_rows(q3tts_engine* e, const std::vector<int>& live_in) {
     bool ok = bi == e->cur_bucket;
     if (ok) for (int b : live) if (e->row_of_slot[b] >= e->buckets[bi]) { ok = false; break; }
     if (ok) return Q3TTS_OK;
-    std::vector<int> slot_of_row(B, -1), perm(B), used(B, 0), sla(2 * (size_t)B, 0), pa(2 * (size_t)B, 0);
+    std::vector<int> slot_of_row(B, -1), perm(B), used(B, 0);
     int r = 0;
     for (int b : live) { slot_of_row[r++] = b; used[b] = 1; }
     for (int b = 0; b < B && r < B; ++b) if (!used[b]) slot_of_row[r++] = b;
-    const int bs = e->buckets[bi];  // pass A: rows [0, bs) at position 0, rows [bs, 2 bs) at position 1
     for (r = 0; r < B; ++r) perm[r] = e->row_of_slot[slot_of_row[r]];
-    for (r = 0; r < bs; ++r) { sla[r] = sla[bs + r] = slot_of_row[r]; pa[bs + r] = 1; }
     hipStream_t s = e->stream;
     Q3_HIP(e, hipMemcpyAsync(L.perm, perm.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
     Q3_HIP(e, hipMemcpyAsync(L.slot_id, slot_of_row.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
-    Q3_HIP(e, hipMemcpyAsync(L.slotA, sla.data(), (size_t)2 * B * 4, hipMemcpyHostToDevice, s));
-    Q3_HIP(e, hipMemcpyAsync(L.posA, pa.data(), (size_t)2 * B * 4, hipMemcpyHostToDevice, s));
     // row state that outlives a frame: the Talker logits (sampled at the next frame) and its last hidden row (the
     // Predictor's first input)
     q3_launch_gather_rows(L.logits_tmp, L.logits, L.perm, B, e->cfg.model.t_vocab, s);
     Q3_HIP(e, hipMemcpyAsync(L.logits, L.logits_tmp, (size_t)B * e->cfg.model.t_vocab * 4, hipMemcpyDeviceToDevice, s));
-    q3_launch_gather_rows(L.logits_tmp, L.xT, L.perm, B, e->cfg.model.t_d_model, s);
-    Q3_HIP(e, hipMemcpyAsync(L.xT, L.logits_tmp, (size_t)B * e->cfg.model.t_d_model * 4, hipMemcpyDeviceToDevice, s));
+    q3_launch_gather_rows(L.logits_tmp, L.T.x, L.perm, B, e->cfg.model.t_d_model, s);
+    Q3_HIP(e, hipMemcpyAsync(L.T.x, L.logits_tmp, (size_t)B * e->cfg.model.t_d_model * 4, hipMemcpyDeviceToDevice, s));
     Q3_HIP(e, hipStreamSynchronize(s));  // the uploads read locals
     for (r = 0; r < B; ++r) e->row_of_slot[slot_of_row[r]] = r;
     e->slot_of_row = slot_of_row;
@@ -866,7 +863,7 @@ static int plan_rows(q3tts_engine* e, const std::vector<int>& live_in) {
 static double now_ms();
 static int run_chunk(q3tts_engine* e, int CH, float* dev_ms) {
     hipStream_t s = e->stream;
-    Q3Lane& L = e->lanes[0];
+    Q3Lane& L = e->lane;
     const double hp0 = now_ms();
     Q3_HIP(e, hipEventRecord(e->ev1, s));  // admissions (prefill, state uploads) precede the frames
     Q3_HIP(e, hipStreamWaitEvent(L.stream, e->ev1, 0));
@@ -911,14 +908,33 @@ static uint64_t wall_seed() {
 // P positions receive a copy of the prefix's K/V (k_kv_prefix, one launch for the group) before the layers run.
 struct Adm { int b; const q3tts_request* r; int n, row0, max_steps, P; };
 
+// The Talker's layers over the first pos.size() prefill rows (e->pf.x holds them): row i sits at position pos[i] of slot slot[i]; seg: the
+// same rows as per-slot runs (pf_seg), seg_max_n the longest run, seg_max_t the furthest position + 1. The maps are uploaded and the stream
+// is synchronised (they are the caller's locals); kp (admission only): the voice prefixes' K/V enter their slots before the layers run.
+// Returns the number of refused launches, or -1 when an upload failed (e->err says which).
+static int prefill_layers(q3tts_engine* e, const std::vector<int>& pos, const std::vector<int>& slot, const std::vector<int>& seg, int seg_max_n,
+                          int seg_max_t, const Q3KvPrefix* kp) {
+    const int rows = (int)pos.size(), d = e->T.d;
+    hipStream_t s = e->stream;
+    hipError_t er = hipMemcpyAsync(e->pf_pos, pos.data(), (size_t)rows * 4, hipMemcpyHostToDevice, s);
+    if (er == hipSuccess) er = hipMemcpyAsync(e->pf_slot, slot.data(), (size_t)rows * 4, hipMemcpyHostToDevice, s);
+    if (er == hipSuccess) er = hipMemcpyAsync(e->pf_seg, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, s);
+    if (er == hipSuccess) er = hipStreamSynchronize(s);
+    if (er != hipSuccess) { q3_set_err(e, Q3TTS_ERR_DEVICE, std::string("prefill row maps: ") + hipGetErrorString(er)); return -1; }
+    if (kp) q3_launch_kv_prefix(*kp, s);
+    const Q3Rows& r = e->pf;
+    if (e->T.a8) q3_launch_norm_inputs_q8(r.x, d, rows, d, e->T.attn_norm[0], (int8_t*)r.xb, r.ascale, r.rt16, r.ssp, d / 16, s);
+    else q3_launch_norm_inputs(r.x, d, rows, d, e->T.attn_norm[0], r.xb, 0, r.ssp, d / 16, s);
+    return run_layers(e, e->T, r, {.rows = rows, .row_pos = e->pf_pos, .row_slot = e->pf_slot, .seg = e->pf_seg, .n_seg = (int)seg.size() / 4,
+                                   .seg_max_n = seg_max_n, .seg_max_t = seg_max_t}, e->sc_pre, s);
+}
+
 static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
     const q3tts_model_config& m = e->cfg.model;
     hipStream_t s = e->stream;
     if (grp.empty()) return Q3TTS_OK;
     std::vector<int> pos(total), slot(total);
     for (const Adm& a : grp) for (int i = 0; i < a.n; ++i) { pos[a.row0 + i] = a.P + i; slot[a.row0 + i] = a.b; }
-    Q3_HIP(e, hipMemcpyAsync(e->pf_pos, pos.data(), (size_t)total * 4, hipMemcpyHostToDevice, s));
-    Q3_HIP(e, hipMemcpyAsync(e->pf_slot, slot.data(), (size_t)total * 4, hipMemcpyHostToDevice, s));
     std::vector<int> seg; int seg_max = 0, seg_max_t = 0;  // the same rows as runs: every request's rows are consecutive, positions P .. P + n - 1
     Q3KvPrefix kp{}; kp.kc = e->T.kc; kp.vc = e->T.vc; kp.layer_stride = e->T.layer_stride; kp.n_ctx = e->T.n_ctx; kp.L = e->T.L; kp.Hkv = e->T.Hkv; kp.hd = e->T.hd;
     for (const Adm& a : grp) {
@@ -930,25 +946,21 @@ static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
             kp.pk[kp.n] = x->k; kp.pv[kp.n] = x->v; kp.P[kp.n] = x->P; kp.slot[kp.n] = a.b; ++kp.n;
         }
     }
-    Q3_HIP(e, hipMemcpyAsync(e->pf_seg, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, s));
-    Q3_HIP(e, hipStreamSynchronize(s));  // pos/slot are locals
-    q3_launch_kv_prefix(kp, s);
-    if (e->T.a8) q3_launch_norm_inputs_q8(e->xp, m.t_d_model, total, m.t_d_model, e->T.attn_norm[0], (int8_t*)e->xbp, e->ascp, e->rt16p, e->sspp, m.t_d_model / 16, s);
-    else q3_launch_norm_inputs(e->xp, m.t_d_model, total, m.t_d_model, e->T.attn_norm[0], e->xbp, 0, e->sspp, m.t_d_model / 16, s);
-    const int rl = run_layers(e, e->T, e->xp, e->xbp, e->sspp, total, e->pf_pos, e->pf_slot, e->sc_pre, s, false, nullptr, 0, 0, e->pf_seg, (int)grp.size(), seg_max, seg_max_t, e->ascp, e->rt16p);
+    const int rl = prefill_layers(e, pos, slot, seg, seg_max, seg_max_t, &kp);
+    if (rl < 0) return Q3TTS_ERR_DEVICE;
     if (rl) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefill: a kernel launch was refused for this model shape");
     Q3_HIP(e, hipGetLastError());
     for (const Adm& a : grp) {
         const q3tts_request* r = a.r;
         const int b = a.b;
-        Q3Lane& L = e->lanes[0];
+        Q3Lane& L = e->lane;
         const int row = e->row_of_slot[b];
-        q3_launch_copy_rows(L.xT + (size_t)row * m.t_d_model, m.t_d_model, e->xp + (size_t)(a.row0 + a.n - 1) * m.t_d_model, m.t_d_model, 1, m.t_d_model, s);
+        q3_launch_copy_rows(L.T.x + (size_t)row * m.t_d_model, m.t_d_model, e->pf.x + (size_t)(a.row0 + a.n - 1) * m.t_d_model, m.t_d_model, 1, m.t_d_model, s);
         const size_t lastr = (size_t)(a.row0 + a.n - 1);  // the last prompt row's norm inputs for out_norm came out of the last block
-        Q3BGemm g{}; g.a = e->xbp; g.a_row0 = (int)lastr; g.B = 1; g.w = e->T.head; g.wscale = e->T.q8 ? e->T.shead : nullptr; g.K = m.t_d_model; g.N = m.t_vocab;
-        g.ssp = e->sspp + lastr * (m.t_d_model / 16); g.ld_ssp = m.t_d_model / 16; g.ntiles = m.t_d_model / 16; g.d_norm = m.t_d_model; g.eps = m.rms_eps;
+        Q3BGemm g{}; g.a = e->pf.xb; g.a_row0 = (int)lastr; g.B = 1; g.w = e->T.head; g.wscale = e->T.q8 ? e->T.shead : nullptr; g.K = m.t_d_model; g.N = m.t_vocab;
+        g.ssp = e->pf.ssp + lastr * (m.t_d_model / 16); g.ld_ssp = m.t_d_model / 16; g.ntiles = m.t_d_model / 16; g.d_norm = m.t_d_model; g.eps = m.rms_eps;
         g.epi = Q3_EPI_STORE; g.y = L.logits + (size_t)row * m.t_vocab; g.ldy = m.t_vocab;
-        if (e->T.a8) { g.ascale = e->ascp; g.a_rt16 = e->rt16p; }
+        if (e->T.a8) { g.ascale = e->pf.ascale; g.a_rt16 = e->pf.rt16; }
         if (e->T.a8 ? q3_launch_bgemm8(g, s) : q3_launch_bgemm(g, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefill head: launch refused for this model shape");
         // sampler stream (src/tts/engine.rs:473-485)
         float temperature = e->temperature, top_p = e->top_p; int top_k = e->top_k, has_seed = e->has_seed; uint64_t seed = e->seed;
@@ -992,9 +1004,9 @@ static int admit_many(q3tts_engine* e, const int* slots, const q3tts_request* co
                 n = r->n_tok;
                 if (n <= 0 || P + n > e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "n_tok out of range"); break; }
                 if (n > room) { if (total == 0) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "n_tok out of range"); break; } }
-                else { Q3_HIP(e, hipMemcpyAsync(e->xp + (size_t)total * m.d_embed, r->prompt_embd, (size_t)n * m.d_embed * 4, hipMemcpyHostToDevice, s)); break; }
+                else { Q3_HIP(e, hipMemcpyAsync(e->pf.x + (size_t)total * m.d_embed, r->prompt_embd, (size_t)n * m.d_embed * 4, hipMemcpyHostToDevice, s)); break; }
             } else if (r->prompt) {
-                const int brc = build_prompt_dev(e, r->prompt, e->xp + (size_t)total * m.d_embed, room, &n, x ? PROMPT_TEXT : PROMPT_WHOLE);
+                const int brc = build_prompt_dev(e, r->prompt, e->pf.x + (size_t)total * m.d_embed, room, &n, x ? PROMPT_TEXT : PROMPT_WHOLE);
                 if (brc == Q3TTS_OK) break;
                 if (total == 0) { rc[i] = brc; break; }
             } else { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "request has neither prompt_embd nor prompt"); break; }
@@ -1031,11 +1043,11 @@ extern "C" int q3tts_prefix_create(q3tts_engine* e, const q3tts_prompt_desc* p, 
     hipStream_t s = e->stream;
     const int n_ctx = e->cfg.n_ctx;
     int n = 0;
-    if (p) TRY(build_prompt_dev(e, p, e->xp, n_ctx - 1, &n, PROMPT_VOICE));
+    if (p) TRY(build_prompt_dev(e, p, e->pf.x, n_ctx - 1, &n, PROMPT_VOICE));
     else {
         if (n_tok <= 0 || n_tok >= n_ctx) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: n_tok outside 1 .. n_ctx - 1");
         n = n_tok;
-        Q3_HIP(e, hipMemcpyAsync(e->xp, embd, (size_t)n * m.d_embed * 4, hipMemcpyHostToDevice, s));
+        Q3_HIP(e, hipMemcpyAsync(e->pf.x, embd, (size_t)n * m.d_embed * 4, hipMemcpyHostToDevice, s));
     }
     Q3Tfm& t = e->T;
     q3tts_prefix* x = new q3tts_prefix();
@@ -1047,20 +1059,13 @@ extern "C" int q3tts_prefix_create(q3tts_engine* e, const q3tts_prompt_desc* p, 
     auto fail = [&](int code, const std::string& msg) { hipStreamSynchronize(s); hipFree(x->k); hipFree(x->v); delete x; return q3_set_err(e, code, msg); };
     std::vector<int> pos(n), zero(n, 0);
     for (int i = 0; i < n; ++i) pos[i] = i;
-    const int seg[4] = {0, n, 0, 0};
-    hipError_t er = hipMemcpyAsync(e->pf_pos, pos.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
-    if (er == hipSuccess) er = hipMemcpyAsync(e->pf_slot, zero.data(), (size_t)n * 4, hipMemcpyHostToDevice, s);
-    if (er == hipSuccess) er = hipMemcpyAsync(e->pf_seg, seg, sizeof(seg), hipMemcpyHostToDevice, s);
-    if (er == hipSuccess) er = hipStreamSynchronize(s);  // locals
-    if (er != hipSuccess) return fail(Q3TTS_ERR_DEVICE, hipGetErrorString(er));
-    if (t.a8) q3_launch_norm_inputs_q8(e->xp, m.t_d_model, n, m.t_d_model, t.attn_norm[0], (int8_t*)e->xbp, e->ascp, e->rt16p, e->sspp, m.t_d_model / 16, s);
-    else q3_launch_norm_inputs(e->xp, m.t_d_model, n, m.t_d_model, t.attn_norm[0], e->xbp, 0, e->sspp, m.t_d_model / 16, s);
     uint16_t *kc = t.kc, *vc = t.vc; const size_t ls = t.layer_stride; const int nc = t.n_ctx;
     t.kc = x->k; t.vc = x->v; t.layer_stride = (size_t)t.Hkv * x->np * t.hd; t.n_ctx = x->np;
-    const int rl = run_layers(e, t, e->xp, e->xbp, e->sspp, n, e->pf_pos, e->pf_slot, e->sc_pre, s, false, nullptr, 0, 0, e->pf_seg, 1, n, n, e->ascp, e->rt16p);
+    const int rl = prefill_layers(e, pos, zero, {0, n, 0, 0}, n, n, nullptr);
     t.kc = kc; t.vc = vc; t.layer_stride = ls; t.n_ctx = nc;
+    if (rl < 0) return fail(Q3TTS_ERR_DEVICE, std::string(e->err));
     if (rl) return fail(Q3TTS_ERR_INVALID, "prefix: a kernel launch was refused for this model shape");
-    er = hipGetLastError();
+    hipError_t er = hipGetLastError();
     if (er == hipSuccess) er = hipStreamSynchronize(s);
     if (er != hipSuccess) return fail(Q3TTS_ERR_DEVICE, hipGetErrorString(er));
     *out = x;
@@ -1453,641 +1458,4 @@ extern "C" int q3tts_stream_end(q3tts_stream* st, q3tts_result* out) {
     hipStreamSynchronize(e->stream);
     delete st;
     return rc;
-}
-
-// ------------------------------------------------------------------------------------------------
-// kernel-level test hooks
-// ------------------------------------------------------------------------------------------------
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes + 64) == hipSuccess && hipMemset(p, 0, bytes + 64) == hipSuccess ? 0 : -1; }
-};
-#define HK(call) do { hipError_t er__ = (call); if (er__ != hipSuccess) return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(er__)); } while (0)
-
-extern "C" int q3tts_k_gemm_exact(int32_t device, const float* x, int32_t B, int32_t K, const uint16_t* w, int32_t N, const float* norm_w,
-                                  float eps, const float* bias, int32_t epi, float* y, uint64_t* keys, int32_t iters, float* mean_ms) {
-    if (!x || !w || !y || B <= 0 || K % 512 || N % 16 || (norm_w && K > 8192)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "gemm hook: bad shape");
-    if (epi == Q3_EPI_SWIGLU && (N % 32)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "swiglu needs N % 32 == 0");
-    HK(hipSetDevice(device));
-    const int F = N / 2;
-    const size_t ny = epi == Q3_EPI_SWIGLU ? (size_t)B * F : (size_t)B * N;
-    DevBuf dx, dw, dwt, dn, db, dy, dk;
-    if (dx.alloc((size_t)B * K * 4) || dw.alloc((size_t)N * K * 2) || dwt.alloc((size_t)N * K * 2) || dn.alloc((size_t)K * 4) ||
-        db.alloc((size_t)N * 4) || dy.alloc(ny * 4) || dk.alloc((size_t)B * 8))
-        return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    HK(hipMemcpy(dx.p, x, (size_t)B * K * 4, hipMemcpyHostToDevice));
-    HK(hipMemcpy(dw.p, w, (size_t)N * K * 2, hipMemcpyHostToDevice));
-    if (norm_w) HK(hipMemcpy(dn.p, norm_w, (size_t)K * 4, hipMemcpyHostToDevice));
-    if (bias) HK(hipMemcpy(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
-    if (epi == Q3_EPI_RESID) HK(hipMemcpy(dy.p, y, ny * 4, hipMemcpyHostToDevice));
-    Q3Fill f{}; f.dst = (uint4*)dwt.p; f.N = N; f.K = K;
-    if (epi == Q3_EPI_SWIGLU) { f.mode = 1; f.src_a = (const uint16_t*)dw.p; f.src_b = (const uint16_t*)dw.p + (size_t)F * K; }
-    else { f.mode = 0; f.row0 = 0; f.rows = N; f.src_a = (const uint16_t*)dw.p; }
-    q3_launch_fill_tiled(f, nullptr);
-    Q3Gemm g{}; g.x = (const float*)dx.p; g.ldx = K; g.B = B; g.w = (const uint4*)dwt.p; g.K = K; g.N = N;
-    g.norm_w = norm_w ? (const float*)dn.p : nullptr; g.eps = eps; g.bias = bias ? (const float*)db.p : nullptr;
-    g.y = (float*)dy.p; g.ldy = epi == Q3_EPI_SWIGLU ? F : N; g.keys = (unsigned long long*)dk.p; g.key_stride = 1; g.epi = epi;
-    q3_launch_gemm(g, nullptr);
-    HK(hipDeviceSynchronize());
-    if (epi == Q3_EPI_ARGMAX) {
-        if (keys) HK(hipMemcpy(keys, dk.p, (size_t)B * 8, hipMemcpyDeviceToHost));
-    } else HK(hipMemcpy(y, dy.p, ny * 4, hipMemcpyDeviceToHost));
-#ifdef Q3_STAMPS
-    {  // experiment builds: phase stamps of workgroup 0 / wave 0 of one warm launch (shader-clock cycles from kernel entry)
-        DevBuf dd; dd.alloc(64 * 8);
-        g.dbg = nullptr; q3_launch_gemm(g, nullptr); q3_launch_gemm(g, nullptr);
-        g.dbg = (unsigned long long*)dd.p; hipMemset(dd.p, 0, 64 * 8);
-        q3_launch_gemm(g, nullptr); hipDeviceSynchronize();
-        unsigned long long st[8]; hipMemcpy(st, dd.p, 64, hipMemcpyDeviceToHost);
-        fprintf(stderr, "stamps B=%d K=%d N=%d norm=%d epi=%d: entry->loop %llu | first operands %llu | loop end %llu | barrier %llu | sums %llu | stores done %llu\n",
-                B, K, N, norm_w ? 1 : 0, epi, st[1] - st[0], st[2] - st[0], st[3] - st[0], st[4] - st[0], st[5] - st[0], st[6] - st[0]);
-        unsigned long long ws[64]; hipMemcpy(ws, dd.p, 64 * 8, hipMemcpyDeviceToHost);
-        for (int w = 0; w < 8; ++w)
-            fprintf(stderr, "   wave %d: first operands %llu, mid loop %llu, loop end %llu\n", w, ws[8 + w * 4] - st[0], ws[8 + w * 4 + 1] - st[0], ws[8 + w * 4 + 2] - st[0]);
-        g.dbg = nullptr;
-    }
-#endif
-    if (iters > 0 && mean_ms) {
-        g.epi = epi == Q3_EPI_RESID ? Q3_EPI_STORE : epi;
-        hipEvent_t a, b; HK(hipEventCreate(&a)); HK(hipEventCreate(&b));
-        q3_launch_gemm(g, nullptr);
-        HK(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; ++i) q3_launch_gemm(g, nullptr);
-        HK(hipEventRecord(b, nullptr)); HK(hipEventSynchronize(b));
-        float ms = 0; hipEventElapsedTime(&ms, a, b); *mean_ms = ms / iters;
-        hipEventDestroy(a); hipEventDestroy(b);
-    }
-    return Q3TTS_OK;
-}
-
-extern "C" int q3tts_k_attention(int32_t device, const float* qkv, int32_t n_rows, int32_t pos0, int32_t Hq, int32_t Hkv, int32_t hd,
-                                 const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, float* out) {
-    if (!qkv || !out || hd != 128 || n_rows <= 0 || Hq % Hkv) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention hook: bad shape");
-    HK(hipSetDevice(device));
-    const int n_ctx = ((pos0 + n_rows + 63) / 64) * 64, ld = (Hq + 2 * Hkv) * hd;
-    std::vector<float> cs, sn;
-    rope_tables(n_ctx, hd, theta, sections, cs, sn);
-    std::vector<int> rp(n_rows), rs(n_rows, 0);
-    for (int i = 0; i < n_rows; ++i) rp[i] = pos0 + i;
-    DevBuf dq, dout, dqn, dkn, dcs, dsn, dkc, dvc, drp, drs;
-    if (dq.alloc((size_t)n_rows * ld * 4) || dout.alloc((size_t)n_rows * Hq * hd * 4) || dqn.alloc(hd * 4) || dkn.alloc(hd * 4) ||
-        dcs.alloc(cs.size() * 4) || dsn.alloc(sn.size() * 4) || dkc.alloc((size_t)Hkv * n_ctx * hd * 2) || dvc.alloc((size_t)Hkv * n_ctx * hd * 2) ||
-        drp.alloc(n_rows * 4) || drs.alloc(n_rows * 4))
-        return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    HK(hipMemcpy(dq.p, qkv, (size_t)n_rows * ld * 4, hipMemcpyHostToDevice));
-    HK(hipMemcpy(dqn.p, qnw, hd * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dkn.p, knw, hd * 4, hipMemcpyHostToDevice));
-    HK(hipMemcpy(dcs.p, cs.data(), cs.size() * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dsn.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
-    HK(hipMemcpy(drp.p, rp.data(), n_rows * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(drs.p, rs.data(), n_rows * 4, hipMemcpyHostToDevice));
-    Q3QkPrep qp{}; qp.qkv = (float*)dq.p; qp.ld = ld; qp.rows = n_rows; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = hd; qp.qnw = (const float*)dqn.p;
-    qp.knw = (const float*)dkn.p; qp.eps = eps; qp.cs = (const float*)dcs.p; qp.sn = (const float*)dsn.p; qp.kc = (uint16_t*)dkc.p;
-    qp.vc = (uint16_t*)dvc.p; qp.n_ctx = n_ctx; qp.row_pos = (const int*)drp.p; qp.row_slot = (const int*)drs.p;
-    q3_launch_qk_prep(qp, nullptr);
-    Q3Attend at{}; at.qkv = (const float*)dq.p; at.ld = ld; at.rows = n_rows; at.out = (float*)dout.p; at.ldo = Hq * hd; at.Hq = Hq; at.Hkv = Hkv;
-    at.hd = hd; at.kc = (const uint16_t*)dkc.p; at.vc = (const uint16_t*)dvc.p; at.n_ctx = n_ctx; at.row_pos = qp.row_pos; at.row_slot = qp.row_slot;
-    q3_launch_attend(at, nullptr);
-    HK(hipDeviceSynchronize());
-    HK(hipMemcpy(out, dout.p, (size_t)n_rows * Hq * hd * 4, hipMemcpyDeviceToHost));
-    return Q3TTS_OK;
-}
-
-// Decode attention as the engine's frame step runs it: per slot, rows 0 .. len - 2 go through k_qk_prep into a cache of n_ctx positions,
-// then ONE fused decode launch (one row per slot at pos = len - 1; q/k prep and the K/V append in-kernel) through q3_launch_attend under
-// decode policy `policy` (-1: the current one). qkv holds the slots' rows back to back ([sum lens][(Hq + 2 Hkv) hd]); out_f32 [n_slots][Hq hd];
-// out_bf16 (optional): the same launch writing the A-tiled bf16 operand of the O projection, untiled here to [n_slots][Hq hd].
-extern "C" int q3tts_k_attention_decode(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq,
-                                        int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta,
-                                        const int32_t* sections, int32_t policy, float* out_f32, uint16_t* out_bf16) {
-    if (!qkv || !lens || !out_f32 || hd != 128 || n_slots <= 0 || Hkv <= 0 || Hq % Hkv || Hq / Hkv < 2 || n_ctx <= 0 || n_ctx % 64 || policy < -1 || policy > 1)
-        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode hook: bad shape");
-    long long total = 0;
-    for (int s = 0; s < n_slots; ++s) {
-        if (lens[s] < 1 || lens[s] > n_ctx) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode hook: a length outside 1 .. n_ctx");
-        total += lens[s];
-    }
-    HK(hipSetDevice(device));
-    const int ld = (Hq + 2 * Hkv) * hd, nq = Hq * hd, npre = (int)(total - n_slots), r16 = (n_slots + 15) & ~15;
-    std::vector<float> cs, sn;
-    rope_tables(n_ctx, hd, theta, sections, cs, sn);
-    std::vector<float> last((size_t)n_slots * ld);
-    std::vector<int> pp, ps, dp(n_slots), ds(n_slots);
-    pp.reserve(npre); ps.reserve(npre);
-    {
-        size_t r0 = 0;
-        for (int s = 0; s < n_slots; ++s) {
-            for (int r = 0; r < lens[s] - 1; ++r) { pp.push_back(r); ps.push_back(s); }
-            memcpy(&last[(size_t)s * ld], qkv + (r0 + lens[s] - 1) * ld, (size_t)ld * 4);
-            dp[s] = lens[s] - 1; ds[s] = s;
-            r0 += lens[s];
-        }
-    }
-    DevBuf dpre, dlast, dout, dob, dqn, dkn, dcs, dsn, dkc, dvc, dpp, dps, ddp, dds;
-    const size_t cache = (size_t)n_slots * Hkv * n_ctx * hd * 2;
-    if (dpre.alloc((size_t)std::max(npre, 1) * ld * 4) || dlast.alloc(last.size() * 4) || dout.alloc((size_t)n_slots * nq * 4) ||
-        dob.alloc((size_t)r16 * nq * 2) || dqn.alloc(hd * 4) || dkn.alloc(hd * 4) || dcs.alloc(cs.size() * 4) || dsn.alloc(sn.size() * 4) ||
-        dkc.alloc(cache) || dvc.alloc(cache) || dpp.alloc((size_t)std::max(npre, 1) * 4) || dps.alloc((size_t)std::max(npre, 1) * 4) ||
-        ddp.alloc(n_slots * 4) || dds.alloc(n_slots * 4))
-        return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    {
-        size_t r0 = 0, o = 0;
-        for (int s = 0; s < n_slots; ++s) {
-            const size_t n = lens[s] - 1;
-            if (n) HK(hipMemcpy((float*)dpre.p + o * ld, qkv + r0 * ld, n * ld * 4, hipMemcpyHostToDevice));
-            o += n; r0 += lens[s];
-        }
-    }
-    HK(hipMemcpy(dqn.p, qnw, hd * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dkn.p, knw, hd * 4, hipMemcpyHostToDevice));
-    HK(hipMemcpy(dcs.p, cs.data(), cs.size() * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dsn.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
-    if (npre) { HK(hipMemcpy(dpp.p, pp.data(), npre * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dps.p, ps.data(), npre * 4, hipMemcpyHostToDevice)); }
-    HK(hipMemcpy(ddp.p, dp.data(), n_slots * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dds.p, ds.data(), n_slots * 4, hipMemcpyHostToDevice));
-    Q3QkPrep qp{}; qp.qkv = (float*)dpre.p; qp.ld = ld; qp.rows = npre; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = hd; qp.qnw = (const float*)dqn.p;
-    qp.knw = (const float*)dkn.p; qp.eps = eps; qp.cs = (const float*)dcs.p; qp.sn = (const float*)dsn.p; qp.kc = (uint16_t*)dkc.p;
-    qp.vc = (uint16_t*)dvc.p; qp.n_ctx = n_ctx; qp.row_pos = (const int*)dpp.p; qp.row_slot = (const int*)dps.p;
-    if (npre) q3_launch_qk_prep(qp, nullptr);
-    int old_dec = 0, old_pre = 0;
-    q3_attend_policy_get(&old_dec, &old_pre);
-    if (policy >= 0) q3_attend_policy(policy, old_pre);
-    for (int pass = 0; pass < (out_bf16 ? 2 : 1); ++pass) {
-        // both passes start from the same cache: the fused launch's append rewrites position len - 1 with the same bits
-        HK(hipMemcpy(dlast.p, last.data(), last.size() * 4, hipMemcpyHostToDevice));
-        Q3QkPrep dq = qp; dq.qkv = (float*)dlast.p; dq.rows = n_slots; dq.row_pos = (const int*)ddp.p; dq.row_slot = (const int*)dds.p;
-        Q3Attend at{}; at.qkv = (const float*)dlast.p; at.ld = ld; at.rows = n_slots; at.ldo = nq; at.Hq = Hq; at.Hkv = Hkv; at.hd = hd;
-        at.kc = (const uint16_t*)dkc.p; at.vc = (const uint16_t*)dvc.p; at.n_ctx = n_ctx; at.row_pos = dq.row_pos; at.row_slot = dq.row_slot;
-        at.fused = 1; at.prep = dq;
-        if (pass == 0) { at.out = (float*)dout.p; at.out_bf16 = 0; }
-        else { at.out = (float*)dob.p; at.out_bf16 = 1; }
-        q3_launch_attend(at, nullptr);
-        const hipError_t er = hipDeviceSynchronize();
-        if (er != hipSuccess) { q3_attend_policy(old_dec, old_pre); return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, std::string("attention decode hook: ") + hipGetErrorString(er)); }
-    }
-    q3_attend_policy(old_dec, old_pre);
-    HK(hipGetLastError());
-    HK(hipMemcpy(out_f32, dout.p, (size_t)n_slots * nq * 4, hipMemcpyDeviceToHost));
-    if (out_bf16) {
-        std::vector<uint16_t> t((size_t)r16 * nq);
-        HK(hipMemcpy(t.data(), dob.p, t.size() * 2, hipMemcpyDeviceToHost));
-        for (int r = 0; r < n_slots; ++r)
-            for (int c = 0; c < nq; ++c) out_bf16[(size_t)r * nq + c] = t[q3_atile_off(r, c, nq >> 5)];
-    }
-    return Q3TTS_OK;
-}
-
-extern "C" int q3tts_k_sample(int32_t device, const float* logits, int32_t n, int32_t ld, int32_t limit, float temperature, int32_t top_k,
-                              float top_p, const float* r, int32_t* out) {
-    if (!logits || !out || n <= 0 || limit <= 0 || limit > 4096 || limit > ld) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "sample hook: bad shape");
-    HK(hipSetDevice(device));
-    DevBuf dl, dr, dout;
-    if (dl.alloc((size_t)n * ld * 4) || dr.alloc((size_t)n * 4) || dout.alloc((size_t)n * 4)) return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    HK(hipMemcpy(dl.p, logits, (size_t)n * ld * 4, hipMemcpyHostToDevice));
-    if (r) HK(hipMemcpy(dr.p, r, (size_t)n * 4, hipMemcpyHostToDevice));
-    q3_launch_sample_rows((const float*)dl.p, n, ld, limit, temperature, top_k, top_p, r ? (const float*)dr.p : nullptr, (int*)dout.p, nullptr);
-    HK(hipDeviceSynchronize());
-    HK(hipMemcpy(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return Q3TTS_OK;
-}
-
-// natural row-major bf16 rows <-> the A-tiled layout of the device buffers (q3_kernels.h)
-static std::vector<uint16_t> atile_host(const uint16_t* src, int rows, int K) {
-    std::vector<uint16_t> out((((size_t)rows + 15) & ~(size_t)15) * K, 0);
-    for (int r = 0; r < rows; ++r) for (int k = 0; k < K; ++k) out[q3_atile_off(r, k, K >> 5)] = src[(size_t)r * K + k];
-    return out;
-}
-static void untile_host(const std::vector<uint16_t>& t, int rows, int K, uint16_t* dst) {
-    for (int r = 0; r < rows; ++r) for (int k = 0; k < K; ++k) dst[(size_t)r * K + k] = t[q3_atile_off(r, k, K >> 5)];
-}
-
-// the decoder's GEMM through its launcher (q3_bgemm.hip): xb bf16 bits [B][K]; w bf16 bits row-major [N][K] (epi 2: the F gate rows,
-// then the F up rows); ssp [B][ntiles] or NULL; y in/out for epi 1. Mirrors oracle/q3_oracle_bf16.c q3o_bgemm.
-extern "C" int q3tts_k_bgemm(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const uint16_t* w, int32_t N, const float* ssp, int32_t ntiles,
-                             int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb, float* ssp_out, uint64_t* keys,
-                             int32_t iters, float* mean_ms) {
-    if (!xb || !w || B <= 0 || K % 256 || K < 256 || N % 16 || epi < 0 || epi > 3) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: K % 256 == 0, N % 16 == 0");
-    if (epi == Q3_EPI_SWIGLU && (N % 64 || !yb)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: swiglu needs N % 64 == 0 and yb");
-    if (epi == Q3_EPI_RESID && nw_next && N % 32) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: norm outputs need N % 32 == 0");
-    if ((epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) && !y) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: y missing");
-    if (epi == Q3_EPI_ARGMAX && !keys) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: keys missing");
-    if (epi == Q3_EPI_RESID && nw_next && (!yb || !ssp_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: norm outputs missing");
-    HK(hipSetDevice(device));
-    const int F = N / 2;
-    const size_t B16 = ((size_t)B + 15) & ~(size_t)15;
-    DevBuf dx, dw, dwt, ds, dn, dy, dyb, dso, dk;
-    if (dx.alloc(B16 * K * 2) || dw.alloc((size_t)N * K * 2) || dwt.alloc((size_t)N * K * 2) || ds.alloc((size_t)B * (ntiles > 0 ? ntiles : 1) * 4) ||
-        dn.alloc((size_t)N * 4) || dy.alloc((size_t)B * N * 4) || dyb.alloc(B16 * N * 2) || dso.alloc((size_t)B * (N / 16) * 4) || dk.alloc((size_t)B * (N / 16) * 8))
-        return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    { const std::vector<uint16_t> xt = atile_host(xb, B, K); HK(hipMemcpy(dx.p, xt.data(), xt.size() * 2, hipMemcpyHostToDevice)); }
-    HK(hipMemcpy(dw.p, w, (size_t)N * K * 2, hipMemcpyHostToDevice));
-    if (ssp) HK(hipMemcpy(ds.p, ssp, (size_t)B * ntiles * 4, hipMemcpyHostToDevice));
-    if (nw_next) HK(hipMemcpy(dn.p, nw_next, (size_t)N * 4, hipMemcpyHostToDevice));
-    if (epi == Q3_EPI_RESID) HK(hipMemcpy(dy.p, y, (size_t)B * N * 4, hipMemcpyHostToDevice));
-    Q3Fill f{}; f.dst = (uint4*)dwt.p; f.N = N; f.K = K;
-    if (epi == Q3_EPI_SWIGLU) { f.mode = 1; f.src_a = (const uint16_t*)dw.p; f.src_b = (const uint16_t*)dw.p + (size_t)F * K; }
-    else { f.mode = 0; f.row0 = 0; f.rows = N; f.src_a = (const uint16_t*)dw.p; }
-    q3_launch_fill_tiled(f, nullptr);
-    Q3BGemm g{}; g.a = (const uint16_t*)dx.p; g.a_row0 = 0; g.B = B; g.w = (const uint4*)dwt.p; g.K = K; g.N = N;
-    g.ssp = ssp ? (const float*)ds.p : nullptr; g.ld_ssp = ntiles; g.ntiles = ntiles; g.d_norm = d_norm; g.eps = eps; g.epi = epi;
-    g.y = (float*)dy.p; g.ldy = N; g.yb = (uint16_t*)dyb.p;
-    g.nw_next = nw_next ? (const float*)dn.p : nullptr; g.ssp_out = (float*)dso.p; g.ld_ssp_out = N / 16;
-    g.keys = (unsigned long long*)dk.p; g.key_stride = N / 16;
-    if (q3_launch_bgemm(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm: shape");
-    HK(hipDeviceSynchronize());
-    if (epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) HK(hipMemcpy(y, dy.p, (size_t)B * N * 4, hipMemcpyDeviceToHost));
-    if (epi == Q3_EPI_SWIGLU) { std::vector<uint16_t> t(B16 * F); HK(hipMemcpy(t.data(), dyb.p, t.size() * 2, hipMemcpyDeviceToHost)); untile_host(t, B, F, yb); }
-    if (epi == Q3_EPI_RESID && nw_next) {
-        { std::vector<uint16_t> t(B16 * N); HK(hipMemcpy(t.data(), dyb.p, t.size() * 2, hipMemcpyDeviceToHost)); untile_host(t, B, N, yb); }
-        HK(hipMemcpy(ssp_out, dso.p, (size_t)B * (N / 16) * 4, hipMemcpyDeviceToHost));
-    }
-    if (epi == Q3_EPI_ARGMAX) {  // the kernel leaves one maximum per (row, 16-column tile); the consumer (here: the hook) takes the row maximum
-        std::vector<uint64_t> parts((size_t)B * (N / 16));
-        HK(hipMemcpy(parts.data(), dk.p, parts.size() * 8, hipMemcpyDeviceToHost));
-        for (int b = 0; b < B; ++b) { uint64_t m = 0; for (int t = 0; t < N / 16; ++t) m = std::max(m, parts[(size_t)b * (N / 16) + t]); keys[b] = m; }
-    }
-    if (iters > 0 && mean_ms) {
-        if (epi == Q3_EPI_RESID) { g.epi = Q3_EPI_STORE; g.nw_next = nullptr; }
-        hipEvent_t a, b; HK(hipEventCreate(&a)); HK(hipEventCreate(&b));
-        q3_launch_bgemm(g, nullptr);
-        HK(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; ++i) q3_launch_bgemm(g, nullptr);
-        HK(hipEventRecord(b, nullptr)); HK(hipEventSynchronize(b));
-        float ms = 0; hipEventElapsedTime(&ms, a, b); *mean_ms = ms / iters;
-        hipEventDestroy(a); hipEventDestroy(b);
-    }
-    return Q3TTS_OK;
-}
-
-// the same launch with ggml Q8_0 weights kept in block form: q int8 [N][K], d_f16 [N][K/32]. Mirrors oracle q3o_bgemm_q8.
-extern "C" int q3tts_k_bgemm_q8(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N, const float* ssp,
-                                int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb, float* ssp_out,
-                                uint64_t* keys, int32_t iters, float* mean_ms) {
-    if (!xb || !q || !d_f16 || B <= 0 || K % 512 || K < 512 || N % 16 || epi < 0 || epi > 3) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8 hook: K % 512 == 0, N % 16 == 0");
-    if (epi == Q3_EPI_SWIGLU && (N % 64 || !yb)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8 hook: swiglu needs N % 64 == 0 and yb");
-    if (epi == Q3_EPI_RESID && nw_next && (N % 32 || !yb || !ssp_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8 hook: norm outputs");
-    if ((epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) && !y) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8 hook: y missing");
-    if (epi == Q3_EPI_ARGMAX && !keys) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8 hook: keys missing");
-    HK(hipSetDevice(device));
-    const int F = N / 2, kb = K / 32;
-    const size_t B16 = ((size_t)B + 15) & ~(size_t)15;
-    std::vector<uint8_t> blocks((size_t)N * kb * 34);  // the rows as a GGUF file holds them: block_q8_0 = f16 d, 32 x int8
-    for (size_t n = 0; n < (size_t)N; ++n)
-        for (int b = 0; b < kb; ++b) {
-            uint8_t* blk = &blocks[(n * kb + b) * 34];
-            const uint16_t dd = d_f16[n * kb + b];
-            blk[0] = (uint8_t)(dd & 0xff); blk[1] = (uint8_t)(dd >> 8);
-            memcpy(blk + 2, q + n * K + (size_t)b * 32, 32);
-        }
-    DevBuf dx, dw, dwt, dsc, ds, dn, dy, dyb, dso, dk;
-    if (dx.alloc(B16 * K * 2) || dw.alloc(blocks.size()) || dwt.alloc((size_t)N * K) || dsc.alloc((size_t)N * kb * 2) || ds.alloc((size_t)B * (ntiles > 0 ? ntiles : 1) * 4) ||
-        dn.alloc((size_t)N * 4) || dy.alloc((size_t)B * N * 4) || dyb.alloc(B16 * N * 2) || dso.alloc((size_t)B * (N / 16) * 4) || dk.alloc((size_t)B * (N / 16) * 8))
-        return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    { const std::vector<uint16_t> xt = atile_host(xb, B, K); HK(hipMemcpy(dx.p, xt.data(), xt.size() * 2, hipMemcpyHostToDevice)); }
-    HK(hipMemcpy(dw.p, blocks.data(), blocks.size(), hipMemcpyHostToDevice));
-    if (ssp) HK(hipMemcpy(ds.p, ssp, (size_t)B * ntiles * 4, hipMemcpyHostToDevice));
-    if (nw_next) HK(hipMemcpy(dn.p, nw_next, (size_t)N * 4, hipMemcpyHostToDevice));
-    if (epi == Q3_EPI_RESID) HK(hipMemcpy(dy.p, y, (size_t)B * N * 4, hipMemcpyHostToDevice));
-    Q3Fill f{}; f.dst = (uint4*)dwt.p; f.dst_scale = (uint16_t*)dsc.p; f.N = N; f.K = K;
-    if (epi == Q3_EPI_SWIGLU) { f.mode = 1; f.src8_a = (const uint8_t*)dw.p; f.src8_b = (const uint8_t*)dw.p + (size_t)F * kb * 34; }
-    else { f.mode = 0; f.row0 = 0; f.rows = N; f.src8_a = (const uint8_t*)dw.p; }
-    q3_launch_fill_tiled_q8(f, nullptr);
-    Q3BGemm g{}; g.a = (const uint16_t*)dx.p; g.a_row0 = 0; g.B = B; g.w = (const uint4*)dwt.p; g.wscale = (const uint16_t*)dsc.p; g.K = K; g.N = N;
-    g.ssp = ssp ? (const float*)ds.p : nullptr; g.ld_ssp = ntiles; g.ntiles = ntiles; g.d_norm = d_norm; g.eps = eps; g.epi = epi;
-    g.y = (float*)dy.p; g.ldy = N; g.yb = (uint16_t*)dyb.p;
-    g.nw_next = nw_next ? (const float*)dn.p : nullptr; g.ssp_out = (float*)dso.p; g.ld_ssp_out = N / 16;
-    g.keys = (unsigned long long*)dk.p; g.key_stride = N / 16;
-    if (q3_launch_bgemm(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8: shape");
-    HK(hipDeviceSynchronize());
-    if (epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) HK(hipMemcpy(y, dy.p, (size_t)B * N * 4, hipMemcpyDeviceToHost));
-    if (epi == Q3_EPI_SWIGLU) { std::vector<uint16_t> t(B16 * F); HK(hipMemcpy(t.data(), dyb.p, t.size() * 2, hipMemcpyDeviceToHost)); untile_host(t, B, F, yb); }
-    if (epi == Q3_EPI_RESID && nw_next) {
-        { std::vector<uint16_t> t(B16 * N); HK(hipMemcpy(t.data(), dyb.p, t.size() * 2, hipMemcpyDeviceToHost)); untile_host(t, B, N, yb); }
-        HK(hipMemcpy(ssp_out, dso.p, (size_t)B * (N / 16) * 4, hipMemcpyDeviceToHost));
-    }
-    if (epi == Q3_EPI_ARGMAX) {
-        std::vector<uint64_t> parts((size_t)B * (N / 16));
-        HK(hipMemcpy(parts.data(), dk.p, parts.size() * 8, hipMemcpyDeviceToHost));
-        for (int b = 0; b < B; ++b) { uint64_t m = 0; for (int t = 0; t < N / 16; ++t) m = std::max(m, parts[(size_t)b * (N / 16) + t]); keys[b] = m; }
-    }
-    if (iters > 0 && mean_ms) {
-        if (epi == Q3_EPI_RESID) { g.epi = Q3_EPI_STORE; g.nw_next = nullptr; }
-        hipEvent_t a, b; HK(hipEventCreate(&a)); HK(hipEventCreate(&b));
-        q3_launch_bgemm(g, nullptr);
-        HK(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; ++i) q3_launch_bgemm(g, nullptr);
-        HK(hipEventRecord(b, nullptr)); HK(hipEventSynchronize(b));
-        float ms = 0; hipEventElapsedTime(&ms, a, b); *mean_ms = ms / iters;
-        hipEventDestroy(a); hipEventDestroy(b);
-    }
-    return Q3TTS_OK;
-}
-
-// H6 through the projection kernel: y[rows][n_out] = bias + sum x * w (reference order); nw != NULL: the rows' norm inputs too
-// The vocoder's extras of the decoder GEMM (bias, GELU -> bf16, LayerScale column scale, per-slot row segments, a bf16 copy of the
-// residual result) through one hook: epi 0 (store) / 1 (residual) / 4 (GELU). y0 / y are dense [B][N]; with seg_rows > 0 the kernel
-// works on a buffer of B / seg_rows segments, each preceded by gap_rows sentinel rows that must come back untouched.
-// W8A8 (q3_bgemm8.hip): activations and weights as ggml Q8_0 blocks in natural order in / out; the hook tiles them for the device
-extern "C" int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const float* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N,
-                                  const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, float* yd,
-                                  float* ssp_out, int32_t iters, float* mean_ms) {
-    if (!aq || !ad || !q || !d_f16 || B <= 0 || K % 512 || K < 512 || N % 32 || epi < 0 || epi > 2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8 hook: K % 512 == 0, N % 32 == 0, epilogue 0..2");
-    if (epi == Q3_EPI_SWIGLU && (N % 128 || !yq || !yd)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8 hook: swiglu needs N % 128 == 0, yq, yd");
-    if (epi == Q3_EPI_RESID && (N % 64 || !nw_next || !yq || !yd || !ssp_out || !y)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8 hook: residual needs N % 64 == 0, nw_next, y, yq, yd, ssp_out");
-    if (epi == Q3_EPI_STORE && !y) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8 hook: y missing");
-    HK(hipSetDevice(device));
-    const int F = N / 2, kb = K / 32, Nout = epi == Q3_EPI_SWIGLU ? F : N;
-    const size_t B16 = ((size_t)B + 15) & ~(size_t)15; const int rt16 = (int)(B16 / 16);
-    std::vector<uint8_t> blocks((size_t)N * kb * 34);
-    for (size_t n = 0; n < (size_t)N; ++n)
-        for (int b = 0; b < kb; ++b) {
-            uint8_t* blk = &blocks[(n * kb + b) * 34];
-            const uint16_t dd = d_f16[n * kb + b];
-            blk[0] = (uint8_t)(dd & 0xff); blk[1] = (uint8_t)(dd >> 8);
-            memcpy(blk + 2, q + n * K + (size_t)b * 32, 32);
-        }
-    std::vector<int8_t> at(B16 * K, 0); std::vector<float> ast((size_t)kb * B16, 0.0f);
-    for (int r = 0; r < B; ++r) {
-        for (int k = 0; k < K; ++k) at[q3_q8_off(r, k, K >> 6)] = aq[(size_t)r * K + k];
-        for (int b = 0; b < kb; ++b) ast[q3_q8_scale_idx(r, b, rt16)] = ad[(size_t)r * kb + b];
-    }
-    DevBuf dx, dxs, dw, dwt, dsc, ds, dn, dy, dyq, dys, dso;
-    if (dx.alloc(at.size()) || dxs.alloc(ast.size() * 4) || dw.alloc(blocks.size()) || dwt.alloc((size_t)N * K) || dsc.alloc((size_t)N * kb * 2) ||
-        ds.alloc((size_t)B * (ntiles > 0 ? ntiles : 1) * 4) || dn.alloc((size_t)N * 4) || dy.alloc((size_t)B * N * 4) || dyq.alloc(B16 * Nout) ||
-        dys.alloc((size_t)(Nout / 32 + 2) * B16 * 4) || dso.alloc((size_t)B * (N / 16) * 4))
-        return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    HK(hipMemcpy(dx.p, at.data(), at.size(), hipMemcpyHostToDevice)); HK(hipMemcpy(dxs.p, ast.data(), ast.size() * 4, hipMemcpyHostToDevice));
-    HK(hipMemcpy(dw.p, blocks.data(), blocks.size(), hipMemcpyHostToDevice));
-    if (ssp) HK(hipMemcpy(ds.p, ssp, (size_t)B * ntiles * 4, hipMemcpyHostToDevice));
-    if (nw_next) HK(hipMemcpy(dn.p, nw_next, (size_t)N * 4, hipMemcpyHostToDevice));
-    if (epi == Q3_EPI_RESID) HK(hipMemcpy(dy.p, y, (size_t)B * N * 4, hipMemcpyHostToDevice));
-    Q3Fill f{}; f.dst = (uint4*)dwt.p; f.dst_scale = (uint16_t*)dsc.p; f.N = N; f.K = K;
-    if (epi == Q3_EPI_SWIGLU) { f.mode = 1; f.src8_a = (const uint8_t*)dw.p; f.src8_b = (const uint8_t*)dw.p + (size_t)F * kb * 34; }
-    else { f.mode = 0; f.row0 = 0; f.rows = N; f.src8_a = (const uint8_t*)dw.p; }
-    q3_launch_fill_tiled_q8(f, nullptr);
-    Q3BGemm g{}; g.a = (const uint16_t*)dx.p; g.ascale = (const float*)dxs.p; g.a_rt16 = rt16; g.a_row0 = 0; g.B = B;
-    g.w = (const uint4*)dwt.p; g.wscale = (const uint16_t*)dsc.p; g.K = K; g.N = N;
-    g.ssp = ssp ? (const float*)ds.p : nullptr; g.ld_ssp = ntiles; g.ntiles = ntiles; g.d_norm = d_norm; g.eps = eps; g.epi = epi;
-    g.y = (float*)dy.p; g.ldy = N; g.yb = (uint16_t*)dyq.p; g.yscale = (float*)dys.p; g.y_rt16 = rt16;
-    g.nw_next = nw_next ? (const float*)dn.p : nullptr; g.ssp_out = (float*)dso.p; g.ld_ssp_out = N / 16;
-    if (q3_launch_bgemm8(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8: shape");
-    HK(hipDeviceSynchronize());
-    if (epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) HK(hipMemcpy(y, dy.p, (size_t)B * N * 4, hipMemcpyDeviceToHost));
-    if (epi != Q3_EPI_STORE) {
-        std::vector<int8_t> qt(B16 * Nout); std::vector<float> st((size_t)(Nout / 32) * B16);
-        HK(hipMemcpy(qt.data(), dyq.p, qt.size(), hipMemcpyDeviceToHost)); HK(hipMemcpy(st.data(), dys.p, st.size() * 4, hipMemcpyDeviceToHost));
-        for (int r = 0; r < B; ++r) {
-            for (int k = 0; k < Nout; ++k) yq[(size_t)r * Nout + k] = qt[q3_q8_off(r, k, Nout >> 6)];
-            for (int b = 0; b < Nout / 32; ++b) yd[(size_t)r * (Nout / 32) + b] = st[q3_q8_scale_idx(r, b, rt16)];
-        }
-        if (epi == Q3_EPI_RESID) HK(hipMemcpy(ssp_out, dso.p, (size_t)B * (N / 16) * 4, hipMemcpyDeviceToHost));
-    }
-    if (iters > 0 && mean_ms) {
-        if (epi == Q3_EPI_RESID) g.epi = Q3_EPI_STORE;
-        hipEvent_t a, b; HK(hipEventCreate(&a)); HK(hipEventCreate(&b));
-        q3_launch_bgemm8(g, nullptr);
-        HK(hipEventRecord(a, nullptr));
-        for (int i = 0; i < iters; ++i) q3_launch_bgemm8(g, nullptr);
-        HK(hipEventRecord(b, nullptr)); HK(hipEventSynchronize(b));
-        float ms = 0; hipEventElapsedTime(&ms, a, b); *mean_ms = ms / iters;
-        hipEventDestroy(a); hipEventDestroy(b);
-    }
-    return Q3TTS_OK;
-}
-
-extern "C" int q3tts_k_bgemm_voc(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const uint16_t* w, int32_t N, int32_t epi, const float* bias,
-                                 int32_t bias_n, const float* col_scale, int32_t seg_rows, int32_t gap_rows, float* y, uint16_t* yb, int32_t want_yb) {
-    if (!xb || !w || B <= 0 || K % 256 || K < 256 || N % 32 || (epi != Q3_EPI_STORE && epi != Q3_EPI_RESID && epi != Q3_EPI_GELU))
-        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_voc hook: K % 256 == 0, N % 32 == 0, epilogue 0 / 1 / 4");
-    if ((epi != Q3_EPI_GELU && !y) || ((epi == Q3_EPI_GELU || want_yb) && !yb)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_voc hook: output missing");
-    if (seg_rows < 0 || gap_rows < 0 || (seg_rows > 0 && B % seg_rows) || (bias && bias_n < 1)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_voc hook: segments / bias");
-    HK(hipSetDevice(device));
-    const size_t B16 = ((size_t)B + 15) & ~(size_t)15;
-    const int T = seg_rows > 0 ? seg_rows : B, S = B / T, P = T + (seg_rows > 0 ? gap_rows : 0);
-    DevBuf dx, dw, dwt, db, dc, dy, dyb;
-    if (dx.alloc(B16 * K * 2) || dw.alloc((size_t)N * K * 2) || dwt.alloc((size_t)N * K * 2) || db.alloc((size_t)(bias ? bias_n : 1) * 4) || dc.alloc((size_t)N * 4) ||
-        dy.alloc((size_t)S * P * N * 4) || dyb.alloc(B16 * N * 2))
-        return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    { const std::vector<uint16_t> xt = atile_host(xb, B, K); HK(hipMemcpy(dx.p, xt.data(), xt.size() * 2, hipMemcpyHostToDevice)); }
-    HK(hipMemcpy(dw.p, w, (size_t)N * K * 2, hipMemcpyHostToDevice));
-    if (bias) HK(hipMemcpy(db.p, bias, (size_t)bias_n * 4, hipMemcpyHostToDevice));
-    if (col_scale) HK(hipMemcpy(dc.p, col_scale, (size_t)N * 4, hipMemcpyHostToDevice));
-    std::vector<float> seg((size_t)S * P * N, -12345.5f);  // sentinel in the gap rows
-    if (epi != Q3_EPI_GELU)
-        for (int sidx = 0; sidx < S; ++sidx)
-            for (int t = 0; t < T; ++t) memcpy(&seg[((size_t)sidx * P + (P - T) + t) * N], y + ((size_t)sidx * T + t) * N, (size_t)N * 4);
-    HK(hipMemcpy(dy.p, seg.data(), seg.size() * 4, hipMemcpyHostToDevice));
-    Q3Fill f{}; f.dst = (uint4*)dwt.p; f.N = N; f.K = K; f.mode = 0; f.row0 = 0; f.rows = N; f.src_a = (const uint16_t*)dw.p;
-    q3_launch_fill_tiled(f, nullptr);
-    Q3BGemm g{}; g.a = (const uint16_t*)dx.p; g.B = B; g.w = (const uint4*)dwt.p; g.K = K; g.N = N; g.epi = epi;
-    g.y = (float*)dy.p + (size_t)(P - T) * N; g.ldy = N;
-    if (seg_rows > 0) { g.seg_rows = T; g.seg_stride = (size_t)P * N; }
-    g.bias = bias ? (const float*)db.p : nullptr; g.bias_n = bias_n; g.col_scale = col_scale ? (const float*)dc.p : nullptr;
-    if (epi == Q3_EPI_GELU || want_yb) g.yb = (uint16_t*)dyb.p;
-    if (q3_launch_bgemm(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_voc: shape");
-    HK(hipDeviceSynchronize());
-    if (epi != Q3_EPI_GELU) {
-        HK(hipMemcpy(seg.data(), dy.p, seg.size() * 4, hipMemcpyDeviceToHost));
-        for (int sidx = 0; sidx < S; ++sidx) {
-            for (int t = 0; t < P - T; ++t)
-                for (int c = 0; c < N; ++c)
-                    if (seg[((size_t)sidx * P + t) * N + c] != -12345.5f) return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, "bgemm_voc: a gap row was written");
-            for (int t = 0; t < T; ++t) memcpy(y + ((size_t)sidx * T + t) * N, &seg[((size_t)sidx * P + (P - T) + t) * N], (size_t)N * 4);
-        }
-    }
-    if (epi == Q3_EPI_GELU || want_yb) { std::vector<uint16_t> t(B16 * N); HK(hipMemcpy(t.data(), dyb.p, t.size() * 2, hipMemcpyDeviceToHost)); untile_host(t, B, N, yb); }
-    return Q3TTS_OK;
-}
-
-extern "C" int q3tts_k_project(int32_t device, const float* x, int32_t rows, int32_t n_in, const float* w, const float* bias, int32_t n_out, const float* nw,
-                               float* y, uint16_t* xb, float* ssp) {
-    if (!x || !w || !bias || !y || rows <= 0 || n_in % 64 || n_out % 16 || (nw && (!xb || !ssp))) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "project hook: n_in % 64 == 0, n_out % 16 == 0");
-    HK(hipSetDevice(device));
-    DevBuf dx, dw, db, dn, dy, dxb, dss;
-    if (dx.alloc((size_t)rows * n_in * 4) || dw.alloc((size_t)n_out * n_in * 4) || db.alloc((size_t)n_out * 4) || dn.alloc((size_t)n_out * 4) ||
-        dy.alloc((size_t)rows * n_out * 4) || dxb.alloc((((size_t)rows + 15) & ~(size_t)15) * n_out * 2) || dss.alloc((size_t)rows * (n_out / 16) * 4))
-        return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    HK(hipMemcpy(dx.p, x, (size_t)rows * n_in * 4, hipMemcpyHostToDevice));
-    HK(hipMemcpy(dw.p, w, (size_t)n_out * n_in * 4, hipMemcpyHostToDevice));
-    HK(hipMemcpy(db.p, bias, (size_t)n_out * 4, hipMemcpyHostToDevice));
-    if (nw) HK(hipMemcpy(dn.p, nw, (size_t)n_out * 4, hipMemcpyHostToDevice));
-    Q3Project pj{}; pj.x = (const float*)dx.p; pj.ldx = n_in; pj.rows = rows; pj.w = (const float*)dw.p; pj.bias = (const float*)db.p; pj.n_in = n_in; pj.n_out = n_out;
-    pj.y = (float*)dy.p; pj.ldy = n_out; pj.nw = nw ? (const float*)dn.p : nullptr; pj.xb = (uint16_t*)dxb.p; pj.ssp = (float*)dss.p; pj.ld_ssp = n_out / 16;
-    if (q3_launch_project(pj, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "project: shape");
-    HK(hipDeviceSynchronize());
-    HK(hipMemcpy(y, dy.p, (size_t)rows * n_out * 4, hipMemcpyDeviceToHost));
-    if (nw) {
-        if (n_out % 32) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "project hook: norm outputs need n_out % 32 == 0");
-        std::vector<uint16_t> t((((size_t)rows + 15) & ~(size_t)15) * n_out);
-        HK(hipMemcpy(t.data(), dxb.p, t.size() * 2, hipMemcpyDeviceToHost)); untile_host(t, rows, n_out, xb);
-        HK(hipMemcpy(ssp, dss.p, (size_t)rows * (n_out / 16) * 4, hipMemcpyDeviceToHost));
-    }
-    return Q3TTS_OK;
-}
-
-// producer side of the split RMSNorm for plain f32 rows (d % 256 == 0)
-extern "C" int q3tts_k_norm_inputs(int32_t device, const float* x, int32_t rows, int32_t d, const float* nw, uint16_t* xb, float* ssp) {
-    if (!x || !nw || !xb || !ssp || rows <= 0 || d % 256) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "norm-inputs hook: d % 256 == 0");
-    HK(hipSetDevice(device));
-    DevBuf dx, dn, dxb, dss;
-    const size_t r16 = ((size_t)rows + 15) & ~(size_t)15;
-    if (dx.alloc((size_t)rows * d * 4) || dn.alloc((size_t)d * 4) || dxb.alloc(r16 * d * 2) || dss.alloc((size_t)rows * (d / 16) * 4)) return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    HK(hipMemcpy(dx.p, x, (size_t)rows * d * 4, hipMemcpyHostToDevice));
-    HK(hipMemcpy(dn.p, nw, (size_t)d * 4, hipMemcpyHostToDevice));
-    q3_launch_norm_inputs((const float*)dx.p, d, rows, d, (const float*)dn.p, (uint16_t*)dxb.p, 0, (float*)dss.p, d / 16, nullptr);
-    HK(hipDeviceSynchronize());
-    { std::vector<uint16_t> t(r16 * d); HK(hipMemcpy(t.data(), dxb.p, t.size() * 2, hipMemcpyDeviceToHost)); untile_host(t, rows, d, xb); }
-    HK(hipMemcpy(ssp, dss.p, (size_t)rows * (d / 16) * 4, hipMemcpyDeviceToHost));
-    return Q3TTS_OK;
-}
-
-// one v_mfma_f32_16x16x32_bf16 chain per case (test hook: pins the instruction's accumulation arithmetic against the
-// oracle's integer restatement, oracle/q3_oracle.c q3o_mfma_bf16_dot32)
-typedef float q3_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 q3_bf16x8 __attribute__((ext_vector_type(8)));
-__global__ void k_mfma_bf16_cases(const uint16_t* A, const uint16_t* B, const float* C, float* D, int chain) {
-    const int l = threadIdx.x, cs = blockIdx.x;
-    const uint16_t* a = A + (size_t)cs * chain * 512; const uint16_t* b = B + (size_t)cs * chain * 512;
-    q3_f32x4 acc;
-    for (int j = 0; j < 4; ++j) acc[j] = C[(size_t)cs * 256 + (4 * (l >> 4) + j) * 16 + (l & 15)];
-    for (int st = 0; st < chain; ++st) {
-        union { q3_bf16x8 v; uint16_t u[8]; } af, bf;
-        for (int j = 0; j < 8; ++j) {  // lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15]
-            af.u[j] = a[(size_t)st * 512 + (l & 15) * 32 + 8 * (l >> 4) + j];
-            bf.u[j] = b[(size_t)st * 512 + (8 * (l >> 4) + j) * 16 + (l & 15)];
-        }
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.v, bf.v, acc, 0, 0, 0);
-    }
-    for (int j = 0; j < 4; ++j) D[(size_t)cs * 256 + (4 * (l >> 4) + j) * 16 + (l & 15)] = acc[j];
-}
-extern "C" int q3tts_k_mfma_bf16(int32_t device, const uint16_t* a, const uint16_t* b, const float* c, float* d, int32_t n_cases, int32_t chain) {
-    if (!a || !b || !c || !d || n_cases <= 0 || chain <= 0) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "mfma hook: bad shape");
-    HK(hipSetDevice(device));
-    const size_t nab = (size_t)n_cases * chain * 512 * 2, ncd = (size_t)n_cases * 256 * 4;
-    DevBuf da, db, dc, dd;
-    if (da.alloc(nab) || db.alloc(nab) || dc.alloc(ncd) || dd.alloc(ncd)) return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    HK(hipMemcpy(da.p, a, nab, hipMemcpyHostToDevice)); HK(hipMemcpy(db.p, b, nab, hipMemcpyHostToDevice)); HK(hipMemcpy(dc.p, c, ncd, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_mfma_bf16_cases, dim3(n_cases), dim3(64), 0, nullptr, (const uint16_t*)da.p, (const uint16_t*)db.p, (const float*)dc.p, (float*)dd.p, chain);
-    HK(hipDeviceSynchronize());
-    HK(hipMemcpy(d, dd.p, ncd, hipMemcpyDeviceToHost));
-    return Q3TTS_OK;
-}
-
-static int talker_prefill(q3tts_engine* e, const q3tts_prefix* prefix, const float* embd, int32_t n_tok, float* hidden_out, float* logits_out) {
-    Q3_NOT_IN_SESSION(e);
-    if (!e || !embd || n_tok <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
-    Q3_HIP(e, hipSetDevice(e->cfg.device));
-    q3tts_request r{}; r.prompt_embd = embd; r.n_tok = n_tok; r.use_engine_sampler = 0; r.temperature = 0; r.max_steps = 1; r.prefix = prefix;
-    TRY(plan_rows(e, std::vector<int>{0}));
-    TRY(admit(e, 0, &r));
-    const q3tts_model_config& m = e->cfg.model;
-    hipStream_t s = e->stream;
-    if (hidden_out) {
-        q3_launch_rmsnorm_rows(e->lanes[0].xT, m.t_d_model, e->T.out_norm, m.rms_eps, m.t_d_model, 1, e->lanes[0].logits_tmp, m.t_d_model, s);
-        Q3_HIP(e, hipMemcpyAsync(hidden_out, e->lanes[0].logits_tmp, (size_t)m.t_d_model * 4, hipMemcpyDeviceToHost, s));
-    }
-    if (logits_out) Q3_HIP(e, hipMemcpyAsync(logits_out, e->lanes[0].logits, (size_t)m.t_vocab * 4, hipMemcpyDeviceToHost, s));
-    Q3Slot* stage = e->slots_host + e->B; memset(stage, 0, sizeof(Q3Slot));
-    Q3_HIP(e, hipMemcpyAsync(e->slots, stage, sizeof(Q3Slot), hipMemcpyHostToDevice, s));  // retire the slot again
-    Q3_HIP(e, hipStreamSynchronize(s));
-    return Q3TTS_OK;
-}
-extern "C" int q3tts_k_talker_prefill(q3tts_engine* e, const float* embd, int32_t n_tok, float* hidden_out, float* logits_out) {
-    return talker_prefill(e, nullptr, embd, n_tok, hidden_out, logits_out);
-}
-extern "C" int q3tts_k_talker_prefill_prefix(q3tts_engine* e, const q3tts_prefix* prefix, const float* embd, int32_t n_tok, float* hidden_out,
-                                             float* logits_out) {
-    if (!prefix) return q3_set_err(e, Q3TTS_ERR_INVALID, "null prefix");
-    return talker_prefill(e, prefix, embd, n_tok, hidden_out, logits_out);
-}
-
-extern "C" int q3tts_k_probe(q3tts_engine* e, int32_t enable) {
-    Q3_NOT_IN_SESSION(e);
-    if (!e) return Q3TTS_ERR_INVALID;
-    Q3_HIP(e, hipSetDevice(e->cfg.device));
-    if (enable && e->probe_ev.empty()) {
-        e->probe_ev.resize(10, nullptr);  // 4 frames x 2 + one empty bracket per chunk (event overhead calibration)
-        for (auto& ev : e->probe_ev) Q3_HIP(e, hipEventCreate(&ev));
-    }
-    const int model = enable & 15, kind = enable >> 4;
-    if (model > 2 || kind < 0 || kind > 4) return q3_set_err(e, Q3TTS_ERR_INVALID, "probe: model 0..2, kind 0..4");
-    e->probe = model; e->probe_kind = kind;
-    return Q3TTS_OK;
-}
-
-// The allocator's contract (q3_dev_alloc_zeroed): the zero fill has completed when the pointer is handed out. The hook allocates
-// `bytes` through it, uploads a pattern into the first and last 4 KiB on the NULL stream at once (the stream an unsuspecting call
-// site would use), and counts the bytes that do not read back as written / as zero. An asynchronous fill on e->stream — the state
-// of rounds 1 and 2 — loses this race on large buffers.
-extern "C" int q3tts_k_alloc_upload(q3tts_engine* e, int64_t bytes, int64_t* mismatches) {
-    Q3_NOT_IN_SESSION(e);
-    if (!e || !mismatches || bytes < 16384) return q3_set_err(e, Q3TTS_ERR_INVALID, "alloc hook: bytes >= 16384");
-    Q3_HIP(e, hipSetDevice(e->cfg.device));
-    void* q = nullptr;
-    TRY(q3_dev_alloc_zeroed(e, &q, (size_t)bytes));
-    std::vector<uint8_t> pat(4096), back(12288);
-    for (int i = 0; i < 4096; ++i) pat[i] = (uint8_t)(1 + i % 251);
-    hipError_t er = hipMemcpyAsync(q, pat.data(), 4096, hipMemcpyHostToDevice, nullptr);
-    if (er == hipSuccess) er = hipMemcpyAsync((char*)q + bytes - 4096, pat.data(), 4096, hipMemcpyHostToDevice, nullptr);
-    if (er == hipSuccess) er = hipDeviceSynchronize();
-    if (er == hipSuccess) er = hipMemcpy(back.data(), q, 8192, hipMemcpyDeviceToHost);
-    if (er == hipSuccess) er = hipMemcpy(back.data() + 8192, (char*)q + bytes - 4096, 4096, hipMemcpyDeviceToHost);
-    hipFree(q);
-    if (er != hipSuccess) return q3_set_err(e, Q3TTS_ERR_DEVICE, hipGetErrorString(er));
-    int64_t bad = 0;
-    for (int i = 0; i < 4096; ++i) bad += (back[i] != pat[i]) + (back[4096 + i] != 0) + (back[8192 + i] != pat[i]);
-    *mismatches = bad;
-    return Q3TTS_OK;
-}
-
-extern "C" int q3tts_k_bgemm_policy(int32_t big) {
-    if (big < -1 || big > 1) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm policy: -1, 0 or 1");
-    q3_bgemm_big_policy(big);
-    return Q3TTS_OK;
-}
-
-extern "C" int q3tts_k_attend_policy(int32_t decode, int32_t prefill) {
-    if (decode < 0 || decode > 1 || prefill < 0 || prefill > 2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attend policy: decode 0..1, prefill 0..2");
-    q3_attend_policy(decode, prefill);
-    return Q3TTS_OK;
-}
-
-extern "C" int q3tts_k_bgemm_pick(int32_t B, int32_t K, int32_t N, int32_t epilogue, int32_t w_once, int32_t q8, int32_t* out5) {
-    if (!out5 || B < 1 || K < 256 || K % 256 || N % 16) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm pick: bad shape");
-    Q3BGemm g{}; g.B = B; g.K = K; g.N = N; g.epi = epilogue; g.w_once = w_once;
-    g.a = (const uint16_t*)16; g.w = (const uint4*)16; g.wscale = q8 ? (const uint16_t*)16 : nullptr;  // (never dereferenced: nothing is launched)
-    if (epilogue == Q3_EPI_SWIGLU || epilogue == Q3_EPI_GELU) g.yb = (uint16_t*)16;
-    if (epilogue == Q3_EPI_RESID) { g.yb = (uint16_t*)16; g.nw_next = (const float*)16; }
-    int rt, nt, d, ntw, big;
-    q3_bgemm_pick(g, &rt, &nt, &d, &ntw, &big);
-    out5[0] = rt; out5[1] = nt; out5[2] = d; out5[3] = ntw; out5[4] = big;
-    return Q3TTS_OK;
-}
-
-extern "C" int q3tts_k_pcm_pack(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* ent_row, const int32_t* ent_first,
-                                const int32_t* ent_count, const int64_t* ent_dst, int32_t n_ent, int32_t format, void* out, int64_t out_n) {
-    if (!src || !out || rows <= 0 || stride <= 0 || stride > (1 << 28) || n_ent < 0 || n_ent > Q3_PCM_MAX_ENT || (format != 0 && format != 1) || out_n < 0 ||
-        (n_ent > 0 && (!ent_row || !ent_first || !ent_count || !ent_dst)))
-        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm pack hook: bad arguments");
-    Q3PcmPack pk{};
-    int mx = 0;
-    for (int j = 0; j < n_ent; ++j) {
-        const long long r = ent_row[j], f = ent_first[j], c = ent_count[j], d = ent_dst[j];
-        if (r < 0 || r >= rows || f < 0 || c < 0 || f + c > stride || d < 0 || d + c > out_n)
-            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm pack hook: a window lies outside src or out");
-        pk.e[j] = Q3PcmEnt{(int32_t)r, (int32_t)f, (int32_t)c, 0, d};
-        mx = std::max(mx, (int)c);
-    }
-    const size_t es = format ? 2 : 4;
-    HK(hipSetDevice(device));
-    DevBuf s, o;
-    if (s.alloc(sizeof(float) * (size_t)rows * stride) || o.alloc(es * (size_t)std::max<int64_t>(out_n, 1))) return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
-    HK(hipMemcpy(s.p, src, sizeof(float) * (size_t)rows * stride, hipMemcpyHostToDevice));
-    if (out_n > 0) HK(hipMemcpy(o.p, out, es * (size_t)out_n, hipMemcpyHostToDevice));  // samples outside every window keep their values
-    q3_launch_pcm_pack((const float*)s.p, (size_t)stride, pk, n_ent, mx, format, o.p, nullptr);
-    HK(hipGetLastError());
-    HK(hipDeviceSynchronize());
-    if (out_n > 0) HK(hipMemcpy(out, o.p, es * (size_t)out_n, hipMemcpyDeviceToHost));
-    return Q3TTS_OK;
-}
-
-extern "C" int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out) {
-    if (!out || n < 0) return Q3TTS_ERR_INVALID;
-    q3_stdrng_f32(seed, n, out);
-    return Q3TTS_OK;
 }

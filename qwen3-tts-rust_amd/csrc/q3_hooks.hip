@@ -1,0 +1,563 @@
+// q3_hooks.hip — the kernel-level test hooks q3tts_k_* of include/q3tts.h: each uploads its arguments, launches one kernel (or one engine
+// step) through the launcher the engine uses, and reads the result back. No engine code: the tests and the benchmarks of single kernels
+// call these. (The hooks of the vocoder, the clone encoders and the GGUF reader are in those files, beside the state they use.)
+#include "q3_engine.h"
+
+#include <cstdio>
+#include <cstring>
+
+#define TRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
+#define HK(call) do { hipError_t er__ = (call); if (er__ != hipSuccess) return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(er__)); } while (0)
+
+// A device buffer of a hook, freed on every return path. put: `bytes` (+ 64 of slack) of zero-filled memory, then the host's `bytes` when
+// host != NULL; get: the first `bytes` back. Synchronous copies on the NULL stream. Both return a Q3TTS_ status (error text set).
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) hipFree(p); }
+    template <class T> operator T*() const { return (T*)p; }
+    int put(const void* host, size_t bytes) {
+        if (hipMalloc(&p, bytes + 64) != hipSuccess || hipMemset(p, 0, bytes + 64) != hipSuccess) return q3_set_err(nullptr, Q3TTS_ERR_OOM, "hipMalloc");
+        if (host) HK(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+        return Q3TTS_OK;
+    }
+    int alloc(size_t bytes) { return put(nullptr, bytes); }
+    int get(void* host, size_t bytes) const { HK(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost)); return Q3TTS_OK; }
+};
+
+// mean time of a launch: one untimed warm-up, then `iters` launches between two events on the NULL stream (nothing when iters <= 0 or !mean_ms)
+template <class F>
+static int time_launches(int iters, F launch, float* mean_ms) {
+    if (iters <= 0 || !mean_ms) return Q3TTS_OK;
+    hipEvent_t a, b; HK(hipEventCreate(&a)); HK(hipEventCreate(&b));
+    launch();
+    HK(hipEventRecord(a, nullptr));
+    for (int i = 0; i < iters; ++i) launch();
+    HK(hipEventRecord(b, nullptr)); HK(hipEventSynchronize(b));
+    float ms = 0; hipEventElapsedTime(&ms, a, b); *mean_ms = ms / iters;
+    hipEventDestroy(a); hipEventDestroy(b);
+    return Q3TTS_OK;
+}
+
+static size_t pad16(size_t rows) { return (rows + 15) & ~(size_t)15; }
+// natural row-major bf16 rows <-> the A-tiled layout of the device buffers (q3_kernels.h)
+static std::vector<uint16_t> atile_host(const uint16_t* src, int rows, int K) {
+    std::vector<uint16_t> out(pad16(rows) * K, 0);
+    for (int r = 0; r < rows; ++r) for (int k = 0; k < K; ++k) out[q3_atile_off(r, k, K >> 5)] = src[(size_t)r * K + k];
+    return out;
+}
+static int untile_host(const DevBuf& d, int rows, int K, uint16_t* dst) {  // (reads the device buffer back first)
+    std::vector<uint16_t> t(pad16(rows) * K);
+    TRY(d.get(t.data(), t.size() * 2));
+    for (int r = 0; r < rows; ++r) for (int k = 0; k < K; ++k) dst[(size_t)r * K + k] = t[q3_atile_off(r, k, K >> 5)];
+    return Q3TTS_OK;
+}
+// q int8 [N][K] + d_f16 [N][K/32] -> the rows as a GGUF file holds them: block_q8_0 = f16 d, 32 x int8
+static std::vector<uint8_t> pack_q8_0(const int8_t* q, const uint16_t* d_f16, int N, int K) {
+    const int kb = K / 32;
+    std::vector<uint8_t> blocks((size_t)N * kb * 34);
+    for (size_t n = 0; n < (size_t)N; ++n)
+        for (int b = 0; b < kb; ++b) {
+            uint8_t* blk = &blocks[(n * kb + b) * 34];
+            const uint16_t dd = d_f16[n * kb + b];
+            blk[0] = (uint8_t)(dd & 0xff); blk[1] = (uint8_t)(dd >> 8);
+            memcpy(blk + 2, q + n * K + (size_t)b * 32, 32);
+        }
+    return blocks;
+}
+// Tile a row-major [N][K] weight on the device for the GEMM kernels. sc == NULL: src holds bf16 bits; else src holds block_q8_0 rows and
+// sc receives the f16 block scales. swiglu: src is the N/2 gate rows, then the N/2 up rows (interleaved in dst).
+static void tile_weight(const DevBuf& src, const DevBuf& dst, const DevBuf* sc, int N, int K, bool swiglu) {
+    Q3Fill f{}; f.dst = dst; f.N = N; f.K = K; f.mode = swiglu ? 1 : 0;
+    if (!swiglu) { f.row0 = 0; f.rows = N; }
+    const size_t up = (size_t)(N / 2) * (sc ? (size_t)(K / 32) * 34 : (size_t)K * 2);  // byte offset of the up rows
+    if (sc) {
+        f.dst_scale = *sc; f.src8_a = src; if (swiglu) f.src8_b = f.src8_a + up;
+        q3_launch_fill_tiled_q8(f, nullptr);
+    } else {
+        f.src_a = src; if (swiglu) f.src_b = (const uint16_t*)((const char*)src.p + up);
+        q3_launch_fill_tiled(f, nullptr);
+    }
+}
+
+extern "C" int q3tts_k_gemm_exact(int32_t device, const float* x, int32_t B, int32_t K, const uint16_t* w, int32_t N, const float* norm_w,
+                                  float eps, const float* bias, int32_t epi, float* y, uint64_t* keys, int32_t iters, float* mean_ms) {
+    if (!x || !w || !y || B <= 0 || K % 512 || N % 16 || (norm_w && K > 8192)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "gemm hook: bad shape");
+    if (epi == Q3_EPI_SWIGLU && (N % 32)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "swiglu needs N % 32 == 0");
+    HK(hipSetDevice(device));
+    const int F = N / 2;
+    const size_t ny = epi == Q3_EPI_SWIGLU ? (size_t)B * F : (size_t)B * N;
+    DevBuf dx, dw, dwt, dn, db, dy, dk;
+    TRY(dx.put(x, (size_t)B * K * 4)); TRY(dw.put(w, (size_t)N * K * 2)); TRY(dwt.alloc((size_t)N * K * 2)); TRY(dn.put(norm_w, (size_t)K * 4));
+    TRY(db.put(bias, (size_t)N * 4)); TRY(dy.put(epi == Q3_EPI_RESID ? y : nullptr, ny * 4)); TRY(dk.alloc((size_t)B * 8));
+    tile_weight(dw, dwt, nullptr, N, K, epi == Q3_EPI_SWIGLU);
+    Q3Gemm g{}; g.x = dx; g.ldx = K; g.B = B; g.w = dwt; g.K = K; g.N = N; g.eps = eps; g.epi = epi;
+    if (norm_w) g.norm_w = dn;
+    if (bias) g.bias = db;
+    g.y = dy; g.ldy = epi == Q3_EPI_SWIGLU ? F : N; g.keys = dk; g.key_stride = 1;
+    q3_launch_gemm(g, nullptr);
+    HK(hipDeviceSynchronize());
+    if (epi == Q3_EPI_ARGMAX) {
+        if (keys) TRY(dk.get(keys, (size_t)B * 8));
+    } else TRY(dy.get(y, ny * 4));
+#ifdef Q3_STAMPS
+    {  // experiment builds: phase stamps of workgroup 0 / wave 0 of one warm launch (shader-clock cycles from kernel entry)
+        DevBuf dd; dd.alloc(64 * 8);
+        g.dbg = nullptr; q3_launch_gemm(g, nullptr); q3_launch_gemm(g, nullptr);
+        g.dbg = (unsigned long long*)dd.p; hipMemset(dd.p, 0, 64 * 8);
+        q3_launch_gemm(g, nullptr); hipDeviceSynchronize();
+        unsigned long long st[8]; hipMemcpy(st, dd.p, 64, hipMemcpyDeviceToHost);
+        fprintf(stderr, "stamps B=%d K=%d N=%d norm=%d epi=%d: entry->loop %llu | first operands %llu | loop end %llu | barrier %llu | sums %llu | stores done %llu\n",
+                B, K, N, norm_w ? 1 : 0, epi, st[1] - st[0], st[2] - st[0], st[3] - st[0], st[4] - st[0], st[5] - st[0], st[6] - st[0]);
+        unsigned long long ws[64]; hipMemcpy(ws, dd.p, 64 * 8, hipMemcpyDeviceToHost);
+        for (int w = 0; w < 8; ++w)
+            fprintf(stderr, "   wave %d: first operands %llu, mid loop %llu, loop end %llu\n", w, ws[8 + w * 4] - st[0], ws[8 + w * 4 + 1] - st[0], ws[8 + w * 4 + 2] - st[0]);
+        g.dbg = nullptr;
+    }
+#endif
+    g.epi = epi == Q3_EPI_RESID ? Q3_EPI_STORE : epi;
+    return time_launches(iters, [&] { q3_launch_gemm(g, nullptr); }, mean_ms);
+}
+
+extern "C" int q3tts_k_attention(int32_t device, const float* qkv, int32_t n_rows, int32_t pos0, int32_t Hq, int32_t Hkv, int32_t hd,
+                                 const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, float* out) {
+    if (!qkv || !out || hd != 128 || n_rows <= 0 || Hq % Hkv) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention hook: bad shape");
+    HK(hipSetDevice(device));
+    const int n_ctx = ((pos0 + n_rows + 63) / 64) * 64, ld = (Hq + 2 * Hkv) * hd;
+    std::vector<float> cs, sn;
+    q3_rope_tables(n_ctx, hd, theta, sections, cs, sn);
+    std::vector<int> rp(n_rows), rs(n_rows, 0);
+    for (int i = 0; i < n_rows; ++i) rp[i] = pos0 + i;
+    DevBuf dq, dout, dqn, dkn, dcs, dsn, dkc, dvc, drp, drs;
+    TRY(dq.put(qkv, (size_t)n_rows * ld * 4)); TRY(dout.alloc((size_t)n_rows * Hq * hd * 4)); TRY(dqn.put(qnw, hd * 4)); TRY(dkn.put(knw, hd * 4));
+    TRY(dcs.put(cs.data(), cs.size() * 4)); TRY(dsn.put(sn.data(), sn.size() * 4));
+    TRY(dkc.alloc((size_t)Hkv * n_ctx * hd * 2)); TRY(dvc.alloc((size_t)Hkv * n_ctx * hd * 2));
+    TRY(drp.put(rp.data(), n_rows * 4)); TRY(drs.put(rs.data(), n_rows * 4));
+    Q3QkPrep qp{}; qp.qkv = dq; qp.ld = ld; qp.rows = n_rows; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = hd; qp.qnw = dqn; qp.knw = dkn; qp.eps = eps;
+    qp.cs = dcs; qp.sn = dsn; qp.kc = dkc; qp.vc = dvc; qp.n_ctx = n_ctx; qp.row_pos = drp; qp.row_slot = drs;
+    q3_launch_qk_prep(qp, nullptr);
+    Q3Attend at{}; at.qkv = dq; at.ld = ld; at.rows = n_rows; at.out = dout; at.ldo = Hq * hd; at.Hq = Hq; at.Hkv = Hkv; at.hd = hd;
+    at.kc = dkc; at.vc = dvc; at.n_ctx = n_ctx; at.row_pos = qp.row_pos; at.row_slot = qp.row_slot;
+    q3_launch_attend(at, nullptr);
+    HK(hipDeviceSynchronize());
+    return dout.get(out, (size_t)n_rows * Hq * hd * 4);
+}
+
+// Decode attention as the engine's frame step runs it: per slot, rows 0 .. len - 2 go through k_qk_prep into a cache of n_ctx positions,
+// then ONE fused decode launch (one row per slot at pos = len - 1; q/k prep and the K/V append in-kernel) through q3_launch_attend under
+// decode policy `policy` (-1: the current one). qkv holds the slots' rows back to back ([sum lens][(Hq + 2 Hkv) hd]); out_f32 [n_slots][Hq hd];
+// out_bf16 (optional): the same launch writing the A-tiled bf16 operand of the O projection, untiled here to [n_slots][Hq hd].
+extern "C" int q3tts_k_attention_decode(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq,
+                                        int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta,
+                                        const int32_t* sections, int32_t policy, float* out_f32, uint16_t* out_bf16) {
+    if (!qkv || !lens || !out_f32 || hd != 128 || n_slots <= 0 || Hkv <= 0 || Hq % Hkv || Hq / Hkv < 2 || n_ctx <= 0 || n_ctx % 64 || policy < -1 || policy > 1)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode hook: bad shape");
+    long long total = 0;
+    for (int s = 0; s < n_slots; ++s) {
+        if (lens[s] < 1 || lens[s] > n_ctx) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode hook: a length outside 1 .. n_ctx");
+        total += lens[s];
+    }
+    HK(hipSetDevice(device));
+    const int ld = (Hq + 2 * Hkv) * hd, nq = Hq * hd, npre = (int)(total - n_slots);
+    std::vector<float> cs, sn;
+    q3_rope_tables(n_ctx, hd, theta, sections, cs, sn);
+    std::vector<float> last((size_t)n_slots * ld);
+    std::vector<int> pp, ps, dp(n_slots), ds(n_slots);
+    pp.reserve(npre); ps.reserve(npre);
+    {
+        size_t r0 = 0;
+        for (int s = 0; s < n_slots; ++s) {
+            for (int r = 0; r < lens[s] - 1; ++r) { pp.push_back(r); ps.push_back(s); }
+            memcpy(&last[(size_t)s * ld], qkv + (r0 + lens[s] - 1) * ld, (size_t)ld * 4);
+            dp[s] = lens[s] - 1; ds[s] = s;
+            r0 += lens[s];
+        }
+    }
+    DevBuf dpre, dlast, dout, dob, dqn, dkn, dcs, dsn, dkc, dvc, dpp, dps, ddp, dds;
+    const size_t cache = (size_t)n_slots * Hkv * n_ctx * hd * 2, npre1 = (size_t)std::max(npre, 1);
+    TRY(dpre.alloc(npre1 * ld * 4)); TRY(dlast.alloc(last.size() * 4)); TRY(dout.alloc((size_t)n_slots * nq * 4)); TRY(dob.alloc(pad16(n_slots) * nq * 2));
+    TRY(dqn.put(qnw, hd * 4)); TRY(dkn.put(knw, hd * 4)); TRY(dcs.put(cs.data(), cs.size() * 4)); TRY(dsn.put(sn.data(), sn.size() * 4));
+    TRY(dkc.alloc(cache)); TRY(dvc.alloc(cache)); TRY(dpp.alloc(npre1 * 4)); TRY(dps.alloc(npre1 * 4));
+    TRY(ddp.put(dp.data(), n_slots * 4)); TRY(dds.put(ds.data(), n_slots * 4));
+    {
+        size_t r0 = 0, o = 0;
+        for (int s = 0; s < n_slots; ++s) {
+            const size_t n = lens[s] - 1;
+            if (n) HK(hipMemcpy((float*)dpre.p + o * ld, qkv + r0 * ld, n * ld * 4, hipMemcpyHostToDevice));
+            o += n; r0 += lens[s];
+        }
+    }
+    if (npre) { HK(hipMemcpy(dpp.p, pp.data(), npre * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dps.p, ps.data(), npre * 4, hipMemcpyHostToDevice)); }
+    Q3QkPrep qp{}; qp.qkv = dpre; qp.ld = ld; qp.rows = npre; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = hd; qp.qnw = dqn; qp.knw = dkn; qp.eps = eps;
+    qp.cs = dcs; qp.sn = dsn; qp.kc = dkc; qp.vc = dvc; qp.n_ctx = n_ctx; qp.row_pos = dpp; qp.row_slot = dps;
+    if (npre) q3_launch_qk_prep(qp, nullptr);
+    int old_dec = 0, old_pre = 0;
+    q3_attend_policy_get(&old_dec, &old_pre);
+    if (policy >= 0) q3_attend_policy(policy, old_pre);
+    for (int pass = 0; pass < (out_bf16 ? 2 : 1); ++pass) {
+        // both passes start from the same cache: the fused launch's append rewrites position len - 1 with the same bits
+        HK(hipMemcpy(dlast.p, last.data(), last.size() * 4, hipMemcpyHostToDevice));
+        Q3QkPrep dq = qp; dq.qkv = dlast; dq.rows = n_slots; dq.row_pos = ddp; dq.row_slot = dds;
+        Q3Attend at{}; at.qkv = dlast; at.ld = ld; at.rows = n_slots; at.ldo = nq; at.Hq = Hq; at.Hkv = Hkv; at.hd = hd;
+        at.kc = dkc; at.vc = dvc; at.n_ctx = n_ctx; at.row_pos = dq.row_pos; at.row_slot = dq.row_slot;
+        at.fused = 1; at.prep = dq;
+        if (pass == 0) { at.out = dout; at.out_bf16 = 0; }
+        else { at.out = dob; at.out_bf16 = 1; }
+        q3_launch_attend(at, nullptr);
+        const hipError_t er = hipDeviceSynchronize();
+        if (er != hipSuccess) { q3_attend_policy(old_dec, old_pre); return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, std::string("attention decode hook: ") + hipGetErrorString(er)); }
+    }
+    q3_attend_policy(old_dec, old_pre);
+    HK(hipGetLastError());
+    TRY(dout.get(out_f32, (size_t)n_slots * nq * 4));
+    return out_bf16 ? untile_host(dob, n_slots, nq, out_bf16) : Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_sample(int32_t device, const float* logits, int32_t n, int32_t ld, int32_t limit, float temperature, int32_t top_k,
+                              float top_p, const float* r, int32_t* out) {
+    if (!logits || !out || n <= 0 || limit <= 0 || limit > 4096 || limit > ld) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "sample hook: bad shape");
+    HK(hipSetDevice(device));
+    DevBuf dl, dr, dout;
+    TRY(dl.put(logits, (size_t)n * ld * 4)); TRY(dr.put(r, (size_t)n * 4)); TRY(dout.alloc((size_t)n * 4));
+    q3_launch_sample_rows(dl, n, ld, limit, temperature, top_k, top_p, r ? (const float*)dr.p : nullptr, dout, nullptr);
+    HK(hipDeviceSynchronize());
+    return dout.get(out, (size_t)n * 4);
+}
+
+// The decoder's GEMM on bf16 rows through its launcher (q3_bgemm.hip), behind q3tts_k_bgemm (w: bf16 bits row-major [N][K]) and
+// q3tts_k_bgemm_q8 (q8: w holds block_q8_0 rows). The entry points have checked the arguments.
+static int bgemm_hook(const char* name, int device, const uint16_t* xb, int B, int K, const void* w, bool q8, int N, const float* ssp, int ntiles, int d_norm,
+                      float eps, int epi, const float* nw_next, float* y, uint16_t* yb, float* ssp_out, uint64_t* keys, int iters, float* mean_ms) {
+    HK(hipSetDevice(device));
+    const int F = N / 2, nt = N / 16;
+    DevBuf dx, dw, dwt, dsc, ds, dn, dy, dyb, dso, dk;
+    { const std::vector<uint16_t> xt = atile_host(xb, B, K); TRY(dx.put(xt.data(), xt.size() * 2)); }
+    TRY(dw.put(w, q8 ? (size_t)N * (K / 32) * 34 : (size_t)N * K * 2)); TRY(dwt.alloc(q8 ? (size_t)N * K : (size_t)N * K * 2));
+    if (q8) TRY(dsc.alloc((size_t)N * (K / 32) * 2));
+    TRY(ds.put(ntiles > 0 ? ssp : nullptr, (size_t)B * std::max(ntiles, 1) * 4)); TRY(dn.put(nw_next, (size_t)N * 4));
+    TRY(dy.put(epi == Q3_EPI_RESID ? y : nullptr, (size_t)B * N * 4)); TRY(dyb.alloc(pad16(B) * N * 2)); TRY(dso.alloc((size_t)B * nt * 4)); TRY(dk.alloc((size_t)B * nt * 8));
+    tile_weight(dw, dwt, q8 ? &dsc : nullptr, N, K, epi == Q3_EPI_SWIGLU);
+    Q3BGemm g{}; g.a = dx; g.a_row0 = 0; g.B = B; g.w = dwt; g.K = K; g.N = N;
+    if (q8) g.wscale = dsc;
+    if (ssp) g.ssp = ds;
+    g.ld_ssp = ntiles; g.ntiles = ntiles; g.d_norm = d_norm; g.eps = eps; g.epi = epi;
+    g.y = dy; g.ldy = N; g.yb = dyb;
+    if (nw_next) g.nw_next = dn;
+    g.ssp_out = dso; g.ld_ssp_out = nt; g.keys = dk; g.key_stride = nt;
+    if (q3_launch_bgemm(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string(name) + ": shape");
+    HK(hipDeviceSynchronize());
+    if (epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) TRY(dy.get(y, (size_t)B * N * 4));
+    if (epi == Q3_EPI_SWIGLU) TRY(untile_host(dyb, B, F, yb));
+    if (epi == Q3_EPI_RESID && nw_next) { TRY(untile_host(dyb, B, N, yb)); TRY(dso.get(ssp_out, (size_t)B * nt * 4)); }
+    if (epi == Q3_EPI_ARGMAX) {  // the kernel leaves one maximum per (row, 16-column tile); the consumer (here: the hook) takes the row maximum
+        std::vector<uint64_t> parts((size_t)B * nt);
+        TRY(dk.get(parts.data(), parts.size() * 8));
+        for (int b = 0; b < B; ++b) { uint64_t m = 0; for (int t = 0; t < nt; ++t) m = std::max(m, parts[(size_t)b * nt + t]); keys[b] = m; }
+    }
+    if (epi == Q3_EPI_RESID) { g.epi = Q3_EPI_STORE; g.nw_next = nullptr; }
+    return time_launches(iters, [&] { q3_launch_bgemm(g, nullptr); }, mean_ms);
+}
+
+// xb bf16 bits [B][K]; w bf16 bits row-major [N][K] (epi 2: the F gate rows, then the F up rows); ssp [B][ntiles] or NULL; y in/out for
+// epi 1. Mirrors oracle/q3_oracle_bf16.c q3o_bgemm.
+extern "C" int q3tts_k_bgemm(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const uint16_t* w, int32_t N, const float* ssp, int32_t ntiles,
+                             int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb, float* ssp_out, uint64_t* keys,
+                             int32_t iters, float* mean_ms) {
+    if (!xb || !w || B <= 0 || K % 256 || K < 256 || N % 16 || epi < 0 || epi > 3) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: K % 256 == 0, N % 16 == 0");
+    if (epi == Q3_EPI_SWIGLU && (N % 64 || !yb)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: swiglu needs N % 64 == 0 and yb");
+    if (epi == Q3_EPI_RESID && nw_next && N % 32) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: norm outputs need N % 32 == 0");
+    if ((epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) && !y) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: y missing");
+    if (epi == Q3_EPI_ARGMAX && !keys) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: keys missing");
+    if (epi == Q3_EPI_RESID && nw_next && (!yb || !ssp_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: norm outputs missing");
+    return bgemm_hook("bgemm", device, xb, B, K, w, false, N, ssp, ntiles, d_norm, eps, epi, nw_next, y, yb, ssp_out, keys, iters, mean_ms);
+}
+
+// the same launch with ggml Q8_0 weights kept in block form: q int8 [N][K], d_f16 [N][K/32]. Mirrors oracle q3o_bgemm_q8.
+extern "C" int q3tts_k_bgemm_q8(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N, const float* ssp,
+                                int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb, float* ssp_out,
+                                uint64_t* keys, int32_t iters, float* mean_ms) {
+    if (!xb || !q || !d_f16 || B <= 0 || K % 512 || K < 512 || N % 16 || epi < 0 || epi > 3) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8 hook: K % 512 == 0, N % 16 == 0");
+    if (epi == Q3_EPI_SWIGLU && (N % 64 || !yb)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8 hook: swiglu needs N % 64 == 0 and yb");
+    if (epi == Q3_EPI_RESID && nw_next && (N % 32 || !yb || !ssp_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8 hook: norm outputs");
+    if ((epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) && !y) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8 hook: y missing");
+    if (epi == Q3_EPI_ARGMAX && !keys) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8 hook: keys missing");
+    const std::vector<uint8_t> blocks = pack_q8_0(q, d_f16, N, K);
+    return bgemm_hook("bgemm_q8", device, xb, B, K, blocks.data(), true, N, ssp, ntiles, d_norm, eps, epi, nw_next, y, yb, ssp_out, keys, iters, mean_ms);
+}
+
+// W8A8 (q3_bgemm8.hip): activations and weights as ggml Q8_0 blocks in natural order in / out; the hook tiles them for the device
+extern "C" int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const float* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N,
+                                  const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, float* yd,
+                                  float* ssp_out, int32_t iters, float* mean_ms) {
+    if (!aq || !ad || !q || !d_f16 || B <= 0 || K % 512 || K < 512 || N % 32 || epi < 0 || epi > 2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8 hook: K % 512 == 0, N % 32 == 0, epilogue 0..2");
+    if (epi == Q3_EPI_SWIGLU && (N % 128 || !yq || !yd)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8 hook: swiglu needs N % 128 == 0, yq, yd");
+    if (epi == Q3_EPI_RESID && (N % 64 || !nw_next || !yq || !yd || !ssp_out || !y)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8 hook: residual needs N % 64 == 0, nw_next, y, yq, yd, ssp_out");
+    if (epi == Q3_EPI_STORE && !y) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8 hook: y missing");
+    HK(hipSetDevice(device));
+    const int F = N / 2, kb = K / 32, Nout = epi == Q3_EPI_SWIGLU ? F : N;
+    const size_t B16 = pad16(B); const int rt16 = (int)(B16 / 16);
+    const std::vector<uint8_t> blocks = pack_q8_0(q, d_f16, N, K);
+    std::vector<int8_t> at(B16 * K, 0); std::vector<float> ast((size_t)kb * B16, 0.0f);
+    for (int r = 0; r < B; ++r) {
+        for (int k = 0; k < K; ++k) at[q3_q8_off(r, k, K >> 6)] = aq[(size_t)r * K + k];
+        for (int b = 0; b < kb; ++b) ast[q3_q8_scale_idx(r, b, rt16)] = ad[(size_t)r * kb + b];
+    }
+    DevBuf dx, dxs, dw, dwt, dsc, ds, dn, dy, dyq, dys, dso;
+    TRY(dx.put(at.data(), at.size())); TRY(dxs.put(ast.data(), ast.size() * 4)); TRY(dw.put(blocks.data(), blocks.size())); TRY(dwt.alloc((size_t)N * K));
+    TRY(dsc.alloc((size_t)N * kb * 2)); TRY(ds.put(ntiles > 0 ? ssp : nullptr, (size_t)B * std::max(ntiles, 1) * 4)); TRY(dn.put(nw_next, (size_t)N * 4));
+    TRY(dy.put(epi == Q3_EPI_RESID ? y : nullptr, (size_t)B * N * 4)); TRY(dyq.alloc(B16 * Nout)); TRY(dys.alloc((size_t)(Nout / 32 + 2) * B16 * 4));
+    TRY(dso.alloc((size_t)B * (N / 16) * 4));
+    tile_weight(dw, dwt, &dsc, N, K, epi == Q3_EPI_SWIGLU);
+    Q3BGemm g{}; g.a = dx; g.ascale = dxs; g.a_rt16 = rt16; g.a_row0 = 0; g.B = B; g.w = dwt; g.wscale = dsc; g.K = K; g.N = N;
+    if (ssp) g.ssp = ds;
+    g.ld_ssp = ntiles; g.ntiles = ntiles; g.d_norm = d_norm; g.eps = eps; g.epi = epi;
+    g.y = dy; g.ldy = N; g.yb = dyq; g.yscale = dys; g.y_rt16 = rt16;
+    if (nw_next) g.nw_next = dn;
+    g.ssp_out = dso; g.ld_ssp_out = N / 16;
+    if (q3_launch_bgemm8(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8: shape");
+    HK(hipDeviceSynchronize());
+    if (epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) TRY(dy.get(y, (size_t)B * N * 4));
+    if (epi != Q3_EPI_STORE) {
+        std::vector<int8_t> qt(B16 * Nout); std::vector<float> st((size_t)(Nout / 32) * B16);
+        TRY(dyq.get(qt.data(), qt.size())); TRY(dys.get(st.data(), st.size() * 4));
+        for (int r = 0; r < B; ++r) {
+            for (int k = 0; k < Nout; ++k) yq[(size_t)r * Nout + k] = qt[q3_q8_off(r, k, Nout >> 6)];
+            for (int b = 0; b < Nout / 32; ++b) yd[(size_t)r * (Nout / 32) + b] = st[q3_q8_scale_idx(r, b, rt16)];
+        }
+        if (epi == Q3_EPI_RESID) TRY(dso.get(ssp_out, (size_t)B * (N / 16) * 4));
+    }
+    if (epi == Q3_EPI_RESID) g.epi = Q3_EPI_STORE;
+    return time_launches(iters, [&] { q3_launch_bgemm8(g, nullptr); }, mean_ms);
+}
+
+// The vocoder's extras of the decoder GEMM (bias, GELU -> bf16, LayerScale column scale, per-slot row segments, a bf16 copy of the
+// residual result) through one hook: epi 0 (store) / 1 (residual) / 4 (GELU). y0 / y are dense [B][N]; with seg_rows > 0 the kernel
+// works on a buffer of B / seg_rows segments, each preceded by gap_rows sentinel rows that must come back untouched.
+extern "C" int q3tts_k_bgemm_voc(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const uint16_t* w, int32_t N, int32_t epi, const float* bias,
+                                 int32_t bias_n, const float* col_scale, int32_t seg_rows, int32_t gap_rows, float* y, uint16_t* yb, int32_t want_yb) {
+    if (!xb || !w || B <= 0 || K % 256 || K < 256 || N % 32 || (epi != Q3_EPI_STORE && epi != Q3_EPI_RESID && epi != Q3_EPI_GELU))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_voc hook: K % 256 == 0, N % 32 == 0, epilogue 0 / 1 / 4");
+    if ((epi != Q3_EPI_GELU && !y) || ((epi == Q3_EPI_GELU || want_yb) && !yb)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_voc hook: output missing");
+    if (seg_rows < 0 || gap_rows < 0 || (seg_rows > 0 && B % seg_rows) || (bias && bias_n < 1)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_voc hook: segments / bias");
+    HK(hipSetDevice(device));
+    const int T = seg_rows > 0 ? seg_rows : B, S = B / T, P = T + (seg_rows > 0 ? gap_rows : 0);
+    std::vector<float> seg((size_t)S * P * N, -12345.5f);  // sentinel in the gap rows
+    if (epi != Q3_EPI_GELU)
+        for (int sidx = 0; sidx < S; ++sidx)
+            for (int t = 0; t < T; ++t) memcpy(&seg[((size_t)sidx * P + (P - T) + t) * N], y + ((size_t)sidx * T + t) * N, (size_t)N * 4);
+    DevBuf dx, dw, dwt, db, dc, dy, dyb;
+    { const std::vector<uint16_t> xt = atile_host(xb, B, K); TRY(dx.put(xt.data(), xt.size() * 2)); }
+    TRY(dw.put(w, (size_t)N * K * 2)); TRY(dwt.alloc((size_t)N * K * 2)); TRY(db.put(bias, (size_t)(bias ? bias_n : 1) * 4)); TRY(dc.put(col_scale, (size_t)N * 4));
+    TRY(dy.put(seg.data(), seg.size() * 4)); TRY(dyb.alloc(pad16(B) * N * 2));
+    tile_weight(dw, dwt, nullptr, N, K, false);
+    Q3BGemm g{}; g.a = dx; g.B = B; g.w = dwt; g.K = K; g.N = N; g.epi = epi;
+    g.y = (float*)dy.p + (size_t)(P - T) * N; g.ldy = N;
+    if (seg_rows > 0) { g.seg_rows = T; g.seg_stride = (size_t)P * N; }
+    if (bias) g.bias = db;
+    g.bias_n = bias_n;
+    if (col_scale) g.col_scale = dc;
+    if (epi == Q3_EPI_GELU || want_yb) g.yb = dyb;
+    if (q3_launch_bgemm(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_voc: shape");
+    HK(hipDeviceSynchronize());
+    if (epi != Q3_EPI_GELU) {
+        TRY(dy.get(seg.data(), seg.size() * 4));
+        for (int sidx = 0; sidx < S; ++sidx) {
+            for (int t = 0; t < P - T; ++t)
+                for (int c = 0; c < N; ++c)
+                    if (seg[((size_t)sidx * P + t) * N + c] != -12345.5f) return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, "bgemm_voc: a gap row was written");
+            for (int t = 0; t < T; ++t) memcpy(y + ((size_t)sidx * T + t) * N, &seg[((size_t)sidx * P + (P - T) + t) * N], (size_t)N * 4);
+        }
+    }
+    return (epi == Q3_EPI_GELU || want_yb) ? untile_host(dyb, B, N, yb) : Q3TTS_OK;
+}
+
+// H6 through the projection kernel: y[rows][n_out] = bias + sum x * w (reference order); nw != NULL: the rows' norm inputs too
+extern "C" int q3tts_k_project(int32_t device, const float* x, int32_t rows, int32_t n_in, const float* w, const float* bias, int32_t n_out, const float* nw,
+                               float* y, uint16_t* xb, float* ssp) {
+    if (!x || !w || !bias || !y || rows <= 0 || n_in % 64 || n_out % 16 || (nw && (!xb || !ssp))) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "project hook: n_in % 64 == 0, n_out % 16 == 0");
+    HK(hipSetDevice(device));
+    DevBuf dx, dw, db, dn, dy, dxb, dss;
+    TRY(dx.put(x, (size_t)rows * n_in * 4)); TRY(dw.put(w, (size_t)n_out * n_in * 4)); TRY(db.put(bias, (size_t)n_out * 4)); TRY(dn.put(nw, (size_t)n_out * 4));
+    TRY(dy.alloc((size_t)rows * n_out * 4)); TRY(dxb.alloc(pad16(rows) * n_out * 2)); TRY(dss.alloc((size_t)rows * (n_out / 16) * 4));
+    Q3Project pj{}; pj.x = dx; pj.ldx = n_in; pj.rows = rows; pj.w = dw; pj.bias = db; pj.n_in = n_in; pj.n_out = n_out;
+    pj.y = dy; pj.ldy = n_out; pj.xb = dxb; pj.ssp = dss; pj.ld_ssp = n_out / 16;
+    if (nw) pj.nw = dn;
+    if (q3_launch_project(pj, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "project: shape");
+    HK(hipDeviceSynchronize());
+    TRY(dy.get(y, (size_t)rows * n_out * 4));
+    if (nw) {
+        if (n_out % 32) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "project hook: norm outputs need n_out % 32 == 0");
+        TRY(untile_host(dxb, rows, n_out, xb));
+        TRY(dss.get(ssp, (size_t)rows * (n_out / 16) * 4));
+    }
+    return Q3TTS_OK;
+}
+
+// producer side of the split RMSNorm for plain f32 rows (d % 256 == 0)
+extern "C" int q3tts_k_norm_inputs(int32_t device, const float* x, int32_t rows, int32_t d, const float* nw, uint16_t* xb, float* ssp) {
+    if (!x || !nw || !xb || !ssp || rows <= 0 || d % 256) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "norm-inputs hook: d % 256 == 0");
+    HK(hipSetDevice(device));
+    DevBuf dx, dn, dxb, dss;
+    TRY(dx.put(x, (size_t)rows * d * 4)); TRY(dn.put(nw, (size_t)d * 4)); TRY(dxb.alloc(pad16(rows) * d * 2)); TRY(dss.alloc((size_t)rows * (d / 16) * 4));
+    q3_launch_norm_inputs(dx, d, rows, d, dn, dxb, 0, dss, d / 16, nullptr);
+    HK(hipDeviceSynchronize());
+    TRY(untile_host(dxb, rows, d, xb));
+    return dss.get(ssp, (size_t)rows * (d / 16) * 4);
+}
+
+// one v_mfma_f32_16x16x32_bf16 chain per case (test hook: pins the instruction's accumulation arithmetic against the
+// oracle's integer restatement, oracle/q3_oracle.c q3o_mfma_bf16_dot32)
+typedef float q3_f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 q3_bf16x8 __attribute__((ext_vector_type(8)));
+__global__ void k_mfma_bf16_cases(const uint16_t* A, const uint16_t* B, const float* C, float* D, int chain) {
+    const int l = threadIdx.x, cs = blockIdx.x;
+    const uint16_t* a = A + (size_t)cs * chain * 512; const uint16_t* b = B + (size_t)cs * chain * 512;
+    q3_f32x4 acc;
+    for (int j = 0; j < 4; ++j) acc[j] = C[(size_t)cs * 256 + (4 * (l >> 4) + j) * 16 + (l & 15)];
+    for (int st = 0; st < chain; ++st) {
+        union { q3_bf16x8 v; uint16_t u[8]; } af, bf;
+        for (int j = 0; j < 8; ++j) {  // lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15]
+            af.u[j] = a[(size_t)st * 512 + (l & 15) * 32 + 8 * (l >> 4) + j];
+            bf.u[j] = b[(size_t)st * 512 + (8 * (l >> 4) + j) * 16 + (l & 15)];
+        }
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.v, bf.v, acc, 0, 0, 0);
+    }
+    for (int j = 0; j < 4; ++j) D[(size_t)cs * 256 + (4 * (l >> 4) + j) * 16 + (l & 15)] = acc[j];
+}
+extern "C" int q3tts_k_mfma_bf16(int32_t device, const uint16_t* a, const uint16_t* b, const float* c, float* d, int32_t n_cases, int32_t chain) {
+    if (!a || !b || !c || !d || n_cases <= 0 || chain <= 0) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "mfma hook: bad shape");
+    HK(hipSetDevice(device));
+    const size_t nab = (size_t)n_cases * chain * 512 * 2, ncd = (size_t)n_cases * 256 * 4;
+    DevBuf da, db, dc, dd;
+    TRY(da.put(a, nab)); TRY(db.put(b, nab)); TRY(dc.put(c, ncd)); TRY(dd.alloc(ncd));
+    hipLaunchKernelGGL(k_mfma_bf16_cases, dim3(n_cases), dim3(64), 0, nullptr, (const uint16_t*)da.p, (const uint16_t*)db.p, (const float*)dc.p, (float*)dd.p, chain);
+    HK(hipDeviceSynchronize());
+    return dd.get(d, ncd);
+}
+
+// Talker prefill of one prompt (behind a voice prefix, if given) through the engine's own admission into slot 0; the slot is retired again
+static int talker_prefill(q3tts_engine* e, const q3tts_prefix* prefix, const float* embd, int32_t n_tok, float* hidden_out, float* logits_out) {
+    Q3_NOT_IN_SESSION(e);
+    if (!e || !embd || n_tok <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
+    Q3_HIP(e, hipSetDevice(e->cfg.device));
+    q3tts_request r{}; r.prompt_embd = embd; r.n_tok = n_tok; r.use_engine_sampler = 0; r.temperature = 0; r.max_steps = 1; r.prefix = prefix;
+    const q3tts_request* rp = &r;
+    const int slot = 0;
+    int rc = Q3TTS_OK;
+    TRY(q3_plan_rows(e, std::vector<int>{slot}));
+    TRY(q3_admit_many(e, &slot, &rp, 1, &rc));
+    TRY(rc);
+    const q3tts_model_config& m = e->cfg.model;
+    const Q3Lane& L = e->lane;
+    hipStream_t s = e->stream;
+    if (hidden_out) {
+        q3_launch_rmsnorm_rows(L.T.x, m.t_d_model, e->T.out_norm, m.rms_eps, m.t_d_model, 1, L.logits_tmp, m.t_d_model, s);
+        Q3_HIP(e, hipMemcpyAsync(hidden_out, L.logits_tmp, (size_t)m.t_d_model * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (logits_out) Q3_HIP(e, hipMemcpyAsync(logits_out, L.logits, (size_t)m.t_vocab * 4, hipMemcpyDeviceToHost, s));
+    Q3Slot* stage = e->slots_host + e->B; memset(stage, 0, sizeof(Q3Slot));
+    Q3_HIP(e, hipMemcpyAsync(e->slots, stage, sizeof(Q3Slot), hipMemcpyHostToDevice, s));  // retire the slot again
+    Q3_HIP(e, hipStreamSynchronize(s));
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_k_talker_prefill(q3tts_engine* e, const float* embd, int32_t n_tok, float* hidden_out, float* logits_out) {
+    return talker_prefill(e, nullptr, embd, n_tok, hidden_out, logits_out);
+}
+extern "C" int q3tts_k_talker_prefill_prefix(q3tts_engine* e, const q3tts_prefix* prefix, const float* embd, int32_t n_tok, float* hidden_out,
+                                             float* logits_out) {
+    if (!prefix) return q3_set_err(e, Q3TTS_ERR_INVALID, "null prefix");
+    return talker_prefill(e, prefix, embd, n_tok, hidden_out, logits_out);
+}
+
+extern "C" int q3tts_k_probe(q3tts_engine* e, int32_t enable) {
+    Q3_NOT_IN_SESSION(e);
+    if (!e) return Q3TTS_ERR_INVALID;
+    Q3_HIP(e, hipSetDevice(e->cfg.device));
+    if (enable && e->probe_ev.empty()) {
+        e->probe_ev.resize(10, nullptr);  // 4 frames x 2 + one empty bracket per chunk (event overhead calibration)
+        for (auto& ev : e->probe_ev) Q3_HIP(e, hipEventCreate(&ev));
+    }
+    const int model = enable & 15, kind = enable >> 4;
+    if (model > 2 || kind < 0 || kind > 4) return q3_set_err(e, Q3TTS_ERR_INVALID, "probe: model 0..2, kind 0..4");
+    e->probe = model; e->probe_kind = kind;
+    return Q3TTS_OK;
+}
+
+// The allocator's contract (q3_dev_alloc_zeroed): the zero fill has completed when the pointer is handed out. The hook allocates
+// `bytes` through it, uploads a pattern into the first and last 4 KiB on the NULL stream at once (the stream an unsuspecting call
+// site would use), and counts the bytes that do not read back as written / as zero. An asynchronous fill on e->stream — the state
+// of rounds 1 and 2 — loses this race on large buffers.
+extern "C" int q3tts_k_alloc_upload(q3tts_engine* e, int64_t bytes, int64_t* mismatches) {
+    Q3_NOT_IN_SESSION(e);
+    if (!e || !mismatches || bytes < 16384) return q3_set_err(e, Q3TTS_ERR_INVALID, "alloc hook: bytes >= 16384");
+    Q3_HIP(e, hipSetDevice(e->cfg.device));
+    void* q = nullptr;
+    TRY(q3_dev_alloc_zeroed(e, &q, (size_t)bytes));
+    std::vector<uint8_t> pat(4096), back(12288);
+    for (int i = 0; i < 4096; ++i) pat[i] = (uint8_t)(1 + i % 251);
+    hipError_t er = hipMemcpyAsync(q, pat.data(), 4096, hipMemcpyHostToDevice, nullptr);
+    if (er == hipSuccess) er = hipMemcpyAsync((char*)q + bytes - 4096, pat.data(), 4096, hipMemcpyHostToDevice, nullptr);
+    if (er == hipSuccess) er = hipDeviceSynchronize();
+    if (er == hipSuccess) er = hipMemcpy(back.data(), q, 8192, hipMemcpyDeviceToHost);
+    if (er == hipSuccess) er = hipMemcpy(back.data() + 8192, (char*)q + bytes - 4096, 4096, hipMemcpyDeviceToHost);
+    hipFree(q);
+    if (er != hipSuccess) return q3_set_err(e, Q3TTS_ERR_DEVICE, hipGetErrorString(er));
+    int64_t bad = 0;
+    for (int i = 0; i < 4096; ++i) bad += (back[i] != pat[i]) + (back[4096 + i] != 0) + (back[8192 + i] != pat[i]);
+    *mismatches = bad;
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_bgemm_policy(int32_t big) {
+    if (big < -1 || big > 1) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm policy: -1, 0 or 1");
+    q3_bgemm_big_policy(big);
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_attend_policy(int32_t decode, int32_t prefill) {
+    if (decode < 0 || decode > 1 || prefill < 0 || prefill > 2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attend policy: decode 0..1, prefill 0..2");
+    q3_attend_policy(decode, prefill);
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_bgemm_pick(int32_t B, int32_t K, int32_t N, int32_t epilogue, int32_t w_once, int32_t q8, int32_t* out5) {
+    if (!out5 || B < 1 || K < 256 || K % 256 || N % 16) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm pick: bad shape");
+    Q3BGemm g{}; g.B = B; g.K = K; g.N = N; g.epi = epilogue; g.w_once = w_once;
+    g.a = (const uint16_t*)16; g.w = (const uint4*)16; g.wscale = q8 ? (const uint16_t*)16 : nullptr;  // (never dereferenced: nothing is launched)
+    if (epilogue == Q3_EPI_SWIGLU || epilogue == Q3_EPI_GELU) g.yb = (uint16_t*)16;
+    if (epilogue == Q3_EPI_RESID) { g.yb = (uint16_t*)16; g.nw_next = (const float*)16; }
+    int rt, nt, d, ntw, big;
+    q3_bgemm_pick(g, &rt, &nt, &d, &ntw, &big);
+    out5[0] = rt; out5[1] = nt; out5[2] = d; out5[3] = ntw; out5[4] = big;
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_pcm_pack(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* ent_row, const int32_t* ent_first,
+                                const int32_t* ent_count, const int64_t* ent_dst, int32_t n_ent, int32_t format, void* out, int64_t out_n) {
+    if (!src || !out || rows <= 0 || stride <= 0 || stride > (1 << 28) || n_ent < 0 || n_ent > Q3_PCM_MAX_ENT || (format != 0 && format != 1) || out_n < 0 ||
+        (n_ent > 0 && (!ent_row || !ent_first || !ent_count || !ent_dst)))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm pack hook: bad arguments");
+    Q3PcmPack pk{};
+    int mx = 0;
+    for (int j = 0; j < n_ent; ++j) {
+        const long long r = ent_row[j], f = ent_first[j], c = ent_count[j], d = ent_dst[j];
+        if (r < 0 || r >= rows || f < 0 || c < 0 || f + c > stride || d < 0 || d + c > out_n)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm pack hook: a window lies outside src or out");
+        pk.e[j] = Q3PcmEnt{(int32_t)r, (int32_t)f, (int32_t)c, 0, d};
+        mx = std::max(mx, (int)c);
+    }
+    const size_t es = format ? 2 : 4;
+    HK(hipSetDevice(device));
+    DevBuf s, o;
+    TRY(s.put(src, sizeof(float) * (size_t)rows * stride)); TRY(o.alloc(es * (size_t)std::max<int64_t>(out_n, 1)));
+    if (out_n > 0) HK(hipMemcpy(o.p, out, es * (size_t)out_n, hipMemcpyHostToDevice));  // samples outside every window keep their values
+    q3_launch_pcm_pack(s, (size_t)stride, pk, n_ent, mx, format, o.p, nullptr);
+    HK(hipGetLastError());
+    HK(hipDeviceSynchronize());
+    return out_n > 0 ? o.get(out, es * (size_t)out_n) : Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out) {
+    if (!out || n < 0) return Q3TTS_ERR_INVALID;
+    q3_stdrng_f32(seed, n, out);
+    return Q3TTS_OK;
+}
