@@ -106,7 +106,7 @@ typedef struct q3tts_engine_config {
                                * MFMA product scaled by f32(d)) — the reference's default quantisation (gguf_q8_0,
                                * src/tts/engine.rs:91-95). Q8_0 tensors of weights_path are kept as stored; other tensor types and the
                                * synthetic weights are quantised with ggml's reference rule. 0 (default): bf16 weights. The Predictor
-                               * keeps bf16 weights either way (157 MB, Infinity-Cache resident: its launches are latency-bound).
+                               * is not touched by this field (predictor_q8_0 below).
                                * 2: W8A8 — as 1, and every Talker GEMM's ACTIVATIONS are Q8_0 blocks too, multiplied in ggml's
                                * Q8_0 x Q8_0 arithmetic on the int8 MFMA (exact int32 block sums x f32(d_w) * d_x): what
                                * llama.cpp computes for a gguf_q8_0 directory, and what the Python API and the Rust shim select for
@@ -121,6 +121,18 @@ typedef struct q3tts_engine_config {
                                * is_last only with a non-empty final buffer (src/tts/engine.rs:510-536), so an utterance of n_frames % 4 == 0
                                * never flushes the withheld look-ahead tail and its audio ends lookahead_frames short (restated by the oracle's
                                * q3o_chunk_plan). 1: always flush at the end of an utterance (every generated frame becomes audio). */
+    int32_t predictor_q8_0;   /* 0 (default): bf16 Predictor — Q8_0 tensors of qwen3_tts_predictor.gguf are widened to bf16 at load.
+                               * 2: W8A8 — the Predictor's layer matrices and its n_codebooks - 1 heads (row blocks of output.weight) stay
+                               * ggml Q8_0 blocks on the device, and every Predictor GEMM, the argmax heads included, runs in the Q8_0 x Q8_0
+                               * arithmetic of csrc/q3_bgemm8.hip. It shares every rule of talker_q8_0 = 2: Q8_0 tensors
+                               * of the file are kept as stored, other types and the synthetic weights are quantised with ggml's reference
+                               * rule; an activation is quantised where it is produced, from the un-normalised v = x * nw; block scales are
+                               * amax / 127 rounded to an 11-bit significand and kept in f32. As for the Talker, parity with llama.cpp's own
+                               * summation order is not pinned: the order is this library's canonical one, restated by tests/_pred_q8.py.
+                               * Needs p_d_model, p_d_ffn and p_n_head * p_head_dim multiples of 512 and codebook_size a multiple of 32.
+                               * 1 (W8A16 for the Predictor) is refused with Q3TTS_ERR_UNSUPPORTED; the numbering is parallel to talker_q8_0.
+                               * Independent of talker_q8_0: any Talker mode combines with any Predictor mode. Opt-in: no API default
+                               * selects it. */
 } q3tts_engine_config;
 
 typedef struct q3tts_engine q3tts_engine;
@@ -144,7 +156,7 @@ void q3tts_default_config(q3tts_engine_config* cfg);
  *    qwen3_assets.gguf (or codec_embedding_N.npy files), contiguous from 0; codebook_size = rows of the Predictor's output.weight /
  *    (n_codebooks - 1), exactly; d_embed = the codec tables' row length (= t_d_model); text_vocab (0 without a text table,
  *    src/assets_manager.rs:244-249), codec0_rows, codecq_rows = the tables' row counts (tables 1 .. must agree).
- * Everything else is left alone: device, max_batch, n_ctx, max_steps_cap, with_vocoder, synth_seed, talker_q8_0, vocoder_flush_tail,
+ * Everything else is left alone: device, max_batch, n_ctx, max_steps_cap, with_vocoder, synth_seed, talker_q8_0, predictor_q8_0, vocoder_flush_tail,
  * the whole vocoder block, and the protocol fields no file states (sample_limit, eos_code, tts_pad_id).
  * Cross-checks: proj.weight is [p_d_model][d_embed], and blk.0.attn_q / attn_k / attn_output / ffn_gate / ffn_down.weight of both files
  * have the shapes the metadata implies. What only the device path can judge, and what q3tts_engine_create checks (K % 512,
@@ -534,6 +546,11 @@ int q3tts_k_bgemm_q8(int32_t device, const uint16_t* xb, int32_t B, int32_t K, c
 int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const float* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N,
                        const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epilogue, const float* nw_next, float* y, int8_t* yq,
                        float* yd, float* ssp_out, int32_t iters, float* mean_kernel_ms);
+/* The same launch with epilogue 3 (ARGMAX: the heads of a Predictor with predictor_q8_0 = 2): per-tile maxima keys over s_r * RAW, reduced as
+ * k_pred_next reduces them (the row's largest key; of equal logits the lower column wins) -> ids_out[B] = the winning column of each row.
+ * ssp may be NULL (no row scale). Equals np.argmax of oracle q3o_bgemm_q8a8_f32 (epilogue 0) per row. */
+int q3tts_k_bgemm_q8a8_argmax(int32_t device, const int8_t* aq, const float* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N,
+                              const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t* ids_out);
 /* The same GEMM with the epilogue extras only the vocoder uses (nothing in the reference: its vocoder is an ONNX graph, src/models/onnx.rs:342-459):
  * bias[col % bias_n] added to RAW first; epilogue 0: y = RAW + bias; 1: y += col_scale[col] * (RAW + bias), optionally yb = bf16(y);
  * 4: yb = bf16(gelu_erf(RAW + bias)). seg_rows > 0: the f32 rows live in B / seg_rows segments separated by gap_rows rows the kernel

@@ -1,7 +1,7 @@
 // q3_bgemm8.hip — the decoder's GEMM in ggml's Q8_0 x Q8_0 arithmetic (W8A8) on v_mfma_i32_16x16x32_i8: what llama.cpp computes for the
 // reference's default model directory gguf_q8_0 (/root/reference/src/tts/engine.rs:91-95, README.md:29-32: Q8_0 weights; llama.cpp's CPU
 // and GPU back ends quantise the activations of a mul_mat to Q8_0 blocks as well and multiply block by block: vec_dot_q8_0_q8_0).
-// q3tts_engine_config.talker_q8_0 = 2; oracle q3o_bgemm_q8a8_raw (oracle/q3_oracle_bf16.c).
+// q3tts_engine_config.talker_q8_0 = 2 / predictor_q8_0 = 2; oracle q3o_bgemm_q8a8_raw (oracle/q3_oracle_bf16.c).
 //
 // Canonical order: a block of 32 k contributes  p_b = f32(sumi_b) * (f32(d_w) * f32(d_x)),  sumi_b = the EXACT int32 sum of its 32 int8
 // products (one v_mfma_i32_16x16x32_i8 from a zero accumulator: integer arithmetic has no order), the scales multiplied first — ggml's
@@ -18,7 +18,8 @@
 // in f32 (q3_q8_sig11: the activations carry the magnitude of the un-normalised residual stream, which an f16 exponent does not hold).
 //
 // Workgroup = 8 waves = the 8 K slices of one (16 RT) x (16 NT) tile, DP block pairs of operands in flight per wave; slice partials meet
-// in LDS and are added in slice order, as in q3_bgemm.hip. Epilogues: STORE (y = s_r RAW), RESID (x += RAW; the consumer's operand
+// in LDS and are added in slice order, as in q3_bgemm.hip. Epilogues: STORE (y = s_r RAW), ARGMAX (per-tile maxima keys of s_r RAW: the Predictor's
+// heads with predictor_q8_0 = 2), RESID (x += RAW; the consumer's operand
 // v = x * nw_next quantised per 32 columns + the tile sums of squares: NT even), SWIGLU (h = swiglu(s_r gate, s_r up) quantised per 32
 // columns: a 16-column weight tile is 8 gate + 8 up columns, so NT = 4).
 #include "q3_kernels.h"
@@ -39,7 +40,7 @@ __device__ __forceinline__ float b8_blk(float mine) {
 __device__ __forceinline__ long b8_pack(uint32_t lo, uint32_t hi) { return (long)(((unsigned long)hi << 32) | (unsigned long)lo); }
 
 #define B8_PH(RT_, NT_) ((8 * (RT_) * (NT_) > 64) ? 2 : 1)  // slice-reduction phases: <= 64 KiB of LDS
-template <int RT, int NT, int DP, bool ALIGNED>
+template <int RT, int NT, int DP, bool ALIGNED, bool AMAX = false>
 __global__ __launch_bounds__(512) void k_bgemm8(Q3BGemm g) {
     extern __shared__ float part[];  // [8 waves][TRP regs][64 lanes]
     __shared__ float srow[64];
@@ -196,7 +197,16 @@ __global__ __launch_bounds__(512) void k_bgemm8(Q3BGemm g) {
                 for (int wv = 1; wv < 8; ++wv) s = s + part[(size_t)wv * (TRP * 64) + o];
                 v[j] = s;
             }
-            if (epi == Q3_EPI_STORE) {
+            if constexpr (AMAX) {  // Q3_EPI_ARGMAX (instances of their own: the Predictor's heads): the largest key of each tile's 16 columns
+                                   // goes to keys[row][column tile], as k_bgemm leaves them; k_pred_next takes the row's maximum
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    unsigned long long key = q3_argmax_key(g.ssp ? sc * v[j] : v[j], (uint32_t)((nb0 + j) * 16 + c));
+#pragma unroll
+                    for (int m = 1; m <= 8; m <<= 1) { const unsigned long long ok = __shfl_xor(key, m); key = ok > key ? ok : key; }
+                    if (live && c == 0) g.keys[(size_t)row * g.key_stride + (nb0 + j)] = key;
+                }
+            } else if (epi == Q3_EPI_STORE) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j)
                     if (live) g.y[(size_t)row * g.ldy + (nb0 + j) * 16 + c] = g.ssp ? sc * v[j] : v[j];
@@ -257,12 +267,21 @@ struct B8Inst {
     static void launch(const Q3BGemm& g, dim3 grid, hipStream_t s) { hipLaunchKernelGGL((k_bgemm8<RT, NT, DP, true>), grid, dim3(512), lds, s, g); }
 };
 #define B8_EACH(X) X(1, 2) X(2, 2) X(4, 2) X(1, 4) X(2, 4)   // ((4, 4) needs more than 256 registers per wave: gate/up runs 32-row chunks)
-static void b8_prepare() {
+// ARGMAX: NT = 2 only — N = codebook_size columns are one round of workgroups at any row count, where the narrowest tile costs least
+template <int RT>
+struct B8Amax {
+    static constexpr int DP = B8Inst<RT, 2>::DP;
+    static constexpr size_t lds = B8Inst<RT, 2>::lds;
+    static void prepare() { if (lds + 1024 > 65536) hipFuncSetAttribute((const void*)k_bgemm8<RT, 2, DP, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
+    static void launch(const Q3BGemm& g, dim3 grid, hipStream_t s) { hipLaunchKernelGGL((k_bgemm8<RT, 2, DP, true, true>), grid, dim3(512), lds, s, g); }
+};
+void q3_bgemm8_prepare() {  // once per device; the engine calls it before it captures a frame step (no attribute call inside a capture)
     static Q3PerDevice pd;
     pd.ensure(1, []() {
 #define P(RT_, NT_) B8Inst<RT_, NT_>::prepare();
         B8_EACH(P)
 #undef P
+        B8Amax<1>::prepare(); B8Amax<2>::prepare(); B8Amax<4>::prepare();
     });
 }
 // tile choice: as q3_launch_bgemm (fewest operand bytes per workgroup round: 16 RT + 17 NT bytes per k); RESID needs NT even, SWIGLU NT = 4
@@ -273,6 +292,7 @@ void q3_bgemm8_pick(const Q3BGemm& g, int* rt, int* nt) {
         for (int NT = 2; NT <= 4; NT *= 2) {
             if (tiles % NT) continue;
             if (g.epi == Q3_EPI_SWIGLU && NT != 4) continue;
+            if (g.epi == Q3_EPI_ARGMAX && NT != 2) continue;
             if (RT == 4 && NT == 4) continue;
             if (g.B > 64 && RT != 4 && !(RT == 2 && NT == 4)) continue;   // many rows (prefill): the largest row chunk of the column width
             const long chunks = (g.B + 16 * RT - 1) / (16 * RT);
@@ -285,21 +305,29 @@ void q3_bgemm8_pick(const Q3BGemm& g, int* rt, int* nt) {
 }
 int q3_launch_bgemm8(const Q3BGemm& g, hipStream_t s) {
     if (g.B < 1 || g.N % 32 || g.K % 512 || g.K < 512 || !g.a || !g.w || !g.wscale || !g.ascale || g.a_row0 < 0 || g.a_rt16 < 1) return -1;
-    if (g.epi != Q3_EPI_STORE && g.epi != Q3_EPI_RESID && g.epi != Q3_EPI_SWIGLU) return -1;
-    if ((g.a_row0 & 15) && g.B != 1) return -1;   // unaligned first row: the single-row pick of the prefill head only
+    if (g.epi != Q3_EPI_STORE && g.epi != Q3_EPI_RESID && g.epi != Q3_EPI_SWIGLU && g.epi != Q3_EPI_ARGMAX) return -1;
+    // unaligned first row: the single-row pick of the prefill head, and the heads of the Predictor's pass A (its code rows start at row B)
+    if ((g.a_row0 & 15) && g.B != 1 && g.epi != Q3_EPI_ARGMAX) return -1;
     if (g.epi == Q3_EPI_RESID && (!g.yb || !g.yscale || !g.nw_next || !g.ssp_out || g.N % 64 || g.y_rt16 < 1)) return -1;
     if (g.epi == Q3_EPI_SWIGLU && (!g.yb || !g.yscale || g.N % 128 || g.y_rt16 < 1)) return -1;
+    if (g.epi == Q3_EPI_ARGMAX && (!g.keys || g.key_stride < g.N / 16)) return -1;
     if (g.ssp && g.ntiles < 1) return -1;
-    b8_prepare();
-    if (g.a_row0 & 15) {  // one row that does not start a tile (the last prompt row's head at prefill): the scales are fetched row by row
+    q3_bgemm8_prepare();
+    if (g.a_row0 & 15) {  // rows that do not start a tile: the scales are fetched row by row, 16-row chunks
         if ((g.N / 16) % 2) return -1;
         const size_t lds12 = B8Inst<1, 2>::lds;
-        hipLaunchKernelGGL((k_bgemm8<1, 2, 2, false>), dim3(g.N / 32, 1), dim3(512), lds12, s, g);
+        const dim3 grid(g.N / 32, (g.B + 15) / 16);
+        if (g.epi == Q3_EPI_ARGMAX) hipLaunchKernelGGL((k_bgemm8<1, 2, 2, false, true>), grid, dim3(512), lds12, s, g);
+        else hipLaunchKernelGGL((k_bgemm8<1, 2, 2, false>), grid, dim3(512), lds12, s, g);
         return 0;
     }
     int rt, nt; q3_bgemm8_pick(g, &rt, &nt);
     if ((g.N / 16) % nt) return -1;
     const dim3 grid(g.N / 16 / nt, (g.B + 16 * rt - 1) / (16 * rt));
+    if (g.epi == Q3_EPI_ARGMAX) {
+        if (rt == 1) B8Amax<1>::launch(g, grid, s); else if (rt == 2) B8Amax<2>::launch(g, grid, s); else B8Amax<4>::launch(g, grid, s);
+        return 0;
+    }
 #define L(RT_, NT_) if (rt == RT_ && nt == NT_) { B8Inst<RT_, NT_>::launch(g, grid, s); return 0; }
     B8_EACH(L)
 #undef L

@@ -19,10 +19,10 @@ struct Q3Tfm {
     std::vector<uint4*> wqkv, wo, wgu, wd;
     float* out_norm = nullptr;
     uint4* head = nullptr;
-    // Q8_0 mode (cfg.talker_q8_0, the Talker only): the matrices above hold ggml block quants in the tiled Q8 layout (q3_kernels.h) and
+    // Q8_0 mode (cfg.talker_q8_0 / cfg.predictor_q8_0): the matrices above hold ggml block quants in the tiled Q8 layout (q3_kernels.h) and
     // these the f16 block scales [N][K/32]; empty / null = bf16 weights
     std::vector<uint16_t*> sqkv, so, sgu, sd; uint16_t* shead = nullptr; bool q8 = false;
-    bool a8 = false;  // cfg.talker_q8_0 = 2: the GEMMs' ACTIVATIONS are Q8_0 blocks as well (W8A8, q3_bgemm8.hip): every operand buffer then holds int8 quants + f32 block scales (11-bit significand: q3_q8_sig11)
+    bool a8 = false;  // cfg.talker_q8_0 = 2 / cfg.predictor_q8_0 = 2: the GEMMs' ACTIVATIONS are Q8_0 blocks as well (W8A8, q3_bgemm8.hip): every operand buffer then holds int8 quants + f32 block scales (11-bit significand: q3_q8_sig11)
     uint16_t *kc = nullptr, *vc = nullptr;  // [L][slots][Hkv][n_ctx*hd]
     size_t layer_stride = 0;
     int n_ctx = 0, n_slots = 0;

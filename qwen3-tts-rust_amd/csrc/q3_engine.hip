@@ -54,7 +54,7 @@ extern "C" void q3tts_default_config(q3tts_engine_config* c) {
     v.dec_rates[0] = 8; v.dec_rates[1] = 5; v.dec_rates[2] = 4; v.dec_rates[3] = 3;
     v.lookahead_frames = 0; v.sample_rate = 24000;
     c->device = 0; c->max_batch = 1; c->n_ctx = 4096; c->max_steps_cap = 512; c->with_vocoder = 1;
-    c->synth_seed = 0; c->weights_path = nullptr; c->talker_q8_0 = 0; c->vocoder_flush_tail = 0;
+    c->synth_seed = 0; c->weights_path = nullptr; c->talker_q8_0 = 0; c->vocoder_flush_tail = 0; c->predictor_q8_0 = 0;
 }
 
 static int validate(const q3tts_engine_config& c, std::string& why) {
@@ -81,6 +81,11 @@ static int validate(const q3tts_engine_config& c, std::string& why) {
     REQ(c.talker_q8_0 >= 0 && c.talker_q8_0 <= 2);
     if (c.talker_q8_0) REQ(m.t_d_model % 512 == 0 && m.t_d_ffn % 512 == 0 && (m.t_n_head * m.t_head_dim) % 512 == 0);  // Q8_0: an even number of 32-blocks per K slice
     if (c.talker_q8_0 == 2) REQ(m.t_vocab % 32 == 0 && ((m.t_n_head + 2 * m.t_n_kv_head) * m.t_head_dim) % 32 == 0 && m.t_d_ffn % 64 == 0);  // W8A8: whole 32-column blocks per workgroup
+    REQ(c.predictor_q8_0 >= 0 && c.predictor_q8_0 <= 2);
+    if (c.predictor_q8_0 == 2) {  // W8A8 Predictor: an even number of 32-blocks per K slice, whole 32-column blocks per workgroup
+        REQ(m.p_d_model % 512 == 0); REQ(m.p_d_ffn % 512 == 0); REQ((m.p_n_head * m.p_head_dim) % 512 == 0);
+        REQ(m.codebook_size % 32 == 0); REQ(((m.p_n_head + 2 * m.p_n_kv_head) * m.p_head_dim) % 32 == 0); REQ(m.p_d_ffn % 64 == 0);
+    }
 #undef REQ
     return Q3TTS_OK;
 }
@@ -300,7 +305,7 @@ static int alloc_scratch(q3tts_engine* e, Q3Scratch& sc, int rows, int nqkv, int
     const size_t r16 = ((size_t)rows + 15) & ~(size_t)15;  // A-tiled buffers hold whole 16-row tiles
     TRY(dalloc(e, &sc.qkv, (size_t)rows * nqkv)); TRY(dalloc(e, &sc.att, r16 * nq)); TRY(dalloc(e, &sc.h, r16 * F));
     sc.rt16 = (int)(r16 / 16);
-    if (e->T.a8) { TRY(dalloc(e, &sc.asc_att, r16 * (nq / 32))); TRY(dalloc(e, &sc.asc_h, r16 * (F / 32))); }  // W8A8: block scales of both operands
+    if (e->T.a8 || e->P.a8) { TRY(dalloc(e, &sc.asc_att, r16 * (nq / 32))); TRY(dalloc(e, &sc.asc_h, r16 * (F / 32))); }  // W8A8 (either model; nq / F are the larger of the two): block scales of both operands
     return Q3TTS_OK;
 }
 static void free_scratch(Q3Scratch& sc) { hipFree(sc.qkv); hipFree(sc.att); hipFree(sc.h); hipFree(sc.asc_att); hipFree(sc.asc_h); }
@@ -330,7 +335,7 @@ struct Q3LayerRun {
 };
 // Returns the number of launches the GEMM launcher refused (a shape it cannot run: stale activations would follow silently).
 static int run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& a, Q3Scratch& sc, hipStream_t s) {
-    // W8A8 (t.a8: the Talker with talker_q8_0 = 2): xb / sc.att / sc.h hold Q8_0 blocks (int8 quants + the f32 block scales xscale / sc.asc_att /
+    // W8A8 (t.a8: talker_q8_0 = 2 / predictor_q8_0 = 2): xb / sc.att / sc.h hold Q8_0 blocks (int8 quants + the f32 block scales xscale / sc.asc_att /
     // sc.asc_h) and every GEMM runs q3_launch_bgemm8: ggml's Q8_0 x Q8_0 arithmetic
     auto gemm = [&](Q3BGemm& g) { return t.a8 ? q3_launch_bgemm8(g, s) : q3_launch_bgemm(g, s); };
     const float eps = e->cfg.model.rms_eps;
@@ -399,21 +404,24 @@ static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
     Q3PredInput pi{}; pi.xT = L.T.x; pi.out_norm = e->T.out_norm; pi.eps = eps; pi.d = de; pi.codec0 = e->codec[0]; pi.codec0_rows = m.codec0_rows;
     pi.slots = slots; pi.row_slot = L.slot_id; pi.X = nullptr; pi.fb = L.fb; pi.B = B; pi.pproj0 = e->pproj[0]; pi.proj_b = e->proj_b; pi.dp = dp; pi.px = L.P.x;
     pi.nw = e->P.attn_norm[0]; pi.xb = L.P.xb; pi.ssp = L.P.ssp;
+    if (e->P.a8) { pi.xscale = L.P.ascale; pi.x_rt16 = L.P.rt16; }  // W8A8 Predictor: every pass-A input as Q8_0 blocks
     {   // H6 (src/assets_manager.rs:383-399) for the hidden rows only (every code embedding arrives pre-projected), in the same launch
         // as the sampler: the tiles normalise the Talker's raw output rows themselves
         Q3Project pj{}; pj.x = L.T.x; pj.ldx = de; pj.rows = B; pj.w = e->proj_w; pj.bias = e->proj_b; pj.n_in = de; pj.n_out = dp; pj.y = L.P.x; pj.ldy = dp;
         pj.nw = e->P.attn_norm[0]; pj.xb = L.P.xb; pj.ssp = L.P.ssp; pj.ld_ssp = dp / 16;  // rows [0, B) of pass A
         pj.norm_w = e->T.out_norm; pj.eps = eps;
+        if (e->P.a8) { pj.xscale = L.P.ascale; pj.x_rt16 = L.P.rt16; }
         bad += q3_launch_sample_input(sa, pi, pj, s) != 0;
     }
-    const size_t head_tile_stride = (size_t)(cbs / 16) * (dp / 32) * 64;  // uint4 per predictor head
+    // head q = rows [q cbs, (q + 1) cbs) of output.weight: uint4 per head (bf16 tiles of 32 k, Q8 tile pairs of 64 k) and its f16 block scales
+    const size_t head_tile_stride = (size_t)(cbs / 16) * (dp / (e->P.q8 ? 64 : 32)) * 64, head_scale_stride = (size_t)cbs * (dp / 32);
     auto pred_next = [&](int q) {
         Q3PredNext pn{}; pn.keys = L.keys; pn.n_key_parts = cbs / 16; pn.q = q; pn.ncb = ncb; pn.codec_q = e->codec[q]; pn.rows_q = m.codecq_rows; pn.d = de;
         pn.slots = slots; pn.row_slot = L.slot_id; pn.B = B; pn.codes = codes; pn.max_steps_cap = cap; pn.fb = L.fb;
         pn.tts_pad = e->tts_pad; pn.xT = L.T.x; pn.row_pos_t = L.row_pos_t; pn.pproj_q = e->pproj[q]; pn.proj_b = e->proj_b; pn.dp = dp; pn.px = L.P.x;
         const bool last = q == ncb - 1;
         pn.nw = last ? e->T.attn_norm[0] : e->P.attn_norm[0]; pn.xb = last ? L.T.xb : L.P.xb; pn.ssp = last ? L.T.ssp : L.P.ssp;
-        if (last && e->T.a8) { pn.xscale = L.T.ascale; pn.x_rt16 = L.T.rt16; }  // W8A8 Talker: its first operand as Q8_0 blocks
+        if (last ? e->T.a8 : e->P.a8) { pn.xscale = last ? L.T.ascale : L.P.ascale; pn.x_rt16 = last ? L.T.rt16 : L.P.rt16; }  // W8A8 consumer: its first operand as Q8_0 blocks
         q3_launch_pred_next(pn, s);
     };
     for (int q = 0; q < ncb - 1; ++q) {  // pass q produces code_{q+1}
@@ -428,7 +436,8 @@ static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
         Q3BGemm g{}; g.a = L.P.xb; g.a_row0 = q == 0 ? B : 0; g.B = B; g.w = e->P.head + head_tile_stride * q; g.K = dp; g.N = cbs;
         g.ssp = q == 0 ? L.P.ssp + (size_t)B * (dp / 16) : L.P.ssp; g.ld_ssp = dp / 16; g.ntiles = dp / 16; g.d_norm = dp; g.eps = eps;
         g.epi = Q3_EPI_ARGMAX; g.keys = L.keys; g.key_stride = cbs / 16;  // per-tile maxima; k_pred_next(q + 1) reduces them
-        bad += q3_launch_bgemm(g, s) != 0;
+        if (e->P.a8) { g.wscale = e->P.shead + head_scale_stride * q; g.ascale = L.P.ascale; g.a_rt16 = L.P.rt16; bad += q3_launch_bgemm8(g, s) != 0; }
+        else bad += q3_launch_bgemm(g, s) != 0;
     }
     pred_next(ncb - 1);
     hipEvent_t* pt = nullptr;  // probe mode 2: the Talker's layer-0 gate/up GEMM (the largest GEMM of the frame step)
@@ -521,6 +530,8 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     if (!cfg || !out) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
     std::string why;
     if (validate(*cfg, why) != Q3TTS_OK) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, why);
+    if (cfg->predictor_q8_0 == 1)
+        return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, "predictor_q8_0 = 1 (Q8_0 weights x bf16 activations) is not implemented for the Predictor: use 0 (bf16) or 2 (Q8_0 x Q8_0)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, "no HIP device: libq3tts has no CPU fallback");
@@ -533,6 +544,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
 #define HIPC(call) do { hipError_t er__ = (call); if (er__ != hipSuccess) { q3_set_err(e, Q3TTS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(er__)); return fail(Q3TTS_ERR_DEVICE); } } while (0)
     HIPC(hipSetDevice(cfg->device));
     q3_bgemm_prepare();
+    if (cfg->talker_q8_0 == 2 || cfg->predictor_q8_0 == 2) q3_bgemm8_prepare();  // kernel attributes: never inside the captures below
     HIPC(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     // Q3TTS_VOC_SERIAL=1: the vocoder shares the decoder stream (no overlap): isolates its kernels in a profile
     // (highest / lowest stream priority for the decoder / vocoder streams was measured in both rounds: no change, left out)
@@ -563,7 +575,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     TRYC(init_tfm(e, e->T, Q3G_TALKER, m.t_n_layer, m.t_d_model, m.t_n_head, m.t_n_kv_head, m.t_head_dim, m.t_d_ffn, m.t_vocab,
                   m.t_rope_theta, m.t_mrope_sections, cfg->n_ctx, B, wdir.empty() ? nullptr : &st, cfg->talker_q8_0));
     TRYC(init_tfm(e, e->P, Q3G_PRED, m.p_n_layer, m.p_d_model, m.p_n_head, m.p_n_kv_head, m.p_head_dim, m.p_d_ffn,
-                  (m.n_codebooks - 1) * m.codebook_size, m.p_rope_theta, nullptr, 64, B, wdir.empty() ? nullptr : &sp));
+                  (m.n_codebooks - 1) * m.codebook_size, m.p_rope_theta, nullptr, 64, B, wdir.empty() ? nullptr : &sp, cfg->predictor_q8_0));
     // assets (F32 tables like qwen3_assets.gguf: src/assets_manager.rs:212-241; values bf16-representable)
     const uint64_t seed = cfg->synth_seed;
     const float es = 0.05f / Q3_IH4_STD;
@@ -612,7 +624,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
         L.nb = nb;
         HIPC(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
         HIPC(hipEventCreate(&L.ev_begin)); HIPC(hipEventCreate(&L.ev_end));
-        TRYC(alloc_rows(e, L.T, (size_t)nb, m.t_d_model, e->T.a8)); TRYC(alloc_rows(e, L.P, (size_t)2 * nb, m.p_d_model, false));
+        TRYC(alloc_rows(e, L.T, (size_t)nb, m.t_d_model, e->T.a8)); TRYC(alloc_rows(e, L.P, (size_t)2 * nb, m.p_d_model, e->P.a8));
         TRYC(dalloc(e, &L.logits, (size_t)nb * m.t_vocab)); TRYC(dalloc(e, &L.logits_tmp, (size_t)nb * std::max(m.t_vocab, m.t_d_model)));
         TRYC(dalloc(e, &L.fb, (size_t)nb * m.d_embed)); TRYC(dalloc(e, &L.keys, (size_t)nb * (m.codebook_size / 16)));
         TRYC(dalloc(e, &L.row_pos_t, (size_t)nb)); TRYC(dalloc(e, &L.slot_id, (size_t)nb)); TRYC(dalloc(e, &L.perm, (size_t)nb));
@@ -1325,8 +1337,9 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
     {
         const q3tts_model_config& m = e->cfg.model;
         const long long wt = (long long)e->T.weight_bytes;  // includes lm_head
-        const long long wp_layers = (long long)e->P.weight_bytes - 2ll * e->P.head_n * m.p_d_model;
-        const long long head1 = 2ll * m.codebook_size * m.p_d_model, pj = 2ll * m.p_d_model * m.d_embed;
+        const double bpw_p = e->P.q8 ? 1.0625 : 2.0;  // the Predictor's bytes per weight (predictor_q8_0 = 2: Q8_0 blocks)
+        const long long wp_layers = (long long)e->P.weight_bytes - (long long)(bpw_p * (double)((size_t)e->P.head_n * m.p_d_model));
+        const long long head1 = (long long)(bpw_p * (double)((size_t)m.codebook_size * m.p_d_model)), pj = 2ll * m.p_d_model * m.d_embed;
         const long long kv_per_tok = 2ll * m.t_n_layer * 2 * m.t_n_kv_head * m.t_head_dim;
         const long long fixed = wt + (m.n_codebooks - 1) * (wp_layers + head1) + pj;  // one projection GEMM per frame (hidden rows); codes come pre-projected
         e->tm.algo_bytes_per_step = fixed + (steps ? kv_per_tok * (ctx_tokens / steps) : 0);

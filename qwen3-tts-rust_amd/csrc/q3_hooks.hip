@@ -329,6 +329,36 @@ extern "C" int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const float*
     return time_launches(iters, [&] { q3_launch_bgemm8(g, nullptr); }, mean_ms);
 }
 
+// The same launch with the ARGMAX epilogue (the heads of a W8A8 Predictor: predictor_q8_0 = 2): one launch through q3_launch_bgemm8, then the
+// reduction k_pred_next applies to the per-tile keys it leaves — the largest key of the row, first maximum wins — and the winning column per row
+extern "C" int q3tts_k_bgemm_q8a8_argmax(int32_t device, const int8_t* aq, const float* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N,
+                                         const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t* ids_out) {
+    if (!aq || !ad || !q || !d_f16 || !ids_out || B <= 0 || K % 512 || K < 512 || N % 32 || N < 32 || (ssp && ntiles < 1))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8_argmax hook: K % 512 == 0, N % 32 == 0, ids_out");
+    HK(hipSetDevice(device));
+    const int kb = K / 32, nt = N / 16;
+    const size_t B16 = pad16(B); const int rt16 = (int)(B16 / 16);
+    const std::vector<uint8_t> blocks = pack_q8_0(q, d_f16, N, K);
+    std::vector<int8_t> at(B16 * K, 0); std::vector<float> ast((size_t)kb * B16, 0.0f);
+    for (int r = 0; r < B; ++r) {
+        for (int k = 0; k < K; ++k) at[q3_q8_off(r, k, K >> 6)] = aq[(size_t)r * K + k];
+        for (int b = 0; b < kb; ++b) ast[q3_q8_scale_idx(r, b, rt16)] = ad[(size_t)r * kb + b];
+    }
+    DevBuf dx, dxs, dw, dwt, dsc, ds, dk;
+    TRY(dx.put(at.data(), at.size())); TRY(dxs.put(ast.data(), ast.size() * 4)); TRY(dw.put(blocks.data(), blocks.size())); TRY(dwt.alloc((size_t)N * K));
+    TRY(dsc.alloc((size_t)N * kb * 2)); TRY(ds.put(ssp, (size_t)B * std::max(ntiles, 1) * 4)); TRY(dk.alloc((size_t)B * nt * 8));
+    tile_weight(dw, dwt, &dsc, N, K, false);
+    Q3BGemm g{}; g.a = dx; g.ascale = dxs; g.a_rt16 = rt16; g.a_row0 = 0; g.B = B; g.w = dwt; g.wscale = dsc; g.K = K; g.N = N;
+    if (ssp) g.ssp = ds;
+    g.ld_ssp = ntiles; g.ntiles = ntiles; g.d_norm = d_norm; g.eps = eps; g.epi = Q3_EPI_ARGMAX; g.keys = dk; g.key_stride = nt;
+    if (q3_launch_bgemm8(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_q8a8_argmax: shape");
+    HK(hipDeviceSynchronize());
+    std::vector<uint64_t> parts((size_t)B * nt);
+    TRY(dk.get(parts.data(), parts.size() * 8));
+    for (int b = 0; b < B; ++b) { uint64_t m = 0; for (int t = 0; t < nt; ++t) m = std::max(m, parts[(size_t)b * nt + t]); ids_out[b] = q3_argmax_idx(m); }
+    return Q3TTS_OK;
+}
+
 // The vocoder's extras of the decoder GEMM (bias, GELU -> bf16, LayerScale column scale, per-slot row segments, a bf16 copy of the
 // residual result) through one hook: epi 0 (store) / 1 (residual) / 4 (GELU). y0 / y are dense [B][N]; with seg_rows > 0 the kernel
 // works on a buffer of B / seg_rows segments, each preceded by gap_rows sentinel rows that must come back untouched.

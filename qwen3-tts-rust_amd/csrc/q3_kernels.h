@@ -106,7 +106,8 @@ struct Q3BGemm {
     Q3_STAMP_FIELD
 };
 int q3_launch_bgemm(const Q3BGemm& g, hipStream_t s);
-int q3_launch_bgemm8(const Q3BGemm& g, hipStream_t s);   // the same launch in ggml's Q8_0 x Q8_0 arithmetic (STORE / RESID / SWIGLU)
+int q3_launch_bgemm8(const Q3BGemm& g, hipStream_t s);   // the same launch in ggml's Q8_0 x Q8_0 arithmetic (STORE / RESID / SWIGLU / ARGMAX)
+void q3_bgemm8_prepare();  // its kernel attributes, once per device; call outside stream capture
 void q3_bgemm8_pick(const Q3BGemm& g, int* rt, int* nt);
 void q3_bgemm_pick(const Q3BGemm& g, int* rt, int* nt, int* d, int* ntw, int* big);  // the instance q3_launch_bgemm takes for g (no launch)
 void q3_bgemm_force(int rt, int nt);  // tuning only: force a tile instance (0, 0: back to the cost model)
@@ -124,6 +125,7 @@ struct Q3Project {
     float* y; int ldy;
     const float* nw; uint16_t* xb; float* ssp; int ld_ssp;   // xb A-tiled (n_out columns), rows as y
     const float* norm_w; float eps;   // != nullptr: x holds raw rows, the kernel projects rmsnorm(x) * norm_w (normalised while staging)
+    float* xscale; int x_rt16;        // W8A8 Predictor (with nw): xb takes y * nw as Q8_0 blocks (int8 quants + these f32 block scales); n_out % 32 == 0
 };
 int q3_launch_project(const Q3Project& p, hipStream_t s);
 // Workgroup barrier that orders LDS traffic only. __syncthreads() also fences global memory, and on gfx9-family parts loads and stores
@@ -157,6 +159,14 @@ __device__ __forceinline__ void q3_q8_out32(float v, int row, int k, int kpairs,
     const float d = amax / 127.0f, id = d != 0.0f ? 1.0f / d : 0.0f;
     q[q3_q8_off(row, k, kpairs)] = (int8_t)(int)roundf(v * id);
     if ((k & 31) == 0) sc[q3_q8_scale_idx(row, k >> 5, rt16)] = q3_q8_sig11(d);
+}
+// one element of a norm-input row for a W8A8 consumer (q3_norm_out's counterpart): v * nwv into the Q8_0 block of the half wave, the tile's
+// sum of squares of v to *ssp_tile
+__device__ __forceinline__ void q3_norm_out_q8(float v, float nwv, int row, int k, int kpairs, int rt16, int8_t* q, float* sc, float* ssp_tile, bool tile_leader) {
+    q3_q8_out32(v * nwv, row, k, kpairs, rt16, q, sc);
+    float sq = v * v;
+    sq = sq + __shfl_xor(sq, 1); sq = sq + __shfl_xor(sq, 2); sq = sq + __shfl_xor(sq, 4); sq = sq + __shfl_xor(sq, 8);
+    if (tile_leader) *ssp_tile = sq;
 }
 // q3_q8_out2x16: a lane holds columns k0, k0 + 1 (k0 even), 16 consecutive lanes the block
 __device__ __forceinline__ void q3_q8_out2x16(float v0, float v1, int row, int k0, int kpairs, int rt16, int8_t* q, float* sc) {
@@ -270,6 +280,7 @@ struct Q3PredInput {
     const float* pproj0; const float* proj_b; int dp;  // proj(codec0) table [codec0_rows][dp]; bias = proj(0)
     const Q3Slot* slots; const int* row_slot; float* X; float* px; float* fb; int B;
     const float* nw; uint16_t* xb; float* ssp;         // norm inputs of px row B + b (the code row; A-tiled xb, ssp ld dp/16)
+    float* xscale; int x_rt16;                         // W8A8 Predictor: xb takes the row as Q8_0 blocks (int8 quants + these f32 block scales)
 };
 void q3_launch_pred_input(const Q3PredInput& a, hipStream_t s);
 // the frame's first kernel: sampler + code rows (B workgroups) and the H6 tiles of the hidden rows (pj, with norm_w) side by side in one launch
@@ -285,7 +296,7 @@ struct Q3PredNext {
     float* fb; const float* tts_pad; float* xT; int* row_pos_t;
     const float* pproj_q; const float* proj_b; int dp; float* px;  // q < ncb-1: px[b] = proj(codec_q[code]) from the table
     const float* nw; uint16_t* xb; float* ssp;  // norm inputs of the row just written: px[b] (Predictor layer 0) or, last, xT[b] (Talker layer 0)
-    float* xscale; int x_rt16;                  // last pass with a W8A8 Talker: xb then takes the row as Q8_0 blocks (int8 quants + these f32 block scales)
+    float* xscale; int x_rt16;                  // the row's consumer is W8A8 (the Predictor for q < ncb - 1, the Talker for the last pass): xb then takes the row as Q8_0 blocks (int8 quants + these f32 block scales)
     Q3_STAMP_FIELD
 };
 void q3_launch_pred_next(const Q3PredNext& a, hipStream_t s);

@@ -724,7 +724,8 @@ __global__ __launch_bounds__((R + 1) * 64) void k_attend_small(Q3Attend a) {
     }
     const float ov0 = (((r0[0] + r0[1]) + r0[2]) + r0[3]) / l, ov1 = (((r1[0] + r1[1]) + r1[2]) + r1[3]) / l;
     const int d0 = 2 * lane;
-    if (a.out_bf16) *(uint32_t*)((uint16_t*)a.out + q3_atile_off(row, hq * hd + d0, (a.Hq * hd) >> 5)) = (uint32_t)q3_bf16(ov0) | ((uint32_t)q3_bf16(ov1) << 16);
+    if (a.out_bf16 == 2) q3_q8_out2x16(ov0, ov1, row, hq * hd + d0, (a.Hq * hd) >> 6, a.out_rt16, (int8_t*)a.out, a.out_scale);  // W8A8: Q8_0 blocks (16 lanes x 2 dims; the whole query wave is here)
+    else if (a.out_bf16) *(uint32_t*)((uint16_t*)a.out + q3_atile_off(row, hq * hd + d0, (a.Hq * hd) >> 5)) = (uint32_t)q3_bf16(ov0) | ((uint32_t)q3_bf16(ov1) << 16);
     else *(float2*)(a.out + (size_t)row * a.ldo + (size_t)hq * hd + d0) = make_float2(ov0, ov1);
 #ifdef Q3_STAMPS
     Q3_STAMP(a, 4);
@@ -807,7 +808,12 @@ __global__ __launch_bounds__(256) void k_attend_pair(Q3Attend a) {
             out8[i] = uu == 0 ? r : out8[i] + r;
         }
     }
-    if (kg == 0) {
+    if (a.out_bf16 == 2) {  // W8A8: Q8_0 blocks — a lane owns 8 consecutive dims, lanes dl ^ 1, dl ^ 2 the rest of its block (every lane group holds the same sums)
+        float ov8[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ov8[i] = out8[i] / l;
+        q3_q8_out8x4(ov8, row, (g * R + hh) * hd + dl * 8, (a.Hq * hd) >> 6, a.out_rt16, (int8_t*)a.out, a.out_scale, kg == 0);
+    } else if (kg == 0) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int d = dl * 8 + i;
@@ -1248,7 +1254,8 @@ __device__ void pred_input_row(const Q3PredInput& a, int b, int code0) {
             const int i = i0 + tid + u * 256;
             if (i < a.dp) {  // (uniform per wave: dp % 256 == 0)
                 a.px[(size_t)r1 * a.dp + i] = pv[u];
-                q3_norm_out(pv[u], wv[u], a.xb + q3_atile_off(r1, i, a.dp >> 5), a.ssp + (size_t)r1 * (a.dp >> 4) + (i >> 4), (i & 15) == 0);
+                if (a.xscale) q3_norm_out_q8(pv[u], wv[u], r1, i, a.dp >> 6, a.x_rt16, (int8_t*)a.xb, a.xscale, a.ssp + (size_t)r1 * (a.dp >> 4) + (i >> 4), (i & 15) == 0);
+                else q3_norm_out(pv[u], wv[u], a.xb + q3_atile_off(r1, i, a.dp >> 5), a.ssp + (size_t)r1 * (a.dp >> 4) + (i >> 4), (i & 15) == 0);
             }
         }
     }
@@ -1272,20 +1279,27 @@ void q3_launch_pred_input(const Q3PredInput& a, hipStream_t s) { hipLaunchKernel
 // the canonical 64-lane chain (the same operations pred_input_row used to store as X), so that the projection
 // does not wait for another kernel's normalised copy.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int PJ_KC = 64, PJ_LD = PJ_KC + 4, PJ_LDS_FLOATS = 4 * 16 * PJ_LD;
+constexpr int PJ_KC = 64, PJ_LD = PJ_KC + 4, PJ_LDS_FLOATS = 4 * 16 * PJ_LD, PJ_LDS_FLOATS_Q8 = 6 * 16 * PJ_LD;
+// NO = outputs per thread: 1 — the 16 x 16 tile above; 2 — a W8A8 consumer (p.xscale): a thread owns outputs o and o + 16 of a 16 x 32 tile
+// (two independent chains, each the same sequence as before), so that a 16-lane group holds one whole Q8_0 block of y * nw
+template <int NO>
 __device__ void project_tile(const Q3Project& p, int bx, int by, float* lds) {
     constexpr int KC = PJ_KC, LD = PJ_LD;
-    float* ws = lds; float* xs = lds + 2 * 16 * LD;  // [2][16 * LD] each
+    float* ws = lds; float* xs = lds + 2 * NO * 16 * LD;  // ws [2][NO * 16 * LD], xs [2][16 * LD]
     __shared__ float rinv16[16];
     const int tid = threadIdx.x, oc = tid & 15, rr = tid >> 4;
-    const int o = bx * 16 + oc, row = by * 16 + rr;
-    // staging role: thread t loads 4 consecutive inputs (t & 15) of weight row / activation row (t >> 4)
-    const float* wsrc = p.w + (size_t)(bx * 16 + rr) * p.n_in + 4 * oc;
+    const int o = bx * (16 * NO) + oc, row = by * 16 + rr;
+    // staging role: thread t loads 4 consecutive inputs (t & 15) of weight row(s) / activation row (t >> 4)
+    const float* wsrc = p.w + (size_t)(bx * (16 * NO) + rr) * p.n_in + 4 * oc;
     const float* xsrc = p.x + (size_t)min(by * 16 + rr, p.rows - 1) * p.ldx + 4 * oc;
     const float* nsrc = p.norm_w ? p.norm_w + 4 * oc : nullptr;
-    float sum = p.bias[o];
+    float sum[NO];
+#pragma unroll
+    for (int j = 0; j < NO; ++j) sum[j] = p.bias[o + 16 * j];
     const int nch = p.n_in / KC;
-    float4 wv = *(const float4*)wsrc, xv = *(const float4*)xsrc, nv = nsrc ? *(const float4*)nsrc : float4{1.0f, 1.0f, 1.0f, 1.0f};
+    float4 wv[NO], xv = *(const float4*)xsrc, nv = nsrc ? *(const float4*)nsrc : float4{1.0f, 1.0f, 1.0f, 1.0f};
+#pragma unroll
+    for (int j = 0; j < NO; ++j) wv[j] = *(const float4*)(wsrc + (size_t)16 * j * p.n_in);
     float rinv = 1.0f;
     if (nsrc) {  // (uniform) wave w owns rows 4w .. 4w + 3 of the tile: four chains side by side, lane c takes the float4 chunks c, c + 64, ...
         const int wave = tid >> 6, lane = tid & 63;
@@ -1306,40 +1320,62 @@ __device__ void project_tile(const Q3Project& p, int bx, int by, float* lds) {
         rinv = rinv16[rr];
     }
     for (int c = 0; c < nch; ++c) {
-        float* wl = ws + (c & 1) * 16 * LD; float* xl = xs + (c & 1) * 16 * LD;
+        float* wl = ws + (c & 1) * (NO * 16 * LD); float* xl = xs + (c & 1) * 16 * LD;
         if (nsrc) { xv.x = (xv.x * rinv) * nv.x; xv.y = (xv.y * rinv) * nv.y; xv.z = (xv.z * rinv) * nv.z; xv.w = (xv.w * rinv) * nv.w; }
-        *(float4*)(wl + rr * LD + 4 * oc) = wv; *(float4*)(xl + rr * LD + 4 * oc) = xv;
+#pragma unroll
+        for (int j = 0; j < NO; ++j) *(float4*)(wl + (rr + 16 * j) * LD + 4 * oc) = wv[j];
+        *(float4*)(xl + rr * LD + 4 * oc) = xv;
         if (c + 1 < nch) {
-            wv = *(const float4*)(wsrc + (c + 1) * KC); xv = *(const float4*)(xsrc + (c + 1) * KC);
+#pragma unroll
+            for (int j = 0; j < NO; ++j) wv[j] = *(const float4*)(wsrc + (size_t)16 * j * p.n_in + (c + 1) * KC);
+            xv = *(const float4*)(xsrc + (c + 1) * KC);
             if (nsrc) nv = *(const float4*)(nsrc + (c + 1) * KC);
         }
         __syncthreads();  // (two buffers: the stores of chunk c + 2 come after the barrier of chunk c + 1, which every reader of chunk c has passed)
-        const float* wr = wl + oc * LD; const float* xr = xl + rr * LD;
+        const float* xr = xl + rr * LD;
 #pragma unroll
         for (int k = 0; k < KC; k += 4) {
-            const float4 a = *(const float4*)(xr + k), w4 = *(const float4*)(wr + k);
-            sum += a.x * w4.x; sum += a.y * w4.y; sum += a.z * w4.z; sum += a.w * w4.w;
+            const float4 a = *(const float4*)(xr + k);
+#pragma unroll
+            for (int j = 0; j < NO; ++j) {
+                const float4 w4 = *(const float4*)(wl + (oc + 16 * j) * LD + k);
+                sum[j] += a.x * w4.x; sum[j] += a.y * w4.y; sum[j] += a.z * w4.z; sum[j] += a.w * w4.w;
+            }
         }
     }
     const bool live = row < p.rows;
-    if (live) p.y[(size_t)row * p.ldy + o] = sum;
+#pragma unroll
+    for (int j = 0; j < NO; ++j)
+        if (live) p.y[(size_t)row * p.ldy + o + 16 * j] = sum[j];
     if (p.nw) {
-        uint16_t hb = q3_bf16(sum * p.nw[o]);
-        float sq = sum * sum;
-        sq = sq + __shfl_xor(sq, 1); sq = sq + __shfl_xor(sq, 2); sq = sq + __shfl_xor(sq, 4); sq = sq + __shfl_xor(sq, 8);
-        if (live) {
-            p.xb[q3_atile_off(row, o, p.n_out >> 5)] = hb;
-            if (oc == 0) p.ssp[(size_t)row * p.ld_ssp + (o >> 4)] = sq;
+        float sq[NO];
+#pragma unroll
+        for (int j = 0; j < NO; ++j) {
+            sq[j] = sum[j] * sum[j];
+            sq[j] = sq[j] + __shfl_xor(sq[j], 1); sq[j] = sq[j] + __shfl_xor(sq[j], 2); sq[j] = sq[j] + __shfl_xor(sq[j], 4); sq[j] = sq[j] + __shfl_xor(sq[j], 8);
+            if (live && oc == 0) p.ssp[(size_t)row * p.ld_ssp + ((o + 16 * j) >> 4)] = sq[j];
         }
+        if constexpr (NO == 2) {  // the block = the 32 outputs of this row's 16 lanes: ggml's quantiser on v = y * nw
+            const float u0 = sum[0] * p.nw[o], u1 = sum[1] * p.nw[o + 16];
+            float amax = fmaxf(fabsf(u0), fabsf(u1));
+#pragma unroll
+            for (int m = 1; m <= 8; m <<= 1) amax = fmaxf(amax, __shfl_xor(amax, m));
+            const float d = amax / 127.0f, id = d != 0.0f ? 1.0f / d : 0.0f;
+            if (live) {
+                ((int8_t*)p.xb)[q3_q8_off(row, o, p.n_out >> 6)] = (int8_t)(int)roundf(u0 * id);
+                ((int8_t*)p.xb)[q3_q8_off(row, o + 16, p.n_out >> 6)] = (int8_t)(int)roundf(u1 * id);
+                if (oc == 0) p.xscale[q3_q8_scale_idx(row, o >> 5, p.x_rt16)] = q3_q8_sig11(d);
+            }
+        } else if (live) p.xb[q3_atile_off(row, o, p.n_out >> 5)] = q3_bf16(sum[0] * p.nw[o]);
     }
 }
 __global__ __launch_bounds__(256) void k_project(Q3Project p) {
     __shared__ __attribute__((aligned(16))) float lds[PJ_LDS_FLOATS];
-    project_tile(p, blockIdx.x, blockIdx.y, lds);
+    project_tile<1>(p, blockIdx.x, blockIdx.y, lds);
 }
-static bool project_ok(const Q3Project& p) { return p.rows >= 1 && p.n_out % 16 == 0 && p.n_in % 64 == 0 && p.ldx % 4 == 0; }
+static bool project_ok(const Q3Project& p) { return p.rows >= 1 && p.n_out % 16 == 0 && p.n_in % 64 == 0 && p.ldx % 4 == 0 && !(p.xscale && (!p.nw || p.n_out % 32 || p.x_rt16 < 1)); }
 int q3_launch_project(const Q3Project& p, hipStream_t s) {
-    if (!project_ok(p)) return -1;
+    if (!project_ok(p) || p.xscale) return -1;  // (the Q8_0 output exists in the frame's first launch only: q3_launch_sample_input)
     hipLaunchKernelGGL(k_project, dim3(p.n_out / 16, (p.rows + 15) / 16), dim3(256), 0, s, p);
     return 0;
 }
@@ -1347,13 +1383,14 @@ int q3_launch_project(const Q3Project& p, hipStream_t s) {
 // the frame's first launch, two kinds of workgroup side by side (they touch disjoint data, so neither waits for the other):
 //  [0, B)   H4/H5 (sample, EOS, bookkeeping) and, for rows that go on, the code row of the Predictor's pass A and the feedback start
 //  [B, ...) H6 for the hidden rows, normalised in the tile (project_tile with norm_w)
-static_assert(PJ_LDS_FLOATS * sizeof(float) <= SAMP_MAX * sizeof(unsigned long long), "the projection tile stages through the sampler's key array");
+static_assert(PJ_LDS_FLOATS_Q8 * sizeof(float) <= SAMP_MAX * sizeof(unsigned long long), "the projection tile stages through the sampler's key array");
 __global__ __launch_bounds__(256) void k_sample_input(Q3Sample a, Q3PredInput p, Q3Project pj) {
     __shared__ __attribute__((aligned(16))) unsigned long long keys[SAMP_MAX];
     __shared__ float probs[SAMP_MAX];
     if ((int)blockIdx.x >= a.B) {  // (uniform over the workgroup)
-        const int t = blockIdx.x - a.B, nx = pj.n_out >> 4;
-        project_tile(pj, t % nx, t / nx, (float*)keys);
+        const int t = blockIdx.x - a.B;
+        if (pj.xscale) { const int nx = pj.n_out >> 5; project_tile<2>(pj, t % nx, t / nx, (float*)keys); }   // (uniform) W8A8 Predictor: 16 x 32 tiles
+        else { const int nx = pj.n_out >> 4; project_tile<1>(pj, t % nx, t / nx, (float*)keys); }
         return;
     }
     const int code0 = sample_frame(a, blockIdx.x, keys, probs);  // (uniform over the workgroup)
@@ -1362,7 +1399,7 @@ __global__ __launch_bounds__(256) void k_sample_input(Q3Sample a, Q3PredInput p,
 }
 int q3_launch_sample_input(const Q3Sample& a, const Q3PredInput& p, const Q3Project& pj, hipStream_t s) {
     if (!project_ok(pj) || !pj.norm_w) return -1;
-    hipLaunchKernelGGL(k_sample_input, dim3(a.B + (pj.n_out / 16) * ((pj.rows + 15) / 16)), dim3(256), 0, s, a, p, pj);
+    hipLaunchKernelGGL(k_sample_input, dim3(a.B + (pj.n_out / (pj.xscale ? 32 : 16)) * ((pj.rows + 15) / 16)), dim3(256), 0, s, a, p, pj);
     return 0;
 }
 
@@ -1416,13 +1453,9 @@ __global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
             if (!last) a.fb[(size_t)b * d + i] = f;
             else {  // the Talker's next input row and its norm inputs for layer 0
                 f = f + tp[u]; a.xT[(size_t)b * d + i] = f;
-                if (a.xscale) {  // W8A8 Talker: the row as Q8_0 blocks (a half wave = 32 consecutive columns = one block)
-                    q3_q8_out32(f * nv[u], b, i, d >> 6, a.x_rt16, (int8_t*)a.xb, a.xscale);
-                    float sq = f * f;
-                    sq = sq + __shfl_xor(sq, 1); sq = sq + __shfl_xor(sq, 2); sq = sq + __shfl_xor(sq, 4); sq = sq + __shfl_xor(sq, 8);
-                    if ((i & 15) == 0) a.ssp[(size_t)b * (d >> 4) + (i >> 4)] = sq;
-                } else
-                q3_norm_out(f, nv[u], a.xb + q3_atile_off(b, i, d >> 5), a.ssp + (size_t)b * (d >> 4) + (i >> 4), (i & 15) == 0);
+                // W8A8 consumer: the row as Q8_0 blocks (a half wave = 32 consecutive columns = one block)
+                if (a.xscale) q3_norm_out_q8(f, nv[u], b, i, d >> 6, a.x_rt16, (int8_t*)a.xb, a.xscale, a.ssp + (size_t)b * (d >> 4) + (i >> 4), (i & 15) == 0);
+                else q3_norm_out(f, nv[u], a.xb + q3_atile_off(b, i, d >> 5), a.ssp + (size_t)b * (d >> 4) + (i >> 4), (i & 15) == 0);
             }
         }
     }
@@ -1432,13 +1465,15 @@ __global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
             const int i = tid + u * 256;
             if (i < a.dp) {
                 a.px[(size_t)b * a.dp + i] = pv[u];
-                q3_norm_out(pv[u], wv[u], a.xb + q3_atile_off(b, i, a.dp >> 5), a.ssp + (size_t)b * (a.dp >> 4) + (i >> 4), (i & 15) == 0);
+                if (a.xscale) q3_norm_out_q8(pv[u], wv[u], b, i, a.dp >> 6, a.x_rt16, (int8_t*)a.xb, a.xscale, a.ssp + (size_t)b * (a.dp >> 4) + (i >> 4), (i & 15) == 0);
+                else q3_norm_out(pv[u], wv[u], a.xb + q3_atile_off(b, i, a.dp >> 5), a.ssp + (size_t)b * (a.dp >> 4) + (i >> 4), (i & 15) == 0);
             }
         }
         for (int i = tid + NP * 256; i < a.dp; i += 256) {  // (dp > 1024: not a shipped shape)
             const float v = pr[i];
             a.px[(size_t)b * a.dp + i] = v;
-            q3_norm_out(v, a.nw[i], a.xb + q3_atile_off(b, i, a.dp >> 5), a.ssp + (size_t)b * (a.dp >> 4) + (i >> 4), (i & 15) == 0);
+            if (a.xscale) q3_norm_out_q8(v, a.nw[i], b, i, a.dp >> 6, a.x_rt16, (int8_t*)a.xb, a.xscale, a.ssp + (size_t)b * (a.dp >> 4) + (i >> 4), (i & 15) == 0);
+            else q3_norm_out(v, a.nw[i], a.xb + q3_atile_off(b, i, a.dp >> 5), a.ssp + (size_t)b * (a.dp >> 4) + (i >> 4), (i & 15) == 0);
         }
     }
     if (last) {

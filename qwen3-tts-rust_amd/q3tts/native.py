@@ -570,6 +570,23 @@ def k_bgemm_q8(xb, q, d16, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=
     return dict(y=y, yb=yb, ssp_out=sso, keys=keys, ms=ms.value)
 
 
+def k_bgemm_q8a8_argmax(aq, ad, q, d16, ssp, d_norm, eps, device=0):
+    """The W8A8 GEMM with the ARGMAX epilogue and k_pred_next's key reduction (q3tts_k_bgemm_q8a8_argmax): the winning column of every row.
+    aq int8 [B][K], ad f32 [B][K/32], weights q int8 [N][K] / d16 f16 bits [N][K/32]; ssp [B][ntiles] or None (no row scale)."""
+    lib = _abi.load_library()
+    aq = np.ascontiguousarray(aq, dtype=np.int8); ad = np.ascontiguousarray(ad, dtype=np.float32)
+    q = np.ascontiguousarray(q, dtype=np.int8); d16 = np.ascontiguousarray(d16, dtype=np.uint16)
+    B, K = aq.shape
+    N = q.shape[0]
+    sp = None if ssp is None else np.ascontiguousarray(ssp, dtype=np.float32)
+    ids = np.full(B, -1, dtype=np.int32)
+    rc = lib.q3tts_k_bgemm_q8a8_argmax(device, aq.ctypes.data, ad.ctypes.data, B, K, q.ctypes.data, d16.ctypes.data, N, None if sp is None else sp.ctypes.data,
+                                       0 if sp is None else sp.shape[1], d_norm, eps, ids.ctypes.data)
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_bgemm_q8a8_argmax failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return ids
+
+
 def k_bgemm_q8a8(aq, ad, q, d16, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=0, iters=0):
     """The decoder's GEMM in ggml's Q8_0 x Q8_0 arithmetic (q3tts_k_bgemm_q8a8): activations aq int8 [B][K] + their block scales ad [B][K/32], weights q / d16.
     ad: f32 (what the W8A8 producers store: d rounded to f16's 11-bit significand, kept in f32; yd comes back as f32) or f16 bit patterns
