@@ -14,6 +14,7 @@
 #include <cmath>
 #include <map>
 #include <set>
+#include <tuple>
 #include <vector>
 
 #include "q3_engine.h"
@@ -36,9 +37,14 @@ struct VCall {  // passed by value to the kernels of one batched call
 };
 
 struct VConv { int ntap = 1, dil = 1, cin = 0, nout = 0, bias_n = 0; uint16_t* w = nullptr; float* b = nullptr; };
+// rows of a GEMM operand or result: row (s, t) at p + s * stride + off + t * (row width), in elements; bf16: the elements are bf16
+struct VRows { float* p = nullptr; size_t stride = 0; int off = 0; int bf16 = 0;
+               VRows as_bf16() const { return {p, stride, off, 1}; } };
 // work buffer of a conv input: [VOC_MAX_NS][H + Tcap][C] (slot-major) + per-slot history [B][H][C]
 struct VBuf { float* p = nullptr; float* hist = nullptr; int H = 0, C = 0, Tcap = 0; int bf16 = 0;  // bf16: elements are bf16 (GEMM-only inputs)
-              size_t stride() const { return (size_t)(H + Tcap) * C; } };  // in elements
+              size_t stride() const { return (size_t)(H + Tcap) * C; }  // in elements
+              VRows rows() const { return {p, stride(), H * C, bf16}; }  // a call's rows, past the history rows
+              static VRows flat(float* q, int T, int C) { return {q, (size_t)T * C, 0, 0}; } };  // contiguous scratch [slot][T][C]
 
 struct VLayer { float *in_norm, *post_norm, *ls_attn, *ls_mlp; VConv q, k, v, o, gate, up, down;
                 uint4 *qkv_t = nullptr, *o_t = nullptr, *gu_t = nullptr, *down_t = nullptr;  // the four projections in the decoder GEMM's tiled layout (tfm_bg)
@@ -47,6 +53,27 @@ struct VUp { VConv ct, pw1, pw2; float *dw_w, *dw_b, *ln_w, *ln_b, *gamma; int r
              uint4 *ct_t = nullptr, *pw1_t = nullptr, *pw2_t = nullptr; };  // tiled copies for k_bgemm (up_bg)
 struct VRes { float *ea, *ib, *ea2, *ib2; VConv c1, c2; VBuf c1_in; };
 struct VBlk { float *ea, *ib; VConv ct; VRes res[3]; int r, cin, cout; VBuf ct_in; };
+
+// "Polite" launches (DESIGN.md §16): while the decoder is running beside it, every long-lived vocoder workgroup is ONE per CU (>= 81 KiB of LDS
+// declared: a second cannot join it) with 4 waves of <= 208 VGPRs, so that 79 KiB of LDS and >= 304 VGPRs per SIMD stay free for the decoder's
+// 8-wave workgroups — which otherwise wait, launch after launch, for a vocoder workgroup to retire on every CU (tools/coresidency_bench.hip:
+// 3.7 us per launch alone, 24-81 us beside workgroups of 30-80 us that leave no room, 3.6-4.0 beside one that does). The vocoder itself is
+// slower that way, which costs nothing while it hides behind the decoder; a call that has the GPU to itself (a draining batch's tail, the
+// stand-alone hooks) and small calls (short-lived workgroups anyway) are launched greedily. The engine sets the mode per call
+// (q3_voc_decode_batch); Q3TTS_VOC_POLITE=0 / 1 forces never / always. Same bits either way (a launch parameter and a tile choice).
+//
+// VLaunch: that mode and the other launch switches of ONE vocoder call, read once in voc_call() (the tests flip them between calls of one
+// process) and handed to every launcher; the call's captured graph is cached under the same value, so launches and key cannot disagree.
+struct VLaunch {  // (DESIGN.md's switch table says what each one selects)
+    bool polite = false;                                    // Q3TTS_VOC_POLITE=0 / 1, else the caller's "beside the decoder and >= 16 slots wide"
+    bool no_ring = false, no_tap = false, no_fuse = false;  // Q3TTS_VOC_NORING / _NOTAP / _NOFUSE = 1
+    bool out_old = false, attn_old = false;                 // Q3TTS_VOC_OUT_OLD set, Q3TTS_VOC_ATTN_OLD=1
+    long tap_min = 128;                                     // Q3TTS_VOC_TAP_MIN: the least number of workgroups for which k_vconv_tap is taken (vgemm)
+    auto tie() const { return std::tie(polite, no_ring, no_tap, tap_min, no_fuse, out_old, attn_old); }
+    bool operator<(const VLaunch& o) const { return tie() < o.tie(); }
+};
+typedef std::tuple<int, int, VLaunch> VCallKey;  // (slots, frames, switches)
+static size_t voc_lds_floor(const VLaunch& vl, size_t lds) { return vl.polite ? std::max(lds, (size_t)81 * 1024) : lds; }
 
 // Test taps (q3tts_k_vocoder_taps): while a sink is set, voc_call_body copies named intermediate tensors of slot 0 to the caller's host
 // buffer between its launches. nullptr in every other call: no launch, copy or branch on the device changes.
@@ -75,25 +102,15 @@ struct Q3Voc {
     std::vector<int> frames_done, last_flag;
     VCall* call_dev = nullptr;                   // the running call's slot / position table (kernels read it; voc_call uploads it in stream order)
     VCall* call_host = nullptr; hipEvent_t call_ev[16] = {}; unsigned call_i = 0;  // pinned staging ring of the uploads + "copy done" events
-    std::map<unsigned long long, hipGraphExec_t> call_graphs;  // one captured call per (slots, frames, launch mode, switches): voc_call
-    std::set<unsigned long long> call_seen;
+    std::map<VCallKey, hipGraphExec_t> call_graphs;  // one captured call per (slots, frames, launch switches): voc_call
+    std::set<VCallKey> call_seen;
     std::vector<void*> allocs;
 };
 
-// "Polite" launches (DESIGN.md §16): while the decoder is running beside it, every long-lived vocoder workgroup is ONE per CU (>= 81 KiB of LDS
-// declared: a second cannot join it) with 4 waves of <= 208 VGPRs, so that 79 KiB of LDS and >= 304 VGPRs per SIMD stay free for the decoder's
-// 8-wave workgroups — which otherwise wait, launch after launch, for a vocoder workgroup to retire on every CU (tools/coresidency_bench.hip:
-// 3.7 us per launch alone, 24-81 us beside workgroups of 30-80 us that leave no room, 3.6-4.0 beside one that does). The vocoder itself is
-// slower that way, which costs nothing while it hides behind the decoder; a call that has the GPU to itself (a draining batch's tail, the
-// stand-alone hooks) and small calls (short-lived workgroups anyway) are launched greedily. The engine sets the mode per call
-// (q3_voc_decode_batch); Q3TTS_VOC_POLITE=0 / 1 forces never / always. Same bits either way (a launch parameter and a tile choice).
-static thread_local bool g_voc_polite_now = false;   // (one host thread drives an engine: q3tts_node_* runs one per device)
-static int voc_polite_env() { const char* ev = getenv("Q3TTS_VOC_POLITE"); return ev ? (atoi(ev) ? 1 : 0) : -1; }  // (read per launch: the tests compare both modes in one process)
-static bool voc_polite() { const int ev = voc_polite_env(); return ev >= 0 ? ev == 1 : g_voc_polite_now; }
-static size_t voc_lds_floor(size_t lds) { return voc_polite() ? std::max(lds, (size_t)81 * 1024) : lds; }
 // ------------------------------------------------------------------------------------------------------------------
 // kernels
 // ------------------------------------------------------------------------------------------------------------------
+enum VEpi { VEPI_STORE = 0, VEPI_SCALE_ADD = 1, VEPI_ADD = 2, VEPI_GELU = 3, VEPI_SWIGLU = 4 };  // (the kernels compare g.epi with the values)
 struct VGemm {
     const float* x; size_t x_stride; int x_off;   // row (s, t) tap 0 shift 0 at x + s*x_stride + x_off + t*cin
     int T, M;                                     // rows per slot, total rows = ns*T
@@ -101,7 +118,7 @@ struct VGemm {
     float* y; size_t y_stride; int y_off;         // out row (s,t) at y + s*y_stride + y_off + t*nout (t*nout/2 for epi 4)
     const float* scale;                           // epilogue 1: y += scale[n % scale_n] * (acc + bias)
     int scale_n;
-    int epi;                                      // 0 store, 1 y += scale*(.), 2 y += (.), 3 gelu, 4 swiglu (16-column tiles alternate gate / up)
+    int epi;                                      // VEpi: 0 store, 1 y += scale*(.), 2 y += (.), 3 gelu, 4 swiglu (16-column tiles alternate gate / up)
     int store;                                    // 0: the primary output is not written (only y2 is wanted)
     int a_bf16;                                   // x holds bf16 (the value a f32 source would be rounded to anyway); strides in elements
     int y_bf16;                                   // epi 4 only: write the SwiGLU result as bf16 (it only ever feeds a GEMM)
@@ -428,7 +445,7 @@ __device__ __forceinline__ void vepi_tile(const VGemm& g, const float* Ot, const
 // lane l FETCHES the chunk that belongs there: row l >> 2 of its 16-row group, chunk (l & 3) ^ VR_SW(row).
 // Accumulation order per output element is unchanged (32-wide K steps ascending over taps, then channels).
 // VR_NS stages (4: three in flight)
-#ifdef Q3_VOC_STAMPS  // experiment builds (tools/r3_voc_stamps.sh): s_memrealtime (100 MHz) stamps of three workgroups of the NJ = 3 instance
+#ifdef Q3_VOC_STAMPS  // experiment builds (tools/build_stamps.sh voc): s_memrealtime (100 MHz) stamps of three workgroups of the NJ = 3 instance
 __device__ unsigned long long g_ring_stamps[4][8];
 #define VG_STAMP(i_) do { if (NJ == 3 && vg_wg >= 0 && threadIdx.x == 0) g_ring_stamps[vg_wg][i_] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
@@ -551,16 +568,16 @@ __global__ __launch_bounds__(256) void k_vgemm_ring(VGemm g) {
 #endif
 }
 template <int NJ, int NS>
-static void launch_vgemm_ring_t(hipStream_t s, const VGemm& g, dim3 grid) {
+static void launch_vgemm_ring_t(const VLaunch& vl, hipStream_t s, const VGemm& g, dim3 grid) {
     constexpr size_t lds_ring = (size_t)NS * (128 + NJ * 32) * 64, lds_out = (size_t)128 * (NJ * 32 + 4) * 4 + 128 * 4, lds = lds_ring > lds_out ? lds_ring : lds_out;
     static Q3PerDevice pd;
-    const size_t ldsp = voc_lds_floor(lds);
+    const size_t ldsp = voc_lds_floor(vl, lds);
     pd.ensure(ldsp, [&]() { hipFuncSetAttribute((const void*)k_vgemm_ring<NJ, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp); });
     hipLaunchKernelGGL((k_vgemm_ring<NJ, NS>), grid, dim3(256), ldsp, s, g);
 }
 template <int NJ>
-static void launch_vgemm_ring(hipStream_t s, const VGemm& g, dim3 grid) {
-    launch_vgemm_ring_t<NJ, 4>(s, g, grid);  // (six stages for the one-workgroup-per-CU launches beside the decoder: 107 against 104 us — depth is not their limit)
+static void launch_vgemm_ring(const VLaunch& vl, hipStream_t s, const VGemm& g, dim3 grid) {
+    launch_vgemm_ring_t<NJ, 4>(vl, s, g, grid);  // (six stages for the one-workgroup-per-CU launches beside the decoder: 107 against 104 us — depth is not their limit)
 }
 
 // The wide 7-tap convolutions of the decoder blocks (768 / 384 channels: 40 % of a batched call) on a tile that keeps its INPUT ROWS in LDS
@@ -714,11 +731,11 @@ __global__ __launch_bounds__(256 * NSUB) void k_vconv_tap(VGemm g) {
     else vepi_tile<BN, ROWS, 64 * NW, false>(g, Ot, rinfo, n0);
 }
 template <int NSUB>
-static void launch_vconv_tap(hipStream_t s, const VGemm& g) {
+static void launch_vconv_tap(const VLaunch& vl, hipStream_t s, const VGemm& g) {
     constexpr int NS = NSUB == 2 ? 12 : 8;
     const int halo = (g.c.ntap - 1) * g.c.dil, RA = (128 + halo + 15) & ~15;
     const size_t lds_main = (size_t)2 * NSUB * RA * 64 + (size_t)NS * 128 * 64, lds_out = (size_t)128 * NSUB * (128 + 4) * 4 + 128 * NSUB * 4;
-    const size_t lds = voc_lds_floor(std::max(lds_main, lds_out));
+    const size_t lds = voc_lds_floor(vl, std::max(lds_main, lds_out));
     static Q3PerDevice pd;
     pd.ensure(1, []() { hipFuncSetAttribute((const void*)k_vconv_tap<7, NSUB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); });
     const int tps = (g.T + 127) / 128, nsub = (g.M / g.T) * tps;
@@ -1546,90 +1563,81 @@ int q3_voc_reset(q3tts_engine* e, int slot) {
     return Q3TTS_OK;
 }
 
-struct VSnake { float* y2 = nullptr; size_t stride = 0; int off = 0; const float* ea = nullptr; const float* ib = nullptr; int n = 1; int bf16 = 0; };
-static VSnake snake_into(const VBuf& dst, const float* ea, const float* ib, int C) {
-    VSnake k; k.y2 = dst.p; k.stride = dst.stride(); k.off = dst.H * dst.C; k.ea = ea; k.ib = ib; k.n = C; k.bf16 = dst.bf16; return k;
-}
+// SnakeBeta(v) with the NEXT layer's parameters (C channels) as a GEMM's second output, written straight into that layer's conv-input rows
+struct VSnake { VRows to; const float* ea = nullptr; const float* ib = nullptr; int n = 1; };
+static VSnake snake_into(const VBuf& dst, const float* ea, const float* ib, int C) { return {dst.rows(), ea, ib, C}; }
+// the optional parts of a vgemm call
+struct VOpt {
+    const float* scale = nullptr; int scale_n = 1;  // VEPI_SCALE_ADD: the LayerScale vector and its modulus
+    VSnake snake;                                   // second output (to.p == nullptr: none)
+    int store = 1;                                  // 0: the primary output is not written (only the SnakeBeta output is wanted)
+    VOpt& layer_scale(const float* v, int n) { scale = v; scale_n = n; return *this; }
+    VOpt& snake_to(const VSnake& k) { snake = k; return *this; }
+    VOpt& no_store() { store = 0; return *this; }
+};
 // the wide 7-tap convolutions run their K steps chunk by chunk (vstep), whichever kernel serves them
 static bool vconv_chunked(const VConv& c) { return c.ntap == 7 && c.cin % 64 == 0 && c.cin >= 256; }
-// Q3TTS_VOC_NOTAP=1: those convolutions on the ring / register-staged GEMMs instead of k_vconv_tap (same bits; A/B runs and tests)
-static bool voc_tap() { const char* ev = getenv("Q3TTS_VOC_NOTAP"); return !(ev && atoi(ev)); }
-// fewer workgroups than this (a draining batch, a single stream) leave most CUs idle under 256-row tiles: the finer 128 x 128 tiles serve them.
-// Q3TTS_VOC_TAP_MIN overrides it (tests force k_vconv_tap onto one-slot calls with 1)
-static long voc_tap_min() { const char* ev = getenv("Q3TTS_VOC_TAP_MIN"); return ev ? atol(ev) : 128; }
-// Q3TTS_VOC_NORING=1: the register-staged kernel for bf16 A as well (A/B runs and the tests that compare the two)
-static bool voc_ring() { const char* ev = getenv("Q3TTS_VOC_NORING"); return !(ev && atoi(ev)); }
-// (its epilogue moves 4 columns at a time: nout and every row start are multiples of 4 elements for all convolutions of the vocoder)
-static bool voc_ring_ok(const VGemm& g) { return voc_ring() && g.c.nout % 4 == 0 && g.y_off % 4 == 0 && g.y_stride % 4 == 0 && g.y2_off % 4 == 0 && g.y2_stride % 4 == 0; }
-static void vgemm(hipStream_t s, const VConv& c, const float* x, size_t x_stride, int x_off, int ns, int T, float* y, size_t y_stride, int y_off,
-                  int epi = 0, const float* scale = nullptr, int scale_n = 1, const VSnake* sk = nullptr, int store = 1, int a_bf16 = 0, int y_bf16 = 0) {
-    VGemm g; g.x = x; g.x_stride = x_stride; g.x_off = x_off; g.T = T; g.M = ns * T; g.c = c; g.y = y; g.y_stride = y_stride; g.y_off = y_off;
-    g.scale = scale; g.scale_n = scale_n; g.epi = epi; g.store = store; g.a_bf16 = a_bf16; g.y_bf16 = y_bf16;
-    g.y2 = nullptr; g.y2_stride = 0; g.y2_off = 0; g.ea = g.ib = nullptr; g.snake_n = 1; g.y2_bf16 = 0;
-    if (sk) { g.y2 = sk->y2; g.y2_stride = sk->stride; g.y2_off = sk->off; g.ea = sk->ea; g.ib = sk->ib; g.snake_n = sk->n; g.y2_bf16 = sk->bf16; }
+// (the ring kernel's epilogue moves 4 columns at a time: nout and every row start are multiples of 4 elements for all convolutions of the vocoder)
+static bool voc_ring_ok(const VLaunch& vl, const VGemm& g) { return !vl.no_ring && g.c.nout % 4 == 0 && g.y_off % 4 == 0 && g.y_stride % 4 == 0 && g.y2_off % 4 == 0 && g.y2_stride % 4 == 0; }
+template <int NJ>  // 64 x 16 NJ tiles
+static void launch_vgemm_small(hipStream_t s, const VGemm& g) {
+    const dim3 grid((g.c.nout + 16 * NJ - 1) / (16 * NJ), (g.M + 63) / 64);
+    if (g.a_bf16) hipLaunchKernelGGL((k_vgemm_small<NJ, true>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((k_vgemm_small<NJ, false>), grid, dim3(256), 0, s, g);
+}
+template <int NJ>  // 128 x 32 NJ tiles: the LDS-DMA ring for bf16 A, else (or with vl.no_ring) the register-staged kernel
+static void launch_vgemm_tile(const VLaunch& vl, hipStream_t s, const VGemm& g) {
+    const dim3 grid((g.c.nout + 32 * NJ - 1) / (32 * NJ), (g.M + 127) / 128);
+    if (g.a_bf16 && voc_ring_ok(vl, g)) launch_vgemm_ring<NJ>(vl, s, g, grid);
+    else if (g.a_bf16) hipLaunchKernelGGL((k_vgemm_lds<NJ, true>), grid, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL((k_vgemm_lds<NJ, false>), grid, dim3(256), 0, s, g);
+}
+// y = epi(convolution c of x), ns slots x T rows each
+static void vgemm(const VLaunch& vl, hipStream_t s, const VConv& c, const VRows& x, int ns, int T, const VRows& y, VEpi epi = VEPI_STORE, const VOpt& o = VOpt()) {
+    VGemm g; g.x = x.p; g.x_stride = x.stride; g.x_off = x.off; g.T = T; g.M = ns * T; g.c = c; g.y = y.p; g.y_stride = y.stride; g.y_off = y.off;
+    g.scale = o.scale; g.scale_n = o.scale_n; g.epi = epi; g.store = o.store; g.a_bf16 = x.bf16; g.y_bf16 = y.bf16;
+    g.y2 = o.snake.to.p; g.y2_stride = o.snake.to.stride; g.y2_off = o.snake.to.off; g.ea = o.snake.ea; g.ib = o.snake.ib; g.snake_n = o.snake.n; g.y2_bf16 = o.snake.to.bf16;
     g.chunked = vconv_chunked(c) ? 1 : 0;
     // every kernel accumulates the same 32-wide K steps in the same order: the choice never changes a result
+    // k_vconv_tap: fewer workgroups than tap_min (a draining batch, a single stream) leave most CUs idle under 256-row tiles: the finer 128 x 128
+    // tiles serve them (the tests force it onto one-slot calls with Q3TTS_VOC_TAP_MIN=1)
     const long tap_wgs = (long)(c.nout / 128) * ((ns * ((T + 127) / 128) + 1) / 2);  // (counted in 256-row workgroups for both forms)
-    if (g.chunked && a_bf16 && voc_tap() && voc_ring_ok(g) && c.nout % 128 == 0 && 6 * c.dil <= 64 && epi != 4 &&
+    if (g.chunked && g.a_bf16 && !vl.no_tap && voc_ring_ok(vl, g) && c.nout % 128 == 0 && 6 * c.dil <= 64 && epi != VEPI_SWIGLU &&
         ((T + 127) / 128) * 128 * 3 <= T * 4 &&  /* at most a quarter of the 128-row sub-tiles' rows beyond T */
-        tap_wgs >= voc_tap_min()) {
-        if (voc_polite()) launch_vconv_tap<1>(s, g); else launch_vconv_tap<2>(s, g);
-    } else if (g.M <= 512 || epi == 4) {
+        tap_wgs >= vl.tap_min) {
+        if (vl.polite) launch_vconv_tap<1>(vl, s, g); else launch_vconv_tap<2>(vl, s, g);
+    } else if (g.M <= 512 || epi == VEPI_SWIGLU) {
         // the kernel is bound by what one CU's load path delivers: a narrow N runs 64 x 16 tiles to put a workgroup on
         // every CU instead of on half of them
         const long wg32 = (long)((c.nout + 31) / 32) * ((g.M + 63) / 64);
-        if (epi != 4 && wg32 < 256) {
-            dim3 grid((c.nout + 15) / 16, (g.M + 63) / 64);
-            if (a_bf16) hipLaunchKernelGGL((k_vgemm_small<1, true>), grid, dim3(256), 0, s, g);
-            else hipLaunchKernelGGL((k_vgemm_small<1, false>), grid, dim3(256), 0, s, g);
-        } else {
-            dim3 grid((c.nout + 31) / 32, (g.M + 63) / 64);
-            if (a_bf16) hipLaunchKernelGGL((k_vgemm_small<2, true>), grid, dim3(256), 0, s, g);
-            else hipLaunchKernelGGL((k_vgemm_small<2, false>), grid, dim3(256), 0, s, g);
-        }
-    } else if (c.nout % 128 != 0 && c.nout % 96 == 0) {
-        dim3 grid(c.nout / 96, (g.M + 127) / 128);
-        if (a_bf16 && voc_ring_ok(g)) launch_vgemm_ring<3>(s, g, grid);
-        else if (a_bf16) hipLaunchKernelGGL((k_vgemm_lds<3, true>), grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((k_vgemm_lds<3, false>), grid, dim3(256), 0, s, g);
-    } else if (c.nout % 64 == 0 && (long)((c.nout + 127) / 128) * ((g.M + 127) / 128) < 192) {
-        // too few 128 x 128 tiles for 256 CUs (the decoder's input convolution: 1024 rows x 1536 columns): 128 x 64 tiles, twice the workgroups
-        dim3 grid(c.nout / 64, (g.M + 127) / 128);
-        if (a_bf16 && voc_ring_ok(g)) launch_vgemm_ring<2>(s, g, grid);
-        else if (a_bf16) hipLaunchKernelGGL((k_vgemm_lds<2, true>), grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((k_vgemm_lds<2, false>), grid, dim3(256), 0, s, g);
-    } else {
-        dim3 grid((c.nout + 127) / 128, (g.M + 127) / 128);
-        if (a_bf16 && voc_ring_ok(g)) launch_vgemm_ring<4>(s, g, grid);
-        else if (a_bf16) hipLaunchKernelGGL((k_vgemm_lds<4, true>), grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((k_vgemm_lds<4, false>), grid, dim3(256), 0, s, g);
-    }
+        if (epi != VEPI_SWIGLU && wg32 < 256) launch_vgemm_small<1>(s, g); else launch_vgemm_small<2>(s, g);
+    } else if (c.nout % 128 != 0 && c.nout % 96 == 0) launch_vgemm_tile<3>(vl, s, g);
+    // too few 128 x 128 tiles for 256 CUs (the decoder's input convolution: 1024 rows x 1536 columns): 128 x 64 tiles, twice the workgroups
+    else if (c.nout % 64 == 0 && (long)((c.nout + 127) / 128) * ((g.M + 127) / 128) < 192) launch_vgemm_tile<2>(vl, s, g);
+    else launch_vgemm_tile<4>(vl, s, g);
 }
-static bool resunit_ok(int C) {
-    const char* ev = getenv("Q3TTS_VOC_NOFUSE");  // (read per call: the tests compare both paths in one process)
-    const int off = ev ? atoi(ev) : 0;
-    return !off && (C == 32 || C == 64 || C == 96 || C == 128 || C == 192);
-}
+static bool resunit_ok(const VLaunch& vl, int C) { return !vl.no_fuse && (C == 32 || C == 64 || C == 96 || C == 128 || C == 192); }
 template <int NT, int MT, int NWV = 4>
-static void launch_resunit_t(hipStream_t s, const VResUnit& g, int ns) {
+static void launch_resunit_t(const VLaunch& vl, hipStream_t s, const VResUnit& g, int ns) {
     constexpr int C = NT * 16, R = 64 * MT, LDA = C + 16;
-    const size_t lds = voc_lds_floor(std::max(((size_t)(R + 6 * g.dil) * LDA + (size_t)2 * C * 32) * 2, (size_t)R * (C + 4) * 4));  // input tile + weight ring, later the f32 output tile
+    const size_t lds = voc_lds_floor(vl, std::max(((size_t)(R + 6 * g.dil) * LDA + (size_t)2 * C * 32) * 2, (size_t)R * (C + 4) * 4));  // input tile + weight ring, later the f32 output tile
     static Q3PerDevice pd;
     pd.ensure(1, []() { hipFuncSetAttribute((const void*)k_voc_resunit<NT, MT, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); });
     hipLaunchKernelGGL((k_voc_resunit<NT, MT, NWV>), dim3((g.T + R - 1) / R, ns), dim3(64 * NWV), lds, s, g);
 }
-static void launch_resunit(hipStream_t s, const VRes& r, int ns, int T, int C, float* o, int store_o, const VSnake& sk) {
+// one fused residual unit over o[ns][T][C]; store_o = 0: only SnakeBeta of the sum (sk) is wanted
+static void launch_resunit(const VLaunch& vl, hipStream_t s, const VRes& r, int ns, int T, int C, float* o, int store_o, const VSnake& sk) {
     VResUnit g;
     g.xin = r.c1_in.p; g.xin_stride = r.c1_in.stride(); g.T = T; g.dil = r.c1.dil;
     g.w1 = r.c1.w; g.w2 = r.c2.w; g.b1 = r.c1.b; g.b2 = r.c2.b; g.ea2 = r.ea2; g.ib2 = r.ib2;
     g.o = o; g.o_stride = (size_t)T * C; g.store_o = store_o;
-    g.y2 = sk.y2; g.y2_stride = sk.stride; g.y2_off = sk.off; g.ea3 = sk.ea; g.ib3 = sk.ib;
+    g.y2 = sk.to.p; g.y2_stride = sk.to.stride; g.y2_off = sk.to.off; g.ea3 = sk.ea; g.ib3 = sk.ib;
     switch (C) {
-        case 32: launch_resunit_t<2, 4>(s, g, ns); break;
-        case 64: launch_resunit_t<4, 3>(s, g, ns); break;
-        case 96: launch_resunit_t<6, 2>(s, g, ns); break;  // (beside the decoder, one workgroup per CU: 192-row tiles 233 us against 200, 232 VGPRs)
-        case 128: launch_resunit_t<8, 1>(s, g, ns); break;
-        default: if (voc_polite()) launch_resunit_t<12, 1>(s, g, ns); else launch_resunit_t<12, 2, 8>(s, g, ns); break;  // (64-row tiles, 4 waves, two workgroups per CU: 182 us; 128 rows with 4 waves: 215; 128 rows with 8 waves: 168)
+        case 32: launch_resunit_t<2, 4>(vl, s, g, ns); break;
+        case 64: launch_resunit_t<4, 3>(vl, s, g, ns); break;
+        case 96: launch_resunit_t<6, 2>(vl, s, g, ns); break;  // (beside the decoder, one workgroup per CU: 192-row tiles 233 us against 200, 232 VGPRs)
+        case 128: launch_resunit_t<8, 1>(vl, s, g, ns); break;
+        default: if (vl.polite) launch_resunit_t<12, 1>(vl, s, g, ns); else launch_resunit_t<12, 2, 8>(vl, s, g, ns); break;  // (64-row tiles, 4 waves, two workgroups per CU: 182 us; 128 rows with 4 waves: 215; 128 rows with 8 waves: 168)
     }
 }
 static void hist(hipStream_t s, const VCall& cl, const VCall* cld, VBuf& b, int T, int save) {
@@ -1656,24 +1664,23 @@ static void hist_all(hipStream_t s, const VCall& cl, const VCall* cld, Q3Voc* v,
     add(v->out_in, T, true);
     if (tab.n) hipLaunchKernelGGL(k_voc_hist_all, dim3(16, cl.ns, tab.n), dim3(256), 0, s, cld, tab, save);
 }
-// one batched streaming call: ns slots x nf new frames each (uniform nf <= VOC_FCAP)
-// sliding-window attention of a call: the LDS-staged kernel for heads of <= 64 dims (Q3TTS_VOC_ATTN_OLD=1: the row-walking kernel; same bits)
-static void voc_launch_attn(hipStream_t s, const VCall* cld, Q3Voc* v, float* kr, float* vr, int ns, int nf, int tiled) {
+// sliding-window attention of a call: the LDS-staged kernel for heads of <= 64 dims, else (or with vl.attn_old) the row-walking kernel; same bits
+static void voc_launch_attn(const VLaunch& vl, hipStream_t s, const VCall* cld, Q3Voc* v, float* kr, float* vr, int ns, int nf, int tiled) {
     const q3tts_vocoder_config& c = v->c;
-    const char* ev = getenv("Q3TTS_VOC_ATTN_OLD");   // (read per launch: a test compares the two kernels in one process)
-    const bool old = ev && atoi(ev);
     const size_t lds = (size_t)(c.sliding_window + nf - 1) * (2 * c.head_dim + 1) * sizeof(float);
-    if (!old && c.head_dim <= 64 && c.head_dim % 4 == 0 && lds <= 48 * 1024) {
+    if (!vl.attn_old && c.head_dim <= 64 && c.head_dim % 4 == 0 && lds <= 48 * 1024) {
         hipLaunchKernelGGL(k_voc_attn_lds, dim3(c.n_head, ns), dim3(64 * nf), lds, s, cld, v->qkv, kr, vr, v->rope, c.n_head, c.head_dim, v->RW, c.sliding_window, v->att, tiled);
         return;
     }
     hipLaunchKernelGGL(k_voc_attn, dim3(c.n_head, ns), dim3(64 * nf), 0, s, cld, v->qkv, kr, vr, v->rope, c.n_head, c.head_dim, v->RW, c.sliding_window, v->att, tiled);
 }
-// one tap: (H + T) rows of C elements at p, f32 (dtype 0) or bf16 (1), plain rows (layout 0) or the decoder GEMM's A-tiled layout (1: whole
-// 16-row tiles, q3_atile_off), copied in stream order, i.e. after the launches issued so far and before the next one overwrites p
-static void vtap(Q3Voc* v, hipStream_t s, const void* p, int dtype, int layout, int H, int T, int C, const char* fmt, int a = 0, int b = 0) {
+// one tap (a no-op unless a sink is set): (H + T) rows of C elements at p — f32, bf16, or bf16 in the decoder GEMM's A-tiled layout (whole
+// 16-row tiles, q3_atile_off) — copied in stream order, i.e. after the launches issued so far and before the next one overwrites p
+enum VTapKind { VT_F32, VT_BF16, VT_BF16_TILED };
+static void vtap_rows(Q3Voc* v, hipStream_t s, const void* p, VTapKind kind, int H, int T, int C, const char* fmt, int a, int b) {
     VTapSink* k = v->taps;
     if (!k || k->overflow) return;
+    const int dtype = kind != VT_F32, layout = kind == VT_BF16_TILED;
     const size_t rows = layout ? (size_t)((H + T + 15) / 16) * 16 : (size_t)(H + T), bytes = rows * C * (dtype ? 2 : 4);
     if (k->n >= k->rec_cap || k->used + bytes > k->cap) { k->overflow = true; return; }
     q3tts_voc_tap& r = k->recs[k->n++];
@@ -1683,147 +1690,131 @@ static void vtap(Q3Voc* v, hipStream_t s, const void* p, int dtype, int layout, 
     if (hipMemcpyAsync(k->buf + k->used, p, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) k->overflow = true;
     k->used += (bytes + 15) & ~(size_t)15;
 }
-static void vtap_buf(Q3Voc* v, hipStream_t s, const VBuf& b, int T, const char* fmt, int a = 0, int c = 0) {
-    vtap(v, s, b.p, b.bf16, 0, b.H, T, b.C, fmt, a, c);
+static void vtap(Q3Voc* v, hipStream_t s, const void* p, VTapKind kind, int T, int C, const char* fmt, int a = 0, int b = 0) {  // scratch: no history rows
+    vtap_rows(v, s, p, kind, 0, T, C, fmt, a, b);
 }
-static int voc_call_body(q3tts_engine* e, const VCall& cl, hipStream_t s) {
-    Q3Voc* v = e->voc;
-    const VCall* cld = v->call_dev;
-    const bool tp = v->taps != nullptr;
-    const q3tts_vocoder_config& c = v->c;
-    const int ns = cl.ns, nf = cl.nf, d = c.latent_dim, HH = c.n_head * c.head_dim, M = ns * nf;
-    hist_all(s, cl, cld, v, nf, 0);
-    // V1 + V2
-    hipLaunchKernelGGL(k_voc_embed, dim3(nf, ns), dim3(128), 0, s, cld, e->codes, e->cfg.max_steps_cap, e->cfg.model.n_codebooks, v->cb_dev,
+static void vtap_buf(Q3Voc* v, hipStream_t s, const VBuf& b, int T, const char* fmt, int a = 0, int c = 0) {
+    vtap_rows(v, s, b.p, b.bf16 ? VT_BF16 : VT_F32, b.H, T, b.C, fmt, a, c);
+}
+// one launch of the decoder's k_bgemm for the vocoder: a[rows][K] (A-tiled bf16) x tiled weights w[N][K], plus the outputs, bias and scale named
+// after it; vbgemm launches it and turns a refused shape into an error
+struct VBg : Q3BGemm {
+    VBg(const void* a_, int rows, const uint4* w_, int K_, int N_, int epi_) : Q3BGemm{} { a = (const uint16_t*)a_; B = rows; w = w_; K = K_; N = N_; epi = epi_; }
+    VBg& to(float* y_, int ldy_) { y = y_; ldy = ldy_; return *this; }  // f32 rows
+    VBg& to_slots(const VRows& r, int T, int ldy_) { y = r.p + r.off; ldy = ldy_; seg_rows = T; seg_stride = r.stride; return *this; }  // f32 rows, T per slot
+    VBg& to_tiled(void* p) { yb = (uint16_t*)p; return *this; }         // A-tiled bf16
+    VBg& bias_of(const VConv& c) { bias = c.b; bias_n = c.bias_n; return *this; }
+    VBg& scaled(const float* cs) { col_scale = cs; return *this; }
+};
+static int vbgemm(q3tts_engine* e, hipStream_t s, const Q3BGemm& g, const char* msg) {
+    return q3_launch_bgemm(g, s) ? q3_set_err(e, Q3TTS_ERR_INVALID, msg) : Q3TTS_OK;
+}
+
+// The stages of one batched streaming call: ns slots x nf new frames each (uniform nf <= VOC_FCAP), in the order voc_call_body lists them.
+// V1 + V2: codebook embedding sum into the pre-conv's rows, pre-conv -> x [M = ns * nf][d]
+static void voc_embed_pre(q3tts_engine* e, const VLaunch& vl, const VCall& cl, hipStream_t s) {
+    Q3Voc* v = e->voc; const q3tts_vocoder_config& c = v->c;
+    hipLaunchKernelGGL(k_voc_embed, dim3(cl.nf, cl.ns), dim3(128), 0, s, v->call_dev, e->codes, e->cfg.max_steps_cap, e->cfg.model.n_codebooks, v->cb_dev,
                        c.n_codebooks, c.codebook_size, c.codebook_dim, v->pre_in.p, v->pre_in.stride(), v->pre_in.H * v->pre_in.C);
-    vgemm(s, v->pre, v->pre_in.p, v->pre_in.stride(), v->pre_in.H * v->pre_in.C, ns, nf, v->x, (size_t)nf * d, 0);
-    // V3 transformer (rows m = s*nf + t)
-    for (int l = 0; l < c.n_layer; ++l) {
-        VLayer& L = v->L[l];
-        // GEMM-only activations (normed input, attention output, SwiGLU output) are stored as the bf16 they would be rounded to
-        float* kr = v->kring + (size_t)l * v->B * v->RW * HH; float* vr = v->vring + (size_t)l * v->B * v->RW * HH;
-        if (v->tfm_bg) {  // the decoder's GEMM: A-tiled bf16 rows in, 8 K-slices per output (its tile choice never changes a result)
-            Q3BGemm g{}; g.B = M;
-            hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, L.in_norm, c.rms_eps, d, v->xnb, 2);
-            g.a = (const uint16_t*)v->xnb; g.w = L.qkv_t; g.K = d; g.N = 3 * HH; g.epi = Q3_EPI_STORE; g.y = v->qkv; g.ldy = 3 * HH;
-            if (q3_launch_bgemm(g, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder: qkv GEMM shape");
-            voc_launch_attn(s, cld, v, kr, vr, ns, nf, 1);
-            g.a = (const uint16_t*)v->att; g.w = L.o_t; g.K = HH; g.N = d; g.epi = Q3_EPI_RESID; g.y = v->x; g.ldy = d; g.col_scale = L.ls_attn;
-            if (q3_launch_bgemm(g, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder: o GEMM shape");
-            hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, L.post_norm, c.rms_eps, d, v->xnb, 2);
-            g.a = (const uint16_t*)v->xnb; g.w = L.gu_t; g.K = d; g.N = 2 * c.d_ffn; g.epi = Q3_EPI_SWIGLU; g.y = nullptr; g.yb = (uint16_t*)v->g; g.col_scale = nullptr;
-            if (q3_launch_bgemm(g, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder: gate/up GEMM shape");
-            g.a = (const uint16_t*)v->g; g.w = L.down_t; g.K = c.d_ffn; g.N = d; g.epi = Q3_EPI_RESID; g.y = v->x; g.ldy = d; g.yb = nullptr; g.col_scale = L.ls_mlp;
-            if (q3_launch_bgemm(g, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder: down GEMM shape");
-            continue;
-        }
-        hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, L.in_norm, c.rms_eps, d, v->xnb, 1);
-        vgemm(s, L.qkv, v->xnb, 0, 0, 1, M, v->qkv, 0, 0, 0, nullptr, 1, nullptr, 1, 1);
-        voc_launch_attn(s, cld, v, kr, vr, ns, nf, 0);
-        vgemm(s, L.o, v->att, 0, 0, 1, M, v->x, 0, 0, 1, L.ls_attn, d, nullptr, 1, 1);
-        hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, L.post_norm, c.rms_eps, d, v->xnb, 1);
-        vgemm(s, L.gu, v->xnb, 0, 0, 1, M, v->g, 0, 0, 4, nullptr, 1, nullptr, 1, 1, 1);  // gate | up in one launch, SwiGLU in the epilogue
-        vgemm(s, L.down, v->g, 0, 0, 1, M, v->x, 0, 0, 1, L.ls_mlp, d, nullptr, 1, 1);
-    }
-    // V5a upsample stages; cur = [ns][T][d] contiguous per slot (stride T*d)
-    const float* cur = v->xn; int T = nf; size_t cur_stride = (size_t)nf * d; int cur_off = 0;
-    if (v->up_bg) {
-        // the stages' single-tap GEMMs on the decoder's k_bgemm: A-tiled bf16 rows (row m = s * T + t) in, f32 results into the per-slot
-        // work buffers (segmented rows), bias / GELU / LayerScale-residual in the epilogue
-        hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, v->final_norm, c.rms_eps, d, v->xnb, 2);
-        const uint16_t* a_in = (const uint16_t*)v->xnb;
-        for (size_t ui = 0; ui < v->U.size(); ++ui) {
-            VUp& p = v->U[ui];
-            if (tp) vtap(v, s, a_in, 1, 1, 0, T, d, "up%d.in", (int)ui);
-            Q3BGemm g{}; g.a = a_in; g.B = ns * T; g.w = p.ct_t; g.K = d; g.N = p.r * d; g.epi = Q3_EPI_STORE;  // [T][r*d] == [T*r][d]
-            g.bias = p.ct.b; g.bias_n = p.ct.bias_n; g.y = p.dw_in.p + (size_t)p.dw_in.H * d; g.ldy = p.r * d; g.seg_rows = T; g.seg_stride = p.dw_in.stride();
-            if (q3_launch_bgemm(g, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder: upsample ConvTranspose GEMM shape");
-            T *= p.r;
-            if (tp) vtap_buf(v, s, p.dw_in, T, "up%d.raw", (int)ui);
-            hipLaunchKernelGGL(k_voc_dw_ln, dim3(T, ns), dim3(64), (size_t)d * 4, s, p.dw_in.p, p.dw_in.stride(), p.dw_in.H, T, d, p.dw_w, p.dw_b, p.ln_w, p.ln_b, v->t1, 1);
-            if (tp) vtap(v, s, v->t1, 1, 1, 0, T, d, "up%d.ln", (int)ui);
-            hist(s, cl, cld, p.dw_in, T, 1);  // history = the raw ConvTranspose output, saved before the in-place residual below
-            Q3BGemm h{}; h.a = (const uint16_t*)v->t1; h.B = ns * T; h.w = p.pw1_t; h.K = d; h.N = 4 * d; h.epi = Q3_EPI_GELU;
-            h.bias = p.pw1.b; h.bias_n = p.pw1.bias_n; h.yb = (uint16_t*)v->t2;
-            if (q3_launch_bgemm(h, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder: pointwise-1 GEMM shape");
-            if (tp) vtap(v, s, v->t2, 1, 1, 0, T, 4 * d, "up%d.gelu", (int)ui);
-            Q3BGemm r{}; r.a = (const uint16_t*)v->t2; r.B = ns * T; r.w = p.pw2_t; r.K = 4 * d; r.N = d; r.epi = Q3_EPI_RESID;  // residual in place
-            r.bias = p.pw2.b; r.bias_n = p.pw2.bias_n; r.col_scale = p.gamma; r.y = p.dw_in.p + (size_t)p.dw_in.H * d; r.ldy = d; r.seg_rows = T; r.seg_stride = p.dw_in.stride();
-            if (ui + 1 < v->U.size()) r.yb = v->upb;  // the next stage's GEMM input
-            if (q3_launch_bgemm(r, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder: pointwise-2 GEMM shape");
-            if (tp) vtap_buf(v, s, p.dw_in, T, "up%d.out", (int)ui);
-            a_in = v->upb;
-            cur = p.dw_in.p; cur_stride = p.dw_in.stride(); cur_off = p.dw_in.H * d;
-        }
-    } else {
-        hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, v->final_norm, c.rms_eps, d, v->xn, 0);
-        for (size_t ui = 0; ui < v->U.size(); ++ui) {
-            VUp& p = v->U[ui];
-            if (tp) vtap(v, s, cur + cur_off, 0, 0, 0, T, d, "up%d.in", (int)ui);
-            vgemm(s, p.ct, cur, cur_stride, cur_off, ns, T, p.dw_in.p, p.dw_in.stride(), p.dw_in.H * d);  // [T][r*d] == [T*r][d]
-            T *= p.r;
-            if (tp) vtap_buf(v, s, p.dw_in, T, "up%d.raw", (int)ui);
-            hipLaunchKernelGGL(k_voc_dw_ln, dim3(T, ns), dim3(64), (size_t)d * 4, s, p.dw_in.p, p.dw_in.stride(), p.dw_in.H, T, d, p.dw_w, p.dw_b, p.ln_w, p.ln_b, v->t1, 0);
-            if (tp) vtap(v, s, v->t1, 0, 0, 0, T, d, "up%d.ln", (int)ui);
-            hist(s, cl, cld, p.dw_in, T, 1);  // history = the raw ConvTranspose output, saved before the in-place residual below
-            vgemm(s, p.pw1, v->t1, (size_t)T * d, 0, ns, T, v->t2, (size_t)T * 4 * d, 0, 3);
-            if (tp) vtap(v, s, v->t2, 0, 0, 0, T, 4 * d, "up%d.gelu", (int)ui);
-            vgemm(s, p.pw2, v->t2, (size_t)T * 4 * d, 0, ns, T, p.dw_in.p, p.dw_in.stride(), p.dw_in.H * d, 1, p.gamma, d);  // residual in place
-            if (tp) vtap_buf(v, s, p.dw_in, T, "up%d.out", (int)ui);
-            cur = p.dw_in.p; cur_stride = p.dw_in.stride(); cur_off = p.dw_in.H * d;
-        }
-    }
-    {   // timing experiment only (results are then garbage): Q3TTS_EXP_VOC_SKIP=2 ends the call here — the launch-bound front end (embedding,
-        // transformer, up-sampling) alone beside the decoder, to split the interference between the two halves of a call (profiles/README.md)
-        static const int exp_skip = getenv("Q3TTS_EXP_VOC_SKIP") ? atoi(getenv("Q3TTS_EXP_VOC_SKIP")) : 0;
-        if (exp_skip == 2) { Q3_HIP(e, hipGetLastError()); return Q3TTS_OK; }
-    }
-    // V5b decoder
-    hipLaunchKernelGGL(k_voc_rows_bf16, dim3((unsigned)(((size_t)T * d / 4 + 255) / 256), ns), dim3(256), 0, s, cur + cur_off, cur_stride,
+    vgemm(vl, s, v->pre, v->pre_in.rows(), cl.ns, cl.nf, VBuf::flat(v->x, cl.nf, c.latent_dim));
+}
+// V3, one transformer layer on x (rows m = s * nf + t). GEMM-only activations (normed input, attention output, SwiGLU output) are stored as
+// the bf16 they would be rounded to: A-tiled for the decoder's k_bgemm (tfm_bg; 8 K-slices per output, its tile choice never changes a
+// result), plain rows for vgemm, which takes the M rows as one slot
+static int voc_tfm_layer(q3tts_engine* e, const VLaunch& vl, const VCall& cl, hipStream_t s, int l) {
+    Q3Voc* v = e->voc; const q3tts_vocoder_config& c = v->c; VLayer& L = v->L[l];
+    const int d = c.latent_dim, HH = c.n_head * c.head_dim, M = cl.ns * cl.nf, one_slot = 1, tiled = v->tfm_bg ? 1 : 0;
+    float* kr = v->kring + (size_t)l * v->B * v->RW * HH; float* vr = v->vring + (size_t)l * v->B * v->RW * HH;
+    const VRows x = VBuf::flat(v->x, M, d), xnb = VBuf::flat(v->xnb, M, d).as_bf16(), att = VBuf::flat(v->att, M, HH).as_bf16();
+    const VRows g = VBuf::flat(v->g, M, c.d_ffn).as_bf16();
+    hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, L.in_norm, c.rms_eps, d, v->xnb, tiled ? 2 : 1);
+    if (tiled) VTRY(vbgemm(e, s, VBg(v->xnb, M, L.qkv_t, d, 3 * HH, Q3_EPI_STORE).to(v->qkv, 3 * HH), "vocoder: qkv GEMM shape"));
+    else vgemm(vl, s, L.qkv, xnb, one_slot, M, VBuf::flat(v->qkv, M, 3 * HH));
+    voc_launch_attn(vl, s, v->call_dev, v, kr, vr, cl.ns, cl.nf, tiled);
+    if (tiled) VTRY(vbgemm(e, s, VBg(v->att, M, L.o_t, HH, d, Q3_EPI_RESID).to(v->x, d).scaled(L.ls_attn), "vocoder: o GEMM shape"));
+    else vgemm(vl, s, L.o, att, one_slot, M, x, VEPI_SCALE_ADD, VOpt().layer_scale(L.ls_attn, d));
+    hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, L.post_norm, c.rms_eps, d, v->xnb, tiled ? 2 : 1);
+    if (tiled) VTRY(vbgemm(e, s, VBg(v->xnb, M, L.gu_t, d, 2 * c.d_ffn, Q3_EPI_SWIGLU).to_tiled(v->g), "vocoder: gate/up GEMM shape"));
+    else vgemm(vl, s, L.gu, xnb, one_slot, M, g, VEPI_SWIGLU);  // gate | up in one launch, SwiGLU in the epilogue
+    if (tiled) VTRY(vbgemm(e, s, VBg(v->g, M, L.down_t, c.d_ffn, d, Q3_EPI_RESID).to(v->x, d).scaled(L.ls_mlp), "vocoder: down GEMM shape"));
+    else vgemm(vl, s, L.down, g, one_slot, M, x, VEPI_SCALE_ADD, VOpt().layer_scale(L.ls_mlp, d));
+    return Q3TTS_OK;
+}
+// V5a, one up-sampling stage: ConvTranspose ([T][r*d] == [T*r][d]) into dw_in's rows, depthwise conv + LayerNorm -> t1, pointwise GELU MLP
+// through t2, LayerScale residual in place. cur / T: the rows this stage reads, on return the rows it wrote. up_bg: the single-tap GEMMs on the
+// decoder's k_bgemm — A-tiled bf16 rows (row m = s * T + t) in, f32 results into the per-slot work buffers (segmented rows), bias / GELU /
+// LayerScale-residual in the epilogue; a stage's output also goes to upb as the next stage's A-tiled input
+static int voc_up_stage(q3tts_engine* e, const VLaunch& vl, const VCall& cl, hipStream_t s, size_t ui, VRows& cur, int& T) {
+    Q3Voc* v = e->voc; VUp& p = v->U[ui];
+    const int ns = cl.ns, d = v->c.latent_dim, i = (int)ui, bg = v->up_bg ? 1 : 0;
+    const VTapKind kind = bg ? VT_BF16_TILED : VT_F32;
+    const uint16_t* a_in = ui ? v->upb : (const uint16_t*)v->xnb;
+    const VRows raw = p.dw_in.rows();
+    vtap(v, s, bg ? (const void*)a_in : (const void*)(cur.p + cur.off), kind, T, d, "up%d.in", i);
+    if (bg) VTRY(vbgemm(e, s, VBg(a_in, ns * T, p.ct_t, d, p.r * d, Q3_EPI_STORE).bias_of(p.ct).to_slots(raw, T, p.r * d), "vocoder: upsample ConvTranspose GEMM shape"));
+    else vgemm(vl, s, p.ct, cur, ns, T, raw);
+    T *= p.r;
+    vtap_buf(v, s, p.dw_in, T, "up%d.raw", i);
+    hipLaunchKernelGGL(k_voc_dw_ln, dim3(T, ns), dim3(64), (size_t)d * 4, s, p.dw_in.p, p.dw_in.stride(), p.dw_in.H, T, d, p.dw_w, p.dw_b, p.ln_w, p.ln_b, v->t1, bg);
+    vtap(v, s, v->t1, kind, T, d, "up%d.ln", i);
+    hist(s, cl, v->call_dev, p.dw_in, T, 1);  // history = the raw ConvTranspose output, saved before the in-place residual below
+    if (bg) VTRY(vbgemm(e, s, VBg(v->t1, ns * T, p.pw1_t, d, 4 * d, Q3_EPI_GELU).bias_of(p.pw1).to_tiled(v->t2), "vocoder: pointwise-1 GEMM shape"));
+    else vgemm(vl, s, p.pw1, VBuf::flat(v->t1, T, d), ns, T, VBuf::flat(v->t2, T, 4 * d), VEPI_GELU);
+    vtap(v, s, v->t2, kind, T, 4 * d, "up%d.gelu", i);
+    if (bg) {
+        VBg r(v->t2, ns * T, p.pw2_t, 4 * d, d, Q3_EPI_RESID);
+        r.bias_of(p.pw2).scaled(p.gamma).to_slots(raw, T, d).to_tiled(ui + 1 < v->U.size() ? v->upb : nullptr);  // (upb: the next stage's GEMM input)
+        VTRY(vbgemm(e, s, r, "vocoder: pointwise-2 GEMM shape"));
+    } else vgemm(vl, s, p.pw2, VBuf::flat(v->t2, T, 4 * d), ns, T, raw, VEPI_SCALE_ADD, VOpt().layer_scale(p.gamma, d));
+    vtap_buf(v, s, p.dw_in, T, "up%d.out", i);
+    cur = raw;
+    return Q3TTS_OK;
+}
+// where SnakeBeta of residual unit (bi, u)'s sum lands: the next unit's c1_in, the next block's ct_in or the final convolution's window
+static VSnake snake_next(Q3Voc* v, size_t bi, int u) {
+    VBlk& k = v->Bk[bi];
+    if (u < 2) return snake_into(k.res[u + 1].c1_in, k.res[u + 1].ea, k.res[u + 1].ib, k.cout);
+    if (bi + 1 < v->Bk.size()) { VBlk& nx = v->Bk[bi + 1]; return snake_into(nx.ct_in, nx.ea, nx.ib, k.cout); }
+    return snake_into(v->out_in, v->oea, v->oib, k.cout);
+}
+// V5b, the decoder: cur (T rows of d per slot) as bf16 -> input convolution -> the blocks (ConvTranspose, three residual units each); T grows to
+// the samples per slot. Every SnakeBeta runs in the epilogue of the convolution that produces its input and lands directly in the work
+// buffer of the convolution that consumes it: dec_in -> blk0.ct_in; ct -> res0.c1_in; c1 -> (snake2) -> c2's input; c2 -> snake_next.
+static void voc_dec_blocks(q3tts_engine* e, const VLaunch& vl, const VCall& cl, hipStream_t s, const VRows& cur, int& T) {
+    Q3Voc* v = e->voc;
+    const int ns = cl.ns, d = v->c.latent_dim;
+    hipLaunchKernelGGL(k_voc_rows_bf16, dim3((unsigned)(((size_t)T * d / 4 + 255) / 256), ns), dim3(256), 0, s, cur.p + cur.off, cur.stride,
                        (uint16_t*)v->dec_in_in.p + (size_t)v->dec_in_in.H * d, v->dec_in_in.stride(), T * d);
-    int ch = c.decoder_dim;
-    // Every SnakeBeta runs in the epilogue of the convolution that produces its input and lands directly in the
-    // work buffer of the convolution that consumes it: dec_in -> blk0.ct_in; ct -> res0.c1_in; c1 -> (snake2) -> c2's
-    // input; c2 -> next unit's c1_in / next block's ct_in / the final conv's window.
-    {
-        const VSnake sk = snake_into(v->Bk[0].ct_in, v->Bk[0].ea, v->Bk[0].ib, ch);
-        vgemm(s, v->dec_in, v->dec_in_in.p, v->dec_in_in.stride(), v->dec_in_in.H * d, ns, T, v->t1, (size_t)T * ch, 0, 0, nullptr, 1, &sk, 0, 1);
-    }
+    int ch = v->c.decoder_dim;
     float* z = v->t1; float* o = v->t2;
+    vgemm(vl, s, v->dec_in, v->dec_in_in.rows(), ns, T, VBuf::flat(z, T, ch), VEPI_STORE,
+          VOpt().snake_to(snake_into(v->Bk[0].ct_in, v->Bk[0].ea, v->Bk[0].ib, ch)).no_store());
     for (size_t bi = 0; bi < v->Bk.size(); ++bi) {
-        VBlk& k = v->Bk[bi];
-        {
-            const VSnake sk = snake_into(k.res[0].c1_in, k.res[0].ea, k.res[0].ib, k.cout);
-            vgemm(s, k.ct, k.ct_in.p, k.ct_in.stride(), k.ct_in.H * k.cin, ns, T, o, (size_t)T * k.r * k.cout, 0, 0, nullptr, 1, &sk, 1, 1);
-        }
+        VBlk& k = v->Bk[bi]; const int b = (int)bi;
+        vgemm(vl, s, k.ct, k.ct_in.rows(), ns, T, VBuf::flat(o, T * k.r, k.cout), VEPI_STORE, VOpt().snake_to(snake_into(k.res[0].c1_in, k.res[0].ea, k.res[0].ib, k.cout)));
         T *= k.r; ch = k.cout;
-        if (tp) vtap(v, s, o, 0, 0, 0, T, ch, "b%d.o_ct", (int)bi);
+        vtap(v, s, o, VT_F32, T, ch, "b%d.o_ct", b);
         for (int u = 0; u < 3; ++u) {
             VRes& r = k.res[u];
-            if (resunit_ok(ch)) {  // narrow blocks: the whole residual unit in one pass over HBM
-                VSnake sk;
-                if (u < 2) { sk = snake_into(k.res[u + 1].c1_in, k.res[u + 1].ea, k.res[u + 1].ib, ch); }
-                else if (bi + 1 < v->Bk.size()) { VBlk& nx = v->Bk[bi + 1]; sk = snake_into(nx.ct_in, nx.ea, nx.ib, ch); }
-                else { sk = snake_into(v->out_in, v->oea, v->oib, ch); }
-                launch_resunit(s, r, ns, T, ch, o, u < 2 ? 1 : 0, sk);
-                if (tp && u < 2) vtap(v, s, o, 0, 0, 0, T, ch, "b%d.r%d.o", (int)bi, u);  // (the last unit's sum only exists as the next SnakeBeta's input)
-                continue;
+            const VSnake next = snake_next(v, bi, u);
+            const int store_o = u < 2 ? 1 : 0;  // (the last unit's sum only exists as the next SnakeBeta's input)
+            if (resunit_ok(vl, ch)) launch_resunit(vl, s, r, ns, T, ch, o, store_o, next);  // narrow blocks: the whole residual unit in one pass over HBM
+            else {
+                const VRows zf = VBuf::flat(z, T, ch), zb = zf.as_bf16(), orows = VBuf::flat(o, T, ch);
+                vgemm(vl, s, r.c1, r.c1_in.rows(), ns, T, zf, VEPI_STORE, VOpt().snake_to({zb, r.ea2, r.ib2, ch}).no_store());  // snake2 -> z (bf16)
+                vtap(v, s, z, VT_BF16, T, ch, "b%d.r%d.z", b, u);
+                VOpt opt; opt.snake = next; opt.store = store_o;
+                vgemm(vl, s, r.c2, zb, ns, T, orows, VEPI_ADD, opt);  // o += conv k1
             }
-            {
-                VSnake sk; sk.y2 = z; sk.stride = (size_t)T * ch; sk.off = 0; sk.ea = r.ea2; sk.ib = r.ib2; sk.n = ch; sk.bf16 = 1;  // snake2 -> z (bf16)
-                vgemm(s, r.c1, r.c1_in.p, r.c1_in.stride(), r.c1_in.H * ch, ns, T, z, (size_t)T * ch, 0, 0, nullptr, 1, &sk, 0, 1);
-                if (tp) vtap(v, s, z, 1, 0, 0, T, ch, "b%d.r%d.z", (int)bi, u);
-            }
-            VSnake sk;
-            if (u < 2) { sk = snake_into(k.res[u + 1].c1_in, k.res[u + 1].ea, k.res[u + 1].ib, ch); }
-            else if (bi + 1 < v->Bk.size()) { VBlk& nx = v->Bk[bi + 1]; sk = snake_into(nx.ct_in, nx.ea, nx.ib, ch); }
-            else { sk = snake_into(v->out_in, v->oea, v->oib, ch); }
-            vgemm(s, r.c2, z, (size_t)T * ch, 0, ns, T, o, (size_t)T * ch, 0, 2, nullptr, 1, &sk, u < 2 ? 1 : 0, 1);  // o += conv k1
-            if (tp && u < 2) vtap(v, s, o, 0, 0, 0, T, ch, "b%d.r%d.o", (int)bi, u);
+            if (store_o) vtap(v, s, o, VT_F32, T, ch, "b%d.r%d.o", b, u);
         }
     }
-    // V6
-    if (ch % 8 == 0 && ch / 8 <= 32 && !getenv("Q3TTS_VOC_OUT_OLD")) {
+}
+// V6: SnakeBeta'd window -> 7-tap convolution to one channel, clamp -> pcm (k_voc_out8: channels in slices of 8; vl.out_old: k_voc_out)
+static void voc_out(q3tts_engine* e, const VLaunch& vl, const VCall& cl, hipStream_t s, int T) {
+    Q3Voc* v = e->voc; const VCall* cld = v->call_dev;
+    const int ns = cl.ns, ch = v->out_c;
+    if (ch % 8 == 0 && ch / 8 <= 32 && !vl.out_old) {
         const int NS = ch / 8, G = std::min(16, 256 / NS), R = G * 8;
         static Q3PerDevice pd8;
         pd8.ensure(1, []() { hipFuncSetAttribute((const void*)k_voc_out8, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); });
@@ -1832,8 +1823,28 @@ static int voc_call_body(q3tts_engine* e, const VCall& cl, hipStream_t s) {
     } else
         hipLaunchKernelGGL(k_voc_out, dim3((T + 63) / 64, ns), dim3(256), (size_t)(70 * (ch + 1) + 7 * ch) * 4, s, cld, v->out_in.p, v->out_in.stride(), v->out_in.H, T, ch, v->out_w, v->out_b,
                            v->pcm, v->pcm_stride, v->spf);
-    if (tp) {  // the convolutions' work buffers as the MFMAs consumed them (history rows first; each is written once per call), and the call's PCM
-        int Tb = nf; for (auto& p : v->U) Tb *= p.r;
+}
+static int voc_call_body(q3tts_engine* e, const VLaunch& vl, const VCall& cl, hipStream_t s) {
+    Q3Voc* v = e->voc;
+    const q3tts_vocoder_config& c = v->c;
+    const int nf = cl.nf, d = c.latent_dim, M = cl.ns * nf;
+    hist_all(s, cl, v->call_dev, v, nf, 0);
+    voc_embed_pre(e, vl, cl, s);
+    for (int l = 0; l < c.n_layer; ++l) VTRY(voc_tfm_layer(e, vl, cl, s, l));
+    // final norm: f32 rows xn for vgemm, A-tiled bf16 xnb for k_bgemm
+    hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, v->final_norm, c.rms_eps, d, v->up_bg ? v->xnb : v->xn, v->up_bg ? 2 : 0);
+    VRows cur = VBuf::flat(v->xn, nf, d); int T = nf;  // the rows the next stage reads: T per slot
+    for (size_t ui = 0; ui < v->U.size(); ++ui) VTRY(voc_up_stage(e, vl, cl, s, ui, cur, T));
+    {   // timing experiment only (results are then garbage): Q3TTS_EXP_VOC_SKIP=2 ends the call here — the launch-bound front end (embedding,
+        // transformer, up-sampling) alone beside the decoder, to split the interference between the two halves of a call (profiles/README.md)
+        static const int exp_skip = getenv("Q3TTS_EXP_VOC_SKIP") ? atoi(getenv("Q3TTS_EXP_VOC_SKIP")) : 0;
+        if (exp_skip == 2) { Q3_HIP(e, hipGetLastError()); return Q3TTS_OK; }
+    }
+    const int Tup = T;
+    voc_dec_blocks(e, vl, cl, s, cur, T);
+    voc_out(e, vl, cl, s, T);
+    if (v->taps) {  // the convolutions' work buffers as the MFMAs consumed them (history rows first; each is written once per call), and the call's PCM
+        int Tb = Tup;
         vtap_buf(v, s, v->dec_in_in, Tb, "dec_in.in");
         for (size_t bi = 0; bi < v->Bk.size(); ++bi) {
             VBlk& k = v->Bk[bi];
@@ -1842,28 +1853,18 @@ static int voc_call_body(q3tts_engine* e, const VCall& cl, hipStream_t s) {
             for (int u = 0; u < 3; ++u) vtap_buf(v, s, k.res[u].c1_in, Tb, "b%d.r%d.c1_in", (int)bi, u);
         }
         vtap_buf(v, s, v->out_in, Tb, "out.in");
-        vtap(v, s, v->pcm + (size_t)cl.slot[0] * v->pcm_stride + (size_t)cl.pos[0] * v->spf, 0, 0, 0, Tb, 1, "pcm");
+        vtap(v, s, v->pcm + (size_t)cl.slot[0] * v->pcm_stride + (size_t)cl.pos[0] * v->spf, VT_F32, Tb, 1, "pcm");
     }
-    hist_all(s, cl, cld, v, nf, 1);
+    hist_all(s, cl, v->call_dev, v, nf, 1);
     Q3_HIP(e, hipGetLastError());
     return Q3TTS_OK;
 }
 
-// One vocoder call = ~100 launches whose shapes depend only on (slots, frames) and the launch mode: the slot / position table goes to the
-// device in stream order and the launches are replayed as ONE hipGraph per (slots, frames, mode, switches) — issuing them one by one took the
+// One vocoder call = ~100 launches whose shapes depend only on (slots, frames) and the launch switches: the slot / position table goes to the
+// device in stream order and the launches are replayed as ONE hipGraph per (slots, frames, VLaunch) — issuing them one by one took the
 // host 0.5 ms per 4-frame chunk, time in which the engine's loop launches no frame step. The first call of a shape runs eagerly (it also sets
-// the kernels' attributes), the second is captured. Q3TTS_VOC_NO_GRAPH=1: always eager.
-static unsigned long long voc_call_key(const VCall& cl) {
-    unsigned long long k = (unsigned long long)cl.ns | ((unsigned long long)cl.nf << 8) | ((unsigned long long)(voc_polite() ? 1 : 0) << 12);
-    unsigned long long h = 1469598103934665603ull;  // the launch-time switches (tests flip them inside one process)
-    for (const char* name : {"Q3TTS_VOC_NORING", "Q3TTS_VOC_NOFUSE", "Q3TTS_VOC_NOTAP", "Q3TTS_VOC_TAP_MIN", "Q3TTS_VOC_OUT_OLD", "Q3TTS_VOC_ATTN_OLD"}) {
-        const char* ev = getenv(name);
-        for (const char* c = ev ? ev : "-"; *c; ++c) h = (h ^ (unsigned char)*c) * 1099511628211ull;
-        h = (h ^ 0xFFu) * 1099511628211ull;
-    }
-    return k | (h << 16);
-}
-static int voc_call(q3tts_engine* e, const VCall& cl, hipStream_t s) {
+// the kernels' attributes), the second is captured. Q3TTS_VOC_NO_GRAPH=1: always eager. polite_call: the caller's mode for this call (VLaunch).
+static int voc_call(q3tts_engine* e, const VCall& cl, hipStream_t s, bool polite_call) {
     Q3Voc* v = e->voc;
     {   // upload through a pinned ring: entry i is reused only after its copy has been seen done
         const unsigned i = v->call_i++ & 15;
@@ -1873,15 +1874,22 @@ static int voc_call(q3tts_engine* e, const VCall& cl, hipStream_t s) {
         Q3_HIP(e, hipMemcpyAsync(v->call_dev, &v->call_host[i], sizeof(VCall), hipMemcpyHostToDevice, s));
         Q3_HIP(e, hipEventRecord(v->call_ev[i], s));
     }
+    VLaunch vl;  // the switches, read here and nowhere else
+    auto on = [](const char* name) { const char* ev = getenv(name); return ev && atoi(ev); };
+    const char* pol = getenv("Q3TTS_VOC_POLITE"); const char* tmin = getenv("Q3TTS_VOC_TAP_MIN");
+    vl.polite = pol ? atoi(pol) != 0 : polite_call;
+    vl.no_ring = on("Q3TTS_VOC_NORING"); vl.no_tap = on("Q3TTS_VOC_NOTAP"); vl.no_fuse = on("Q3TTS_VOC_NOFUSE"); vl.attn_old = on("Q3TTS_VOC_ATTN_OLD");
+    vl.tap_min = tmin ? atol(tmin) : 128;
+    vl.out_old = getenv("Q3TTS_VOC_OUT_OLD") != nullptr;  // (set to anything, as it always was)
     static const bool no_graph = [] { const char* ev = getenv("Q3TTS_VOC_NO_GRAPH"); return ev && atoi(ev); }();
-    if (no_graph || v->taps) return voc_call_body(e, cl, s);  // a tapped call runs eagerly and is never recorded or captured
-    const unsigned long long key = voc_call_key(cl);
+    if (no_graph || v->taps) return voc_call_body(e, vl, cl, s);  // a tapped call runs eagerly and is never recorded or captured
+    const VCallKey key(cl.ns, cl.nf, vl);
     auto it = v->call_graphs.find(key);
     if (it == v->call_graphs.end()) {
-        if (!v->call_seen.count(key)) { v->call_seen.insert(key); return voc_call_body(e, cl, s); }
+        if (v->call_seen.insert(key).second) return voc_call_body(e, vl, cl, s);
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
         Q3_HIP(e, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = voc_call_body(e, cl, s);
+        const int rc = voc_call_body(e, vl, cl, s);
         const hipError_t er = hipStreamEndCapture(s, &graph);
         if (rc != Q3TTS_OK) { if (graph) hipGraphDestroy(graph); return rc; }
         if (er != hipSuccess || !graph) return q3_set_err(e, Q3TTS_ERR_DEVICE, std::string("vocoder call capture: ") + hipGetErrorString(er));
@@ -1903,7 +1911,7 @@ int q3_voc_decode(q3tts_engine* e, int slot, int f0, int nf, int is_last, hipStr
         const int n = std::min(nf, VOC_FCAP);
         VCall cl; memset(&cl, 0, sizeof(cl));
         cl.ns = 1; cl.nf = n; cl.slot[0] = slot; cl.pos[0] = v->frames_done[slot];
-        VTRY(voc_call(e, cl, s));
+        VTRY(voc_call(e, cl, s, false));
         v->frames_done[slot] += n; nf -= n;
     }
     if (is_last) v->last_flag[slot] = 1;
@@ -1917,10 +1925,7 @@ int q3_voc_decode_batch(q3tts_engine* e, const int* slots, const int* real, int 
     VCall cl; memset(&cl, 0, sizeof(cl));
     cl.ns = ns; cl.nf = nf;
     for (int i = 0; i < ns; ++i) { cl.slot[i] = slots[i]; cl.pos[i] = v->frames_done[slots[i]]; }
-    g_voc_polite_now = beside_decoder && ns >= 16;  // (fewer slots: few and short-lived workgroups — greedy launches, the least latency)
-    const int rc = voc_call(e, cl, s);
-    g_voc_polite_now = false;
-    VTRY(rc);
+    VTRY(voc_call(e, cl, s, beside_decoder && ns >= 16));  // (fewer slots: few and short-lived workgroups — greedy launches, the least latency)
     for (int i = 0; i < ns; ++i) v->frames_done[slots[i]] += real ? real[i] : nf;
     return Q3TTS_OK;
 }
@@ -1936,83 +1941,75 @@ int q3_voc_samples(q3tts_engine* e, int slot) {
     return fr * v->spf;
 }
 
-extern "C" int q3tts_k_vocoder(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, float* pcm_out, int32_t* n_samples_out) {
+// The one drive behind q3tts_k_vocoder, _latent and _taps: codes to slot 0, reset, then the frames chunk by chunk (chunk_frames; <= 0: all at
+// once) and inside a chunk call by call (<= VOC_FCAP frames; the drive's last call flushes the look-ahead). step(call, after) runs before and
+// after every call and returns Q3TTS_OK, an error, or VOC_DRIVE_STOP to end the drive there; args_ok: the hook's own pointer checks. Once
+// calls were issued the stream is synchronised before the return, also on error: the steps' copies land in the caller's buffers.
+struct VDriveCall { int index, f0, n; bool last; };  // call number, its frames [f0, f0 + n), whether it is the drive's last
+static const int VOC_DRIVE_STOP = 1;
+template <class Step>
+static int voc_drive(q3tts_engine* e, const int32_t* codes, int n_frames, int chunk_frames, bool args_ok, Step step) {
     Q3_NOT_IN_SESSION(e);
-    if (!e || !codes || !pcm_out || !n_samples_out || n_frames <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
+    if (!e || !codes || !args_ok || n_frames <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "engine created with with_vocoder = 0");
     if (n_frames > e->cfg.max_steps_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "n_frames exceeds max_steps_cap");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
-    const int ncb = e->cfg.model.n_codebooks;
     hipStream_t s = e->stream;
-    Q3_HIP(e, hipMemcpyAsync(e->codes, codes, sizeof(int32_t) * (size_t)n_frames * ncb, hipMemcpyHostToDevice, s));  // slot 0
+    Q3_HIP(e, hipMemcpyAsync(e->codes, codes, sizeof(int32_t) * (size_t)n_frames * e->cfg.model.n_codebooks, hipMemcpyHostToDevice, s));  // slot 0
     VTRY(q3_voc_reset(e, 0));
-    const int step = chunk_frames > 0 ? chunk_frames : n_frames;
-    for (int f = 0; f < n_frames; f += step) {
-        const int n = std::min(step, n_frames - f);
-        VTRY(q3_voc_decode(e, 0, f, n, f + n >= n_frames, s));
+    const int chunk = chunk_frames > 0 ? chunk_frames : n_frames;
+    int rc = Q3TTS_OK; VDriveCall c = {0, 0, 0, false};
+    for (int f = 0; f < n_frames && rc == Q3TTS_OK; f += chunk) {
+        const int end = std::min(f + chunk, n_frames);
+        for (c.f0 = f; c.f0 < end && rc == Q3TTS_OK; c.f0 += c.n, ++c.index) {
+            c.n = std::min(VOC_FCAP, end - c.f0); c.last = c.f0 + c.n >= n_frames;
+            rc = step(c, false);
+            if (rc == Q3TTS_OK) rc = q3_voc_decode(e, 0, c.f0, c.n, c.last, s);
+            if (rc == Q3TTS_OK) rc = step(c, true);
+        }
     }
-    const int ns = q3_voc_samples(e, 0);
-    Q3_HIP(e, hipMemcpyAsync(pcm_out, q3_voc_pcm(e, 0), sizeof(float) * (size_t)ns, hipMemcpyDeviceToHost, s));
-    Q3_HIP(e, hipStreamSynchronize(s));
+    const hipError_t er = hipStreamSynchronize(s);
+    if (rc < 0) return rc;
+    Q3_HIP(e, er);
+    return rc;
+}
+
+extern "C" int q3tts_k_vocoder(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, float* pcm_out, int32_t* n_samples_out) {
+    int ns = 0;
+    VTRY(voc_drive(e, codes, n_frames, chunk_frames, pcm_out && n_samples_out, [&](const VDriveCall& c, bool after) {
+        if (!after || !c.last) return Q3TTS_OK;
+        ns = q3_voc_samples(e, 0);  // (flushed: the whole utterance)
+        Q3_HIP(e, hipMemcpyAsync(pcm_out, q3_voc_pcm(e, 0), sizeof(float) * (size_t)ns, hipMemcpyDeviceToHost, e->stream));
+        return Q3TTS_OK;
+    }));
     *n_samples_out = ns;
     return Q3TTS_OK;
 }
 
-// Test hook: slot 0 driven exactly as q3tts_k_vocoder drives it, and after every call the transformer's f32 residual rows v->x (after the
-// last layer, before the final norm; nothing later in the call writes them) copied to out[n_frames][latent_dim].
+// Test hook: after every call of the drive the transformer's f32 residual rows v->x (after the last layer, before the final norm; nothing
+// later in the call writes them) copied to out[n_frames][latent_dim].
 extern "C" int q3tts_k_vocoder_latent(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, float* out) {
-    Q3_NOT_IN_SESSION(e);
-    if (!e || !codes || !out || n_frames <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
-    if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "engine created with with_vocoder = 0");
-    if (n_frames > e->cfg.max_steps_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "n_frames exceeds max_steps_cap");
-    Q3_HIP(e, hipSetDevice(e->cfg.device));
-    const int ncb = e->cfg.model.n_codebooks, d = e->voc->c.latent_dim;
-    hipStream_t s = e->stream;
-    Q3_HIP(e, hipMemcpyAsync(e->codes, codes, sizeof(int32_t) * (size_t)n_frames * ncb, hipMemcpyHostToDevice, s));  // slot 0
-    VTRY(q3_voc_reset(e, 0));
-    const int step = chunk_frames > 0 ? chunk_frames : n_frames;
-    for (int f = 0; f < n_frames; f += step) {
-        const int n = std::min(step, n_frames - f);
-        for (int f1 = f; f1 < f + n; f1 += VOC_FCAP) {  // q3_voc_decode's own split, one call at a time so each call's rows can be read
-            const int n1 = std::min(VOC_FCAP, f + n - f1);
-            VTRY(q3_voc_decode(e, 0, f1, n1, f1 + n1 >= n_frames, s));
-            Q3_HIP(e, hipMemcpyAsync(out + (size_t)f1 * d, e->voc->x, sizeof(float) * (size_t)n1 * d, hipMemcpyDeviceToHost, s));
-        }
-    }
-    Q3_HIP(e, hipStreamSynchronize(s));
-    return Q3TTS_OK;
+    return voc_drive(e, codes, n_frames, chunk_frames, out != nullptr, [&](const VDriveCall& c, bool after) {
+        const int d = e->voc->c.latent_dim;
+        if (after) Q3_HIP(e, hipMemcpyAsync(out + (size_t)c.f0 * d, e->voc->x, sizeof(float) * (size_t)c.n * d, hipMemcpyDeviceToHost, e->stream));
+        return Q3TTS_OK;
+    });
 }
 
-// Test hook: slot 0 driven exactly as q3tts_k_vocoder drives it (same reset, same split into calls of <= VOC_FCAP frames, same launches:
-// voc_call_body itself), and call number tap_call (0-based) runs with the tap sink set — see vtap() and include/q3tts.h. The calls before
+// Test hook: call number tap_call (0-based) of the drive runs with the tap sink set — see vtap_rows() and include/q3tts.h. The calls before
 // it go through voc_call as always (eager the first time, then the captured graph); the drive ends after the tapped call.
 extern "C" int q3tts_k_vocoder_taps(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, int32_t tap_call, void* buf,
                                     uint64_t buf_bytes, q3tts_voc_tap* recs, int32_t rec_cap, int32_t* n_recs) {
-    Q3_NOT_IN_SESSION(e);
-    if (!e || !codes || !buf || !recs || !n_recs || n_frames <= 0 || tap_call < 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
-    if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "engine created with with_vocoder = 0");
-    if (n_frames > e->cfg.max_steps_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "n_frames exceeds max_steps_cap");
-    Q3_HIP(e, hipSetDevice(e->cfg.device));
-    const int ncb = e->cfg.model.n_codebooks;
-    hipStream_t s = e->stream;
-    Q3_HIP(e, hipMemcpyAsync(e->codes, codes, sizeof(int32_t) * (size_t)n_frames * ncb, hipMemcpyHostToDevice, s));  // slot 0
-    VTRY(q3_voc_reset(e, 0));
     VTapSink sink; sink.buf = (uint8_t*)buf; sink.cap = (size_t)buf_bytes; sink.recs = recs; sink.rec_cap = rec_cap;
-    const int step = chunk_frames > 0 ? chunk_frames : n_frames;
-    int call = 0, rc = Q3TTS_OK; bool done = false;
-    for (int f = 0; f < n_frames && !done && rc == Q3TTS_OK; f += step) {
-        const int n = std::min(step, n_frames - f);
-        for (int f1 = f; f1 < f + n && !done && rc == Q3TTS_OK; f1 += VOC_FCAP, ++call) {  // q3_voc_decode's own split, one call at a time
-            const int n1 = std::min(VOC_FCAP, f + n - f1);
-            if (call == tap_call) { e->voc->taps = &sink; done = true; }
-            rc = q3_voc_decode(e, 0, f1, n1, f1 + n1 >= n_frames, s);
-            e->voc->taps = nullptr;
-        }
-    }
-    const hipError_t er = hipStreamSynchronize(s);  // (the copies land in the caller's buffer: nothing may outlive this call)
-    VTRY(rc);
-    Q3_HIP(e, er);
-    if (!done) return q3_set_err(e, Q3TTS_ERR_INVALID, "tap_call is past the last call of this drive");
+    bool tapped = false;
+    const int rc = voc_drive(e, codes, n_frames, chunk_frames, buf && recs && n_recs && tap_call >= 0, [&](const VDriveCall& c, bool after) {
+        if (c.index != tap_call) return Q3TTS_OK;
+        if (!after) { e->voc->taps = &sink; tapped = true; }
+        return after ? VOC_DRIVE_STOP : Q3TTS_OK;
+    });
+    if (tapped) e->voc->taps = nullptr;
+    if (rc < 0) return rc;
+    if (rc != VOC_DRIVE_STOP) return q3_set_err(e, Q3TTS_ERR_INVALID, "tap_call is past the last call of this drive");
     if (sink.overflow) return q3_set_err(e, Q3TTS_ERR_INVALID, "tap buffer or record table too small");
     *n_recs = sink.n;
     return Q3TTS_OK;
