@@ -181,6 +181,31 @@ const char* q3tts_last_error(const q3tts_engine* e);
 int q3tts_set_sampler(q3tts_engine* e, float temperature, int32_t top_k, float top_p, int32_t has_seed, uint64_t seed);
 int q3tts_set_max_steps(q3tts_engine* e, int32_t max_steps);
 
+/* ---- Predictor sampler and repetition penalty ----------------------------------------------------------------------------
+ * Two controls of the model family's own generation code that the reference does not have: it fixes the Predictor's sampler to greedy
+ * (src/tts/engine.rs:470, LlamaSampler::greedy) and applies no penalty. Both are engine state, like the sampler above (neither
+ * q3tts_request nor q3tts_engine_config grows): they apply to every request admitted after the call, which takes a snapshot of them
+ * at admission. Defaults: temperature 0 (greedy) and penalty 1.0 (off) — with them every launch and every bit of the frame step is what
+ * it was without these calls. The setters return Q3TTS_ERR_STATE while a session or a stream is open on the engine, and
+ * Q3TTS_ERR_INVALID (state unchanged) for a NULL engine, a temperature that is negative or not finite, a top_p that is not finite, a
+ * penalty that is not finite or <= 0, and a temperature > 0 on a model whose codebook_size exceeds 4096.
+ * On a node the state is per engine, as the sampler's is: set it on every q3tts_node_engine(node, rank), rank 0 .. q3tts_node_size - 1,
+ * before q3tts_node_generate_batch; engines left with different states make a request's result depend on the device that owns it.
+ *
+ * Predictor sampler: codes 1 .. n_codebooks - 1 of every frame are drawn from their head's codebook_size logits by the reference's
+ * sampler (H4: src/models/llama/mod.rs:666-772 — `top_k as usize`, top-p cut inclusive, r < cumsum, the fallback), the one code 0 is
+ * drawn with. temperature 0: the first maximum, no draw is consumed. The draws of a request with seed S (has_seed == 0: the wall-clock
+ * seed the request resolved to) are the StdRng stream of S ^ 0x9E3779B97F4A7C15; draw frame * (n_codebooks - 1) + (q - 1) serves code q
+ * of that frame, so results stay independent of batch size, slot assignment and GPU count.
+ *
+ * Repetition penalty p on the Talker's code-0 logits: after the min_frames EOS mask and before the sample (at temperature 0 too), every
+ * logit v whose code this utterance has already GENERATED (the prompt and a voice prefix do not count) becomes v > 0 ? v / p : v * p;
+ * then the chosen code is marked. force_eos_at bypasses it. p == 1.0 leaves the logits untouched. */
+int q3tts_set_predictor_sampler(q3tts_engine* e, float temperature, int32_t top_k, float top_p);
+int q3tts_get_predictor_sampler(const q3tts_engine* e, float* temperature, int32_t* top_k, float* top_p);
+int q3tts_set_repetition_penalty(q3tts_engine* e, float penalty);   /* 1.0 = off (default) */
+int q3tts_get_repetition_penalty(const q3tts_engine* e, float* penalty);
+
 /* ---- prompt (H1: src/tts/prompt.rs:141-277 build_core, :28-118 build_clone_prompt) ------------- */
 typedef struct q3tts_prompt_desc {
     const uint32_t* text_ids;     int32_t n_text;     /* tokenizer.encode(text) */
@@ -529,6 +554,10 @@ int q3tts_k_bgemm_policy(int32_t big);
  * prompts (0 = k_attend_prefill when the launch has >= 128 (run, KV head) workgroups, default; 1 = never: k_attend<2, false>; 2 = whenever
  * eligible). Same bits either way (tests compare them in one process); Q3TTS_ATT_OLD / Q3TTS_ATT_PREFILL_OLD set the initial values. */
 int q3tts_k_attend_policy(int32_t decode, int32_t prefill);
+/* force = 1: the frame step runs its sampling form (the Predictor's heads store their logits, k_pred_next<true> picks from them) whatever the
+ * Predictor sampler's temperature; at temperature 0 that is sample_row's greedy branch, which must give the ids of the default form (the
+ * heads' ARGMAX epilogue). 0: back to the rule (sampling form iff temperature > 0). Q3TTS_ERR_STATE while a session or a stream is open. */
+int q3tts_k_pred_variant(q3tts_engine* e, int32_t force);
 /* The k_bgemm instance the launcher takes for a shape, without launching: out5 = {row tiles, column tiles, ring depth, non-temporal weight
  * loads, 1 if k_bgemm_big}. bench.py names the kernel symbol of a probed launch from it. */
 int q3tts_k_bgemm_pick(int32_t B, int32_t K, int32_t N, int32_t epilogue, int32_t w_once, int32_t q8, int32_t* out5);

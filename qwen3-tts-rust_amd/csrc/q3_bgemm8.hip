@@ -306,8 +306,9 @@ void q3_bgemm8_pick(const Q3BGemm& g, int* rt, int* nt) {
 int q3_launch_bgemm8(const Q3BGemm& g, hipStream_t s) {
     if (g.B < 1 || g.N % 32 || g.K % 512 || g.K < 512 || !g.a || !g.w || !g.wscale || !g.ascale || g.a_row0 < 0 || g.a_rt16 < 1) return -1;
     if (g.epi != Q3_EPI_STORE && g.epi != Q3_EPI_RESID && g.epi != Q3_EPI_SWIGLU && g.epi != Q3_EPI_ARGMAX) return -1;
-    // unaligned first row: the single-row pick of the prefill head, and the heads of the Predictor's pass A (its code rows start at row B)
-    if ((g.a_row0 & 15) && g.B != 1 && g.epi != Q3_EPI_ARGMAX) return -1;
+    // unaligned first row: the single-row pick of the prefill head, and the heads of the Predictor's pass A (its code rows start at row B):
+    // ARGMAX, or STORE when the Predictor samples — both write plain rows; the quantising epilogues need whole row tiles
+    if ((g.a_row0 & 15) && g.B != 1 && g.epi != Q3_EPI_ARGMAX && g.epi != Q3_EPI_STORE) return -1;
     if (g.epi == Q3_EPI_RESID && (!g.yb || !g.yscale || !g.nw_next || !g.ssp_out || g.N % 64 || g.y_rt16 < 1)) return -1;
     if (g.epi == Q3_EPI_SWIGLU && (!g.yb || !g.yscale || g.N % 128 || g.y_rt16 < 1)) return -1;
     if (g.epi == Q3_EPI_ARGMAX && (!g.keys || g.key_stride < g.N / 16)) return -1;

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #define Q3_HD __host__ __device__ __forceinline__
+#define Q3_SAMP_MAX 4096  // the sampler's widest row (sample_limit; codebook_size when the Predictor samples): its sort keys fill 32 KiB of LDS
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -87,6 +88,10 @@ struct Q3Slot {
     float temperature, top_p;
     int32_t rng_base;     // offset of this utterance's f32 draws in the rng buffer
     int32_t code0;        // code sampled in the current frame
-    int32_t steps;        // loop iterations executed (== n_frames unless EOS)
-    int32_t pad_[3];
+    // the Predictor's sampler and the code-0 repetition penalty (q3tts_set_predictor_sampler / q3tts_set_repetition_penalty), snapshotted
+    // at admission like the Talker's fields above. A free slot is all zeros: neither is read while active == 0
+    int32_t p_top_k;
+    float p_temperature, p_top_p;   // p_temperature == 0: greedy (first maximum), no draw
+    float rep_penalty;              // 1.0: off (the sampler does not touch the logits)
 };
+static_assert(sizeof(Q3Slot) == 64, "a slot is one 64-byte record");

@@ -54,8 +54,11 @@ struct Q3Lane {
     unsigned long long* keys = nullptr;
     int *row_pos_t = nullptr, *slot_id = nullptr, *perm = nullptr;
     Q3Scratch sc;
+    float* plogits = nullptr;                // [nb][codebook_size] f32: a Predictor head's logits when the Predictor samples (Q3_EPI_STORE)
     std::vector<hipGraph_t> graphs;          // per bucket
     std::vector<hipGraphExec_t> execs;
+    std::vector<hipGraph_t> graphs_s;        // the same frame step with the sampling Predictor (captured when it is first turned on)
+    std::vector<hipGraphExec_t> execs_s;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
 };
 
@@ -95,6 +98,14 @@ struct q3tts_engine {
     // sampler defaults (SamplerConfig::default: src/tts/engine.rs:25-34)
     float temperature = 0.7f; int top_k = 40; float top_p = 0.9f; int has_seed = 0; uint64_t seed = 0;
     int max_steps = 512;
+    // the Predictor's sampler and the code-0 repetition penalty (include/q3tts.h; the reference has neither): snapshotted into a request's
+    // slot at admission. pred_variant: which frame step runs — 0 the ARGMAX heads + k_pred_next<false>, 1 STORE heads + k_pred_next<true>;
+    // = (p_temperature > 0 || pred_force), fixed while anything is in flight (the setters are refused then)
+    float p_temperature = 0.0f; int p_top_k = 0; float p_top_p = 1.0f; float rep_penalty = 1.0f;
+    int pred_force = 0, pred_variant = 0;
+    int streams_open = 0;                 // q3tts_stream_begin .. q3tts_stream_end
+    float* prng = nullptr;                // [B][max_steps_cap * (n_codebooks - 1)] the Predictor's draws, positional
+    uint32_t* seen = nullptr; int seen_words = 0;  // [B][ceil(sample_limit / 32)] codes 0 generated so far, per slot
     // timing
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
     std::vector<hipEvent_t> fin_ev;     // per slot: PCM of a finished utterance copied to the host (vocoder stream)
@@ -170,5 +181,7 @@ size_t q3_voc_pcm_stride(const q3tts_engine* e);  // samples between the PCM buf
 int q3_plan_rows(q3tts_engine* e, const std::vector<int>& live);
 int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc);
 int q3_run_chunk(q3tts_engine* e, int CH);
+// test hook (q3tts_k_pred_variant): force = 1 runs the sampling frame step whatever the temperature
+int q3_pred_force_variant(q3tts_engine* e, int force);
 int q3_voc_dispatch(q3tts_engine* e, const char* live, const char* want, int* voc_frames, bool more, bool* first);
 double q3_now_ms();

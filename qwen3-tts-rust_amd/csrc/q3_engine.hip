@@ -400,7 +400,8 @@ static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
     Q3Slot* slots = e->slots;
     int* codes = e->codes;
     Q3Sample sa{}; sa.logits = L.logits; sa.ld = m.t_vocab; sa.limit = m.sample_limit; sa.eos = m.eos_code; sa.slots = slots; sa.B = B; sa.row_slot = L.slot_id;
-    sa.rng = e->rng; sa.codes = codes; sa.max_steps_cap = cap; sa.ncb = ncb;
+    sa.rng = e->rng; sa.codes = codes; sa.max_steps_cap = cap; sa.ncb = ncb; sa.seen = e->seen; sa.seen_words = e->seen_words;
+    const bool smp = e->pred_variant != 0;  // the Predictor samples: heads store their logits, k_pred_next<true> draws from them (same launch count)
     Q3PredInput pi{}; pi.xT = L.T.x; pi.out_norm = e->T.out_norm; pi.eps = eps; pi.d = de; pi.codec0 = e->codec[0]; pi.codec0_rows = m.codec0_rows;
     pi.slots = slots; pi.row_slot = L.slot_id; pi.X = nullptr; pi.fb = L.fb; pi.B = B; pi.pproj0 = e->pproj[0]; pi.proj_b = e->proj_b; pi.dp = dp; pi.px = L.P.x;
     pi.nw = e->P.attn_norm[0]; pi.xb = L.P.xb; pi.ssp = L.P.ssp;
@@ -422,7 +423,8 @@ static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
         const bool last = q == ncb - 1;
         pn.nw = last ? e->T.attn_norm[0] : e->P.attn_norm[0]; pn.xb = last ? L.T.xb : L.P.xb; pn.ssp = last ? L.T.ssp : L.P.ssp;
         if (last ? e->T.a8 : e->P.a8) { pn.xscale = last ? L.T.ascale : L.P.ascale; pn.x_rt16 = last ? L.T.rt16 : L.P.rt16; }  // W8A8 consumer: its first operand as Q8_0 blocks
-        q3_launch_pred_next(pn, s);
+        if (smp) { pn.plogits = L.plogits; pn.cbs = cbs; pn.prng = e->prng; pn.prng_stride = cap * (ncb - 1); }
+        bad += q3_launch_pred_next(pn, s, smp) != 0;
     };
     for (int q = 0; q < ncb - 1; ++q) {  // pass q produces code_{q+1}
         const int rows = q == 0 ? 2 * B : B;
@@ -435,7 +437,8 @@ static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
         // head q on the rows that carry the newest position (pass 0: rows [B, 2B)), argmax epilogue
         Q3BGemm g{}; g.a = L.P.xb; g.a_row0 = q == 0 ? B : 0; g.B = B; g.w = e->P.head + head_tile_stride * q; g.K = dp; g.N = cbs;
         g.ssp = q == 0 ? L.P.ssp + (size_t)B * (dp / 16) : L.P.ssp; g.ld_ssp = dp / 16; g.ntiles = dp / 16; g.d_norm = dp; g.eps = eps;
-        g.epi = Q3_EPI_ARGMAX; g.keys = L.keys; g.key_stride = cbs / 16;  // per-tile maxima; k_pred_next(q + 1) reduces them
+        if (smp) { g.epi = Q3_EPI_STORE; g.y = L.plogits; g.ldy = cbs; }  // the logits themselves; k_pred_next<true>(q + 1) samples from them
+        else { g.epi = Q3_EPI_ARGMAX; g.keys = L.keys; g.key_stride = cbs / 16; }  // per-tile maxima; k_pred_next(q + 1) reduces them
         if (e->P.a8) { g.wscale = e->P.shead + head_scale_stride * q; g.ascale = L.P.ascale; g.a_rt16 = L.P.rt16; bad += q3_launch_bgemm8(g, s) != 0; }
         else bad += q3_launch_bgemm(g, s) != 0;
     }
@@ -449,6 +452,21 @@ static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
     if (e->T.a8) { g.ascale = L.T.ascale; g.a_rt16 = L.T.rt16; bad += q3_launch_bgemm8(g, s) != 0; }
     else bad += q3_launch_bgemm(g, s) != 0;
     return bad;
+}
+
+// one captured frame step per row bucket, of the variant e->pred_variant names
+static int capture_frames(q3tts_engine* e, std::vector<hipGraph_t>& graphs, std::vector<hipGraphExec_t>& execs) {
+    Q3Lane& L = e->lane;
+    graphs.resize(e->buckets.size(), nullptr); execs.resize(e->buckets.size(), nullptr);
+    for (size_t bi = 0; bi < e->buckets.size(); ++bi) {
+        Q3_HIP(e, hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal));
+        const int refused = record_frame(e, L, L.stream, e->buckets[bi]);
+        Q3_HIP(e, hipStreamEndCapture(L.stream, &graphs[bi]));
+        if (refused) return q3_set_err(e, Q3TTS_ERR_INVALID, "frame step: " + std::to_string(refused) + " kernel launch(es) refused for this model shape");
+        Q3_HIP(e, hipGraphInstantiate(&execs[bi], graphs[bi], nullptr, nullptr, 0));
+        Q3_HIP(e, hipStreamSynchronize(L.stream));
+    }
+    return Q3TTS_OK;
 }
 
 static bool file_exists(const std::string& p) { FILE* f = fopen(p.c_str(), "rb"); if (f) fclose(f); return f != nullptr; }
@@ -617,6 +635,9 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     HIPC(hipHostMalloc((void**)&e->slots_host, sizeof(Q3Slot) * 2 * B, hipHostMallocDefault));
     memset(e->slots_host, 0, sizeof(Q3Slot) * 2 * B);
     TRYC(dalloc(e, &e->codes, (size_t)B * cfg->max_steps_cap * m.n_codebooks)); TRYC(dalloc(e, &e->rng, (size_t)B * cfg->max_steps_cap));
+    TRYC(dalloc(e, &e->prng, (size_t)B * cfg->max_steps_cap * (m.n_codebooks - 1)));
+    e->seen_words = (m.sample_limit + 31) / 32;
+    TRYC(dalloc(e, &e->seen, (size_t)B * e->seen_words));
     {
         const int nb = B;
         const int nqkv_max = std::max(e->T.nqkv, e->P.nqkv), nq_max = std::max(e->T.nq, e->P.nq), F_max = std::max(e->T.F, e->P.F);
@@ -627,6 +648,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
         TRYC(alloc_rows(e, L.T, (size_t)nb, m.t_d_model, e->T.a8)); TRYC(alloc_rows(e, L.P, (size_t)2 * nb, m.p_d_model, e->P.a8));
         TRYC(dalloc(e, &L.logits, (size_t)nb * m.t_vocab)); TRYC(dalloc(e, &L.logits_tmp, (size_t)nb * std::max(m.t_vocab, m.t_d_model)));
         TRYC(dalloc(e, &L.fb, (size_t)nb * m.d_embed)); TRYC(dalloc(e, &L.keys, (size_t)nb * (m.codebook_size / 16)));
+        TRYC(dalloc(e, &L.plogits, (size_t)nb * m.codebook_size));
         TRYC(dalloc(e, &L.row_pos_t, (size_t)nb)); TRYC(dalloc(e, &L.slot_id, (size_t)nb)); TRYC(dalloc(e, &L.perm, (size_t)nb));
         std::vector<int> sid(nb), rp(nb, -1);
         for (int b = 0; b < nb; ++b) sid[b] = b;
@@ -665,18 +687,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     // capture the frame step once per row-count bucket; every later frame is a replay (Q3TTS_NO_GRAPH=1: eager launches,
     // for profilers)
     HIPC(hipStreamSynchronize(s));
-    if (!(getenv("Q3TTS_NO_GRAPH") && atoi(getenv("Q3TTS_NO_GRAPH")))) {
-        Q3Lane& L = e->lane;
-        L.graphs.resize(e->buckets.size(), nullptr); L.execs.resize(e->buckets.size(), nullptr);
-        for (size_t bi = 0; bi < e->buckets.size(); ++bi) {
-            HIPC(hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal));
-            const int refused = record_frame(e, L, L.stream, e->buckets[bi]);
-            HIPC(hipStreamEndCapture(L.stream, &L.graphs[bi]));
-            if (refused) { q3_set_err(e, Q3TTS_ERR_INVALID, "frame step: " + std::to_string(refused) + " kernel launch(es) refused for this model shape"); return fail(Q3TTS_ERR_INVALID); }
-            HIPC(hipGraphInstantiate(&L.execs[bi], L.graphs[bi], nullptr, nullptr, 0));
-            HIPC(hipStreamSynchronize(L.stream));
-        }
-    }
+    if (!(getenv("Q3TTS_NO_GRAPH") && atoi(getenv("Q3TTS_NO_GRAPH")))) TRYC(capture_frames(e, e->lane.graphs, e->lane.execs));
     // algorithmic bytes of one frame step, context term added per run
     e->tm.algo_bytes_per_step = 0;
 #undef TRYC
@@ -700,8 +711,10 @@ extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
         if (L.stream) hipStreamSynchronize(L.stream);
         for (auto ge : L.execs) if (ge) hipGraphExecDestroy(ge);
         for (auto gr : L.graphs) if (gr) hipGraphDestroy(gr);
+        for (auto ge : L.execs_s) if (ge) hipGraphExecDestroy(ge);
+        for (auto gr : L.graphs_s) if (gr) hipGraphDestroy(gr);
         free_rows(L.T); free_rows(L.P); free_scratch(L.sc);
-        hipFree(L.logits); hipFree(L.logits_tmp); hipFree(L.fb); hipFree(L.keys);
+        hipFree(L.logits); hipFree(L.logits_tmp); hipFree(L.fb); hipFree(L.keys); hipFree(L.plogits);
         hipFree(L.row_pos_t); hipFree(L.slot_id); hipFree(L.perm);
         if (L.ev_begin) hipEventDestroy(L.ev_begin); if (L.ev_end) hipEventDestroy(L.ev_end);
         if (L.stream) hipStreamDestroy(L.stream);
@@ -710,7 +723,7 @@ extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
     hipFree(e->text); for (auto p : e->codec) hipFree(p); for (auto p : e->pproj) hipFree(p); hipFree((void*)e->codec_dev); hipFree(e->proj_w); hipFree(e->proj_b);
     hipFree(e->tts_pad_own); hipFree(e->marker_row); hipFree(e->dev_pcm);
     hipFree(e->slots); if (e->slots_host) hipHostFree(e->slots_host);
-    hipFree(e->codes); hipFree(e->rng);
+    hipFree(e->codes); hipFree(e->rng); hipFree(e->prng); hipFree(e->seen);
     free_scratch(e->sc_pre); free_rows(e->pf);
     hipFree(e->pf_pos); hipFree(e->pf_slot); hipFree(e->pf_seg); hipFree(e->prow_dev); hipFree(e->spk_dev); hipFree(e->refcodes_dev);
     for (auto ev : e->fin_ev) if (ev) hipEventDestroy(ev);
@@ -726,6 +739,72 @@ extern "C" int q3tts_set_sampler(q3tts_engine* e, float temperature, int32_t top
     Q3_NOT_IN_SESSION(e);
     e->temperature = temperature; e->top_k = top_k; e->top_p = top_p; e->has_seed = has_seed; e->seed = seed;
     return Q3TTS_OK;
+}
+// Predictor sampler + repetition penalty (include/q3tts.h). Engine state like the sampler's above; refused while a session or a stream is
+// open, so every live slot was admitted under the state the frame step's variant was chosen from.
+static int refuse_busy(q3tts_engine* e) {
+    if (e->streams_open > 0) return q3_set_err(e, Q3TTS_ERR_STATE, "a stream is open on this engine (q3tts_stream_end first)");
+    return Q3TTS_OK;
+}
+// the frame step e->pred_variant names must exist before the next frame: the sampling kernel's attributes (never inside a capture) and,
+// when frames are replayed from graphs, its own set of them — captured the first time the variant is needed, kept afterwards
+static int set_pred_variant(q3tts_engine* e, int variant) {
+    if (variant && e->cfg.model.codebook_size > Q3_SAMP_MAX) return q3_set_err(e, Q3TTS_ERR_INVALID, "the Predictor sampler needs codebook_size <= 4096");
+    if (!variant) { e->pred_variant = 0; return Q3TTS_OK; }
+    Q3_HIP(e, hipSetDevice(e->cfg.device));
+    if (q3_pred_next_prepare() != 0) return q3_set_err(e, Q3TTS_ERR_DEVICE, "the Predictor sampler's kernel: the device refused its LDS size (hipFuncSetAttribute)");
+    e->pred_variant = variant;
+    Q3Lane& L = e->lane;
+    if (!L.execs.empty() && L.execs_s.empty()) {
+        Q3_HIP(e, hipStreamSynchronize(e->stream));
+        const int rc = capture_frames(e, L.graphs_s, L.execs_s);
+        if (rc != Q3TTS_OK) {
+            for (auto ge : L.execs_s) if (ge) hipGraphExecDestroy(ge);
+            for (auto gr : L.graphs_s) if (gr) hipGraphDestroy(gr);
+            L.execs_s.clear(); L.graphs_s.clear(); e->pred_variant = 0;
+            return rc;
+        }
+    }
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_set_predictor_sampler(q3tts_engine* e, float temperature, int32_t top_k, float top_p) {
+    if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
+    Q3_NOT_IN_SESSION(e);
+    TRY(refuse_busy(e));
+    if (!std::isfinite(temperature) || temperature < 0.0f) return q3_set_err(e, Q3TTS_ERR_INVALID, "predictor sampler: temperature must be finite and >= 0");
+    if (!std::isfinite(top_p)) return q3_set_err(e, Q3TTS_ERR_INVALID, "predictor sampler: top_p must be finite");
+    if (temperature > 0.0f && e->cfg.model.codebook_size > Q3_SAMP_MAX) return q3_set_err(e, Q3TTS_ERR_INVALID, "the Predictor sampler needs codebook_size <= 4096");
+    TRY(set_pred_variant(e, (temperature > 0.0f || e->pred_force) ? 1 : 0));
+    e->p_temperature = temperature; e->p_top_k = top_k; e->p_top_p = top_p;
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_get_predictor_sampler(const q3tts_engine* e, float* temperature, int32_t* top_k, float* top_p) {
+    if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
+    if (temperature) *temperature = e->p_temperature;
+    if (top_k) *top_k = e->p_top_k;
+    if (top_p) *top_p = e->p_top_p;
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_set_repetition_penalty(q3tts_engine* e, float penalty) {
+    if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
+    Q3_NOT_IN_SESSION(e);
+    TRY(refuse_busy(e));
+    if (!std::isfinite(penalty) || !(penalty > 0.0f)) return q3_set_err(e, Q3TTS_ERR_INVALID, "repetition penalty must be finite and > 0");
+    e->rep_penalty = penalty;
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_get_repetition_penalty(const q3tts_engine* e, float* penalty) {
+    if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
+    if (penalty) *penalty = e->rep_penalty;
+    return Q3TTS_OK;
+}
+int q3_pred_force_variant(q3tts_engine* e, int force) {
+    TRY(refuse_busy(e));
+    const int was = e->pred_force;
+    e->pred_force = force ? 1 : 0;
+    const int rc = set_pred_variant(e, (e->p_temperature > 0.0f || e->pred_force) ? 1 : 0);
+    if (rc != Q3TTS_OK) e->pred_force = was;
+    return rc;
 }
 extern "C" int q3tts_set_max_steps(q3tts_engine* e, int32_t n) {
     if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
@@ -882,8 +961,9 @@ static int run_chunk(q3tts_engine* e, int CH, float* dev_ms) {
     Q3_HIP(e, hipEventRecord(L.ev_begin, L.stream));
     e->probe_i = 0;
     if (e->probe) { hipEventRecord(e->probe_ev[8], L.stream); hipEventRecord(e->probe_ev[9], L.stream); }  // empty bracket
+    const std::vector<hipGraphExec_t>& execs = e->pred_variant ? L.execs_s : L.execs;  // (set_pred_variant captured the second set)
     for (int i = 0; i < CH; ++i) {
-        if (!L.execs.empty() && !e->probe) { Q3_HIP(e, hipGraphLaunch(L.execs[e->cur_bucket], L.stream)); }
+        if (!execs.empty() && !e->probe) { Q3_HIP(e, hipGraphLaunch(execs[e->cur_bucket], L.stream)); }
         else {
             if (record_frame(e, L, L.stream, e->buckets[e->cur_bucket])) return q3_set_err(e, Q3TTS_ERR_INVALID, "frame step: a kernel launch was refused for this model shape");
             Q3_HIP(e, hipGetLastError());
@@ -984,11 +1064,20 @@ static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
             Q3_HIP(e, hipMemcpyAsync(e->rng + (size_t)b * e->cfg.max_steps_cap, draws.data(), (size_t)a.max_steps * 4, hipMemcpyHostToDevice, s));
             Q3_HIP(e, hipStreamSynchronize(s));
         }
+        if (e->p_temperature > 0.0f) {  // the Predictor's own stream: draw frame * (n_codebooks - 1) + (q - 1) serves code q of that frame
+            const size_t per = (size_t)(m.n_codebooks - 1), nd = (size_t)a.max_steps * per;
+            std::vector<float> draws(nd);
+            q3_stdrng_f32(seed ^ 0x9E3779B97F4A7C15ull, (int)nd, draws.data());
+            Q3_HIP(e, hipMemcpyAsync(e->prng + (size_t)b * e->cfg.max_steps_cap * per, draws.data(), nd * 4, hipMemcpyHostToDevice, s));
+            Q3_HIP(e, hipStreamSynchronize(s));
+        }
+        if (e->rep_penalty != 1.0f) Q3_HIP(e, hipMemsetAsync(e->seen + (size_t)b * e->seen_words, 0, (size_t)e->seen_words * 4, s));  // generated codes only: a prompt or a voice prefix leaves it empty
         Q3Slot* st = e->slots_host + e->B + b;  // pinned staging half
         memset(st, 0, sizeof(*st));
         st->active = 1; st->cur_pos = a.P + a.n; st->n_frames = 0; st->max_steps = a.max_steps; st->min_frames = r->min_frames;
         st->force_eos_at = r->force_eos_at; st->top_k = top_k; st->temperature = temperature; st->top_p = top_p;
         st->rng_base = b * e->cfg.max_steps_cap;
+        st->p_temperature = e->p_temperature; st->p_top_k = e->p_top_k; st->p_top_p = e->p_top_p; st->rep_penalty = e->rep_penalty;
         Q3_HIP(e, hipMemcpyAsync(e->slots + b, st, sizeof(Q3Slot), hipMemcpyHostToDevice, s));
         if (e->voc) TRY(q3_voc_reset(e, b));
     }
@@ -1397,6 +1486,7 @@ extern "C" int q3tts_stream_begin(q3tts_engine* e, const q3tts_request* req, q3t
     int rc = plan_rows(e, std::vector<int>{0});
     if (rc == Q3TTS_OK) rc = admit(e, 0, req);
     if (rc != Q3TTS_OK) { delete st; return rc; }
+    ++e->streams_open;
     *out = st;
     return Q3TTS_OK;
 }
@@ -1469,6 +1559,7 @@ extern "C" int q3tts_stream_end(q3tts_stream* st, q3tts_result* out) {
     }
     hipMemcpyAsync(e->slots, stage, sizeof(Q3Slot), hipMemcpyHostToDevice, e->stream);
     hipStreamSynchronize(e->stream);
+    --e->streams_open;
     delete st;
     return rc;
 }

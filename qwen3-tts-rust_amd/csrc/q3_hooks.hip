@@ -549,6 +549,13 @@ extern "C" int q3tts_k_attend_policy(int32_t decode, int32_t prefill) {
     return Q3TTS_OK;
 }
 
+extern "C" int q3tts_k_pred_variant(q3tts_engine* e, int32_t force) {
+    if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
+    Q3_NOT_IN_SESSION(e);
+    if (force < 0 || force > 1) return q3_set_err(e, Q3TTS_ERR_INVALID, "pred variant: 0 or 1");
+    return q3_pred_force_variant(e, force);
+}
+
 extern "C" int q3tts_k_bgemm_pick(int32_t B, int32_t K, int32_t N, int32_t epilogue, int32_t w_once, int32_t q8, int32_t* out5) {
     if (!out5 || B < 1 || K < 256 || K % 256 || N % 16) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm pick: bad shape");
     Q3BGemm g{}; g.B = B; g.K = K; g.N = N; g.epi = epilogue; g.w_once = w_once;

@@ -264,6 +264,9 @@ struct Q3Sample {
     const int* row_slot;
     const float* rng;                 // per-slot draws: rng[slot.rng_base + step]
     int* codes; int max_steps_cap; int ncb;
+    // repetition penalty (Q3Slot.rep_penalty != 1): seen[slot][seen_words] holds one bit per code 0 generated so far in the utterance
+    // (cleared at admission); a seen logit v becomes v > 0 ? v / p : v * p before the sample, the chosen code's bit is set after it
+    uint32_t* seen; int seen_words;
 };
 void q3_launch_sample(const Q3Sample& a, hipStream_t s);
 // stand-alone sampler for the test hook: n rows, explicit draws
@@ -288,6 +291,8 @@ int q3_launch_sample_input(const Q3Sample& a, const Q3PredInput& p, const Q3Proj
 
 // after pass q-1: code_q from the argmax key, record it, fb += codec_q[code_q]; q<ncb-1: px[b] = projected emb;
 // last: fb += tts_pad -> xT[b], row_pos_t[b] = cur_pos++, n_frames++
+// sample = true (q3_launch_pred_next): code_q is drawn from the head's stored logits instead — plogits[b][cbs] (the head GEMM ran Q3_EPI_STORE),
+// the slot's Predictor sampler (Q3Slot.p_*), draw prng[slot * prng_stride + frame * (ncb - 1) + (q - 1)]; keys is not read
 struct Q3PredNext {
     const unsigned long long* keys; int n_key_parts; int q; int ncb;  // keys[b][n_key_parts]: the head GEMM's per-tile maxima of pass q - 1
     const float* codec_q; int rows_q; int d;
@@ -297,9 +302,11 @@ struct Q3PredNext {
     const float* pproj_q; const float* proj_b; int dp; float* px;  // q < ncb-1: px[b] = proj(codec_q[code]) from the table
     const float* nw; uint16_t* xb; float* ssp;  // norm inputs of the row just written: px[b] (Predictor layer 0) or, last, xT[b] (Talker layer 0)
     float* xscale; int x_rt16;                  // the row's consumer is W8A8 (the Predictor for q < ncb - 1, the Talker for the last pass): xb then takes the row as Q8_0 blocks (int8 quants + these f32 block scales)
+    const float* plogits; int cbs; const float* prng; int prng_stride;   // the sampling variant only
     Q3_STAMP_FIELD
 };
-void q3_launch_pred_next(const Q3PredNext& a, hipStream_t s);
+int q3_launch_pred_next(const Q3PredNext& a, hipStream_t s, bool sample = false);  // -1: the sampling variant refuses cbs > Q3_SAMP_MAX
+int q3_pred_next_prepare();  // the sampling variant's kernel attributes, once per device; call outside stream capture. -1: the device refused them
 
 // prompt builder (H1): out[row] = tabA[idA] (+ tabB[idB]) with the reference's OOB rules
 struct Q3PromptRow { int32_t kindA, idA, kindB, idB; };  // kind: 0 none, 1 text, 2.. codec table (kind-2), -1 spk_emb, -2 zero

@@ -1037,7 +1037,7 @@ void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s) {
 // Sampler (H4: src/models/llama/mod.rs:666-772). 256 threads; keys sorted by (logit desc, index asc) which is
 // what the reference's stable descending sort of an index-ordered list produces.
 // ---------------------------------------------------------------------------------------------------
-#define SAMP_MAX 4096
+#define SAMP_MAX Q3_SAMP_MAX
 __device__ int sample_row(const float* logits, int limit, float temperature, int top_k_i, float top_p, float r,
                           unsigned long long* keys, float* probs) {
     const int tid = threadIdx.x;
@@ -1175,9 +1175,17 @@ __device__ int sample_frame(const Q3Sample& a, int b, unsigned long long* keys, 
     else {
         if (step < sl->min_frames && a.eos < a.limit) { if (tid == 0) lg[a.eos] = -INFINITY; }
         __syncthreads();
+        const float pen = sl->rep_penalty;
+        uint32_t* seen = a.seen + (size_t)slot * a.seen_words;
+        if (pen != 1.0f) {  // (uniform) the codes 0 this utterance has produced so far: IEEE division, as the restatement's
+            for (int i = tid; i < a.limit; i += 256)
+                if ((seen[i >> 5] >> (i & 31)) & 1u) { const float v = lg[i]; lg[i] = v > 0.0f ? v / pen : v * pen; }
+            __syncthreads();
+        }
         const float temperature = sl->temperature;
         const float r = temperature > 0.0f ? a.rng[sl->rng_base + step] : 0.0f;
         code0 = sample_row(lg, a.limit, temperature, sl->top_k, sl->top_p, r, keys, probs);
+        if (pen != 1.0f && tid == 0 && code0 >= 0 && code0 < a.limit) seen[code0 >> 5] |= 1u << (code0 & 31);
     }
     __syncthreads();
     if (tid == 0) {
@@ -1403,10 +1411,20 @@ int q3_launch_sample_input(const Q3Sample& a, const Q3PredInput& p, const Q3Proj
     return 0;
 }
 
+// SAMPLE = false: code_q = argmax, from the per-tile keys of the head GEMM's ARGMAX epilogue. SAMPLE = true: the head GEMM stored its
+// logits (plogits) and code_q = sample_row on them with the slot's Predictor sampler — the reference's sampler (H4) on codebook_size
+// logits; a slot whose p_temperature is 0 takes sample_row's greedy branch: the same q3_argmax_key maximum as the keys' (ties -> smaller
+// index, NaN never wins). The sampler's 48 KiB of LDS (+ the row, dynamic: cbs floats) exist in the SAMPLE instantiation only.
+template <bool SAMPLE>
 __global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
     const int b = blockIdx.x, tid = threadIdx.x, d = a.d;
-    // the per-tile keys do not depend on the slot: requested before the slot state is looked at (one round trip less on the chain)
-    unsigned long long kk = tid < a.n_key_parts ? a.keys[(size_t)b * a.n_key_parts + tid] : 0ull;
+    // the per-tile keys / the logits row do not depend on the slot: requested before the slot state is looked at (one round trip less on the chain)
+    unsigned long long kk = 0ull;
+    float lv[SAMPLE ? SAMP_MAX / 256 : 1];
+    if constexpr (SAMPLE) {
+#pragma unroll
+        for (int j = 0; j < SAMP_MAX / 256; ++j) { const int i = tid + j * 256; lv[j] = i < a.cbs ? a.plogits[(size_t)b * a.cbs + i] : 0.0f; }
+    } else kk = tid < a.n_key_parts ? a.keys[(size_t)b * a.n_key_parts + tid] : 0ull;
     const int slot = a.row_slot[b];
     Q3Slot* sl = a.slots + slot;
     const bool last = a.q == a.ncb - 1;
@@ -1414,6 +1432,20 @@ __global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
         if (last && tid == 0) a.row_pos_t[b] = -1;
         return;
     }
+    int code;
+    if constexpr (SAMPLE) {
+        __shared__ unsigned long long keys[SAMP_MAX];
+        __shared__ float probs[SAMP_MAX];
+        extern __shared__ float lrow[];  // [cbs]: sample_row reads the row up to three times
+#pragma unroll
+        for (int j = 0; j < SAMP_MAX / 256; ++j) { const int i = tid + j * 256; if (i < a.cbs) lrow[i] = lv[j]; }
+        const float temperature = sl->p_temperature;
+        // positional draw index: the same stream whatever the batch, the slot and the number of GPUs
+        const float r = temperature > 0.0f ? a.prng[(size_t)slot * a.prng_stride + (size_t)sl->n_frames * (a.ncb - 1) + (a.q - 1)] : 0.0f;
+        const int top_k = sl->p_top_k; const float top_p = sl->p_top_p;
+        __syncthreads();
+        code = sample_row(lrow, a.cbs, temperature, top_k, top_p, r, keys, probs);
+    } else {
     // code_q = argmax of the head's logits: the maximum of the per-tile keys the head GEMM left (ties -> smaller index, NaN never wins)
     __shared__ unsigned long long kmax_s[4];
     for (int t = tid + 256; t < a.n_key_parts; t += 256) { const unsigned long long o = a.keys[(size_t)b * a.n_key_parts + t]; kk = o > kk ? o : kk; }
@@ -1424,7 +1456,8 @@ __global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
     kk = kmax_s[0];
 #pragma unroll
     for (int w = 1; w < 4; ++w) kk = kmax_s[w] > kk ? kmax_s[w] : kk;
-    const int code = q3_argmax_idx(kk);
+    code = q3_argmax_idx(kk);
+    }
     const bool ok = code >= 0 && code < a.rows_q;
     const float* e = a.codec_q + (size_t)(ok ? code : 0) * d;
     const int frame = sl->n_frames;
@@ -1481,7 +1514,27 @@ __global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
         if (tid == 0) { a.row_pos_t[b] = sl->cur_pos; sl->cur_pos = sl->cur_pos + 1; sl->n_frames = frame + 1; }
     }
 }
-void q3_launch_pred_next(const Q3PredNext& a, hipStream_t s) { hipLaunchKernelGGL(k_pred_next, dim3(a.B), dim3(256), 0, s, a); }
+// the sampling variant's LDS: 48 KiB static + the row; above 64 KiB in all when cbs > ~3500, so the attribute is set once per device.
+// A device that refuses it is reported (-1) and asked again by the next call: nothing may launch the kernel on the strength of a failed call.
+int q3_pred_next_prepare() {
+    static std::mutex mu;
+    static bool done[64] = {false};
+    int dev = 0; if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    std::lock_guard<std::mutex> lk(mu);
+    if (done[dev & 63]) return 0;
+    if (hipFuncSetAttribute((const void*)k_pred_next<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SAMP_MAX * (int)sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    done[dev & 63] = true;
+    return 0;
+}
+int q3_launch_pred_next(const Q3PredNext& a, hipStream_t s, bool sample) {
+    if (!sample) { hipLaunchKernelGGL(k_pred_next<false>, dim3(a.B), dim3(256), 0, s, a); return 0; }
+    if (a.cbs < 1 || a.cbs > SAMP_MAX || !a.plogits || !a.prng || a.q < 1) return -1;
+    hipLaunchKernelGGL(k_pred_next<true>, dim3(a.B), dim3(256), (size_t)a.cbs * sizeof(float), s, a);
+    return 0;
+}
 
 // ---------------------------------------------------------------------------------------------------
 // Prompt builder (H1: src/tts/prompt.rs:141-277)

@@ -153,6 +153,8 @@ SYMBOLS = [
     "q3tts_session_last_error", "q3tts_k_pcm_pack",
     "q3tts_prefix_create", "q3tts_prefix_rows", "q3tts_prefix_destroy", "q3tts_k_talker_prefill_prefix",
     "q3tts_config_from_model_dir", "q3tts_k_gguf_meta",
+    "q3tts_set_predictor_sampler", "q3tts_get_predictor_sampler", "q3tts_set_repetition_penalty", "q3tts_get_repetition_penalty",
+    "q3tts_k_pred_variant",
 ]
 
 
@@ -185,6 +187,11 @@ def load_library(path=None):
     lib.q3tts_last_error.restype = C.c_char_p
     lib.q3tts_set_sampler.argtypes = [vp, C.c_float, C.c_int32, C.c_float, C.c_int32, C.c_uint64]
     lib.q3tts_set_max_steps.argtypes = [vp, C.c_int32]
+    lib.q3tts_set_predictor_sampler.argtypes = [vp, C.c_float, C.c_int32, C.c_float]
+    lib.q3tts_get_predictor_sampler.argtypes = [vp, f32p, i32p, f32p]
+    lib.q3tts_set_repetition_penalty.argtypes = [vp, C.c_float]
+    lib.q3tts_get_repetition_penalty.argtypes = [vp, f32p]
+    lib.q3tts_k_pred_variant.argtypes = [vp, C.c_int32]
     lib.q3tts_build_prompt.argtypes = [vp, C.POINTER(PromptDesc), C.POINTER(f32p), i32p]
     lib.q3tts_free.argtypes = [vp]
     lib.q3tts_free.restype = None

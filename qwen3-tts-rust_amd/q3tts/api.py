@@ -179,6 +179,24 @@ class TtsEngine:
     def get_sampler_config(self) -> SamplerConfig:
         return self.sampler_config
 
+    # The two controls below have no counterpart in the reference, whose Predictor is greedy (src/tts/engine.rs:470) and which applies no
+    # penalty; the defaults keep that behaviour. They apply to requests admitted after the call.
+    def set_predictor_sampler_config(self, config: SamplerConfig):
+        """Sampler of the 15 residual codes of every frame (temperature 0 = greedy, the default). config.seed is ignored: the Predictor's
+        draws are derived from each request's own seed."""
+        self._native.set_predictor_sampler(config.temperature, config.top_k, config.top_p)
+
+    def get_predictor_sampler_config(self) -> SamplerConfig:
+        t, k, p = self._native.predictor_sampler()
+        return SamplerConfig(temperature=t, top_k=k, top_p=p, seed=None)
+
+    def set_repetition_penalty(self, p: float):
+        """Repetition penalty on the Talker's code-0 logits over the codes generated so far; 1.0 = off (the default)."""
+        self._native.set_repetition_penalty(p)
+
+    def get_repetition_penalty(self) -> float:
+        return self._native.repetition_penalty()
+
     def load_speakers(self, speakers_dir):  # src/tts/engine.rs:187-208 (files that fail to parse are skipped)
         for fn in sorted(os.listdir(speakers_dir)):
             if fn.endswith(".json"):

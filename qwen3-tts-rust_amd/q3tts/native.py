@@ -107,6 +107,29 @@ class NativeEngine:
     def set_max_steps(self, n):
         self._check(self.lib.q3tts_set_max_steps(self.h, n), "q3tts_set_max_steps")
 
+    def set_predictor_sampler(self, temperature, top_k, top_p):
+        """The sampler of codes 1 .. n_codebooks - 1 (q3tts_set_predictor_sampler) for requests admitted from now on; temperature 0 = greedy,
+        the default. The reference has no such control (its Predictor is greedy)."""
+        self._check(self.lib.q3tts_set_predictor_sampler(self.h, temperature, top_k, top_p), "q3tts_set_predictor_sampler")
+
+    def predictor_sampler(self):
+        t, k, p = C.c_float(), C.c_int32(), C.c_float()
+        self._check(self.lib.q3tts_get_predictor_sampler(self.h, C.byref(t), C.byref(k), C.byref(p)), "q3tts_get_predictor_sampler")
+        return t.value, k.value, p.value
+
+    def set_repetition_penalty(self, p):
+        """Repetition penalty on the Talker's code-0 logits over the codes generated so far (q3tts_set_repetition_penalty); 1.0 = off."""
+        self._check(self.lib.q3tts_set_repetition_penalty(self.h, p), "q3tts_set_repetition_penalty")
+
+    def repetition_penalty(self):
+        p = C.c_float()
+        self._check(self.lib.q3tts_get_repetition_penalty(self.h, C.byref(p)), "q3tts_get_repetition_penalty")
+        return p.value
+
+    def k_pred_variant(self, force):
+        """Test hook: force = 1 runs the sampling form of the frame step whatever the Predictor sampler's temperature."""
+        self._check(self.lib.q3tts_k_pred_variant(self.h, int(force)), "q3tts_k_pred_variant")
+
     def build_prompt(self, desc):
         out, n = f32p(), C.c_int32()
         self._check(self.lib.q3tts_build_prompt(self.h, C.byref(desc), C.byref(out), C.byref(n)), "q3tts_build_prompt")

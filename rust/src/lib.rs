@@ -67,6 +67,11 @@ extern "C" {
     pub fn q3tts_last_error(e: *const q3tts_engine) -> *const c_char;
     pub fn q3tts_set_sampler(e: *mut q3tts_engine, temperature: c_float, top_k: i32, top_p: c_float, has_seed: i32, seed: u64) -> c_int;
     pub fn q3tts_set_max_steps(e: *mut q3tts_engine, max_steps: i32) -> c_int;
+    // Predictor sampler and code-0 repetition penalty: engine state, no counterpart in the reference (greedy Predictor, no penalty)
+    pub fn q3tts_set_predictor_sampler(e: *mut q3tts_engine, temperature: c_float, top_k: i32, top_p: c_float) -> c_int;
+    pub fn q3tts_get_predictor_sampler(e: *const q3tts_engine, temperature: *mut c_float, top_k: *mut i32, top_p: *mut c_float) -> c_int;
+    pub fn q3tts_set_repetition_penalty(e: *mut q3tts_engine, penalty: c_float) -> c_int;
+    pub fn q3tts_get_repetition_penalty(e: *const q3tts_engine, penalty: *mut c_float) -> c_int;
     pub fn q3tts_generate(e: *mut q3tts_engine, req: *const q3tts_request, out: *mut q3tts_result) -> c_int;
     pub fn q3tts_generate_batch(e: *mut q3tts_engine, reqs: *const q3tts_request, n: i32, outs: *mut q3tts_result) -> c_int;
     pub fn q3tts_result_free(r: *mut q3tts_result);
@@ -145,6 +150,32 @@ impl TtsEngine {
     pub fn set_max_steps(&mut self, steps: usize) { self.max_steps = steps; }
     pub fn set_sampler_config(&mut self, c: SamplerConfig) { self.sampler = c; }
     pub fn get_sampler_config(&self) -> &SamplerConfig { &self.sampler }
+    fn check(&self, rc: c_int, what: &str) -> Result<(), String> {
+        if rc == 0 { Ok(()) } else { Err(format!("{} failed ({}): {}", what, rc, unsafe { CStr::from_ptr(q3tts_last_error(self.raw)) }.to_string_lossy())) }
+    }
+    /// Sampler of the 15 residual codes of every frame for requests admitted from now on (temperature 0 = greedy, the default; the
+    /// reference's Predictor is always greedy). `c.seed` is ignored: the Predictor's draws derive from each request's own seed.
+    pub fn set_predictor_sampler_config(&mut self, c: &SamplerConfig) -> Result<(), String> {
+        let rc = unsafe { q3tts_set_predictor_sampler(self.raw, c.temperature, c.top_k, c.top_p) };
+        self.check(rc, "q3tts_set_predictor_sampler")
+    }
+    pub fn get_predictor_sampler_config(&self) -> Result<SamplerConfig, String> {
+        let (mut t, mut k, mut p) = (0.0 as c_float, 0i32, 0.0 as c_float);
+        let rc = unsafe { q3tts_get_predictor_sampler(self.raw, &mut t, &mut k, &mut p) };
+        self.check(rc, "q3tts_get_predictor_sampler")?;
+        Ok(SamplerConfig { temperature: t, top_k: k, top_p: p, seed: None })
+    }
+    /// Repetition penalty on the Talker's code-0 logits over the codes generated so far; 1.0 = off (the default).
+    pub fn set_repetition_penalty(&mut self, p: f32) -> Result<(), String> {
+        let rc = unsafe { q3tts_set_repetition_penalty(self.raw, p) };
+        self.check(rc, "q3tts_set_repetition_penalty")
+    }
+    pub fn get_repetition_penalty(&self) -> Result<f32, String> {
+        let mut p = 0.0 as c_float;
+        let rc = unsafe { q3tts_get_repetition_penalty(self.raw, &mut p) };
+        self.check(rc, "q3tts_get_repetition_penalty")?;
+        Ok(p)
+    }
 
     /// generate_with_voice — src/tts/engine.rs:390. `text_ids` = tokenizer.encode(text) (the tokenizer stays in Rust).
     pub fn generate_with_voice(&mut self, text_ids: &[u32], voice: &VoiceFile, instruct_ids: Option<&[u32]>) -> Result<AudioSample, String> {
