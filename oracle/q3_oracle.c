@@ -648,7 +648,7 @@ static void bgemm_rows_a8(const float* v, int n, int K, const uint16_t* wp, cons
 
 /* One transformer over n rows (positions pos0.. of one sequence), canonical arithmetic. x [n][d] is the f32 residual stream,
  * updated in place. On entry xb / ssp are the norm inputs of x for attn_norm[0] (q3o_norm_inputs); on exit for out_norm.
- * Device: run_layers in q3_engine.hip — bgemm(QKV) -> k_attend -> bgemm(O, residual + norm outputs) -> bgemm(gate/up, SwiGLU)
+ * Device: q3_run_layers in q3_layers.hip — bgemm(QKV) -> k_attend -> bgemm(O, residual + norm outputs) -> bgemm(gate/up, SwiGLU)
  * -> bgemm(down, residual + norm outputs). */
 static void tfm_layers(tfm* t, float* x, uint16_t* xb, float* ssp, int n, int pos0, float eps) {
     const int d = t->d, nq = t->Hq * t->hd, nkv = t->Hkv * t->hd, nqkv = nq + 2 * nkv, F = t->F, nt = d / 16;

@@ -66,6 +66,7 @@ struct q3tts_engine {
     q3tts_engine_config cfg;
     std::string err;
     hipStream_t stream = nullptr, vstream = nullptr;
+    std::vector<void*> allocs;          // every q3_dalloc of this engine, freed by q3tts_engine_destroy
     Q3Tfm T, P;
     // assets
     float* text = nullptr;
@@ -74,8 +75,7 @@ struct q3tts_engine {
     std::vector<float*> pproj;            // proj(codec table q) [rows_q][p_d_model] f32: the Predictor's inputs are gathers
     float* proj_w = nullptr;              // f32 [p_d_model][d_embed], as the reference keeps it (src/assets_manager.rs:212-241)
     float* proj_b = nullptr;
-    float* tts_pad = nullptr;             // = text[tts_pad_id] (or tts_pad_own: zeros, when the loaded text table is too small)
-    float* tts_pad_own = nullptr;
+    float* tts_pad = nullptr;             // = text[tts_pad_id] (or a row of zeros of its own, when the loaded text table is too small)
     float* marker_row = nullptr;          // text[tts_pad_id] through the out-of-range rule (the clone prompt's per-frame marker)
     // decode state: B = max_batch slots. A frame step runs on `rows` = the smallest bucket (1, 2, 4, ... B) that holds
     // the live slots: rows [0, n_live) carry the live slots, the rest carry distinct idle slots (row -> slot map on the
@@ -92,7 +92,7 @@ struct q3tts_engine {
     // prefill
     Q3Rows pf;                            // the prefill rows [n_ctx] (x also receives the prompt builder's rows)
     int *pf_pos = nullptr, *pf_slot = nullptr;
-    int* pf_seg = nullptr;              // the prefill launch's rows as per-slot runs {first row, n, slot, first position} (device, 4 ints each): prefill_layers uploads it and hands it to run_layers
+    int* pf_seg = nullptr;              // the prefill launch's rows as per-slot runs {first row, n, slot, first position} (device, 4 ints each): prefill_layers uploads it and hands it to q3_run_layers
     Q3PromptRow* prow_dev = nullptr; int prow_cap = 0;
     float* spk_dev = nullptr; int* refcodes_dev = nullptr;
     // sampler defaults (SamplerConfig::default: src/tts/engine.rs:25-34)
@@ -149,7 +149,54 @@ int q3_refuse_in_session(q3tts_engine* e);
 // zero-filled device memory whose fill has completed on return (the one allocator of engine, vocoder, mel and clone state)
 int q3_dev_alloc_zeroed(q3tts_engine* e, void** p, size_t bytes);
 
-// RoPE tables [n_pos][hd / 2] in double on the host (q3_engine.hip; the attention hooks build their own)
+// Device memory that lives as long as the engine: n zero-filled elements (+ 64 bytes of slack), recorded in e->allocs and freed in one loop
+// by q3tts_engine_destroy (of a whole or a half-built engine). The rule: engine lifetime -> q3_dalloc; anything shorter, or that regrows
+// (weight staging, dev_pcm, a prefix's K/V, a session's staging) -> its own hipMalloc / hipFree pair.
+template <class T>
+int q3_dalloc(q3tts_engine* e, T** p, size_t n) {
+    void* q = nullptr;
+    const int rc = q3_dev_alloc_zeroed(e, &q, n * sizeof(T) + 64);
+    if (rc != Q3TTS_OK) return rc;
+    e->allocs.push_back(q);
+    *p = (T*)q;
+    return Q3TTS_OK;
+}
+
+// weights and assets (q3_weights.hip), used by q3tts_engine_create only
+class Q3Gguf;
+struct Q3TfmShape {
+    int grp;                  // Q3G_TALKER / Q3G_PRED: the synthetic tensors' id group
+    int L, d, Hq, Hkv, hd, F, head_n;
+    float theta; const int* sections;  // RoPE base; M-RoPE sections (null: every dimension rotates)
+    int n_ctx, n_slots;       // KV cache: positions per slot, slots
+};
+// the transformer's weights, KV cache and RoPE tables. g: the opened GGUF `file` (null: seeded synthetic weights);
+// q8mode: cfg.talker_q8_0 / cfg.predictor_q8_0
+int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode);
+// text / codec tables, codec_dev, proj_w / proj_b, tts_pad and the pre-projected codec tables, from the files of wdir (empty: synthetic)
+int q3_assets_init(q3tts_engine* e, const std::string& wdir);
+
+// the two transformers' launches (q3_layers.hip)
+// What one call runs them on; a zero member means "not used":
+struct Q3LayerRun {
+    int rows;                                       // the first `rows` rows of the Q3Rows
+    const int *row_pos, *row_slot;                  // per-row position / slot maps (device); null: slot = row % slot_mod, position = pos_const (+ row / slot_mod)
+    bool one_row_per_slot;                          // decode rows: q/k prep and the K/V append are fused into the attention launch
+    hipEvent_t* probe;                              // q3tts_k_probe: two events that bracket launch e->probe_kind of block 0
+    int slot_mod, pos_const;
+    const int* seg; int n_seg, seg_max_n, seg_max_t;  // prefill of whole prompts: the rows as per-slot runs (pf_seg), the longest run, the furthest position + 1
+};
+// `a.rows` rows of r through every block of t; returns the number of launches the GEMM launcher refused
+int q3_run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& a, Q3Scratch& sc, hipStream_t s);
+// one frame step over the first B rows of the lane, issued on s; returns the number of refused launches (0 = the frame was issued completely)
+int q3_record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B);
+// one captured frame step per row bucket, of the variant e->pred_variant names
+int q3_capture_frames(q3tts_engine* e, std::vector<hipGraph_t>& graphs, std::vector<hipGraphExec_t>& execs);
+// the descriptor of head q ([q N, (q + 1) N) of t's output.weight) on rows [row0, row0 + rows) of r, and the one launch helper of t's GEMMs
+Q3BGemm q3_gemm_head(const Q3Tfm& t, int q, int N, const Q3Rows& r, int row0, int rows, float eps, int once, float* y);
+int q3_launch_gemm(q3tts_engine* e, const Q3Tfm& t, const Q3BGemm& g, hipStream_t s, hipEvent_t* probe = nullptr, int kind = -1);
+
+// RoPE tables [n_pos][hd / 2] in double on the host (q3_weights.hip; the attention hooks build their own)
 void q3_rope_tables(int n_pos, int hd, float theta, const int* sections, std::vector<float>& cs, std::vector<float>& sn);
 
 // host ChaCha12 StdRng (q3_rng.cpp)

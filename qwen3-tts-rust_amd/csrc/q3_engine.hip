@@ -1,6 +1,6 @@
-// q3_engine.hip — host side of libq3tts: weights, KV slabs, the replayable frame-step graph, batched prefill, voice prefixes,
-// the continuous batching loop and the engine part of the C ABI of include/q3tts.h (the kernel-level test hooks q3tts_k_*
-// are in q3_hooks.hip). The loop restates the reference's run_inference_stream (src/tts/engine.rs:445-656) with every
+// q3_engine.hip — host side of libq3tts: engine creation and teardown, batched prefill, voice prefixes, the continuous batching loop
+// and the engine part of the C ABI of include/q3tts.h (weights and assets: q3_weights.hip; the transformers' launches and the
+// frame step: q3_layers.hip; the kernel-level test hooks q3tts_k_*: q3_hooks.hip). The loop restates the reference's run_inference_stream (src/tts/engine.rs:445-656) with every
 // per-frame decision on the device: one graph replay = sample -> 15 predictor passes -> feedback -> Talker step, no host
 // round trip (the reference crosses the host<->backend boundary >= 33 times per frame).
 #include "q3_engine.h"
@@ -103,444 +103,23 @@ int q3_dev_alloc_zeroed(q3tts_engine* e, void** p, size_t bytes) {
     *p = q;
     return Q3TTS_OK;
 }
-template <class T>
-static int dalloc(q3tts_engine* e, T** p, size_t n) {
-    void* q = nullptr;
-    const int rc = q3_dev_alloc_zeroed(e, &q, n * sizeof(T) + 64);
-    if (rc != Q3TTS_OK) return rc;
-    *p = (T*)q;
-    return Q3TTS_OK;
-}
 #define TRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
-
-// RoPE tables in double on the host (same formula the oracle restates)
-void q3_rope_tables(int n_pos, int hd, float theta, const int* sections, std::vector<float>& cs, std::vector<float>& sn) {
-    const int half = hd / 2;
-    int s3 = half;
-    if (sections) s3 = sections[0] + sections[1] + sections[2];
-    cs.resize((size_t)n_pos * half); sn.resize((size_t)n_pos * half);
-    for (int p = 0; p < n_pos; ++p)
-        for (int i = 0; i < half; ++i) {
-            const double inv = pow((double)theta, -2.0 * (double)i / (double)hd);
-            const double ang = (i < s3) ? (double)p * inv : 0.0;
-            cs[(size_t)p * half + i] = (float)cos(ang);
-            sn[(size_t)p * half + i] = (float)sin(ang);
-        }
-}
-
-// ---- real weights: llama.cpp's tensor names for the qwen3 architecture --------------------------
-struct GgSrc {
-    q3tts_engine* e; const Q3Gguf* g; const char* file;
-    std::vector<uint16_t> host; uint16_t* dev[2] = {nullptr, nullptr}; size_t dev_cap[2] = {0, 0};
-    ~GgSrc() { for (auto p : dev) if (p) hipFree(p); for (auto p : dev8) if (p) hipFree(p); }
-    int fail(const std::string& msg) { return q3_set_err(e, Q3TTS_ERR_INVALID, std::string(file) + ": " + msg); }
-    const Q3GgufTensor* need(const std::string& name, uint64_t ne0, uint64_t ne1, int* rc) {
-        const Q3GgufTensor* t = g->find(name);
-        if (!t) { *rc = fail("tensor '" + name + "' is missing"); return nullptr; }
-        const uint64_t d1 = t->dims.size() > 1 ? t->dims[1] : 1;
-        if (t->dims[0] != ne0 || d1 != ne1 || t->dims.size() > 2) {
-            *rc = fail("tensor '" + name + "' has shape [" + std::to_string(d1) + "][" + std::to_string(t->dims[0]) + "], the configuration needs [" +
-                       std::to_string(ne1) + "][" + std::to_string(ne0) + "]");
-            return nullptr;
-        }
-        *rc = Q3TTS_OK;
-        return t;
-    }
-    // f32 vector -> device
-    int vec(const std::string& name, size_t n, float* dst) {
-        int rc; const Q3GgufTensor* t = need(name, n, 1, &rc);
-        if (!t) return rc;
-        std::vector<float> h(n); std::string err;
-        if (q3_gguf_to_f32(*t, h.data(), err)) return fail(err);
-        Q3_HIP(e, hipMemcpy(dst, h.data(), n * 4, hipMemcpyHostToDevice));  // (h is a local: synchronous copy)
-        return Q3TTS_OK;
-    }
-    // Q8_0 mode: a tensor stored as Q8_0 goes to the device as it is ([N][K/32] blocks of 34 bytes) into staging buffer `which`
-    // (raw[which] = true); any other type is widened to bf16 as below and quantised on the device
-    uint8_t* dev8[2] = {nullptr, nullptr}; size_t dev8_cap[2] = {0, 0}; bool raw[2] = {false, false};
-    int mat_q8(const std::string& name, size_t N, size_t K, int which) {
-        int rc; const Q3GgufTensor* t = need(name, K, N, &rc);
-        if (!t) return rc;
-        raw[which] = false;
-        if (t->type != Q3_GGML_Q8_0) return mat(name, N, K, which);
-        const size_t bytes = N * (K / 32) * 34;
-        if (t->nbytes < bytes) return fail("tensor '" + name + "' is shorter than its Q8_0 shape");
-        if (dev8_cap[which] < bytes) {
-            if (dev8[which]) hipFree(dev8[which]);
-            dev8[which] = nullptr; dev8_cap[which] = 0;
-            void* p = nullptr;
-            if (hipMalloc(&p, bytes) != hipSuccess) return q3_set_err(e, Q3TTS_ERR_OOM, "hipMalloc (Q8_0 staging)");
-            dev8[which] = (uint8_t*)p; dev8_cap[which] = bytes;
-        }
-        Q3_HIP(e, hipMemcpy(dev8[which], t->data, bytes, hipMemcpyHostToDevice));
-        raw[which] = true;
-        return Q3TTS_OK;
-    }
-    // [N][K] matrix -> bf16 row-major staging buffer `which` on the device
-    int mat(const std::string& name, size_t N, size_t K, int which) {
-        int rc; const Q3GgufTensor* t = need(name, K, N, &rc);
-        if (!t) return rc;
-        host.resize(N * K); std::string err;
-        if (q3_gguf_to_bf16(*t, host.data(), err)) return fail(err);
-        if (dev_cap[which] < N * K) {
-            if (dev[which]) hipFree(dev[which]);
-            dev[which] = nullptr; dev_cap[which] = 0;
-            void* p = nullptr;
-            if (hipMalloc(&p, N * K * 2) != hipSuccess) return q3_set_err(e, Q3TTS_ERR_OOM, "hipMalloc (weight staging)");
-            dev[which] = (uint16_t*)p; dev_cap[which] = N * K;
-        }
-        Q3_HIP(e, hipMemcpy(dev[which], host.data(), N * K * 2, hipMemcpyHostToDevice));
-        return Q3TTS_OK;
-    }
-};
-
-static int init_tfm(q3tts_engine* e, Q3Tfm& t, int grp, int L, int d, int Hq, int Hkv, int hd, int F, int head_n, float theta,
-                    const int* sections, int n_ctx, int n_slots, GgSrc* gg = nullptr, int q8mode = 0) {
-    const bool q8 = q8mode != 0;
-    t.L = L; t.d = d; t.Hq = Hq; t.Hkv = Hkv; t.hd = hd; t.F = F; t.nq = Hq * hd; t.nkv = Hkv * hd; t.nqkv = t.nq + 2 * t.nkv;
-    t.head_n = head_n; t.n_ctx = n_ctx; t.n_slots = n_slots; t.q8 = q8; t.a8 = q8mode == 2;
-    const uint64_t seed = e->cfg.synth_seed;
-    const float ms = 0.02f / Q3_IH4_STD, ns = 0.05f / Q3_IH4_STD;
-    hipStream_t s = e->stream;
-    t.attn_norm.resize(L); t.ffn_norm.resize(L); t.qn.resize(L); t.kn.resize(L);
-    t.wqkv.resize(L); t.wo.resize(L); t.wgu.resize(L); t.wd.resize(L);
-    if (q8) { t.sqkv.assign(L, nullptr); t.so.assign(L, nullptr); t.sgu.assign(L, nullptr); t.sd.assign(L, nullptr); }
-    // a matrix [N][K]: bf16 tiles (2 bytes per weight), or in Q8_0 mode block quants (1 byte) + f16 block scales [N][K/32]
-    const size_t wdiv = q8 ? 16 : 8;  // weights per uint4
-    auto alloc_mat = [&](uint4** w, uint16_t** sc, size_t N, size_t K) -> int {
-        TRY(dalloc(e, w, N * K / wdiv));
-        if (q8) TRY(dalloc(e, sc, N * K / 32));
-        return Q3TTS_OK;
-    };
-    auto fill = [&](Q3Fill& f, uint16_t* sc) { if (q8) { f.dst_scale = sc; q3_launch_fill_tiled_q8(f, s); } else q3_launch_fill_tiled(f, s); };
-    const double bpw = q8 ? 1.0625 : 2.0;  // bytes per weight streamed by a GEMM
-    for (int l = 0; l < L; ++l) {
-        TRY(dalloc(e, &t.attn_norm[l], (size_t)d)); TRY(dalloc(e, &t.ffn_norm[l], (size_t)d));
-        TRY(dalloc(e, &t.qn[l], (size_t)hd)); TRY(dalloc(e, &t.kn[l], (size_t)hd));
-        uint16_t *sc_qkv = nullptr, *sc_o = nullptr, *sc_gu = nullptr, *sc_d = nullptr;
-        TRY(alloc_mat(&t.wqkv[l], &sc_qkv, t.nqkv, d)); TRY(alloc_mat(&t.wo[l], &sc_o, d, t.nq));
-        TRY(alloc_mat(&t.wgu[l], &sc_gu, (size_t)2 * F, d)); TRY(alloc_mat(&t.wd[l], &sc_d, d, F));
-        if (q8) { t.sqkv[l] = sc_qkv; t.so[l] = sc_o; t.sgu[l] = sc_gu; t.sd[l] = sc_d; }
-        t.weight_bytes += (size_t)(bpw * (double)((size_t)t.nqkv * d + (size_t)d * t.nq + 3ull * F * d));
-        if (gg) {  // blk.N.* of a llama.cpp qwen3 GGUF (weights [out][in], NeoX RoPE: no q/k permutation)
-            const std::string b = "blk." + std::to_string(l) + ".";
-            Q3_HIP(e, hipStreamSynchronize(s));
-            TRY(gg->vec(b + "attn_norm.weight", d, t.attn_norm[l])); TRY(gg->vec(b + "ffn_norm.weight", d, t.ffn_norm[l]));
-            TRY(gg->vec(b + "attn_q_norm.weight", hd, t.qn[l])); TRY(gg->vec(b + "attn_k_norm.weight", hd, t.kn[l]));
-            Q3Fill f{}; f.mode = 0;
-            auto stage = [&](const std::string& name, size_t N, size_t K, int which) -> int { return q8 ? gg->mat_q8(name, N, K, which) : gg->mat(name, N, K, which); };
-            auto put = [&](const std::string& name, uint4* dst, uint16_t* sc, int Ntot, int K, int row0, int rows) -> int {
-                TRY(stage(name, rows, K, 0));
-                f.dst = dst; f.N = Ntot; f.K = K; f.mode = 0; f.row0 = row0; f.rows = rows; f.src_b = nullptr; f.src8_b = nullptr;
-                f.src_a = (q8 && gg->raw[0]) ? nullptr : gg->dev[0]; f.src8_a = (q8 && gg->raw[0]) ? gg->dev8[0] : nullptr;
-                fill(f, sc);
-                Q3_HIP(e, hipStreamSynchronize(s));  // the staging buffer is reused by the next tensor
-                return Q3TTS_OK;
-            };
-            TRY(put(b + "attn_q.weight", t.wqkv[l], sc_qkv, t.nqkv, d, 0, t.nq));
-            TRY(put(b + "attn_k.weight", t.wqkv[l], sc_qkv, t.nqkv, d, t.nq, t.nkv));
-            TRY(put(b + "attn_v.weight", t.wqkv[l], sc_qkv, t.nqkv, d, t.nq + t.nkv, t.nkv));
-            TRY(put(b + "attn_output.weight", t.wo[l], sc_o, d, t.nq, 0, d));
-            TRY(stage(b + "ffn_gate.weight", F, d, 0)); TRY(stage(b + "ffn_up.weight", F, d, 1));
-            f.dst = t.wgu[l]; f.N = 2 * F; f.K = d; f.mode = 1;
-            f.src_a = (q8 && gg->raw[0]) ? nullptr : gg->dev[0]; f.src8_a = (q8 && gg->raw[0]) ? gg->dev8[0] : nullptr;
-            f.src_b = (q8 && gg->raw[1]) ? nullptr : gg->dev[1]; f.src8_b = (q8 && gg->raw[1]) ? gg->dev8[1] : nullptr;
-            if (q8 && gg->raw[0] != gg->raw[1]) return gg->fail("ffn_gate / ffn_up of block " + std::to_string(l) + " differ in type (one Q8_0, one not)");
-            fill(f, sc_gu);
-            Q3_HIP(e, hipStreamSynchronize(s));
-            TRY(put(b + "ffn_down.weight", t.wd[l], sc_d, d, F, 0, d));
-            continue;
-        }
-        q3_launch_fill_f32(t.attn_norm[l], d, seed, Q3_TID(grp, l, Q3W_ATTN_NORM), 1.0f, ns, 0, s);
-        q3_launch_fill_f32(t.ffn_norm[l], d, seed, Q3_TID(grp, l, Q3W_FFN_NORM), 1.0f, ns, 0, s);
-        q3_launch_fill_f32(t.qn[l], hd, seed, Q3_TID(grp, l, Q3W_QNORM), 1.0f, ns, 0, s);
-        q3_launch_fill_f32(t.kn[l], hd, seed, Q3_TID(grp, l, Q3W_KNORM), 1.0f, ns, 0, s);
-        Q3Fill f{}; f.seed = seed; f.scale = ms;
-        f.dst = t.wqkv[l]; f.N = t.nqkv; f.K = d; f.mode = 0;
-        f.row0 = 0; f.rows = t.nq; f.tid_a = Q3_TID(grp, l, Q3W_Q); fill(f, sc_qkv);
-        f.row0 = t.nq; f.rows = t.nkv; f.tid_a = Q3_TID(grp, l, Q3W_K); fill(f, sc_qkv);
-        f.row0 = t.nq + t.nkv; f.rows = t.nkv; f.tid_a = Q3_TID(grp, l, Q3W_V); fill(f, sc_qkv);
-        f.dst = t.wo[l]; f.N = d; f.K = t.nq; f.row0 = 0; f.rows = d; f.tid_a = Q3_TID(grp, l, Q3W_O); fill(f, sc_o);
-        f.dst = t.wgu[l]; f.N = 2 * F; f.K = d; f.mode = 1; f.tid_a = Q3_TID(grp, l, Q3W_GATE); f.tid_b = Q3_TID(grp, l, Q3W_UP);
-        fill(f, sc_gu);
-        f.dst = t.wd[l]; f.N = d; f.K = F; f.mode = 0; f.row0 = 0; f.rows = d; f.tid_a = Q3_TID(grp, l, Q3W_DOWN); fill(f, sc_d);
-    }
-    TRY(dalloc(e, &t.out_norm, (size_t)d));
-    TRY(alloc_mat(&t.head, &t.shead, (size_t)head_n, d));
-    t.weight_bytes += (size_t)(bpw * (double)((size_t)head_n * d));
-    if (gg) {
-        Q3_HIP(e, hipStreamSynchronize(s));
-        TRY(gg->vec("output_norm.weight", d, t.out_norm));
-        TRY(q8 ? gg->mat_q8("output.weight", head_n, d, 0) : gg->mat("output.weight", head_n, d, 0));
-        Q3Fill f{}; f.dst = t.head; f.N = head_n; f.K = d; f.mode = 0; f.row0 = 0; f.rows = head_n;
-        f.src_a = (q8 && gg->raw[0]) ? nullptr : gg->dev[0]; f.src8_a = (q8 && gg->raw[0]) ? gg->dev8[0] : nullptr;
-        fill(f, t.shead);
-        Q3_HIP(e, hipStreamSynchronize(s));
-    } else {
-        q3_launch_fill_f32(t.out_norm, d, seed, Q3_TID(grp, Q3_L_MODEL, Q3WM_OUT_NORM), 1.0f, ns, 0, s);
-        Q3Fill f{}; f.seed = seed; f.scale = ms; f.dst = t.head; f.N = head_n; f.K = d; f.mode = 0; f.row0 = 0; f.rows = head_n;
-        f.tid_a = Q3_TID(grp, Q3_L_MODEL, Q3WM_HEAD); fill(f, t.shead);
-    }
-    t.layer_stride = (size_t)n_slots * Hkv * n_ctx * hd;
-    TRY(dalloc(e, &t.kc, t.layer_stride * L)); TRY(dalloc(e, &t.vc, t.layer_stride * L));
-    std::vector<float> cs, sn;
-    q3_rope_tables(n_ctx, hd, theta, sections, cs, sn);
-    TRY(dalloc(e, &t.cs, cs.size())); TRY(dalloc(e, &t.sn, sn.size()));
-    Q3_HIP(e, hipMemcpyAsync(t.cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, s));
-    Q3_HIP(e, hipMemcpyAsync(t.sn, sn.data(), sn.size() * 4, hipMemcpyHostToDevice, s));
-    Q3_HIP(e, hipStreamSynchronize(s));
-    return Q3TTS_OK;
-}
-static void free_tfm(Q3Tfm& t) {
-    for (auto p : t.attn_norm) hipFree(p); for (auto p : t.ffn_norm) hipFree(p); for (auto p : t.qn) hipFree(p);
-    for (auto p : t.kn) hipFree(p); for (auto p : t.wqkv) hipFree(p); for (auto p : t.wo) hipFree(p);
-    for (auto p : t.wgu) hipFree(p); for (auto p : t.wd) hipFree(p);
-    hipFree(t.out_norm); hipFree(t.head); hipFree(t.kc); hipFree(t.vc); hipFree(t.cs); hipFree(t.sn);
-    for (auto p : t.sqkv) hipFree(p); for (auto p : t.so) hipFree(p); for (auto p : t.sgu) hipFree(p); for (auto p : t.sd) hipFree(p);
-    hipFree(t.shead);
-}
 
 static int alloc_scratch(q3tts_engine* e, Q3Scratch& sc, int rows, int nqkv, int nq, int F) {
     sc.rows = rows;
     const size_t r16 = ((size_t)rows + 15) & ~(size_t)15;  // A-tiled buffers hold whole 16-row tiles
-    TRY(dalloc(e, &sc.qkv, (size_t)rows * nqkv)); TRY(dalloc(e, &sc.att, r16 * nq)); TRY(dalloc(e, &sc.h, r16 * F));
+    TRY(q3_dalloc(e, &sc.qkv, (size_t)rows * nqkv)); TRY(q3_dalloc(e, &sc.att, r16 * nq)); TRY(q3_dalloc(e, &sc.h, r16 * F));
     sc.rt16 = (int)(r16 / 16);
-    if (e->T.a8 || e->P.a8) { TRY(dalloc(e, &sc.asc_att, r16 * (nq / 32))); TRY(dalloc(e, &sc.asc_h, r16 * (F / 32))); }  // W8A8 (either model; nq / F are the larger of the two): block scales of both operands
+    if (e->T.a8 || e->P.a8) { TRY(q3_dalloc(e, &sc.asc_att, r16 * (nq / 32))); TRY(q3_dalloc(e, &sc.asc_h, r16 * (F / 32))); }  // W8A8 (either model; nq / F are the larger of the two): block scales of both operands
     return Q3TTS_OK;
 }
-static void free_scratch(Q3Scratch& sc) { hipFree(sc.qkv); hipFree(sc.att); hipFree(sc.h); hipFree(sc.asc_att); hipFree(sc.asc_h); }
 
 // `rows` residual rows of width d with their norm inputs (the A-tiled operand holds whole 16-row tiles); scales: the W8A8 block scales too
 static int alloc_rows(q3tts_engine* e, Q3Rows& r, size_t rows, int d, bool scales) {
     const size_t r16 = (rows + 15) & ~(size_t)15;
-    TRY(dalloc(e, &r.x, rows * d)); TRY(dalloc(e, &r.xb, r16 * d)); TRY(dalloc(e, &r.ssp, rows * (d / 16)));
+    TRY(q3_dalloc(e, &r.x, rows * d)); TRY(q3_dalloc(e, &r.xb, r16 * d)); TRY(q3_dalloc(e, &r.ssp, rows * (d / 16)));
     r.rt16 = (int)(r16 / 16);
-    if (scales) TRY(dalloc(e, &r.ascale, r16 * (d / 32)));
-    return Q3TTS_OK;
-}
-static void free_rows(Q3Rows& r) { hipFree(r.x); hipFree(r.xb); hipFree(r.ssp); hipFree(r.ascale); }
-
-// K1-K8 of SURVEY.md §8a: one decoder block per iteration, 5 launches — QKV GEMM (row scale from the producer's tile partials),
-// attention (q/k norm + RoPE + KV append fused for decode rows), O GEMM (+ residual, + the FFN norm inputs), gate/up GEMM
-// (+ SwiGLU), down GEMM (+ residual, + the next block's / the head's norm inputs). x: f32 residual rows; xb / ssp: their norm
-// inputs for attn_norm[0] on entry, for out_norm on exit. Restated by oracle/q3_oracle.c tfm_layers.
-// What one call runs them on; a zero member means "not used":
-struct Q3LayerRun {
-    int rows;                                       // the first `rows` rows of the Q3Rows
-    const int *row_pos, *row_slot;                  // per-row position / slot maps (device); null: slot = row % slot_mod, position = pos_const (+ row / slot_mod)
-    bool one_row_per_slot;                          // decode rows: q/k prep and the K/V append are fused into the attention launch
-    hipEvent_t* probe;                              // q3tts_k_probe: two events that bracket launch e->probe_kind of block 0
-    int slot_mod, pos_const;
-    const int* seg; int n_seg, seg_max_n, seg_max_t;  // prefill of whole prompts: the rows as per-slot runs (pf_seg), the longest run, the furthest position + 1
-};
-// Returns the number of launches the GEMM launcher refused (a shape it cannot run: stale activations would follow silently).
-static int run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& a, Q3Scratch& sc, hipStream_t s) {
-    // W8A8 (t.a8: talker_q8_0 = 2 / predictor_q8_0 = 2): xb / sc.att / sc.h hold Q8_0 blocks (int8 quants + the f32 block scales xscale / sc.asc_att /
-    // sc.asc_h) and every GEMM runs q3_launch_bgemm8: ggml's Q8_0 x Q8_0 arithmetic
-    auto gemm = [&](Q3BGemm& g) { return t.a8 ? q3_launch_bgemm8(g, s) : q3_launch_bgemm(g, s); };
-    const float eps = e->cfg.model.rms_eps;
-    int bad = 0;
-    const int nt = t.d / 16;
-    const int once = &t == &e->T ? 1 : 0;  // the Talker's 2.8 GB stream once per frame step; the Predictor's weights are re-read 15 times (Infinity Cache)
-    for (int l = 0; l < t.L; ++l) {
-        Q3BGemm g{};
-        g.w_once = once;
-        g.a = r.xb; g.B = a.rows; g.w = t.wqkv[l]; g.wscale = t.q8 ? t.sqkv[l] : nullptr; g.K = t.d; g.N = t.nqkv; g.ssp = r.ssp; g.ld_ssp = nt; g.ntiles = nt; g.d_norm = t.d; g.eps = eps;
-        g.epi = Q3_EPI_STORE; g.y = sc.qkv; g.ldy = t.nqkv;
-        if (t.a8) { g.ascale = r.ascale; g.a_rt16 = r.rt16; }
-        const int pk = (a.probe && l == 0) ? e->probe_kind : -1;  // which launch of block 0 the probe events bracket (q3tts_k_probe)
-        if (pk == 1) hipEventRecord(a.probe[0], s);
-        bad += gemm(g) != 0;
-        if (pk == 1) hipEventRecord(a.probe[1], s);
-        Q3QkPrep qp{}; qp.qkv = sc.qkv; qp.ld = t.nqkv; qp.rows = a.rows; qp.Hq = t.Hq; qp.Hkv = t.Hkv; qp.hd = t.hd;
-        qp.qnw = t.qn[l]; qp.knw = t.kn[l]; qp.eps = eps; qp.cs = t.cs; qp.sn = t.sn;
-        qp.kc = t.kc + l * t.layer_stride; qp.vc = t.vc + l * t.layer_stride; qp.n_ctx = t.n_ctx; qp.row_pos = a.row_pos; qp.row_slot = a.row_slot;
-        qp.slot_mod = a.slot_mod; qp.pos_const = a.pos_const;
-        const bool fused = a.one_row_per_slot && t.Hq / t.Hkv >= 2;
-        // the Predictor's pass A: rows [0, B) at position 0 and [B, 2B) at position 1 of an empty per-frame cache: one fused launch
-        const bool pair = !a.one_row_per_slot && a.slot_mod > 0 && a.rows == 2 * a.slot_mod && a.pos_const == 0 && t.Hq / t.Hkv == 2 && t.hd == 128;
-        if (!fused && !pair) q3_launch_qk_prep(qp, s);
-        Q3Attend at{}; at.qkv = sc.qkv; at.ld = t.nqkv; at.rows = a.rows; at.out = (float*)sc.att; at.ldo = t.nq; at.Hq = t.Hq; at.Hkv = t.Hkv; at.hd = t.hd;
-        at.kc = qp.kc; at.vc = qp.vc; at.n_ctx = t.n_ctx; at.row_pos = a.row_pos; at.row_slot = a.row_slot;
-        at.fused = pair ? 2 : (fused ? 1 : 0); at.prep = qp; at.out_bf16 = 1; at.slot_mod = a.slot_mod; at.pos_const = a.pos_const;
-        if (t.a8) { at.out_bf16 = 2; at.out_scale = sc.asc_att; at.out_rt16 = sc.rt16; }
-        if (!fused && !pair && a.n_seg > 0) { at.seg = a.seg; at.n_seg = a.n_seg; at.seg_max_n = a.seg_max_n; at.seg_max_t = a.seg_max_t; }  // prefill of whole prompts (prefill_layers): the launch's rows as per-slot runs
-        if (pk == 2) hipEventRecord(a.probe[0], s);
-        q3_launch_attend(at, s);
-        if (pk == 2) hipEventRecord(a.probe[1], s);
-        g = Q3BGemm{}; g.w_once = once; g.a = sc.att; g.B = a.rows; g.w = t.wo[l]; g.wscale = t.q8 ? t.so[l] : nullptr; g.K = t.nq; g.N = t.d; g.epi = Q3_EPI_RESID; g.y = r.x; g.ldy = t.d;
-        g.yb = r.xb; g.nw_next = t.ffn_norm[l]; g.ssp_out = r.ssp; g.ld_ssp_out = nt;
-        if (t.a8) { g.ascale = sc.asc_att; g.a_rt16 = sc.rt16; g.yscale = r.ascale; g.y_rt16 = r.rt16; }
-        if (pk == 3) hipEventRecord(a.probe[0], s);
-        bad += gemm(g) != 0;
-        if (pk == 3) hipEventRecord(a.probe[1], s);
-        g = Q3BGemm{}; g.w_once = once; g.a = r.xb; g.B = a.rows; g.w = t.wgu[l]; g.wscale = t.q8 ? t.sgu[l] : nullptr; g.K = t.d; g.N = 2 * t.F; g.ssp = r.ssp; g.ld_ssp = nt; g.ntiles = nt; g.d_norm = t.d;
-        g.eps = eps; g.epi = Q3_EPI_SWIGLU; g.yb = sc.h;
-        if (t.a8) { g.ascale = r.ascale; g.a_rt16 = r.rt16; g.yscale = sc.asc_h; g.y_rt16 = sc.rt16; }
-        if (pk == 0) hipEventRecord(a.probe[0], s);
-        bad += gemm(g) != 0;
-        if (pk == 0) hipEventRecord(a.probe[1], s);
-        g = Q3BGemm{}; g.w_once = once; g.a = sc.h; g.B = a.rows; g.w = t.wd[l]; g.wscale = t.q8 ? t.sd[l] : nullptr; g.K = t.F; g.N = t.d; g.epi = Q3_EPI_RESID; g.y = r.x; g.ldy = t.d;
-        g.yb = r.xb; g.nw_next = l + 1 < t.L ? t.attn_norm[l + 1] : t.out_norm; g.ssp_out = r.ssp; g.ld_ssp_out = nt;
-        if (t.a8) { g.ascale = sc.asc_h; g.a_rt16 = sc.rt16; g.yscale = r.ascale; g.y_rt16 = r.rt16; }
-        if (pk == 4) hipEventRecord(a.probe[0], s);
-        bad += gemm(g) != 0;
-        if (pk == 4) hipEventRecord(a.probe[1], s);
-    }
-    return bad;
-}
-
-// one frame: src/tts/engine.rs:545-642 for the slots [b0, b0 + nb) of one lane
-// Returns the number of refused launches (0 = the frame was issued completely).
-static int record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
-    int bad = 0;
-    const q3tts_model_config& m = e->cfg.model;
-    const int ncb = m.n_codebooks, cbs = m.codebook_size, dp = m.p_d_model, de = m.d_embed, cap = e->cfg.max_steps_cap;
-    const float eps = m.rms_eps;
-    Q3Slot* slots = e->slots;
-    int* codes = e->codes;
-    Q3Sample sa{}; sa.logits = L.logits; sa.ld = m.t_vocab; sa.limit = m.sample_limit; sa.eos = m.eos_code; sa.slots = slots; sa.B = B; sa.row_slot = L.slot_id;
-    sa.rng = e->rng; sa.codes = codes; sa.max_steps_cap = cap; sa.ncb = ncb; sa.seen = e->seen; sa.seen_words = e->seen_words;
-    const bool smp = e->pred_variant != 0;  // the Predictor samples: heads store their logits, k_pred_next<true> draws from them (same launch count)
-    Q3PredInput pi{}; pi.xT = L.T.x; pi.out_norm = e->T.out_norm; pi.eps = eps; pi.d = de; pi.codec0 = e->codec[0]; pi.codec0_rows = m.codec0_rows;
-    pi.slots = slots; pi.row_slot = L.slot_id; pi.X = nullptr; pi.fb = L.fb; pi.B = B; pi.pproj0 = e->pproj[0]; pi.proj_b = e->proj_b; pi.dp = dp; pi.px = L.P.x;
-    pi.nw = e->P.attn_norm[0]; pi.xb = L.P.xb; pi.ssp = L.P.ssp;
-    if (e->P.a8) { pi.xscale = L.P.ascale; pi.x_rt16 = L.P.rt16; }  // W8A8 Predictor: every pass-A input as Q8_0 blocks
-    {   // H6 (src/assets_manager.rs:383-399) for the hidden rows only (every code embedding arrives pre-projected), in the same launch
-        // as the sampler: the tiles normalise the Talker's raw output rows themselves
-        Q3Project pj{}; pj.x = L.T.x; pj.ldx = de; pj.rows = B; pj.w = e->proj_w; pj.bias = e->proj_b; pj.n_in = de; pj.n_out = dp; pj.y = L.P.x; pj.ldy = dp;
-        pj.nw = e->P.attn_norm[0]; pj.xb = L.P.xb; pj.ssp = L.P.ssp; pj.ld_ssp = dp / 16;  // rows [0, B) of pass A
-        pj.norm_w = e->T.out_norm; pj.eps = eps;
-        if (e->P.a8) { pj.xscale = L.P.ascale; pj.x_rt16 = L.P.rt16; }
-        bad += q3_launch_sample_input(sa, pi, pj, s) != 0;
-    }
-    // head q = rows [q cbs, (q + 1) cbs) of output.weight: uint4 per head (bf16 tiles of 32 k, Q8 tile pairs of 64 k) and its f16 block scales
-    const size_t head_tile_stride = (size_t)(cbs / 16) * (dp / (e->P.q8 ? 64 : 32)) * 64, head_scale_stride = (size_t)cbs * (dp / 32);
-    auto pred_next = [&](int q) {
-        Q3PredNext pn{}; pn.keys = L.keys; pn.n_key_parts = cbs / 16; pn.q = q; pn.ncb = ncb; pn.codec_q = e->codec[q]; pn.rows_q = m.codecq_rows; pn.d = de;
-        pn.slots = slots; pn.row_slot = L.slot_id; pn.B = B; pn.codes = codes; pn.max_steps_cap = cap; pn.fb = L.fb;
-        pn.tts_pad = e->tts_pad; pn.xT = L.T.x; pn.row_pos_t = L.row_pos_t; pn.pproj_q = e->pproj[q]; pn.proj_b = e->proj_b; pn.dp = dp; pn.px = L.P.x;
-        const bool last = q == ncb - 1;
-        pn.nw = last ? e->T.attn_norm[0] : e->P.attn_norm[0]; pn.xb = last ? L.T.xb : L.P.xb; pn.ssp = last ? L.T.ssp : L.P.ssp;
-        if (last ? e->T.a8 : e->P.a8) { pn.xscale = last ? L.T.ascale : L.P.ascale; pn.x_rt16 = last ? L.T.rt16 : L.P.rt16; }  // W8A8 consumer: its first operand as Q8_0 blocks
-        if (smp) { pn.plogits = L.plogits; pn.cbs = cbs; pn.prng = e->prng; pn.prng_stride = cap * (ncb - 1); }
-        bad += q3_launch_pred_next(pn, s, smp) != 0;
-    };
-    for (int q = 0; q < ncb - 1; ++q) {  // pass q produces code_{q+1}
-        const int rows = q == 0 ? 2 * B : B;
-        if (q > 0) pred_next(q);
-        hipEvent_t* pe = nullptr;
-        if (e->probe == 1 && q == 1 && B == L.nb && e->probe_i + 2 <= 8) { pe = &e->probe_ev[e->probe_i]; e->probe_i += 2; }
-        // the Predictor's cache lives for one frame (src/tts/engine.rs:575: cleared per frame), so it is indexed by ROW: slot = row % B,
-        // position = (q == 0 ? row / B : q + 1) — known without a load, the attention kernels request their operands at once
-        bad += run_layers(e, e->P, L.P, {.rows = rows, .one_row_per_slot = q > 0, .probe = pe, .slot_mod = B, .pos_const = q == 0 ? 0 : q + 1}, L.sc, s);
-        // head q on the rows that carry the newest position (pass 0: rows [B, 2B)), argmax epilogue
-        Q3BGemm g{}; g.a = L.P.xb; g.a_row0 = q == 0 ? B : 0; g.B = B; g.w = e->P.head + head_tile_stride * q; g.K = dp; g.N = cbs;
-        g.ssp = q == 0 ? L.P.ssp + (size_t)B * (dp / 16) : L.P.ssp; g.ld_ssp = dp / 16; g.ntiles = dp / 16; g.d_norm = dp; g.eps = eps;
-        if (smp) { g.epi = Q3_EPI_STORE; g.y = L.plogits; g.ldy = cbs; }  // the logits themselves; k_pred_next<true>(q + 1) samples from them
-        else { g.epi = Q3_EPI_ARGMAX; g.keys = L.keys; g.key_stride = cbs / 16; }  // per-tile maxima; k_pred_next(q + 1) reduces them
-        if (e->P.a8) { g.wscale = e->P.shead + head_scale_stride * q; g.ascale = L.P.ascale; g.a_rt16 = L.P.rt16; bad += q3_launch_bgemm8(g, s) != 0; }
-        else bad += q3_launch_bgemm(g, s) != 0;
-    }
-    pred_next(ncb - 1);
-    hipEvent_t* pt = nullptr;  // probe mode 2: the Talker's layer-0 gate/up GEMM (the largest GEMM of the frame step)
-    if (e->probe == 2 && B == L.nb && e->probe_i + 2 <= 8) { pt = &e->probe_ev[e->probe_i]; e->probe_i += 2; }
-    bad += run_layers(e, e->T, L.T, {.rows = B, .row_pos = L.row_pos_t, .row_slot = L.slot_id, .one_row_per_slot = true, .probe = pt}, L.sc, s);
-    Q3BGemm g{}; g.w_once = 1; g.a = L.T.xb; g.B = B; g.w = e->T.head; g.wscale = e->T.q8 ? e->T.shead : nullptr; g.K = m.t_d_model; g.N = m.t_vocab;
-    g.ssp = L.T.ssp; g.ld_ssp = m.t_d_model / 16; g.ntiles = m.t_d_model / 16; g.d_norm = m.t_d_model; g.eps = eps;
-    g.epi = Q3_EPI_STORE; g.y = L.logits; g.ldy = m.t_vocab;
-    if (e->T.a8) { g.ascale = L.T.ascale; g.a_rt16 = L.T.rt16; bad += q3_launch_bgemm8(g, s) != 0; }
-    else bad += q3_launch_bgemm(g, s) != 0;
-    return bad;
-}
-
-// one captured frame step per row bucket, of the variant e->pred_variant names
-static int capture_frames(q3tts_engine* e, std::vector<hipGraph_t>& graphs, std::vector<hipGraphExec_t>& execs) {
-    Q3Lane& L = e->lane;
-    graphs.resize(e->buckets.size(), nullptr); execs.resize(e->buckets.size(), nullptr);
-    for (size_t bi = 0; bi < e->buckets.size(); ++bi) {
-        Q3_HIP(e, hipStreamBeginCapture(L.stream, hipStreamCaptureModeThreadLocal));
-        const int refused = record_frame(e, L, L.stream, e->buckets[bi]);
-        Q3_HIP(e, hipStreamEndCapture(L.stream, &graphs[bi]));
-        if (refused) return q3_set_err(e, Q3TTS_ERR_INVALID, "frame step: " + std::to_string(refused) + " kernel launch(es) refused for this model shape");
-        Q3_HIP(e, hipGraphInstantiate(&execs[bi], graphs[bi], nullptr, nullptr, 0));
-        Q3_HIP(e, hipStreamSynchronize(L.stream));
-    }
-    return Q3TTS_OK;
-}
-
-static bool file_exists(const std::string& p) { FILE* f = fopen(p.c_str(), "rb"); if (f) fclose(f); return f != nullptr; }
-static uint16_t host_bf16(float f) {
-    uint32_t u; memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-static int upload_table(q3tts_engine* e, float** dst, const float* host, size_t n) {
-    TRY(dalloc(e, dst, n));
-    Q3_HIP(e, hipMemcpy(*dst, host, n * 4, hipMemcpyHostToDevice));  // `host` may be a temporary of the caller: synchronous copy
-    return Q3TTS_OK;
-}
-static int upload_proj(q3tts_engine* e, const float* w, const float* b) {  // proj.weight stays f32 (src/assets_manager.rs:212-241, :383-399)
-    const q3tts_model_config& m = e->cfg.model;
-    TRY(upload_table(e, &e->proj_w, w, (size_t)m.p_d_model * m.d_embed));
-    return upload_table(e, &e->proj_b, b, (size_t)m.p_d_model);
-}
-// Assets::load (src/assets_manager.rs:14-26): qwen3_assets.gguf if present, else the NPY files. Table row counts come from
-// the files (they define the out-of-range rules, :419-460); a missing text table means "every id is out of range".
-static int load_assets_files(q3tts_engine* e, const std::string& dir) {
-    q3tts_model_config& m = e->cfg.model;
-    const size_t d = (size_t)m.d_embed;
-    std::vector<std::vector<float>> tabs(1 + m.n_codebooks);  // text, codec 0..
-    std::vector<size_t> rows(1 + m.n_codebooks, 0);
-    std::vector<float> pw, pb;
-    std::string err;
-    const std::string gpath = dir + "/qwen3_assets.gguf";
-    if (file_exists(gpath)) {
-        Q3Gguf g;
-        if (g.open(gpath, err)) return q3_set_err(e, Q3TTS_ERR_INVALID, err);
-        auto fetch = [&](const std::string& name, uint64_t ne0, bool required, std::vector<float>& out, size_t* nrows) -> int {
-            const Q3GgufTensor* t = g.find(name);
-            if (!t) return required ? q3_set_err(e, Q3TTS_ERR_INVALID, gpath + ": " + name + " (tensor) missing") : Q3TTS_OK;
-            if (t->dims[0] != ne0 || t->dims.size() > 2) return q3_set_err(e, Q3TTS_ERR_INVALID, gpath + ": tensor '" + name + "' has the wrong row length");
-            out.resize(t->nelem);
-            if (q3_gguf_to_f32(*t, out.data(), err)) return q3_set_err(e, Q3TTS_ERR_INVALID, gpath + ": " + err);
-            if (nrows) *nrows = t->dims.size() > 1 ? (size_t)t->dims[1] : 1;
-            return Q3TTS_OK;
-        };
-        size_t pr = 0;
-        TRY(fetch("proj.weight", d, true, pw, &pr));
-        if (pr != (size_t)m.p_d_model) return q3_set_err(e, Q3TTS_ERR_INVALID, gpath + ": proj.weight does not have p_d_model rows");
-        TRY(fetch("proj.bias", (uint64_t)m.p_d_model, true, pb, nullptr));
-        TRY(fetch("text_embd", d, false, tabs[0], &rows[0]));
-        for (int q = 0; q < m.n_codebooks; ++q) TRY(fetch("codec_embd." + std::to_string(q), d, true, tabs[1 + q], &rows[1 + q]));
-    } else {
-        auto fetch = [&](const std::string& file, bool required, std::vector<float>& out, size_t* nrows, size_t row_len) -> int {
-            const std::string path = dir + "/" + file;
-            if (!file_exists(path)) return required ? q3_set_err(e, Q3TTS_ERR_INVALID, "neither qwen3_assets.gguf nor " + file + " in " + dir) : Q3TTS_OK;
-            std::vector<size_t> shape;
-            if (q3_npy_load_f32(path, out, shape, err)) return q3_set_err(e, Q3TTS_ERR_INVALID, err);
-            if (out.size() % row_len) return q3_set_err(e, Q3TTS_ERR_INVALID, path + ": size is not a multiple of the row length");
-            if (nrows) *nrows = out.size() / row_len;
-            return Q3TTS_OK;
-        };
-        size_t pr = 0, br = 0;
-        TRY(fetch("proj_weight.npy", true, pw, &pr, d));
-        TRY(fetch("proj_bias.npy", true, pb, &br, 1));
-        if (pr != (size_t)m.p_d_model || br != (size_t)m.p_d_model) return q3_set_err(e, Q3TTS_ERR_INVALID, dir + ": projection shape does not match p_d_model");
-        TRY(fetch("text_embedding_projected.npy", false, tabs[0], &rows[0], d));
-        for (int q = 0; q < m.n_codebooks; ++q) TRY(fetch("codec_embedding_" + std::to_string(q) + ".npy", true, tabs[1 + q], &rows[1 + q], d));
-    }
-    for (int q = 2; q < m.n_codebooks; ++q)
-        if (rows[1 + q] != rows[2]) return q3_set_err(e, Q3TTS_ERR_INVALID, dir + ": codec tables 1.." + std::to_string(m.n_codebooks - 1) + " differ in size");
-    m.text_vocab = (int32_t)rows[0]; m.codec0_rows = (int32_t)rows[1];
-    if (m.n_codebooks > 1) m.codecq_rows = (int32_t)rows[2];
-    if (rows[0]) TRY(upload_table(e, &e->text, tabs[0].data(), tabs[0].size()));
-    e->codec.resize(m.n_codebooks);
-    for (int q = 0; q < m.n_codebooks; ++q) TRY(upload_table(e, &e->codec[q], tabs[1 + q].data(), tabs[1 + q].size()));
-    TRY(upload_proj(e, pw.data(), pb.data()));
-    // tts_pad = row 151671 of the text table when it is that large, else zeros (src/assets_manager.rs:244-249)
-    if ((size_t)m.tts_pad_id < rows[0]) e->tts_pad = e->text + (size_t)m.tts_pad_id * d;
-    else { TRY(dalloc(e, &e->tts_pad_own, d)); Q3_HIP(e, hipMemset(e->tts_pad_own, 0, d * 4)); e->tts_pad = e->tts_pad_own; }
+    if (scales) TRY(q3_dalloc(e, &r.ascale, r16 * (d / 32)));
     return Q3TTS_OK;
 }
 
@@ -577,67 +156,30 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     HIPC(hipEventCreate(&e->ev0)); HIPC(hipEventCreate(&e->ev1)); HIPC(hipEventCreate(&e->ev2)); HIPC(hipEventCreate(&e->ev3));
     e->fin_ev.resize(cfg->max_batch, nullptr);
     for (auto& ev : e->fin_ev) HIPC(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    q3tts_model_config& m = e->cfg.model;  // (table row counts follow the files when weights_path is given)
+    const q3tts_model_config& m = e->cfg.model;  // (q3_assets_init: the table row counts follow the files when weights_path is given)
     const int B = cfg->max_batch;
     e->B = B;
     hipStream_t s = e->stream;
-    // weights_path = the reference's quant directory (src/tts/engine.rs:91-131): qwen3_tts_talker.gguf,
-    // qwen3_tts_predictor.gguf, qwen3_assets.gguf (or the NPY fallback). NULL: seeded synthetic weights.
+    // weights_path: the reference's quant directory (q3_weights.hip); NULL: seeded synthetic weights
     const std::string wdir = cfg->weights_path ? cfg->weights_path : "";
     Q3Gguf gt, gp;
-    GgSrc st{e, &gt, "qwen3_tts_talker.gguf"}, sp{e, &gp, "qwen3_tts_predictor.gguf"};
-    if (!wdir.empty()) {
-        std::string er;
-        if (gt.open(wdir + "/qwen3_tts_talker.gguf", er) || gp.open(wdir + "/qwen3_tts_predictor.gguf", er)) { q3_set_err(e, Q3TTS_ERR_INVALID, er); return fail(Q3TTS_ERR_INVALID); }
-    }
-    TRYC(init_tfm(e, e->T, Q3G_TALKER, m.t_n_layer, m.t_d_model, m.t_n_head, m.t_n_kv_head, m.t_head_dim, m.t_d_ffn, m.t_vocab,
-                  m.t_rope_theta, m.t_mrope_sections, cfg->n_ctx, B, wdir.empty() ? nullptr : &st, cfg->talker_q8_0));
-    TRYC(init_tfm(e, e->P, Q3G_PRED, m.p_n_layer, m.p_d_model, m.p_n_head, m.p_n_kv_head, m.p_head_dim, m.p_d_ffn,
-                  (m.n_codebooks - 1) * m.codebook_size, m.p_rope_theta, nullptr, 64, B, wdir.empty() ? nullptr : &sp, cfg->predictor_q8_0));
-    // assets (F32 tables like qwen3_assets.gguf: src/assets_manager.rs:212-241; values bf16-representable)
-    const uint64_t seed = cfg->synth_seed;
-    const float es = 0.05f / Q3_IH4_STD;
-    if (!wdir.empty()) {
-        TRYC(load_assets_files(e, wdir));
-        { void* cd = nullptr; HIPC(hipMalloc(&cd, sizeof(float*) * 16)); e->codec_dev = (const float**)cd; }
-        HIPC(hipMemcpyAsync((void*)e->codec_dev, e->codec.data(), sizeof(float*) * m.n_codebooks, hipMemcpyHostToDevice, s));
-    } else {
-    TRYC(dalloc(e, &e->text, (size_t)m.text_vocab * m.d_embed));
-    q3_launch_fill_f32(e->text, (size_t)m.text_vocab * m.d_embed, seed, Q3_TID(Q3G_ASSET, 0, Q3WA_TEXT), 0.0f, es, 1, s);
-    e->codec.resize(m.n_codebooks);
-    for (int q = 0; q < m.n_codebooks; ++q) {
-        const size_t rows = q == 0 ? m.codec0_rows : m.codecq_rows;
-        TRYC(dalloc(e, &e->codec[q], rows * m.d_embed));
-        q3_launch_fill_f32(e->codec[q], rows * m.d_embed, seed, Q3_TID(Q3G_ASSET, 1 + q, 0), 0.0f, es, 1, s);
-    }
-    { void* cd = nullptr; HIPC(hipMalloc(&cd, sizeof(float*) * 16)); e->codec_dev = (const float**)cd; }
-    HIPC(hipMemcpyAsync((void*)e->codec_dev, e->codec.data(), sizeof(float*) * m.n_codebooks, hipMemcpyHostToDevice, s));
-    TRYC(dalloc(e, &e->proj_w, (size_t)m.p_d_model * m.d_embed));  // f32 [out][in]; synthetic values are bf16-representable like every synthetic matrix
-    q3_launch_fill_f32(e->proj_w, (size_t)m.p_d_model * m.d_embed, seed, Q3_TID(Q3G_ASSET, 0, Q3WA_PROJ_W), 0.0f, 0.02f / Q3_IH4_STD, 1, s);
-    TRYC(dalloc(e, &e->proj_b, (size_t)m.p_d_model));
-    q3_launch_fill_f32(e->proj_b, m.p_d_model, seed, Q3_TID(Q3G_ASSET, 0, Q3WA_PROJ_B), 0.0f, 0.02f / Q3_IH4_STD, 0, s);
-    e->tts_pad = e->text + (size_t)m.tts_pad_id * m.d_embed;  // src/assets_manager.rs:244-249
-    }
-    // pre-projected codec tables: proj(codec_q[code]) for every code, computed once with the projection kernel (a row's result
-    // does not depend on the other rows, so a table row equals the on-the-fly projection bit for bit): the 15 Predictor passes
-    // after the first read their input with a gather instead of a projection launch each
-    e->pproj.assign(m.n_codebooks, nullptr);
-    for (int q = 0; q < m.n_codebooks; ++q) {
-        const int rows = q == 0 ? m.codec0_rows : m.codecq_rows;
-        TRYC(dalloc(e, &e->pproj[q], (size_t)rows * m.p_d_model));
-        Q3Project pj{}; pj.x = e->codec[q]; pj.ldx = m.d_embed; pj.rows = rows; pj.w = e->proj_w; pj.bias = e->proj_b; pj.n_in = m.d_embed; pj.n_out = m.p_d_model;
-        pj.y = e->pproj[q]; pj.ldy = m.p_d_model;
-        q3_launch_project(pj, s);
-    }
-    HIPC(hipStreamSynchronize(s));
+    std::string er;
+    if (!wdir.empty() && (gt.open(wdir + "/qwen3_tts_talker.gguf", er) || gp.open(wdir + "/qwen3_tts_predictor.gguf", er))) { q3_set_err(e, Q3TTS_ERR_INVALID, er); return fail(Q3TTS_ERR_INVALID); }
+    TRYC(q3_tfm_init(e, e->T, {.grp = Q3G_TALKER, .L = m.t_n_layer, .d = m.t_d_model, .Hq = m.t_n_head, .Hkv = m.t_n_kv_head, .hd = m.t_head_dim, .F = m.t_d_ffn,
+                               .head_n = m.t_vocab, .theta = m.t_rope_theta, .sections = m.t_mrope_sections, .n_ctx = cfg->n_ctx, .n_slots = B},
+                     wdir.empty() ? nullptr : &gt, "qwen3_tts_talker.gguf", cfg->talker_q8_0));
+    TRYC(q3_tfm_init(e, e->P, {.grp = Q3G_PRED, .L = m.p_n_layer, .d = m.p_d_model, .Hq = m.p_n_head, .Hkv = m.p_n_kv_head, .hd = m.p_head_dim, .F = m.p_d_ffn,
+                               .head_n = (m.n_codebooks - 1) * m.codebook_size, .theta = m.p_rope_theta, .sections = nullptr, .n_ctx = 64, .n_slots = B},
+                     wdir.empty() ? nullptr : &gp, "qwen3_tts_predictor.gguf", cfg->predictor_q8_0));
+    TRYC(q3_assets_init(e, wdir));
     // decode state
-    TRYC(dalloc(e, &e->slots, (size_t)B));
+    TRYC(q3_dalloc(e, &e->slots, (size_t)B));
     HIPC(hipHostMalloc((void**)&e->slots_host, sizeof(Q3Slot) * 2 * B, hipHostMallocDefault));
     memset(e->slots_host, 0, sizeof(Q3Slot) * 2 * B);
-    TRYC(dalloc(e, &e->codes, (size_t)B * cfg->max_steps_cap * m.n_codebooks)); TRYC(dalloc(e, &e->rng, (size_t)B * cfg->max_steps_cap));
-    TRYC(dalloc(e, &e->prng, (size_t)B * cfg->max_steps_cap * (m.n_codebooks - 1)));
+    TRYC(q3_dalloc(e, &e->codes, (size_t)B * cfg->max_steps_cap * m.n_codebooks)); TRYC(q3_dalloc(e, &e->rng, (size_t)B * cfg->max_steps_cap));
+    TRYC(q3_dalloc(e, &e->prng, (size_t)B * cfg->max_steps_cap * (m.n_codebooks - 1)));
     e->seen_words = (m.sample_limit + 31) / 32;
-    TRYC(dalloc(e, &e->seen, (size_t)B * e->seen_words));
+    TRYC(q3_dalloc(e, &e->seen, (size_t)B * e->seen_words));
     {
         const int nb = B;
         const int nqkv_max = std::max(e->T.nqkv, e->P.nqkv), nq_max = std::max(e->T.nq, e->P.nq), F_max = std::max(e->T.F, e->P.F);
@@ -646,10 +188,10 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
         HIPC(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
         HIPC(hipEventCreate(&L.ev_begin)); HIPC(hipEventCreate(&L.ev_end));
         TRYC(alloc_rows(e, L.T, (size_t)nb, m.t_d_model, e->T.a8)); TRYC(alloc_rows(e, L.P, (size_t)2 * nb, m.p_d_model, e->P.a8));
-        TRYC(dalloc(e, &L.logits, (size_t)nb * m.t_vocab)); TRYC(dalloc(e, &L.logits_tmp, (size_t)nb * std::max(m.t_vocab, m.t_d_model)));
-        TRYC(dalloc(e, &L.fb, (size_t)nb * m.d_embed)); TRYC(dalloc(e, &L.keys, (size_t)nb * (m.codebook_size / 16)));
-        TRYC(dalloc(e, &L.plogits, (size_t)nb * m.codebook_size));
-        TRYC(dalloc(e, &L.row_pos_t, (size_t)nb)); TRYC(dalloc(e, &L.slot_id, (size_t)nb)); TRYC(dalloc(e, &L.perm, (size_t)nb));
+        TRYC(q3_dalloc(e, &L.logits, (size_t)nb * m.t_vocab)); TRYC(q3_dalloc(e, &L.logits_tmp, (size_t)nb * std::max(m.t_vocab, m.t_d_model)));
+        TRYC(q3_dalloc(e, &L.fb, (size_t)nb * m.d_embed)); TRYC(q3_dalloc(e, &L.keys, (size_t)nb * (m.codebook_size / 16)));
+        TRYC(q3_dalloc(e, &L.plogits, (size_t)nb * m.codebook_size));
+        TRYC(q3_dalloc(e, &L.row_pos_t, (size_t)nb)); TRYC(q3_dalloc(e, &L.slot_id, (size_t)nb)); TRYC(q3_dalloc(e, &L.perm, (size_t)nb));
         std::vector<int> sid(nb), rp(nb, -1);
         for (int b = 0; b < nb; ++b) sid[b] = b;
         HIPC(hipMemcpyAsync(L.slot_id, sid.data(), nb * 4, hipMemcpyHostToDevice, s));
@@ -665,15 +207,15 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     }
     TRYC(alloc_scratch(e, e->sc_pre, cfg->n_ctx, e->T.nqkv, e->T.nq, e->T.F));
     TRYC(alloc_rows(e, e->pf, (size_t)cfg->n_ctx, m.t_d_model, e->T.a8));
-    TRYC(dalloc(e, &e->pf_pos, (size_t)cfg->n_ctx)); TRYC(dalloc(e, &e->pf_slot, (size_t)cfg->n_ctx)); TRYC(dalloc(e, &e->pf_seg, (size_t)4 * cfg->max_batch));
+    TRYC(q3_dalloc(e, &e->pf_pos, (size_t)cfg->n_ctx)); TRYC(q3_dalloc(e, &e->pf_slot, (size_t)cfg->n_ctx)); TRYC(q3_dalloc(e, &e->pf_seg, (size_t)4 * cfg->max_batch));
     { std::vector<int> pp(cfg->n_ctx); for (int i = 0; i < cfg->n_ctx; ++i) pp[i] = i;
       HIPC(hipMemcpyAsync(e->pf_pos, pp.data(), pp.size() * 4, hipMemcpyHostToDevice, s)); HIPC(hipStreamSynchronize(s)); }
     e->prow_cap = cfg->n_ctx;
-    TRYC(dalloc(e, &e->prow_dev, (size_t)e->prow_cap)); TRYC(dalloc(e, &e->spk_dev, (size_t)m.d_embed));
-    TRYC(dalloc(e, &e->refcodes_dev, (size_t)cfg->n_ctx * 16));
+    TRYC(q3_dalloc(e, &e->prow_dev, (size_t)e->prow_cap)); TRYC(q3_dalloc(e, &e->spk_dev, (size_t)m.d_embed));
+    TRYC(q3_dalloc(e, &e->refcodes_dev, (size_t)cfg->n_ctx * 16));
     {   // the marker row text[151671] through the table's out-of-range rule (src/assets_manager.rs:444-460): a missing or short text
         // table gives the fallback pattern, never a null / out-of-bounds read (the clone prompt adds this row to every reference frame)
-        TRYC(dalloc(e, &e->marker_row, (size_t)m.d_embed));
+        TRYC(q3_dalloc(e, &e->marker_row, (size_t)m.d_embed));
         const Q3PromptRow mr{1, m.tts_pad_id, 0, 0};
         HIPC(hipMemcpyAsync(e->prow_dev, &mr, sizeof(mr), hipMemcpyHostToDevice, s));
         HIPC(hipStreamSynchronize(s));
@@ -684,12 +226,9 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
         TRYC(q3_voc_create(e));
         HIPC(hipHostMalloc((void**)&e->first_chunk_host, sizeof(float) * 4 * (size_t)q3_voc_samples_per_frame(e), hipHostMallocDefault));
     }
-    // capture the frame step once per row-count bucket; every later frame is a replay (Q3TTS_NO_GRAPH=1: eager launches,
-    // for profilers)
+    // capture the frame step once per row-count bucket; every later frame is a replay (Q3TTS_NO_GRAPH=1: eager launches, for profilers)
     HIPC(hipStreamSynchronize(s));
-    if (!(getenv("Q3TTS_NO_GRAPH") && atoi(getenv("Q3TTS_NO_GRAPH")))) TRYC(capture_frames(e, e->lane.graphs, e->lane.execs));
-    // algorithmic bytes of one frame step, context term added per run
-    e->tm.algo_bytes_per_step = 0;
+    if (!(getenv("Q3TTS_NO_GRAPH") && atoi(getenv("Q3TTS_NO_GRAPH")))) TRYC(q3_capture_frames(e, e->lane.graphs, e->lane.execs));
 #undef TRYC
 #undef HIPC
     *out = e;
@@ -713,19 +252,12 @@ extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
         for (auto gr : L.graphs) if (gr) hipGraphDestroy(gr);
         for (auto ge : L.execs_s) if (ge) hipGraphExecDestroy(ge);
         for (auto gr : L.graphs_s) if (gr) hipGraphDestroy(gr);
-        free_rows(L.T); free_rows(L.P); free_scratch(L.sc);
-        hipFree(L.logits); hipFree(L.logits_tmp); hipFree(L.fb); hipFree(L.keys); hipFree(L.plogits);
-        hipFree(L.row_pos_t); hipFree(L.slot_id); hipFree(L.perm);
         if (L.ev_begin) hipEventDestroy(L.ev_begin); if (L.ev_end) hipEventDestroy(L.ev_end);
         if (L.stream) hipStreamDestroy(L.stream);
     }
-    free_tfm(e->T); free_tfm(e->P);
-    hipFree(e->text); for (auto p : e->codec) hipFree(p); for (auto p : e->pproj) hipFree(p); hipFree((void*)e->codec_dev); hipFree(e->proj_w); hipFree(e->proj_b);
-    hipFree(e->tts_pad_own); hipFree(e->marker_row); hipFree(e->dev_pcm);
-    hipFree(e->slots); if (e->slots_host) hipHostFree(e->slots_host);
-    hipFree(e->codes); hipFree(e->rng); hipFree(e->prng); hipFree(e->seen);
-    free_scratch(e->sc_pre); free_rows(e->pf);
-    hipFree(e->pf_pos); hipFree(e->pf_slot); hipFree(e->pf_seg); hipFree(e->prow_dev); hipFree(e->spk_dev); hipFree(e->refcodes_dev);
+    for (void* p : e->allocs) hipFree(p);  // every q3_dalloc: weights, tables, caches, rows, scratch, decode and prefill state
+    hipFree(e->dev_pcm);                   // regrows per batch: its own pair (q3tts_generate_batch)
+    if (e->slots_host) hipHostFree(e->slots_host);
     for (auto ev : e->fin_ev) if (ev) hipEventDestroy(ev);
     for (auto ev : e->probe_ev) if (ev) hipEventDestroy(ev);
     if (e->ev0) hipEventDestroy(e->ev0); if (e->ev1) hipEventDestroy(e->ev1); if (e->ev2) hipEventDestroy(e->ev2); if (e->ev3) hipEventDestroy(e->ev3);
@@ -757,7 +289,7 @@ static int set_pred_variant(q3tts_engine* e, int variant) {
     Q3Lane& L = e->lane;
     if (!L.execs.empty() && L.execs_s.empty()) {
         Q3_HIP(e, hipStreamSynchronize(e->stream));
-        const int rc = capture_frames(e, L.graphs_s, L.execs_s);
+        const int rc = q3_capture_frames(e, L.graphs_s, L.execs_s);
         if (rc != Q3TTS_OK) {
             for (auto ge : L.execs_s) if (ge) hipGraphExecDestroy(ge);
             for (auto gr : L.graphs_s) if (gr) hipGraphDestroy(gr);
@@ -965,7 +497,7 @@ static int run_chunk(q3tts_engine* e, int CH, float* dev_ms) {
     for (int i = 0; i < CH; ++i) {
         if (!execs.empty() && !e->probe) { Q3_HIP(e, hipGraphLaunch(execs[e->cur_bucket], L.stream)); }
         else {
-            if (record_frame(e, L, L.stream, e->buckets[e->cur_bucket])) return q3_set_err(e, Q3TTS_ERR_INVALID, "frame step: a kernel launch was refused for this model shape");
+            if (q3_record_frame(e, L, L.stream, e->buckets[e->cur_bucket])) return q3_set_err(e, Q3TTS_ERR_INVALID, "frame step: a kernel launch was refused for this model shape");
             Q3_HIP(e, hipGetLastError());
         }
     }
@@ -1017,7 +549,7 @@ static int prefill_layers(q3tts_engine* e, const std::vector<int>& pos, const st
     const Q3Rows& r = e->pf;
     if (e->T.a8) q3_launch_norm_inputs_q8(r.x, d, rows, d, e->T.attn_norm[0], (int8_t*)r.xb, r.ascale, r.rt16, r.ssp, d / 16, s);
     else q3_launch_norm_inputs(r.x, d, rows, d, e->T.attn_norm[0], r.xb, 0, r.ssp, d / 16, s);
-    return run_layers(e, e->T, r, {.rows = rows, .row_pos = e->pf_pos, .row_slot = e->pf_slot, .seg = e->pf_seg, .n_seg = (int)seg.size() / 4,
+    return q3_run_layers(e, e->T, r, {.rows = rows, .row_pos = e->pf_pos, .row_slot = e->pf_slot, .seg = e->pf_seg, .n_seg = (int)seg.size() / 4,
                                    .seg_max_n = seg_max_n, .seg_max_t = seg_max_t}, e->sc_pre, s);
 }
 
@@ -1048,12 +580,9 @@ static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
         Q3Lane& L = e->lane;
         const int row = e->row_of_slot[b];
         q3_launch_copy_rows(L.T.x + (size_t)row * m.t_d_model, m.t_d_model, e->pf.x + (size_t)(a.row0 + a.n - 1) * m.t_d_model, m.t_d_model, 1, m.t_d_model, s);
-        const size_t lastr = (size_t)(a.row0 + a.n - 1);  // the last prompt row's norm inputs for out_norm came out of the last block
-        Q3BGemm g{}; g.a = e->pf.xb; g.a_row0 = (int)lastr; g.B = 1; g.w = e->T.head; g.wscale = e->T.q8 ? e->T.shead : nullptr; g.K = m.t_d_model; g.N = m.t_vocab;
-        g.ssp = e->pf.ssp + lastr * (m.t_d_model / 16); g.ld_ssp = m.t_d_model / 16; g.ntiles = m.t_d_model / 16; g.d_norm = m.t_d_model; g.eps = m.rms_eps;
-        g.epi = Q3_EPI_STORE; g.y = L.logits + (size_t)row * m.t_vocab; g.ldy = m.t_vocab;
-        if (e->T.a8) { g.ascale = e->pf.ascale; g.a_rt16 = e->pf.rt16; }
-        if (e->T.a8 ? q3_launch_bgemm8(g, s) : q3_launch_bgemm(g, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefill head: launch refused for this model shape");
+        // the last prompt row's norm inputs for out_norm came out of the last block
+        if (q3_launch_gemm(e, e->T, q3_gemm_head(e->T, 0, m.t_vocab, e->pf, a.row0 + a.n - 1, 1, m.rms_eps, 0, L.logits + (size_t)row * m.t_vocab), s))
+            return q3_set_err(e, Q3TTS_ERR_INVALID, "prefill head: launch refused for this model shape");
         // sampler stream (src/tts/engine.rs:473-485)
         float temperature = e->temperature, top_p = e->top_p; int top_k = e->top_k, has_seed = e->has_seed; uint64_t seed = e->seed;
         if (!r->use_engine_sampler) { temperature = r->temperature; top_k = r->top_k; top_p = r->top_p; has_seed = r->has_seed; seed = r->seed; }

@@ -7,7 +7,7 @@
 //     /root/reference/src/models/llama/mod.rs:360-398), for the tensor types the released quant dirs use that this engine
 //     can take: F32, F16, BF16, Q8_0 and the K-quants Q4_K / Q5_K / Q6_K of the gguf_q5_k_m directory (src/tts/engine.rs:91-95);
 //     every type is de-quantised on the host and stored as bf16 (the decoder's weight format), other types are refused loudly.
-// Files are mmap'ed; tensors are converted on the host and uploaded by the engine (q3_engine.hip).
+// Files are mmap'ed; tensors are converted on the host and uploaded by the engine (q3_weights.hip).
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -671,14 +671,23 @@ def test_mel_matches_oracle(oracle, tiny, n):
         assert np.abs(got - ref).max() <= 4e-6, float(np.abs(got - ref).max())
 
 
-def test_probe_mode_is_transparent(oracle, tiny):
-    """q3tts_k_probe (bench.py's in-situ kernel timer): eager frame steps with event brackets give the same ids as graph
-    replay and report a positive mean duration for the probed launches."""
+@pytest.fixture(scope="module")
+def probe_ref(oracle, tiny):
+    """Four seeded requests (a full row bucket of the tiny engine) and their codes by graph replay, computed once."""
     cfg, eng, om = tiny
     desc, keep = oracle.make_prompt_desc(np.arange(70, 80), spk_emb=_spk(cfg.model.d_embed))
     reqs = [dict(desc=desc, temperature=0.7, seed=40 + i, max_steps=12, min_frames=8, force_eos_at=8) for i in range(4)]
-    ref = [o.codes for o in eng.generate_batch(reqs)]
-    eng.probe(True)
+    return reqs, keep, [o.codes for o in eng.generate_batch(reqs)]
+
+
+@pytest.mark.parametrize("kind", [0, 1, 2, 3, 4])   # q3tts_k_probe's numbering (ABI): gate/up, QKV, attention, O, down
+@pytest.mark.parametrize("model", [2, 1])           # the Talker's block 0, the Predictor's (pass 1, block 0)
+def test_probe_mode_is_transparent(tiny, probe_ref, model, kind):
+    """q3tts_k_probe (bench.py's in-situ kernel timer): eager frame steps with event brackets give the same ids as graph
+    replay and report a positive mean duration for the probed launches, whichever launch of the block the events bracket."""
+    cfg, eng, om = tiny
+    reqs, keep, ref = probe_ref
+    eng.probe(model + 16 * kind)
     try:
         outs = eng.generate_batch(reqs)
         tm = eng.timings()
