@@ -120,7 +120,7 @@ extern "C" int q3tts_k_gemm_exact(int32_t device, const float* x, int32_t B, int
 
 extern "C" int q3tts_k_attention(int32_t device, const float* qkv, int32_t n_rows, int32_t pos0, int32_t Hq, int32_t Hkv, int32_t hd,
                                  const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, float* out) {
-    if (!qkv || !out || hd != 128 || n_rows <= 0 || Hq % Hkv) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention hook: bad shape");
+    if (!qkv || !out || hd != 128 || n_rows <= 0 || Hkv <= 0 || Hq % Hkv) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention hook: bad shape");
     HK(hipSetDevice(device));
     const int n_ctx = ((pos0 + n_rows + 63) / 64) * 64, ld = (Hq + 2 * Hkv) * hd;
     std::vector<float> cs, sn;
@@ -134,10 +134,10 @@ extern "C" int q3tts_k_attention(int32_t device, const float* qkv, int32_t n_row
     TRY(drp.put(rp.data(), n_rows * 4)); TRY(drs.put(rs.data(), n_rows * 4));
     Q3QkPrep qp{}; qp.qkv = dq; qp.ld = ld; qp.rows = n_rows; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = hd; qp.qnw = dqn; qp.knw = dkn; qp.eps = eps;
     qp.cs = dcs; qp.sn = dsn; qp.kc = dkc; qp.vc = dvc; qp.n_ctx = n_ctx; qp.row_pos = drp; qp.row_slot = drs;
-    q3_launch_qk_prep(qp, nullptr);
+    if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention hook: the q/k prep launch was refused");
     Q3Attend at{}; at.qkv = dq; at.ld = ld; at.rows = n_rows; at.out = dout; at.ldo = Hq * hd; at.Hq = Hq; at.Hkv = Hkv; at.hd = hd;
     at.kc = dkc; at.vc = dvc; at.n_ctx = n_ctx; at.row_pos = qp.row_pos; at.row_slot = qp.row_slot;
-    q3_launch_attend(at, nullptr);
+    if (q3_launch_attend(at, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention hook: the attention launch was refused");
     HK(hipDeviceSynchronize());
     return dout.get(out, (size_t)n_rows * Hq * hd * 4);
 }
@@ -189,7 +189,7 @@ extern "C" int q3tts_k_attention_decode(int32_t device, const float* qkv, int32_
     if (npre) { HK(hipMemcpy(dpp.p, pp.data(), npre * 4, hipMemcpyHostToDevice)); HK(hipMemcpy(dps.p, ps.data(), npre * 4, hipMemcpyHostToDevice)); }
     Q3QkPrep qp{}; qp.qkv = dpre; qp.ld = ld; qp.rows = npre; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = hd; qp.qnw = dqn; qp.knw = dkn; qp.eps = eps;
     qp.cs = dcs; qp.sn = dsn; qp.kc = dkc; qp.vc = dvc; qp.n_ctx = n_ctx; qp.row_pos = dpp; qp.row_slot = dps;
-    if (npre) q3_launch_qk_prep(qp, nullptr);
+    if (npre && q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode hook: the q/k prep launch was refused");
     int old_dec = 0, old_pre = 0;
     q3_attend_policy_get(&old_dec, &old_pre);
     if (policy >= 0) q3_attend_policy(policy, old_pre);
@@ -202,7 +202,7 @@ extern "C" int q3tts_k_attention_decode(int32_t device, const float* qkv, int32_
         at.fused = 1; at.prep = dq;
         if (pass == 0) { at.out = dout; at.out_bf16 = 0; }
         else { at.out = dob; at.out_bf16 = 1; }
-        q3_launch_attend(at, nullptr);
+        if (q3_launch_attend(at, nullptr)) { q3_attend_policy(old_dec, old_pre); return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode hook: the attention launch was refused"); }
         const hipError_t er = hipDeviceSynchronize();
         if (er != hipSuccess) { q3_attend_policy(old_dec, old_pre); return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, std::string("attention decode hook: ") + hipGetErrorString(er)); }
     }

@@ -15,15 +15,21 @@ enum { Q3_EPI_STORE = 0, Q3_EPI_RESID = 1, Q3_EPI_SWIGLU = 2, Q3_EPI_ARGMAX = 3,
 #endif
 
 // Kernel attributes (dynamic LDS above 64 KiB) belong to a function ON A DEVICE: a process that drives several GPUs (q3tts_node_*)
-// has to set them once per device, not once per process. need(dev_value) returns true when the current device has not yet been given
-// a value >= dev_value; the caller then sets the attribute and calls done(dev_value). One lock per launch site, uncontended.
+// has to set them once per device, not once per process. ensure(want, set_attr) runs set_attr when the current device has not yet been
+// given a value >= want. set_attr returns nothing, or a hipError_t: then a failure is not recorded and ensure returns false (the caller
+// refuses its launch). One lock per launch site, uncontended.
 #include <mutex>
+#include <type_traits>
 struct Q3PerDevice {
     std::mutex mu; size_t have[64] = {0};
-    template <class F> void ensure(size_t want, F set_attr) {
+    template <class F> bool ensure(size_t want, F set_attr) {
         int dev = 0; if (hipGetDevice(&dev) != hipSuccess) dev = 0;
         std::lock_guard<std::mutex> lk(mu);
-        if (have[dev & 63] < want) { set_attr(); have[dev & 63] = want; }
+        if (have[dev & 63] >= want) return true;
+        if constexpr (std::is_void_v<decltype(set_attr())>) set_attr();
+        else if (set_attr() != hipSuccess) return false;
+        have[dev & 63] = want;
+        return true;
     }
 };
 
@@ -135,6 +141,17 @@ int q3_launch_project(const Q3Project& p, hipStream_t s);
 // was written to GLOBAL memory by another wave of the workgroup; data brought by LDS-DMA needs its own s_waitcnt vmcnt(N) before it.
 #define Q3_LDS_BARRIER() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
 #ifdef __HIPCC__
+// 64-lane butterflies (xor 32, 16, 8, 4, 2, 1): the canonical order of every wave-wide sum / maximum
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
 __device__ __forceinline__ void q3_row_map(int row, const int* row_pos, const int* row_slot, int slot_mod, int pos_const, int* pos, int* slot) {
     if (slot_mod > 0) { *slot = row % slot_mod; *pos = pos_const + row / slot_mod; }
     else { *pos = row_pos[row]; *slot = *pos < 0 ? 0 : row_slot[row]; }
@@ -210,6 +227,9 @@ void q3_launch_fill_tiled(const Q3Fill& f, hipStream_t s);
 void q3_launch_fill_tiled_q8(const Q3Fill& f, hipStream_t s);
 void q3_launch_fill_f32(float* dst, size_t n, uint64_t seed, uint32_t tid, float base, float scale, int round_bf16, hipStream_t s);
 
+// The one head size of the attention kernels (q3_attend.hip). The hd fields of Q3QkPrep / Q3Attend say what the caller has; the launchers
+// refuse anything else.
+constexpr int Q3_ATT_HD = 128;
 // q/k RMSNorm + RoPE (q in place) + bf16 K/V append. One wave per (row, head).
 struct Q3QkPrep {
     float* qkv; int ld; int rows;
@@ -220,7 +240,7 @@ struct Q3QkPrep {
     const int* row_pos; const int* row_slot;
     int slot_mod, pos_const;  // slot_mod > 0: slot = row % slot_mod, pos = pos_const + row / slot_mod (no loads: the Predictor's per-frame cache is indexed by row)
 };
-void q3_launch_qk_prep(const Q3QkPrep& a, hipStream_t s);
+int q3_launch_qk_prep(const Q3QkPrep& a, hipStream_t s);  // 0: launched; nonzero: refused (hd != Q3_ATT_HD), nothing launched
 
 // decode / prefill attention over the cache (canonical order DESIGN.md §4.4). One workgroup per (kv head, row).
 struct Q3Attend {
@@ -234,16 +254,16 @@ struct Q3Attend {
     const int* row_pos; const int* row_slot;
     int slot_mod, pos_const;  // as in Q3QkPrep
     int fused;        // 1: every slot has exactly one row in this launch -> q/k prep + KV append done in-kernel (R >= 2)
-                      // 2: rows b (position 0) and slot_mod + b (position 1) of every slot, nothing cached yet (R == 2, hd == 128): k_attend_pair
+                      // 2: rows b (position 0) and slot_mod + b (position 1) of every slot, nothing cached yet (R == 2): k_attend_pair
     Q3QkPrep prep;    // used when fused
     // prefill (fused == 0): the launch's rows as per-slot runs of consecutive positions pos0 .. pos0 + n - 1 — seg[i] = {first row, n, slot,
     // pos0}, device memory; pos0 > 0 when the slot's first pos0 positions hold a voice prefix (q3tts_prefix). seg_max_n = max n,
-    // seg_max_t = max (pos0 + n). With it (and hd = 128, two query heads per KV head, every n <= 128, every pos0 + n <= 256) one workgroup
+    // seg_max_t = max (pos0 + n). With it (and two query heads per KV head, every n <= 128, every pos0 + n <= 256) one workgroup
     // serves a whole run from LDS: k_attend_prefill
     const int* seg; int n_seg; int seg_max_n; int seg_max_t;
     Q3_STAMP_FIELD
 };
-void q3_launch_attend(const Q3Attend& a, hipStream_t s);
+int q3_launch_attend(const Q3Attend& a, hipStream_t s);  // 0: launched; nonzero: refused (see its definition), nothing launched
 // Voice prefixes (q3tts_prefix): copy a prefix store into slots before their prefill. A store is laid out as one slot's cache of
 // np = ceil(P / 64) * 64 positions: k / v [L][Hkv][np * hd] bf16 (keys in 64-position blocks, values row-major). Entry j copies every
 // layer's whole key blocks and the values of positions < P[j] into slot[j]; keys at positions P .. np - 1 of the slot are overwritten.

@@ -82,7 +82,7 @@ int q3_launch_gemm(q3tts_engine* e, const Q3Tfm& t, const Q3BGemm& g, hipStream_
 // attention (q/k norm + RoPE + KV append fused for decode rows), O GEMM (+ residual, + the FFN norm inputs), gate/up GEMM
 // (+ SwiGLU), down GEMM (+ residual, + the next block's / the head's norm inputs). x: f32 residual rows; xb / ssp: their norm
 // inputs for attn_norm[0] on entry, for out_norm on exit. Restated by oracle/q3_oracle.c tfm_layers.
-// Returns the number of launches the GEMM launcher refused (a shape it cannot run: stale activations would follow silently).
+// Returns the number of launches a launcher refused (a shape it cannot run: stale activations would follow silently).
 int q3_run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& a, Q3Scratch& sc, hipStream_t s) {
     const float eps = e->cfg.model.rms_eps;
     int bad = 0;
@@ -97,13 +97,13 @@ int q3_run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& 
         const bool fused = a.one_row_per_slot && t.Hq / t.Hkv >= 2;
         // the Predictor's pass A: rows [0, B) at position 0 and [B, 2B) at position 1 of an empty per-frame cache: one fused launch
         const bool pair = !a.one_row_per_slot && a.slot_mod > 0 && a.rows == 2 * a.slot_mod && a.pos_const == 0 && t.Hq / t.Hkv == 2 && t.hd == 128;
-        if (!fused && !pair) q3_launch_qk_prep(qp, s);
+        if (!fused && !pair) bad += q3_launch_qk_prep(qp, s) ? 1 : 0;
         Q3Attend at{}; at.qkv = sc.qkv; at.ld = t.nqkv; at.rows = a.rows; at.out = (float*)sc.att; at.ldo = t.nq; at.Hq = t.Hq; at.Hkv = t.Hkv; at.hd = t.hd;
         at.kc = qp.kc; at.vc = qp.vc; at.n_ctx = t.n_ctx; at.row_pos = a.row_pos; at.row_slot = a.row_slot;
         at.fused = pair ? 2 : (fused ? 1 : 0); at.prep = qp; at.out_bf16 = 1; at.slot_mod = a.slot_mod; at.pos_const = a.pos_const;
         if (t.a8) { at.out_bf16 = 2; at.out_scale = sc.asc_att; at.out_rt16 = sc.rt16; }
         if (!fused && !pair && a.n_seg > 0) { at.seg = a.seg; at.n_seg = a.n_seg; at.seg_max_n = a.seg_max_n; at.seg_max_t = a.seg_max_t; }  // prefill of whole prompts (prefill_layers): the launch's rows as per-slot runs
-        bad += probed(e, pe, 2, s, [&] { q3_launch_attend(at, s); return false; });
+        bad += probed(e, pe, 2, s, [&] { return q3_launch_attend(at, s) != 0; });
         bad += q3_launch_gemm(e, t, gemm_o(t, l, r, sc, a.rows, once), s, pe, 3);
         bad += q3_launch_gemm(e, t, gemm_gate_up(t, l, r, sc, a.rows, eps, once), s, pe, 0);
         bad += q3_launch_gemm(e, t, gemm_down(t, l, r, sc, a.rows, once), s, pe, 4);

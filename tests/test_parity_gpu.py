@@ -97,7 +97,7 @@ def test_gemm_exact_residual_swiglu_argmax(oracle, native):
     assert np.array_equal(k, k_ref)
 
 
-@pytest.mark.parametrize("n_rows,pos0,Hq,Hkv", [(1, 0, 2, 1), (5, 0, 4, 2), (3, 70, 4, 2), (2, 300, 16, 8), (1, 1000, 4, 4)])
+@pytest.mark.parametrize("n_rows,pos0,Hq,Hkv", [(1, 0, 2, 1), (5, 0, 4, 2), (3, 70, 4, 2), (3, 70, 4, 1), (2, 300, 16, 8), (1, 1000, 4, 4)])
 def test_attention_exact(oracle, native, n_rows, pos0, Hq, Hkv):
     # the hook starts from an empty cache, so rows before pos0 are zero keys in both implementations
     rng = np.random.default_rng(100 + pos0 + Hq)
@@ -113,6 +113,21 @@ def test_attention_exact(oracle, native, n_rows, pos0, Hq, Hkv):
                     1e6, oracle.ptr(sec, oracle.i32p), oracle.ptr(ref, oracle.f32p))
     out = native.k_attention(qkv, 0, Hq, Hkv, hd, qn, kn, 1e-6, 1e6, sec)
     assert np.array_equal(_bits(out), _bits(ref))
+
+
+def test_attention_refuses_unsupported_gqa_ratio(native):
+    """The attention launcher serves 1, 2 or 4 query heads per KV head (fused decode: 2 or 4); any other ratio is refused before a
+    launch and the hooks report Q3TTS_ERR_INVALID (-1) instead of running a kernel built for another geometry."""
+    from q3tts import _abi
+    rng = np.random.default_rng(7)
+    hd = 128
+    qn = np.ones(hd, dtype=np.float32)
+    sec = np.array([24, 20, 20, 0], dtype=np.int32)
+    for Hq, Hkv in [(3, 1), (8, 1)]:
+        with pytest.raises(_abi.Q3Error, match=r"\(-1\).*refused"):
+            native.k_attention(_rand(rng, (2, (Hq + 2 * Hkv) * hd)), 0, Hq, Hkv, hd, qn, qn, 1e-6, 1e6, sec)
+    with pytest.raises(_abi.Q3Error, match=r"\(-1\).*refused"):
+        native.k_attention_decode(_rand(rng, (3, (6 + 2 * 2) * hd)), [3], 64, 6, 2, hd, qn, qn, 1e-6, 1e6, sec)
 
 
 def test_sampler_matches_oracle(oracle, native):

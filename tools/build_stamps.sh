@@ -9,9 +9,10 @@ chain)
   F="--offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -w -DQ3_STAMPS -I $C"
   hipcc $F -c $C/q3_bgemm.hip -o tools/exp/bs/cs_bgemm.o &
   hipcc $F -c $C/q3_kernels.hip -o tools/exp/bs/cs_kernels.o &
+  hipcc $F -c $C/q3_attend.hip -o tools/exp/bs/cs_attend.o &
   hipcc $F -c tools/chain_stamps.hip -o tools/exp/bs/cs_main.o &
   wait
-  hipcc --offload-arch=gfx950 -o tools/chain_stamps tools/exp/bs/cs_main.o tools/exp/bs/cs_bgemm.o tools/exp/bs/cs_kernels.o;;
+  hipcc --offload-arch=gfx950 -o tools/chain_stamps tools/exp/bs/cs_main.o tools/exp/bs/cs_bgemm.o tools/exp/bs/cs_kernels.o tools/exp/bs/cs_attend.o;;
 voc)
   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -std=c++17 -w -DQ3_VOC_STAMPS -c $C/q3_vocoder.hip -o tools/exp/bs/vs_vocoder.o
   O=$(ls $C/build/*.o | grep -v q3_vocoder)

@@ -1,4 +1,4 @@
-// Where do the microseconds of a decoder block go? Replays a chain of the engine's own kernels (csrc/q3_bgemm.hip, q3_kernels.hip built
+// Where do the microseconds of a decoder block go? Replays a chain of the engine's own kernels (csrc/q3_bgemm.hip, q3_attend.hip, q3_kernels.hip built
 // with -DQ3_STAMPS) inside one hipGraph and prints, per launch, constant-rate (100 MHz) timestamps taken INSIDE the kernels by every
 // workgroup: when the first / last workgroup started, the phases of the median workgroup, when the last one finished, and the gap between
 // the previous kernel's last store and this kernel's first instruction (= the real launch-to-launch cost, which a tracer cannot see).
