@@ -229,6 +229,30 @@ void q3tts_free(void* p);
 int q3tts_set_device_pcm(q3tts_engine* e, int32_t enable);
 int q3tts_get_device_pcm(q3tts_engine* e, float** base, int64_t* stride_samples, int32_t* n_rows);
 
+/* ---- output sample rate and a one-shot resampler ---------------------------------------------------------------
+ * The vocoder speaks its own rate (24 kHz). q3tts_set_output_rate(e, R) makes the engine resample on the device, by a rational
+ * polyphase Kaiser-windowed sinc filter whose f32 summation order is fixed, so that everything below is reproducible bit for bit:
+ *   - q3tts_generate / q3tts_generate_batch with want_pcm = 1, q3tts_stream_poll chunks (and q3tts_stream_end's PCM), session chunks in
+ *     f32 and i16 carry rate R; result.sample_rate = R and result.n_samples = N(ns) = ceil(ns L / M) for ns vocoder samples, with
+ *     L / M = R / 24000 in lowest terms;
+ *   - a chunk that is not an utterance's last carries the outputs whose filter windows end inside the PCM produced so far,
+ *     D(ns) = ceil((ns - H) L / M) minus those already delivered; the last one carries the rest. The chunks of an utterance joined are
+ *     its one-shot PCM bit for bit, as at the native rate. The added latency is H input samples (104 = 4.3 ms at 8 kHz, 35 = 1.5 ms at
+ *     48 kHz); first_chunk_ms keeps its meaning (the first native-rate chunk resident on the host).
+ * R = 0 or the vocoder's own rate turns it off (the default): every launch and every bit is then what it is without this call.
+ * Engine state like q3tts_set_predictor_sampler: Q3TTS_ERR_STATE while a session or a stream is open. Device-resident PCM
+ * (q3tts_set_device_pcm, want_pcm = 2) and the node's i16 gather stay native-rate: the setter returns Q3TTS_ERR_STATE while device PCM
+ * is enabled, and q3tts_set_device_pcm(e, 1) is refused while a rate is set. Q3TTS_ERR_INVALID outside 4000..96000 Hz,
+ * Q3TTS_ERR_UNSUPPORTED when the pair needs more than 32768 coefficients (L x T); a refused call leaves the state as it was.
+ * f32 output is not clamped (overshoot above +-1 is expected on a full-scale input); i16 is the Q3TTS_PCM_I16 rule on the resampled value.
+ * The reference has neither: it emits 24 kHz and refuses clone clips at any other rate (src/tts/engine.rs:341). */
+int q3tts_set_output_rate(q3tts_engine* e, int32_t rate);
+int q3tts_get_output_rate(const q3tts_engine* e, int32_t* rate);   /* 0 = off */
+/* One-shot: the finished clip in[0, n_in) at rate_in -> *n_out = ceil(n_in L / M) samples at rate_out in out (cap samples; too small:
+ * Q3TTS_ERR_INVALID with *n_out set). Host buffers, the same kernel and table on the engine's device; the table of a pair is built once
+ * and kept on the engine (64 pairs at the most). The rates must differ. This is the clone path's entry for clips that are not 24 kHz. */
+int q3tts_resample(q3tts_engine* e, const float* in, int64_t n_in, int32_t rate_in, int32_t rate_out, float* out, int64_t cap, int64_t* n_out);
+
 /* ---- generation (run_inference_stream: src/tts/engine.rs:445-656) ------------------------------ */
 typedef struct q3tts_prefix q3tts_prefix;  /* a voice prefix: see "voice prefixes" below */
 typedef struct q3tts_request {
@@ -600,6 +624,16 @@ int q3tts_k_alloc_upload(q3tts_engine* e, int64_t bytes, int64_t* mismatches);
  * the reference's WAV rule. Windows outside src or out (out_n samples) are refused. */
 int q3tts_k_pcm_pack(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* ent_row, const int32_t* ent_first,
                      const int32_t* ent_count, const int64_t* ent_dst, int32_t n_ent, int32_t format, void* out, int64_t out_n);
+/* The resampler's coefficient table, host only (no GPU needed): L, M, H of the pair and tab[p][k], L x (2H + 1) values
+ * computed in double and rounded once to f32; *n = L x (2H + 1) (cap too small: Q3TTS_ERR_INVALID with L, M, H and *n set). */
+int q3tts_k_resample_table(int32_t rate_in, int32_t rate_out, int32_t* L, int32_t* M, int32_t* H, float* tab, int64_t cap, int64_t* n);
+/* The resampling sibling of q3tts_k_pcm_pack (one launch): row r of src [rows][stride] holds row_len[r] valid samples at rate_in (what
+ * lies beyond is never loaded) and is finished or not (row_final[r]); entry j writes outputs [first_j, first_j + count_j) of its row AT
+ * rate_out to out[dst_j, ...). A window past what the row can deliver (N of its length when final, D otherwise) is refused.
+ * iters > 0 and mean_ms != NULL: the launch is repeated iters times between two events and *mean_ms receives the mean. */
+int q3tts_k_pcm_resample(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* row_len, const int32_t* row_final,
+                         const int32_t* ent_row, const int32_t* ent_first, const int32_t* ent_count, const int64_t* ent_dst, int32_t n_ent,
+                         int32_t rate_in, int32_t rate_out, int32_t format, void* out, int64_t out_n, int32_t iters, float* mean_ms);
 /* rand 0.8 StdRng (ChaCha12) stream: seed_from_u64(seed) then n x gen::<f32>() */
 int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out);
 

@@ -120,6 +120,10 @@ struct q3tts_engine {
     double probe_ms = 0, probe_empty_ms = 0; long long probe_cnt = 0, probe_empty_cnt = 0, row_steps = 0;
     // q3tts_set_device_pcm: packed device copy of the last batch's PCM, one row of dev_pcm_stride samples per request
     int dev_pcm_on = 0; float* dev_pcm = nullptr; int dev_pcm_n = 0; size_t dev_pcm_stride = 0;
+    // q3tts_set_output_rate (q3_resample.hip): out_rate 0 = off (every launch and bit as without it). rs_out: the vocoder's rate -> out_rate.
+    // rs_stage [B][rs_stage_stride] f32: the resampled PCM of a slot on its way to the host (q3tts_generate_batch, streams)
+    int out_rate = 0; Q3Resamp rs_out{}; std::vector<Q3Resamp> rs_cache;
+    float* rs_stage = nullptr; size_t rs_stage_stride = 0, rs_stage_cap = 0;
     double hp_launch = 0, hp_sync = 0;  // Q3TTS_HOST_PROF: host wall of run_chunk's launch part / of its wait (per engine: the node drives several from threads)
     float* first_chunk_host = nullptr;  // pinned landing buffer of the first 4-frame PCM chunk (first-chunk latency)
     std::atomic<q3tts_session*> session{nullptr};  // an open session owns the engine (q3_session.hip)
@@ -222,6 +226,11 @@ float* q3_voc_pcm(q3tts_engine* e, int slot);
 int q3_voc_samples(q3tts_engine* e, int slot);
 int q3_voc_samples_per_frame(const q3tts_engine* e);
 size_t q3_voc_pcm_stride(const q3tts_engine* e);  // samples between the PCM buffers of consecutive slots
+
+// the resampler's engine side (q3_resample.hip): the cached table of a rate pair (built and uploaded on first use), and outputs
+// [first_out, first_out + count) of slot b's PCM row (n_valid samples so far) at e->out_rate into the start of the slot's row of e->rs_stage
+int q3_resample_get(q3tts_engine* e, int rate_in, int rate_out, Q3Resamp* out);
+int q3_resample_slot(q3tts_engine* e, int b, long long first_out, int count, int n_valid, bool is_final, hipStream_t s);
 
 // the scheduler steps of q3_engine.hip that the session worker (q3_session.hip) drives between 4-frame chunks
 // (q3_plan_rows + q3_admit_many are also the single-request admission of the talker-prefill hook)

@@ -257,6 +257,7 @@ extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
     }
     for (void* p : e->allocs) hipFree(p);  // every q3_dalloc: weights, tables, caches, rows, scratch, decode and prefill state
     hipFree(e->dev_pcm);                   // regrows per batch: its own pair (q3tts_generate_batch)
+    hipFree(e->rs_stage);                  // regrows with the output rate: its own pair (q3tts_set_output_rate)
     if (e->slots_host) hipHostFree(e->slots_host);
     for (auto ev : e->fin_ev) if (ev) hipEventDestroy(ev);
     for (auto ev : e->probe_ev) if (ev) hipEventDestroy(ev);
@@ -352,6 +353,7 @@ extern "C" void q3tts_free(void* p) { free(p); }
 extern "C" int q3tts_set_device_pcm(q3tts_engine* e, int32_t enable) {
     Q3_NOT_IN_SESSION(e);
     if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
+    if (enable && e->out_rate) return q3_set_err(e, Q3TTS_ERR_STATE, "device-resident PCM is native-rate only (q3tts_set_output_rate(engine, 0) first)");
     e->dev_pcm_on = enable ? 1 : 0;
     return Q3TTS_OK;
 }
@@ -803,7 +805,7 @@ static int finalize(q3tts_engine* e, int b, const q3tts_request* r, q3tts_result
     if (st.n_frames > 0)
         Q3_HIP(e, hipMemcpyAsync(o->codes, e->codes + (size_t)b * e->cfg.max_steps_cap * ncb, sizeof(int32_t) * (size_t)st.n_frames * ncb,
                                  hipMemcpyDeviceToHost, e->stream));
-    o->sample_rate = e->cfg.vocoder.sample_rate;
+    o->sample_rate = e->out_rate && e->voc ? e->out_rate : e->cfg.vocoder.sample_rate;
     if (r->want_pcm && e->voc && e->dev_pcm && ri >= 0 && ri < e->dev_pcm_n) {
         // device copy of the utterance's PCM (q3tts_set_device_pcm): row ri of the packed buffer, for collectives that read device memory
         const int ns = q3_voc_samples(e, b);
@@ -814,11 +816,17 @@ static int finalize(q3tts_engine* e, int b, const q3tts_request* r, q3tts_result
         if (defer) Q3_HIP(e, hipEventRecord(fin_ev, e->vstream));
         else Q3_HIP(e, hipStreamSynchronize(e->vstream));
     } else if (r->want_pcm && e->voc) {
-        const int ns = q3_voc_samples(e, b);
+        int ns = q3_voc_samples(e, b);
+        const float* from = q3_voc_pcm(e, b);
+        if (e->out_rate) {  // the finished row at the output rate: N(ns) samples through the slot's staging row
+            const int no = (int)q3_resample_N(ns, e->rs_out.L, e->rs_out.M);
+            TRY(q3_resample_slot(e, b, 0, no, ns, true, e->vstream));
+            ns = no; from = e->rs_stage + (size_t)b * e->rs_stage_stride;
+        }
         o->n_samples = ns;
         o->pcm = pin_alloc(sizeof(float) * (size_t)std::max(1, ns));
         if (!o->pcm) return q3_set_err(e, Q3TTS_ERR_OOM, "hipHostMalloc");
-        if (ns > 0) Q3_HIP(e, hipMemcpyAsync(o->pcm, q3_voc_pcm(e, b), sizeof(float) * (size_t)ns, hipMemcpyDeviceToHost, e->vstream));
+        if (ns > 0) Q3_HIP(e, hipMemcpyAsync(o->pcm, from, sizeof(float) * (size_t)ns, hipMemcpyDeviceToHost, e->vstream));
         if (defer) Q3_HIP(e, hipEventRecord(fin_ev, e->vstream));
         else Q3_HIP(e, hipStreamSynchronize(e->vstream));
     } else if (defer) {
@@ -1003,7 +1011,29 @@ extern "C" int q3tts_get_timings(const q3tts_engine* e, q3tts_timings* out) {
 struct q3tts_stream {
     q3tts_engine* e; q3tts_request req; int voc_frames = 0; bool finished = false; bool final_sent = false;
     std::vector<float> chunk; double t0 = 0, t_first = 0;
+    long long delivered = 0;  // output-rate samples handed out so far (q3tts_set_output_rate)
 };
+
+// the samples a poll hands out into st->chunk: the slot's new PCM [before, after), or with an output rate set the outputs the row can
+// deliver now (D(after), N(after) when `fin`) beyond those delivered
+static int stream_emit(q3tts_stream* st, int before, int after, bool fin, const float** chunk, int32_t* n_samples) {
+    q3tts_engine* e = st->e;
+    hipStream_t s = e->stream;
+    const float* from = q3_voc_pcm(e, 0) + before;
+    int c = after - before;
+    if (e->out_rate) {
+        const Q3Resamp& r = e->rs_out;
+        c = (int)((fin ? q3_resample_N(after, r.L, r.M) : q3_resample_D(after, r.L, r.M, r.H)) - st->delivered);
+        TRY(q3_resample_slot(e, 0, st->delivered, c, after, fin, s));
+        from = e->rs_stage;
+        st->delivered += std::max(c, 0);
+    }
+    st->chunk.resize((size_t)std::max(1, c));
+    if (c > 0) Q3_HIP(e, hipMemcpyAsync(st->chunk.data(), from, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, s));
+    Q3_HIP(e, hipStreamSynchronize(s));
+    *chunk = st->chunk.data(); *n_samples = std::max(c, 0);
+    return Q3TTS_OK;
+}
 
 extern "C" int q3tts_stream_begin(q3tts_engine* e, const q3tts_request* req, q3tts_stream** out) {
     if (!e || !req || !out) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
@@ -1044,28 +1074,21 @@ extern "C" int q3tts_stream_poll(q3tts_stream* st, const float** chunk, int32_t*
             TRY(q3_voc_decode(e, 0, st->voc_frames, nf, last, s));
             st->voc_frames += nf;
             const int after = q3_voc_samples(e, 0);
-            st->chunk.resize((size_t)std::max(1, after - before));
-            if (after > before)
-                Q3_HIP(e, hipMemcpyAsync(st->chunk.data(), q3_voc_pcm(e, 0) + before, sizeof(float) * (size_t)(after - before), hipMemcpyDeviceToHost, s));
-            Q3_HIP(e, hipStreamSynchronize(s));
+            const bool fin = st->finished && st->voc_frames >= sl.n_frames;
+            TRY(stream_emit(st, before, after, fin, chunk, n_samples));
             if (st->t_first == 0) st->t_first = now_ms();
-            *chunk = st->chunk.data(); *n_samples = after - before;
-            if (st->finished && st->voc_frames >= sl.n_frames) { *is_final = 1; st->final_sent = true; }
+            if (fin) { *is_final = 1; st->final_sent = true; }
             (void)spf;
             return Q3TTS_OK;
         }
         if (st->finished) {
-            if (e->cfg.vocoder_flush_tail) {  // EOS arrived with no frames left over: the withheld look-ahead tail goes out as a last chunk of its own
-                const int before = q3_voc_samples(e, 0);
-                q3_voc_mark_last(e, 0);
-                const int after = q3_voc_samples(e, 0);
-                if (after > before) {
-                    st->chunk.resize((size_t)(after - before));
-                    Q3_HIP(e, hipMemcpyAsync(st->chunk.data(), q3_voc_pcm(e, 0) + before, sizeof(float) * (size_t)(after - before), hipMemcpyDeviceToHost, s));
-                    Q3_HIP(e, hipStreamSynchronize(s));
-                    *chunk = st->chunk.data(); *n_samples = after - before;
-                }
-            }
+            // EOS arrived with no frames left over: the withheld look-ahead tail (vocoder_flush_tail) and, with an output rate set, the
+            // outputs whose windows waited for more input go out as a last chunk of their own
+            const int before = q3_voc_samples(e, 0);
+            if (e->cfg.vocoder_flush_tail) q3_voc_mark_last(e, 0);
+            const int after = q3_voc_samples(e, 0);
+            if (after > before || (e->out_rate && q3_resample_N(after, e->rs_out.L, e->rs_out.M) > st->delivered))
+                TRY(stream_emit(st, before, after, true, chunk, n_samples));
             *is_final = 1; st->final_sent = true; return Q3TTS_OK;
         }
     }

@@ -593,6 +593,60 @@ extern "C" int q3tts_k_pcm_pack(int32_t device, const float* src, int32_t rows, 
     return out_n > 0 ? o.get(out, es * (size_t)out_n) : Q3TTS_OK;
 }
 
+extern "C" int q3tts_k_resample_table(int32_t rate_in, int32_t rate_out, int32_t* L, int32_t* M, int32_t* H, float* tab, int64_t cap, int64_t* n) {
+    if (!L || !M || !H || !n || cap < 0 || (cap > 0 && !tab)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "resample table hook: null argument");
+    std::vector<float> t;
+    int l = 0, m = 0, h = 0;
+    const int rc = q3_resample_table(rate_in, rate_out, &l, &m, &h, t);
+    if (rc != Q3TTS_OK) return q3_set_err(nullptr, rc, rc == Q3TTS_ERR_UNSUPPORTED ? "resample: this rate pair needs more than 32768 filter coefficients"
+                                                                                  : "resample: rates must lie in 4000..96000 Hz and differ");
+    *L = l; *M = m; *H = h; *n = (int64_t)t.size();
+    if (cap < (int64_t)t.size()) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "resample table hook: tab holds fewer than L x T values (*n says how many)");
+    memcpy(tab, t.data(), sizeof(float) * t.size());
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_pcm_resample(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* row_len, const int32_t* row_final,
+                                    const int32_t* ent_row, const int32_t* ent_first, const int32_t* ent_count, const int64_t* ent_dst, int32_t n_ent,
+                                    int32_t rate_in, int32_t rate_out, int32_t format, void* out, int64_t out_n, int32_t iters, float* mean_ms) {
+    if (!src || !out || !row_len || !row_final || rows <= 0 || stride <= 0 || stride > (1 << 28) || n_ent < 0 || n_ent > Q3_PCM_MAX_ENT ||
+        (format != 0 && format != 1) || out_n < 0 || (n_ent > 0 && (!ent_row || !ent_first || !ent_count || !ent_dst)))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm resample hook: bad arguments");
+    Q3Resamp rs{};
+    std::vector<float> t;
+    const int prc = q3_resample_table(rate_in, rate_out, &rs.L, &rs.M, &rs.H, t);
+    if (prc != Q3TTS_OK) return q3_set_err(nullptr, prc, "pcm resample hook: the rate pair is refused");
+    rs.rate_in = rate_in; rs.rate_out = rate_out; rs.T = 2 * rs.H + 1;
+    for (int r = 0; r < rows; ++r)
+        if (row_len[r] < 0 || row_len[r] > stride) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm resample hook: a row's valid length lies outside its row");
+    Q3PcmPack pk{}; Q3PcmSrc ps{};
+    int mx = 0;
+    for (int j = 0; j < n_ent; ++j) {
+        const long long r = ent_row[j], f = ent_first[j], c = ent_count[j], d = ent_dst[j];
+        if (r < 0 || r >= rows || f < 0 || c < 0 || d < 0 || d + c > out_n)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm resample hook: a window lies outside src or out");
+        const long long lim = row_final[r] ? q3_resample_N(row_len[r], rs.L, rs.M) : q3_resample_D(row_len[r], rs.L, rs.M, rs.H);
+        if (f + c > lim) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm resample hook: a window asks for outputs the row cannot deliver yet (N or D of its length)");
+        pk.e[j] = Q3PcmEnt{(int32_t)r, (int32_t)f, (int32_t)c, 0, d};
+        ps.len[j] = row_len[r]; if (row_final[r]) ps.final_mask |= 1ull << j;
+        mx = std::max(mx, (int)c);
+    }
+    const size_t es = format ? 2 : 4;
+    HK(hipSetDevice(device));
+    const std::vector<float> dl = q3_resample_device_layout(t, rs.L, rs.M, rs.T);
+    DevBuf s, o, tb;
+    TRY(s.put(src, sizeof(float) * (size_t)rows * stride)); TRY(o.alloc(es * (size_t)std::max<int64_t>(out_n, 1)));
+    TRY(tb.put(dl.data(), sizeof(float) * dl.size()));
+    rs.tab = tb;
+    if (out_n > 0) HK(hipMemcpy(o.p, out, es * (size_t)out_n, hipMemcpyHostToDevice));  // samples outside every window keep their values
+    if (q3_launch_pcm_resample(s, (size_t)stride, pk, ps, n_ent, mx, rs, format, o.p, nullptr) != 0)
+        return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, "pcm resample hook: the input span of one tile does not fit the LDS");
+    HK(hipGetLastError());
+    HK(hipDeviceSynchronize());
+    TRY(time_launches(iters, [&] { q3_launch_pcm_resample(s, (size_t)stride, pk, ps, n_ent, mx, rs, format, o.p, nullptr); }, mean_ms));
+    return out_n > 0 ? o.get(out, es * (size_t)out_n) : Q3TTS_OK;
+}
+
 extern "C" int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out) {
     if (!out || n < 0) return Q3TTS_ERR_INVALID;
     q3_stdrng_f32(seed, n, out);

@@ -20,6 +20,7 @@ enum { Q3_EPI_STORE = 0, Q3_EPI_RESID = 1, Q3_EPI_SWIGLU = 2, Q3_EPI_ARGMAX = 3,
 // refuses its launch). One lock per launch site, uncontended.
 #include <mutex>
 #include <type_traits>
+#include <vector>
 struct Q3PerDevice {
     std::mutex mu; size_t have[64] = {0};
     template <class F> bool ensure(size_t want, F set_attr) {
@@ -350,3 +351,29 @@ void q3_launch_rmsnorm_rows(const float* x, int ldx, const float* w, float eps, 
 struct Q3PcmEnt { int32_t row, first, count, pad; long long dst_off; };
 struct Q3PcmPack { Q3PcmEnt e[Q3_PCM_MAX_ENT]; };
 void q3_launch_pcm_pack(const float* src, size_t stride, const Q3PcmPack& ents, int n_ent, int max_count, int i16, void* dst, hipStream_t s);
+// the i16 rule above (and the f32 store) as the two PCM kernels apply it to one sample
+__device__ __forceinline__ void q3_pcm_put(float* d, float v) { *d = v; }
+__device__ __forceinline__ void q3_pcm_put(int16_t* d, float v) {
+    v = v * 32767.0f;
+    v = fminf(fmaxf(v, -32768.0f), 32767.0f);
+    *d = (int16_t)(int)truncf(v);
+}
+
+// PCM resampler (q3_resample.hip): k_pcm_pack's sibling. Entry j writes outputs [first, first + count) of src[row] AT THE
+// OUTPUT RATE to dst[dst_off, ...); Q3PcmSrc adds what the filter needs to know about the entry's row: len[j] valid samples (nothing past
+// them is loaded; they count as zeros) and whether the row is finished (bit j of final_mask). A finished row of n samples has
+// N(n) = ceil(n L / M) outputs; an unfinished one can deliver the D(n) = ceil((n - H) L / M) whose windows end inside the data.
+#define Q3_RESAMPLE_MAX_COEF 32768     // L x T coefficients at the most (128 KiB)
+#define Q3_RESAMPLE_LDS_BYTES 65536    // a workgroup's LDS: one tile's input span and, when it fits beside it, the table
+struct Q3Resamp { int32_t rate_in, rate_out, L, M, H, T; const float* tab; };  // tab (device): [T][L], tab[k * L + (m mod L)] = tap k of output m
+struct Q3PcmSrc { int32_t len[Q3_PCM_MAX_ENT]; unsigned long long final_mask; };
+// the plan of a rate pair; Q3TTS_ERR_INVALID outside 4000..96000 Hz (or equal rates), Q3TTS_ERR_UNSUPPORTED past Q3_RESAMPLE_MAX_COEF
+int q3_resample_plan(int rate_in, int rate_out, int* L, int* M, int* H, int* T);
+// the table as DESIGN.md §19 states it, tab[p][k] (host, double, rounded once), and the same values in the kernel's layout
+int q3_resample_table(int rate_in, int rate_out, int* L, int* M, int* H, std::vector<float>& tab);
+std::vector<float> q3_resample_device_layout(const std::vector<float>& tab, int L, int M, int T);
+long long q3_resample_N(long long n, int L, int M);
+long long q3_resample_D(long long n, int L, int M, int H);
+// i16 as q3_launch_pcm_pack; -1 (nothing launched): one tile's input span does not fit the LDS
+int q3_launch_pcm_resample(const float* src, size_t stride, const Q3PcmPack& ents, const Q3PcmSrc& rows, int n_ent, int max_count, const Q3Resamp& rs,
+                           int i16, void* dst, hipStream_t s);

@@ -728,12 +728,6 @@ void q3_launch_rmsnorm_rows(const float* x, int ldx, const float* w, float eps, 
 }
 
 // ---- PCM gather (sessions, the node's i16 gather) -----------------------------------------------------------------------------
-__device__ __forceinline__ void pcm_put(float* d, float v) { *d = v; }
-__device__ __forceinline__ void pcm_put(int16_t* d, float v) {
-    v = v * 32767.0f;
-    v = fminf(fmaxf(v, -32768.0f), 32767.0f);
-    *d = (int16_t)(int)truncf(v);
-}
 // grid (x, n_ent): blockIdx.y = entry. The window's head up to the first 16-byte boundary of the source row is copied element-wise,
 // the body with one float4 load per thread and iteration, the tail element-wise.
 template <typename T>
@@ -746,14 +740,14 @@ __global__ __launch_bounds__(256) void k_pcm_pack(const float* __restrict__ src,
     const int head = min(n, (int)((4 - (((uintptr_t)s >> 2) & 3)) & 3));
     const int nv = (n - head) >> 2;
     const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
-    if (tid < head) pcm_put(d + tid, s[tid]);
+    if (tid < head) q3_pcm_put(d + tid, s[tid]);
     const float4* sv = (const float4*)(s + head);
     for (int i = tid; i < nv; i += nth) {
         const float4 v = sv[i];
         T* o = d + head + 4 * i;
-        pcm_put(o, v.x); pcm_put(o + 1, v.y); pcm_put(o + 2, v.z); pcm_put(o + 3, v.w);
+        q3_pcm_put(o, v.x); q3_pcm_put(o + 1, v.y); q3_pcm_put(o + 2, v.z); q3_pcm_put(o + 3, v.w);
     }
-    for (int i = head + 4 * nv + tid; i < n; i += nth) pcm_put(d + i, s[i]);
+    for (int i = head + 4 * nv + tid; i < n; i += nth) q3_pcm_put(d + i, s[i]);
 }
 void q3_launch_pcm_pack(const float* src, size_t stride, const Q3PcmPack& ents, int n_ent, int max_count, int i16, void* dst, hipStream_t s) {
     if (n_ent <= 0) return;

@@ -227,7 +227,8 @@ int step(q3tts_session* s) {
     { std::lock_guard<std::mutex> lk(s->mu); more = !s->pending.empty(); }
     TRY(q3_voc_dispatch(e, run.data(), run.data(), s->voc_frames.data(), more, &first));
     // 5. every slot's new window [delivered, samples) in one gather launch and one copy
-    Q3PcmPack pk{};
+    const Q3Resamp* rs = e->out_rate ? &e->rs_out : nullptr;
+    Q3PcmPack pk{}; Q3PcmSrc src{};
     int ne = 0, mx = 0;
     size_t tot = 0;
     std::vector<SEv> chunks;
@@ -235,8 +236,10 @@ int step(q3tts_session* s) {
     for (int b = 0; b < B; ++b) {
         if (!run[b]) continue;
         SSlot& sl = s->slots[b];
-        const int ns = q3_voc_samples(e, b), c = ns - sl.delivered;
         const bool done = !e->slots_host[b].active;
+        const int ns = q3_voc_samples(e, b);
+        // the samples to hand out: the row's new ones, or with an output rate set the outputs it can deliver by now
+        const int c = (rs ? (int)(done ? q3_resample_N(ns, rs->L, rs->M) : q3_resample_D(ns, rs->L, rs->M, rs->H)) : ns) - sl.delivered;
         if (c < 0 || tot + (size_t)std::max(c, 0) > s->ring_cap || ns > (int)q3_voc_pcm_stride(e))
             return q3_set_err(e, Q3TTS_ERR_STATE, "session: a chunk window exceeds the staging bound");
         if (c > 0 || done) {
@@ -244,9 +247,10 @@ int step(q3tts_session* s) {
             chunks.push_back(v);
         }
         if (c > 0) {
+            src.len[ne] = ns; if (done) src.final_mask |= 1ull << ne;
             pk.e[ne++] = Q3PcmEnt{b, sl.delivered, c, 0, (long long)tot};
             mx = std::max(mx, c);
-            tot += (size_t)c; sl.delivered = ns;
+            tot += (size_t)c; sl.delivered += c;
         }
         if (done) fin.push_back(b);
     }
@@ -254,7 +258,9 @@ int step(q3tts_session* s) {
         const int k = s->ring_next;
         const int rc = take_ring(s, k);
         if (rc) return rc;
-        q3_launch_pcm_pack(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, ne, mx, s->fmt, s->dev, vs);
+        if (!rs) q3_launch_pcm_pack(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, ne, mx, s->fmt, s->dev, vs);
+        else if (q3_launch_pcm_resample(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, src, ne, mx, *rs, s->fmt, s->dev, vs) != 0)
+            return q3_set_err(e, Q3TTS_ERR_UNSUPPORTED, "session: the resampler's input span does not fit the LDS");
         Q3_HIP(e, hipGetLastError());
         Q3_HIP(e, hipMemcpyAsync(s->host[k], s->dev, tot * s->es, hipMemcpyDeviceToHost, vs));
         Q3_HIP(e, hipEventRecord(s->ev[k], vs));
@@ -270,7 +276,7 @@ int step(q3tts_session* s) {
         const Q3Slot& st = e->slots_host[b];
         SEv v = final_ev(s->slots[b].req->id, Q3TTS_EV_DONE, Q3TTS_OK);
         q3tts_result& o = v.res;
-        o.n_frames = st.n_frames; o.hit_eos = st.hit_eos; o.n_samples = s->slots[b].delivered; o.sample_rate = e->cfg.vocoder.sample_rate;
+        o.n_frames = st.n_frames; o.hit_eos = st.hit_eos; o.n_samples = s->slots[b].delivered; o.sample_rate = rs ? e->out_rate : e->cfg.vocoder.sample_rate;
         o.codes = (int32_t*)malloc(sizeof(int32_t) * (size_t)std::max(1, st.n_frames * ncb));
         if (!o.codes) return q3_set_err(e, Q3TTS_ERR_OOM, "malloc");
         if (st.n_frames > 0)
@@ -374,6 +380,11 @@ extern "C" int q3tts_session_create(q3tts_engine* e, int32_t pcm_format, q3tts_s
     std::unique_ptr<q3tts_session> s(new q3tts_session());
     s->e = e; s->fmt = pcm_format; s->es = pcm_format ? 2 : 4;
     s->ring_cap = (size_t)e->B * (4 + std::max(0, e->cfg.vocoder.lookahead_frames)) * q3_voc_samples_per_frame(e);
+    if (e->out_rate) {  // the larger of the two rates: a boundary's window at the output rate, plus the H input samples a final chunk releases
+        const Q3Resamp& r = e->rs_out;
+        const size_t per = (size_t)q3_resample_N((long long)(s->ring_cap / e->B) + r.H, r.L, r.M) + 2;
+        s->ring_cap = std::max(s->ring_cap, (size_t)e->B * per);
+    }
     auto release = [&]() {
         for (int k = 0; k < kRing; ++k) { if (s->host[k]) hipHostFree(s->host[k]); if (s->ev[k]) hipEventDestroy(s->ev[k]); }
         if (s->dev) hipFree(s->dev);

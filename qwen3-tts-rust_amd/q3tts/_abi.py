@@ -155,6 +155,7 @@ SYMBOLS = [
     "q3tts_config_from_model_dir", "q3tts_k_gguf_meta",
     "q3tts_set_predictor_sampler", "q3tts_get_predictor_sampler", "q3tts_set_repetition_penalty", "q3tts_get_repetition_penalty",
     "q3tts_k_pred_variant",
+    "q3tts_set_output_rate", "q3tts_get_output_rate", "q3tts_resample", "q3tts_k_resample_table", "q3tts_k_pcm_resample",
 ]
 
 
@@ -208,6 +209,12 @@ def load_library(path=None):
     lib.q3tts_session_last_error.restype = C.c_char_p
     lib.q3tts_k_pcm_pack.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, vp,
                                      C.c_int64]
+    lib.q3tts_set_output_rate.argtypes = [vp, C.c_int32]
+    lib.q3tts_get_output_rate.argtypes = [vp, i32p]
+    lib.q3tts_resample.argtypes = [vp, f32p, C.c_int64, C.c_int32, C.c_int32, f32p, C.c_int64, C.POINTER(C.c_int64)]
+    lib.q3tts_k_resample_table.argtypes = [C.c_int32, C.c_int32, i32p, i32p, i32p, f32p, C.c_int64, C.POINTER(C.c_int64)]
+    lib.q3tts_k_pcm_resample.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, i32p, i32p, C.POINTER(C.c_int64), C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, f32p]
     lib.q3tts_stream_begin.argtypes = [vp, C.POINTER(Request), C.POINTER(vp)]
     lib.q3tts_stream_poll.argtypes = [vp, C.POINTER(f32p), i32p, i32p]
     lib.q3tts_stream_end.argtypes = [vp, C.POINTER(Result)]

@@ -197,6 +197,14 @@ class TtsEngine:
     def get_repetition_penalty(self) -> float:
         return self._native.repetition_penalty()
 
+    def set_output_sample_rate(self, rate: int):
+        """Sample rate of every AudioSample and stream chunk from now on (8000 for telephony, 16000, 48000, ...), resampled on the device
+        (DESIGN.md §19); 0 or the vocoder's own 24000 = off, the default. The reference emits 24 kHz only."""
+        self._native.set_output_rate(rate)
+
+    def get_output_sample_rate(self) -> int:
+        return self._native.get_output_rate() or self.cfg.vocoder.sample_rate
+
     def load_speakers(self, speakers_dir):  # src/tts/engine.rs:187-208 (files that fail to parse are skipped)
         for fn in sorted(os.listdir(speakers_dir)):
             if fn.endswith(".json"):
@@ -278,8 +286,7 @@ class TtsEngine:
         for o in outs:
             if o.status != 0:
                 raise _abi.Q3Error(f"generation failed with status {o.status}")
-        sr = self.cfg.vocoder.sample_rate
-        return [AudioSample(o.pcm, sr, 1) for o in outs]
+        return [AudioSample(o.pcm, o.sample_rate, 1) for o in outs]
 
     def stream_batch_with_voice(self, texts, voices, instructs=None, seeds=None, *, prefix=None):
         """The streaming twin of generate_batch_with_voice: every utterance runs through one session (continuous batching over the
@@ -314,9 +321,9 @@ class TtsEngine:
             clone_config.ae_codebook_size = self.cfg.model.codebook_size
         self._native.clone_init(clone_config)
 
-    @staticmethod
-    def _read_wav_any(path):
-        """create_voice_file's own WAV decoding (src/tts/engine.rs:339-373): f32 / i16 / i32, first channel, 24 kHz only."""
+    def _read_wav_any(self, path, resample=False):
+        """create_voice_file's own WAV decoding (src/tts/engine.rs:339-373): f32 / i16 / i32, first channel, 24 kHz only. resample = True
+        (an extension): a file at another rate is accepted, and its first channel converted to 24 kHz by the device resampler."""
         with open(path, "rb") as f:
             raw = f.read()
         if raw[:4] != b"RIFF" or raw[8:12] != b"WAVE":
@@ -335,7 +342,7 @@ class TtsEngine:
         if fmt is None or data is None:
             raise _abi.Q3Error("WAV error: missing fmt or data chunk")
         tag, channels, rate, _, _, bits = fmt
-        if rate != 24000:
+        if rate != 24000 and not resample:
             raise _abi.Q3Error(f"Expected 24000Hz audio, found {rate}Hz")
         if tag == 3 and bits == 32:
             a = np.frombuffer(data[:len(data) // 4 * 4], dtype="<f4").astype(np.float32)
@@ -345,17 +352,22 @@ class TtsEngine:
             a = (np.frombuffer(data[:len(data) // 4 * 4], dtype="<i4").astype(np.float32) / np.float32(2147483648.0)).astype(np.float32)
         else:
             raise _abi.Q3Error(f"Unsupported WAV format: {'Float' if tag == 3 else 'Int'} {bits} bits")
-        return a[::channels].copy() if channels > 1 else a
+        a = a[::channels].copy() if channels > 1 else a
+        return a if rate == 24000 else self._native.resample(a, rate, 24000)
 
-    def create_voice_file(self, audio_path, ref_text):  # src/tts/engine.rs:324-387
+    def create_voice_file(self, audio_path, ref_text, *, resample=False):  # src/tts/engine.rs:324-387
+        """resample = True: a clip at 8, 16, 44.1, 48 kHz, ... is converted to 24 kHz first (q3tts_resample); the default refuses it with
+        the reference's error."""
         if not hasattr(self._native, "clone_cfg"):
             raise _abi.Q3Error("AudioEncoder not loaded. Please ensure models/onnx/qwen3_tts_codec_encoder.onnx exists.")
-        audio = self._read_wav_any(audio_path)
+        audio = self._read_wav_any(audio_path, resample)
         codes = self._native.audio_encode(audio)            # "Extracting audio codes..."
         emb = self._native.speaker_encode(audio)            # "Extracting speaker embedding..."
         return VoiceFile.new(ref_text, codes.reshape(-1).tolist(), emb.tolist())
 
-    def _process_reference(self, audio_path):  # src/tts/engine.rs:275-302 (TTSC cache beside the audio file)
+    def _process_reference(self, audio_path, *, resample=False):  # src/tts/engine.rs:275-302 (TTSC cache beside the audio file)
+        """resample = True: a file whose rate is not 24000 Hz is converted, channel by channel, before it reaches the encoders (the
+        default hands the samples over whatever the file's rate says, as the reference does)."""
         cache_path = os.path.splitext(str(audio_path))[0] + ".cache"
         if os.path.exists(cache_path):
             try:
@@ -365,16 +377,20 @@ class TtsEngine:
         audio = AudioSample.load_wav(audio_path)
         if not hasattr(self._native, "clone_cfg"):
             raise _abi.Q3Error("AudioEncoder not loaded (required for processing raw audio)")
-        codes = self._native.audio_encode(audio.samples).reshape(-1).tolist()
-        emb = self._native.speaker_encode(audio.samples).tolist()
+        samples = audio.samples
+        if resample and audio.sample_rate != 24000:
+            ch = max(1, audio.channels)
+            samples = np.stack([self._native.resample(samples[c::ch], audio.sample_rate, 24000) for c in range(ch)], axis=1).reshape(-1)
+        codes = self._native.audio_encode(samples).reshape(-1).tolist()
+        emb = self._native.speaker_encode(samples).tolist()
         try:
             save_cache(cache_path, codes, emb)
         except OSError:
             pass
         return codes, emb
 
-    def generate(self, text, ref_audio_path, ref_text, instruct=None):  # src/tts/engine.rs:243-272
-        codes, emb = self._process_reference(ref_audio_path)
+    def generate(self, text, ref_audio_path, ref_text, instruct=None, *, resample=False):  # src/tts/engine.rs:243-272
+        codes, emb = self._process_reference(ref_audio_path, resample=resample)
         return self.generate_with_voice(text, VoiceFile.new(ref_text, codes, emb), instruct)
 
 

@@ -1,5 +1,6 @@
 """Thin object wrapper over the C ABI (include/q3tts.h). No arithmetic happens in Python."""
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -217,6 +218,27 @@ class NativeEngine:
         base, stride, n = f32p(), C.c_int64(0), C.c_int32(0)
         self._check(self.lib.q3tts_get_device_pcm(self.h, C.byref(base), C.byref(stride), C.byref(n)), "q3tts_get_device_pcm")
         return (C.cast(base, C.c_void_p).value or 0), int(stride.value), int(n.value)
+
+    def set_output_rate(self, rate):
+        """q3tts_set_output_rate: PCM of generate / generate_batch (want_pcm = 1), of streams and of session chunks leaves the engine at
+        `rate` Hz, resampled on the device; 0 or the vocoder's own rate = off, the default. Refused while a session or a
+        stream is open and while device PCM is enabled. The reference has no such control."""
+        self._check(self.lib.q3tts_set_output_rate(self.h, int(rate)), "q3tts_set_output_rate")
+
+    def get_output_rate(self):
+        r = C.c_int32(0)
+        self._check(self.lib.q3tts_get_output_rate(self.h, C.byref(r)), "q3tts_get_output_rate")
+        return r.value
+
+    def resample(self, audio, rate_in, rate_out):
+        """q3tts_resample: the finished f32 clip `audio` at rate_in -> ceil(n L / M) samples at rate_out, by the engine's device resampler."""
+        a = np.ascontiguousarray(audio, dtype=np.float32).reshape(-1)
+        g = math.gcd(int(rate_in), int(rate_out))
+        cap = -(-a.size * (int(rate_out) // g) // (int(rate_in) // g)) if g else 0
+        out = np.zeros(max(cap, 1), dtype=np.float32)
+        n = C.c_int64(0)
+        self._check(self.lib.q3tts_resample(self.h, _ptr(a, f32p), a.size, int(rate_in), int(rate_out), _ptr(out, f32p), cap, C.byref(n)), "q3tts_resample")
+        return out[:n.value]
 
     def vocoder_bench(self, n_slots, chunks):
         ms = C.c_float(0)
@@ -815,6 +837,42 @@ def k_pcm_pack(src, entries, out_n, fmt=0, device=0):
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_pcm_pack failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return out[:int(out_n)]
+
+
+def k_resample_table(rate_in, rate_out):
+    """q3tts_k_resample_table (host only): (L, M, H, tab [L][2H + 1] f32) of the resampler's filter for rate_in -> rate_out."""
+    lib = _abi.load_library()
+    L, M, H, n = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    tab = np.zeros(32768, dtype=np.float32)
+    rc = lib.q3tts_k_resample_table(int(rate_in), int(rate_out), C.byref(L), C.byref(M), C.byref(H), _ptr(tab, f32p), tab.size, C.byref(n))
+    if rc != 0:
+        e = _abi.Q3Error(f"q3tts_k_resample_table failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+        e.status = rc
+        raise e
+    return L.value, M.value, H.value, tab[:n.value].reshape(L.value, 2 * H.value + 1).copy()
+
+
+def k_pcm_resample(src, row_len, row_final, entries, out_n, rate_in, rate_out, fmt=0, device=0, iters=0):
+    """q3tts_k_pcm_resample: src [rows][stride] f32 at rate_in with row_len[r] valid samples per row (finished or not: row_final[r]),
+    entries [(row, first_out, count, dst)] (<= 64) in output samples at rate_out; returns the f32 (fmt 0) or i16 (fmt 1) output of out_n
+    samples (zeros outside the windows); with iters > 0, (that, the launch's mean time in ms over iters repetitions)."""
+    lib = _abi.load_library()
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    rows, stride = src.shape
+    ms = C.c_float(0)
+    rl, rf = np.ascontiguousarray(row_len, dtype=np.int32), np.ascontiguousarray(row_final, dtype=np.int32)
+    if rl.shape != (rows,) or rf.shape != (rows,):
+        raise ValueError("k_pcm_resample: row_len and row_final take one value per row of src")
+    e = np.asarray(entries, dtype=np.int64).reshape(-1, 4)
+    er, ef, ec = (np.ascontiguousarray(e[:, i], dtype=np.int32) for i in range(3))
+    ed = np.ascontiguousarray(e[:, 3], dtype=np.int64)
+    out = np.zeros(max(int(out_n), 1), dtype=np.int16 if fmt else np.float32)
+    rc = lib.q3tts_k_pcm_resample(device, _ptr(src, f32p), rows, stride, _ptr(rl, i32p), _ptr(rf, i32p), _ptr(er, i32p), _ptr(ef, i32p),
+                                  _ptr(ec, i32p), ed.ctypes.data_as(C.POINTER(C.c_int64)), len(e), int(rate_in), int(rate_out), fmt,
+                                  out.ctypes.data, int(out_n), int(iters), C.byref(ms))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_pcm_resample failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return (out[:int(out_n)], ms.value) if iters > 0 else out[:int(out_n)]
 
 
 def k_rng_f32(seed, n):
