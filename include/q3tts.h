@@ -257,9 +257,16 @@ int q3tts_resample(q3tts_engine* e, const float* in, int64_t n_in, int32_t rate_
 typedef struct q3tts_prefix q3tts_prefix;  /* a voice prefix: see "voice prefixes" below */
 typedef struct q3tts_request {
     const float* prompt_embd; int32_t n_tok; /* [n_tok][d_embed] f32 host rows (PromptData.embd), or NULL ... */
+    int32_t text_stream;  /* 1: the streamed text layout (see "streaming text input"): only the first text id is in the prompt, the rest
+                           * joins the feedback rows. Needs `prompt` with n_text >= 1. Any other value: the whole text is in the prompt
+                           * (the reference). This field and text_open occupy the two 4-byte alignment gaps the struct always had (behind
+                           * n_tok and behind has_seed): no field moved, sizeof is 80 as before, `prefix` is still the last field, and a
+                           * caller that zero-fills its requests gets the behaviour it had */
     const q3tts_prompt_desc* prompt;         /* ... to build from ids on the device */
     int32_t use_engine_sampler;              /* 1: ignore the five fields below, use q3tts_set_sampler state */
-    float temperature; int32_t top_k; float top_p; int32_t has_seed; uint64_t seed;
+    float temperature; int32_t top_k; float top_p; int32_t has_seed;
+    int32_t text_open;    /* sessions only, with text_stream = 1: 1 = more text follows through q3tts_session_append_text; else the text is closed */
+    uint64_t seed;
     int32_t max_steps;    /* 0 -> engine value */
     int32_t min_frames;   /* bench control: EOS logit masked while n_frames < min_frames (0 = reference) */
     int32_t force_eos_at; /* bench control: EOS forced at this step (<0 = off) */
@@ -379,6 +386,32 @@ int q3tts_session_next(q3tts_session* s, int32_t timeout_ms, q3tts_session_event
 int q3tts_session_close(q3tts_session* s);
 /* Message of the last failing session call or of the worker's failure. */
 const char* q3tts_session_last_error(const q3tts_session* s);
+
+/* ---- streaming text input: feed a running request its text as it arrives ---------------------------------------
+ * The reference puts a request's whole text into the prompt (build_core, src/tts/prompt.rs:229-264) and adds tts_pad to every feedback
+ * row (src/tts/engine.rs:622-631). request.text_stream = 1 selects the model's second layout, in which a sentence can start to sound
+ * after its first word. PARITY IS UNPINNED: the reference crate has only the whole-text layout and no other implementation was at hand,
+ * so the contract is the layout as written here (tests/_text_stream.py restates it on the CPU):
+ *   - the voice part of the prompt (instruct, role and control blocks, speaker row, clone rows) is unchanged, so voice prefixes compose
+ *     with streaming (a text-only desc behind request.prefix);
+ *   - with text ids x[0, n), n >= 1, the text part is two rows instead of n + 3: text[tts_bos] + codec0[PAD], then
+ *     text[x[0]] + codec0[BOS] (in place of the activation row text[tts_pad] + codec0[BOS]);
+ *   - the trailing rows are T[j] = text[x[j + 1]] for j < n - 1, and T[n - 1] = text[tts_eos] once the text is closed;
+ *   - after frame f the Talker's next input row is fb + T[f] when f < len(T), else fb + tts_pad, in f32 as (fb + codec_15) + row.
+ * Table look-ups follow the prompt builder's out-of-range rule. prompt_embd with text_stream = 1, and n_text = 0, are Q3TTS_ERR_INVALID.
+ * q3tts_generate, q3tts_generate_batch and q3tts_stream_begin take closed text and never wait: text_open = 1 is Q3TTS_ERR_INVALID there.
+ * q3tts_node_generate_batch refuses text_stream (Q3TTS_ERR_INVALID). Streamed and whole-text requests mix freely in a batch; a request
+ * with text_stream = 0 computes exactly what it did before.
+ *
+ * In a session a request submitted with text_open = 1 receives more text while it runs:
+ *   q3tts_session_append_text(s, id, ids, n, close) appends ids[0, n) (copied) and, with close = 1, ends the text; n = 0 with close = 1
+ *   only ends it. Thread-safe. Q3TTS_ERR_INVALID for a NULL session, NULL ids with n > 0, n < 0, an unknown or finished id, a request
+ *   without text_stream and text that is already closed. Trailing rows beyond the request's max_steps are accepted and never read.
+ * Readiness: a request at n_frames = f takes part in the next chunk of 4 frame steps iff its text is closed or len(T) >= f + 4 (those
+ * steps read T[f .. f + 3]); otherwise it is PARKED for that chunk boundary: it produces nothing and loses nothing, and what it produces
+ * is bit for bit what the same text gives when it is all there at submission. A request that stays open and is never fed stays parked
+ * (the worker sleeps; an append wakes it); q3tts_session_cancel and q3tts_session_close end it. The reference has no counterpart. */
+int q3tts_session_append_text(q3tts_session* s, uint64_t id, const uint32_t* ids, int32_t n, int32_t close);
 
 /* ---- one node, several GPUs ----------------------------------------------------------------------
  * The reference is one utterance at a time on one device (n_seq_max = 1, src/models/llama/mod.rs:413; `&mut self`,
@@ -582,6 +615,9 @@ int q3tts_k_attend_policy(int32_t decode, int32_t prefill);
  * Predictor sampler's temperature; at temperature 0 that is sample_row's greedy branch, which must give the ids of the default form (the
  * heads' ARGMAX epilogue). 0: back to the rule (sampling form iff temperature > 0). Q3TTS_ERR_STATE while a session or a stream is open. */
 int q3tts_k_pred_variant(q3tts_engine* e, int32_t force);
+/* The readiness rule of "streaming text input" as the session worker applies it: 1 iff a request with n_text text ids so far (x, the
+ * first one included), closed or not, at n_frames frames may take part in the next chunk of 4 frame steps. Needs no GPU. */
+int q3tts_k_text_ready(int32_t n_text, int32_t closed, int32_t n_frames);
 /* The k_bgemm instance the launcher takes for a shape, without launching: out5 = {row tiles, column tiles, ring depth, non-temporal weight
  * loads, 1 if k_bgemm_big}. bench.py names the kernel symbol of a probed launch from it. */
 int q3tts_k_bgemm_pick(int32_t B, int32_t K, int32_t N, int32_t epilogue, int32_t w_once, int32_t q8, int32_t* out5);

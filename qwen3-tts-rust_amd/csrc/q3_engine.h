@@ -1,6 +1,7 @@
 // q3_engine.h — internal engine state of libq3tts (host side, C++). The public surface is include/q3tts.h.
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <atomic>
 #include <mutex>
 #include <string>
@@ -8,6 +9,10 @@
 
 #include "../../include/q3tts.h"
 #include "q3_kernels.h"
+
+// text_stream / text_open live in the alignment gaps of q3tts_request (include/q3tts.h): the struct's size and every other offset are what they were
+static_assert(sizeof(q3tts_request) == 80 && offsetof(q3tts_request, text_stream) == 12 && offsetof(q3tts_request, prompt) == 16 &&
+              offsetof(q3tts_request, text_open) == 44 && offsetof(q3tts_request, seed) == 48 && offsetof(q3tts_request, prefix) == 72, "q3tts_request layout");
 
 struct Q3Voc;  // vocoder (q3_vocoder.hip)
 struct Q3Mel;  // log-mel front-end (q3_mel.hip)
@@ -59,6 +64,10 @@ struct Q3Lane {
     std::vector<hipGraphExec_t> execs;
     std::vector<hipGraph_t> graphs_s;        // the same frame step with the sampling Predictor (captured when it is first turned on)
     std::vector<hipGraphExec_t> execs_s;
+    // the frame step whose last k_pred_next pass takes streamed text rows, per Predictor variant: captured when the first
+    // text_stream request is admitted under that variant, kept afterwards. graphs / execs / graphs_s / execs_s are never touched by it.
+    std::vector<hipGraph_t> graphs_t[2];
+    std::vector<hipGraphExec_t> execs_t[2];
     hipEvent_t ev_begin = nullptr, ev_end = nullptr;
 };
 
@@ -104,6 +113,12 @@ struct q3tts_engine {
     float p_temperature = 0.0f; int p_top_k = 0; float p_top_p = 1.0f; float rep_penalty = 1.0f;
     int pred_force = 0, pred_variant = 0;
     int streams_open = 0;                 // q3tts_stream_begin .. q3tts_stream_end
+    // streamed text (include/q3tts.h, "streaming text input"; Q3TextRows): the slots' trailing ids, counts and cursors on the device.
+    // ts_slot[b]: slot b's last admission was a text_stream request — while any is set, run_chunk runs the text form of the frame step
+    // (ts_variant = 1: what q3_record_frame issues / q3_capture_frames captures). ts_used: a text_stream request was admitted at some time
+    // (from then on every admission resets its slot's count and cursor).
+    int* ts_ids = nullptr; int* ts_cnt = nullptr; int2* ts_cur = nullptr;
+    std::vector<char> ts_slot; int ts_variant = 0, ts_used = 0;
     float* prng = nullptr;                // [B][max_steps_cap * (n_codebooks - 1)] the Predictor's draws, positional
     uint32_t* seen = nullptr; int seen_words = 0;  // [B][ceil(sample_limit / 32)] codes 0 generated so far, per slot
     // timing
@@ -125,6 +140,7 @@ struct q3tts_engine {
     int out_rate = 0; Q3Resamp rs_out{}; std::vector<Q3Resamp> rs_cache;
     float* rs_stage = nullptr; size_t rs_stage_stride = 0, rs_stage_cap = 0;
     double hp_launch = 0, hp_sync = 0;  // Q3TTS_HOST_PROF: host wall of run_chunk's launch part / of its wait (per engine: the node drives several from threads)
+    float *park_logits = nullptr, *park_x = nullptr;  // [B][t_vocab], [B][t_d_model]: a parked slot's rows (q3_park_rows)
     float* first_chunk_host = nullptr;  // pinned landing buffer of the first 4-frame PCM chunk (first-chunk latency)
     std::atomic<q3tts_session*> session{nullptr};  // an open session owns the engine (q3_session.hip)
     std::mutex err_mu;                  // err is written by the session worker too
@@ -232,11 +248,20 @@ size_t q3_voc_pcm_stride(const q3tts_engine* e);  // samples between the PCM buf
 int q3_resample_get(q3tts_engine* e, int rate_in, int rate_out, Q3Resamp* out);
 int q3_resample_slot(q3tts_engine* e, int b, long long first_out, int count, int n_valid, bool is_final, hipStream_t s);
 
+enum { BOS_TOKEN = 151672, EOS_TOKEN = 151673 };  // tts_bos, tts_eos (src/tts/prompt.rs); tts_pad is the model's tts_pad_id
+
 // the scheduler steps of q3_engine.hip that the session worker (q3_session.hip) drives between 4-frame chunks
 // (q3_plan_rows + q3_admit_many are also the single-request admission of the talker-prefill hook)
 int q3_plan_rows(q3tts_engine* e, const std::vector<int>& live);
 int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc);
 int q3_run_chunk(q3tts_engine* e, int CH);
+// streamed text, between frame steps: slot b's trailing ids become T[0, n) (entries [from, n) are uploaded; the first max_steps_cap count)
+// and its cursor the row of frame n_frames. n = 0: the slot takes tts_pad (a request without text_stream).
+int q3_text_rows_set(q3tts_engine* e, int b, const int32_t* T, int from, int n, int n_frames);
+// parking a slot between chunks (q3_session.hip): its Talker logits row and hidden row, which outlive a frame, to / from the slot's side rows
+int q3_park_rows(q3tts_engine* e, int b, bool save);
+// the ids behind a text_stream request's first one, with tts_eos when its text is closed: T of include/q3tts.h
+void q3_text_trailing(const q3tts_request* r, std::vector<int32_t>& T);
 // test hook (q3tts_k_pred_variant): force = 1 runs the sampling frame step whatever the temperature
 int q3_pred_force_variant(q3tts_engine* e, int force);
 int q3_voc_dispatch(q3tts_engine* e, const char* live, const char* want, int* voc_frames, bool more, bool* first);

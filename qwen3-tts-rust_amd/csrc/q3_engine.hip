@@ -180,6 +180,10 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     TRYC(q3_dalloc(e, &e->prng, (size_t)B * cfg->max_steps_cap * (m.n_codebooks - 1)));
     e->seen_words = (m.sample_limit + 31) / 32;
     TRYC(q3_dalloc(e, &e->seen, (size_t)B * e->seen_words));
+    // streamed text (Q3TextRows) and a parked slot's rows: zero = no slot streams, every cursor says tts_pad
+    TRYC(q3_dalloc(e, &e->ts_ids, (size_t)B * cfg->max_steps_cap)); TRYC(q3_dalloc(e, &e->ts_cnt, (size_t)B)); TRYC(q3_dalloc(e, &e->ts_cur, (size_t)B));
+    TRYC(q3_dalloc(e, &e->park_logits, (size_t)B * m.t_vocab)); TRYC(q3_dalloc(e, &e->park_x, (size_t)B * m.t_d_model));
+    e->ts_slot.assign(B, 0);
     {
         const int nb = B;
         const int nqkv_max = std::max(e->T.nqkv, e->P.nqkv), nq_max = std::max(e->T.nq, e->P.nq), F_max = std::max(e->T.F, e->P.F);
@@ -252,6 +256,10 @@ extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
         for (auto gr : L.graphs) if (gr) hipGraphDestroy(gr);
         for (auto ge : L.execs_s) if (ge) hipGraphExecDestroy(ge);
         for (auto gr : L.graphs_s) if (gr) hipGraphDestroy(gr);
+        for (int v = 0; v < 2; ++v) {
+            for (auto ge : L.execs_t[v]) if (ge) hipGraphExecDestroy(ge);
+            for (auto gr : L.graphs_t[v]) if (gr) hipGraphDestroy(gr);
+        }
         if (L.ev_begin) hipEventDestroy(L.ev_begin); if (L.ev_end) hipEventDestroy(L.ev_end);
         if (L.stream) hipStreamDestroy(L.stream);
     }
@@ -367,14 +375,16 @@ extern "C" int q3tts_get_device_pcm(q3tts_engine* e, float** base, int64_t* stri
 // H1 prompt builder: row list on the host (src/tts/prompt.rs:141-277, :28-118), gathers on the device
 // ------------------------------------------------------------------------------------------------
 enum { PAD = 2148, BOS = 2149, THINK = 2154, NOTHINK = 2155, THINK_BOS = 2156, THINK_EOS = 2157, CODEC_BOS_ICL = 2160 };
-enum { BOS_TOKEN = 151672, EOS_TOKEN = 151673 };
 
 // part: which rows to build. The voice part (instruct, role, control, speaker, clone blocks) comes first and the text part (BOS, text,
 // EOS, activation row) last, so PROMPT_VOICE ++ PROMPT_TEXT is PROMPT_WHOLE row for row (voice prefixes: include/q3tts.h).
+// text_stream: the text part in the streamed layout (include/q3tts.h, "streaming text input"): BOS, then text[x[0]] + codec0[BOS] in place of
+// the activation row; x[1 ..) and EOS join the feedback rows (q3_text_trailing, Q3TextRows). The voice part is the same either way.
 enum { PROMPT_WHOLE = 0, PROMPT_VOICE = 1, PROMPT_TEXT = 2 };
-static int build_prompt_dev(q3tts_engine* e, const q3tts_prompt_desc* p, float* out, int max_rows, int* n_out, int part = PROMPT_WHOLE) {
+static int build_prompt_dev(q3tts_engine* e, const q3tts_prompt_desc* p, float* out, int max_rows, int* n_out, int part = PROMPT_WHOLE, bool text_stream = false) {
     const q3tts_model_config& m = e->cfg.model;
     if (!p || (p->n_text > 0 && !p->text_ids)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prompt: text_ids missing");
+    if (text_stream && (part == PROMPT_VOICE || p->n_text < 1)) return q3_set_err(e, Q3TTS_ERR_INVALID, "text_stream: the prompt needs n_text >= 1 (its first text id is the prompt's last row)");
     if (part == PROMPT_VOICE && p->n_text != 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: a voice desc has n_text == 0");
     if (part == PROMPT_TEXT) {  // behind a prefix: the voice is the prefix's
         const char* f = p->instruct_ids ? "instruct_ids" : p->lang_id >= 0 ? "lang_id" : p->spk_id >= 0 ? "spk_id" : p->spk_emb ? "spk_emb"
@@ -408,7 +418,10 @@ static int build_prompt_dev(q3tts_engine* e, const q3tts_prompt_desc* p, float* 
             MC(PAD);
         }
     }
-    if (part != PROMPT_VOICE) {  // the text part
+    if (part != PROMPT_VOICE && text_stream) {  // the streamed text part
+        TP(BOS_TOKEN);
+        rows.push_back({1, (int)p->text_ids[0], 2, BOS});
+    } else if (part != PROMPT_VOICE) {  // the text part
         TP(BOS_TOKEN);                                             // :229-239
         for (int i = 0; i < p->n_text; ++i) TP((int)p->text_ids[i]);  // :241-245
         TP(EOS_TOKEN);                                             // :247-254
@@ -495,7 +508,12 @@ static int run_chunk(q3tts_engine* e, int CH, float* dev_ms) {
     Q3_HIP(e, hipEventRecord(L.ev_begin, L.stream));
     e->probe_i = 0;
     if (e->probe) { hipEventRecord(e->probe_ev[8], L.stream); hipEventRecord(e->probe_ev[9], L.stream); }  // empty bracket
-    const std::vector<hipGraphExec_t>& execs = e->pred_variant ? L.execs_s : L.execs;  // (set_pred_variant captured the second set)
+    // while a slot streams its text the frames come from the text form's own sets (ensure_text_frames captured them); without one the
+    // choice, the sets and so every launch are what they were before text streaming existed
+    bool ts = false;
+    for (char f : e->ts_slot) ts |= f != 0;
+    e->ts_variant = ts ? 1 : 0;
+    const std::vector<hipGraphExec_t>& execs = ts ? L.execs_t[e->pred_variant ? 1 : 0] : e->pred_variant ? L.execs_s : L.execs;  // (set_pred_variant captured the second set)
     for (int i = 0; i < CH; ++i) {
         if (!execs.empty() && !e->probe) { Q3_HIP(e, hipGraphLaunch(execs[e->cur_bucket], L.stream)); }
         else {
@@ -533,6 +551,54 @@ static uint64_t wall_seed() {
 // A request behind a voice prefix (P > 0 rows) brings only its own n rows: they sit at positions P .. P + n - 1 of its slot, whose first
 // P positions receive a copy of the prefix's K/V (k_kv_prefix, one launch for the group) before the layers run.
 struct Adm { int b; const q3tts_request* r; int n, row0, max_steps, P; };
+
+// ---- streamed text (include/q3tts.h, "streaming text input") ----
+void q3_text_trailing(const q3tts_request* r, std::vector<int32_t>& T) {
+    T.clear();
+    const q3tts_prompt_desc* p = r->prompt;
+    for (int i = 1; p && i < p->n_text; ++i) T.push_back((int32_t)p->text_ids[i]);
+    if (!(r->text_open == 1)) T.push_back(EOS_TOKEN);
+}
+int q3_text_rows_set(q3tts_engine* e, int b, const int32_t* T, int from, int n, int n_frames) {
+    const int cap = e->cfg.max_steps_cap, c = std::min(std::max(n, 0), cap);  // (frames stop at max_steps <= cap: later rows are never read)
+    hipStream_t s = e->stream;
+    from = std::max(from, 0);
+    if (from < c) Q3_HIP(e, hipMemcpyAsync(e->ts_ids + (size_t)b * cap + from, T + from, (size_t)(c - from) * 4, hipMemcpyHostToDevice, s));
+    const int2 cur = n_frames >= 0 && n_frames < c ? make_int2(1, T[n_frames]) : make_int2(0, 0);
+    Q3_HIP(e, hipMemcpyAsync(e->ts_cnt + b, &c, 4, hipMemcpyHostToDevice, s));
+    Q3_HIP(e, hipMemcpyAsync(e->ts_cur + b, &cur, sizeof(cur), hipMemcpyHostToDevice, s));
+    Q3_HIP(e, hipStreamSynchronize(s));  // the uploads read locals
+    return Q3TTS_OK;
+}
+int q3_park_rows(q3tts_engine* e, int b, bool save) {
+    const q3tts_model_config& m = e->cfg.model;
+    Q3Lane& L = e->lane;
+    const size_t row = (size_t)e->row_of_slot[b], nl = (size_t)m.t_vocab, nx = (size_t)m.t_d_model;
+    float *lg = L.logits + row * nl, *x = L.T.x + row * nx, *plg = e->park_logits + (size_t)b * nl, *px = e->park_x + (size_t)b * nx;
+    Q3_HIP(e, hipMemcpyAsync(save ? plg : lg, save ? lg : plg, nl * 4, hipMemcpyDeviceToDevice, e->stream));
+    Q3_HIP(e, hipMemcpyAsync(save ? px : x, save ? x : px, nx * 4, hipMemcpyDeviceToDevice, e->stream));
+    return Q3TTS_OK;
+}
+// The text form of the frame step exists before a text_stream request's first frame: its own graph sets for the current Predictor
+// variant, captured the first time one is needed and kept (the variant cannot change while anything is in flight). The sets of the
+// default path are not touched. Without graphs (Q3TTS_NO_GRAPH, the probe) frames are issued eagerly and nothing is captured.
+static int ensure_text_frames(q3tts_engine* e) {
+    e->ts_used = 1;
+    Q3Lane& L = e->lane;
+    const int v = e->pred_variant ? 1 : 0;
+    if (L.execs.empty() || !L.execs_t[v].empty()) return Q3TTS_OK;
+    Q3_HIP(e, hipStreamSynchronize(e->stream));
+    const int was = e->ts_variant;
+    e->ts_variant = 1;
+    const int rc = q3_capture_frames(e, L.graphs_t[v], L.execs_t[v]);
+    e->ts_variant = was;
+    if (rc != Q3TTS_OK) {
+        for (auto ge : L.execs_t[v]) if (ge) hipGraphExecDestroy(ge);
+        for (auto gr : L.graphs_t[v]) if (gr) hipGraphDestroy(gr);
+        L.execs_t[v].clear(); L.graphs_t[v].clear();
+    }
+    return rc;
+}
 
 // The Talker's layers over the first pos.size() prefill rows (e->pf.x holds them): row i sits at position pos[i] of slot slot[i]; seg: the
 // same rows as per-slot runs (pf_seg), seg_max_n the longest run, seg_max_t the furthest position + 1. The maps are uploaded and the stream
@@ -610,6 +676,12 @@ static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
         st->rng_base = b * e->cfg.max_steps_cap;
         st->p_temperature = e->p_temperature; st->p_top_k = e->p_top_k; st->p_top_p = e->p_top_p; st->rep_penalty = e->rep_penalty;
         Q3_HIP(e, hipMemcpyAsync(e->slots + b, st, sizeof(Q3Slot), hipMemcpyHostToDevice, s));
+        if (r->text_stream == 1) {  // the slot's trailing rows; (nothing here until a text_stream request has been seen: the arrays are zero)
+            std::vector<int32_t> T;
+            q3_text_trailing(r, T);
+            TRY(q3_text_rows_set(e, b, T.data(), 0, (int)T.size(), 0));
+        } else if (e->ts_used) TRY(q3_text_rows_set(e, b, nullptr, 0, 0, 0));
+        e->ts_slot[b] = (r->text_stream == 1) ? 1 : 0;
         if (e->voc) TRY(q3_voc_reset(e, b));
     }
     return Q3TTS_OK;
@@ -629,6 +701,13 @@ static int admit_many(q3tts_engine* e, const int* slots, const q3tts_request* co
         const q3tts_prefix* x = r->prefix;
         if (x && x->e != e) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: made by another engine"); continue; }
         const int P = x ? x->P : 0;  // the prefix's rows come first; only the request's own rows enter the prefill buffer
+        if ((r->text_open == 1) && !(r->text_stream == 1)) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "text_open needs text_stream = 1"); continue; }
+        if (r->text_stream == 1) {
+            if (r->prompt_embd || !r->prompt) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "text_stream needs a prompt built from ids (prompt), not prompt_embd"); continue; }
+            if (r->prompt->n_text < 1 || !r->prompt->text_ids) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "text_stream: the prompt needs n_text >= 1 (its first text id is the prompt's last row)"); continue; }
+            const int trc = ensure_text_frames(e);
+            if (trc != Q3TTS_OK) { rc[i] = trc; continue; }
+        }
         int n = 0;
         for (int attempt = 0; attempt < 2; ++attempt) {
             const int room = e->cfg.n_ctx - total;
@@ -638,7 +717,7 @@ static int admit_many(q3tts_engine* e, const int* slots, const q3tts_request* co
                 if (n > room) { if (total == 0) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "n_tok out of range"); break; } }
                 else { Q3_HIP(e, hipMemcpyAsync(e->pf.x + (size_t)total * m.d_embed, r->prompt_embd, (size_t)n * m.d_embed * 4, hipMemcpyHostToDevice, s)); break; }
             } else if (r->prompt) {
-                const int brc = build_prompt_dev(e, r->prompt, e->pf.x + (size_t)total * m.d_embed, room, &n, x ? PROMPT_TEXT : PROMPT_WHOLE);
+                const int brc = build_prompt_dev(e, r->prompt, e->pf.x + (size_t)total * m.d_embed, room, &n, x ? PROMPT_TEXT : PROMPT_WHOLE, r->text_stream == 1);
                 if (brc == Q3TTS_OK) break;
                 if (total == 0) { rc[i] = brc; break; }
             } else { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "request has neither prompt_embd nor prompt"); break; }
@@ -854,7 +933,9 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
     for (int i = 0; i < n; ++i) {
         if (reqs[i].want_pcm && !e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "want_pcm on an engine created with with_vocoder = 0");
         if (reqs[i].want_pcm == 2 && !e->dev_pcm_on) return q3_set_err(e, Q3TTS_ERR_STATE, "want_pcm = 2 (device only) needs q3tts_set_device_pcm(engine, 1)");
+        if (reqs[i].text_open == 1) return q3_set_err(e, Q3TTS_ERR_INVALID, "text_open = 1 is for sessions (q3tts_session_append_text): this call takes closed text and never waits");
     }
+    std::fill(e->ts_slot.begin(), e->ts_slot.end(), 0);  // nothing is in flight
     if (e->dev_pcm_on && e->voc) {  // one row of max_steps_cap frames per request of this call
         const size_t stride = (size_t)e->cfg.max_steps_cap * q3_voc_samples_per_frame(e);
         if (e->dev_pcm_n < n || e->dev_pcm_stride != stride) {
@@ -947,6 +1028,7 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
             TRY(finalize(e, b, &reqs[run[b].req], &outs[run[b].req], run[b], t0, true, e->fin_ev[b], run[b].req));
             pending[b] = run[b].req;
             run[b].req = -1; ++done;
+            e->ts_slot[b] = 0;
         }
         hp_lap(hp_fin);
     }
@@ -1039,7 +1121,9 @@ extern "C" int q3tts_stream_begin(q3tts_engine* e, const q3tts_request* req, q3t
     if (!e || !req || !out) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     Q3_NOT_IN_SESSION(e);
     if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "streaming needs with_vocoder = 1");
+    if (req->text_open == 1) return q3_set_err(e, Q3TTS_ERR_INVALID, "text_open = 1 is for sessions (q3tts_session_append_text): a stream takes closed text and never waits");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
+    std::fill(e->ts_slot.begin(), e->ts_slot.end(), 0);  // nothing else is in flight
     q3tts_stream* st = new q3tts_stream();
     st->e = e; st->req = *req; st->t0 = now_ms();
     int rc = plan_rows(e, std::vector<int>{0});
@@ -1112,6 +1196,7 @@ extern "C" int q3tts_stream_end(q3tts_stream* st, q3tts_result* out) {
     hipMemcpyAsync(e->slots, stage, sizeof(Q3Slot), hipMemcpyHostToDevice, e->stream);
     hipStreamSynchronize(e->stream);
     --e->streams_open;
+    e->ts_slot[0] = 0;
     delete st;
     return rc;
 }

@@ -328,6 +328,17 @@ struct Q3PredNext {
 };
 int q3_launch_pred_next(const Q3PredNext& a, hipStream_t s, bool sample = false);  // -1: the sampling variant refuses cbs > Q3_SAMP_MAX
 int q3_pred_next_prepare();  // the sampling variant's kernel attributes, once per device; call outside stream capture. -1: the device refused them
+// Streamed text (include/q3tts.h, "streaming text input"): the last pass's addend row is text[id] (the prompt builder's out-of-range rule)
+// instead of tts_pad, per slot and frame. ids[slot][cap]: the slot's trailing ids T; cnt[slot] <= cap: how many are valid; cur[slot]: the
+// row of the slot's NEXT frame, {1, T[n_frames]} or {0, 0} = tts_pad — kept beside the slot record so that the kernel loads it with the
+// record (the row load is the one added dependent round trip) and advanced by the kernel: after frame f it becomes T[f + 1] or tts_pad.
+// The host rewrites cur whenever it changes cnt (between frame steps only). A slot with cnt = 0 gets tts_pad: q3_launch_pred_next's bits.
+struct Q3TextRows {
+    const float* text; int text_vocab;
+    const int* ids; const int* cnt; int2* cur; int cap;
+};
+// the last pass (a.q == a.ncb - 1) of q3_launch_pred_next with the addend row from t; -1: refused (not the last pass / the sampling variant's checks)
+int q3_launch_pred_last_text(const Q3PredNext& a, const Q3TextRows& t, hipStream_t s, bool sample);
 
 // prompt builder (H1): out[row] = tabA[idA] (+ tabB[idB]) with the reference's OOB rules
 struct Q3PromptRow { int32_t kindA, idA, kindB, idB; };  // kind: 0 none, 1 text, 2.. codec table (kind-2), -1 spk_emb, -2 zero

@@ -496,8 +496,17 @@ int q3_launch_sample_input(const Q3Sample& a, const Q3PredInput& p, const Q3Proj
 // logits (plogits) and code_q = sample_row on them with the slot's Predictor sampler — the reference's sampler (H4) on codebook_size
 // logits; a slot whose p_temperature is 0 takes sample_row's greedy branch: the same q3_argmax_key maximum as the keys' (ties -> smaller
 // index, NaN never wins). The sampler's 48 KiB of LDS (+ the row, dynamic: cbs floats) exist in the SAMPLE instantiation only.
-template <bool SAMPLE>
-__global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
+// text[id][i] through the table's out-of-range rule (src/assets_manager.rs:444-460): the prompt builder's and the streamed text rows'
+__device__ __forceinline__ float text_elem(const float* text, int text_vocab, int id, int i, int d) {
+    if (id >= 0 && id < text_vocab) return text[(size_t)id * d + i];
+    return fmodf((float)((unsigned long long)id * 17ull + (unsigned long long)i), 2.0f) - 1.0f;
+}
+__device__ __forceinline__ const Q3TextRows& text_rows(const Q3TextRows& t) { return t; }
+// TX: nothing (the kernel every pass of the default frame step runs: its arguments are Q3PredNext alone), or Q3TextRows — the last pass
+// of the text form (q3_launch_pred_last_text): the addend row is the slot's streamed text row t.cur[slot] instead of tts_pad
+template <bool SAMPLE, class... TX>
+__global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a, TX... tx) {
+    constexpr bool TEXT = sizeof...(TX) != 0;
     const int b = blockIdx.x, tid = threadIdx.x, d = a.d;
     // the per-tile keys / the logits row do not depend on the slot: requested before the slot state is looked at (one round trip less on the chain)
     unsigned long long kk = 0ull;
@@ -509,6 +518,9 @@ __global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
     const int slot = a.row_slot[b];
     Q3Slot* sl = a.slots + slot;
     const bool last = a.q == a.ncb - 1;
+    // the slot's text cursor and count travel with the slot record (both hang off `slot` alone)
+    int2 cur = make_int2(0, 0); int tcnt = 0;
+    if constexpr (TEXT) { const Q3TextRows& t = text_rows(tx...); cur = t.cur[slot]; tcnt = min(t.cnt[slot], t.cap); }
     if (!sl->active) {
         if (last && tid == 0) a.row_pos_t[b] = -1;
         return;
@@ -546,6 +558,7 @@ __global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
     // operands of the whole row first, stores after (see pred_input_row): the table rows and the running feedback sum in one round trip
     constexpr int NI = 8, NP = 4;
     const float* pr = ok ? a.pproj_q + (size_t)code * a.dp : a.proj_b;
+    const bool trow = cur.x != 0;  // (uniform over the workgroup; TEXT only)
     float pv[NP], wv[NP];
     if (!last) {
 #pragma unroll
@@ -557,7 +570,11 @@ __global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
         for (int u = 0; u < NI; ++u) {
             const int i = min(i0 + tid + u * 256, d - 1);
             ev[u] = ok ? e[i] : 0.0f; fv[u] = a.fb[(size_t)b * d + i];
-            if (last) { tp[u] = a.tts_pad[i]; nv[u] = a.nw[i]; }
+            if (last) {
+                if constexpr (TEXT) tp[u] = trow ? text_elem(text_rows(tx...).text, text_rows(tx...).text_vocab, cur.y, i, d) : a.tts_pad[i];
+                else tp[u] = a.tts_pad[i];
+                nv[u] = a.nw[i];
+            }
         }
 #pragma unroll
         for (int u = 0; u < NI; ++u) {
@@ -592,7 +609,13 @@ __global__ __launch_bounds__(256) void k_pred_next(Q3PredNext a) {
     }
     if (last) {
         __syncthreads();
-        if (tid == 0) { a.row_pos_t[b] = sl->cur_pos; sl->cur_pos = sl->cur_pos + 1; sl->n_frames = frame + 1; }
+        if (tid == 0) {
+            a.row_pos_t[b] = sl->cur_pos; sl->cur_pos = sl->cur_pos + 1; sl->n_frames = frame + 1;
+            if constexpr (TEXT) {  // the next frame's row
+                const Q3TextRows& t = text_rows(tx...);
+                t.cur[slot] = frame + 1 < tcnt ? make_int2(1, t.ids[(size_t)slot * t.cap + frame + 1]) : make_int2(0, 0);
+            }
+        }
     }
 }
 // the sampling variant's LDS: 48 KiB static + the row; above 64 KiB in all when cbs > ~3500, so the attribute is set once per device.
@@ -603,7 +626,8 @@ int q3_pred_next_prepare() {
     int dev = 0; if (hipGetDevice(&dev) != hipSuccess) dev = 0;
     std::lock_guard<std::mutex> lk(mu);
     if (done[dev & 63]) return 0;
-    if (hipFuncSetAttribute((const void*)k_pred_next<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SAMP_MAX * (int)sizeof(float)) != hipSuccess) {
+    if (hipFuncSetAttribute((const void*)k_pred_next<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SAMP_MAX * (int)sizeof(float)) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_pred_next<true, Q3TextRows>, hipFuncAttributeMaxDynamicSharedMemorySize, SAMP_MAX * (int)sizeof(float)) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }
@@ -616,6 +640,13 @@ int q3_launch_pred_next(const Q3PredNext& a, hipStream_t s, bool sample) {
     hipLaunchKernelGGL(k_pred_next<true>, dim3(a.B), dim3(256), (size_t)a.cbs * sizeof(float), s, a);
     return 0;
 }
+int q3_launch_pred_last_text(const Q3PredNext& a, const Q3TextRows& t, hipStream_t s, bool sample) {
+    if (a.q != a.ncb - 1 || !t.ids || !t.cnt || !t.cur || t.cap < 1 || (t.text_vocab > 0 && !t.text)) return -1;
+    if (!sample) { hipLaunchKernelGGL((k_pred_next<false, Q3TextRows>), dim3(a.B), dim3(256), 0, s, a, t); return 0; }
+    if (a.cbs < 1 || a.cbs > SAMP_MAX || !a.plogits || !a.prng || a.q < 1) return -1;
+    hipLaunchKernelGGL((k_pred_next<true, Q3TextRows>), dim3(a.B), dim3(256), (size_t)a.cbs * sizeof(float), s, a, t);
+    return 0;
+}
 
 // ---------------------------------------------------------------------------------------------------
 // Prompt builder (H1: src/tts/prompt.rs:141-277)
@@ -623,10 +654,7 @@ int q3_launch_pred_next(const Q3PredNext& a, hipStream_t s, bool sample) {
 __device__ __forceinline__ float prompt_elem(int kind, int id, int i, const float* text, int text_vocab,
                                              const float* const* codec, int codec0_rows, int codecq_rows, int ncb,
                                              const float* spk, int d) {
-    if (kind == 1) {  // src/assets_manager.rs:444-460
-        if (id >= 0 && id < text_vocab) return text[(size_t)id * d + i];
-        return fmodf((float)((unsigned long long)id * 17ull + (unsigned long long)i), 2.0f) - 1.0f;
-    }
+    if (kind == 1) return text_elem(text, text_vocab, id, i, d);
     if (kind >= 2) {  // src/assets_manager.rs:419-437
         const int q = kind - 2;
         const int rows = q == 0 ? codec0_rows : codecq_rows;

@@ -143,7 +143,10 @@ int q3_record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
         pn.nw = last ? e->T.attn_norm[0] : e->P.attn_norm[0]; pn.xb = last ? L.T.xb : L.P.xb; pn.ssp = last ? L.T.ssp : L.P.ssp;
         if (last ? e->T.a8 : e->P.a8) { pn.xscale = last ? L.T.ascale : L.P.ascale; pn.x_rt16 = last ? L.T.rt16 : L.P.rt16; }  // W8A8 consumer: its first operand as Q8_0 blocks
         if (smp) { pn.plogits = L.plogits; pn.cbs = cbs; pn.prng = e->prng; pn.prng_stride = cap * (ncb - 1); }
-        bad += q3_launch_pred_next(pn, s, smp) != 0;
+        if (last && e->ts_variant) {  // streamed text rows instead of tts_pad; every other launch of the frame is the default's
+            const Q3TextRows tr{e->text, m.text_vocab, e->ts_ids, e->ts_cnt, e->ts_cur, cap};
+            bad += q3_launch_pred_last_text(pn, tr, s, smp) != 0;
+        } else bad += q3_launch_pred_next(pn, s, smp) != 0;
     };
     for (int q = 0; q < ncb - 1; ++q) {  // pass q produces code_{q+1}
         const int rows = q == 0 ? 2 * B : B;
@@ -166,7 +169,7 @@ int q3_record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
     return bad;
 }
 
-// one captured frame step per row bucket, of the variant e->pred_variant names
+// one captured frame step per row bucket, of the variant e->pred_variant and e->ts_variant name
 int q3_capture_frames(q3tts_engine* e, std::vector<hipGraph_t>& graphs, std::vector<hipGraphExec_t>& execs) {
     Q3Lane& L = e->lane;
     graphs.resize(e->buckets.size(), nullptr); execs.resize(e->buckets.size(), nullptr);

@@ -255,6 +255,8 @@ extern "C" int q3tts_node_generate_batch(q3tts_node* n, const q3tts_request* req
     for (int i = 0; i < n_reqs; ++i) { memset(&outs[i], 0, sizeof(outs[i])); outs[i].status = Q3TTS_ERR_STATE; if (gather) pcm_i16[i] = nullptr; }
     for (int i = 0; i < n_reqs; ++i)  // a prefix belongs to one engine (include/q3tts.h, "voice prefixes")
         if (reqs[i].prefix) return node_err(n, Q3TTS_ERR_INVALID, "node: requests with a voice prefix are not supported (a prefix belongs to one engine)");
+    for (int i = 0; i < n_reqs; ++i)  // streamed text stays on one engine (include/q3tts.h, "streaming text input")
+        if ((reqs[i].text_stream == 1) || (reqs[i].text_open == 1)) return node_err(n, Q3TTS_ERR_INVALID, "node: requests with text_stream are not supported");
     if (gather) { const int rc = node_comms(n); if (rc != Q3TTS_OK) return rc; }
     const double t0 = node_now_ms();
     // ---- generation: device r runs requests {i : i mod G == r} through its own continuous-batching engine, no exchange

@@ -46,11 +46,19 @@ struct Batch {  // the events of one chunk boundary, published together once the
 struct IdState {
     bool cancelled = false, queued = true, final_ready = false;
     double t_submit = 0, t_first = 0;
+    // streamed text (include/q3tts.h, "streaming text input"): the request's trailing ids T so far (tts_eos last once closed)
+    bool ts = false, closed = true;
+    std::vector<int32_t> T;
 };
 
 struct SSlot {
     std::unique_ptr<SReq> req;  // null: the slot is free
     int delivered = 0;          // samples handed out in chunks so far
+    // streamed text: t_len / t_closed: the worker's view of T; t_up: entries of T on the device. parked: the slot sits out of the frame
+    // steps (its device record is idle) until its text suffices; rec: its real record meanwhile
+    bool ts = false, t_closed = true, parked = false;
+    int t_len = 0, t_up = 0;
+    Q3Slot rec{};
 };
 
 }  // namespace
@@ -73,6 +81,7 @@ struct q3tts_session {
     std::deque<SEv> ready;
     uint64_t next_id = 1;
     bool stop = false, dead = false;
+    bool text_dirty = false;        // q3tts_session_append_text added something the worker has not seen
     int held_ring = -1;             // ring buffer of the chunk the consumer holds (released at its next call)
     int worker_rc = Q3TTS_OK;
     std::string err;
@@ -152,6 +161,41 @@ int take_ring(q3tts_session* s, int k) {
     return s->stop ? kStopping : Q3TTS_OK;
 }
 
+void free_slot(q3tts_session* s, int b) {
+    SSlot& sl = s->slots[b];
+    sl.req.reset(); sl.ts = false; sl.parked = false;
+    s->e->ts_slot[b] = 0;
+}
+
+// the slot's device record (between chunks; the caller synchronises the stream before `rec` can change)
+int put_record(q3tts_engine* e, int b, const Q3Slot* rec) {
+    Q3_HIP(e, hipMemcpyAsync(e->slots + b, rec, sizeof(Q3Slot), hipMemcpyHostToDevice, e->stream));
+    return Q3TTS_OK;
+}
+// Parking: the slot leaves the frame steps with everything it needs to come back. Its K/V, codes and vocoder state stay
+// where they are; the two rows that outlive a frame go to the slot's side rows (any row of the bucket is overwritten by the GEMMs, and
+// q3_plan_rows may move it), the real record stays on the host (q3_run_chunk refreshes the mirror from the idle one on the device).
+int park(q3tts_session* s, int b, const Q3Slot& rec) {
+    static const Q3Slot idle{};
+    q3tts_engine* e = s->e;
+    SSlot& sl = s->slots[b];
+    TRY(q3_park_rows(e, b, true));
+    sl.rec = rec; sl.parked = true;
+    return put_record(e, b, &idle);
+}
+// after q3_plan_rows with the slot among the live ones: the rows into its row, the record back
+int resume(q3tts_session* s, int b) {
+    q3tts_engine* e = s->e;
+    SSlot& sl = s->slots[b];
+    TRY(q3_park_rows(e, b, false));
+    sl.parked = false;
+    e->slots_host[b] = sl.rec;
+    return put_record(e, b, &sl.rec);
+}
+bool text_ready(const SSlot& sl, int n_frames) {
+    return !sl.ts || q3tts_k_text_ready(sl.t_len + (sl.t_closed ? 0 : 1), sl.t_closed ? 1 : 0, n_frames) != 0;  // x = the prompt's id + T without tts_eos
+}
+
 // upload a free state (active = 0) for slot b from the pinned staging half admissions use; its vocoder work so far precedes fin_ev[b]
 int retire_slot(q3tts_session* s, int b) {
     q3tts_engine* e = s->e;
@@ -159,7 +203,7 @@ int retire_slot(q3tts_session* s, int b) {
     memset(st, 0, sizeof(*st));
     Q3_HIP(e, hipMemcpyAsync(e->slots + b, st, sizeof(Q3Slot), hipMemcpyHostToDevice, e->stream));
     Q3_HIP(e, hipEventRecord(e->fin_ev[b], e->vstream));
-    s->slots[b].req.reset();
+    free_slot(s, b);
     return Q3TTS_OK;
 }
 
@@ -172,6 +216,14 @@ int step(q3tts_session* s) {
     std::vector<std::unique_ptr<SReq>> adm;
     int nfree = 0;
     for (int b = 0; b < B; ++b) if (!s->slots[b].req) ++nfree;
+    struct TextNow { bool have = false, closed = true; std::vector<int32_t> T; };  // a streamed request's text as of this boundary
+    std::vector<TextNow> tn(B), tn_adm;
+    auto text_now = [&](uint64_t id, int t_up, TextNow& t) {  // (mu held) T is copied only when the device lacks some of it
+        auto it = s->ids.find(id);
+        if (it == s->ids.end() || !it->second.ts) return;
+        t.have = true; t.closed = it->second.closed;
+        if ((int)it->second.T.size() != t_up) t.T = it->second.T;
+    };
     {
         std::lock_guard<std::mutex> lk(s->mu);
         cancels.swap(s->cancels);
@@ -180,6 +232,10 @@ int step(q3tts_session* s) {
             adm.push_back(std::move(s->pending.front()));
             s->pending.pop_front();
         }
+        s->text_dirty = false;
+        for (int b = 0; b < B; ++b) if (s->slots[b].req && s->slots[b].ts) text_now(s->slots[b].req->id, s->slots[b].t_up, tn[b]);
+        tn_adm.resize(adm.size());
+        for (size_t i = 0; i < adm.size(); ++i) if (adm[i]->r.text_stream == 1) text_now(adm[i]->id, -1, tn_adm[i]);
     }
     Batch bt;
     // 1. cancellations: the slot is retired now and admitted into again from the next boundary on
@@ -192,6 +248,17 @@ int step(q3tts_session* s) {
                 cool[b] = 1; retired = true;
                 bt.evs.push_back(final_ev(id, Q3TTS_EV_CANCELLED, Q3TTS_OK));
             }
+    // 1b. streamed text: what arrived since the last boundary, and the readiness rule — a running slot whose text does not reach 4 more
+    // frames is parked before the rows are planned without it
+    std::vector<int> nf(B, 0);
+    bool moved = false;
+    for (int b = 0; b < B; ++b) {
+        SSlot& sl = s->slots[b];
+        if (!sl.req || !sl.ts) continue;
+        if (tn[b].have) { sl.t_closed = tn[b].closed; if (!tn[b].T.empty()) sl.t_len = (int)tn[b].T.size(); }
+        nf[b] = sl.parked ? sl.rec.n_frames : e->slots_host[b].n_frames;
+        if (!sl.parked && !text_ready(sl, nf[b])) { TRY(park(s, b, e->slots_host[b])); moved = true; }
+    }
     // 2. admissions into free slots
     std::vector<int> as;
     std::vector<const q3tts_request*> ar;
@@ -199,7 +266,7 @@ int step(q3tts_session* s) {
         if (!s->slots[b].req && !cool[b]) { as.push_back(b); ar.push_back(&adm[as.size() - 1]->r); }
     for (int b : as) Q3_HIP(e, hipEventSynchronize(e->fin_ev[b]));  // the previous occupant's vocoder work is done before the slot's reset
     std::vector<int> live(as);
-    for (int b = 0; b < B; ++b) if (s->slots[b].req) live.push_back(b);
+    for (int b = 0; b < B; ++b) if (s->slots[b].req && (!s->slots[b].parked || text_ready(s->slots[b], nf[b]))) live.push_back(b);
     if (!live.empty()) TRY(q3_plan_rows(e, live));
     if (!as.empty()) {
         std::vector<int> rcs(as.size());
@@ -211,11 +278,35 @@ int step(q3tts_session* s) {
             if (rcs[i] != Q3TTS_OK) { bt.evs.push_back(final_ev(adm[i]->id, Q3TTS_EV_FAILED, rcs[i])); continue; }
             SSlot& sl = s->slots[as[i]];
             sl.req = std::move(adm[i]); sl.delivered = 0; s->voc_frames[as[i]] = 0;
+            sl.ts = sl.req->r.text_stream == 1; sl.parked = false;
+            if (!sl.ts) continue;
+            std::vector<int32_t> T0;  // what the admission put on the device: the request as submitted
+            q3_text_trailing(&sl.req->r, T0);
+            sl.t_up = sl.t_len = (int)T0.size(); sl.t_closed = !(sl.req->r.text_open == 1);
+            tn[as[i]] = std::move(tn_adm[i]);
+            TextNow& t = tn[as[i]];
+            if (t.have) { sl.t_closed = t.closed; if ((int)t.T.size() > sl.t_len) sl.t_len = (int)t.T.size(); }
+            nf[as[i]] = 0;
+            if (!text_ready(sl, 0)) { TRY(park(s, as[i], e->slots_host[e->B + as[i]])); moved = true; }  // (the staging half holds the record just admitted)
         }
     }
+    // 2b. parked slots whose text suffices come back (the rows were planned with them), and new text goes to the device
+    for (int b = 0; b < B; ++b) {
+        SSlot& sl = s->slots[b];
+        if (!sl.req || !sl.ts) continue;
+        if (sl.parked) {
+            if (!text_ready(sl, nf[b])) continue;
+            TRY(resume(s, b)); moved = true;
+        }
+        if (sl.t_len > sl.t_up && (int)tn[b].T.size() >= sl.t_len) {
+            TRY(q3_text_rows_set(e, b, tn[b].T.data(), sl.t_up, sl.t_len, nf[b]));
+            sl.t_up = sl.t_len;
+        }
+    }
+    if (moved) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (the record uploads read the slots' host copies)
     std::vector<char> run(B, 0);
     bool any = false;
-    for (int b = 0; b < B; ++b) if (s->slots[b].req) { run[b] = 1; any = true; }
+    for (int b = 0; b < B; ++b) if (s->slots[b].req && !s->slots[b].parked) { run[b] = 1; any = true; }
     if (!any) {
         if (retired) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (the staging half is rewritten by the next admission)
         if (!bt.evs.empty()) s->flight.push_back(std::move(bt));
@@ -283,7 +374,7 @@ int step(q3tts_session* s) {
             Q3_HIP(e, hipMemcpyAsync(o.codes, e->codes + (size_t)b * e->cfg.max_steps_cap * ncb, sizeof(int32_t) * (size_t)st.n_frames * ncb,
                                      hipMemcpyDeviceToHost, e->stream));
         Q3_HIP(e, hipEventRecord(e->fin_ev[b], vs));  // (behind the gather that read the slot's PCM)
-        s->slots[b].req.reset();
+        free_slot(s, b);
         bt.evs.push_back(v);
     }
     if (!fin.empty()) Q3_HIP(e, hipStreamSynchronize(e->stream));
@@ -313,15 +404,16 @@ void worker(q3tts_session* s) {
     q3tts_engine* e = s->e;
     int rc = hipSetDevice(e->cfg.device) == hipSuccess ? Q3TTS_OK : q3_set_err(e, Q3TTS_ERR_DEVICE, "session: hipSetDevice");
     while (rc == Q3TTS_OK) {
-        bool running = false;
-        for (const SSlot& sl : s->slots) if (sl.req) running = true;
+        bool running = false, room = false;  // running: a slot takes frame steps (parked slots wait for text); room: a slot is free
+        for (const SSlot& sl : s->slots) { if (sl.req && !sl.parked) running = true; if (!sl.req) room = true; }
         bool work;
         {
             std::unique_lock<std::mutex> lk(s->mu);
-            if (!running && s->flight.empty())  // idle: sleep until a submission, a cancel or close
-                s->cv_work.wait(lk, [&] { return s->stop || !s->pending.empty() || !s->cancels.empty(); });
+            auto todo = [&] { return (room && !s->pending.empty()) || !s->cancels.empty() || s->text_dirty; };
+            if (!running && s->flight.empty())  // idle: sleep until a submission that fits, a cancel, new text or close
+                s->cv_work.wait(lk, [&] { return s->stop || todo(); });
             if (s->stop) break;
-            work = !s->pending.empty() || !s->cancels.empty();
+            work = todo();
         }
         if (!running && !work) { rc = publish(s, true); continue; }  // only copies in flight: wait for the oldest
         rc = step(s);
@@ -410,14 +502,44 @@ extern "C" int q3tts_session_submit(q3tts_session* s, const q3tts_request* req, 
         std::lock_guard<std::mutex> lk(s->mu);
         return serr(s, Q3TTS_ERR_INVALID, "submit: the request's prompt cannot be copied (n_tok outside 1..n_ctx or a null array with a length)");
     }
+    if ((req->text_open == 1) && !(req->text_stream == 1)) { std::lock_guard<std::mutex> lk(s->mu); return serr(s, Q3TTS_ERR_INVALID, "submit: text_open needs text_stream = 1"); }
+    if ((req->text_stream == 1) && (req->prompt_embd || !req->prompt || req->prompt->n_text < 1)) {
+        std::lock_guard<std::mutex> lk(s->mu);
+        return serr(s, Q3TTS_ERR_INVALID, "submit: text_stream needs a prompt built from ids with n_text >= 1 (not prompt_embd)");
+    }
     {
         std::lock_guard<std::mutex> lk(s->mu);
         if (s->stop || s->dead) return serr(s, Q3TTS_ERR_STATE, s->dead ? "submit: the session's worker failed" : "submit: the session is closing");
         q->id = s->next_id++;
         IdState st; st.t_submit = q3_now_ms();
+        if (q->r.text_stream == 1) { st.ts = true; st.closed = !(q->r.text_open == 1); q3_text_trailing(&q->r, st.T); }
         s->ids[q->id] = st;
         *id = q->id;
         s->pending.push_back(std::move(q));
+    }
+    s->cv_work.notify_one();
+    return Q3TTS_OK;
+}
+
+// the readiness rule (include/q3tts.h, "streaming text input"): the steps producing frames f .. f + 3 read T[f .. f + 3], and open text has
+// len(T) = n_text - 1
+extern "C" int q3tts_k_text_ready(int32_t n_text, int32_t closed, int32_t n_frames) {
+    return (closed || (long long)n_text - 1 >= (long long)n_frames + 4) ? 1 : 0;
+}
+
+extern "C" int q3tts_session_append_text(q3tts_session* s, uint64_t id, const uint32_t* ids, int32_t n, int32_t close) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (n < 0 || (n > 0 && !ids)) return serr(s, Q3TTS_ERR_INVALID, "append_text: ids missing");
+        auto it = s->ids.find(id);
+        if (it == s->ids.end() || it->second.final_ready || it->second.cancelled) return serr(s, Q3TTS_ERR_INVALID, "append_text: unknown id, or the request has finished");
+        IdState& st = it->second;
+        if (!st.ts) return serr(s, Q3TTS_ERR_INVALID, "append_text: the request was submitted without text_stream");
+        if (st.closed) return serr(s, Q3TTS_ERR_INVALID, "append_text: the request's text is closed");
+        for (int i = 0; i < n; ++i) st.T.push_back((int32_t)ids[i]);
+        if (close) { st.T.push_back(EOS_TOKEN); st.closed = true; }
+        if (n > 0 || close) s->text_dirty = true;
     }
     s->cv_work.notify_one();
     return Q3TTS_OK;

@@ -71,9 +71,11 @@ class PromptDesc(C.Structure):
 class Request(C.Structure):
     _fields_ = [
         ("prompt_embd", C.POINTER(C.c_float)), ("n_tok", C.c_int32),
+        ("text_stream", C.c_int32),  # 1: the streamed text layout (include/q3tts.h, "streaming text input"); in the alignment gap behind n_tok
         ("prompt", C.POINTER(PromptDesc)),
         ("use_engine_sampler", C.c_int32),
         ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float), ("has_seed", C.c_int32),
+        ("text_open", C.c_int32),  # sessions: 1 = more text follows (q3tts_session_append_text); in the alignment gap behind has_seed
         ("seed", C.c_uint64),
         ("max_steps", C.c_int32), ("min_frames", C.c_int32), ("force_eos_at", C.c_int32), ("want_pcm", C.c_int32),
         ("prefix", C.c_void_p),  # const q3tts_prefix*: NULL, or a voice prefix of the same engine (include/q3tts.h, "voice prefixes")
@@ -156,6 +158,7 @@ SYMBOLS = [
     "q3tts_set_predictor_sampler", "q3tts_get_predictor_sampler", "q3tts_set_repetition_penalty", "q3tts_get_repetition_penalty",
     "q3tts_k_pred_variant",
     "q3tts_set_output_rate", "q3tts_get_output_rate", "q3tts_resample", "q3tts_k_resample_table", "q3tts_k_pcm_resample",
+    "q3tts_session_append_text", "q3tts_k_text_ready",
 ]
 
 
@@ -207,6 +210,8 @@ def load_library(path=None):
     lib.q3tts_session_close.argtypes = [vp]
     lib.q3tts_session_last_error.argtypes = [vp]
     lib.q3tts_session_last_error.restype = C.c_char_p
+    lib.q3tts_session_append_text.argtypes = [vp, C.c_uint64, u32p, C.c_int32, C.c_int32]
+    lib.q3tts_k_text_ready.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.q3tts_k_pcm_pack.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, vp,
                                      C.c_int64]
     lib.q3tts_set_output_rate.argtypes = [vp, C.c_int32]

@@ -309,6 +309,73 @@ class TtsEngine:
                 elif kind != _abi.EV_DONE:
                     raise _abi.Q3Error(f"generation failed with status {res.status if res is not None else kind}")
 
+    def stream_text_with_voice(self, pieces, voice: VoiceFile, instruct=None, *, prefix=None, seed=None):
+        """Speech for text that is still being written (an extension; include/q3tts.h, "streaming text input"). pieces: an iterator of
+        strings or id lists, e.g. the words a language model emits; the first non-empty piece starts the request, the others are fed
+        from a helper thread as the iterator yields them, and its end closes the text. Yields (f32 chunk, is_final) as the 4-frame
+        chunks are produced: the first can sound once 5 text ids exist, long before the sentence is complete.
+
+        Each piece is tokenised on its own, so cut at word boundaries (keep the leading space with the next word, as the tokenizer's
+        pre-tokeniser would): a piece that ends inside a word gives other ids than the whole text. The audio is that of the streamed
+        layout for the concatenated ids, however they were cut and whenever they arrived; it is NOT the audio of generate_with_voice
+        for the same text (another prompt layout)."""
+        import threading
+        sc = self.sampler_config
+        if prefix is not None:
+            self._check_prefix(prefix, voice, instruct)
+        it = iter(pieces)
+        first = np.zeros(0, dtype=np.uint32)
+        ended = False
+        while first.size == 0:
+            try:
+                first = self._encode(next(it))
+            except StopIteration:
+                ended = True
+                break
+        if first.size == 0:
+            raise ValueError("stream_text_with_voice: the pieces hold no text")
+        desc, keep = self._desc(first, voice, instruct, part="whole" if prefix is None else "text")
+        with native.NativeSession(self._native) as sess:
+            rid = sess.submit(desc=desc, temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p, seed=sc.seed if seed is None else seed,
+                              max_steps=self.max_steps, prefix=prefix, text_stream=True, text_open=not ended)
+            failure = []
+            gate, live = threading.Lock(), [True]  # the feeder touches the session only while the consumer is inside this block
+
+            def feed():
+                try:
+                    for piece in it:
+                        ids = self._encode(piece)
+                        with gate:
+                            if not live[0]:
+                                return
+                            if ids.size:
+                                sess.append_text(rid, ids)
+                    with gate:
+                        if live[0]:
+                            sess.append_text(rid, None, close=True)
+                except Exception as ex:  # the request ended meanwhile (EOS, max_steps), or the iterator failed
+                    failure.append(ex)
+                    with gate:
+                        if live[0]:
+                            try:
+                                sess.cancel(rid)
+                            except _abi.Q3Error:
+                                pass
+            th = threading.Thread(target=feed, daemon=True) if not ended else None
+            if th is not None:
+                th.start()
+            try:
+                for _, kind, pcm, is_final, res in sess.events():
+                    if kind == _abi.EV_CHUNK:
+                        yield pcm, is_final
+                    elif kind == _abi.EV_CANCELLED and failure:
+                        raise failure[0]
+                    elif kind != _abi.EV_DONE:
+                        raise _abi.Q3Error(f"generation failed with status {res.status if res is not None else kind}")
+            finally:
+                with gate:   # (also when the consumer stops early: the feeder ends at its next piece, the session closes below)
+                    live[0] = False
+
     def load_clone_encoders(self, clone_config=None):
         """The reference loads onnx/qwen3_tts_codec_encoder.onnx and onnx/qwen3_tts_speaker_encoder.onnx when they exist
         (src/tts/engine.rs:105-119). Those graphs are not available; this loads the family-structure encoders with seeded

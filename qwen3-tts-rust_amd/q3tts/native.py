@@ -156,7 +156,9 @@ class NativeEngine:
 
     @staticmethod
     def make_request(embd=None, desc=None, temperature=0.0, top_k=40, top_p=0.9, seed=None, max_steps=0, min_frames=0,
-                     force_eos_at=-1, want_pcm=0, use_engine_sampler=0, prefix=None):
+                     force_eos_at=-1, want_pcm=0, use_engine_sampler=0, prefix=None, text_stream=False, text_open=False):
+        """text_stream: the streamed text layout (include/q3tts.h, "streaming text input"; needs desc with at least one text id);
+        text_open (sessions only): more text follows through NativeSession.append_text."""
         r = _abi.Request()
         keep = []
         if prefix is not None:
@@ -175,6 +177,7 @@ class NativeEngine:
         r.temperature, r.top_k, r.top_p = temperature, top_k, top_p
         r.has_seed, r.seed = (0, 0) if seed is None else (1, seed)
         r.max_steps, r.min_frames, r.force_eos_at, r.want_pcm = max_steps, min_frames, force_eos_at, want_pcm
+        r.text_stream, r.text_open = int(bool(text_stream)), int(bool(text_open))
         return r, keep
 
     def _unpack(self, res):
@@ -426,8 +429,8 @@ class NativeSession:
             raise _abi.Q3Error(f"{what} failed ({rc}): {self.lib.q3tts_session_last_error(self.h).decode()}")
 
     def submit(self, **request_kw):
-        """request_kw: NativeEngine.make_request keywords, prefix= included (want_pcm is ignored: a session always produces PCM).
-        Returns the id."""
+        """request_kw: NativeEngine.make_request keywords, prefix=, text_stream= and text_open= included (want_pcm is ignored: a session
+        always produces PCM). Returns the id."""
         if not self.h:
             raise _abi.Q3Error("q3tts_session_submit: the session is closed")
         r, keep = NativeEngine.make_request(**request_kw)
@@ -438,6 +441,13 @@ class NativeSession:
 
     def cancel(self, rid):
         self._check(self.lib.q3tts_session_cancel(self.h, rid), "q3tts_session_cancel")
+
+    def append_text(self, rid, ids, close=False):
+        """q3tts_session_append_text: more text ids for a request submitted with text_stream=True, text_open=True; close=True ends its text
+        (ids may then be empty). Thread-safe."""
+        t = np.ascontiguousarray([] if ids is None else ids, dtype=np.uint32)
+        self._check(self.lib.q3tts_session_append_text(self.h, rid, _ptr(t, u32p) if t.size else None, t.size, 1 if close else 0),
+                    "q3tts_session_append_text")
 
     def next(self, timeout_ms=-1):
         """One event as (id, kind, pcm ndarray | None, is_final, GenResult | None), or None on timeout."""

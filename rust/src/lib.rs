@@ -39,8 +39,12 @@ pub struct q3tts_prompt_desc {
 }
 #[repr(C)]
 pub struct q3tts_request {
-    pub prompt_embd: *const c_float, pub n_tok: i32, pub prompt: *const q3tts_prompt_desc, pub use_engine_sampler: i32,
-    pub temperature: c_float, pub top_k: i32, pub top_p: c_float, pub has_seed: i32, pub seed: u64,
+    pub prompt_embd: *const c_float, pub n_tok: i32,
+    pub text_stream: i32,   // 1: the streamed text layout (include/q3tts.h, "streaming text input"); 0: the whole text is in the prompt. In the gap behind n_tok
+    pub prompt: *const q3tts_prompt_desc, pub use_engine_sampler: i32,
+    pub temperature: c_float, pub top_k: i32, pub top_p: c_float, pub has_seed: i32,
+    pub text_open: i32,     // sessions only: 1 = more text follows (q3tts_session_append_text); 0: the text is closed. In the gap behind has_seed
+    pub seed: u64,
     pub max_steps: i32, pub min_frames: i32, pub force_eos_at: i32, pub want_pcm: i32,
     pub prefix: *const q3tts_prefix,   // null, or a voice prefix of the same engine: the prompt is its rows followed by this request's own
 }
@@ -191,7 +195,7 @@ impl TtsEngine {
             prompt_embd: std::ptr::null(), n_tok: 0, prompt: &desc, use_engine_sampler: 0,
             temperature: self.sampler.temperature, top_k: self.sampler.top_k, top_p: self.sampler.top_p,
             has_seed: self.sampler.seed.is_some() as i32, seed: self.sampler.seed.unwrap_or(0),
-            max_steps: self.max_steps as i32, min_frames: 0, force_eos_at: -1, want_pcm: 1, prefix: std::ptr::null(),
+            max_steps: self.max_steps as i32, min_frames: 0, force_eos_at: -1, want_pcm: 1, prefix: std::ptr::null(), text_stream: 0, text_open: 0,
         };
         unsafe {
             let mut out: q3tts_result = std::mem::zeroed();
@@ -222,7 +226,7 @@ impl TtsEngine {
             prompt_embd: std::ptr::null(), n_tok: 0, prompt: &desc, use_engine_sampler: 0,
             temperature: self.sampler.temperature, top_k: self.sampler.top_k, top_p: self.sampler.top_p,
             has_seed: self.sampler.seed.is_some() as i32, seed: self.sampler.seed.unwrap_or(0),
-            max_steps: self.max_steps as i32, min_frames: 0, force_eos_at: -1, want_pcm: 1, prefix: std::ptr::null(),
+            max_steps: self.max_steps as i32, min_frames: 0, force_eos_at: -1, want_pcm: 1, prefix: std::ptr::null(), text_stream: 0, text_open: 0,
         };
         unsafe {
             let err = |e: *mut q3tts_engine| CStr::from_ptr(q3tts_last_error(e)).to_string_lossy().into_owned();
