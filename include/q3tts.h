@@ -543,6 +543,36 @@ int q3tts_k_attention(int32_t device, const float* qkv /*[n][(Hq+2Hkv)*hd]*/, in
 int q3tts_k_attention_decode(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t n_head,
                              int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps, float rope_theta,
                              const int32_t* mrope_sections, int32_t policy, float* out_f32, uint16_t* out_bf16);
+/* The attention hooks below reach every kernel of csrc/q3_attend.hip with every output form, and return the cache. Shared by the three:
+ *   out_form 0: out = f32 rows [rows][Hq*hd]; 1: out = the bf16 operand of the O projection as bit patterns [rows][Hq*hd] (untiled here);
+ *   2: out = int8 quants [rows][Hq*hd] and out_scale = f32 block scales [rows][Hq*hd/32] of the Q8_0 blocks a W8A8 engine's launch writes.
+ *   k_cache / v_cache (optional): the cache of every slot after the launch, un-blocked, as bf16 bits [slot][n_kv_head][n_ctx][hd].
+ * Every argument is checked on the host — head_dim 128, n_ctx a multiple of 64, the GQA ratio, every length and pos0 + n <= n_ctx — and a
+ * bad one returns Q3TTS_ERR_INVALID with nothing launched. */
+/* Whole prompt runs as the engine's admission launches them: run i (slot i) has run_pos0[i] rows that k_qk_prep puts into the cache (they
+ * stand for a voice prefix) and then run_n[i] rows at positions run_pos0[i] ..; qkv holds run 0's run_pos0[0] + run_n[0] rows, then run
+ * 1's, ... The runs' rows go through k_qk_prep and ONE non-fused attention launch that carries the run table, under prefill policy
+ * `policy` (-1: the current one; 0 / 1 / 2 as in q3tts_k_attend_policy). out rows: the runs' rows back to back ([sum run_n]). */
+int q3tts_k_attention_runs(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx,
+                           int32_t n_head, int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
+                           float rope_theta, const int32_t* mrope_sections, int32_t policy, int32_t out_form, void* out, float* out_scale,
+                           uint16_t* k_cache, uint16_t* v_cache);
+/* q3tts_k_attention_decode with one output form per call and the cache; row_indexed = 1: the Predictor's addressing (no row tables:
+ * slot = row % n_slots, every slot at the same length lens[0]). out rows: [n_slots]. */
+int q3tts_k_attention_decode_ex(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t n_head,
+                                int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
+                                float rope_theta, const int32_t* mrope_sections, int32_t policy, int32_t row_indexed, int32_t out_form,
+                                void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache);
+/* The Predictor's pass A (k_attend_pair): qkv [2 * n_slots] rows — row b at position 0 and row n_slots + b at position 1 of slot b — in one
+ * launch on an empty cache; two query heads per KV head. out rows: [2 * n_slots], in the same order. */
+int q3tts_k_attention_pair(int32_t device, const float* qkv, int32_t n_slots, int32_t n_ctx, int32_t n_head, int32_t n_kv_head,
+                           int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps, float rope_theta,
+                           const int32_t* mrope_sections, int32_t out_form, void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache);
+/* Host only: the kernel the attention launcher takes for a shape under the current policies, without launching. fused 0 (rows of runs), 1
+ * (one row per slot) or 2 (pass A); n_seg = 0: a launch without a run table. *kernel = 0 / 1 / 2: k_attend<1 / 2 / 4, false>; 3 / 4:
+ * k_attend<2 / 4, true>; 5: k_attend_gqa2; 6: k_attend_small<2>; 7: k_attend_pair; 8: k_attend_prefill; -1: the launcher refuses. */
+int q3tts_k_attend_pick(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t,
+                        int32_t n_kv_head, int32_t* kernel);
 /* sampler (H4: src/models/llama/mod.rs:666-772) on n rows of logits; r_uniform[n] are the f32 draws */
 int q3tts_k_sample(int32_t device, const float* logits, int32_t n, int32_t ld, int32_t limit, float temperature,
                    int32_t top_k, float top_p, const float* r_uniform, int32_t* out_ids);

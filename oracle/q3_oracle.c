@@ -363,6 +363,35 @@ void q3o_attention(const float* qkv, int32_t n_rows, int32_t pos0, int32_t Hq, i
     attn_rows(qkv, n_rows, pos0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_ctx, out);
     free(kc); free(vc); free(cs); free(sn);
 }
+/* The preparation stage of q3o_attention on its own: for qkv rows at positions pos0 .. pos0 + n_rows - 1, q after RMSNorm + RoPE (f32,
+ * [n_rows][Hq * hd]) and the bf16-rounded K and V rows attn_rows_from puts in its cache ([n_rows][Hkv * hd] each, as f32 values) */
+void q3o_attention_prep(const float* qkv, int32_t n_rows, int32_t pos0, int32_t Hq, int32_t Hkv, int32_t hd, const float* qnw, const float* knw,
+                        float eps, float theta, const int32_t* sections, float* q_out, float* k_out, float* v_out) {
+    const int n_ctx = pos0 + n_rows, half = hd / 2, ld = (Hq + 2 * Hkv) * hd;
+    float* cs = (float*)malloc((size_t)n_ctx * half * 4);
+    float* sn = (float*)malloc((size_t)n_ctx * half * 4);
+    rope_tables(n_ctx, hd, theta, sections, cs, sn);
+    float* tmp = (float*)malloc((size_t)hd * 4);
+    for (int r = 0; r < n_rows; ++r) {
+        const int pos = pos0 + r;
+        const float* row = qkv + (size_t)r * ld;
+        for (int g = 0; g < Hkv; ++g) {
+            q3o_rmsnorm(row + (size_t)(Hq + g) * hd, hd, knw, eps, tmp);
+            rope_apply(tmp, hd, cs + (size_t)pos * half, sn + (size_t)pos * half);
+            const float* vs = row + (size_t)(Hq + Hkv + g) * hd;
+            for (int d = 0; d < hd; ++d) {
+                k_out[((size_t)r * Hkv + g) * hd + d] = round_bf16(tmp[d]);
+                v_out[((size_t)r * Hkv + g) * hd + d] = round_bf16(vs[d]);
+            }
+        }
+        for (int h = 0; h < Hq; ++h) {
+            float* qd = q_out + ((size_t)r * Hq + h) * hd;
+            q3o_rmsnorm(row + (size_t)h * hd, hd, qnw, eps, qd);
+            rope_apply(qd, hd, cs + (size_t)pos * half, sn + (size_t)pos * half);
+        }
+    }
+    free(tmp); free(cs); free(sn);
+}
 /* q3o_attention's output for the LAST row only (rows 0 .. n_rows - 1 at positions 0 .. n_rows - 1, the earlier ones only appended):
  * the decode step over long caches without the all-rows cost */
 void q3o_attention_last(const float* qkv, int32_t n_rows, int32_t Hq, int32_t Hkv, int32_t hd, const float* qnw, const float* knw,

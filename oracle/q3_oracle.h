@@ -90,6 +90,10 @@ void q3o_attention(const float* qkv, int32_t n_rows, int32_t pos0, int32_t n_hea
 /* the same for the LAST of n_rows rows at positions 0 .. n_rows - 1 only: out[Hq * head_dim] */
 void q3o_attention_last(const float* qkv, int32_t n_rows, int32_t n_head, int32_t n_kv_head, int32_t head_dim, const float* q_norm_w,
                         const float* k_norm_w, float eps, float rope_theta, const int32_t* mrope_sections, float* out);
+/* q3o_attention's preparation stage on its own: q after RMSNorm + RoPE (f32, [n_rows][Hq * hd]) and the bf16-rounded K and V rows it
+ * caches (f32 values, [n_rows][Hkv * hd] each) for rows at positions pos0 .. pos0 + n_rows - 1 */
+void q3o_attention_prep(const float* qkv, int32_t n_rows, int32_t pos0, int32_t n_head, int32_t n_kv_head, int32_t head_dim, const float* q_norm_w,
+                        const float* k_norm_w, float eps, float rope_theta, const int32_t* mrope_sections, float* q_out, float* k_out, float* v_out);
 /* one output element of v_mfma_f32_16x16x32_bf16 (gfx950), restated in integers: a[32], b[32] bf16 bits in operand order
  * (position 8g + e = operand e of lane group g), c the accumulator. _ref: the 128-bit form the 64-bit one is tested against. */
 float q3o_mfma_bf16_dot32(const uint16_t* a, const uint16_t* b, float c);

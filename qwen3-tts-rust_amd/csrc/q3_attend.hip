@@ -820,36 +820,51 @@ void q3_attend_policy_get(int* decode, int* prefill) { att_policy_init(); *decod
 // dynamic LDS above 64 KiB has to be allowed per kernel (and per device); a refused attribute is a refused launch
 static hipError_t att_allow_lds(const void* kernel, size_t lds) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
 
-// 0: launched. Nonzero: refused, nothing launched — a head size other than Q3_ATT_HD, a GQA ratio outside {1, 2, 4}, a fused launch
-// without a second wave for k / v (R == 1), the pair kernel for another ratio than 2, or a device that refuses the LDS size.
-int q3_launch_attend(const Q3Attend& a, hipStream_t s) {
+// The kernel q3_launch_attend takes for a launch, under the current policies (the one place that decides; q3tts_k_attend_pick asks here too).
+// Q3_ATT_REFUSED: a head size other than Q3_ATT_HD, a GQA ratio outside {1, 2, 4}, a fused launch without a second wave for k / v (R == 1),
+// or the pair kernel for another ratio than 2.
+int q3_attend_pick(const Q3Attend& a) {
     att_policy_init();
-    if (a.hd != Q3_ATT_HD || a.Hkv <= 0 || a.Hq % a.Hkv) return 1;
+    if (a.hd != Q3_ATT_HD || a.Hkv <= 0 || a.Hq % a.Hkv) return Q3_ATT_REFUSED;
     const int R = a.Hq / a.Hkv;
-    if ((R != 1 && R != 2 && R != 4) || (a.fused && R == 1) || (a.fused == 2 && R != 2)) return 1;
+    if ((R != 1 && R != 2 && R != 4) || (a.fused && R == 1) || (a.fused == 2 && R != 2)) return Q3_ATT_REFUSED;
+    if (a.fused == 2) return Q3_ATT_PAIR;  // two rows per slot, empty cache (the Predictor's pass A): see k_attend_pair
+    if (a.fused && a.n_ctx <= 64 && R == 2) return Q3_ATT_SMALL2;  // short caches (the Predictor): one wave per query head
+    // the Talker's decode step: one workgroup of four waves per (slot, KV head), both query heads
+    // (1: k_attend<2, true> below — same bits: test_attention_kernel_variants_agree)
+    if (a.fused && R == 2 && g_att_decode == 0) return Q3_ATT_GQA2;
+    // whole prompt runs (admit_group): keys and values once per run — when there are enough runs to occupy the chip (one workgroup per run and
+    // KV head walks its rows 8 at a time: a single prompt of 31 rows took 45 us per layer on 8 workgroups against 9 us on k_attend's 248)
+    // With voice prefixes a run attends to pos0 + n keys: up to 256 of them still fit (4 key blocks of 16 KiB + 256 values of 256 B + 8 waves
+    // x (256 + 128) floats = 140 KiB); without prefixes seg_max_t = seg_max_n and the rule and the LDS size are what they were.
+    if (!a.fused && R == 2 && a.seg && a.seg_max_n <= 128 && a.seg_max_t <= 256 && g_att_prefill != 1 &&
+        (a.n_seg * a.Hkv >= 128 || g_att_prefill == 2)) return Q3_ATT_PREFILL;
+    if (a.fused) return R == 2 ? Q3_ATT_F2 : Q3_ATT_F4;
+    return R == 1 ? Q3_ATT_N1 : (R == 2 ? Q3_ATT_N2 : Q3_ATT_N4);
+}
+
+// 0: launched. Nonzero: refused, nothing launched — a shape q3_attend_pick refuses, or a device that refuses the LDS size.
+int q3_launch_attend(const Q3Attend& a, hipStream_t s) {
+    const int pick = q3_attend_pick(a);
+    if (pick == Q3_ATT_REFUSED) return 1;
+    const int R = a.Hq / a.Hkv;
     const dim3 grid(a.Hkv, a.rows);
-    if (a.fused == 2) {  // two rows per slot, empty cache (the Predictor's pass A): see k_attend_pair
+    if (pick == Q3_ATT_PAIR) {
         hipLaunchKernelGGL(k_attend_pair, dim3(a.Hkv, a.slot_mod), dim3(256), 0, s, a);
         return 0;
     }
-    if (a.fused && a.n_ctx <= 64 && R == 2) {  // short caches (the Predictor): one wave per query head
+    if (pick == Q3_ATT_SMALL2) {
         hipLaunchKernelGGL((k_attend_small<2>), grid, dim3(192), 0, s, a);
         return 0;
     }
-    if (a.fused && R == 2 && g_att_decode == 0) {  // the Talker's decode step: one workgroup of four waves per (slot, KV head), both query heads
-                                                    // (1: k_attend<2, true> below — same bits: test_attention_kernel_variants_agree)
+    if (pick == Q3_ATT_GQA2) {
         const size_t lds2 = ((size_t)2 * a.n_ctx + 2 * Q3_ATT_HD + 8 * Q3_ATT_HD + 16 + 128) * sizeof(float);  // as k_attend_gqa2 lays it out
         static Q3PerDevice pd2;
         if (lds2 > 65536 && !pd2.ensure(lds2, [&]() { return att_allow_lds((const void*)k_attend_gqa2, lds2); })) return 1;
         hipLaunchKernelGGL(k_attend_gqa2, grid, dim3(256), lds2, s, a);
         return 0;
     }
-    // whole prompt runs (admit_group): keys and values once per run — when there are enough runs to occupy the chip (one workgroup per run and
-    // KV head walks its rows 8 at a time: a single prompt of 31 rows took 45 us per layer on 8 workgroups against 9 us on k_attend's 248)
-    // With voice prefixes a run attends to pos0 + n keys: up to 256 of them still fit (4 key blocks of 16 KiB + 256 values of 256 B + 8 waves
-    // x (256 + 128) floats = 140 KiB); without prefixes seg_max_t = seg_max_n and the rule and the LDS size are what they were.
-    if (!a.fused && R == 2 && a.seg && a.seg_max_n <= 128 && a.seg_max_t <= 256 && g_att_prefill != 1 &&
-        (a.n_seg * a.Hkv >= 128 || g_att_prefill == 2)) {
+    if (pick == Q3_ATT_PREFILL) {
         const int nblk = (a.seg_max_t + 63) / 64;
         const int pw = a.seg_max_t > 128 ? (a.seg_max_t + 63) & ~63 : 128;  // as k_attend_prefill computes it
         const size_t lds3 = (size_t)nblk * 16384 + (size_t)a.seg_max_t * 256 + (size_t)8 * (pw + 128) * sizeof(float);
@@ -868,12 +883,11 @@ int q3_launch_attend(const Q3Attend& a, hipStream_t s) {
                 if (e == hipSuccess) e = att_allow_lds(k, lds);
             return e;
         })) return 1;
-    if (a.fused) {
-        if (R == 2) hipLaunchKernelGGL((k_attend<2, true>), grid, dim3(512), lds, s, a);
-        else hipLaunchKernelGGL((k_attend<4, true>), grid, dim3(1024), lds, s, a);  // R == 4
-    } else if (R == 1) hipLaunchKernelGGL((k_attend<1, false>), grid, dim3(256), lds, s, a);
-    else if (R == 2) hipLaunchKernelGGL((k_attend<2, false>), grid, dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((k_attend<4, false>), grid, dim3(1024), lds, s, a);  // R == 4
+    if (pick == Q3_ATT_F2) hipLaunchKernelGGL((k_attend<2, true>), grid, dim3(512), lds, s, a);
+    else if (pick == Q3_ATT_F4) hipLaunchKernelGGL((k_attend<4, true>), grid, dim3(1024), lds, s, a);
+    else if (pick == Q3_ATT_N1) hipLaunchKernelGGL((k_attend<1, false>), grid, dim3(256), lds, s, a);
+    else if (pick == Q3_ATT_N2) hipLaunchKernelGGL((k_attend<2, false>), grid, dim3(512), lds, s, a);
+    else hipLaunchKernelGGL((k_attend<4, false>), grid, dim3(1024), lds, s, a);  // Q3_ATT_N4
     return 0;
 }
 

@@ -212,6 +212,219 @@ extern "C" int q3tts_k_attention_decode(int32_t device, const float* qkv, int32_
     return out_bf16 ? untile_host(dob, n_slots, nq, out_bf16) : Q3TTS_OK;
 }
 
+// ---- the attention hooks with every output form and the cache returned (q3tts_k_attention_runs / _decode_ex / _pair) ----------------
+// What the three share: the norm weights and RoPE tables of a cache of n_slots x Hkv x n_ctx positions, the output buffers of one form
+// (0: f32 rows; 1: the A-tiled bf16 operand; 2: Q8_0 blocks + f32 block scales), the read-back in natural order and the un-blocked cache.
+struct AttHook {
+    int n_slots = 0, n_ctx = 0, Hq = 0, Hkv = 0, ld = 0, nq = 0, form = 0, out_rows = 0, rt16 = 0;
+    DevBuf qn, kn, cs, sn, kc, vc, out, osc;
+    // the arguments every attention hook checks before anything is allocated or launched
+    static const char* check(const float* qkv, int n_slots, int n_ctx, int Hq, int Hkv, int hd, const float* qnw, const float* knw, int form, const void* out,
+                             const float* out_scale) {
+        if (!qkv || !qnw || !knw || !out) return "a null argument";
+        if (hd != Q3_ATT_HD) return "head_dim must be 128";
+        if (n_slots <= 0 || n_slots > 4096) return "1 .. 4096 slots";
+        if (n_ctx <= 0 || n_ctx % 64 || n_ctx > 8192) return "n_ctx must be a multiple of 64 in 64 .. 8192";
+        if (Hkv <= 0 || Hq <= 0 || Hq % Hkv || Hq > 64) return "n_head must be a multiple of n_kv_head";
+        const int R = Hq / Hkv;
+        if (R != 1 && R != 2 && R != 4) return "the GQA ratio must be 1, 2 or 4";
+        if (form < 0 || form > 2) return "out_form 0 (f32), 1 (bf16) or 2 (Q8_0)";
+        if (form == 2 && !out_scale) return "out_form 2 needs out_scale";
+        return nullptr;
+    }
+    int init(int slots, int nctx, int hq, int hkv, const float* qnw, const float* knw, float theta, const int32_t* sections, int out_form, int rows) {
+        n_slots = slots; n_ctx = nctx; Hq = hq; Hkv = hkv; ld = (hq + 2 * hkv) * Q3_ATT_HD; nq = hq * Q3_ATT_HD; form = out_form; out_rows = rows;
+        rt16 = (int)(pad16(rows) / 16);
+        std::vector<float> c, s;
+        q3_rope_tables(n_ctx, Q3_ATT_HD, theta, sections, c, s);
+        TRY(qn.put(qnw, Q3_ATT_HD * 4)); TRY(kn.put(knw, Q3_ATT_HD * 4)); TRY(cs.put(c.data(), c.size() * 4)); TRY(sn.put(s.data(), s.size() * 4));
+        const size_t cache = (size_t)n_slots * Hkv * n_ctx * Q3_ATT_HD * 2;
+        TRY(kc.alloc(cache)); TRY(vc.alloc(cache));
+        TRY(out.alloc(form == 0 ? (size_t)rows * nq * 4 : pad16(rows) * nq * (form == 1 ? 2 : 1)));
+        if (form == 2) TRY(osc.alloc((size_t)(nq / 32 + 2) * pad16(rows) * 4));
+        return Q3TTS_OK;
+    }
+    Q3QkPrep prep(float* rows_dev, int rows, float eps) const {
+        Q3QkPrep qp{}; qp.qkv = rows_dev; qp.ld = ld; qp.rows = rows; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = Q3_ATT_HD; qp.qnw = qn; qp.knw = kn; qp.eps = eps;
+        qp.cs = cs; qp.sn = sn; qp.kc = kc; qp.vc = vc; qp.n_ctx = n_ctx;
+        return qp;
+    }
+    Q3Attend attend(const float* rows_dev, int rows) const {
+        Q3Attend at{}; at.qkv = rows_dev; at.ld = ld; at.rows = rows; at.out = out; at.ldo = nq; at.out_bf16 = form; at.Hq = Hq; at.Hkv = Hkv; at.hd = Q3_ATT_HD;
+        at.kc = kc; at.vc = vc; at.n_ctx = n_ctx;
+        if (form == 2) { at.out_scale = osc; at.out_rt16 = rt16; }
+        return at;
+    }
+    // the output rows in natural order: f32 / bf16 bits [rows][nq], or int8 [rows][nq] + f32 [rows][nq / 32]
+    int read_out(void* host, float* host_scale) const {
+        if (form == 0) return out.get(host, (size_t)out_rows * nq * 4);
+        if (form == 1) return untile_host(out, out_rows, nq, (uint16_t*)host);
+        const size_t B16 = pad16(out_rows);
+        std::vector<int8_t> qt(B16 * nq); std::vector<float> st((size_t)(nq / 32) * B16);
+        TRY(out.get(qt.data(), qt.size())); TRY(osc.get(st.data(), st.size() * 4));
+        for (int r = 0; r < out_rows; ++r) {
+            for (int k = 0; k < nq; ++k) ((int8_t*)host)[(size_t)r * nq + k] = qt[q3_q8_off(r, k, nq >> 6)];
+            for (int b = 0; b < nq / 32; ++b) host_scale[(size_t)r * (nq / 32) + b] = st[q3_q8_scale_idx(r, b, rt16)];
+        }
+        return Q3TTS_OK;
+    }
+    // the cache of every slot as bf16 bits [slot][Hkv][n_ctx][hd]: keys out of their 64-key blocks (k_cache_elem), values as stored
+    int read_cache(uint16_t* k_host, uint16_t* v_host) const {
+        constexpr int hd = Q3_ATT_HD;
+        const size_t n = (size_t)n_slots * Hkv * n_ctx * hd;
+        if (v_host) TRY(vc.get(v_host, n * 2));
+        if (!k_host) return Q3TTS_OK;
+        std::vector<uint16_t> t(n);
+        TRY(kc.get(t.data(), n * 2));
+        for (size_t h = 0; h < (size_t)n_slots * Hkv; ++h)
+            for (int pos = 0; pos < n_ctx; ++pos)
+                for (int d = 0; d < hd; ++d)
+                    k_host[(h * n_ctx + pos) * hd + d] = t[h * n_ctx * hd + ((size_t)((pos >> 6) * (hd >> 3) + (d >> 3)) * 64 + (pos & 63)) * 8 + (d & 7)];
+        return Q3TTS_OK;
+    }
+};
+// one attention launch of a hook under a temporary policy (-1: keep), then the device's verdict
+static int att_hook_launch(const char* name, const Q3Attend& at, int decode, int prefill) {
+    int old_dec = 0, old_pre = 0;
+    q3_attend_policy_get(&old_dec, &old_pre);
+    q3_attend_policy(decode >= 0 ? decode : old_dec, prefill >= 0 ? prefill : old_pre);
+    const int refused = q3_launch_attend(at, nullptr);
+    q3_attend_policy(old_dec, old_pre);
+    if (refused) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string(name) + ": the attention launch was refused");
+    hipError_t er = hipGetLastError();
+    if (er == hipSuccess) er = hipDeviceSynchronize();
+    if (er != hipSuccess) return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, std::string(name) + ": " + hipGetErrorString(er));
+    return Q3TTS_OK;
+}
+
+// Whole prompt runs as admit_group launches them: run i has run_pos0[i] prefix rows (prepared into slot i's cache by k_qk_prep: they stand for
+// a voice prefix) followed by run_n[i] rows; qkv holds run 0's run_pos0[0] + run_n[0] rows, then run 1's, ... The runs' rows go through
+// k_qk_prep and ONE non-fused q3_launch_attend that carries the seg table, seg_max_n and seg_max_t, under prefill policy `policy`.
+extern "C" int q3tts_k_attention_runs(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx, int32_t Hq,
+                                      int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections,
+                                      int32_t policy, int32_t out_form, void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache) {
+    if (const char* why = AttHook::check(qkv, n_runs, n_ctx, Hq, Hkv, hd, qnw, knw, out_form, out, out_scale))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string("attention runs hook: ") + why);
+    if (!run_n || !run_pos0 || policy < -1 || policy > 2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention runs hook: run tables, prefill policy -1 .. 2");
+    long long n_pre = 0, n_run = 0;
+    int seg_max_n = 0, seg_max_t = 0;
+    for (int i = 0; i < n_runs; ++i) {
+        if (run_n[i] < 1 || run_pos0[i] < 0 || (long long)run_pos0[i] + run_n[i] > n_ctx)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention runs hook: a run needs n >= 1, pos0 >= 0 and pos0 + n <= n_ctx");
+        n_pre += run_pos0[i]; n_run += run_n[i];
+        seg_max_n = std::max(seg_max_n, run_n[i]); seg_max_t = std::max(seg_max_t, run_pos0[i] + run_n[i]);
+    }
+    HK(hipSetDevice(device));
+    AttHook h;
+    TRY(h.init(n_runs, n_ctx, Hq, Hkv, qnw, knw, theta, sections, out_form, (int)n_run));
+    const int ld = h.ld;
+    std::vector<float> pre((size_t)std::max<long long>(n_pre, 1) * ld), run((size_t)n_run * ld);
+    std::vector<int> pp, ps, rp, rs, seg;
+    {
+        size_t src = 0, ip = 0, ir = 0;
+        for (int i = 0; i < n_runs; ++i) {
+            seg.push_back((int)ir); seg.push_back(run_n[i]); seg.push_back(i); seg.push_back(run_pos0[i]);
+            for (int r = 0; r < run_pos0[i]; ++r, ++src, ++ip) { memcpy(&pre[ip * ld], qkv + src * ld, (size_t)ld * 4); pp.push_back(r); ps.push_back(i); }
+            for (int r = 0; r < run_n[i]; ++r, ++src, ++ir) { memcpy(&run[ir * ld], qkv + src * ld, (size_t)ld * 4); rp.push_back(run_pos0[i] + r); rs.push_back(i); }
+        }
+    }
+    DevBuf dpre, drun, dpp, dps, drp, drs, dseg;
+    TRY(dpre.put(pre.data(), pre.size() * 4)); TRY(drun.put(run.data(), run.size() * 4));
+    TRY(dpp.put(pp.data(), pp.size() * 4)); TRY(dps.put(ps.data(), ps.size() * 4));
+    TRY(drp.put(rp.data(), rp.size() * 4)); TRY(drs.put(rs.data(), rs.size() * 4)); TRY(dseg.put(seg.data(), seg.size() * 4));
+    if (n_pre) {
+        Q3QkPrep qp = h.prep(dpre, (int)n_pre, eps); qp.row_pos = dpp; qp.row_slot = dps;
+        if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention runs hook: the q/k prep launch was refused");
+    }
+    Q3QkPrep qp = h.prep(drun, (int)n_run, eps); qp.row_pos = drp; qp.row_slot = drs;
+    if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention runs hook: the q/k prep launch was refused");
+    Q3Attend at = h.attend(drun, (int)n_run); at.row_pos = drp; at.row_slot = drs;
+    at.seg = dseg; at.n_seg = n_runs; at.seg_max_n = seg_max_n; at.seg_max_t = seg_max_t;
+    TRY(att_hook_launch("attention runs hook", at, -1, policy));
+    TRY(h.read_out(out, out_scale));
+    return h.read_cache(k_cache, v_cache);
+}
+
+// q3tts_k_attention_decode with one output form of the three per call, the cache returned, and (row_indexed = 1) the Predictor's addressing:
+// no row tables, slot = row % n_slots, every slot at the same length (pos_const = lens[0] - 1)
+extern "C" int q3tts_k_attention_decode_ex(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq, int32_t Hkv,
+                                           int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, int32_t policy,
+                                           int32_t row_indexed, int32_t out_form, void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache) {
+    if (const char* why = AttHook::check(qkv, n_slots, n_ctx, Hq, Hkv, hd, qnw, knw, out_form, out, out_scale))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string("attention decode_ex hook: ") + why);
+    if (!lens || Hq / Hkv < 2 || policy < -1 || policy > 1 || row_indexed < 0 || row_indexed > 1)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode_ex hook: lens, a GQA ratio of 2 or 4, decode policy -1 .. 1, row_indexed 0 / 1");
+    long long total = 0;
+    for (int s = 0; s < n_slots; ++s) {
+        if (lens[s] < 1 || lens[s] > n_ctx) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode_ex hook: a length outside 1 .. n_ctx");
+        if (row_indexed && lens[s] != lens[0]) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode_ex hook: row-indexed addressing needs equal lengths");
+        total += lens[s];
+    }
+    HK(hipSetDevice(device));
+    AttHook h;
+    TRY(h.init(n_slots, n_ctx, Hq, Hkv, qnw, knw, theta, sections, out_form, n_slots));
+    const int ld = h.ld, npre = (int)(total - n_slots);
+    std::vector<float> pre((size_t)std::max(npre, 1) * ld), last((size_t)n_slots * ld);
+    std::vector<int> pp, ps, dp(n_slots), ds(n_slots);
+    {
+        size_t src = 0, ip = 0;
+        for (int s = 0; s < n_slots; ++s) {
+            for (int r = 0; r < lens[s] - 1; ++r, ++src, ++ip) { memcpy(&pre[ip * ld], qkv + src * ld, (size_t)ld * 4); pp.push_back(r); ps.push_back(s); }
+            memcpy(&last[(size_t)s * ld], qkv + src * ld, (size_t)ld * 4); ++src;
+            dp[s] = lens[s] - 1; ds[s] = s;
+        }
+    }
+    DevBuf dpre, dlast, dpp, dps, ddp, dds;
+    TRY(dpre.put(pre.data(), pre.size() * 4)); TRY(dlast.put(last.data(), last.size() * 4));
+    TRY(dpp.put(pp.data(), pp.size() * 4)); TRY(dps.put(ps.data(), ps.size() * 4)); TRY(ddp.put(dp.data(), n_slots * 4)); TRY(dds.put(ds.data(), n_slots * 4));
+    if (npre) {
+        Q3QkPrep qp = h.prep(dpre, npre, eps); qp.row_pos = dpp; qp.row_slot = dps;
+        if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode_ex hook: the q/k prep launch was refused");
+    }
+    Q3QkPrep dq = h.prep(dlast, n_slots, eps);
+    Q3Attend at = h.attend(dlast, n_slots);
+    if (row_indexed) { dq.slot_mod = at.slot_mod = n_slots; dq.pos_const = at.pos_const = lens[0] - 1; }
+    else { dq.row_pos = at.row_pos = ddp; dq.row_slot = at.row_slot = dds; }
+    at.fused = 1; at.prep = dq;
+    TRY(att_hook_launch("attention decode_ex hook", at, policy, -1));
+    TRY(h.read_out(out, out_scale));
+    return h.read_cache(k_cache, v_cache);
+}
+
+// The Predictor's pass A: 2 * n_slots rows — row b at position 0, row n_slots + b at position 1 of slot b — in ONE launch with fused = 2 on an
+// empty cache (k_attend_pair); out rows in the same order
+extern "C" int q3tts_k_attention_pair(int32_t device, const float* qkv, int32_t n_slots, int32_t n_ctx, int32_t Hq, int32_t Hkv, int32_t hd, const float* qnw,
+                                      const float* knw, float eps, float theta, const int32_t* sections, int32_t out_form, void* out, float* out_scale,
+                                      uint16_t* k_cache, uint16_t* v_cache) {
+    if (const char* why = AttHook::check(qkv, n_slots, n_ctx, Hq, Hkv, hd, qnw, knw, out_form, out, out_scale))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string("attention pair hook: ") + why);
+    if (Hq / Hkv != 2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention pair hook: the GQA ratio must be 2");
+    HK(hipSetDevice(device));
+    AttHook h;
+    TRY(h.init(n_slots, n_ctx, Hq, Hkv, qnw, knw, theta, sections, out_form, 2 * n_slots));
+    DevBuf drows;
+    TRY(drows.put(qkv, (size_t)2 * n_slots * h.ld * 4));
+    Q3QkPrep qp = h.prep(drows, 2 * n_slots, eps); qp.slot_mod = n_slots; qp.pos_const = 0;
+    Q3Attend at = h.attend(drows, 2 * n_slots); at.slot_mod = n_slots; at.pos_const = 0;
+    at.fused = 2; at.prep = qp;
+    TRY(att_hook_launch("attention pair hook", at, -1, -1));
+    TRY(h.read_out(out, out_scale));
+    return h.read_cache(k_cache, v_cache);
+}
+
+// The kernel q3_launch_attend takes for a shape under the current policies, without launching: *kernel = 0 / 1 / 2 k_attend<1 / 2 / 4, false>,
+// 3 / 4 k_attend<2 / 4, true>, 5 k_attend_gqa2, 6 k_attend_small<2>, 7 k_attend_pair, 8 k_attend_prefill, -1 a launch the launcher refuses
+extern "C" int q3tts_k_attend_pick(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t, int32_t n_kv_head,
+                                   int32_t* kernel) {
+    if (!kernel || fused < 0 || fused > 2 || gqa_ratio <= 0 || gqa_ratio > 64 || n_ctx <= 0 || n_seg < 0 || seg_max_n < 0 || seg_max_t < 0 || n_kv_head <= 0 ||
+        n_kv_head > 4096)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attend pick: bad shape");
+    Q3Attend a{}; a.hd = Q3_ATT_HD; a.Hkv = n_kv_head; a.Hq = n_kv_head * gqa_ratio; a.fused = fused; a.n_ctx = n_ctx;
+    if (n_seg > 0) { a.seg = (const int*)16; a.n_seg = n_seg; a.seg_max_n = seg_max_n; a.seg_max_t = seg_max_t; }  // (never dereferenced: nothing is launched)
+    *kernel = q3_attend_pick(a);
+    return Q3TTS_OK;
+}
+
 extern "C" int q3tts_k_sample(int32_t device, const float* logits, int32_t n, int32_t ld, int32_t limit, float temperature, int32_t top_k,
                               float top_p, const float* r, int32_t* out) {
     if (!logits || !out || n <= 0 || limit <= 0 || limit > 4096 || limit > ld) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "sample hook: bad shape");

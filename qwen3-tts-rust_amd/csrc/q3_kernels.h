@@ -265,6 +265,12 @@ struct Q3Attend {
     Q3_STAMP_FIELD
 };
 int q3_launch_attend(const Q3Attend& a, hipStream_t s);  // 0: launched; nonzero: refused (see its definition), nothing launched
+// the nine attention kernels of q3_attend.hip as q3_attend_pick names them (q3tts_k_attend_pick reports these numbers)
+enum { Q3_ATT_REFUSED = -1, Q3_ATT_N1 = 0, Q3_ATT_N2 = 1, Q3_ATT_N4 = 2,   // k_attend<1 / 2 / 4, false>
+       Q3_ATT_F2 = 3, Q3_ATT_F4 = 4,                                       // k_attend<2 / 4, true>
+       Q3_ATT_GQA2 = 5, Q3_ATT_SMALL2 = 6, Q3_ATT_PAIR = 7, Q3_ATT_PREFILL = 8 };
+int q3_attend_pick(const Q3Attend& a);  // the kernel q3_launch_attend takes for a under the current policies (no launch); reads hd, Hq, Hkv,
+                                        // fused, n_ctx and the seg fields only
 // Voice prefixes (q3tts_prefix): copy a prefix store into slots before their prefill. A store is laid out as one slot's cache of
 // np = ceil(P / 64) * 64 positions: k / v [L][Hkv][np * hd] bf16 (keys in 64-position blocks, values row-major). Entry j copies every
 // layer's whole key blocks and the values of positions < P[j] into slot[j]; keys at positions P .. np - 1 of the slot are overwritten.

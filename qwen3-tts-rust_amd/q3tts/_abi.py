@@ -159,6 +159,7 @@ SYMBOLS = [
     "q3tts_k_pred_variant",
     "q3tts_set_output_rate", "q3tts_get_output_rate", "q3tts_resample", "q3tts_k_resample_table", "q3tts_k_pcm_resample",
     "q3tts_session_append_text", "q3tts_k_text_ready",
+    "q3tts_k_attention_runs", "q3tts_k_attention_decode_ex", "q3tts_k_attention_pair", "q3tts_k_attend_pick",
 ]
 
 
@@ -230,6 +231,13 @@ def load_library(path=None):
                                       C.c_float, C.c_float, i32p, f32p]
     lib.q3tts_k_attention_decode.argtypes = [C.c_int32, f32p, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p,
                                              C.c_float, C.c_float, i32p, C.c_int32, f32p, C.POINTER(C.c_uint16)]
+    lib.q3tts_k_attention_runs.argtypes = [C.c_int32, f32p, C.c_int32, i32p, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float,
+                                           C.c_float, i32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.q3tts_k_attention_decode_ex.argtypes = [C.c_int32, f32p, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float,
+                                                C.c_float, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.q3tts_k_attention_pair.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float, C.c_float,
+                                           i32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.q3tts_k_attend_pick.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
     lib.q3tts_k_sample.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float,
                                    f32p, i32p]
     lib.q3tts_k_talker_prefill.argtypes = [vp, f32p, C.c_int32, f32p, f32p]

@@ -754,6 +754,97 @@ def k_attention_decode(qkv, lens, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, 
     return out, ob
 
 
+ATTEND_KERNELS = ("k_attend<1, false>", "k_attend<2, false>", "k_attend<4, false>", "k_attend<2, true>", "k_attend<4, true>", "k_attend_gqa2",
+                  "k_attend_small<2>", "k_attend_pair", "k_attend_prefill")
+
+
+def k_attend_pick(fused, gqa_ratio, n_ctx, n_kv_head, n_seg=0, seg_max_n=0, seg_max_t=0):
+    """q3tts_k_attend_pick (host only): the name of the kernel the attention launcher takes for a shape under the current policies, or
+    None when it refuses the launch."""
+    lib = _abi.load_library()
+    k = C.c_int32(-2)
+    rc = lib.q3tts_k_attend_pick(fused, gqa_ratio, n_ctx, n_seg, seg_max_n, seg_max_t, n_kv_head, C.byref(k))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_attend_pick failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return None if k.value < 0 else ATTEND_KERNELS[k.value]
+
+
+def _att_hook_out(rows, nq, out_form, n_slots, n_kv_head, n_ctx, head_dim, want_cache):
+    out = np.zeros((rows, nq), dtype=(np.float32, np.uint16, np.int8)[out_form] if 0 <= out_form <= 2 else np.float32)
+    sc = np.zeros((rows, nq // 32), dtype=np.float32) if out_form == 2 else None
+    kc = np.zeros((n_slots, n_kv_head, n_ctx, head_dim), dtype=np.uint16) if want_cache else None
+    vc = np.zeros((n_slots, n_kv_head, n_ctx, head_dim), dtype=np.uint16) if want_cache else None
+    return out, sc, kc, vc
+
+
+def _att_hook_ret(out, sc, kc, vc):
+    return dict(out=out, scale=sc, k_cache=kc, v_cache=vc)
+
+
+def _dp(a):
+    return None if a is None else a.ctypes.data
+
+
+def k_attention_runs(qkv, runs, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, policy=-1, out_form=0,
+                     want_cache=True, device=0):
+    """q3tts_k_attention_runs: runs = [(pos0, n), ...], one slot each; qkv holds every run's pos0 + n rows back to back. Returns a dict:
+    out [sum n][n_head * head_dim] in the form asked for (f32 / bf16 bits / int8 with `scale`), k_cache / v_cache bf16 bits
+    [run][n_kv_head][n_ctx][head_dim]."""
+    lib = _abi.load_library()
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+    p0 = np.ascontiguousarray([r[0] for r in runs], dtype=np.int32)
+    nn = np.ascontiguousarray([r[1] for r in runs], dtype=np.int32)
+    assert qkv.shape[0] == int(p0.sum() + nn.sum())
+    qn = np.ascontiguousarray(q_norm_w, dtype=np.float32)
+    kn = np.ascontiguousarray(k_norm_w, dtype=np.float32)
+    sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
+    out, sc, kc, vc = _att_hook_out(max(int(nn.sum()), 1), n_head * head_dim, out_form, len(runs), n_kv_head, n_ctx, head_dim, want_cache)
+    rc = lib.q3tts_k_attention_runs(device, _ptr(qkv, f32p), len(runs), _ptr(nn, i32p), _ptr(p0, i32p), n_ctx, n_head, n_kv_head, head_dim,
+                                    _ptr(qn, f32p), _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, out_form,
+                                    _dp(out), _dp(sc), _dp(kc), _dp(vc))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_attention_runs failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return _att_hook_ret(out, sc, kc, vc)
+
+
+def k_attention_decode_ex(qkv, lens, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, policy=-1,
+                          row_indexed=False, out_form=0, want_cache=True, device=0):
+    """q3tts_k_attention_decode_ex: k_attention_decode with one output form per call, the cache, and the Predictor's row-indexed addressing.
+    Returns the dict of k_attention_runs with out [n_slots][n_head * head_dim]."""
+    lib = _abi.load_library()
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    assert qkv.shape[0] == int(ln.sum())
+    qn = np.ascontiguousarray(q_norm_w, dtype=np.float32)
+    kn = np.ascontiguousarray(k_norm_w, dtype=np.float32)
+    sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
+    out, sc, kc, vc = _att_hook_out(max(ln.size, 1), n_head * head_dim, out_form, ln.size, n_kv_head, n_ctx, head_dim, want_cache)
+    rc = lib.q3tts_k_attention_decode_ex(device, _ptr(qkv, f32p), ln.size, _ptr(ln, i32p), n_ctx, n_head, n_kv_head, head_dim, _ptr(qn, f32p),
+                                         _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy,
+                                         1 if row_indexed else 0, out_form, _dp(out), _dp(sc), _dp(kc), _dp(vc))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_attention_decode_ex failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return _att_hook_ret(out, sc, kc, vc)
+
+
+def k_attention_pair(qkv, n_slots, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, out_form=0,
+                     want_cache=True, device=0):
+    """q3tts_k_attention_pair: qkv [2 * n_slots] rows in the Predictor's order (row b at position 0, row n_slots + b at position 1). Returns
+    the dict of k_attention_runs with out [2 * n_slots][n_head * head_dim]."""
+    lib = _abi.load_library()
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+    assert qkv.shape[0] == 2 * n_slots
+    qn = np.ascontiguousarray(q_norm_w, dtype=np.float32)
+    kn = np.ascontiguousarray(k_norm_w, dtype=np.float32)
+    sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
+    out, sc, kc, vc = _att_hook_out(max(2 * n_slots, 1), n_head * head_dim, out_form, n_slots, n_kv_head, n_ctx, head_dim, want_cache)
+    rc = lib.q3tts_k_attention_pair(device, _ptr(qkv, f32p), n_slots, n_ctx, n_head, n_kv_head, head_dim, _ptr(qn, f32p), _ptr(kn, f32p), eps,
+                                    rope_theta, None if sec is None else _ptr(sec, i32p), out_form, _dp(out), _dp(sc), _dp(kc), _dp(vc))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_attention_pair failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return _att_hook_ret(out, sc, kc, vc)
+
+
 def k_sample(logits, limit, temperature, top_k, top_p, r=None, device=0):
     lib = _abi.load_library()
     lg = np.ascontiguousarray(logits, dtype=np.float32)
