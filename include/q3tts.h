@@ -573,6 +573,39 @@ int q3tts_k_attention_pair(int32_t device, const float* qkv, int32_t n_slots, in
  * k_attend<2 / 4, true>; 5: k_attend_gqa2; 6: k_attend_small<2>; 7: k_attend_pair; 8: k_attend_prefill; -1: the launcher refuses. */
 int q3tts_k_attend_pick(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t,
                         int32_t n_kv_head, int32_t* kernel);
+/* ---- the Predictor's layer-0 QKV table ----
+ * With a bf16 Predictor and greedy heads, block 0 of passes q = 1 .. n_codebooks - 2 reads its raw q / k / v from a table built at engine
+ * creation (one row per (q, code), + one fallback row per q for a code outside [0, codecq_rows)) instead of launching k_pred_next(q) and
+ * the QKV GEMM. Environment, read at engine creation: Q3TTS_PRED_TABLE=0 builds no table; Q3TTS_PRED_TABLE_MAX_MB (default 1024): a
+ * larger table is not built. Without a table the frame step is the one with those launches; the ids are the same either way.
+ * Row `code` of slice q: n_head * head_dim + 2 * n_kv_head * head_dim f32 of the Predictor. Q3TTS_ERR_STATE: the engine has no table. */
+int q3tts_k_pred_table_row(q3tts_engine* e, int32_t q, int32_t code, float* out);
+/* What one k_pred_next(q) launch of the greedy frame step, 1 <= q <= n_codebooks - 2, works on; row b stands for slot b. codes, fb and px
+ * are read and written back: codes[b][n_frames[b]][q] = code, fb[b] += codec_q[code] (+ 0 when the code is outside [0, rows_q)),
+ * px[b] = pproj_q[code] (proj_b then). A row with active[b] = 0 is left alone. code = the column of the largest key of keys[b][...]. */
+typedef struct q3tts_k_pred_step {
+    int32_t n_rows, q, n_codebooks, n_key_parts, rows_q, d_embed, d_proj, max_steps_cap;
+    const uint64_t* keys;      /* [n_rows][n_key_parts] */
+    const int32_t* active;     /* [n_rows] */
+    const int32_t* n_frames;   /* [n_rows], each in [0, max_steps_cap) */
+    const float* codec_q;      /* [rows_q][d_embed] */
+    const float* pproj_q;      /* [rows_q][d_proj] */
+    const float* proj_b;       /* [d_proj] */
+    float* fb;                 /* [n_rows][d_embed] */
+    float* px;                 /* [n_rows][d_proj] */
+    int32_t* codes;            /* [n_rows][max_steps_cap][n_codebooks] */
+} q3tts_k_pred_step;
+/* k_pred_next<false>(q) on st; also the norm inputs it writes for norm_w [d_proj]: xb bf16 bits [n_rows][d_proj] (natural order; rows of
+ * inactive slots stay zero), ssp [n_rows][d_proj / 16]. */
+int q3tts_k_pred_next(int32_t device, q3tts_k_pred_step* st, const float* norm_w, uint16_t* xb, float* ssp);
+/* One launch of the gathering form of k_attend_small<2> as block 0 of pass st->q issues it: row b (slot b at position len - 1 of the
+ * Predictor's row-indexed cache, n_ctx = 64) takes its q / k / v from table[code] (table [rows_q + 1][ld], ld = (n_head + 2 n_kv_head) *
+ * head_dim; row rows_q = the fallback row) and one more workgroup column does st's bookkeeping. qkv: n_rows runs of len rows as
+ * q3tts_k_attention_decode_ex takes them: the first len - 1 of a run fill the slot's cache, the last one is not read. Outputs as there. */
+int q3tts_k_attention_gather(int32_t device, q3tts_k_pred_step* st, const float* table, const float* qkv, int32_t len, int32_t n_ctx,
+                             int32_t n_head, int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
+                             float rope_theta, const int32_t* mrope_sections, int32_t out_form, void* out, float* out_scale,
+                             uint16_t* k_cache, uint16_t* v_cache);
 /* sampler (H4: src/models/llama/mod.rs:666-772) on n rows of logits; r_uniform[n] are the f32 draws */
 int q3tts_k_sample(int32_t device, const float* logits, int32_t n, int32_t ld, int32_t limit, float temperature,
                    int32_t top_k, float top_p, const float* r_uniform, int32_t* out_ids);

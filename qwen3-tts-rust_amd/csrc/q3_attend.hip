@@ -489,12 +489,64 @@ __global__ __launch_bounds__(256, 2) void k_attend_gqa2(Q3Attend a) {  // (<= 25
 //    from v_readlane (a scalar); r_w = (o_4w + o_4w+1) + (o_4w+2 + o_4w+3), o = ((r0 + r1) + r2) + r3 are plain adds in the lane
 //  * l = the 64-lane butterfly of wave 0 of k_attend (+0 +0 +0 for the three absent waves is exact)
 // ---------------------------------------------------------------------------------------------------------------------
-template <int R>
-__global__ __launch_bounds__((R + 1) * 64) void k_attend_small(Q3Attend a) {
+//
+// The GATHERING form (TX = Q3AttGather: q3_launch_attend_gather) serves block 0 of the greedy Predictor's passes q >= 1,
+// whose input row is a table row chosen by the code of pass q - 1: every wave requests the row's per-tile argmax keys FIRST, then the
+// operands that do not depend on the code (cached keys / values, norm weights, RoPE entries) — still one round trip — reduces the keys to
+// the code k_pred_next<false> takes (the largest key; q3_argmax_idx) and only then requests its segment of tab[code]: the one added
+// dependent round trip. From rowp on the two forms are the same statements: same chains, same append, same bits as the plain form fed
+// that row. Workgroup column blockIdx.x == Hkv is att_gather_book: k_pred_next's bookkeeping, off the query waves' chain.
+__device__ __forceinline__ const Q3AttGather& att_gather(const Q3AttGather& t) { return t; }
+// the wave's share of the row's keys (parts lane, lane + 64: every part of a codebook of <= 2048 codes), requested; the rest by loop.
+// Unconditional loads (a lane past the end re-reads the last part, which changes no maximum): straight-line code, nothing waits here.
+__device__ __forceinline__ void att_keys_load(const Q3AttGather& t, int row, int lane, unsigned long long kk[2]) {
+    const unsigned long long* kr = t.keys + (size_t)row * t.n_key_parts;
+    kk[0] = kr[min(lane, t.n_key_parts - 1)];
+    kk[1] = kr[min(lane + 64, t.n_key_parts - 1)];
+}
+// ... reduced to the row's code as k_pred_next<false> does (a maximum: any order gives the same key), and the table row it selects. Any
+// 64-bit pattern in the keys (an idle row's leftovers) gives a row inside the table.
+__device__ __forceinline__ int att_keys_code(const Q3AttGather& t, int row, int lane, const unsigned long long kk[2]) {
+    unsigned long long k = kk[1] > kk[0] ? kk[1] : kk[0];
+    for (int p = lane + 128; p < t.n_key_parts; p += 64) { const unsigned long long o = t.keys[(size_t)row * t.n_key_parts + p]; k = o > k ? o : k; }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { const unsigned long long o = __shfl_xor(k, m); k = o > k ? o : k; }
+    return __builtin_amdgcn_readfirstlane(q3_argmax_idx(k));
+}
+__device__ __forceinline__ bool att_code_ok(const Q3AttGather& t, int code) { return code >= 0 && code < t.tab_rows; }
+// What k_pred_next<false>(q) does besides the row's norm inputs, for row b, by one workgroup of NT threads: the same values, element by element
+// (fb + codec_q[code], or + 0 for a code out of range, in f32; the px row copied). Skips a row whose slot is not active, as k_pred_next does.
+template <int NT>
+__device__ __forceinline__ void att_gather_book(const Q3AttGather& t, int b, int tid) {
+    unsigned long long kk[2];
+    att_keys_load(t, b, tid & 63, kk);
+    const int slot = t.row_slot[b];
+    const Q3Slot* sl = t.slots + slot;
+    const int active = sl->active, frame = sl->n_frames;
+    const int code = att_keys_code(t, b, tid & 63, kk);  // (every wave reduces the whole row: no LDS, no barrier)
+    if (!active) return;
+    const bool ok = att_code_ok(t, code);
+    if (tid == 0) t.codes[((size_t)slot * t.max_steps_cap + frame) * t.ncb + t.q] = code;
+    const float4* e = (const float4*)(t.codec_q + (size_t)(ok ? code : 0) * t.d);
+    const float4* pr = (const float4*)(ok ? t.pproj_q + (size_t)code * t.dp : t.proj_b);
+    float4* fb = (float4*)(t.fb + (size_t)b * t.d);
+    float4* px = (float4*)(t.px + (size_t)b * t.dp);
+    for (int i = tid; i < (t.d >> 2); i += NT) {
+        const float4 f = fb[i], ev = ok ? e[i] : (float4){0.f, 0.f, 0.f, 0.f};
+        fb[i] = (float4){f.x + ev.x, f.y + ev.y, f.z + ev.z, f.w + ev.w};
+    }
+    for (int i = tid; i < (t.dp >> 2); i += NT) px[i] = pr[i];
+}
+template <int R, class... TX>
+__global__ __launch_bounds__((R + 1) * 64) void k_attend_small(Q3Attend a, TX... tx) {
+    constexpr bool GATHER = sizeof...(TX) != 0;
     __shared__ __attribute__((aligned(16))) float qh[R][Q3_ATT_HD]; // q after norm + RoPE (f32)
     __shared__ __attribute__((aligned(16))) uint32_t knew[64];     // newest key, bf16 pairs in the cache's chunk order: chunk c = 16 bytes at knew + 4 c
     __shared__ __attribute__((aligned(16))) uint32_t vnew[64];     // newest value, bf16 pairs: dims 2 i, 2 i + 1 in word i
     const int g = blockIdx.x, row = blockIdx.y, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if constexpr (GATHER) {
+        if (g == a.Hkv) { att_gather_book<(R + 1) * 64>(att_gather(tx...), row, threadIdx.x); return; }
+    }
     Q3_STAMP(a, 0);
     int pos, slot;
     q3_row_map(row, a.row_pos, a.row_slot, a.slot_mod, a.pos_const, &pos, &slot);
@@ -508,12 +560,23 @@ __global__ __launch_bounds__((R + 1) * 64) void k_attend_small(Q3Attend a) {
     const float* rowp = a.qkv + (size_t)row * a.ld;
     const float* csp = pr.cs + (size_t)pos * half + 4 * (lane & 15);
     const float* snp = pr.sn + (size_t)pos * half + 4 * (lane & 15);
+    unsigned long long kk[2] = {0ull, 0ull};
+    if constexpr (GATHER) att_keys_load(att_gather(tx...), row, lane, kk);
     if (wv == R) {
         // ---- k (lanes 0..31) and v (lanes 32..63) of this row: norm + RoPE, bf16, append, and the LDS copies the query waves read
         const bool isk = lane < nl;
-        const float4 x4 = isk ? ((const float4*)(rowp + (size_t)(a.Hq + g) * hd))[lane] : ((const float4*)(rowp + (size_t)(a.Hq + a.Hkv + g) * hd))[lane - nl];
         float4 w4 = (float4){0.f, 0.f, 0.f, 0.f}, c4 = (float4){1.f, 1.f, 1.f, 1.f}, s4 = (float4){0.f, 0.f, 0.f, 0.f};
-        if (isk) { w4 = ((const float4*)pr.knw)[lane]; c4 = *(const float4*)csp; s4 = *(const float4*)snp; }
+        if constexpr (GATHER) {  // (the code-independent operands go out before the keys are waited for)
+            if (isk) { w4 = ((const float4*)pr.knw)[lane]; c4 = *(const float4*)csp; s4 = *(const float4*)snp; }
+            const Q3AttGather& t = att_gather(tx...);
+            __builtin_amdgcn_sched_barrier(0);  // (keep the reduction, and its wait, behind every request above)
+            const int code = att_keys_code(t, row, lane, kk);
+            rowp = t.tab + (size_t)(att_code_ok(t, code) ? code : t.tab_rows) * a.ld;
+        }
+        const float4 x4 = isk ? ((const float4*)(rowp + (size_t)(a.Hq + g) * hd))[lane] : ((const float4*)(rowp + (size_t)(a.Hq + a.Hkv + g) * hd))[lane - nl];
+        if constexpr (!GATHER) {
+            if (isk) { w4 = ((const float4*)pr.knw)[lane]; c4 = *(const float4*)csp; s4 = *(const float4*)snp; }
+        }
         // (lanes >= 32, which hold v, contribute +0 to the sum of squares, as in prep_head)
         const float4 v = isk ? x4 : (float4){0.f, 0.f, 0.f, 0.f};
         float o[4];
@@ -541,7 +604,16 @@ __global__ __launch_bounds__((R + 1) * 64) void k_attend_small(Q3Attend a) {
 #pragma unroll
     for (int u = 0; u < 16; ++u) vv[u] = u < pos ? *(const uint32_t*)(vb + (size_t)u * hd + 2 * lane) : 0u;
     float4 x4 = (float4){0.f, 0.f, 0.f, 0.f}, w4 = x4, c4 = (float4){1.f, 1.f, 1.f, 1.f}, s4 = x4;
+    if constexpr (GATHER) {  // the row segment alone waits for the code
+        if (lane < nl) { w4 = ((const float4*)pr.qnw)[lane]; c4 = *(const float4*)csp; s4 = *(const float4*)snp; }
+        const Q3AttGather& t = att_gather(tx...);
+        __builtin_amdgcn_sched_barrier(0);
+        const int code = att_keys_code(t, row, lane, kk);
+        rowp = t.tab + (size_t)(att_code_ok(t, code) ? code : t.tab_rows) * a.ld;
+        if (lane < nl) x4 = ((const float4*)(rowp + (size_t)hq * hd))[lane];
+    } else {
     if (lane < nl) { x4 = ((const float4*)(rowp + (size_t)hq * hd))[lane]; w4 = ((const float4*)pr.qnw)[lane]; c4 = *(const float4*)csp; s4 = *(const float4*)snp; }
+    }
     {
         float y[4];
         prep_norm(x4, prep_rinv(x4, pr.eps, hd), w4, y);
@@ -888,6 +960,18 @@ int q3_launch_attend(const Q3Attend& a, hipStream_t s) {
     else if (pick == Q3_ATT_N1) hipLaunchKernelGGL((k_attend<1, false>), grid, dim3(256), lds, s, a);
     else if (pick == Q3_ATT_N2) hipLaunchKernelGGL((k_attend<2, false>), grid, dim3(512), lds, s, a);
     else hipLaunchKernelGGL((k_attend<4, false>), grid, dim3(1024), lds, s, a);  // Q3_ATT_N4
+    return 0;
+}
+
+// The gathering form exists for k_attend_small<2> only: any other launch is refused, as is one whose table or bookkeeping is incomplete.
+int q3_launch_attend_gather(const Q3Attend& a, const Q3AttGather& t, hipStream_t s) {
+    if (q3_attend_pick(a) != Q3_ATT_SMALL2 || a.rows < 1) return 1;
+    if (!t.tab || t.tab_rows < 1 || !t.keys || t.n_key_parts < 1 || t.q < 1 || t.q >= t.ncb || !t.codec_q || !t.slots || !t.row_slot || !t.codes ||
+        t.max_steps_cap < 1 || !t.fb || !t.pproj_q || !t.proj_b || !t.px || t.d < 4 || (t.d & 3) || t.dp < 4 || (t.dp & 3)) return 1;
+#ifdef Q3_STAMPS
+    if (a.dbg) return 1;  // (the stamp buffer is laid out for Hkv workgroup columns)
+#endif
+    hipLaunchKernelGGL((k_attend_small<2, Q3AttGather>), dim3(a.Hkv + 1, a.rows), dim3(192), 0, s, a, t);
     return 0;
 }
 

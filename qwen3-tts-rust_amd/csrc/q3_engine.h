@@ -84,6 +84,10 @@ struct q3tts_engine {
     std::vector<float*> pproj;            // proj(codec table q) [rows_q][p_d_model] f32: the Predictor's inputs are gathers
     float* proj_w = nullptr;              // f32 [p_d_model][d_embed], as the reference keeps it (src/assets_manager.rs:212-241)
     float* proj_b = nullptr;
+    // The Predictor's layer-0 QKV of every input row a code can select (q3_pred_table_init): qkv0 [n_codebooks - 2][codecq_rows + 1]
+    // [P.nqkv] f32 — slice q - 1, row c = block 0's raw q / k / v for the row pproj[q][c], its last row the same for proj_b (a code out of range).
+    // Null: no table (Q3TTS_PRED_TABLE=0, a table above Q3TTS_PRED_TABLE_MAX_MB, a W8A8 Predictor): the frame step keeps k_pred_next(q) and block 0's QKV GEMM.
+    float* qkv0 = nullptr;
     float* tts_pad = nullptr;             // = text[tts_pad_id] (or a row of zeros of its own, when the loaded text table is too small)
     float* marker_row = nullptr;          // text[tts_pad_id] through the out-of-range rule (the clone prompt's per-frame marker)
     // decode state: B = max_batch slots. A frame step runs on `rows` = the smallest bucket (1, 2, 4, ... B) that holds
@@ -195,6 +199,13 @@ struct Q3TfmShape {
 int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode);
 // text / codec tables, codec_dev, proj_w / proj_b, tts_pad and the pre-projected codec tables, from the files of wdir (empty: synthetic)
 int q3_assets_init(q3tts_engine* e, const std::string& wdir);
+// e->qkv0 (after both of the above), or nothing where the switches or the model say so; a refused launch is an error
+int q3_pred_table_init(q3tts_engine* e);
+// slice q (1 .. n_codebooks - 2) of e->qkv0 and its rows without the fallback row
+inline int q3_pred_table_rows(const q3tts_engine* e) { return e->cfg.model.codecq_rows; }
+inline const float* q3_pred_table_slice(const q3tts_engine* e, int q) { return e->qkv0 + (size_t)(q - 1) * (q3_pred_table_rows(e) + 1) * e->P.nqkv; }
+// whether the frame step e->pred_variant names gathers from the table: the greedy heads only (the sampling form keeps every launch)
+inline bool q3_pred_table_on(const q3tts_engine* e) { return e->qkv0 && !e->P.a8 && e->pred_variant == 0; }
 
 // the two transformers' launches (q3_layers.hip)
 // What one call runs them on; a zero member means "not used":
@@ -205,6 +216,7 @@ struct Q3LayerRun {
     hipEvent_t* probe;                              // q3tts_k_probe: two events that bracket launch e->probe_kind of block 0
     int slot_mod, pos_const;
     const int* seg; int n_seg, seg_max_n, seg_max_t;  // prefill of whole prompts: the rows as per-slot runs (pf_seg), the longest run, the furthest position + 1
+    const Q3AttGather* gather;                      // block 0 takes its q / k / v rows from the table: no QKV launch, the gathering attention (q3_launch_attend_gather)
 };
 // `a.rows` rows of r through every block of t; returns the number of launches the GEMM launcher refused
 int q3_run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& a, Q3Scratch& sc, hipStream_t s);
@@ -212,6 +224,8 @@ int q3_run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& 
 int q3_record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B);
 // one captured frame step per row bucket, of the variant e->pred_variant names
 int q3_capture_frames(q3tts_engine* e, std::vector<hipGraph_t>& graphs, std::vector<hipGraphExec_t>& execs);
+// block l's QKV GEMM of t on the first `rows` rows of r into sc.qkv
+Q3BGemm q3_gemm_qkv(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, float eps, int once);
 // the descriptor of head q ([q N, (q + 1) N) of t's output.weight) on rows [row0, row0 + rows) of r, and the one launch helper of t's GEMMs
 Q3BGemm q3_gemm_head(const Q3Tfm& t, int q, int N, const Q3Rows& r, int row0, int rows, float eps, int once, float* y);
 int q3_launch_gemm(q3tts_engine* e, const Q3Tfm& t, const Q3BGemm& g, hipStream_t s, hipEvent_t* probe = nullptr, int kind = -1);

@@ -172,6 +172,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
                                .head_n = (m.n_codebooks - 1) * m.codebook_size, .theta = m.p_rope_theta, .sections = nullptr, .n_ctx = 64, .n_slots = B},
                      wdir.empty() ? nullptr : &gp, "qwen3_tts_predictor.gguf", cfg->predictor_q8_0));
     TRYC(q3_assets_init(e, wdir));
+    TRYC(q3_pred_table_init(e));
     // decode state
     TRYC(q3_dalloc(e, &e->slots, (size_t)B));
     HIPC(hipHostMalloc((void**)&e->slots_host, sizeof(Q3Slot) * 2 * B, hipHostMallocDefault));
@@ -1049,9 +1050,14 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
         const long long wp_layers = (long long)e->P.weight_bytes - (long long)(bpw_p * (double)((size_t)e->P.head_n * m.p_d_model));
         const long long head1 = (long long)(bpw_p * (double)((size_t)m.codebook_size * m.p_d_model)), pj = 2ll * m.p_d_model * m.d_embed;
         const long long kv_per_tok = 2ll * m.t_n_layer * 2 * m.t_n_kv_head * m.t_head_dim;
-        const long long fixed = wt + (m.n_codebooks - 1) * (wp_layers + head1) + pj;  // one projection GEMM per frame (hidden rows); codes come pre-projected
-        e->tm.algo_bytes_per_step = fixed + (steps ? kv_per_tok * (ctx_tokens / steps) : 0);
+        long long fixed = wt + (m.n_codebooks - 1) * (wp_layers + head1) + pj;  // one projection GEMM per frame (hidden rows); codes come pre-projected
         e->tm.mean_live_slots = steps ? (float)((double)live_slot_steps / (double)steps) : 0.0f;
+        long long gathered = 0;  // with the layer-0 QKV table, passes 1 .. n_codebooks - 2 do not stream wqkv[0]: every live row reads its table row instead
+        if (q3_pred_table_on(e)) {
+            fixed -= (long long)(m.n_codebooks - 2) * (long long)(bpw_p * (double)((size_t)e->P.nqkv * m.p_d_model));
+            gathered = (long long)((double)(m.n_codebooks - 2) * (double)e->tm.mean_live_slots * (double)e->P.nqkv * 4.0);
+        }
+        e->tm.algo_bytes_per_step = fixed + gathered + (steps ? kv_per_tok * (ctx_tokens / steps) : 0);
         e->tm.algo_flops_per_step = (long long)((double)fixed * (double)e->tm.mean_live_slots);  // 2 flop per bf16 weight (2 bytes) per live row
         e->tm.mean_rows = steps ? (float)((double)e->row_steps / (double)steps) : 0.0f;
         e->tm.mean_ctx_tokens = steps ? (float)((double)ctx_tokens / (double)steps) : 0.0f;

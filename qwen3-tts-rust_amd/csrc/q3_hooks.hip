@@ -425,6 +425,109 @@ extern "C" int q3tts_k_attend_pick(int32_t fused, int32_t gqa_ratio, int32_t n_c
     return Q3TTS_OK;
 }
 
+// ---- the Predictor's layer-0 QKV table and the gathering attention ----------------------------------------------------
+extern "C" int q3tts_k_pred_table_row(q3tts_engine* e, int32_t q, int32_t code, float* out) {
+    if (!e || !out) return q3_set_err(e, Q3TTS_ERR_INVALID, "pred table row: null argument");
+    Q3_NOT_IN_SESSION(e);
+    if (!e->qkv0) return q3_set_err(e, Q3TTS_ERR_STATE, "pred table row: this engine has no layer-0 QKV table");
+    if (q < 1 || q > e->cfg.model.n_codebooks - 2) return q3_set_err(e, Q3TTS_ERR_INVALID, "pred table row: q outside 1 .. n_codebooks - 2");
+    const int rows = q3_pred_table_rows(e), r = (code >= 0 && code < rows) ? code : rows;  // the kernel's rule: anything else is the fallback row
+    Q3_HIP(e, hipSetDevice(e->cfg.device));
+    Q3_HIP(e, hipStreamSynchronize(e->stream));
+    Q3_HIP(e, hipMemcpy(out, q3_pred_table_slice(e, q) + (size_t)r * e->P.nqkv, (size_t)e->P.nqkv * 4, hipMemcpyDeviceToHost));
+    return Q3TTS_OK;
+}
+
+// The state one k_pred_next<false>(q) launch, or the bookkeeping column of one gathering attention launch, works on (row b = slot b)
+struct PredStepHook {
+    DevBuf keys, slots, row_slot, codec, pproj, bias, fb, px, codes;
+    static const char* check(const q3tts_k_pred_step* st) {
+        if (!st || !st->keys || !st->active || !st->n_frames || !st->codec_q || !st->pproj_q || !st->proj_b || !st->fb || !st->px || !st->codes) return "a null argument";
+        if (st->n_rows < 1 || st->n_rows > 4096 || st->n_key_parts < 1 || st->n_key_parts > 4096 || st->rows_q < 1) return "1 .. 4096 rows and key parts, rows_q >= 1";
+        if (st->n_codebooks < 3 || st->q < 1 || st->q > st->n_codebooks - 2) return "q in 1 .. n_codebooks - 2";
+        if (st->d_embed < 256 || st->d_embed % 256 || st->d_proj < 32 || st->d_proj % 32) return "d_embed % 256 == 0, d_proj % 32 == 0";
+        if (st->max_steps_cap < 1) return "max_steps_cap >= 1";
+        for (int b = 0; b < st->n_rows; ++b) if (st->n_frames[b] < 0 || st->n_frames[b] >= st->max_steps_cap) return "n_frames in [0, max_steps_cap)";
+        return nullptr;
+    }
+    int init(const q3tts_k_pred_step* st) {
+        const size_t B = st->n_rows;
+        std::vector<Q3Slot> sl(B); std::vector<int> id(B);
+        memset(sl.data(), 0, B * sizeof(Q3Slot));
+        for (size_t b = 0; b < B; ++b) { sl[b].active = st->active[b] ? 1 : 0; sl[b].n_frames = st->n_frames[b]; id[b] = (int)b; }
+        TRY(keys.put(st->keys, B * st->n_key_parts * 8)); TRY(slots.put(sl.data(), B * sizeof(Q3Slot))); TRY(row_slot.put(id.data(), B * 4));
+        TRY(codec.put(st->codec_q, (size_t)st->rows_q * st->d_embed * 4)); TRY(pproj.put(st->pproj_q, (size_t)st->rows_q * st->d_proj * 4));
+        TRY(bias.put(st->proj_b, (size_t)st->d_proj * 4)); TRY(fb.put(st->fb, B * st->d_embed * 4)); TRY(px.put(st->px, B * st->d_proj * 4));
+        return codes.put(st->codes, B * st->max_steps_cap * st->n_codebooks * 4);
+    }
+    int read(q3tts_k_pred_step* st) const {
+        const size_t B = st->n_rows;
+        TRY(fb.get(st->fb, B * st->d_embed * 4)); TRY(px.get(st->px, B * st->d_proj * 4));
+        return codes.get(st->codes, B * st->max_steps_cap * st->n_codebooks * 4);
+    }
+};
+
+extern "C" int q3tts_k_pred_next(int32_t device, q3tts_k_pred_step* st, const float* norm_w, uint16_t* xb, float* ssp) {
+    if (const char* why = PredStepHook::check(st)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string("pred next hook: ") + why);
+    if (!norm_w || !xb || !ssp) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pred next hook: a null argument");
+    HK(hipSetDevice(device));
+    PredStepHook h;
+    TRY(h.init(st));
+    const int B = st->n_rows, dp = st->d_proj;
+    DevBuf dnw, dxb, dssp;
+    TRY(dnw.put(norm_w, (size_t)dp * 4)); TRY(dxb.alloc(pad16(B) * dp * 2)); TRY(dssp.alloc((size_t)B * (dp / 16) * 4));
+    Q3PredNext pn{}; pn.keys = h.keys; pn.n_key_parts = st->n_key_parts; pn.q = st->q; pn.ncb = st->n_codebooks; pn.codec_q = h.codec; pn.rows_q = st->rows_q;
+    pn.d = st->d_embed; pn.slots = h.slots; pn.row_slot = h.row_slot; pn.B = B; pn.codes = h.codes; pn.max_steps_cap = st->max_steps_cap; pn.fb = h.fb;
+    pn.pproj_q = h.pproj; pn.proj_b = h.bias; pn.dp = dp; pn.px = h.px; pn.nw = dnw; pn.xb = dxb; pn.ssp = dssp;
+    if (q3_launch_pred_next(pn, nullptr, false)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pred next hook: the launch was refused");
+    HK(hipGetLastError()); HK(hipDeviceSynchronize());
+    TRY(h.read(st)); TRY(untile_host(dxb, B, dp, xb));
+    return dssp.get(ssp, (size_t)B * (dp / 16) * 4);
+}
+
+// One gathering attention launch as block 0 of pass st->q issues it: row b (= slot b, position len - 1, the Predictor's row-indexed cache) takes its
+// q / k / v from table[code of keys[b]] ([rows_q + 1][ld]; row rows_q = the fallback) and the extra workgroup column does st's bookkeeping.
+// qkv: n_rows runs of len rows as q3tts_k_attention_decode_ex takes them — the first len - 1 fill the slot's cache, the last one is NOT read.
+extern "C" int q3tts_k_attention_gather(int32_t device, q3tts_k_pred_step* st, const float* table, const float* qkv, int32_t len, int32_t n_ctx, int32_t Hq,
+                                        int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections,
+                                        int32_t out_form, void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache) {
+    if (const char* why = PredStepHook::check(st)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string("attention gather hook: ") + why);
+    const int n_slots = st->n_rows;
+    if (const char* why = AttHook::check(qkv, n_slots, n_ctx, Hq, Hkv, hd, qnw, knw, out_form, out, out_scale))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string("attention gather hook: ") + why);
+    if (!table || len < 1 || len > n_ctx) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention gather hook: table, 1 <= len <= n_ctx");
+    HK(hipSetDevice(device));
+    AttHook h;
+    TRY(h.init(n_slots, n_ctx, Hq, Hkv, qnw, knw, theta, sections, out_form, n_slots));
+    PredStepHook ps;
+    TRY(ps.init(st));
+    const int ld = h.ld, npre = n_slots * (len - 1);
+    std::vector<float> pre((size_t)std::max(npre, 1) * ld);
+    std::vector<int> pp, psl;
+    for (int s = 0, ip = 0; s < n_slots; ++s)
+        for (int r = 0; r < len - 1; ++r, ++ip) { memcpy(&pre[(size_t)ip * ld], qkv + ((size_t)s * len + r) * ld, (size_t)ld * 4); pp.push_back(r); psl.push_back(s); }
+    DevBuf dpre, dpp, dps, dtab;
+    TRY(dpre.put(pre.data(), pre.size() * 4)); TRY(dpp.put(pp.data(), pp.size() * 4)); TRY(dps.put(psl.data(), psl.size() * 4));
+    TRY(dtab.put(table, (size_t)(st->rows_q + 1) * ld * 4));
+    if (npre) {
+        Q3QkPrep qp = h.prep(dpre, npre, eps); qp.row_pos = dpp; qp.row_slot = dps;
+        if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention gather hook: the q/k prep launch was refused");
+    }
+    Q3QkPrep dq = h.prep(nullptr, n_slots, eps);   // (no row buffer: the gathering form reads the table)
+    Q3Attend at = h.attend(nullptr, n_slots);
+    dq.slot_mod = at.slot_mod = n_slots; dq.pos_const = at.pos_const = len - 1;
+    at.fused = 1; at.prep = dq;
+    Q3AttGather gt{}; gt.tab = dtab; gt.tab_rows = st->rows_q; gt.keys = ps.keys; gt.n_key_parts = st->n_key_parts; gt.q = st->q; gt.ncb = st->n_codebooks;
+    gt.codec_q = ps.codec; gt.d = st->d_embed; gt.slots = ps.slots; gt.row_slot = ps.row_slot; gt.codes = ps.codes; gt.max_steps_cap = st->max_steps_cap;
+    gt.fb = ps.fb; gt.pproj_q = ps.pproj; gt.proj_b = ps.bias; gt.dp = st->d_proj; gt.px = ps.px;
+    if (q3_launch_attend_gather(at, gt, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention gather hook: the launch was refused (two query heads per KV head, n_ctx 64)");
+    hipError_t er = hipGetLastError();
+    if (er == hipSuccess) er = hipDeviceSynchronize();
+    if (er != hipSuccess) return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, std::string("attention gather hook: ") + hipGetErrorString(er));
+    TRY(h.read_out(out, out_scale)); TRY(h.read_cache(k_cache, v_cache));
+    return ps.read(st);
+}
+
 extern "C" int q3tts_k_sample(int32_t device, const float* logits, int32_t n, int32_t ld, int32_t limit, float temperature, int32_t top_k,
                               float top_p, const float* r, int32_t* out) {
     if (!logits || !out || n <= 0 || limit <= 0 || limit > 4096 || limit > ld) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "sample hook: bad shape");

@@ -265,6 +265,23 @@ struct Q3Attend {
     Q3_STAMP_FIELD
 };
 int q3_launch_attend(const Q3Attend& a, hipStream_t s);  // 0: launched; nonzero: refused (see its definition), nothing launched
+// The gathering form of k_attend_small (block 0 of passes q >= 1 of the greedy bf16 Predictor): the row's q / k / v are not
+// read from a.qkv but from a table of every possible input row's layer-0 QKV, tab[code], where code is the argmax k_pred_next<false>(q)
+// takes from the same per-tile keys (largest key of the row, q3_argmax_idx); a code outside [0, tab_rows) reads the fallback row tab_rows.
+// One more workgroup column (blockIdx.x == Hkv) does what k_pred_next(q) did besides the row's norm inputs, for rows whose slot is active:
+// codes[slot][n_frames][q] = code, fb[row] += codec_q[code] (+ 0 out of range), px[row] = pproj_q[code] (proj_b out of range).
+struct Q3AttGather {
+    const float* tab; int tab_rows;                    // [tab_rows + 1][a.ld] f32
+    const unsigned long long* keys; int n_key_parts;   // keys[row][n_key_parts]: the head GEMM's per-tile maxima of pass q - 1
+    int q, ncb;
+    const float* codec_q; int d;                       // [tab_rows][d]; d % 4 == 0
+    const Q3Slot* slots; const int* row_slot;          // the slot RECORD of a row (the cache stays indexed as a says)
+    int* codes; int max_steps_cap;
+    float* fb;
+    const float* pproj_q; const float* proj_b; int dp; float* px;  // [tab_rows][dp], [dp]; dp % 4 == 0
+};
+// 0: launched; nonzero: refused, nothing launched — a launch q3_attend_pick does not give to k_attend_small<2>, or a missing table / pointer
+int q3_launch_attend_gather(const Q3Attend& a, const Q3AttGather& t, hipStream_t s);
 // the nine attention kernels of q3_attend.hip as q3_attend_pick names them (q3tts_k_attend_pick reports these numbers)
 enum { Q3_ATT_REFUSED = -1, Q3_ATT_N1 = 0, Q3_ATT_N2 = 1, Q3_ATT_N4 = 2,   // k_attend<1 / 2 / 4, false>
        Q3_ATT_F2 = 3, Q3_ATT_F4 = 4,                                       // k_attend<2 / 4, true>
@@ -333,6 +350,9 @@ struct Q3PredNext {
     Q3_STAMP_FIELD
 };
 int q3_launch_pred_next(const Q3PredNext& a, hipStream_t s, bool sample = false);  // -1: the sampling variant refuses cbs > Q3_SAMP_MAX
+// The norm inputs for nw (A-tiled xb with dp columns, ssp [rows + 1][dp / 16]) of the rows k_pred_next<false> can write into px from one
+// pre-projected table: row c < rows = tab[c], row `rows` = bias (a code out of range). q3_norm_out on every element, as k_pred_next applies it.
+void q3_launch_pred_table_rows(const float* tab, int rows, const float* bias, int dp, const float* nw, uint16_t* xb, float* ssp, hipStream_t s);
 int q3_pred_next_prepare();  // the sampling variant's kernel attributes, once per device; call outside stream capture. -1: the device refused them
 // Streamed text (include/q3tts.h, "streaming text input"): the last pass's addend row is text[id] (the prompt builder's out-of-range rule)
 // instead of tts_pad, per slot and frame. ids[slot][cap]: the slot's trailing ids T; cnt[slot] <= cap: how many are valid; cur[slot]: the

@@ -640,6 +640,17 @@ int q3_launch_pred_next(const Q3PredNext& a, hipStream_t s, bool sample) {
     hipLaunchKernelGGL(k_pred_next<true>, dim3(a.B), dim3(256), (size_t)a.cbs * sizeof(float), s, a);
     return 0;
 }
+// One workgroup per table row: what k_pred_next<false> writes into xb / ssp for px = that row (the same q3_norm_out per element; a tile's
+// 16 lanes are all active since dp % 16 == 0).
+__global__ __launch_bounds__(256) void k_pred_table_rows(const float* tab, int rows, const float* bias, int dp, const float* nw, uint16_t* xb, float* ssp) {
+    const int c = blockIdx.x;
+    const float* pr = c < rows ? tab + (size_t)c * dp : bias;
+    for (int i = threadIdx.x; i < dp; i += 256)
+        q3_norm_out(pr[i], nw[i], xb + q3_atile_off(c, i, dp >> 5), ssp + (size_t)c * (dp >> 4) + (i >> 4), (i & 15) == 0);
+}
+void q3_launch_pred_table_rows(const float* tab, int rows, const float* bias, int dp, const float* nw, uint16_t* xb, float* ssp, hipStream_t s) {
+    hipLaunchKernelGGL(k_pred_table_rows, dim3(rows + 1), dim3(256), 0, s, tab, rows, bias, dp, nw, xb, ssp);
+}
 int q3_launch_pred_last_text(const Q3PredNext& a, const Q3TextRows& t, hipStream_t s, bool sample) {
     if (a.q != a.ncb - 1 || !t.ids || !t.cnt || !t.cur || t.cap < 1 || (t.text_vocab > 0 && !t.text)) return -1;
     if (!sample) { hipLaunchKernelGGL((k_pred_next<false, Q3TextRows>), dim3(a.B), dim3(256), 0, s, a, t); return 0; }

@@ -27,7 +27,7 @@ static void y_rows(Q3BGemm& g, const Q3Tfm& t, const Q3Rows& r, const float* nw_
     g.epi = Q3_EPI_RESID; g.y = r.x; g.ldy = t.d; g.yb = r.xb; g.nw_next = nw_next; g.ssp_out = r.ssp; g.ld_ssp_out = t.d / 16;
     if (t.a8) { g.yscale = r.ascale; g.y_rt16 = r.rt16; }
 }
-static Q3BGemm gemm_qkv(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, float eps, int once) {
+Q3BGemm q3_gemm_qkv(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, float eps, int once) {
     Q3BGemm g = gemm_w(t.wqkv[l], t.q8 ? t.sqkv[l] : nullptr, t.d, t.nqkv, rows, once);
     a_rows(g, t, r, eps);
     g.epi = Q3_EPI_STORE; g.y = sc.qkv; g.ldy = t.nqkv;
@@ -89,7 +89,9 @@ int q3_run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& 
     const int once = &t == &e->T ? 1 : 0;
     for (int l = 0; l < t.L; ++l) {
         hipEvent_t* pe = l == 0 ? a.probe : nullptr;  // the probe brackets one launch of block 0
-        bad += q3_launch_gemm(e, t, gemm_qkv(t, l, r, sc, a.rows, eps, once), s, pe, 1);
+        // block 0 of a gathering pass has no QKV launch (its rows come from e->qkv0): the QKV probe then brackets block 1's, the same shape and instance
+        const bool gather = a.gather && l == 0;
+        if (!gather) bad += q3_launch_gemm(e, t, q3_gemm_qkv(t, l, r, sc, a.rows, eps, once), s, l == (a.gather ? 1 : 0) ? a.probe : nullptr, 1);
         Q3QkPrep qp{}; qp.qkv = sc.qkv; qp.ld = t.nqkv; qp.rows = a.rows; qp.Hq = t.Hq; qp.Hkv = t.Hkv; qp.hd = t.hd;
         qp.qnw = t.qn[l]; qp.knw = t.kn[l]; qp.eps = eps; qp.cs = t.cs; qp.sn = t.sn;
         qp.kc = t.kc + l * t.layer_stride; qp.vc = t.vc + l * t.layer_stride; qp.n_ctx = t.n_ctx; qp.row_pos = a.row_pos; qp.row_slot = a.row_slot;
@@ -103,7 +105,7 @@ int q3_run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& 
         at.fused = pair ? 2 : (fused ? 1 : 0); at.prep = qp; at.out_bf16 = 1; at.slot_mod = a.slot_mod; at.pos_const = a.pos_const;
         if (t.a8) { at.out_bf16 = 2; at.out_scale = sc.asc_att; at.out_rt16 = sc.rt16; }
         if (!fused && !pair && a.n_seg > 0) { at.seg = a.seg; at.n_seg = a.n_seg; at.seg_max_n = a.seg_max_n; at.seg_max_t = a.seg_max_t; }  // prefill of whole prompts (prefill_layers): the launch's rows as per-slot runs
-        bad += probed(e, pe, 2, s, [&] { return q3_launch_attend(at, s) != 0; });
+        bad += probed(e, pe, 2, s, [&] { return (gather ? q3_launch_attend_gather(at, *a.gather, s) : q3_launch_attend(at, s)) != 0; });
         bad += q3_launch_gemm(e, t, gemm_o(t, l, r, sc, a.rows, once), s, pe, 3);
         bad += q3_launch_gemm(e, t, gemm_gate_up(t, l, r, sc, a.rows, eps, once), s, pe, 0);
         bad += q3_launch_gemm(e, t, gemm_down(t, l, r, sc, a.rows, once), s, pe, 4);
@@ -148,14 +150,24 @@ int q3_record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B) {
             bad += q3_launch_pred_last_text(pn, tr, s, smp) != 0;
         } else bad += q3_launch_pred_next(pn, s, smp) != 0;
     };
+    // With the table (q3_pred_table_on), pass q >= 1 launches neither k_pred_next(q) nor block 0's QKV GEMM: block 0's attention takes the row's
+    // q / k / v from qkv0[q][code_q] and its extra workgroup column records the code, adds codec_q[code_q] to fb and writes the row into P.x
+    // (the O projection's residual); the row's norm inputs are not written (only the skipped GEMM read them).
+    const bool tab = q3_pred_table_on(e);
     for (int q = 0; q < ncb - 1; ++q) {  // pass q produces code_{q+1}
         const int rows = q == 0 ? 2 * B : B;
-        if (q > 0) pred_next(q);
+        const bool gq = tab && q > 0;
+        Q3AttGather gt{};
+        if (gq) {
+            gt.tab = q3_pred_table_slice(e, q); gt.tab_rows = q3_pred_table_rows(e); gt.keys = L.keys; gt.n_key_parts = cbs / 16; gt.q = q; gt.ncb = ncb;
+            gt.codec_q = e->codec[q]; gt.d = de; gt.slots = slots; gt.row_slot = L.slot_id; gt.codes = codes; gt.max_steps_cap = cap; gt.fb = L.fb;
+            gt.pproj_q = e->pproj[q]; gt.proj_b = e->proj_b; gt.dp = dp; gt.px = L.P.x;
+        } else if (q > 0) pred_next(q);
         hipEvent_t* pe = nullptr;
         if (e->probe == 1 && q == 1 && B == L.nb && e->probe_i + 2 <= 8) { pe = &e->probe_ev[e->probe_i]; e->probe_i += 2; }
         // the Predictor's cache lives for one frame (src/tts/engine.rs:575: cleared per frame), so it is indexed by ROW: slot = row % B,
         // position = (q == 0 ? row / B : q + 1) — known without a load, the attention kernels request their operands at once
-        bad += q3_run_layers(e, e->P, L.P, {.rows = rows, .one_row_per_slot = q > 0, .probe = pe, .slot_mod = B, .pos_const = q == 0 ? 0 : q + 1}, L.sc, s);
+        bad += q3_run_layers(e, e->P, L.P, {.rows = rows, .one_row_per_slot = q > 0, .probe = pe, .slot_mod = B, .pos_const = q == 0 ? 0 : q + 1, .gather = gq ? &gt : nullptr}, L.sc, s);
         // head q on the rows that carry the newest position (pass 0: rows [B, 2B)), argmax epilogue
         Q3BGemm g = q3_gemm_head(e->P, q, cbs, L.P, q == 0 ? B : 0, B, eps, 0, smp ? L.plogits : nullptr);  // smp: the logits themselves; k_pred_next<true>(q + 1) samples from them
         if (!smp) { g.epi = Q3_EPI_ARGMAX; g.keys = L.keys; g.key_stride = cbs / 16; }  // per-tile maxima; k_pred_next(q + 1) reduces them

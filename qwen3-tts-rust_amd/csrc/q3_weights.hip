@@ -299,3 +299,44 @@ int q3_assets_init(q3tts_engine* e, const std::string& wdir) {
     Q3_HIP(e, hipStreamSynchronize(s));
     return Q3TTS_OK;
 }
+
+// ---- the Predictor's layer-0 QKV table --------------------------------------------------------------------------------
+// In passes 1 .. n_codebooks - 2 of the greedy Predictor the first block's input is no computed activation but a row of pproj[q] (or
+// proj_b), chosen by the code of the pass before: block 0's raw q / k / v are a function of (q, code) and of the weights alone. They are
+// computed here once, with the decode path's own kernels — q3_norm_out on every element of the row, as k_pred_next applies it, then
+// the QKV GEMM descriptor of q3_run_layers with its STORE epilogue pointed at the table — so a table row holds the bits the two launches
+// left in sc.qkv (a GEMM row depends on no other row, and every k_bgemm instance computes the one canonical order).
+// Q3TTS_PRED_TABLE=0: no table. Q3TTS_PRED_TABLE_MAX_MB (default 1024): a larger table is not built. Both read here, once per engine.
+int q3_pred_table_init(q3tts_engine* e) {
+    const q3tts_model_config& m = e->cfg.model;
+    const Q3Tfm& P = e->P;
+    const int nq = m.n_codebooks - 2, rows = m.codecq_rows, R = rows + 1, dp = m.p_d_model;
+    if (const char* ev = getenv("Q3TTS_PRED_TABLE")) if (!atoi(ev)) return Q3TTS_OK;
+    if (P.a8 || nq < 1 || rows < 1) return Q3TTS_OK;
+    {   // the gathering form exists for k_attend_small<2> only: a Predictor whose decode attention is another kernel keeps its launches
+        Q3Attend at{}; at.hd = P.hd; at.Hq = P.Hq; at.Hkv = P.Hkv; at.fused = 1; at.n_ctx = P.n_ctx;
+        if (q3_attend_pick(at) != Q3_ATT_SMALL2 || (m.d_embed & 3) || (dp & 3)) return Q3TTS_OK;
+    }
+    long long max_mb = 1024;
+    if (const char* ev = getenv("Q3TTS_PRED_TABLE_MAX_MB")) max_mb = atoll(ev);
+    const size_t n = (size_t)nq * R * P.nqkv;
+    if ((double)n * 4.0 > (double)max_mb * 1048576.0) return Q3TTS_OK;
+    TRY(q3_dalloc(e, &e->qkv0, n));
+    // the rows' norm inputs: staging that lives for this call (its own hipMalloc / hipFree pair)
+    const size_t r16 = ((size_t)R + 15) & ~(size_t)15;
+    struct Stage { void* p = nullptr; ~Stage() { if (p) hipFree(p); } } xb, ssp;
+    if (hipMalloc(&xb.p, r16 * dp * 2) != hipSuccess || hipMalloc(&ssp.p, (size_t)R * (dp / 16) * 4) != hipSuccess)
+        return q3_set_err(e, Q3TTS_ERR_OOM, "hipMalloc (Predictor QKV table staging)");
+    hipStream_t s = e->stream;
+    Q3_HIP(e, hipMemsetAsync(xb.p, 0, r16 * dp * 2, s));
+    Q3Rows r{}; r.xb = (uint16_t*)xb.p; r.ssp = (float*)ssp.p;
+    for (int q = 1; q <= nq; ++q) {
+        q3_launch_pred_table_rows(e->pproj[q], rows, e->proj_b, dp, P.attn_norm[0], r.xb, r.ssp, s);
+        Q3Scratch sc{}; sc.qkv = e->qkv0 + (size_t)(q - 1) * R * P.nqkv;
+        if (q3_launch_gemm(e, P, q3_gemm_qkv(P, 0, r, sc, R, m.rms_eps, 0), s))
+            return q3_set_err(e, Q3TTS_ERR_INVALID, "Predictor QKV table: the GEMM launch was refused for this model shape");
+    }
+    Q3_HIP(e, hipGetLastError());
+    Q3_HIP(e, hipStreamSynchronize(s));
+    return Q3TTS_OK;
+}

@@ -160,7 +160,18 @@ SYMBOLS = [
     "q3tts_set_output_rate", "q3tts_get_output_rate", "q3tts_resample", "q3tts_k_resample_table", "q3tts_k_pcm_resample",
     "q3tts_session_append_text", "q3tts_k_text_ready",
     "q3tts_k_attention_runs", "q3tts_k_attention_decode_ex", "q3tts_k_attention_pair", "q3tts_k_attend_pick",
+    "q3tts_k_pred_table_row", "q3tts_k_pred_next", "q3tts_k_attention_gather",
 ]
+
+
+class PredStep(C.Structure):
+    """q3tts_k_pred_step: the state of one k_pred_next(q) launch / of the gathering attention's bookkeeping column."""
+    _fields_ = [
+        ("n_rows", C.c_int32), ("q", C.c_int32), ("n_codebooks", C.c_int32), ("n_key_parts", C.c_int32), ("rows_q", C.c_int32),
+        ("d_embed", C.c_int32), ("d_proj", C.c_int32), ("max_steps_cap", C.c_int32),
+        ("keys", C.c_void_p), ("active", C.c_void_p), ("n_frames", C.c_void_p), ("codec_q", C.c_void_p), ("pproj_q", C.c_void_p),
+        ("proj_b", C.c_void_p), ("fb", C.c_void_p), ("px", C.c_void_p), ("codes", C.c_void_p),
+    ]
 
 
 class Q3Error(RuntimeError):
@@ -238,6 +249,10 @@ def load_library(path=None):
     lib.q3tts_k_attention_pair.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float, C.c_float,
                                            i32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.q3tts_k_attend_pick.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
+    lib.q3tts_k_pred_table_row.argtypes = [vp, C.c_int32, C.c_int32, f32p]
+    lib.q3tts_k_pred_next.argtypes = [C.c_int32, C.POINTER(PredStep), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.q3tts_k_attention_gather.argtypes = [C.c_int32, C.POINTER(PredStep), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             f32p, f32p, C.c_float, C.c_float, i32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.q3tts_k_sample.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float,
                                    f32p, i32p]
     lib.q3tts_k_talker_prefill.argtypes = [vp, f32p, C.c_int32, f32p, f32p]

@@ -131,6 +131,14 @@ class NativeEngine:
         """Test hook: force = 1 runs the sampling form of the frame step whatever the Predictor sampler's temperature."""
         self._check(self.lib.q3tts_k_pred_variant(self.h, int(force)), "q3tts_k_pred_variant")
 
+    def pred_table_row(self, q, code):
+        """Test hook (q3tts_k_pred_table_row): row `code` of slice q of the Predictor's layer-0 QKV table (a code out of range: the
+        fallback row). Raises Q3Error when the engine has no table."""
+        m = self.cfg.model
+        out = np.zeros((m.p_n_head + 2 * m.p_n_kv_head) * m.p_head_dim, dtype=np.float32)
+        self._check(self.lib.q3tts_k_pred_table_row(self.h, int(q), int(code), _ptr(out, f32p)), "q3tts_k_pred_table_row")
+        return out
+
     def build_prompt(self, desc):
         out, n = f32p(), C.c_int32()
         self._check(self.lib.q3tts_build_prompt(self.h, C.byref(desc), C.byref(out), C.byref(n)), "q3tts_build_prompt")
@@ -842,6 +850,64 @@ def k_attention_pair(qkv, n_slots, n_ctx, n_head, n_kv_head, head_dim, q_norm_w,
                                     rope_theta, None if sec is None else _ptr(sec, i32p), out_form, _dp(out), _dp(sc), _dp(kc), _dp(vc))
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_attention_pair failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return _att_hook_ret(out, sc, kc, vc)
+
+
+class PredStepState:
+    """The arrays behind a q3tts_k_pred_step (q3tts_k_pred_next / q3tts_k_attention_gather): row b stands for slot b. keys u64
+    [n_rows][n_key_parts]; active / n_frames [n_rows]; codec_q [rows_q][d_embed]; pproj_q [rows_q][d_proj]; proj_b [d_proj]; fb, px and codes
+    ([n_rows][max_steps_cap][n_codebooks]) are copied here and updated in place by a call."""
+
+    def __init__(self, q, n_codebooks, keys, active, n_frames, codec_q, pproj_q, proj_b, fb, px, codes):
+        c = np.ascontiguousarray
+        self.keys = c(keys, dtype=np.uint64); self.active = c(active, dtype=np.int32); self.n_frames = c(n_frames, dtype=np.int32)
+        self.codec_q = c(codec_q, dtype=np.float32); self.pproj_q = c(pproj_q, dtype=np.float32); self.proj_b = c(proj_b, dtype=np.float32)
+        self.fb = np.array(fb, dtype=np.float32, order="C"); self.px = np.array(px, dtype=np.float32, order="C")
+        self.codes = np.array(codes, dtype=np.int32, order="C")
+        n = self.keys.shape[0]
+        assert self.active.shape == (n,) and self.n_frames.shape == (n,) and self.fb.shape == (n, self.codec_q.shape[1])
+        assert self.px.shape == (n, self.pproj_q.shape[1]) and self.codes.shape[0] == n and self.codes.shape[2] == n_codebooks
+        st = _abi.PredStep()
+        st.n_rows, st.q, st.n_codebooks, st.n_key_parts, st.rows_q = n, q, n_codebooks, self.keys.shape[1], self.codec_q.shape[0]
+        st.d_embed, st.d_proj, st.max_steps_cap = self.codec_q.shape[1], self.pproj_q.shape[1], self.codes.shape[1]
+        for name in ("keys", "active", "n_frames", "codec_q", "pproj_q", "proj_b", "fb", "px", "codes"):
+            setattr(st, name, getattr(self, name).ctypes.data)
+        self.st = st
+
+
+def k_pred_next(state, norm_w, device=0):
+    """q3tts_k_pred_next: k_pred_next<false>(q) on a PredStepState (fb / px / codes updated in place). Returns the norm inputs it wrote for
+    norm_w: (xb bf16 bits [n_rows][d_proj], ssp [n_rows][d_proj / 16])."""
+    lib = _abi.load_library()
+    nw = np.ascontiguousarray(norm_w, dtype=np.float32)
+    n, dp = state.px.shape
+    xb = np.zeros((n, dp), dtype=np.uint16); ssp = np.zeros((n, dp // 16), dtype=np.float32)
+    rc = lib.q3tts_k_pred_next(device, C.byref(state.st), nw.ctypes.data, xb.ctypes.data, ssp.ctypes.data)
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_pred_next failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return xb, ssp
+
+
+def k_attention_gather(state, table, qkv, length, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, out_form=0,
+                       want_cache=True, device=0):
+    """q3tts_k_attention_gather: one gathering launch of k_attend_small<2> on a PredStepState (updated in place). table [rows_q + 1][ld];
+    qkv: n_rows runs of `length` rows as k_attention_decode_ex takes them, of which the last row of a run is not read. Returns the dict of
+    k_attention_runs with out [n_rows][n_head * head_dim]."""
+    lib = _abi.load_library()
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+    n = state.px.shape[0]
+    ld = (n_head + 2 * n_kv_head) * head_dim
+    assert qkv.shape == (n * length, ld) and tab.shape == (state.codec_q.shape[0] + 1, ld)
+    qn = np.ascontiguousarray(q_norm_w, dtype=np.float32)
+    kn = np.ascontiguousarray(k_norm_w, dtype=np.float32)
+    sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
+    out, sc, kc, vc = _att_hook_out(n, n_head * head_dim, out_form, n, n_kv_head, n_ctx, head_dim, want_cache)
+    rc = lib.q3tts_k_attention_gather(device, C.byref(state.st), tab.ctypes.data, qkv.ctypes.data, length, n_ctx, n_head, n_kv_head, head_dim,
+                                      _ptr(qn, f32p), _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), out_form,
+                                      _dp(out), _dp(sc), _dp(kc), _dp(vc))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_attention_gather failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return _att_hook_ret(out, sc, kc, vc)
 
 

@@ -21,9 +21,12 @@ def show(seq):
         print(f"{r['Kernel_Name'][:34]:34s} g=({int(r['Grid_Size_X']) // int(r['Workgroup_Size_X'])},{r['Grid_Size_Y']}) {dur(r):7.2f} us")
 
 
-pn = [i for i, r in enumerate(fr) if r['Kernel_Name'].startswith('k_pred_next')]
+pn = [i for i, r in enumerate(fr) if 'k_pred_next' in r['Kernel_Name']]
+# with the layer-0 QKV table passes 1 .. 14 start at their gathering attention launch, not at a k_pred_next
+ga = [i for i, r in enumerate(fr) if 'Q3AttGather' in r['Kernel_Name']]
+p5 = ga[4] if len(ga) > 4 else pn[4]
 print("--- head of frame"); show(fr[:8])
-print("--- pass 5"); show(fr[pn[4]:pn[4] + 7])
+print("--- pass 5"); show(fr[p5:p5 + 7])
 print("--- talker"); show(fr[pn[-1]:pn[-1] + 7]); show(fr[-2:])
 for nm, part in (("predictor", fr[:pn[-1]]), ("talker", fr[pn[-1]:])):
     print(nm, len(part), "kernels,", round(sum(dur(r) for r in part), 1), "us")
