@@ -37,6 +37,7 @@ extern "C" {
 #define Q3TTS_ERR_IO (-4)          /* weight / asset file problem */
 #define Q3TTS_ERR_STATE (-5)       /* call order / handle state */
 #define Q3TTS_ERR_UNSUPPORTED (-6)
+#define Q3TTS_MAX_BATCH 256        /* the largest q3tts_engine_config.max_batch */
 
 #define Q3TTS_MAX_UPSAMPLE 4
 #define Q3TTS_MAX_DEC_BLOCKS 8
@@ -88,7 +89,16 @@ typedef struct q3tts_engine_config {
     q3tts_model_config model;
     q3tts_vocoder_config vocoder;
     int32_t device;        /* HIP device ordinal */
-    int32_t max_batch;     /* concurrent utterance slots, 1..64 */
+    int32_t max_batch;     /* concurrent utterance slots, 1..Q3TTS_MAX_BATCH (256). Results do not depend on it. Device memory per slot:
+                            *   Talker KV  2 * t_n_layer * t_n_kv_head * t_head_dim * n_ctx * 2 B  (470 MB at the 1.7B shape with n_ctx = 4096:
+                            *              256 slots need a smaller n_ctx, e.g. 1024: 117 MB per slot, 30 GB)
+                            *   Predictor cache  2 * p_n_layer * p_n_kv_head * p_head_dim * 64 * 2 B
+                            *   codes, Talker draws  max_steps_cap * (n_codebooks + 1) * 4 B;  Predictor draws (prng)  max_steps_cap *
+                            *              (n_codebooks - 1) * 4 B;  seen codes  ceil(sample_limit / 32) * 4 B
+                            *   vocoder  PCM row max_steps_cap * samples per frame * 4 B, attention rings 2 * n_layer * sliding_window *
+                            *              n_head * head_dim * 4 B, the convolutions' history rows
+                            * q3tts_engine_create adds these to the weights and the row buffers before it allocates anything and returns
+                            * Q3TTS_ERR_OOM, with the bytes needed and the bytes free in the message, when the device has less. */
     int32_t n_ctx;         /* Talker context per slot (reference 4096: src/tts/engine.rs:133) */
     int32_t max_steps_cap; /* upper bound accepted by q3tts_set_max_steps (reference default 512) */
     int32_t with_vocoder;  /* 0: codes only (no vocoder weights allocated) */
@@ -733,6 +743,24 @@ int q3tts_k_resample_table(int32_t rate_in, int32_t rate_out, int32_t* L, int32_
 int q3tts_k_pcm_resample(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* row_len, const int32_t* row_final,
                          const int32_t* ent_row, const int32_t* ent_first, const int32_t* ent_count, const int64_t* ent_dst, int32_t n_ent,
                          int32_t rate_in, int32_t rate_out, int32_t format, void* out, int64_t out_n, int32_t iters, float* mean_ms);
+/* The row buckets of an engine with max_batch slots, ascending (a frame step runs on the smallest bucket that holds the live slots; one
+ * captured graph per bucket): 1, 2, 4, 8, the multiples of 16 up to 64, above 64 the multiples of 32, last max_batch itself. Returns the
+ * count (<= cap), Q3TTS_ERR_INVALID for max_batch outside 1..Q3TTS_MAX_BATCH or a cap too small. Needs no GPU. */
+int q3tts_k_row_buckets(int32_t max_batch, int32_t* out, int32_t cap);
+/* out[i] = the frame steps the engine has run on bucket i of q3tts_k_row_buckets(max_batch) since it was created. Returns the bucket count.
+ * The counters are atomic: the hook may be called from any thread while a session's worker runs. */
+int q3tts_k_bucket_steps(const q3tts_engine* e, int64_t* out, int32_t cap);
+/* out2[0] = k_kv_prefix launches since the engine was created, out2[1] = the most prefixed requests one prefill group has held (a group of
+ * more than 64 launches the full 64-entry descriptor and starts another). */
+int q3tts_k_prefix_stats(const q3tts_engine* e, int64_t* out2);
+/* What q3tts_engine_create compares with the device's free memory before it allocates: the bytes the config alone sizes (weights, the
+ * two caches, per-slot decode state, the lane's and the prefill's rows and scratch, the vocoder's PCM rows and attention rings). A lower
+ * bound of q3tts_k_device_bytes of the created engine (the tests hold it to that). Needs no GPU. */
+int q3tts_k_engine_footprint(const q3tts_engine_config* cfg, int64_t* bytes);
+/* Device bytes the engine's one allocator has handed out so far: everything that lives as long as the engine (weights, tables, caches,
+ * rows, scratch, the vocoder's weights, work buffers and per-slot state). Not counted: what regrows on demand (device-resident PCM, the
+ * resampler's staging, voice prefixes, a session's staging buffer) and the weight loaders' temporary staging. */
+int q3tts_k_device_bytes(const q3tts_engine* e, int64_t* bytes);
 /* rand 0.8 StdRng (ChaCha12) stream: seed_from_u64(seed) then n x gen::<f32>() */
 int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out);
 

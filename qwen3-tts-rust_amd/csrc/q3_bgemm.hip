@@ -571,12 +571,19 @@ static void bg_pick(const Q3BGemm& g, int* rt, int* nt, int* big) {
         for (int NT = 1; NT <= 3; ++NT) {
             if (tiles % NT) continue;
             if (g_lds_cap_kb > 0 && 8 * RT * NT / BG_PH(RT, NT) > g_lds_cap_kb && !(RT == 1 && NT == 1)) continue;
-            if (g.B > 64 && RT != 4 && !(RT == 2 && g.B <= 128)) continue;  // many rows (prefill): 64-row chunks
+            // 65 .. 512 rows of bf16 weights (decode steps of engines with more than 64 slots, pass A at twice the rows; short prefills): every
+            // row tile competes — the rounds term below already charges a narrow tile for its extra row chunks, and 96 or 192 rows are whole
+            // chunks of RT = 3 but pad RT = 4 by a third (profiles/r05/slots_gemm_sweep.txt: the RT = 4 rule lost 13 - 27 % there).
+            // More rows (prefill) and Q8_0 weights, which the sweep did not cover, keep the 64-row chunks.
+            const bool mid = g.B > 64 && g.B <= 512 && !g.wscale;
+            if (g.B > 64 && !mid && RT != 4 && !(RT == 2 && g.B <= 128)) continue;  // many rows (prefill): 64-row chunks
             const long chunks = (g.B + 16 * RT - 1) / (16 * RT);
             if (g.B <= 64 && RT > 1 && 16 * (RT - 1) * chunks >= g.B) continue;  // a smaller RT covers the rows with the same chunk count
             const long wgs = (long)(tiles / NT) * chunks, rounds = (wgs + 255) / 256;
             const long cost = rounds * ((g.wscale ? 32L * RT + 17L * NT : 32L * (RT + NT)) * g.K + 24000L);  // + a fixed cost per round (ramp, reduction); Q8_0 weights: 17 bytes per k per column tile
-            if (bestCost < 0 || cost < bestCost || (cost == bestCost && (wgs > bestWgs || (wgs == bestWgs && NT > bestNT)))) { bestCost = cost; bestRT = RT; bestNT = NT; bestWgs = wgs; }
+            // equal cost: more workgroups, then the wider column tile; at 65 .. 512 rows the wider column tile first (the sweep: (2,2) over (3,1))
+            const bool tie = mid ? (NT > bestNT || (NT == bestNT && wgs > bestWgs)) : (wgs > bestWgs || (wgs == bestWgs && NT > bestNT));
+            if (bestCost < 0 || cost < bestCost || (cost == bestCost && tie)) { bestCost = cost; bestRT = RT; bestNT = NT; bestWgs = wgs; }
         }
     if (g_force_rt > 0 && g_force_nt > 0 && tiles % g_force_nt == 0) { bestRT = g_force_rt; bestNT = g_force_nt; }
     *rt = bestRT; *nt = bestNT;

@@ -76,6 +76,7 @@ struct q3tts_engine {
     std::string err;
     hipStream_t stream = nullptr, vstream = nullptr;
     std::vector<void*> allocs;          // every q3_dalloc of this engine, freed by q3tts_engine_destroy
+    size_t dev_bytes = 0;               // bytes handed out by q3_dev_alloc_zeroed so far (q3tts_k_device_bytes)
     Q3Tfm T, P;
     // assets
     float* text = nullptr;
@@ -95,6 +96,8 @@ struct q3tts_engine {
     // device), so a draining batch stops paying for rows it no longer has.
     int B = 0;
     std::vector<int> buckets; int cur_bucket = -1;
+    std::vector<std::atomic<long long>> bucket_steps;  // frame steps run on each bucket since creation (q3tts_k_bucket_steps: read from any thread while a session's worker counts)
+    std::atomic<long long> kvp_launches{0}, kvp_group_max{0};  // k_kv_prefix launches since creation; the most prefixed requests one prefill group held (q3tts_k_prefix_stats)
     std::vector<int> row_of_slot, slot_of_row;
     Q3Slot* slots = nullptr;              // device [B]
     Q3Slot* slots_host = nullptr;         // pinned mirror [B] + staging [B]

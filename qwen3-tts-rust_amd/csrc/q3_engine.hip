@@ -74,7 +74,7 @@ static int validate(const q3tts_engine_config& c, std::string& why) {
     REQ(m.sample_limit > 0 && m.sample_limit <= m.t_vocab && m.sample_limit <= 4096);
     REQ(m.t_mrope_sections[0] + m.t_mrope_sections[1] + m.t_mrope_sections[2] + m.t_mrope_sections[3] == m.t_head_dim / 2);
     REQ(m.tts_pad_id >= 0 && (c.weights_path || m.tts_pad_id < m.text_vocab));  // with weights_path the text table's row count is the file's (0 without one: tts_pad is then zeros)
-    REQ(c.max_batch >= 1 && c.max_batch <= 64);
+    REQ(c.max_batch >= 1 && c.max_batch <= Q3TTS_MAX_BATCH);
     REQ(c.n_ctx >= 64 && c.n_ctx % 64 == 0 && c.n_ctx <= 8192);
     REQ(c.max_steps_cap >= 1 && c.max_steps_cap < c.n_ctx);
     REQ(m.n_codebooks + 1 <= 64);
@@ -90,6 +90,66 @@ static int validate(const q3tts_engine_config& c, std::string& why) {
     return Q3TTS_OK;
 }
 
+// Row buckets of an engine with max_batch slots (host only; also the test hook q3tts_k_row_buckets): 1, 2, 4, 8, then the multiples of 16
+// (the GEMM's row tiles are 16 wide: a 48-row step costs 3/4 of a 64-row one) up to 64; above 64 the multiples of 32 (a frame step is
+// captured per bucket x Predictor variant x text form: capture time and graph memory grow with the count — 14 sets at 256 slots, not 20);
+// last max_batch itself. For max_batch <= 64 this is the list the engine always had.
+static void row_buckets(int nb, std::vector<int>& out) {
+    out.clear();
+    for (int r = 1; r < nb && r < 16; r *= 2) out.push_back(r);
+    for (int r = 16; r < nb && r <= 64; r += 16) out.push_back(r);
+    for (int r = 96; r < nb; r += 32) out.push_back(r);
+    out.push_back(nb);
+}
+extern "C" int q3tts_k_row_buckets(int32_t max_batch, int32_t* out, int32_t cap) {
+    if (max_batch < 1 || max_batch > Q3TTS_MAX_BATCH || !out) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "row buckets: max_batch outside 1..256 or null output");
+    std::vector<int> b;
+    row_buckets(max_batch, b);
+    if ((int)b.size() > cap) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "row buckets: output too small");
+    for (size_t i = 0; i < b.size(); ++i) out[i] = b[i];
+    return (int)b.size();
+}
+
+// The device bytes an engine of this config allocates for what the config alone sizes (include/q3tts.h, "memory"): the two transformers'
+// weights and caches, the per-slot decode state, the lane's and the prefill's rows and scratch, the vocoder's per-slot state. A lower
+// bound of the real total (tables, the vocoder's weights and work buffers, RoPE tables are left out): it refuses only what cannot fit.
+static unsigned long long tfm_weight_bytes(int L, int d, int Hq, int Hkv, int hd, int F, int head_n, int q8) {
+    const unsigned long long per = (unsigned long long)d * (Hq + 2 * Hkv) * hd + (unsigned long long)Hq * hd * d + 3ull * d * F;
+    const unsigned long long n = per * L + (unsigned long long)head_n * d;
+    return q8 ? n + n / 16 : 2 * n;  // Q8_0: 34 bytes per 32 weights
+}
+static unsigned long long engine_footprint(const q3tts_engine_config& c) {
+    const q3tts_model_config& m = c.model;
+    const unsigned long long B = c.max_batch, nctx = c.n_ctx, cap = c.max_steps_cap;
+    unsigned long long t = tfm_weight_bytes(m.t_n_layer, m.t_d_model, m.t_n_head, m.t_n_kv_head, m.t_head_dim, m.t_d_ffn, m.t_vocab, c.talker_q8_0) +
+                           tfm_weight_bytes(m.p_n_layer, m.p_d_model, m.p_n_head, m.p_n_kv_head, m.p_head_dim, m.p_d_ffn, (m.n_codebooks - 1) * m.codebook_size, c.predictor_q8_0);
+    t += B * 2ull * m.t_n_layer * m.t_n_kv_head * m.t_head_dim * nctx * 2;  // Talker KV
+    t += B * 2ull * m.p_n_layer * m.p_n_kv_head * m.p_head_dim * 64 * 2;    // Predictor cache (64 positions, one frame)
+    t += B * cap * 4ull * (m.n_codebooks + 1 + (m.n_codebooks - 1));        // codes, rng, prng
+    t += B * 4ull * ((m.sample_limit + 31) / 32 + cap + 2ull * m.t_vocab + 2ull * m.t_d_model);  // seen, streamed text ids, the parked and the lane's logits / rows
+    const unsigned long long nqkv = std::max((m.t_n_head + 2 * m.t_n_kv_head) * m.t_head_dim, (m.p_n_head + 2 * m.p_n_kv_head) * m.p_head_dim);
+    const unsigned long long nq = std::max(m.t_n_head * m.t_head_dim, m.p_n_head * m.p_head_dim), F = std::max(m.t_d_ffn, m.p_d_ffn);
+    t += 2 * B * (4 * nqkv + 2 * nq + 2 * F) + B * 6ull * m.t_d_model + 2 * B * 6ull * m.p_d_model;  // lane scratch and rows
+    t += nctx * (4ull * (m.t_n_head + 2 * m.t_n_kv_head) * m.t_head_dim + 2ull * m.t_n_head * m.t_head_dim + 2ull * m.t_d_ffn + 6ull * m.t_d_model);  // prefill scratch and rows
+    if (c.with_vocoder) {
+        const q3tts_vocoder_config& v = c.vocoder;
+        unsigned long long spf = 1;
+        for (int i = 0; i < v.n_upsample; ++i) spf *= v.upsample_ratios[i];
+        for (int i = 0; i < v.n_dec_blocks; ++i) spf *= v.dec_rates[i];
+        t += B * cap * spf * 4;                                                           // PCM rows
+        t += B * 2ull * v.n_layer * v.sliding_window * v.n_head * v.head_dim * 4;        // attention rings
+    }
+    return t;
+}
+
+extern "C" int q3tts_k_engine_footprint(const q3tts_engine_config* cfg, int64_t* bytes) {
+    std::string why;
+    if (!cfg || !bytes) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    if (validate(*cfg, why) != Q3TTS_OK) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, why);
+    *bytes = (int64_t)engine_footprint(*cfg);
+    return Q3TTS_OK;
+}
+
 // Zero-filled device memory. The fill has COMPLETED when the pointer is handed out: an upload on any stream (the null stream, the
 // vocoder stream, a caller's) can never be overtaken by it. (Rounds 1 and 2 filled asynchronously on e->stream, a non-blocking stream,
 // and patched three call sites whose uploads were zeroed again; the allocator is the one place to close that race.)
@@ -100,7 +160,23 @@ int q3_dev_alloc_zeroed(q3tts_engine* e, void** p, size_t bytes) {
     err = hipMemsetAsync(q, 0, bytes, e->stream);
     if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
     if (err != hipSuccess) { hipFree(q); return q3_set_err(e, Q3TTS_ERR_DEVICE, std::string("hipMemset: ") + hipGetErrorString(err)); }
+    if (e) e->dev_bytes += bytes;
     *p = q;
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_k_bucket_steps(const q3tts_engine* e, int64_t* out, int32_t cap) {
+    if (!e || !out || cap < (int)e->bucket_steps.size()) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bucket steps: null argument or output too small");
+    for (size_t i = 0; i < e->bucket_steps.size(); ++i) out[i] = e->bucket_steps[i].load(std::memory_order_relaxed);
+    return (int)e->bucket_steps.size();
+}
+extern "C" int q3tts_k_prefix_stats(const q3tts_engine* e, int64_t* out2) {
+    if (!e || !out2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    out2[0] = e->kvp_launches.load(std::memory_order_relaxed); out2[1] = e->kvp_group_max.load(std::memory_order_relaxed);
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_k_device_bytes(const q3tts_engine* e, int64_t* bytes) {
+    if (!e || !bytes) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    *bytes = (int64_t)e->dev_bytes;
     return Q3TTS_OK;
 }
 #define TRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
@@ -140,6 +216,16 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
 #define TRYC(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return fail(rc__); } while (0)
 #define HIPC(call) do { hipError_t er__ = (call); if (er__ != hipSuccess) { q3_set_err(e, Q3TTS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(er__)); return fail(Q3TTS_ERR_DEVICE); } } while (0)
     HIPC(hipSetDevice(cfg->device));
+    {   // before the first allocation: what the config sizes against the device's free memory (not a failure half-way through q3_dalloc)
+        size_t free_b = 0, total_b = 0;
+        HIPC(hipMemGetInfo(&free_b, &total_b));
+        const unsigned long long need = engine_footprint(*cfg);
+        if (need > (unsigned long long)free_b) {
+            q3_set_err(e, Q3TTS_ERR_OOM, "engine needs at least " + std::to_string(need) + " bytes of device memory for max_batch = " + std::to_string(cfg->max_batch) +
+                       ", n_ctx = " + std::to_string(cfg->n_ctx) + "; the device has " + std::to_string((unsigned long long)free_b) + " bytes free (fewer slots or a smaller n_ctx)");
+            return fail(Q3TTS_ERR_OOM);
+        }
+    }
     q3_bgemm_prepare();
     if (cfg->talker_q8_0 == 2 || cfg->predictor_q8_0 == 2) q3_bgemm8_prepare();  // kernel attributes: never inside the captures below
     HIPC(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
@@ -203,10 +289,8 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
         HIPC(hipMemcpyAsync(L.row_pos_t, rp.data(), nb * 4, hipMemcpyHostToDevice, s));
         HIPC(hipStreamSynchronize(s));
         TRYC(alloc_scratch(e, L.sc, 2 * nb, nqkv_max, nq_max, F_max));
-        // row buckets: 1, 2, 4, 8, then the multiples of 16 (the GEMM's row tiles are 16 wide: a 48-row step costs 3/4 of a 64-row one)
-        for (int r = 1; r < nb && r < 16; r *= 2) e->buckets.push_back(r);
-        for (int r = 16; r < nb; r += 16) e->buckets.push_back(r);
-        e->buckets.push_back(nb);
+        row_buckets(nb, e->buckets);
+        e->bucket_steps = std::vector<std::atomic<long long>>(e->buckets.size());
         e->cur_bucket = (int)e->buckets.size() - 1;
         e->row_of_slot = sid; e->slot_of_row = sid;
     }
@@ -523,6 +607,7 @@ static int run_chunk(q3tts_engine* e, int CH, float* dev_ms) {
         }
     }
     e->row_steps += (long long)CH * e->buckets[e->cur_bucket];
+    e->bucket_steps[e->cur_bucket].fetch_add(CH, std::memory_order_relaxed);
     Q3_HIP(e, hipEventRecord(L.ev_end, L.stream));
     Q3_HIP(e, hipStreamWaitEvent(s, L.ev_end, 0));
     Q3_HIP(e, hipEventRecord(e->ev3, s));  // the vocoder stream waits on this
@@ -628,17 +713,20 @@ static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
     if (grp.empty()) return Q3TTS_OK;
     std::vector<int> pos(total), slot(total);
     for (const Adm& a : grp) for (int i = 0; i < a.n; ++i) { pos[a.row0 + i] = a.P + i; slot[a.row0 + i] = a.b; }
+    int n_kvp_launch = 0; long long n_prefixed = 0;
     std::vector<int> seg; int seg_max = 0, seg_max_t = 0;  // the same rows as runs: every request's rows are consecutive, positions P .. P + n - 1
     Q3KvPrefix kp{}; kp.kc = e->T.kc; kp.vc = e->T.vc; kp.layer_stride = e->T.layer_stride; kp.n_ctx = e->T.n_ctx; kp.L = e->T.L; kp.Hkv = e->T.Hkv; kp.hd = e->T.hd;
     for (const Adm& a : grp) {
         seg.push_back(a.row0); seg.push_back(a.n); seg.push_back(a.b); seg.push_back(a.P);
         seg_max = std::max(seg_max, a.n); seg_max_t = std::max(seg_max_t, a.P + a.n);
         if (a.P > 0) {
-            if (kp.n == Q3_KVP_MAX) { q3_launch_kv_prefix(kp, s); kp.n = 0; }  // (a group holds at most B <= 64 requests: not reached)
+            if (kp.n == Q3_KVP_MAX) { q3_launch_kv_prefix(kp, s); kp.n = 0; ++n_kvp_launch; }  // the descriptor is full (more than 64 prefixed requests in a group): these copies go now, ahead of the group's layers on the same stream
             const q3tts_prefix* x = a.r->prefix;
-            kp.pk[kp.n] = x->k; kp.pv[kp.n] = x->v; kp.P[kp.n] = x->P; kp.slot[kp.n] = a.b; ++kp.n;
+            kp.pk[kp.n] = x->k; kp.pv[kp.n] = x->v; kp.P[kp.n] = x->P; kp.slot[kp.n] = a.b; ++kp.n; ++n_prefixed;
         }
     }
+    e->kvp_launches.fetch_add(n_kvp_launch + (kp.n > 0 ? 1 : 0), std::memory_order_relaxed);  // (prefill_layers launches the rest)
+    if (n_prefixed > e->kvp_group_max.load(std::memory_order_relaxed)) e->kvp_group_max.store(n_prefixed, std::memory_order_relaxed);
     const int rl = prefill_layers(e, pos, slot, seg, seg_max, seg_max_t, &kp);
     if (rl < 0) return Q3TTS_ERR_DEVICE;
     if (rl) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefill: a kernel launch was refused for this model shape");
@@ -815,7 +903,7 @@ int q3_voc_dispatch(q3tts_engine* e, const char* live, const char* want, int* vo
     // ONE batched call per chunk: every slot with new frames runs nf = 4. A finished utterance whose tail is
     // shorter is padded with throw-away frames: the vocoder is causal, so they cannot change the samples already
     // due, their own samples are never reported, and the slot's vocoder state is reset at its next admission.
-    int list[64], real[64];
+    std::vector<int> list(B), real(B);  // (q3_voc_decode_batch runs more than 64 slots as several calls)
     for (;;) {
         int ns = 0;
         for (int b = 0; b < B; ++b) {
@@ -827,7 +915,7 @@ int q3_voc_dispatch(q3tts_engine* e, const char* live, const char* want, int* vo
         TRY(ensure_wait());
         int still = 0;  // slots that go on decoding while this call runs
         for (int b = 0; b < B; ++b) if (live[b] && e->slots_host[b].active) ++still;
-        TRY(q3_voc_decode_batch(e, list, real, ns, 4, vs, (still > 0 || more) ? 1 : 0));
+        TRY(q3_voc_decode_batch(e, list.data(), real.data(), ns, 4, vs, (still > 0 || more) ? 1 : 0));
         for (int i = 0; i < ns; ++i) { if (voc_frames[list[i]] == 0) *first = true; voc_frames[list[i]] += real[i]; }
     }
     // V4 flush: the reference sends is_last only when its final buffer is not empty, i.e. n_frames % 4 != 0 (src/tts/engine.rs:510-536,

@@ -319,8 +319,8 @@ int step(q3tts_session* s) {
     TRY(q3_voc_dispatch(e, run.data(), run.data(), s->voc_frames.data(), more, &first));
     // 5. every slot's new window [delivered, samples) in one gather launch and one copy
     const Q3Resamp* rs = e->out_rate ? &e->rs_out : nullptr;
-    Q3PcmPack pk{}; Q3PcmSrc src{};
-    int ne = 0, mx = 0;
+    std::vector<Q3PcmEnt> ents; std::vector<int> ent_len; std::vector<char> ent_fin;  // (a gather launch takes Q3_PCM_MAX_ENT entries: more slots, more launches)
+    int ne = 0;
     size_t tot = 0;
     std::vector<SEv> chunks;
     std::vector<int> fin;
@@ -338,9 +338,8 @@ int step(q3tts_session* s) {
             chunks.push_back(v);
         }
         if (c > 0) {
-            src.len[ne] = ns; if (done) src.final_mask |= 1ull << ne;
-            pk.e[ne++] = Q3PcmEnt{b, sl.delivered, c, 0, (long long)tot};
-            mx = std::max(mx, c);
+            ent_len.push_back(ns); ent_fin.push_back(done ? 1 : 0);
+            ents.push_back(Q3PcmEnt{b, sl.delivered, c, 0, (long long)tot}); ++ne;
             tot += (size_t)c; sl.delivered += c;
         }
         if (done) fin.push_back(b);
@@ -349,9 +348,18 @@ int step(q3tts_session* s) {
         const int k = s->ring_next;
         const int rc = take_ring(s, k);
         if (rc) return rc;
-        if (!rs) q3_launch_pcm_pack(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, ne, mx, s->fmt, s->dev, vs);
-        else if (q3_launch_pcm_resample(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, src, ne, mx, *rs, s->fmt, s->dev, vs) != 0)
-            return q3_set_err(e, Q3TTS_ERR_UNSUPPORTED, "session: the resampler's input span does not fit the LDS");
+        for (int g0 = 0; g0 < ne; g0 += Q3_PCM_MAX_ENT) {  // the windows in launches of at most Q3_PCM_MAX_ENT entries, all into the one staging buffer
+            const int n = std::min(ne - g0, (int)Q3_PCM_MAX_ENT);
+            Q3PcmPack pk{}; Q3PcmSrc src{};
+            int mx = 0;
+            for (int i = 0; i < n; ++i) {
+                pk.e[i] = ents[g0 + i]; src.len[i] = ent_len[g0 + i]; mx = std::max(mx, ents[g0 + i].count);
+                if (ent_fin[g0 + i]) src.final_mask |= 1ull << i;
+            }
+            if (!rs) q3_launch_pcm_pack(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, n, mx, s->fmt, s->dev, vs);
+            else if (q3_launch_pcm_resample(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, src, n, mx, *rs, s->fmt, s->dev, vs) != 0)
+                return q3_set_err(e, Q3TTS_ERR_UNSUPPORTED, "session: the resampler's input span does not fit the LDS");
+        }
         Q3_HIP(e, hipGetLastError());
         Q3_HIP(e, hipMemcpyAsync(s->host[k], s->dev, tot * s->es, hipMemcpyDeviceToHost, vs));
         Q3_HIP(e, hipEventRecord(s->ev[k], vs));

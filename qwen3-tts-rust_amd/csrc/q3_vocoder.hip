@@ -1921,12 +1921,17 @@ int q3_voc_decode(q3tts_engine* e, int slot, int f0, int nf, int is_last, hipStr
 int q3_voc_decode_batch(q3tts_engine* e, const int* slots, const int* real, int ns, int nf, hipStream_t s, int beside_decoder) {
     Q3Voc* v = e->voc;
     if (!v) return q3_set_err(e, Q3TTS_ERR_STATE, "engine has no vocoder");
-    if (ns <= 0 || ns > VOC_MAX_NS || nf <= 0 || nf > VOC_FCAP) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder batch shape");
-    VCall cl; memset(&cl, 0, sizeof(cl));
-    cl.ns = ns; cl.nf = nf;
-    for (int i = 0; i < ns; ++i) { cl.slot[i] = slots[i]; cl.pos[i] = v->frames_done[slots[i]]; }
-    VTRY(voc_call(e, cl, s, beside_decoder && ns >= 16));  // (fewer slots: few and short-lived workgroups — greedy launches, the least latency)
-    for (int i = 0; i < ns; ++i) v->frames_done[slots[i]] += real ? real[i] : nf;
+    if (ns <= 0 || ns > v->B || nf <= 0 || nf > VOC_FCAP) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder batch shape");
+    // More than VOC_MAX_NS slots (engines of more than 64): calls of at most VOC_MAX_NS slots each, back to back on the stream. The work
+    // buffers and the descriptor keep their size; a slot's samples do not depend on the slots it shares a call with.
+    for (int g0 = 0; g0 < ns; g0 += VOC_MAX_NS) {
+        const int n = std::min(ns - g0, VOC_MAX_NS);
+        VCall cl; memset(&cl, 0, sizeof(cl));
+        cl.ns = n; cl.nf = nf;
+        for (int i = 0; i < n; ++i) { cl.slot[i] = slots[g0 + i]; cl.pos[i] = v->frames_done[slots[g0 + i]]; }
+        VTRY(voc_call(e, cl, s, beside_decoder && n >= 16));  // (fewer slots: few and short-lived workgroups — greedy launches, the least latency)
+        for (int i = g0; i < g0 + n; ++i) v->frames_done[slots[i]] += real ? real[i] : nf;  // per group: a later group's failure leaves host and device agreeing on the earlier ones
+    }
     return Q3TTS_OK;
 }
 void q3_voc_mark_last(q3tts_engine* e, int slot) { if (e->voc) e->voc->last_flag[slot] = 1; }
@@ -2032,7 +2037,7 @@ extern "C" int q3tts_k_vocoder_bench(q3tts_engine* e, int32_t n_slots, int32_t c
     Q3_NOT_IN_SESSION(e);
     if (!e || !ms_per_chunk || n_slots <= 0 || chunks <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder bench: bad argument");
     if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "engine created with with_vocoder = 0");
-    if (n_slots > e->B || n_slots > VOC_MAX_NS || (chunks + 2) * 4 > e->cfg.max_steps_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder bench: shape exceeds the engine's");
+    if (n_slots > e->B || (chunks + 2) * 4 > e->cfg.max_steps_cap) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder bench: shape exceeds the engine's");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     const int ncb = e->cfg.model.n_codebooks, cap = e->cfg.max_steps_cap, cbs = e->cfg.vocoder.codebook_size;
     hipStream_t s = e->stream;

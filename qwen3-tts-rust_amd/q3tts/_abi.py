@@ -161,6 +161,7 @@ SYMBOLS = [
     "q3tts_session_append_text", "q3tts_k_text_ready",
     "q3tts_k_attention_runs", "q3tts_k_attention_decode_ex", "q3tts_k_attention_pair", "q3tts_k_attend_pick",
     "q3tts_k_pred_table_row", "q3tts_k_pred_next", "q3tts_k_attention_gather",
+    "q3tts_k_row_buckets", "q3tts_k_bucket_steps", "q3tts_k_device_bytes", "q3tts_k_engine_footprint", "q3tts_k_prefix_stats",
 ]
 
 
@@ -315,6 +316,11 @@ def load_library(path=None):
     lib.q3tts_k_attend_policy.argtypes = [C.c_int32, C.c_int32]
     lib.q3tts_k_bgemm_pick.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
     lib.q3tts_k_alloc_upload.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.q3tts_k_row_buckets.argtypes = [C.c_int32, i32p, C.c_int32]
+    lib.q3tts_k_bucket_steps.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]
+    lib.q3tts_k_device_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.q3tts_k_prefix_stats.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.q3tts_k_engine_footprint.argtypes = [C.POINTER(EngineConfig), C.POINTER(C.c_int64)]
     lib.q3tts_tokenizer_load.argtypes = [C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_int32]
     lib.q3tts_tokenizer_free.argtypes = [vp]
     lib.q3tts_tokenizer_free.restype = None

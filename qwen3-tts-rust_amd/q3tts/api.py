@@ -133,11 +133,12 @@ class TtsEngine:
         self.sampler_config = SamplerConfig()
 
     @classmethod
-    def new(cls, model_dir: Optional[str] = None, quant: str = "none", config=None):
+    def new(cls, model_dir: Optional[str] = None, quant: str = "none", config=None, max_batch: Optional[int] = None):
         """TtsEngine::new(model_dir, quant) (src/tts/engine.rs:84-169). With no config the model's shape comes from the GGUF files of the
         quant directory (q3tts_config_from_model_dir), whatever member of the family it holds; a config given by the caller is used as it
         is (its shapes must match the files) and is not modified. There is no network here: with no weight container under model_dir the
-        engine uses seeded synthetic weights of the configured (default: 1.7B) shape."""
+        engine uses seeded synthetic weights of the configured (default: 1.7B) shape. max_batch (1..256): the engine's slot count, in
+        place of the config's (include/q3tts.h states the memory per slot; 256 slots of the 1.7B shape need n_ctx <= 1024 or so)."""
         wdir = None
         if model_dir:
             quant_dir = {"q5_k_m": "gguf_q5_k_m", "q8_0": "gguf_q8_0"}.get(quant, "gguf")  # src/tts/engine.rs:91-95
@@ -154,6 +155,8 @@ class TtsEngine:
             cfg = _abi.default_config()
         if quant == "q8_0" and not cfg.talker_q8_0:
             cfg.talker_q8_0 = 2   # the gguf_q8_0 directory is multiplied as llama.cpp multiplies it: Q8_0 x Q8_0 (W8A8)
+        if max_batch is not None:
+            cfg.max_batch = int(max_batch)
         tok = load_tokenizer(model_dir) if model_dir else None
         eng = cls(cfg, tok)
         for d in ([os.path.join(model_dir, "preset_speakers")] if model_dir else []) + ["speakers"]:  # :156-166

@@ -256,6 +256,30 @@ class NativeEngine:
         self._check(self.lib.q3tts_k_vocoder_bench(self.h, n_slots, chunks, C.byref(ms)), "q3tts_k_vocoder_bench")
         return ms.value
 
+    def row_buckets(self):
+        """The engine's row buckets (q3tts_k_row_buckets of its max_batch)."""
+        return row_buckets(self.cfg.max_batch)
+
+    def bucket_steps(self):
+        """{bucket rows: frame steps run on it since the engine was created} (q3tts_k_bucket_steps)."""
+        out = (C.c_int64 * 32)()
+        n = self.lib.q3tts_k_bucket_steps(self.h, out, 32)
+        if n < 0:
+            raise _abi.Q3Error("q3tts_k_bucket_steps failed")
+        return dict(zip(self.row_buckets(), [int(out[i]) for i in range(n)]))
+
+    def prefix_stats(self):
+        """(k_kv_prefix launches since creation, the most prefixed requests one prefill group has held) — q3tts_k_prefix_stats."""
+        o = (C.c_int64 * 2)()
+        self._check(self.lib.q3tts_k_prefix_stats(self.h, o), "q3tts_k_prefix_stats")
+        return int(o[0]), int(o[1])
+
+    def device_bytes(self):
+        """Device bytes the engine's allocator has handed out (q3tts_k_device_bytes)."""
+        b = C.c_int64(0)
+        self._check(self.lib.q3tts_k_device_bytes(self.h, C.byref(b)), "q3tts_k_device_bytes")
+        return int(b.value)
+
     def timings(self):
         t = _abi.Timings()
         self._check(self.lib.q3tts_get_timings(self.h, C.byref(t)), "q3tts_get_timings")
@@ -496,6 +520,24 @@ class NativeSession:
 
 
 # ---- kernel-level hooks (host arrays in / out) -------------------------------------------------
+
+def engine_footprint(cfg):
+    """q3tts_k_engine_footprint: the device bytes q3tts_engine_create checks against the free memory for cfg (needs no GPU)."""
+    b = C.c_int64(0)
+    rc = _abi.load_library().q3tts_k_engine_footprint(C.byref(cfg), C.byref(b))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_engine_footprint failed ({rc}): {_abi.load_library().q3tts_last_error(None).decode()}")
+    return int(b.value)
+
+
+def row_buckets(max_batch):
+    """q3tts_k_row_buckets: the row buckets of an engine with max_batch slots (needs no GPU). Raises Q3Error outside 1..256."""
+    out = (C.c_int32 * 32)()
+    n = _abi.load_library().q3tts_k_row_buckets(max_batch, out, 32)
+    if n < 0:
+        raise _abi.Q3Error(f"q3tts_k_row_buckets({max_batch}) failed ({n})")
+    return [int(out[i]) for i in range(n)]
+
 
 class NativeNode:
     """q3tts_node_*: one engine + one host thread per listed GPU inside the library, requests sharded by index (i mod G), the PCM of a
