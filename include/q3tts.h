@@ -91,7 +91,8 @@ typedef struct q3tts_engine_config {
     int32_t device;        /* HIP device ordinal */
     int32_t max_batch;     /* concurrent utterance slots, 1..Q3TTS_MAX_BATCH (256). Results do not depend on it. Device memory per slot:
                             *   Talker KV  2 * t_n_layer * t_n_kv_head * t_head_dim * n_ctx * 2 B  (470 MB at the 1.7B shape with n_ctx = 4096:
-                            *              256 slots need a smaller n_ctx, e.g. 1024: 117 MB per slot, 30 GB)
+                            *              256 slots need a smaller n_ctx, e.g. 1024: 117 MB per slot, 30 GB); with kv_q8_0 = 1
+                            *              2 * t_n_layer * t_n_kv_head * n_ctx * (t_head_dim + 2 * t_head_dim / 32) B (250 MB at n_ctx = 4096)
                             *   Predictor cache  2 * p_n_layer * p_n_kv_head * p_head_dim * 64 * 2 B
                             *   codes, Talker draws  max_steps_cap * (n_codebooks + 1) * 4 B;  Predictor draws (prng)  max_steps_cap *
                             *              (n_codebooks - 1) * 4 B;  seen codes  ceil(sample_limit / 32) * 4 B
@@ -143,6 +144,26 @@ typedef struct q3tts_engine_config {
                                * 1 (W8A16 for the Predictor) is refused with Q3TTS_ERR_UNSUPPORTED; the numbering is parallel to talker_q8_0.
                                * Independent of talker_q8_0: any Talker mode combines with any Predictor mode. Opt-in: no API default
                                * selects it. */
+    int32_t kv_q8_0;          /* NOTE for callers built against an earlier header: this member takes what was the struct's tail padding
+                               * (sizeof is unchanged), so a struct filled member by member without q3tts_default_config or
+                               * zero-initialisation hands indeterminate bytes over here — Q3TTS_ERR_INVALID, or silently a Q8_0 cache.
+                               * Start every q3tts_engine_config from q3tts_default_config (or zero it) before setting members.
+                               * 0 (default): the Talker's K/V cache is bf16 — no bit, launch, graph or allocation differs from an engine built
+                               * before this field existed. 1: the Talker's K and V are ggml Q8_0 blocks on the device (llama.cpp's
+                               * --cache-type-k q8_0 --cache-type-v q8_0): per-slot memory becomes 2 * t_n_layer * t_n_kv_head * n_ctx *
+                               * (t_head_dim + 2 * t_head_dim / 32) bytes, 0.53 of bf16. Any other value: Q3TTS_ERR_INVALID. The
+                               * Predictor's per-frame cache (17 keys) stays bf16. Independent of talker_q8_0 and predictor_q8_0.
+                               * Blocks: 32 consecutive dims of one (position, KV head) vector — four per key, taken after q/k-norm and
+                               * RoPE, four per value, taken from the raw f32 row. Quantiser: ggml's quantize_row_q8_0 in f32 (d = amax /
+                               * 127, id = d ? 1 / d : 0, q = roundf(x * id), d stored as f16; a zero block has d = 0, q = 0).
+                               * Arithmetic rule: the cached value is x^ = f32(d) * float(q), exact in f32, and attention is the
+                               * canonical order of DESIGN.md section 4.4 unchanged with x^ wherever it has a bf16 value today — the same
+                               * key-per-lane d-ascending fmaf score chain, the same 16 key-partials of the value pass, the same
+                               * combination and expf. The newest key and value take part as x^ too, never as the unquantised row, so a
+                               * row sees the same keys whether it was decoded or prefilled, and every kernel variant gives the same bits.
+                               * The results are NOT those of the bf16 cache (ids may differ). Parity with llama.cpp's flash-attention
+                               * summation order is not pinned, as for the W8A8 GEMMs. Voice prefixes are stored in the engine's format.
+                               * A model shape the Q8_0-cache kernels cannot run: Q3TTS_ERR_UNSUPPORTED at q3tts_engine_create. */
 } q3tts_engine_config;
 
 typedef struct q3tts_engine q3tts_engine;
@@ -583,6 +604,24 @@ int q3tts_k_attention_pair(int32_t device, const float* qkv, int32_t n_slots, in
  * k_attend<2 / 4, true>; 5: k_attend_gqa2; 6: k_attend_small<2>; 7: k_attend_pair; 8: k_attend_prefill; -1: the launcher refuses. */
 int q3tts_k_attend_pick(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t,
                         int32_t n_kv_head, int32_t* kernel);
+/* ---- the same over a Q8_0 cache (q3tts_engine_config.kv_q8_0; csrc/q3_attend_kv8.hip) ----
+ * q3tts_k_attention_runs / q3tts_k_attention_decode_ex (without row_indexed) with the launch's cache in Q8_0 blocks: the quantising append
+ * k_qk_prep_kv8 for the rows that are only cached, then ONE launch through the engine's launcher. The cache comes back un-blocked:
+ * k_q / v_q int8 [slot][n_kv_head][n_ctx][hd], k_d / v_d f16 bits [slot][n_kv_head][n_ctx][hd / 32] (each optional). Arguments are
+ * checked on the host as above. */
+int q3tts_k_attention_runs_kv8(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx,
+                               int32_t n_head, int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
+                               float rope_theta, const int32_t* mrope_sections, int32_t policy, int32_t out_form, void* out, float* out_scale,
+                               int8_t* k_q, int8_t* v_q, uint16_t* k_d, uint16_t* v_d);
+int q3tts_k_attention_decode_kv8(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t n_head,
+                                 int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
+                                 float rope_theta, const int32_t* mrope_sections, int32_t policy, int32_t out_form, void* out,
+                                 float* out_scale, int8_t* k_q, int8_t* v_q, uint16_t* k_d, uint16_t* v_d);
+/* Host only: q3tts_k_attend_pick for a launch over a Q8_0 cache. *kernel = 9 / 10 / 11: k_attend_kv8<1 / 2 / 4, false>; 12 / 13:
+ * k_attend_kv8<2 / 4, true>; 14: k_attend_gqa2_kv8 (decode policy 0; policy 1 gives 12); -1: the launcher refuses (fused = 2, a fused
+ * launch with one query head per KV head, a GQA ratio outside 1, 2, 4). Never 0 .. 8: there is no Q8 form of k_attend_prefill. */
+int q3tts_k_attend_pick_kv8(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t,
+                            int32_t n_kv_head, int32_t* kernel);
 /* ---- the Predictor's layer-0 QKV table ----
  * With a bf16 Predictor and greedy heads, block 0 of passes q = 1 .. n_codebooks - 2 reads its raw q / k / v from a table built at engine
  * creation (one row per (q, code), + one fallback row per q for a code outside [0, codecq_rows)) instead of launching k_pred_next(q) and

@@ -17,47 +17,8 @@ __device__ __forceinline__ uint16_t* k_cache_elem(uint16_t* khead, int pos, int 
     const int blk = pos >> 6, kl = pos & 63, c = lane >> 1, e0 = 4 * (lane & 1);
     return khead + ((size_t)(blk * (Q3_ATT_HD >> 3) + c) * 64 + kl) * 8 + e0;
 }
-// RMSNorm(hd) + RoPE of one head by one wave, the arithmetic in its three steps. Lane (< hd/4) holds its 4 consecutive elements x4, their
-// norm weights w4 and RoPE entries c4 / s4; every other lane holds x4 = 0 (+0 to the sum of squares).
-__device__ __forceinline__ float prep_rinv(const float4 x4, float eps, int hd) {  // 1 / rms of the head
-    float acc = 0.0f;
-    acc = fmaf(x4.x, x4.x, acc); acc = fmaf(x4.y, x4.y, acc); acc = fmaf(x4.z, x4.z, acc); acc = fmaf(x4.w, x4.w, acc);
-    acc = wave_sum(acc);
-    return 1.0f / sqrtf(acc / (float)hd + eps);
-}
-__device__ __forceinline__ void prep_norm(const float4 x4, float rinv, const float4 w4, float y[4]) {
-    y[0] = (x4.x * rinv) * w4.x; y[1] = (x4.y * rinv) * w4.y; y[2] = (x4.z * rinv) * w4.z; y[3] = (x4.w * rinv) * w4.w;
-}
-// RoPE (NeoX pairing i <-> i + hd/2): lanes [0, hd/8) hold the first halves, partner lane = lane ^ (hd/8)
-__device__ __forceinline__ void prep_rope(const float y[4], const float4 c4, const float4 s4, int hl, int lane, float o[4]) {  // hl = hd/8
-    const float cc[4] = {c4.x, c4.y, c4.z, c4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float other = __shfl_xor(y[e], hl);
-        o[e] = (lane < hl) ? fmaf(-other, ss[e], y[e] * cc[e])     // x_i*c - x_{i+half}*s
-                           : fmaf(other, ss[e], y[e] * cc[e]);     // x_{i+half}*c + x_i*s
-    }
-}
-// All three on operands that are already there: kernels that request their operands early (k_attend_gqa2, k_attend_small) call this.
-__device__ __forceinline__ void prep_arith(const float4 x4, const float4 w4, const float4 c4, const float4 s4, float eps, int lane, float o[4]) {
-    float y[4];
-    prep_norm(x4, prep_rinv(x4, eps, Q3_ATT_HD), w4, y);
-    prep_rope(y, c4, s4, Q3_ATT_HD >> 3, lane, o);
-}
-// The same with its loads, each in front of the step that needs it: lanes [0, hd/4) own 4 consecutive elements each; result in o[4]
-__device__ __forceinline__ void prep_head(const float* src, const float* nw, float eps, const float* cs, const float* sn, int hd,
-                                          int lane, float o[4]) {
-    const int nl = hd >> 2, hl = nl >> 1;
-    float4 x4 = (float4){0.f, 0.f, 0.f, 0.f}, w4 = x4, c4 = (float4){1.f, 1.f, 1.f, 1.f}, s4 = x4;
-    if (lane < nl) x4 = ((const float4*)src)[lane];
-    const float rinv = prep_rinv(x4, eps, hd);
-    if (lane < nl) w4 = ((const float4*)nw)[lane];
-    float y[4];
-    prep_norm(x4, rinv, w4, y);
-    const int i0 = 4 * (lane & (hl - 1));
-    if (lane < nl) { c4 = *(const float4*)(cs + i0); s4 = *(const float4*)(sn + i0); }
-    prep_rope(y, c4, s4, hl, lane, o);
-}
+// (prep_rinv / prep_norm / prep_rope / prep_arith / prep_head — RMSNorm + RoPE of one head by one wave — are in q3_kernels.h: the Q8_0-cache
+// kernels of q3_attend_kv8.hip run the same statements)
 // bf16 K (key-interleaved blocks; k_cache_elem's address for a run-time hd) and V (row-major) append of one kv head by lanes [0, hd/4)
 __device__ __forceinline__ void kv_append(uint16_t* kc, uint16_t* vc, size_t hb, int hd, int pos, int lane, const float o[4], const float4 vv) {
     const int blk = pos >> 6, kl = pos & 63, c = lane >> 1, e0 = 4 * (lane & 1);
@@ -92,19 +53,7 @@ __device__ __forceinline__ void att_pv8x2(float pa, float pb, const uint4 w, flo
     o1[0] = fmaf(pb, v0, o1[0]); o1[1] = fmaf(pb, v1, o1[1]); o1[2] = fmaf(pb, v2, o1[2]); o1[3] = fmaf(pb, v3, o1[3]);
     o1[4] = fmaf(pb, v4, o1[4]); o1[5] = fmaf(pb, v5, o1[5]); o1[6] = fmaf(pb, v6, o1[6]); o1[7] = fmaf(pb, v7, o1[7]);
 }
-// The attention output in the form Q3Attend.out_bf16 names, for a lane that holds 1 or 2 consecutive dims of `row` from dim `d` of query
-// head `head` on: f32 rows (0), the O projection's A-tiled bf16 operand (1), W8A8 Q8_0 blocks (2: 32 lanes x 1 / 16 lanes x 2, all active).
-__device__ __forceinline__ void att_out1(const Q3Attend& a, int row, int head, int d, float v) {
-    const int col = head * Q3_ATT_HD + d;
-    if (a.out_bf16 == 2) q3_q8_out32(v, row, col, (a.Hq * Q3_ATT_HD) >> 6, a.out_rt16, (int8_t*)a.out, a.out_scale);
-    else if (a.out_bf16) ((uint16_t*)a.out)[q3_atile_off(row, col, (a.Hq * Q3_ATT_HD) >> 5)] = q3_bf16(v);
-    else a.out[(size_t)row * a.ldo + (size_t)head * Q3_ATT_HD + d] = v;
-}
-__device__ __forceinline__ void att_out2(const Q3Attend& a, int row, int head, int d, float v0, float v1) {  // d even: one 4-byte store of the bf16 pair
-    if (a.out_bf16 == 2) q3_q8_out2x16(v0, v1, row, head * Q3_ATT_HD + d, (a.Hq * Q3_ATT_HD) >> 6, a.out_rt16, (int8_t*)a.out, a.out_scale);
-    else if (a.out_bf16) *(uint32_t*)((uint16_t*)a.out + q3_atile_off(row, head * Q3_ATT_HD + d, (a.Hq * Q3_ATT_HD) >> 5)) = (uint32_t)q3_bf16(v0) | ((uint32_t)q3_bf16(v1) << 16);
-    else *(float2*)(a.out + (size_t)row * a.ldo + (size_t)head * Q3_ATT_HD + d) = make_float2(v0, v1);
-}
+// (att_out1 / att_out2 — the attention output in the form Q3Attend.out_bf16 names — are in q3_kernels.h)
 
 // hd stays the run-time a.hd here (the launcher admits only Q3_ATT_HD): with the constant folded in, the kernel traced 80-140 ns per launch
 // slower (4.76 -> 4.84-4.89 us at 31 rows x 24 heads; two runs of the same build differ by 0.02 us)
@@ -128,6 +77,7 @@ __global__ __launch_bounds__(64) void k_qk_prep(Q3QkPrep a) {
     }
 }
 int q3_launch_qk_prep(const Q3QkPrep& a, hipStream_t s) {
+    if (a.kv8) return q3_launch_qk_prep_kv8(a, s);  // Q8_0 cache: the quantising append of q3_attend_kv8.hip
     if (a.hd != Q3_ATT_HD) return 1;
     hipLaunchKernelGGL(k_qk_prep, dim3(a.rows, a.Hq + a.Hkv), dim3(64), 0, s, a);
     return 0;
@@ -140,20 +90,7 @@ int q3_launch_qk_prep(const Q3QkPrep& a, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------------
 // FUSED (one row per slot, e.g. every decode step): the workgroup first does the q/k RMSNorm + RoPE + KV append of
 // its own row (k_qk_prep's work) and serves the newest key/value from LDS, saving one launch per layer.
-// its dynamic LDS, offsets in floats (the kernel and q3_launch_attend both ask here)
-struct AttLds { size_t qh, ow, lw, mw, kh, vh, bytes; };
-Q3_HD AttLds att_lds(int R, int n_ctx) {
-    constexpr int hd = Q3_ATT_HD;
-    AttLds L;
-    L.qh = (size_t)R * n_ctx;       // [R][n_ctx] scores / probabilities in front of it; qh: [R][hd] the query heads
-    L.ow = L.qh + R * hd;           // [R][4][hd] per-wave value sums
-    L.lw = L.ow + R * 4 * hd;       // [R][4] per-wave weight sums
-    L.mw = L.lw + R * 4;            // [R][4] per-wave score maxima
-    L.kh = L.mw + R * 4;            // [hd] newest key (the cache's packed bf16 form in the first half), FUSED only
-    L.vh = L.kh + hd;               // [hd] newest value (bf16-rounded), FUSED only
-    L.bytes = (L.vh + hd) * sizeof(float);
-    return L;
-}
+// its dynamic LDS: AttLds / att_lds of q3_kernels.h (the kernel and q3_launch_attend both ask there)
 template <int R, bool FUSED>
 __global__ __launch_bounds__(R * 256) void k_attend(Q3Attend a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -897,6 +834,7 @@ static hipError_t att_allow_lds(const void* kernel, size_t lds) { return hipFunc
 // or the pair kernel for another ratio than 2.
 int q3_attend_pick(const Q3Attend& a) {
     att_policy_init();
+    if (a.kv8) return q3_attend_pick_kv8(a);  // Q8_0 cache: one of the six kernels of q3_attend_kv8.hip, never one of the nine below
     if (a.hd != Q3_ATT_HD || a.Hkv <= 0 || a.Hq % a.Hkv) return Q3_ATT_REFUSED;
     const int R = a.Hq / a.Hkv;
     if ((R != 1 && R != 2 && R != 4) || (a.fused && R == 1) || (a.fused == 2 && R != 2)) return Q3_ATT_REFUSED;
@@ -917,6 +855,7 @@ int q3_attend_pick(const Q3Attend& a) {
 
 // 0: launched. Nonzero: refused, nothing launched — a shape q3_attend_pick refuses, or a device that refuses the LDS size.
 int q3_launch_attend(const Q3Attend& a, hipStream_t s) {
+    if (a.kv8) return q3_launch_attend_kv8(a, s);
     const int pick = q3_attend_pick(a);
     if (pick == Q3_ATT_REFUSED) return 1;
     const int R = a.Hq / a.Hkv;
@@ -989,5 +928,6 @@ __global__ __launch_bounds__(256) void k_kv_prefix(Q3KvPrefix a) {
 }
 void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s) {
     if (a.n <= 0) return;
+    if (a.kv8) { q3_launch_kv_prefix_kv8(a, s); return; }
     hipLaunchKernelGGL(k_kv_prefix, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
 }

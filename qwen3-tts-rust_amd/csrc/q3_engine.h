@@ -30,6 +30,9 @@ struct Q3Tfm {
     bool a8 = false;  // cfg.talker_q8_0 = 2 / cfg.predictor_q8_0 = 2: the GEMMs' ACTIVATIONS are Q8_0 blocks as well (W8A8, q3_bgemm8.hip): every operand buffer then holds int8 quants + f32 block scales (11-bit significand: q3_q8_sig11)
     uint16_t *kc = nullptr, *vc = nullptr;  // [L][slots][Hkv][n_ctx*hd]
     size_t layer_stride = 0;
+    // cfg.kv_q8_0 (the Talker only): the cache is ggml Q8_0 blocks — kc / vc hold int8 quants (layer_stride BYTES per layer) and
+    // kd / vd the f16 block scales [L][slots][Hkv][n_ctx*hd/32], which follow the quants in the same allocation. q3_layer_cache does the arithmetic.
+    bool kv8 = false; uint16_t *kd = nullptr, *vd = nullptr;
     int n_ctx = 0, n_slots = 0;
     float *cs = nullptr, *sn = nullptr;  // RoPE tables [n_ctx][hd/2]
     size_t weight_bytes = 0;              // bf16 matrix bytes of all layers + head
@@ -158,7 +161,7 @@ struct q3tts_engine {
 struct q3tts_prefix {
     q3tts_engine* e = nullptr;          // the engine that made it (and whose slots it may enter)
     int P = 0, np = 0;
-    uint16_t *k = nullptr, *v = nullptr;
+    uint16_t *k = nullptr, *v = nullptr;  // (kv_q8_0: int8 quants [L][Hkv][np * hd], then their f16 scales [L][Hkv][np * hd / 32])
 };
 
 // helpers shared with q3_vocoder.hip and the kernel-level test hooks (q3_hooks.hip)
@@ -196,7 +199,15 @@ struct Q3TfmShape {
     int L, d, Hq, Hkv, hd, F, head_n;
     float theta; const int* sections;  // RoPE base; M-RoPE sections (null: every dimension rotates)
     int n_ctx, n_slots;       // KV cache: positions per slot, slots
+    int kv8;                  // cfg.kv_q8_0: the cache as Q8_0 blocks
 };
+// layer l's part of t's cache: bf16 elements, or (t.kv8) int8 quants and their scales
+inline void q3_layer_cache(const Q3Tfm& t, int l, uint16_t** kc, uint16_t** vc, uint16_t** kd, uint16_t** vd) {
+    if (t.kv8) {
+        *kc = (uint16_t*)((int8_t*)t.kc + l * t.layer_stride); *vc = (uint16_t*)((int8_t*)t.vc + l * t.layer_stride);
+        *kd = t.kd + l * (t.layer_stride >> 5); *vd = t.vd + l * (t.layer_stride >> 5);
+    } else { *kc = t.kc + l * t.layer_stride; *vc = t.vc + l * t.layer_stride; *kd = *vd = nullptr; }
+}
 // the transformer's weights, KV cache and RoPE tables. g: the opened GGUF `file` (null: seeded synthetic weights);
 // q8mode: cfg.talker_q8_0 / cfg.predictor_q8_0
 int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode);

@@ -54,7 +54,7 @@ extern "C" void q3tts_default_config(q3tts_engine_config* c) {
     v.dec_rates[0] = 8; v.dec_rates[1] = 5; v.dec_rates[2] = 4; v.dec_rates[3] = 3;
     v.lookahead_frames = 0; v.sample_rate = 24000;
     c->device = 0; c->max_batch = 1; c->n_ctx = 4096; c->max_steps_cap = 512; c->with_vocoder = 1;
-    c->synth_seed = 0; c->weights_path = nullptr; c->talker_q8_0 = 0; c->vocoder_flush_tail = 0; c->predictor_q8_0 = 0;
+    c->synth_seed = 0; c->weights_path = nullptr; c->talker_q8_0 = 0; c->vocoder_flush_tail = 0; c->predictor_q8_0 = 0; c->kv_q8_0 = 0;
 }
 
 static int validate(const q3tts_engine_config& c, std::string& why) {
@@ -82,6 +82,7 @@ static int validate(const q3tts_engine_config& c, std::string& why) {
     if (c.talker_q8_0) REQ(m.t_d_model % 512 == 0 && m.t_d_ffn % 512 == 0 && (m.t_n_head * m.t_head_dim) % 512 == 0);  // Q8_0: an even number of 32-blocks per K slice
     if (c.talker_q8_0 == 2) REQ(m.t_vocab % 32 == 0 && ((m.t_n_head + 2 * m.t_n_kv_head) * m.t_head_dim) % 32 == 0 && m.t_d_ffn % 64 == 0);  // W8A8: whole 32-column blocks per workgroup
     REQ(c.predictor_q8_0 >= 0 && c.predictor_q8_0 <= 2);
+    REQ(c.kv_q8_0 == 0 || c.kv_q8_0 == 1);
     if (c.predictor_q8_0 == 2) {  // W8A8 Predictor: an even number of 32-blocks per K slice, whole 32-column blocks per workgroup
         REQ(m.p_d_model % 512 == 0); REQ(m.p_d_ffn % 512 == 0); REQ((m.p_n_head * m.p_head_dim) % 512 == 0);
         REQ(m.codebook_size % 32 == 0); REQ(((m.p_n_head + 2 * m.p_n_kv_head) * m.p_head_dim) % 32 == 0); REQ(m.p_d_ffn % 64 == 0);
@@ -123,7 +124,9 @@ static unsigned long long engine_footprint(const q3tts_engine_config& c) {
     const unsigned long long B = c.max_batch, nctx = c.n_ctx, cap = c.max_steps_cap;
     unsigned long long t = tfm_weight_bytes(m.t_n_layer, m.t_d_model, m.t_n_head, m.t_n_kv_head, m.t_head_dim, m.t_d_ffn, m.t_vocab, c.talker_q8_0) +
                            tfm_weight_bytes(m.p_n_layer, m.p_d_model, m.p_n_head, m.p_n_kv_head, m.p_head_dim, m.p_d_ffn, (m.n_codebooks - 1) * m.codebook_size, c.predictor_q8_0);
-    t += B * 2ull * m.t_n_layer * m.t_n_kv_head * m.t_head_dim * nctx * 2;  // Talker KV
+    // Talker KV: bf16, or (kv_q8_0) Q8_0 blocks — 2 * t_n_layer * t_n_kv_head * n_ctx * (t_head_dim + 2 * t_head_dim / 32) bytes per slot
+    if (c.kv_q8_0) t += B * 2ull * m.t_n_layer * m.t_n_kv_head * nctx * (m.t_head_dim + 2ull * m.t_head_dim / 32);
+    else t += B * 2ull * m.t_n_layer * m.t_n_kv_head * m.t_head_dim * nctx * 2;
     t += B * 2ull * m.p_n_layer * m.p_n_kv_head * m.p_head_dim * 64 * 2;    // Predictor cache (64 positions, one frame)
     t += B * cap * 4ull * (m.n_codebooks + 1 + (m.n_codebooks - 1));        // codes, rng, prng
     t += B * 4ull * ((m.sample_limit + 31) / 32 + cap + 2ull * m.t_vocab + 2ull * m.t_d_model);  // seen, streamed text ids, the parked and the lane's logits / rows
@@ -205,6 +208,20 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     if (validate(*cfg, why) != Q3TTS_OK) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, why);
     if (cfg->predictor_q8_0 == 1)
         return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, "predictor_q8_0 = 1 (Q8_0 weights x bf16 activations) is not implemented for the Predictor: use 0 (bf16) or 2 (Q8_0 x Q8_0)");
+    // what the Q8_0-cache kernels (q3_attend_kv8.hip) cannot run is refused here, not at the first launch. (Today validate() above admits
+    // no such shape — it already holds t_head_dim to 128, the GQA ratio to 1, 2, 4 and n_ctx to whole key blocks for every engine — so this
+    // cannot be reached through the ABI yet; it is the place a wider validate() falls back on. The launcher's own refusals are tested
+    // through q3tts_k_attend_pick_kv8.)
+    if (cfg->kv_q8_0) {
+        const q3tts_model_config& mm = cfg->model;
+        Q3Attend pa{}; pa.kv8 = 1; pa.hd = mm.t_head_dim; pa.Hq = mm.t_n_head; pa.Hkv = mm.t_n_kv_head; pa.n_ctx = cfg->n_ctx;
+        const int R = mm.t_n_head / mm.t_n_kv_head;
+        const bool prefill_ok = q3_attend_pick_kv8(pa) != Q3_ATT_REFUSED;
+        pa.fused = R >= 2 ? 1 : 0;
+        if (!prefill_ok || q3_attend_pick_kv8(pa) == Q3_ATT_REFUSED || mm.t_head_dim % 32 || cfg->n_ctx % 64)
+            return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, "kv_q8_0 = 1: the Q8_0-cache attention kernels need t_head_dim = 128, a GQA ratio of 1, 2 or 4 and n_ctx in whole 64-key blocks; this model has t_head_dim = " +
+                              std::to_string(mm.t_head_dim) + ", ratio " + std::to_string(R) + ", n_ctx = " + std::to_string(cfg->n_ctx));
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, "no HIP device: libq3tts has no CPU fallback");
@@ -222,7 +239,8 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
         const unsigned long long need = engine_footprint(*cfg);
         if (need > (unsigned long long)free_b) {
             q3_set_err(e, Q3TTS_ERR_OOM, "engine needs at least " + std::to_string(need) + " bytes of device memory for max_batch = " + std::to_string(cfg->max_batch) +
-                       ", n_ctx = " + std::to_string(cfg->n_ctx) + "; the device has " + std::to_string((unsigned long long)free_b) + " bytes free (fewer slots or a smaller n_ctx)");
+                       ", n_ctx = " + std::to_string(cfg->n_ctx) + (cfg->kv_q8_0 ? " (Q8_0 cache)" : "") + "; the device has " + std::to_string((unsigned long long)free_b) +
+                       (cfg->kv_q8_0 ? " bytes free (fewer slots or a smaller n_ctx)" : " bytes free (fewer slots, a smaller n_ctx, or kv_q8_0 = 1: the cache in 0.53 of the bytes)"));
             return fail(Q3TTS_ERR_OOM);
         }
     }
@@ -252,10 +270,10 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     std::string er;
     if (!wdir.empty() && (gt.open(wdir + "/qwen3_tts_talker.gguf", er) || gp.open(wdir + "/qwen3_tts_predictor.gguf", er))) { q3_set_err(e, Q3TTS_ERR_INVALID, er); return fail(Q3TTS_ERR_INVALID); }
     TRYC(q3_tfm_init(e, e->T, {.grp = Q3G_TALKER, .L = m.t_n_layer, .d = m.t_d_model, .Hq = m.t_n_head, .Hkv = m.t_n_kv_head, .hd = m.t_head_dim, .F = m.t_d_ffn,
-                               .head_n = m.t_vocab, .theta = m.t_rope_theta, .sections = m.t_mrope_sections, .n_ctx = cfg->n_ctx, .n_slots = B},
+                               .head_n = m.t_vocab, .theta = m.t_rope_theta, .sections = m.t_mrope_sections, .n_ctx = cfg->n_ctx, .n_slots = B, .kv8 = cfg->kv_q8_0},
                      wdir.empty() ? nullptr : &gt, "qwen3_tts_talker.gguf", cfg->talker_q8_0));
     TRYC(q3_tfm_init(e, e->P, {.grp = Q3G_PRED, .L = m.p_n_layer, .d = m.p_d_model, .Hq = m.p_n_head, .Hkv = m.p_n_kv_head, .hd = m.p_head_dim, .F = m.p_d_ffn,
-                               .head_n = (m.n_codebooks - 1) * m.codebook_size, .theta = m.p_rope_theta, .sections = nullptr, .n_ctx = 64, .n_slots = B},
+                               .head_n = (m.n_codebooks - 1) * m.codebook_size, .theta = m.p_rope_theta, .sections = nullptr, .n_ctx = 64, .n_slots = B, .kv8 = 0},
                      wdir.empty() ? nullptr : &gp, "qwen3_tts_predictor.gguf", cfg->predictor_q8_0));
     TRYC(q3_assets_init(e, wdir));
     TRYC(q3_pred_table_init(e));
@@ -716,6 +734,7 @@ static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
     int n_kvp_launch = 0; long long n_prefixed = 0;
     std::vector<int> seg; int seg_max = 0, seg_max_t = 0;  // the same rows as runs: every request's rows are consecutive, positions P .. P + n - 1
     Q3KvPrefix kp{}; kp.kc = e->T.kc; kp.vc = e->T.vc; kp.layer_stride = e->T.layer_stride; kp.n_ctx = e->T.n_ctx; kp.L = e->T.L; kp.Hkv = e->T.Hkv; kp.hd = e->T.hd;
+    kp.kv8 = e->T.kv8 ? 1 : 0; kp.kd = e->T.kd; kp.vd = e->T.vd;
     for (const Adm& a : grp) {
         seg.push_back(a.row0); seg.push_back(a.n); seg.push_back(a.b); seg.push_back(a.P);
         seg_max = std::max(seg_max, a.n); seg_max_t = std::max(seg_max_t, a.P + a.n);
@@ -853,16 +872,18 @@ extern "C" int q3tts_prefix_create(q3tts_engine* e, const q3tts_prompt_desc* p, 
     q3tts_prefix* x = new q3tts_prefix();
     x->e = e; x->P = n; x->np = (n + 63) & ~63;
     const size_t per = (size_t)t.L * t.Hkv * x->np * t.hd;
-    int rc = q3_dev_alloc_zeroed(e, (void**)&x->k, per * 2);
-    if (rc == Q3TTS_OK) rc = q3_dev_alloc_zeroed(e, (void**)&x->v, per * 2);
+    const size_t store = t.kv8 ? per + per / 16 : per * 2;  // the slots' format: bf16, or Q8_0 quants with their f16 scales behind them
+    int rc = q3_dev_alloc_zeroed(e, (void**)&x->k, store);
+    if (rc == Q3TTS_OK) rc = q3_dev_alloc_zeroed(e, (void**)&x->v, store);
     if (rc != Q3TTS_OK) { hipFree(x->k); hipFree(x->v); delete x; return rc; }
     auto fail = [&](int code, const std::string& msg) { hipStreamSynchronize(s); hipFree(x->k); hipFree(x->v); delete x; return q3_set_err(e, code, msg); };
     std::vector<int> pos(n), zero(n, 0);
     for (int i = 0; i < n; ++i) pos[i] = i;
-    uint16_t *kc = t.kc, *vc = t.vc; const size_t ls = t.layer_stride; const int nc = t.n_ctx;
+    uint16_t *kc = t.kc, *vc = t.vc, *kd = t.kd, *vd = t.vd; const size_t ls = t.layer_stride; const int nc = t.n_ctx;
     t.kc = x->k; t.vc = x->v; t.layer_stride = (size_t)t.Hkv * x->np * t.hd; t.n_ctx = x->np;
+    if (t.kv8) { t.kd = (uint16_t*)((int8_t*)x->k + per); t.vd = (uint16_t*)((int8_t*)x->v + per); }
     const int rl = prefill_layers(e, pos, zero, {0, n, 0, 0}, n, n, nullptr);
-    t.kc = kc; t.vc = vc; t.layer_stride = ls; t.n_ctx = nc;
+    t.kc = kc; t.vc = vc; t.kd = kd; t.vd = vd; t.layer_stride = ls; t.n_ctx = nc;
     if (rl < 0) return fail(Q3TTS_ERR_DEVICE, std::string(e->err));
     if (rl) return fail(Q3TTS_ERR_INVALID, "prefix: a kernel launch was refused for this model shape");
     hipError_t er = hipGetLastError();

@@ -217,7 +217,8 @@ extern "C" int q3tts_k_attention_decode(int32_t device, const float* qkv, int32_
 // (0: f32 rows; 1: the A-tiled bf16 operand; 2: Q8_0 blocks + f32 block scales), the read-back in natural order and the un-blocked cache.
 struct AttHook {
     int n_slots = 0, n_ctx = 0, Hq = 0, Hkv = 0, ld = 0, nq = 0, form = 0, out_rows = 0, rt16 = 0;
-    DevBuf qn, kn, cs, sn, kc, vc, out, osc;
+    int kv8 = 0;  // the cache as Q8_0 blocks (the _kv8 hooks; set before init): kc / vc then hold int8 quants, kd / vd their f16 scales
+    DevBuf qn, kn, cs, sn, kc, vc, kd, vd, out, osc;
     // the arguments every attention hook checks before anything is allocated or launched
     static const char* check(const float* qkv, int n_slots, int n_ctx, int Hq, int Hkv, int hd, const float* qnw, const float* knw, int form, const void* out,
                              const float* out_scale) {
@@ -238,8 +239,9 @@ struct AttHook {
         std::vector<float> c, s;
         q3_rope_tables(n_ctx, Q3_ATT_HD, theta, sections, c, s);
         TRY(qn.put(qnw, Q3_ATT_HD * 4)); TRY(kn.put(knw, Q3_ATT_HD * 4)); TRY(cs.put(c.data(), c.size() * 4)); TRY(sn.put(s.data(), s.size() * 4));
-        const size_t cache = (size_t)n_slots * Hkv * n_ctx * Q3_ATT_HD * 2;
+        const size_t cache = (size_t)n_slots * Hkv * n_ctx * Q3_ATT_HD * (kv8 ? 1 : 2);
         TRY(kc.alloc(cache)); TRY(vc.alloc(cache));
+        if (kv8) { TRY(kd.alloc(cache / 16)); TRY(vd.alloc(cache / 16)); }
         TRY(out.alloc(form == 0 ? (size_t)rows * nq * 4 : pad16(rows) * nq * (form == 1 ? 2 : 1)));
         if (form == 2) TRY(osc.alloc((size_t)(nq / 32 + 2) * pad16(rows) * 4));
         return Q3TTS_OK;
@@ -247,11 +249,13 @@ struct AttHook {
     Q3QkPrep prep(float* rows_dev, int rows, float eps) const {
         Q3QkPrep qp{}; qp.qkv = rows_dev; qp.ld = ld; qp.rows = rows; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = Q3_ATT_HD; qp.qnw = qn; qp.knw = kn; qp.eps = eps;
         qp.cs = cs; qp.sn = sn; qp.kc = kc; qp.vc = vc; qp.n_ctx = n_ctx;
+        if (kv8) { qp.kv8 = 1; qp.kd = kd; qp.vd = vd; }
         return qp;
     }
     Q3Attend attend(const float* rows_dev, int rows) const {
         Q3Attend at{}; at.qkv = rows_dev; at.ld = ld; at.rows = rows; at.out = out; at.ldo = nq; at.out_bf16 = form; at.Hq = Hq; at.Hkv = Hkv; at.hd = Q3_ATT_HD;
         at.kc = kc; at.vc = vc; at.n_ctx = n_ctx;
+        if (kv8) { at.kv8 = 1; at.kd = kd; at.vd = vd; }
         if (form == 2) { at.out_scale = osc; at.out_rt16 = rt16; }
         return at;
     }
@@ -282,7 +286,34 @@ struct AttHook {
                     k_host[(h * n_ctx + pos) * hd + d] = t[h * n_ctx * hd + ((size_t)((pos >> 6) * (hd >> 3) + (d >> 3)) * 64 + (pos & 63)) * 8 + (d & 7)];
         return Q3TTS_OK;
     }
+    // the Q8_0 cache of every slot, un-blocked: quants int8 [slot][Hkv][n_ctx][hd], scales f16 bits [slot][Hkv][n_ctx][hd / 32] (each optional)
+    int read_cache_kv8(int8_t* kq_host, int8_t* vq_host, uint16_t* kd_host, uint16_t* vd_host) const {
+        constexpr int hd = Q3_ATT_HD, nb = hd / 32;
+        const size_t n = (size_t)n_slots * Hkv * n_ctx * hd, heads = (size_t)n_slots * Hkv;
+        if (vq_host) TRY(vc.get(vq_host, n));
+        if (vd_host) TRY(vd.get(vd_host, n / 16));
+        if (kq_host) {
+            std::vector<int8_t> t(n);
+            TRY(kc.get(t.data(), n));
+            for (size_t h = 0; h < heads; ++h)
+                for (int pos = 0; pos < n_ctx; ++pos)
+                    for (int d = 0; d < hd; ++d) kq_host[(h * n_ctx + pos) * hd + d] = t[h * n_ctx * hd + q3_kv8_k_off(pos, d)];
+        }
+        if (kd_host) {
+            std::vector<uint16_t> t(n / 32);
+            TRY(kd.get(t.data(), n / 16));
+            for (size_t h = 0; h < heads; ++h)
+                for (int pos = 0; pos < n_ctx; ++pos)
+                    for (int j = 0; j < nb; ++j) kd_host[(h * n_ctx + pos) * nb + j] = t[h * n_ctx * nb + q3_kv8_kd_idx(pos, j)];
+        }
+        return Q3TTS_OK;
+    }
 };
+// what a hook hands back of the cache: bf16 bits (k16 / v16), or with kv8 the quants and scales
+struct AttCacheOut { int kv8 = 0; uint16_t *k16 = nullptr, *v16 = nullptr; int8_t *kq = nullptr, *vq = nullptr; uint16_t *kd = nullptr, *vd = nullptr; };
+static int att_read_cache(const AttHook& h, const AttCacheOut& c) {
+    return c.kv8 ? h.read_cache_kv8(c.kq, c.vq, c.kd, c.vd) : h.read_cache(c.k16, c.v16);
+}
 // one attention launch of a hook under a temporary policy (-1: keep), then the device's verdict
 static int att_hook_launch(const char* name, const Q3Attend& at, int decode, int prefill) {
     int old_dec = 0, old_pre = 0;
@@ -300,22 +331,23 @@ static int att_hook_launch(const char* name, const Q3Attend& at, int decode, int
 // Whole prompt runs as admit_group launches them: run i has run_pos0[i] prefix rows (prepared into slot i's cache by k_qk_prep: they stand for
 // a voice prefix) followed by run_n[i] rows; qkv holds run 0's run_pos0[0] + run_n[0] rows, then run 1's, ... The runs' rows go through
 // k_qk_prep and ONE non-fused q3_launch_attend that carries the seg table, seg_max_n and seg_max_t, under prefill policy `policy`.
-extern "C" int q3tts_k_attention_runs(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx, int32_t Hq,
-                                      int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections,
-                                      int32_t policy, int32_t out_form, void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache) {
+static int attention_runs(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx, int32_t Hq,
+                          int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections,
+                          int32_t policy, int32_t out_form, void* out, float* out_scale, const AttCacheOut& cache) {
+    const std::string hook = cache.kv8 ? "attention runs_kv8 hook" : "attention runs hook";   // (the exported entry that was called)
     if (const char* why = AttHook::check(qkv, n_runs, n_ctx, Hq, Hkv, hd, qnw, knw, out_form, out, out_scale))
-        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string("attention runs hook: ") + why);
-    if (!run_n || !run_pos0 || policy < -1 || policy > 2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention runs hook: run tables, prefill policy -1 .. 2");
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": " + why);
+    if (!run_n || !run_pos0 || policy < -1 || policy > 2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": run tables, prefill policy -1 .. 2");
     long long n_pre = 0, n_run = 0;
     int seg_max_n = 0, seg_max_t = 0;
     for (int i = 0; i < n_runs; ++i) {
         if (run_n[i] < 1 || run_pos0[i] < 0 || (long long)run_pos0[i] + run_n[i] > n_ctx)
-            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention runs hook: a run needs n >= 1, pos0 >= 0 and pos0 + n <= n_ctx");
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": a run needs n >= 1, pos0 >= 0 and pos0 + n <= n_ctx");
         n_pre += run_pos0[i]; n_run += run_n[i];
         seg_max_n = std::max(seg_max_n, run_n[i]); seg_max_t = std::max(seg_max_t, run_pos0[i] + run_n[i]);
     }
     HK(hipSetDevice(device));
-    AttHook h;
+    AttHook h; h.kv8 = cache.kv8;
     TRY(h.init(n_runs, n_ctx, Hq, Hkv, qnw, knw, theta, sections, out_form, (int)n_run));
     const int ld = h.ld;
     std::vector<float> pre((size_t)std::max<long long>(n_pre, 1) * ld), run((size_t)n_run * ld);
@@ -334,34 +366,48 @@ extern "C" int q3tts_k_attention_runs(int32_t device, const float* qkv, int32_t 
     TRY(drp.put(rp.data(), rp.size() * 4)); TRY(drs.put(rs.data(), rs.size() * 4)); TRY(dseg.put(seg.data(), seg.size() * 4));
     if (n_pre) {
         Q3QkPrep qp = h.prep(dpre, (int)n_pre, eps); qp.row_pos = dpp; qp.row_slot = dps;
-        if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention runs hook: the q/k prep launch was refused");
+        if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": the q/k prep launch was refused");
     }
     Q3QkPrep qp = h.prep(drun, (int)n_run, eps); qp.row_pos = drp; qp.row_slot = drs;
-    if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention runs hook: the q/k prep launch was refused");
+    if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": the q/k prep launch was refused");
     Q3Attend at = h.attend(drun, (int)n_run); at.row_pos = drp; at.row_slot = drs;
     at.seg = dseg; at.n_seg = n_runs; at.seg_max_n = seg_max_n; at.seg_max_t = seg_max_t;
-    TRY(att_hook_launch("attention runs hook", at, -1, policy));
+    TRY(att_hook_launch(hook.c_str(), at, -1, policy));
     TRY(h.read_out(out, out_scale));
-    return h.read_cache(k_cache, v_cache);
+    return att_read_cache(h, cache);
+}
+extern "C" int q3tts_k_attention_runs(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx, int32_t Hq,
+                                      int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections,
+                                      int32_t policy, int32_t out_form, void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache) {
+    AttCacheOut c; c.k16 = k_cache; c.v16 = v_cache;
+    return attention_runs(device, qkv, n_runs, run_n, run_pos0, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, out_form, out, out_scale, c);
+}
+// ... over a Q8_0 cache (kv_q8_0): the same rows, the quantising append, one launch through q3_launch_attend with kv8 set
+extern "C" int q3tts_k_attention_runs_kv8(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx, int32_t Hq,
+                                          int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections,
+                                          int32_t policy, int32_t out_form, void* out, float* out_scale, int8_t* k_q, int8_t* v_q, uint16_t* k_d, uint16_t* v_d) {
+    AttCacheOut c; c.kv8 = 1; c.kq = k_q; c.vq = v_q; c.kd = k_d; c.vd = v_d;
+    return attention_runs(device, qkv, n_runs, run_n, run_pos0, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, out_form, out, out_scale, c);
 }
 
 // q3tts_k_attention_decode with one output form of the three per call, the cache returned, and (row_indexed = 1) the Predictor's addressing:
 // no row tables, slot = row % n_slots, every slot at the same length (pos_const = lens[0] - 1)
-extern "C" int q3tts_k_attention_decode_ex(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq, int32_t Hkv,
-                                           int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, int32_t policy,
-                                           int32_t row_indexed, int32_t out_form, void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache) {
+static int attention_decode_ex(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq, int32_t Hkv,
+                               int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, int32_t policy,
+                               int32_t row_indexed, int32_t out_form, void* out, float* out_scale, const AttCacheOut& cache) {
+    const std::string hook = cache.kv8 ? "attention decode_kv8 hook" : "attention decode_ex hook";
     if (const char* why = AttHook::check(qkv, n_slots, n_ctx, Hq, Hkv, hd, qnw, knw, out_form, out, out_scale))
-        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string("attention decode_ex hook: ") + why);
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": " + why);
     if (!lens || Hq / Hkv < 2 || policy < -1 || policy > 1 || row_indexed < 0 || row_indexed > 1)
-        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode_ex hook: lens, a GQA ratio of 2 or 4, decode policy -1 .. 1, row_indexed 0 / 1");
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": lens, a GQA ratio of 2 or 4, decode policy -1 .. 1, row_indexed 0 / 1");
     long long total = 0;
     for (int s = 0; s < n_slots; ++s) {
-        if (lens[s] < 1 || lens[s] > n_ctx) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode_ex hook: a length outside 1 .. n_ctx");
-        if (row_indexed && lens[s] != lens[0]) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode_ex hook: row-indexed addressing needs equal lengths");
+        if (lens[s] < 1 || lens[s] > n_ctx) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": a length outside 1 .. n_ctx");
+        if (row_indexed && lens[s] != lens[0]) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": row-indexed addressing needs equal lengths");
         total += lens[s];
     }
     HK(hipSetDevice(device));
-    AttHook h;
+    AttHook h; h.kv8 = cache.kv8;
     TRY(h.init(n_slots, n_ctx, Hq, Hkv, qnw, knw, theta, sections, out_form, n_slots));
     const int ld = h.ld, npre = (int)(total - n_slots);
     std::vector<float> pre((size_t)std::max(npre, 1) * ld), last((size_t)n_slots * ld);
@@ -379,16 +425,28 @@ extern "C" int q3tts_k_attention_decode_ex(int32_t device, const float* qkv, int
     TRY(dpp.put(pp.data(), pp.size() * 4)); TRY(dps.put(ps.data(), ps.size() * 4)); TRY(ddp.put(dp.data(), n_slots * 4)); TRY(dds.put(ds.data(), n_slots * 4));
     if (npre) {
         Q3QkPrep qp = h.prep(dpre, npre, eps); qp.row_pos = dpp; qp.row_slot = dps;
-        if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode_ex hook: the q/k prep launch was refused");
+        if (q3_launch_qk_prep(qp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": the q/k prep launch was refused");
     }
     Q3QkPrep dq = h.prep(dlast, n_slots, eps);
     Q3Attend at = h.attend(dlast, n_slots);
     if (row_indexed) { dq.slot_mod = at.slot_mod = n_slots; dq.pos_const = at.pos_const = lens[0] - 1; }
     else { dq.row_pos = at.row_pos = ddp; dq.row_slot = at.row_slot = dds; }
     at.fused = 1; at.prep = dq;
-    TRY(att_hook_launch("attention decode_ex hook", at, policy, -1));
+    TRY(att_hook_launch(hook.c_str(), at, policy, -1));
     TRY(h.read_out(out, out_scale));
-    return h.read_cache(k_cache, v_cache);
+    return att_read_cache(h, cache);
+}
+extern "C" int q3tts_k_attention_decode_ex(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq, int32_t Hkv,
+                                           int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, int32_t policy,
+                                           int32_t row_indexed, int32_t out_form, void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache) {
+    AttCacheOut c; c.k16 = k_cache; c.v16 = v_cache;
+    return attention_decode_ex(device, qkv, n_slots, lens, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, row_indexed, out_form, out, out_scale, c);
+}
+extern "C" int q3tts_k_attention_decode_kv8(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq, int32_t Hkv,
+                                            int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, int32_t policy,
+                                            int32_t out_form, void* out, float* out_scale, int8_t* k_q, int8_t* v_q, uint16_t* k_d, uint16_t* v_d) {
+    AttCacheOut c; c.kv8 = 1; c.kq = k_q; c.vq = v_q; c.kd = k_d; c.vd = v_d;
+    return attention_decode_ex(device, qkv, n_slots, lens, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, 0, out_form, out, out_scale, c);
 }
 
 // The Predictor's pass A: 2 * n_slots rows — row b at position 0, row n_slots + b at position 1 of slot b — in ONE launch with fused = 2 on an
@@ -420,6 +478,16 @@ extern "C" int q3tts_k_attend_pick(int32_t fused, int32_t gqa_ratio, int32_t n_c
         n_kv_head > 4096)
         return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attend pick: bad shape");
     Q3Attend a{}; a.hd = Q3_ATT_HD; a.Hkv = n_kv_head; a.Hq = n_kv_head * gqa_ratio; a.fused = fused; a.n_ctx = n_ctx;
+    if (n_seg > 0) { a.seg = (const int*)16; a.n_seg = n_seg; a.seg_max_n = seg_max_n; a.seg_max_t = seg_max_t; }  // (never dereferenced: nothing is launched)
+    *kernel = q3_attend_pick(a);
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_k_attend_pick_kv8(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t, int32_t n_kv_head,
+                                       int32_t* kernel) {
+    if (!kernel || fused < 0 || fused > 2 || gqa_ratio <= 0 || gqa_ratio > 64 || n_ctx <= 0 || n_seg < 0 || seg_max_n < 0 || seg_max_t < 0 || n_kv_head <= 0 ||
+        n_kv_head > 4096)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attend pick (Q8_0 cache): bad shape");
+    Q3Attend a{}; a.hd = Q3_ATT_HD; a.Hkv = n_kv_head; a.Hq = n_kv_head * gqa_ratio; a.fused = fused; a.n_ctx = n_ctx; a.kv8 = 1;
     if (n_seg > 0) { a.seg = (const int*)16; a.n_seg = n_seg; a.seg_max_n = seg_max_n; a.seg_max_t = seg_max_t; }  // (never dereferenced: nothing is launched)
     *kernel = q3_attend_pick(a);
     return Q3TTS_OK;

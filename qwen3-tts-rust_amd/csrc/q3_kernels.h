@@ -240,6 +240,9 @@ struct Q3QkPrep {
     uint16_t* kc; uint16_t* vc; int n_ctx;  // layer base; per (slot, kv head): n_ctx*hd elements
     const int* row_pos; const int* row_slot;
     int slot_mod, pos_const;  // slot_mod > 0: slot = row % slot_mod, pos = pos_const + row / slot_mod (no loads: the Predictor's per-frame cache is indexed by row)
+    // Q8_0 cache (kv8 = 1; q3_attend_kv8.hip): kc / vc then hold the int8 quants (one byte per element, layouts at q3_kv8_k_off)
+    // and kd / vd the f16 block scales, per (slot, kv head) n_ctx * hd / 32 of them
+    int kv8; uint16_t* kd; uint16_t* vd;
 };
 int q3_launch_qk_prep(const Q3QkPrep& a, hipStream_t s);  // 0: launched; nonzero: refused (hd != Q3_ATT_HD), nothing launched
 
@@ -254,6 +257,7 @@ struct Q3Attend {
     const uint16_t* kc; const uint16_t* vc; int n_ctx;
     const int* row_pos; const int* row_slot;
     int slot_mod, pos_const;  // as in Q3QkPrep
+    int kv8; const uint16_t* kd; const uint16_t* vd;  // Q8_0 cache, as in Q3QkPrep: q3_launch_attend then takes the kernels of q3_attend_kv8.hip
     int fused;        // 1: every slot has exactly one row in this launch -> q/k prep + KV append done in-kernel (R >= 2)
                       // 2: rows b (position 0) and slot_mod + b (position 1) of every slot, nothing cached yet (R == 2): k_attend_pair
     Q3QkPrep prep;    // used when fused
@@ -265,6 +269,87 @@ struct Q3Attend {
     Q3_STAMP_FIELD
 };
 int q3_launch_attend(const Q3Attend& a, hipStream_t s);  // 0: launched; nonzero: refused (see its definition), nothing launched
+// k_attend's dynamic LDS (and k_attend_kv8's), offsets in floats: the kernels and their launchers both ask here
+struct AttLds { size_t qh, ow, lw, mw, kh, vh, bytes; };
+Q3_HD AttLds att_lds(int R, int n_ctx) {
+    constexpr int hd = Q3_ATT_HD;
+    AttLds L;
+    L.qh = (size_t)R * n_ctx;       // [R][n_ctx] scores / probabilities in front of it; qh: [R][hd] the query heads
+    L.ow = L.qh + R * hd;           // [R][4][hd] per-wave value sums
+    L.lw = L.ow + R * 4 * hd;       // [R][4] per-wave weight sums
+    L.mw = L.lw + R * 4;            // [R][4] per-wave score maxima
+    L.kh = L.mw + R * 4;            // [hd] newest key (the cache's packed form in front), FUSED only
+    L.vh = L.kh + hd;               // [hd] newest value (bf16 cache: bf16-rounded floats; Q8_0 cache: the packed form), FUSED only
+    L.bytes = (L.vh + hd) * sizeof(float);
+    return L;
+}
+#ifdef __HIPCC__
+// RMSNorm(hd) + RoPE of one head by one wave, the arithmetic in its three steps. Lane (< hd/4) holds its 4 consecutive elements x4, their
+// norm weights w4 and RoPE entries c4 / s4; every other lane holds x4 = 0 (+0 to the sum of squares).
+__device__ __forceinline__ float prep_rinv(const float4 x4, float eps, int hd) {  // 1 / rms of the head
+    float acc = 0.0f;
+    acc = fmaf(x4.x, x4.x, acc); acc = fmaf(x4.y, x4.y, acc); acc = fmaf(x4.z, x4.z, acc); acc = fmaf(x4.w, x4.w, acc);
+    acc = wave_sum(acc);
+    return 1.0f / sqrtf(acc / (float)hd + eps);
+}
+__device__ __forceinline__ void prep_norm(const float4 x4, float rinv, const float4 w4, float y[4]) {
+    y[0] = (x4.x * rinv) * w4.x; y[1] = (x4.y * rinv) * w4.y; y[2] = (x4.z * rinv) * w4.z; y[3] = (x4.w * rinv) * w4.w;
+}
+// RoPE (NeoX pairing i <-> i + hd/2): lanes [0, hd/8) hold the first halves, partner lane = lane ^ (hd/8)
+__device__ __forceinline__ void prep_rope(const float y[4], const float4 c4, const float4 s4, int hl, int lane, float o[4]) {  // hl = hd/8
+    const float cc[4] = {c4.x, c4.y, c4.z, c4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float other = __shfl_xor(y[e], hl);
+        o[e] = (lane < hl) ? fmaf(-other, ss[e], y[e] * cc[e])     // x_i*c - x_{i+half}*s
+                           : fmaf(other, ss[e], y[e] * cc[e]);     // x_{i+half}*c + x_i*s
+    }
+}
+// All three on operands that are already there: kernels that request their operands early (k_attend_gqa2, k_attend_small) call this.
+__device__ __forceinline__ void prep_arith(const float4 x4, const float4 w4, const float4 c4, const float4 s4, float eps, int lane, float o[4]) {
+    float y[4];
+    prep_norm(x4, prep_rinv(x4, eps, Q3_ATT_HD), w4, y);
+    prep_rope(y, c4, s4, Q3_ATT_HD >> 3, lane, o);
+}
+// The same with its loads, each in front of the step that needs it: lanes [0, hd/4) own 4 consecutive elements each; result in o[4]
+__device__ __forceinline__ void prep_head(const float* src, const float* nw, float eps, const float* cs, const float* sn, int hd,
+                                          int lane, float o[4]) {
+    const int nl = hd >> 2, hl = nl >> 1;
+    float4 x4 = (float4){0.f, 0.f, 0.f, 0.f}, w4 = x4, c4 = (float4){1.f, 1.f, 1.f, 1.f}, s4 = x4;
+    if (lane < nl) x4 = ((const float4*)src)[lane];
+    const float rinv = prep_rinv(x4, eps, hd);
+    if (lane < nl) w4 = ((const float4*)nw)[lane];
+    float y[4];
+    prep_norm(x4, rinv, w4, y);
+    const int i0 = 4 * (lane & (hl - 1));
+    if (lane < nl) { c4 = *(const float4*)(cs + i0); s4 = *(const float4*)(sn + i0); }
+    prep_rope(y, c4, s4, hl, lane, o);
+}
+// The attention output in the form Q3Attend.out_bf16 names, for a lane that holds 1 or 2 consecutive dims of `row` from dim `d` of query
+// head `head` on: f32 rows (0), the O projection's A-tiled bf16 operand (1), W8A8 Q8_0 blocks (2: 32 lanes x 1 / 16 lanes x 2, all active).
+__device__ __forceinline__ void att_out1(const Q3Attend& a, int row, int head, int d, float v) {
+    const int col = head * Q3_ATT_HD + d;
+    if (a.out_bf16 == 2) q3_q8_out32(v, row, col, (a.Hq * Q3_ATT_HD) >> 6, a.out_rt16, (int8_t*)a.out, a.out_scale);
+    else if (a.out_bf16) ((uint16_t*)a.out)[q3_atile_off(row, col, (a.Hq * Q3_ATT_HD) >> 5)] = q3_bf16(v);
+    else a.out[(size_t)row * a.ldo + (size_t)head * Q3_ATT_HD + d] = v;
+}
+__device__ __forceinline__ void att_out2(const Q3Attend& a, int row, int head, int d, float v0, float v1) {  // d even: one 4-byte store of the bf16 pair
+    if (a.out_bf16 == 2) q3_q8_out2x16(v0, v1, row, head * Q3_ATT_HD + d, (a.Hq * Q3_ATT_HD) >> 6, a.out_rt16, (int8_t*)a.out, a.out_scale);
+    else if (a.out_bf16) *(uint32_t*)((uint16_t*)a.out + q3_atile_off(row, head * Q3_ATT_HD + d, (a.Hq * Q3_ATT_HD) >> 5)) = (uint32_t)q3_bf16(v0) | ((uint32_t)q3_bf16(v1) << 16);
+    else *(float2*)(a.out + (size_t)row * a.ldo + (size_t)head * Q3_ATT_HD + d) = make_float2(v0, v1);
+}
+#endif
+// The Talker's cache as ggml Q8_0 blocks (q3_attend_kv8.hip; q3tts_engine_config.kv_q8_0). A block is 32 consecutive dims of
+// one (position, KV head) vector: four per key (after q/k-norm and RoPE), four per value (the raw f32 row). Per (slot, KV head):
+//   K quants [64-key block][hd / 16 chunks][64 keys][16] int8 — one key per lane, one 16-byte load per chunk, 1 KiB contiguous per wave-load
+//   K scales [64-key block][hd / 32][64 keys] f16;  V quants [t][hd] int8 row-major;  V scales [t][hd / 32] f16
+// Byte offset of key element (pos, d) / f16 index of the scale of (pos, block j) inside a head's K cache:
+Q3_HD size_t q3_kv8_k_off(int pos, int d) { return ((size_t)((pos >> 6) * (Q3_ATT_HD >> 4) + (d >> 4)) * 64 + (pos & 63)) * 16 + (d & 15); }
+Q3_HD size_t q3_kv8_kd_idx(int pos, int j) { return ((size_t)(pos >> 6) * (Q3_ATT_HD >> 5) + j) * 64 + (pos & 63); }
+// the launches of q3_attend_kv8.hip: q3_launch_qk_prep / q3_attend_pick / q3_launch_attend / q3_launch_kv_prefix hand over when kv8 is set
+int q3_launch_qk_prep_kv8(const Q3QkPrep& a, hipStream_t s);
+int q3_attend_pick_kv8(const Q3Attend& a);
+int q3_launch_attend_kv8(const Q3Attend& a, hipStream_t s);
 // The gathering form of k_attend_small (block 0 of passes q >= 1 of the greedy bf16 Predictor): the row's q / k / v are not
 // read from a.qkv but from a table of every possible input row's layer-0 QKV, tab[code], where code is the argmax k_pred_next<false>(q)
 // takes from the same per-tile keys (largest key of the row, q3_argmax_idx); a code outside [0, tab_rows) reads the fallback row tab_rows.
@@ -285,7 +370,9 @@ int q3_launch_attend_gather(const Q3Attend& a, const Q3AttGather& t, hipStream_t
 // the nine attention kernels of q3_attend.hip as q3_attend_pick names them (q3tts_k_attend_pick reports these numbers)
 enum { Q3_ATT_REFUSED = -1, Q3_ATT_N1 = 0, Q3_ATT_N2 = 1, Q3_ATT_N4 = 2,   // k_attend<1 / 2 / 4, false>
        Q3_ATT_F2 = 3, Q3_ATT_F4 = 4,                                       // k_attend<2 / 4, true>
-       Q3_ATT_GQA2 = 5, Q3_ATT_SMALL2 = 6, Q3_ATT_PAIR = 7, Q3_ATT_PREFILL = 8 };
+       Q3_ATT_GQA2 = 5, Q3_ATT_SMALL2 = 6, Q3_ATT_PAIR = 7, Q3_ATT_PREFILL = 8,
+       // the six of q3_attend_kv8.hip (Q3Attend.kv8; q3tts_k_attend_pick_kv8): k_attend_kv8<1 / 2 / 4, false>, k_attend_kv8<2 / 4, true>, k_attend_gqa2_kv8
+       Q3_ATT8_N1 = 9, Q3_ATT8_N2 = 10, Q3_ATT8_N4 = 11, Q3_ATT8_F2 = 12, Q3_ATT8_F4 = 13, Q3_ATT8_GQA2 = 14 };
 int q3_attend_pick(const Q3Attend& a);  // the kernel q3_launch_attend takes for a under the current policies (no launch); reads hd, Hq, Hkv,
                                         // fused, n_ctx and the seg fields only
 // Voice prefixes (q3tts_prefix): copy a prefix store into slots before their prefill. A store is laid out as one slot's cache of
@@ -296,8 +383,13 @@ struct Q3KvPrefix {
     uint16_t* kc; uint16_t* vc; size_t layer_stride; int n_ctx;  // the Talker's cache: [L][slots][Hkv][n_ctx * hd]
     int L, Hkv, hd, n;
     const uint16_t* pk[Q3_KVP_MAX]; const uint16_t* pv[Q3_KVP_MAX]; int P[Q3_KVP_MAX]; int slot[Q3_KVP_MAX];
+    // Q8_0 cache (kv8 = 1): kc / vc hold int8 quants (layer_stride in bytes), kd / vd the cache's f16 scales (layer_stride / 32 per layer). A
+    // store then is k / v [L][Hkv][np * hd] int8 followed by its scales [L][Hkv][np * hd / 32] f16 in the same allocation: pk / pv name the
+    // quants. Whole key blocks (quants and scales) are copied for K, positions < P for V.
+    int kv8; uint16_t* kd; uint16_t* vd;
 };
 void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s);
+void q3_launch_kv_prefix_kv8(const Q3KvPrefix& a, hipStream_t s);  // (q3_attend_kv8.hip; q3_launch_kv_prefix hands over when kv8 is set)
 void q3_attend_policy(int decode, int prefill);  // test hook (q3tts_k_attend_policy): which kernel variant serves decode / prefill attention (same bits)
 void q3_attend_policy_get(int* decode, int* prefill);
 

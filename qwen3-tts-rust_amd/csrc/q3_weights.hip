@@ -178,7 +178,15 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
         f.tid_a = Q3_TID(grp, Q3_L_MODEL, Q3WM_HEAD); fill(f, t.shead);
     }
     t.layer_stride = (size_t)t.n_slots * t.Hkv * t.n_ctx * hd;
+    t.kv8 = sh.kv8 != 0;
+    if (t.kv8) {  // Q8_0 cache: per element one byte of quants + 1/16 byte of f16 block scales, the scales behind the quants in one allocation
+        int8_t *kq = nullptr, *vq = nullptr;
+        const size_t nq = t.layer_stride * L;
+        TRY(q3_dalloc(e, &kq, nq + nq / 16)); TRY(q3_dalloc(e, &vq, nq + nq / 16));
+        t.kc = (uint16_t*)kq; t.vc = (uint16_t*)vq; t.kd = (uint16_t*)(kq + nq); t.vd = (uint16_t*)(vq + nq);
+    } else {
     TRY(q3_dalloc(e, &t.kc, t.layer_stride * L)); TRY(q3_dalloc(e, &t.vc, t.layer_stride * L));
+    }
     std::vector<float> cs, sn;
     q3_rope_tables(t.n_ctx, hd, sh.theta, sh.sections, cs, sn);
     TRY(q3_dalloc(e, &t.cs, cs.size())); TRY(q3_dalloc(e, &t.sn, sn.size()));

@@ -133,12 +133,18 @@ class TtsEngine:
         self.sampler_config = SamplerConfig()
 
     @classmethod
-    def new(cls, model_dir: Optional[str] = None, quant: str = "none", config=None, max_batch: Optional[int] = None):
+    def new(cls, model_dir: Optional[str] = None, quant: str = "none", config=None, max_batch: Optional[int] = None,
+            kv_cache: Optional[str] = None):
         """TtsEngine::new(model_dir, quant) (src/tts/engine.rs:84-169). With no config the model's shape comes from the GGUF files of the
         quant directory (q3tts_config_from_model_dir), whatever member of the family it holds; a config given by the caller is used as it
         is (its shapes must match the files) and is not modified. There is no network here: with no weight container under model_dir the
         engine uses seeded synthetic weights of the configured (default: 1.7B) shape. max_batch (1..256): the engine's slot count, in
-        place of the config's (include/q3tts.h states the memory per slot; 256 slots of the 1.7B shape need n_ctx <= 1024 or so)."""
+        place of the config's (include/q3tts.h states the memory per slot; 256 slots of the 1.7B shape need n_ctx <= 1024 or so).
+        kv_cache: None — a given config's own kv_q8_0 is kept (0, bf16, everywhere else); "bf16" — the Talker's K/V cache in bf16, whatever
+        the config says; "q8_0" — ggml Q8_0 blocks
+        (q3tts_engine_config.kv_q8_0 = 1: 0.53 of the memory; the results are not the bf16 cache's). Anything else: ValueError."""
+        if kv_cache not in (None, "bf16", "q8_0"):
+            raise ValueError(f"kv_cache must be None, 'bf16' or 'q8_0', not {kv_cache!r}")
         wdir = None
         if model_dir:
             quant_dir = {"q5_k_m": "gguf_q5_k_m", "q8_0": "gguf_q8_0"}.get(quant, "gguf")  # src/tts/engine.rs:91-95
@@ -155,6 +161,8 @@ class TtsEngine:
             cfg = _abi.default_config()
         if quant == "q8_0" and not cfg.talker_q8_0:
             cfg.talker_q8_0 = 2   # the gguf_q8_0 directory is multiplied as llama.cpp multiplies it: Q8_0 x Q8_0 (W8A8)
+        if kv_cache is not None:
+            cfg.kv_q8_0 = 1 if kv_cache == "q8_0" else 0
         if max_batch is not None:
             cfg.max_batch = int(max_batch)
         tok = load_tokenizer(model_dir) if model_dir else None

@@ -819,6 +819,74 @@ def k_attend_pick(fused, gqa_ratio, n_ctx, n_kv_head, n_seg=0, seg_max_n=0, seg_
     return None if k.value < 0 else ATTEND_KERNELS[k.value]
 
 
+ATTEND_KERNELS_KV8 = {9: "k_attend_kv8<1, false>", 10: "k_attend_kv8<2, false>", 11: "k_attend_kv8<4, false>", 12: "k_attend_kv8<2, true>",
+                      13: "k_attend_kv8<4, true>", 14: "k_attend_gqa2_kv8"}
+
+
+def k_attend_pick_kv8(fused, gqa_ratio, n_ctx, n_kv_head, n_seg=0, seg_max_n=0, seg_max_t=0, want_code=False):
+    """q3tts_k_attend_pick_kv8 (host only): the kernel of csrc/q3_attend_kv8.hip the launcher takes for a launch over a Q8_0 cache under the
+    current policies — its name (want_code: its number 9 .. 14) — or None when the launcher refuses."""
+    lib = _abi.load_library()
+    k = C.c_int32(-2)
+    rc = lib.q3tts_k_attend_pick_kv8(fused, gqa_ratio, n_ctx, n_seg, seg_max_n, seg_max_t, n_kv_head, C.byref(k))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_attend_pick_kv8 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    if k.value < 0:
+        return None
+    return k.value if want_code else ATTEND_KERNELS_KV8[k.value]
+
+
+def _att_hook_cache_kv8(n_slots, n_kv_head, n_ctx, head_dim, want_cache):
+    if not want_cache:
+        return None, None, None, None
+    q = lambda: np.zeros((n_slots, n_kv_head, n_ctx, head_dim), dtype=np.int8)
+    d = lambda: np.zeros((n_slots, n_kv_head, n_ctx, head_dim // 32), dtype=np.uint16)
+    return q(), q(), d(), d()
+
+
+def k_attention_runs_kv8(qkv, runs, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, policy=-1, out_form=0,
+                         want_cache=True, device=0):
+    """q3tts_k_attention_runs_kv8: k_attention_runs over a Q8_0 cache. Returns a dict: out / scale as there, and the cache un-blocked:
+    k_q / v_q int8 [run][n_kv_head][n_ctx][head_dim], k_d / v_d f16 bits [run][n_kv_head][n_ctx][head_dim / 32]."""
+    lib = _abi.load_library()
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+    p0 = np.ascontiguousarray([r[0] for r in runs], dtype=np.int32)
+    nn = np.ascontiguousarray([r[1] for r in runs], dtype=np.int32)
+    assert qkv.shape[0] == int(p0.sum() + nn.sum())
+    qn = np.ascontiguousarray(q_norm_w, dtype=np.float32)
+    kn = np.ascontiguousarray(k_norm_w, dtype=np.float32)
+    sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
+    out, sc, _, _ = _att_hook_out(max(int(nn.sum()), 1), n_head * head_dim, out_form, len(runs), n_kv_head, n_ctx, head_dim, False)
+    kq, vq, kd, vd = _att_hook_cache_kv8(len(runs), n_kv_head, n_ctx, head_dim, want_cache)
+    rc = lib.q3tts_k_attention_runs_kv8(device, _ptr(qkv, f32p), len(runs), _ptr(nn, i32p), _ptr(p0, i32p), n_ctx, n_head, n_kv_head, head_dim,
+                                        _ptr(qn, f32p), _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, out_form,
+                                        _dp(out), _dp(sc), _dp(kq), _dp(vq), _dp(kd), _dp(vd))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_attention_runs_kv8 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return dict(out=out, scale=sc, k_q=kq, v_q=vq, k_d=kd, v_d=vd)
+
+
+def k_attention_decode_kv8(qkv, lens, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, policy=-1, out_form=0,
+                           want_cache=True, device=0):
+    """q3tts_k_attention_decode_kv8: k_attention_decode_ex (without row_indexed) over a Q8_0 cache. Returns the dict of k_attention_runs_kv8
+    with out [n_slots][n_head * head_dim]."""
+    lib = _abi.load_library()
+    qkv = np.ascontiguousarray(qkv, dtype=np.float32)
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    assert qkv.shape[0] == int(ln.sum())
+    qn = np.ascontiguousarray(q_norm_w, dtype=np.float32)
+    kn = np.ascontiguousarray(k_norm_w, dtype=np.float32)
+    sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
+    out, sc, _, _ = _att_hook_out(max(ln.size, 1), n_head * head_dim, out_form, ln.size, n_kv_head, n_ctx, head_dim, False)
+    kq, vq, kd, vd = _att_hook_cache_kv8(ln.size, n_kv_head, n_ctx, head_dim, want_cache)
+    rc = lib.q3tts_k_attention_decode_kv8(device, _ptr(qkv, f32p), ln.size, _ptr(ln, i32p), n_ctx, n_head, n_kv_head, head_dim, _ptr(qn, f32p),
+                                          _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, out_form,
+                                          _dp(out), _dp(sc), _dp(kq), _dp(vq), _dp(kd), _dp(vd))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_attention_decode_kv8 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return dict(out=out, scale=sc, k_q=kq, v_q=vq, k_d=kd, v_d=vd)
+
+
 def _att_hook_out(rows, nq, out_form, n_slots, n_kv_head, n_ctx, head_dim, want_cache):
     out = np.zeros((rows, nq), dtype=(np.float32, np.uint16, np.int8)[out_form] if 0 <= out_form <= 2 else np.float32)
     sc = np.zeros((rows, nq // 32), dtype=np.float32) if out_form == 2 else None

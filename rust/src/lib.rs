@@ -30,6 +30,7 @@ pub struct q3tts_engine_config {
     pub talker_q8_0: i32,   // 2: the Talker's Q8_0 blocks stay quantised on the device and meet Q8_0 activations (W8A8, the crate's default "q8_0" directory); 1: W8A16; 0: bf16
     pub vocoder_flush_tail: i32,   // 0: the look-ahead tail is flushed as the reference does (only when n_frames % 4 != 0); 1: always
     pub predictor_q8_0: i32,   // 0: bf16 Predictor; 2: its Q8_0 blocks stay quantised on the device and meet Q8_0 activations (W8A8), opt-in; 1: refused
+    pub kv_q8_0: i32,   // 0: bf16 Talker K/V cache; 1: the cache as ggml Q8_0 blocks on the device (0.53 of the bytes; results differ from the bf16 cache's), opt-in; else refused
 }
 #[repr(C)]
 pub struct q3tts_prompt_desc {
