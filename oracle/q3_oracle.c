@@ -320,9 +320,29 @@ static void attend_one(const float* qh, const float* Kc, const float* Vc, int T,
     free(ou); free(sc);
 }
 
-/* rows of one sequence in order: q/k RMSNorm -> RoPE -> append bf16 K/V -> attention (rows before `attend_from` only append) */
+void q3o_quantize_q8_0(const float* x, int64_t n, int8_t* q, uint16_t* d_f16);
+float q3o_f16_to_f32(uint16_t h);
+/* one K or V head vector into a Q8_0 cache: ggml's quantiser per 32 dims on the f32 values, cached as x^ = f32(f16 d) * q
+ * (exact in f32); q_out / d_out (optional): the blocks themselves */
+static void cache_q8_0(const float* x, int hd, float* dst, int8_t* q_out, uint16_t* d_out) {
+    int8_t q[32]; uint16_t d16;
+    for (int b = 0; b < hd / 32; ++b) {
+        q3o_quantize_q8_0(x + 32 * b, 32, q, &d16);
+        const float d = q3o_f16_to_f32(d16);
+        for (int i = 0; i < 32; ++i) dst[32 * b + i] = d * (float)q[i];
+        if (q_out) memcpy(q_out + 32 * b, q, 32);
+        if (d_out) d_out[b] = d16;
+    }
+}
+
+/* rows of one sequence in order: q/k RMSNorm -> RoPE -> append bf16 K/V -> attention (rows before `attend_from` only append).
+ * kv8: the cache holds Q8_0 blocks instead (K quantised from its f32 values after the norm and RoPE, V from the raw f32 row); the
+ * attention downstream is the same code on x^. kv8_out (optional, kv8 only): k_q, k_d, v_q, v_d of the rows, [n_rows][Hkv][hd] int8 and
+ * [n_rows][Hkv][hd / 32] f16 bits. */
+typedef struct { int8_t* k_q; uint16_t* k_d; int8_t* v_q; uint16_t* v_d; } kv8_blocks;
 static void attn_rows_from(const float* qkv, int n_rows, int pos0, int Hq, int Hkv, int hd, const float* qnw, const float* knw,
-                           float eps, const float* cs, const float* sn, float* kc, float* vc, int n_ctx, int attend_from, float* out) {
+                           float eps, const float* cs, const float* sn, float* kc, float* vc, int n_ctx, int attend_from, float* out,
+                           int kv8, const kv8_blocks* kv8_out) {
     const int ld = (Hq + 2 * Hkv) * hd, R = Hq / Hkv, half = hd / 2;
     float* tmp = (float*)malloc((size_t)hd * 4);
     for (int r = 0; r < n_rows; ++r) {
@@ -334,6 +354,11 @@ static void attn_rows_from(const float* qkv, int n_rows, int pos0, int Hq, int H
             float* kd = kc + ((size_t)g * n_ctx + pos) * hd;
             float* vd = vc + ((size_t)g * n_ctx + pos) * hd;
             const float* vs = row + (size_t)(Hq + Hkv + g) * hd;
+            if (kv8) {
+                const size_t e = ((size_t)r * Hkv + g) * hd, b = ((size_t)r * Hkv + g) * (hd / 32);
+                cache_q8_0(tmp, hd, kd, kv8_out ? kv8_out->k_q + e : NULL, kv8_out ? kv8_out->k_d + b : NULL);
+                cache_q8_0(vs, hd, vd, kv8_out ? kv8_out->v_q + e : NULL, kv8_out ? kv8_out->v_d + b : NULL);
+            } else
             for (int d = 0; d < hd; ++d) { kd[d] = round_bf16(tmp[d]); vd[d] = round_bf16(vs[d]); }
         }
         if (r < attend_from) continue;
@@ -348,8 +373,8 @@ static void attn_rows_from(const float* qkv, int n_rows, int pos0, int Hq, int H
     free(tmp);
 }
 static void attn_rows(const float* qkv, int n_rows, int pos0, int Hq, int Hkv, int hd, const float* qnw, const float* knw,
-                      float eps, const float* cs, const float* sn, float* kc, float* vc, int n_ctx, float* out) {
-    attn_rows_from(qkv, n_rows, pos0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_ctx, 0, out);
+                      float eps, const float* cs, const float* sn, float* kc, float* vc, int n_ctx, int kv8, float* out) {
+    attn_rows_from(qkv, n_rows, pos0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_ctx, 0, out, kv8, NULL);
 }
 
 void q3o_attention(const float* qkv, int32_t n_rows, int32_t pos0, int32_t Hq, int32_t Hkv, int32_t hd, const float* qnw,
@@ -360,7 +385,24 @@ void q3o_attention(const float* qkv, int32_t n_rows, int32_t pos0, int32_t Hq, i
     rope_tables(n_ctx, hd, theta, sections, cs, sn);
     float* kc = (float*)calloc((size_t)Hkv * n_ctx * hd, 4);
     float* vc = (float*)calloc((size_t)Hkv * n_ctx * hd, 4);
-    attn_rows(qkv, n_rows, pos0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_ctx, out);
+    attn_rows(qkv, n_rows, pos0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_ctx, 0, out);
+    free(kc); free(vc); free(cs); free(sn);
+}
+/* q3o_attention over a Q8_0 cache (what q3o_set_talker_kv_q8 makes the Talker compute): rows at positions 0 .. n_rows - 1
+ * of one sequence, a fresh cache. out [n_rows - attend_from][Hq * hd]: the rows from attend_from on (0: every row, as q3o_attention;
+ * n_rows - 1: the last row only, as q3o_attention_last; n_rows: none, the preparation stage alone — q is q3o_attention_prep's).
+ * k_q, v_q [n_rows][Hkv][hd] int8 and k_d, v_d [n_rows][Hkv][hd / 32] f16 bits (all four or none): the cache, in natural order. */
+void q3o_attention_kv_q8(const float* qkv, int32_t n_rows, int32_t attend_from, int32_t Hq, int32_t Hkv, int32_t hd, const float* qnw,
+                         const float* knw, float eps, float theta, const int32_t* sections, float* out, int8_t* k_q, uint16_t* k_d,
+                         int8_t* v_q, uint16_t* v_d) {
+    const int half = hd / 2;
+    float* cs = (float*)malloc((size_t)n_rows * half * 4);
+    float* sn = (float*)malloc((size_t)n_rows * half * 4);
+    rope_tables(n_rows, hd, theta, sections, cs, sn);
+    float* kc = (float*)calloc((size_t)Hkv * n_rows * hd, 4);
+    float* vc = (float*)calloc((size_t)Hkv * n_rows * hd, 4);
+    const kv8_blocks b = {k_q, k_d, v_q, v_d};
+    attn_rows_from(qkv, n_rows, 0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_rows, attend_from, out, 1, k_q ? &b : NULL);
     free(kc); free(vc); free(cs); free(sn);
 }
 /* The preparation stage of q3o_attention on its own: for qkv rows at positions pos0 .. pos0 + n_rows - 1, q after RMSNorm + RoPE (f32,
@@ -402,7 +444,7 @@ void q3o_attention_last(const float* qkv, int32_t n_rows, int32_t Hq, int32_t Hk
     rope_tables(n_rows, hd, theta, sections, cs, sn);
     float* kc = (float*)calloc((size_t)Hkv * n_rows * hd, 4);
     float* vc = (float*)calloc((size_t)Hkv * n_rows * hd, 4);
-    attn_rows_from(qkv, n_rows, 0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_rows, n_rows - 1, out);
+    attn_rows_from(qkv, n_rows, 0, Hq, Hkv, hd, qnw, knw, eps, cs, sn, kc, vc, n_rows, n_rows - 1, out, 0, NULL);
     free(kc); free(vc); free(cs); free(sn);
 }
 
@@ -550,6 +592,7 @@ typedef struct {
     /* Q8_0 mode (q3o_set_talker_q8): the matrices above then hold the block quants as (exact) bf16 in operand order and these the
      * block scales f32(f16 d) [N][K/32]; NULL = bf16 weights */
     float** s_qkv; float** s_o; float** s_g; float** s_u; float** s_d; float* s_head;
+    int kv8; /* 1: the K/V cache holds ggml Q8_0 blocks (q3o_set_talker_kv_q8; attn_rows_from) */
     int a8;  /* 1: the ACTIVATIONS of every GEMM are Q8_0 blocks too (W8A8, ggml's vec_dot_q8_0_q8_0: q3o_bgemm_q8a8_raw); needs s_* */
     float *kc, *vc; int n_ctx; /* [L][Hkv][n_ctx][hd] */
     float *cs, *sn;
@@ -699,7 +742,7 @@ static void tfm_layers(tfm* t, float* x, uint16_t* xb, float* ssp, int n, int po
         bgemm_rows(xb, n, d, t->wqkv[l], t->s_qkv ? t->s_qkv[l] : NULL, nqkv, qkv, nqkv);
         scale_rows(qkv, n, nqkv, nqkv, sc);
         size_t co = (size_t)l * t->Hkv * t->n_ctx * t->hd;
-        attn_rows(qkv, n, pos0, t->Hq, t->Hkv, t->hd, t->qn[l], t->kn[l], eps, t->cs, t->sn, t->kc + co, t->vc + co, t->n_ctx, att);
+        attn_rows(qkv, n, pos0, t->Hq, t->Hkv, t->hd, t->qn[l], t->kn[l], eps, t->cs, t->sn, t->kc + co, t->vc + co, t->n_ctx, t->kv8, att);
         if (t->a8) bgemm_rows_a8(att, n, nq, t->wo[l], t->s_o[l], d, y, d);
         else {
         for (size_t i = 0; i < (size_t)n * nq; ++i) ab[i] = q3o_bf16(att[i]);
@@ -841,6 +884,9 @@ void q3o_set_arith(q3o_model* m, int32_t arith) { m->arith = arith; }
 void q3o_set_talker_q8(q3o_model* m) { tfm_to_q8(&m->T); }
 /* ... and every GEMM's activations as Q8_0 blocks as well: W8A8, what llama.cpp computes on a gguf_q8_0 model (talker_q8_0 = 2) */
 void q3o_set_talker_q8a8(q3o_model* m) { tfm_to_q8(&m->T); m->T.a8 = 1; }
+/* The Talker's K/V cache as ggml Q8_0 blocks — what the device computes with q3tts_engine_config.kv_q8_0 = 1. One-way;
+ * combines with either of the two above. The Predictor's cache stays bf16, as on the device. */
+void q3o_set_talker_kv_q8(q3o_model* m) { m->T.kv8 = 1; }
 void q3o_set_threads(int32_t n) { g_threads = n > 0 ? n : 1; }  /* OpenMP threads of the GEMMs (bench.py: the 4-thread and all-cores legs) */
 /* natural-order f32 copies of the synthetic tensors, for loading the same model into the family code (tests) */
 const float* q3o_norm_weight(const q3o_model* m, int32_t talker, int32_t layer, int32_t which) {
@@ -987,7 +1033,7 @@ static void head_row(const q3o_model* m, tfm* t, const float* xrow, const uint16
 /* rows through one transformer in the model's arithmetic; xb / ssp as in tfm_layers (ignored by the plain form) */
 static void run_tfm(const q3o_model* m, tfm* t, float* x, uint16_t* xb, float* ssp, int n, int pos0) {
     if (m->arith == 1) { tfm_layers_plain(t, x, n, pos0, m->c.rms_eps); return; }
-    for (int r = 0; r < n; ++r) q3o_norm_inputs(x + (size_t)r * t->d, t->d, t->attn_norm[0], xb + (size_t)r * t->d, ssp + (size_t)r * (t->d / 16));
+    for (int r = 0; r < n; ++r) q3o_norm_inputs(x + (size_t)r * t->d, t->d, t->L ? t->attn_norm[0] : t->out_norm, xb + (size_t)r * t->d, ssp + (size_t)r * (t->d / 16));
     tfm_layers(t, x, xb, ssp, n, pos0, m->c.rms_eps);
 }
 

@@ -94,6 +94,12 @@ void q3o_attention_last(const float* qkv, int32_t n_rows, int32_t n_head, int32_
  * caches (f32 values, [n_rows][Hkv * hd] each) for rows at positions pos0 .. pos0 + n_rows - 1 */
 void q3o_attention_prep(const float* qkv, int32_t n_rows, int32_t pos0, int32_t n_head, int32_t n_kv_head, int32_t head_dim, const float* q_norm_w,
                         const float* k_norm_w, float eps, float rope_theta, const int32_t* mrope_sections, float* q_out, float* k_out, float* v_out);
+/* q3o_attention over a cache of ggml Q8_0 blocks: rows at positions 0 .. n_rows - 1, out for the rows from attend_from on
+ * (0 every row, n_rows - 1 the last only, n_rows none); the cache in natural order, k_q / v_q [n_rows][Hkv][hd] int8, k_d / v_d
+ * [n_rows][Hkv][hd / 32] f16 bits (all four or all NULL) */
+void q3o_attention_kv_q8(const float* qkv, int32_t n_rows, int32_t attend_from, int32_t n_head, int32_t n_kv_head, int32_t head_dim,
+                         const float* q_norm_w, const float* k_norm_w, float eps, float rope_theta, const int32_t* mrope_sections, float* out,
+                         int8_t* k_q, uint16_t* k_d, int8_t* v_q, uint16_t* v_d);
 /* one output element of v_mfma_f32_16x16x32_bf16 (gfx950), restated in integers: a[32], b[32] bf16 bits in operand order
  * (position 8g + e = operand e of lane group g), c the accumulator. _ref: the 128-bit form the 64-bit one is tested against. */
 float q3o_mfma_bf16_dot32(const uint16_t* a, const uint16_t* b, float c);
@@ -122,6 +128,7 @@ void q3o_bgemm_q8a8_f32(const int8_t* aq, const float* ad, int32_t B, int32_t K,
 /* ... with the activation scales as f16 bit patterns in and out (exact wherever they are normal f16) */
 void q3o_bgemm_q8a8(const int8_t* aq, const uint16_t* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N, const float* ssp,
                     int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, uint16_t* yd, float* ssp_out);
+void q3o_set_talker_kv_q8(q3o_model* m);  /* the Talker's K/V cache as ggml Q8_0 blocks (q3tts_engine_config.kv_q8_0 = 1); combines with talker_q8 / q8a8; the Predictor's stays bf16 */
 void q3o_set_talker_q8(q3o_model* m);  /* the Talker's matrices + lm_head as ggml Q8_0 blocks, canonical Q8 order (q3tts_engine_config.talker_q8_0) */
 void q3o_quantize_q8_0(const float* x, int64_t n, int8_t* q, uint16_t* d_f16);  /* ggml's reference quantiser */
 float q3o_f16_to_f32(uint16_t h);

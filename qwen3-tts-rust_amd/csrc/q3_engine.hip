@@ -65,8 +65,11 @@ static int validate(const q3tts_engine_config& c, std::string& why) {
     REQ(m.t_d_model % 512 == 0 && m.p_d_model % 512 == 0 && m.t_d_ffn % 512 == 0 && m.p_d_ffn % 512 == 0);
     REQ(m.t_d_model <= 8192 && m.p_d_model <= 8192);  // fused RMSNorm: a wave's share of the norm weights is one LDS strip of <= 1024 floats
     REQ((m.t_n_head * m.t_head_dim) % 512 == 0 && (m.p_n_head * m.p_head_dim) % 512 == 0);
+    REQ(m.t_n_head > 0 && m.t_n_kv_head > 0 && m.p_n_head > 0 && m.p_n_kv_head > 0);
     REQ(m.t_n_head % m.t_n_kv_head == 0 && m.p_n_head % m.p_n_kv_head == 0);
-    { int r = m.t_n_head / m.t_n_kv_head; REQ(r == 1 || r == 2 || r == 4); r = m.p_n_head / m.p_n_kv_head; REQ(r == 1 || r == 2 || r == 4); }
+    // the attention kernels serve 1, 2 or 4 query heads per KV head (spelled with the fields, so that the message names them)
+    REQ(m.t_n_head == m.t_n_kv_head || m.t_n_head == 2 * m.t_n_kv_head || m.t_n_head == 4 * m.t_n_kv_head);
+    REQ(m.p_n_head == m.p_n_kv_head || m.p_n_head == 2 * m.p_n_kv_head || m.p_n_head == 4 * m.p_n_kv_head);
     REQ(m.t_vocab % 16 == 0 && m.codebook_size % 16 == 0 && m.t_d_ffn % 8 == 0);
     REQ(m.d_embed == m.t_d_model);  // feedback row feeds the Talker directly (src/tts/engine.rs:631)
     REQ(m.d_embed % 512 == 0);

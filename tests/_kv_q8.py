@@ -263,3 +263,72 @@ def grid_inputs(spec, seed=A.SEED):
         x.reshape(tot, Hq + 2 * Hkv, HD)[:, Hq + Hkv:] = v.reshape(tot, Hkv, HD)
         assert np.array_equal(A.bf16_value(A.bf16_bits(v)), v)
     return xs, qn, kn
+
+
+# ---- the oracle's Q8_0 cache mode (q3o_attention_kv_q8; OracleModel.set_talker_kv_q8) ------------------------------------------------------
+def oracle_q(O, x, Hq, Hkv, qn, kn):
+    """The oracle's f32 q after RMSNorm + RoPE of every row of a sequence, [tot][Hq][HD] (q3o_attention_prep; its K / V outputs are the
+    bf16 cache's and are not used here)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    tot = x.shape[0]
+    sec = np.ascontiguousarray(A.SECTIONS)
+    q = np.zeros((tot, Hq, HD), dtype=np.float32)
+    k = np.zeros((tot, Hkv, HD), dtype=np.float32)
+    v = np.zeros((tot, Hkv, HD), dtype=np.float32)
+    O.lib().q3o_attention_prep(O.ptr(x, O.f32p), tot, 0, Hq, Hkv, HD, O.ptr(qn, O.f32p), O.ptr(kn, O.f32p), A.EPS, A.THETA, O.ptr(sec, O.i32p),
+                               O.ptr(q, O.f32p), O.ptr(k, O.f32p), O.ptr(v, O.f32p))
+    return q
+
+
+def oracle_seq_kv8(O, x, pos0, n, Hq, Hkv, qn, kn):
+    """The oracle over a Q8_0 cache on one sequence: out [n][Hq HD] of the attending rows, and the cache k_q, k_d, v_q, v_d of ALL rows in
+    natural order ([tot][Hkv][HD] int8, [tot][Hkv][NB] f16 bits) — the form test_kv_q8_gpu.py::_per_seq gives the hooks' cache."""
+    assert x.shape[0] == pos0 + n
+    return O.attention_kv_q8(x, pos0, Hq, Hkv, HD, qn, kn, A.EPS, A.THETA, A.SECTIONS)
+
+
+_ORACLE_KV8 = {}
+
+
+def oracle_case_kv8(O, spec, kind):
+    """(xs, qn, kn, per-sequence oracle_seq_kv8 results) of one (spec, kind): computed once, shared, never changed. kind "grid": grid_inputs."""
+    key = (spec["name"], kind)
+    if key not in _ORACLE_KV8:
+        xs, qn, kn = grid_inputs(spec) if kind == "grid" else make_inputs(spec, kind)
+        Hq, Hkv = spec["heads"]
+        res = [oracle_seq_kv8(O, x, p, n, Hq, Hkv, qn, kn) for x, (p, n) in zip(xs, spec["seqs"])]
+        for a in xs + [qn, kn] + [t for r in res for t in r]:
+            a.setflags(write=False)
+        _ORACLE_KV8[key] = (xs, qn, kn, res)
+    return _ORACLE_KV8[key]
+
+
+# ---- whole engines against the oracle (tests/test_kv_q8_gpu.py, tests/test_shapes_gpu.py): the inputs, made by the oracle alone ------------------
+def spk(d):
+    return ((np.arange(d) % 13 - 6) * 0.03125).astype(np.float32)
+
+
+def prompt_rows(O, om, rows, seed):
+    """The last `rows` rows of a prompt the oracle builds from `rows` random text ids (a prompt has about ten rows more than its text)."""
+    desc, keep = O.make_prompt_desc(np.random.default_rng([seed, rows]).integers(0, 151643, size=rows), spk_emb=spk(om.cfg.d_embed))
+    return np.ascontiguousarray(om.build_prompt(desc)[-rows:])
+
+
+GREEDY = dict(temperature=0.0)
+SAMPLED = dict(temperature=0.9, top_k=0, top_p=1.0)   # the whole distribution: the ids follow every logit, not the top few
+
+
+def batch_requests(O, om, n, lo=40, hi=130, frames=(6, 12), seed=77):
+    """n sampled requests of mixed prompt length (lo .. hi rows, both ends present) and forced lengths (frames[0] .. frames[1]): more than an
+    engine's slots, so that slots are reused."""
+    rng = np.random.default_rng(seed)
+    rows = [lo, hi] + [int(r) for r in rng.integers(lo, hi + 1, size=n - 2)]
+    reqs = []
+    for i, r in enumerate(rows):
+        t = int(rng.integers(frames[0], frames[1] + 1))
+        reqs.append(dict(embd=prompt_rows(O, om, r, seed + i), seed=seed + i, max_steps=t + 2, min_frames=t, force_eos_at=t, **SAMPLED))
+    return reqs
+
+
+def oracle_kw(r):
+    return {k: v for k, v in r.items() if k not in ("embd", "want_pcm", "desc", "prefix")}

@@ -110,6 +110,9 @@ def lib():
     L.q3o_attention_prep.argtypes = [f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float, C.c_float, i32p,
                                      f32p, f32p, f32p]
     L.q3o_attention_prep.restype = None
+    L.q3o_attention_kv_q8.argtypes = [f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float, C.c_float, i32p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.q3o_attention_kv_q8.restype = None
     L.q3o_sample.argtypes = [f32p, C.c_int32, C.c_float, C.c_int32, C.c_float, C.c_float]
     L.q3o_sample.restype = C.c_int32
     L.q3o_rng_f32.argtypes = [C.c_uint64, C.c_int32, f32p]
@@ -167,6 +170,8 @@ def lib():
     L.q3o_bgemm_q8a8_f32.restype = None
     L.q3o_set_talker_q8a8.argtypes = [vp]
     L.q3o_set_talker_q8a8.restype = None
+    L.q3o_set_talker_kv_q8.argtypes = [vp]
+    L.q3o_set_talker_kv_q8.restype = None
     L.q3o_set_talker_q8.argtypes = [vp]
     L.q3o_set_talker_q8.restype = None
     L.q3o_project_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
@@ -229,6 +234,11 @@ class OracleModel:
         """... and every Talker GEMM's activations as Q8_0 blocks as well: ggml's W8A8 (device: talker_q8_0 = 2). One-way."""
         self.L.q3o_set_talker_q8a8(self.h)
 
+    def set_talker_kv_q8(self):
+        """The Talker's K/V cache as ggml Q8_0 blocks (device: q3tts_engine_config.kv_q8_0 = 1). One-way; combines with
+        set_talker_q8 / set_talker_q8a8. The Predictor's cache stays bf16."""
+        self.L.q3o_set_talker_kv_q8(self.h)
+
     def set_arith(self, mode):
         """0: the canonical bf16-MFMA order (default); 1: plain f32 of the same structure (family pinning)."""
         self.L.q3o_set_arith(self.h, mode)
@@ -283,6 +293,22 @@ def bgemm(xb, wb, ssp, d_norm, eps, epi, nw_next=None, y0=None):
     lib().q3o_bgemm(xb.ctypes.data, B, K, wb.ctypes.data, N, None if sp is None else sp.ctypes.data, 0 if sp is None else sp.shape[1], d_norm, eps, epi,
                     None if nw is None else nw.ctypes.data, y.ctypes.data, yb.ctypes.data, sso.ctypes.data, keys.ctypes.data)
     return dict(y=y, yb=yb, ssp_out=sso, keys=keys)
+
+
+def attention_kv_q8(x, attend_from, Hq, Hkv, hd, qn, kn, eps, theta, sections):
+    """q3o_attention_kv_q8 on one sequence's qkv rows x [tot][(Hq + 2 Hkv) hd] at positions 0 .. tot - 1: (out [tot - attend_from][Hq hd] f32,
+    k_q, k_d, v_q, v_d) — the cache in natural order, [tot][Hkv][hd] int8 and [tot][Hkv][hd / 32] f16 bits."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    qn = np.ascontiguousarray(qn, dtype=np.float32); kn = np.ascontiguousarray(kn, dtype=np.float32)
+    sec = np.ascontiguousarray(sections, dtype=np.int32)
+    tot = x.shape[0]
+    assert x.shape[1] == (Hq + 2 * Hkv) * hd and 0 <= attend_from <= tot
+    out = np.zeros((tot - attend_from, Hq * hd), dtype=np.float32)
+    k_q = np.zeros((tot, Hkv, hd), dtype=np.int8); v_q = np.zeros((tot, Hkv, hd), dtype=np.int8)
+    k_d = np.zeros((tot, Hkv, hd // 32), dtype=np.uint16); v_d = np.zeros((tot, Hkv, hd // 32), dtype=np.uint16)
+    lib().q3o_attention_kv_q8(ptr(x, f32p), tot, attend_from, Hq, Hkv, hd, ptr(qn, f32p), ptr(kn, f32p), eps, theta, ptr(sec, i32p),
+                              out.ctypes.data, k_q.ctypes.data, k_d.ctypes.data, v_q.ctypes.data, v_d.ctypes.data)
+    return out, k_q, k_d, v_q, v_d
 
 
 def quantize_q8_0(x):

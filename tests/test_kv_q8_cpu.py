@@ -1,6 +1,7 @@
 """The Q8_0 K/V cache (kv_q8_0) without a device: the checks of tests/_kv_q8.py on a numpy-f32 restatement of the
 preparation and the quantiser, planted defects they must reject, the layout's index functions, the launcher's choice
-(q3tts_k_attend_pick_kv8), the hooks' argument checks and the configuration field in its three mirrors."""
+(q3tts_k_attend_pick_kv8), the hooks' argument checks and the configuration field in its three mirrors; and the oracle's own Q8_0 cache
+mode (q3o_attention_kv_q8, OracleModel.set_talker_kv_q8) under the same checks, since the device is compared with it bit for bit."""
 import ctypes as C
 import os
 import re
@@ -228,3 +229,130 @@ def test_api_kv_cache_argument():
     for bad in ("q4", "Q8_0", "f16", ""):
         with pytest.raises(ValueError):
             api.TtsEngine.new(None, "none", kv_cache=bad)
+
+
+# ---- the oracle's own Q8_0 cache mode (q3o_attention_kv_q8, OracleModel.set_talker_kv_q8): what tests/test_kv_q8_gpu.py and
+# tests/test_shapes_gpu.py compare the device with, bit for bit — held to the same float64 checks as the device, so that the two cannot be
+# wrong in the same way ----------------------------------------------------------------------------------------------------------------------
+def test_oracle_kv_q8_passes_stage1_and_stage2_on_all_cases(oracle):
+    """q3o_attention_kv_q8 on every spec x kind of test_restatement_passes_stage1_on_all_cases: its K cache within the windows and the
+    caps, its V cache equal to q3o_quantize_q8_0 of the f32 rows, its output within ATT_STAGE2_TOL of float64 over its own cache."""
+    total, worst = K.Counts(), 0.0
+    for spec in PLAIN:
+        Hq, Hkv = spec["heads"]
+        c = K.Counts()
+        for kind in K.KINDS:
+            xs, qn, kn, res = K.oracle_case_kv8(oracle, spec, kind)
+            for x, (pos0, n), (out, k_q, k_d, v_q, v_d) in zip(xs, spec["seqs"], res):
+                K.check_stage1_k(x, Hq, Hkv, kn, k_q, k_d, c)
+                K.check_stage1_v(oracle, x, Hq, Hkv, v_q, v_d)
+                q = K.oracle_q(oracle, x, Hq, Hkv, qn, kn)
+                err = K.stage2_error(out, q[pos0:], k_q, k_d, v_q, v_d, pos0, Hq, Hkv)
+                assert err <= ATT_STAGE2_TOL, (spec["name"], kind, pos0, n, err)
+                worst = max(worst, err)
+        c.check_caps(spec["name"])
+        for f in ("elems", "near_q", "diff_q", "blocks", "near_d", "diff_d"):
+            setattr(total, f, getattr(total, f) + getattr(c, f))
+        total.worst_q = max(total.worst_q, c.worst_q)
+    print(total.line("oracle, Q8_0 cache mode, all cases"))
+    print(f"oracle, Q8_0 cache mode: worst error vs float64 / max|v^|: {worst:.1e} (bound {ATT_STAGE2_TOL:.1e})")
+    total.check_caps("all cases")
+    assert total.elems >= 6_247_808 and total.blocks >= 195_244
+
+
+def test_oracle_kv_q8_equals_the_bf16_oracle_on_the_grid(oracle):
+    """On grid_inputs the Q8_0 cache holds exactly what the bf16 cache holds (x^ = v = bf16(v), K all zeros): the Q8 oracle's output equals
+    q3o_attention's in all 32 bits, and its cache dequantises to the bf16 oracle's V."""
+    for spec in PLAIN:
+        Hq, Hkv = spec["heads"]
+        xs, qn, kn, res = K.oracle_case_kv8(oracle, spec, "grid")
+        for x, (pos0, n), (out, k_q, k_d, v_q, v_d) in zip(xs, spec["seqs"], res):
+            want, _, _, vb = K.oracle_seq(oracle, x, pos0, n, Hq, Hkv, qn, kn)
+            assert not k_q.any() and not k_d.any() and np.array_equal(K.dequant(v_q, v_d), A.bf16_value(vb)), (spec["name"], pos0, n)
+            assert np.array_equal(A.bits(out), A.bits(want)), (spec["name"], pos0, n)
+
+
+def test_oracle_kv_q8_entry_points_agree(oracle):
+    """attend_from selects rows and nothing else: the last row alone (as q3o_attention_last) and no row at all (the preparation stage)
+    give the same bits and the same cache as the whole sequence."""
+    spec = K.SPEC["prefill_a"]
+    Hq, Hkv = spec["heads"]
+    xs, qn, kn = K.make_inputs(spec, "normal")
+    x = xs[-2]   # 127 rows
+    every = K.oracle_seq_kv8(oracle, x, 0, x.shape[0], Hq, Hkv, qn, kn)
+    last = K.oracle_seq_kv8(oracle, x, x.shape[0] - 1, 1, Hq, Hkv, qn, kn)
+    none = K.oracle_seq_kv8(oracle, x, x.shape[0], 0, Hq, Hkv, qn, kn)
+    assert np.array_equal(A.bits(last[0]), A.bits(every[0][-1:])) and none[0].shape[0] == 0
+    for a, b, c in zip(every[1:], last[1:], none[1:]):
+        assert np.array_equal(a, b) and np.array_equal(a, c)
+
+
+def _model_prompt(oracle, om, rows, seed):
+    desc, keep = oracle.make_prompt_desc(np.random.default_rng(seed).integers(0, 151643, size=rows), spk_emb=((np.arange(om.cfg.d_embed) % 13 - 6) * 0.03125).astype(np.float32))
+    return om.build_prompt(desc)[-rows:]
+
+
+@pytest.mark.parametrize("combine", [0, 1, 2])
+def test_oracle_model_kv_q8_changes_the_talker_and_is_deterministic(oracle, combine):
+    """Tiny shape, prompts of 5, 40 and 130 rows: with set_talker_kv_q8 the prefill logits differ in bits from the bf16-cache model's (alone,
+    and combined with set_talker_q8 / set_talker_q8a8 against the same mode without it), and two runs of generate give the same ids."""
+    from q3tts import _abi
+    cfg = _abi.tiny_config(max_batch=1, n_ctx=256, with_vocoder=0)
+    om, om8 = (oracle.OracleModel(cfg.model, seed=0, n_ctx=256, n_threads=8) for _ in range(2))
+    try:
+        for m in (om, om8):
+            if combine:
+                (m.set_talker_q8, m.set_talker_q8a8)[combine - 1]()
+        om8.set_talker_kv_q8()
+        for rows in (5, 40, 130):
+            pe = _model_prompt(oracle, om, rows, 700 + rows)
+            (h, l), (h8, l8) = om.talker_prefill(pe), om8.talker_prefill(pe)
+            assert np.all(np.isfinite(l8)) and not np.array_equal(A.bits(l8), A.bits(l)) and not np.array_equal(A.bits(h8), A.bits(h)), rows
+            assert np.abs(l8 - l).max() < 0.25 * np.abs(l).max(), rows   # another rounding of the cache, not another model
+            kw = dict(temperature=0.7, top_k=40, top_p=0.9, seed=rows, max_steps=6, min_frames=6)
+            a, b = om8.generate(pe, **kw), om8.generate(pe, **kw)
+            assert a[0].shape == (6, cfg.model.n_codebooks) and np.array_equal(a[0], b[0]) and a[1] == b[1], rows
+    finally:
+        om.close()
+        om8.close()
+
+
+def test_oracle_model_kv_q8_leaves_the_predictor_alone(oracle):
+    """A Talker of NO layers has no cache: there set_talker_kv_q8 must change nothing at all — the Predictor (five layers, 2 .. 16 keys per
+    frame, a bf16 cache as on the device) computes every code after the first, and all logits and ids stay the same. With the Talker's
+    layers back the same flag changes the logits of the same prompt."""
+    from q3tts import _abi
+    kw = dict(temperature=0.7, top_k=40, top_p=0.9, seed=3, max_steps=8, min_frames=8)
+    got = {}
+    for layers in (0, None):
+        cfg = _abi.tiny_config(max_batch=1, n_ctx=256, with_vocoder=0)
+        if layers is not None:
+            cfg.model.t_n_layer = layers
+        for kv in (0, 1):
+            om = oracle.OracleModel(cfg.model, seed=0, n_ctx=256, n_threads=8)
+            try:
+                if kv:
+                    om.set_talker_kv_q8()
+                pe = _model_prompt(oracle, om, 40, 740)
+                got[layers, kv] = (om.talker_prefill(pe)[1], om.generate(pe, **kw)[0])
+            finally:
+                om.close()
+    assert np.array_equal(A.bits(got[0, 0][0]), A.bits(got[0, 1][0])) and np.array_equal(got[0, 0][1], got[0, 1][1])
+    assert got[0, 0][1].shape[0] == 8 and len(np.unique(got[0, 0][1])) > 16
+    assert not np.array_equal(A.bits(got[None, 0][0]), A.bits(got[None, 1][0]))
+
+
+def test_equality_with_the_oracle_kv_q8_pins_the_summation_order(oracle):
+    """What `==` against q3o_attention_kv_q8 adds to the float64 bound: the same attention over the SAME cache and the same q in another
+    f32 summation order (numpy's) is inside ATT_STAGE2_TOL — the float64 checks accept it — and differs from the oracle in the bits of
+    most outputs. And a cache read with the scales of the neighbouring block is outside the bound."""
+    spec = K.SPEC["prefill_a"]
+    Hq, Hkv = spec["heads"]
+    xs, qn, kn, res = K.oracle_case_kv8(oracle, spec, "normal")
+    x, (out, k_q, k_d, v_q, v_d) = xs[-1], res[-1]   # the run of 128 rows
+    q = K.oracle_q(oracle, x, Hq, Hkv, qn, kn)
+    other = K.attend32(q, K.dequant(k_q, k_d), K.dequant(v_q, v_d), 0, Hq, Hkv)
+    assert K.stage2_error(other, q, k_q, k_d, v_q, v_d, 0, Hq, Hkv) <= ATT_STAGE2_TOL
+    assert (A.bits(other) != A.bits(out)).mean() > 0.5
+    swapped = K.attend32(q, K.dequant(k_q, k_d[..., ::-1]), K.dequant(v_q, v_d), 0, Hq, Hkv)
+    assert K.stage2_error(swapped, q, k_q, k_d, v_q, v_d, 0, Hq, Hkv) > ATT_STAGE2_TOL

@@ -6,9 +6,11 @@ Kernel level, one launch at a time through q3tts_k_attention_runs_kv8 / _decode_
   3. the last row of a sequence through the decode hook equals the same row of the sequence run as one prefill run, all 32 bits;
   4. on the int8 grid (x^ = v = bf16(v), every score 0) the output equals q3o_attention's, all 32 bits;
   5. output forms 1 and 2 are the form-0 output converted by the existing rules.
+  6. cache and output equal the oracle's Q8_0 cache mode (q3o_attention_kv_q8), every bit, on every case, kind and kernel.
 Engine level (tiny shape, kv_q8_0 = 1): ids and PCM do not depend on the batch, the slot count, sessions or voice prefixes; the memory
-formula; kv_q8_0 = 0 is today's engine; kv_q8_0 = 2 is refused. Ids with the Q8_0 cache may differ from the bf16 cache's: that is
-recorded by tools/kv_q8_bench.py, not asserted."""
+formula; kv_q8_0 = 0 is today's engine; kv_q8_0 = 2 is refused; prefill hidden / logits and ids equal the oracle's with
+set_talker_kv_q8 (prompts over the key-block edges, greedy and sampled, a batch with reused slots, voice prefixes, three layers,
+talker_q8_0 = 2, the full shape), and the bf16-cache oracle gives other logits and other sampled ids."""
 import ctypes as C
 
 import numpy as np
@@ -305,3 +307,202 @@ def test_kv_q8_0_other_values_are_refused():
         h = C.c_void_p()
         assert lib.q3tts_engine_create(C.byref(cfg), C.byref(h)) == -1 and not h.value   # Q3TTS_ERR_INVALID
         assert b"kv_q8_0" in lib.q3tts_last_error(None)
+
+
+# ---- the kernels against the oracle's Q8_0 cache mode, bit for bit ----------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(K.CASES))
+def test_kv8_kernel_case_equals_the_oracle(oracle, name):
+    """Every case x input kind x kernel the case names against q3o_attention_kv_q8 with `==`: the cache (quants and f16 scale bits of K and
+    V, nothing written past the sequence's end) and the f32 output, all 32 bits. K is not zero here (unlike the grid case), so this is what
+    pins the ORDER of the score chain over x^ = f32(d) * q, and the quantiser's f32 input (the norm's and the rotation's own order), to
+    DESIGN.md §4.4 / §22; decode_long runs k_attend_gqa2_kv8 past 256 keys on every kind, `wide` and `newest` among them, with the
+    newest key served from LDS. The float64 checks of test_kv8_kernel_case stay: they keep the oracle and the device from being wrong
+    together (tests/test_kv_q8_cpu.py holds the oracle to them too)."""
+    from q3tts import _abi, native
+    lib = _abi.load_library()
+    case = K.CASES[name]
+    spec = case["spec"]
+    try:
+        for kind in K.KINDS:
+            xs, qn, kn, res = K.oracle_case_kv8(oracle, spec, kind)
+            for policy, code in case["variants"]:
+                what = (name, kind, K.KERNELS[code])
+                _policy(lib, case, policy)
+                assert native.k_attend_pick_kv8(want_code=True, **K.pick_args(case)) == code, what
+                r = K.launch(native, case, policy, xs, qn, kn, 0)
+                for i, (dev, (pos0, n), want) in enumerate(zip(A.hook_out_split(spec, r["out"]), spec["seqs"], res)):
+                    tot = pos0 + n
+                    for key, got, ref in zip(("k_q", "k_d", "v_q", "v_d"), _per_seq(case, r, i), want[1:]):
+                        assert np.array_equal(got[:tot], ref) and not got[tot:].any(), what + (i, key)
+                    assert np.array_equal(A.bits(dev), A.bits(want[0])), what + (i, "out")
+    finally:
+        lib.q3tts_k_attend_policy(0, 0)
+
+
+# ---- engines with kv_q8_0 = 1 against the oracle with set_talker_kv_q8 ---------------------------------------------------------------------
+# Everything above the kernels — the scale pointers behind the quants in one allocation, the per-layer cache pointers, the prefix store's
+# scales, the layer and head a scale belongs to — is wrong in the same way for every batch size and slot count, so the invariants above
+# cannot see it. These tests tie one engine of each kind to the oracle; the invariants then carry that to 65 slots and sessions.
+class _Oracles:
+    """Pairs (bf16-cache model, Q8_0-cache model) of the tiny shape per (talker_q8_0, t_n_layer)."""
+
+    def __init__(self, oracle):
+        self.O, self.pairs = oracle, {}
+
+    def get(self, talker_q8=0, layers=None):
+        key = (talker_q8, layers)
+        if key not in self.pairs:
+            cfg = _cfg(1, talker_q8=talker_q8)
+            if layers is not None:
+                cfg.model.t_n_layer = layers
+            pair = tuple(self.O.OracleModel(cfg.model, seed=0, n_ctx=256, n_threads=8) for _ in range(2))
+            for m in pair:
+                if talker_q8 == 2:
+                    m.set_talker_q8a8()
+            pair[1].set_talker_kv_q8()
+            self.pairs[key] = pair
+        return self.pairs[key]
+
+    def close(self):
+        for pair in self.pairs.values():
+            for m in pair:
+                m.close()
+
+
+@pytest.fixture(scope="module")
+def oracles(oracle):
+    o = _Oracles(oracle)
+    yield o
+    o.close()
+
+
+def _prefill_equal(eng, om, om8, pe, what):
+    """eng.talker_prefill(pe) == the Q8_0-cache oracle's, hidden and logits, all bits; and the bf16-cache oracle's logits are others."""
+    h_ref, l_ref = om8.talker_prefill(pe)
+    assert not np.array_equal(_bits(l_ref), _bits(om.talker_prefill(pe)[1])), what   # an engine that ignored kv_q8_0 fails below
+    h, l = eng.talker_prefill(pe)
+    assert np.array_equal(_bits(l), _bits(l_ref)) and np.array_equal(_bits(h), _bits(h_ref)), what
+    return h_ref, l_ref
+
+
+def _generate_equal(eng, om, om8, r, what, prefix=None):
+    """One request through eng == the Q8_0-cache oracle alone (ids and hit_eos); a sampled request's ids differ from the bf16-cache
+    oracle's (a greedy one's need not: on the CPU oracle greedy ids of some prompts are the same under both caches)."""
+    ref, eos = om8.generate(r["embd"], **K.oracle_kw(r))
+    if r["temperature"] > 0:
+        assert not np.array_equal(ref, om.generate(r["embd"], **K.oracle_kw(r))[0]), what
+    got = eng.generate(**r) if prefix is None else eng.generate(**dict(r, embd=r["embd"][prefix[1]:], prefix=prefix[0]))
+    assert got.status == 0 and got.codes.shape == ref.shape and np.array_equal(got.codes, ref) and got.hit_eos == eos, what
+    return ref
+
+
+@pytest.mark.parametrize("talker_q8", [0, 2])
+def test_engine_prefill_equals_the_oracle(oracle, engines, oracles, talker_q8):
+    """Prompts of 1, 5, 63, 64, 65, 130 and 200 rows (the 64-key block edges) under prefill policies 0 and 2 and decode policies 0 and 1:
+    hidden and logits of the last row, all bits. With talker_q8_0 = 2 the attention kernels write Q8_0 blocks (att_out1 / att_out2)."""
+    from q3tts import _abi
+    lib = _abi.load_library()
+    eng = engines.get(8, talker_q8=talker_q8)
+    om, om8 = oracles.get(talker_q8)
+    try:
+        for rows in (1, 5, 63, 64, 65, 130, 200):
+            pe = K.prompt_rows(oracle, om, rows, 300)
+            ref = None
+            for dec, pre in ((0, 0), (1, 2), (0, 2), (1, 0)):
+                assert lib.q3tts_k_attend_policy(dec, pre) == 0
+                if ref is None:
+                    ref = _prefill_equal(eng, om, om8, pe, (rows, dec, pre))
+                else:
+                    h, l = eng.talker_prefill(pe)
+                    assert np.array_equal(_bits(l), _bits(ref[1])) and np.array_equal(_bits(h), _bits(ref[0])), (rows, dec, pre)
+    finally:
+        lib.q3tts_k_attend_policy(0, 0)
+
+
+@pytest.mark.parametrize("rows", [60, 130])
+def test_engine_generate_equals_the_oracle(oracle, engines, oracles, rows):
+    """Greedy and sampled, 12 frames: from 60 rows the decode step appends across position 64 (a new key block, its scales behind the
+    quants); from 130 rows it starts in the third block. Ids and hit_eos."""
+    eng = engines.get(8)
+    om, om8 = oracles.get()
+    pe = K.prompt_rows(oracle, om, rows, 5)
+    _prefill_equal(eng, om, om8, pe, rows)
+    for kw in (K.GREEDY, K.SAMPLED):
+        ref = _generate_equal(eng, om, om8, dict(embd=pe, seed=9, max_steps=12, min_frames=12, **kw), (rows, kw))
+        assert ref.shape[0] == 12
+    r = dict(embd=pe, seed=10, max_steps=12, min_frames=12, force_eos_at=7, **K.SAMPLED)
+    assert _generate_equal(eng, om, om8, r, (rows, "eos")).shape[0] == 7
+
+
+@pytest.mark.parametrize("talker_q8", [0, 2])
+def test_engine_batch_equals_the_oracle_alone(oracle, engines, oracles, talker_q8):
+    """11 sampled requests of 40 .. 130 prompt rows and forced lengths on 8 slots (three slots are used again): each == the oracle run
+    alone. With this the invariants above (65 slots, sessions) are tied to the reference."""
+    eng = engines.get(8, talker_q8=talker_q8)
+    om, om8 = oracles.get(talker_q8)
+    reqs = K.batch_requests(oracle, om, 11)
+    refs = [om8.generate(r["embd"], **K.oracle_kw(r)) for r in reqs]
+    for i, (r, ref) in enumerate(zip(reqs, refs)):
+        assert ref[0].shape[0] == r["force_eos_at"] and not np.array_equal(ref[0], om.generate(r["embd"], **K.oracle_kw(r))[0]), i
+    for i, (g, ref) in enumerate(zip(eng.generate_batch(reqs), refs)):
+        assert g.status == 0 and g.codes.shape == ref[0].shape and np.array_equal(g.codes, ref[0]) and g.hit_eos == ref[1], (talker_q8, i)
+
+
+@pytest.mark.parametrize("P,rows", [(40, 90), (64, 100)])
+def test_engine_voice_prefix_equals_the_oracle(oracle, engines, oracles, P, rows):
+    """create_prefix(w[:P]) + w[P:] == the oracle on the whole prompt w: P = 40 ends inside a key block (k_kv_prefix_kv8 copies the whole
+    block and the store's scales), P = 64 on its edge. Also talker_prefill_prefix == the oracle's prefill of w."""
+    eng = engines.get(8)
+    om, om8 = oracles.get()
+    w = K.prompt_rows(oracle, om, rows, P)
+    with eng.create_prefix(embd=w[:P]) as x:
+        _generate_equal(eng, om, om8, dict(embd=w, seed=P, max_steps=9, min_frames=9, **K.SAMPLED), (P, "prefix"), prefix=(x, P))
+        h_ref, l_ref = om8.talker_prefill(w)
+        assert not np.array_equal(_bits(l_ref), _bits(om.talker_prefill(w)[1]))
+        h, l = eng.talker_prefill_prefix(x, w[P:])
+        assert np.array_equal(_bits(l), _bits(l_ref)) and np.array_equal(_bits(h), _bits(h_ref)), P
+
+
+def test_engine_of_three_layers_equals_the_oracle(oracle, oracles):
+    """t_n_layer = 3: with two layers a wrong layer stride of the cache (or of its scales) can land on the other layer's rows of the same
+    slot and cancel in no test above; with three it cannot."""
+    from q3tts import native
+    cfg = _cfg(2)
+    cfg.model.t_n_layer, cfg.with_vocoder = 3, 0
+    om, om8 = oracles.get(0, 3)
+    eng = native.NativeEngine(cfg)
+    try:
+        pe = K.prompt_rows(oracle, om, 70, 3)
+        _prefill_equal(eng, om, om8, pe, "3 layers")
+        _generate_equal(eng, om, om8, dict(embd=pe, seed=3, max_steps=10, min_frames=10, **K.SAMPLED), "3 layers")
+        reqs = K.batch_requests(oracle, om, 4, frames=(4, 6), seed=33)
+        for i, (g, r) in enumerate(zip(eng.generate_batch(reqs), reqs)):
+            assert g.status == 0 and np.array_equal(g.codes, om8.generate(r["embd"], **K.oracle_kw(r))[0]), i
+    finally:
+        eng.close()
+
+
+def test_full_shape_kv_q8_0_prefill_and_frames(oracle):
+    """The benchmarked shape (Hkv = 8, 28 layers: the tiny shape covers neither) with kv_q8_0 = 1, laid out as
+    test_parity_gpu.py::test_talker_q8_0_full_shape_prefill_and_frames: prefill hidden / logits bits and 4 greedy frames == the oracle; the
+    bf16-cache oracle (the same model before the flag is set) gives other logits."""
+    from q3tts import _abi, native
+    cfg = _abi.full_config_py()
+    cfg.max_batch, cfg.n_ctx, cfg.max_steps_cap, cfg.with_vocoder, cfg.kv_q8_0 = 2, 128, 16, 0, 1
+    eng = native.NativeEngine(cfg)
+    om = oracle.OracleModel(cfg.model, seed=0, n_ctx=128, n_threads=16)
+    try:
+        desc, keep = oracle.make_prompt_desc(np.random.default_rng(1234).integers(0, 151643, size=12), spk_emb=K.spk(cfg.model.d_embed))
+        pe = om.build_prompt(desc)
+        l_bf16 = om.talker_prefill(pe)[1]
+        om.set_talker_kv_q8()
+        h_ref, l_ref = om.talker_prefill(pe)
+        assert not np.array_equal(_bits(l_ref), _bits(l_bf16))
+        h, l = eng.talker_prefill(pe)
+        assert np.array_equal(_bits(l), _bits(l_ref)) and np.array_equal(_bits(h), _bits(h_ref))
+        ref, _ = om.generate(pe, temperature=0.0, max_steps=4, min_frames=4)
+        res = eng.generate(desc=desc, temperature=0.0, max_steps=4, min_frames=4)
+        assert ref.shape == (4, 16) and np.array_equal(res.codes, ref)
+    finally:
+        eng.close()
+        om.close()
