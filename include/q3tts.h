@@ -338,7 +338,8 @@ int q3tts_stream_end(q3tts_stream* s, q3tts_result* out_codes_optional);
  * reference has no counterpart (it serves one request at a time and rebuilds the whole prompt each call, src/tts/engine.rs:390-466).
  *
  * q3tts_prefix_create: exactly one of p (its voice fields; n_text must be 0) or embd / n_tok (host rows [n_tok][d_embed]) is given;
- * 1 <= rows < n_ctx. Refused (Q3TTS_ERR_STATE) while a session is open. Destroy every prefix before its engine.
+ * 1 <= rows < n_ctx. Refused (Q3TTS_ERR_STATE) while a session is open — the session makes prefixes itself then ("voices in a session"
+ * below: q3tts_session_prefix_create, q3tts_session_submit_keep_voice). Destroy every prefix before its engine.
  * A request with prefix != NULL:
  *  - its prompt_embd / n_tok are the rows after the prefix; otherwise `prompt` builds only the text part: text_ids are used and every
  *    voice field must be in its None state (instruct_ids NULL, lang_id < 0, spk_id < 0, spk_emb NULL, ref_codes NULL, ref_text_ids NULL),
@@ -417,6 +418,47 @@ int q3tts_session_next(q3tts_session* s, int32_t timeout_ms, q3tts_session_event
 int q3tts_session_close(q3tts_session* s);
 /* Message of the last failing session call or of the worker's failure. */
 const char* q3tts_session_last_error(const q3tts_session* s);
+
+/* ---- voices in a session: create prefixes and clone voices while the batch runs --------------------------------
+ * Voice work as part of the running batch. Prefix jobs and requests share the session's one FIFO; the worker stays the only thread that
+ * touches the GPU. The reference has no counterpart.
+ *
+ *  - q3tts_session_prefix_create: a standalone prefix job, arguments as q3tts_prefix_create (copied before it returns). At a chunk
+ *    boundary its voice rows take a free slot, ride the same batched prefill as the requests admitted there, and the slot's first P
+ *    positions are copied into the prefix's store; the slot is free again from the next boundary. 1 <= P < n_ctx.
+ *  - q3tts_session_submit_keep_voice: a whole-prompt request whose voice part is kept. After its prefill the first voice_rows positions
+ *    of its slot are copied into the store: no second prefill. voice_rows = 0 takes the voice part of req->prompt (the whole prompt
+ *    minus its n_text + 3 text rows, 2 with text_stream); a prompt_embd request states it (1 <= voice_rows < n_tok). A request that
+ *    names a prefix cannot keep one (Q3TTS_ERR_INVALID).
+ *    Either store is byte for byte the one q3tts_prefix_create makes of the same rows.
+ *  - Both are thread-safe, return at once and hand out a handle that is valid immediately, in the pending state: q3tts_prefix_state is 0
+ *    (pending), 1 (ready) or < 0 (the status it failed with); q3tts_prefix_rows is 0 until it is ready. When the store is written (or the
+ *    entry failed) a Q3TTS_EV_PREFIX event with the call's id and the status is published: is_final = 1 for a job, 0 for a keep-voice
+ *    request, whose own events follow as usual. A keep-voice request that fails at admission fails its prefix with the same status; one
+ *    cancelled before admission (and a cancelled job) fails it with Q3TTS_ERR_STATE, and the PREFIX event says so.
+ *  - A request may name a pending prefix: the worker does not take it, or anything behind it in the FIFO, until the prefix is ready. If
+ *    the prefix failed, the request gets FAILED / Q3TTS_ERR_INVALID with a message. Prefixes made before the session opened work as ever.
+ *  - q3tts_session_prefix_release (thread-safe) gives a handle back during the session, whatever its state: a later submit that names it
+ *    returns Q3TTS_ERR_INVALID, and the worker frees the store once no queued request names it (admitted requests hold their own copy).
+ *    Every handle is given back exactly once: released during the session, or passed to q3tts_prefix_destroy after
+ *    q3tts_session_close. Close cancels pending jobs, whose handles then read failed; ready prefixes survive it as ordinary prefixes.
+ *  - q3tts_session_clone blocks its caller while the worker runs the clone encoders between two chunk boundaries, on the engine's
+ *    stream: audio at `rate` Hz (converted to 24000 Hz by the device resampler first when it differs, as q3tts_resample does) -> codes
+ *    [n_frames][ae_n_codebooks] and the speaker embedding, bit for bit what q3tts_clone_audio_encode / q3tts_clone_speaker_encode give
+ *    outside a session. Either output may be NULL. Q3TTS_ERR_STATE before q3tts_clone_init ("not loaded"), and once the session is
+ *    closing or its worker has failed (a waiting caller is woken then). Clone calls do not queue behind requests, and the caller may
+ *    be the consumer thread: a worker that waits for staging space (events nobody reads meanwhile) serves clone calls while it waits.
+ * Still refused while a session is open (Q3TTS_ERR_STATE): q3tts_prefix_create, q3tts_prefix_destroy, q3tts_clone_audio_encode,
+ * q3tts_clone_speaker_encode, q3tts_clone_init, q3tts_mel, q3tts_resample, and everything "sessions" lists above. */
+#define Q3TTS_EV_PREFIX 5
+int q3tts_session_prefix_create(q3tts_session* s, const q3tts_prompt_desc* p, const float* embd, int32_t n_tok,
+                                q3tts_prefix** out, uint64_t* id);
+int q3tts_session_submit_keep_voice(q3tts_session* s, const q3tts_request* req, int32_t voice_rows /* 0: from the desc */,
+                                    uint64_t* id, q3tts_prefix** out);
+int q3tts_session_prefix_release(q3tts_session* s, q3tts_prefix* x);
+int q3tts_session_clone(q3tts_session* s, const float* audio, int64_t n_samples, int32_t rate,
+                        int64_t* codes, int32_t cap_frames, int32_t* n_frames, float* spk_emb);
+int32_t q3tts_prefix_state(const q3tts_prefix* x);   /* 0 pending, 1 ready, < 0 the status it failed with */
 
 /* ---- streaming text input: feed a running request its text as it arrives ---------------------------------------
  * The reference puts a request's whole text into the prompt (build_core, src/tts/prompt.rs:229-264) and adds tts_pad to every feedback
@@ -663,6 +705,9 @@ int q3tts_k_talker_prefill(q3tts_engine* e, const float* embd, int32_t n_tok, fl
 /* The same behind a voice prefix: the prompt is the prefix's rows followed by embd [n_tok][d_embed] */
 int q3tts_k_talker_prefill_prefix(q3tts_engine* e, const q3tts_prefix* prefix, const float* embd, int32_t n_tok, float* hidden_out,
                                   float* logits_out);
+/* A ready prefix's K store and V store as bytes, zero padding included: *bytes receives the size of each (k = v = NULL only asks for it);
+ * cap = bytes each of k / v holds. Refused while a session is open on the prefix's engine. */
+int q3tts_k_prefix_read(const q3tts_prefix* x, void* k, void* v, int64_t cap, int64_t* bytes);
 /* Vocoder: codes [n_frames][n_codebooks] -> pcm; chunk_frames frames per streaming call (0 = one call) */
 int q3tts_k_vocoder(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, float* pcm_out,
                     int32_t* n_samples_out);

@@ -931,3 +931,35 @@ void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s) {
     if (a.kv8) { q3_launch_kv_prefix_kv8(a, s); return; }
     hipLaunchKernelGGL(k_kv_prefix, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
 }
+
+// The inverse (sessions): the first P positions of slot[j] into the store pk[j] / pv[j], which becomes byte for byte what
+// q3tts_prefix_create writes for the same rows. That store is zero outside positions < P, so the keys P .. np - 1 of the last block —
+// in the slot they are the request's own rows, or an earlier occupant's — are written as zeros, and values stop at P (the store comes
+// zero-filled from its allocator). 16-byte unit i of a head's keys holds key (i & 63) of block i / (8 hd).
+__global__ __launch_bounds__(256) void k_kv_prefix_save(Q3KvPrefix a) {
+    const int j = blockIdx.y, isv = blockIdx.x & 1, lg = blockIdx.x >> 1, l = lg / a.Hkv, g = lg - l * a.Hkv;
+    const int P = a.P[j], np = (P + 63) & ~63;
+    const size_t dst = ((size_t)l * a.Hkv + g) * np * a.hd;
+    const size_t src = (size_t)l * a.layer_stride + ((size_t)a.slot[j] * a.Hkv + g) * a.n_ctx * a.hd;
+    const uint4* sp = (const uint4*)((isv ? a.vc : a.kc) + src);
+    uint4* dp = (uint4*)(const_cast<uint16_t*>(isv ? a.pv[j] : a.pk[j]) + dst);
+    if (isv) {
+        const int n16 = P * (a.hd >> 3);
+        for (int i = threadIdx.x; i < n16; i += 256) dp[i] = sp[i];
+        return;
+    }
+    const int n16 = np * (a.hd >> 3), per_blk = a.hd * 8;
+    for (int i = threadIdx.x; i < n16; i += 256) {
+        const int pos = (i / per_blk) * 64 + (i & 63);
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (pos < P) v = sp[i];
+        dp[i] = v;
+    }
+}
+int q3_launch_kv_prefix_save(const Q3KvPrefix& a, hipStream_t s) {
+    if (a.n <= 0) return 0;
+    if (a.hd != Q3_ATT_HD || a.n > Q3_KVP_MAX) return 1;
+    if (a.kv8) return q3_launch_kv_prefix_save_kv8(a, s);
+    hipLaunchKernelGGL(k_kv_prefix_save, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
+    return 0;
+}

@@ -457,6 +457,47 @@ __global__ __launch_bounds__(256) void k_kv_prefix_kv8(Q3KvPrefix a) {
     const uint2* s8 = (const uint2*)(ss + sh * nb); uint2* d8 = (uint2*)ds;   // hd / 32 = 4 scales per position: 8 bytes
     for (int i = threadIdx.x; i < n; i += 256) d8[i] = s8[i];
 }
+
+// The inverse (k_kv_prefix_save, q3_attend.hip): quants and scales of positions < P of slot[j] into the store, zeros for the keys
+// P .. np - 1 of the last block (quants and scales), values only below P. 16-byte unit i of a head's key quants holds key (i & 63) of
+// block i / (4 hd); scale i of a head's keys (q3_kv8_kd_idx) belongs to key (i & 63) of block i / (64 hd / 32), four per 8-byte unit.
+__global__ __launch_bounds__(256) void k_kv_prefix_save_kv8(Q3KvPrefix a) {
+    const int j = blockIdx.y, isv = blockIdx.x & 1, lg = blockIdx.x >> 1, l = lg / a.Hkv, g = lg - l * a.Hkv;
+    const int P = a.P[j], np = (P + 63) & ~63, nb = a.hd >> 5;
+    const size_t store_q = (size_t)a.L * a.Hkv * np * a.hd;
+    const size_t dh = ((size_t)l * a.Hkv + g) * np;                    // the head's first position in the store ...
+    const size_t sh = ((size_t)a.slot[j] * a.Hkv + g) * a.n_ctx;       // ... and in the layer's cache
+    int8_t* dq = const_cast<int8_t*>((const int8_t*)(isv ? a.pv[j] : a.pk[j]));
+    uint16_t* dsc = (uint16_t*)(dq + store_q);
+    const int8_t* sq = (const int8_t*)(isv ? a.vc : a.kc) + (size_t)l * a.layer_stride + sh * a.hd;
+    const uint16_t* ssc = (isv ? a.vd : a.kd) + (size_t)l * (a.layer_stride >> 5) + sh * nb;
+    const uint4* s16 = (const uint4*)sq; uint4* d16 = (uint4*)(dq + dh * a.hd);
+    const uint2* s8 = (const uint2*)ssc; uint2* d8 = (uint2*)(dsc + dh * nb);
+    if (isv) {
+        for (int i = threadIdx.x; i < P * (a.hd >> 4); i += 256) d16[i] = s16[i];
+        for (int i = threadIdx.x; i < P; i += 256) d8[i] = s8[i];
+        return;
+    }
+    const int per_blk = a.hd * 4;
+    for (int i = threadIdx.x; i < np * (a.hd >> 4); i += 256) {
+        const int pos = (i / per_blk) * 64 + (i & 63);
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (pos < P) v = s16[i];
+        d16[i] = v;
+    }
+    const int sc_blk = nb * 64;
+    for (int i = threadIdx.x; i < np; i += 256) {  // np * nb scales, nb = 4 per unit: keys p0 .. p0 + 3 of one 32-dim block
+        const int k0 = i * 4, p0 = (k0 / sc_blk) * 64 + (k0 & 63);
+        uint2 v = make_uint2(0u, 0u);
+        if (p0 < P) {
+            v = s8[i];
+            if (p0 + 1 >= P) v.x &= 0xffffu;
+            if (p0 + 2 >= P) v.y = 0u;
+            else if (p0 + 3 >= P) v.y &= 0xffffu;
+        }
+        d8[i] = v;
+    }
+}
 }  // namespace
 
 int q3_launch_qk_prep_kv8(const Q3QkPrep& a, hipStream_t s) {
@@ -467,6 +508,12 @@ int q3_launch_qk_prep_kv8(const Q3QkPrep& a, hipStream_t s) {
 void q3_launch_kv_prefix_kv8(const Q3KvPrefix& a, hipStream_t s) {
     if (a.n <= 0 || a.hd != Q3_ATT_HD) return;
     hipLaunchKernelGGL(k_kv_prefix_kv8, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
+}
+int q3_launch_kv_prefix_save_kv8(const Q3KvPrefix& a, hipStream_t s) {
+    if (a.n <= 0) return 0;
+    if (a.hd != Q3_ATT_HD || a.n > Q3_KVP_MAX || !a.kd || !a.vd) return 1;
+    hipLaunchKernelGGL(k_kv_prefix_save_kv8, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
+    return 0;
 }
 
 // The kernel q3_launch_attend_kv8 takes (q3_attend_pick asks here when a.kv8 is set; q3tts_k_attend_pick_kv8 reports it). Whole prompt runs

@@ -717,6 +717,9 @@ int audio_run(q3tts_engine* e, const float* audio, int64_t n, int64_t* codes, fl
 extern "C" int q3tts_clone_audio_encode(q3tts_engine* e, const float* audio, int64_t n_samples, int64_t* codes, int32_t cap_frames,
                                         int32_t* n_frames) {
     Q3_NOT_IN_SESSION(e);
+    return q3_clone_audio_encode_run(e, audio, n_samples, codes, cap_frames, n_frames);
+}
+int q3_clone_audio_encode_run(q3tts_engine* e, const float* audio, int64_t n_samples, int64_t* codes, int32_t cap_frames, int32_t* n_frames) {
     if (!e) return Q3TTS_ERR_INVALID;
     if (!codes) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
     return audio_run(e, audio, n_samples, codes, nullptr, cap_frames, n_frames);
@@ -731,6 +734,9 @@ extern "C" int q3tts_k_audio_latent(q3tts_engine* e, const float* audio, int64_t
 
 extern "C" int q3tts_clone_speaker_encode(q3tts_engine* e, const float* audio, int64_t n_samples, float* spk_emb) {
     Q3_NOT_IN_SESSION(e);
+    return q3_clone_speaker_encode_run(e, audio, n_samples, spk_emb);
+}
+int q3_clone_speaker_encode_run(q3tts_engine* e, const float* audio, int64_t n_samples, float* spk_emb) {
     if (!e) return Q3TTS_ERR_INVALID;
     if (!e->clone) return not_loaded(e, "SpeakerEncoder");
     if (!spk_emb || n_samples < 0 || (n_samples > 0 && !audio)) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");

@@ -162,7 +162,13 @@ struct q3tts_prefix {
     q3tts_engine* e = nullptr;          // the engine that made it (and whose slots it may enter)
     int P = 0, np = 0;
     uint16_t *k = nullptr, *v = nullptr;  // (kv_q8_0: int8 quants [L][Hkv][np * hd], then their f16 scales [L][Hkv][np * hd / 32])
+    // A prefix made through a session (q3_session.hip) exists before its store does. state: 0 pending, 1 ready, < 0 the
+    // status it failed with; the worker writes P / np / k / v and then state (release), any thread reads state first (acquire).
+    // released / qrefs (the session's mutex): q3tts_session_prefix_release was called; queued requests of the session that name it.
+    std::atomic<int> state{1};
+    bool released = false; int qrefs = 0;
 };
+size_t q3_prefix_store_bytes(const q3tts_engine* e, int np);  // bytes of ONE of a prefix's two stores (k or v) of np positions
 
 // helpers shared with q3_vocoder.hip and the kernel-level test hooks (q3_hooks.hip)
 int q3_set_err(q3tts_engine* e, int code, const std::string& msg);
@@ -282,7 +288,22 @@ enum { BOS_TOKEN = 151672, EOS_TOKEN = 151673 };  // tts_bos, tts_eos (src/tts/p
 // (q3_plan_rows + q3_admit_many are also the single-request admission of the talker-prefill hook)
 int q3_plan_rows(q3tts_engine* e, const std::vector<int>& live);
 int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc);
+// One entry of an admission group in its general form (q3_admit_many passes requests only). keep != null: after the group's layers the
+// slot's first rows are saved into that (empty) prefix — a request's voice part (keep_rows, 0: taken from r->prompt; 1 <= rows < n), or
+// with r == null a prefill-only prefix job: voice / embd + n_tok as q3tts_prefix_create takes them, into a free slot that stays free.
+// The store is allocated here; the caller marks the prefix ready once the call has succeeded for the item.
+struct Q3AdmItem {
+    int slot; const q3tts_request* r;
+    q3tts_prefix* keep; int keep_rows;
+    const q3tts_prompt_desc* voice; const float* embd; int n_tok;
+};
+int q3_admit_items(q3tts_engine* e, const Q3AdmItem* items, int count, int* rc);
 int q3_run_chunk(q3tts_engine* e, int CH);
+// the bodies of q3tts_clone_audio_encode / q3tts_clone_speaker_encode / q3tts_resample without the session check: the session worker
+// runs them on the engine's stream between two chunk boundaries (q3tts_session_clone)
+int q3_clone_audio_encode_run(q3tts_engine* e, const float* audio, int64_t n_samples, int64_t* codes, int32_t cap_frames, int32_t* n_frames);
+int q3_clone_speaker_encode_run(q3tts_engine* e, const float* audio, int64_t n_samples, float* spk_emb);
+int q3_resample_run(q3tts_engine* e, const float* in, int64_t n_in, int32_t rate_in, int32_t rate_out, float* out, int64_t cap, int64_t* n_out);
 // streamed text, between frame steps: slot b's trailing ids become T[0, n) (entries [from, n) are uploaded; the first max_steps_cap count)
 // and its cursor the row of frame n_frames. n = 0: the slot takes tts_pad (a request without text_stream).
 int q3_text_rows_set(q3tts_engine* e, int b, const int32_t* T, int from, int n, int n_frames);

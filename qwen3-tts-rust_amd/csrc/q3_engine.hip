@@ -657,7 +657,10 @@ static uint64_t wall_seed() {
 // seeds the slot (logits, state, sampler draws). rc[i] receives the per-request status.
 // A request behind a voice prefix (P > 0 rows) brings only its own n rows: they sit at positions P .. P + n - 1 of its slot, whose first
 // P positions receive a copy of the prefix's K/V (k_kv_prefix, one launch for the group) before the layers run.
-struct Adm { int b; const q3tts_request* r; int n, row0, max_steps, P; };
+// keep (sessions): after the group's layers, positions 0 .. keep_rows - 1 of the slot are copied into that prefix's store
+// (k_kv_prefix_save, one launch for the group). r == null: a prefill-only prefix job — its voice rows ride the group's prefill into a
+// free slot and are saved; no head GEMM, no draws, no slot record, no vocoder reset: the slot never becomes active.
+struct Adm { int b; const q3tts_request* r; int n, row0, max_steps, P; q3tts_prefix* keep; int keep_rows; };
 
 // ---- streamed text (include/q3tts.h, "streaming text input") ----
 void q3_text_trailing(const q3tts_request* r, std::vector<int32_t>& T) {
@@ -753,8 +756,21 @@ static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
     if (rl < 0) return Q3TTS_ERR_DEVICE;
     if (rl) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefill: a kernel launch was refused for this model shape");
     Q3_HIP(e, hipGetLastError());
+    bool keeps = false;
+    for (const Adm& a : grp) keeps |= a.keep != nullptr;
+    if (keeps) {  // the slots' voice rows into their prefix stores, behind the layers on the same stream
+        Q3KvPrefix sv = kp; sv.n = 0;
+        for (const Adm& a : grp) {
+            if (!a.keep) continue;
+            if (sv.n == Q3_KVP_MAX) { if (q3_launch_kv_prefix_save(sv, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix save: launch refused for this model shape"); sv.n = 0; }
+            sv.pk[sv.n] = a.keep->k; sv.pv[sv.n] = a.keep->v; sv.P[sv.n] = a.keep_rows; sv.slot[sv.n] = a.b; ++sv.n;
+        }
+        if (q3_launch_kv_prefix_save(sv, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix save: launch refused for this model shape");
+        Q3_HIP(e, hipGetLastError());
+    }
     for (const Adm& a : grp) {
         const q3tts_request* r = a.r;
+        if (!r) continue;  // a prefix job: the slot stays free
         const int b = a.b;
         Q3Lane& L = e->lane;
         const int row = e->row_of_slot[b];
@@ -798,19 +814,66 @@ static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
     return Q3TTS_OK;
 }
 
-// slots[i] <- reqs[i]; rc[i] = status of request i (a failing request does not stop the others)
-static int admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc) {
+// bytes of one of a prefix's two stores of np positions, in the slots' format: bf16, or Q8_0 quants with their f16 scales behind them
+size_t q3_prefix_store_bytes(const q3tts_engine* e, int np) {
+    const size_t per = (size_t)e->T.L * e->T.Hkv * np * e->T.hd;
+    return e->T.kv8 ? per + per / 16 : per * 2;
+}
+// the zero-filled store of a prefix that a slot's first `rows` positions will be saved into (k_kv_prefix_save)
+static int prefix_store_alloc(q3tts_engine* e, q3tts_prefix* x, int rows) {
+    if (e->T.hd != Q3_ATT_HD) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the save kernel needs head_dim 128");
+    if (x->k || x->v || x->e != e) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the handle to fill is not an empty one of this engine");
+    const int np = (rows + 63) & ~63;
+    const size_t store = q3_prefix_store_bytes(e, np);
+    int rc = q3_dev_alloc_zeroed(e, (void**)&x->k, store);
+    if (rc == Q3TTS_OK) { rc = q3_dev_alloc_zeroed(e, (void**)&x->v, store); if (rc != Q3TTS_OK) e->dev_bytes -= store; }
+    if (rc != Q3TTS_OK) { hipFree(x->k); x->k = x->v = nullptr; return rc; }
+    x->P = rows; x->np = np;
+    return Q3TTS_OK;
+}
+
+// items[i] enters its slot; rc[i] = status of item i (a failing item does not stop the others)
+static int admit_items(q3tts_engine* e, const Q3AdmItem* items, int count, int* rc) {
     const q3tts_model_config& m = e->cfg.model;
     hipStream_t s = e->stream;
     std::vector<Adm> grp;
     int total = 0;
     for (int i = 0; i < count; ++i) {
-        const q3tts_request* r = reqs[i];
+        const Q3AdmItem& it = items[i];
+        const q3tts_request* r = it.r;
         rc[i] = Q3TTS_OK;
+        if (!r) {  // a prefill-only prefix job: 1 <= rows < n_ctx, as q3tts_prefix_create
+            if (!it.keep || (it.voice != nullptr) == (it.embd != nullptr)) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: give exactly one of a voice desc or host rows"); continue; }
+            int n = 0;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                const int room = std::min(e->cfg.n_ctx - total, e->cfg.n_ctx - 1);
+                if (it.embd) {
+                    n = it.n_tok;
+                    if (n <= 0 || n >= e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: n_tok outside 1 .. n_ctx - 1"); break; }
+                    if (n <= room) { Q3_HIP(e, hipMemcpyAsync(e->pf.x + (size_t)total * m.d_embed, it.embd, (size_t)n * m.d_embed * 4, hipMemcpyHostToDevice, s)); break; }
+                } else {
+                    const int brc = build_prompt_dev(e, it.voice, e->pf.x + (size_t)total * m.d_embed, room, &n, PROMPT_VOICE);
+                    if (brc == Q3TTS_OK) break;
+                    if (total == 0) { rc[i] = brc; break; }
+                }
+                TRY(admit_group(e, grp, total));  // batch full: flush, then retry this job in an empty batch
+                grp.clear(); total = 0;
+            }
+            if (rc[i] == Q3TTS_OK && n < 1) rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the voice part has no rows");
+            if (rc[i] == Q3TTS_OK) rc[i] = prefix_store_alloc(e, it.keep, n);
+            if (rc[i] != Q3TTS_OK) continue;
+            grp.push_back(Adm{it.slot, nullptr, n, total, 0, 0, it.keep, n});
+            total += n;
+            continue;
+        }
         const int max_steps = r->max_steps > 0 ? r->max_steps : e->max_steps;
         if (max_steps > e->cfg.max_steps_cap) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "max_steps exceeds max_steps_cap"); continue; }
         const q3tts_prefix* x = r->prefix;
         if (x && x->e != e) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: made by another engine"); continue; }
+        if (x && x->state.load(std::memory_order_acquire) != 1) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: not ready (a session's pending or failed prefix)"); continue; }
+        if (x && it.keep) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "keep-voice: a request that names a prefix cannot keep one"); continue; }
+        if (it.keep && it.keep_rows == 0 && (r->prompt_embd || !r->prompt)) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "keep-voice: a prompt_embd request states its voice rows"); continue; }
+        if (it.keep && it.keep_rows < 0) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "keep-voice: voice_rows is negative"); continue; }
         const int P = x ? x->P : 0;  // the prefix's rows come first; only the request's own rows enter the prefill buffer
         if ((r->text_open == 1) && !(r->text_stream == 1)) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "text_open needs text_stream = 1"); continue; }
         if (r->text_stream == 1) {
@@ -838,10 +901,24 @@ static int admit_many(q3tts_engine* e, const int* slots, const q3tts_request* co
         if (rc[i] != Q3TTS_OK) continue;
         if (P + n > e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix + prompt longer than n_ctx"); continue; }
         if (P + n + max_steps > e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prompt + max_steps exceeds n_ctx"); continue; }
-        grp.push_back(Adm{slots[i], r, n, total, max_steps, P});
+        int keep_rows = 0;
+        if (it.keep) {  // the voice part of a whole prompt: everything in front of the text part's n_text + 3 rows (text_stream: 2)
+            keep_rows = it.keep_rows > 0 ? it.keep_rows : n - (r->text_stream == 1 ? 2 : r->prompt->n_text + 3);
+            if (keep_rows < 1 || keep_rows >= n) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "keep-voice: voice_rows outside 1 .. n - 1"); continue; }
+            rc[i] = prefix_store_alloc(e, it.keep, keep_rows);
+            if (rc[i] != Q3TTS_OK) continue;
+        }
+        grp.push_back(Adm{it.slot, r, n, total, max_steps, P, it.keep, keep_rows});
         total += n;
     }
     return admit_group(e, grp, total);
+}
+
+// slots[i] <- reqs[i]; rc[i] = status of request i (a failing request does not stop the others)
+static int admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc) {
+    std::vector<Q3AdmItem> items(count);
+    for (int i = 0; i < count; ++i) { items[i] = Q3AdmItem{}; items[i].slot = slots[i]; items[i].r = reqs[i]; }
+    return admit_items(e, items.data(), count, rc);
 }
 
 static int admit(q3tts_engine* e, int b, const q3tts_request* r) {
@@ -895,7 +972,8 @@ extern "C" int q3tts_prefix_create(q3tts_engine* e, const q3tts_prompt_desc* p, 
     *out = x;
     return Q3TTS_OK;
 }
-extern "C" int32_t q3tts_prefix_rows(const q3tts_prefix* x) { return x ? x->P : 0; }
+extern "C" int32_t q3tts_prefix_rows(const q3tts_prefix* x) { return x && x->state.load(std::memory_order_acquire) == 1 ? x->P : 0; }
+extern "C" int32_t q3tts_prefix_state(const q3tts_prefix* x) { return x ? x->state.load(std::memory_order_acquire) : Q3TTS_ERR_INVALID; }
 extern "C" int q3tts_prefix_destroy(q3tts_prefix* x) {
     if (!x) return Q3TTS_OK;
     q3tts_engine* e = x->e;
@@ -1183,6 +1261,7 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
 // the scheduler steps as the session worker drives them (q3_session.hip)
 int q3_plan_rows(q3tts_engine* e, const std::vector<int>& live) { return plan_rows(e, live); }
 int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc) { return admit_many(e, slots, reqs, count, rc); }
+int q3_admit_items(q3tts_engine* e, const Q3AdmItem* items, int count, int* rc) { return admit_items(e, items, count, rc); }
 int q3_run_chunk(q3tts_engine* e, int CH) { return run_chunk(e, CH, nullptr); }
 double q3_now_ms() { return now_ms(); }
 

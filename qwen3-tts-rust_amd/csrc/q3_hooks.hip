@@ -882,6 +882,23 @@ extern "C" int q3tts_k_talker_prefill_prefix(q3tts_engine* e, const q3tts_prefix
     return talker_prefill(e, prefix, embd, n_tok, hidden_out, logits_out);
 }
 
+// a ready prefix's two stores as bytes, padding included (*bytes: the size of each; k / v may be null to ask for it)
+extern "C" int q3tts_k_prefix_read(const q3tts_prefix* x, void* k, void* v, int64_t cap, int64_t* bytes) {
+    if (!x || !bytes) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    q3tts_engine* e = x->e;
+    Q3_NOT_IN_SESSION(e);
+    if (x->state.load() != 1 || !x->k || !x->v) return q3_set_err(e, Q3TTS_ERR_STATE, "prefix read: the prefix is not ready");
+    const size_t n = q3_prefix_store_bytes(e, x->np);
+    *bytes = (int64_t)n;
+    if (!k && !v) return Q3TTS_OK;
+    if (cap < (int64_t)n) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix read: the buffers hold fewer than *bytes bytes");
+    Q3_HIP(e, hipSetDevice(e->cfg.device));
+    Q3_HIP(e, hipStreamSynchronize(e->stream));
+    if (k) Q3_HIP(e, hipMemcpy(k, x->k, n, hipMemcpyDeviceToHost));
+    if (v) Q3_HIP(e, hipMemcpy(v, x->v, n, hipMemcpyDeviceToHost));
+    return Q3TTS_OK;
+}
+
 extern "C" int q3tts_k_probe(q3tts_engine* e, int32_t enable) {
     Q3_NOT_IN_SESSION(e);
     if (!e) return Q3TTS_ERR_INVALID;

@@ -390,6 +390,12 @@ struct Q3KvPrefix {
 };
 void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s);
 void q3_launch_kv_prefix_kv8(const Q3KvPrefix& a, hipStream_t s);  // (q3_attend_kv8.hip; q3_launch_kv_prefix hands over when kv8 is set)
+// The other direction (k_kv_prefix_save / k_kv_prefix_save_kv8): positions < P[j] of slot[j] into the store pk[j] / pv[j] (written, though
+// the struct names them const), which must come zero-filled: the result is byte for byte the store q3tts_prefix_create makes of the same
+// rows — the keys P[j] .. np - 1 of the last block are written as zeros, values and (Q8_0) scales likewise stop at P[j].
+// 0: launched (or n == 0); nonzero: refused, nothing launched (hd != Q3_ATT_HD, more than Q3_KVP_MAX entries, a Q8_0 cache without scales)
+int q3_launch_kv_prefix_save(const Q3KvPrefix& a, hipStream_t s);
+int q3_launch_kv_prefix_save_kv8(const Q3KvPrefix& a, hipStream_t s);
 void q3_attend_policy(int decode, int prefill);  // test hook (q3tts_k_attend_policy): which kernel variant serves decode / prefill attention (same bits)
 void q3_attend_policy_get(int* decode, int* prefill);
 

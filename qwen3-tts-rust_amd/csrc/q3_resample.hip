@@ -223,6 +223,9 @@ struct Tmp {  // a device buffer of one call
 extern "C" int q3tts_resample(q3tts_engine* e, const float* in, int64_t n_in, int32_t rate_in, int32_t rate_out, float* out, int64_t cap, int64_t* n_out) {
     if (!e || !n_out || n_in < 0 || (n_in > 0 && !in) || cap < 0 || (cap > 0 && !out)) return q3_set_err(e, Q3TTS_ERR_INVALID, "resample: null argument or negative length");
     Q3_NOT_IN_SESSION(e);
+    return q3_resample_run(e, in, n_in, rate_in, rate_out, out, cap, n_out);
+}
+int q3_resample_run(q3tts_engine* e, const float* in, int64_t n_in, int32_t rate_in, int32_t rate_out, float* out, int64_t cap, int64_t* n_out) {
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     Q3Resamp rs{};
     TRY(q3_resample_get(e, rate_in, rate_out, &rs));

@@ -29,6 +29,17 @@ struct SReq {
     std::vector<float> embd, spk;
     std::vector<uint32_t> text, instr, ref_text;
     std::vector<int32_t> ref_codes;
+    // voice work (include/q3tts.h, "voices in a session"). kind 1: a standalone prefix job — desc / embd hold its voice rows (n_tok of
+    // them for embd), r is unused. keep: the prefix this entry fills (a job's, or a keep-voice request's with voice_rows as submitted)
+    int kind = 0, voice_rows = 0, n_tok = 0;
+    q3tts_prefix* keep = nullptr;
+};
+
+// a q3tts_session_clone call waiting for the worker (the caller's stack; mu guards done)
+struct CloneJob {
+    const float* audio = nullptr; int64_t n = 0; int rate = 0;
+    int64_t* codes = nullptr; int cap = 0; int32_t* n_frames = nullptr; float* spk = nullptr;
+    int rc = Q3TTS_OK; bool done = false; std::string err;
 };
 
 struct SEv {  // an event on its way to the consumer
@@ -79,6 +90,11 @@ struct q3tts_session {
     std::vector<uint64_t> cancels;
     std::map<uint64_t, IdState> ids;  // accepted ids whose final event has not been delivered
     std::deque<SEv> ready;
+    std::deque<CloneJob*> clones;        // q3tts_session_clone calls the worker has not run yet
+    int clone_waiters = 0;               // callers inside q3tts_session_clone (close waits for them to leave)
+    std::condition_variable cv_clone;
+    std::vector<q3tts_prefix*> made;     // the prefixes this session created and has not freed
+    std::vector<q3tts_prefix*> trash;    // released and no longer named by a queued request: the worker frees them at the next boundary
     uint64_t next_id = 1;
     bool stop = false, dead = false;
     bool text_dirty = false;        // q3tts_session_append_text added something the worker has not seen
@@ -109,6 +125,11 @@ void deliver(q3tts_session* s, SEv& v, double t) {
     auto it = s->ids.find(v.id);
     if (it == s->ids.end() || it->second.final_ready) { copy_result_free(v.res); return; }
     IdState& st = it->second;
+    if (v.kind == Q3TTS_EV_PREFIX) {  // a job's only event, or the one in front of a keep-voice request's own (cancelled or not: the store's fate is news)
+        if (v.is_final) st.final_ready = true;
+        s->ready.push_back(v);
+        return;
+    }
     if (st.cancelled) {
         if (v.kind == Q3TTS_EV_CHUNK) return;
         if (v.kind != Q3TTS_EV_CANCELLED) { copy_result_free(v.res); v.kind = Q3TTS_EV_CANCELLED; v.status = Q3TTS_OK; }
@@ -128,6 +149,61 @@ void deliver(q3tts_session* s, SEv& v, double t) {
 SEv final_ev(uint64_t id, int kind, int status) {
     SEv v; v.id = id; v.kind = kind; v.status = status; v.is_final = 1; v.res.status = status;
     return v;
+}
+
+SEv prefix_ev(uint64_t id, int status, bool is_final) {
+    SEv v; v.id = id; v.kind = Q3TTS_EV_PREFIX; v.status = status; v.is_final = is_final ? 1 : 0; v.res.status = status;
+    return v;
+}
+
+// (mu held) a released prefix that is settled and that no queued request names goes to the worker, which frees it at the next boundary
+void maybe_reap(q3tts_session* s, q3tts_prefix* x) {
+    if (!x->released || x->qrefs > 0 || x->state.load() == 0) return;
+    if (std::find(s->trash.begin(), s->trash.end(), x) == s->trash.end()) s->trash.push_back(x);
+}
+// (mu held) a queued request that named x has left the queue
+void unref_prefix(q3tts_session* s, const q3tts_prefix* cx) {
+    q3tts_prefix* x = const_cast<q3tts_prefix*>(cx);
+    if (!x || x->e != s->e) return;
+    if (x->qrefs > 0) --x->qrefs;
+    maybe_reap(s, x);
+}
+// (mu held) the prefix of an entry that will not be admitted fails with `status`
+void fail_keep(q3tts_session* s, q3tts_prefix* x, int status) {
+    if (!x || x->state.load() != 0) return;
+    x->state.store(status, std::memory_order_release);
+    maybe_reap(s, x);
+}
+// the store and the handle of a prefix nobody can name any more (the stream is idle, or synchronised by the caller)
+void free_prefix(q3tts_session* s, q3tts_prefix* x) {
+    q3tts_engine* e = s->e;
+    if (x->k) e->dev_bytes -= q3_prefix_store_bytes(e, x->np);
+    if (x->v) e->dev_bytes -= q3_prefix_store_bytes(e, x->np);
+    hipFree(x->k); hipFree(x->v);
+    delete x;
+}
+
+// one q3tts_session_clone call, on the engine's stream between two chunk boundaries: the bodies of q3tts_resample (a clip at another
+// rate first, as create_voice_file(resample=True) does), q3tts_clone_audio_encode and q3tts_clone_speaker_encode, in that order
+void run_clone(q3tts_session* s, CloneJob& j) {
+    q3tts_engine* e = s->e;
+    const float* a = j.audio; int64_t n = j.n;
+    std::vector<float> rs;
+    int rc = Q3TTS_OK;
+    if (j.rate != 24000) {
+        int L = 0, M = 0, H = 0, T = 0;
+        if (q3_resample_plan(j.rate, 24000, &L, &M, &H, &T) != Q3TTS_OK) rc = q3_set_err(e, Q3TTS_ERR_INVALID, "clone: the resampler cannot convert the clip's rate to 24000 Hz");
+        else {
+            rs.resize((size_t)std::max<long long>(1, q3_resample_N(n, L, M)));
+            int64_t n_out = 0;
+            rc = q3_resample_run(e, a, n, j.rate, 24000, rs.data(), (int64_t)rs.size(), &n_out);
+            a = rs.data(); n = n_out;
+        }
+    }
+    if (rc == Q3TTS_OK && j.codes) rc = q3_clone_audio_encode_run(e, a, n, j.codes, j.cap, j.n_frames);
+    if (rc == Q3TTS_OK && j.spk) rc = q3_clone_speaker_encode_run(e, a, n, j.spk);
+    if (rc != Q3TTS_OK) { std::lock_guard<std::mutex> lk(e->err_mu); j.err = e->err; }
+    j.rc = rc;
 }
 
 // publish finished batches in order; wait: block on the first one's copy
@@ -153,12 +229,30 @@ int publish(q3tts_session* s, bool wait) {
     return Q3TTS_OK;
 }
 
-// ring buffer k free: its copy published and every chunk in it released by the consumer (the worker waits: memory does not grow)
+// the waiting q3tts_session_clone calls, run and their callers woken
+void serve_clones(q3tts_session* s, const std::vector<CloneJob*>& clones) {
+    if (clones.empty()) return;
+    for (CloneJob* j : clones) run_clone(s, *j);
+    { std::lock_guard<std::mutex> lk(s->mu); for (CloneJob* j : clones) j->done = true; }
+    s->cv_clone.notify_all();
+}
+
+// ring buffer k free: its copy published and every chunk in it released by the consumer (the worker waits: memory does not grow).
+// Clone calls are served while it waits: their caller may be the consumer itself, which reads no event until its call returns. (This
+// boundary's frame steps are complete by now — q3_run_chunk synchronised the engine's stream — and the next have not begun.)
 int take_ring(q3tts_session* s, int k) {
     while (s->inflight[k]) { const int rc = publish(s, true); if (rc) return rc; }
-    std::unique_lock<std::mutex> lk(s->mu);
-    s->cv_space.wait(lk, [&] { return s->stop || s->refs[k] == 0; });
-    return s->stop ? kStopping : Q3TTS_OK;
+    for (;;) {
+        std::vector<CloneJob*> clones;
+        {
+            std::unique_lock<std::mutex> lk(s->mu);
+            s->cv_space.wait(lk, [&] { return s->stop || s->refs[k] == 0 || !s->clones.empty(); });
+            if (s->stop) return kStopping;
+            if (s->clones.empty()) return Q3TTS_OK;
+            clones.assign(s->clones.begin(), s->clones.end()); s->clones.clear();
+        }
+        serve_clones(s, clones);
+    }
 }
 
 void free_slot(q3tts_session* s, int b) {
@@ -224,12 +318,26 @@ int step(q3tts_session* s) {
         t.have = true; t.closed = it->second.closed;
         if ((int)it->second.T.size() != t_up) t.T = it->second.T;
     };
+    std::vector<std::unique_ptr<SReq>> orphans;  // requests whose prefix failed
+    std::vector<CloneJob*> clones;
+    std::vector<q3tts_prefix*> trash;
     {
         std::lock_guard<std::mutex> lk(s->mu);
         cancels.swap(s->cancels);
-        while (nfree-- > 0 && !s->pending.empty()) {
-            s->ids[s->pending.front()->id].queued = false;
-            adm.push_back(std::move(s->pending.front()));
+        trash.swap(s->trash);
+        clones.assign(s->clones.begin(), s->clones.end()); s->clones.clear();
+        // the FIFO's head: a request that names a pending prefix waits, and so does everything behind it; one whose prefix failed
+        // fails without a slot; a prefix job takes a free slot for this boundary as a request does
+        while (!s->pending.empty()) {
+            SReq& f = *s->pending.front();
+            const q3tts_prefix* x = f.kind == 0 ? f.r.prefix : nullptr;
+            const int xs = x && x->e == e ? x->state.load(std::memory_order_acquire) : 1;
+            if (xs == 0) break;
+            if (xs == 1 && nfree <= 0) break;
+            s->ids[f.id].queued = false;
+            unref_prefix(s, x);
+            if (xs < 0) orphans.push_back(std::move(s->pending.front()));
+            else { --nfree; adm.push_back(std::move(s->pending.front())); }
             s->pending.pop_front();
         }
         s->text_dirty = false;
@@ -238,9 +346,23 @@ int step(q3tts_session* s) {
         for (size_t i = 0; i < adm.size(); ++i) if (adm[i]->r.text_stream == 1) text_now(adm[i]->id, -1, tn_adm[i]);
     }
     Batch bt;
+    for (auto& q : orphans) {
+        q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the request names a prefix that failed");
+        bt.evs.push_back(final_ev(q->id, Q3TTS_EV_FAILED, Q3TTS_ERR_INVALID));
+    }
+    // 0. voice work that needs no slot: released prefixes (the admissions that copied them are behind us on the stream), clone calls
+    if (!trash.empty()) {
+        Q3_HIP(e, hipStreamSynchronize(e->stream));
+        std::lock_guard<std::mutex> lk(s->mu);
+        for (q3tts_prefix* x : trash) {
+            s->made.erase(std::remove(s->made.begin(), s->made.end(), x), s->made.end());
+            free_prefix(s, x);
+        }
+    }
+    serve_clones(s, clones);
     // 1. cancellations: the slot is retired now and admitted into again from the next boundary on
     std::vector<char> cool(B, 0);
-    bool retired = false;
+    bool retired = false, made_prefix = false;
     for (uint64_t id : cancels)
         for (int b = 0; b < B; ++b)
             if (s->slots[b].req && s->slots[b].req->id == id) {
@@ -261,20 +383,38 @@ int step(q3tts_session* s) {
     }
     // 2. admissions into free slots
     std::vector<int> as;
-    std::vector<const q3tts_request*> ar;
+    std::vector<Q3AdmItem> ar;
     for (int b = 0; b < B && as.size() < adm.size(); ++b)
-        if (!s->slots[b].req && !cool[b]) { as.push_back(b); ar.push_back(&adm[as.size() - 1]->r); }
+        if (!s->slots[b].req && !cool[b]) {
+            const SReq& q = *adm[as.size()];
+            Q3AdmItem it{};
+            it.slot = b; it.keep = q.keep;
+            if (q.kind == 1) { it.voice = q.embd.empty() ? &q.desc : nullptr; it.embd = q.embd.empty() ? nullptr : q.embd.data(); it.n_tok = q.n_tok; }
+            else { it.r = &q.r; it.keep_rows = q.voice_rows; }
+            as.push_back(b); ar.push_back(it);
+        }
     for (int b : as) Q3_HIP(e, hipEventSynchronize(e->fin_ev[b]));  // the previous occupant's vocoder work is done before the slot's reset
-    std::vector<int> live(as);
+    std::vector<int> live;
+    for (size_t i = 0; i < as.size(); ++i) if (adm[i]->kind == 0) live.push_back(as[i]);  // (a prefix job's slot takes no frame step)
     for (int b = 0; b < B; ++b) if (s->slots[b].req && (!s->slots[b].parked || text_ready(s->slots[b], nf[b]))) live.push_back(b);
     if (!live.empty()) TRY(q3_plan_rows(e, live));
     if (!as.empty()) {
         std::vector<int> rcs(as.size());
-        TRY(q3_admit_many(e, as.data(), ar.data(), (int)as.size(), rcs.data()));
+        TRY(q3_admit_items(e, ar.data(), (int)as.size(), rcs.data()));
         bool failed = false;
         for (int rc : rcs) failed |= rc != Q3TTS_OK;
+        for (size_t i = 0; i < as.size(); ++i) failed |= adm[i]->kind == 1;  // (a job's rows are freed below as a refused request's are)
         if (failed) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (a refused request's uploads may still read its copy, freed below)
         for (size_t i = 0; i < as.size(); ++i) {
+            if (adm[i]->keep) {  // the store is written behind the group's layers on the stream: ready for everything the worker issues from now on
+                q3tts_prefix* x = adm[i]->keep;
+                x->state.store(rcs[i] == Q3TTS_OK ? 1 : rcs[i], std::memory_order_release);
+                bt.evs.push_back(prefix_ev(adm[i]->id, rcs[i], adm[i]->kind == 1));
+                made_prefix = true;
+                std::lock_guard<std::mutex> lk(s->mu);
+                maybe_reap(s, x);
+            }
+            if (adm[i]->kind == 1) continue;  // the slot stays free
             if (rcs[i] != Q3TTS_OK) { bt.evs.push_back(final_ev(adm[i]->id, Q3TTS_EV_FAILED, rcs[i])); continue; }
             SSlot& sl = s->slots[as[i]];
             sl.req = std::move(adm[i]); sl.delivered = 0; s->voc_frames[as[i]] = 0;
@@ -308,7 +448,7 @@ int step(q3tts_session* s) {
     bool any = false;
     for (int b = 0; b < B; ++b) if (s->slots[b].req && !s->slots[b].parked) { run[b] = 1; any = true; }
     if (!any) {
-        if (retired) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (the staging half is rewritten by the next admission)
+        if (retired || made_prefix) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (the staging half is rewritten by the next admission; a PREFIX event says the store is written)
         if (!bt.evs.empty()) s->flight.push_back(std::move(bt));
         return Q3TTS_OK;
     }
@@ -398,6 +538,7 @@ void fail_all(q3tts_session* s, int rc) {
     s->dead = true; s->worker_rc = rc; s->err = "session worker: " + m;
     for (Batch& b : s->flight) for (SEv& v : b.evs) copy_result_free(v.res);
     s->flight.clear();
+    for (auto& q : s->pending) { if (q->kind == 0) unref_prefix(s, q->r.prefix); fail_keep(s, q->keep, rc); }
     s->pending.clear();
     const double t = q3_now_ms();
     for (auto& kv : s->ids)
@@ -417,7 +558,7 @@ void worker(q3tts_session* s) {
         bool work;
         {
             std::unique_lock<std::mutex> lk(s->mu);
-            auto todo = [&] { return (room && !s->pending.empty()) || !s->cancels.empty() || s->text_dirty; };
+            auto todo = [&] { return (room && !s->pending.empty()) || !s->cancels.empty() || s->text_dirty || !s->clones.empty() || !s->trash.empty(); };
             if (!running && s->flight.empty())  // idle: sleep until a submission that fits, a cancel, new text or close
                 s->cv_work.wait(lk, [&] { return s->stop || todo(); });
             if (s->stop) break;
@@ -433,6 +574,15 @@ void worker(q3tts_session* s) {
     for (int b = 0; b < e->B; ++b) if (s->slots[b].req) retire_slot(s, b);
     hipStreamSynchronize(e->stream);
     hipStreamSynchronize(e->vstream);
+    // voice work nobody will run any more: queued jobs' and keep-voice requests' prefixes read failed, waiting clone callers wake
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        for (q3tts_prefix* x : std::vector<q3tts_prefix*>(s->made)) fail_keep(s, x, rc != Q3TTS_OK ? rc : Q3TTS_ERR_STATE);  // (whatever is still pending)
+        for (CloneJob* j : s->clones) { j->rc = Q3TTS_ERR_STATE; j->err = "clone: the session is closing, or its worker failed"; j->done = true; }
+        s->clones.clear();
+        s->dead = s->dead || !s->stop;
+    }
+    s->cv_clone.notify_all();
 }
 
 int copy_request(q3tts_engine* e, const q3tts_request* req, SReq* q) {
@@ -503,8 +653,16 @@ extern "C" int q3tts_session_create(q3tts_engine* e, int32_t pcm_format, q3tts_s
     return Q3TTS_OK;
 }
 
-extern "C" int q3tts_session_submit(q3tts_session* s, const q3tts_request* req, uint64_t* id) {
+// q3tts_session_submit, and with out != null q3tts_session_submit_keep_voice: *out receives a pending prefix the request's admission fills
+static int submit_request(q3tts_session* s, const q3tts_request* req, uint64_t* id, int32_t voice_rows, q3tts_prefix** out) {
     if (!s || !req || !id) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    if (out) {
+        *out = nullptr;
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (req->prefix) return serr(s, Q3TTS_ERR_INVALID, "submit_keep_voice: a request that names a prefix cannot keep one");
+        if (voice_rows < 0 || (voice_rows == 0 && (req->prompt_embd || !req->prompt)))
+            return serr(s, Q3TTS_ERR_INVALID, "submit_keep_voice: voice_rows >= 1 with prompt_embd, >= 0 with a prompt built from ids");
+    }
     std::unique_ptr<SReq> q(new SReq());
     if (copy_request(s->e, req, q.get()) != Q3TTS_OK) {
         std::lock_guard<std::mutex> lk(s->mu);
@@ -518,6 +676,19 @@ extern "C" int q3tts_session_submit(q3tts_session* s, const q3tts_request* req, 
     {
         std::lock_guard<std::mutex> lk(s->mu);
         if (s->stop || s->dead) return serr(s, Q3TTS_ERR_STATE, s->dead ? "submit: the session's worker failed" : "submit: the session is closing");
+        if (q3tts_prefix* x = const_cast<q3tts_prefix*>(req->prefix)) {
+            if (x->e == s->e) {
+                if (x->released) return serr(s, Q3TTS_ERR_INVALID, "submit: the prefix was released");
+                ++x->qrefs;
+            }
+        }
+        if (out) {
+            q->keep = new q3tts_prefix();
+            q->keep->e = s->e; q->keep->state.store(0);
+            q->voice_rows = voice_rows;
+            s->made.push_back(q->keep);
+            *out = q->keep;
+        }
         q->id = s->next_id++;
         IdState st; st.t_submit = q3_now_ms();
         if (q->r.text_stream == 1) { st.ts = true; st.closed = !(q->r.text_open == 1); q3_text_trailing(&q->r, st.T); }
@@ -527,6 +698,82 @@ extern "C" int q3tts_session_submit(q3tts_session* s, const q3tts_request* req, 
     }
     s->cv_work.notify_one();
     return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_submit(q3tts_session* s, const q3tts_request* req, uint64_t* id) { return submit_request(s, req, id, 0, nullptr); }
+
+// ---- voices in a session (include/q3tts.h) ----
+extern "C" int q3tts_session_submit_keep_voice(q3tts_session* s, const q3tts_request* req, int32_t voice_rows, uint64_t* id, q3tts_prefix** out) {
+    if (!out) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    return submit_request(s, req, id, voice_rows, out);
+}
+
+extern "C" int q3tts_session_prefix_create(q3tts_session* s, const q3tts_prompt_desc* p, const float* embd, int32_t n_tok, q3tts_prefix** out, uint64_t* id) {
+    if (!s || !out || !id) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    *out = nullptr;
+    auto refuse = [&](int code, const char* m) { std::lock_guard<std::mutex> lk(s->mu); return serr(s, code, m); };
+    if ((p != nullptr) == (embd != nullptr)) return refuse(Q3TTS_ERR_INVALID, "prefix: give exactly one of a voice desc or host rows");
+    if (embd && n_tok <= 0) return refuse(Q3TTS_ERR_INVALID, "prefix: n_tok outside 1 .. n_ctx - 1");
+    if (p && p->n_text != 0) return refuse(Q3TTS_ERR_INVALID, "prefix: a voice desc has n_text == 0");
+    std::unique_ptr<SReq> q(new SReq());
+    q->kind = 1; q->n_tok = n_tok;
+    if (embd && n_tok >= s->e->cfg.n_ctx) q->embd.assign(1, 0.0f);  // too long: refused at admission by its length (a PREFIX event says so); no row is read
+    else {
+        q3tts_request tmp{};
+        tmp.prompt = p; tmp.prompt_embd = embd; tmp.n_tok = n_tok;
+        if (copy_request(s->e, &tmp, q.get()) != Q3TTS_OK) return refuse(Q3TTS_ERR_INVALID, "prefix: the voice cannot be copied (a null array with a length)");
+    }
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->stop || s->dead) return serr(s, Q3TTS_ERR_STATE, s->dead ? "prefix: the session's worker failed" : "prefix: the session is closing");
+        q->keep = new q3tts_prefix();
+        q->keep->e = s->e; q->keep->state.store(0);
+        s->made.push_back(q->keep);
+        *out = q->keep;
+        q->id = s->next_id++;
+        IdState st; st.t_submit = q3_now_ms();
+        s->ids[q->id] = st;
+        *id = q->id;
+        s->pending.push_back(std::move(q));
+    }
+    s->cv_work.notify_one();
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_prefix_release(q3tts_session* s, q3tts_prefix* x) {
+    if (!s || !x) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (x->e != s->e) return serr(s, Q3TTS_ERR_INVALID, "prefix_release: made by another engine");
+        if (x->released) return serr(s, Q3TTS_ERR_INVALID, "prefix_release: released already");
+        if (std::find(s->made.begin(), s->made.end(), x) == s->made.end()) s->made.push_back(x);  // (made before the session opened: the session frees it now)
+        x->released = true;
+        maybe_reap(s, x);
+    }
+    s->cv_work.notify_one();
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_clone(q3tts_session* s, const float* audio, int64_t n_samples, int32_t rate, int64_t* codes, int32_t cap_frames,
+                                   int32_t* n_frames, float* spk_emb) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (!s->e->clone) return serr(s, Q3TTS_ERR_STATE, "AudioEncoder not loaded (q3tts_clone_init was not called)");
+    if (n_samples < 0 || (n_samples > 0 && !audio) || (codes && !n_frames) || rate < 4000 || rate > 96000)
+        return serr(s, Q3TTS_ERR_INVALID, "clone: null argument, negative length, or a rate outside 4000..96000 Hz");
+    if (s->stop || s->dead) return serr(s, Q3TTS_ERR_STATE, s->dead ? "clone: the session's worker failed" : "clone: the session is closing");
+    CloneJob j;
+    j.audio = audio; j.n = n_samples; j.rate = rate; j.codes = codes; j.cap = cap_frames; j.n_frames = n_frames; j.spk = spk_emb;
+    s->clones.push_back(&j);
+    ++s->clone_waiters;
+    s->cv_work.notify_one(); s->cv_space.notify_all();  // (the worker sleeps on the one when idle, on the other while it waits for staging)
+    s->cv_clone.wait(lk, [&] { return j.done; });
+    --s->clone_waiters;
+    const int rc = j.rc;
+    if (rc != Q3TTS_OK) serr(s, rc, j.err);
+    lk.unlock();
+    s->cv_clone.notify_all();
+    return rc;
 }
 
 // the readiness rule (include/q3tts.h, "streaming text input"): the steps producing frames f .. f + 3 read T[f .. f + 3], and open text has
@@ -563,10 +810,21 @@ extern "C" int q3tts_session_cancel(q3tts_session* s, uint64_t id) {
         if (st.cancelled) return Q3TTS_OK;
         st.cancelled = true;
         if (st.queued) {
+            bool job = false;
             for (auto p = s->pending.begin(); p != s->pending.end(); ++p)
-                if ((*p)->id == id) { s->pending.erase(p); break; }
+                if ((*p)->id == id) {  // its prefix will never be written: the handle reads failed, a PREFIX event says so
+                    job = (*p)->kind == 1;
+                    if (!job) unref_prefix(s, (*p)->r.prefix);
+                    if ((*p)->keep) {
+                        fail_keep(s, (*p)->keep, Q3TTS_ERR_STATE);
+                        SEv pv = prefix_ev(id, Q3TTS_ERR_STATE, job);
+                        deliver(s, pv, q3_now_ms());
+                    }
+                    s->pending.erase(p);
+                    break;
+                }
             SEv v = final_ev(id, Q3TTS_EV_CANCELLED, Q3TTS_OK);
-            deliver(s, v, q3_now_ms());
+            if (!job) deliver(s, v, q3_now_ms());
         } else {
             for (auto r = s->ready.begin(); r != s->ready.end();) {  // no further chunk from now on; a waiting final becomes CANCELLED
                 if (r->id != id) { ++r; continue; }
@@ -605,7 +863,7 @@ extern "C" int q3tts_session_next(q3tts_session* s, int32_t timeout_ms, q3tts_se
         if (v.ring >= 0) { ev->pcm = (const char*)s->host[v.ring] + v.off * s->es; s->held_ring = v.ring; }  // (its reference moves to the consumer)
     } else {
         ev->result = v.res;
-        s->ids.erase(v.id);
+        if (v.is_final) s->ids.erase(v.id);  // (a keep-voice request's PREFIX event is not its last)
     }
     return Q3TTS_OK;
 }
@@ -620,6 +878,12 @@ extern "C" int q3tts_session_close(q3tts_session* s) {
     if (s->th.joinable()) s->th.join();
     q3tts_engine* e = s->e;
     hipSetDevice(e->cfg.device);
+    {   // callers still inside q3tts_session_clone leave first (the worker woke them); released prefixes go, the others stay the engine's
+        std::unique_lock<std::mutex> lk(s->mu);
+        s->cv_clone.wait(lk, [&] { return s->clone_waiters == 0; });
+        for (q3tts_prefix* x : s->made) if (x->released) free_prefix(s, x);
+        s->made.clear(); s->trash.clear();
+    }
     for (Batch& b : s->flight) for (SEv& v : b.evs) copy_result_free(v.res);
     for (SEv& v : s->ready) copy_result_free(v.res);
     for (int k = 0; k < kRing; ++k) { if (s->host[k]) hipHostFree(s->host[k]); if (s->ev[k]) hipEventDestroy(s->ev[k]); }

@@ -129,6 +129,7 @@ class SessionEvent(C.Structure):
 
 
 EV_NONE, EV_CHUNK, EV_DONE, EV_FAILED, EV_CANCELLED = 0, 1, 2, 3, 4
+EV_PREFIX = 5  # a session's prefix store is written, or its entry failed (include/q3tts.h, "voices in a session")
 PCM_F32, PCM_I16 = 0, 1
 SESSION_RING_DEPTH = 4
 
@@ -184,6 +185,8 @@ SYMBOLS = [
     "q3tts_k_attention_runs_kv8", "q3tts_k_attention_decode_kv8", "q3tts_k_attend_pick_kv8",
     "q3tts_k_pred_table_row", "q3tts_k_pred_next", "q3tts_k_attention_gather",
     "q3tts_k_row_buckets", "q3tts_k_bucket_steps", "q3tts_k_device_bytes", "q3tts_k_engine_footprint", "q3tts_k_prefix_stats",
+    "q3tts_session_prefix_create", "q3tts_session_submit_keep_voice", "q3tts_session_prefix_release", "q3tts_session_clone",
+    "q3tts_prefix_state", "q3tts_k_prefix_read",
 ]
 
 
@@ -246,6 +249,13 @@ def load_library(path=None):
     lib.q3tts_session_last_error.argtypes = [vp]
     lib.q3tts_session_last_error.restype = C.c_char_p
     lib.q3tts_session_append_text.argtypes = [vp, C.c_uint64, u32p, C.c_int32, C.c_int32]
+    lib.q3tts_session_prefix_create.argtypes = [vp, C.POINTER(PromptDesc), f32p, C.c_int32, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    lib.q3tts_session_submit_keep_voice.argtypes = [vp, C.POINTER(Request), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(vp)]
+    lib.q3tts_session_prefix_release.argtypes = [vp, vp]
+    lib.q3tts_session_clone.argtypes = [vp, f32p, C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32), f32p]
+    lib.q3tts_prefix_state.argtypes = [vp]
+    lib.q3tts_prefix_state.restype = C.c_int32
+    lib.q3tts_k_prefix_read.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.q3tts_k_text_ready.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.q3tts_k_pcm_pack.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, vp,
                                      C.c_int64]

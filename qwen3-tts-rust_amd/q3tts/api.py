@@ -302,23 +302,45 @@ class TtsEngine:
     def stream_batch_with_voice(self, texts, voices, instructs=None, seeds=None, *, prefix=None):
         """The streaming twin of generate_batch_with_voice: every utterance runs through one session (continuous batching over the
         engine's slots) and its 4-frame chunks are yielded as they are produced, as (index, f32 chunk, is_final); chunks of different
-        utterances interleave, each utterance's come in order and its last has is_final = True."""
+        utterances interleave, each utterance's come in order and its last has is_final = True.
+        prefix="auto" (opt-in; the same chunks, bit for bit): within this call the first utterance of each (voice, instruct) pair is
+        submitted keep-voice — its own prefill leaves the voice part's K/V behind as a prefix — and the later ones name that prefix while
+        it is still pending, so the voice rows run once per pair. The prefixes are released before the call ends."""
         sc = self.sampler_config
+        auto = isinstance(prefix, str)
+        if auto and prefix != "auto":
+            raise ValueError('prefix= is None, a voice_prefix() handle or "auto"')
         with native.NativeSession(self._native) as sess:
-            index = {}
-            for i, (t, v) in enumerate(zip(texts, voices)):
-                ins = None if instructs is None else instructs[i]
-                if prefix is not None:
-                    self._check_prefix(prefix, v, ins)
-                desc, keep = self._desc(t, v, ins, part="whole" if prefix is None else "text")
-                seed = sc.seed if seeds is None else seeds[i]
-                index[sess.submit(desc=desc, temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p, seed=seed, max_steps=self.max_steps,
-                                  prefix=prefix)] = i
-            for rid, kind, pcm, is_final, res in sess.events():
-                if kind == _abi.EV_CHUNK:
-                    yield index[rid], pcm, is_final
-                elif kind != _abi.EV_DONE:
-                    raise _abi.Q3Error(f"generation failed with status {res.status if res is not None else kind}")
+            index, made = {}, {}
+            try:
+                for i, (t, v) in enumerate(zip(texts, voices)):
+                    ins = None if instructs is None else instructs[i]
+                    seed = sc.seed if seeds is None else seeds[i]
+                    kw = dict(temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p, seed=seed, max_steps=self.max_steps)
+                    if auto:
+                        key = self._prefix_key(v, ins)
+                        if key not in made:
+                            desc, keep = self._desc(t, v, ins, part="whole")
+                            rid, made[key] = sess.submit(desc=desc, keep_voice=True, **kw)
+                        else:
+                            desc, keep = self._desc(t, v, ins, part="text")
+                            rid = sess.submit(desc=desc, prefix=made[key], **kw)
+                        index[rid] = i
+                        continue
+                    if prefix is not None:
+                        self._check_prefix(prefix, v, ins)
+                    desc, keep = self._desc(t, v, ins, part="whole" if prefix is None else "text")
+                    index[sess.submit(desc=desc, prefix=prefix, **kw)] = i
+                for rid, kind, pcm, is_final, res in sess.events():
+                    if kind == _abi.EV_CHUNK:
+                        yield index[rid], pcm, is_final
+                    elif kind == _abi.EV_PREFIX and res.status == 0:
+                        continue
+                    elif kind != _abi.EV_DONE:
+                        raise _abi.Q3Error(f"generation failed with status {res.status if res is not None else kind}")
+            finally:
+                for x in made.values():
+                    x.close()
 
     def stream_text_with_voice(self, pieces, voice: VoiceFile, instruct=None, *, prefix=None, seed=None):
         """Speech for text that is still being written (an extension; include/q3tts.h, "streaming text input"). pieces: an iterator of

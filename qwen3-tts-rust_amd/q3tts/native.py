@@ -422,13 +422,33 @@ class NativePrefix:
     """q3tts_prefix: a voice part's Talker K/V on the device of one engine (NativeEngine.create_prefix). close() is refused while a session
     is open on the engine; the engine closes its prefixes when it closes."""
 
-    def __init__(self, engine: NativeEngine, h):
+    def __init__(self, engine: NativeEngine, h, session=None):
         self.engine, self.lib, self.h = engine, engine.lib, h
-        self.n_rows = int(self.lib.q3tts_prefix_rows(h))
+        self.session = session   # the NativeSession that made it (create_prefix / submit(keep_voice=True)): pending until its PREFIX event
+        self._n_rows = int(self.lib.q3tts_prefix_rows(h))
+
+    @property
+    def n_rows(self):
+        """The prefix's rows; 0 while a session's prefix is pending (or when it failed)."""
+        if not self._n_rows and getattr(self, "h", None):
+            self._n_rows = int(self.lib.q3tts_prefix_rows(self.h))
+        return self._n_rows
+
+    @property
+    def state(self):
+        """q3tts_prefix_state: 0 pending, 1 ready, < 0 the status it failed with."""
+        if not getattr(self, "h", None):
+            raise _abi.Q3Error("the prefix is closed")
+        return int(self.lib.q3tts_prefix_state(self.h))
 
     def close(self):
+        """Gives the handle back, once: released to its session while that is open, destroyed otherwise."""
         if getattr(self, "h", None):
-            self.engine._check(self.lib.q3tts_prefix_destroy(self.h), "q3tts_prefix_destroy")
+            sess = self.session
+            if sess is not None and getattr(sess, "h", None):
+                sess._check(self.lib.q3tts_session_prefix_release(sess.h, self.h), "q3tts_session_prefix_release")
+            else:
+                self.engine._check(self.lib.q3tts_prefix_destroy(self.h), "q3tts_prefix_destroy")
             self.h = None
 
     def __enter__(self):
@@ -460,16 +480,67 @@ class NativeSession:
         if rc != 0:
             raise _abi.Q3Error(f"{what} failed ({rc}): {self.lib.q3tts_session_last_error(self.h).decode()}")
 
-    def submit(self, **request_kw):
+    def submit(self, keep_voice=False, voice_rows=0, **request_kw):
         """request_kw: NativeEngine.make_request keywords, prefix=, text_stream= and text_open= included (want_pcm is ignored: a session
-        always produces PCM). Returns the id."""
+        always produces PCM). Returns the id.
+        keep_voice=True (q3tts_session_submit_keep_voice): a whole-prompt request whose voice part becomes a prefix without a second
+        prefill — voice_rows rows of it, 0 = the voice part of desc. Returns (id, prefix): the prefix is pending until its EV_PREFIX
+        event, and requests may name it at once."""
         if not self.h:
             raise _abi.Q3Error("q3tts_session_submit: the session is closed")
         r, keep = NativeEngine.make_request(**request_kw)
         rid = C.c_uint64(0)
-        self._check(self.lib.q3tts_session_submit(self.h, C.byref(r), C.byref(rid)), "q3tts_session_submit")
+        if not keep_voice:
+            self._check(self.lib.q3tts_session_submit(self.h, C.byref(r), C.byref(rid)), "q3tts_session_submit")
+            self._open.add(rid.value)
+            return rid.value
+        h = C.c_void_p()
+        self._check(self.lib.q3tts_session_submit_keep_voice(self.h, C.byref(r), int(voice_rows), C.byref(rid), C.byref(h)),
+                    "q3tts_session_submit_keep_voice")
         self._open.add(rid.value)
-        return rid.value
+        return rid.value, self._adopt(h)
+
+    def _adopt(self, h):
+        x = NativePrefix(self.engine, h, session=self)
+        self.engine._prefixes.add(x)
+        return x
+
+    def create_prefix(self, desc=None, embd=None):
+        """q3tts_session_prefix_create: a prefix job in the running batch, arguments as NativeEngine.create_prefix. Returns (id, prefix);
+        its one event is EV_PREFIX (is_final) with the job's status."""
+        if (desc is None) == (embd is None):
+            raise ValueError("create_prefix: give exactly one of desc or embd")
+        h, rid = C.c_void_p(), C.c_uint64(0)
+        if desc is not None:
+            rc = self.lib.q3tts_session_prefix_create(self.h, C.byref(desc), None, 0, C.byref(h), C.byref(rid))
+        else:
+            e = np.ascontiguousarray(embd, dtype=np.float32)
+            rc = self.lib.q3tts_session_prefix_create(self.h, None, _ptr(e, f32p), e.shape[0], C.byref(h), C.byref(rid))
+        self._check(rc, "q3tts_session_prefix_create")
+        self._open.add(rid.value)
+        return rid.value, self._adopt(h)
+
+    def release_prefix(self, x):
+        """q3tts_session_prefix_release: gives a prefix back during the session, in any state; the store is freed once no queued request
+        names it. Also takes a prefix made before the session opened."""
+        if not x.h:
+            raise _abi.Q3Error("the prefix is closed")
+        self._check(self.lib.q3tts_session_prefix_release(self.h, x.h), "q3tts_session_prefix_release")
+        x.h = None
+
+    def clone_voice(self, audio, rate=24000):
+        """q3tts_session_clone: (codes i64 [n_frames][n_codebooks], speaker embedding) of a mono f32 clip at `rate` Hz, encoded between two
+        chunk boundaries while the batch runs; blocks. The bits of NativeEngine.audio_encode / speaker_encode outside a session."""
+        a = np.ascontiguousarray(audio, dtype=np.float32).reshape(-1)
+        n24 = a.size if rate == 24000 else -(-a.size * (24000 // math.gcd(int(rate), 24000)) // (int(rate) // math.gcd(int(rate), 24000)))
+        cap = max(self.engine.clone_audio_frames(n24), 1)
+        codes = np.zeros((cap, self.engine._clone_codebooks()), dtype=np.int64)
+        c = getattr(self.engine, "clone_cfg", None)
+        spk = np.zeros(c.se_dim if c is not None else self.engine.cfg.model.d_embed, dtype=np.float32)
+        n = C.c_int32(0)
+        self._check(self.lib.q3tts_session_clone(self.h, _ptr(a, f32p) if a.size else None, a.size, int(rate),
+                                                 codes.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n), _ptr(spk, f32p)), "q3tts_session_clone")
+        return codes[:n.value].copy(), spk
 
     def cancel(self, rid):
         self._check(self.lib.q3tts_session_cancel(self.h, rid), "q3tts_session_cancel")
@@ -482,7 +553,8 @@ class NativeSession:
                     "q3tts_session_append_text")
 
     def next(self, timeout_ms=-1):
-        """One event as (id, kind, pcm ndarray | None, is_final, GenResult | None), or None on timeout."""
+        """One event as (id, kind, pcm ndarray | None, is_final, GenResult | None), or None on timeout. EV_PREFIX (only after create_prefix
+        or submit(keep_voice=True)): the result's status is the prefix's; it is final for a job, not for a keep-voice request."""
         ev = _abi.SessionEvent()
         self._check(self.lib.q3tts_session_next(self.h, timeout_ms, C.byref(ev)), "q3tts_session_next")
         if ev.kind == _abi.EV_NONE:
@@ -493,7 +565,8 @@ class NativeSession:
                 np.zeros(0, dtype=self.dtype)
         else:
             res = self.engine._unpack(ev.result)
-            self._open.discard(ev.id)
+            if ev.is_final:
+                self._open.discard(ev.id)
         return ev.id, ev.kind, pcm, bool(ev.is_final), res
 
     def events(self, timeout_ms=-1):
