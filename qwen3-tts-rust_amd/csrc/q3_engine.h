@@ -181,6 +181,7 @@ int q3_refuse_in_session(q3tts_engine* e);
         if (err__ != hipSuccess)                                                                                \
             return q3_set_err((e), Q3TTS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(err__));     \
     } while (0)
+#define TRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
 
 // zero-filled device memory whose fill has completed on return (the one allocator of engine, vocoder, mel and clone state)
 int q3_dev_alloc_zeroed(q3tts_engine* e, void** p, size_t bytes);
@@ -284,7 +285,11 @@ int q3_resample_slot(q3tts_engine* e, int b, long long first_out, int count, int
 
 enum { BOS_TOKEN = 151672, EOS_TOKEN = 151673 };  // tts_bos, tts_eos (src/tts/prompt.rs); tts_pad is the model's tts_pad_id
 
-// the scheduler steps of q3_engine.hip that the session worker (q3_session.hip) drives between 4-frame chunks
+// the prompt builder (q3_engine.hip): the rows of `part` of p on the device at out; text_stream: the text part in the streamed layout
+enum { PROMPT_WHOLE = 0, PROMPT_VOICE = 1, PROMPT_TEXT = 2 };
+int build_prompt_dev(q3tts_engine* e, const q3tts_prompt_desc* p, float* out, int max_rows, int* n_out, int part = PROMPT_WHOLE, bool text_stream = false);
+
+// the scheduler steps of q3_generate.hip that the session worker (q3_session.hip) drives between 4-frame chunks
 // (q3_plan_rows + q3_admit_many are also the single-request admission of the talker-prefill hook)
 int q3_plan_rows(q3tts_engine* e, const std::vector<int>& live);
 int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc);
@@ -298,7 +303,16 @@ struct Q3AdmItem {
     const q3tts_prompt_desc* voice; const float* embd; int n_tok;
 };
 int q3_admit_items(q3tts_engine* e, const Q3AdmItem* items, int count, int* rc);
-int q3_run_chunk(q3tts_engine* e, int CH);
+// CH frame steps over the current row bucket; afterwards the slot mirror is on the host. *dev_ms: the device time
+int q3_run_chunk(q3tts_engine* e, int CH, float* dev_ms = nullptr);
+// finished slot b's n_frames, hit_eos and codes (malloc) into o: the copy runs on the decode stream, whose next synchronise completes it
+int q3_codes_back(q3tts_engine* e, int b, q3tts_result* o);
+// a free record (active = 0) for slot b from the pinned staging half admissions use; fin_ev[b] on evs, the stream of the slot's vocoder work
+int q3_retire_slot(q3tts_engine* e, int b, hipStream_t evs);
+// what a boundary hands out of a PCM row of ns samples (done: all there are) beyond `delivered`: the new ones, or at an output rate the outputs it can deliver by now
+int q3_emit_count(const q3tts_engine* e, int ns, bool done, long long delivered);
+// x's two stores freed and taken off e->dev_bytes, the handle deleted (nothing on the device reads the stores any more)
+void q3_prefix_free(q3tts_prefix* x);
 // the bodies of q3tts_clone_audio_encode / q3tts_clone_speaker_encode / q3tts_resample without the session check: the session worker
 // runs them on the engine's stream between two chunk boundaries (q3tts_session_clone)
 int q3_clone_audio_encode_run(q3tts_engine* e, const float* audio, int64_t n_samples, int64_t* codes, int32_t cap_frames, int32_t* n_frames);

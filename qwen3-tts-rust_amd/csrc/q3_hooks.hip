@@ -6,7 +6,6 @@
 #include <cstdio>
 #include <cstring>
 
-#define TRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
 #define HK(call) do { hipError_t er__ = (call); if (er__ != hipSuccess) return q3_set_err(nullptr, Q3TTS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(er__)); } while (0)
 
 // A device buffer of a hook, freed on every return path. put: `bytes` (+ 64 of slack) of zero-filled memory, then the host's `bytes` when

@@ -7,8 +7,6 @@
 #include <cmath>
 #include <numeric>
 
-#define TRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
-
 // ---- the filter (host, double; rounded once to f32) ---------------------------------------------------------------------------
 namespace {
 constexpr double kRho = 0.93, kZeros = 32.0, kBeta = 9.0, kPi = 3.14159265358979323846;

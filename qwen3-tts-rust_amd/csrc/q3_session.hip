@@ -1,8 +1,8 @@
 // q3_session.hip — sessions (include/q3tts.h): continuous batching with per-request streaming, the serving form of
 // run_inference_stream (src/tts/engine.rs:445-656) for many utterances at once. One worker thread per session drives the engine's slots
-// between 4-frame chunks: cancellations, admissions (plan_rows + admit_many), the frame steps (run_chunk), the batched vocoder
-// (q3_voc_dispatch, shared with q3tts_generate_batch), then ONE PCM gather launch and ONE device-to-host copy of every slot's new
-// samples into a ring of pinned staging buffers. Chunk events are published when that copy's event has fired (queried, never waited
+// between 4-frame chunks, one named phase after the other (step): cancellations, admissions (q3_plan_rows + q3_admit_items), the frame
+// steps (q3_run_chunk), the batched vocoder (q3_voc_dispatch, shared with q3tts_generate_batch), then ONE PCM gather launch and ONE
+// device-to-host copy of every slot's new samples into a ring of pinned staging buffers. Chunk events are published when that copy's event has fired (queried, never waited
 // for while slots are decoding), so decode keeps overlapping the vocoder as in q3tts_generate_batch. DESIGN.md §"Streams".
 #include "q3_engine.h"
 
@@ -15,8 +15,6 @@
 #include <thread>
 
 namespace {
-
-#define TRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
 
 constexpr int kRing = Q3TTS_SESSION_RING_DEPTH;
 constexpr int kStopping = 1;  // (positive: the worker was told to stop while it waited for staging)
@@ -174,14 +172,6 @@ void fail_keep(q3tts_session* s, q3tts_prefix* x, int status) {
     x->state.store(status, std::memory_order_release);
     maybe_reap(s, x);
 }
-// the store and the handle of a prefix nobody can name any more (the stream is idle, or synchronised by the caller)
-void free_prefix(q3tts_session* s, q3tts_prefix* x) {
-    q3tts_engine* e = s->e;
-    if (x->k) e->dev_bytes -= q3_prefix_store_bytes(e, x->np);
-    if (x->v) e->dev_bytes -= q3_prefix_store_bytes(e, x->np);
-    hipFree(x->k); hipFree(x->v);
-    delete x;
-}
 
 // one q3tts_session_clone call, on the engine's stream between two chunk boundaries: the bodies of q3tts_resample (a clip at another
 // rate first, as create_voice_file(resample=True) does), q3tts_clone_audio_encode and q3tts_clone_speaker_encode, in that order
@@ -290,103 +280,131 @@ bool text_ready(const SSlot& sl, int n_frames) {
     return !sl.ts || q3tts_k_text_ready(sl.t_len + (sl.t_closed ? 0 : 1), sl.t_closed ? 1 : 0, n_frames) != 0;  // x = the prompt's id + T without tts_eos
 }
 
-// upload a free state (active = 0) for slot b from the pinned staging half admissions use; its vocoder work so far precedes fin_ev[b]
-int retire_slot(q3tts_session* s, int b) {
+struct TextNow { bool have = false, closed = true; std::vector<int32_t> T; };  // a streamed request's text as of this boundary
+
+// What one chunk boundary (step) carries from phase to phase, destroyed when step returns. Per member: the phase that fills it and,
+// where an asynchronous upload reads host memory, the synchronisation that memory outlives. (The slots' records live in SSlot and in
+// the engine's staging half: `moved` and `retired` say that an upload of one is in flight.)
+struct Boundary {
+    explicit Boundary(int B) : tn(B), cool(B, 0), nf(B, 0), run(B, 0) {}
+    // collect, under one hold of mu
+    std::vector<uint64_t> cancels;               // ids to retire (cancel_slots)
+    std::vector<q3tts_prefix*> trash;            // released prefixes: voice_work frees them behind a synchronise of the decode stream
+    std::vector<CloneJob*> clones;               // q3tts_session_clone calls (voice_work)
+    std::vector<std::unique_ptr<SReq>> orphans;  // popped entries whose prefix failed: FAILED without a slot (voice_work)
+    // the popped entries that get a slot, in FIFO order. The admission's uploads read their rows: an entry that does not move into a slot
+    // (a prefix job, a refused request) lives until step returns, behind the synchronise plan_and_admit makes for exactly these
+    std::vector<std::unique_ptr<SReq>> adm;
+    // the text of slot b / of adm[i], from the same hold of mu as the pop. plan_and_admit moves tn_adm[i] to its slot's tn; resume_and_feed
+    // uploads from tn[b].T (q3_text_rows_set synchronises before it returns)
+    std::vector<TextNow> tn, tn_adm;
+    // the worker's phases
+    Batch bt;                  // the boundary's events in order: orphans' FAILED, CANCELLED, per admitted item PREFIX then FAILED, CHUNKs, DONE
+    std::vector<char> cool;    // cancel_slots: retired at this boundary, so not admitted into before the next (its staging record is being uploaded)
+    std::vector<int> nf;       // park_starved, plan_and_admit: a text_stream slot's frames so far (a parked slot's from the record it kept)
+    bool retired = false;      // cancel_slots: a staging-half record is being uploaded; until q3_run_chunk's synchronise or the idle return's
+    bool moved = false;        // park / resume: an upload reads SSlot::rec; until the synchronise that ends resume_and_feed
+    bool made_prefix = false;  // plan_and_admit: a PREFIX event says a store is written; it leaves behind q3_run_chunk's synchronise or the idle return's
+    std::vector<char> run;     // run_frames: the slots that take this boundary's frame steps (vocoder dispatch, gather_pcm)
+    std::vector<int> fin;      // gather_pcm: slots whose utterance ended. finish_slots' copies into their DONE events' codes end at its synchronise
+};
+
+// (mu held) id's streamed text; T is copied only when the device lacks some of it (it holds t_up entries)
+void text_now(q3tts_session* s, uint64_t id, int t_up, TextNow& t) {
+    auto it = s->ids.find(id);
+    if (it == s->ids.end() || !it->second.ts) return;
+    t.have = true; t.closed = it->second.closed;
+    if ((int)it->second.T.size() != t_up) t.T = it->second.T;
+}
+
+// 1. what the callers left since the last boundary, under one hold of mu: cancels, released prefixes, clone calls, the queue's head, and
+// the text of the running slots and of the entries just popped
+void collect(q3tts_session* s, Boundary& bd) {
     q3tts_engine* e = s->e;
-    Q3Slot* st = e->slots_host + e->B + b;
-    memset(st, 0, sizeof(*st));
-    Q3_HIP(e, hipMemcpyAsync(e->slots + b, st, sizeof(Q3Slot), hipMemcpyHostToDevice, e->stream));
-    Q3_HIP(e, hipEventRecord(e->fin_ev[b], e->vstream));
-    free_slot(s, b);
+    const int B = e->B;
+    int nfree = 0;
+    for (int b = 0; b < B; ++b) if (!s->slots[b].req) ++nfree;
+    std::lock_guard<std::mutex> lk(s->mu);
+    bd.cancels.swap(s->cancels);
+    bd.trash.swap(s->trash);
+    bd.clones.assign(s->clones.begin(), s->clones.end()); s->clones.clear();
+    // the FIFO's head: a request that names a pending prefix waits, and so does everything behind it; one whose prefix failed
+    // fails without a slot; a prefix job takes a free slot for this boundary as a request does
+    while (!s->pending.empty()) {
+        SReq& f = *s->pending.front();
+        const q3tts_prefix* x = f.kind == 0 ? f.r.prefix : nullptr;
+        const int xs = x && x->e == e ? x->state.load(std::memory_order_acquire) : 1;
+        if (xs == 0) break;
+        if (xs == 1 && nfree <= 0) break;
+        s->ids[f.id].queued = false;
+        unref_prefix(s, x);
+        if (xs < 0) bd.orphans.push_back(std::move(s->pending.front()));
+        else { --nfree; bd.adm.push_back(std::move(s->pending.front())); }
+        s->pending.pop_front();
+    }
+    s->text_dirty = false;
+    for (int b = 0; b < B; ++b) if (s->slots[b].req && s->slots[b].ts) text_now(s, s->slots[b].req->id, s->slots[b].t_up, bd.tn[b]);
+    bd.tn_adm.resize(bd.adm.size());
+    for (size_t i = 0; i < bd.adm.size(); ++i) if (bd.adm[i]->r.text_stream == 1) text_now(s, bd.adm[i]->id, -1, bd.tn_adm[i]);
+}
+
+// 2. voice work that needs no slot: requests whose prefix failed, released prefixes (the admissions that copied them are behind us on
+// the stream), clone calls
+int voice_work(q3tts_session* s, Boundary& bd) {
+    q3tts_engine* e = s->e;
+    for (auto& q : bd.orphans) {
+        q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the request names a prefix that failed");
+        bd.bt.evs.push_back(final_ev(q->id, Q3TTS_EV_FAILED, Q3TTS_ERR_INVALID));
+    }
+    if (!bd.trash.empty()) {
+        Q3_HIP(e, hipStreamSynchronize(e->stream));
+        std::lock_guard<std::mutex> lk(s->mu);
+        for (q3tts_prefix* x : bd.trash) {
+            s->made.erase(std::remove(s->made.begin(), s->made.end(), x), s->made.end());
+            q3_prefix_free(x);
+        }
+    }
+    serve_clones(s, bd.clones);
     return Q3TTS_OK;
 }
 
-// one chunk boundary
-int step(q3tts_session* s) {
-    q3tts_engine* e = s->e;
-    const int B = e->B;
-    hipStream_t vs = e->vstream;
-    std::vector<uint64_t> cancels;
-    std::vector<std::unique_ptr<SReq>> adm;
-    int nfree = 0;
-    for (int b = 0; b < B; ++b) if (!s->slots[b].req) ++nfree;
-    struct TextNow { bool have = false, closed = true; std::vector<int32_t> T; };  // a streamed request's text as of this boundary
-    std::vector<TextNow> tn(B), tn_adm;
-    auto text_now = [&](uint64_t id, int t_up, TextNow& t) {  // (mu held) T is copied only when the device lacks some of it
-        auto it = s->ids.find(id);
-        if (it == s->ids.end() || !it->second.ts) return;
-        t.have = true; t.closed = it->second.closed;
-        if ((int)it->second.T.size() != t_up) t.T = it->second.T;
-    };
-    std::vector<std::unique_ptr<SReq>> orphans;  // requests whose prefix failed
-    std::vector<CloneJob*> clones;
-    std::vector<q3tts_prefix*> trash;
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        cancels.swap(s->cancels);
-        trash.swap(s->trash);
-        clones.assign(s->clones.begin(), s->clones.end()); s->clones.clear();
-        // the FIFO's head: a request that names a pending prefix waits, and so does everything behind it; one whose prefix failed
-        // fails without a slot; a prefix job takes a free slot for this boundary as a request does
-        while (!s->pending.empty()) {
-            SReq& f = *s->pending.front();
-            const q3tts_prefix* x = f.kind == 0 ? f.r.prefix : nullptr;
-            const int xs = x && x->e == e ? x->state.load(std::memory_order_acquire) : 1;
-            if (xs == 0) break;
-            if (xs == 1 && nfree <= 0) break;
-            s->ids[f.id].queued = false;
-            unref_prefix(s, x);
-            if (xs < 0) orphans.push_back(std::move(s->pending.front()));
-            else { --nfree; adm.push_back(std::move(s->pending.front())); }
-            s->pending.pop_front();
-        }
-        s->text_dirty = false;
-        for (int b = 0; b < B; ++b) if (s->slots[b].req && s->slots[b].ts) text_now(s->slots[b].req->id, s->slots[b].t_up, tn[b]);
-        tn_adm.resize(adm.size());
-        for (size_t i = 0; i < adm.size(); ++i) if (adm[i]->r.text_stream == 1) text_now(adm[i]->id, -1, tn_adm[i]);
-    }
-    Batch bt;
-    for (auto& q : orphans) {
-        q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the request names a prefix that failed");
-        bt.evs.push_back(final_ev(q->id, Q3TTS_EV_FAILED, Q3TTS_ERR_INVALID));
-    }
-    // 0. voice work that needs no slot: released prefixes (the admissions that copied them are behind us on the stream), clone calls
-    if (!trash.empty()) {
-        Q3_HIP(e, hipStreamSynchronize(e->stream));
-        std::lock_guard<std::mutex> lk(s->mu);
-        for (q3tts_prefix* x : trash) {
-            s->made.erase(std::remove(s->made.begin(), s->made.end(), x), s->made.end());
-            free_prefix(s, x);
-        }
-    }
-    serve_clones(s, clones);
-    // 1. cancellations: the slot is retired now and admitted into again from the next boundary on
-    std::vector<char> cool(B, 0);
-    bool retired = false, made_prefix = false;
-    for (uint64_t id : cancels)
-        for (int b = 0; b < B; ++b)
+// 3. cancellations: the slot is retired now and admitted into again from the next boundary on
+int cancel_slots(q3tts_session* s, Boundary& bd) {
+    for (uint64_t id : bd.cancels)
+        for (int b = 0; b < s->e->B; ++b)
             if (s->slots[b].req && s->slots[b].req->id == id) {
-                TRY(retire_slot(s, b));
-                cool[b] = 1; retired = true;
-                bt.evs.push_back(final_ev(id, Q3TTS_EV_CANCELLED, Q3TTS_OK));
+                TRY(q3_retire_slot(s->e, b, s->e->vstream)); free_slot(s, b);
+                bd.cool[b] = 1; bd.retired = true;
+                bd.bt.evs.push_back(final_ev(id, Q3TTS_EV_CANCELLED, Q3TTS_OK));
             }
-    // 1b. streamed text: what arrived since the last boundary, and the readiness rule — a running slot whose text does not reach 4 more
-    // frames is parked before the rows are planned without it
-    std::vector<int> nf(B, 0);
-    bool moved = false;
-    for (int b = 0; b < B; ++b) {
+    return Q3TTS_OK;
+}
+
+// 4. streamed text: what arrived since the last boundary, and the readiness rule — a running slot whose text does not reach 4 more
+// frames is parked before the rows are planned without it
+int park_starved(q3tts_session* s, Boundary& bd) {
+    q3tts_engine* e = s->e;
+    for (int b = 0; b < e->B; ++b) {
         SSlot& sl = s->slots[b];
         if (!sl.req || !sl.ts) continue;
-        if (tn[b].have) { sl.t_closed = tn[b].closed; if (!tn[b].T.empty()) sl.t_len = (int)tn[b].T.size(); }
-        nf[b] = sl.parked ? sl.rec.n_frames : e->slots_host[b].n_frames;
-        if (!sl.parked && !text_ready(sl, nf[b])) { TRY(park(s, b, e->slots_host[b])); moved = true; }
+        const TextNow& t = bd.tn[b];
+        if (t.have) { sl.t_closed = t.closed; if (!t.T.empty()) sl.t_len = (int)t.T.size(); }
+        bd.nf[b] = sl.parked ? sl.rec.n_frames : e->slots_host[b].n_frames;
+        if (!sl.parked && !text_ready(sl, bd.nf[b])) { TRY(park(s, b, e->slots_host[b])); bd.moved = true; }
     }
-    // 2. admissions into free slots
+    return Q3TTS_OK;
+}
+
+// 5. the rows are planned for the slots that will run and the popped entries admitted into free slots in one batched prefill; then
+// what became of each: PREFIX events, FAILED, or a running slot with its text-stream bookkeeping
+int plan_and_admit(q3tts_session* s, Boundary& bd) {
+    q3tts_engine* e = s->e;
+    const int B = e->B;
     std::vector<int> as;
     std::vector<Q3AdmItem> ar;
-    for (int b = 0; b < B && as.size() < adm.size(); ++b)
-        if (!s->slots[b].req && !cool[b]) {
-            const SReq& q = *adm[as.size()];
+    for (int b = 0; b < B && as.size() < bd.adm.size(); ++b)
+        if (!s->slots[b].req && !bd.cool[b]) {
+            const SReq& q = *bd.adm[as.size()];
             Q3AdmItem it{};
             it.slot = b; it.keep = q.keep;
             if (q.kind == 1) { it.voice = q.embd.empty() ? &q.desc : nullptr; it.embd = q.embd.empty() ? nullptr : q.embd.data(); it.n_tok = q.n_tok; }
@@ -395,82 +413,94 @@ int step(q3tts_session* s) {
         }
     for (int b : as) Q3_HIP(e, hipEventSynchronize(e->fin_ev[b]));  // the previous occupant's vocoder work is done before the slot's reset
     std::vector<int> live;
-    for (size_t i = 0; i < as.size(); ++i) if (adm[i]->kind == 0) live.push_back(as[i]);  // (a prefix job's slot takes no frame step)
-    for (int b = 0; b < B; ++b) if (s->slots[b].req && (!s->slots[b].parked || text_ready(s->slots[b], nf[b]))) live.push_back(b);
+    for (size_t i = 0; i < as.size(); ++i) if (bd.adm[i]->kind == 0) live.push_back(as[i]);  // (a prefix job's slot takes no frame step)
+    for (int b = 0; b < B; ++b) if (s->slots[b].req && (!s->slots[b].parked || text_ready(s->slots[b], bd.nf[b]))) live.push_back(b);
     if (!live.empty()) TRY(q3_plan_rows(e, live));
-    if (!as.empty()) {
-        std::vector<int> rcs(as.size());
-        TRY(q3_admit_items(e, ar.data(), (int)as.size(), rcs.data()));
-        bool failed = false;
-        for (int rc : rcs) failed |= rc != Q3TTS_OK;
-        for (size_t i = 0; i < as.size(); ++i) failed |= adm[i]->kind == 1;  // (a job's rows are freed below as a refused request's are)
-        if (failed) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (a refused request's uploads may still read its copy, freed below)
-        for (size_t i = 0; i < as.size(); ++i) {
-            if (adm[i]->keep) {  // the store is written behind the group's layers on the stream: ready for everything the worker issues from now on
-                q3tts_prefix* x = adm[i]->keep;
-                x->state.store(rcs[i] == Q3TTS_OK ? 1 : rcs[i], std::memory_order_release);
-                bt.evs.push_back(prefix_ev(adm[i]->id, rcs[i], adm[i]->kind == 1));
-                made_prefix = true;
-                std::lock_guard<std::mutex> lk(s->mu);
-                maybe_reap(s, x);
-            }
-            if (adm[i]->kind == 1) continue;  // the slot stays free
-            if (rcs[i] != Q3TTS_OK) { bt.evs.push_back(final_ev(adm[i]->id, Q3TTS_EV_FAILED, rcs[i])); continue; }
-            SSlot& sl = s->slots[as[i]];
-            sl.req = std::move(adm[i]); sl.delivered = 0; s->voc_frames[as[i]] = 0;
-            sl.ts = sl.req->r.text_stream == 1; sl.parked = false;
-            if (!sl.ts) continue;
-            std::vector<int32_t> T0;  // what the admission put on the device: the request as submitted
-            q3_text_trailing(&sl.req->r, T0);
-            sl.t_up = sl.t_len = (int)T0.size(); sl.t_closed = !(sl.req->r.text_open == 1);
-            tn[as[i]] = std::move(tn_adm[i]);
-            TextNow& t = tn[as[i]];
-            if (t.have) { sl.t_closed = t.closed; if ((int)t.T.size() > sl.t_len) sl.t_len = (int)t.T.size(); }
-            nf[as[i]] = 0;
-            if (!text_ready(sl, 0)) { TRY(park(s, as[i], e->slots_host[e->B + as[i]])); moved = true; }  // (the staging half holds the record just admitted)
+    if (as.empty()) return Q3TTS_OK;
+    std::vector<int> rcs(as.size());
+    TRY(q3_admit_items(e, ar.data(), (int)as.size(), rcs.data()));
+    bool failed = false;
+    for (int rc : rcs) failed |= rc != Q3TTS_OK;
+    for (size_t i = 0; i < as.size(); ++i) failed |= bd.adm[i]->kind == 1;  // (a job's rows are freed with the boundary as a refused request's are)
+    if (failed) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (a refused request's uploads may still read its copy)
+    for (size_t i = 0; i < as.size(); ++i) {
+        std::unique_ptr<SReq>& q = bd.adm[i];
+        const int b = as[i];
+        if (q->keep) {  // the store is written behind the group's layers on the stream: ready for everything the worker issues from now on
+            q->keep->state.store(rcs[i] == Q3TTS_OK ? 1 : rcs[i], std::memory_order_release);
+            bd.bt.evs.push_back(prefix_ev(q->id, rcs[i], q->kind == 1));
+            bd.made_prefix = true;
+            std::lock_guard<std::mutex> lk(s->mu);
+            maybe_reap(s, q->keep);
         }
+        if (q->kind == 1) continue;  // the slot stays free
+        if (rcs[i] != Q3TTS_OK) { bd.bt.evs.push_back(final_ev(q->id, Q3TTS_EV_FAILED, rcs[i])); continue; }
+        SSlot& sl = s->slots[b];
+        sl.req = std::move(q); sl.delivered = 0; s->voc_frames[b] = 0;
+        sl.ts = sl.req->r.text_stream == 1; sl.parked = false;
+        if (!sl.ts) continue;
+        std::vector<int32_t> T0;  // what the admission put on the device: the request as submitted
+        q3_text_trailing(&sl.req->r, T0);
+        sl.t_up = sl.t_len = (int)T0.size(); sl.t_closed = !(sl.req->r.text_open == 1);
+        bd.tn[b] = std::move(bd.tn_adm[i]);
+        const TextNow& t = bd.tn[b];
+        if (t.have) { sl.t_closed = t.closed; if ((int)t.T.size() > sl.t_len) sl.t_len = (int)t.T.size(); }
+        bd.nf[b] = 0;
+        if (!text_ready(sl, 0)) { TRY(park(s, b, e->slots_host[e->B + b])); bd.moved = true; }  // (the staging half holds the record just admitted)
     }
-    // 2b. parked slots whose text suffices come back (the rows were planned with them), and new text goes to the device
-    for (int b = 0; b < B; ++b) {
+    return Q3TTS_OK;
+}
+
+// 6. parked slots whose text suffices come back (the rows were planned with them), and new text goes to the device
+int resume_and_feed(q3tts_session* s, Boundary& bd) {
+    q3tts_engine* e = s->e;
+    for (int b = 0; b < e->B; ++b) {
         SSlot& sl = s->slots[b];
         if (!sl.req || !sl.ts) continue;
         if (sl.parked) {
-            if (!text_ready(sl, nf[b])) continue;
-            TRY(resume(s, b)); moved = true;
+            if (!text_ready(sl, bd.nf[b])) continue;
+            TRY(resume(s, b)); bd.moved = true;
         }
-        if (sl.t_len > sl.t_up && (int)tn[b].T.size() >= sl.t_len) {
-            TRY(q3_text_rows_set(e, b, tn[b].T.data(), sl.t_up, sl.t_len, nf[b]));
+        if (sl.t_len > sl.t_up && (int)bd.tn[b].T.size() >= sl.t_len) {
+            TRY(q3_text_rows_set(e, b, bd.tn[b].T.data(), sl.t_up, sl.t_len, bd.nf[b]));
             sl.t_up = sl.t_len;
         }
     }
-    if (moved) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (the record uploads read the slots' host copies)
-    std::vector<char> run(B, 0);
-    bool any = false;
-    for (int b = 0; b < B; ++b) if (s->slots[b].req && !s->slots[b].parked) { run[b] = 1; any = true; }
-    if (!any) {
-        if (retired || made_prefix) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (the staging half is rewritten by the next admission; a PREFIX event says the store is written)
-        if (!bt.evs.empty()) s->flight.push_back(std::move(bt));
+    if (bd.moved) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (the record uploads read the slots' host copies)
+    return Q3TTS_OK;
+}
+
+// 7. nothing runs (*idle): what the boundary's events promise is on the device before they leave. Otherwise four frame steps, then
+// the vocoder on its stream
+int run_frames(q3tts_session* s, Boundary& bd, bool* idle) {
+    q3tts_engine* e = s->e;
+    *idle = true;
+    for (int b = 0; b < e->B; ++b) if (s->slots[b].req && !s->slots[b].parked) { bd.run[b] = 1; *idle = false; }
+    if (*idle) {
+        if (bd.retired || bd.made_prefix) Q3_HIP(e, hipStreamSynchronize(e->stream));  // (the staging half is rewritten by the next admission; a PREFIX event says the store is written)
         return Q3TTS_OK;
     }
-    // 3. four frame steps, 4. the vocoder
     TRY(q3_run_chunk(e, 4));
     bool more, first = false;
     { std::lock_guard<std::mutex> lk(s->mu); more = !s->pending.empty(); }
-    TRY(q3_voc_dispatch(e, run.data(), run.data(), s->voc_frames.data(), more, &first));
-    // 5. every slot's new window [delivered, samples) in one gather launch and one copy
+    return q3_voc_dispatch(e, bd.run.data(), bd.run.data(), s->voc_frames.data(), more, &first);
+}
+
+// 8. every running slot's new window [delivered, samples) as a gather entry and a CHUNK event; the entries (by-value kernel arguments)
+// in launches of at most Q3_PCM_MAX_ENT, all into the one staging buffer; one copy to the ring, one event
+int gather_pcm(q3tts_session* s, Boundary& bd) {
+    q3tts_engine* e = s->e;
+    hipStream_t vs = e->vstream;
     const Q3Resamp* rs = e->out_rate ? &e->rs_out : nullptr;
-    std::vector<Q3PcmEnt> ents; std::vector<int> ent_len; std::vector<char> ent_fin;  // (a gather launch takes Q3_PCM_MAX_ENT entries: more slots, more launches)
-    int ne = 0;
+    std::vector<Q3PcmEnt> ents; std::vector<int> ent_len; std::vector<char> ent_fin;
     size_t tot = 0;
     std::vector<SEv> chunks;
-    std::vector<int> fin;
-    for (int b = 0; b < B; ++b) {
-        if (!run[b]) continue;
+    for (int b = 0; b < e->B; ++b) {
+        if (!bd.run[b]) continue;
         SSlot& sl = s->slots[b];
         const bool done = !e->slots_host[b].active;
         const int ns = q3_voc_samples(e, b);
-        // the samples to hand out: the row's new ones, or with an output rate set the outputs it can deliver by now
-        const int c = (rs ? (int)(done ? q3_resample_N(ns, rs->L, rs->M) : q3_resample_D(ns, rs->L, rs->M, rs->H)) : ns) - sl.delivered;
+        const int c = q3_emit_count(e, ns, done, sl.delivered);
         if (c < 0 || tot + (size_t)std::max(c, 0) > s->ring_cap || ns > (int)q3_voc_pcm_stride(e))
             return q3_set_err(e, Q3TTS_ERR_STATE, "session: a chunk window exceeds the staging bound");
         if (c > 0 || done) {
@@ -479,16 +509,16 @@ int step(q3tts_session* s) {
         }
         if (c > 0) {
             ent_len.push_back(ns); ent_fin.push_back(done ? 1 : 0);
-            ents.push_back(Q3PcmEnt{b, sl.delivered, c, 0, (long long)tot}); ++ne;
+            ents.push_back(Q3PcmEnt{b, sl.delivered, c, 0, (long long)tot});
             tot += (size_t)c; sl.delivered += c;
         }
-        if (done) fin.push_back(b);
+        if (done) bd.fin.push_back(b);
     }
+    const int ne = (int)ents.size(), k = s->ring_next;
     if (ne > 0) {
-        const int k = s->ring_next;
         const int rc = take_ring(s, k);
         if (rc) return rc;
-        for (int g0 = 0; g0 < ne; g0 += Q3_PCM_MAX_ENT) {  // the windows in launches of at most Q3_PCM_MAX_ENT entries, all into the one staging buffer
+        for (int g0 = 0; g0 < ne; g0 += Q3_PCM_MAX_ENT) {
             const int n = std::min(ne - g0, (int)Q3_PCM_MAX_ENT);
             Q3PcmPack pk{}; Q3PcmSrc src{};
             int mx = 0;
@@ -505,28 +535,41 @@ int step(q3tts_session* s) {
         Q3_HIP(e, hipEventRecord(s->ev[k], vs));
         s->inflight[k] = true;
         s->ring_next = (k + 1) % kRing;
-        bt.ring = k;
+        bd.bt.ring = k;
         for (SEv& v : chunks) if (v.n > 0) v.ring = k;
     }
-    for (SEv& v : chunks) bt.evs.push_back(v);
-    // finished utterances: codes back on the decoder stream, the slot free from the next boundary on
-    const int ncb = e->cfg.model.n_codebooks;
-    for (int b : fin) {
-        const Q3Slot& st = e->slots_host[b];
+    for (SEv& v : chunks) bd.bt.evs.push_back(v);
+    return Q3TTS_OK;
+}
+
+// 9. finished utterances: codes back on the decoder stream, the slot free from the next boundary on
+int finish_slots(q3tts_session* s, Boundary& bd) {
+    q3tts_engine* e = s->e;
+    for (int b : bd.fin) {
         SEv v = final_ev(s->slots[b].req->id, Q3TTS_EV_DONE, Q3TTS_OK);
-        q3tts_result& o = v.res;
-        o.n_frames = st.n_frames; o.hit_eos = st.hit_eos; o.n_samples = s->slots[b].delivered; o.sample_rate = rs ? e->out_rate : e->cfg.vocoder.sample_rate;
-        o.codes = (int32_t*)malloc(sizeof(int32_t) * (size_t)std::max(1, st.n_frames * ncb));
-        if (!o.codes) return q3_set_err(e, Q3TTS_ERR_OOM, "malloc");
-        if (st.n_frames > 0)
-            Q3_HIP(e, hipMemcpyAsync(o.codes, e->codes + (size_t)b * e->cfg.max_steps_cap * ncb, sizeof(int32_t) * (size_t)st.n_frames * ncb,
-                                     hipMemcpyDeviceToHost, e->stream));
-        Q3_HIP(e, hipEventRecord(e->fin_ev[b], vs));  // (behind the gather that read the slot's PCM)
+        TRY(q3_codes_back(e, b, &v.res));
+        v.res.n_samples = s->slots[b].delivered; v.res.sample_rate = e->out_rate ? e->out_rate : e->cfg.vocoder.sample_rate;
+        Q3_HIP(e, hipEventRecord(e->fin_ev[b], e->vstream));  // (behind the gather that read the slot's PCM)
         free_slot(s, b);
-        bt.evs.push_back(v);
+        bd.bt.evs.push_back(v);
     }
-    if (!fin.empty()) Q3_HIP(e, hipStreamSynchronize(e->stream));
-    s->flight.push_back(std::move(bt));
+    if (!bd.fin.empty()) Q3_HIP(e, hipStreamSynchronize(e->stream));
+    return Q3TTS_OK;
+}
+
+// one chunk boundary: the phases in their order, over one Boundary
+int step(q3tts_session* s) {
+    Boundary bd(s->e->B);
+    bool idle = false;
+    collect(s, bd);
+    TRY(voice_work(s, bd));
+    TRY(cancel_slots(s, bd));
+    TRY(park_starved(s, bd));
+    TRY(plan_and_admit(s, bd));
+    TRY(resume_and_feed(s, bd));
+    TRY(run_frames(s, bd, &idle));
+    if (!idle) { TRY(gather_pcm(s, bd)); TRY(finish_slots(s, bd)); }
+    if (!idle || !bd.bt.evs.empty()) s->flight.push_back(std::move(bd.bt));
     return Q3TTS_OK;
 }
 
@@ -571,7 +614,7 @@ void worker(q3tts_session* s) {
     if (rc == kStopping) rc = Q3TTS_OK;
     if (rc != Q3TTS_OK) fail_all(s, rc);
     // close (or failure): retire the slots still decoding, so the engine is usable as before
-    for (int b = 0; b < e->B; ++b) if (s->slots[b].req) retire_slot(s, b);
+    for (int b = 0; b < e->B; ++b) if (s->slots[b].req) { q3_retire_slot(e, b, e->vstream); free_slot(s, b); }
     hipStreamSynchronize(e->stream);
     hipStreamSynchronize(e->vstream);
     // voice work nobody will run any more: queued jobs' and keep-voice requests' prefixes read failed, waiting clone callers wake
@@ -881,7 +924,7 @@ extern "C" int q3tts_session_close(q3tts_session* s) {
     {   // callers still inside q3tts_session_clone leave first (the worker woke them); released prefixes go, the others stay the engine's
         std::unique_lock<std::mutex> lk(s->mu);
         s->cv_clone.wait(lk, [&] { return s->clone_waiters == 0; });
-        for (q3tts_prefix* x : s->made) if (x->released) free_prefix(s, x);
+        for (q3tts_prefix* x : s->made) if (x->released) q3_prefix_free(x);  // (the worker synchronised both streams before it left)
         s->made.clear(); s->trash.clear();
     }
     for (Batch& b : s->flight) for (SEv& v : b.evs) copy_result_free(v.res);

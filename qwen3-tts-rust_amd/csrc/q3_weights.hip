@@ -7,8 +7,6 @@
 #include <cmath>
 #include <cstdio>
 
-#define TRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
-
 // RoPE tables in double on the host (same formula the oracle restates)
 void q3_rope_tables(int n_pos, int hd, float theta, const int* sections, std::vector<float>& cs, std::vector<float>& sn) {
     const int half = hd / 2;

@@ -47,10 +47,10 @@ def _attend_policy(decode, prefill):
     assert _abi.load_library().q3tts_k_attend_policy(decode, prefill) == 0
 
 
-def _engine(mode=0, max_batch=4, n_ctx=N_CTX):
+def _engine(mode=0, max_batch=4, n_ctx=N_CTX, kv8=0):
     from q3tts import _abi, native
     cfg = _abi.tiny_config(max_batch=max_batch, n_ctx=n_ctx, with_vocoder=1)
-    cfg.talker_q8_0 = mode
+    cfg.talker_q8_0, cfg.kv_q8_0 = mode, kv8
     return cfg, native.NativeEngine(cfg)
 
 
@@ -233,6 +233,25 @@ def test_q8_0_modes(oracle, mode):
     finally:
         eng.close()
         om.close()
+
+
+# ---- 5b. the store's bytes come and go in q3tts_k_device_bytes -------------------------------------------------------------------------------
+@pytest.mark.parametrize("kv8", [0, 1])
+def test_destroy_gives_device_bytes_back(oracle, kv8):
+    """q3tts_prefix_create adds its two stores (K and V, each the size q3tts_k_prefix_read reports) to the engine's device bytes, and
+    q3tts_prefix_destroy takes exactly them off again, in the bf16 and the Q8_0 cache format."""
+    cfg, eng = _engine(kv8=kv8)
+    try:
+        dv, keep = oracle.make_prompt_desc(None, part="voice", spk_id=3000, lang_id=None)
+        b0 = eng.device_bytes()
+        x = eng.create_prefix(desc=dv)
+        n = C.c_int64(0)
+        assert x.lib.q3tts_k_prefix_read(x.h, None, None, 0, C.byref(n)) == 0 and n.value > 0
+        assert eng.device_bytes() == b0 + 2 * n.value
+        x.close()
+        assert eng.device_bytes() == b0
+    finally:
+        eng.close()
 
 
 # ---- 6. streams and sessions -------------------------------------------------------------------------------------------------------------
