@@ -486,6 +486,52 @@ int32_t q3tts_prefix_state(const q3tts_prefix* x);   /* 0 pending, 1 ready, < 0 
  * (the worker sleeps; an append wakes it); q3tts_session_cancel and q3tts_session_close end it. The reference has no counterpart. */
 int q3tts_session_append_text(q3tts_session* s, uint64_t id, const uint32_t* ids, int32_t n, int32_t close);
 
+/* ---- paced requests and swapping: a listener says how far ahead its request may run; a parked request leaves its slot ----
+ * A session synthesises many times faster than a listener plays, and a request holds its slot until its final event. Two calls let a
+ * GPU serve more open requests than it has slots: a frame CREDIT per request (pacing), and moving a parked request's whole state into
+ * a device arena and later into any free slot (swapping). Neither is on unless asked for: with q3tts_session_set_swap never called and
+ * no paced submission, no launch, bit, event or scheduling decision differs.
+ *
+ * CONTRACT. For any schedule of grants, text arrivals, swap-outs and swap-ins, a request's events are those of the same request through
+ * q3tts_session_submit: the same chunk sample counts in the same order; the chunks joined equal q3tts_generate_batch's PCM bit for bit
+ * (f32 and i16, with and without an output rate); the same codes, n_frames and hit_eos — in every talker_q8_0 / predictor_q8_0 /
+ * kv_q8_0 mode, with voice prefixes, the Predictor sampler and the repetition penalty. Other requests' results do not change.
+ *
+ *   q3tts_session_submit_paced(s, req, credit_frames, &id): q3tts_session_submit plus a frame credit. credit_frames >= 4, else
+ *     Q3TTS_ERR_INVALID. There is no paced form of q3tts_session_submit_keep_voice: a keep-voice request runs unpaced.
+ *   q3tts_session_grant(s, id, frames): thread-safe, at any time. frames > 0 adds to the credit; frames < 0 lifts the limit for good.
+ *     Q3TTS_ERR_INVALID for frames == 0, an unknown or finished id, and an id that was not submitted paced.
+ *   The credit rule: at a chunk boundary a paced request with n frames so far takes the next chunk iff n + 4 <= credit. Otherwise it is
+ *     parked exactly as a text-starved request is ("streaming text input"); a request that is both paced and text_stream runs when both
+ *     rules allow it. A grant wakes the worker as an append does.
+ *   q3tts_session_set_swap(s, arena_bytes): valid before the first submission (Q3TTS_ERR_STATE later). 0 (the default): off. Otherwise
+ *     one device arena of that size for the session's lifetime, checked against the device's free memory as q3tts_engine_create checks its
+ *     own sum (Q3TTS_ERR_OOM, the message names both numbers), freed by q3tts_session_close. The arena is carved on the host — first fit
+ *     over 256-byte units, neighbours coalesced on free — so no chunk boundary allocates or frees device memory.
+ *   With swapping on, while the slots wanted (swapped-out requests whose rule holds again, and the queue's admissible head) exceed the
+ *     free ones, parked slots are swapped out, longest-parked first; a running request is never preempted; with no room in the arena the
+ *     slot stays parked and nothing fails. Swapped-out requests whose rule holds again take free slots oldest-ready first, ahead of new
+ *     admissions. A slot freed by a swap-out is refilled at the NEXT boundary. q3tts_session_cancel, q3tts_session_close and a worker
+ *     failure treat a swapped-out request as any open one (exactly one final event; its block is freed); q3tts_session_append_text keeps
+ *     working (the text is uploaded whole at swap-in).
+ *   q3tts_session_swap_stats(s, out): out[0] swap-outs, [1] swap-ins, [2] swap-ins into a slot other than the one left, [3] arena bytes
+ *     in use, [4] their peak, [5] swap-outs skipped because the arena had no room. A block counts as in use until the last copy that
+ *     read or wrote it has run on the device: its bytes are not handed out again before that.
+ * Every call refuses a NULL session with Q3TTS_ERR_INVALID ("null session").
+ *
+ * MEMORY. Beside the per-slot memory stated at q3tts_engine_config.kv_q8_0 (the Talker's K/V: n_ctx positions per slot), a swapped-out request at Talker
+ * position cur_pos whose vocoder has taken f frames occupies one block of
+ *     2 * store(np) + S + up16(f * samples_per_frame * 4)      bytes, rounded up to 256,
+ * np = ceil(cur_pos / 64) * 64; store(np) = t_n_layer * t_n_kv_head * np * t_head_dim * 2 (kv_q8_0: * 17 / 16 instead of * 2), one
+ * voice-prefix store each for K and V; S = the sum, each term rounded up to 16, of max_steps_cap * 4 * (n_codebooks + 1 + n_codebooks - 1)
+ * (codes, both samplers' draws), ceil(sample_limit / 32) * 4 (codes 0 seen), 4 * (t_vocab + t_d_model) (the parked rows), the vocoder's
+ * per-slot history blocks (what a slot's reset zeroes) and 2 * n_layer * (sliding_window + 4) * n_head * head_dim * 4 (its rings); the
+ * last term is the produced part of the slot's PCM row. */
+int q3tts_session_submit_paced(q3tts_session* s, const q3tts_request* req, int32_t credit_frames, uint64_t* id);
+int q3tts_session_grant(q3tts_session* s, uint64_t id, int32_t frames);
+int q3tts_session_set_swap(q3tts_session* s, int64_t arena_bytes);
+int q3tts_session_swap_stats(const q3tts_session* s, int64_t out[6]);
+
 /* ---- one node, several GPUs ----------------------------------------------------------------------
  * The reference is one utterance at a time on one device (n_seq_max = 1, src/models/llama/mod.rs:413; `&mut self`,
  * src/tts/engine.rs:390). Utterances share nothing but read-only weights, so a batch shards over independent units:
@@ -775,6 +821,18 @@ int q3tts_k_pred_variant(q3tts_engine* e, int32_t force);
 /* The readiness rule of "streaming text input" as the session worker applies it: 1 iff a request with n_text text ids so far (x, the
  * first one included), closed or not, at n_frames frames may take part in the next chunk of 4 frame steps. Needs no GPU. */
 int q3tts_k_text_ready(int32_t n_text, int32_t closed, int32_t n_frames);
+/* The credit rule of "paced requests and swapping" as the session worker applies it: 1 iff a paced request with that credit at n_frames
+ * frames may take the next chunk of 4 frame steps (n_frames + 4 <= credit; a negative credit is a lifted limit). Needs no GPU. */
+int q3tts_k_credit_ready(int64_t credit, int32_t n_frames);
+/* The swap arena's allocator alone (host only): ops[0, n) replayed over an arena of cap bytes. ops[i] > 0 allocates that many bytes:
+ * offsets[i] = the block's offset (a multiple of 256), or -1 for "no room". ops[i] = -(k + 1) frees what ops[k] allocated (k < i, a live
+ * allocation): offsets[i] = the freed offset. Anything else is Q3TTS_ERR_INVALID. */
+int q3tts_k_swap_arena(int64_t cap, const int64_t* ops, int32_t n, int64_t* offsets);
+/* Measurement hook (tools/paced_bench.py): the worker's HOST wall time in the two swap phases of its chunk boundaries so far, counted
+ * over the boundaries that moved at least one block: out[0] ms in swap_out, out[1] ms in swap_in (launches, the host waits for a target
+ * slot's previous occupant, the text upload's synchronise), out[2] the number of such boundaries. The copies themselves run on the two
+ * streams behind these phases and are not in it. Q3TTS_ERR_INVALID for a NULL session ("null session") or a NULL out. */
+int q3tts_k_swap_phase_ms(const q3tts_session* s, double out[3]);
 /* The k_bgemm instance the launcher takes for a shape, without launching: out5 = {row tiles, column tiles, ring depth, non-temporal weight
  * loads, 1 if k_bgemm_big}. bench.py names the kernel symbol of a probed launch from it. */
 int q3tts_k_bgemm_pick(int32_t B, int32_t K, int32_t N, int32_t epilogue, int32_t w_once, int32_t q8, int32_t* out5);

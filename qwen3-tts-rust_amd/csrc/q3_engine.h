@@ -277,6 +277,36 @@ float* q3_voc_pcm(q3tts_engine* e, int slot);
 int q3_voc_samples(q3tts_engine* e, int slot);
 int q3_voc_samples_per_frame(const q3tts_engine* e);
 size_t q3_voc_pcm_stride(const q3tts_engine* e);  // samples between the PCM buffers of consecutive slots
+// a piece of per-slot device state: slot b's part is [base + b * stride, + bytes)
+struct Q3SlotBlock { char* base; unsigned long long stride, bytes; };
+// the vocoder's per-slot state that outlives a call: its history blocks (the list q3_voc_reset zeroes) and every layer's ring slices
+void q3_voc_slot_blocks(q3tts_engine* e, std::vector<Q3SlotBlock>& out);
+// a slot's frames_done / last_flag, read (set = false) or written
+void q3_voc_host_state(q3tts_engine* e, int slot, int* frames_done, int* last_flag, bool set);
+
+// Swapping (q3_swap.hip; include/q3tts.h, "paced requests and swapping"): one device arena carved on the host, and the moves
+// of a slot's whole state into a block of it and back into any slot.
+struct Q3Swap;
+// the arena (arena_bytes > 0) and the state table, checked against the device's free memory; counted in e->dev_bytes until q3_swap_destroy
+int q3_swap_create(q3tts_engine* e, long long arena_bytes, Q3Swap** out);
+void q3_swap_destroy(q3tts_engine* e, Q3Swap* sw);
+// bytes of the block of a request at Talker position cur_pos whose vocoder has taken voc_frames frames (the formula of include/q3tts.h)
+long long q3_swap_block_bytes(const q3tts_engine* e, const Q3Swap* sw, int cur_pos, int voc_frames);
+// first-fit over 256-byte units: the block's offset or -1 (no room); q3_swap_release coalesces with the free neighbours
+long long q3_swap_alloc(Q3Swap* sw, long long bytes);
+void q3_swap_release(Q3Swap* sw, long long off, long long bytes);
+long long q3_swap_used(const Q3Swap* sw);
+// One group's moves, one launch per kernel and Q3_KVP_MAX items: the K/V of positions < cur_pos (q3_launch_kv_prefix_save / q3_launch_kv_prefix)
+// and the decoder's per-slot state on e->stream, the vocoder's on e->vstream. save: slot -> block; else block -> slot.
+struct Q3SwapItem { int slot, cur_pos, voc_frames; long long off; };
+// *ticket names the move: q3_swap_done(sw, ticket) says (without waiting) whether both streams' halves of it, and of every earlier move,
+// have run. A block goes back to q3_swap_release only then — whatever is carved over its bytes next has another layout, so stream order
+// alone does not keep the new block's decode-stream half off the old block's vocoder-stream half.
+int q3_swap_move(q3tts_engine* e, Q3Swap* sw, const Q3SwapItem* items, int n, bool save, unsigned long long* ticket);
+bool q3_swap_done(Q3Swap* sw, unsigned long long ticket);
+// streamed text for several slots behind ONE synchronise of the decode stream (q3_text_rows_set is the group of one)
+struct Q3TextSet { int b; const int32_t* T; int from, n, n_frames; };
+int q3_text_rows_set_group(q3tts_engine* e, const Q3TextSet* items, int count);
 
 // the resampler's engine side (q3_resample.hip): the cached table of a rate pair (built and uploaded on first use), and outputs
 // [first_out, first_out + count) of slot b's PCM row (n_valid samples so far) at e->out_rate into the start of the slot's row of e->rs_stage

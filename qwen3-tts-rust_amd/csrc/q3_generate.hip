@@ -112,16 +112,25 @@ void q3_text_trailing(const q3tts_request* r, std::vector<int32_t>& T) {
     for (int i = 1; p && i < p->n_text; ++i) T.push_back((int32_t)p->text_ids[i]);
     if (!(r->text_open == 1)) T.push_back(EOS_TOKEN);
 }
-int q3_text_rows_set(q3tts_engine* e, int b, const int32_t* T, int from, int n, int n_frames) {
-    const int cap = e->cfg.max_steps_cap, c = std::min(std::max(n, 0), cap);  // (frames stop at max_steps <= cap: later rows are never read)
+int q3_text_rows_set_group(q3tts_engine* e, const Q3TextSet* items, int count) {
+    if (count <= 0) return Q3TTS_OK;
+    const int cap = e->cfg.max_steps_cap;
     hipStream_t s = e->stream;
-    from = std::max(from, 0);
-    if (from < c) Q3_HIP(e, hipMemcpyAsync(e->ts_ids + (size_t)b * cap + from, T + from, (size_t)(c - from) * 4, hipMemcpyHostToDevice, s));
-    const int2 cur = n_frames >= 0 && n_frames < c ? make_int2(1, T[n_frames]) : make_int2(0, 0);
-    Q3_HIP(e, hipMemcpyAsync(e->ts_cnt + b, &c, 4, hipMemcpyHostToDevice, s));
-    Q3_HIP(e, hipMemcpyAsync(e->ts_cur + b, &cur, sizeof(cur), hipMemcpyHostToDevice, s));
+    std::vector<int> cs(count); std::vector<int2> curs(count);
+    for (int i = 0; i < count; ++i) {
+        const Q3TextSet& it = items[i];
+        const int c = std::min(std::max(it.n, 0), cap), from = std::max(it.from, 0);  // (frames stop at max_steps <= cap: later rows are never read)
+        if (from < c) Q3_HIP(e, hipMemcpyAsync(e->ts_ids + (size_t)it.b * cap + from, it.T + from, (size_t)(c - from) * 4, hipMemcpyHostToDevice, s));
+        cs[i] = c; curs[i] = it.n_frames >= 0 && it.n_frames < c ? make_int2(1, it.T[it.n_frames]) : make_int2(0, 0);
+        Q3_HIP(e, hipMemcpyAsync(e->ts_cnt + it.b, &cs[i], 4, hipMemcpyHostToDevice, s));
+        Q3_HIP(e, hipMemcpyAsync(e->ts_cur + it.b, &curs[i], sizeof(int2), hipMemcpyHostToDevice, s));
+    }
     Q3_HIP(e, hipStreamSynchronize(s));  // the uploads read locals
     return Q3TTS_OK;
+}
+int q3_text_rows_set(q3tts_engine* e, int b, const int32_t* T, int from, int n, int n_frames) {
+    const Q3TextSet it{b, T, from, n, n_frames};
+    return q3_text_rows_set_group(e, &it, 1);
 }
 int q3_park_rows(q3tts_engine* e, int b, bool save) {
     const q3tts_model_config& m = e->cfg.model;

@@ -4,6 +4,8 @@
 // steps (q3_run_chunk), the batched vocoder (q3_voc_dispatch, shared with q3tts_generate_batch), then ONE PCM gather launch and ONE
 // device-to-host copy of every slot's new samples into a ring of pinned staging buffers. Chunk events are published when that copy's event has fired (queried, never waited
 // for while slots are decoding), so decode keeps overlapping the vocoder as in q3tts_generate_batch. DESIGN.md §"Streams".
+// Paced requests and swapping: a request whose frame credit is used up is parked like a text-starved one, and with a swap
+// arena parked requests leave their slots for waiting ones (swap_out) and return into any free slot (swap_in); q3_swap.hip moves the state.
 #include "q3_engine.h"
 
 #include <chrono>
@@ -58,7 +60,13 @@ struct IdState {
     // streamed text (include/q3tts.h, "streaming text input"): the request's trailing ids T so far (tts_eos last once closed)
     bool ts = false, closed = true;
     std::vector<int32_t> T;
+    // pacing (include/q3tts.h, "paced requests and swapping"): the frame credit granted so far; kNoLimit once the limit is lifted
+    bool paced = false;
+    long long credit = 0;
 };
+
+constexpr long long kNoLimit = -1;   // a paced request's credit after q3tts_session_grant(frames < 0)
+constexpr long long kNotPaced = -2;  // (Boundary::cr_adm) the popped entry was submitted without a credit
 
 struct SSlot {
     std::unique_ptr<SReq> req;  // null: the slot is free
@@ -68,6 +76,22 @@ struct SSlot {
     bool ts = false, t_closed = true, parked = false;
     int t_len = 0, t_up = 0;
     Q3Slot rec{};
+    // pacing: the worker's view of the credit (collect refreshes it). parked_at: the boundary count when the slot was parked
+    bool paced = false;
+    long long credit = 0;
+    uint64_t parked_at = 0;
+};
+
+struct TextNow { bool have = false, closed = true; std::vector<int32_t> T; };  // a streamed request's text as of this boundary
+
+// A request that left its slot: the slot's bookkeeping as it was when parked, the vocoder's host state, and its block
+struct Swapped {
+    SSlot sl;
+    int voc_frames = 0, frames_done = 0, last_flag = 0, from_slot = -1;
+    long long off = -1, bytes = 0;
+    unsigned long long ticket = 0;  // the move that wrote the block (q3_swap_move)
+    uint64_t ready_at = 0;  // the boundary count when its rule was first seen satisfied again (0: it is not)
+    TextNow tn;             // a text_stream request's whole text as of the last collect that saw it change
 };
 
 }  // namespace
@@ -99,7 +123,16 @@ struct q3tts_session {
     int held_ring = -1;             // ring buffer of the chunk the consumer holds (released at its next call)
     int worker_rc = Q3TTS_OK;
     std::string err;
+    bool grant_dirty = false;       // q3tts_session_grant changed a credit the worker has not seen
+    std::atomic<Q3Swap*> swap{nullptr};  // q3tts_session_set_swap (before the first submission; then the worker's)
+    std::atomic<long long> st_out{0}, st_in{0}, st_moved{0}, st_used{0}, st_peak{0}, st_skipped{0};  // q3tts_session_swap_stats
+    std::atomic<long long> st_out_us{0}, st_in_us{0}, st_bounds{0};  // q3tts_k_swap_phase_ms: host microseconds in the two phases; boundaries that moved a block
     // worker only
+    std::vector<Swapped> out;       // swapped-out requests
+    struct Limbo { long long off, bytes; unsigned long long ticket; };
+    std::vector<Limbo> limbo;       // blocks nobody owns any more whose last move may still be running on a stream (reap_blocks)
+    uint64_t seq = 0;               // chunk boundaries so far
+    bool evict_stuck = false;       // the last swap_out found no room in the arena; cleared when a block or a slot is freed
     std::vector<SSlot> slots;
     std::vector<int> voc_frames;
     std::deque<Batch> flight;
@@ -196,9 +229,34 @@ void run_clone(q3tts_session* s, CloneJob& j) {
     j.rc = rc;
 }
 
+// (worker) A swapped-out request gives its block up. The bytes return to the arena only when the last move that touched them — `ticket`:
+// the save that wrote the block, or the load that read it — has run on BOTH streams: the next block carved over them has another layout,
+// so its decode-stream half may cover what was this block's vocoder-stream half, and nothing orders the two streams. Until then the
+// block waits in limbo (and counts as in use).
+void drop_block(q3tts_session* s, Swapped& o, unsigned long long ticket) {
+    if (o.off < 0) return;
+    s->limbo.push_back({o.off, o.bytes, ticket});
+    o.off = -1;
+}
+// (worker) limbo blocks whose move is over go back to the arena; never waits
+void reap_blocks(q3tts_session* s) {
+    if (s->limbo.empty()) return;
+    Q3Swap* sw = s->swap;
+    size_t keep = 0;
+    for (const auto& l : s->limbo) {
+        if (q3_swap_done(sw, l.ticket)) q3_swap_release(sw, l.off, l.bytes);
+        else s->limbo[keep++] = l;
+    }
+    if (keep == s->limbo.size()) return;
+    s->limbo.resize(keep);
+    s->st_used.store(q3_swap_used(sw), std::memory_order_relaxed);
+    s->evict_stuck = false;
+}
+
 // publish finished batches in order; wait: block on the first one's copy
 int publish(q3tts_session* s, bool wait) {
     q3tts_engine* e = s->e;
+    reap_blocks(s);  // (before any event leaves: q3tts_session_swap_stats read behind a final event sees the blocks of finished moves returned)
     while (!s->flight.empty()) {
         Batch& b = s->flight.front();
         if (b.ring >= 0) {
@@ -208,6 +266,7 @@ int publish(q3tts_session* s, bool wait) {
             s->inflight[b.ring] = false;
         }
         wait = false;
+        reap_blocks(s);  // (again behind the batch's copy: what ran in front of it on the vocoder stream is over)
         const double t = q3_now_ms();
         {
             std::lock_guard<std::mutex> lk(s->mu);
@@ -247,8 +306,9 @@ int take_ring(q3tts_session* s, int k) {
 
 void free_slot(q3tts_session* s, int b) {
     SSlot& sl = s->slots[b];
-    sl.req.reset(); sl.ts = false; sl.parked = false;
+    sl.req.reset(); sl.ts = false; sl.parked = false; sl.paced = false;
     s->e->ts_slot[b] = 0;
+    s->evict_stuck = false;
 }
 
 // the slot's device record (between chunks; the caller synchronises the stream before `rec` can change)
@@ -264,7 +324,7 @@ int park(q3tts_session* s, int b, const Q3Slot& rec) {
     q3tts_engine* e = s->e;
     SSlot& sl = s->slots[b];
     TRY(q3_park_rows(e, b, true));
-    sl.rec = rec; sl.parked = true;
+    sl.rec = rec; sl.parked = true; sl.parked_at = s->seq;
     return put_record(e, b, &idle);
 }
 // after q3_plan_rows with the slot among the live ones: the rows into its row, the record back
@@ -279,14 +339,19 @@ int resume(q3tts_session* s, int b) {
 bool text_ready(const SSlot& sl, int n_frames) {
     return !sl.ts || q3tts_k_text_ready(sl.t_len + (sl.t_closed ? 0 : 1), sl.t_closed ? 1 : 0, n_frames) != 0;  // x = the prompt's id + T without tts_eos
 }
-
-struct TextNow { bool have = false, closed = true; std::vector<int32_t> T; };  // a streamed request's text as of this boundary
+// the two rules of taking the next chunk at n_frames: the text reaches it (streaming text input) and the credit covers it (pacing)
+bool slot_ready(const SSlot& sl, int n_frames) {
+    return text_ready(sl, n_frames) && (!sl.paced || q3tts_k_credit_ready(sl.credit, n_frames) != 0);
+}
+bool gated(const SSlot& sl) { return sl.ts || sl.paced; }
 
 // What one chunk boundary (step) carries from phase to phase, destroyed when step returns. Per member: the phase that fills it and,
 // where an asynchronous upload reads host memory, the synchronisation that memory outlives. (The slots' records live in SSlot and in
 // the engine's staging half: `moved` and `retired` say that an upload of one is in flight.)
 struct Boundary {
     explicit Boundary(int B) : tn(B), cool(B, 0), nf(B, 0), run(B, 0) {}
+    std::vector<long long> cr_adm;               // collect: adm[i]'s credit as of the pop (kNotPaced: submitted without one)
+    int waiting = 0;                             // collect: admissible entries left at the queue's head for want of a slot (swap_out)
     // collect, under one hold of mu
     std::vector<uint64_t> cancels;               // ids to retire (cancel_slots)
     std::vector<q3tts_prefix*> trash;            // released prefixes: voice_work frees them behind a synchronise of the decode stream
@@ -325,6 +390,22 @@ void collect(q3tts_session* s, Boundary& bd) {
     int nfree = 0;
     for (int b = 0; b < B; ++b) if (!s->slots[b].req) ++nfree;
     std::lock_guard<std::mutex> lk(s->mu);
+    // credits first: a swapped-out request whose rule holds again takes a free slot ahead of the queue's head
+    s->grant_dirty = false;
+    for (int b = 0; b < B; ++b)
+        if (s->slots[b].req && s->slots[b].paced) { auto it = s->ids.find(s->slots[b].req->id); if (it != s->ids.end()) s->slots[b].credit = it->second.credit; }
+    for (Swapped& o : s->out) {
+        auto it = s->ids.find(o.sl.req->id);
+        if (it == s->ids.end()) continue;
+        if (o.sl.paced) o.sl.credit = it->second.credit;
+        if (o.sl.ts && ((int)it->second.T.size() != o.sl.t_len || it->second.closed != o.sl.t_closed || !o.tn.have)) {
+            o.tn.have = true; o.tn.closed = it->second.closed; o.tn.T = it->second.T;
+            o.sl.t_closed = o.tn.closed; o.sl.t_len = (int)o.tn.T.size();
+        }
+        const bool rdy = !it->second.cancelled && slot_ready(o.sl, o.sl.rec.n_frames);
+        if (!rdy) o.ready_at = 0;
+        else { if (!o.ready_at) o.ready_at = s->seq; --nfree; }
+    }
     bd.cancels.swap(s->cancels);
     bd.trash.swap(s->trash);
     bd.clones.assign(s->clones.begin(), s->clones.end()); s->clones.clear();
@@ -339,9 +420,15 @@ void collect(q3tts_session* s, Boundary& bd) {
         s->ids[f.id].queued = false;
         unref_prefix(s, x);
         if (xs < 0) bd.orphans.push_back(std::move(s->pending.front()));
-        else { --nfree; bd.adm.push_back(std::move(s->pending.front())); }
+        else { --nfree; bd.cr_adm.push_back(s->ids[f.id].paced ? s->ids[f.id].credit : kNotPaced); bd.adm.push_back(std::move(s->pending.front())); }
         s->pending.pop_front();
     }
+    if (s->swap)  // what still waits at the head and could enter a slot: swap_out makes room for it
+        for (const auto& q : s->pending) {
+            const q3tts_prefix* x = q->kind == 0 ? q->r.prefix : nullptr;
+            if ((x && x->e == e ? x->state.load(std::memory_order_acquire) : 1) != 1) break;
+            ++bd.waiting;
+        }
     s->text_dirty = false;
     for (int b = 0; b < B; ++b) if (s->slots[b].req && s->slots[b].ts) text_now(s, s->slots[b].req->id, s->slots[b].t_up, bd.tn[b]);
     bd.tn_adm.resize(bd.adm.size());
@@ -377,21 +464,127 @@ int cancel_slots(q3tts_session* s, Boundary& bd) {
                 bd.cool[b] = 1; bd.retired = true;
                 bd.bt.evs.push_back(final_ev(id, Q3TTS_EV_CANCELLED, Q3TTS_OK));
             }
+    for (uint64_t id : bd.cancels)  // a swapped-out request holds no slot: its block returns to the arena
+        for (size_t i = 0; i < s->out.size(); ++i)
+            if (s->out[i].sl.req->id == id) {
+                drop_block(s, s->out[i], s->out[i].ticket);
+                s->out.erase(s->out.begin() + i);
+                bd.bt.evs.push_back(final_ev(id, Q3TTS_EV_CANCELLED, Q3TTS_OK));
+                break;
+            }
     return Q3TTS_OK;
 }
 
-// 4. streamed text: what arrived since the last boundary, and the readiness rule — a running slot whose text does not reach 4 more
-// frames is parked before the rows are planned without it
+// 4. streamed text and pacing: what arrived since the last boundary, and the two rules — a running slot whose text does not reach 4 more
+// frames, or whose credit does not cover them, is parked before the rows are planned without it
 int park_starved(q3tts_session* s, Boundary& bd) {
     q3tts_engine* e = s->e;
     for (int b = 0; b < e->B; ++b) {
         SSlot& sl = s->slots[b];
-        if (!sl.req || !sl.ts) continue;
+        if (!sl.req || !gated(sl)) continue;
         const TextNow& t = bd.tn[b];
         if (t.have) { sl.t_closed = t.closed; if (!t.T.empty()) sl.t_len = (int)t.T.size(); }
         bd.nf[b] = sl.parked ? sl.rec.n_frames : e->slots_host[b].n_frames;
-        if (!sl.parked && !text_ready(sl, bd.nf[b])) { TRY(park(s, b, e->slots_host[b])); bd.moved = true; }
+        if (!sl.parked && !slot_ready(sl, bd.nf[b])) { TRY(park(s, b, e->slots_host[b])); bd.moved = true; }
     }
+    return Q3TTS_OK;
+}
+
+// 4a. swapping out: while the slots wanted — swapped-out requests whose rule holds again, and what waits at the queue's
+// head — exceed the free ones, parked slots leave, longest-parked first, each into a block of the arena; one group of launches for all
+// of them. A running slot is never touched, and a slot the arena has no room for simply stays parked. The slot is free from the next
+// boundary on (cool, as a cancelled one): fin_ev orders its next occupant behind the vocoder-state copy.
+int swap_out(q3tts_session* s, Boundary& bd) {
+    q3tts_engine* e = s->e;
+    Q3Swap* sw = s->swap;
+    if (!sw) return Q3TTS_OK;
+    reap_blocks(s);
+    int nfree = 0, ready_out = 0;
+    for (int b = 0; b < e->B; ++b) if (!s->slots[b].req && !bd.cool[b]) ++nfree;
+    for (const Swapped& o : s->out) if (o.ready_at) ++ready_out;
+    int need = ready_out + (int)bd.adm.size() + bd.waiting - nfree;
+    if (need <= 0) return Q3TTS_OK;
+    std::vector<int> cand;
+    for (int b = 0; b < e->B; ++b) if (s->slots[b].req && s->slots[b].parked && !slot_ready(s->slots[b], bd.nf[b])) cand.push_back(b);
+    std::stable_sort(cand.begin(), cand.end(), [&](int a, int b) { return s->slots[a].parked_at < s->slots[b].parked_at; });
+    std::vector<Q3SwapItem> items;
+    for (int b : cand) {
+        if (need <= 0) break;
+        SSlot& sl = s->slots[b];
+        Swapped o;
+        q3_voc_host_state(e, b, &o.frames_done, &o.last_flag, false);
+        o.bytes = q3_swap_block_bytes(e, sw, sl.rec.cur_pos, o.frames_done);
+        o.off = q3_swap_alloc(sw, o.bytes);
+        if (o.off < 0) { s->st_skipped.fetch_add(1, std::memory_order_relaxed); s->evict_stuck = true; continue; }
+        items.push_back(Q3SwapItem{b, sl.rec.cur_pos, o.frames_done, o.off});
+        o.voc_frames = s->voc_frames[b]; o.from_slot = b;
+        o.sl = std::move(sl);
+        s->out.push_back(std::move(o));
+        free_slot(s, b);
+        bd.cool[b] = 1;
+        --need;
+    }
+    if (items.empty()) return Q3TTS_OK;
+    unsigned long long ticket = 0;
+    TRY(q3_swap_move(e, sw, items.data(), (int)items.size(), true, &ticket));
+    for (size_t i = s->out.size() - items.size(); i < s->out.size(); ++i) s->out[i].ticket = ticket;
+    for (const Q3SwapItem& it : items) Q3_HIP(e, hipEventRecord(e->fin_ev[it.slot], e->vstream));
+    s->st_out.fetch_add((long long)items.size(), std::memory_order_relaxed);
+    const long long used = q3_swap_used(sw);
+    s->st_used.store(used, std::memory_order_relaxed);
+    if (used > s->st_peak.load(std::memory_order_relaxed)) s->st_peak.store(used, std::memory_order_relaxed);
+    return Q3TTS_OK;
+}
+
+// 4b. swapping in: swapped-out requests whose rule holds again take free slots, oldest-ready first and ahead of the admissions (collect
+// kept these slots from the queue's head). Each arrives as a parked slot — its rows in the slot's side rows, its record on the host with
+// rng_base re-pointed — so plan_and_admit plans a row for it and resume_and_feed brings it back like any parked slot. Its block goes to
+// limbo behind the load (drop_block).
+int swap_in(q3tts_session* s, Boundary& bd) {
+    q3tts_engine* e = s->e;
+    Q3Swap* sw = s->swap;
+    if (!sw || s->out.empty()) return Q3TTS_OK;
+    std::vector<size_t> order;
+    for (size_t i = 0; i < s->out.size(); ++i) if (s->out[i].ready_at) order.push_back(i);
+    if (order.empty()) return Q3TTS_OK;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return s->out[a].ready_at < s->out[b].ready_at; });
+    std::vector<Q3SwapItem> items;
+    std::vector<size_t> taken;
+    int b = 0;
+    for (size_t i : order) {
+        while (b < e->B && (s->slots[b].req || bd.cool[b])) ++b;
+        if (b >= e->B) break;
+        Swapped& o = s->out[i];
+        Q3_HIP(e, hipEventSynchronize(e->fin_ev[b]));  // the previous occupant's vocoder work is done, as before an admission
+        items.push_back(Q3SwapItem{b, o.sl.rec.cur_pos, o.frames_done, o.off});
+        taken.push_back(i);
+        SSlot& sl = s->slots[b];
+        sl = std::move(o.sl);
+        sl.parked = true; sl.parked_at = s->seq;
+        sl.rec.rng_base = b * e->cfg.max_steps_cap;
+        s->voc_frames[b] = o.voc_frames;
+        q3_voc_host_state(e, b, &o.frames_done, &o.last_flag, true);
+        e->ts_slot[b] = sl.ts ? 1 : 0;
+        bd.nf[b] = sl.rec.n_frames;
+        if (b != o.from_slot) s->st_moved.fetch_add(1, std::memory_order_relaxed);
+        ++b;
+    }
+    if (items.empty()) return Q3TTS_OK;
+    unsigned long long ticket = 0;
+    TRY(q3_swap_move(e, sw, items.data(), (int)items.size(), false, &ticket));
+    std::vector<Q3TextSet> texts;  // the text, whole, from IdState::T as collect copied it; every slot's behind one synchronise
+    for (size_t k = 0; k < taken.size(); ++k) {
+        Swapped& o = s->out[taken[k]];
+        const int sb = items[k].slot;
+        SSlot& sl = s->slots[sb];
+        if (sl.ts) { texts.push_back(Q3TextSet{sb, o.tn.T.data(), 0, (int)o.tn.T.size(), bd.nf[sb]}); sl.t_up = sl.t_len = (int)o.tn.T.size(); }
+        else if (e->ts_used) texts.push_back(Q3TextSet{sb, nullptr, 0, 0, 0});
+        drop_block(s, o, ticket);
+    }
+    TRY(q3_text_rows_set_group(e, texts.data(), (int)texts.size()));
+    std::sort(taken.begin(), taken.end());
+    for (size_t k = taken.size(); k-- > 0;) s->out.erase(s->out.begin() + taken[k]);
+    s->st_in.fetch_add((long long)items.size(), std::memory_order_relaxed);
     return Q3TTS_OK;
 }
 
@@ -414,7 +607,7 @@ int plan_and_admit(q3tts_session* s, Boundary& bd) {
     for (int b : as) Q3_HIP(e, hipEventSynchronize(e->fin_ev[b]));  // the previous occupant's vocoder work is done before the slot's reset
     std::vector<int> live;
     for (size_t i = 0; i < as.size(); ++i) if (bd.adm[i]->kind == 0) live.push_back(as[i]);  // (a prefix job's slot takes no frame step)
-    for (int b = 0; b < B; ++b) if (s->slots[b].req && (!s->slots[b].parked || text_ready(s->slots[b], bd.nf[b]))) live.push_back(b);
+    for (int b = 0; b < B; ++b) if (s->slots[b].req && (!s->slots[b].parked || slot_ready(s->slots[b], bd.nf[b]))) live.push_back(b);
     if (!live.empty()) TRY(q3_plan_rows(e, live));
     if (as.empty()) return Q3TTS_OK;
     std::vector<int> rcs(as.size());
@@ -438,6 +631,7 @@ int plan_and_admit(q3tts_session* s, Boundary& bd) {
         SSlot& sl = s->slots[b];
         sl.req = std::move(q); sl.delivered = 0; s->voc_frames[b] = 0;
         sl.ts = sl.req->r.text_stream == 1; sl.parked = false;
+        sl.paced = bd.cr_adm[i] != kNotPaced; sl.credit = sl.paced ? bd.cr_adm[i] : 0;  // (a credit is >= 4: frame 0 never waits for it)
         if (!sl.ts) continue;
         std::vector<int32_t> T0;  // what the admission put on the device: the request as submitted
         q3_text_trailing(&sl.req->r, T0);
@@ -451,17 +645,17 @@ int plan_and_admit(q3tts_session* s, Boundary& bd) {
     return Q3TTS_OK;
 }
 
-// 6. parked slots whose text suffices come back (the rows were planned with them), and new text goes to the device
+// 6. parked slots whose text and credit suffice come back (the rows were planned with them), and new text goes to the device
 int resume_and_feed(q3tts_session* s, Boundary& bd) {
     q3tts_engine* e = s->e;
     for (int b = 0; b < e->B; ++b) {
         SSlot& sl = s->slots[b];
-        if (!sl.req || !sl.ts) continue;
+        if (!sl.req || !gated(sl)) continue;
         if (sl.parked) {
-            if (!text_ready(sl, bd.nf[b])) continue;
+            if (!slot_ready(sl, bd.nf[b])) continue;
             TRY(resume(s, b)); bd.moved = true;
         }
-        if (sl.t_len > sl.t_up && (int)bd.tn[b].T.size() >= sl.t_len) {
+        if (sl.ts && sl.t_len > sl.t_up && (int)bd.tn[b].T.size() >= sl.t_len) {
             TRY(q3_text_rows_set(e, b, bd.tn[b].T.data(), sl.t_up, sl.t_len, bd.nf[b]));
             sl.t_up = sl.t_len;
         }
@@ -561,10 +755,24 @@ int finish_slots(q3tts_session* s, Boundary& bd) {
 int step(q3tts_session* s) {
     Boundary bd(s->e->B);
     bool idle = false;
+    ++s->seq;
     collect(s, bd);
     TRY(voice_work(s, bd));
     TRY(cancel_slots(s, bd));
     TRY(park_starved(s, bd));
+    if (s->swap) {  // (the two phases' host time, for q3tts_k_swap_phase_ms)
+        const long long o0 = s->st_out.load(std::memory_order_relaxed), i0 = s->st_in.load(std::memory_order_relaxed);
+        const double t0 = q3_now_ms();
+        TRY(swap_out(s, bd));
+        const double t1 = q3_now_ms();
+        TRY(swap_in(s, bd));
+        const double t2 = q3_now_ms();
+        if (s->st_out.load(std::memory_order_relaxed) != o0 || s->st_in.load(std::memory_order_relaxed) != i0) {
+            s->st_out_us.fetch_add((long long)((t1 - t0) * 1e3), std::memory_order_relaxed);
+            s->st_in_us.fetch_add((long long)((t2 - t1) * 1e3), std::memory_order_relaxed);
+            s->st_bounds.fetch_add(1, std::memory_order_relaxed);
+        }
+    }
     TRY(plan_and_admit(s, bd));
     TRY(resume_and_feed(s, bd));
     TRY(run_frames(s, bd, &idle));
@@ -596,12 +804,20 @@ void worker(q3tts_session* s) {
     q3tts_engine* e = s->e;
     int rc = hipSetDevice(e->cfg.device) == hipSuccess ? Q3TTS_OK : q3_set_err(e, Q3TTS_ERR_DEVICE, "session: hipSetDevice");
     while (rc == Q3TTS_OK) {
-        bool running = false, room = false;  // running: a slot takes frame steps (parked slots wait for text); room: a slot is free
-        for (const SSlot& sl : s->slots) { if (sl.req && !sl.parked) running = true; if (!sl.req) room = true; }
+        bool running = false, room = false;  // running: a slot takes frame steps (parked slots wait for text or credit); room: a slot is free
+        bool evictable = false, out_ready = false;  // swapping: a parked slot could leave; a swapped-out request's rule holds again
+        if (!s->limbo.empty()) {  // about to go idle with blocks in limbo: their moves are waited for, so that a full arena cannot keep the worker asleep
+            bool busy = !s->flight.empty();
+            for (const SSlot& sl : s->slots) busy |= sl.req && !sl.parked;
+            if (!busy) { hipStreamSynchronize(e->stream); hipStreamSynchronize(e->vstream); }
+            reap_blocks(s);
+        }
+        for (const SSlot& sl : s->slots) { if (sl.req && !sl.parked) running = true; if (!sl.req) room = true; if (sl.req && sl.parked && s->swap && !s->evict_stuck) evictable = true; }
+        for (const Swapped& o : s->out) if (o.ready_at) out_ready = true;
         bool work;
         {
             std::unique_lock<std::mutex> lk(s->mu);
-            auto todo = [&] { return (room && !s->pending.empty()) || !s->cancels.empty() || s->text_dirty || !s->clones.empty() || !s->trash.empty(); };
+            auto todo = [&] { return ((room || evictable) && (!s->pending.empty() || out_ready)) || !s->cancels.empty() || s->text_dirty || s->grant_dirty || !s->clones.empty() || !s->trash.empty(); };
             if (!running && s->flight.empty())  // idle: sleep until a submission that fits, a cancel, new text or close
                 s->cv_work.wait(lk, [&] { return s->stop || todo(); });
             if (s->stop) break;
@@ -617,6 +833,9 @@ void worker(q3tts_session* s) {
     for (int b = 0; b < e->B; ++b) if (s->slots[b].req) { q3_retire_slot(e, b, e->vstream); free_slot(s, b); }
     hipStreamSynchronize(e->stream);
     hipStreamSynchronize(e->vstream);
+    for (Swapped& o : s->out) drop_block(s, o, o.ticket);  // (their ids got FAILED above, or the session is closing)
+    s->out.clear();
+    reap_blocks(s);  // (every move is over)
     // voice work nobody will run any more: queued jobs' and keep-voice requests' prefixes read failed, waiting clone callers wake
     {
         std::lock_guard<std::mutex> lk(s->mu);
@@ -697,7 +916,8 @@ extern "C" int q3tts_session_create(q3tts_engine* e, int32_t pcm_format, q3tts_s
 }
 
 // q3tts_session_submit, and with out != null q3tts_session_submit_keep_voice: *out receives a pending prefix the request's admission fills
-static int submit_request(q3tts_session* s, const q3tts_request* req, uint64_t* id, int32_t voice_rows, q3tts_prefix** out) {
+// credit > 0: q3tts_session_submit_paced
+static int submit_request(q3tts_session* s, const q3tts_request* req, uint64_t* id, int32_t voice_rows, q3tts_prefix** out, int32_t credit = 0) {
     if (!s || !req || !id) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
     if (out) {
         *out = nullptr;
@@ -735,11 +955,70 @@ static int submit_request(q3tts_session* s, const q3tts_request* req, uint64_t* 
         q->id = s->next_id++;
         IdState st; st.t_submit = q3_now_ms();
         if (q->r.text_stream == 1) { st.ts = true; st.closed = !(q->r.text_open == 1); q3_text_trailing(&q->r, st.T); }
+        if (credit > 0) { st.paced = true; st.credit = credit; }
         s->ids[q->id] = st;
         *id = q->id;
         s->pending.push_back(std::move(q));
     }
     s->cv_work.notify_one();
+    return Q3TTS_OK;
+}
+
+// ---- paced requests and swapping (include/q3tts.h) ----
+extern "C" int q3tts_k_credit_ready(int64_t credit, int32_t n_frames) { return (credit < 0 || (long long)n_frames + 4 <= credit) ? 1 : 0; }
+
+extern "C" int q3tts_session_submit_paced(q3tts_session* s, const q3tts_request* req, int32_t credit_frames, uint64_t* id) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    if (credit_frames < 4) { std::lock_guard<std::mutex> lk(s->mu); return serr(s, Q3TTS_ERR_INVALID, "submit_paced: credit_frames >= 4 (a request takes its frames four at a time)"); }
+    return submit_request(s, req, id, 0, nullptr, credit_frames);
+}
+
+extern "C" int q3tts_session_grant(q3tts_session* s, uint64_t id, int32_t frames) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (frames == 0) return serr(s, Q3TTS_ERR_INVALID, "grant: frames is 0 (> 0 adds to the credit, < 0 lifts the limit)");
+        auto it = s->ids.find(id);
+        if (it == s->ids.end() || it->second.final_ready || it->second.cancelled) return serr(s, Q3TTS_ERR_INVALID, "grant: unknown id, or the request has finished");
+        IdState& st = it->second;
+        if (!st.paced) return serr(s, Q3TTS_ERR_INVALID, "grant: the request was not submitted paced");
+        if (frames < 0) st.credit = kNoLimit;
+        else if (st.credit != kNoLimit) st.credit += frames;
+        s->grant_dirty = true;
+    }
+    s->cv_work.notify_one();
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_set_swap(q3tts_session* s, int64_t arena_bytes) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    std::lock_guard<std::mutex> lk(s->mu);  // (the worker is idle: nothing was submitted)
+    if (s->next_id != 1) return serr(s, Q3TTS_ERR_STATE, "set_swap: valid before the first submission only");
+    if (s->stop || s->dead) return serr(s, Q3TTS_ERR_STATE, "set_swap: the session is closing, or its worker failed");
+    if (arena_bytes < 0) return serr(s, Q3TTS_ERR_INVALID, "set_swap: arena_bytes is negative (0 turns swapping off)");
+    q3tts_engine* e = s->e;
+    if (Q3Swap* old = s->swap.exchange(nullptr)) q3_swap_destroy(e, old);
+    if (arena_bytes == 0) return Q3TTS_OK;
+    Q3Swap* sw = nullptr;
+    const int rc = q3_swap_create(e, arena_bytes, &sw);
+    s->swap = sw;
+    if (rc != Q3TTS_OK) { std::string m; { std::lock_guard<std::mutex> el(e->err_mu); m = e->err; } return serr(s, rc, m); }
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_swap_stats(const q3tts_session* s, int64_t out[6]) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    if (!out) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    out[0] = s->st_out.load(std::memory_order_relaxed); out[1] = s->st_in.load(std::memory_order_relaxed); out[2] = s->st_moved.load(std::memory_order_relaxed);
+    out[3] = s->st_used.load(std::memory_order_relaxed); out[4] = s->st_peak.load(std::memory_order_relaxed); out[5] = s->st_skipped.load(std::memory_order_relaxed);
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_swap_phase_ms(const q3tts_session* s, double out[3]) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    if (!out) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    out[0] = s->st_out_us.load(std::memory_order_relaxed) * 1e-3; out[1] = s->st_in_us.load(std::memory_order_relaxed) * 1e-3;
+    out[2] = (double)s->st_bounds.load(std::memory_order_relaxed);
     return Q3TTS_OK;
 }
 
@@ -931,6 +1210,7 @@ extern "C" int q3tts_session_close(q3tts_session* s) {
     for (SEv& v : s->ready) copy_result_free(v.res);
     for (int k = 0; k < kRing; ++k) { if (s->host[k]) hipHostFree(s->host[k]); if (s->ev[k]) hipEventDestroy(s->ev[k]); }
     if (s->dev) hipFree(s->dev);
+    if (Q3Swap* sw = s->swap.exchange(nullptr)) q3_swap_destroy(e, sw);  // (the worker returned every block and synchronised both streams before it left)
     const int rc = s->worker_rc;
     e->session.store(nullptr);
     delete s;

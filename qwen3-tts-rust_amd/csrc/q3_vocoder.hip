@@ -1536,6 +1536,34 @@ void q3_voc_destroy(q3tts_engine* e) {
     e->voc = nullptr;
 }
 
+// The per-slot history blocks (base + slot * bytes), in pipeline order: THE list of what a slot's streaming state is besides its attention
+// rings and its PCM row. q3_voc_reset zeroes exactly these and a swapped-out request carries exactly these (q3_voc_slot_blocks), so a
+// history buffer added here is both reset and swapped.
+static std::vector<Q3SlotBlock> voc_hist_blocks(const Q3Voc* v) {
+    std::vector<Q3SlotBlock> tab;
+    auto add = [&](const VBuf& b) { if (b.H > 0) { const unsigned long long n = (unsigned long long)b.H * b.C * (b.bf16 ? 2 : 4); tab.push_back({(char*)b.hist, n, n}); } };
+    add(v->pre_in);
+    for (auto& u : v->U) add(u.dw_in);
+    add(v->dec_in_in);
+    for (auto& b : v->Bk) { add(b.ct_in); for (auto& r : b.res) add(r.c1_in); }
+    add(v->out_in);
+    return tab;
+}
+// everything of the vocoder that belongs to one slot and outlives a call, for the swap kernels (q3_swap.hip): the history blocks, then
+// every layer's kring / vring slice [RW][HH]. (The PCM row is q3_voc_pcm / q3_voc_pcm_stride; frames_done / last_flag: q3_voc_host_state.)
+void q3_voc_slot_blocks(q3tts_engine* e, std::vector<Q3SlotBlock>& out) {
+    const Q3Voc* v = e->voc;
+    out = voc_hist_blocks(v);
+    const unsigned long long ring = (unsigned long long)v->RW * v->c.n_head * v->c.head_dim * 4;
+    for (int l = 0; l < v->c.n_layer; ++l)
+        for (float* r : {v->kring, v->vring}) out.push_back({(char*)r + (unsigned long long)l * v->B * ring, ring, ring});
+}
+void q3_voc_host_state(q3tts_engine* e, int slot, int* frames_done, int* last_flag, bool set) {
+    Q3Voc* v = e->voc;
+    if (set) { v->frames_done[slot] = *frames_done; v->last_flag[slot] = *last_flag; }
+    else { *frames_done = v->frames_done[slot]; *last_flag = v->last_flag[slot]; }
+}
+
 // zeroes every history block of a slot: grid (entries, 4)
 __global__ void k_voc_zero(const Q3Voc::ZeroEnt* tab, int slot) {
     const Q3Voc::ZeroEnt z = tab[blockIdx.x];
@@ -1548,12 +1576,7 @@ int q3_voc_reset(q3tts_engine* e, int slot) {
     if (!v) return Q3TTS_OK;
     if (!v->zero_tab) {  // built at the first reset: the work buffers exist by then
         std::vector<Q3Voc::ZeroEnt> tab;
-        auto add = [&](const VBuf& b) { if (b.H > 0) tab.push_back({(char*)b.hist, (unsigned long long)b.H * b.C * (b.bf16 ? 2 : 4)}); };
-        add(v->pre_in);
-        for (auto& u : v->U) add(u.dw_in);
-        add(v->dec_in_in);
-        for (auto& b : v->Bk) { add(b.ct_in); for (auto& r : b.res) add(r.c1_in); }
-        add(v->out_in);
+        for (const Q3SlotBlock& h : voc_hist_blocks(v)) tab.push_back({h.base, h.bytes});
         v->n_zero = (int)tab.size();
         VTRY(valloc(e, v, &v->zero_tab, tab.size()));
         Q3_HIP(e, hipMemcpy(v->zero_tab, tab.data(), tab.size() * sizeof(Q3Voc::ZeroEnt), hipMemcpyHostToDevice));

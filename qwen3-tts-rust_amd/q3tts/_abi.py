@@ -187,6 +187,8 @@ SYMBOLS = [
     "q3tts_k_row_buckets", "q3tts_k_bucket_steps", "q3tts_k_device_bytes", "q3tts_k_engine_footprint", "q3tts_k_prefix_stats",
     "q3tts_session_prefix_create", "q3tts_session_submit_keep_voice", "q3tts_session_prefix_release", "q3tts_session_clone",
     "q3tts_prefix_state", "q3tts_k_prefix_read",
+    "q3tts_session_submit_paced", "q3tts_session_grant", "q3tts_session_set_swap", "q3tts_session_swap_stats",
+    "q3tts_k_credit_ready", "q3tts_k_swap_arena", "q3tts_k_swap_phase_ms",
 ]
 
 
@@ -257,6 +259,13 @@ def load_library(path=None):
     lib.q3tts_prefix_state.restype = C.c_int32
     lib.q3tts_k_prefix_read.argtypes = [vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.q3tts_k_text_ready.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.q3tts_session_submit_paced.argtypes = [vp, C.POINTER(Request), C.c_int32, C.POINTER(C.c_uint64)]
+    lib.q3tts_session_grant.argtypes = [vp, C.c_uint64, C.c_int32]
+    lib.q3tts_session_set_swap.argtypes = [vp, C.c_int64]
+    lib.q3tts_session_swap_stats.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.q3tts_k_credit_ready.argtypes = [C.c_int64, C.c_int32]
+    lib.q3tts_k_swap_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.q3tts_k_swap_arena.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int64)]
     lib.q3tts_k_pcm_pack.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, vp,
                                      C.c_int64]
     lib.q3tts_set_output_rate.argtypes = [vp, C.c_int32]

@@ -299,14 +299,25 @@ class TtsEngine:
                 raise _abi.Q3Error(f"generation failed with status {o.status}")
         return [AudioSample(o.pcm, o.sample_rate, 1) for o in outs]
 
-    def stream_batch_with_voice(self, texts, voices, instructs=None, seeds=None, *, prefix=None):
+    def stream_batch_with_voice(self, texts, voices, instructs=None, seeds=None, *, prefix=None, realtime_lead_s=None):
         """The streaming twin of generate_batch_with_voice: every utterance runs through one session (continuous batching over the
         engine's slots) and its 4-frame chunks are yielded as they are produced, as (index, f32 chunk, is_final); chunks of different
         utterances interleave, each utterance's come in order and its last has is_final = True.
         prefix="auto" (opt-in; the same chunks, bit for bit): within this call the first utterance of each (voice, instruct) pair is
         submitted keep-voice — its own prefill leaves the voice part's K/V behind as a prefix — and the later ones name that prefix while
-        it is still pending, so the voice rows run once per pair. The prefixes are released before the call ends."""
+        it is still pending, so the voice rows run once per pair. The prefixes are released before the call ends.
+        realtime_lead_s (the same chunks, bit for bit): every request is submitted paced and granted frames by the wall clock, so that
+        the audio delivered for it stays at most that many seconds (never less than one 4-frame chunk) ahead of a listener whose
+        playback starts at the request's first chunk. A convenience over NativeSession.grant for consumers that play what they receive;
+        a keep-voice request of prefix="auto" (the first utterance of each voice) is not paced: the C ABI has no paced keep-voice submission."""
+        import time
         sc = self.sampler_config
+        v = self.cfg.vocoder
+        spf = int(np.prod([v.upsample_ratios[i] for i in range(v.n_upsample)] + [v.dec_rates[i] for i in range(v.n_dec_blocks)]))
+        frame_s = spf / float(v.sample_rate)
+        lead = None if realtime_lead_s is None else max(float(realtime_lead_s), 0.0)
+        credit0 = None if lead is None else max(4, int(lead / frame_s) // 4 * 4)
+        granted, started = {}, {}  # paced ids: frames of credit so far; the wall clock of the first chunk
         auto = isinstance(prefix, str)
         if auto and prefix != "auto":
             raise ValueError('prefix= is None, a voice_prefix() handle or "auto"')
@@ -324,15 +335,40 @@ class TtsEngine:
                             rid, made[key] = sess.submit(desc=desc, keep_voice=True, **kw)
                         else:
                             desc, keep = self._desc(t, v, ins, part="text")
-                            rid = sess.submit(desc=desc, prefix=made[key], **kw)
+                            rid = sess.submit(desc=desc, prefix=made[key], credit_frames=credit0, **kw)
+                            if credit0 is not None:
+                                granted[rid] = credit0
                         index[rid] = i
                         continue
                     if prefix is not None:
                         self._check_prefix(prefix, v, ins)
                     desc, keep = self._desc(t, v, ins, part="whole" if prefix is None else "text")
-                    index[sess.submit(desc=desc, prefix=prefix, **kw)] = i
-                for rid, kind, pcm, is_final, res in sess.events():
+                    rid = sess.submit(desc=desc, prefix=prefix, credit_frames=credit0, **kw)
+                    index[rid] = i
+                    if credit0 is not None:
+                        granted[rid] = credit0
+
+                def events():
+                    if lead is None:
+                        yield from sess.events()
+                        return
+                    while sess.open_ids:  # between events: each playing request's credit follows its playback clock
+                        now, live = time.monotonic(), sess.open_ids
+                        nxt = now + 4 * frame_s   # when the earliest next grant falls due
+                        for r, t0 in started.items():
+                            if r in live and r in granted:
+                                want = int((now - t0 + lead) / frame_s) // 4 * 4
+                                if want > granted[r]:
+                                    sess.grant(r, want - granted[r])
+                                    granted[r] = want
+                                nxt = min(nxt, t0 + (granted[r] + 4) * frame_s - lead)
+                        ev = sess.next(max(1, int((nxt - now) * 1000)))
+                        if ev is not None:
+                            yield ev
+
+                for rid, kind, pcm, is_final, res in events():
                     if kind == _abi.EV_CHUNK:
+                        started.setdefault(rid, time.monotonic())
                         yield index[rid], pcm, is_final
                     elif kind == _abi.EV_PREFIX and res.status == 0:
                         continue

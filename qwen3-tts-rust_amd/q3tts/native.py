@@ -468,20 +468,57 @@ class NativeSession:
     """q3tts_session_*: continuous batching with per-request streaming on one engine (include/q3tts.h, "sessions"). The session owns the
     engine until close(); submit() and cancel() may be called from any thread, events() from one consumer thread."""
 
-    def __init__(self, engine: NativeEngine, pcm_format=_abi.PCM_F32):
+    def __init__(self, engine: NativeEngine, pcm_format=_abi.PCM_F32, swap_mb=0):
+        """swap_mb > 0 (q3tts_session_set_swap): a device arena of that many MiB that parked requests are swapped out into while others
+        wait for their slots (include/q3tts.h, "paced requests and swapping"). A fraction is allowed."""
         self.engine, self.lib = engine, engine.lib
         self.dtype = np.int16 if pcm_format == _abi.PCM_I16 else np.float32
         self._ctype = C.c_int16 if pcm_format == _abi.PCM_I16 else C.c_float
         self._open = set()   # ids without their final event yet
         self.h = C.c_void_p()
         engine._check(self.lib.q3tts_session_create(engine.h, pcm_format, C.byref(self.h)), "q3tts_session_create")
+        if swap_mb:
+            try:
+                self.set_swap(int(swap_mb * (1 << 20)))
+            except _abi.Q3Error:
+                self.close()
+                raise
 
     def _check(self, rc, what):
         if rc != 0:
             raise _abi.Q3Error(f"{what} failed ({rc}): {self.lib.q3tts_session_last_error(self.h).decode()}")
 
-    def submit(self, keep_voice=False, voice_rows=0, **request_kw):
-        """request_kw: NativeEngine.make_request keywords, prefix=, text_stream= and text_open= included (want_pcm is ignored: a session
+    @property
+    def open_ids(self):
+        """The ids submitted through this object whose final event next() has not returned yet."""
+        return frozenset(self._open)
+
+    def set_swap(self, arena_bytes):
+        """q3tts_session_set_swap: the swap arena's size in bytes (0: off), before the first submission."""
+        self._check(self.lib.q3tts_session_set_swap(self.h, int(arena_bytes)), "q3tts_session_set_swap")
+
+    def grant(self, rid, frames):
+        """q3tts_session_grant: frames > 0 more frames of credit for a request submitted with credit_frames; frames < 0 lifts its limit.
+        Thread-safe."""
+        self._check(self.lib.q3tts_session_grant(self.h, rid, int(frames)), "q3tts_session_grant")
+
+    def swap_stats(self):
+        """q3tts_session_swap_stats as a dict: swap_outs, swap_ins, moved (swap-ins into another slot), arena_used, arena_peak (bytes),
+        skipped (swap-outs the arena had no room for)."""
+        out = (C.c_int64 * 6)()
+        self._check(self.lib.q3tts_session_swap_stats(self.h, out), "q3tts_session_swap_stats")
+        return dict(zip(("swap_outs", "swap_ins", "moved", "arena_used", "arena_peak", "skipped"), (int(v) for v in out)))
+
+    def swap_phase_ms(self):
+        """q3tts_k_swap_phase_ms: (host ms in swap_out, host ms in swap_in, boundaries that moved a block) so far."""
+        out = (C.c_double * 3)()
+        self._check(self.lib.q3tts_k_swap_phase_ms(self.h, out), "q3tts_k_swap_phase_ms")
+        return float(out[0]), float(out[1]), int(out[2])
+
+    def submit(self, keep_voice=False, voice_rows=0, credit_frames=None, **request_kw):
+        """credit_frames (q3tts_session_submit_paced): the request is paced — it takes its next 4 frames only while n_frames + 4 <= its
+        credit, which starts at credit_frames (>= 4) and grows through grant(). Not with keep_voice.
+        request_kw: NativeEngine.make_request keywords, prefix=, text_stream= and text_open= included (want_pcm is ignored: a session
         always produces PCM). Returns the id.
         keep_voice=True (q3tts_session_submit_keep_voice): a whole-prompt request whose voice part becomes a prefix without a second
         prefill — voice_rows rows of it, 0 = the voice part of desc. Returns (id, prefix): the prefix is pending until its EV_PREFIX
@@ -490,6 +527,12 @@ class NativeSession:
             raise _abi.Q3Error("q3tts_session_submit: the session is closed")
         r, keep = NativeEngine.make_request(**request_kw)
         rid = C.c_uint64(0)
+        if credit_frames is not None:
+            if keep_voice:
+                raise ValueError("submit: credit_frames and keep_voice do not combine")
+            self._check(self.lib.q3tts_session_submit_paced(self.h, C.byref(r), int(credit_frames), C.byref(rid)), "q3tts_session_submit_paced")
+            self._open.add(rid.value)
+            return rid.value
         if not keep_voice:
             self._check(self.lib.q3tts_session_submit(self.h, C.byref(r), C.byref(rid)), "q3tts_session_submit")
             self._open.add(rid.value)

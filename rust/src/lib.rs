@@ -58,6 +58,7 @@ pub enum q3tts_engine {}
 pub enum q3tts_stream {}
 pub enum q3tts_node {}
 pub enum q3tts_prefix {}
+pub enum q3tts_session {}
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct q3tts_node_timings { pub generate_ms: c_float, pub gather_ms: c_float, pub total_ms: c_float, pub gathered_bytes: i64, pub n_devices: i32 }
 
@@ -90,6 +91,12 @@ extern "C" {
     pub fn q3tts_prefix_create(e: *mut q3tts_engine, p: *const q3tts_prompt_desc, embd: *const c_float, n_tok: i32, out: *mut *mut q3tts_prefix) -> c_int;
     pub fn q3tts_prefix_rows(x: *const q3tts_prefix) -> i32;
     pub fn q3tts_prefix_destroy(x: *mut q3tts_prefix) -> c_int;
+    // paced requests and swapping (include/q3tts.h; sessions are otherwise driven through the C header): a frame credit per request,
+    // granted as the listener plays, and a device arena that parked requests are swapped out into while others wait for their slots
+    pub fn q3tts_session_submit_paced(s: *mut q3tts_session, req: *const q3tts_request, credit_frames: i32, id: *mut u64) -> c_int;
+    pub fn q3tts_session_grant(s: *mut q3tts_session, id: u64, frames: i32) -> c_int;
+    pub fn q3tts_session_set_swap(s: *mut q3tts_session, arena_bytes: i64) -> c_int;
+    pub fn q3tts_session_swap_stats(s: *const q3tts_session, out: *mut i64) -> c_int;
     // one node, several GPUs (no counterpart in the reference: n_seq_max = 1, src/models/llama/mod.rs:413): one engine + host thread per device
     // inside the library, request i on device i % n_devices, optional RCCL gather of the i16 PCM to the first device
     pub fn q3tts_node_create(cfg: *const q3tts_engine_config, devices: *const i32, n_devices: i32, out: *mut *mut q3tts_node) -> c_int;
