@@ -824,6 +824,11 @@ int q3tts_k_text_ready(int32_t n_text, int32_t closed, int32_t n_frames);
 /* The credit rule of "paced requests and swapping" as the session worker applies it: 1 iff a paced request with that credit at n_frames
  * frames may take the next chunk of 4 frame steps (n_frames + 4 <= credit; a negative credit is a lifted limit). Needs no GPU. */
 int q3tts_k_credit_ready(int64_t credit, int32_t n_frames);
+/* The rules of a well-formed request that every entry refuses alike (sessions at submit, every admission): text_open needs text_stream;
+ * text_stream needs a prompt built from ids with n_text >= 1; with keep != 0 (the request's voice is to be kept as a prefix, keep_rows =
+ * voice_rows) it names no prefix and states voice_rows >= 1 with prompt_embd, >= 0 with a prompt. Q3TTS_OK, or Q3TTS_ERR_INVALID (a NULL
+ * request too) with the rule named in msg, a string of at most cap - 1 characters (msg may be NULL). Needs no GPU. */
+int q3tts_k_request_rules(const q3tts_request* r, int32_t keep, int32_t keep_rows, char* msg, int32_t cap);
 /* The swap arena's allocator alone (host only): ops[0, n) replayed over an arena of cap bytes. ops[i] > 0 allocates that many bytes:
  * offsets[i] = the block's offset (a multiple of 256), or -1 for "no room". ops[i] = -(k + 1) frees what ops[k] allocated (k < i, a live
  * allocation): offsets[i] = the freed offset. Anything else is Q3TTS_ERR_INVALID. */

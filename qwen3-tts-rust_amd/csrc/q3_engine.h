@@ -18,6 +18,16 @@ struct Q3Voc;  // vocoder (q3_vocoder.hip)
 struct Q3Mel;  // log-mel front-end (q3_mel.hip)
 struct Q3Clone;  // voice-clone encoders (q3_clone.hip)
 
+// a K/V cache: the engine's own (Q3Tfm::cache, q3_tfm_init) or a voice prefix's store seen as one (q3_admit.hip)
+struct Q3KvCache {
+    uint16_t *kc = nullptr, *vc = nullptr;  // [L][slots][Hkv][n_ctx*hd]
+    size_t layer_stride = 0;
+    // cfg.kv_q8_0 (the Talker only; DESIGN.md §22): the cache is ggml Q8_0 blocks — kc / vc hold int8 quants (layer_stride BYTES per layer) and
+    // kd / vd the f16 block scales [L][slots][Hkv][n_ctx*hd/32], which follow the quants in the same allocation. q3_layer_cache does the arithmetic.
+    bool kv8 = false; uint16_t *kd = nullptr, *vd = nullptr;
+    int n_ctx = 0, n_slots = 0;
+};
+
 struct Q3Tfm {
     int L = 0, d = 0, Hq = 0, Hkv = 0, hd = 0, F = 0, nq = 0, nkv = 0, nqkv = 0, head_n = 0;
     std::vector<float*> attn_norm, ffn_norm, qn, kn;
@@ -28,13 +38,8 @@ struct Q3Tfm {
     // these the f16 block scales [N][K/32]; empty / null = bf16 weights
     std::vector<uint16_t*> sqkv, so, sgu, sd; uint16_t* shead = nullptr; bool q8 = false;
     bool a8 = false;  // cfg.talker_q8_0 = 2 / cfg.predictor_q8_0 = 2: the GEMMs' ACTIVATIONS are Q8_0 blocks as well (W8A8, q3_bgemm8.hip): every operand buffer then holds int8 quants + f32 block scales (11-bit significand: q3_q8_sig11)
-    uint16_t *kc = nullptr, *vc = nullptr;  // [L][slots][Hkv][n_ctx*hd]
-    size_t layer_stride = 0;
-    // cfg.kv_q8_0 (the Talker only; DESIGN.md §22): the cache is ggml Q8_0 blocks — kc / vc hold int8 quants (layer_stride BYTES per layer) and
-    // kd / vd the f16 block scales [L][slots][Hkv][n_ctx*hd/32], which follow the quants in the same allocation. q3_layer_cache does the arithmetic.
-    bool kv8 = false; uint16_t *kd = nullptr, *vd = nullptr;
-    int n_ctx = 0, n_slots = 0;
-    float *cs = nullptr, *sn = nullptr;  // RoPE tables [n_ctx][hd/2]
+    Q3KvCache cache;
+    float *cs = nullptr, *sn = nullptr;  // RoPE tables [cache.n_ctx][hd/2]
     size_t weight_bytes = 0;              // bf16 matrix bytes of all layers + head
 };
 
@@ -208,12 +213,18 @@ struct Q3TfmShape {
     int n_ctx, n_slots;       // KV cache: positions per slot, slots
     int kv8;                  // cfg.kv_q8_0: the cache as Q8_0 blocks
 };
-// layer l's part of t's cache: bf16 elements, or (t.kv8) int8 quants and their scales
-inline void q3_layer_cache(const Q3Tfm& t, int l, uint16_t** kc, uint16_t** vc, uint16_t** kd, uint16_t** vd) {
+// layer l's part of the cache t: bf16 elements, or (t.kv8) int8 quants and their scales
+inline void q3_layer_cache(const Q3KvCache& t, int l, uint16_t** kc, uint16_t** vc, uint16_t** kd, uint16_t** vd) {
     if (t.kv8) {
         *kc = (uint16_t*)((int8_t*)t.kc + l * t.layer_stride); *vc = (uint16_t*)((int8_t*)t.vc + l * t.layer_stride);
         *kd = t.kd + l * (t.layer_stride >> 5); *vd = t.vd + l * (t.layer_stride >> 5);
     } else { *kc = t.kc + l * t.layer_stride; *vc = t.vc + l * t.layer_stride; *kd = *vd = nullptr; }
+}
+// the descriptor of K/V copies between t's cache and stores (voice prefixes, swap blocks): everything but the entries
+inline Q3KvPrefix q3_kv_prefix_of(const Q3Tfm& t) {
+    const Q3KvCache& c = t.cache;
+    Q3KvPrefix kp{c.kc, c.vc, c.layer_stride, c.n_ctx, t.L, t.Hkv, t.hd}; kp.kv8 = c.kv8 ? 1 : 0; kp.kd = c.kd; kp.vd = c.vd;
+    return kp;
 }
 // the transformer's weights, KV cache and RoPE tables. g: the opened GGUF `file` (null: seeded synthetic weights);
 // q8mode: cfg.talker_q8_0 / cfg.predictor_q8_0
@@ -238,9 +249,10 @@ struct Q3LayerRun {
     int slot_mod, pos_const;
     const int* seg; int n_seg, seg_max_n, seg_max_t;  // prefill of whole prompts: the rows as per-slot runs (pf_seg), the longest run, the furthest position + 1
     const Q3AttGather* gather;                      // block 0 takes its q / k / v rows from the table: no QKV launch, the gathering attention (q3_launch_attend_gather)
+    const Q3KvCache* cache;                         // the K/V cache the blocks append to and attend over; null: t's own
 };
 // `a.rows` rows of r through every block of t; returns the number of launches the GEMM launcher refused
-int q3_run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& a, Q3Scratch& sc, hipStream_t s);
+int q3_run_layers(q3tts_engine* e, const Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& a, Q3Scratch& sc, hipStream_t s);
 // one frame step over the first B rows of the lane, issued on s; returns the number of refused launches (0 = the frame was issued completely)
 int q3_record_frame(q3tts_engine* e, Q3Lane& L, hipStream_t s, int B);
 // one captured frame step per row bucket, of the variant e->pred_variant names
@@ -319,10 +331,17 @@ enum { BOS_TOKEN = 151672, EOS_TOKEN = 151673 };  // tts_bos, tts_eos (src/tts/p
 enum { PROMPT_WHOLE = 0, PROMPT_VOICE = 1, PROMPT_TEXT = 2 };
 int build_prompt_dev(q3tts_engine* e, const q3tts_prompt_desc* p, float* out, int max_rows, int* n_out, int part = PROMPT_WHOLE, bool text_stream = false);
 
-// the scheduler steps of q3_generate.hip that the session worker (q3_session.hip) drives between 4-frame chunks
-// (q3_plan_rows + q3_admit_many are also the single-request admission of the talker-prefill hook)
+// the scheduler steps that the session worker (q3_session.hip) drives between 4-frame chunks: row planning, the chunk, the vocoder boundary
+// and the result helpers in q3_generate.hip; admission, the streamed-text rows, parking and the voice prefixes in q3_admit.hip
+// (q3_plan_rows + q3_admit_many are also the single-request admission of the talker-prefill hook; q3_admit is that of a stream)
 int q3_plan_rows(q3tts_engine* e, const std::vector<int>& live);
 int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc);
+int q3_admit(q3tts_engine* e, int b, const q3tts_request* r);
+// What a well-formed request / voice job is, as far as no engine is needed to say: the rules every entry refuses alike (pure host code).
+// keep: the request's voice part is to be kept as a prefix, keep_rows rows of it (0: taken from r->prompt). Q3TTS_OK, or Q3TTS_ERR_INVALID
+// with *msg naming the rule; the session sites put their "submit: " / "prefix: " in front (q3tts_k_request_rules is the first as a test hook).
+int q3_request_rules(const q3tts_request* r, bool keep, int keep_rows, const char** msg);
+int q3_voice_job_rules(const q3tts_prompt_desc* p, const float* embd, int n_tok, const char** msg);
 // One entry of an admission group in its general form (q3_admit_many passes requests only). keep != null: after the group's layers the
 // slot's first rows are saved into that (empty) prefix — a request's voice part (keep_rows, 0: taken from r->prompt; 1 <= rows < n), or
 // with r == null a prefill-only prefix job: voice / embd + n_tok as q3tts_prefix_create takes them, into a free slot that stays free.

@@ -1,5 +1,5 @@
 // q3_engine.hip — host side of libq3tts: errors, configuration and validation, the footprint, engine creation and teardown, the setters
-// and the prompt builder: the engine part of the C ABI of include/q3tts.h (prefill, voice prefixes and the continuous batching loop:
+// and the prompt builder: the engine part of the C ABI of include/q3tts.h (prefill and voice prefixes: q3_admit.hip; the continuous batching loop:
 // q3_generate.hip; weights and assets: q3_weights.hip; the transformers' launches and the frame step: q3_layers.hip; the kernel-level
 // test hooks q3tts_k_*: q3_hooks.hip).
 #include "q3_engine.h"

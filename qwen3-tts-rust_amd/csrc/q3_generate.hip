@@ -1,6 +1,6 @@
-// q3_generate.hip — the scheduler of libq3tts: row planning, the frame-step chunk, batched prefill and admission, voice prefixes, the
-// vocoder's chunk boundary, and the drivers built on them: q3tts_generate_batch and q3tts_stream_* here, the session worker in
-// q3_session.hip. The loop restates the reference's run_inference_stream (src/tts/engine.rs:445-656) with every per-frame decision on
+// q3_generate.hip — the scheduler of libq3tts: row planning, the frame-step chunk, the vocoder's chunk boundary, the pinned result pool
+// and result helpers, and the drivers built on them: q3tts_generate_batch and q3tts_stream_* here, the session worker in
+// q3_session.hip. Admission (batched prefill, voice prefixes) is q3_admit.hip. The loop restates the reference's run_inference_stream (src/tts/engine.rs:445-656) with every per-frame decision on
 // the device: one graph replay = sample -> 15 predictor passes -> feedback -> Talker step, no host round trip (the reference crosses
 // the host<->backend boundary >= 33 times per frame).
 #include "q3_engine.h"
@@ -88,347 +88,6 @@ int q3_run_chunk(q3tts_engine* e, int CH, float* dev_ms) {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, e->probe_ev[8], e->probe_ev[9]) == hipSuccess) { e->probe_empty_ms += ms; ++e->probe_empty_cnt; }
     }
-    return Q3TTS_OK;
-}
-
-static uint64_t wall_seed() {
-    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::system_clock::now().time_since_epoch()).count();
-}
-
-// Talker prefill (src/tts/engine.rs:455-462) of several requests at once: their prompt rows are concatenated into one
-// batch (row -> (slot, position) maps), so the weights stream once for all of them; then per request the last row
-// seeds the slot (logits, state, sampler draws). rc[i] receives the per-request status.
-// A request behind a voice prefix (P > 0 rows) brings only its own n rows: they sit at positions P .. P + n - 1 of its slot, whose first
-// P positions receive a copy of the prefix's K/V (k_kv_prefix, one launch for the group) before the layers run.
-// keep (sessions): after the group's layers, positions 0 .. keep_rows - 1 of the slot are copied into that prefix's store
-// (k_kv_prefix_save, one launch for the group). r == null: a prefill-only prefix job — its voice rows ride the group's prefill into a
-// free slot and are saved; no head GEMM, no draws, no slot record, no vocoder reset: the slot never becomes active.
-struct Adm { int b; const q3tts_request* r; int n, row0, max_steps, P; q3tts_prefix* keep; int keep_rows; };
-
-// ---- streamed text (include/q3tts.h, "streaming text input") ----
-void q3_text_trailing(const q3tts_request* r, std::vector<int32_t>& T) {
-    T.clear();
-    const q3tts_prompt_desc* p = r->prompt;
-    for (int i = 1; p && i < p->n_text; ++i) T.push_back((int32_t)p->text_ids[i]);
-    if (!(r->text_open == 1)) T.push_back(EOS_TOKEN);
-}
-int q3_text_rows_set_group(q3tts_engine* e, const Q3TextSet* items, int count) {
-    if (count <= 0) return Q3TTS_OK;
-    const int cap = e->cfg.max_steps_cap;
-    hipStream_t s = e->stream;
-    std::vector<int> cs(count); std::vector<int2> curs(count);
-    for (int i = 0; i < count; ++i) {
-        const Q3TextSet& it = items[i];
-        const int c = std::min(std::max(it.n, 0), cap), from = std::max(it.from, 0);  // (frames stop at max_steps <= cap: later rows are never read)
-        if (from < c) Q3_HIP(e, hipMemcpyAsync(e->ts_ids + (size_t)it.b * cap + from, it.T + from, (size_t)(c - from) * 4, hipMemcpyHostToDevice, s));
-        cs[i] = c; curs[i] = it.n_frames >= 0 && it.n_frames < c ? make_int2(1, it.T[it.n_frames]) : make_int2(0, 0);
-        Q3_HIP(e, hipMemcpyAsync(e->ts_cnt + it.b, &cs[i], 4, hipMemcpyHostToDevice, s));
-        Q3_HIP(e, hipMemcpyAsync(e->ts_cur + it.b, &curs[i], sizeof(int2), hipMemcpyHostToDevice, s));
-    }
-    Q3_HIP(e, hipStreamSynchronize(s));  // the uploads read locals
-    return Q3TTS_OK;
-}
-int q3_text_rows_set(q3tts_engine* e, int b, const int32_t* T, int from, int n, int n_frames) {
-    const Q3TextSet it{b, T, from, n, n_frames};
-    return q3_text_rows_set_group(e, &it, 1);
-}
-int q3_park_rows(q3tts_engine* e, int b, bool save) {
-    const q3tts_model_config& m = e->cfg.model;
-    Q3Lane& L = e->lane;
-    const size_t row = (size_t)e->row_of_slot[b], nl = (size_t)m.t_vocab, nx = (size_t)m.t_d_model;
-    float *lg = L.logits + row * nl, *x = L.T.x + row * nx, *plg = e->park_logits + (size_t)b * nl, *px = e->park_x + (size_t)b * nx;
-    Q3_HIP(e, hipMemcpyAsync(save ? plg : lg, save ? lg : plg, nl * 4, hipMemcpyDeviceToDevice, e->stream));
-    Q3_HIP(e, hipMemcpyAsync(save ? px : x, save ? x : px, nx * 4, hipMemcpyDeviceToDevice, e->stream));
-    return Q3TTS_OK;
-}
-// The text form of the frame step exists before a text_stream request's first frame: its own graph sets for the current Predictor
-// variant, captured the first time one is needed and kept (the variant cannot change while anything is in flight). The sets of the
-// default path are not touched. Without graphs (Q3TTS_NO_GRAPH, the probe) frames are issued eagerly and nothing is captured.
-static int ensure_text_frames(q3tts_engine* e) {
-    e->ts_used = 1;
-    Q3Lane& L = e->lane;
-    const int v = e->pred_variant ? 1 : 0;
-    if (L.execs.empty() || !L.execs_t[v].empty()) return Q3TTS_OK;
-    Q3_HIP(e, hipStreamSynchronize(e->stream));
-    const int was = e->ts_variant;
-    e->ts_variant = 1;
-    const int rc = q3_capture_frames(e, L.graphs_t[v], L.execs_t[v]);
-    e->ts_variant = was;
-    if (rc != Q3TTS_OK) {
-        for (auto ge : L.execs_t[v]) if (ge) hipGraphExecDestroy(ge);
-        for (auto gr : L.graphs_t[v]) if (gr) hipGraphDestroy(gr);
-        L.execs_t[v].clear(); L.graphs_t[v].clear();
-    }
-    return rc;
-}
-
-// The Talker's layers over the first pos.size() prefill rows (e->pf.x holds them): row i sits at position pos[i] of slot slot[i]; seg: the
-// same rows as per-slot runs (pf_seg), seg_max_n the longest run, seg_max_t the furthest position + 1. The maps are uploaded and the stream
-// is synchronised (they are the caller's locals); kp (admission only): the voice prefixes' K/V enter their slots before the layers run.
-// Returns the number of refused launches, or -1 when an upload failed (e->err says which).
-static int prefill_layers(q3tts_engine* e, const std::vector<int>& pos, const std::vector<int>& slot, const std::vector<int>& seg, int seg_max_n,
-                          int seg_max_t, const Q3KvPrefix* kp) {
-    const int rows = (int)pos.size(), d = e->T.d;
-    hipStream_t s = e->stream;
-    hipError_t er = hipMemcpyAsync(e->pf_pos, pos.data(), (size_t)rows * 4, hipMemcpyHostToDevice, s);
-    if (er == hipSuccess) er = hipMemcpyAsync(e->pf_slot, slot.data(), (size_t)rows * 4, hipMemcpyHostToDevice, s);
-    if (er == hipSuccess) er = hipMemcpyAsync(e->pf_seg, seg.data(), seg.size() * 4, hipMemcpyHostToDevice, s);
-    if (er == hipSuccess) er = hipStreamSynchronize(s);
-    if (er != hipSuccess) { q3_set_err(e, Q3TTS_ERR_DEVICE, std::string("prefill row maps: ") + hipGetErrorString(er)); return -1; }
-    if (kp) q3_launch_kv_prefix(*kp, s);
-    const Q3Rows& r = e->pf;
-    if (e->T.a8) q3_launch_norm_inputs_q8(r.x, d, rows, d, e->T.attn_norm[0], (int8_t*)r.xb, r.ascale, r.rt16, r.ssp, d / 16, s);
-    else q3_launch_norm_inputs(r.x, d, rows, d, e->T.attn_norm[0], r.xb, 0, r.ssp, d / 16, s);
-    return q3_run_layers(e, e->T, r, {.rows = rows, .row_pos = e->pf_pos, .row_slot = e->pf_slot, .seg = e->pf_seg, .n_seg = (int)seg.size() / 4,
-                                   .seg_max_n = seg_max_n, .seg_max_t = seg_max_t}, e->sc_pre, s);
-}
-
-static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
-    const q3tts_model_config& m = e->cfg.model;
-    hipStream_t s = e->stream;
-    if (grp.empty()) return Q3TTS_OK;
-    std::vector<int> pos(total), slot(total);
-    for (const Adm& a : grp) for (int i = 0; i < a.n; ++i) { pos[a.row0 + i] = a.P + i; slot[a.row0 + i] = a.b; }
-    int n_kvp_launch = 0; long long n_prefixed = 0;
-    std::vector<int> seg; int seg_max = 0, seg_max_t = 0;  // the same rows as runs: every request's rows are consecutive, positions P .. P + n - 1
-    Q3KvPrefix kp{}; kp.kc = e->T.kc; kp.vc = e->T.vc; kp.layer_stride = e->T.layer_stride; kp.n_ctx = e->T.n_ctx; kp.L = e->T.L; kp.Hkv = e->T.Hkv; kp.hd = e->T.hd;
-    kp.kv8 = e->T.kv8 ? 1 : 0; kp.kd = e->T.kd; kp.vd = e->T.vd;
-    for (const Adm& a : grp) {
-        seg.push_back(a.row0); seg.push_back(a.n); seg.push_back(a.b); seg.push_back(a.P);
-        seg_max = std::max(seg_max, a.n); seg_max_t = std::max(seg_max_t, a.P + a.n);
-        if (a.P > 0) {
-            if (kp.n == Q3_KVP_MAX) { q3_launch_kv_prefix(kp, s); kp.n = 0; ++n_kvp_launch; }  // the descriptor is full (more than 64 prefixed requests in a group): these copies go now, ahead of the group's layers on the same stream
-            const q3tts_prefix* x = a.r->prefix;
-            kp.pk[kp.n] = x->k; kp.pv[kp.n] = x->v; kp.P[kp.n] = x->P; kp.slot[kp.n] = a.b; ++kp.n; ++n_prefixed;
-        }
-    }
-    e->kvp_launches.fetch_add(n_kvp_launch + (kp.n > 0 ? 1 : 0), std::memory_order_relaxed);  // (prefill_layers launches the rest)
-    if (n_prefixed > e->kvp_group_max.load(std::memory_order_relaxed)) e->kvp_group_max.store(n_prefixed, std::memory_order_relaxed);
-    const int rl = prefill_layers(e, pos, slot, seg, seg_max, seg_max_t, &kp);
-    if (rl < 0) return Q3TTS_ERR_DEVICE;
-    if (rl) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefill: a kernel launch was refused for this model shape");
-    Q3_HIP(e, hipGetLastError());
-    bool keeps = false;
-    for (const Adm& a : grp) keeps |= a.keep != nullptr;
-    if (keeps) {  // the slots' voice rows into their prefix stores, behind the layers on the same stream
-        Q3KvPrefix sv = kp; sv.n = 0;
-        for (const Adm& a : grp) {
-            if (!a.keep) continue;
-            if (sv.n == Q3_KVP_MAX) { if (q3_launch_kv_prefix_save(sv, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix save: launch refused for this model shape"); sv.n = 0; }
-            sv.pk[sv.n] = a.keep->k; sv.pv[sv.n] = a.keep->v; sv.P[sv.n] = a.keep_rows; sv.slot[sv.n] = a.b; ++sv.n;
-        }
-        if (q3_launch_kv_prefix_save(sv, s)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix save: launch refused for this model shape");
-        Q3_HIP(e, hipGetLastError());
-    }
-    for (const Adm& a : grp) {
-        const q3tts_request* r = a.r;
-        if (!r) continue;  // a prefix job: the slot stays free
-        const int b = a.b;
-        Q3Lane& L = e->lane;
-        const int row = e->row_of_slot[b];
-        q3_launch_copy_rows(L.T.x + (size_t)row * m.t_d_model, m.t_d_model, e->pf.x + (size_t)(a.row0 + a.n - 1) * m.t_d_model, m.t_d_model, 1, m.t_d_model, s);
-        // the last prompt row's norm inputs for out_norm came out of the last block
-        if (q3_launch_gemm(e, e->T, q3_gemm_head(e->T, 0, m.t_vocab, e->pf, a.row0 + a.n - 1, 1, m.rms_eps, 0, L.logits + (size_t)row * m.t_vocab), s))
-            return q3_set_err(e, Q3TTS_ERR_INVALID, "prefill head: launch refused for this model shape");
-        // sampler stream (src/tts/engine.rs:473-485)
-        float temperature = e->temperature, top_p = e->top_p; int top_k = e->top_k, has_seed = e->has_seed; uint64_t seed = e->seed;
-        if (!r->use_engine_sampler) { temperature = r->temperature; top_k = r->top_k; top_p = r->top_p; has_seed = r->has_seed; seed = r->seed; }
-        if (!has_seed) seed = wall_seed();
-        if (temperature > 0.0f) {
-            std::vector<float> draws(a.max_steps);
-            q3_stdrng_f32(seed, a.max_steps, draws.data());
-            Q3_HIP(e, hipMemcpyAsync(e->rng + (size_t)b * e->cfg.max_steps_cap, draws.data(), (size_t)a.max_steps * 4, hipMemcpyHostToDevice, s));
-            Q3_HIP(e, hipStreamSynchronize(s));
-        }
-        if (e->p_temperature > 0.0f) {  // the Predictor's own stream: draw frame * (n_codebooks - 1) + (q - 1) serves code q of that frame
-            const size_t per = (size_t)(m.n_codebooks - 1), nd = (size_t)a.max_steps * per;
-            std::vector<float> draws(nd);
-            q3_stdrng_f32(seed ^ 0x9E3779B97F4A7C15ull, (int)nd, draws.data());
-            Q3_HIP(e, hipMemcpyAsync(e->prng + (size_t)b * e->cfg.max_steps_cap * per, draws.data(), nd * 4, hipMemcpyHostToDevice, s));
-            Q3_HIP(e, hipStreamSynchronize(s));
-        }
-        if (e->rep_penalty != 1.0f) Q3_HIP(e, hipMemsetAsync(e->seen + (size_t)b * e->seen_words, 0, (size_t)e->seen_words * 4, s));  // generated codes only: a prompt or a voice prefix leaves it empty
-        Q3Slot* st = e->slots_host + e->B + b;  // pinned staging half
-        memset(st, 0, sizeof(*st));
-        st->active = 1; st->cur_pos = a.P + a.n; st->n_frames = 0; st->max_steps = a.max_steps; st->min_frames = r->min_frames;
-        st->force_eos_at = r->force_eos_at; st->top_k = top_k; st->temperature = temperature; st->top_p = top_p;
-        st->rng_base = b * e->cfg.max_steps_cap;
-        st->p_temperature = e->p_temperature; st->p_top_k = e->p_top_k; st->p_top_p = e->p_top_p; st->rep_penalty = e->rep_penalty;
-        Q3_HIP(e, hipMemcpyAsync(e->slots + b, st, sizeof(Q3Slot), hipMemcpyHostToDevice, s));
-        if (r->text_stream == 1) {  // the slot's trailing rows; (nothing here until a text_stream request has been seen: the arrays are zero)
-            std::vector<int32_t> T;
-            q3_text_trailing(r, T);
-            TRY(q3_text_rows_set(e, b, T.data(), 0, (int)T.size(), 0));
-        } else if (e->ts_used) TRY(q3_text_rows_set(e, b, nullptr, 0, 0, 0));
-        e->ts_slot[b] = (r->text_stream == 1) ? 1 : 0;
-        if (e->voc) TRY(q3_voc_reset(e, b));
-    }
-    return Q3TTS_OK;
-}
-
-// bytes of one of a prefix's two stores of np positions, in the slots' format: bf16, or Q8_0 quants with their f16 scales behind them
-size_t q3_prefix_store_bytes(const q3tts_engine* e, int np) {
-    const size_t per = (size_t)e->T.L * e->T.Hkv * np * e->T.hd;
-    return e->T.kv8 ? per + per / 16 : per * 2;
-}
-// the zero-filled store of a prefix that a slot's first `rows` positions will be saved into (k_kv_prefix_save)
-static int prefix_store_alloc(q3tts_engine* e, q3tts_prefix* x, int rows) {
-    if (e->T.hd != Q3_ATT_HD) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the save kernel needs head_dim 128");
-    if (x->k || x->v || x->e != e) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the handle to fill is not an empty one of this engine");
-    const int np = (rows + 63) & ~63;
-    const size_t store = q3_prefix_store_bytes(e, np);
-    int rc = q3_dev_alloc_zeroed(e, (void**)&x->k, store);
-    if (rc == Q3TTS_OK) { rc = q3_dev_alloc_zeroed(e, (void**)&x->v, store); if (rc != Q3TTS_OK) e->dev_bytes -= store; }
-    if (rc != Q3TTS_OK) { hipFree(x->k); x->k = x->v = nullptr; return rc; }
-    x->P = rows; x->np = np;
-    return Q3TTS_OK;
-}
-void q3_prefix_free(q3tts_prefix* x) {
-    for (uint16_t* p : {x->k, x->v}) if (p) { x->e->dev_bytes -= q3_prefix_store_bytes(x->e, x->np); hipFree(p); }
-    delete x;
-}
-
-// One item's rows join the prefill batch behind the `total` rows it holds: n_tok host rows (embd), or `part` of p built on the device; at
-// most max_rows of them. A batch too full for them is flushed (admit_group) and the item placed in the empty one. *n: the row count, or
-// the item's status (< 0) when even that fails. The return value is the admission's own status (a failed flush or upload ends it).
-static int place_rows(q3tts_engine* e, std::vector<Adm>& grp, int& total, int max_rows, const float* embd, int n_tok, const q3tts_prompt_desc* p,
-                      int part, bool text_stream, int* n) {
-    const size_t d = (size_t)e->cfg.model.d_embed;
-    for (;;) {
-        const int room = std::min(e->cfg.n_ctx - total, max_rows);
-        int st = Q3TTS_OK;
-        if (!embd) st = build_prompt_dev(e, p, e->pf.x + total * d, room, n, part, text_stream);
-        else if (n_tok > room) st = total ? Q3TTS_ERR_INVALID : q3_set_err(e, Q3TTS_ERR_INVALID, "n_tok out of range");
-        else { *n = n_tok; Q3_HIP(e, hipMemcpyAsync(e->pf.x + total * d, embd, n_tok * d * 4, hipMemcpyHostToDevice, e->stream)); }
-        if (st == Q3TTS_OK) return Q3TTS_OK;
-        if (total == 0) { *n = st; return Q3TTS_OK; }
-        TRY(admit_group(e, grp, total));  // batch full: flush, then retry this item in an empty batch
-        grp.clear(); total = 0;
-    }
-}
-
-// items[i] enters its slot; rc[i] = status of item i (a failing item does not stop the others)
-int q3_admit_items(q3tts_engine* e, const Q3AdmItem* items, int count, int* rc) {
-    std::vector<Adm> grp;
-    int total = 0;
-    for (int i = 0; i < count; ++i) {
-        const Q3AdmItem& it = items[i];
-        const q3tts_request* r = it.r;
-        rc[i] = Q3TTS_OK;
-        if (!r) {  // a prefill-only prefix job: 1 <= rows < n_ctx, as q3tts_prefix_create
-            if (!it.keep || (it.voice != nullptr) == (it.embd != nullptr)) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: give exactly one of a voice desc or host rows"); continue; }
-            if (it.embd && (it.n_tok <= 0 || it.n_tok >= e->cfg.n_ctx)) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: n_tok outside 1 .. n_ctx - 1"); continue; }
-            int n = 0;
-            TRY(place_rows(e, grp, total, e->cfg.n_ctx - 1, it.embd, it.n_tok, it.voice, PROMPT_VOICE, false, &n));
-            if (n < 0) rc[i] = n;
-            if (rc[i] == Q3TTS_OK && n < 1) rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the voice part has no rows");
-            if (rc[i] == Q3TTS_OK) rc[i] = prefix_store_alloc(e, it.keep, n);
-            if (rc[i] != Q3TTS_OK) continue;
-            grp.push_back(Adm{it.slot, nullptr, n, total, 0, 0, it.keep, n});
-            total += n;
-            continue;
-        }
-        const int max_steps = r->max_steps > 0 ? r->max_steps : e->max_steps;
-        if (max_steps > e->cfg.max_steps_cap) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "max_steps exceeds max_steps_cap"); continue; }
-        const q3tts_prefix* x = r->prefix;
-        if (x && x->e != e) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: made by another engine"); continue; }
-        if (x && x->state.load(std::memory_order_acquire) != 1) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: not ready (a session's pending or failed prefix)"); continue; }
-        if (x && it.keep) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "keep-voice: a request that names a prefix cannot keep one"); continue; }
-        if (it.keep && it.keep_rows == 0 && (r->prompt_embd || !r->prompt)) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "keep-voice: a prompt_embd request states its voice rows"); continue; }
-        if (it.keep && it.keep_rows < 0) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "keep-voice: voice_rows is negative"); continue; }
-        const int P = x ? x->P : 0;  // the prefix's rows come first; only the request's own rows enter the prefill buffer
-        if ((r->text_open == 1) && !(r->text_stream == 1)) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "text_open needs text_stream = 1"); continue; }
-        if (r->text_stream == 1) {
-            if (r->prompt_embd || !r->prompt) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "text_stream needs a prompt built from ids (prompt), not prompt_embd"); continue; }
-            if (r->prompt->n_text < 1 || !r->prompt->text_ids) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "text_stream: the prompt needs n_text >= 1 (its first text id is the prompt's last row)"); continue; }
-            const int trc = ensure_text_frames(e);
-            if (trc != Q3TTS_OK) { rc[i] = trc; continue; }
-        }
-        if (r->prompt_embd && (r->n_tok <= 0 || P + r->n_tok > e->cfg.n_ctx)) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "n_tok out of range"); continue; }
-        if (!r->prompt_embd && !r->prompt) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "request has neither prompt_embd nor prompt"); continue; }
-        int n = 0;
-        TRY(place_rows(e, grp, total, e->cfg.n_ctx, r->prompt_embd, r->n_tok, r->prompt, x ? PROMPT_TEXT : PROMPT_WHOLE, r->text_stream == 1, &n));
-        if (n < 0) rc[i] = n;
-        if (rc[i] != Q3TTS_OK) continue;
-        if (P + n > e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prefix + prompt longer than n_ctx"); continue; }
-        if (P + n + max_steps > e->cfg.n_ctx) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "prompt + max_steps exceeds n_ctx"); continue; }
-        int keep_rows = 0;
-        if (it.keep) {  // the voice part of a whole prompt: everything in front of the text part's n_text + 3 rows (text_stream: 2)
-            keep_rows = it.keep_rows > 0 ? it.keep_rows : n - (r->text_stream == 1 ? 2 : r->prompt->n_text + 3);
-            if (keep_rows < 1 || keep_rows >= n) { rc[i] = q3_set_err(e, Q3TTS_ERR_INVALID, "keep-voice: voice_rows outside 1 .. n - 1"); continue; }
-            rc[i] = prefix_store_alloc(e, it.keep, keep_rows);
-            if (rc[i] != Q3TTS_OK) continue;
-        }
-        grp.push_back(Adm{it.slot, r, n, total, max_steps, P, it.keep, keep_rows});
-        total += n;
-    }
-    return admit_group(e, grp, total);
-}
-
-// slots[i] <- reqs[i]; rc[i] = status of request i (a failing request does not stop the others)
-int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc) {
-    std::vector<Q3AdmItem> items(count);
-    for (int i = 0; i < count; ++i) { items[i] = Q3AdmItem{}; items[i].slot = slots[i]; items[i].r = reqs[i]; }
-    return q3_admit_items(e, items.data(), count, rc);
-}
-
-static int admit(q3tts_engine* e, int b, const q3tts_request* r) {
-    int rc = Q3TTS_OK;
-    int st = q3_admit_many(e, &b, &r, 1, &rc);
-    return st != Q3TTS_OK ? st : rc;
-}
-
-// ------------------------------------------------------------------------------------------------
-// voice prefixes (include/q3tts.h): the Talker runs the voice rows once, at positions 0 .. P - 1, straight into the prefix store — for
-// that one run the Talker's cache fields point at the store, a cache of one slot and np = ceil(P / 64) * 64 positions — so no slot's
-// state changes. Same launches, same rows, same positions as the whole prompt's prefill: the same K/V bits.
-// ------------------------------------------------------------------------------------------------
-extern "C" int q3tts_prefix_create(q3tts_engine* e, const q3tts_prompt_desc* p, const float* embd, int32_t n_tok, q3tts_prefix** out) {
-    if (!e || !out) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
-    Q3_NOT_IN_SESSION(e);
-    *out = nullptr;
-    if ((p != nullptr) == (embd != nullptr)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: give exactly one of a voice desc or host rows");
-    Q3_HIP(e, hipSetDevice(e->cfg.device));
-    const q3tts_model_config& m = e->cfg.model;
-    hipStream_t s = e->stream;
-    const int n_ctx = e->cfg.n_ctx;
-    int n = 0;
-    if (p) TRY(build_prompt_dev(e, p, e->pf.x, n_ctx - 1, &n, PROMPT_VOICE));
-    else {
-        if (n_tok <= 0 || n_tok >= n_ctx) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: n_tok outside 1 .. n_ctx - 1");
-        n = n_tok;
-        Q3_HIP(e, hipMemcpyAsync(e->pf.x, embd, (size_t)n * m.d_embed * 4, hipMemcpyHostToDevice, s));
-    }
-    Q3Tfm& t = e->T;
-    q3tts_prefix* x = new q3tts_prefix();
-    x->e = e;
-    const int rc = prefix_store_alloc(e, x, n);
-    if (rc != Q3TTS_OK) { q3_prefix_free(x); return rc; }
-    auto fail = [&](int code, const std::string& msg) { hipStreamSynchronize(s); q3_prefix_free(x); return q3_set_err(e, code, msg); };
-    std::vector<int> pos(n), zero(n, 0);
-    for (int i = 0; i < n; ++i) pos[i] = i;
-    uint16_t *kc = t.kc, *vc = t.vc, *kd = t.kd, *vd = t.vd; const size_t ls = t.layer_stride; const int nc = t.n_ctx;
-    t.kc = x->k; t.vc = x->v; t.layer_stride = (size_t)t.Hkv * x->np * t.hd; t.n_ctx = x->np;
-    if (t.kv8) { const size_t quants = t.L * t.layer_stride; t.kd = (uint16_t*)((int8_t*)x->k + quants); t.vd = (uint16_t*)((int8_t*)x->v + quants); }  // (the scales follow the quants)
-    const int rl = prefill_layers(e, pos, zero, {0, n, 0, 0}, n, n, nullptr);
-    t.kc = kc; t.vc = vc; t.kd = kd; t.vd = vd; t.layer_stride = ls; t.n_ctx = nc;
-    if (rl < 0) return fail(Q3TTS_ERR_DEVICE, std::string(e->err));
-    if (rl) return fail(Q3TTS_ERR_INVALID, "prefix: a kernel launch was refused for this model shape");
-    hipError_t er = hipGetLastError();
-    if (er == hipSuccess) er = hipStreamSynchronize(s);
-    if (er != hipSuccess) return fail(Q3TTS_ERR_DEVICE, hipGetErrorString(er));
-    *out = x;
-    return Q3TTS_OK;
-}
-extern "C" int32_t q3tts_prefix_rows(const q3tts_prefix* x) { return x && x->state.load(std::memory_order_acquire) == 1 ? x->P : 0; }
-extern "C" int32_t q3tts_prefix_state(const q3tts_prefix* x) { return x ? x->state.load(std::memory_order_acquire) : Q3TTS_ERR_INVALID; }
-extern "C" int q3tts_prefix_destroy(q3tts_prefix* x) {
-    if (!x) return Q3TTS_OK;
-    q3tts_engine* e = x->e;
-    Q3_NOT_IN_SESSION(e);  // an open session may still admit requests that name it
-    hipSetDevice(e->cfg.device);
-    hipStreamSynchronize(e->stream);
-    q3_prefix_free(x);
     return Q3TTS_OK;
 }
 
@@ -774,7 +433,7 @@ extern "C" int q3tts_stream_begin(q3tts_engine* e, const q3tts_request* req, q3t
     q3tts_stream* st = new q3tts_stream();
     st->e = e; st->req = *req; st->t0 = q3_now_ms();
     int rc = q3_plan_rows(e, std::vector<int>{0});
-    if (rc == Q3TTS_OK) rc = admit(e, 0, req);
+    if (rc == Q3TTS_OK) rc = q3_admit(e, 0, req);
     if (rc != Q3TTS_OK) { delete st; return rc; }
     ++e->streams_open;
     *out = st;

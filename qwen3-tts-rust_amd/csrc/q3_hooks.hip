@@ -867,8 +867,7 @@ static int talker_prefill(q3tts_engine* e, const q3tts_prefix* prefix, const flo
         Q3_HIP(e, hipMemcpyAsync(hidden_out, L.logits_tmp, (size_t)m.t_d_model * 4, hipMemcpyDeviceToHost, s));
     }
     if (logits_out) Q3_HIP(e, hipMemcpyAsync(logits_out, L.logits, (size_t)m.t_vocab * 4, hipMemcpyDeviceToHost, s));
-    Q3Slot* stage = e->slots_host + e->B; memset(stage, 0, sizeof(Q3Slot));
-    Q3_HIP(e, hipMemcpyAsync(e->slots, stage, sizeof(Q3Slot), hipMemcpyHostToDevice, s));  // retire the slot again
+    TRY(q3_retire_slot(e, slot, s));  // retire the slot again
     Q3_HIP(e, hipStreamSynchronize(s));
     return Q3TTS_OK;
 }
@@ -879,6 +878,13 @@ extern "C" int q3tts_k_talker_prefill_prefix(q3tts_engine* e, const q3tts_prefix
                                              float* logits_out) {
     if (!prefix) return q3_set_err(e, Q3TTS_ERR_INVALID, "null prefix");
     return talker_prefill(e, prefix, embd, n_tok, hidden_out, logits_out);
+}
+// q3_request_rules (q3_admit.hip) with its message copied into msg[cap] (host only)
+extern "C" int q3tts_k_request_rules(const q3tts_request* r, int32_t keep, int32_t keep_rows, char* msg, int32_t cap) {
+    const char* why = "";
+    const int st = q3_request_rules(r, keep != 0, keep_rows, &why);
+    if (msg && cap > 0) { strncpy(msg, why, (size_t)cap - 1); msg[cap - 1] = 0; }
+    return st;
 }
 
 // a ready prefix's two stores as bytes, padding included (*bytes: the size of each; k / v may be null to ask for it)

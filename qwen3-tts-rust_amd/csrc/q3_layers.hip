@@ -83,10 +83,11 @@ int q3_launch_gemm(q3tts_engine* e, const Q3Tfm& t, const Q3BGemm& g, hipStream_
 // (+ SwiGLU), down GEMM (+ residual, + the next block's / the head's norm inputs). x: f32 residual rows; xb / ssp: their norm
 // inputs for attn_norm[0] on entry, for out_norm on exit. Restated by oracle/q3_oracle.c tfm_layers.
 // Returns the number of launches a launcher refused (a shape it cannot run: stale activations would follow silently).
-int q3_run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& a, Q3Scratch& sc, hipStream_t s) {
+int q3_run_layers(q3tts_engine* e, const Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& a, Q3Scratch& sc, hipStream_t s) {
     const float eps = e->cfg.model.rms_eps;
     int bad = 0;
     const int once = &t == &e->T ? 1 : 0;
+    const Q3KvCache& c = a.cache ? *a.cache : t.cache;
     for (int l = 0; l < t.L; ++l) {
         hipEvent_t* pe = l == 0 ? a.probe : nullptr;  // the probe brackets one launch of block 0
         // block 0 of a gathering pass has no QKV launch (its rows come from e->qkv0): the QKV probe then brackets block 1's, the same shape and instance
@@ -94,15 +95,15 @@ int q3_run_layers(q3tts_engine* e, Q3Tfm& t, const Q3Rows& r, const Q3LayerRun& 
         if (!gather) bad += q3_launch_gemm(e, t, q3_gemm_qkv(t, l, r, sc, a.rows, eps, once), s, l == (a.gather ? 1 : 0) ? a.probe : nullptr, 1);
         Q3QkPrep qp{}; qp.qkv = sc.qkv; qp.ld = t.nqkv; qp.rows = a.rows; qp.Hq = t.Hq; qp.Hkv = t.Hkv; qp.hd = t.hd;
         qp.qnw = t.qn[l]; qp.knw = t.kn[l]; qp.eps = eps; qp.cs = t.cs; qp.sn = t.sn;
-        q3_layer_cache(t, l, &qp.kc, &qp.vc, &qp.kd, &qp.vd); qp.kv8 = t.kv8 ? 1 : 0;  // (kv_q8_0: quants + scales, and the kernels of q3_attend_kv8.hip)
-        qp.n_ctx = t.n_ctx; qp.row_pos = a.row_pos; qp.row_slot = a.row_slot;
+        q3_layer_cache(c, l, &qp.kc, &qp.vc, &qp.kd, &qp.vd); qp.kv8 = c.kv8 ? 1 : 0;  // (kv_q8_0: quants + scales, and the kernels of q3_attend_kv8.hip)
+        qp.n_ctx = c.n_ctx; qp.row_pos = a.row_pos; qp.row_slot = a.row_slot;
         qp.slot_mod = a.slot_mod; qp.pos_const = a.pos_const;
         const bool fused = a.one_row_per_slot && t.Hq / t.Hkv >= 2;
         // the Predictor's pass A: rows [0, B) at position 0 and [B, 2B) at position 1 of an empty per-frame cache: one fused launch
         const bool pair = !a.one_row_per_slot && a.slot_mod > 0 && a.rows == 2 * a.slot_mod && a.pos_const == 0 && t.Hq / t.Hkv == 2 && t.hd == 128;
         if (!fused && !pair) bad += q3_launch_qk_prep(qp, s) ? 1 : 0;
         Q3Attend at{}; at.qkv = sc.qkv; at.ld = t.nqkv; at.rows = a.rows; at.out = (float*)sc.att; at.ldo = t.nq; at.Hq = t.Hq; at.Hkv = t.Hkv; at.hd = t.hd;
-        at.kc = qp.kc; at.vc = qp.vc; at.kv8 = qp.kv8; at.kd = qp.kd; at.vd = qp.vd; at.n_ctx = t.n_ctx; at.row_pos = a.row_pos; at.row_slot = a.row_slot;
+        at.kc = qp.kc; at.vc = qp.vc; at.kv8 = qp.kv8; at.kd = qp.kd; at.vd = qp.vd; at.n_ctx = c.n_ctx; at.row_pos = a.row_pos; at.row_slot = a.row_slot;
         at.fused = pair ? 2 : (fused ? 1 : 0); at.prep = qp; at.out_bf16 = 1; at.slot_mod = a.slot_mod; at.pos_const = a.pos_const;
         if (t.a8) { at.out_bf16 = 2; at.out_scale = sc.asc_att; at.out_rt16 = sc.rt16; }
         if (!fused && !pair && a.n_seg > 0) { at.seg = a.seg; at.n_seg = a.n_seg; at.seg_max_n = a.seg_max_n; at.seg_max_t = a.seg_max_t; }  // prefill of whole prompts (prefill_layers): the launch's rows as per-slot runs

@@ -919,22 +919,13 @@ extern "C" int q3tts_session_create(q3tts_engine* e, int32_t pcm_format, q3tts_s
 // credit > 0: q3tts_session_submit_paced
 static int submit_request(q3tts_session* s, const q3tts_request* req, uint64_t* id, int32_t voice_rows, q3tts_prefix** out, int32_t credit = 0) {
     if (!s || !req || !id) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
-    if (out) {
-        *out = nullptr;
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (req->prefix) return serr(s, Q3TTS_ERR_INVALID, "submit_keep_voice: a request that names a prefix cannot keep one");
-        if (voice_rows < 0 || (voice_rows == 0 && (req->prompt_embd || !req->prompt)))
-            return serr(s, Q3TTS_ERR_INVALID, "submit_keep_voice: voice_rows >= 1 with prompt_embd, >= 0 with a prompt built from ids");
-    }
+    if (out) *out = nullptr;
+    const char* why = "";
+    if (q3_request_rules(req, out != nullptr, voice_rows, &why) != Q3TTS_OK) { std::lock_guard<std::mutex> lk(s->mu); return serr(s, Q3TTS_ERR_INVALID, std::string("submit: ") + why); }
     std::unique_ptr<SReq> q(new SReq());
     if (copy_request(s->e, req, q.get()) != Q3TTS_OK) {
         std::lock_guard<std::mutex> lk(s->mu);
         return serr(s, Q3TTS_ERR_INVALID, "submit: the request's prompt cannot be copied (n_tok outside 1..n_ctx or a null array with a length)");
-    }
-    if ((req->text_open == 1) && !(req->text_stream == 1)) { std::lock_guard<std::mutex> lk(s->mu); return serr(s, Q3TTS_ERR_INVALID, "submit: text_open needs text_stream = 1"); }
-    if ((req->text_stream == 1) && (req->prompt_embd || !req->prompt || req->prompt->n_text < 1)) {
-        std::lock_guard<std::mutex> lk(s->mu);
-        return serr(s, Q3TTS_ERR_INVALID, "submit: text_stream needs a prompt built from ids with n_text >= 1 (not prompt_embd)");
     }
     {
         std::lock_guard<std::mutex> lk(s->mu);
@@ -1033,9 +1024,9 @@ extern "C" int q3tts_session_submit_keep_voice(q3tts_session* s, const q3tts_req
 extern "C" int q3tts_session_prefix_create(q3tts_session* s, const q3tts_prompt_desc* p, const float* embd, int32_t n_tok, q3tts_prefix** out, uint64_t* id) {
     if (!s || !out || !id) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
     *out = nullptr;
-    auto refuse = [&](int code, const char* m) { std::lock_guard<std::mutex> lk(s->mu); return serr(s, code, m); };
-    if ((p != nullptr) == (embd != nullptr)) return refuse(Q3TTS_ERR_INVALID, "prefix: give exactly one of a voice desc or host rows");
-    if (embd && n_tok <= 0) return refuse(Q3TTS_ERR_INVALID, "prefix: n_tok outside 1 .. n_ctx - 1");
+    auto refuse = [&](int code, const std::string& m) { std::lock_guard<std::mutex> lk(s->mu); return serr(s, code, m); };
+    const char* why = "";
+    if (q3_voice_job_rules(p, embd, n_tok, &why) != Q3TTS_OK) return refuse(Q3TTS_ERR_INVALID, std::string("prefix: ") + why);
     if (p && p->n_text != 0) return refuse(Q3TTS_ERR_INVALID, "prefix: a voice desc has n_text == 0");
     std::unique_ptr<SReq> q(new SReq());
     q->kind = 1; q->n_tok = n_tok;

@@ -120,7 +120,7 @@ int q3_swap_create(q3tts_engine* e, long long arena_bytes, Q3Swap** out) {
     *out = nullptr;
     if (arena_bytes <= 0) return q3_set_err(e, Q3TTS_ERR_INVALID, "swap: the arena needs a positive size");
     if (!e->voc) return q3_set_err(e, Q3TTS_ERR_STATE, "swap: the engine has no vocoder");
-    if (e->T.hd != Q3_ATT_HD || e->T.n_ctx % 64) return q3_set_err(e, Q3TTS_ERR_UNSUPPORTED, "swap: the K/V copy needs head_dim 128 and n_ctx in whole key blocks");
+    if (e->T.hd != Q3_ATT_HD || e->T.cache.n_ctx % 64) return q3_set_err(e, Q3TTS_ERR_UNSUPPORTED, "swap: the K/V copy needs head_dim 128 and n_ctx in whole key blocks");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     size_t free_b = 0, total_b = 0;
     Q3_HIP(e, hipMemGetInfo(&free_b, &total_b));
@@ -182,13 +182,12 @@ void q3_swap_destroy(q3tts_engine* e, Q3Swap* sw) {
 int q3_swap_move(q3tts_engine* e, Q3Swap* sw, const Q3SwapItem* items, int n, bool save, unsigned long long* ticket) {
     for (int g0 = 0; g0 < n; g0 += Q3_KVP_MAX) {
         const int c = std::min(n - g0, (int)Q3_KVP_MAX);
-        Q3KvPrefix kp{}; kp.kc = e->T.kc; kp.vc = e->T.vc; kp.layer_stride = e->T.layer_stride; kp.n_ctx = e->T.n_ctx; kp.L = e->T.L; kp.Hkv = e->T.Hkv; kp.hd = e->T.hd;
-        kp.kv8 = e->T.kv8 ? 1 : 0; kp.kd = e->T.kd; kp.vd = e->T.vd; kp.n = c;
+        Q3KvPrefix kp = q3_kv_prefix_of(e->T); kp.n = c;
         SwapReq rq{};
         for (int i = 0; i < c; ++i) {
             const Q3SwapItem& it = items[g0 + i];
             const long long need = q3_swap_block_bytes(e, sw, it.cur_pos, it.voc_frames);
-            if (it.slot < 0 || it.slot >= e->B || it.cur_pos < 1 || it.cur_pos > e->T.n_ctx || it.off < 0 || (it.off & 255) || it.off + need > sw->cap)
+            if (it.slot < 0 || it.slot >= e->B || it.cur_pos < 1 || it.cur_pos > e->T.cache.n_ctx || it.off < 0 || (it.off & 255) || it.off + need > sw->cap)
                 return q3_set_err(e, Q3TTS_ERR_STATE, "swap: a block lies outside the arena, or a slot or position outside the engine's");
             const size_t store = q3_prefix_store_bytes(e, kv_np(it.cur_pos));
             char* blk = sw->base + it.off;

@@ -95,7 +95,7 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
     const bool q8 = q8mode != 0;
     const int grp = sh.grp, L = sh.L, d = sh.d, hd = sh.hd, F = sh.F;
     t.L = L; t.d = d; t.Hq = sh.Hq; t.Hkv = sh.Hkv; t.hd = hd; t.F = F; t.nq = sh.Hq * hd; t.nkv = sh.Hkv * hd; t.nqkv = t.nq + 2 * t.nkv;
-    t.head_n = sh.head_n; t.n_ctx = sh.n_ctx; t.n_slots = sh.n_slots; t.q8 = q8; t.a8 = q8mode == 2;
+    t.head_n = sh.head_n; t.q8 = q8; t.a8 = q8mode == 2;
     GgSrc src{e, g, file};
     GgSrc* gg = g ? &src : nullptr;
     const uint64_t seed = e->cfg.synth_seed;
@@ -175,18 +175,19 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
         Q3Fill f{}; f.seed = seed; f.scale = ms; f.dst = t.head; f.N = t.head_n; f.K = d; f.mode = 0; f.row0 = 0; f.rows = t.head_n;
         f.tid_a = Q3_TID(grp, Q3_L_MODEL, Q3WM_HEAD); fill(f, t.shead);
     }
-    t.layer_stride = (size_t)t.n_slots * t.Hkv * t.n_ctx * hd;
-    t.kv8 = sh.kv8 != 0;
-    if (t.kv8) {  // Q8_0 cache: per element one byte of quants + 1/16 byte of f16 block scales, the scales behind the quants in one allocation
+    Q3KvCache& c = t.cache; c.n_ctx = sh.n_ctx; c.n_slots = sh.n_slots;
+    c.layer_stride = (size_t)c.n_slots * t.Hkv * c.n_ctx * hd;
+    c.kv8 = sh.kv8 != 0;
+    if (c.kv8) {  // Q8_0 cache: per element one byte of quants + 1/16 byte of f16 block scales, the scales behind the quants in one allocation
         int8_t *kq = nullptr, *vq = nullptr;
-        const size_t nq = t.layer_stride * L;
+        const size_t nq = c.layer_stride * L;
         TRY(q3_dalloc(e, &kq, nq + nq / 16)); TRY(q3_dalloc(e, &vq, nq + nq / 16));
-        t.kc = (uint16_t*)kq; t.vc = (uint16_t*)vq; t.kd = (uint16_t*)(kq + nq); t.vd = (uint16_t*)(vq + nq);
+        c.kc = (uint16_t*)kq; c.vc = (uint16_t*)vq; c.kd = (uint16_t*)(kq + nq); c.vd = (uint16_t*)(vq + nq);
     } else {
-    TRY(q3_dalloc(e, &t.kc, t.layer_stride * L)); TRY(q3_dalloc(e, &t.vc, t.layer_stride * L));
+    TRY(q3_dalloc(e, &c.kc, c.layer_stride * L)); TRY(q3_dalloc(e, &c.vc, c.layer_stride * L));
     }
     std::vector<float> cs, sn;
-    q3_rope_tables(t.n_ctx, hd, sh.theta, sh.sections, cs, sn);
+    q3_rope_tables(c.n_ctx, hd, sh.theta, sh.sections, cs, sn);
     TRY(q3_dalloc(e, &t.cs, cs.size())); TRY(q3_dalloc(e, &t.sn, sn.size()));
     Q3_HIP(e, hipMemcpyAsync(t.cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, s));
     Q3_HIP(e, hipMemcpyAsync(t.sn, sn.data(), sn.size() * 4, hipMemcpyHostToDevice, s));
@@ -320,7 +321,7 @@ int q3_pred_table_init(q3tts_engine* e) {
     if (const char* ev = getenv("Q3TTS_PRED_TABLE")) if (!atoi(ev)) return Q3TTS_OK;
     if (P.a8 || nq < 1 || rows < 1) return Q3TTS_OK;
     {   // the gathering form exists for k_attend_small<2> only: a Predictor whose decode attention is another kernel keeps its launches
-        Q3Attend at{}; at.hd = P.hd; at.Hq = P.Hq; at.Hkv = P.Hkv; at.fused = 1; at.n_ctx = P.n_ctx;
+        Q3Attend at{}; at.hd = P.hd; at.Hq = P.Hq; at.Hkv = P.Hkv; at.fused = 1; at.n_ctx = P.cache.n_ctx;
         if (q3_attend_pick(at) != Q3_ATT_SMALL2 || (m.d_embed & 3) || (dp & 3)) return Q3TTS_OK;
     }
     long long max_mb = 1024;

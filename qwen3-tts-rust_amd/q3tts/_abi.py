@@ -189,6 +189,7 @@ SYMBOLS = [
     "q3tts_prefix_state", "q3tts_k_prefix_read",
     "q3tts_session_submit_paced", "q3tts_session_grant", "q3tts_session_set_swap", "q3tts_session_swap_stats",
     "q3tts_k_credit_ready", "q3tts_k_swap_arena", "q3tts_k_swap_phase_ms",
+    "q3tts_k_request_rules",
 ]
 
 
@@ -264,6 +265,7 @@ def load_library(path=None):
     lib.q3tts_session_set_swap.argtypes = [vp, C.c_int64]
     lib.q3tts_session_swap_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.q3tts_k_credit_ready.argtypes = [C.c_int64, C.c_int32]
+    lib.q3tts_k_request_rules.argtypes = [C.POINTER(Request), C.c_int32, C.c_int32, C.c_char_p, C.c_int32]
     lib.q3tts_k_swap_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
     lib.q3tts_k_swap_arena.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int64)]
     lib.q3tts_k_pcm_pack.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, C.POINTER(C.c_int64), C.c_int32, C.c_int32, vp,
