@@ -284,6 +284,42 @@ int q3tts_get_output_rate(const q3tts_engine* e, int32_t* rate);   /* 0 = off */
  * and kept on the engine (64 pairs at the most). The rates must differ. This is the clone path's entry for clips that are not 24 kHz. */
 int q3tts_resample(q3tts_engine* e, const float* in, int64_t n_in, int32_t rate_in, int32_t rate_out, float* out, int64_t cap, int64_t* n_out);
 
+/* ---- speaking rate and a one-shot time-stretch -----------------------------------------------------------------
+ * The model has no rate input. q3tts_set_speed(e, s) makes the engine stretch the vocoder's PCM on the device without moving its pitch,
+ * by WSOLA (waveform-similarity overlap-add) whose every f32 operation and order is fixed, so that everything below is reproducible bit
+ * for bit. s is the speed in per mille, 500 <= s <= 2000 (2000: twice as fast, half the samples); 0 or 1000 turns it off (the default):
+ * every launch, bit, allocation, event and scheduling decision is then what it is without this call.
+ * The arithmetic, at the vocoder's rate, all indices 64-bit: hop Hs = 256, window Wn = 512, offsets d in [-128, 127], HOLD = 640.
+ *   x[j]: the PCM row, 0 for j < 0 and for j >= n (its valid length; nothing at or past n is ever loaded).
+ *   a_k = (k Hs s) div 1000; p_{-1} = -Hs, p_0 = 0, p_k = a_k + d_k for k >= 1.
+ *   d_k: with the template t[j] = x[p_{k-1} + Hs + j] (the previous frame's natural continuation) and c(d) = sum_{j < Wn} x[a_k + d + j] t[j]
+ *     — one sequential f32 chain in ascending j, acc = acc + x * t with one rounded multiply and one rounded add per step, never
+ *     contracted — d_k is the FIRST maximum of c in ascending d. Non-finite PCM is not defined.
+ *   w[j] = 0.5 - 0.5 cos(2 pi j / Wn), computed in double and rounded once to f32.
+ *   y[m], k = m div Hs, j = m mod Hs: (w[j + Hs] * x[p_{k-1} + j + Hs]) + (w[j] * x[p_k + j]), two rounded multiplies and one rounded add.
+ *   A finished row of n samples gives N_t(n) = ceil(n 1000 / s) outputs, every frame k < ceil(N_t / Hs) decided with zeros behind n.
+ *   On an unfinished row frame k is decidable iff need_k + HOLD <= n, need_0 = 0, need_k = max(a_k, a_{k-1} + Hs): the rule knows no d, and
+ *   a decidable frame never reads at or beyond n. D_t(n) = Hs x (the number of leading decidable frames).
+ * What follows the speed:
+ *   - q3tts_generate / q3tts_generate_batch with want_pcm = 1, q3tts_stream_poll chunks (and q3tts_stream_end's PCM), session chunks in f32
+ *     and i16; result.n_samples = N_t(ns) for ns vocoder samples. sample_rate is untouched, first_chunk_ms keeps its meaning (the first
+ *     unstretched chunk resident on the host). The codes, n_frames and hit_eos are those of the unstretched run.
+ *   - a chunk that is not an utterance's last carries D_t(ns) minus what was delivered; the last one the rest. The chunks of an utterance
+ *     joined are its one-shot PCM bit for bit, whatever the batch, the slot, the schedule or the swap history. The added latency is HOLD
+ *     input samples (26.7 ms) plus at most one hop.
+ *   - with an output rate set as well, the resampler reads the stretched row (valid length N_t or D_t, the same finished flag):
+ *     the result is q3tts_resample(q3tts_time_stretch(native PCM)).
+ * Engine state like q3tts_set_output_rate: Q3TTS_ERR_STATE while a session or a stream is open and while q3tts_set_device_pcm is enabled
+ * (device-resident PCM, want_pcm = 2 and the node's gather stay unstretched; q3tts_set_device_pcm(e, 1) is refused while a speed is set);
+ * Q3TTS_ERR_INVALID outside 500..2000 and on an engine without a vocoder; Q3TTS_ERR_OOM, naming the bytes needed and the bytes free, when
+ * the stretched rows do not fit the device. A refused call leaves the state as it was. The speed is the engine's, not a request's.
+ * The constants are quality parameters that nobody has listened to yet. The reference has no counterpart. */
+int q3tts_set_speed(q3tts_engine* e, int32_t permille);
+int q3tts_get_speed(const q3tts_engine* e, int32_t* permille);   /* 0 = off */
+/* One-shot: the finished clip in[0, n_in) -> *n_out = ceil(n_in 1000 / permille) samples in out (cap samples; too small:
+ * Q3TTS_ERR_INVALID with *n_out set). Host buffers, the same kernel on the engine's device; permille in 500..2000 and not 1000. */
+int q3tts_time_stretch(q3tts_engine* e, const float* in, int64_t n_in, int32_t permille, float* out, int64_t cap, int64_t* n_out);
+
 /* ---- generation (run_inference_stream: src/tts/engine.rs:445-656) ------------------------------ */
 typedef struct q3tts_prefix q3tts_prefix;  /* a voice prefix: see "voice prefixes" below */
 typedef struct q3tts_request {
@@ -890,6 +926,15 @@ int q3tts_k_resample_table(int32_t rate_in, int32_t rate_out, int32_t* L, int32_
 int q3tts_k_pcm_resample(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* row_len, const int32_t* row_final,
                          const int32_t* ent_row, const int32_t* ent_first, const int32_t* ent_count, const int64_t* ent_dst, int32_t n_ent,
                          int32_t rate_in, int32_t rate_out, int32_t format, void* out, int64_t out_n, int32_t iters, float* mean_ms);
+/* N_t(n) and D_t(n) of the time-stretch at `permille` (500..2000), as the engine's host code computes them. Needs no GPU. */
+int q3tts_k_tempo_counts(int64_t n, int32_t permille, int64_t* N, int64_t* D);
+/* The time-stretch kernel through the engine's launcher: src [rows][stride] f32; step t of n_steps makes one launch (per 64 rows) with
+ * row r's valid length lens[t * rows + r] (ascending in t; what lies beyond is never loaded), finished in the last step where
+ * row_final[r]. out [n_steps][rows][out_stride] receives the whole output rows after every step (what no launch has written is NaN),
+ * n_valid [n_steps][rows] the outputs a row holds then (N_t or D_t), delta [rows][delta_stride] (delta_stride > 0) every decided frame's
+ * d_k. iters > 0 and mean_ms != NULL: the last step's launches are repeated iters times between two events and *mean_ms receives the mean. */
+int q3tts_k_pcm_tempo(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* lens, int32_t n_steps, const int32_t* row_final,
+                      int32_t permille, float* out, int64_t out_stride, int32_t* n_valid, int32_t* delta, int64_t delta_stride, int32_t iters, float* mean_ms);
 /* The row buckets of an engine with max_batch slots, ascending (a frame step runs on the smallest bucket that holds the live slots; one
  * captured graph per bucket): 1, 2, 4, 8, the multiples of 16 up to 64, above 64 the multiples of 32, last max_batch itself. Returns the
  * count (<= cap), Q3TTS_ERR_INVALID for max_batch outside 1..Q3TTS_MAX_BATCH or a cap too small. Needs no GPU. */
@@ -906,7 +951,7 @@ int q3tts_k_prefix_stats(const q3tts_engine* e, int64_t* out2);
 int q3tts_k_engine_footprint(const q3tts_engine_config* cfg, int64_t* bytes);
 /* Device bytes the engine's one allocator has handed out so far: everything that lives as long as the engine (weights, tables, caches,
  * rows, scratch, the vocoder's weights, work buffers and per-slot state). Not counted: what regrows on demand (device-resident PCM, the
- * resampler's staging, voice prefixes, a session's staging buffer) and the weight loaders' temporary staging. */
+ * resampler's staging, the time-stretch's rows, voice prefixes, a session's staging buffer) and the weight loaders' temporary staging. */
 int q3tts_k_device_bytes(const q3tts_engine* e, int64_t* bytes);
 /* rand 0.8 StdRng (ChaCha12) stream: seed_from_u64(seed) then n x gen::<f32>() */
 int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out);

@@ -154,6 +154,12 @@ struct q3tts_engine {
     // rs_stage [B][rs_stage_stride] f32: the resampled PCM of a slot on its way to the host (q3tts_generate_batch, streams)
     int out_rate = 0; Q3Resamp rs_out{}; std::vector<Q3Resamp> rs_cache;
     float* rs_stage = nullptr; size_t rs_stage_stride = 0, rs_stage_cap = 0;
+    // q3tts_set_speed (q3_tempo.hip): speed 0 = off (every launch and bit as without it), else per mille. tp_row
+    // [B][tp_stride] f32: the slots' stretched PCM, which every PCM exit then reads instead of the vocoder's rows (q3_pcm_rows). The rest is
+    // a memo of a pure function of a vocoder row's prefix: tp_done[b] frames of slot b are in its tempo row (host; 0 for a new occupant and
+    // after a swap-in, which rebuilds), tp_last[b] = p of the last of them (device). tp_win: the window (device).
+    int speed = 0; float* tp_row = nullptr; size_t tp_stride = 0, tp_cap = 0;
+    long long* tp_last = nullptr; float* tp_win = nullptr; std::vector<int> tp_done;
     double hp_launch = 0, hp_sync = 0;  // Q3TTS_HOST_PROF: host wall of run_chunk's launch part / of its wait (per engine: the node drives several from threads)
     float *park_logits = nullptr, *park_x = nullptr;  // [B][t_vocab], [B][t_d_model]: a parked slot's rows (q3_park_rows)
     float* first_chunk_host = nullptr;  // pinned landing buffer of the first 4-frame PCM chunk (first-chunk latency)
@@ -324,6 +330,20 @@ int q3_text_rows_set_group(q3tts_engine* e, const Q3TextSet* items, int count);
 // [first_out, first_out + count) of slot b's PCM row (n_valid samples so far) at e->out_rate into the start of the slot's row of e->rs_stage
 int q3_resample_get(q3tts_engine* e, int rate_in, int rate_out, Q3Resamp* out);
 int q3_resample_slot(q3tts_engine* e, int b, long long first_out, int count, int n_valid, bool is_final, hipStream_t s);
+// the slots' staging rows sized for rs over the rows the PCM exits read now (q3_pcm_rows_stride); regrows, never shrinks
+int q3_rs_stage_fit(q3tts_engine* e, const Q3Resamp& rs, size_t* stride);
+
+// the time-stretch's engine side (q3_tempo.hip). The rows every PCM exit reads: the vocoder's, or with a speed set the tempo rows
+inline const float* q3_pcm_rows(q3tts_engine* e) { return e->speed ? e->tp_row : q3_voc_pcm(e, 0); }
+inline size_t q3_pcm_rows_stride(const q3tts_engine* e) { return e->speed ? e->tp_stride : q3_voc_pcm_stride(e); }
+// what a PCM row of ns vocoder samples (done: all there are) holds for the exits: ns, or with a speed set N_t(ns) / D_t(ns)
+inline long long q3_pcm_valid(const q3tts_engine* e, long long ns, bool done) { return e->speed ? q3_tempo_valid(ns, e->speed, done) : ns; }
+// one launch (per 64 slots) on s that brings the listed slots' tempo rows up to what ns[i] vocoder samples (done[i]: all there are) decide
+int q3_tempo_slots(q3tts_engine* e, const int* slots, const int* ns, const char* done, int count, hipStream_t s);
+// slot b's memo is forgotten: a new occupant, or a swapped-in request whose tempo row is rebuilt from its PCM row (host state only)
+inline void q3_tempo_forget(q3tts_engine* e, int b) { if ((size_t)b < e->tp_done.size()) e->tp_done[b] = 0; }
+// the body of q3tts_time_stretch without the session check
+int q3_time_stretch_run(q3tts_engine* e, const float* in, int64_t n_in, int32_t permille, float* out, int64_t cap, int64_t* n_out);
 
 enum { BOS_TOKEN = 151672, EOS_TOKEN = 151673 };  // tts_bos, tts_eos (src/tts/prompt.rs); tts_pad is the model's tts_pad_id
 

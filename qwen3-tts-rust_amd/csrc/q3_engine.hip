@@ -369,6 +369,7 @@ extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
     for (void* p : e->allocs) hipFree(p);  // every q3_dalloc: weights, tables, caches, rows, scratch, decode and prefill state
     hipFree(e->dev_pcm);                   // regrows per batch: its own pair (q3tts_generate_batch)
     hipFree(e->rs_stage);                  // regrows with the output rate: its own pair (q3tts_set_output_rate)
+    hipFree(e->tp_row);                    // regrows with the speed: its own pair (q3tts_set_speed)
     if (e->slots_host) hipHostFree(e->slots_host);
     for (auto ev : e->fin_ev) if (ev) hipEventDestroy(ev);
     for (auto ev : e->probe_ev) if (ev) hipEventDestroy(ev);
@@ -465,6 +466,7 @@ extern "C" int q3tts_set_device_pcm(q3tts_engine* e, int32_t enable) {
     Q3_NOT_IN_SESSION(e);
     if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
     if (enable && e->out_rate) return q3_set_err(e, Q3TTS_ERR_STATE, "device-resident PCM is native-rate only (q3tts_set_output_rate(engine, 0) first)");
+    if (enable && e->speed) return q3_set_err(e, Q3TTS_ERR_STATE, "device-resident PCM is unstretched (q3tts_set_speed(engine, 0) first)");
     e->dev_pcm_on = enable ? 1 : 0;
     return Q3TTS_OK;
 }

@@ -184,7 +184,8 @@ int q3_retire_slot(q3tts_engine* e, int b, hipStream_t evs) {
 }
 int q3_emit_count(const q3tts_engine* e, int ns, bool done, long long delivered) {
     const Q3Resamp& r = e->rs_out;
-    return (int)((e->out_rate ? (done ? q3_resample_N(ns, r.L, r.M) : q3_resample_D(ns, r.L, r.M, r.H)) : ns) - delivered);
+    const long long nt = q3_pcm_valid(e, ns, done);  // with a speed set the resampler's row is the tempo row: N_t(ns) / D_t(ns) valid samples, the same `done`
+    return (int)((e->out_rate ? (done ? q3_resample_N(nt, r.L, r.M) : q3_resample_D(nt, r.L, r.M, r.H)) : nt) - delivered);
 }
 // Results of a finished slot. The codes come back on the decoder stream at once; the PCM (pinned host buffer) is copied
 // on the vocoder stream. With `defer` the call does not wait for the vocoder: the copy is enqueued behind the slot's last
@@ -206,6 +207,11 @@ static int finalize(q3tts_engine* e, int b, const q3tts_request* r, q3tts_result
     } else if (r->want_pcm && e->voc) {
         int ns = q3_voc_samples(e, b);
         const float* from = q3_voc_pcm(e, b);
+        if (e->speed) {  // the finished row stretched: N_t(ns) samples in the slot's tempo row
+            const char fin = 1;
+            TRY(q3_tempo_slots(e, &b, &ns, &fin, 1, e->vstream));
+            ns = (int)q3_tempo_N(ns, e->speed); from = e->tp_row + (size_t)b * e->tp_stride;
+        }
         if (e->out_rate) {  // the finished row at the output rate: N(ns) samples through the slot's staging row
             const int no = (int)q3_resample_N(ns, e->rs_out.L, e->rs_out.M);
             TRY(q3_resample_slot(e, b, 0, no, ns, true, e->vstream));
@@ -410,12 +416,17 @@ static int stream_emit(q3tts_stream* st, int before, int after, bool fin, const 
     q3tts_engine* e = st->e;
     hipStream_t s = e->stream;
     const float* from = q3_voc_pcm(e, 0) + before;
-    const int c = q3_emit_count(e, after, fin, e->out_rate ? st->delivered : before);
-    if (e->out_rate) {
-        TRY(q3_resample_slot(e, 0, st->delivered, c, after, fin, s));
-        from = e->rs_stage;
-        st->delivered += std::max(c, 0);
+    const int c = q3_emit_count(e, after, fin, e->out_rate || e->speed ? st->delivered : before);
+    if (e->speed) {  // the tempo row first: what `after` samples decide, on the stream the vocoder just ran on
+        const int b0 = 0; const char f = fin ? 1 : 0;
+        TRY(q3_tempo_slots(e, &b0, &after, &f, 1, s));
+        from = e->tp_row + st->delivered;
     }
+    if (e->out_rate) {
+        TRY(q3_resample_slot(e, 0, st->delivered, c, (int)q3_pcm_valid(e, after, fin), fin, s));
+        from = e->rs_stage;
+    }
+    if (e->out_rate || e->speed) st->delivered += std::max(c, 0);
     st->chunk.resize((size_t)std::max(1, c));
     if (c > 0) Q3_HIP(e, hipMemcpyAsync(st->chunk.data(), from, sizeof(float) * (size_t)c, hipMemcpyDeviceToHost, s));
     Q3_HIP(e, hipStreamSynchronize(s));
@@ -477,7 +488,7 @@ extern "C" int q3tts_stream_poll(q3tts_stream* st, const float** chunk, int32_t*
             const int before = q3_voc_samples(e, 0);
             if (e->cfg.vocoder_flush_tail) q3_voc_mark_last(e, 0);
             const int after = q3_voc_samples(e, 0);
-            if (after > before || (e->out_rate && q3_resample_N(after, e->rs_out.L, e->rs_out.M) > st->delivered))
+            if (after > before || ((e->out_rate || e->speed) && q3_emit_count(e, after, true, st->delivered) > 0))
                 TRY(stream_emit(st, before, after, true, chunk, n_samples));
             *is_final = 1; st->final_sent = true; return Q3TTS_OK;
         }

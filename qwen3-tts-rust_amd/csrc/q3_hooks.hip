@@ -1053,6 +1053,60 @@ extern "C" int q3tts_k_pcm_resample(int32_t device, const float* src, int32_t ro
     return out_n > 0 ? o.get(out, es * (size_t)out_n) : Q3TTS_OK;
 }
 
+extern "C" int q3tts_k_tempo_counts(int64_t n, int32_t permille, int64_t* N, int64_t* D) {
+    if (!N || !D || n < 0 || n > (1ll << 40) || permille < Q3_TEMPO_MIN || permille > Q3_TEMPO_MAX) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "tempo counts hook: bad arguments");
+    *N = q3_tempo_N(n, permille); *D = q3_tempo_valid(n, permille, false);
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_pcm_tempo(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* lens, int32_t n_steps, const int32_t* row_final,
+                                 int32_t permille, float* out, int64_t out_stride, int32_t* n_valid, int32_t* delta, int64_t delta_stride, int32_t iters, float* mean_ms) {
+    if (!src || !lens || !row_final || !out || !n_valid || rows <= 0 || rows > 4096 || stride <= 0 || stride > (1 << 28) || n_steps <= 0 || n_steps > 64 ||
+        permille < Q3_TEMPO_MIN || permille > Q3_TEMPO_MAX || out_stride <= 0 || delta_stride < 0 || (delta_stride > 0 && !delta))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm tempo hook: bad arguments");
+    for (int r = 0; r < rows; ++r)
+        for (int t = 0; t < n_steps; ++t) {
+            const long long n = lens[(size_t)t * rows + r];
+            if (n < 0 || n > stride || (t > 0 && n < lens[(size_t)(t - 1) * rows + r])) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm tempo hook: a row's valid lengths must ascend inside its row");
+            if (q3_tempo_valid(n, permille, t == n_steps - 1 && row_final[r]) > out_stride) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm tempo hook: out_stride is below a row's outputs");
+        }
+    HK(hipSetDevice(device));
+    std::vector<float> w;
+    q3_tempo_window(w);
+    DevBuf s, o, dw, pl, dd;
+    const size_t ob = sizeof(float) * (size_t)rows * out_stride;
+    TRY(s.put(src, sizeof(float) * (size_t)rows * stride)); TRY(o.alloc(ob)); TRY(dw.put(w.data(), sizeof(float) * w.size()));
+    TRY(pl.alloc(sizeof(long long) * rows)); TRY(dd.alloc(sizeof(int32_t) * (size_t)rows * std::max<int64_t>(delta_stride, 1)));
+    HK(hipMemset(o.p, 0xFF, ob));  // what no launch writes reads back as NaN
+    if (delta_stride > 0) HK(hipMemset(dd.p, 0x7F, sizeof(int32_t) * (size_t)rows * delta_stride));
+    std::vector<int> done(rows, 0);
+    std::vector<Q3TempoPack> last; std::vector<int> last_n;
+    for (int t = 0; t < n_steps; ++t) {
+        std::vector<Q3TempoPack> pks; std::vector<int> cnt;
+        for (int r = 0; r < rows; ++r) {
+            const int n = lens[(size_t)t * rows + r];
+            const bool fin = t == n_steps - 1 && row_final[r];
+            const long long kt = q3_tempo_frames(n, permille, fin), nv = q3_tempo_valid(n, permille, fin);
+            n_valid[(size_t)t * rows + r] = (int32_t)nv;
+            if (kt <= done[r]) continue;
+            if (pks.empty() || cnt.back() == Q3_PCM_MAX_ENT) { pks.push_back(Q3TempoPack{}); cnt.push_back(0); }
+            pks.back().e[cnt.back()++] = Q3TempoEnt{r, n, done[r], (int32_t)kt, (int32_t)nv, 0};
+            done[r] = (int)kt;
+        }
+        for (size_t g = 0; g < pks.size(); ++g)
+            q3_launch_pcm_tempo(s, (size_t)stride, o, (size_t)out_stride, pl, dw, permille, pks[g], cnt[g], delta_stride > 0 ? (int32_t*)dd : nullptr, (size_t)delta_stride, nullptr);
+        HK(hipGetLastError());
+        HK(hipDeviceSynchronize());
+        TRY(o.get(out + (size_t)t * rows * out_stride, ob));
+        last = pks; last_n = cnt;
+    }
+    if (delta_stride > 0) TRY(dd.get(delta, sizeof(int32_t) * (size_t)rows * delta_stride));
+    // (the timed launches repeat the last step's: its outputs were copied above)
+    return time_launches(iters, [&] {
+        for (size_t g = 0; g < last.size(); ++g) q3_launch_pcm_tempo(s, (size_t)stride, o, (size_t)out_stride, pl, dw, permille, last[g], last_n[g], nullptr, 0, nullptr);
+    }, mean_ms);
+}
+
 extern "C" int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out) {
     if (!out || n < 0) return Q3TTS_ERR_INVALID;
     q3_stdrng_f32(seed, n, out);

@@ -512,3 +512,25 @@ long long q3_resample_D(long long n, int L, int M, int H);
 // i16 as q3_launch_pcm_pack; -1 (nothing launched): one tile's input span does not fit the LDS
 int q3_launch_pcm_resample(const float* src, size_t stride, const Q3PcmPack& ents, const Q3PcmSrc& rows, int n_ent, int max_count, const Q3Resamp& rs,
                            int i16, void* dst, hipStream_t s);
+
+// PCM time-stretch (q3_tempo.hip): WSOLA at the vocoder's rate, pitch kept. Frame k of a row is Q3_TEMPO_HS outputs, read
+// from p_k = a_k + delta_k with a_k = (k Hs s) div 1000 (s: the speed in per mille) and delta_k the first maximum of the 256 correlations
+// with the previous frame's continuation. The constants are quality parameters nobody has listened to yet; they live here and nowhere else.
+#define Q3_TEMPO_HS 256                                           // synthesis hop = outputs per frame
+#define Q3_TEMPO_WN (2 * Q3_TEMPO_HS)                             // window, template and chain length
+#define Q3_TEMPO_DMIN (-128)                                      // candidates delta in [DMIN, DMIN + ND)
+#define Q3_TEMPO_ND 256                                           // = threads per workgroup: one chain per thread
+#define Q3_TEMPO_HOLD (Q3_TEMPO_DMIN + Q3_TEMPO_ND - 1 + Q3_TEMPO_WN + 1)  // 640: input samples behind need_k a frame waits for
+#define Q3_TEMPO_MIN 500
+#define Q3_TEMPO_MAX 2000
+// Entry j: frames [k_from, k_to) of src[row] (n valid samples: nothing at or past n is loaded, it counts as zeros) into dst[row]; outputs
+// m >= n_out are not written. p_last[row] holds p of frame k_from - 1 (read when k_from >= 2) and receives p of frame k_to - 1.
+struct Q3TempoEnt { int32_t row, n, k_from, k_to, n_out, pad; };
+struct Q3TempoPack { Q3TempoEnt e[Q3_PCM_MAX_ENT]; };
+long long q3_tempo_N(long long n, int permille);        // outputs of a finished row of n samples: ceil(n 1000 / s)
+long long q3_tempo_frames(long long n, int permille, bool done);  // frames decided: all ceil(N / Hs) of a finished row, else the leading decidable ones
+inline long long q3_tempo_valid(long long n, int permille, bool done) { return done ? q3_tempo_N(n, permille) : Q3_TEMPO_HS * q3_tempo_frames(n, permille, false); }
+void q3_tempo_window(std::vector<float>& w);            // the periodic Hann of Q3_TEMPO_WN points, double rounded once
+// win: the window on the device. delta != null: delta[row * delta_stride + k] = delta_k of every frame the launch decides (k < delta_stride)
+void q3_launch_pcm_tempo(const float* src, size_t stride, float* dst, size_t dst_stride, long long* p_last, const float* win, int permille,
+                         const Q3TempoPack& ents, int n_ent, int32_t* delta, size_t delta_stride, hipStream_t s);

@@ -174,9 +174,24 @@ int q3_resample_slot(q3tts_engine* e, int b, long long first_out, int count, int
     Q3PcmPack pk{}; Q3PcmSrc rows{};
     pk.e[0] = Q3PcmEnt{b, (int32_t)first_out, count, 0, (long long)((size_t)b * e->rs_stage_stride)};
     rows.len[0] = n_valid; rows.final_mask = is_final ? 1ull : 0ull;
-    if (q3_launch_pcm_resample(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, rows, 1, count, e->rs_out, 0, e->rs_stage, s) != 0)
+    if (q3_launch_pcm_resample(q3_pcm_rows(e), q3_pcm_rows_stride(e), pk, rows, 1, count, e->rs_out, 0, e->rs_stage, s) != 0)
         return q3_set_err(e, Q3TTS_ERR_UNSUPPORTED, "resample: the input span of one tile does not fit the LDS");
     Q3_HIP(e, hipGetLastError());
+    return Q3TTS_OK;
+}
+
+// the staging rows for rs over the rows the PCM exits read (the vocoder's, or the tempo rows when a speed is set)
+int q3_rs_stage_fit(q3tts_engine* e, const Q3Resamp& rs, size_t* stride_out) {
+    const size_t stride = ((size_t)q3_resample_N((long long)q3_pcm_rows_stride(e), rs.L, rs.M) + 3) & ~(size_t)3;
+    if (e->rs_stage_cap < stride * (size_t)e->B) {  // regrows with the rate: its own hipMalloc / hipFree pair
+        Q3_HIP(e, hipStreamSynchronize(e->vstream));
+        Q3_HIP(e, hipStreamSynchronize(e->stream));
+        if (e->rs_stage) { hipFree(e->rs_stage); e->rs_stage = nullptr; e->rs_stage_cap = 0; }
+        void* p = nullptr;
+        if (hipMalloc(&p, stride * (size_t)e->B * sizeof(float)) != hipSuccess) return q3_set_err(e, Q3TTS_ERR_OOM, "hipMalloc (resampler staging)");
+        e->rs_stage = (float*)p; e->rs_stage_cap = stride * (size_t)e->B;
+    }
+    *stride_out = stride;
     return Q3TTS_OK;
 }
 
@@ -192,15 +207,8 @@ extern "C" int q3tts_set_output_rate(q3tts_engine* e, int32_t rate) {
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     Q3Resamp rs{};
     TRY(q3_resample_get(e, native, rate, &rs));
-    const size_t stride = ((size_t)q3_resample_N((long long)q3_voc_pcm_stride(e), rs.L, rs.M) + 3) & ~(size_t)3;
-    if (e->rs_stage_cap < stride * (size_t)e->B) {  // regrows with the rate: its own hipMalloc / hipFree pair
-        Q3_HIP(e, hipStreamSynchronize(e->vstream));
-        Q3_HIP(e, hipStreamSynchronize(e->stream));
-        if (e->rs_stage) { hipFree(e->rs_stage); e->rs_stage = nullptr; e->rs_stage_cap = 0; }
-        void* p = nullptr;
-        if (hipMalloc(&p, stride * (size_t)e->B * sizeof(float)) != hipSuccess) return q3_set_err(e, Q3TTS_ERR_OOM, "hipMalloc (resampler staging)");
-        e->rs_stage = (float*)p; e->rs_stage_cap = stride * (size_t)e->B;
-    }
+    size_t stride = 0;
+    TRY(q3_rs_stage_fit(e, rs, &stride));
     e->rs_stage_stride = stride; e->rs_out = rs; e->out_rate = rate;
     return Q3TTS_OK;
 }

@@ -564,6 +564,7 @@ int swap_in(q3tts_session* s, Boundary& bd) {
         sl.rec.rng_base = b * e->cfg.max_steps_cap;
         s->voc_frames[b] = o.voc_frames;
         q3_voc_host_state(e, b, &o.frames_done, &o.last_flag, true);
+        q3_tempo_forget(e, b);  // (the tempo row is rebuilt from the PCM row the block carries: DESIGN.md §24)
         e->ts_slot[b] = sl.ts ? 1 : 0;
         bd.nf[b] = sl.rec.n_frames;
         if (b != o.from_slot) s->st_moved.fetch_add(1, std::memory_order_relaxed);
@@ -689,6 +690,12 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
     std::vector<Q3PcmEnt> ents; std::vector<int> ent_len; std::vector<char> ent_fin;
     size_t tot = 0;
     std::vector<SEv> chunks;
+    if (e->speed) {  // one tempo launch for all running slots in front of the gather: their tempo rows up to what their PCM decides by now
+        std::vector<int> tb, tn; std::vector<char> td;
+        for (int b = 0; b < e->B; ++b)
+            if (bd.run[b]) { tb.push_back(b); tn.push_back(q3_voc_samples(e, b)); td.push_back(e->slots_host[b].active ? 0 : 1); }
+        TRY(q3_tempo_slots(e, tb.data(), tn.data(), td.data(), (int)tb.size(), vs));
+    }
     for (int b = 0; b < e->B; ++b) {
         if (!bd.run[b]) continue;
         SSlot& sl = s->slots[b];
@@ -702,7 +709,7 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
             chunks.push_back(v);
         }
         if (c > 0) {
-            ent_len.push_back(ns); ent_fin.push_back(done ? 1 : 0);
+            ent_len.push_back((int)q3_pcm_valid(e, ns, done)); ent_fin.push_back(done ? 1 : 0);
             ents.push_back(Q3PcmEnt{b, sl.delivered, c, 0, (long long)tot});
             tot += (size_t)c; sl.delivered += c;
         }
@@ -720,8 +727,8 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
                 pk.e[i] = ents[g0 + i]; src.len[i] = ent_len[g0 + i]; mx = std::max(mx, ents[g0 + i].count);
                 if (ent_fin[g0 + i]) src.final_mask |= 1ull << i;
             }
-            if (!rs) q3_launch_pcm_pack(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, n, mx, s->fmt, s->dev, vs);
-            else if (q3_launch_pcm_resample(q3_voc_pcm(e, 0), q3_voc_pcm_stride(e), pk, src, n, mx, *rs, s->fmt, s->dev, vs) != 0)
+            if (!rs) q3_launch_pcm_pack(q3_pcm_rows(e), q3_pcm_rows_stride(e), pk, n, mx, s->fmt, s->dev, vs);
+            else if (q3_launch_pcm_resample(q3_pcm_rows(e), q3_pcm_rows_stride(e), pk, src, n, mx, *rs, s->fmt, s->dev, vs) != 0)
                 return q3_set_err(e, Q3TTS_ERR_UNSUPPORTED, "session: the resampler's input span does not fit the LDS");
         }
         Q3_HIP(e, hipGetLastError());
@@ -892,6 +899,10 @@ extern "C" int q3tts_session_create(q3tts_engine* e, int32_t pcm_format, q3tts_s
     std::unique_ptr<q3tts_session> s(new q3tts_session());
     s->e = e; s->fmt = pcm_format; s->es = pcm_format ? 2 : 4;
     s->ring_cap = (size_t)e->B * (4 + std::max(0, e->cfg.vocoder.lookahead_frames)) * q3_voc_samples_per_frame(e);
+    if (e->speed) {  // a boundary's window stretched (twice the samples at 500 per mille), plus the hold-back and the frames a final chunk releases
+        const size_t per = (size_t)q3_tempo_N((long long)(s->ring_cap / e->B) + Q3_TEMPO_HOLD + 2 * Q3_TEMPO_HS, e->speed) + 2 * Q3_TEMPO_HS;
+        s->ring_cap = std::max(s->ring_cap, (size_t)e->B * per);
+    }
     if (e->out_rate) {  // the larger of the two rates: a boundary's window at the output rate, plus the H input samples a final chunk releases
         const Q3Resamp& r = e->rs_out;
         const size_t per = (size_t)q3_resample_N((long long)(s->ring_cap / e->B) + r.H, r.L, r.M) + 2;

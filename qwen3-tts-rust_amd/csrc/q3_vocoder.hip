@@ -1583,6 +1583,7 @@ int q3_voc_reset(q3tts_engine* e, int slot) {
     }
     if (v->n_zero) hipLaunchKernelGGL(k_voc_zero, dim3(v->n_zero, 4), dim3(256), 0, e->stream, v->zero_tab, slot);
     v->frames_done[slot] = 0; v->last_flag[slot] = 0;
+    q3_tempo_forget(e, slot);  // (the memo of the previous occupant's PCM row: q3_tempo.hip)
     return Q3TTS_OK;
 }
 

@@ -190,6 +190,7 @@ SYMBOLS = [
     "q3tts_session_submit_paced", "q3tts_session_grant", "q3tts_session_set_swap", "q3tts_session_swap_stats",
     "q3tts_k_credit_ready", "q3tts_k_swap_arena", "q3tts_k_swap_phase_ms",
     "q3tts_k_request_rules",
+    "q3tts_set_speed", "q3tts_get_speed", "q3tts_time_stretch", "q3tts_k_tempo_counts", "q3tts_k_pcm_tempo",
 ]
 
 
@@ -276,6 +277,12 @@ def load_library(path=None):
     lib.q3tts_k_resample_table.argtypes = [C.c_int32, C.c_int32, i32p, i32p, i32p, f32p, C.c_int64, C.POINTER(C.c_int64)]
     lib.q3tts_k_pcm_resample.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, i32p, i32p, C.POINTER(C.c_int64), C.c_int32,
                                          C.c_int32, C.c_int32, C.c_int32, vp, C.c_int64, C.c_int32, f32p]
+    lib.q3tts_set_speed.argtypes = [vp, C.c_int32]
+    lib.q3tts_get_speed.argtypes = [vp, i32p]
+    lib.q3tts_time_stretch.argtypes = [vp, f32p, C.c_int64, C.c_int32, f32p, C.c_int64, C.POINTER(C.c_int64)]
+    lib.q3tts_k_tempo_counts.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.q3tts_k_pcm_tempo.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, C.c_int32, i32p, C.c_int32, f32p, C.c_int64, i32p, i32p, C.c_int64,
+                                      C.c_int32, f32p]
     lib.q3tts_stream_begin.argtypes = [vp, C.POINTER(Request), C.POINTER(vp)]
     lib.q3tts_stream_poll.argtypes = [vp, C.POINTER(f32p), i32p, i32p]
     lib.q3tts_stream_end.argtypes = [vp, C.POINTER(Result)]

@@ -216,6 +216,15 @@ class TtsEngine:
     def get_output_sample_rate(self) -> int:
         return self._native.get_output_rate() or self.cfg.vocoder.sample_rate
 
+    def set_speed(self, speed: float):
+        """Speaking rate of every AudioSample, stream chunk and session chunk from now on: 1.25 = a quarter faster, 0.5 .. 2.0, the pitch
+        kept (a time-stretch on the device); 1.0 (or 0) = off, the default. The engine keeps it in per mille. The reference
+        has no such control."""
+        self._native.set_speed(int(round(float(speed) * 1000.0)))
+
+    def get_speed(self) -> float:
+        return (self._native.get_speed() or 1000) / 1000.0
+
     def load_speakers(self, speakers_dir):  # src/tts/engine.rs:187-208 (files that fail to parse are skipped)
         for fn in sorted(os.listdir(speakers_dir)):
             if fn.endswith(".json"):

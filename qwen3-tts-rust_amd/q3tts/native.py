@@ -251,6 +251,26 @@ class NativeEngine:
         self._check(self.lib.q3tts_resample(self.h, _ptr(a, f32p), a.size, int(rate_in), int(rate_out), _ptr(out, f32p), cap, C.byref(n)), "q3tts_resample")
         return out[:n.value]
 
+    def set_speed(self, permille):
+        """q3tts_set_speed: PCM of generate / generate_batch (want_pcm = 1), of streams and of session chunks is time-stretched on the
+        device, pitch kept; `permille` in 500..2000 (2000: twice as fast), 0 or 1000 = off, the default. Refused while a
+        session or a stream is open and while device PCM is enabled. The reference has no such control."""
+        self._check(self.lib.q3tts_set_speed(self.h, int(permille)), "q3tts_set_speed")
+
+    def get_speed(self):
+        r = C.c_int32(0)
+        self._check(self.lib.q3tts_get_speed(self.h, C.byref(r)), "q3tts_get_speed")
+        return r.value
+
+    def time_stretch(self, audio, permille):
+        """q3tts_time_stretch: the finished f32 clip `audio` -> ceil(n 1000 / permille) samples, by the engine's device time-stretch."""
+        a = np.ascontiguousarray(audio, dtype=np.float32).reshape(-1)
+        cap = -(-a.size * 1000 // int(permille)) if int(permille) > 0 else 0
+        out = np.zeros(max(cap, 1), dtype=np.float32)
+        n = C.c_int64(0)
+        self._check(self.lib.q3tts_time_stretch(self.h, _ptr(a, f32p), a.size, int(permille), _ptr(out, f32p), cap, C.byref(n)), "q3tts_time_stretch")
+        return out[:n.value]
+
     def vocoder_bench(self, n_slots, chunks):
         ms = C.c_float(0)
         self._check(self.lib.q3tts_k_vocoder_bench(self.h, n_slots, chunks, C.byref(ms)), "q3tts_k_vocoder_bench")
@@ -1266,6 +1286,40 @@ def k_pcm_resample(src, row_len, row_final, entries, out_n, rate_in, rate_out, f
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_pcm_resample failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return (out[:int(out_n)], ms.value) if iters > 0 else out[:int(out_n)]
+
+
+def k_tempo_counts(n, permille):
+    """q3tts_k_tempo_counts (host only): (N_t(n), D_t(n)) of the time-stretch at `permille`."""
+    lib = _abi.load_library()
+    N, D = C.c_int64(), C.c_int64()
+    rc = lib.q3tts_k_tempo_counts(int(n), int(permille), C.byref(N), C.byref(D))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_tempo_counts failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return N.value, D.value
+
+
+def k_pcm_tempo(src, lens, row_final, permille, out_stride, delta_stride=0, device=0, iters=0):
+    """q3tts_k_pcm_tempo: src [rows][stride] f32; lens [n_steps][rows] valid lengths (one launch per step), row_final[r]: the last step
+    finishes row r. Returns (out [n_steps][rows][out_stride] f32 — the whole output rows after every step, NaN where nothing was written —,
+    n_valid [n_steps][rows], delta [rows][delta_stride] i32); with iters > 0 the last step's mean launch time in ms as a fourth."""
+    lib = _abi.load_library()
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    rows, stride = src.shape
+    ln = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1, rows)
+    rf = np.ascontiguousarray(row_final, dtype=np.int32)
+    if rf.shape != (rows,):
+        raise ValueError("k_pcm_tempo: row_final takes one value per row of src")
+    steps = ln.shape[0]
+    out = np.zeros((steps, rows, int(out_stride)), dtype=np.float32)
+    nv = np.zeros((steps, rows), dtype=np.int32)
+    dl = np.zeros((rows, max(int(delta_stride), 1)), dtype=np.int32)
+    ms = C.c_float(0)
+    rc = lib.q3tts_k_pcm_tempo(device, _ptr(src, f32p), rows, stride, _ptr(ln, i32p), steps, _ptr(rf, i32p), int(permille), _ptr(out, f32p),
+                               int(out_stride), _ptr(nv, i32p), _ptr(dl, i32p), int(delta_stride), int(iters), C.byref(ms))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_pcm_tempo failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    dl = dl[:, :int(delta_stride)]
+    return (out, nv, dl, ms.value) if iters > 0 else (out, nv, dl)
 
 
 def k_rng_f32(seed, n):

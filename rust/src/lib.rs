@@ -97,6 +97,9 @@ extern "C" {
     pub fn q3tts_session_grant(s: *mut q3tts_session, id: u64, frames: i32) -> c_int;
     pub fn q3tts_session_set_swap(s: *mut q3tts_session, arena_bytes: i64) -> c_int;
     pub fn q3tts_session_swap_stats(s: *const q3tts_session, out: *mut i64) -> c_int;
+    // speaking rate (no counterpart in the reference): engine state in per mille, 500..2000, 0 or 1000 = off; a pitch-preserving time-stretch on the device
+    pub fn q3tts_set_speed(e: *mut q3tts_engine, permille: i32) -> c_int;
+    pub fn q3tts_get_speed(e: *const q3tts_engine, permille: *mut i32) -> c_int;
     // one node, several GPUs (no counterpart in the reference: n_seq_max = 1, src/models/llama/mod.rs:413): one engine + host thread per device
     // inside the library, request i on device i % n_devices, optional RCCL gather of the i16 PCM to the first device
     pub fn q3tts_node_create(cfg: *const q3tts_engine_config, devices: *const i32, n_devices: i32, out: *mut *mut q3tts_node) -> c_int;
