@@ -956,6 +956,112 @@ int q3tts_k_device_bytes(const q3tts_engine* e, int64_t* bytes);
 /* rand 0.8 StdRng (ChaCha12) stream: seed_from_u64(seed) then n x gen::<f32>() */
 int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out);
 
+/* ---- long documents: split text, run the segments as one batch, join their PCM on the device --------------------
+ * A request carries one prompt and ends at max_steps (512 frames, 41 s: the reference's own cap, src/tts/engine.rs:152, where
+ * generate_with_voice truncates). A document is cut into segments, every segment runs as a request in one voice through the
+ * continuous batch, and a device stage trims, fades and lays the segments' PCM rows out as ONE row, so the audio crosses to the host
+ * once, with a table of where every segment landed. The reference has no counterpart. Off unless called: nothing else changes.
+ *
+ * 1. The splitter (host only: no engine, no GPU). Lengths are UTF-8 BYTES on purpose: a CJK character is 3 bytes and about 0.22 s of
+ *    speech, a Latin letter 1 byte and about 0.07 s, so bytes track duration across scripts; 240 bytes are about 17 s, well inside 512
+ *    frames. The defaults (target 120, max 240) are first choices that nobody has listened to. Rules, on code points:
+ *    - invalid UTF-8: Q3TTS_ERR_INVALID, the message holds the byte offset of the offending sequence. Limits: 16 <= target <= max <= 4096.
+ *    - whitespace: U+0020 \t \r \n U+00A0 U+3000. A paragraph break is a whitespace run holding two or more \n (one \n is plain
+ *      whitespace: hard-wrapped text does not split).
+ *    - terminators . ! ? U+2026 U+3002 U+FF01 U+FF1F; closers " ' ) ] } U+201D U+2019 U+300D U+300F U+FF09 U+3011 U+300B. A sentence
+ *      end is a maximal run of terminators plus the maximal run of closers behind it. A run of ASCII terminators only counts when
+ *      whitespace or the end of the text follows the closers (3.14 and a.b do not cut). A run that is one lone '.' does not count when
+ *      the maximal run of ASCII letters directly before it is a single letter (J. K., e.g.) or, case-insensitively, one of
+ *      mr mrs ms dr prof sr jr st vs.
+ *    - units: the text is cut after every sentence end (kind SENTENCE) and at every paragraph break (PARAGRAPH); each unit is trimmed of
+ *      whitespace; a unit without a \p{L} or \p{N} code point is dropped, and if it ended on a paragraph break that kind moves to the
+ *      previous kept unit.
+ *    - a unit longer than max_bytes is cut repeatedly, at the first of: after the last clause mark (, ; : followed by whitespace, or
+ *      U+FF0C U+3001 U+FF1B U+FF1A) whose end lies in (begin + max / 4, begin + max], kind CLAUSE; at the last whitespace code point that
+ *      starts in that range, kind HARD; at the largest code-point boundary <= begin + max, kind HARD. The pieces are trimmed and count as
+ *      units from here on; the last one keeps the unit's kind.
+ *    - packing: greedy, left to right, never across a PARAGRAPH end: the current span absorbs the next unit iff next.end - cur.begin <=
+ *      target_bytes. A span's kind is that of its last unit's end; the last span of the text has kind END.
+ *    *n_spans is set even when cap is too small (then Q3TTS_ERR_INVALID, as q3tts_tokenizer_encode). Text with nothing speakable gives
+ *    Q3TTS_OK and 0 spans. Errors go to err (always NUL-terminated when err_cap > 0; may be NULL). */
+#define Q3TTS_BREAK_END 0        /* last segment of the text */
+#define Q3TTS_BREAK_HARD 1       /* forced cut at whitespace or a code-point boundary */
+#define Q3TTS_BREAK_CLAUSE 2     /* forced cut after a clause mark */
+#define Q3TTS_BREAK_SENTENCE 3
+#define Q3TTS_BREAK_PARAGRAPH 4
+typedef struct q3tts_text_span { int64_t begin, end; int32_t kind; } q3tts_text_span;   /* byte range of the source */
+int q3tts_text_split(const char* utf8, int64_t n_bytes, int32_t target_bytes /*0: 120*/, int32_t max_bytes /*0: 240*/,
+                     q3tts_text_span* spans, int32_t cap, int32_t* n_spans, char* err, int32_t err_cap);
+
+/* 2. The join: its arithmetic. All at the vocoder's rate, indices 64-bit. A segment is a device row x_i[0, n_i) plus its break kind.
+ *    The block length is the constant W = 240 (10 ms). Every value of q3tts_join_opts and W are quality parameters nobody has heard yet.
+ *    - edges: block b covers [bW, min((b + 1)W, n_i)); it is loud iff some sample in it has fabsf(x) > threshold (strict; a NaN is not
+ *      loud). trim = 0: lo = 0, hi = n_i. trim = 1 with no loud block: lo = hi = 0, the segment is empty. trim = 1 otherwise, with the
+ *      first and last loud block: lo = max(0, first W - keep), hi = min(n_i, (last + 1) W + keep). The measure is a peak magnitude, not an
+ *      energy sum, on purpose: there is no summation order to pin.
+ *    - piece: L_i = hi - lo, F_i = min(fade, L_i div 2). Sample j of the piece is x_i[lo + j]; for j < F_i it is multiplied by g(j, F_i),
+ *      for j >= L_i - F_i by g(L_i - 1 - j, F_i), g(j, F) = (float)(j + 1) / (float)(F + 1), the correctly rounded f32 quotient. The gain
+ *      is one rounded f32 multiply; outside the fades the sample is copied bit for bit.
+ *    - layout: non-empty pieces in order; between consecutive non-empty pieces a < b lie pause_ms[k] * (rate / 1000) samples of +0.0f
+ *      (24 per ms), k the largest break kind of segments a .. b - 1, so a dropped piece cannot swallow a paragraph pause. N is the total;
+ *      nothing at or beyond N is written. An empty piece reports begin == end == the end of the last non-empty piece before it (0: none).
+ *    Q3TTS_ERR_INVALID for trim outside 0 / 1, a threshold that is negative or NaN, a negative keep or fade, a pause outside 0..60000 ms. */
+typedef struct q3tts_join_opts {
+    int32_t trim;          /* 1 */
+    float threshold;       /* 0.01f */
+    int32_t keep;          /* 480 samples */
+    int32_t fade;          /* 120 samples */
+    int32_t pause_ms[5];   /* by break kind: {0, 0, 150, 300, 600} */
+} q3tts_join_opts;
+
+/* 3. The entry points. q3tts_generate_long runs segment i as a request built from: a text-only desc over ids, the prefix, want_pcm = 2,
+ *    the template's sampler fields, min_frames and force_eos_at, its own max_steps (0: the template's), and seed_i = tmpl.seed + i
+ *    (mod 2^64) when has_seed. use_engine_sampler = 1 is resolved into explicit fields at entry, then the same seed rule applies. The
+ *    template's text_stream must be off and its prompt_embd, prompt and prefix NULL. Exactly one of voice (a voice-only desc, n_text == 0:
+ *    a prefix is created from it at entry and destroyed at return) and prefix (the caller's own) is given. opts == NULL: the defaults.
+ *    All segments go through q3tts_generate_batch's machinery with device PCM switched on for the call: the caller's
+ *    q3tts_set_device_pcm state is put back as it was, the device buffer's content is replaced as any call replaces it, the segments are
+ *    not copied to the host. There may be more segments than slots; n_segs <= 1024. Device memory: n_segs rows of max_steps_cap x samples
+ *    per frame x 4 B plus the document rows (the joined row of at most sum_i max_steps_i x samples per frame + the pauses; with a speed
+ *    its stretched row, with a rate its resampled row), checked against the device's free memory first: Q3TTS_ERR_OOM naming both numbers.
+ *    Then: the edges, the join, with speed_permille the time-stretch's launch over the document row, with output_rate the resampler's,
+ *    one device-to-host copy.
+ *    Contract: pcm == q3tts_resample(q3tts_time_stretch(J)) bit for bit, J the join (2.) of the PCM q3tts_generate_batch returns for
+ *    the same requests with want_pcm = 1 — by the prefix contract also the join of whole-prompt requests, independent of max_batch, of
+ *    slot assignment and of admission order.
+ *    Failures: a segment that fails by itself makes the call return that segment's status (the first such); info[i].status is filled for
+ *    every segment, pcm is NULL, everything stays freeable. Q3TTS_ERR_STATE while a session or a stream is open, and while an engine-level
+ *    speed or output rate is set (q3tts_set_speed / q3tts_set_output_rate are the engine's for plain requests; a document carries its own
+ *    in opts). Q3TTS_ERR_INVALID: no vocoder, n_segs outside 1..1024, a break kind outside 0..4, a speed or rate outside the ranges of the
+ *    two setters, join options outside theirs, a document of more than 2^28 samples. A refused call leaves every piece of engine state as
+ *    it was. q3tts_long_result_free releases pcm (pinned) and info. */
+typedef struct q3tts_long_segment { const uint32_t* ids; int32_t n_ids; int32_t kind; int32_t max_steps /*0: the template's*/; } q3tts_long_segment;
+typedef struct q3tts_long_opts { q3tts_join_opts join; int32_t speed_permille /*0 or 1000: off*/; int32_t output_rate /*0: native*/; } q3tts_long_opts;
+typedef struct q3tts_long_info {   /* one per segment */
+    int32_t status, n_frames, hit_eos; int64_t n_native, lo, hi;   /* the segment's own row and its kept range */
+    int64_t begin, end;           /* the piece in the joined 24 kHz timeline (begin == end: empty) */
+    int64_t out_begin, out_end;   /* the same through the speed and rate maps: ceil(s*1000/speed), then ceil(s*L/M) */
+} q3tts_long_info;
+typedef struct q3tts_long_result { int32_t status, n_segments, n_truncated /*hit_eos == 0*/, sample_rate; int64_t n_samples; float* pcm /*pinned*/;
+    q3tts_long_info* info; float generate_ms, join_ms, total_ms; } q3tts_long_result;
+void q3tts_long_default_opts(q3tts_long_opts*);
+int q3tts_generate_long(q3tts_engine* e, const q3tts_request* tmpl, const q3tts_prompt_desc* voice, const q3tts_prefix* prefix,
+                        const q3tts_long_segment* segs, int32_t n_segs, const q3tts_long_opts* opts, q3tts_long_result* out);
+void q3tts_long_result_free(q3tts_long_result*);
+/* one-shot join of finished host clips: uploads, the same two kernels, one copy back. n_clips in 1..1024; *n_out = N (cap too small:
+ * Q3TTS_ERR_INVALID with *n_out set). opts == NULL: the defaults. */
+int q3tts_pcm_join(q3tts_engine* e, const float* const* clips, const int64_t* n, const int32_t* kinds, int32_t n_clips,
+                   const q3tts_join_opts* opts, float* out, int64_t cap, int64_t* n_out, int64_t* edges /*[n_clips][4]: lo, hi, begin, end; may be NULL*/);
+/* Kernel hooks, one launch each through the engine's launcher. src [rows][stride] f32 is uploaded as it is (the tests put NaN behind every
+ * valid length lens[r]: nothing at or past it is loaded). q3tts_k_pcm_edges: edges[r] = {first, last} loud block of row r, {INT32_MAX, -1}
+ * when none is. q3tts_k_pcm_join: the plan (lo, hi, begin, end per row, and *N) from such edges, the kinds and opts at `rate` samples per
+ * second, then the launch into out [out_cap] (uploaded first, so what the launch does not write keeps its value) and the whole buffer back.
+ * iters > 0 and mean_ms != NULL: the launch is repeated iters times between two events and *mean_ms receives the mean. */
+int q3tts_k_pcm_edges(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* lens, float threshold, int32_t* edges,
+                      int32_t iters, float* mean_ms);
+int q3tts_k_pcm_join(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* lens, const int32_t* kinds, const int32_t* edges,
+                     const q3tts_join_opts* opts, int32_t rate, float* out, int64_t out_cap, int64_t* plan, int64_t* N, int32_t iters, float* mean_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -345,6 +345,22 @@ inline void q3_tempo_forget(q3tts_engine* e, int b) { if ((size_t)b < e->tp_done
 // the body of q3tts_time_stretch without the session check
 int q3_time_stretch_run(q3tts_engine* e, const float* in, int64_t n_in, int32_t permille, float* out, int64_t cap, int64_t* n_out);
 
+// the one-shots' launches over device rows (what q3tts_time_stretch / q3tts_resample run between their upload and their copy back):
+// dst[0, N_t(n_in)) from src[0, n_in) with the window and one long long of scratch on the device; dst[0, N(n_in)) at rs's output rate
+// (-1, nothing launched: one tile's input span does not fit the LDS)
+void q3_time_stretch_dev(const float* src, long long n_in, int permille, float* dst, const float* win, long long* p_last, hipStream_t s);
+int q3_resample_dev(const float* src, long long n_in, const Q3Resamp& rs, float* dst, hipStream_t s);
+
+// long documents (q3_long.hip). The plan is a pure function of the edges and the options (host): per row lo, hi, begin,
+// end (plan [rows][4]) and the join kernel's table (segs [rows], *max_span = the longest piece + gap); returns N
+long long q3_join_plan(const int32_t* lens, const int32_t* kinds, const int32_t* edges, int rows, const q3tts_join_opts& o, int rate,
+                       long long* plan, Q3JoinSeg* segs, long long* max_span);
+// Q3TTS_OK, or Q3TTS_ERR_INVALID with *msg naming the rule
+int q3_join_opts_rules(const q3tts_join_opts& o, const char** msg);
+// pinned host memory of a result's PCM (q3_generate.hip's pool): what q3tts_result_free gives back
+float* q3_pin_alloc(size_t bytes);
+void q3_pin_free(float* p);
+
 enum { BOS_TOKEN = 151672, EOS_TOKEN = 151673 };  // tts_bos, tts_eos (src/tts/prompt.rs); tts_pad is the model's tts_pad_id
 
 // the prompt builder (q3_engine.hip): the rows of `part` of p on the device at out; text_stream: the text part in the streamed layout

@@ -162,6 +162,8 @@ void pin_free(float* q) {
     hipHostFree(h);
 }
 }  // namespace
+float* q3_pin_alloc(size_t bytes) { return pin_alloc(bytes); }
+void q3_pin_free(float* p) { pin_free(p); }
 
 // the pieces of a chunk boundary that the three drivers share (q3_engine.h)
 int q3_codes_back(q3tts_engine* e, int b, q3tts_result* o) {

@@ -1107,6 +1107,63 @@ extern "C" int q3tts_k_pcm_tempo(int32_t device, const float* src, int32_t rows,
     }, mean_ms);
 }
 
+static int long_hook_rows(const char* what, const float* src, int32_t rows, int64_t stride, const int32_t* lens, long long* max_len) {
+    if (!src || !lens || rows <= 0 || rows > 4096 || stride <= 0 || stride > (1 << 28)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string(what) + ": bad arguments");
+    *max_len = 0;
+    for (int r = 0; r < rows; ++r) {
+        if (lens[r] < 0 || lens[r] > stride) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string(what) + ": a row's valid length lies outside its row");
+        *max_len = std::max<long long>(*max_len, lens[r]);
+    }
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_pcm_edges(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* lens, float threshold, int32_t* edges,
+                                 int32_t iters, float* mean_ms) {
+    long long mx = 0;
+    TRY(long_hook_rows("pcm edges hook", src, rows, stride, lens, &mx));
+    if (!edges || !(threshold >= 0.0f)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm edges hook: bad arguments");
+    HK(hipSetDevice(device));
+    std::vector<int32_t> init((size_t)2 * rows);
+    for (int r = 0; r < rows; ++r) { init[2 * r] = INT32_MAX; init[2 * r + 1] = -1; }
+    DevBuf s, l, ed;
+    TRY(s.put(src, sizeof(float) * (size_t)rows * stride)); TRY(l.put(lens, sizeof(int32_t) * rows)); TRY(ed.put(init.data(), sizeof(int32_t) * 2 * rows));
+    q3_launch_pcm_edges(s, (size_t)stride, l, rows, mx, threshold, ed, nullptr);
+    HK(hipGetLastError());
+    HK(hipDeviceSynchronize());
+    TRY(ed.get(edges, sizeof(int32_t) * 2 * rows));
+    return time_launches(iters, [&] { q3_launch_pcm_edges(s, (size_t)stride, l, rows, mx, threshold, ed, nullptr); }, mean_ms);
+}
+
+extern "C" int q3tts_k_pcm_join(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* lens, const int32_t* kinds, const int32_t* edges,
+                                const q3tts_join_opts* opts, int32_t rate, float* out, int64_t out_cap, int64_t* plan, int64_t* N, int32_t iters, float* mean_ms) {
+    long long mx = 0;
+    TRY(long_hook_rows("pcm join hook", src, rows, stride, lens, &mx));
+    if (!kinds || !edges || !opts || !out || !plan || !N || out_cap <= 0 || rate < 1000) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm join hook: bad arguments");
+    const char* msg = nullptr;
+    if (q3_join_opts_rules(*opts, &msg) != Q3TTS_OK) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, msg);
+    for (int r = 0; r < rows; ++r) {
+        if (kinds[r] < 0 || kinds[r] > 4) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm join hook: a break kind lies outside 0..4");
+        const long long nb = ((long long)lens[r] + Q3_JOIN_W - 1) / Q3_JOIN_W;
+        if (edges[2 * r + 1] >= 0 && (edges[2 * r] < 0 || edges[2 * r] > edges[2 * r + 1] || edges[2 * r + 1] >= nb))
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm join hook: a row's edges lie outside its blocks");
+    }
+    std::vector<Q3JoinSeg> segs((size_t)rows);
+    std::vector<long long> pl((size_t)4 * rows);
+    long long span = 0;
+    const long long n_doc = q3_join_plan(lens, kinds, edges, rows, *opts, rate, pl.data(), segs.data(), &span);
+    *N = n_doc;
+    for (size_t k = 0; k < pl.size(); ++k) plan[k] = pl[k];
+    if (n_doc > out_cap) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "pcm join hook: out holds fewer than N samples (*N says how many)");
+    HK(hipSetDevice(device));
+    DevBuf s, sg, o;
+    TRY(s.put(src, sizeof(float) * (size_t)rows * stride)); TRY(sg.put(segs.data(), sizeof(Q3JoinSeg) * rows)); TRY(o.put(out, sizeof(float) * (size_t)out_cap));
+    q3_launch_pcm_join(s, (size_t)stride, sg, rows, span, o, nullptr);
+    HK(hipGetLastError());
+    HK(hipDeviceSynchronize());
+    TRY(o.get(out, sizeof(float) * (size_t)out_cap));
+    return time_launches(iters, [&] { q3_launch_pcm_join(s, (size_t)stride, sg, rows, span, o, nullptr); }, mean_ms);
+}
+
 extern "C" int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out) {
     if (!out || n < 0) return Q3TTS_ERR_INVALID;
     q3_stdrng_f32(seed, n, out);

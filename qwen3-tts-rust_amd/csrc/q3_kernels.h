@@ -534,3 +534,14 @@ void q3_tempo_window(std::vector<float>& w);            // the periodic Hann of 
 // win: the window on the device. delta != null: delta[row * delta_stride + k] = delta_k of every frame the launch decides (k < delta_stride)
 void q3_launch_pcm_tempo(const float* src, size_t stride, float* dst, size_t dst_stride, long long* p_last, const float* win, int permille,
                          const Q3TempoPack& ents, int n_ent, int32_t* delta, size_t delta_stride, hipStream_t s);
+
+// Long documents (q3_long.hip): the two kernels that turn the segments' PCM rows into one document row.
+// k_pcm_edges: edges[2 r] / edges[2 r + 1] = the first / last block of Q3_JOIN_W samples of row r (lens[r] valid samples: nothing at or
+// past them is loaded) that holds a sample with fabsf(x) > threshold, by integer min / max; the caller fills edges with {INT32_MAX, -1}.
+// k_pcm_join: piece r is dst[off, off + L) = src[r][lo, lo + L) with fades of F samples at both ends, then `gap` samples of +0.0f.
+// The block length is a quality parameter nobody has listened to yet; it lives here and nowhere else.
+#define Q3_JOIN_W 240
+#define Q3_JOIN_MAX_SEG 1024
+struct Q3JoinSeg { long long lo, L, off, gap; int32_t F, pad; };
+void q3_launch_pcm_edges(const float* src, size_t stride, const int32_t* lens, int rows, long long max_len, float threshold, int32_t* edges, hipStream_t s);
+void q3_launch_pcm_join(const float* src, size_t stride, const Q3JoinSeg* segs, int rows, long long max_span, float* dst, hipStream_t s);

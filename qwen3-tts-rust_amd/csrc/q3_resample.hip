@@ -231,6 +231,13 @@ extern "C" int q3tts_resample(q3tts_engine* e, const float* in, int64_t n_in, in
     Q3_NOT_IN_SESSION(e);
     return q3_resample_run(e, in, n_in, rate_in, rate_out, out, cap, n_out);
 }
+int q3_resample_dev(const float* src, long long n_in, const Q3Resamp& rs, float* dst, hipStream_t s) {
+    const long long N = q3_resample_N(n_in, rs.L, rs.M);
+    Q3PcmPack pk{}; Q3PcmSrc rows{};
+    pk.e[0] = Q3PcmEnt{0, 0, (int32_t)N, 0, 0};
+    rows.len[0] = (int32_t)n_in; rows.final_mask = 1ull;
+    return q3_launch_pcm_resample(src, (size_t)n_in, pk, rows, 1, (int)N, rs, 0, dst, s);
+}
 int q3_resample_run(q3tts_engine* e, const float* in, int64_t n_in, int32_t rate_in, int32_t rate_out, float* out, int64_t cap, int64_t* n_out) {
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     Q3Resamp rs{};
@@ -246,10 +253,7 @@ int q3_resample_run(q3tts_engine* e, const float* in, int64_t n_in, int32_t rate
         return q3_set_err(e, Q3TTS_ERR_OOM, "hipMalloc (resample)");
     hipStream_t s = e->stream;
     Q3_HIP(e, hipMemcpyAsync(src.p, in, sizeof(float) * (size_t)n_in, hipMemcpyHostToDevice, s));
-    Q3PcmPack pk{}; Q3PcmSrc rows{};
-    pk.e[0] = Q3PcmEnt{0, 0, (int32_t)N, 0, 0};
-    rows.len[0] = (int32_t)n_in; rows.final_mask = 1ull;
-    if (q3_launch_pcm_resample((const float*)src.p, (size_t)n_in, pk, rows, 1, (int)N, rs, 0, dst.p, s) != 0)
+    if (q3_resample_dev((const float*)src.p, n_in, rs, (float*)dst.p, s) != 0)
         return q3_set_err(e, Q3TTS_ERR_UNSUPPORTED, "resample: the input span of one tile does not fit the LDS");
     Q3_HIP(e, hipGetLastError());
     Q3_HIP(e, hipMemcpyAsync(out, dst.p, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost, s));

@@ -226,6 +226,12 @@ extern "C" int q3tts_time_stretch(q3tts_engine* e, const float* in, int64_t n_in
     Q3_NOT_IN_SESSION(e);
     return q3_time_stretch_run(e, in, n_in, permille, out, cap, n_out);
 }
+void q3_time_stretch_dev(const float* src, long long n_in, int permille, float* dst, const float* win, long long* p_last, hipStream_t s) {
+    const long long N = q3_tempo_N(n_in, permille);
+    Q3TempoPack pk{};
+    pk.e[0] = Q3TempoEnt{0, (int32_t)n_in, 0, (int32_t)q3_tempo_frames(n_in, permille, true), (int32_t)N, 0};
+    q3_launch_pcm_tempo(src, (size_t)n_in, dst, (size_t)N, p_last, win, permille, pk, 1, nullptr, 0, s);
+}
 int q3_time_stretch_run(q3tts_engine* e, const float* in, int64_t n_in, int32_t permille, float* out, int64_t cap, int64_t* n_out) {
     if (permille < Q3_TEMPO_MIN || permille > Q3_TEMPO_MAX || permille == 1000) return q3_set_err(e, Q3TTS_ERR_INVALID, "time stretch: 500..2000 per mille, and not 1000");
     if (n_in > (1ll << 28)) return q3_set_err(e, Q3TTS_ERR_INVALID, "time stretch: more than 2^28 input samples");
@@ -243,9 +249,7 @@ int q3_time_stretch_run(q3tts_engine* e, const float* in, int64_t n_in, int32_t 
     hipStream_t s = e->stream;
     Q3_HIP(e, hipMemcpyAsync(src.p, in, sizeof(float) * (size_t)n_in, hipMemcpyHostToDevice, s));
     Q3_HIP(e, hipMemcpyAsync(win.p, w.data(), sizeof(float) * w.size(), hipMemcpyHostToDevice, s));
-    Q3TempoPack pk{};
-    pk.e[0] = Q3TempoEnt{0, (int32_t)n_in, 0, (int32_t)q3_tempo_frames(n_in, permille, true), (int32_t)N, 0};
-    q3_launch_pcm_tempo((const float*)src.p, (size_t)n_in, (float*)dst.p, (size_t)N, (long long*)pl.p, (const float*)win.p, permille, pk, 1, nullptr, 0, s);
+    q3_time_stretch_dev((const float*)src.p, n_in, permille, (float*)dst.p, (const float*)win.p, (long long*)pl.p, s);
     Q3_HIP(e, hipGetLastError());
     Q3_HIP(e, hipMemcpyAsync(out, dst.p, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost, s));
     Q3_HIP(e, hipStreamSynchronize(s));  // (w outlives the upload)

@@ -191,7 +191,46 @@ SYMBOLS = [
     "q3tts_k_credit_ready", "q3tts_k_swap_arena", "q3tts_k_swap_phase_ms",
     "q3tts_k_request_rules",
     "q3tts_set_speed", "q3tts_get_speed", "q3tts_time_stretch", "q3tts_k_tempo_counts", "q3tts_k_pcm_tempo",
+    "q3tts_text_split", "q3tts_long_default_opts", "q3tts_generate_long", "q3tts_long_result_free", "q3tts_pcm_join",
+    "q3tts_k_pcm_edges", "q3tts_k_pcm_join",
 ]
+
+# long documents (include/q3tts.h, "long documents"): break kinds, the join's block length, and the structs field for field
+BREAK_END, BREAK_HARD, BREAK_CLAUSE, BREAK_SENTENCE, BREAK_PARAGRAPH = 0, 1, 2, 3, 4
+JOIN_W = 240
+LONG_MAX_SEGMENTS = 1024
+
+
+class TextSpan(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("kind", C.c_int32)]
+
+
+class JoinOpts(C.Structure):
+    _fields_ = [("trim", C.c_int32), ("threshold", C.c_float), ("keep", C.c_int32), ("fade", C.c_int32), ("pause_ms", C.c_int32 * 5)]
+
+
+class LongSegment(C.Structure):
+    _fields_ = [("ids", C.POINTER(C.c_uint32)), ("n_ids", C.c_int32), ("kind", C.c_int32), ("max_steps", C.c_int32)]
+
+
+class LongOpts(C.Structure):
+    _fields_ = [("join", JoinOpts), ("speed_permille", C.c_int32), ("output_rate", C.c_int32)]
+
+
+class LongInfo(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("n_frames", C.c_int32), ("hit_eos", C.c_int32),
+        ("n_native", C.c_int64), ("lo", C.c_int64), ("hi", C.c_int64),
+        ("begin", C.c_int64), ("end", C.c_int64), ("out_begin", C.c_int64), ("out_end", C.c_int64),
+    ]
+
+
+class LongResult(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32), ("n_segments", C.c_int32), ("n_truncated", C.c_int32), ("sample_rate", C.c_int32),
+        ("n_samples", C.c_int64), ("pcm", C.POINTER(C.c_float)), ("info", C.POINTER(LongInfo)),
+        ("generate_ms", C.c_float), ("join_ms", C.c_float), ("total_ms", C.c_float),
+    ]
 
 
 class PredStep(C.Structure):
@@ -283,6 +322,18 @@ def load_library(path=None):
     lib.q3tts_k_tempo_counts.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.q3tts_k_pcm_tempo.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, C.c_int32, i32p, C.c_int32, f32p, C.c_int64, i32p, i32p, C.c_int64,
                                       C.c_int32, f32p]
+    i64p = C.POINTER(C.c_int64)
+    lib.q3tts_text_split.argtypes = [C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(TextSpan), C.c_int32, i32p, C.c_char_p, C.c_int32]
+    lib.q3tts_long_default_opts.argtypes = [C.POINTER(LongOpts)]
+    lib.q3tts_long_default_opts.restype = None
+    lib.q3tts_generate_long.argtypes = [vp, C.POINTER(Request), C.POINTER(PromptDesc), vp, C.POINTER(LongSegment), C.c_int32, C.POINTER(LongOpts),
+                                        C.POINTER(LongResult)]
+    lib.q3tts_long_result_free.argtypes = [C.POINTER(LongResult)]
+    lib.q3tts_long_result_free.restype = None
+    lib.q3tts_pcm_join.argtypes = [vp, C.POINTER(f32p), i64p, i32p, C.c_int32, C.POINTER(JoinOpts), f32p, C.c_int64, i64p, i64p]
+    lib.q3tts_k_pcm_edges.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, C.c_float, i32p, C.c_int32, f32p]
+    lib.q3tts_k_pcm_join.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, C.POINTER(JoinOpts), C.c_int32, f32p, C.c_int64, i64p, i64p,
+                                     C.c_int32, f32p]
     lib.q3tts_stream_begin.argtypes = [vp, C.POINTER(Request), C.POINTER(vp)]
     lib.q3tts_stream_poll.argtypes = [vp, C.POINTER(f32p), i32p, i32p]
     lib.q3tts_stream_end.argtypes = [vp, C.POINTER(Result)]

@@ -308,6 +308,45 @@ class TtsEngine:
                 raise _abi.Q3Error(f"generation failed with status {o.status}")
         return [AudioSample(o.pcm, o.sample_rate, 1) for o in outs]
 
+    def generate_long(self, text, voice: VoiceFile, instruct=None, *, prefix=None, seed=None, speed=None, sample_rate=None,
+                      target_bytes=0, max_bytes=0, **join_opts):
+        """A document of any length in one voice (an extension: the reference's generate_with_voice takes one text and truncates it at
+        max_steps). The text is split at paragraphs, sentences and, where a sentence is too long, clauses
+        (native.text_split); every span is encoded on its own and runs as a segment of one continuous batch behind a voice prefix; the
+        segments' PCM is trimmed, faded and joined with pauses on the device and crosses to the host once. Returns (AudioSample,
+        segments), segments a list of (text_slice, t_begin_s, t_end_s, hit_eos): where each piece of text landed in the audio (a segment
+        with hit_eos False ran into max_steps). speed / sample_rate default to the engine's set_speed / set_output_sample_rate values,
+        which are cleared around the call and restored. join_opts: trim, threshold, keep, fade, pause_ms (include/q3tts.h)."""
+        if not isinstance(text, str):
+            raise TypeError("generate_long takes the text as a str: it is split before it is encoded")
+        raw = text.encode("utf-8")
+        spans = native.text_split(raw, target_bytes, max_bytes)
+        if not spans:
+            raise ValueError("generate_long: the text holds nothing speakable")
+        pieces = [raw[b:e].decode("utf-8") for b, e, _ in spans]
+        segs = [(self._encode(p), k) for p, (_, _, k) in zip(pieces, spans)]
+        sc = self.sampler_config
+        if prefix is not None:
+            self._check_prefix(prefix, voice, instruct)
+            vdesc, keep = None, None
+        else:
+            vdesc, keep = self._desc(None, voice, instruct, part="voice")
+        eng_speed, eng_rate = self._native.get_speed(), self._native.get_output_rate()
+        permille = eng_speed if speed is None else int(round(float(speed) * 1000.0))
+        rate = eng_rate if sample_rate is None else int(sample_rate)
+        self._native.set_speed(0)
+        self._native.set_output_rate(0)
+        try:
+            out = self._native.generate_long(segs, voice=vdesc, prefix=prefix, speed_permille=permille, output_rate=rate, join=join_opts,
+                                             temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p,
+                                             seed=sc.seed if seed is None else seed, max_steps=self.max_steps)
+        finally:
+            self._native.set_output_rate(eng_rate)
+            self._native.set_speed(eng_speed)
+        r = float(out.sample_rate)
+        table = [(p, f["out_begin"] / r, f["out_end"] / r, bool(f["hit_eos"])) for p, f in zip(pieces, out.info)]
+        return AudioSample(out.pcm, out.sample_rate, 1), table
+
     def stream_batch_with_voice(self, texts, voices, instructs=None, seeds=None, *, prefix=None, realtime_lead_s=None):
         """The streaming twin of generate_batch_with_voice: every utterance runs through one session (continuous batching over the
         engine's slots) and its 4-frame chunks are yielded as they are produced, as (index, f32 chunk, is_final); chunks of different

@@ -271,6 +271,63 @@ class NativeEngine:
         self._check(self.lib.q3tts_time_stretch(self.h, _ptr(a, f32p), a.size, int(permille), _ptr(out, f32p), cap, C.byref(n)), "q3tts_time_stretch")
         return out[:n.value]
 
+    def pcm_join(self, clips, kinds, **opts):
+        """q3tts_pcm_join: finished host clips and their break kinds (_abi.BREAK_*) -> (the joined f32 PCM, edges [n][4] = lo, hi, begin,
+        end), trimmed, faded and laid out by the two device kernels of DESIGN.md §26; opts: the fields of q3tts_join_opts."""
+        arrs = [np.ascontiguousarray(c, dtype=np.float32).reshape(-1) for c in clips]
+        n = len(arrs)
+        ptrs = (f32p * max(n, 1))(*[_ptr(a, f32p) for a in arrs])
+        lens = np.array([a.size for a in arrs], dtype=np.int64)
+        kd = np.ascontiguousarray(kinds, dtype=np.int32)
+        if kd.shape != (n,):
+            raise ValueError("pcm_join: kinds takes one value per clip")
+        o = join_opts(**opts)
+        cap = int(lens.sum()) + max(n - 1, 0) * max(o.pause_ms) * (self.cfg.vocoder.sample_rate // 1000 + 1)
+        out = np.zeros(max(cap, 1), dtype=np.float32)
+        edges = np.zeros((max(n, 1), 4), dtype=np.int64)
+        n_out = C.c_int64(0)
+        i64p = C.POINTER(C.c_int64)
+        self._check(self.lib.q3tts_pcm_join(self.h, ptrs, _ptr(lens, i64p), _ptr(kd, i32p), n, C.byref(o), _ptr(out, f32p), cap, C.byref(n_out),
+                                            _ptr(edges, i64p)), "q3tts_pcm_join")
+        return out[:n_out.value], edges[:n]
+
+    def generate_long(self, segments, voice=None, prefix=None, speed_permille=0, output_rate=0, join=None, **template_kw):
+        """q3tts_generate_long: `segments` is a list of (ids, kind) or (ids, kind, max_steps); exactly one of voice (a voice-only desc) and
+        prefix (a NativePrefix); template_kw are make_request's sampler fields, min_frames, force_eos_at and max_steps; join: a dict of
+        q3tts_join_opts fields. Returns a GenResult-like object: pcm, n_samples, sample_rate, n_truncated, generate_ms / join_ms / total_ms
+        and info, one dict per segment (status, n_frames, hit_eos, n_native, lo, hi, begin, end, out_begin, out_end). A segment that fails
+        by itself raises Q3Error; the error's `info` attribute then holds the per-segment statuses."""
+        tmpl, keep = self.make_request(**template_kw)
+        n = len(segments)
+        segs = (_abi.LongSegment * max(n, 1))()
+        for i, sg in enumerate(segments):
+            ids = np.ascontiguousarray(sg[0], dtype=np.uint32)
+            keep.append(ids)
+            segs[i].ids, segs[i].n_ids, segs[i].kind = _ptr(ids, u32p), ids.size, int(sg[1])
+            segs[i].max_steps = int(sg[2]) if len(sg) > 2 else 0
+        o = _abi.LongOpts()
+        o.join = join_opts(**(join or {}))
+        o.speed_permille, o.output_rate = int(speed_permille), int(output_rate)
+        if prefix is not None and not prefix.h:
+            raise _abi.Q3Error("the prefix is closed")
+        res = _abi.LongResult()
+        rc = self.lib.q3tts_generate_long(self.h, C.byref(tmpl), C.byref(voice) if voice is not None else None,
+                                          prefix.h if prefix is not None else None, segs, n, C.byref(o), C.byref(res))
+        names = [f[0] for f in _abi.LongInfo._fields_]
+        info = [{k: int(getattr(res.info[i], k)) for k in names} for i in range(res.n_segments)] if res.info else []
+        try:
+            if rc != 0:
+                err = _abi.Q3Error(f"q3tts_generate_long failed ({rc}): {self.lib.q3tts_last_error(self.h).decode()}")
+                err.status, err.info, err.pcm_is_null = rc, info, not bool(res.pcm)
+                raise err
+            pcm = np.ctypeslib.as_array(res.pcm, shape=(res.n_samples,)).copy() if res.n_samples > 0 else np.zeros(0, dtype=np.float32)
+            out = GenResult(res.status, np.zeros((0, self.cfg.model.n_codebooks), dtype=np.int32), pcm, res.n_truncated == 0, 0.0, res.total_ms, res.sample_rate)
+            out.n_samples, out.n_truncated, out.info = int(res.n_samples), int(res.n_truncated), info
+            out.generate_ms, out.join_ms = float(res.generate_ms), float(res.join_ms)
+            return out
+        finally:
+            self.lib.q3tts_long_result_free(C.byref(res))
+
     def vocoder_bench(self, n_slots, chunks):
         ms = C.c_float(0)
         self._check(self.lib.q3tts_k_vocoder_bench(self.h, n_slots, chunks, C.byref(ms)), "q3tts_k_vocoder_bench")
@@ -1320,6 +1377,79 @@ def k_pcm_tempo(src, lens, row_final, permille, out_stride, delta_stride=0, devi
         raise _abi.Q3Error(f"q3tts_k_pcm_tempo failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     dl = dl[:, :int(delta_stride)]
     return (out, nv, dl, ms.value) if iters > 0 else (out, nv, dl)
+
+
+def text_split(text, target_bytes=0, max_bytes=0):
+    """q3tts_text_split (host only): UTF-8 text (str or bytes) -> [(begin, end, kind)], byte ranges of the source with their break kind
+    (_abi.BREAK_*); 0 selects the defaults (120 / 240 bytes)."""
+    lib = _abi.load_library()
+    raw = text.encode("utf-8") if isinstance(text, str) else bytes(text)
+    cap = 16
+    err = C.create_string_buffer(256)
+    while True:
+        spans = (_abi.TextSpan * cap)()
+        n = C.c_int32(0)
+        rc = lib.q3tts_text_split(raw, len(raw), int(target_bytes), int(max_bytes), spans, cap, C.byref(n), err, len(err))
+        if rc != 0 and n.value > cap:  # *n_spans carries the size needed
+            cap = n.value
+            continue
+        if rc != 0:
+            raise _abi.Q3Error(f"q3tts_text_split failed ({rc}): {err.value.decode('utf-8', 'replace')}")
+        return [(int(spans[i].begin), int(spans[i].end), int(spans[i].kind)) for i in range(n.value)]
+
+
+def join_opts(trim=1, threshold=0.01, keep=480, fade=120, pause_ms=(0, 0, 150, 300, 600)):
+    """A q3tts_join_opts with the header's defaults."""
+    o = _abi.JoinOpts()
+    o.trim, o.threshold, o.keep, o.fade = int(trim), float(threshold), int(keep), int(fade)
+    o.pause_ms[:] = [int(p) for p in pause_ms]
+    return o
+
+
+def pcm_join(engine: "NativeEngine", clips, kinds, **opts):
+    """q3tts_pcm_join: finished host clips and their break kinds -> (the joined f32 PCM, edges [n][4] = lo, hi, begin, end)."""
+    return engine.pcm_join(clips, kinds, **opts)
+
+
+def _long_rows(src, lens):
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    ln = np.ascontiguousarray(lens, dtype=np.int32)
+    if src.ndim != 2 or ln.shape != (src.shape[0],):
+        raise ValueError("src is [rows][stride] and lens takes one value per row")
+    return src, ln
+
+
+def k_pcm_edges(src, lens, threshold, device=0, iters=0):
+    """q3tts_k_pcm_edges: src [rows][stride] f32 with lens[r] valid samples -> edges [rows][2] = the first and last loud block of 240
+    samples (INT32_MAX, -1 when none is); with iters > 0 the mean launch time in ms as a second."""
+    lib = _abi.load_library()
+    src, ln = _long_rows(src, lens)
+    ed = np.zeros((src.shape[0], 2), dtype=np.int32)
+    ms = C.c_float(0)
+    rc = lib.q3tts_k_pcm_edges(device, _ptr(src, f32p), src.shape[0], src.shape[1], _ptr(ln, i32p), float(threshold), _ptr(ed, i32p), int(iters), C.byref(ms))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_pcm_edges failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return (ed, ms.value) if iters > 0 else ed
+
+
+def k_pcm_join(src, lens, kinds, edges, out_cap, rate=24000, device=0, iters=0, **opts):
+    """q3tts_k_pcm_join: the plan from `edges` (as k_pcm_edges gives them), the kinds and the join options, then one launch. Returns (out
+    [out_cap] f32, NaN where the launch wrote nothing, plan [rows][4] = lo, hi, begin, end, N); with iters > 0 the mean launch time too."""
+    lib = _abi.load_library()
+    src, ln = _long_rows(src, lens)
+    kd = np.ascontiguousarray(kinds, dtype=np.int32)
+    ed = np.ascontiguousarray(edges, dtype=np.int32)
+    if kd.shape != ln.shape or ed.shape != (ln.size, 2):
+        raise ValueError("k_pcm_join: kinds takes one value per row and edges two")
+    o = join_opts(**opts)
+    out = np.full(int(out_cap), np.nan, dtype=np.float32)
+    plan = np.zeros((ln.size, 4), dtype=np.int64)
+    N, ms = C.c_int64(0), C.c_float(0)
+    rc = lib.q3tts_k_pcm_join(device, _ptr(src, f32p), src.shape[0], src.shape[1], _ptr(ln, i32p), _ptr(kd, i32p), _ptr(ed, i32p), C.byref(o), int(rate),
+                              _ptr(out, f32p), out.size, _ptr(plan, C.POINTER(C.c_int64)), C.byref(N), int(iters), C.byref(ms))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_pcm_join failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return (out, plan, N.value, ms.value) if iters > 0 else (out, plan, N.value)
 
 
 def k_rng_f32(seed, n):

@@ -62,8 +62,43 @@ pub enum q3tts_session {}
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct q3tts_node_timings { pub generate_ms: c_float, pub gather_ms: c_float, pub total_ms: c_float, pub gathered_bytes: i64, pub n_devices: i32 }
 
+// long documents (include/q3tts.h, "long documents"): the splitter's spans, the join's options, a document's segments and its result
+pub const Q3TTS_BREAK_END: i32 = 0;
+pub const Q3TTS_BREAK_HARD: i32 = 1;
+pub const Q3TTS_BREAK_CLAUSE: i32 = 2;
+pub const Q3TTS_BREAK_SENTENCE: i32 = 3;
+pub const Q3TTS_BREAK_PARAGRAPH: i32 = 4;
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct q3tts_text_span { pub begin: i64, pub end: i64, pub kind: i32 }
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct q3tts_join_opts { pub trim: i32, pub threshold: c_float, pub keep: i32, pub fade: i32, pub pause_ms: [i32; 5] }
+#[repr(C)]
+pub struct q3tts_long_segment { pub ids: *const u32, pub n_ids: i32, pub kind: i32, pub max_steps: i32 }
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct q3tts_long_opts { pub join: q3tts_join_opts, pub speed_permille: i32, pub output_rate: i32 }
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct q3tts_long_info {
+    pub status: i32, pub n_frames: i32, pub hit_eos: i32, pub n_native: i64, pub lo: i64, pub hi: i64,
+    pub begin: i64, pub end: i64, pub out_begin: i64, pub out_end: i64,
+}
+#[repr(C)]
+pub struct q3tts_long_result {
+    pub status: i32, pub n_segments: i32, pub n_truncated: i32, pub sample_rate: i32, pub n_samples: i64, pub pcm: *mut c_float,
+    pub info: *mut q3tts_long_info, pub generate_ms: c_float, pub join_ms: c_float, pub total_ms: c_float,
+}
+
 #[link(name = "q3tts")]
 extern "C" {
+    // long documents (no counterpart in the reference, whose generate_with_voice truncates one text at 512 steps): split on the host,
+    // the segments as one batch behind a voice prefix, their PCM trimmed, faded and joined on the device, one copy to the host
+    pub fn q3tts_text_split(utf8: *const c_char, n_bytes: i64, target_bytes: i32, max_bytes: i32, spans: *mut q3tts_text_span, cap: i32,
+                            n_spans: *mut i32, err: *mut c_char, err_cap: i32) -> c_int;
+    pub fn q3tts_long_default_opts(o: *mut q3tts_long_opts);
+    pub fn q3tts_generate_long(e: *mut q3tts_engine, tmpl: *const q3tts_request, voice: *const q3tts_prompt_desc, prefix: *const q3tts_prefix,
+                               segs: *const q3tts_long_segment, n_segs: i32, opts: *const q3tts_long_opts, out: *mut q3tts_long_result) -> c_int;
+    pub fn q3tts_long_result_free(r: *mut q3tts_long_result);
+    pub fn q3tts_pcm_join(e: *mut q3tts_engine, clips: *const *const c_float, n: *const i64, kinds: *const i32, n_clips: i32,
+                          opts: *const q3tts_join_opts, out: *mut c_float, cap: i64, n_out: *mut i64, edges: *mut i64) -> c_int;
     pub fn q3tts_default_config(cfg: *mut q3tts_engine_config);
     // every model dimension and weights_path from the files of model_dir's quant directory (host only); errors go to err, cfg is then unchanged
     pub fn q3tts_config_from_model_dir(model_dir: *const c_char, quant: *const c_char, cfg: *mut q3tts_engine_config, path_buf: *mut c_char, path_cap: i32,
@@ -100,6 +135,9 @@ extern "C" {
     // speaking rate (no counterpart in the reference): engine state in per mille, 500..2000, 0 or 1000 = off; a pitch-preserving time-stretch on the device
     pub fn q3tts_set_speed(e: *mut q3tts_engine, permille: i32) -> c_int;
     pub fn q3tts_get_speed(e: *const q3tts_engine, permille: *mut i32) -> c_int;
+    // output sample rate (no counterpart in the reference, which emits 24 kHz only): engine state, 4000..96000 Hz, 0 or 24000 = off
+    pub fn q3tts_set_output_rate(e: *mut q3tts_engine, rate: i32) -> c_int;
+    pub fn q3tts_get_output_rate(e: *const q3tts_engine, rate: *mut i32) -> c_int;
     // one node, several GPUs (no counterpart in the reference: n_seq_max = 1, src/models/llama/mod.rs:413): one engine + host thread per device
     // inside the library, request i on device i % n_devices, optional RCCL gather of the i16 PCM to the first device
     pub fn q3tts_node_create(cfg: *const q3tts_engine_config, devices: *const i32, n_devices: i32, out: *mut *mut q3tts_node) -> c_int;
@@ -215,6 +253,76 @@ impl TtsEngine {
             let samples = std::slice::from_raw_parts(out.pcm, out.n_samples as usize).to_vec();
             q3tts_result_free(&mut out);
             Ok(AudioSample { samples, sample_rate: 24000, channels: 1 })
+        }
+    }
+}
+/// One segment of a document: its text, where it lies in the audio (seconds) and whether it ended by EOS (false: it ran into max_steps).
+pub struct LongSegment { pub text: String, pub t_begin_s: f64, pub t_end_s: f64, pub hit_eos: bool }
+
+impl TtsEngine {
+    /// A document of any length in one voice (no counterpart in the reference; include/q3tts.h, "long documents"): the text is split by
+    /// q3tts_text_split, every span is encoded on its own by `encode` (the tokenizer stays in Rust) and runs as a segment of one batch behind
+    /// a prefix made from the voice; the segments' PCM is trimmed, faded and joined on the device and copied to the host once.
+    /// `speed`: Some(1.25) = a quarter faster, the pitch kept; `sample_rate`: Some(16000), ...; None = off / the vocoder's 24 kHz.
+    pub fn generate_long(&mut self, text: &str, voice: &VoiceFile, instruct_ids: Option<&[u32]>, encode: &dyn Fn(&str) -> Vec<u32>,
+                         speed: Option<f32>, sample_rate: Option<u32>) -> Result<(AudioSample, Vec<LongSegment>), String> {
+        let mut err: Vec<c_char> = vec![0; 256];
+        let mut spans = vec![q3tts_text_span::default(); 64];
+        let mut n = 0i32;
+        unsafe {
+            let mut rc = q3tts_text_split(text.as_ptr() as *const c_char, text.len() as i64, 0, 0, spans.as_mut_ptr(), spans.len() as i32, &mut n,
+                                          err.as_mut_ptr(), err.len() as i32);
+            if rc != 0 && n as usize > spans.len() {   // *n_spans carries the size needed
+                spans.resize(n as usize, q3tts_text_span::default());
+                rc = q3tts_text_split(text.as_ptr() as *const c_char, text.len() as i64, 0, 0, spans.as_mut_ptr(), spans.len() as i32, &mut n,
+                                      err.as_mut_ptr(), err.len() as i32);
+            }
+            if rc != 0 { return Err(format!("q3tts_text_split failed ({}): {}", rc, CStr::from_ptr(err.as_ptr()).to_string_lossy())); }
+        }
+        spans.truncate(n as usize);
+        if spans.is_empty() { return Err("generate_long: the text holds nothing speakable".into()); }
+        let pieces: Vec<&str> = spans.iter().map(|s| &text[s.begin as usize..s.end as usize]).collect();
+        let ids: Vec<Vec<u32>> = pieces.iter().map(|p| encode(p)).collect();
+        let segs: Vec<q3tts_long_segment> = ids.iter().zip(spans.iter())
+            .map(|(v, s)| q3tts_long_segment { ids: v.as_ptr(), n_ids: v.len() as i32, kind: s.kind, max_steps: 0 }).collect();
+        let codes32: Vec<i32> = voice.audio_codes.iter().map(|&c| c as i32).collect();
+        let vdesc = q3tts_prompt_desc {
+            text_ids: std::ptr::null(), n_text: 0,
+            instruct_ids: instruct_ids.map_or(std::ptr::null(), |s| s.as_ptr()), n_instruct: instruct_ids.map_or(0, |s| s.len() as i32),
+            lang_id: 2055, spk_id: -1, spk_emb: voice.speaker_embedding.as_ptr(),
+            ref_codes: if codes32.is_empty() { std::ptr::null() } else { codes32.as_ptr() }, n_ref_frames: (codes32.len() / 16) as i32,
+            ref_text_ids: std::ptr::null(), n_ref_text: 0,
+        };
+        let tmpl = q3tts_request {
+            prompt_embd: std::ptr::null(), n_tok: 0, prompt: std::ptr::null(), use_engine_sampler: 0,
+            temperature: self.sampler.temperature, top_k: self.sampler.top_k, top_p: self.sampler.top_p,
+            has_seed: self.sampler.seed.is_some() as i32, seed: self.sampler.seed.unwrap_or(0),
+            max_steps: self.max_steps as i32, min_frames: 0, force_eos_at: -1, want_pcm: 0, prefix: std::ptr::null(), text_stream: 0, text_open: 0,
+        };
+        unsafe {
+            let (mut eng_speed, mut eng_rate) = (0i32, 0i32);   // the engine's own speed and rate are for plain requests: cleared around the call
+            q3tts_get_speed(self.raw, &mut eng_speed);
+            q3tts_get_output_rate(self.raw, &mut eng_rate);
+            let mut opts: q3tts_long_opts = std::mem::zeroed();
+            q3tts_long_default_opts(&mut opts);
+            opts.speed_permille = speed.map_or(eng_speed, |s| (s * 1000.0).round() as i32);
+            opts.output_rate = sample_rate.map_or(eng_rate, |r| r as i32);
+            q3tts_set_speed(self.raw, 0);
+            q3tts_set_output_rate(self.raw, 0);
+            let mut out: q3tts_long_result = std::mem::zeroed();
+            let rc = q3tts_generate_long(self.raw, &tmpl, &vdesc, std::ptr::null(), segs.as_ptr(), segs.len() as i32, &opts, &mut out);
+            let msg = if rc != 0 { CStr::from_ptr(q3tts_last_error(self.raw)).to_string_lossy().into_owned() } else { String::new() };
+            q3tts_set_output_rate(self.raw, eng_rate);
+            q3tts_set_speed(self.raw, eng_speed);
+            if rc != 0 { q3tts_long_result_free(&mut out); return Err(msg); }
+            let samples = std::slice::from_raw_parts(out.pcm, out.n_samples as usize).to_vec();
+            let r = out.sample_rate as f64;
+            let info = std::slice::from_raw_parts(out.info, out.n_segments as usize);
+            let table = pieces.iter().zip(info.iter()).map(|(p, f)| LongSegment {
+                text: p.to_string(), t_begin_s: f.out_begin as f64 / r, t_end_s: f.out_end as f64 / r, hit_eos: f.hit_eos != 0 }).collect();
+            let rate = out.sample_rate as u32;
+            q3tts_long_result_free(&mut out);
+            Ok((AudioSample { samples, sample_rate: rate, channels: 1 }, table))
         }
     }
 }
