@@ -110,8 +110,16 @@ typedef struct q3tts_engine_config {
                                * bf16 at load) and qwen3_assets.gguf or its NPY fallback
                                * (src/assets_manager.rs:14-26). Shapes must match `model`: q3tts_config_from_model_dir below
                                * fills `model` and this field from the files themselves. The table row counts
-                               * (text_vocab, codec0_rows, codecq_rows) are taken from the files. The vocoder stays
-                               * synthetic: the reference ships it as ONNX only. */
+                               * (text_vocab, codec0_rows, codecq_rows) are taken from the files. The vocoder
+                               * (with_vocoder = 1) takes trained weights from qwen3_tts_vocoder.gguf when that file lies in this
+                               * directory or, failing that, in its parent (the model directory: one unquantised file serves every
+                               * quant directory); q3tts_get_vocoder_source says which it was. Without the file the vocoder's
+                               * weights are the seeded synthetic ones. A file that is there but wrong (a missing tensor, a shape
+                               * or metadata value that disagrees with `vocoder`, an unsupported tensor type, a value that is not
+                               * finite, a file that ends early) fails q3tts_engine_create with a message naming the file and the
+                               * tensor or key, before anything is allocated on the device: never a silent fall-back. Names,
+                               * layouts and the precision rule: DESIGN.md section 27; tools/vocoder_to_gguf.py writes the file
+                               * from a PyTorch checkpoint. */
     int32_t talker_q8_0;      /* 1: the Talker's matrices and lm_head stay ggml Q8_0 blocks ON THE DEVICE (f16 scale + 32 int8 per block,
                                * 1.06 bytes per weight instead of 2) and are multiplied in that form (W8A16: bf16 activations, every block's
                                * MFMA product scaled by f32(d)) — the reference's default quantisation (gguf_q8_0,
@@ -187,8 +195,11 @@ void q3tts_default_config(q3tts_engine_config* cfg);
  *    qwen3_assets.gguf (or codec_embedding_N.npy files), contiguous from 0; codebook_size = rows of the Predictor's output.weight /
  *    (n_codebooks - 1), exactly; d_embed = the codec tables' row length (= t_d_model); text_vocab (0 without a text table,
  *    src/assets_manager.rs:244-249), codec0_rows, codecq_rows = the tables' row counts (tables 1 .. must agree).
+ *  - cfg->vocoder, when cfg->with_vocoder != 0 and qwen3_tts_vocoder.gguf lies in the quant directory or, failing that, in model_dir
+ *    itself: every field q3tts_vocoder_config_from_file (below) takes from that file, under its checks. Without such a file, or with
+ *    with_vocoder = 0, the whole vocoder block is left alone.
  * Everything else is left alone: device, max_batch, n_ctx, max_steps_cap, with_vocoder, synth_seed, talker_q8_0, predictor_q8_0, vocoder_flush_tail,
- * the whole vocoder block, and the protocol fields no file states (sample_limit, eos_code, tts_pad_id).
+ * vocoder.layer_scale_init, and the protocol fields no file states (sample_limit, eos_code, tts_pad_id).
  * Cross-checks: proj.weight is [p_d_model][d_embed], and blk.0.attn_q / attn_k / attn_output / ffn_gate / ffn_down.weight of both files
  * have the shapes the metadata implies. What only the device path can judge, and what q3tts_engine_create checks (K % 512,
  * t_vocab % 16, ...), is not checked here: q3tts_engine_create stays the one place for that.
@@ -199,9 +210,25 @@ void q3tts_default_config(q3tts_engine_config* cfg);
 int q3tts_config_from_model_dir(const char* model_dir, const char* quant, q3tts_engine_config* cfg, char* path_buf, int32_t path_cap,
                                 char* err, int32_t err_cap);
 
+/* The vocoder's shape from its weights file (host only, no GPU). On entry *vc holds a complete vocoder block. On
+ * success every field the file's metadata states is overwritten — with A = "q3tts-vocoder" (the file's general.architecture):
+ * A.n_codebooks, A.codebook_size, A.codebook_dim, A.latent_dim, A.pre_conv_kernel, A.block_count -> n_layer, A.attention.head_count ->
+ * n_head, A.attention.key_length -> head_dim, A.feed_forward_length -> d_ffn, A.attention.sliding_window, A.rope.freq_base ->
+ * rope_theta, A.attention.layer_norm_rms_epsilon -> rms_eps, A.upsample_ratios (integer array; its length -> n_upsample), A.decoder_dim,
+ * A.decoder_rates (integer array; its length -> n_dec_blocks), A.lookahead_frames, A.sample_rate; every key is required.
+ * layer_scale_init parametrises only the synthetic generator and is left alone. Cross-checks: the numbers of codebook.N.weight tables,
+ * transformer layers, up-sampling stages and decoder blocks, and the shape of every tensor the metadata implies (the tables, q_proj,
+ * gate_proj, ..., the [in][out][kernel] of every ConvTranspose against its ratio, the decoder's channel halving). Errors as for
+ * q3tts_config_from_model_dir: the message goes to err and names the file and the key or tensor (with both numbers), *vc stays
+ * unchanged; Q3TTS_ERR_IO for a file that cannot be opened or ends early, Q3TTS_ERR_INVALID otherwise. */
+int q3tts_vocoder_config_from_file(const char* path, q3tts_vocoder_config* vc, char* err, int32_t err_cap);
+
 /* TtsEngine::new (reference: src/tts/engine.rs:84-169): allocates weights, KV slabs, vocoder state on the
  * device and builds the replayable frame-step graphs. */
 int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine** out);
+/* Where the engine's vocoder weights came from: 0 = no vocoder (with_vocoder = 0), 1 = the seeded synthetic generator, 2 = the file
+ * qwen3_tts_vocoder.gguf (q3tts_engine_config.weights_path). Audio of an engine that answers 1 is the output of random filters. */
+int q3tts_get_vocoder_source(const q3tts_engine* e, int32_t* source);
 void q3tts_engine_destroy(q3tts_engine* e);
 
 /* Message for the last failing call on this engine (or on this thread when e == NULL). */
@@ -809,6 +836,10 @@ typedef struct q3tts_voc_tap {
 } q3tts_voc_tap;
 int q3tts_k_vocoder_taps(q3tts_engine* e, const int32_t* codes, int32_t n_frames, int32_t chunk_frames, int32_t tap_call, void* buf,
                          uint64_t buf_bytes, q3tts_voc_tap* recs, int32_t rec_cap, int32_t* n_recs);
+/* Host-only: the array q3tts_engine_create would upload from the vocoder file `path` for the synthetic generator's tensor id (comp,
+ * which) of oracle/q3_oracle_vocoder.c, at the shape *vc: in device layout, after rounding (bf16-representable where the device holds
+ * bf16), as f32; for a SnakeBeta id the evaluated exp(alpha) / 1 / (exp(beta) + 1e-9). out may be NULL to query *n. Needs no GPU. */
+int q3tts_k_voc_file_tensor(const char* path, const q3tts_vocoder_config* vc, int32_t comp, int32_t which, float* out, int64_t cap, int64_t* n);
 /* Measurement (bench.py roofline_vocoder): the batched vocoder alone, n_slots slots x `chunks` 4-frame calls with nothing else on the
  * GPU; *ms_per_chunk = mean duration of one batched call (n_slots x 4 frames of PCM) by HIP events on its stream. */
 int q3tts_k_vocoder_bench(q3tts_engine* e, int32_t n_slots, int32_t chunks, float* ms_per_chunk);

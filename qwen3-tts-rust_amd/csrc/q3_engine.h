@@ -141,6 +141,7 @@ struct q3tts_engine {
     std::vector<hipEvent_t> fin_ev;     // per slot: PCM of a finished utterance copied to the host (vocoder stream)
     q3tts_timings tm{};
     Q3Voc* voc = nullptr;
+    int voc_source = 0;                 // q3tts_get_vocoder_source: 0 no vocoder, 1 synthetic weights, 2 qwen3_tts_vocoder.gguf
     Q3Mel* mel = nullptr;               // created on first use
     Q3Clone* clone = nullptr;           // q3tts_clone_init
     // q3tts_k_probe: eager frame steps, events around the Predictor gate/up GEMM (pass 1, layer 0) of every frame
@@ -279,7 +280,9 @@ void q3_mel_destroy(q3tts_engine* e);
 int q3_mel_run(q3tts_engine* e, const float* audio, int64_t n_samples, int32_t* n_frames, float** out_dev);
 void q3_clone_destroy(q3tts_engine* e);
 // vocoder interface (q3_vocoder.hip)
-int q3_voc_create(q3tts_engine* e);
+// voc_file: the opened and checked qwen3_tts_vocoder.gguf (q3_voc_file_check has passed) whose tensors fill the weights, `file` its path for
+// messages; nullptr: the seeded synthetic generator. One creation path: only the source of each array differs.
+int q3_voc_create(q3tts_engine* e, const Q3Gguf* voc_file, const std::string& file);
 void q3_voc_destroy(q3tts_engine* e);
 // reset the streaming state of a slot
 int q3_voc_reset(q3tts_engine* e, int slot);

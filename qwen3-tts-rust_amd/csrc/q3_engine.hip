@@ -179,6 +179,11 @@ extern "C" int q3tts_k_prefix_stats(const q3tts_engine* e, int64_t* out2) {
     out2[0] = e->kvp_launches.load(std::memory_order_relaxed); out2[1] = e->kvp_group_max.load(std::memory_order_relaxed);
     return Q3TTS_OK;
 }
+extern "C" int q3tts_get_vocoder_source(const q3tts_engine* e, int32_t* source) {
+    if (!e || !source) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    *source = e->voc_source;
+    return Q3TTS_OK;
+}
 extern "C" int q3tts_k_device_bytes(const q3tts_engine* e, int64_t* bytes) {
     if (!e || !bytes) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
     *bytes = (int64_t)e->dev_bytes;
@@ -221,6 +226,15 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
         if (!prefill_ok || q3_attend_pick_kv8(pa) == Q3_ATT_REFUSED || mm.t_head_dim % 32 || cfg->n_ctx % 64)
             return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, "kv_q8_0 = 1: the Q8_0-cache attention kernels need t_head_dim = 128, a GQA ratio of 1, 2 or 4 and n_ctx in whole 64-key blocks; this model has t_head_dim = " +
                               std::to_string(mm.t_head_dim) + ", ratio " + std::to_string(R) + ", n_ctx = " + std::to_string(cfg->n_ctx));
+    }
+    // The vocoder's weights file, found beside the model (q3_voc_file_find), is opened and checked in full here, on the host, before the
+    // device is touched: a file that is there but wrong fails the create, it never falls back to synthetic weights and never reaches a kernel.
+    Q3Gguf gv;
+    std::string vfile;
+    if (cfg->with_vocoder && cfg->weights_path) {
+        vfile = q3_voc_file_find(cfg->weights_path);
+        std::string er;
+        if (!vfile.empty() && (gv.open(vfile, er) || q3_voc_file_check(gv, vfile, cfg->vocoder, er))) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, er);
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -330,7 +344,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
         HIPC(hipStreamSynchronize(s));
     }
     if (cfg->with_vocoder) {
-        TRYC(q3_voc_create(e));
+        TRYC(q3_voc_create(e, vfile.empty() ? nullptr : &gv, vfile));
         HIPC(hipHostMalloc((void**)&e->first_chunk_host, sizeof(float) * 4 * (size_t)q3_voc_samples_per_frame(e), hipHostMallocDefault));
     }
     // capture the frame step once per row-count bucket; every later frame is a replay (Q3TTS_NO_GRAPH=1: eager launches, for profilers)

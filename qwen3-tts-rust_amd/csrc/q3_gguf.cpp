@@ -400,10 +400,385 @@ int q3_npy_shape(const std::string& path, std::vector<size_t>& shape, std::strin
     return 0;
 }
 
-// ---- C ABI test hook (host only) -------------------------------------------------------------------------------
+// ---- the vocoder's weights file (q3_gguf.h; the table is DESIGN.md §27) ----------------------------------------------------------------
 #include "../../include/q3tts.h"
+
+#include <algorithm>
+#include <cmath>
+#include <set>
+
+namespace {
+
+const char* const kVocArch = "q3tts-vocoder";
+
+// how a file tensor (PyTorch layout) becomes the device's array
+enum VfKind {
+    VF_COPY,     // vectors, [out][in] matrices, codebook tables: as stored
+    VF_CONV,     // Conv1d [n][ci][k] -> W[tap][n][ci]
+    VF_CONVT,    // ConvTranspose1d [i][o][r] (kernel = stride = r) -> W[j][o][i]
+    VF_CONVT2,   // ConvTranspose1d [i][o][2r] (stride r) -> W[tap][j][o][i]: tap 1 = kernel taps 0 .. r-1 (the current step), tap 0 = r .. 2r-1
+    VF_DW,       // depth-wise Conv1d [c][1][7] -> [7][c]
+    VF_SNAKE_A,  // log alpha -> exp(alpha)
+    VF_SNAKE_B   // log beta -> 1 / (exp(beta) + 1e-9)
+};
+struct VfSpec { std::string name; std::vector<int64_t> shape; VfKind kind = VF_COPY; bool bf16 = false; };
+
+// decoder block b's input channels
+int64_t vf_block_in(const q3tts_vocoder_config& c, int b) { int64_t ch = c.decoder_dim; for (int i = 0; i < b; ++i) ch /= 2; return ch; }
+
+// generator id (comp, which) -> file tensor; false for an id the shape vc does not have
+bool vf_spec(const q3tts_vocoder_config& c, int comp, int which, VfSpec* s) {
+    const int64_t d = c.latent_dim, H = (int64_t)c.n_head * c.head_dim, F = c.d_ffn, dd = c.decoder_dim;
+    auto set = [&](const std::string& name, std::vector<int64_t> shape, VfKind kind, bool bf16) { s->name = name; s->shape = std::move(shape); s->kind = kind; s->bf16 = bf16; return true; };
+    auto vec = [&](const std::string& name, int64_t n) { return set(name, {n}, VF_COPY, false); };
+    auto mat = [&](const std::string& name, int64_t rows, int64_t cols) { return set(name, {rows, cols}, VF_COPY, true); };
+    auto conv = [&](const std::string& name, int64_t n, int64_t ci, int64_t k) { return set(name, {n, ci, k}, VF_CONV, true); };
+    if (comp >= VC_CODEBOOK && comp < VC_CODEBOOK + c.n_codebooks && comp < VC_PRE)
+        return which == VW_W && mat("codebook." + std::to_string(comp - VC_CODEBOOK) + ".weight", c.codebook_size, c.codebook_dim);
+    if (comp == VC_PRE) {
+        if (which == VW_W) return conv("pre_conv.conv.weight", d, c.codebook_dim, c.pre_conv_kernel);
+        return which == VW_B && vec("pre_conv.conv.bias", d);
+    }
+    if (comp >= VC_TFM && comp < VC_TFM + c.n_layer && comp < VC_FINAL_NORM) {
+        const std::string p = "pre_transformer.layers." + std::to_string(comp - VC_TFM) + ".";
+        switch (which) {
+            case VW_IN_NORM: return vec(p + "input_layernorm.weight", d);
+            case VW_POST_NORM: return vec(p + "post_attention_layernorm.weight", d);
+            case VW_LS_ATTN: return vec(p + "self_attn_layer_scale.scale", d);
+            case VW_LS_MLP: return vec(p + "mlp_layer_scale.scale", d);
+            case VW_Q: return mat(p + "self_attn.q_proj.weight", H, d);
+            case VW_K: return mat(p + "self_attn.k_proj.weight", H, d);
+            case VW_V: return mat(p + "self_attn.v_proj.weight", H, d);
+            case VW_O: return mat(p + "self_attn.o_proj.weight", d, H);
+            case VW_GATE: return mat(p + "mlp.gate_proj.weight", F, d);
+            case VW_UP: return mat(p + "mlp.up_proj.weight", F, d);
+            case VW_DOWN: return mat(p + "mlp.down_proj.weight", d, F);
+            default: return false;
+        }
+    }
+    if (comp == VC_FINAL_NORM) return which == VW_W && vec("pre_transformer.norm.weight", d);
+    if (comp >= VC_UP && comp < VC_UP + c.n_upsample && comp < VC_UP + Q3TTS_MAX_UPSAMPLE) {
+        const int u = comp - VC_UP;
+        const std::string p = "upsample." + std::to_string(u) + ".";
+        switch (which) {
+            case VW_W: return set(p + "0.conv.weight", {d, d, c.upsample_ratios[u]}, VF_CONVT, true);
+            case VW_B: return vec(p + "0.conv.bias", d);
+            case VW_DW_W: return set(p + "1.dwconv.conv.weight", {d, 1, 7}, VF_DW, false);
+            case VW_DW_B: return vec(p + "1.dwconv.conv.bias", d);
+            case VW_LN_W: return vec(p + "1.norm.weight", d);
+            case VW_LN_B: return vec(p + "1.norm.bias", d);
+            case VW_PW1: return mat(p + "1.pwconv1.weight", 4 * d, d);
+            case VW_PW1_B: return vec(p + "1.pwconv1.bias", 4 * d);
+            case VW_PW2: return mat(p + "1.pwconv2.weight", d, 4 * d);
+            case VW_PW2_B: return vec(p + "1.pwconv2.bias", d);
+            case VW_GAMMA: return vec(p + "1.gamma", d);
+            default: return false;
+        }
+    }
+    if (comp == VC_DEC_IN) {
+        if (which == VW_W) return conv("decoder.0.conv.weight", dd, d, 7);
+        return which == VW_B && vec("decoder.0.conv.bias", dd);
+    }
+    if (comp >= VC_BLK && comp < VC_BLK + 4 * c.n_dec_blocks && comp < VC_BLK + 4 * Q3TTS_MAX_DEC_BLOCKS) {
+        const int b = (comp - VC_BLK) / 4, part = (comp - VC_BLK) % 4;
+        const int64_t ch = vf_block_in(c, b), co = ch / 2, r = c.dec_rates[b];
+        const std::string p = "decoder." + std::to_string(1 + b) + ".block.";
+        if (part == 0) switch (which) {
+            case VW_ALPHA: return set(p + "0.alpha", {ch}, VF_SNAKE_A, false);
+            case VW_BETA: return set(p + "0.beta", {ch}, VF_SNAKE_B, false);
+            case VW_W: return set(p + "1.conv.weight", {ch, co, 2 * r}, VF_CONVT2, true);
+            case VW_B: return vec(p + "1.conv.bias", co);
+            default: return false;
+        }
+        const std::string q = p + std::to_string(1 + part) + ".";
+        switch (which) {
+            case VW_ALPHA: return set(q + "act1.alpha", {co}, VF_SNAKE_A, false);
+            case VW_BETA: return set(q + "act1.beta", {co}, VF_SNAKE_B, false);
+            case VW_W: return conv(q + "conv1.conv.weight", co, co, 7);
+            case VW_B: return vec(q + "conv1.conv.bias", co);
+            case VW_ALPHA2: return set(q + "act2.alpha", {co}, VF_SNAKE_A, false);
+            case VW_BETA2: return set(q + "act2.beta", {co}, VF_SNAKE_B, false);
+            case VW_W2: return conv(q + "conv2.conv.weight", co, co, 1);
+            case VW_B2: return vec(q + "conv2.conv.bias", co);
+            default: return false;
+        }
+    }
+    if (comp == VC_OUT) {
+        const int64_t ch = vf_block_in(c, c.n_dec_blocks);
+        switch (which) {
+            case VW_ALPHA: return set("decoder." + std::to_string(1 + c.n_dec_blocks) + ".alpha", {ch}, VF_SNAKE_A, false);
+            case VW_BETA: return set("decoder." + std::to_string(1 + c.n_dec_blocks) + ".beta", {ch}, VF_SNAKE_B, false);
+            case VW_W: return conv("decoder." + std::to_string(2 + c.n_dec_blocks) + ".conv.weight", 1, ch, 7);
+            case VW_B: return vec("decoder." + std::to_string(2 + c.n_dec_blocks) + ".conv.bias", 1);
+            default: return false;
+        }
+    }
+    return false;
+}
+
+// every id the shape vc has, in the order q3_voc_create takes them
+std::vector<std::pair<int, int>> vf_ids(const q3tts_vocoder_config& c) {
+    std::vector<std::pair<int, int>> ids;
+    for (int q = 0; q < c.n_codebooks; ++q) ids.push_back({VC_CODEBOOK + q, VW_W});
+    ids.push_back({VC_PRE, VW_W}); ids.push_back({VC_PRE, VW_B});
+    for (int l = 0; l < c.n_layer; ++l)
+        for (int w : {VW_IN_NORM, VW_POST_NORM, VW_LS_ATTN, VW_LS_MLP, VW_Q, VW_K, VW_V, VW_O, VW_GATE, VW_UP, VW_DOWN}) ids.push_back({VC_TFM + l, w});
+    ids.push_back({VC_FINAL_NORM, VW_W});
+    for (int u = 0; u < c.n_upsample; ++u)
+        for (int w : {VW_W, VW_B, VW_DW_W, VW_DW_B, VW_LN_W, VW_LN_B, VW_PW1, VW_PW1_B, VW_PW2, VW_PW2_B, VW_GAMMA}) ids.push_back({VC_UP + u, w});
+    ids.push_back({VC_DEC_IN, VW_W}); ids.push_back({VC_DEC_IN, VW_B});
+    for (int b = 0; b < c.n_dec_blocks; ++b) {
+        for (int w : {VW_ALPHA, VW_BETA, VW_W, VW_B}) ids.push_back({VC_BLK + 4 * b, w});
+        for (int u = 1; u <= 3; ++u)
+            for (int w : {VW_ALPHA, VW_BETA, VW_W, VW_B, VW_ALPHA2, VW_BETA2, VW_W2, VW_B2}) ids.push_back({VC_BLK + 4 * b + u, w});
+    }
+    for (int w : {VW_ALPHA, VW_BETA, VW_W, VW_B}) ids.push_back({VC_OUT, w});
+    return ids;
+}
+
+std::string vf_shape_str(const std::vector<int64_t>& s) { std::string r; for (int64_t v : s) r += "[" + std::to_string(v) + "]"; return r; }
+
+// the file's tensor of `s`, present and of its PyTorch shape (GGUF lists dimensions innermost first); `whence` says where the expected shape came from
+const Q3GgufTensor* vf_tensor(const Q3Gguf& g, const std::string& file, const VfSpec& s, const char* whence, std::string& err) {
+    const Q3GgufTensor* t = g.find(s.name);
+    if (!t) { err = file + ": tensor '" + s.name + "' is missing"; return nullptr; }
+    std::vector<int64_t> have(t->dims.rbegin(), t->dims.rend());
+    if (have != s.shape) { err = file + ": tensor '" + s.name + "' has shape " + vf_shape_str(have) + ", " + whence + " " + vf_shape_str(s.shape); return nullptr; }
+    return t;
+}
+
+// the metadata: every key is required
+struct VfIntKey { const char* key; int32_t q3tts_vocoder_config::*field; };
+const VfIntKey kVfInts[] = {
+    {"n_codebooks", &q3tts_vocoder_config::n_codebooks}, {"codebook_size", &q3tts_vocoder_config::codebook_size},
+    {"codebook_dim", &q3tts_vocoder_config::codebook_dim}, {"latent_dim", &q3tts_vocoder_config::latent_dim},
+    {"pre_conv_kernel", &q3tts_vocoder_config::pre_conv_kernel}, {"block_count", &q3tts_vocoder_config::n_layer},
+    {"attention.head_count", &q3tts_vocoder_config::n_head}, {"attention.key_length", &q3tts_vocoder_config::head_dim},
+    {"feed_forward_length", &q3tts_vocoder_config::d_ffn}, {"attention.sliding_window", &q3tts_vocoder_config::sliding_window},
+    {"decoder_dim", &q3tts_vocoder_config::decoder_dim}, {"sample_rate", &q3tts_vocoder_config::sample_rate},
+};
+std::string vf_key(const char* k) { return std::string(kVocArch) + "." + k; }
+
+int vf_read_meta(const Q3Gguf& g, const std::string& file, q3tts_vocoder_config* vc, std::string& err) {
+    auto bad = [&](const std::string& m) { err = file + ": " + m; return -1; };
+    std::string arch;
+    const int st = g.meta_str("general.architecture", &arch);
+    if (st == Q3_META_MISSING) return bad("metadata key 'general.architecture' is missing");
+    if (st == Q3_META_TYPE) return bad("metadata key 'general.architecture' is not a string");
+    if (arch != kVocArch) return bad("metadata key 'general.architecture' = '" + arch + "', a vocoder file has '" + kVocArch + "'");
+    auto integer = [&](const std::string& k, int64_t lo, int32_t* out) {
+        int64_t v = 0;
+        const int s = g.meta_int(k, &v);
+        if (s == Q3_META_MISSING) return bad("metadata key '" + k + "' is missing");
+        if (s == Q3_META_TYPE) return bad("metadata key '" + k + "' is not an integer");
+        if (v < lo || v > (1 << 24)) return bad("metadata key '" + k + "' = " + std::to_string(v) + " is out of range");
+        *out = (int32_t)v;
+        return 0;
+    };
+    for (const VfIntKey& k : kVfInts) if (integer(vf_key(k.key), 1, &(vc->*k.field))) return -1;
+    if (integer(vf_key("lookahead_frames"), 0, &vc->lookahead_frames)) return -1;
+    auto real = [&](const std::string& k, float* out) {
+        double v = 0;
+        const int s = g.meta_float(k, &v);
+        if (s == Q3_META_MISSING) return bad("metadata key '" + k + "' is missing");
+        if (s == Q3_META_TYPE) return bad("metadata key '" + k + "' is not a float");
+        if (!std::isfinite(v)) return bad("metadata key '" + k + "' is not finite");
+        *out = (float)v;
+        return 0;
+    };
+    if (real(vf_key("rope.freq_base"), &vc->rope_theta) || real(vf_key("attention.layer_norm_rms_epsilon"), &vc->rms_eps)) return -1;
+    auto ints = [&](const std::string& k, int cap, int32_t* n, int32_t* out) {
+        std::vector<int64_t> v;
+        const int s = g.meta_int_array(k, &v);
+        if (s == Q3_META_MISSING) return bad("metadata key '" + k + "' is missing");
+        if (s == Q3_META_TYPE) return bad("metadata key '" + k + "' is not an integer array");
+        if ((int64_t)v.size() > cap) return bad("metadata key '" + k + "' has " + std::to_string(v.size()) + " entries, at most " + std::to_string(cap) + " are allowed");
+        for (int i = 0; i < cap; ++i) out[i] = 0;
+        for (size_t i = 0; i < v.size(); ++i) {
+            if (v[i] < 1 || v[i] > 4096) return bad("metadata key '" + k + "' entry " + std::to_string(i) + " = " + std::to_string(v[i]) + " is out of range");
+            out[i] = (int32_t)v[i];
+        }
+        *n = (int32_t)v.size();
+        return 0;
+    };
+    if (ints(vf_key("upsample_ratios"), Q3TTS_MAX_UPSAMPLE, &vc->n_upsample, vc->upsample_ratios)) return -1;
+    if (ints(vf_key("decoder_rates"), Q3TTS_MAX_DEC_BLOCKS, &vc->n_dec_blocks, vc->dec_rates)) return -1;
+    return 0;
+}
+
+// how many distinct N have a tensor "<prefix>N<suffix>..."
+int64_t vf_count(const Q3Gguf& g, const std::string& prefix, const std::string& suffix) {
+    std::set<std::string> idx;
+    for (const Q3GgufTensor& t : g.tensors()) {
+        if (t.name.compare(0, prefix.size(), prefix) != 0) continue;
+        size_t i = prefix.size();
+        while (i < t.name.size() && t.name[i] >= '0' && t.name[i] <= '9') ++i;
+        if (i > prefix.size() && t.name.compare(i, suffix.size(), suffix) == 0) idx.insert(t.name.substr(prefix.size(), i - prefix.size()));
+    }
+    return (int64_t)idx.size();
+}
+
+// one tensor as the device's array (see q3_voc_file_array); tmp is scratch
+int vf_array(const Q3GgufTensor& t, const VfSpec& s, std::vector<float>& tmp, std::vector<float>& out, std::string& err) {
+    const size_t n = t.nelem;
+    out.resize(n);
+    std::vector<float>& src = s.kind == VF_COPY ? out : tmp;
+    src.resize(n);
+    if (q3_gguf_to_f32(t, src.data(), err)) return -1;
+    const float* w = src.data();
+    switch (s.kind) {
+        case VF_COPY: break;
+        case VF_CONV: {
+            const size_t N = (size_t)s.shape[0], CI = (size_t)s.shape[1], K = (size_t)s.shape[2];
+            for (size_t nn = 0; nn < N; ++nn) for (size_t ci = 0; ci < CI; ++ci) for (size_t k = 0; k < K; ++k) out[(k * N + nn) * CI + ci] = w[(nn * CI + ci) * K + k];
+            break;
+        }
+        case VF_CONVT: {
+            const size_t I = (size_t)s.shape[0], O = (size_t)s.shape[1], R = (size_t)s.shape[2];
+            for (size_t i = 0; i < I; ++i) for (size_t o = 0; o < O; ++o) for (size_t j = 0; j < R; ++j) out[(j * O + o) * I + i] = w[(i * O + o) * R + j];
+            break;
+        }
+        case VF_CONVT2: {
+            const size_t I = (size_t)s.shape[0], O = (size_t)s.shape[1], R = (size_t)s.shape[2] / 2;
+            for (size_t i = 0; i < I; ++i) for (size_t o = 0; o < O; ++o) for (size_t j = 0; j < R; ++j) {
+                out[(((size_t)1 * R + j) * O + o) * I + i] = w[(i * O + o) * 2 * R + j];
+                out[(((size_t)0 * R + j) * O + o) * I + i] = w[(i * O + o) * 2 * R + R + j];
+            }
+            break;
+        }
+        case VF_DW: {
+            const size_t C = (size_t)s.shape[0], K = (size_t)s.shape[2];
+            for (size_t c = 0; c < C; ++c) for (size_t k = 0; k < K; ++k) out[k * C + c] = w[c * K + k];
+            break;
+        }
+        case VF_SNAKE_A: for (size_t i = 0; i < n; ++i) out[i] = (float)exp((double)w[i]); break;
+        case VF_SNAKE_B: for (size_t i = 0; i < n; ++i) out[i] = (float)(1.0 / (exp((double)w[i]) + 1e-9)); break;
+    }
+    if (s.bf16)
+        for (size_t i = 0; i < n; ++i) { const uint32_t u = (uint32_t)f32_to_bf16_rne(out[i]) << 16; memcpy(&out[i], &u, 4); }
+    return 0;
+}
+
+// every tensor of the shape vc: present, of vc's shape, of a type the reader reads
+int vf_check_tensors(const Q3Gguf& g, const std::string& file, const q3tts_vocoder_config& vc, const char* whence, std::string& err) {
+    if (vc.n_layer > VC_FINAL_NORM - VC_TFM) { err = file + ": metadata key '" + vf_key("block_count") + "' = " + std::to_string(vc.n_layer) + " is out of range"; return -1; }
+    for (const auto& id : vf_ids(vc)) {
+        VfSpec s;
+        if (!vf_spec(vc, id.first, id.second, &s)) { err = file + ": no tensor for id (" + std::to_string(id.first) + ", " + std::to_string(id.second) + ")"; return -1; }
+        const Q3GgufTensor* t = vf_tensor(g, file, s, whence, err);
+        if (!t) return -1;
+        if (!t->data) { err = file + ": tensor '" + s.name + "': unsupported ggml type " + std::to_string(t->type) + " (supported: F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K)"; return -1; }
+    }
+    return 0;
+}
+
+}  // namespace
+
+std::string q3_voc_file_find(const std::string& wdir) {
+    auto is_file = [](const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); };
+    std::string d = wdir;
+    while (d.size() > 1 && d.back() == '/') d.pop_back();
+    if (is_file(d + "/" + Q3_VOC_FILE_NAME)) return d + "/" + Q3_VOC_FILE_NAME;
+    const size_t sl = d.rfind('/');
+    const std::string parent = sl == std::string::npos ? std::string(".") : sl == 0 ? std::string("/") : d.substr(0, sl);
+    const std::string p = (parent == "/" ? std::string() : parent) + "/" + Q3_VOC_FILE_NAME;
+    return is_file(p) ? p : std::string();
+}
+
+int q3_voc_file_config(const Q3Gguf& g, const std::string& file, q3tts_vocoder_config* vc, std::string& err) {
+    q3tts_vocoder_config c = *vc;  // (*vc is written only on success; layer_scale_init is no file's to state)
+    if (vf_read_meta(g, file, &c, err)) return -1;
+    auto count = [&](const char* key, int64_t want, const std::string& prefix, const std::string& suffix) {
+        const int64_t have = vf_count(g, prefix, suffix);
+        if (have == want) return 0;
+        err = file + ": metadata key '" + vf_key(key) + "' implies " + std::to_string(want) + " tensors '" + prefix + "N" + suffix + "...', the file has " + std::to_string(have);
+        return -1;
+    };
+    if (count("n_codebooks", c.n_codebooks, "codebook.", ".weight") || count("block_count", c.n_layer, "pre_transformer.layers.", ".") ||
+        count("upsample_ratios", c.n_upsample, "upsample.", ".0.conv.weight") || count("decoder_rates", c.n_dec_blocks, "decoder.", ".block.0.alpha")) return -1;
+    {   // the decoder halves its channels block by block
+        int64_t ch = c.decoder_dim;
+        for (int b = 0; b < c.n_dec_blocks; ++b) {
+            if (ch % 2) { err = file + ": metadata key '" + vf_key("decoder_dim") + "' = " + std::to_string(c.decoder_dim) + " cannot be halved " + std::to_string(c.n_dec_blocks) + " times ('" + vf_key("decoder_rates") + "')"; return -1; }
+            ch /= 2;
+        }
+    }
+    if (vf_check_tensors(g, file, c, "the file's metadata implies", err)) return -1;
+    *vc = c;
+    return 0;
+}
+
+int q3_voc_file_check(const Q3Gguf& g, const std::string& file, const q3tts_vocoder_config& vc, std::string& err) {
+    q3tts_vocoder_config m = vc;
+    if (vf_read_meta(g, file, &m, err)) return -1;
+    auto differs = [&](const std::string& key, const std::string& have, const std::string& want) {
+        err = file + ": metadata key '" + key + "' = " + have + ", the configuration has " + want;
+        return -1;
+    };
+    for (const VfIntKey& k : kVfInts) if (m.*k.field != vc.*k.field) return differs(vf_key(k.key), std::to_string(m.*k.field), std::to_string(vc.*k.field));
+    if (m.lookahead_frames != vc.lookahead_frames) return differs(vf_key("lookahead_frames"), std::to_string(m.lookahead_frames), std::to_string(vc.lookahead_frames));
+    auto g9 = [](float v) { char b[40]; snprintf(b, sizeof b, "%.9g", (double)v); return std::string(b); };
+    if (m.rope_theta != vc.rope_theta) return differs(vf_key("rope.freq_base"), g9(m.rope_theta), g9(vc.rope_theta));
+    if (m.rms_eps != vc.rms_eps) return differs(vf_key("attention.layer_norm_rms_epsilon"), g9(m.rms_eps), g9(vc.rms_eps));
+    auto list = [](const int32_t* v, int n) { std::string r = "["; for (int i = 0; i < n; ++i) r += (i ? ", " : "") + std::to_string(v[i]); return r + "]"; };
+    if (m.n_upsample != vc.n_upsample || memcmp(m.upsample_ratios, vc.upsample_ratios, sizeof(int32_t) * (size_t)std::max(0, std::min<int>(vc.n_upsample, Q3TTS_MAX_UPSAMPLE))))
+        return differs(vf_key("upsample_ratios"), list(m.upsample_ratios, m.n_upsample), list(vc.upsample_ratios, std::max(0, std::min<int>(vc.n_upsample, Q3TTS_MAX_UPSAMPLE))));
+    if (m.n_dec_blocks != vc.n_dec_blocks || memcmp(m.dec_rates, vc.dec_rates, sizeof(int32_t) * (size_t)std::max(0, std::min<int>(vc.n_dec_blocks, Q3TTS_MAX_DEC_BLOCKS))))
+        return differs(vf_key("decoder_rates"), list(m.dec_rates, m.n_dec_blocks), list(vc.dec_rates, std::max(0, std::min<int>(vc.n_dec_blocks, Q3TTS_MAX_DEC_BLOCKS))));
+    if (vf_check_tensors(g, file, vc, "the configuration needs", err)) return -1;
+    std::vector<float> buf;
+    for (const auto& id : vf_ids(vc)) {
+        VfSpec s;
+        vf_spec(vc, id.first, id.second, &s);
+        const Q3GgufTensor* t = g.find(s.name);
+        buf.resize(t->nelem);
+        if (q3_gguf_to_f32(*t, buf.data(), err)) { err = file + ": " + err; return -1; }
+        for (size_t i = 0; i < buf.size(); ++i)
+            if (!std::isfinite(buf[i])) { err = file + ": tensor '" + s.name + "' holds a value that is not finite (element " + std::to_string(i) + ")"; return -1; }
+    }
+    return 0;
+}
+
+int q3_voc_file_array(const Q3Gguf& g, const std::string& file, const q3tts_vocoder_config& vc, int comp, int which, std::vector<float>& out, std::string& err) {
+    VfSpec s;
+    if (!vf_spec(vc, comp, which, &s)) { err = file + ": the vocoder shape has no tensor of id (" + std::to_string(comp) + ", " + std::to_string(which) + ")"; return -1; }
+    const Q3GgufTensor* t = vf_tensor(g, file, s, "the configuration needs", err);
+    if (!t) return -1;
+    std::vector<float> tmp;
+    if (vf_array(*t, s, tmp, out, err)) { err = file + ": " + err; return -1; }
+    return 0;
+}
+
+// ---- C ABI test hook (host only) -------------------------------------------------------------------------------
 struct q3tts_engine;
 int q3_set_err(q3tts_engine* e, int code, const std::string& msg);  // q3_engine.hip (engine == nullptr: the global error slot)
+
+extern "C" int q3tts_vocoder_config_from_file(const char* path, q3tts_vocoder_config* vc, char* err, int32_t err_cap) {
+    std::string msg;
+    auto done = [&](int rc) {
+        if (err && err_cap > 0) { const size_t n = msg.size() < (size_t)err_cap - 1 ? msg.size() : (size_t)err_cap - 1; memcpy(err, msg.data(), n); err[n] = '\0'; }
+        return rc;
+    };
+    if (!path || !vc) { msg = "null argument"; return done(Q3TTS_ERR_INVALID); }
+    Q3Gguf g;
+    if (g.open(path, msg)) return done(Q3TTS_ERR_IO);
+    return done(q3_voc_file_config(g, path, vc, msg) ? Q3TTS_ERR_INVALID : Q3TTS_OK);
+}
+
+extern "C" int q3tts_k_voc_file_tensor(const char* path, const q3tts_vocoder_config* vc, int32_t comp, int32_t which, float* out, int64_t cap, int64_t* n) {
+    if (!path || !vc || !n) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    std::string err;
+    Q3Gguf g;
+    if (g.open(path, err)) return q3_set_err(nullptr, Q3TTS_ERR_IO, err);
+    std::vector<float> a;
+    if (q3_voc_file_array(g, path, *vc, comp, which, a, err)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, err);
+    *n = (int64_t)a.size();
+    if (out) {
+        if (cap < *n) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "output buffer too small");
+        memcpy(out, a.data(), a.size() * 4);
+    }
+    return Q3TTS_OK;
+}
 
 extern "C" int q3tts_k_gguf_read(const char* path, const char* tensor, float* out, int64_t cap, int64_t* nelem, int64_t* dims4, int32_t* ggml_type) {
     if (!path || !tensor || !nelem) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");

@@ -81,3 +81,27 @@ int q3_gguf_to_bf16(const Q3GgufTensor& t, uint16_t* dst, std::string& err);
 int q3_npy_load_f32(const std::string& path, std::vector<float>& out, std::vector<size_t>& shape, std::string& err);
 // the same header checks, shape only (the data is not read)
 int q3_npy_shape(const std::string& path, std::vector<size_t>& shape, std::string& err);
+
+// ---- the vocoder's weights file qwen3_tts_vocoder.gguf -------------------------------------------------------------------
+// Tensor names and layouts are the state_dict keys and PyTorch layouts of the model family's module (transformers' Qwen3OmniMoeCode2Wav)
+// plus codebook.{q}.weight and pre_conv.conv.*; every relayout to the device's arrays happens here, on the host, and the vocoder's one
+// creation path (q3_voc_create) takes each array either from the seeded generator or from q3_voc_file_array.
+struct q3tts_vocoder_config;
+// tensor ids of the vocoder's synthetic generator (oracle/q3_oracle_vocoder.c): component, tensor of the component
+enum { VC_CODEBOOK = 0, VC_PRE = 32, VC_TFM = 40, VC_FINAL_NORM = 60, VC_UP = 64, VC_DEC_IN = 72, VC_BLK = 80, VC_OUT = 120 };
+enum { VW_W = 0, VW_B = 1, VW_IN_NORM = 2, VW_Q = 3, VW_K = 4, VW_V = 5, VW_O = 6, VW_LS_ATTN = 7, VW_POST_NORM = 8, VW_GATE = 9,
+       VW_UP = 10, VW_DOWN = 11, VW_LS_MLP = 12, VW_DW_W = 13, VW_DW_B = 14, VW_LN_W = 15, VW_LN_B = 16, VW_PW1 = 17, VW_PW1_B = 18,
+       VW_PW2 = 19, VW_PW2_B = 20, VW_GAMMA = 21, VW_ALPHA = 22, VW_BETA = 23, VW_W2 = 24, VW_B2 = 25, VW_ALPHA2 = 26, VW_BETA2 = 27 };
+#define Q3_VOC_FILE_NAME "qwen3_tts_vocoder.gguf"
+// wdir/qwen3_tts_vocoder.gguf (the quant directory), else the same name in wdir's parent (the model directory); "" when neither exists
+std::string q3_voc_file_find(const std::string& wdir);
+// The three calls below return 0, or -1 with the reason in err (it names `file` and the tensor or key).
+// every field of *vc the metadata states (layer_scale_init is left alone), cross-checked against the shapes of every tensor
+int q3_voc_file_config(const Q3Gguf& g, const std::string& file, q3tts_vocoder_config* vc, std::string& err);
+// what q3tts_engine_create refuses before it touches the device: metadata that disagrees with vc, a missing tensor, a shape that
+// disagrees with vc, an unsupported tensor type, a value that is not finite
+int q3_voc_file_check(const Q3Gguf& g, const std::string& file, const q3tts_vocoder_config& vc, std::string& err);
+// the array the device holds for generator id (comp, which), as f32 in device layout: matrices, convolutions and codebooks rounded to
+// nearest-even bf16 (a BF16 source passes bit for bit), vectors as stored, a SnakeBeta id evaluated in double (exp(alpha),
+// 1 / (exp(beta) + 1e-9)) like the generator's
+int q3_voc_file_array(const Q3Gguf& g, const std::string& file, const q3tts_vocoder_config& vc, int comp, int which, std::vector<float>& out, std::string& err);

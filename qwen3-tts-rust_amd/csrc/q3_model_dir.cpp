@@ -269,8 +269,18 @@ extern "C" int q3tts_config_from_model_dir(const char* model_dir, const char* qu
     q3tts_model_config m = cfg->model;  // cfg itself is written only on success
     const int rc = from_dir(dir, &m, f);
     if (rc != Q3TTS_OK) return done(rc);
+    // the vocoder's shape from its own file, found by the engine's rule (q3_voc_file_find); without one the block is left alone
+    q3tts_vocoder_config vc = cfg->vocoder;
+    const std::string vfile = cfg->with_vocoder ? q3_voc_file_find(dir) : std::string();
+    if (!vfile.empty()) {
+        Q3Gguf g;
+        std::string er;
+        if (g.open(vfile, er)) return done(f.set(Q3TTS_ERR_IO, er));
+        if (q3_voc_file_config(g, vfile, &vc, er)) return done(f.set(Q3TTS_ERR_INVALID, er));
+    }
     memcpy(path_buf, dir.c_str(), dir.size() + 1);
     cfg->model = m;
+    cfg->vocoder = vc;
     cfg->weights_path = path_buf;
     return done(Q3TTS_OK);
 }

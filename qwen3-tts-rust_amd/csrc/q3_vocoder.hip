@@ -18,16 +18,13 @@
 #include <vector>
 
 #include "q3_engine.h"
+#include "q3_gguf.h"  // the generator's tensor ids VC_* / VW_* and the vocoder's weights file
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #define VOC_MAX_NS 64   // slots per batched call
 #define VOC_FCAP 4      // frames per slot per call (the reference's 4-frame chunk: src/tts/engine.rs:509-512)
 
-enum { VC_CODEBOOK = 0, VC_PRE = 32, VC_TFM = 40, VC_FINAL_NORM = 60, VC_UP = 64, VC_DEC_IN = 72, VC_BLK = 80, VC_OUT = 120 };
-enum { VW_W = 0, VW_B = 1, VW_IN_NORM = 2, VW_Q = 3, VW_K = 4, VW_V = 5, VW_O = 6, VW_LS_ATTN = 7, VW_POST_NORM = 8, VW_GATE = 9,
-       VW_UP = 10, VW_DOWN = 11, VW_LS_MLP = 12, VW_DW_W = 13, VW_DW_B = 14, VW_LN_W = 15, VW_LN_B = 16, VW_PW1 = 17, VW_PW1_B = 18,
-       VW_PW2 = 19, VW_PW2_B = 20, VW_GAMMA = 21, VW_ALPHA = 22, VW_BETA = 23, VW_W2 = 24, VW_B2 = 25, VW_ALPHA2 = 26, VW_BETA2 = 27 };
 #define VTID(l, w) Q3_TID(Q3G_VOC, l, w)
 
 struct VCall {  // passed by value to the kernels of one batched call
@@ -105,6 +102,7 @@ struct Q3Voc {
     std::map<VCallKey, hipGraphExec_t> call_graphs;  // one captured call per (slots, frames, launch switches): voc_call
     std::set<VCallKey> call_seen;
     std::vector<void*> allocs;
+    const Q3Gguf* file = nullptr; std::string file_name;  // q3_voc_create only: the weights file its arrays come from (nullptr: the generator)
 };
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1339,9 +1337,36 @@ static int valloc(q3tts_engine* e, Q3Voc* v, T** p, size_t n) {
 }
 #define VTRY(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return rc__; } while (0)
 
-static int gen_vec(q3tts_engine* e, Q3Voc* v, float** p, uint32_t tid, size_t n, float base, float std) {
+// The weights' two sources. Each gen_* below allocates one device array and fills it either from the seeded generator (id (comp, which),
+// as the oracle's) or, with a weights file, from q3_voc_file_array's host array for the same id: already in device layout and rounded
+// like the generator's, so everything q3_voc_create derives from these arrays (fused rows, tiled copies) cannot tell the sources apart.
+static int file_array(q3tts_engine* e, Q3Voc* v, int comp, int which, size_t n, std::vector<float>& a) {
+    std::string err;
+    if (q3_voc_file_array(*v->file, v->file_name, v->c, comp, which, a, err)) return q3_set_err(e, Q3TTS_ERR_INVALID, err);
+    if (a.size() != n) return q3_set_err(e, Q3TTS_ERR_INVALID, v->file_name + ": tensor id (" + std::to_string(comp) + ", " + std::to_string(which) + ") has " + std::to_string(a.size()) + " elements, the vocoder needs " + std::to_string(n));
+    return Q3TTS_OK;
+}
+static int gen_vec(q3tts_engine* e, Q3Voc* v, float** p, int comp, int which, size_t n, float base, float std) {
     VTRY(valloc(e, v, p, n));
-    q3_launch_fill_f32(*p, n, e->cfg.synth_seed, tid, base, std / Q3_IH4_STD, 0, e->stream);
+    if (v->file) {
+        std::vector<float> a;
+        VTRY(file_array(e, v, comp, which, n, a));
+        Q3_HIP(e, hipMemcpy(*p, a.data(), n * 4, hipMemcpyHostToDevice));  // (a is a local: synchronous copy)
+        return Q3TTS_OK;
+    }
+    q3_launch_fill_f32(*p, n, e->cfg.synth_seed, VTID(comp, which), base, std / Q3_IH4_STD, 0, e->stream);
+    return Q3TTS_OK;
+}
+// an f32 array of bf16-representable values (the codebook tables, the output convolution's weights)
+static int gen_f32_rounded(q3tts_engine* e, Q3Voc* v, float** p, int comp, int which, size_t n, float std) {
+    VTRY(valloc(e, v, p, n));
+    if (v->file) {
+        std::vector<float> a;
+        VTRY(file_array(e, v, comp, which, n, a));
+        Q3_HIP(e, hipMemcpy(*p, a.data(), n * 4, hipMemcpyHostToDevice));
+        return Q3TTS_OK;
+    }
+    q3_launch_fill_f32(*p, n, e->cfg.synth_seed, VTID(comp, which), 0.0f, std / Q3_IH4_STD, 1, e->stream);
     return Q3TTS_OK;
 }
 __global__ void k_fill_bf16(uint16_t* dst, size_t n, uint64_t seed, uint32_t tid, float scale) {
@@ -1352,20 +1377,33 @@ static int gen_conv(q3tts_engine* e, Q3Voc* v, VConv* c, int comp, int ww, int w
     c->ntap = ntap; c->dil = dil; c->cin = cin; c->nout = nout; c->bias_n = bias_n;
     const size_t n = (size_t)ntap * nout * cin;
     VTRY(valloc(e, v, &c->w, n));
-    const float scale = (gain / sqrtf((float)(ntap * cin))) / Q3_IH4_STD;
-    hipLaunchKernelGGL(k_fill_bf16, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, e->stream, c->w, n,
-                       e->cfg.synth_seed, VTID(comp, ww), scale);
+    if (v->file) {  // the file's values arrive rounded to bf16 in f32: their upper halves are the bf16 bits
+        std::vector<float> a;
+        VTRY(file_array(e, v, comp, ww, n, a));
+        std::vector<uint16_t> h(n);
+        for (size_t i = 0; i < n; ++i) { uint32_t u; memcpy(&u, &a[i], 4); h[i] = (uint16_t)(u >> 16); }
+        Q3_HIP(e, hipMemcpy(c->w, h.data(), n * 2, hipMemcpyHostToDevice));
+    } else {
+        const float scale = (gain / sqrtf((float)(ntap * cin))) / Q3_IH4_STD;
+        hipLaunchKernelGGL(k_fill_bf16, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)), dim3(256), 0, e->stream, c->w, n,
+                           e->cfg.synth_seed, VTID(comp, ww), scale);
+    }
     c->b = nullptr;
-    if (bias_n) VTRY(gen_vec(e, v, &c->b, VTID(comp, wb), bias_n, 0.0f, 0.02f));
+    if (bias_n) VTRY(gen_vec(e, v, &c->b, comp, wb, bias_n, 0.0f, 0.02f));
     return Q3TTS_OK;
 }
 // SnakeBeta parameters: exp() evaluated in double on the host (same as the oracle)
-static int gen_snake(q3tts_engine* e, Q3Voc* v, uint32_t ta, uint32_t tb, int C, float** ea, float** ib) {
+static int gen_snake(q3tts_engine* e, Q3Voc* v, int comp, int wa, int wb, int C, float** ea, float** ib) {
     std::vector<float> a(C), b(C);
-    const float scale = 0.1f / Q3_IH4_STD;
-    for (int i = 0; i < C; ++i) {
-        const float al = 0.0f + q3_synth(e->cfg.synth_seed, ta, i, scale), be = 0.0f + q3_synth(e->cfg.synth_seed, tb, i, scale);
-        a[i] = (float)exp((double)al); b[i] = (float)(1.0 / (exp((double)be) + 1e-9));
+    if (v->file) {  // (q3_voc_file_array evaluates the file's logs with the expressions below)
+        VTRY(file_array(e, v, comp, wa, (size_t)C, a)); VTRY(file_array(e, v, comp, wb, (size_t)C, b));
+    } else {
+        const float scale = 0.1f / Q3_IH4_STD;
+        const uint32_t ta = VTID(comp, wa), tb = VTID(comp, wb);
+        for (int i = 0; i < C; ++i) {
+            const float al = 0.0f + q3_synth(e->cfg.synth_seed, ta, i, scale), be = 0.0f + q3_synth(e->cfg.synth_seed, tb, i, scale);
+            a[i] = (float)exp((double)al); b[i] = (float)(1.0 / (exp((double)be) + 1e-9));
+        }
     }
     VTRY(valloc(e, v, ea, (size_t)C)); VTRY(valloc(e, v, ib, (size_t)C));
     Q3_HIP(e, hipMemcpy(*ea, a.data(), (size_t)C * 4, hipMemcpyHostToDevice));  // (a / b are locals: synchronous copies)
@@ -1381,7 +1419,7 @@ static int mk_buf(q3tts_engine* e, Q3Voc* v, VBuf* b, int H, int C, int Tcap, in
 
 int q3_voc_samples_per_frame(const q3tts_engine* e) { return e->voc ? e->voc->spf : 0; }
 
-int q3_voc_create(q3tts_engine* e) {
+int q3_voc_create(q3tts_engine* e, const Q3Gguf* voc_file, const std::string& file) {
     const q3tts_vocoder_config& c = e->cfg.vocoder;
 #define REQ(cond) do { if (!(cond)) return q3_set_err(e, Q3TTS_ERR_INVALID, "vocoder config check failed: " #cond); } while (0)
     REQ(c.n_codebooks >= 1 && c.n_codebooks <= 16 && c.n_codebooks <= e->cfg.model.n_codebooks);
@@ -1395,13 +1433,13 @@ int q3_voc_create(q3tts_engine* e) {
     Q3Voc* v = new Q3Voc();
     e->voc = v;
     v->c = c; v->B = e->B;
+    v->file = voc_file; v->file_name = file;
+    e->voc_source = voc_file ? 2 : 1;
     const int d = c.latent_dim, HH = c.n_head * c.head_dim;
     v->RW = c.sliding_window + VOC_FCAP;
     v->cb.resize(c.n_codebooks);
     for (int q = 0; q < c.n_codebooks; ++q) {
-        VTRY(valloc(e, v, &v->cb[q], (size_t)c.codebook_size * c.codebook_dim));
-        q3_launch_fill_f32(v->cb[q], (size_t)c.codebook_size * c.codebook_dim, e->cfg.synth_seed, VTID(VC_CODEBOOK + q, VW_W), 0.0f,
-                           (1.0f / sqrtf(16.0f)) / Q3_IH4_STD, 1, e->stream);
+        VTRY(gen_f32_rounded(e, v, &v->cb[q], VC_CODEBOOK + q, VW_W, (size_t)c.codebook_size * c.codebook_dim, 1.0f / sqrtf(16.0f)));
     }
     { float** cd = nullptr; VTRY(valloc(e, v, &cd, (size_t)16)); v->cb_dev = (const float**)cd;
       Q3_HIP(e, hipMemcpy((void*)cd, v->cb.data(), sizeof(float*) * c.n_codebooks, hipMemcpyHostToDevice)); }
@@ -1410,10 +1448,10 @@ int q3_voc_create(q3tts_engine* e) {
     v->L.resize(c.n_layer);
     for (int l = 0; l < c.n_layer; ++l) {
         VLayer& y = v->L[l]; const int comp = VC_TFM + l;
-        VTRY(gen_vec(e, v, &y.in_norm, VTID(comp, VW_IN_NORM), d, 1.0f, 0.05f));
-        VTRY(gen_vec(e, v, &y.post_norm, VTID(comp, VW_POST_NORM), d, 1.0f, 0.05f));
-        VTRY(gen_vec(e, v, &y.ls_attn, VTID(comp, VW_LS_ATTN), d, c.layer_scale_init, 0.1f * c.layer_scale_init));
-        VTRY(gen_vec(e, v, &y.ls_mlp, VTID(comp, VW_LS_MLP), d, c.layer_scale_init, 0.1f * c.layer_scale_init));
+        VTRY(gen_vec(e, v, &y.in_norm, comp, VW_IN_NORM, d, 1.0f, 0.05f));
+        VTRY(gen_vec(e, v, &y.post_norm, comp, VW_POST_NORM, d, 1.0f, 0.05f));
+        VTRY(gen_vec(e, v, &y.ls_attn, comp, VW_LS_ATTN, d, c.layer_scale_init, 0.1f * c.layer_scale_init));
+        VTRY(gen_vec(e, v, &y.ls_mlp, comp, VW_LS_MLP, d, c.layer_scale_init, 0.1f * c.layer_scale_init));
         VTRY(gen_conv(e, v, &y.q, comp, VW_Q, 0, 1, 1, d, HH, 0, 1.0f)); VTRY(gen_conv(e, v, &y.k, comp, VW_K, 0, 1, 1, d, HH, 0, 1.0f));
         VTRY(gen_conv(e, v, &y.v, comp, VW_V, 0, 1, 1, d, HH, 0, 1.0f)); VTRY(gen_conv(e, v, &y.o, comp, VW_O, 0, 1, 1, HH, d, 0, 1.0f));
         VTRY(gen_conv(e, v, &y.gate, comp, VW_GATE, 0, 1, 1, d, c.d_ffn, 0, 1.0f)); VTRY(gen_conv(e, v, &y.up, comp, VW_UP, 0, 1, 1, d, c.d_ffn, 0, 1.0f));
@@ -1458,7 +1496,7 @@ int q3_voc_create(q3tts_engine* e) {
         VTRY(valloc(e, v, &v->rope, tab.size()));
         Q3_HIP(e, hipMemcpy(v->rope, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
     }
-    VTRY(gen_vec(e, v, &v->final_norm, VTID(VC_FINAL_NORM, VW_W), d, 1.0f, 0.05f));
+    VTRY(gen_vec(e, v, &v->final_norm, VC_FINAL_NORM, VW_W, d, 1.0f, 0.05f));
     int rows = VOC_FCAP;  // rows per slot at the current stage
     v->spf = 1;
     v->U.resize(c.n_upsample);
@@ -1467,8 +1505,8 @@ int q3_voc_create(q3tts_engine* e) {
         VTRY(gen_conv(e, v, &p.ct, comp, VW_W, VW_B, 1, 1, d, r * d, d, 1.0f));
         rows *= r;
         VTRY(mk_buf(e, v, &p.dw_in, 6, d, rows));
-        VTRY(gen_vec(e, v, &p.dw_w, VTID(comp, VW_DW_W), (size_t)7 * d, 0.0f, 0.3f)); VTRY(gen_vec(e, v, &p.dw_b, VTID(comp, VW_DW_B), d, 0.0f, 0.02f));
-        VTRY(gen_vec(e, v, &p.ln_w, VTID(comp, VW_LN_W), d, 1.0f, 0.05f)); VTRY(gen_vec(e, v, &p.ln_b, VTID(comp, VW_LN_B), d, 0.0f, 0.02f));
+        VTRY(gen_vec(e, v, &p.dw_w, comp, VW_DW_W, (size_t)7 * d, 0.0f, 0.3f)); VTRY(gen_vec(e, v, &p.dw_b, comp, VW_DW_B, d, 0.0f, 0.02f));
+        VTRY(gen_vec(e, v, &p.ln_w, comp, VW_LN_W, d, 1.0f, 0.05f)); VTRY(gen_vec(e, v, &p.ln_b, comp, VW_LN_B, d, 0.0f, 0.02f));
         VTRY(gen_conv(e, v, &p.pw1, comp, VW_PW1, VW_PW1_B, 1, 1, d, 4 * d, 4 * d, 1.0f));
         VTRY(gen_conv(e, v, &p.pw2, comp, VW_PW2, VW_PW2_B, 1, 1, 4 * d, d, d, 1.0f));
         if (d % 256 == 0) {  // tiled copies for k_bgemm (K = d and 4 d, N = r d, 4 d, d: all multiples of 32)
@@ -1479,7 +1517,7 @@ int q3_voc_create(q3tts_engine* e) {
             f.dst = p.pw1_t; f.N = 4 * d; f.K = d; f.rows = 4 * d; f.src_a = p.pw1.w; q3_launch_fill_tiled(f, e->stream);
             f.dst = p.pw2_t; f.N = d; f.K = 4 * d; f.rows = d; f.src_a = p.pw2.w; q3_launch_fill_tiled(f, e->stream);
         }
-        VTRY(gen_vec(e, v, &p.gamma, VTID(comp, VW_GAMMA), d, 0.1f, 0.01f));
+        VTRY(gen_vec(e, v, &p.gamma, comp, VW_GAMMA, d, 0.1f, 0.01f));
     }
     VTRY(gen_conv(e, v, &v->dec_in, VC_DEC_IN, VW_W, VW_B, 7, 1, d, c.decoder_dim, c.decoder_dim, 1.0f));
     VTRY(mk_buf(e, v, &v->dec_in_in, 6, d, rows, 1));  // bf16: it only ever feeds the decoder's input convolution
@@ -1488,7 +1526,7 @@ int q3_voc_create(q3tts_engine* e) {
     int ch = c.decoder_dim;
     for (int b = 0; b < c.n_dec_blocks; ++b) {
         VBlk& k = v->Bk[b]; const int comp = VC_BLK + 4 * b, r = c.dec_rates[b]; k.r = r; k.cin = ch; k.cout = ch / 2; v->spf *= r;
-        VTRY(gen_snake(e, v, VTID(comp, VW_ALPHA), VTID(comp, VW_BETA), ch, &k.ea, &k.ib));
+        VTRY(gen_snake(e, v, comp, VW_ALPHA, VW_BETA, ch, &k.ea, &k.ib));
         VTRY(gen_conv(e, v, &k.ct, comp, VW_W, VW_B, 2, 1, ch, r * k.cout, k.cout, 1.0f));
         VTRY(mk_buf(e, v, &k.ct_in, 1, ch, rows, 1));
         rows *= r;
@@ -1496,18 +1534,17 @@ int q3_voc_create(q3tts_engine* e) {
         const int dil[3] = {1, 3, 9};
         for (int u = 0; u < 3; ++u) {
             VRes& s = k.res[u]; const int rc = comp + 1 + u;
-            VTRY(gen_snake(e, v, VTID(rc, VW_ALPHA), VTID(rc, VW_BETA), k.cout, &s.ea, &s.ib));
+            VTRY(gen_snake(e, v, rc, VW_ALPHA, VW_BETA, k.cout, &s.ea, &s.ib));
             VTRY(gen_conv(e, v, &s.c1, rc, VW_W, VW_B, 7, dil[u], k.cout, k.cout, k.cout, 0.5f));
             VTRY(mk_buf(e, v, &s.c1_in, 6 * dil[u], k.cout, rows, 1));
-            VTRY(gen_snake(e, v, VTID(rc, VW_ALPHA2), VTID(rc, VW_BETA2), k.cout, &s.ea2, &s.ib2));
+            VTRY(gen_snake(e, v, rc, VW_ALPHA2, VW_BETA2, k.cout, &s.ea2, &s.ib2));
             VTRY(gen_conv(e, v, &s.c2, rc, VW_W2, VW_B2, 1, 1, k.cout, k.cout, k.cout, 0.5f));
         }
         ch = k.cout;
     }
     v->out_c = ch;
-    VTRY(gen_snake(e, v, VTID(VC_OUT, VW_ALPHA), VTID(VC_OUT, VW_BETA), ch, &v->oea, &v->oib));
-    VTRY(valloc(e, v, &v->out_w, (size_t)7 * ch)); VTRY(gen_vec(e, v, &v->out_b, VTID(VC_OUT, VW_B), 1, 0.0f, 0.02f));
-    q3_launch_fill_f32(v->out_w, (size_t)7 * ch, e->cfg.synth_seed, VTID(VC_OUT, VW_W), 0.0f, (0.1f / sqrtf((float)(7 * ch))) / Q3_IH4_STD, 1, e->stream);
+    VTRY(gen_snake(e, v, VC_OUT, VW_ALPHA, VW_BETA, ch, &v->oea, &v->oib));
+    VTRY(gen_f32_rounded(e, v, &v->out_w, VC_OUT, VW_W, (size_t)7 * ch, 0.1f / sqrtf((float)(7 * ch)))); VTRY(gen_vec(e, v, &v->out_b, VC_OUT, VW_B, 1, 0.0f, 0.02f));
     VTRY(mk_buf(e, v, &v->out_in, 6, ch, rows, 1));
     // transformer scratch [VOC_MAX_NS * VOC_FCAP][.]
     const size_t M = (size_t)VOC_MAX_NS * VOC_FCAP;
@@ -1522,6 +1559,7 @@ int q3_voc_create(q3tts_engine* e) {
     VTRY(valloc(e, v, &v->call_dev, 1));
     Q3_HIP(e, hipHostMalloc((void**)&v->call_host, 16 * sizeof(VCall)));
     Q3_HIP(e, hipStreamSynchronize(e->stream));
+    v->file = nullptr;  // (the caller closes it)
     return Q3TTS_OK;
 }
 

@@ -193,6 +193,7 @@ SYMBOLS = [
     "q3tts_set_speed", "q3tts_get_speed", "q3tts_time_stretch", "q3tts_k_tempo_counts", "q3tts_k_pcm_tempo",
     "q3tts_text_split", "q3tts_long_default_opts", "q3tts_generate_long", "q3tts_long_result_free", "q3tts_pcm_join",
     "q3tts_k_pcm_edges", "q3tts_k_pcm_join",
+    "q3tts_vocoder_config_from_file", "q3tts_get_vocoder_source", "q3tts_k_voc_file_tensor",
 ]
 
 # long documents (include/q3tts.h, "long documents"): break kinds, the join's block length, and the structs field for field
@@ -383,6 +384,9 @@ def load_library(path=None):
     lib.q3tts_k_gguf_meta.argtypes = [C.c_char_p, C.c_char_p, i32p, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int64, C.c_char_p, C.c_int64,
                                       C.POINTER(C.c_int64)]
     lib.q3tts_config_from_model_dir.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(EngineConfig), C.c_char_p, C.c_int32, C.c_char_p, C.c_int32]
+    lib.q3tts_vocoder_config_from_file.argtypes = [C.c_char_p, C.POINTER(VocoderConfig), C.c_char_p, C.c_int32]
+    lib.q3tts_get_vocoder_source.argtypes = [vp, i32p]
+    lib.q3tts_k_voc_file_tensor.argtypes = [C.c_char_p, C.POINTER(VocoderConfig), C.c_int32, C.c_int32, f32p, C.c_int64, C.POINTER(C.c_int64)]
     lib.q3tts_clone_default_config.argtypes = [C.POINTER(CloneConfig)]
     lib.q3tts_clone_default_config.restype = None
     lib.q3tts_clone_init.argtypes = [vp, C.POINTER(CloneConfig)]

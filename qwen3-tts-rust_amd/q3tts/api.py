@@ -137,7 +137,8 @@ class TtsEngine:
             kv_cache: Optional[str] = None):
         """TtsEngine::new(model_dir, quant) (src/tts/engine.rs:84-169). With no config the model's shape comes from the GGUF files of the
         quant directory (q3tts_config_from_model_dir), whatever member of the family it holds; a config given by the caller is used as it
-        is (its shapes must match the files) and is not modified. There is no network here: with no weight container under model_dir the
+        is (its shapes must match the files) and is not modified. The vocoder's trained weights and shape come the same way from
+        qwen3_tts_vocoder.gguf in the quant directory or in model_dir (vocoder_is_synthetic tells whether there was one). There is no network here: with no weight container under model_dir the
         engine uses seeded synthetic weights of the configured (default: 1.7B) shape. max_batch (1..256): the engine's slot count, in
         place of the config's (include/q3tts.h states the memory per slot; 256 slots of the 1.7B shape need n_ctx <= 1024 or so).
         kv_cache: None — a given config's own kv_q8_0 is kept (0, bf16, everywhere else); "bf16" — the Talker's K/V cache in bf16, whatever
@@ -175,6 +176,12 @@ class TtsEngine:
 
     def close(self):
         self._native.close()
+
+    @property
+    def vocoder_is_synthetic(self) -> bool:
+        """True when the vocoder's weights are the seeded synthetic ones (no qwen3_tts_vocoder.gguf beside the model): the PCM is then the
+        output of random filters, not speech. False with trained weights from the file. Meaningless without a vocoder (False)."""
+        return self._native.vocoder_source == 1
 
     def set_max_steps(self, steps: int):
         self.max_steps = steps

@@ -351,6 +351,13 @@ class NativeEngine:
         self._check(self.lib.q3tts_k_prefix_stats(self.h, o), "q3tts_k_prefix_stats")
         return int(o[0]), int(o[1])
 
+    @property
+    def vocoder_source(self):
+        """q3tts_get_vocoder_source: 0 = no vocoder, 1 = seeded synthetic weights, 2 = the file qwen3_tts_vocoder.gguf."""
+        s = C.c_int32(0)
+        self._check(self.lib.q3tts_get_vocoder_source(self.h, C.byref(s)), "q3tts_get_vocoder_source")
+        return int(s.value)
+
     def device_bytes(self):
         """Device bytes the engine's allocator has handed out (q3tts_k_device_bytes)."""
         b = C.c_int64(0)
@@ -1290,6 +1297,34 @@ def config_from_model_dir(model_dir, quant=None, base=None):
         raise _abi.Q3Error(f"q3tts_config_from_model_dir failed ({rc}): {err.value.decode('utf-8', 'replace')}")
     cfg._path_buf = buf  # weights_path points into it
     return cfg
+
+
+def vocoder_config_from_file(path, base=None):
+    """q3tts_vocoder_config_from_file: a copy of the vocoder block `base` (default: q3tts_default_config's) with every field the weights
+    file `path` states, cross-checked against its tensor shapes. Host only."""
+    lib = _abi.load_library()
+    vc = _abi.VocoderConfig.from_buffer_copy(base if base is not None else _abi.default_config().vocoder)
+    err = C.create_string_buffer(1024)
+    rc = lib.q3tts_vocoder_config_from_file(os.fsencode(path), C.byref(vc), err, len(err))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_vocoder_config_from_file failed ({rc}): {err.value.decode('utf-8', 'replace')}")
+    return vc
+
+
+def k_voc_file_tensor(path, vc, comp, which):
+    """q3tts_k_voc_file_tensor: the f32 array (device layout, after rounding) the engine would upload from the vocoder file `path` for the
+    synthetic generator's tensor id (comp, which) at the shape `vc`. Host only."""
+    lib = _abi.load_library()
+    n = C.c_int64(0)
+    p = os.fsencode(path)
+    rc = lib.q3tts_k_voc_file_tensor(p, C.byref(vc), comp, which, None, 0, C.byref(n))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_voc_file_tensor failed ({rc}): {lib.q3tts_last_error(None).decode('utf-8', 'replace')}")
+    out = np.zeros(n.value, dtype=np.float32)
+    rc = lib.q3tts_k_voc_file_tensor(p, C.byref(vc), comp, which, _ptr(out, f32p), out.size, C.byref(n))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_voc_file_tensor failed ({rc}): {lib.q3tts_last_error(None).decode('utf-8', 'replace')}")
+    return out
 
 
 def k_pcm_pack(src, entries, out_n, fmt=0, device=0):

@@ -105,6 +105,8 @@ extern "C" {
                                        err: *mut c_char, err_cap: i32) -> c_int;
     pub fn q3tts_engine_create(cfg: *const q3tts_engine_config, out: *mut *mut q3tts_engine) -> c_int;
     pub fn q3tts_engine_destroy(e: *mut q3tts_engine);
+    // where the vocoder's weights came from: 0 none, 1 seeded synthetic, 2 qwen3_tts_vocoder.gguf beside the model
+    pub fn q3tts_get_vocoder_source(e: *const q3tts_engine, source: *mut i32) -> c_int;
     pub fn q3tts_last_error(e: *const q3tts_engine) -> *const c_char;
     pub fn q3tts_set_sampler(e: *mut q3tts_engine, temperature: c_float, top_k: i32, top_p: c_float, has_seed: i32, seed: u64) -> c_int;
     pub fn q3tts_set_max_steps(e: *mut q3tts_engine, max_steps: i32) -> c_int;
@@ -180,7 +182,8 @@ pub struct TtsEngine { raw: *mut q3tts_engine, sampler: SamplerConfig, max_steps
 impl TtsEngine {
     /// TtsEngine::new(model_dir, quant) — src/tts/engine.rs:84-169. `model_dir/<quant dir>` (src/tts/engine.rs:91-95) holds
     /// qwen3_tts_talker.gguf, qwen3_tts_predictor.gguf and qwen3_assets.gguf (or the NPY assets). Every model dimension comes from those
-    /// files (q3tts_config_from_model_dir), as llama.cpp reads them for the reference: no shape is assumed here.
+    /// files (q3tts_config_from_model_dir), as llama.cpp reads them for the reference: no shape is assumed here. The same call takes the
+    /// vocoder's shape from qwen3_tts_vocoder.gguf when that file lies in the quant directory or in `model_dir`; the engine then loads it.
     pub fn new(model_dir: &str, quant: &str) -> Result<Self, String> {
         let dir = std::ffi::CString::new(model_dir).map_err(|e| e.to_string())?;
         let q = std::ffi::CString::new(quant).map_err(|e| e.to_string())?;
@@ -199,6 +202,13 @@ impl TtsEngine {
             if rc != 0 { return Err(format!("q3tts_engine_create failed ({}): {}", rc, CStr::from_ptr(q3tts_last_error(std::ptr::null())).to_string_lossy())); }
             Ok(Self { raw, sampler: SamplerConfig::default(), max_steps: 512 })
         }
+    }
+    /// true: the vocoder runs on seeded synthetic weights (no qwen3_tts_vocoder.gguf was found), so the PCM is not speech
+    pub fn vocoder_is_synthetic(&self) -> Result<bool, String> {
+        let mut src = 0i32;
+        let rc = unsafe { q3tts_get_vocoder_source(self.raw, &mut src) };
+        self.check(rc, "q3tts_get_vocoder_source")?;
+        Ok(src == 1)
     }
     pub fn set_max_steps(&mut self, steps: usize) { self.max_steps = steps; }
     pub fn set_sampler_config(&mut self, c: SamplerConfig) { self.sampler = c; }
