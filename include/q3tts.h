@@ -828,7 +828,12 @@ int q3tts_k_vocoder_latent(q3tts_engine* e, const int32_t* codes, int32_t n_fram
  * tap is (hist_rows + rows) x channels elements at buf + offset, f32 (dtype 0) or bf16 bits (dtype 1), as plain rows (layout 0) or in
  * the GEMM's A-tiled layout (layout 1: whole 16-row tiles). Names: up<u>.in / .raw / .ln / .gelu / .out (ConvTranspose input, its raw
  * output with the depthwise history, LayerNorm output, GELU output, the stage's result), dec_in.in, b<b>.ct_in, b<b>.o_ct,
- * b<b>.r<u>.c1_in, b<b>.r<u>.z (un-fused path only), b<b>.r<u>.o (u < 2: the last unit's sum is never stored), out.in, pcm. */
+ * b<b>.r<u>.c1_in, b<b>.r<u>.z (un-fused path only), b<b>.r<u>.o (u < 2: the last unit's sum is never stored), out.in, pcm.
+ * Front half (slot 0's rows of the call): emb (the pre-conv's input: the codebook sums behind pre_conv_kernel - 1 history rows), x0 (the
+ * pre-conv's output), per transformer layer l: l<l>.xn (input norm, bf16), l<l>.qkv (q | k | v before RoPE, f32), l<l>.kring / l<l>.vring
+ * (slot 0's whole ring after the attention launch: sliding_window + 4 rows of n_head * head_dim, position p in row p % rows; rotated keys),
+ * l<l>.att (bf16), l<l>.x_att (the residual rows after the attention branch), l<l>.xn2 (post norm, bf16), l<l>.g (SwiGLU output, bf16),
+ * l<l>.x_out (the residual rows after the MLP branch); final.xn (the final norm: f32, or A-tiled bf16 where the up-sampling GEMMs read that). */
 typedef struct q3tts_voc_tap {
     char name[32];
     int32_t dtype, layout, hist_rows, rows, channels, reserved;

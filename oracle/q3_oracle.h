@@ -205,6 +205,8 @@ int32_t q3o_vocoder_stage(q3o_vocoder* v, const int32_t* codes, int32_t n_frames
  * inject_stage by the caller's values before the decode goes on */
 int32_t q3o_vocoder_stage_inject(q3o_vocoder* v, const int32_t* codes, int32_t n_frames, int32_t stage, float* out, int32_t inject_stage,
                                  const float* inject);
+/* n tensors of the front half (ids 1, 2, 5 and 500 + 20 l + k, listed there too) out of one decode that ends after the final norm */
+int32_t q3o_vocoder_stages(q3o_vocoder* v, const int32_t* codes, int32_t n_frames, int32_t n, const int32_t* ids, float* const* outs);
 /* one causal multi-tap convolution as a chain of q3o_mfma_bf16_dot32 in the device's K-step order (no bias): x [(ntap-1)*dil + T][cin] */
 void q3o_vconv_mfma(const uint16_t* x, int32_t T, int32_t cin, const uint16_t* w, int32_t ntap, int32_t dil, int32_t nout, int32_t chunked,
                     float* out, int32_t threads);

@@ -209,12 +209,23 @@ void q3o_vocoder_set_arith_mask(q3o_vocoder* v, uint32_t mask) { (void)v; g_vf32
  *   300 + 20 b + k, decoder block b: k = 0 the transposed convolution's input (after SnakeBeta), 1 its output o, and for unit u = 0..2:
  *     2 + 4 u the unit's convolution input (after SnakeBeta), 3 + 4 u the dilated convolution's output, 4 + 4 u the same after SnakeBeta 2,
  *     5 + 4 u the residual stream o after the unit;   400 the output convolution's input (after SnakeBeta).
+ * Inside the front half (tests/_voc_tfm_ref.py names them; none of these ends the decode):
+ *   5 the codebook sums [T][codebook_dim], the pre-conv's input (1 is its output);
+ *   500 + 20 l + k, transformer layer l: k = 0 the input norm's output [T][d], 1 / 2 / 3 q / k / v before RoPE [T][n_head head_dim], 4 / 5 q / k
+ *     after RoPE, 6 the attention output, 7 the residual rows after the attention branch, 8 the post norm's output, 9 the SwiGLU output
+ *     [T][d_ffn], 10 the residual rows after the MLP branch (2 is the final norm of the last layer's).
  * q3o_vocoder_stage_inject: the tensor at `inject_stage` is REPLACED by the caller's values before the decode goes on (the CPU tests push a
  * deliberately wrong stage output through the rest of the vocoder to see what the PCM checks would have made of it). */
 static int g_stage = 0; static float* g_stage_out = NULL;
 static int g_inject = 0; static const float* g_inject_src = NULL;
-#define STAGE(k, ptr, n) do { if (g_inject == (k) && g_inject_src) memcpy((ptr), g_inject_src, (size_t)(n) * 4); \
-                              if (g_stage == (k) && g_stage_out) memcpy(g_stage_out, (ptr), (size_t)(n) * 4); } while (0)
+/* q3o_vocoder_stages: several front-half tensors out of ONE decode, which ends after the final norm */
+static int g_nstages = 0; static const int32_t* g_stage_ids = NULL; static float* const* g_stage_outs = NULL;
+static void stage_copy(int k, float* ptr, size_t n) {
+    if (g_inject == k && g_inject_src) memcpy(ptr, g_inject_src, n * 4);
+    if (g_stage == k && g_stage_out) memcpy(g_stage_out, ptr, n * 4);
+    for (int i = 0; i < g_nstages; ++i) if (g_stage_ids[i] == k && g_stage_outs[i]) memcpy(g_stage_outs[i], ptr, n * 4);
+}
+#define STAGE(k, ptr, n) stage_copy((k), (ptr), (size_t)(n))
 static float* decode_all(q3o_vocoder* v, int T) {
     const q3o_vocoder_config* c = &v->c;
     const int d = c->latent_dim, H = c->n_head, hd = c->head_dim, HH = H * hd, F = c->d_ffn, W = c->sliding_window;
@@ -230,6 +241,7 @@ static float* decode_all(q3o_vocoder* v, int T) {
     /* V2: causal pre-conv */
     g_vgroup = 0;
     float* x = malloc((size_t)T * d * 4);
+    STAGE(5, e, (size_t)T * c->codebook_dim);
     conv_fwd(&v->pre, e, T, x); free(e);
     STAGE(1, x, (size_t)T * d);
     if (g_stage == 1) { free(x); return NULL; }
@@ -240,8 +252,11 @@ static float* decode_all(q3o_vocoder* v, int T) {
     const int half = hd / 2;
     for (int l = 0; l < c->n_layer; ++l) {
         vlayer* L = &v->L[l];
+        const int sb = 500 + 20 * l;
         rmsnorm_rows(x, T, d, L->in_norm, c->rms_eps, xn);
+        STAGE(sb + 0, xn, (size_t)T * d);
         conv_fwd(&L->q, xn, T, q); conv_fwd(&L->k, xn, T, k); conv_fwd(&L->v, xn, T, vv);
+        STAGE(sb + 1, q, (size_t)T * HH); STAGE(sb + 2, k, (size_t)T * HH); STAGE(sb + 3, vv, (size_t)T * HH);
         for (int t = 0; t < T; ++t)
             for (int h = 0; h < H; ++h)
                 for (int i = 0; i < half; ++i) {
@@ -251,6 +266,7 @@ static float* decode_all(q3o_vocoder* v, int T) {
                     float a = qp[i], b = qp[i + half]; qp[i] = a * cs - b * sn; qp[i + half] = b * cs + a * sn;
                     a = kp[i]; b = kp[i + half]; kp[i] = a * cs - b * sn; kp[i + half] = b * cs + a * sn;
                 }
+        STAGE(sb + 4, q, (size_t)T * HH); STAGE(sb + 5, k, (size_t)T * HH);
         const float scale = 1.0f / sqrtf((float)hd);
         for (int t = 0; t < T; ++t)
             for (int h = 0; h < H; ++h) {
@@ -269,18 +285,23 @@ static float* decode_all(q3o_vocoder* v, int T) {
                     att[(size_t)t * HH + h * hd + i] = o / l;
                 }
             }
+        STAGE(sb + 6, att, (size_t)T * HH);
         conv_fwd(&L->o, att, T, y);
         for (int t = 0; t < T; ++t) for (int i = 0; i < d; ++i) x[(size_t)t * d + i] += L->ls_attn[i] * y[(size_t)t * d + i];
+        STAGE(sb + 7, x, (size_t)T * d);
         rmsnorm_rows(x, T, d, L->post_norm, c->rms_eps, xn);
+        STAGE(sb + 8, xn, (size_t)T * d);
         conv_fwd(&L->gate, xn, T, g); conv_fwd(&L->up, xn, T, u);
         for (size_t i = 0; i < (size_t)T * F; ++i) g[i] = (g[i] / (1.0f + expf(-g[i]))) * u[i];
+        STAGE(sb + 9, g, (size_t)T * F);
         conv_fwd(&L->down, g, T, y);
         for (int t = 0; t < T; ++t) for (int i = 0; i < d; ++i) x[(size_t)t * d + i] += L->ls_mlp[i] * y[(size_t)t * d + i];
+        STAGE(sb + 10, x, (size_t)T * d);
     }
     rmsnorm_rows(x, T, d, v->final_norm, c->rms_eps, xn);
     STAGE(2, xn, (size_t)T * d);
     free(q); free(k); free(vv); free(att); free(y); free(g); free(u); free(x);
-    if (g_stage == 2) { free(xn); return NULL; }
+    if (g_stage == 2 || g_nstages) { free(xn); return NULL; }
     /* V5a: upsample stages */
     g_vgroup = 1;
     float* cur = xn; int Tc = T;
@@ -371,6 +392,14 @@ int32_t q3o_vocoder_stage(q3o_vocoder* v, const int32_t* codes, int32_t n_frames
     g_stage = 0; g_stage_out = NULL;
     free(pcm); free(v->codes); v->codes = keep; v->n_frames = kn;
     return n_frames * v->spf;
+}
+
+/* the same with n front-half tensors (ids 1, 2, 5 and 500 + 20 l + k) copied out of one decode, which ends after the final norm */
+int32_t q3o_vocoder_stages(q3o_vocoder* v, const int32_t* codes, int32_t n_frames, int32_t n, const int32_t* ids, float* const* outs) {
+    g_nstages = n; g_stage_ids = ids; g_stage_outs = outs;
+    const int32_t r = q3o_vocoder_stage(v, codes, n_frames, 0, NULL);
+    g_nstages = 0; g_stage_ids = NULL; g_stage_outs = NULL;
+    return r;
 }
 
 int32_t q3o_vocoder_stage_inject(q3o_vocoder* v, const int32_t* codes, int32_t n_frames, int32_t stage, float* out, int32_t inject_stage,

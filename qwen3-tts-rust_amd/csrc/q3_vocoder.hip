@@ -1778,7 +1778,9 @@ static void voc_embed_pre(q3tts_engine* e, const VLaunch& vl, const VCall& cl, h
     Q3Voc* v = e->voc; const q3tts_vocoder_config& c = v->c;
     hipLaunchKernelGGL(k_voc_embed, dim3(cl.nf, cl.ns), dim3(128), 0, s, v->call_dev, e->codes, e->cfg.max_steps_cap, e->cfg.model.n_codebooks, v->cb_dev,
                        c.n_codebooks, c.codebook_size, c.codebook_dim, v->pre_in.p, v->pre_in.stride(), v->pre_in.H * v->pre_in.C);
+    vtap_buf(v, s, v->pre_in, cl.nf, "emb");
     vgemm(vl, s, v->pre, v->pre_in.rows(), cl.ns, cl.nf, VBuf::flat(v->x, cl.nf, c.latent_dim));
+    vtap(v, s, v->x, VT_F32, cl.nf, c.latent_dim, "x0");
 }
 // V3, one transformer layer on x (rows m = s * nf + t). GEMM-only activations (normed input, attention output, SwiGLU output) are stored as
 // the bf16 they would be rounded to: A-tiled for the decoder's k_bgemm (tfm_bg; 8 K-slices per output, its tile choice never changes a
@@ -1789,17 +1791,28 @@ static int voc_tfm_layer(q3tts_engine* e, const VLaunch& vl, const VCall& cl, hi
     float* kr = v->kring + (size_t)l * v->B * v->RW * HH; float* vr = v->vring + (size_t)l * v->B * v->RW * HH;
     const VRows x = VBuf::flat(v->x, M, d), xnb = VBuf::flat(v->xnb, M, d).as_bf16(), att = VBuf::flat(v->att, M, HH).as_bf16();
     const VRows g = VBuf::flat(v->g, M, c.d_ffn).as_bf16();
+    const VTapKind bk = tiled ? VT_BF16_TILED : VT_BF16;  // taps: slot 0's nf rows (row m = t), the ring rows of slot 0
+    const size_t ring0 = (size_t)cl.slot[0] * v->RW * HH;
     hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, L.in_norm, c.rms_eps, d, v->xnb, tiled ? 2 : 1);
+    vtap(v, s, v->xnb, bk, cl.nf, d, "l%d.xn", l);
     if (tiled) VTRY(vbgemm(e, s, VBg(v->xnb, M, L.qkv_t, d, 3 * HH, Q3_EPI_STORE).to(v->qkv, 3 * HH), "vocoder: qkv GEMM shape"));
     else vgemm(vl, s, L.qkv, xnb, one_slot, M, VBuf::flat(v->qkv, M, 3 * HH));
+    vtap(v, s, v->qkv, VT_F32, cl.nf, 3 * HH, "l%d.qkv", l);
     voc_launch_attn(vl, s, v->call_dev, v, kr, vr, cl.ns, cl.nf, tiled);
+    vtap(v, s, kr + ring0, VT_F32, v->RW, HH, "l%d.kring", l);
+    vtap(v, s, vr + ring0, VT_F32, v->RW, HH, "l%d.vring", l);
+    vtap(v, s, v->att, bk, cl.nf, HH, "l%d.att", l);
     if (tiled) VTRY(vbgemm(e, s, VBg(v->att, M, L.o_t, HH, d, Q3_EPI_RESID).to(v->x, d).scaled(L.ls_attn), "vocoder: o GEMM shape"));
     else vgemm(vl, s, L.o, att, one_slot, M, x, VEPI_SCALE_ADD, VOpt().layer_scale(L.ls_attn, d));
+    vtap(v, s, v->x, VT_F32, cl.nf, d, "l%d.x_att", l);
     hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, L.post_norm, c.rms_eps, d, v->xnb, tiled ? 2 : 1);
+    vtap(v, s, v->xnb, bk, cl.nf, d, "l%d.xn2", l);
     if (tiled) VTRY(vbgemm(e, s, VBg(v->xnb, M, L.gu_t, d, 2 * c.d_ffn, Q3_EPI_SWIGLU).to_tiled(v->g), "vocoder: gate/up GEMM shape"));
     else vgemm(vl, s, L.gu, xnb, one_slot, M, g, VEPI_SWIGLU);  // gate | up in one launch, SwiGLU in the epilogue
+    vtap(v, s, v->g, bk, cl.nf, c.d_ffn, "l%d.g", l);
     if (tiled) VTRY(vbgemm(e, s, VBg(v->g, M, L.down_t, c.d_ffn, d, Q3_EPI_RESID).to(v->x, d).scaled(L.ls_mlp), "vocoder: down GEMM shape"));
     else vgemm(vl, s, L.down, g, one_slot, M, x, VEPI_SCALE_ADD, VOpt().layer_scale(L.ls_mlp, d));
+    vtap(v, s, v->x, VT_F32, cl.nf, d, "l%d.x_out", l);
     return Q3TTS_OK;
 }
 // V5a, one up-sampling stage: ConvTranspose ([T][r*d] == [T*r][d]) into dw_in's rows, depthwise conv + LayerNorm -> t1, pointwise GELU MLP
@@ -1895,6 +1908,7 @@ static int voc_call_body(q3tts_engine* e, const VLaunch& vl, const VCall& cl, hi
     for (int l = 0; l < c.n_layer; ++l) VTRY(voc_tfm_layer(e, vl, cl, s, l));
     // final norm: f32 rows xn for vgemm, A-tiled bf16 xnb for k_bgemm
     hipLaunchKernelGGL(k_voc_rmsnorm, dim3(M), dim3(64), 0, s, v->x, v->final_norm, c.rms_eps, d, v->up_bg ? v->xnb : v->xn, v->up_bg ? 2 : 0);
+    vtap(v, s, v->up_bg ? (const void*)v->xnb : (const void*)v->xn, v->up_bg ? VT_BF16_TILED : VT_F32, nf, d, "final.xn");
     VRows cur = VBuf::flat(v->xn, nf, d); int T = nf;  // the rows the next stage reads: T per slot
     for (size_t ui = 0; ui < v->U.size(); ++ui) VTRY(voc_up_stage(e, vl, cl, s, ui, cur, T));
     {   // timing experiment only (results are then garbage): Q3TTS_EXP_VOC_SKIP=2 ends the call here — the launch-bound front end (embedding,

@@ -477,9 +477,11 @@ class NativeEngine:
         return out
 
     def vocoder_taps(self, codes, chunk_frames=0, tap_call=0, buf_bytes=160 << 20):
-        """The convolution half of vocoder call `tap_call` (slot 0 driven as vocoder() drives it; calls of <= 4 frames numbered from 0) as
-        {name: (array[hist_rows + rows][channels], hist_rows)}: f32 taps as float32, bf16 taps as uint16 bits, A-tiled taps untiled
-        (q3tts_k_vocoder_taps; the names are listed in include/q3tts.h)."""
+        """Every tap of vocoder call `tap_call` (slot 0 driven as vocoder() drives it; calls of <= 4 frames numbered from 0; the drive ends
+        after that call): the front half (embedding sum, pre-conv, each transformer layer's stages and slot 0's whole K / V ring, the final
+        norm) and the convolution half, as {name: (array[hist_rows + rows][channels], hist_rows)}: f32 taps as float32, bf16 taps as uint16
+        bits, A-tiled taps untiled (q3tts_k_vocoder_taps; the names are listed in include/q3tts.h). More than 256 taps or buf_bytes is an
+        error, never a cut."""
         c = np.ascontiguousarray(codes, dtype=np.int32)
         buf = np.empty(buf_bytes, dtype=np.uint8)
         recs = (_abi.VocTap * 256)()

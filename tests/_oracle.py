@@ -44,11 +44,23 @@ ATT_STAGE2_TOL = 1.6e-05      # 2 x 8.00e-06 (wide); the issue's ceiling for it 
 # Produced by `python tools/voc_stage_bounds.py` (CPU only, ~4 minutes). The device's bound for a stage is 4 R (VOC_STAGE_MARGIN): it
 # sums the same K in another grouping (K slices, split accumulators), so its error has this scale but not this value, while an
 # indexing error is of order 1 on it. Element-wise f32 roundings, sinf / erff and the bf16 output step are added as stated in _voc_ref.
+# The front half (tests/_voc_tfm_ref.py, tests/test_vocoder_tfm_stages_{cpu,gpu}.py) adds the keys pre / qkv / o / gu / down (the chain of
+# q3o_mfma_bf16_dot32 over the 32-wide K steps, on sqrt(sum_i (x_i w_i)^2)), rmsnorm and attn (the oracle's sequential f32 code on the scales
+# written in _voc_tfm_ref.check_tfm_call), measured over every 4-frame call of sliding_window + 12 frames, rounded up to the printed digits;
+# `python tools/voc_stage_bounds.py tfm` prints them alone (~2 minutes). Shapes without a convolution-half entry share the tiny one's.
 VOC_STAGE_MARGIN = 4.0
 VOC_STAGE_R = {
-    "tiny": {"blk_ct": 1.84e-06, "dec_in": 1.30e-06, "dw_ln": 1.17e-07, "out": 4.35e-07, "pw1": 3.93e-07, "pw2": 6.29e-07, "res_c1": 2.79e-06, "res_c2": 1.05e-06, "up_ct": 3.08e-07},
+    "tiny": {"blk_ct": 1.84e-06, "dec_in": 1.30e-06, "dw_ln": 1.17e-07, "out": 4.35e-07, "pw1": 3.93e-07, "pw2": 6.29e-07, "res_c1": 2.79e-06, "res_c2": 1.05e-06, "up_ct": 3.08e-07,
+             "attn": 5.97e-08, "down": 5.38e-07, "gu": 4.54e-07, "o": 2.88e-07, "pre": 3.98e-07, "qkv": 3.32e-07, "rmsnorm": 2.45e-07},
     "narrow": {"blk_ct": 2.56e-06, "dec_in": 9.05e-07, "dw_ln": 1.17e-07, "out": 5.85e-07, "pw1": 3.93e-07, "pw2": 6.29e-07, "res_c1": 3.13e-06, "res_c2": 1.31e-06, "up_ct": 3.08e-07},
-    "full": {"blk_ct": 3.48e-06, "dec_in": 5.05e-06, "dw_ln": 2.02e-07, "out": 4.99e-07, "pw1": 1.97e-06, "pw2": 4.31e-06, "res_c1": 5.12e-06, "res_c2": 1.95e-06, "up_ct": 1.69e-06},
+    "full": {"blk_ct": 3.48e-06, "dec_in": 5.05e-06, "dw_ln": 2.02e-07, "out": 4.99e-07, "pw1": 1.97e-06, "pw2": 4.31e-06, "res_c1": 5.12e-06, "res_c2": 1.95e-06, "up_ct": 1.69e-06,
+             "attn": 1.56e-07, "down": 4.65e-06, "gu": 2.52e-06, "o": 2.43e-06, "pre": 2.19e-06, "qkv": 2.51e-06, "rmsnorm": 1.13e-06},
+    "hd128": {"attn": 6.58e-08, "down": 1.25e-06, "gu": 9.64e-07, "o": 7.90e-07, "pre": 4.14e-07, "qkv": 9.96e-07, "rmsnorm": 4.63e-07},
+    "hd64t": {"attn": 9.78e-08, "down": 8.03e-07, "gu": 7.36e-07, "o": 7.26e-07, "pre": 4.14e-07, "qkv": 9.96e-07, "rmsnorm": 4.18e-07},
+    "hd96": {"attn": 5.14e-08, "down": 3.71e-07, "gu": 3.15e-07, "o": 3.50e-07, "pre": 3.98e-07, "qkv": 4.47e-07, "rmsnorm": 2.18e-07},
+    "hd48": {"attn": 6.77e-08, "down": 3.93e-07, "gu": 3.56e-07, "o": 3.71e-07, "pre": 3.98e-07, "qkv": 4.47e-07, "rmsnorm": 2.59e-07},
+    "w1": {"attn": 0.00e+00, "down": 4.69e-07, "gu": 2.61e-07, "o": 2.41e-07, "pre": 3.98e-07, "qkv": 3.32e-07, "rmsnorm": 2.15e-07},
+    "w508": {"attn": 5.00e-07, "down": 6.13e-07, "gu": 4.46e-07, "o": 3.95e-07, "pre": 4.44e-07, "qkv": 4.44e-07, "rmsnorm": 3.52e-07},
 }
 
 # The Q8_0 Talker away from O(1) magnitudes (tests/_q8_scales.py, tests/test_q8_scales_{cpu,gpu}.py). W8A8 quantises an activation from the
