@@ -986,7 +986,7 @@ int q3tts_k_prefix_stats(const q3tts_engine* e, int64_t* out2);
  * bound of q3tts_k_device_bytes of the created engine (the tests hold it to that). Needs no GPU. */
 int q3tts_k_engine_footprint(const q3tts_engine_config* cfg, int64_t* bytes);
 /* Device bytes the engine's one allocator has handed out so far: everything that lives as long as the engine (weights, tables, caches,
- * rows, scratch, the vocoder's weights, work buffers and per-slot state). Not counted: what regrows on demand (device-resident PCM, the
+ * rows, scratch, the vocoder's weights, work buffers and per-slot state), and the rows of a session's live documents. Not counted: what regrows on demand (device-resident PCM, the
  * resampler's staging, the time-stretch's rows, voice prefixes, a session's staging buffer) and the weight loaders' temporary staging. */
 int q3tts_k_device_bytes(const q3tts_engine* e, int64_t* bytes);
 /* rand 0.8 StdRng (ChaCha12) stream: seed_from_u64(seed) then n x gen::<f32>() */
@@ -1097,6 +1097,108 @@ int q3tts_k_pcm_edges(int32_t device, const float* src, int32_t rows, int64_t st
                       int32_t iters, float* mean_ms);
 int q3tts_k_pcm_join(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* lens, const int32_t* kinds, const int32_t* edges,
                      const q3tts_join_opts* opts, int32_t rate, float* out, int64_t out_cap, int64_t* plan, int64_t* N, int32_t iters, float* mean_ms);
+
+/* ---- documents in a session: the streaming join --------------------------------------------------------------------
+ * q3tts_generate_long returns when the last segment is done, and is refused while a session is open; a session streams every request's
+ * chunks but a request ends at max_steps. A DOCUMENT is submitted to an open session as segments (ids, a break kind, max_steps: exactly
+ * q3tts_long_segment) and streams in order while later segments still run.
+ *
+ * The bits. The concatenation of all Q3TTS_EV_CHUNK payloads of a document's id is the pcm q3tts_generate_long returns for the same
+ * template, the same voice, the same segments (appended ones included, in order) and the same q3tts_join_opts, with speed_permille = 0
+ * and output_rate = 0: bit for bit, whatever the slot count, `ahead`, the admission order, and whatever plain requests share the
+ * session. In an i16 session the chunks are the Q3TTS_PCM_I16 conversion of that row (k_pcm_pack's, applied after the fade's multiply).
+ * Where the chunk boundaries of a document fall depends on when its segments found slots: only the concatenation is contract.
+ *
+ * Submitting. The template's rules are q3tts_generate_long's: use_engine_sampler = 1 is resolved at entry, seed_i = seed + i over the
+ * GLOBAL segment index, text_stream off, prompt_embd / prompt / prefix NULL. Exactly one of voice (a voice-only desc: the session makes
+ * the prefix as a job of "voices in a session" and releases it when the document ends) and prefix (the caller's, ready or pending) is
+ * given. Everything is copied before the call returns. n_segs is 1..1024 per call (0 allowed with open = 1). The id comes from the
+ * requests' id space. q3tts_session_document_append adds segments to a document submitted with open = 1 and, with close != 0, ends it;
+ * an open document whose segments are all delivered stays open and silent until appended to or closed.
+ * Events, all with the document's id: CHUNK (the last one has is_final = 1 and may be empty); Q3TTS_EV_SEGMENT once per segment, in
+ * order, when the segment's piece (possibly empty) has been fully handed to the ring: n_samples = the segment's index, result = the
+ * segment's own (codes, n_frames, hit_eos; n_samples = the piece's length); DONE once the last segment of a closed document is
+ * delivered: result.n_samples = the total, n_frames the sum, hit_eos = 1 iff every segment ended on EOS, codes NULL, first_chunk_ms
+ * from submit to the first document chunk. q3tts_session_cancel(id) cancels the document: from the moment it returns no further chunk
+ * or SEGMENT event of the id is delivered, every running segment is retired at the next boundary, the final event is CANCELLED, and
+ * the document's rows are freed. A segment that fails by itself (prompt + max_steps > n_ctx) fails the document with that status
+ * (FAILED) at the boundary after; its other segments are cancelled, chunks already delivered stay delivered, other requests and
+ * documents are unaffected.
+ * q3tts_session_document_info (thread-safe): info[0, min(cap, *n_known)) = lo, hi, begin, end, n_frames, hit_eos, n_native, status of the
+ * segments delivered so far, the values q3tts_generate_long reports (out_begin / out_end equal begin / end); *n_known = how many there
+ * are, *n_delivered = the samples handed out so far. This is where a subtitle track reads its times. Readable until the session closes.
+ * Scheduling. Segments are internal session requests behind the prefix: they queue in the session's FIFO behind what is already there
+ * and compete for slots as plain requests do; their own events are not published. Segment j is eligible iff j < head + ahead, head the
+ * first segment not fully delivered: a document holds `ahead` device rows of max_steps_cap x samples per frame f32 (segment j: row j mod
+ * ahead), allocated by the worker at the boundary that accepts it, checked against the free memory first (FAILED with Q3TTS_ERR_OOM, the
+ * message names both numbers), freed at its end. No other boundary allocates, and submitting threads never touch the GPU. A boundary
+ * with document work adds at most two launches (k_doc_scan, k_doc_emit; one more per 64 entries) and no copy: the pieces, and the
+ * documents' edge tables, lie behind the plain requests' chunks in the same staging buffer. The plan of boundary t is made from the
+ * lengths and edges of boundary t - 1 (whose table rode that boundary's copy): a document's chunks trail its segments by one boundary,
+ * and the end of a document takes boundaries that run no frames. A document's emission is clipped to what the staging buffer has left.
+ * Refusals (Q3TTS_ERR_INVALID unless stated; nothing changes): an engine-level speed or output rate is set (Q3TTS_ERR_STATE, as
+ * q3tts_generate_long); join options outside their ranges; ahead outside 0..64; a break kind outside 0..4; both or neither of voice and
+ * prefix; a template with a prompt; append to an unknown, closed or finished document. A document whose delivered length would pass
+ * 2^28 samples fails (FAILED, Q3TTS_ERR_INVALID) at the segment that would pass it.
+ * Not built: speed and output rate for a streamed document, pacing by listener credit, q3tts_node_*, a per-segment
+ * voice, text_stream segments, documents outside a session.
+ *
+ * The rule. Only the head emits: the first segment not yet fully delivered. Of the head it uses n (its valid samples so far), first / last
+ * (the loud-block edges of x[0, n) so far, 2.'s rule), closed (n is final) and e (the piece samples already emitted).
+ *  1. trim = 1 and no loud block yet: nothing is emitted. A closed segment is then an empty piece: the head advances and the segment's
+ *     kind is folded into kmax, exactly as the join does. (trim = 0: a closed segment of 0 samples is the empty piece.)
+ *  2. otherwise lo = max(0, first W - keep) (trim = 0: lo = 0). lo is final from here on.
+ *  3. hi_now = min(n, (last + 1) W + keep) (trim = 0: hi_now = n). It never decreases.
+ *  4. an open segment emits only once hi_now - lo >= 2 fade; from then on the final F is fade. It may emit piece samples
+ *     [e, hi_now - lo - fade): the final fade-out starts at or behind that point, so every emitted sample has its final value.
+ *  5. a closed segment has its final hi, L and F = min(fade, L div 2). It emits [e, L), the fade-out included.
+ *  6. the pause goes out directly in front of the first sample of a non-empty piece when a non-empty piece precedes it:
+ *     pause_ms[kmax] * (rate / 1000) zeros; kmax is final then, because every earlier segment is closed. Never earlier: a pause is not
+ *     emitted before the piece behind it is known to be non-empty.
+ * When the head closes, the next segment becomes head at the same boundary: one boundary may emit the tail of a piece, several whole
+ * pieces and their pauses. What a boundary emits is clipped to the room the staging buffer has left; the rest follows at the next ones.
+ * Segment j may run iff j < head + ahead, and keeps its samples in document row j mod ahead. A delivered length that would pass 2^28
+ * samples is Q3TTS_ERR_INVALID at the segment that would pass it. Where the chunk boundaries of a document fall is not contract; the
+ * concatenation is. i16: k_pcm_pack's conversion of the f32 value, applied after the fade's multiply. */
+typedef struct q3tts_doc_opts { q3tts_join_opts join; int32_t ahead /*0: 8; 1..64*/; int32_t open /*1: more segments follow*/; } q3tts_doc_opts;
+#define Q3TTS_EV_SEGMENT 6
+void q3tts_doc_default_opts(q3tts_doc_opts*);
+int q3tts_session_submit_document(q3tts_session* s, const q3tts_request* tmpl, const q3tts_prompt_desc* voice, q3tts_prefix* prefix,
+                                  const q3tts_long_segment* segs, int32_t n_segs, const q3tts_doc_opts* opts, uint64_t* id);
+int q3tts_session_document_append(q3tts_session* s, uint64_t id, const q3tts_long_segment* segs, int32_t n_segs, int32_t close);
+int q3tts_session_document_info(q3tts_session* s, uint64_t id, q3tts_long_info* info, int32_t cap, int32_t* n_known, int64_t* n_delivered);
+/* Test hook: from now on the worker accepts documents as if the device had at most `bytes` free (the smaller of that and what
+ * hipMemGetInfo reports; < 0: off, the default), so that the Q3TTS_ERR_OOM refusal can be reached on a device that has room. A document's
+ * rows are counted in q3tts_k_device_bytes from the boundary that accepts it to the one that ends it. */
+int q3tts_k_session_doc_mem_cap(q3tts_session* s, int64_t bytes);
+/* The rules of a well-formed document as far as no engine is needed to say them (host only): Q3TTS_ERR_STATE while an engine-level speed
+ * or output rate is set (engine_speed / engine_rate != 0: a streamed document has neither); Q3TTS_ERR_INVALID for NULL opts, join
+ * options outside their ranges, ahead outside 0..64, open outside 0 / 1, n_segs outside 1..1024 (0 allowed with open = 1), a break kind
+ * outside 0..4, both or neither of voice and prefix. msg receives the rule, at most cap - 1 characters (may be NULL). */
+int q3tts_k_doc_rules(const q3tts_doc_opts* opts, const int32_t* kinds, int32_t n_segs, int32_t have_voice, int32_t have_prefix,
+                      int32_t engine_speed, int32_t engine_rate, char* msg, int32_t cap);
+/* One boundary of the host plan (host only). segs [n_segs][5] = n, first, last, closed, kind of every segment as of this boundary
+ * ({INT32_MAX, -1}: no loud block); room: the samples the staging buffer has left; state [7], all zero before the first call, carries the
+ * document between calls (state[0] = head, state[5] = samples delivered). pieces [cap][6] = seg (-1: a run of zeros), the first sample's
+ * offset in the segment's row, its index j0 in the piece, count, the piece's final length L (-1: the segment is open), F; done
+ * [done_cap][5] = seg, lo, hi, begin, end of every segment whose piece (possibly empty) this call has handed out completely — the values
+ * q3tts_generate_long reports. *n_pieces / *n_done are set even when a capacity is too small (then Q3TTS_ERR_INVALID). */
+int q3tts_k_doc_plan(const q3tts_join_opts* opts, int32_t rate, const int32_t* segs, int32_t n_segs, int64_t room, int64_t* state,
+                     int64_t* pieces, int32_t cap, int32_t* n_pieces, int64_t* done, int32_t done_cap, int32_t* n_done);
+/* scan + plan + emit, boundary by boundary, as a session would drive them. src [rows][stride] f32 are the segments' PCM rows, uploaded as
+ * they are (the tests put NaN behind every valid length). sched [rows][sched_stride]: segment i's valid length after each boundary at
+ * which it runs, ascending, sched_n[i] >= 1 entries, the last one final. At a boundary every segment j in [head, head + ahead) that is
+ * not closed takes its next length: one k_doc_scan launch copies the new samples into document row j mod ahead and updates the edges.
+ * The plan is made from this boundary's lengths and edges (lag = 0) or from the previous boundary's (lag = 1, the session's form: the
+ * edges ride the copy of the boundary before), with room = staging - dst0; one k_doc_emit launch per 64 pieces writes the pieces into a
+ * staging buffer of `staging` samples (format 0: f32, 1: i16) at dst0, behind where the plain requests' chunks would lie. out receives
+ * the concatenation (*n_out samples), chunks[b] the samples of boundary b (*n_bounds of them, at most chunk_cap), plan [rows][4] = lo, hi,
+ * begin, end. *bad counts what must not happen: a staging byte outside [dst0, dst0 + chunk) that lost its uploaded value, and with
+ * check_rows != 0 any element of the document rows that differs from "the samples copied so far, the uploaded fill elsewhere". */
+int q3tts_k_doc_stream(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* kinds, const int32_t* sched,
+                       const int32_t* sched_n, int32_t sched_stride, const q3tts_join_opts* opts, int32_t rate, int32_t ahead, int32_t lag,
+                       int64_t staging, int64_t dst0, int32_t format, int32_t check_rows, void* out, int64_t out_cap, int64_t* n_out,
+                       int64_t* chunks, int32_t chunk_cap, int32_t* n_bounds, int64_t* plan, int64_t* bad);
 
 #ifdef __cplusplus
 }

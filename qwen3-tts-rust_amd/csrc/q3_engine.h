@@ -360,6 +360,23 @@ long long q3_join_plan(const int32_t* lens, const int32_t* kinds, const int32_t*
                        long long* plan, Q3JoinSeg* segs, long long* max_span);
 // Q3TTS_OK, or Q3TTS_ERR_INVALID with *msg naming the rule
 int q3_join_opts_rules(const q3tts_join_opts& o, const char** msg);
+// documents in a session (q3_doc.hip): the streaming join's host plan, a pure function. segs[j]: segment j as of the
+// snapshot the plan is made from — n valid samples, first / last the loud-block edges of x[0, n) ({INT32_MAX, -1}: none), closed (n is
+// final), kind. st: the document's state between calls (all zero at the start). One call hands out at most `room` samples: pieces in
+// order (seg -1: `count` zeros; else samples [j0, j0 + count) of segment seg's piece, the first one at row offset src, fades F, final
+// length L or LLONG_MAX while the segment is open; dst is the caller's) and one Q3DocDone per segment whose piece, possibly empty, is
+// now wholly handed out: lo, hi, begin, end as q3_join_plan reports them. Q3TTS_ERR_INVALID: the delivered length would pass 2^28
+// samples at segment st->head (nothing of that piece or pause is handed out).
+struct Q3DocSegNow { int32_t n, first, last, closed, kind; };
+struct Q3DocState { long long head, e, pause_left, have_prev, kmax, delivered, begin; };
+struct Q3DocOut { int32_t seg, F; long long src, j0, count, L, dst; };
+struct Q3DocDone { int32_t seg, pad; long long lo, hi, begin, end; };
+int q3_doc_plan(const q3tts_join_opts& o, int rate, const Q3DocSegNow* segs, int n_segs, long long room, Q3DocState* st,
+                std::vector<Q3DocOut>* pieces, std::vector<Q3DocDone>* done);
+// what a well-formed document is as far as no engine is needed to say (q3tts_k_doc_rules is this as a test hook): Q3TTS_OK,
+// Q3TTS_ERR_STATE (an engine-level speed or output rate is set) or Q3TTS_ERR_INVALID, with *msg naming the rule
+int q3_doc_rules(const q3tts_doc_opts& o, const int32_t* kinds, int n_segs, bool have_voice, bool have_prefix, int engine_speed, int engine_rate,
+                 const char** msg);
 // pinned host memory of a result's PCM (q3_generate.hip's pool): what q3tts_result_free gives back
 float* q3_pin_alloc(size_t bytes);
 void q3_pin_free(float* p);

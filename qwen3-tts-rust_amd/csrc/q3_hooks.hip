@@ -1164,6 +1164,106 @@ extern "C" int q3tts_k_pcm_join(int32_t device, const float* src, int32_t rows, 
     return time_launches(iters, [&] { q3_launch_pcm_join(s, (size_t)stride, sg, rows, span, o, nullptr); }, mean_ms);
 }
 
+// The streaming join boundary by boundary (q3_doc.hip): a model of a session in which the rows are the segments' PCM rows
+extern "C" int q3tts_k_doc_stream(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* kinds, const int32_t* sched,
+                                  const int32_t* sched_n, int32_t sched_stride, const q3tts_join_opts* opts, int32_t rate, int32_t ahead, int32_t lag,
+                                  int64_t staging, int64_t dst0, int32_t format, int32_t check_rows, void* out, int64_t out_cap, int64_t* n_out,
+                                  int64_t* chunks, int32_t chunk_cap, int32_t* n_bounds, int64_t* plan, int64_t* bad) {
+    if (!src || !kinds || !sched || !sched_n || !opts || !out || !n_out || !chunks || !n_bounds || !plan || !bad || rows <= 0 || rows > Q3_JOIN_MAX_SEG ||
+        stride <= 0 || stride > (1 << 28) || sched_stride <= 0 || rate < 1000 || ahead < 1 || ahead > Q3_DOC_MAX_ENT || (lag != 0 && lag != 1) ||
+        dst0 < 0 || staging <= dst0 || staging > (1 << 28) || (format != 0 && format != 1) || out_cap < 0 || chunk_cap <= 0)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc stream hook: bad arguments");
+    const char* msg = nullptr;
+    if (q3_join_opts_rules(*opts, &msg) != Q3TTS_OK) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, msg);
+    for (int i = 0; i < rows; ++i) {
+        if (kinds[i] < 0 || kinds[i] > 4 || sched_n[i] < 1 || sched_n[i] > sched_stride) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc stream hook: a break kind or a schedule's length is out of range");
+        for (int k = 0; k < sched_n[i]; ++k) {
+            const long long v = sched[(size_t)i * sched_stride + k];
+            if (v < 0 || v > stride || (k > 0 && v < sched[(size_t)i * sched_stride + k - 1])) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc stream hook: a row's valid lengths must ascend inside its row");
+        }
+    }
+    HK(hipSetDevice(device));
+    const size_t es = format ? 2 : 4, dstride = ((size_t)stride + 3) & ~(size_t)3;
+    std::vector<int32_t> ed((size_t)2 * rows);
+    for (int i = 0; i < rows; ++i) { ed[2 * i] = INT32_MAX; ed[2 * i + 1] = -1; }
+    std::vector<uint32_t> mirror((size_t)ahead * dstride, 0xFFFFFFFFu), back(check_rows ? mirror.size() : 0);
+    // behind the staging samples (rounded up to 4 bytes) the edge table of all rows: with lag = 1 it rides the boundary's copy, as in a session
+    const size_t stg_al = ((size_t)staging + 1) & ~(size_t)1, tab_bytes = sizeof(int32_t) * 2 * (size_t)rows;
+    std::vector<unsigned char> fill(stg_al * es + tab_bytes, 0xA5), got(fill.size());
+    DevBuf s, dr, de, stg;
+    TRY(s.put(src, sizeof(float) * (size_t)rows * stride)); TRY(dr.put(mirror.data(), sizeof(float) * mirror.size()));
+    TRY(de.put(ed.data(), sizeof(int32_t) * ed.size())); TRY(stg.alloc(fill.size()));
+    std::vector<int> pos((size_t)rows, -1), n((size_t)rows, 0);
+    std::vector<char> closed((size_t)rows, 0);
+    std::vector<Q3DocSegNow> now((size_t)rows), prev((size_t)rows);
+    for (int i = 0; i < rows; ++i) now[i] = prev[i] = Q3DocSegNow{0, INT32_MAX, -1, 0, kinds[i]};
+    Q3DocState st{};
+    long long total = 0;
+    int nbd = 0;
+    *bad = 0;
+    while (st.head < rows) {
+        if (nbd >= chunk_cap) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc stream hook: more boundaries than chunk_cap");
+        Q3DocScanPack sp{};
+        int ns = 0;
+        for (long long i = st.head; i < std::min<long long>(rows, st.head + ahead); ++i) {
+            if (closed[i]) continue;
+            const int nn = sched[(size_t)i * sched_stride + ++pos[i]];
+            if (pos[i] == sched_n[i] - 1) closed[i] = 1;
+            float* drow = (float*)dr + (size_t)(i % ahead) * dstride;
+            sp.e[ns++] = Q3DocScan{(const float*)s + (size_t)i * stride, drow, (int32_t*)de + 2 * i, n[i], nn, opts->threshold, 0};
+            memcpy(mirror.data() + (size_t)(i % ahead) * dstride + n[i], src + (size_t)i * stride + n[i], sizeof(float) * (size_t)(nn - n[i]));
+            n[i] = nn;
+        }
+        q3_launch_doc_scan(sp, ns, nullptr);
+        HK(hipGetLastError());
+        if (!lag) TRY(de.get(ed.data(), sizeof(int32_t) * ed.size()));
+        if (check_rows) {
+            TRY(dr.get(back.data(), sizeof(float) * back.size()));
+            for (size_t k = 0; k < back.size(); ++k) *bad += back[k] != mirror[k];
+        }
+        if (!lag) for (int i = 0; i < rows; ++i) now[i] = Q3DocSegNow{n[i], ed[2 * i], ed[2 * i + 1], closed[i], kinds[i]};
+        std::vector<Q3DocOut> pc; std::vector<Q3DocDone> dn;
+        const int prc = q3_doc_plan(*opts, rate, lag ? prev.data() : now.data(), rows, staging - dst0, &st, &pc, &dn);
+        if (prc != Q3TTS_OK) return q3_set_err(nullptr, prc, "document: the delivered length would pass 2^28 samples at segment " + std::to_string(st.head));
+        for (const Q3DocDone& d : dn) { int64_t* p = plan + 4 * d.seg; p[0] = d.lo; p[1] = d.hi; p[2] = d.begin; p[3] = d.end; }
+        HK(hipMemcpy(stg.p, fill.data(), fill.size(), hipMemcpyHostToDevice));
+        long long cur = dst0;
+        for (size_t g0 = 0; g0 < pc.size(); g0 += Q3_DOC_MAX_ENT) {
+            Q3DocPiecePack pk{};
+            const int np = (int)std::min<size_t>(pc.size() - g0, Q3_DOC_MAX_ENT);
+            for (int k = 0; k < np; ++k) {
+                const Q3DocOut& p = pc[g0 + k];
+                const float* from = p.seg < 0 ? nullptr : (const float*)dr + (size_t)(p.seg % ahead) * dstride + p.src;
+                pk.e[k] = Q3DocPiece{from, p.j0, p.L, cur, (int32_t)p.count, p.F};
+                cur += p.count;
+            }
+            if (cur > staging) return q3_set_err(nullptr, Q3TTS_ERR_STATE, "doc stream hook: the plan exceeds the staging buffer");
+            q3_launch_doc_emit(pk, np, format, stg.p, nullptr);
+        }
+        if (lag) {  // this boundary's edges, for the next boundary's plan
+            Q3DocPiecePack pk{};
+            pk.e[0] = Q3DocPiece{(const float*)de.p, 0, 0, (long long)(stg_al * es), 2 * rows, -1};
+            q3_launch_doc_emit(pk, 1, format, stg.p, nullptr);
+        }
+        HK(hipGetLastError());
+        TRY(stg.get(got.data(), got.size()));
+        if (lag) {
+            memcpy(ed.data(), got.data() + stg_al * es, tab_bytes);
+            for (int i = 0; i < rows; ++i) now[i] = Q3DocSegNow{n[i], ed[2 * i], ed[2 * i + 1], closed[i], kinds[i]};
+        }
+        prev = now;
+        const long long c = cur - dst0;
+        for (size_t k = 0; k < stg_al * es + (lag ? 0 : tab_bytes); ++k)
+            if ((k < (size_t)dst0 * es || k >= (size_t)cur * es) && got[k] != 0xA5) ++*bad;
+        if (total + c > out_cap) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc stream hook: out is too small");
+        memcpy((char*)out + (size_t)total * es, got.data() + (size_t)dst0 * es, (size_t)c * es);
+        total += c;
+        chunks[nbd++] = c;
+    }
+    *n_out = total; *n_bounds = nbd;
+    return Q3TTS_OK;
+}
+
 extern "C" int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out) {
     if (!out || n < 0) return Q3TTS_ERR_INVALID;
     q3_stdrng_f32(seed, n, out);

@@ -545,3 +545,19 @@ void q3_launch_pcm_tempo(const float* src, size_t stride, float* dst, size_t dst
 struct Q3JoinSeg { long long lo, L, off, gap; int32_t F, pad; };
 void q3_launch_pcm_edges(const float* src, size_t stride, const int32_t* lens, int rows, long long max_len, float threshold, int32_t* edges, hipStream_t s);
 void q3_launch_pcm_join(const float* src, size_t stride, const Q3JoinSeg* segs, int rows, long long max_span, float* dst, hipStream_t s);
+
+// Documents in a session (q3_doc.hip): the streaming form of the two kernels above, entries by value as Q3PcmPack.
+// k_doc_scan: entry j is a running segment whose valid length grew from n_prev to n_now: dst[n_prev, n_now) = src[n_prev, n_now) (nothing at
+// or past n_now is loaded, nothing else is written), and edges[0] / edges[1] (the caller's {INT32_MAX, -1} at the segment's start; NULL:
+// not kept) take every block of Q3_JOIN_W samples that intersects the range, by k_pcm_edges' rules against thr.
+// k_doc_emit: piece j is dst[dst, dst + count) = samples [j0, j0 + count) of a piece of final length L (LLONG_MAX: not known yet, and no
+// sample of the fade-out among them) with fades of F samples, read from src[0, count) (NULL: +0.0f, a pause); i16 as q3_launch_pcm_pack.
+// F < 0: the entry is a table, `count` 32-bit words copied bit for bit from src to the BYTE offset dst (a multiple of 4) of the buffer:
+// a document's edges ride the boundary's copy to the host this way.
+#define Q3_DOC_MAX_ENT 64
+struct Q3DocScan { const float* src; float* dst; int32_t* edges; int32_t n_prev, n_now; float thr; int32_t pad; };
+struct Q3DocScanPack { Q3DocScan e[Q3_DOC_MAX_ENT]; };
+struct Q3DocPiece { const float* src; long long j0, L, dst; int32_t count, F; };
+struct Q3DocPiecePack { Q3DocPiece e[Q3_DOC_MAX_ENT]; };
+void q3_launch_doc_scan(const Q3DocScanPack& ents, int n_ent, hipStream_t s);
+void q3_launch_doc_emit(const Q3DocPiecePack& pcs, int n_pc, int i16, void* dst, hipStream_t s);

@@ -33,6 +33,50 @@ struct SReq {
     // them for embd), r is unused. keep: the prefix this entry fills (a job's, or a keep-voice request's with voice_rows as submitted)
     int kind = 0, voice_rows = 0, n_tok = 0;
     q3tts_prefix* keep = nullptr;
+    // documents (include/q3tts.h, "documents in a session"): segment `seg` of doc, or (seg < 0) the job that makes doc's voice prefix.
+    // Such an entry is internal: its id is in no IdState, so deliver() drops whatever event names it
+    struct Doc* doc = nullptr;
+    int seg = -1;
+};
+
+// One segment of a document (the worker's; append hands new ones over through Doc::incoming)
+struct DocSeg {
+    std::vector<uint32_t> ids;
+    int kind = 0, max_steps = 0;
+    bool fresh = true;    // its document row's edges are not reset yet
+    bool ended = false;   // its request is done: n is final
+    int n = 0;            // valid samples in its document row
+    q3tts_result res{};   // its own result (codes), from finish_slots to its SEGMENT event
+};
+
+// A document. Its segments run as internal requests behind px; their samples are scanned into `ahead` device rows (segment j: row
+// j mod ahead), and the plan (q3_doc_plan) of boundary t is made from the lengths and edges of boundary t - 1, whose table rode that
+// boundary's copy into the staging ring.
+struct Doc {
+    uint64_t id = 0;
+    q3tts_request tmpl{};
+    q3tts_join_opts join{};
+    int ahead = 8;
+    q3tts_prefix* px = nullptr;
+    bool own_px = false;
+    // (mu)
+    std::vector<DocSeg> incoming;         // appended, not yet seen by the worker
+    bool open = false, finished = false;  // more segments may follow; its final event is on its way
+    int n_given = 0;                      // segments submitted so far
+    std::vector<q3tts_long_info> info;    // the delivered segments (q3tts_session_document_info)
+    long long n_delivered = 0;
+    // worker only
+    bool accepted = false, w_open = true, ended = false;
+    int failed = Q3TTS_OK;                // a segment failed by itself, or the document's own refusal: torn down at the next boundary
+    std::vector<DocSeg> segs;
+    int queued = 0;                       // segments [0, queued) are in the FIFO, in a slot or done
+    float* rows = nullptr; int32_t* edges = nullptr; size_t stride = 0, bytes = 0;  // bytes: what e->dev_bytes carries for the rows
+    Q3DocState st{};
+    std::vector<Q3DocSegNow> snap;        // per segment: the latest snapshot whose table has landed
+    struct Pend { int seg, n; bool ended; };
+    std::vector<Pend> pend; int pend_ring = -1; size_t pend_off = 0;  // the snapshot on its way: ring buffer, byte offset of its table
+    bool touch = false, clipped = false;  // a segment's length or end changed at this boundary; the last plan ran out of room
+    long long frames = 0; bool all_eos = true;
 };
 
 // a q3tts_session_clone call waiting for the worker (the caller's stack; mu guards done)
@@ -117,6 +161,12 @@ struct q3tts_session {
     std::condition_variable cv_clone;
     std::vector<q3tts_prefix*> made;     // the prefixes this session created and has not freed
     std::vector<q3tts_prefix*> trash;    // released and no longer named by a queued request: the worker frees them at the next boundary
+    std::map<uint64_t, std::shared_ptr<Doc>> doc_ids;  // every document of this session (kept until close: document_info stays readable)
+    std::vector<std::shared_ptr<Doc>> docs_new;        // submitted, not yet accepted by the worker
+    bool doc_dirty = false;              // a document was submitted, appended to or closed since the worker last looked
+    uint64_t next_internal = 1;          // ids of internal entries: bit 63 set
+    std::atomic<int> docs_waiting{0};    // entries of docs_new: accept_docs takes mu only when there are some
+    std::atomic<long long> doc_mem_cap{-1};  // q3tts_k_session_doc_mem_cap: documents are accepted as if the device had at most this free (< 0: off)
     uint64_t next_id = 1;
     bool stop = false, dead = false;
     bool text_dirty = false;        // q3tts_session_append_text added something the worker has not seen
@@ -129,6 +179,7 @@ struct q3tts_session {
     std::atomic<long long> st_out_us{0}, st_in_us{0}, st_bounds{0};  // q3tts_k_swap_phase_ms: host microseconds in the two phases; boundaries that moved a block
     // worker only
     std::vector<Swapped> out;       // swapped-out requests
+    std::vector<std::shared_ptr<Doc>> docs;  // accepted documents without their final event
     struct Limbo { long long off, bytes; unsigned long long ticket; };
     std::vector<Limbo> limbo;       // blocks nobody owns any more whose last move may still be running on a stream (reap_blocks)
     uint64_t seq = 0;               // chunk boundaries so far
@@ -159,6 +210,10 @@ void deliver(q3tts_session* s, SEv& v, double t) {
     if (v.kind == Q3TTS_EV_PREFIX) {  // a job's only event, or the one in front of a keep-voice request's own (cancelled or not: the store's fate is news)
         if (v.is_final) st.final_ready = true;
         s->ready.push_back(v);
+        return;
+    }
+    if (v.kind == Q3TTS_EV_SEGMENT) {  // a document's segment is out: not a final event; a cancelled document publishes no more of them
+        if (st.cancelled) copy_result_free(v.res); else s->ready.push_back(v);
         return;
     }
     if (st.cancelled) {
@@ -374,6 +429,12 @@ struct Boundary {
     std::vector<int> fin;      // gather_pcm: slots whose utterance ended. finish_slots' copies into their DONE events' codes end at its synchronise
 };
 
+// the documents' phases (below, in front of step)
+void feed_docs(q3tts_session* s);
+void doc_slot_scan(q3tts_session* s, int b, int ns, bool done, std::vector<Q3DocScan>& scans, std::vector<int32_t*>& resets);
+int doc_emit(q3tts_session* s, Boundary& bd, size_t* cur, std::vector<Q3DocPiece>& ents, std::vector<SEv>& evs, std::vector<std::shared_ptr<Doc>>& finished);
+int end_doc(q3tts_session* s, Boundary& bd, const std::shared_ptr<Doc>& dp, int kind, int status, const q3tts_result* res);
+
 // (mu held) id's streamed text; T is copied only when the device lacks some of it (it holds t_up entries)
 void text_now(q3tts_session* s, uint64_t id, int t_up, TextNow& t) {
     auto it = s->ids.find(id);
@@ -409,6 +470,7 @@ void collect(q3tts_session* s, Boundary& bd) {
     bd.cancels.swap(s->cancels);
     bd.trash.swap(s->trash);
     bd.clones.assign(s->clones.begin(), s->clones.end()); s->clones.clear();
+    feed_docs(s);
     // the FIFO's head: a request that names a pending prefix waits, and so does everything behind it; one whose prefix failed
     // fails without a slot; a prefix job takes a free slot for this boundary as a request does
     while (!s->pending.empty()) {
@@ -417,10 +479,11 @@ void collect(q3tts_session* s, Boundary& bd) {
         const int xs = x && x->e == e ? x->state.load(std::memory_order_acquire) : 1;
         if (xs == 0) break;
         if (xs == 1 && nfree <= 0) break;
-        s->ids[f.id].queued = false;
+        const bool own = f.doc == nullptr;  // (a document's entries are internal: no IdState)
+        if (own) s->ids[f.id].queued = false;
         unref_prefix(s, x);
         if (xs < 0) bd.orphans.push_back(std::move(s->pending.front()));
-        else { --nfree; bd.cr_adm.push_back(s->ids[f.id].paced ? s->ids[f.id].credit : kNotPaced); bd.adm.push_back(std::move(s->pending.front())); }
+        else { --nfree; bd.cr_adm.push_back(own && s->ids[f.id].paced ? s->ids[f.id].credit : kNotPaced); bd.adm.push_back(std::move(s->pending.front())); }
         s->pending.pop_front();
     }
     if (s->swap)  // what still waits at the head and could enter a slot: swap_out makes room for it
@@ -441,6 +504,7 @@ int voice_work(q3tts_session* s, Boundary& bd) {
     q3tts_engine* e = s->e;
     for (auto& q : bd.orphans) {
         q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the request names a prefix that failed");
+        if (q->doc) { if (q->doc->failed == Q3TTS_OK) q->doc->failed = Q3TTS_ERR_INVALID; continue; }
         bd.bt.evs.push_back(final_ev(q->id, Q3TTS_EV_FAILED, Q3TTS_ERR_INVALID));
     }
     if (!bd.trash.empty()) {
@@ -622,12 +686,13 @@ int plan_and_admit(q3tts_session* s, Boundary& bd) {
         const int b = as[i];
         if (q->keep) {  // the store is written behind the group's layers on the stream: ready for everything the worker issues from now on
             q->keep->state.store(rcs[i] == Q3TTS_OK ? 1 : rcs[i], std::memory_order_release);
-            bd.bt.evs.push_back(prefix_ev(q->id, rcs[i], q->kind == 1));
+            if (!q->doc) bd.bt.evs.push_back(prefix_ev(q->id, rcs[i], q->kind == 1));
             bd.made_prefix = true;
             std::lock_guard<std::mutex> lk(s->mu);
             maybe_reap(s, q->keep);
         }
         if (q->kind == 1) continue;  // the slot stays free
+        if (rcs[i] != Q3TTS_OK && q->doc) { if (q->doc->failed == Q3TTS_OK) q->doc->failed = rcs[i]; continue; }  // (torn down at the next boundary)
         if (rcs[i] != Q3TTS_OK) { bd.bt.evs.push_back(final_ev(q->id, Q3TTS_EV_FAILED, rcs[i])); continue; }
         SSlot& sl = s->slots[b];
         sl.req = std::move(q); sl.delivered = 0; s->voc_frames[b] = 0;
@@ -696,11 +761,23 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
             if (bd.run[b]) { tb.push_back(b); tn.push_back(q3_voc_samples(e, b)); td.push_back(e->slots_host[b].active ? 0 : 1); }
         TRY(q3_tempo_slots(e, tb.data(), tn.data(), td.data(), (int)tb.size(), vs));
     }
+    std::vector<Q3DocScan> scans; std::vector<int32_t*> resets;
     for (int b = 0; b < e->B; ++b) {
         if (!bd.run[b]) continue;
         SSlot& sl = s->slots[b];
         const bool done = !e->slots_host[b].active;
         const int ns = q3_voc_samples(e, b);
+        if (sl.req->doc && sl.req->doc->ended) {  // (end_doc leaves none behind; should one exist it must not run on to max_steps)
+            TRY(q3_retire_slot(e, b, vs)); free_slot(s, b);
+            Q3_HIP(e, hipStreamSynchronize(e->stream));  // (the staging-half record is rewritten by the next admission)
+            continue;
+        }
+        if (sl.req->doc) {  // a document's segment: scanned into its document row, no chunk of its own
+            if (ns > (int)q3_voc_pcm_stride(e)) return q3_set_err(e, Q3TTS_ERR_STATE, "session: a chunk window exceeds the staging bound");
+            doc_slot_scan(s, b, ns, done, scans, resets);
+            if (done) bd.fin.push_back(b);
+            continue;
+        }
         const int c = q3_emit_count(e, ns, done, sl.delivered);
         if (c < 0 || tot + (size_t)std::max(c, 0) > s->ring_cap || ns > (int)q3_voc_pcm_stride(e))
             return q3_set_err(e, Q3TTS_ERR_STATE, "session: a chunk window exceeds the staging bound");
@@ -716,7 +793,22 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
         if (done) bd.fin.push_back(b);
     }
     const int ne = (int)ents.size(), k = s->ring_next;
-    if (ne > 0) {
+    // documents: at most two launches more, no copy more (the pieces and the edge tables lie behind the plain chunks in the same buffer)
+    std::vector<Q3DocPiece> pieces; std::vector<std::shared_ptr<Doc>> finished;
+    if (!s->docs.empty()) {
+        for (int32_t* p : resets) {  // a segment's first boundary in its row: {INT32_MAX, -1}, by device fills in stream order in front of the scan
+            Q3_HIP(e, hipMemsetD32Async((hipDeviceptr_t)p, INT32_MAX, 1, vs));
+            Q3_HIP(e, hipMemsetD32Async((hipDeviceptr_t)(p + 1), -1, 1, vs));
+        }
+        for (size_t g0 = 0; g0 < scans.size(); g0 += Q3_DOC_MAX_ENT) {
+            Q3DocScanPack sp{};
+            const int n = (int)std::min<size_t>(scans.size() - g0, Q3_DOC_MAX_ENT);
+            for (int i = 0; i < n; ++i) sp.e[i] = scans[g0 + i];
+            q3_launch_doc_scan(sp, n, vs);
+        }
+        TRY(doc_emit(s, bd, &tot, pieces, chunks, finished));
+    }
+    if (ne > 0 || !pieces.empty()) {
         const int rc = take_ring(s, k);
         if (rc) return rc;
         for (int g0 = 0; g0 < ne; g0 += Q3_PCM_MAX_ENT) {
@@ -731,15 +823,27 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
             else if (q3_launch_pcm_resample(q3_pcm_rows(e), q3_pcm_rows_stride(e), pk, src, n, mx, *rs, s->fmt, s->dev, vs) != 0)
                 return q3_set_err(e, Q3TTS_ERR_UNSUPPORTED, "session: the resampler's input span does not fit the LDS");
         }
+        for (size_t g0 = 0; g0 < pieces.size(); g0 += Q3_DOC_MAX_ENT) {
+            Q3DocPiecePack pk{};
+            const int n = (int)std::min<size_t>(pieces.size() - g0, Q3_DOC_MAX_ENT);
+            for (int i = 0; i < n; ++i) pk.e[i] = pieces[g0 + i];
+            q3_launch_doc_emit(pk, n, s->fmt, s->dev, vs);
+        }
+        for (auto& d : s->docs) if (d->touch && d->failed == Q3TTS_OK) { d->pend_ring = k; d->touch = false; }
         Q3_HIP(e, hipGetLastError());
         Q3_HIP(e, hipMemcpyAsync(s->host[k], s->dev, tot * s->es, hipMemcpyDeviceToHost, vs));
         Q3_HIP(e, hipEventRecord(s->ev[k], vs));
         s->inflight[k] = true;
         s->ring_next = (k + 1) % kRing;
         bd.bt.ring = k;
-        for (SEv& v : chunks) if (v.n > 0) v.ring = k;
+        for (SEv& v : chunks) if (v.kind == Q3TTS_EV_CHUNK && v.n > 0) v.ring = k;  // (a SEGMENT event's n is an index: it holds no reference)
     }
     for (SEv& v : chunks) bd.bt.evs.push_back(v);
+    for (auto& d : finished) {  // the last segment of a closed document is out: DONE behind its last chunk, the rows freed
+        q3tts_result r{};
+        r.n_frames = (int32_t)d->frames; r.hit_eos = d->all_eos ? 1 : 0; r.n_samples = (int32_t)d->st.delivered; r.sample_rate = e->cfg.vocoder.sample_rate;
+        TRY(end_doc(s, bd, d, Q3TTS_EV_DONE, Q3TTS_OK, &r));
+    }
     return Q3TTS_OK;
 }
 
@@ -747,6 +851,14 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
 int finish_slots(q3tts_session* s, Boundary& bd) {
     q3tts_engine* e = s->e;
     for (int b : bd.fin) {
+        if (Doc* d = s->slots[b].req->doc) {  // a document's segment: its result waits for the SEGMENT event; the slot is free as any other
+            DocSeg& g = d->segs[s->slots[b].req->seg];
+            if (d->ended || d->failed != Q3TTS_OK) { q3tts_result tmp{}; TRY(q3_codes_back(e, b, &tmp)); Q3_HIP(e, hipStreamSynchronize(e->stream)); q3tts_result_free(&tmp); }
+            else { TRY(q3_codes_back(e, b, &g.res)); g.res.status = Q3TTS_OK; }
+            Q3_HIP(e, hipEventRecord(e->fin_ev[b], e->vstream));  // (behind the scan that read the slot's PCM)
+            free_slot(s, b);
+            continue;
+        }
         SEv v = final_ev(s->slots[b].req->id, Q3TTS_EV_DONE, Q3TTS_OK);
         TRY(q3_codes_back(e, b, &v.res));
         v.res.n_samples = s->slots[b].delivered; v.res.sample_rate = e->out_rate ? e->out_rate : e->cfg.vocoder.sample_rate;
@@ -758,14 +870,258 @@ int finish_slots(q3tts_session* s, Boundary& bd) {
     return Q3TTS_OK;
 }
 
+// ---- documents (include/q3tts.h, "documents in a session") -------------------------------------------------------
+// the table of a document's edges in the staging buffer, in samples of the session's format (2 int32 per row)
+size_t doc_table_samples(const q3tts_session* s, const Doc& d) { return (size_t)d.ahead * 8 / s->es; }
+
+// does a boundary have document work although no slot runs? (the worker does not sleep then)
+bool doc_work(const q3tts_session* s) {
+    for (const auto& d : s->docs) {
+        if (d->failed != Q3TTS_OK || d->pend_ring >= 0 || d->clipped || d->touch) return true;
+        if (!d->w_open && d->st.head >= (long long)d->segs.size()) return true;  // its last event is due
+        if (d->queued < std::min<long long>((long long)d->segs.size(), d->st.head + d->ahead)) return true;  // a segment became eligible
+    }
+    return false;
+}
+
+// 0. new documents: the rows of each, checked against the device's free memory first (the one boundary that allocates for a document)
+int accept_docs(q3tts_session* s, Boundary& bd) {
+    q3tts_engine* e = s->e;
+    std::vector<std::shared_ptr<Doc>> fresh;
+    if (s->docs_waiting.load(std::memory_order_acquire) == 0) return Q3TTS_OK;  // (no document: the boundary is what it was)
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        fresh.swap(s->docs_new);
+        s->docs_waiting.store(0, std::memory_order_release);
+        for (auto& d : fresh) { auto it = s->ids.find(d->id); if (it != s->ids.end()) it->second.queued = false; }
+    }
+    for (auto& d : fresh) {
+        d->stride = ((size_t)e->cfg.max_steps_cap * q3_voc_samples_per_frame(e) + 3) & ~(size_t)3;
+        const size_t need = (size_t)d->ahead * d->stride * sizeof(float) + (size_t)d->ahead * 2 * sizeof(int32_t);
+        size_t free_b = 0, total_b = 0;
+        Q3_HIP(e, hipMemGetInfo(&free_b, &total_b));
+        const long long cap = s->doc_mem_cap.load(std::memory_order_relaxed);
+        if (cap >= 0) free_b = std::min(free_b, (size_t)cap);
+        int rc = Q3TTS_OK;
+        // The edge table rides the staging buffer beside the plain chunks. It is emitted only at a boundary at which one of the document's
+        // segments ran, and a running segment emits no chunk of its own: its slot's share of the buffer (ring_cap / B samples) is unused
+        // then. So a table that fits one slot's share always fits (doc_emit fails the document, not the session, should it ever not).
+        if (doc_table_samples(s, *d) * (size_t)e->B > s->ring_cap)
+            rc = q3_set_err(e, Q3TTS_ERR_INVALID, "document: the edge table of ahead = " + std::to_string(d->ahead) + " rows exceeds one slot's share of the staging buffer");
+        else if (need > free_b || hipMalloc((void**)&d->rows, need) != hipSuccess)
+            rc = q3_set_err(e, Q3TTS_ERR_OOM, "document: its " + std::to_string(d->ahead) + " rows need " + std::to_string(need) + " bytes, the device has " + std::to_string(free_b) + " bytes free");
+        if (rc != Q3TTS_OK) {
+            d->rows = nullptr; d->ended = true;
+            std::lock_guard<std::mutex> lk(s->mu);
+            d->finished = true; d->open = false;
+            if (d->own_px) { d->px->released = true; maybe_reap(s, d->px); }
+            bd.bt.evs.push_back(final_ev(d->id, Q3TTS_EV_FAILED, rc));
+            continue;
+        }
+        d->edges = (int32_t*)(d->rows + (size_t)d->ahead * d->stride);
+        d->bytes = need; e->dev_bytes += need;  // (q3tts_k_device_bytes sees a document's rows while they live)
+        d->accepted = true;
+        s->docs.push_back(d);
+    }
+    return Q3TTS_OK;
+}
+
+// (mu held, collect) appended segments reach the worker, and every segment j < head + ahead that is not queued yet joins the FIFO as an
+// internal request behind the document's prefix
+void feed_docs(q3tts_session* s) {
+    q3tts_engine* e = s->e;
+    s->doc_dirty = false;
+    for (auto& dp : s->docs) {
+        Doc& d = *dp;
+        for (DocSeg& g : d.incoming) { d.segs.push_back(std::move(g)); d.snap.push_back(Q3DocSegNow{0, INT32_MAX, -1, 0, d.segs.back().kind}); }
+        d.incoming.clear();
+        d.w_open = d.open;
+        if (d.failed != Q3TTS_OK) continue;
+        const long long lim = std::min<long long>((long long)d.segs.size(), d.st.head + d.ahead);
+        for (; d.queued < lim; ++d.queued) {
+            const DocSeg& g = d.segs[d.queued];
+            std::unique_ptr<SReq> q(new SReq());
+            q->id = (1ull << 63) | s->next_internal++;
+            q->doc = &d; q->seg = d.queued;
+            q->text = g.ids;
+            q->desc.text_ids = q->text.data(); q->desc.n_text = (int32_t)q->text.size(); q->desc.lang_id = -1; q->desc.spk_id = -1;
+            q->r = d.tmpl;
+            q->r.prompt = &q->desc; q->r.prompt_embd = nullptr; q->r.prefix = d.px; q->r.want_pcm = 1; q->r.text_stream = 0; q->r.text_open = 0;
+            if (g.max_steps) q->r.max_steps = g.max_steps;
+            if (d.tmpl.has_seed) q->r.seed = d.tmpl.seed + (uint64_t)d.queued;
+            if (d.px->e == e) ++d.px->qrefs;
+            s->pending.push_back(std::move(q));
+        }
+    }
+}
+
+// a document leaves: its slots are retired, its queued entries dropped, its rows freed (hipFree waits for the launches that read them), its
+// own prefix released; `kind` is its final event. The caller has made sure no launch of this boundary still needs to be issued for it.
+int end_doc(q3tts_session* s, Boundary& bd, const std::shared_ptr<Doc>& dp, int kind, int status, const q3tts_result* res) {
+    q3tts_engine* e = s->e;
+    Doc& d = *dp;
+    for (int b = 0; b < e->B; ++b)
+        if (s->slots[b].req && s->slots[b].req->doc == &d) {
+            TRY(q3_retire_slot(e, b, e->vstream)); free_slot(s, b);
+            bd.cool[b] = 1; bd.retired = true;
+        }
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        for (auto p = s->pending.begin(); p != s->pending.end();) {
+            if ((*p)->doc != &d || (*p)->kind != 0) { ++p; continue; }
+            unref_prefix(s, (*p)->r.prefix);
+            p = s->pending.erase(p);
+        }
+        d.finished = true; d.open = false;
+        if (d.own_px && !d.px->released) { d.px->released = true; maybe_reap(s, d.px); }
+    }
+    // ... and its segments that collect popped at this very boundary (a cancel and the pop share one hold of mu): they would be admitted
+    // into slots behind the rows' free. Their prefix reference went with the pop; cr_adm and tn_adm stay aligned with adm.
+    for (size_t i = bd.adm.size(); i-- > 0;)
+        if (bd.adm[i] && bd.adm[i]->doc == &d && bd.adm[i]->kind == 0) {  // (null: plan_and_admit moved it into its slot — end_doc from gather_pcm)
+            bd.adm.erase(bd.adm.begin() + i); bd.cr_adm.erase(bd.cr_adm.begin() + i);
+            if (i < bd.tn_adm.size()) bd.tn_adm.erase(bd.tn_adm.begin() + i);
+        }
+    if (d.rows) { Q3_HIP(e, hipFree(d.rows)); e->dev_bytes -= d.bytes; d.bytes = 0; }
+    d.rows = nullptr; d.edges = nullptr;
+    for (DocSeg& g : d.segs) copy_result_free(g.res);
+    d.ended = true; d.pend_ring = -1; d.touch = d.clipped = false;
+    SEv v = final_ev(d.id, kind, status);
+    if (res) { v.res = *res; v.res.status = status; }
+    bd.bt.evs.push_back(v);
+    s->docs.erase(std::remove(s->docs.begin(), s->docs.end(), dp), s->docs.end());
+    return Q3TTS_OK;
+}
+
+// 3a. documents that were cancelled, or that failed at the last boundary (a segment failed by itself, the length limit): torn down here,
+// where slots are retired anyway
+int drop_docs(q3tts_session* s, Boundary& bd) {
+    for (size_t i = 0; i < s->docs.size();) {
+        std::shared_ptr<Doc> d = s->docs[i];
+        const bool cancelled = std::find(bd.cancels.begin(), bd.cancels.end(), d->id) != bd.cancels.end();
+        if (!cancelled && d->failed == Q3TTS_OK) { ++i; continue; }
+        TRY(end_doc(s, bd, d, cancelled ? Q3TTS_EV_CANCELLED : Q3TTS_EV_FAILED, cancelled ? Q3TTS_OK : d->failed, nullptr));
+    }
+    return Q3TTS_OK;
+}
+
+// a running document slot at gather time: no CHUNK of its own; its new samples become a scan entry into the segment's document row
+void doc_slot_scan(q3tts_session* s, int b, int ns, bool done, std::vector<Q3DocScan>& scans, std::vector<int32_t*>& resets) {
+    q3tts_engine* e = s->e;
+    SSlot& sl = s->slots[b];
+    Doc& d = *sl.req->doc;
+    DocSeg& g = d.segs[sl.req->seg];
+    if (d.failed != Q3TTS_OK || d.ended || !d.rows) return;  // (nothing is scanned for a document on its way out)
+    const int row = sl.req->seg % d.ahead;
+    if (g.fresh) { resets.push_back(d.edges + 2 * row); g.fresh = false; }
+    if (ns > g.n) {
+        scans.push_back(Q3DocScan{q3_pcm_rows(e) + (size_t)b * q3_pcm_rows_stride(e), d.rows + (size_t)row * d.stride, d.edges + 2 * row, g.n, ns, d.join.threshold, 0});
+        g.n = ns; d.touch = true;
+    }
+    if (done) { g.ended = true; d.touch = true; }
+    sl.delivered = ns;
+}
+
+// 8a. the documents' part of a boundary. Per document: the snapshot of the last boundary lands (its table rode that boundary's copy;
+// its event is waited for, which a whole chunk of frame steps later costs nothing), q3_doc_plan turns it into pieces clipped to what
+// the staging buffer has left behind the plain requests' chunks and the tables, and the pieces, with this boundary's tables, become
+// entries of ONE k_doc_emit launch (per 64 entries). *cur: the staging samples used so far, in and out.
+int doc_emit(q3tts_session* s, Boundary& bd, size_t* cur, std::vector<Q3DocPiece>& ents, std::vector<SEv>& evs, std::vector<std::shared_ptr<Doc>>& finished) {
+    q3tts_engine* e = s->e;
+    const int rate = e->cfg.vocoder.sample_rate;
+    // the last boundary's snapshots land first (pend_off still names THAT boundary's table: the plain chunks in front of it differ in size)
+    for (auto& dp : s->docs) {
+        Doc& d = *dp;
+        if (d.failed != Q3TTS_OK || d.pend_ring < 0) continue;
+        const hipError_t q = hipEventSynchronize(s->ev[d.pend_ring]);
+        if (q != hipSuccess) return q3_set_err(e, Q3TTS_ERR_DEVICE, std::string("session: a document's table: ") + hipGetErrorString(q));
+        const int32_t* tab = (const int32_t*)((const char*)s->host[d.pend_ring] + d.pend_off);
+        for (const Doc::Pend& p : d.pend) {
+            const int row = p.seg % d.ahead;
+            d.snap[p.seg] = Q3DocSegNow{p.n, tab[2 * row], tab[2 * row + 1], p.ended ? 1 : 0, d.segs[p.seg].kind};
+        }
+        d.pend_ring = -1; d.pend.clear();
+    }
+    // this boundary's tables: 4-byte aligned, directly behind the plain chunks
+    for (auto& dp : s->docs) {
+        Doc& d = *dp;
+        if (d.failed != Q3TTS_OK || !d.touch) continue;
+        const size_t at = *cur + (s->es == 2 ? (*cur & 1) : 0);
+        if (at + doc_table_samples(s, d) > s->ring_cap) {  // (accept_docs states why this does not happen; the document fails, the session goes on)
+            q3_set_err(e, Q3TTS_ERR_STATE, "document: its edge table exceeds the staging bound");
+            d.failed = Q3TTS_ERR_STATE;
+            continue;
+        }
+        *cur = at;
+        ents.push_back(Q3DocPiece{(const float*)d.edges, 0, 0, (long long)(*cur * s->es), 2 * d.ahead, -1});
+        d.pend_off = *cur * s->es;
+        *cur += doc_table_samples(s, d);
+    }
+    for (auto& dp : s->docs) {
+        Doc& d = *dp;
+        if (d.failed != Q3TTS_OK) continue;
+        std::vector<Q3DocOut> pc; std::vector<Q3DocDone> dn;
+        const long long room = (long long)(s->ring_cap - *cur);
+        const int prc = q3_doc_plan(d.join, rate, d.snap.data(), (int)d.snap.size(), room, &d.st, &pc, &dn);
+        if (prc != Q3TTS_OK) {
+            q3_set_err(e, prc, "document: the delivered length would pass 2^28 samples at segment " + std::to_string(d.st.head));
+            d.failed = prc;
+            continue;
+        }
+        const size_t c0 = *cur;
+        for (const Q3DocOut& p : pc) {
+            const float* from = p.seg < 0 ? nullptr : d.rows + (size_t)(p.seg % d.ahead) * d.stride + p.src;
+            ents.push_back(Q3DocPiece{from, p.j0, p.L, (long long)*cur, (int32_t)p.count, p.F});
+            *cur += (size_t)p.count;
+        }
+        d.clipped = *cur >= s->ring_cap && d.st.head < (long long)d.segs.size();
+        const bool last = !d.w_open && d.st.head >= (long long)d.segs.size();
+        if (*cur > c0 || last) {
+            SEv v; v.id = d.id; v.kind = Q3TTS_EV_CHUNK; v.n = (int)(*cur - c0); v.is_final = last ? 1 : 0; v.off = c0;
+            evs.push_back(v);
+        }
+        {
+            std::lock_guard<std::mutex> lk(s->mu);
+            d.n_delivered = d.st.delivered;
+            for (const Q3DocDone& x : dn) {
+                DocSeg& g = d.segs[x.seg];
+                q3tts_long_info f{};
+                f.status = g.res.status; f.n_frames = g.res.n_frames; f.hit_eos = g.res.hit_eos; f.n_native = g.n;
+                f.lo = x.lo; f.hi = x.hi; f.begin = f.out_begin = x.begin; f.end = f.out_end = x.end;
+                d.info.push_back(f);
+            }
+        }
+        for (const Q3DocDone& x : dn) {
+            DocSeg& g = d.segs[x.seg];
+            SEv v; v.id = d.id; v.kind = Q3TTS_EV_SEGMENT; v.n = x.seg; v.res = g.res;
+            v.res.n_samples = (int32_t)(x.end - x.begin); v.res.sample_rate = rate;
+            g.res = q3tts_result{};  // (the codes went with the event)
+            d.frames += v.res.n_frames; d.all_eos = d.all_eos && v.res.hit_eos;
+            evs.push_back(v);
+        }
+        if (last) finished.push_back(dp);
+    }
+    // this boundary's snapshots: on their way with this boundary's copy
+    for (auto& dp : s->docs) {
+        Doc& d = *dp;
+        if (d.failed != Q3TTS_OK || !d.touch) continue;
+        d.pend.clear();
+        for (long long j = d.st.head; j < std::min<long long>((long long)d.segs.size(), d.st.head + d.ahead); ++j)
+            if (!d.segs[j].fresh) d.pend.push_back(Doc::Pend{(int)j, d.segs[j].n, d.segs[j].ended});
+    }
+    return Q3TTS_OK;
+}
+
 // one chunk boundary: the phases in their order, over one Boundary
 int step(q3tts_session* s) {
     Boundary bd(s->e->B);
     bool idle = false;
     ++s->seq;
+    TRY(accept_docs(s, bd));
     collect(s, bd);
     TRY(voice_work(s, bd));
     TRY(cancel_slots(s, bd));
+    TRY(drop_docs(s, bd));
     TRY(park_starved(s, bd));
     if (s->swap) {  // (the two phases' host time, for q3tts_k_swap_phase_ms)
         const long long o0 = s->st_out.load(std::memory_order_relaxed), i0 = s->st_in.load(std::memory_order_relaxed);
@@ -783,8 +1139,8 @@ int step(q3tts_session* s) {
     TRY(plan_and_admit(s, bd));
     TRY(resume_and_feed(s, bd));
     TRY(run_frames(s, bd, &idle));
-    if (!idle) { TRY(gather_pcm(s, bd)); TRY(finish_slots(s, bd)); }
-    if (!idle || !bd.bt.evs.empty()) s->flight.push_back(std::move(bd.bt));
+    if (!idle || doc_work(s)) { TRY(gather_pcm(s, bd)); TRY(finish_slots(s, bd)); }  // (a document may emit while no slot runs)
+    if (!idle || !bd.bt.evs.empty() || bd.bt.ring >= 0) s->flight.push_back(std::move(bd.bt));
     return Q3TTS_OK;
 }
 
@@ -821,10 +1177,11 @@ void worker(q3tts_session* s) {
         }
         for (const SSlot& sl : s->slots) { if (sl.req && !sl.parked) running = true; if (!sl.req) room = true; if (sl.req && sl.parked && s->swap && !s->evict_stuck) evictable = true; }
         for (const Swapped& o : s->out) if (o.ready_at) out_ready = true;
+        if (doc_work(s)) running = true;  // (undelivered audio, a segment to queue, a document to end)
         bool work;
         {
             std::unique_lock<std::mutex> lk(s->mu);
-            auto todo = [&] { return ((room || evictable) && (!s->pending.empty() || out_ready)) || !s->cancels.empty() || s->text_dirty || s->grant_dirty || !s->clones.empty() || !s->trash.empty(); };
+            auto todo = [&] { return ((room || evictable) && (!s->pending.empty() || out_ready)) || !s->cancels.empty() || s->text_dirty || s->grant_dirty || !s->clones.empty() || !s->trash.empty() || s->doc_dirty; };
             if (!running && s->flight.empty())  // idle: sleep until a submission that fits, a cancel, new text or close
                 s->cv_work.wait(lk, [&] { return s->stop || todo(); });
             if (s->stop) break;
@@ -840,6 +1197,8 @@ void worker(q3tts_session* s) {
     for (int b = 0; b < e->B; ++b) if (s->slots[b].req) { q3_retire_slot(e, b, e->vstream); free_slot(s, b); }
     hipStreamSynchronize(e->stream);
     hipStreamSynchronize(e->vstream);
+    for (auto& d : s->docs) { if (d->rows) { hipFree(d->rows); e->dev_bytes -= d->bytes; d->bytes = 0; } d->rows = nullptr; for (DocSeg& g : d->segs) copy_result_free(g.res); }  // (both streams are idle)
+    s->docs.clear();
     for (Swapped& o : s->out) drop_block(s, o, o.ticket);  // (their ids got FAILED above, or the session is closing)
     s->out.clear();
     reap_blocks(s);  // (every move is over)
@@ -1026,6 +1385,123 @@ extern "C" int q3tts_k_swap_phase_ms(const q3tts_session* s, double out[3]) {
 
 extern "C" int q3tts_session_submit(q3tts_session* s, const q3tts_request* req, uint64_t* id) { return submit_request(s, req, id, 0, nullptr); }
 
+// ---- documents in a session (include/q3tts.h) ----
+static int doc_segments(const q3tts_long_segment* segs, int32_t n, std::vector<DocSeg>& out, const char** why) {
+    for (int i = 0; i < n; ++i) {
+        if (segs[i].n_ids < 0 || (segs[i].n_ids > 0 && !segs[i].ids) || segs[i].max_steps < 0) { *why = "a segment's ids are null or a count is negative"; return Q3TTS_ERR_INVALID; }
+        DocSeg g;
+        g.ids.assign(segs[i].ids, segs[i].ids + segs[i].n_ids); g.kind = segs[i].kind; g.max_steps = segs[i].max_steps;
+        out.push_back(std::move(g));
+    }
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_submit_document(q3tts_session* s, const q3tts_request* tmpl, const q3tts_prompt_desc* voice, q3tts_prefix* prefix,
+                                             const q3tts_long_segment* segs, int32_t n_segs, const q3tts_doc_opts* opts, uint64_t* id) {
+    if (!s || !tmpl || !id || (n_segs > 0 && !segs)) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    auto refuse = [&](int code, const std::string& m) { std::lock_guard<std::mutex> lk(s->mu); return serr(s, code, m); };
+    q3tts_engine* e = s->e;
+    q3tts_doc_opts o;
+    if (opts) o = *opts; else q3tts_doc_default_opts(&o);
+    std::vector<int32_t> kinds;
+    for (int i = 0; i < n_segs && i < Q3_JOIN_MAX_SEG + 1; ++i) kinds.push_back(segs[i].kind);
+    const char* why = "";
+    const int rrc = q3_doc_rules(o, kinds.data(), n_segs, voice != nullptr, prefix != nullptr, e->speed, e->out_rate, &why);
+    if (rrc != Q3TTS_OK) return refuse(rrc, why);
+    if (tmpl->text_stream == 1 || tmpl->prompt_embd || tmpl->prompt || tmpl->prefix)
+        return refuse(Q3TTS_ERR_INVALID, "document: the template carries no prompt (prompt_embd, prompt, prefix NULL; text_stream off)");
+    if (voice && (voice->n_text != 0 || q3_voice_job_rules(voice, nullptr, 0, &why) != Q3TTS_OK))
+        return refuse(Q3TTS_ERR_INVALID, std::string("document: voice is a voice-only desc (n_text == 0)") + (*why ? std::string(": ") + why : std::string()));
+    if (prefix && prefix->e != e) return refuse(Q3TTS_ERR_INVALID, "document: the prefix was made by another engine");
+    std::shared_ptr<Doc> d(new Doc());
+    if (doc_segments(segs, n_segs, d->incoming, &why) != Q3TTS_OK) return refuse(Q3TTS_ERR_INVALID, std::string("document: ") + why);
+    d->tmpl = *tmpl;
+    d->tmpl.prompt = nullptr; d->tmpl.prompt_embd = nullptr; d->tmpl.prefix = nullptr; d->tmpl.want_pcm = 1;
+    if (d->tmpl.use_engine_sampler == 1) {
+        d->tmpl.use_engine_sampler = 0;
+        d->tmpl.temperature = e->temperature; d->tmpl.top_k = e->top_k; d->tmpl.top_p = e->top_p; d->tmpl.has_seed = e->has_seed; d->tmpl.seed = e->seed;
+    }
+    d->join = o.join; d->ahead = o.ahead ? o.ahead : 8; d->open = o.open == 1; d->n_given = n_segs;
+    std::unique_ptr<SReq> job;
+    if (voice) {  // the document's own prefix: a §23 job in front of its segments, released when the document ends
+        job.reset(new SReq());
+        job->kind = 1;
+        q3tts_request tmp{};
+        tmp.prompt = voice;
+        if (copy_request(e, &tmp, job.get()) != Q3TTS_OK) return refuse(Q3TTS_ERR_INVALID, "document: the voice cannot be copied (a null array with a length)");
+        job->doc = d.get();
+    }
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (s->stop || s->dead) return serr(s, Q3TTS_ERR_STATE, s->dead ? "document: the session's worker failed" : "document: the session is closing");
+        if (prefix && prefix->released) return serr(s, Q3TTS_ERR_INVALID, "document: the prefix was released");
+        if (job) {
+            job->keep = new q3tts_prefix();
+            job->keep->e = e; job->keep->state.store(0);
+            s->made.push_back(job->keep);
+            job->id = (1ull << 63) | s->next_internal++;
+            d->px = job->keep; d->own_px = true;
+            s->pending.push_back(std::move(job));
+        } else d->px = prefix;
+        d->id = s->next_id++;
+        IdState st; st.t_submit = q3_now_ms();
+        s->ids[d->id] = st;
+        s->doc_ids[d->id] = d;
+        s->docs_new.push_back(d);
+        s->docs_waiting.fetch_add(1, std::memory_order_release);
+        s->doc_dirty = true;
+        *id = d->id;
+    }
+    s->cv_work.notify_one();
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_document_append(q3tts_session* s, uint64_t id, const q3tts_long_segment* segs, int32_t n_segs, int32_t close) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    std::vector<DocSeg> add;
+    const char* why = "";
+    const bool bad = n_segs < 0 || n_segs > Q3_JOIN_MAX_SEG || (n_segs > 0 && !segs);
+    if (!bad) for (int i = 0; i < n_segs && !*why; ++i) if (segs[i].kind < 0 || segs[i].kind > 4) why = "a break kind lies outside 0..4";
+    if (!bad && !*why) doc_segments(segs, n_segs, add, &why);
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (bad) return serr(s, Q3TTS_ERR_INVALID, "document_append: n_segs is 0..1024 per call, with its segments");
+        if (*why) return serr(s, Q3TTS_ERR_INVALID, std::string("document_append: ") + why);
+        auto it = s->doc_ids.find(id);
+        auto st = s->ids.find(id);
+        if (it == s->doc_ids.end() || it->second->finished || st == s->ids.end() || st->second.cancelled || st->second.final_ready)
+            return serr(s, Q3TTS_ERR_INVALID, "document_append: unknown id, or the document has finished");
+        Doc& d = *it->second;
+        if (!d.open) return serr(s, Q3TTS_ERR_INVALID, "document_append: the document is closed");
+        if (s->stop || s->dead) return serr(s, Q3TTS_ERR_STATE, "document_append: the session is closing, or its worker failed");
+        for (DocSeg& g : add) d.incoming.push_back(std::move(g));
+        d.n_given += n_segs;
+        if (close) d.open = false;
+        s->doc_dirty = true;
+    }
+    s->cv_work.notify_one();
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_session_doc_mem_cap(q3tts_session* s, int64_t bytes) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    s->doc_mem_cap.store(bytes < 0 ? -1 : (long long)bytes, std::memory_order_relaxed);
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_session_document_info(q3tts_session* s, uint64_t id, q3tts_long_info* info, int32_t cap, int32_t* n_known, int64_t* n_delivered) {
+    if (!s) return serr(nullptr, Q3TTS_ERR_INVALID, "null session");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (cap < 0 || (cap > 0 && !info)) return serr(s, Q3TTS_ERR_INVALID, "document_info: info missing");
+    auto it = s->doc_ids.find(id);
+    if (it == s->doc_ids.end()) return serr(s, Q3TTS_ERR_INVALID, "document_info: unknown id");
+    const Doc& d = *it->second;
+    for (int i = 0; i < cap && i < (int)d.info.size(); ++i) info[i] = d.info[i];
+    if (n_known) *n_known = (int32_t)d.info.size();
+    if (n_delivered) *n_delivered = d.n_delivered;
+    return Q3TTS_OK;
+}
+
 // ---- voices in a session (include/q3tts.h) ----
 extern "C" int q3tts_session_submit_keep_voice(q3tts_session* s, const q3tts_request* req, int32_t voice_rows, uint64_t* id, q3tts_prefix** out) {
     if (!out) return serr(nullptr, Q3TTS_ERR_INVALID, "null argument");
@@ -1147,11 +1623,19 @@ extern "C" int q3tts_session_cancel(q3tts_session* s, uint64_t id) {
                     s->pending.erase(p);
                     break;
                 }
+            for (auto d = s->docs_new.begin(); d != s->docs_new.end(); ++d)
+                if ((*d)->id == id) {  // a document the worker has not accepted: it never will
+                    (*d)->finished = true; (*d)->open = false;
+                    if ((*d)->own_px) { (*d)->px->released = true; maybe_reap(s, (*d)->px); }
+                    s->docs_new.erase(d);
+                    break;
+                }
             SEv v = final_ev(id, Q3TTS_EV_CANCELLED, Q3TTS_OK);
             if (!job) deliver(s, v, q3_now_ms());
         } else {
             for (auto r = s->ready.begin(); r != s->ready.end();) {  // no further chunk from now on; a waiting final becomes CANCELLED
                 if (r->id != id) { ++r; continue; }
+                if (r->kind == Q3TTS_EV_SEGMENT) { copy_result_free(r->res); r = s->ready.erase(r); continue; }  // (a cancelled document's)
                 if (r->kind == Q3TTS_EV_CHUNK) {
                     if (r->ring >= 0 && --s->refs[r->ring] == 0) s->cv_space.notify_all();
                     r = s->ready.erase(r);

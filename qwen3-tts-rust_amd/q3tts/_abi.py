@@ -129,6 +129,7 @@ class SessionEvent(C.Structure):
 
 
 EV_NONE, EV_CHUNK, EV_DONE, EV_FAILED, EV_CANCELLED = 0, 1, 2, 3, 4
+EV_SEGMENT = 6  # a document's segment has been handed out completely (include/q3tts.h, "documents in a session")
 EV_PREFIX = 5  # a session's prefix store is written, or its entry failed (include/q3tts.h, "voices in a session")
 PCM_F32, PCM_I16 = 0, 1
 SESSION_RING_DEPTH = 4
@@ -193,6 +194,8 @@ SYMBOLS = [
     "q3tts_set_speed", "q3tts_get_speed", "q3tts_time_stretch", "q3tts_k_tempo_counts", "q3tts_k_pcm_tempo",
     "q3tts_text_split", "q3tts_long_default_opts", "q3tts_generate_long", "q3tts_long_result_free", "q3tts_pcm_join",
     "q3tts_k_pcm_edges", "q3tts_k_pcm_join",
+    "q3tts_session_submit_document", "q3tts_session_document_append", "q3tts_session_document_info",
+    "q3tts_k_session_doc_mem_cap", "q3tts_doc_default_opts", "q3tts_k_doc_rules", "q3tts_k_doc_plan", "q3tts_k_doc_stream",
     "q3tts_vocoder_config_from_file", "q3tts_get_vocoder_source", "q3tts_k_voc_file_tensor",
 ]
 
@@ -216,6 +219,11 @@ class LongSegment(C.Structure):
 
 class LongOpts(C.Structure):
     _fields_ = [("join", JoinOpts), ("speed_permille", C.c_int32), ("output_rate", C.c_int32)]
+
+
+class DocOpts(C.Structure):
+    """q3tts_doc_opts (include/q3tts.h, "documents in a session: the streaming join")."""
+    _fields_ = [("join", JoinOpts), ("ahead", C.c_int32), ("open", C.c_int32)]
 
 
 class LongInfo(C.Structure):
@@ -335,6 +343,17 @@ def load_library(path=None):
     lib.q3tts_k_pcm_edges.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, C.c_float, i32p, C.c_int32, f32p]
     lib.q3tts_k_pcm_join.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, C.POINTER(JoinOpts), C.c_int32, f32p, C.c_int64, i64p, i64p,
                                      C.c_int32, f32p]
+    lib.q3tts_doc_default_opts.argtypes = [C.POINTER(DocOpts)]
+    lib.q3tts_doc_default_opts.restype = None
+    lib.q3tts_session_submit_document.argtypes = [vp, C.POINTER(Request), C.POINTER(PromptDesc), vp, C.POINTER(LongSegment), C.c_int32, C.POINTER(DocOpts),
+                                                  C.POINTER(C.c_uint64)]
+    lib.q3tts_session_document_append.argtypes = [vp, C.c_uint64, C.POINTER(LongSegment), C.c_int32, C.c_int32]
+    lib.q3tts_k_session_doc_mem_cap.argtypes = [vp, C.c_int64]
+    lib.q3tts_session_document_info.argtypes = [vp, C.c_uint64, C.POINTER(LongInfo), C.c_int32, i32p, i64p]
+    lib.q3tts_k_doc_rules.argtypes = [C.POINTER(DocOpts), i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]
+    lib.q3tts_k_doc_plan.argtypes = [C.POINTER(JoinOpts), C.c_int32, i32p, C.c_int32, C.c_int64, i64p, i64p, C.c_int32, i32p, i64p, C.c_int32, i32p]
+    lib.q3tts_k_doc_stream.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, C.c_int32, C.POINTER(JoinOpts), C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, i64p, i64p, C.c_int32, i32p, i64p, i64p]
     lib.q3tts_stream_begin.argtypes = [vp, C.POINTER(Request), C.POINTER(vp)]
     lib.q3tts_stream_poll.argtypes = [vp, C.POINTER(f32p), i32p, i32p]
     lib.q3tts_stream_end.argtypes = [vp, C.POINTER(Result)]

@@ -354,6 +354,105 @@ class TtsEngine:
         table = [(p, f["out_begin"] / r, f["out_end"] / r, bool(f["hit_eos"])) for p, f in zip(pieces, out.info)]
         return AudioSample(out.pcm, out.sample_rate, 1), table
 
+    def stream_long(self, text_or_pieces, voice: VoiceFile, instruct=None, *, prefix=None, seed=None, pause_ms=None, ahead=None,
+                    target_bytes=0, max_bytes=0, **join_opts):
+        """generate_long's streaming twin (an extension; include/q3tts.h, "documents in a session"): the document plays
+        while it is synthesised. A str is split as generate_long splits it and submitted whole; an iterator of strings (a language
+        model still writing) is split piece by piece and appended as it arrives from a helper thread, each piece ending a paragraph.
+        Yields (f32 chunk, segments_done): segments_done lists (text_slice, t_begin_s, t_end_s, hit_eos) for the segments that this
+        chunk completed; a chunk is yielded as soon as the segment events of its boundary are taken (they arrive with it), not when
+        the next chunk comes. The chunks joined are generate_long's audio for the same segments, bit for bit (without speed or sample_rate:
+        a streamed document has neither, and the call is refused while the engine has one set). ahead: how many segments may run in
+        front of the one being delivered (default 8). join_opts / pause_ms: as generate_long."""
+        import threading
+        sc = self.sampler_config
+        if prefix is not None:
+            self._check_prefix(prefix, voice, instruct)
+            vdesc, keep = None, None
+        else:
+            vdesc, keep = self._desc(None, voice, instruct, part="voice")
+        if pause_ms is not None:
+            join_opts["pause_ms"] = tuple(pause_ms)
+
+        def split(text, last_kind=None):
+            raw = text.encode("utf-8")
+            spans = native.text_split(raw, target_bytes, max_bytes)
+            pieces = [raw[b:e].decode("utf-8") for b, e, _ in spans]
+            kinds = [k for _, _, k in spans]
+            if kinds and last_kind is not None:
+                kinds[-1] = last_kind
+            return pieces, [(self._encode(p), k) for p, k in zip(pieces, kinds)]
+
+        whole = isinstance(text_or_pieces, str)
+        texts, first = [], []
+        it = iter(()) if whole else iter(text_or_pieces)
+        if whole:
+            texts, first = split(text_or_pieces)
+            if not first:
+                raise ValueError("stream_long: the text holds nothing speakable")
+        kw = dict(temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p, seed=sc.seed if seed is None else seed, max_steps=self.max_steps)
+        rate = float(self.cfg.vocoder.sample_rate)
+        with native.NativeSession(self._native) as sess:
+            did = sess.submit_document(first, voice=vdesc, prefix=prefix, join=join_opts, ahead=ahead or 0, open=not whole, **kw)
+            failure = []
+            gate, live = threading.Lock(), [True]  # the feeder touches the session only while the consumer is inside this block
+
+            def feed():
+                try:
+                    for piece in it:
+                        p, segs = split(piece, _abi.BREAK_PARAGRAPH)
+                        with gate:
+                            if not live[0]:
+                                return
+                            if segs:
+                                texts.extend(p)   # (before the append: a SEGMENT event finds its text)
+                                sess.append_document(did, segs)
+                    with gate:
+                        if live[0]:
+                            sess.append_document(did, [], close=True)
+                except Exception as ex:  # the iterator failed, or the document ended meanwhile
+                    failure.append(ex)
+                    with gate:
+                        if live[0]:
+                            try:
+                                sess.cancel(did)
+                            except _abi.Q3Error:
+                                pass
+            th = threading.Thread(target=feed, daemon=True) if not whole else None
+            if th is not None:
+                th.start()
+            try:
+                # A boundary's events (the chunk, then the segments it completed, then DONE) reach the queue together: behind a chunk the
+                # segments are taken without waiting, and the chunk goes out at once, not when the next one arrives
+                ev, ended = None, False
+                while not ended and (ev is not None or sess.open_ids):
+                    if ev is None:
+                        ev = sess.next(-1)
+                    rid, kind, pcm, is_final, res = ev
+                    ev = None
+                    if rid != did:
+                        continue
+                    if kind == _abi.EV_CHUNK:
+                        done = []
+                        while True:
+                            ev = sess.next(0)
+                            if ev is None or ev[0] != did or ev[1] != _abi.EV_SEGMENT:
+                                break
+                            seg = ev[4].segment
+                            f = sess.document_info(did)[0][seg]
+                            done.append((texts[seg], f["begin"] / rate, f["end"] / rate, bool(f["hit_eos"])))
+                        yield pcm, done
+                    elif kind == _abi.EV_SEGMENT:   # (not behind a chunk of its own: cannot happen; kept out of the audio)
+                        continue
+                    elif kind == _abi.EV_DONE:
+                        ended = True
+                    else:
+                        raise _abi.Q3Error(f"stream_long failed with status {res.status if res is not None else kind}" +
+                                           (f": {failure[0]}" if failure else ""))
+            finally:
+                with gate:   # (also when the consumer stops early: the feeder ends at its next piece, the session closes below)
+                    live[0] = False
+
     def stream_batch_with_voice(self, texts, voices, instructs=None, seeds=None, *, prefix=None, realtime_lead_s=None):
         """The streaming twin of generate_batch_with_voice: every utterance runs through one session (continuous batching over the
         engine's slots) and its 4-frame chunks are yielded as they are produced, as (index, f32 chunk, is_final); chunks of different

@@ -69,10 +69,12 @@ class GenResult:
     def __init__(self, status, codes, pcm, hit_eos, first_chunk_ms, total_ms, sample_rate):
         self.status, self.codes, self.pcm, self.hit_eos = status, codes, pcm, hit_eos
         self.first_chunk_ms, self.total_ms, self.sample_rate = first_chunk_ms, total_ms, sample_rate
+        self._n_frames = None
 
     @property
     def n_frames(self):
-        return self.codes.shape[0]
+        """The frames the result counts: its codes' rows, or the sum a document's DONE event reports without codes."""
+        return self.codes.shape[0] if self._n_frames is None else self._n_frames
 
 
 class NativeEngine:
@@ -190,14 +192,16 @@ class NativeEngine:
 
     def _unpack(self, res):
         ncb = self.cfg.model.n_codebooks
-        codes = np.ctypeslib.as_array(res.codes, shape=(res.n_frames, ncb)).copy() if res.n_frames > 0 else \
-            np.zeros((0, ncb), dtype=np.int32)
+        codes = np.ctypeslib.as_array(res.codes, shape=(res.n_frames, ncb)).copy() if res.n_frames > 0 and res.codes else \
+            np.zeros((0, ncb), dtype=np.int32)   # (a document's DONE event counts its frames and carries no codes)
         pcm = None
         if res.pcm:
             pcm = np.ctypeslib.as_array(res.pcm, shape=(res.n_samples,)).copy() if res.n_samples > 0 else \
                 np.zeros(0, dtype=np.float32)
         out = GenResult(res.status, codes, pcm, bool(res.hit_eos), res.first_chunk_ms, res.total_ms, res.sample_rate)
         out.n_samples = int(res.n_samples)
+        if res.n_frames > 0 and not res.codes:
+            out._n_frames = int(res.n_frames)
         self.lib.q3tts_result_free(C.byref(res))
         return out
 
@@ -671,6 +675,60 @@ class NativeSession:
                                                  codes.ctypes.data_as(C.POINTER(C.c_int64)), cap, C.byref(n), _ptr(spk, f32p)), "q3tts_session_clone")
         return codes[:n.value].copy(), spk
 
+    @staticmethod
+    def _doc_segments(segments, keep):
+        n = len(segments)
+        segs = (_abi.LongSegment * max(n, 1))()
+        for i, sg in enumerate(segments):
+            ids = np.ascontiguousarray(sg[0], dtype=np.uint32)
+            keep.append(ids)
+            segs[i].ids, segs[i].n_ids, segs[i].kind = _ptr(ids, u32p), ids.size, int(sg[1])
+            segs[i].max_steps = int(sg[2]) if len(sg) > 2 else 0
+        return segs, n
+
+    def submit_document(self, segments, voice=None, prefix=None, join=None, ahead=0, open=False, **template_kw):
+        """q3tts_session_submit_document: `segments` as NativeEngine.generate_long takes them ((ids, kind) or (ids, kind, max_steps));
+        exactly one of voice (a voice-only desc) and prefix (a NativePrefix, ready or pending); join: a dict of q3tts_join_opts fields;
+        ahead: how many segments may run in front of the one being delivered (0: 8); open=True: more segments follow through
+        append_document. template_kw: make_request's sampler fields, min_frames, force_eos_at, max_steps. Returns the document's id: its
+        EV_CHUNK payloads joined are generate_long's pcm bit for bit; EV_SEGMENT events carry each segment's result (res.segment = its index)."""
+        if not self.h:
+            raise _abi.Q3Error("q3tts_session_submit_document: the session is closed")
+        tmpl, keep = NativeEngine.make_request(**template_kw)
+        segs, n = self._doc_segments(segments, keep)
+        o = doc_opts(ahead=ahead, open=1 if open else 0, **(join or {}))
+        if prefix is not None and not prefix.h:
+            raise _abi.Q3Error("the prefix is closed")
+        did = C.c_uint64(0)
+        self._check(self.lib.q3tts_session_submit_document(self.h, C.byref(tmpl), C.byref(voice) if voice is not None else None,
+                                                           prefix.h if prefix is not None else None, segs, n, C.byref(o), C.byref(did)),
+                    "q3tts_session_submit_document")
+        self._open.add(did.value)
+        return did.value
+
+    def append_document(self, did, segments, close=False):
+        """q3tts_session_document_append: more segments for a document submitted with open=True; close=True ends it (segments may be empty)."""
+        keep = []
+        segs, n = self._doc_segments(segments, keep)
+        self._check(self.lib.q3tts_session_document_append(self.h, did, segs, n, 1 if close else 0), "q3tts_session_document_append")
+
+    def document_info(self, did):
+        """q3tts_session_document_info: (info, n_delivered) — one dict per segment delivered so far (generate_long's info fields) and the
+        samples handed out so far. Thread-safe."""
+        cap = 64
+        while True:
+            arr = (_abi.LongInfo * cap)()
+            n, nd = C.c_int32(0), C.c_int64(0)
+            self._check(self.lib.q3tts_session_document_info(self.h, did, arr, cap, C.byref(n), C.byref(nd)), "q3tts_session_document_info")
+            if n.value <= cap:
+                names = [f[0] for f in _abi.LongInfo._fields_]
+                return [{k: int(getattr(arr[i], k)) for k in names} for i in range(n.value)], int(nd.value)
+            cap = n.value + 64
+
+    def doc_mem_cap(self, nbytes):
+        """q3tts_k_session_doc_mem_cap (test hook): documents are accepted as if the device had at most nbytes free; < 0: off."""
+        self._check(self.lib.q3tts_k_session_doc_mem_cap(self.h, int(nbytes)), "q3tts_k_session_doc_mem_cap")
+
     def cancel(self, rid):
         self._check(self.lib.q3tts_session_cancel(self.h, rid), "q3tts_session_cancel")
 
@@ -682,7 +740,8 @@ class NativeSession:
                     "q3tts_session_append_text")
 
     def next(self, timeout_ms=-1):
-        """One event as (id, kind, pcm ndarray | None, is_final, GenResult | None), or None on timeout. EV_PREFIX (only after create_prefix
+        """One event as (id, kind, pcm ndarray | None, is_final, GenResult | None), or None on timeout. EV_SEGMENT (documents): the result is
+        the segment's own, res.segment its index, res.n_samples its piece's length. EV_PREFIX (only after create_prefix
         or submit(keep_voice=True)): the result's status is the prefix's; it is final for a job, not for a keep-voice request."""
         ev = _abi.SessionEvent()
         self._check(self.lib.q3tts_session_next(self.h, timeout_ms, C.byref(ev)), "q3tts_session_next")
@@ -694,6 +753,8 @@ class NativeSession:
                 np.zeros(0, dtype=self.dtype)
         else:
             res = self.engine._unpack(ev.result)
+            if ev.kind == _abi.EV_SEGMENT:
+                res.segment = int(ev.n_samples)
             if ev.is_final:
                 self._open.discard(ev.id)
         return ev.id, ev.kind, pcm, bool(ev.is_final), res
@@ -1487,6 +1548,77 @@ def k_pcm_join(src, lens, kinds, edges, out_cap, rate=24000, device=0, iters=0, 
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_pcm_join failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return (out, plan, N.value, ms.value) if iters > 0 else (out, plan, N.value)
+
+
+def doc_opts(ahead=0, open=0, **join):
+    """q3tts_doc_opts: q3tts_doc_default_opts, then the join options given and ahead / open."""
+    lib = _abi.load_library()
+    o = _abi.DocOpts()
+    lib.q3tts_doc_default_opts(C.byref(o))
+    if join:
+        d = dict(trim=o.join.trim, threshold=o.join.threshold, keep=o.join.keep, fade=o.join.fade, pause_ms=list(o.join.pause_ms))
+        d.update(join)
+        o.join = join_opts(**d)
+    o.ahead, o.open = int(ahead), int(open)
+    return o
+
+
+def k_doc_rules(opts, kinds, have_voice=1, have_prefix=0, engine_speed=0, engine_rate=0):
+    """q3tts_k_doc_rules (host only): (status, the rule's name) for a document of these options and break kinds."""
+    lib = _abi.load_library()
+    kd = np.ascontiguousarray(kinds, dtype=np.int32)
+    msg = C.create_string_buffer(256)
+    rc = lib.q3tts_k_doc_rules(C.byref(opts) if opts is not None else None, _ptr(kd, i32p) if kd.size else None, kd.size, int(have_voice), int(have_prefix),
+                               int(engine_speed), int(engine_rate), msg, 256)
+    return rc, msg.value.decode()
+
+
+def k_doc_plan(segs, room, state, rate=24000, **opts):
+    """q3tts_k_doc_plan (host only): one boundary of the streaming join's plan. segs [n][5] = n, first, last, closed, kind; state: int64 [7],
+    updated in place (zeros before the first call). Returns (pieces [k][6] = seg, src, j0, count, L, F; done [m][5] = seg, lo, hi, begin, end)."""
+    lib = _abi.load_library()
+    sg = np.ascontiguousarray(segs, dtype=np.int32).reshape(-1, 5)
+    if state.dtype != np.int64 or state.shape != (7,) or not state.flags.c_contiguous:
+        raise ValueError("k_doc_plan: state is a contiguous int64 [7]")
+    o = join_opts(**opts)
+    i64p = C.POINTER(C.c_int64)
+    cap = 2 * sg.shape[0] + 2
+    pieces, done = np.zeros((cap, 6), dtype=np.int64), np.zeros((sg.shape[0] + 1, 5), dtype=np.int64)
+    npc, nd = C.c_int32(0), C.c_int32(0)
+    rc = lib.q3tts_k_doc_plan(C.byref(o), int(rate), _ptr(sg, i32p), sg.shape[0], int(room), _ptr(state, i64p), _ptr(pieces, i64p), cap, C.byref(npc),
+                              _ptr(done, i64p), done.shape[0], C.byref(nd))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_doc_plan failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return pieces[:npc.value].copy(), done[:nd.value].copy()
+
+
+def k_doc_stream(src, kinds, sched, ahead, staging, dst0=0, lag=1, fmt=0, check_rows=0, rate=24000, device=0, out_cap=None, chunk_cap=1 << 16, **opts):
+    """q3tts_k_doc_stream: scan + plan + emit boundary by boundary over the rows src [rows][stride]; sched[i] lists segment i's valid length
+    after every boundary at which it runs (ascending, the last one final). Returns (out f32 or i16, chunks per boundary, plan [rows][4] =
+    lo, hi, begin, end, bad)."""
+    lib = _abi.load_library()
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    kd = np.ascontiguousarray(kinds, dtype=np.int32)
+    if src.ndim != 2 or kd.shape != (src.shape[0],) or len(sched) != src.shape[0]:
+        raise ValueError("k_doc_stream: src is [rows][stride]; kinds and sched take one entry per row")
+    sn = np.array([len(s) for s in sched], dtype=np.int32)
+    sc = np.zeros((src.shape[0], max(1, int(sn.max()))), dtype=np.int32)
+    for i, s in enumerate(sched):
+        sc[i, :len(s)] = s
+    o = join_opts(**opts)
+    if out_cap is None:
+        out_cap = int(sum(s[-1] for s in sched)) + (len(sched) - 1) * max(opts.get("pause_ms", (0, 0, 150, 300, 600))) * rate // 1000
+    out = np.zeros(max(1, int(out_cap)), dtype=np.int16 if fmt else np.float32)
+    chunks = np.zeros(int(chunk_cap), dtype=np.int64)
+    plan = np.zeros((src.shape[0], 4), dtype=np.int64)
+    i64p = C.POINTER(C.c_int64)
+    n_out, bad, nb = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    rc = lib.q3tts_k_doc_stream(device, _ptr(src, f32p), src.shape[0], src.shape[1], _ptr(kd, i32p), _ptr(sc, i32p), _ptr(sn, i32p), sc.shape[1], C.byref(o),
+                                int(rate), int(ahead), int(lag), int(staging), int(dst0), int(fmt), int(check_rows), out.ctypes.data_as(C.c_void_p),
+                                int(out_cap), C.byref(n_out), _ptr(chunks, i64p), chunks.size, C.byref(nb), _ptr(plan, i64p), C.byref(bad))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_doc_stream failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return out[:n_out.value].copy(), chunks[:nb.value].copy(), plan, bad.value
 
 
 def k_rng_f32(seed, n):

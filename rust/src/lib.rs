@@ -74,6 +74,10 @@ pub struct q3tts_text_span { pub begin: i64, pub end: i64, pub kind: i32 }
 pub struct q3tts_join_opts { pub trim: i32, pub threshold: c_float, pub keep: i32, pub fade: i32, pub pause_ms: [i32; 5] }
 #[repr(C)]
 pub struct q3tts_long_segment { pub ids: *const u32, pub n_ids: i32, pub kind: i32, pub max_steps: i32 }
+/// q3tts_session_event.kind of a document's segment whose piece has gone out (include/q3tts.h, "documents in a session")
+pub const Q3TTS_EV_SEGMENT: i32 = 6;
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct q3tts_doc_opts { pub join: q3tts_join_opts, pub ahead: i32, pub open: i32 }
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct q3tts_long_opts { pub join: q3tts_join_opts, pub speed_permille: i32, pub output_rate: i32 }
 #[repr(C)] #[derive(Clone, Copy)]
@@ -132,6 +136,14 @@ extern "C" {
     // granted as the listener plays, and a device arena that parked requests are swapped out into while others wait for their slots
     pub fn q3tts_session_submit_paced(s: *mut q3tts_session, req: *const q3tts_request, credit_frames: i32, id: *mut u64) -> c_int;
     pub fn q3tts_session_grant(s: *mut q3tts_session, id: u64, frames: i32) -> c_int;
+    // documents in a session (include/q3tts.h): a long document streams in order while later segments run; the chunks of its id, joined,
+    // are q3tts_generate_long's pcm bit for bit. Q3TTS_EV_SEGMENT (6) reports each segment as its piece has gone out
+    pub fn q3tts_k_session_doc_mem_cap(s: *mut q3tts_session, bytes: i64) -> c_int;
+    pub fn q3tts_doc_default_opts(o: *mut q3tts_doc_opts);
+    pub fn q3tts_session_submit_document(s: *mut q3tts_session, tmpl: *const q3tts_request, voice: *const q3tts_prompt_desc, prefix: *mut q3tts_prefix,
+                                         segs: *const q3tts_long_segment, n_segs: i32, opts: *const q3tts_doc_opts, id: *mut u64) -> c_int;
+    pub fn q3tts_session_document_append(s: *mut q3tts_session, id: u64, segs: *const q3tts_long_segment, n_segs: i32, close: i32) -> c_int;
+    pub fn q3tts_session_document_info(s: *mut q3tts_session, id: u64, info: *mut q3tts_long_info, cap: i32, n_known: *mut i32, n_delivered: *mut i64) -> c_int;
     pub fn q3tts_session_set_swap(s: *mut q3tts_session, arena_bytes: i64) -> c_int;
     pub fn q3tts_session_swap_stats(s: *const q3tts_session, out: *mut i64) -> c_int;
     // speaking rate (no counterpart in the reference): engine state in per mille, 500..2000, 0 or 1000 = off; a pitch-preserving time-stretch on the device
