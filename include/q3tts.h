@@ -691,6 +691,11 @@ int q3tts_clone_speaker_encode(q3tts_engine* e, const float* audio, int64_t n_sa
 int q3tts_k_speaker_from_mel(q3tts_engine* e, const float* mel, int32_t n_frames, float* spk_emb);
 int q3tts_k_audio_latent(q3tts_engine* e, const float* audio, int64_t n_samples, float* latent, int32_t cap_frames,
                          int32_t* n_frames);
+/* test hook: the audio encoder's split residual VQ alone, on given operands (no engine). ps / pa [T][D] f32 (the semantic / acoustic
+ * projections; pa may be NULL when ncb == 1), books row-major [ncb][CS][D] f32; the production codebook transpose and quantiser kernels
+ * run once; codes [T][ncb]. D a multiple of 16 in 16 .. 4096, ncb 1 .. 64. */
+int q3tts_k_rvq(int32_t device, const float* ps, const float* pa, int32_t T, int32_t D, const float* books, int32_t ncb, int32_t CS,
+                int64_t* codes);
 
 /* ---- tokenizer (host only; replaces the `tokenizers`-crate wrapper src/utils/tokenizer.rs:1-37 for non-Rust hosts) ----
  * Reads model_dir/tokenizer/tokenizer.json of the Qwen2 family: added tokens, NFC, Split(Qwen2 regex) + ByteLevel, BPE.

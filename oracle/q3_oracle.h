@@ -190,6 +190,9 @@ int32_t q3o_speaker_encode(const q3o_clone_config* c, uint64_t seed, const float
 /* returns n_frames; codes [n_frames][ae_n_codebooks]; latent_out (optional) [n_frames][ae_hidden] = the rows fed to the VQ */
 int32_t q3o_audio_encode(const q3o_clone_config* c, uint64_t seed, const float* pcm, int64_t n_samples, int32_t* codes,
                          int32_t cap_frames, float* latent_out);
+/* the audio encoder's split residual VQ alone (q3o_audio_encode calls it): ps / pa [T][D], pa may be NULL when ncb == 1; books row-major
+ * [ncb][CS][D]; codes [T][ncb]; returns 0 / <0 */
+int32_t q3o_rvq(const float* ps, const float* pa, int32_t T, int32_t D, const float* books, int32_t ncb, int32_t CS, int32_t* codes);
 
 typedef struct q3o_vocoder q3o_vocoder;
 q3o_vocoder* q3o_vocoder_create(const q3o_vocoder_config* cfg, uint64_t seed, int32_t n_threads);

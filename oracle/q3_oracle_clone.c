@@ -324,10 +324,24 @@ int32_t q3o_audio_encode(const q3o_clone_config* c, uint64_t seed, const float* 
     float* ps = malloc((size_t)Tf * D * 4); float* pa = malloc((size_t)Tf * D * 4);
     linear(seed, AC_SEM_PROJ, 0, lat, Tf, H, D, ps);
     linear(seed, AC_AC_PROJ, 0, lat, Tf, H, D, pa);
-    for (int q = 0; q < ncb; ++q) {
-        float* cb = gen_vecf(seed, CTID(AC_CODEBOOK + q, 0), (size_t)CS * D, 0.0f, 1.0f / sqrtf((float)D));
-        for (int t = 0; t < Tf; ++t) {
-            float* r = (q == 0 ? ps : pa) + (size_t)t * D;
+    float* books = malloc((size_t)ncb * CS * D * 4);
+    for (int q = 0; q < ncb; ++q)
+        q3o_synth_fill(seed, CTID(AC_CODEBOOK + q, 0), (size_t)CS * D, 0.0f, 1.0f / sqrtf((float)D), 0, books + (size_t)q * CS * D);
+    q3o_rvq(ps, pa, Tf, D, books, ncb, CS, codes);
+    free(books); free(ps); free(pa); free(lat);
+    return Tf;
+}
+
+/* The split residual VQ alone: ps / pa [T][D] (pa may be NULL when ncb == 1), books row-major [ncb][CS][D], codes [T][ncb]. Codebook 0
+ * quantises ps[t]; codebooks 1.. quantise pa[t] and then its running residual (one f32 subtraction per element and codebook). Nearest
+ * codeword in squared Euclidean distance, an ascending-i fmaf chain per codeword; the first codeword of the smallest distance wins. */
+int32_t q3o_rvq(const float* ps, const float* pa, int32_t T, int32_t D, const float* books, int32_t ncb, int32_t CS, int32_t* codes) {
+    if (!ps || (!pa && ncb > 1) || !books || !codes || T < 1 || D < 1 || ncb < 1 || CS < 1) return -1;
+    float* r = malloc((size_t)D * 4);
+    for (int t = 0; t < T; ++t)
+        for (int q = 0; q < ncb; ++q) {
+            const float* cb = books + (size_t)q * CS * D;
+            if (q < 2) memcpy(r, (q == 0 ? ps : pa) + (size_t)t * D, (size_t)D * 4);
             int best = 0; float bd = 0.0f;
             for (int j = 0; j < CS; ++j) {
                 float dist = 0.0f;
@@ -337,8 +351,6 @@ int32_t q3o_audio_encode(const q3o_clone_config* c, uint64_t seed, const float* 
             codes[(size_t)t * ncb + q] = best;
             if (q > 0) for (int i = 0; i < D; ++i) r[i] = r[i] - cb[(size_t)best * D + i];
         }
-        free(cb);
-    }
-    free(ps); free(pa); free(lat);
-    return Tf;
+    free(r);
+    return 0;
 }

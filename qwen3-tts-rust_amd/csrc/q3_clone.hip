@@ -321,6 +321,20 @@ struct Arena {
 
 }  // namespace
 
+// The quantiser as audio_forward launches it. With a.books set, the row-major codebooks [ncb][CS][D] are first transposed by k_cb_transpose into
+// a.booksT (what q3tts_clone_init does once per codebook); a.cbT is the device table of the ncb transposed books. -1: refused, nothing launched.
+int q3_launch_rvq(const Q3Rvq& a, hipStream_t s) {
+    if (!a.ps || (!a.pa && a.ncb > 1) || !a.cbT || !a.codes || a.T < 1 || a.D < 16 || a.D % 16 || a.D > 4096 || a.ncb < 1 || a.CS < 1) return -1;
+    if (a.books) {
+        if (!a.booksT) return -1;
+        const size_t ne = (size_t)a.CS * a.D;
+        for (int q = 0; q < a.ncb; ++q)
+            hipLaunchKernelGGL(k_cb_transpose, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, a.books + q * ne, a.booksT + q * ne, a.CS, a.D);
+    }
+    hipLaunchKernelGGL(k_rvq, dim3(a.T), dim3(RVQ_T), (size_t)a.D * 4, s, a.ps, a.pa, a.D, a.cbT, a.ncb, a.CS, a.codes);
+    return 0;
+}
+
 struct Q3Clone {
     q3tts_clone_config cfg{};
     std::vector<void*> allocs;
@@ -343,12 +357,19 @@ struct Ctx { q3tts_engine* e; Q3Clone* c; hipStream_t s; Arena* A; };
 inline int round512(int k) { return (k + 511) / 512 * 512; }
 inline unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
 
+// The GEMM depth of a convolution mk_conv builds is kp = round512(k * cin), and one rule bounds all of them: kp <= 8192. Read from q3_gemm.hip:
+// at K > 8192 without a norm prologue q3_launch_gemm passes by k_gemm_small and k_gemm_fat (both gated on K <= 8192) and takes the ring
+// kernel's runtime-K instance (BPS = 0), whose only K-sized LDS is the norm strip that is absent here and whose loops run on K >> 9; nothing in
+// that reading bounds K, but no depth above 8192 has ever run through it, under a test or otherwise, so the encoders refuse one on the host.
+bool depth_ok(int64_t k, int64_t cin) { return k >= 1 && cin >= 1 && k * cin <= 8192; }  // (k * cin <= 8192 <=> round512(k * cin) <= 8192)
+
 int dev_alloc(q3tts_engine* e, Q3Clone* c, void** p, size_t bytes) {
     Q3_HIP(e, hipMalloc(p, bytes));
     c->allocs.push_back(*p);
     return Q3TTS_OK;
 }
 int mk_conv(q3tts_engine* e, Q3Clone* c, CConv& cv, int comp, int ww, int wb, int cin, int n, int k, int stride, int dil, int padl, int mode) {
+    if (!depth_ok(k, cin)) return q3_set_err(e, Q3TTS_ERR_INVALID, "clone config: a convolution's GEMM depth exceeds 8192");  // (validate() names it first)
     cv.cin = cin; cv.n = n; cv.k = k; cv.stride = stride; cv.dil = dil; cv.padl = padl; cv.mode = mode; cv.kp = round512(k * cin);
     int rc;
     if ((rc = dev_alloc(e, c, (void**)&cv.w, (size_t)n * cv.kp * 2))) return rc;
@@ -499,12 +520,18 @@ void audio_forward(Ctx& X, const float* pcm, int64_t n, float* lat_dev, long lon
     float* ps = A.get<float>((size_t)Tf * D); float* pa = A.get<float>((size_t)Tf * D);
     conv_run(X, X.c->semp, lat_dev, H, Tf, ACT_NONE, ps, D, Tf);
     conv_run(X, X.c->acp, lat_dev, H, Tf, ACT_NONE, pa, D, Tf);
-    if (!A.dry)
-        hipLaunchKernelGGL(k_rvq, dim3(Tf), dim3(RVQ_T), (size_t)D * 4, X.s, ps, pa, D, X.c->cb_dev, c.ae_n_codebooks, c.ae_codebook_size, codes_dev);
+    if (!A.dry) {
+        Q3Rvq q{}; q.ps = ps; q.pa = pa; q.T = Tf; q.D = D; q.cbT = X.c->cb_dev; q.ncb = c.ae_n_codebooks; q.CS = c.ae_codebook_size; q.codes = codes_dev;
+        q3_launch_rvq(q, X.s);  // (validate() holds every condition the launcher checks)
+    }
 }
 
 int validate(q3tts_engine* e, const q3tts_clone_config& c) {
     auto bad = [&](const char* m) { return q3_set_err(e, Q3TTS_ERR_INVALID, std::string("clone config: ") + m); };
+    // every CConv q3tts_clone_init describes goes through here, in its order (called once the fields it reads are known to be positive)
+    bool deep = false; std::string deep_what;
+    auto conv = [&](const char* what, int64_t k, int64_t cin) { if (!deep && !depth_ok(k, cin)) { deep = true; deep_what = what; } };
+    auto too_deep = [&]() { return bad((deep_what + ": GEMM depth (kernel x input channels) exceeds 8192").c_str()); };
     if (c.mel_dim != 128) return bad("mel_dim must be 128 (the log-mel front-end produces 128 bands)");
     for (int i = 0; i < 5; ++i) {
         if (c.se_channels[i] < 16 || c.se_channels[i] % 16) return bad("se_channels must be positive multiples of 16");
@@ -517,21 +544,40 @@ int validate(q3tts_engine* e, const q3tts_clone_config& c) {
         return bad("block width / se_res2net_scale must be a multiple of 16");
     if (c.se_attn_channels % 16 || c.se_se_channels % 16 || c.se_dim % 16 || c.se_attn_channels < 16 || c.se_se_channels < 16 || c.se_dim < 16)
         return bad("se_attn_channels, se_se_channels, se_dim must be positive multiples of 16");
-    if (round512(3 * c.se_channels[4]) > 8192 || round512(c.se_kernels[0] * c.mel_dim) > 8192) return bad("speaker encoder GEMM depth exceeds 8192");
+    {
+        const int Cs = c.se_channels[0], C4 = c.se_channels[4], wp = Cs / c.se_res2net_scale;
+        conv("speaker TDNN", c.se_kernels[0], c.mel_dim);
+        for (int i = 1; i <= 3; ++i) {
+            conv("SE-Res2Net 1x1 conv", 1, Cs); conv("Res2Net conv", c.se_kernels[i], wp);
+            conv("squeeze-excitation conv", 1, Cs); conv("squeeze-excitation conv", 1, c.se_se_channels);
+        }
+        conv("aggregation (MFA) conv", c.se_kernels[4], 3 * (int64_t)Cs);
+        conv("attentive pooling TDNN", 1, 3 * (int64_t)C4); conv("attentive pooling conv", 1, c.se_attn_channels); conv("speaker output conv", 1, 2 * (int64_t)C4);
+        if (deep) return too_deep();
+    }
     if (c.ae_filters < 32 || c.ae_filters % 32) return bad("ae_filters must be a positive multiple of 32");
     if (c.ae_n_ratios < 1 || c.ae_n_ratios > 4) return bad("ae_n_ratios must be 1..4");
-    int C = c.ae_filters;
+    if (c.ae_kernel < 1 || c.ae_res_kernel < 1 || c.ae_last_kernel < 1) return bad("ae_kernel, ae_res_kernel, ae_last_kernel must be >= 1");
+    int64_t C = c.ae_filters;
+    conv("first audio conv (ae_kernel)", c.ae_kernel, 1);
     for (int i = 0; i < c.ae_n_ratios; ++i) {
         if (c.ae_ratios[i] < 1) return bad("ae_ratios must be >= 1");
-        if (round512(2 * c.ae_ratios[i] * C) > 8192) return bad("a strided conv's GEMM depth (2 x ratio x channels) exceeds 8192");
+        conv("residual conv (ae_res_kernel x channels)", c.ae_res_kernel, C); conv("residual 1x1 conv", 1, C / 2);
+        conv("strided conv (2 x ratio x channels)", 2 * (int64_t)c.ae_ratios[i], C);
+        if (deep) return too_deep();
         C *= 2;
     }
-    if (c.ae_kernel < 1 || c.ae_res_kernel < 1 || c.ae_last_kernel < 1 || round512(c.ae_last_kernel * C) > 8192) return bad("bad conv kernel sizes");
-    if (c.ae_hidden % 16 || c.ae_hidden < 16 || c.ae_hidden > 8192 || c.ae_d_ffn % 16 || c.ae_d_ffn < 16 || c.ae_d_ffn > 8192) return bad("ae_hidden / ae_d_ffn must be multiples of 16, <= 8192");
-    if (c.ae_n_layer < 0 || c.ae_n_layer > 64 || c.ae_n_head < 1 || c.ae_head_dim < 4 || c.ae_head_dim % 4 || c.ae_head_dim > 256 || (c.ae_n_head * c.ae_head_dim) % 16)
+    conv("last audio conv (ae_last_kernel x channels)", c.ae_last_kernel, C);
+    if (deep) return too_deep();
+    if (c.ae_hidden % 16 || c.ae_hidden < 16 || c.ae_d_ffn % 16 || c.ae_d_ffn < 16) return bad("ae_hidden / ae_d_ffn must be positive multiples of 16");
+    if (c.ae_n_layer < 0 || c.ae_n_layer > 64 || c.ae_n_head < 1 || c.ae_head_dim < 4 || c.ae_head_dim % 4 || c.ae_head_dim > 256 ||
+        ((int64_t)c.ae_n_head * c.ae_head_dim) % 16)
         return bad("bad transformer shape");
     if (c.ae_window < 1 || c.ae_window > 8192) return bad("ae_window must be 1..8192");
-    if (c.ae_down_stride < 1 || round512(2 * c.ae_down_stride * c.ae_hidden) > 8192) return bad("bad ae_down_stride");
+    if (c.ae_down_stride < 1) return bad("ae_down_stride must be >= 1");
+    conv("QKV / FC1 / VQ projection (ae_hidden)", 1, c.ae_hidden); conv("O projection (n_head x head_dim)", 1, (int64_t)c.ae_n_head * c.ae_head_dim);
+    conv("FC2 (ae_d_ffn)", 1, c.ae_d_ffn); conv("frame-rate conv (2 x ae_down_stride x ae_hidden)", 2 * (int64_t)c.ae_down_stride, c.ae_hidden);
+    if (deep) return too_deep();
     if (c.ae_vq_dim % 16 || c.ae_vq_dim < 16 || c.ae_vq_dim > 4096) return bad("ae_vq_dim must be a multiple of 16");
     if (c.ae_n_codebooks < 1 || c.ae_n_codebooks > 64 || c.ae_codebook_size < 1) return bad("bad codebook shape");
     return Q3TTS_OK;

@@ -1,6 +1,7 @@
 // q3_hooks.hip — the kernel-level test hooks q3tts_k_* of include/q3tts.h: each uploads its arguments, launches one kernel (or one engine
 // step) through the launcher the engine uses, and reads the result back. No engine code: the tests and the benchmarks of single kernels
-// call these. (The hooks of the vocoder, the clone encoders and the GGUF reader are in those files, beside the state they use.)
+// call these. (The hooks of the vocoder, the clone encoders and the GGUF reader that need an engine's state are in those files, beside it;
+// the clone quantiser's hook needs none and is here.)
 #include "q3_engine.h"
 
 #include <cstdio>
@@ -1268,4 +1269,23 @@ extern "C" int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out) {
     if (!out || n < 0) return Q3TTS_ERR_INVALID;
     q3_stdrng_f32(seed, n, out);
     return Q3TTS_OK;
+}
+
+// The clone audio encoder's quantiser (q3_clone.hip) on given operands: ps / pa [T][D], books row-major [ncb][CS][D] f32; ONE q3_launch_rvq, which
+// transposes every book with the production k_cb_transpose and runs the production k_rvq; codes [T][ncb]. pa may be NULL when ncb == 1.
+extern "C" int q3tts_k_rvq(int32_t device, const float* ps, const float* pa, int32_t T, int32_t D, const float* books, int32_t ncb, int32_t CS, int64_t* codes) {
+    if (!ps || (!pa && ncb > 1) || !books || !codes || T < 1 || T > 65536 || D < 16 || D % 16 || D > 4096 || ncb < 1 || ncb > 64 || CS < 1 || (int64_t)CS * D > ((int64_t)1 << 26))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "rvq hook: bad shape");
+    HK(hipSetDevice(device));
+    const size_t ne = (size_t)CS * D;
+    DevBuf dps, dpa, dbk, dbt, dtab, dcodes;
+    TRY(dps.put(ps, (size_t)T * D * 4)); TRY(dpa.put(pa, (size_t)T * D * 4)); TRY(dbk.put(books, (size_t)ncb * ne * 4)); TRY(dbt.alloc((size_t)ncb * ne * 4));
+    std::vector<const float*> tab(ncb);
+    for (int q = 0; q < ncb; ++q) tab[q] = (const float*)dbt.p + (size_t)q * ne;
+    TRY(dtab.put(tab.data(), (size_t)ncb * sizeof(float*))); TRY(dcodes.alloc((size_t)T * ncb * 8));
+    Q3Rvq a{}; a.ps = dps; a.pa = pa ? (const float*)dpa.p : nullptr; a.T = T; a.D = D; a.cbT = (const float* const*)dtab.p; a.ncb = ncb; a.CS = CS;
+    a.codes = (long long*)dcodes.p; a.books = dbk; a.booksT = dbt;
+    if (q3_launch_rvq(a, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "rvq hook: the launch was refused");
+    HK(hipGetLastError()); HK(hipDeviceSynchronize());
+    return dcodes.get(codes, (size_t)T * ncb * 8);
 }

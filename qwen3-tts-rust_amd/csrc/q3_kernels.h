@@ -474,6 +474,18 @@ void q3_launch_prompt_ref_frames(const int* codes, int n_frames, const float* ma
 
 void q3_launch_copy_rows(float* dst, int ldd, const float* src, int lds, int rows, int cols, hipStream_t s);
 
+// Split residual VQ of the clone audio encoder (q3_clone.hip: k_rvq): frame t takes codebook 0 on ps[t], codebooks 1.. on the
+// residual of pa[t] (pa may be NULL when ncb == 1); nearest codeword in squared Euclidean distance, ties to the smaller index; codes [T][ncb].
+// cbT: device table of the ncb codebooks in k_cb_transpose's layout [D/4][CS][4]. books (optional): row-major [ncb][CS][D], transposed into
+// booksT ([ncb] x that layout, the memory cbT's entries point into) before the quantiser runs.
+struct Q3Rvq {
+    const float* ps; const float* pa; int T, D;
+    const float* const* cbT; int ncb, CS;
+    long long* codes;
+    const float* books; float* booksT;
+};
+int q3_launch_rvq(const Q3Rvq& a, hipStream_t s);  // 0: launched; -1: refused (see its definition), nothing launched
+
 // canonical RMSNorm of rows (test hook / hidden read-back)
 void q3_launch_gather_rows(float* dst, const float* src, const int* perm, int rows, int cols, hipStream_t s);
 void q3_launch_rmsnorm_rows(const float* x, int ldx, const float* w, float eps, int d, int rows, float* out, int ldo, hipStream_t s);

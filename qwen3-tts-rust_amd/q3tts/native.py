@@ -1297,6 +1297,24 @@ def k_sample(logits, limit, temperature, top_k, top_p, r=None, device=0):
     return out
 
 
+def k_rvq(ps, pa, books, device=0):
+    """q3tts_k_rvq: the clone audio encoder's split residual VQ (k_cb_transpose + k_rvq) on ps / pa [T][D] and books [ncb][CS][D], all f32;
+    codes i64 [T][ncb]. pa may be None when ncb == 1."""
+    lib = _abi.load_library()
+    bk = np.ascontiguousarray(books, dtype=np.float32)
+    s = np.ascontiguousarray(ps, dtype=np.float32)
+    a = None if pa is None else np.ascontiguousarray(pa, dtype=np.float32)
+    ncb, CS, D = bk.shape
+    T = s.shape[0]
+    assert s.shape == (T, D) and (a is None or a.shape == (T, D))
+    codes = np.zeros((T, ncb), dtype=np.int64)
+    rc = lib.q3tts_k_rvq(device, _ptr(s, f32p), None if a is None else _ptr(a, f32p), T, D, _ptr(bk, f32p), ncb, CS,
+                         codes.ctypes.data_as(C.POINTER(C.c_int64)))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_rvq failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return codes
+
+
 def k_gguf_read(path, tensor=""):
     """One tensor of a GGUF file / the array of an .npy file as f32, through the engine's own reader (host only).
     Returns (array shaped like numpy would show it, ggml type)."""

@@ -158,6 +158,8 @@ def lib():
     L.q3o_speaker_encode.restype = C.c_int32
     L.q3o_audio_encode.argtypes = [C.POINTER(_abi.CloneConfig), C.c_uint64, f32p, C.c_int64, i32p, C.c_int32, f32p]
     L.q3o_audio_encode.restype = C.c_int32
+    L.q3o_rvq.argtypes = [f32p, f32p, C.c_int32, C.c_int32, f32p, C.c_int32, C.c_int32, i32p]
+    L.q3o_rvq.restype = C.c_int32
     u16p = C.POINTER(C.c_uint16)
     L.q3o_mfma_bf16_dot32.argtypes = [u16p, u16p, C.c_float]
     L.q3o_mfma_bf16_dot32.restype = C.c_float
@@ -506,3 +508,15 @@ def audio_encode(ccfg, seed, audio):
     n = lib().q3o_audio_encode(C.byref(ccfg), seed, ptr(a, f32p) if a.size else None, a.size, ptr(codes, i32p), cap, ptr(lat, f32p))
     assert n >= 0
     return codes[:n].copy(), lat[:n].copy()
+
+
+def rvq(ps, pa, books):
+    """Oracle split residual VQ (q3o_rvq): ps / pa [T][D], books [ncb][CS][D] -> codes int32 [T][ncb]. pa may be None when ncb == 1."""
+    bk = np.ascontiguousarray(books, dtype=np.float32)
+    s = np.ascontiguousarray(ps, dtype=np.float32)
+    a = None if pa is None else np.ascontiguousarray(pa, dtype=np.float32)
+    ncb, CS, D = bk.shape
+    codes = np.zeros((s.shape[0], ncb), dtype=np.int32)
+    rc = lib().q3o_rvq(ptr(s, f32p), None if a is None else ptr(a, f32p), s.shape[0], D, ptr(bk, f32p), ncb, CS, ptr(codes, i32p))
+    assert rc == 0
+    return codes
