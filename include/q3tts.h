@@ -1109,8 +1109,8 @@ int q3tts_k_pcm_join(int32_t device, const float* src, int32_t rows, int64_t str
  * q3tts_long_segment) and streams in order while later segments still run.
  *
  * The bits. The concatenation of all Q3TTS_EV_CHUNK payloads of a document's id is the pcm q3tts_generate_long returns for the same
- * template, the same voice, the same segments (appended ones included, in order) and the same q3tts_join_opts, with speed_permille = 0
- * and output_rate = 0: bit for bit, whatever the slot count, `ahead`, the admission order, and whatever plain requests share the
+ * template, the same voice, the same segments (appended ones included, in order) and the same q3tts_join_opts, speed_permille
+ * and output_rate (below): bit for bit, whatever the slot count, `ahead`, the admission order, and whatever plain requests share the
  * session. In an i16 session the chunks are the Q3TTS_PCM_I16 conversion of that row (k_pcm_pack's, applied after the fade's multiply).
  * Where the chunk boundaries of a document fall depends on when its segments found slots: only the concatenation is contract.
  *
@@ -1130,7 +1130,7 @@ int q3tts_k_pcm_join(int32_t device, const float* src, int32_t rows, int64_t str
  * (FAILED) at the boundary after; its other segments are cancelled, chunks already delivered stay delivered, other requests and
  * documents are unaffected.
  * q3tts_session_document_info (thread-safe): info[0, min(cap, *n_known)) = lo, hi, begin, end, n_frames, hit_eos, n_native, status of the
- * segments delivered so far, the values q3tts_generate_long reports (out_begin / out_end equal begin / end); *n_known = how many there
+ * segments delivered so far, the values q3tts_generate_long reports (out_begin / out_end equal begin / end without a speed or rate); *n_known = how many there
  * are, *n_delivered = the samples handed out so far. This is where a subtitle track reads its times. Readable until the session closes.
  * Scheduling. Segments are internal session requests behind the prefix: they queue in the session's FIFO behind what is already there
  * and compete for slots as plain requests do; their own events are not published. Segment j is eligible iff j < head + ahead, head the
@@ -1145,8 +1145,8 @@ int q3tts_k_pcm_join(int32_t device, const float* src, int32_t rows, int64_t str
  * q3tts_generate_long); join options outside their ranges; ahead outside 0..64; a break kind outside 0..4; both or neither of voice and
  * prefix; a template with a prompt; append to an unknown, closed or finished document. A document whose delivered length would pass
  * 2^28 samples fails (FAILED, Q3TTS_ERR_INVALID) at the segment that would pass it.
- * Not built: speed and output rate for a streamed document, pacing by listener credit, q3tts_node_*, a per-segment
- * voice, text_stream segments, documents outside a session.
+ * Not built: pacing by listener credit, q3tts_node_*, a per-segment voice, a per-segment speed, text_stream segments,
+ * documents outside a session. Speed and output rate: below, behind q3tts_doc_opts.
  *
  * The rule. Only the head emits: the first segment not yet fully delivered. Of the head it uses n (its valid samples so far), first / last
  * (the loud-block edges of x[0, n) so far, 2.'s rule), closed (n is final) and e (the piece samples already emitted).
@@ -1165,8 +1165,45 @@ int q3tts_k_pcm_join(int32_t device, const float* src, int32_t rows, int64_t str
  * Segment j may run iff j < head + ahead, and keeps its samples in document row j mod ahead. A delivered length that would pass 2^28
  * samples is Q3TTS_ERR_INVALID at the segment that would pass it. Where the chunk boundaries of a document fall is not contract; the
  * concatenation is. i16: k_pcm_pack's conversion of the f32 value, applied after the fade's multiply. */
-typedef struct q3tts_doc_opts { q3tts_join_opts join; int32_t ahead /*0: 8; 1..64*/; int32_t open /*1: more segments follow*/; } q3tts_doc_opts;
+typedef struct q3tts_doc_opts { q3tts_join_opts join; int32_t ahead /*0: 8; 1..64*/; int32_t open /*1: more segments follow*/;
+    int32_t speed_permille /*0 or 1000: off; 500..2000*/; int32_t output_rate /*0 or the vocoder's rate: off; 4000..96000*/; } q3tts_doc_opts;
 #define Q3TTS_EV_SEGMENT 6
+/* Speed and output rate of a document (speed_permille, output_rate; both 0: everything above, launch for launch).
+ * The bits. The concatenation of a document's EV_CHUNK payloads is the pcm q3tts_generate_long returns for the same template, voice,
+ * segments, join options, speed_permille and output_rate — resample(time_stretch(J)), J the join — bit for bit, whatever the slot count,
+ * `ahead`, the admission order, the ring sizes below and the neighbouring requests. In an i16 session the chunks are k_pcm_pack's
+ * conversion of that f32 row, applied at the last stage. Chunk boundaries remain outside the contract.
+ * Times. q3tts_session_document_info and EV_SEGMENT: begin / end stay in J (24 kHz); out_begin / out_end are ceil(s 1000 / speed), then
+ * ceil(s L / M), exactly as q3tts_generate_long reports them. EV_SEGMENT of segment j is published at the boundary whose chunk brings the
+ * delivered output count to at least out_end_j; its result.n_samples is out_end - out_begin. result.sample_rate, EV_DONE's total and
+ * *n_delivered are in output samples at the output rate.
+ * The pipeline. J has no row (a document may be 2^28 samples long), so up to three stages run per boundary, all in front of the
+ * boundary's one device-to-host copy: (1) the plan's pieces go into a per-document f32 ring RJ that holds J at positions mod C_J (a
+ * piece or pause that crosses the wrap is split in two); (2) with a speed, k_doc_tempo — k_pcm_tempo's arithmetic reading RJ mod C_J —
+ * writes every decidable frame (need_k + HOLD <= |J| so far, or J is whole) into a second ring RT mod C_T; (3) with a rate,
+ * k_doc_resample — k_pcm_resample's arithmetic reading RT (or RJ without a speed) — writes the decidable outputs into the staging buffer
+ * behind the plain chunks and the edge tables; without a rate the stretched samples go from RT to staging as k_doc_emit pieces.
+ * Flow control is host arithmetic over three counts (samples joined, frames decided, outputs delivered); nothing is read back. No stage
+ * overwrites a ring position that an undecided frame or output may still read: the lower bounds are a_{k-1} + DMIN for the next
+ * undecided frame k and (m M) div L - H for the next output m. The join is clipped to the free space of RJ, the stretch to that of RT,
+ * the exit to the staging room; what does not fit follows at later boundaries, which run while any stage holds undelivered audio:
+ * while a stage moved at the last boundary, or decidable frames or outputs are left that only a ring or the staging room held back.
+ * A document's output count is bounded as its joined length is: one that would pass 2^31 - 1 output samples (speed 500 at 96 kHz can)
+ * fails with Q3TTS_ERR_INVALID at the boundary that would pass it. Ring positions: J stays below 2^28, the stretched audio below 2^29.
+ * An open document whose segments are all delivered keeps the held-back tail (the stretch's HOLD plus at most a hop, the resampler's
+ * H) and stays silent; closing it flushes the tail in the final chunk.
+ * Ring capacities are multiples of 4 and at least the span over which one frame, or one output, becomes decidable: */
+#define Q3_DOC_RING_MIN_J_SPEED 1280   /* RJ under a speed: max over k, s of need_k + HOLD - (a_{k-1} + DMIN) = 256 * 2000 / 1000 + 640 + 128 */
+#define Q3_DOC_RING_MIN_T_SPEED 256    /* RT without a rate: one frame (a hop) */
+#define Q3_DOC_RING_MIN_RATE(H, L, M)   ((2 * (H) + 1 + ((M) + (L) - 1) / (L) + 3) & ~3)         /* the resampler's source: T = 2 H + 1 taps and one input step */
+#define Q3_DOC_RING_MIN_T_RATE(H, L, M) ((2 * (H) + 1 + ((M) + (L) - 1) / (L) + 256 + 3) & ~3)   /* RT under a rate: that, and the frame that feeds it */
+/* A session sizes a ring as its minimum plus what one boundary can produce (twice one slot's chunk window, stretched for RT), so a
+ * boundary is not throttled by the ring: at the full shape under 100 KB for RJ and under 200 KB for RT at speed 500. The rings are
+ * allocated with the document's rows (same check against the free memory, same Q3TTS_ERR_OOM message with both numbers), counted in
+ * q3tts_k_device_bytes and freed with them.
+ * Refusals: a speed outside {0, 1000, 500..2000} or a rate outside {0, 4000..96000} is Q3TTS_ERR_INVALID (q3tts_k_doc_rules names the
+ * field); a rate pair the resampler's plan refuses is Q3TTS_ERR_UNSUPPORTED; an engine-level q3tts_set_speed / q3tts_set_output_rate
+ * still refuses every document with Q3TTS_ERR_STATE: the document carries its own values, as q3tts_generate_long's opts do. */
 void q3tts_doc_default_opts(q3tts_doc_opts*);
 int q3tts_session_submit_document(q3tts_session* s, const q3tts_request* tmpl, const q3tts_prompt_desc* voice, q3tts_prefix* prefix,
                                   const q3tts_long_segment* segs, int32_t n_segs, const q3tts_doc_opts* opts, uint64_t* id);
@@ -1177,8 +1214,9 @@ int q3tts_session_document_info(q3tts_session* s, uint64_t id, q3tts_long_info* 
  * rows are counted in q3tts_k_device_bytes from the boundary that accepts it to the one that ends it. */
 int q3tts_k_session_doc_mem_cap(q3tts_session* s, int64_t bytes);
 /* The rules of a well-formed document as far as no engine is needed to say them (host only): Q3TTS_ERR_STATE while an engine-level speed
- * or output rate is set (engine_speed / engine_rate != 0: a streamed document has neither); Q3TTS_ERR_INVALID for NULL opts, join
- * options outside their ranges, ahead outside 0..64, open outside 0 / 1, n_segs outside 1..1024 (0 allowed with open = 1), a break kind
+ * or output rate is set (engine_speed / engine_rate != 0: a document carries its own); Q3TTS_ERR_INVALID for NULL opts, join
+ * options outside their ranges, ahead outside 0..64, speed_permille outside {0, 500..2000}, output_rate outside {0, 4000..96000},
+ * open outside 0 / 1, n_segs outside 1..1024 (0 allowed with open = 1), a break kind
  * outside 0..4, both or neither of voice and prefix. msg receives the rule, at most cap - 1 characters (may be NULL). */
 int q3tts_k_doc_rules(const q3tts_doc_opts* opts, const int32_t* kinds, int32_t n_segs, int32_t have_voice, int32_t have_prefix,
                       int32_t engine_speed, int32_t engine_rate, char* msg, int32_t cap);
@@ -1204,6 +1242,28 @@ int q3tts_k_doc_stream(int32_t device, const float* src, int32_t rows, int64_t s
                        const int32_t* sched_n, int32_t sched_stride, const q3tts_join_opts* opts, int32_t rate, int32_t ahead, int32_t lag,
                        int64_t staging, int64_t dst0, int32_t format, int32_t check_rows, void* out, int64_t out_cap, int64_t* n_out,
                        int64_t* chunks, int32_t chunk_cap, int32_t* n_bounds, int64_t* plan, int64_t* bad);
+/* The same with a speed and / or an output rate (at least one): scan -> plan -> join into RJ -> stretch into RT -> exit, boundary by
+ * boundary, on uploaded rows; `rate` is the rows' rate and the resampler's input rate. ring_j / ring_t: the rings' capacities (0: the
+ * minimum; below the minimum or no multiple of 4: Q3TTS_ERR_INVALID). `staging` and chunks[b] are in OUTPUT samples. A segment whose
+ * schedule repeats its last length stays open at that length until the schedule's last entry (a segment closed late). delta
+ * [delta_cap] receives delta_k of every frame (*n_frames of them; NULL with delta_cap = 0). *bad counts every staging byte outside
+ * the emitted range that lost its fill. That no ring element was overwritten while a later read still needed it is checked by the final
+ * equality, not by a shadow of J: the tests compare out with the one-shot composition over rings at their minimum. */
+int q3tts_k_doc_stream_rate(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* kinds, const int32_t* sched,
+                            const int32_t* sched_n, int32_t sched_stride, const q3tts_join_opts* opts, int32_t rate, int32_t ahead, int32_t lag,
+                            int64_t staging, int64_t dst0, int32_t format, int32_t check_rows, void* out, int64_t out_cap, int64_t* n_out,
+                            int64_t* chunks, int32_t chunk_cap, int32_t* n_bounds, int64_t* plan, int64_t* bad, int32_t speed_permille,
+                            int32_t output_rate, int64_t ring_j, int64_t ring_t, int32_t* delta, int32_t delta_cap, int32_t* n_frames);
+/* One boundary of the pipeline's flow control (host only). state [4] = samples joined, J whole, frames decided, outputs delivered (all
+ * zero before the first call; updated). The join has `want` more samples to hand out (fin_if_all: J is whole once all of them are);
+ * room_out: the staging room in output samples; ring_j / ring_t as above. out [13] = the join's room, samples joined, k_from, k_to,
+ * stretched samples after them, the exit's valid source samples, whether those are all, the first output, the count, whether the
+ * document is now wholly delivered, the two minimum capacities, and `pending`: decidable frames or outputs are left that only the
+ * free space of RT or room_out held back — the worker must not sleep then, whether or not anything moved at this boundary. */
+int q3tts_k_doc_ring_plan(int32_t speed_permille, int32_t rate_in, int32_t rate_out, int64_t ring_j, int64_t ring_t, int64_t* state,
+                          int64_t want, int32_t fin_if_all, int64_t room_out, int64_t* out);
+/* out_begin / out_end as the session computes them (host only): *out = position pos of J through ceil(s 1000 / speed), then ceil(s L / M) */
+int q3tts_k_doc_out_pos(int64_t pos, int32_t speed_permille, int32_t rate_in, int32_t rate_out, int64_t* out);
 
 #ifdef __cplusplus
 }

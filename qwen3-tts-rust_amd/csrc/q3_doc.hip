@@ -197,13 +197,82 @@ int q3_doc_plan(const q3tts_join_opts& o, int rate, const Q3DocSegNow* segs, int
     return Q3TTS_OK;
 }
 
+// ---- the pipeline of a document with a speed or a rate: flow control (host, pure) ----------------------------------------------
+static_assert(Q3_DOC_RING_MIN_J_SPEED == Q3_TEMPO_HS * Q3_TEMPO_MAX / 1000 + Q3_TEMPO_HOLD - Q3_TEMPO_DMIN && Q3_DOC_RING_MIN_T_SPEED == Q3_TEMPO_HS,
+              "the header's ring minima are written out from the time-stretch's constants");
+namespace {
+constexpr long long Hs = Q3_TEMPO_HS;
+inline long long tempo_a(long long k, int s) { return (k * Hs * s) / 1000; }
+// the lowest position of the exit's source that output m may read
+inline long long rate_low(const Q3DocRing& r) { return std::max(0ll, (r.m * r.M) / r.L - r.H); }
+}  // namespace
+
+long long q3_doc_ring_min_j(int speed, int L, int M, int H) { return speed ? Q3_DOC_RING_MIN_J_SPEED : (L ? Q3_DOC_RING_MIN_RATE(H, L, M) : 0); }
+long long q3_doc_ring_min_t(int speed, int L, int M, int H) { return !speed ? 0 : (L ? Q3_DOC_RING_MIN_T_RATE(H, L, M) : Q3_DOC_RING_MIN_T_SPEED); }
+
+// The lowest position of RJ that may still be read: with a speed the next undecided frame k reads its template from p_{k-1} + Hs and
+// its candidates from a_k + DMIN, both >= a_{k-1} + DMIN (delta >= DMIN, a ascends); without one, output m reads from (m M) div L - H.
+long long q3_doc_ring_room(const Q3DocRing& r) {
+    long long low;
+    if (r.speed) low = r.kt == 0 ? 0 : std::max(0ll, tempo_a(r.kt - 1, r.speed) + Q3_TEMPO_DMIN);
+    else low = rate_low(r);
+    return std::max(0ll, low + r.cj - r.nj);
+}
+
+void q3_doc_ring_step(Q3DocRing* r, long long joined, bool fin_j, long long room_out, Q3DocRingStep* out) {
+    r->nj += joined; r->fin_j = fin_j ? 1 : 0;
+    *out = Q3DocRingStep{};
+    long long nx = r->nj; bool fin_x = fin_j;
+    if (r->speed) {
+        // frame k writes RT[k Hs, (k + 1) Hs): it must end at or below low + ct, low the lowest position the exit may still read
+        const long long low_t = r->L ? rate_low(*r) : r->m;
+        const long long all = q3_tempo_frames(r->nj, r->speed, fin_j), fit = (low_t + r->ct) / Hs;
+        const long long k_to = std::max(r->kt, std::min(all, fit));
+        const long long NT = q3_tempo_N(r->nj, r->speed);
+        out->k_from = (int32_t)r->kt; out->k_to = (int32_t)k_to;
+        r->kt = k_to;
+        fin_x = fin_j && k_to == all;
+        nx = fin_j ? std::min(k_to * Hs, NT) : k_to * Hs;
+        out->nt = nx;
+    }
+    const long long avail = r->L ? (fin_x ? q3_resample_N(nx, r->L, r->M) : q3_resample_D(nx, r->L, r->M, r->H)) : nx;
+    out->nx = nx; out->fin_x = fin_x ? 1 : 0;
+    out->first = r->m; out->count = std::max(0ll, std::min(avail - r->m, room_out));
+    r->m += out->count;
+    out->all_out = fin_x && r->m == avail ? 1 : 0;
+    out->pending = (r->m < avail || (r->speed && r->kt < q3_tempo_frames(r->nj, r->speed, fin_j))) ? 1 : 0;
+}
+
+void q3_doc_ring_put(const Q3DocOut& p, const float* from, long long pos, long long C, std::vector<Q3DocPiece>* ents) {
+    const long long at = pos % C, c1 = std::min(p.count, C - at);
+    if (c1 > 0) ents->push_back(Q3DocPiece{from, p.j0, p.L, at, (int32_t)c1, p.F});
+    if (p.count > c1) ents->push_back(Q3DocPiece{from ? from + c1 : nullptr, p.j0 + c1, p.L, 0, (int32_t)(p.count - c1), p.F});
+}
+
+void q3_doc_ring_get(const float* ring, long long C, long long first, long long count, long long at, std::vector<Q3DocPiece>* ents) {
+    const long long from = first % C, c1 = std::min(count, C - from);
+    if (c1 > 0) ents->push_back(Q3DocPiece{ring + from, 0, LLONG_MAX, at, (int32_t)c1, 0});
+    if (count > c1) ents->push_back(Q3DocPiece{ring, 0, LLONG_MAX, at + c1, (int32_t)(count - c1), 0});
+}
+
+void q3_launch_doc_emit_all(const std::vector<Q3DocPiece>& ents, int i16, void* dst, hipStream_t s) {
+    for (size_t g0 = 0; g0 < ents.size(); g0 += Q3_DOC_MAX_ENT) {
+        Q3DocPiecePack pk{};
+        const int n = (int)std::min<size_t>(ents.size() - g0, Q3_DOC_MAX_ENT);
+        for (int i = 0; i < n; ++i) pk.e[i] = ents[g0 + i];
+        q3_launch_doc_emit(pk, n, i16, dst, s);
+    }
+}
+
 int q3_doc_rules(const q3tts_doc_opts& o, const int32_t* kinds, int n_segs, bool have_voice, bool have_prefix, int engine_speed, int engine_rate,
                  const char** msg) {
     *msg = nullptr;
-    if (engine_speed) { *msg = "document: q3tts_set_speed is set on the engine (a streamed document has no speed; q3tts_set_speed(engine, 0) first)"; return Q3TTS_ERR_STATE; }
-    if (engine_rate) { *msg = "document: q3tts_set_output_rate is set on the engine (a streamed document has no output rate; q3tts_set_output_rate(engine, 0) first)"; return Q3TTS_ERR_STATE; }
+    if (engine_speed) { *msg = "document: q3tts_set_speed is set on the engine (a document carries its own speed_permille; q3tts_set_speed(engine, 0) first)"; return Q3TTS_ERR_STATE; }
+    if (engine_rate) { *msg = "document: q3tts_set_output_rate is set on the engine (a document carries its own output_rate; q3tts_set_output_rate(engine, 0) first)"; return Q3TTS_ERR_STATE; }
     if (q3_join_opts_rules(o.join, msg) != Q3TTS_OK) return Q3TTS_ERR_INVALID;
     if (o.ahead < 0 || o.ahead > 64) *msg = "document: ahead is 0 (the default, 8) or 1..64";
+    else if (o.speed_permille != 0 && (o.speed_permille < Q3_TEMPO_MIN || o.speed_permille > Q3_TEMPO_MAX)) *msg = "document: speed_permille is 0 or 1000 (off), or 500..2000";
+    else if (o.output_rate != 0 && (o.output_rate < 4000 || o.output_rate > 96000)) *msg = "document: output_rate is 0 (off) or 4000..96000 Hz";
     else if (o.open != 0 && o.open != 1) *msg = "document: open is 0 or 1";
     else if (n_segs > Q3_JOIN_MAX_SEG || n_segs < (o.open ? 0 : 1)) *msg = "document: n_segs is 1..1024 per call (0 only with open = 1)";
     else if (n_segs > 0 && !kinds) *msg = "document: the segments are missing";
@@ -258,5 +327,49 @@ extern "C" int q3tts_k_doc_plan(const q3tts_join_opts* opts, int32_t rate, const
         p[0] = dn[i].seg; p[1] = dn[i].lo; p[2] = dn[i].hi; p[3] = dn[i].begin; p[4] = dn[i].end;
     }
     state[0] = st.head; state[1] = st.e; state[2] = st.pause_left; state[3] = st.have_prev; state[4] = st.kmax; state[5] = st.delivered; state[6] = st.begin;
+    return Q3TTS_OK;
+}
+
+// One boundary of the pipeline's flow control (host only): what q3_doc_ring_room / q3_doc_ring_step say for a join that has `want`
+// more samples to hand out (fin_if_all: J is whole once they all are).
+extern "C" int q3tts_k_doc_ring_plan(int32_t speed_permille, int32_t rate_in, int32_t rate_out, int64_t ring_j, int64_t ring_t, int64_t* state,
+                                     int64_t want, int32_t fin_if_all, int64_t room_out, int64_t* out) {
+    if (!state || !out || want < 0 || room_out < 0 || ring_j < 0 || ring_t < 0) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc ring plan hook: bad arguments");
+    const int speed = (speed_permille == 0 || speed_permille == 1000) ? 0 : speed_permille;
+    if (speed && (speed < Q3_TEMPO_MIN || speed > Q3_TEMPO_MAX)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc ring plan hook: speed_permille is 0 or 1000 (off), or 500..2000");
+    Q3DocRing r{};
+    r.speed = speed;
+    if (rate_out != 0 && rate_out != rate_in) {
+        int L = 0, M = 0, H = 0, T = 0;
+        const int rc = q3_resample_plan(rate_in, rate_out, &L, &M, &H, &T);
+        if (rc != Q3TTS_OK) return q3_set_err(nullptr, rc, "doc ring plan hook: the rate pair is refused");
+        r.L = L; r.M = M; r.H = H;
+    }
+    if (!r.speed && !r.L) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc ring plan hook: neither a speed nor a rate");
+    const long long mj = q3_doc_ring_min_j(r.speed, r.L, r.M, r.H), mt = q3_doc_ring_min_t(r.speed, r.L, r.M, r.H);
+    r.cj = ring_j ? ring_j : mj; r.ct = ring_t ? ring_t : mt;
+    if (r.cj < mj || r.ct < mt || (r.cj & 3) || (r.ct & 3))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc ring plan hook: a ring is below its minimum (" + std::to_string(mj) + ", " + std::to_string(mt) + ") or no multiple of 4");
+    r.nj = state[0]; r.fin_j = (int32_t)state[1]; r.kt = state[2]; r.m = state[3];
+    if (r.nj < 0 || r.kt < 0 || r.m < 0 || (r.fin_j && want > 0)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc ring plan hook: bad state (or J is whole and more is to be joined)");
+    const long long room = q3_doc_ring_room(r), joined = std::min<long long>(want, room);
+    Q3DocRingStep st{};
+    q3_doc_ring_step(&r, joined, r.fin_j || (fin_if_all && joined == want), room_out, &st);
+    out[0] = room; out[1] = joined; out[2] = st.k_from; out[3] = st.k_to; out[4] = st.nt; out[5] = st.nx; out[6] = st.fin_x; out[7] = st.first;
+    out[8] = st.count; out[9] = st.all_out; out[10] = mj; out[11] = mt; out[12] = st.pending;
+    state[0] = r.nj; state[1] = r.fin_j; state[2] = r.kt; state[3] = r.m;
+    return Q3TTS_OK;
+}
+
+// out_begin / out_end of q3tts_session_document_info: a position of J through the document's speed and rate maps (host only)
+extern "C" int q3tts_k_doc_out_pos(int64_t pos, int32_t speed_permille, int32_t rate_in, int32_t rate_out, int64_t* out) {
+    const int speed = (speed_permille == 0 || speed_permille == 1000) ? 0 : speed_permille;
+    if (!out || pos < 0 || pos > (1ll << 40) || (speed && (speed < Q3_TEMPO_MIN || speed > Q3_TEMPO_MAX))) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc out pos hook: bad arguments");
+    int L = 0, M = 0, H = 0, T = 0;
+    if (rate_out != 0 && rate_out != rate_in) {
+        const int rc = q3_resample_plan(rate_in, rate_out, &L, &M, &H, &T);
+        if (rc != Q3TTS_OK) return q3_set_err(nullptr, rc, "doc out pos hook: the rate pair is refused");
+    }
+    *out = q3_doc_out_pos(pos, speed, L, M);
     return Q3TTS_OK;
 }

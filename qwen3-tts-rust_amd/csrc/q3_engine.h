@@ -377,6 +377,39 @@ int q3_doc_plan(const q3tts_join_opts& o, int rate, const Q3DocSegNow* segs, int
 // Q3TTS_ERR_STATE (an engine-level speed or output rate is set) or Q3TTS_ERR_INVALID, with *msg naming the rule
 int q3_doc_rules(const q3tts_doc_opts& o, const int32_t* kinds, int n_segs, bool have_voice, bool have_prefix, int engine_speed, int engine_rate,
                  const char** msg);
+// A document with a speed or an output rate ("the pipeline"): join -> ring RJ -> [stretch -> ring RT] -> exit into the
+// staging buffer. Every stage's progress is a host count, so flow control reads nothing back: nj samples joined (fin_j: J is whole), kt
+// frames decided, m outputs delivered. q3_doc_ring_room: what the join may write now without passing the lowest position a frame or an
+// output not yet decided may read. q3_doc_ring_step: after the join has brought nj up by `joined`, the frames to stretch (clipped to the
+// free space of RT) and the outputs to deliver (clipped to room_out, the staging room in output samples); updates r.
+struct Q3DocRing {
+    int32_t speed, L, M, H;  // speed 0: no stretch; L 0: no resampler (H 0 then)
+    long long cj, ct;        // the rings' capacities in samples, multiples of 4 (ct: 0 without a speed)
+    long long nj, kt, m;
+    int32_t fin_j, pad;
+};
+struct Q3DocRingStep {
+    int32_t k_from, k_to;    // k_doc_tempo's frames (none: equal)
+    long long nt;            // the stretched samples there are after them (the launch's n_out)
+    long long nx;            // the exit's source: valid samples ...
+    int32_t fin_x, all_out;  // ... all there will be; every output of the document is delivered with this step
+    long long first, count;  // the exit's outputs
+    int32_t pending, pad;    // decidable work is left that needs no new input: frames that did not fit RT, outputs that did not fit room_out
+};
+long long q3_doc_ring_min_j(int speed, int L, int M, int H);  // Q3_DOC_RING_MIN_* (include/q3tts.h) for these options
+long long q3_doc_ring_min_t(int speed, int L, int M, int H);
+long long q3_doc_ring_room(const Q3DocRing& r);
+void q3_doc_ring_step(Q3DocRing* r, long long joined, bool fin_j, long long room_out, Q3DocRingStep* out);
+// k_doc_emit entries around a ring of C samples, split in two where they cross the wrap (count <= C): a plan's piece (from: its first
+// sample, NULL for a pause) to stream position pos of the ring the launch writes, and samples [first, first + count) of `ring`, bit
+// copies, to dst[at, ...). q3_launch_doc_emit_all: the entries in launches of at most Q3_DOC_MAX_ENT.
+void q3_doc_ring_put(const Q3DocOut& p, const float* from, long long pos, long long C, std::vector<Q3DocPiece>* ents);
+void q3_doc_ring_get(const float* ring, long long C, long long first, long long count, long long at, std::vector<Q3DocPiece>* ents);
+void q3_launch_doc_emit_all(const std::vector<Q3DocPiece>& ents, int i16, void* dst, hipStream_t s);
+inline long long q3_doc_out_pos(long long s, int speed, int L, int M) {  // a position of J through the speed and rate maps
+    if (speed) s = q3_tempo_N(s, speed);
+    return L ? q3_resample_N(s, L, M) : s;
+}
 // pinned host memory of a result's PCM (q3_generate.hip's pool): what q3tts_result_free gives back
 float* q3_pin_alloc(size_t bytes);
 void q3_pin_free(float* p);

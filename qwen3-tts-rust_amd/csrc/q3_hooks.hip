@@ -1165,11 +1165,13 @@ extern "C" int q3tts_k_pcm_join(int32_t device, const float* src, int32_t rows, 
     return time_launches(iters, [&] { q3_launch_pcm_join(s, (size_t)stride, sg, rows, span, o, nullptr); }, mean_ms);
 }
 
-// The streaming join boundary by boundary (q3_doc.hip): a model of a session in which the rows are the segments' PCM rows
-extern "C" int q3tts_k_doc_stream(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* kinds, const int32_t* sched,
-                                  const int32_t* sched_n, int32_t sched_stride, const q3tts_join_opts* opts, int32_t rate, int32_t ahead, int32_t lag,
-                                  int64_t staging, int64_t dst0, int32_t format, int32_t check_rows, void* out, int64_t out_cap, int64_t* n_out,
-                                  int64_t* chunks, int32_t chunk_cap, int32_t* n_bounds, int64_t* plan, int64_t* bad) {
+// The streaming join boundary by boundary (q3_doc.hip): a model of a session in which the rows are the segments' PCM rows. With a speed
+// or an output rate (q3tts_k_doc_stream_rate) the pieces go into the ring RJ and the pipeline's other stages run behind the join.
+static int doc_stream_run(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* kinds, const int32_t* sched,
+                          const int32_t* sched_n, int32_t sched_stride, const q3tts_join_opts* opts, int32_t rate, int32_t ahead, int32_t lag,
+                          int64_t staging, int64_t dst0, int32_t format, int32_t check_rows, void* out, int64_t out_cap, int64_t* n_out,
+                          int64_t* chunks, int32_t chunk_cap, int32_t* n_bounds, int64_t* plan, int64_t* bad, int32_t speed_permille,
+                          int32_t output_rate, int64_t ring_j, int64_t ring_t, int32_t* delta, int32_t delta_cap, int32_t* n_frames) {
     if (!src || !kinds || !sched || !sched_n || !opts || !out || !n_out || !chunks || !n_bounds || !plan || !bad || rows <= 0 || rows > Q3_JOIN_MAX_SEG ||
         stride <= 0 || stride > (1 << 28) || sched_stride <= 0 || rate < 1000 || ahead < 1 || ahead > Q3_DOC_MAX_ENT || (lag != 0 && lag != 1) ||
         dst0 < 0 || staging <= dst0 || staging > (1 << 28) || (format != 0 && format != 1) || out_cap < 0 || chunk_cap <= 0)
@@ -1183,7 +1185,43 @@ extern "C" int q3tts_k_doc_stream(int32_t device, const float* src, int32_t rows
             if (v < 0 || v > stride || (k > 0 && v < sched[(size_t)i * sched_stride + k - 1])) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc stream hook: a row's valid lengths must ascend inside its row");
         }
     }
+    // the pipeline of a document with a speed or a rate: its flow control state, the resampler's table, the rings
+    Q3DocRing rg{};
+    Q3Resamp rs{};
+    std::vector<float> rtab;
+    rg.speed = (speed_permille == 0 || speed_permille == 1000) ? 0 : speed_permille;
+    if (rg.speed && (rg.speed < Q3_TEMPO_MIN || rg.speed > Q3_TEMPO_MAX)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc stream hook: speed_permille is 0 or 1000 (off), or 500..2000");
+    if (output_rate != 0 && output_rate != rate) {
+        const int prc = q3_resample_table(rate, output_rate, &rs.L, &rs.M, &rs.H, rtab);
+        if (prc != Q3TTS_OK) return q3_set_err(nullptr, prc, "doc stream hook: the rate pair is refused");
+        rs.rate_in = rate; rs.rate_out = output_rate; rs.T = 2 * rs.H + 1;
+        rg.L = rs.L; rg.M = rs.M; rg.H = rs.H;
+    }
+    const bool ringed = rg.speed || rg.L;
+    if (ringed) {
+        const long long mj = q3_doc_ring_min_j(rg.speed, rg.L, rg.M, rg.H), mt = q3_doc_ring_min_t(rg.speed, rg.L, rg.M, rg.H);
+        rg.cj = ring_j ? ring_j : mj; rg.ct = ring_t ? ring_t : mt;
+        if (rg.cj < mj || rg.ct < mt || (rg.cj & 3) || (rg.ct & 3) || rg.cj > (1 << 28) || rg.ct > (1 << 28) || delta_cap < 0 || (delta_cap > 0 && !delta))
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc stream hook: a ring is below its minimum (" + std::to_string(mj) + ", " + std::to_string(mt) + ") or no multiple of 4");
+    }
     HK(hipSetDevice(device));
+    DevBuf rj, rt, dw, dpl, dd, dtab;
+    if (ringed) {
+        TRY(rj.alloc(sizeof(float) * (size_t)rg.cj)); HK(hipMemset(rj.p, 0xFF, sizeof(float) * (size_t)rg.cj));
+        if (rg.speed) {
+            std::vector<float> w;
+            q3_tempo_window(w);
+            TRY(rt.alloc(sizeof(float) * (size_t)rg.ct)); HK(hipMemset(rt.p, 0xFF, sizeof(float) * (size_t)rg.ct));
+            TRY(dw.put(w.data(), sizeof(float) * w.size())); TRY(dpl.alloc(sizeof(long long)));
+            TRY(dd.alloc(sizeof(int32_t) * (size_t)std::max(delta_cap, 1))); HK(hipMemset(dd.p, 0x7F, sizeof(int32_t) * (size_t)std::max(delta_cap, 1)));
+        }
+        if (rg.L) {
+            const std::vector<float> dl = q3_resample_device_layout(rtab, rs.L, rs.M, rs.T);
+            TRY(dtab.put(dl.data(), sizeof(float) * dl.size()));
+            rs.tab = dtab;
+        }
+    }
+    bool all_out = false;
     const size_t es = format ? 2 : 4, dstride = ((size_t)stride + 3) & ~(size_t)3;
     std::vector<int32_t> ed((size_t)2 * rows);
     for (int i = 0; i < rows; ++i) { ed[2 * i] = INT32_MAX; ed[2 * i + 1] = -1; }
@@ -1202,7 +1240,7 @@ extern "C" int q3tts_k_doc_stream(int32_t device, const float* src, int32_t rows
     long long total = 0;
     int nbd = 0;
     *bad = 0;
-    while (st.head < rows) {
+    while (st.head < rows || (ringed && !all_out)) {
         if (nbd >= chunk_cap) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc stream hook: more boundaries than chunk_cap");
         Q3DocScanPack sp{};
         int ns = 0;
@@ -1224,11 +1262,35 @@ extern "C" int q3tts_k_doc_stream(int32_t device, const float* src, int32_t rows
         }
         if (!lag) for (int i = 0; i < rows; ++i) now[i] = Q3DocSegNow{n[i], ed[2 * i], ed[2 * i + 1], closed[i], kinds[i]};
         std::vector<Q3DocOut> pc; std::vector<Q3DocDone> dn;
-        const int prc = q3_doc_plan(*opts, rate, lag ? prev.data() : now.data(), rows, staging - dst0, &st, &pc, &dn);
+        const int prc = q3_doc_plan(*opts, rate, lag ? prev.data() : now.data(), rows, ringed ? q3_doc_ring_room(rg) : staging - dst0, &st, &pc, &dn);
         if (prc != Q3TTS_OK) return q3_set_err(nullptr, prc, "document: the delivered length would pass 2^28 samples at segment " + std::to_string(st.head));
         for (const Q3DocDone& d : dn) { int64_t* p = plan + 4 * d.seg; p[0] = d.lo; p[1] = d.hi; p[2] = d.begin; p[3] = d.end; }
         HK(hipMemcpy(stg.p, fill.data(), fill.size(), hipMemcpyHostToDevice));
         long long cur = dst0;
+        if (ringed) {  // join into RJ, stretch into RT, exit into the staging buffer: three stages in stream order
+            std::vector<Q3DocPiece> ents;
+            long long pos = rg.nj;
+            for (const Q3DocOut& p : pc) {
+                q3_doc_ring_put(p, p.seg < 0 ? nullptr : (const float*)dr + (size_t)(p.seg % ahead) * dstride + p.src, pos, rg.cj, &ents);
+                pos += p.count;
+            }
+            q3_launch_doc_emit_all(ents, 0, rj.p, nullptr);
+            Q3DocRingStep rp{};
+            q3_doc_ring_step(&rg, pos - rg.nj, st.head >= rows, staging - dst0, &rp);
+            if (rg.speed) q3_launch_doc_tempo(rj, rg.cj, rt, rg.ct, dpl, dw, rg.speed, rg.nj, rp.k_from, rp.k_to, rp.nt, delta_cap > 0 ? (int32_t*)dd : nullptr, (size_t)delta_cap, nullptr);
+            const float* xr = rg.speed ? (const float*)rt : (const float*)rj;
+            const long long cx = rg.speed ? rg.ct : rg.cj;
+            if (rg.L) {
+                if (q3_launch_doc_resample(xr, cx, rp.nx, rp.fin_x != 0, rp.first, rp.count, rs, format, stg.p, dst0, nullptr) != 0)
+                    return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, "doc stream hook: the input span of one tile does not fit the LDS");
+            } else {
+                ents.clear();
+                q3_doc_ring_get(xr, cx, rp.first, rp.count, dst0, &ents);
+                q3_launch_doc_emit_all(ents, format, stg.p, nullptr);
+            }
+            cur = dst0 + rp.count;
+            all_out = rp.all_out != 0;
+        } else
         for (size_t g0 = 0; g0 < pc.size(); g0 += Q3_DOC_MAX_ENT) {
             Q3DocPiecePack pk{};
             const int np = (int)std::min<size_t>(pc.size() - g0, Q3_DOC_MAX_ENT);
@@ -1262,7 +1324,28 @@ extern "C" int q3tts_k_doc_stream(int32_t device, const float* src, int32_t rows
         chunks[nbd++] = c;
     }
     *n_out = total; *n_bounds = nbd;
+    if (n_frames) *n_frames = (int32_t)rg.kt;
+    if (rg.speed && delta_cap > 0) TRY(dd.get(delta, sizeof(int32_t) * (size_t)delta_cap));
     return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_doc_stream(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* kinds, const int32_t* sched,
+                                  const int32_t* sched_n, int32_t sched_stride, const q3tts_join_opts* opts, int32_t rate, int32_t ahead, int32_t lag,
+                                  int64_t staging, int64_t dst0, int32_t format, int32_t check_rows, void* out, int64_t out_cap, int64_t* n_out,
+                                  int64_t* chunks, int32_t chunk_cap, int32_t* n_bounds, int64_t* plan, int64_t* bad) {
+    return doc_stream_run(device, src, rows, stride, kinds, sched, sched_n, sched_stride, opts, rate, ahead, lag, staging, dst0, format, check_rows, out, out_cap,
+                          n_out, chunks, chunk_cap, n_bounds, plan, bad, 0, 0, 0, 0, nullptr, 0, nullptr);
+}
+
+extern "C" int q3tts_k_doc_stream_rate(int32_t device, const float* src, int32_t rows, int64_t stride, const int32_t* kinds, const int32_t* sched,
+                                       const int32_t* sched_n, int32_t sched_stride, const q3tts_join_opts* opts, int32_t rate, int32_t ahead, int32_t lag,
+                                       int64_t staging, int64_t dst0, int32_t format, int32_t check_rows, void* out, int64_t out_cap, int64_t* n_out,
+                                       int64_t* chunks, int32_t chunk_cap, int32_t* n_bounds, int64_t* plan, int64_t* bad, int32_t speed_permille,
+                                       int32_t output_rate, int64_t ring_j, int64_t ring_t, int32_t* delta, int32_t delta_cap, int32_t* n_frames) {
+    const bool off = (speed_permille == 0 || speed_permille == 1000) && (output_rate == 0 || output_rate == rate);
+    if (off) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "doc stream rate hook: neither a speed nor a rate (q3tts_k_doc_stream is the plain form)");
+    return doc_stream_run(device, src, rows, stride, kinds, sched, sched_n, sched_stride, opts, rate, ahead, lag, staging, dst0, format, check_rows, out, out_cap,
+                          n_out, chunks, chunk_cap, n_bounds, plan, bad, speed_permille, output_rate, ring_j, ring_t, delta, delta_cap, n_frames);
 }
 
 extern "C" int q3tts_k_rng_f32(uint64_t seed, int32_t n, float* out) {

@@ -573,3 +573,13 @@ struct Q3DocPiece { const float* src; long long j0, L, dst; int32_t count, F; };
 struct Q3DocPiecePack { Q3DocPiece e[Q3_DOC_MAX_ENT]; };
 void q3_launch_doc_scan(const Q3DocScanPack& ents, int n_ent, hipStream_t s);
 void q3_launch_doc_emit(const Q3DocPiecePack& pcs, int n_pc, int i16, void* dst, hipStream_t s);
+// A document with a speed or an output rate: the ring forms of k_pcm_tempo / k_pcm_resample (q3_tempo.hip, q3_resample.hip; one copy of
+// each arithmetic, two addressings). A ring of C f32 (C a multiple of 4, an allocation of its own) holds position g of a stream at
+// g mod C. k_doc_tempo: frames [k_from, k_to) of the n joined samples in rj into rt, outputs m >= n_out not written, *p_last as
+// Q3TempoEnt's, delta[k] for k < delta_cap. k_doc_resample: outputs [first, first + count) of the n samples in `ring` (fin: all there
+// will be) to dst[dst_off, ...), f32 or i16; -1 (nothing launched): one tile's span does not fit the LDS. What may be read and what may
+// be overwritten is the host's arithmetic: q3_doc_ring_step (q3_engine.h).
+void q3_launch_doc_tempo(const float* rj, long long cj, float* rt, long long ct, long long* p_last, const float* win, int permille, long long n,
+                         int k_from, int k_to, long long n_out, int32_t* delta, size_t delta_cap, hipStream_t s);
+int q3_launch_doc_resample(const float* ring, long long C, long long n, bool fin, long long first, long long count, const Q3Resamp& rs, int i16,
+                           void* dst, long long dst_off, hipStream_t s);

@@ -66,35 +66,37 @@ long long q3_resample_D(long long n, int L, int M, int H) { return n <= H ? 0 : 
 // straddle 0 or the row's valid length n element by element, zeros outside [0, n): nothing past n is ever loaded — and then every thread
 // runs the T-tap chain of one output, in ascending k, one f32 multiply and one f32 add per tap (the canonical order of DESIGN.md §19).
 // LDS: [span_cap floats][the table, when tab_lds]. Outputs past what the row can deliver (N(n) when final, D(n) otherwise) are not written.
-template <typename T>
-__global__ __launch_bounds__(kOut) void k_pcm_resample(const float* __restrict__ src, size_t stride, const Q3PcmPack ents, const Q3PcmSrc rows,
-                                                       const Q3Resamp rs, int span_cap, int tab_lds, T* __restrict__ dst) {
+// The body is shared by two addressings. Ring = false: the row is linear (k_pcm_resample, as ever). Ring = true (k_doc_resample,
+// DESIGN.md §28): the row is a ring of C samples that holds position g at g mod C, its base 16-byte aligned (a == 0) and C a multiple of
+// 4, so an aligned group of four never crosses the wrap; its positions stay below 2^29 (J below 2^28, stretched at speed 500 at the
+// most), so the modulus is an unsigned 32-bit one.
+template <bool Ring>
+__device__ __forceinline__ long long rs_at(long long g, unsigned C) { return Ring ? (long long)((unsigned)g % C) : g; }
+
+// outputs [first, first + count) of one row (n valid samples, finished or not) to d[0, ...): the workgroups blockIdx.x, + gridDim.x, ...
+template <bool Ring, typename T>
+__device__ __forceinline__ void rs_tiles(const float* __restrict__ row, int a, unsigned C, long long n, bool fin, long long first, long long count,
+                                         T* __restrict__ d, const Q3Resamp& rs, int span_cap, int tab_lds) {
     extern __shared__ float4 q3_rs_lds[];
     float* xs = (float*)q3_rs_lds;
-    const Q3PcmEnt en = ents.e[blockIdx.y];
-    const long long n = rows.len[blockIdx.y];
-    const bool fin = (rows.final_mask >> blockIdx.y) & 1ull;
     const long long L = rs.L, M = rs.M;
     const int H = rs.H, nt = rs.T, tid = threadIdx.x;
     const long long lim = fin ? (n <= 0 ? 0 : (n * L + M - 1) / M) : (n <= H ? 0 : ((n - H) * L + M - 1) / M);
-    const long long cnt = min((long long)en.count, lim - (long long)en.first);
-    if (en.first < 0 || cnt <= 0) return;  // (uniform over the workgroup, as every exit below)
+    const long long cnt = min(count, lim - first);
+    if (first < 0 || cnt <= 0) return;  // (uniform over the workgroup, as every exit below)
     const int ntiles = (int)((cnt + kOut - 1) / kOut);
     if ((int)blockIdx.x >= ntiles) return;
     const float* tab = rs.tab;
     if (tab_lds) {
         float* ts = xs + span_cap;
         const int lt = rs.L * nt, lt4 = lt >> 2;
-        const float4* t4 = (const float4*)rs.tab;  // (a device allocation of its own: 256-byte aligned)
+        const float4* t4 = (const float4*)rs.tab;  // (16-byte aligned: an allocation of its own, or a document's table behind its window)
         for (int j = tid; j < lt4; j += kOut) ((float4*)ts)[j] = t4[j];
         for (int j = 4 * lt4 + tid; j < lt; j += kOut) ts[j] = rs.tab[j];
         tab = ts;
     }
-    const float* row = src + (size_t)en.row * stride;
-    const int a = (int)(((uintptr_t)row >> 2) & 3);
-    T* d = dst + en.dst_off;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const long long m0 = (long long)en.first + (long long)tile * kOut;
+        const long long m0 = first + (long long)tile * kOut;
         const int c = (int)min((long long)kOut, cnt - (long long)tile * kOut);
         const long long i0 = (m0 * M) / L, i1 = ((m0 + c - 1) * M) / L;
         const long long g0 = i0 - H;                                   // the first sample a window of this tile reads
@@ -104,12 +106,12 @@ __global__ __launch_bounds__(kOut) void k_pcm_resample(const float* __restrict__
         for (int j = tid; j < n4; j += kOut) {
             const long long g = gs + 4ll * j;
             float4 v;
-            if (g >= 0 && g + 4 <= n) v = *(const float4*)(row + g);
+            if (g >= 0 && g + 4 <= n) v = *(const float4*)(row + rs_at<Ring>(g, C));
             else {
-                v.x = (g >= 0 && g < n) ? row[g] : 0.0f;
-                v.y = (g + 1 >= 0 && g + 1 < n) ? row[g + 1] : 0.0f;
-                v.z = (g + 2 >= 0 && g + 2 < n) ? row[g + 2] : 0.0f;
-                v.w = (g + 3 >= 0 && g + 3 < n) ? row[g + 3] : 0.0f;
+                v.x = (g >= 0 && g < n) ? row[rs_at<Ring>(g, C)] : 0.0f;
+                v.y = (g + 1 >= 0 && g + 1 < n) ? row[rs_at<Ring>(g + 1, C)] : 0.0f;
+                v.z = (g + 2 >= 0 && g + 2 < n) ? row[rs_at<Ring>(g + 2, C)] : 0.0f;
+                v.w = (g + 3 >= 0 && g + 3 < n) ? row[rs_at<Ring>(g + 3, C)] : 0.0f;
             }
             q3_rs_lds[j] = v;
         }
@@ -121,26 +123,67 @@ __global__ __launch_bounds__(kOut) void k_pcm_resample(const float* __restrict__
             float acc = 0.0f;
 #pragma unroll 4
             for (int k = 0; k < nt; ++k) acc = __fadd_rn(acc, __fmul_rn(x[k], t[(size_t)k * rs.L]));
-            q3_pcm_put(d + (m - en.first), acc);
+            q3_pcm_put(d + (m - first), acc);
         }
     }
 }
 
+template <typename T>
+__global__ __launch_bounds__(kOut) void k_pcm_resample(const float* __restrict__ src, size_t stride, const Q3PcmPack ents, const Q3PcmSrc rows,
+                                                       const Q3Resamp rs, int span_cap, int tab_lds, T* __restrict__ dst) {
+    const Q3PcmEnt en = ents.e[blockIdx.y];
+    const float* row = src + (size_t)en.row * stride;
+    rs_tiles<false, T>(row, (int)(((uintptr_t)row >> 2) & 3), 0u, rows.len[blockIdx.y], (rows.final_mask >> blockIdx.y) & 1ull, en.first, en.count,
+                       dst + en.dst_off, rs, span_cap, tab_lds);
+}
+
+// grid (x): the ring form, one document. Outputs [first, first + count) of the audio of which ring (C samples, position g at g mod C)
+// holds the last C of the n there are so far (fin: all there will be) into dst[dst_off, ...). The host guarantees that every position an
+// output reads is still in the ring (q3_doc_ring_step); nothing at or past n is loaded.
+template <typename T>
+__global__ __launch_bounds__(kOut) void k_doc_resample(const float* __restrict__ ring, unsigned C, long long n, int fin, long long first, long long count,
+                                                       const Q3Resamp rs, int span_cap, int tab_lds, T* __restrict__ dst, long long dst_off) {
+    rs_tiles<true, T>(ring, 0, C, n, fin != 0, first, count, dst + dst_off, rs, span_cap, tab_lds);
+}
+
+namespace {
+// the LDS of a launch: one tile's span, and the table when it fits beside it. false: the span alone does not fit
+bool rs_launch_shape(const Q3Resamp& rs, long long* span, int* tab_lds, size_t* lds, long long* lt4) {
+    // a tile's span: (kOut - 1) M / L + 1 input steps between its first and last output, T taps, up to 3 samples of alignment, whole float4s
+    *span = (((long long)(kOut - 1) * rs.M) / rs.L + 1 + rs.T + 3 + 3) & ~3ll;
+    *lt4 = ((long long)rs.L * rs.T + 3) & ~3ll;
+    if (*span * 4 > Q3_RESAMPLE_LDS_BYTES) return false;
+    *tab_lds = (*span + *lt4) * 4 <= Q3_RESAMPLE_LDS_BYTES ? 1 : 0;
+    *lds = (size_t)(*tab_lds ? *span + *lt4 : *span) * 4;
+    return true;
+}
+}  // namespace
+
 int q3_launch_pcm_resample(const float* src, size_t stride, const Q3PcmPack& ents, const Q3PcmSrc& rows, int n_ent, int max_count, const Q3Resamp& rs,
                            int i16, void* dst, hipStream_t s) {
     if (n_ent <= 0 || max_count <= 0) return 0;
-    // a tile's span: (kOut - 1) M / L + 1 input steps between its first and last output, T taps, up to 3 samples of alignment, whole float4s
-    const long long span = (((long long)(kOut - 1) * rs.M) / rs.L + 1 + rs.T + 3 + 3) & ~3ll;
-    const long long lt4 = ((long long)rs.L * rs.T + 3) & ~3ll;
-    if (span * 4 > Q3_RESAMPLE_LDS_BYTES) return -1;
-    const int tab_lds = (span + lt4) * 4 <= Q3_RESAMPLE_LDS_BYTES ? 1 : 0;
-    const size_t lds = (size_t)(tab_lds ? span + lt4 : span) * 4;
+    long long span, lt4; int tab_lds; size_t lds;
+    if (!rs_launch_shape(rs, &span, &tab_lds, &lds, &lt4)) return -1;
     const int tiles = (max_count + kOut - 1) / kOut;
     int gx = std::min(tiles, std::max(1, 1024 / n_ent));
     if (tab_lds && lt4 > 2048) gx = std::min(gx, (tiles + 3) / 4);  // a large table's copy is spread over four tiles or more
     gx = std::max(gx, 1);
     if (i16) hipLaunchKernelGGL(k_pcm_resample<int16_t>, dim3(gx, n_ent), dim3(kOut), lds, s, src, stride, ents, rows, rs, (int)span, tab_lds, (int16_t*)dst);
     else hipLaunchKernelGGL(k_pcm_resample<float>, dim3(gx, n_ent), dim3(kOut), lds, s, src, stride, ents, rows, rs, (int)span, tab_lds, (float*)dst);
+    return 0;
+}
+
+int q3_launch_doc_resample(const float* ring, long long C, long long n, bool fin, long long first, long long count, const Q3Resamp& rs, int i16,
+                           void* dst, long long dst_off, hipStream_t s) {
+    if (count <= 0) return 0;
+    long long span, lt4; int tab_lds; size_t lds;
+    if (!rs_launch_shape(rs, &span, &tab_lds, &lds, &lt4)) return -1;
+    const int tiles = (int)((count + kOut - 1) / kOut);
+    int gx = std::min(tiles, 1024);
+    if (tab_lds && lt4 > 2048) gx = std::min(gx, (tiles + 3) / 4);
+    gx = std::max(gx, 1);
+    if (i16) hipLaunchKernelGGL(k_doc_resample<int16_t>, dim3(gx), dim3(kOut), lds, s, ring, (unsigned)C, n, fin ? 1 : 0, first, count, rs, (int)span, tab_lds, (int16_t*)dst, dst_off);
+    else hipLaunchKernelGGL(k_doc_resample<float>, dim3(gx), dim3(kOut), lds, s, ring, (unsigned)C, n, fin ? 1 : 0, first, count, rs, (int)span, tab_lds, (float*)dst, dst_off);
     return 0;
 }
 

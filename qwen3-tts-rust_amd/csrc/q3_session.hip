@@ -77,7 +77,17 @@ struct Doc {
     std::vector<Pend> pend; int pend_ring = -1; size_t pend_off = 0;  // the snapshot on its way: ring buffer, byte offset of its table
     bool touch = false, clipped = false;  // a segment's length or end changed at this boundary; the last plan ran out of room
     long long frames = 0; bool all_eos = true;
+    // its own speed / output rate (both 0: nothing below is touched). rg: the pipeline's counts (q3_doc_ring_step); ring_j / ring_t: the
+    // two rings, allocations of their own; aux: the stretch's window and the p of the last decided frame
+    int speed = 0, out_rate = 0;
+    Q3DocRing rg{}; Q3Resamp rs{};
+    float* ring_j = nullptr; float* ring_t = nullptr; float* aux = nullptr;
+    std::vector<Q3DocDone> due;           // segments whose piece is joined and whose outputs are not all delivered yet, in order
+    bool flow = false;                    // a stage moved at the last boundary and the document is not out yet: the next one may move again
+    bool ringed() const { return speed || out_rate; }
 };
+// a rate's exit of one document at this boundary (k_doc_resample writes the staging buffer: issued behind take_ring, with the pieces)
+struct DocExit { Doc* d; Q3DocRingStep st; size_t at; };
 
 // a q3tts_session_clone call waiting for the worker (the caller's stack; mu guards done)
 struct CloneJob {
@@ -432,7 +442,9 @@ struct Boundary {
 // the documents' phases (below, in front of step)
 void feed_docs(q3tts_session* s);
 void doc_slot_scan(q3tts_session* s, int b, int ns, bool done, std::vector<Q3DocScan>& scans, std::vector<int32_t*>& resets);
-int doc_emit(q3tts_session* s, Boundary& bd, size_t* cur, std::vector<Q3DocPiece>& ents, std::vector<SEv>& evs, std::vector<std::shared_ptr<Doc>>& finished);
+int doc_emit(q3tts_session* s, Boundary& bd, size_t* cur, std::vector<Q3DocPiece>& ents, std::vector<DocExit>& exits, std::vector<SEv>& evs,
+             std::vector<std::shared_ptr<Doc>>& finished);
+hipError_t doc_free(q3tts_engine* e, Doc& d);
 int end_doc(q3tts_session* s, Boundary& bd, const std::shared_ptr<Doc>& dp, int kind, int status, const q3tts_result* res);
 
 // (mu held) id's streamed text; T is copied only when the device lacks some of it (it holds t_up entries)
@@ -794,7 +806,7 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
     }
     const int ne = (int)ents.size(), k = s->ring_next;
     // documents: at most two launches more, no copy more (the pieces and the edge tables lie behind the plain chunks in the same buffer)
-    std::vector<Q3DocPiece> pieces; std::vector<std::shared_ptr<Doc>> finished;
+    std::vector<Q3DocPiece> pieces; std::vector<DocExit> exits; std::vector<std::shared_ptr<Doc>> finished;
     if (!s->docs.empty()) {
         for (int32_t* p : resets) {  // a segment's first boundary in its row: {INT32_MAX, -1}, by device fills in stream order in front of the scan
             Q3_HIP(e, hipMemsetD32Async((hipDeviceptr_t)p, INT32_MAX, 1, vs));
@@ -806,9 +818,9 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
             for (int i = 0; i < n; ++i) sp.e[i] = scans[g0 + i];
             q3_launch_doc_scan(sp, n, vs);
         }
-        TRY(doc_emit(s, bd, &tot, pieces, chunks, finished));
+        TRY(doc_emit(s, bd, &tot, pieces, exits, chunks, finished));
     }
-    if (ne > 0 || !pieces.empty()) {
+    if (ne > 0 || !pieces.empty() || !exits.empty()) {
         const int rc = take_ring(s, k);
         if (rc) return rc;
         for (int g0 = 0; g0 < ne; g0 += Q3_PCM_MAX_ENT) {
@@ -829,6 +841,12 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
             for (int i = 0; i < n; ++i) pk.e[i] = pieces[g0 + i];
             q3_launch_doc_emit(pk, n, s->fmt, s->dev, vs);
         }
+        for (const DocExit& x : exits) {  // a document with a rate: its outputs from its ring, behind its stretch (issued by doc_emit, in stream order)
+            const Doc& d = *x.d;
+            if (q3_launch_doc_resample(d.speed ? d.ring_t : d.ring_j, d.speed ? d.rg.ct : d.rg.cj, x.st.nx, x.st.fin_x != 0, x.st.first, x.st.count, d.rs, s->fmt,
+                                       s->dev, (long long)x.at, vs) != 0)
+                return q3_set_err(e, Q3TTS_ERR_UNSUPPORTED, "session: the resampler's input span does not fit the LDS");
+        }
         for (auto& d : s->docs) if (d->touch && d->failed == Q3TTS_OK) { d->pend_ring = k; d->touch = false; }
         Q3_HIP(e, hipGetLastError());
         Q3_HIP(e, hipMemcpyAsync(s->host[k], s->dev, tot * s->es, hipMemcpyDeviceToHost, vs));
@@ -841,7 +859,8 @@ int gather_pcm(q3tts_session* s, Boundary& bd) {
     for (SEv& v : chunks) bd.bt.evs.push_back(v);
     for (auto& d : finished) {  // the last segment of a closed document is out: DONE behind its last chunk, the rows freed
         q3tts_result r{};
-        r.n_frames = (int32_t)d->frames; r.hit_eos = d->all_eos ? 1 : 0; r.n_samples = (int32_t)d->st.delivered; r.sample_rate = e->cfg.vocoder.sample_rate;
+        r.n_frames = (int32_t)d->frames; r.hit_eos = d->all_eos ? 1 : 0;
+        r.n_samples = (int32_t)(d->ringed() ? d->rg.m : d->st.delivered); r.sample_rate = d->out_rate ? d->out_rate : e->cfg.vocoder.sample_rate;
         TRY(end_doc(s, bd, d, Q3TTS_EV_DONE, Q3TTS_OK, &r));
     }
     return Q3TTS_OK;
@@ -877,7 +896,7 @@ size_t doc_table_samples(const q3tts_session* s, const Doc& d) { return (size_t)
 // does a boundary have document work although no slot runs? (the worker does not sleep then)
 bool doc_work(const q3tts_session* s) {
     for (const auto& d : s->docs) {
-        if (d->failed != Q3TTS_OK || d->pend_ring >= 0 || d->clipped || d->touch) return true;
+        if (d->failed != Q3TTS_OK || d->pend_ring >= 0 || d->clipped || d->touch || d->flow) return true;
         if (!d->w_open && d->st.head >= (long long)d->segs.size()) return true;  // its last event is due
         if (d->queued < std::min<long long>((long long)d->segs.size(), d->st.head + d->ahead)) return true;  // a segment became eligible
     }
@@ -897,7 +916,32 @@ int accept_docs(q3tts_session* s, Boundary& bd) {
     }
     for (auto& d : fresh) {
         d->stride = ((size_t)e->cfg.max_steps_cap * q3_voc_samples_per_frame(e) + 3) & ~(size_t)3;
-        const size_t need = (size_t)d->ahead * d->stride * sizeof(float) + (size_t)d->ahead * 2 * sizeof(int32_t);
+        const size_t rows_b = (size_t)d->ahead * d->stride * sizeof(float) + (size_t)d->ahead * 2 * sizeof(int32_t);
+        size_t need = rows_b;
+        int rrc = Q3TTS_OK;
+        std::vector<float> aux;  // what the two kernels read beside the rings: the stretch's window and 16 bytes for its p, the resampler's table
+        if (d->ringed()) {  // its rings: the minimum plus what one boundary can produce (twice one slot's share of the staging buffer)
+            Q3DocRing& g = d->rg;
+            g = Q3DocRing{};
+            g.speed = d->speed;
+            if (g.speed) { q3_tempo_window(aux); aux.resize(aux.size() + 4, 0.0f); }
+            if (d->out_rate) {  // the table is the document's own (freed with it), not the engine's cache of q3tts_set_output_rate
+                Q3Resamp r{};
+                std::vector<float> tab;
+                rrc = q3_resample_table(e->cfg.vocoder.sample_rate, d->out_rate, &r.L, &r.M, &r.H, tab);
+                if (rrc != Q3TTS_OK) q3_set_err(e, rrc, "document: the resampler refuses this output rate");
+                else {
+                    r.rate_in = e->cfg.vocoder.sample_rate; r.rate_out = d->out_rate; r.T = 2 * r.H + 1;
+                    const std::vector<float> dl = q3_resample_device_layout(tab, r.L, r.M, r.T);
+                    aux.insert(aux.end(), dl.begin(), dl.end());
+                    d->rs = r; g.L = r.L; g.M = r.M; g.H = r.H;
+                }
+            }
+            const long long win = 2 * (long long)(s->ring_cap / (size_t)e->B);
+            g.cj = (q3_doc_ring_min_j(g.speed, g.L, g.M, g.H) + win + 3) & ~3ll;
+            g.ct = g.speed ? (q3_doc_ring_min_t(g.speed, g.L, g.M, g.H) + q3_tempo_N(win, g.speed) + Q3_TEMPO_HS + 3) & ~3ll : 0;
+            need += sizeof(float) * ((size_t)(g.cj + g.ct) + aux.size());
+        }
         size_t free_b = 0, total_b = 0;
         Q3_HIP(e, hipMemGetInfo(&free_b, &total_b));
         const long long cap = s->doc_mem_cap.load(std::memory_order_relaxed);
@@ -908,8 +952,19 @@ int accept_docs(q3tts_session* s, Boundary& bd) {
         // then. So a table that fits one slot's share always fits (doc_emit fails the document, not the session, should it ever not).
         if (doc_table_samples(s, *d) * (size_t)e->B > s->ring_cap)
             rc = q3_set_err(e, Q3TTS_ERR_INVALID, "document: the edge table of ahead = " + std::to_string(d->ahead) + " rows exceeds one slot's share of the staging buffer");
-        else if (need > free_b || hipMalloc((void**)&d->rows, need) != hipSuccess)
-            rc = q3_set_err(e, Q3TTS_ERR_OOM, "document: its " + std::to_string(d->ahead) + " rows need " + std::to_string(need) + " bytes, the device has " + std::to_string(free_b) + " bytes free");
+        else if (rrc != Q3TTS_OK) rc = rrc;  // (the resampler's table; submit has checked the plan, so this does not happen)
+        else if (need > free_b || hipMalloc((void**)&d->rows, rows_b) != hipSuccess)
+            rc = q3_set_err(e, Q3TTS_ERR_OOM, "document: its " + std::to_string(d->ahead) + " rows" + (d->ringed() ? " and rings" : "") + " need " + std::to_string(need) + " bytes, the device has " + std::to_string(free_b) + " bytes free");
+        else if (d->ringed()) {
+            if (hipMalloc((void**)&d->ring_j, sizeof(float) * (size_t)d->rg.cj) != hipSuccess ||
+                (d->speed && hipMalloc((void**)&d->ring_t, sizeof(float) * (size_t)d->rg.ct) != hipSuccess) ||
+                hipMalloc((void**)&d->aux, sizeof(float) * aux.size()) != hipSuccess ||
+                hipMemcpy(d->aux, aux.data(), sizeof(float) * aux.size(), hipMemcpyHostToDevice) != hipSuccess) {
+                (void)hipGetLastError();
+                rc = q3_set_err(e, Q3TTS_ERR_OOM, "document: its " + std::to_string(d->ahead) + " rows and rings need " + std::to_string(need) + " bytes, the device has " + std::to_string(free_b) + " bytes free");
+                d->bytes = 0; doc_free(e, *d);
+            }
+        }
         if (rc != Q3TTS_OK) {
             d->rows = nullptr; d->ended = true;
             std::lock_guard<std::mutex> lk(s->mu);
@@ -919,6 +974,7 @@ int accept_docs(q3tts_session* s, Boundary& bd) {
             continue;
         }
         d->edges = (int32_t*)(d->rows + (size_t)d->ahead * d->stride);
+        if (d->out_rate) d->rs.tab = d->aux + (d->speed ? Q3_TEMPO_WN + 4 : 0);  // (16-byte aligned behind the window and the p)
         d->bytes = need; e->dev_bytes += need;  // (q3tts_k_device_bytes sees a document's rows while they live)
         d->accepted = true;
         s->docs.push_back(d);
@@ -982,15 +1038,24 @@ int end_doc(q3tts_session* s, Boundary& bd, const std::shared_ptr<Doc>& dp, int 
             bd.adm.erase(bd.adm.begin() + i); bd.cr_adm.erase(bd.cr_adm.begin() + i);
             if (i < bd.tn_adm.size()) bd.tn_adm.erase(bd.tn_adm.begin() + i);
         }
-    if (d.rows) { Q3_HIP(e, hipFree(d.rows)); e->dev_bytes -= d.bytes; d.bytes = 0; }
-    d.rows = nullptr; d.edges = nullptr;
+    Q3_HIP(e, doc_free(e, d));  // (hipFree waits for the launches that read the rows and rings)
     for (DocSeg& g : d.segs) copy_result_free(g.res);
-    d.ended = true; d.pend_ring = -1; d.touch = d.clipped = false;
+    d.ended = true; d.pend_ring = -1; d.touch = d.clipped = d.flow = false; d.due.clear();
     SEv v = final_ev(d.id, kind, status);
     if (res) { v.res = *res; v.res.status = status; }
     bd.bt.evs.push_back(v);
     s->docs.erase(std::remove(s->docs.begin(), s->docs.end(), dp), s->docs.end());
     return Q3TTS_OK;
+}
+
+// a document's device memory goes: its rows, its rings and their window (the caller knows that no launch reads them any more)
+hipError_t doc_free(q3tts_engine* e, Doc& d) {
+    hipError_t first = hipSuccess;
+    for (float* p : {d.rows, d.ring_j, d.ring_t, d.aux})
+        if (p) { const hipError_t r = hipFree(p); if (first == hipSuccess) first = r; }
+    e->dev_bytes -= d.bytes; d.bytes = 0;
+    d.rows = d.ring_j = d.ring_t = d.aux = nullptr; d.edges = nullptr;
+    return first;  // (the first failure, as the one hipFree of the rows reported it)
 }
 
 // 3a. documents that were cancelled, or that failed at the last boundary (a segment failed by itself, the length limit): torn down here,
@@ -1026,7 +1091,8 @@ void doc_slot_scan(q3tts_session* s, int b, int ns, bool done, std::vector<Q3Doc
 // its event is waited for, which a whole chunk of frame steps later costs nothing), q3_doc_plan turns it into pieces clipped to what
 // the staging buffer has left behind the plain requests' chunks and the tables, and the pieces, with this boundary's tables, become
 // entries of ONE k_doc_emit launch (per 64 entries). *cur: the staging samples used so far, in and out.
-int doc_emit(q3tts_session* s, Boundary& bd, size_t* cur, std::vector<Q3DocPiece>& ents, std::vector<SEv>& evs, std::vector<std::shared_ptr<Doc>>& finished) {
+int doc_emit(q3tts_session* s, Boundary& bd, size_t* cur, std::vector<Q3DocPiece>& ents, std::vector<DocExit>& exits, std::vector<SEv>& evs,
+             std::vector<std::shared_ptr<Doc>>& finished) {
     q3tts_engine* e = s->e;
     const int rate = e->cfg.vocoder.sample_rate;
     // the last boundary's snapshots land first (pend_off still names THAT boundary's table: the plain chunks in front of it differ in size)
@@ -1061,7 +1127,7 @@ int doc_emit(q3tts_session* s, Boundary& bd, size_t* cur, std::vector<Q3DocPiece
         Doc& d = *dp;
         if (d.failed != Q3TTS_OK) continue;
         std::vector<Q3DocOut> pc; std::vector<Q3DocDone> dn;
-        const long long room = (long long)(s->ring_cap - *cur);
+        const long long room = d.ringed() ? q3_doc_ring_room(d.rg) : (long long)(s->ring_cap - *cur);
         const int prc = q3_doc_plan(d.join, rate, d.snap.data(), (int)d.snap.size(), room, &d.st, &pc, &dn);
         if (prc != Q3TTS_OK) {
             q3_set_err(e, prc, "document: the delivered length would pass 2^28 samples at segment " + std::to_string(d.st.head));
@@ -1069,33 +1135,77 @@ int doc_emit(q3tts_session* s, Boundary& bd, size_t* cur, std::vector<Q3DocPiece
             continue;
         }
         const size_t c0 = *cur;
-        for (const Q3DocOut& p : pc) {
-            const float* from = p.seg < 0 ? nullptr : d.rows + (size_t)(p.seg % d.ahead) * d.stride + p.src;
-            ents.push_back(Q3DocPiece{from, p.j0, p.L, (long long)*cur, (int32_t)p.count, p.F});
-            *cur += (size_t)p.count;
+        bool last = false;
+        long long delivered = 0;
+        std::vector<Q3DocDone> pub;  // the segments to publish at this boundary
+        if (d.ringed()) {  // its own speed or rate: the pieces go into RJ, the stretch and the exit run behind them (the pipeline)
+            Q3DocRing& g = d.rg;
+            std::vector<Q3DocPiece> je;
+            long long pos = g.nj;
+            if (q3_doc_out_pos(d.st.delivered, g.speed, g.L, g.M) > 0x7fffffffll) {  // (the counts of the events are int32)
+                q3_set_err(e, Q3TTS_ERR_INVALID, "document: the delivered length would pass 2^31 - 1 output samples at segment " + std::to_string(d.st.head));
+                d.failed = Q3TTS_ERR_INVALID;
+                continue;
+            }
+            for (const Q3DocOut& p : pc) {
+                q3_doc_ring_put(p, p.seg < 0 ? nullptr : d.rows + (size_t)(p.seg % d.ahead) * d.stride + p.src, pos, g.cj, &je);
+                pos += p.count;
+            }
+            q3_launch_doc_emit_all(je, 0, d.ring_j, e->vstream);
+            const bool fin_j = !d.w_open && d.st.head >= (long long)d.segs.size();
+            DocExit x{&d, Q3DocRingStep{}, *cur};
+            q3_doc_ring_step(&g, pos - g.nj, fin_j, (long long)(s->ring_cap - *cur), &x.st);
+            if (g.speed)
+                q3_launch_doc_tempo(d.ring_j, g.cj, d.ring_t, g.ct, (long long*)(d.aux + Q3_TEMPO_WN), d.aux, g.speed, g.nj, x.st.k_from, x.st.k_to, x.st.nt, nullptr, 0, e->vstream);
+            if (x.st.count > 0) {
+                if (g.L) exits.push_back(x);
+                else q3_doc_ring_get(d.ring_t, g.ct, x.st.first, x.st.count, (long long)*cur, &ents);
+                *cur += (size_t)x.st.count;
+            }
+            last = x.st.all_out != 0;
+            // awake while the document is not out and a stage moved, or decidable work is left that only RT's space or the staging room held back
+            d.flow = !last && (!pc.empty() || x.st.k_to > x.st.k_from || x.st.count > 0 || x.st.pending);
+            for (const Q3DocDone& y : dn) d.due.push_back(y);
+            size_t nd = 0;  // the segments whose last output went out with this chunk
+            while (nd < d.due.size() && q3_doc_out_pos(d.due[nd].end, g.speed, g.L, g.M) <= g.m) ++nd;
+            pub.assign(d.due.begin(), d.due.begin() + (long)nd);
+            d.due.erase(d.due.begin(), d.due.begin() + (long)nd);
+            delivered = g.m;
+        } else {
+            for (const Q3DocOut& p : pc) {
+                const float* from = p.seg < 0 ? nullptr : d.rows + (size_t)(p.seg % d.ahead) * d.stride + p.src;
+                ents.push_back(Q3DocPiece{from, p.j0, p.L, (long long)*cur, (int32_t)p.count, p.F});
+                *cur += (size_t)p.count;
+            }
+            d.clipped = *cur >= s->ring_cap && d.st.head < (long long)d.segs.size();
+            last = !d.w_open && d.st.head >= (long long)d.segs.size();
+            pub = dn; delivered = d.st.delivered;
         }
-        d.clipped = *cur >= s->ring_cap && d.st.head < (long long)d.segs.size();
-        const bool last = !d.w_open && d.st.head >= (long long)d.segs.size();
+        // what both kinds of document publish: the chunk, then the segments that are wholly out, positions through the document's maps
+        // (the identity without a speed or rate)
+        const Q3DocRing& g = d.rg;
         if (*cur > c0 || last) {
             SEv v; v.id = d.id; v.kind = Q3TTS_EV_CHUNK; v.n = (int)(*cur - c0); v.is_final = last ? 1 : 0; v.off = c0;
             evs.push_back(v);
         }
         {
             std::lock_guard<std::mutex> lk(s->mu);
-            d.n_delivered = d.st.delivered;
-            for (const Q3DocDone& x : dn) {
-                DocSeg& g = d.segs[x.seg];
+            d.n_delivered = delivered;
+            for (const Q3DocDone& x : pub) {
+                const DocSeg& sg = d.segs[x.seg];
                 q3tts_long_info f{};
-                f.status = g.res.status; f.n_frames = g.res.n_frames; f.hit_eos = g.res.hit_eos; f.n_native = g.n;
-                f.lo = x.lo; f.hi = x.hi; f.begin = f.out_begin = x.begin; f.end = f.out_end = x.end;
+                f.status = sg.res.status; f.n_frames = sg.res.n_frames; f.hit_eos = sg.res.hit_eos; f.n_native = sg.n;
+                f.lo = x.lo; f.hi = x.hi; f.begin = x.begin; f.end = x.end;
+                f.out_begin = q3_doc_out_pos(x.begin, g.speed, g.L, g.M); f.out_end = q3_doc_out_pos(x.end, g.speed, g.L, g.M);
                 d.info.push_back(f);
             }
         }
-        for (const Q3DocDone& x : dn) {
-            DocSeg& g = d.segs[x.seg];
-            SEv v; v.id = d.id; v.kind = Q3TTS_EV_SEGMENT; v.n = x.seg; v.res = g.res;
-            v.res.n_samples = (int32_t)(x.end - x.begin); v.res.sample_rate = rate;
-            g.res = q3tts_result{};  // (the codes went with the event)
+        for (const Q3DocDone& x : pub) {
+            DocSeg& sg = d.segs[x.seg];
+            SEv v; v.id = d.id; v.kind = Q3TTS_EV_SEGMENT; v.n = x.seg; v.res = sg.res;
+            v.res.n_samples = (int32_t)(q3_doc_out_pos(x.end, g.speed, g.L, g.M) - q3_doc_out_pos(x.begin, g.speed, g.L, g.M));
+            v.res.sample_rate = d.out_rate ? d.out_rate : rate;
+            sg.res = q3tts_result{};  // (the codes went with the event)
             d.frames += v.res.n_frames; d.all_eos = d.all_eos && v.res.hit_eos;
             evs.push_back(v);
         }
@@ -1197,7 +1307,7 @@ void worker(q3tts_session* s) {
     for (int b = 0; b < e->B; ++b) if (s->slots[b].req) { q3_retire_slot(e, b, e->vstream); free_slot(s, b); }
     hipStreamSynchronize(e->stream);
     hipStreamSynchronize(e->vstream);
-    for (auto& d : s->docs) { if (d->rows) { hipFree(d->rows); e->dev_bytes -= d->bytes; d->bytes = 0; } d->rows = nullptr; for (DocSeg& g : d->segs) copy_result_free(g.res); }  // (both streams are idle)
+    for (auto& d : s->docs) { doc_free(e, *d); for (DocSeg& g : d->segs) copy_result_free(g.res); }  // (both streams are idle)
     s->docs.clear();
     for (Swapped& o : s->out) drop_block(s, o, o.ticket);  // (their ids got FAILED above, or the session is closing)
     s->out.clear();
@@ -1422,6 +1532,13 @@ extern "C" int q3tts_session_submit_document(q3tts_session* s, const q3tts_reque
         d->tmpl.temperature = e->temperature; d->tmpl.top_k = e->top_k; d->tmpl.top_p = e->top_p; d->tmpl.has_seed = e->has_seed; d->tmpl.seed = e->seed;
     }
     d->join = o.join; d->ahead = o.ahead ? o.ahead : 8; d->open = o.open == 1; d->n_given = n_segs;
+    d->speed = o.speed_permille == 1000 ? 0 : o.speed_permille;
+    d->out_rate = o.output_rate == e->cfg.vocoder.sample_rate ? 0 : o.output_rate;
+    if (d->out_rate) {  // (host only: the table itself is made by the worker at the boundary that accepts the document)
+        int L = 0, M = 0, H = 0, T = 0;
+        const int prc = q3_resample_plan(e->cfg.vocoder.sample_rate, d->out_rate, &L, &M, &H, &T);
+        if (prc != Q3TTS_OK) return refuse(prc, prc == Q3TTS_ERR_UNSUPPORTED ? "document: this output rate needs more than 32768 filter coefficients" : "document: output_rate is 0 (off) or 4000..96000 Hz");
+    }
     std::unique_ptr<SReq> job;
     if (voice) {  // the document's own prefix: a §23 job in front of its segments, released when the document ends
         job.reset(new SReq());

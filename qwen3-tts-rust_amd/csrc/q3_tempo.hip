@@ -34,21 +34,29 @@ void q3_tempo_window(std::vector<float>& w) {
     for (int j = 0; j < Wn; ++j) w[j] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * (double)j / (double)Wn));
 }
 
-// ---- the kernel ---------------------------------------------------------------------------------------------------------------
+// ---- the kernels --------------------------------------------------------------------------------------------------------------
+// Two addressings of one arithmetic. Ring = false: the row is linear (k_pcm_tempo, as ever). Ring = true (k_doc_tempo):
+// the row is a ring of C samples that holds position g at g mod C, its base 16-byte aligned (a == 0) and C a multiple of 4, so an
+// aligned group of four never crosses the wrap. Positions of J stay below 2^28 and those of the stretched audio below 2^29 (speed 500):
+// the modulus is an unsigned 32-bit one.
+template <bool Ring>
+__device__ __forceinline__ long long tempo_at(long long g, unsigned C) { return Ring ? (long long)((unsigned)g % C) : g; }
+
 // dst[0, count) = row[g0, g0 + count), zeros outside [0, n): whole 16-byte groups of the source row with one load where they lie inside
 // [0, n), element by element at the edges. Nothing at or past n is loaded. a: the row's first sample's offset within its 16-byte group.
-__device__ __forceinline__ void tempo_stage(float* dst, const float* __restrict__ row, int a, long long g0, int count, long long n, int tid) {
+template <bool Ring>
+__device__ __forceinline__ void tempo_stage(float* dst, const float* __restrict__ row, int a, unsigned C, long long g0, int count, long long n, int tid) {
     const long long gs = g0 - ((((long long)a + g0) % 4 + 4) % 4);
     const int n4 = (int)((g0 + count - gs + 3) >> 2);
     for (int j = tid; j < n4; j += Nd) {
         const long long g = gs + 4ll * j;
         float4 v;
-        if (g >= 0 && g + 4 <= n) v = *(const float4*)(row + g);
+        if (g >= 0 && g + 4 <= n) v = *(const float4*)(row + tempo_at<Ring>(g, C));
         else {
-            v.x = (g >= 0 && g < n) ? row[g] : 0.0f;
-            v.y = (g + 1 >= 0 && g + 1 < n) ? row[g + 1] : 0.0f;
-            v.z = (g + 2 >= 0 && g + 2 < n) ? row[g + 2] : 0.0f;
-            v.w = (g + 3 >= 0 && g + 3 < n) ? row[g + 3] : 0.0f;
+            v.x = (g >= 0 && g < n) ? row[tempo_at<Ring>(g, C)] : 0.0f;
+            v.y = (g + 1 >= 0 && g + 1 < n) ? row[tempo_at<Ring>(g + 1, C)] : 0.0f;
+            v.z = (g + 2 >= 0 && g + 2 < n) ? row[tempo_at<Ring>(g + 2, C)] : 0.0f;
+            v.w = (g + 3 >= 0 && g + 3 < n) ? row[tempo_at<Ring>(g + 3, C)] : 0.0f;
         }
         const int d = (int)(g - g0);  // -3 .. count - 1
         if (d >= 0 && d < count) dst[d] = v.x;
@@ -58,42 +66,38 @@ __device__ __forceinline__ void tempo_stage(float* dst, const float* __restrict_
     }
 }
 
-// grid (n_ent): one workgroup of 256 threads per entry, which walks the entry's frames in order (delta_k needs p_{k-1}). For a frame it
-// stages the template t[j] = x[p_{k-1} + Hs + j] (512) and the candidates' span x[a_k + Dmin + i] (767) in LDS; thread i runs the chain of
-// candidate delta = Dmin + i alone — acc = acc + x * t over ascending j, one f32 multiply and one f32 add per step; the template word is an
-// LDS broadcast (16 bytes at a time), the span word xs[i + j] lies in consecutive banks for consecutive lanes — then the first maximum over
-// the 256 sums by comparisons (value, then the lower index), and thread j writes output j of the frame: the old frame's second window half
+// One workgroup of 256 threads walks frames [k_from, k_to) of one row in order (delta_k needs p_{k-1}). For a frame it stages the template
+// t[j] = x[p_{k-1} + Hs + j] (512) and the candidates' span x[a_k + Dmin + i] (767) in LDS; thread i runs the chain of candidate
+// delta = Dmin + i alone — acc = acc + x * t over ascending j, one f32 multiply and one f32 add per step; the template word is an LDS
+// broadcast (16 bytes at a time), the span word xs[i + j] lies in consecutive banks for consecutive lanes — then the first maximum over the
+// 256 sums by comparisons (value, then the lower index), and thread j writes output j of the frame: the old frame's second window half
 // times the template's first half, plus the new frame's first window half times the span at the winner. LDS: 2 KiB + 3 KiB + 32 bytes.
-__global__ __launch_bounds__(Nd) void k_pcm_tempo(const float* __restrict__ src, size_t stride, float* __restrict__ dst, size_t dst_stride,
-                                                  long long* __restrict__ p_last, const float* __restrict__ win, int s, const Q3TempoPack ents,
-                                                  int32_t* __restrict__ delta, size_t delta_stride) {
+// y: the outputs' row (Ring: a ring of CT samples); *p_slot holds p of frame k_from - 1 (read when k_from >= 2) and receives p of
+// frame k_to - 1; dl != null: dl[k] = delta_k for k < dl_cap.
+template <bool Ring>
+__device__ __forceinline__ void tempo_walk(const float* __restrict__ row, int a, unsigned C, long long n, float* __restrict__ y, unsigned CT,
+                                           long long* __restrict__ p_slot, const float* __restrict__ win, int s, int k_from, int k_to, long long n_out,
+                                           int32_t* __restrict__ dl, size_t dl_cap) {
     __shared__ float4 ts4[Wn / 4];
     __shared__ float xs[kSpan + 1];
     __shared__ float red_v[Nd / 64];
     __shared__ int red_i[Nd / 64];
     float* ts = (float*)ts4;
-    const Q3TempoEnt en = ents.e[blockIdx.x];
-    if (en.k_to <= en.k_from || en.k_from < 0) return;  // (uniform over the workgroup)
     const int tid = threadIdx.x;
-    const long long n = en.n;
-    const float* row = src + (size_t)en.row * stride;
-    const int a = (int)(((uintptr_t)row >> 2) & 3);
-    float* y = dst + (size_t)en.row * dst_stride;
-    int32_t* dl = delta ? delta + (size_t)en.row * delta_stride : nullptr;
     const float w0 = win[tid], w1 = win[tid + Hs];
-    int k = en.k_from;
-    long long pprev = k >= 2 ? p_last[en.row] : 0;  // p_0 = 0
+    int k = k_from;
+    long long pprev = k >= 2 ? *p_slot : 0;  // p_0 = 0
     if (k == 0) {  // p_{-1} = -Hs: both terms read x[j]
         const float x = tid < n ? row[tid] : 0.0f;
-        if (tid < en.n_out) y[tid] = __fadd_rn(__fmul_rn(w1, x), __fmul_rn(w0, x));
-        if (dl && tid == 0 && delta_stride > 0) dl[0] = 0;
+        if (tid < n_out) y[tid] = __fadd_rn(__fmul_rn(w1, x), __fmul_rn(w0, x));
+        if (dl && tid == 0 && dl_cap > 0) dl[0] = 0;
         k = 1;
     }
-    for (; k < en.k_to; ++k) {
+    for (; k < k_to; ++k) {
         const long long ak = ((long long)k * Hs * s) / 1000;
         __syncthreads();  // the previous frame is done with ts, xs and red
-        tempo_stage(ts, row, a, pprev + Hs, Wn, n, tid);
-        tempo_stage(xs, row, a, ak + Dmin, kSpan, n, tid);
+        tempo_stage<Ring>(ts, row, a, C, pprev + Hs, Wn, n, tid);
+        tempo_stage<Ring>(xs, row, a, C, ak + Dmin, kSpan, n, tid);
         __syncthreads();
         const float* xp = xs + tid;
         float acc = 0.0f;
@@ -120,11 +124,39 @@ __global__ __launch_bounds__(Nd) void k_pcm_tempo(const float* __restrict__ src,
             if (ov > bv) { bv = ov; bi = red_i[w]; }  // (a later wave's indices are higher: a tie keeps the earlier one)
         }
         const long long m = (long long)k * Hs + tid;
-        if (m < en.n_out) y[m] = __fadd_rn(__fmul_rn(w1, ts[tid]), __fmul_rn(w0, xs[bi + tid]));
-        if (dl && tid == 0 && (size_t)k < delta_stride) dl[k] = Dmin + bi;
+        if (m < n_out) y[tempo_at<Ring>(m, CT)] = __fadd_rn(__fmul_rn(w1, ts[tid]), __fmul_rn(w0, xs[bi + tid]));
+        if (dl && tid == 0 && (size_t)k < dl_cap) dl[k] = Dmin + bi;
         pprev = ak + Dmin + bi;
     }
-    if (tid == 0) p_last[en.row] = pprev;
+    if (tid == 0) *p_slot = pprev;
+}
+
+// grid (n_ent): one workgroup per entry, rows linear
+__global__ __launch_bounds__(Nd) void k_pcm_tempo(const float* __restrict__ src, size_t stride, float* __restrict__ dst, size_t dst_stride,
+                                                  long long* __restrict__ p_last, const float* __restrict__ win, int s, const Q3TempoPack ents,
+                                                  int32_t* __restrict__ delta, size_t delta_stride) {
+    const Q3TempoEnt en = ents.e[blockIdx.x];
+    if (en.k_to <= en.k_from || en.k_from < 0) return;  // (uniform over the workgroup)
+    const float* row = src + (size_t)en.row * stride;
+    tempo_walk<false>(row, (int)(((uintptr_t)row >> 2) & 3), 0u, en.n, dst + (size_t)en.row * dst_stride, 0u, p_last + en.row, win, s, en.k_from, en.k_to,
+                      en.n_out, delta ? delta + (size_t)en.row * delta_stride : nullptr, delta_stride);
+}
+
+// grid (1): the ring form, one document. Frames [k_from, k_to) of the joined audio J, of which rj (C_J samples, J at positions mod C_J)
+// holds the last C_J of the n joined so far, into rt (C_T samples, the stretched audio at positions mod C_T); outputs m >= n_out are not
+// written. The host guarantees that every position a frame reads is still in rj and that no frame overwrites a position of rt that the
+// exit still reads (q3_doc_ring_step).
+__global__ __launch_bounds__(Nd) void k_doc_tempo(const float* __restrict__ rj, unsigned cj, float* __restrict__ rt, unsigned ct, long long* __restrict__ p_last,
+                                                  const float* __restrict__ win, int s, long long n, int k_from, int k_to, long long n_out,
+                                                  int32_t* __restrict__ delta, size_t delta_cap) {
+    if (k_to <= k_from || k_from < 0) return;
+    tempo_walk<true>(rj, 0, cj, n, rt, ct, p_last, win, s, k_from, k_to, n_out, delta, delta_cap);
+}
+
+void q3_launch_doc_tempo(const float* rj, long long cj, float* rt, long long ct, long long* p_last, const float* win, int permille, long long n,
+                         int k_from, int k_to, long long n_out, int32_t* delta, size_t delta_cap, hipStream_t s) {
+    if (k_to <= k_from) return;
+    hipLaunchKernelGGL(k_doc_tempo, dim3(1), dim3(Nd), 0, s, rj, (unsigned)cj, rt, (unsigned)ct, p_last, win, permille, n, k_from, k_to, n_out, delta, delta_cap);
 }
 
 void q3_launch_pcm_tempo(const float* src, size_t stride, float* dst, size_t dst_stride, long long* p_last, const float* win, int permille,

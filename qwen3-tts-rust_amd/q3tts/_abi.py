@@ -196,6 +196,7 @@ SYMBOLS = [
     "q3tts_k_pcm_edges", "q3tts_k_pcm_join",
     "q3tts_session_submit_document", "q3tts_session_document_append", "q3tts_session_document_info",
     "q3tts_k_session_doc_mem_cap", "q3tts_doc_default_opts", "q3tts_k_doc_rules", "q3tts_k_doc_plan", "q3tts_k_doc_stream",
+    "q3tts_k_doc_stream_rate", "q3tts_k_doc_ring_plan", "q3tts_k_doc_out_pos",
     "q3tts_vocoder_config_from_file", "q3tts_get_vocoder_source", "q3tts_k_voc_file_tensor",
 ]
 
@@ -223,7 +224,7 @@ class LongOpts(C.Structure):
 
 class DocOpts(C.Structure):
     """q3tts_doc_opts (include/q3tts.h, "documents in a session: the streaming join")."""
-    _fields_ = [("join", JoinOpts), ("ahead", C.c_int32), ("open", C.c_int32)]
+    _fields_ = [("join", JoinOpts), ("ahead", C.c_int32), ("open", C.c_int32), ("speed_permille", C.c_int32), ("output_rate", C.c_int32)]
 
 
 class LongInfo(C.Structure):
@@ -354,6 +355,9 @@ def load_library(path=None):
     lib.q3tts_k_doc_plan.argtypes = [C.POINTER(JoinOpts), C.c_int32, i32p, C.c_int32, C.c_int64, i64p, i64p, C.c_int32, i32p, i64p, C.c_int32, i32p]
     lib.q3tts_k_doc_stream.argtypes = [C.c_int32, f32p, C.c_int32, C.c_int64, i32p, i32p, i32p, C.c_int32, C.POINTER(JoinOpts), C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, i64p, i64p, C.c_int32, i32p, i64p, i64p]
+    lib.q3tts_k_doc_stream_rate.argtypes = lib.q3tts_k_doc_stream.argtypes + [C.c_int32, C.c_int32, C.c_int64, C.c_int64, i32p, C.c_int32, i32p]
+    lib.q3tts_k_doc_ring_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, i64p, C.c_int64, C.c_int32, C.c_int64, i64p]
+    lib.q3tts_k_doc_out_pos.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, i64p]
     lib.q3tts_stream_begin.argtypes = [vp, C.POINTER(Request), C.POINTER(vp)]
     lib.q3tts_stream_poll.argtypes = [vp, C.POINTER(f32p), i32p, i32p]
     lib.q3tts_stream_end.argtypes = [vp, C.POINTER(Result)]

@@ -355,15 +355,16 @@ class TtsEngine:
         return AudioSample(out.pcm, out.sample_rate, 1), table
 
     def stream_long(self, text_or_pieces, voice: VoiceFile, instruct=None, *, prefix=None, seed=None, pause_ms=None, ahead=None,
-                    target_bytes=0, max_bytes=0, **join_opts):
+                    speed=None, sample_rate=None, target_bytes=0, max_bytes=0, **join_opts):
         """generate_long's streaming twin (an extension; include/q3tts.h, "documents in a session"): the document plays
         while it is synthesised. A str is split as generate_long splits it and submitted whole; an iterator of strings (a language
         model still writing) is split piece by piece and appended as it arrives from a helper thread, each piece ending a paragraph.
         Yields (f32 chunk, segments_done): segments_done lists (text_slice, t_begin_s, t_end_s, hit_eos) for the segments that this
         chunk completed; a chunk is yielded as soon as the segment events of its boundary are taken (they arrive with it), not when
-        the next chunk comes. The chunks joined are generate_long's audio for the same segments, bit for bit (without speed or sample_rate:
-        a streamed document has neither, and the call is refused while the engine has one set). ahead: how many segments may run in
-        front of the one being delivered (default 8). join_opts / pause_ms: as generate_long."""
+        the next chunk comes. The chunks joined are generate_long's audio for the same segments, speed and sample_rate, bit for bit.
+        speed (a factor, 0.5 .. 2.0) / sample_rate (Hz) are the document's own, as generate_long names them; the times in segments_done
+        are then in the stretched, resampled audio. The call is refused while the engine itself has a speed or an output rate set.
+        ahead: how many segments may run in front of the one being delivered (default 8). join_opts / pause_ms: as generate_long."""
         import threading
         sc = self.sampler_config
         if prefix is not None:
@@ -391,9 +392,12 @@ class TtsEngine:
             if not first:
                 raise ValueError("stream_long: the text holds nothing speakable")
         kw = dict(temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p, seed=sc.seed if seed is None else seed, max_steps=self.max_steps)
-        rate = float(self.cfg.vocoder.sample_rate)
+        permille = 0 if speed is None else int(round(float(speed) * 1000.0))
+        out_rate = 0 if sample_rate is None else int(sample_rate)
+        rate = float(out_rate or self.cfg.vocoder.sample_rate)
         with native.NativeSession(self._native) as sess:
-            did = sess.submit_document(first, voice=vdesc, prefix=prefix, join=join_opts, ahead=ahead or 0, open=not whole, **kw)
+            did = sess.submit_document(first, voice=vdesc, prefix=prefix, join=join_opts, ahead=ahead or 0, open=not whole,
+                                       speed_permille=permille, output_rate=out_rate, **kw)
             failure = []
             gate, live = threading.Lock(), [True]  # the feeder touches the session only while the consumer is inside this block
 
@@ -440,7 +444,7 @@ class TtsEngine:
                                 break
                             seg = ev[4].segment
                             f = sess.document_info(did)[0][seg]
-                            done.append((texts[seg], f["begin"] / rate, f["end"] / rate, bool(f["hit_eos"])))
+                            done.append((texts[seg], f["out_begin"] / rate, f["out_end"] / rate, bool(f["hit_eos"])))
                         yield pcm, done
                     elif kind == _abi.EV_SEGMENT:   # (not behind a chunk of its own: cannot happen; kept out of the audio)
                         continue

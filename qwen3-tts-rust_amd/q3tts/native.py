@@ -686,17 +686,18 @@ class NativeSession:
             segs[i].max_steps = int(sg[2]) if len(sg) > 2 else 0
         return segs, n
 
-    def submit_document(self, segments, voice=None, prefix=None, join=None, ahead=0, open=False, **template_kw):
+    def submit_document(self, segments, voice=None, prefix=None, join=None, ahead=0, open=False, speed_permille=0, output_rate=0, **template_kw):
         """q3tts_session_submit_document: `segments` as NativeEngine.generate_long takes them ((ids, kind) or (ids, kind, max_steps));
         exactly one of voice (a voice-only desc) and prefix (a NativePrefix, ready or pending); join: a dict of q3tts_join_opts fields;
         ahead: how many segments may run in front of the one being delivered (0: 8); open=True: more segments follow through
-        append_document. template_kw: make_request's sampler fields, min_frames, force_eos_at, max_steps. Returns the document's id: its
-        EV_CHUNK payloads joined are generate_long's pcm bit for bit; EV_SEGMENT events carry each segment's result (res.segment = its index)."""
+        append_document. speed_permille / output_rate: the document's own, as generate_long's (0: off). template_kw: make_request's
+        sampler fields, min_frames, force_eos_at, max_steps. Returns the document's id: its EV_CHUNK payloads joined are generate_long's
+        pcm for the same options bit for bit; EV_SEGMENT events carry each segment's result (res.segment = its index)."""
         if not self.h:
             raise _abi.Q3Error("q3tts_session_submit_document: the session is closed")
         tmpl, keep = NativeEngine.make_request(**template_kw)
         segs, n = self._doc_segments(segments, keep)
-        o = doc_opts(ahead=ahead, open=1 if open else 0, **(join or {}))
+        o = doc_opts(ahead=ahead, open=1 if open else 0, speed_permille=speed_permille, output_rate=output_rate, **(join or {}))
         if prefix is not None and not prefix.h:
             raise _abi.Q3Error("the prefix is closed")
         did = C.c_uint64(0)
@@ -1568,8 +1569,8 @@ def k_pcm_join(src, lens, kinds, edges, out_cap, rate=24000, device=0, iters=0, 
     return (out, plan, N.value, ms.value) if iters > 0 else (out, plan, N.value)
 
 
-def doc_opts(ahead=0, open=0, **join):
-    """q3tts_doc_opts: q3tts_doc_default_opts, then the join options given and ahead / open."""
+def doc_opts(ahead=0, open=0, speed_permille=0, output_rate=0, **join):
+    """q3tts_doc_opts: q3tts_doc_default_opts, then the join options given, ahead / open and the document's own speed / output rate."""
     lib = _abi.load_library()
     o = _abi.DocOpts()
     lib.q3tts_doc_default_opts(C.byref(o))
@@ -1578,6 +1579,7 @@ def doc_opts(ahead=0, open=0, **join):
         d.update(join)
         o.join = join_opts(**d)
     o.ahead, o.open = int(ahead), int(open)
+    o.speed_permille, o.output_rate = int(speed_permille), int(output_rate)
     return o
 
 
@@ -1637,6 +1639,61 @@ def k_doc_stream(src, kinds, sched, ahead, staging, dst0=0, lag=1, fmt=0, check_
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_doc_stream failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return out[:n_out.value].copy(), chunks[:nb.value].copy(), plan, bad.value
+
+
+def k_doc_stream_rate(src, kinds, sched, ahead, staging, speed_permille=0, output_rate=0, ring_j=0, ring_t=0, dst0=0, lag=1, fmt=0, rate=24000,
+                      device=0, out_cap=None, chunk_cap=1 << 16, delta_cap=4096, **opts):
+    """q3tts_k_doc_stream_rate: k_doc_stream with a speed and / or an output rate — scan, plan, join into the ring RJ, stretch into RT,
+    exit — boundary by boundary. ring_j / ring_t: the rings' capacities (0: the minimum). staging and the chunks are in output samples.
+    Returns (out f32 or i16, chunks per boundary, plan [rows][4] = lo, hi, begin, end in J, bad, delta of every frame)."""
+    lib = _abi.load_library()
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    kd = np.ascontiguousarray(kinds, dtype=np.int32)
+    if src.ndim != 2 or kd.shape != (src.shape[0],) or len(sched) != src.shape[0]:
+        raise ValueError("k_doc_stream_rate: src is [rows][stride]; kinds and sched take one entry per row")
+    sn = np.array([len(s) for s in sched], dtype=np.int32)
+    sc = np.zeros((src.shape[0], max(1, int(sn.max()))), dtype=np.int32)
+    for i, s in enumerate(sched):
+        sc[i, :len(s)] = s
+    o = join_opts(**opts)
+    if out_cap is None:
+        nj = int(sum(s[-1] for s in sched)) + (len(sched) - 1) * max(opts.get("pause_ms", (0, 0, 150, 300, 600))) * rate // 1000
+        if speed_permille not in (0, 1000):
+            nj = -(-nj * 1000 // int(speed_permille))
+        if output_rate not in (0, rate):
+            nj = -(-nj * int(output_rate) // int(rate))
+        out_cap = nj + 64
+    out = np.zeros(max(1, int(out_cap)), dtype=np.int16 if fmt else np.float32)
+    chunks = np.zeros(int(chunk_cap), dtype=np.int64)
+    plan = np.zeros((src.shape[0], 4), dtype=np.int64)
+    delta = np.zeros(max(1, int(delta_cap)), dtype=np.int32)
+    i64p = C.POINTER(C.c_int64)
+    n_out, bad, nb, nf = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    rc = lib.q3tts_k_doc_stream_rate(device, _ptr(src, f32p), src.shape[0], src.shape[1], _ptr(kd, i32p), _ptr(sc, i32p), _ptr(sn, i32p), sc.shape[1],
+                                     C.byref(o), int(rate), int(ahead), int(lag), int(staging), int(dst0), int(fmt), 0, out.ctypes.data_as(C.c_void_p),
+                                     int(out_cap), C.byref(n_out), _ptr(chunks, i64p), chunks.size, C.byref(nb), _ptr(plan, i64p), C.byref(bad),
+                                     int(speed_permille), int(output_rate), int(ring_j), int(ring_t), _ptr(delta, i32p), int(delta_cap), C.byref(nf))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_doc_stream_rate failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    if nf.value > delta_cap:
+        raise _abi.Q3Error("k_doc_stream_rate: more frames than delta_cap")
+    return out[:n_out.value].copy(), chunks[:nb.value].copy(), plan, bad.value, delta[:nf.value].copy()
+
+
+def k_doc_ring_plan(state, want, fin_if_all, room_out, speed_permille=0, output_rate=0, ring_j=0, ring_t=0, rate=24000):
+    """q3tts_k_doc_ring_plan (host only): one boundary of a rated document's flow control. state: int64 [4] = samples joined, J whole,
+    frames decided, outputs delivered, updated in place. Returns a dict of the step's counts and the two minimum capacities."""
+    lib = _abi.load_library()
+    if state.dtype != np.int64 or state.shape != (4,) or not state.flags.c_contiguous:
+        raise ValueError("k_doc_ring_plan: state is a contiguous int64 [4]")
+    out = np.zeros(13, dtype=np.int64)
+    i64p = C.POINTER(C.c_int64)
+    rc = lib.q3tts_k_doc_ring_plan(int(speed_permille), int(rate), int(output_rate), int(ring_j), int(ring_t), _ptr(state, i64p), int(want), int(fin_if_all),
+                                   int(room_out), _ptr(out, i64p))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_doc_ring_plan failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    names = ("room", "joined", "k_from", "k_to", "nt", "nx", "fin_x", "first", "count", "all_out", "min_j", "min_t", "pending")
+    return {k: int(v) for k, v in zip(names, out)}
 
 
 def k_rng_f32(seed, n):

@@ -77,7 +77,7 @@ pub struct q3tts_long_segment { pub ids: *const u32, pub n_ids: i32, pub kind: i
 /// q3tts_session_event.kind of a document's segment whose piece has gone out (include/q3tts.h, "documents in a session")
 pub const Q3TTS_EV_SEGMENT: i32 = 6;
 #[repr(C)] #[derive(Clone, Copy)]
-pub struct q3tts_doc_opts { pub join: q3tts_join_opts, pub ahead: i32, pub open: i32 }
+pub struct q3tts_doc_opts { pub join: q3tts_join_opts, pub ahead: i32, pub open: i32, pub speed_permille: i32, pub output_rate: i32 }
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct q3tts_long_opts { pub join: q3tts_join_opts, pub speed_permille: i32, pub output_rate: i32 }
 #[repr(C)] #[derive(Clone, Copy)]

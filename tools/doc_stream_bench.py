@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """doc_stream_bench.py — what streaming a long document through a session costs on one MI355X.
 
-  python tools/doc_stream_bench.py [--steps K] [--warmup W] [--segments N] [--aheads 1,8,64]
+  python tools/doc_stream_bench.py [--steps K] [--warmup W] [--segments N] [--aheads 1,8,64] [--speed 1250] [--rate 16000] [--skip-beside]
 
 tools/long_bench.py's document (the 1.7B shape, 64 slots, vocoder on; 256 segments in one voice behind a prefix made once; bench.py's
 utterance mix four times over with the lengths set through max_steps, EOS masked). Measured in one process:
@@ -27,15 +27,16 @@ sys.path.insert(0, os.path.join(REPO, "qwen3-tts-rust_amd"))
 import bench  # noqa: E402
 
 
-def run_document(eng, segs, px, sampler, ahead, plain=()):
-    """The document (and `plain` requests behind it) through one session. Returns a dict of times and the document's PCM."""
+def run_document(eng, segs, px, sampler, ahead, plain=(), speed=0, rate=0):
+    """The document (and `plain` requests behind it) through one session; speed / rate: the document's own (0: off). Returns a dict of
+    times and the document's PCM."""
     from q3tts import _abi, native
     out = dict(first_s=None, chunks=0)
     pcm, firsts, frames = [], [], 0
     t_plain_end = None
     with native.NativeSession(eng) as sess:
         t0 = time.perf_counter()
-        did = sess.submit_document(segs, prefix=px, seed=1000, ahead=ahead, **sampler) if segs else None
+        did = sess.submit_document(segs, prefix=px, seed=1000, ahead=ahead, speed_permille=speed, output_rate=rate, **sampler) if segs else None
         ids = {sess.submit(**r) for r in plain}
         for rid, kind, chunk, fin, res in sess.events(600000):
             if rid == did:
@@ -66,6 +67,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--segments", type=int, default=256)
     ap.add_argument("--aheads", default="1,8,64")
+    ap.add_argument("--speed", type=int, default=0, help="per mille: adds legs with the document's own speed (and with --rate, both)")
+    ap.add_argument("--rate", type=int, default=0, help="Hz: adds legs with the document's own output rate")
+    ap.add_argument("--skip-beside", action="store_true", help="leave out the session_bench workload beside the document")
     args = ap.parse_args()
     aheads = [int(a) for a in args.aheads.split(",")]
     from q3tts import _abi, native
@@ -111,6 +115,30 @@ def main():
         out["session_document"]["ahead_%d" % a] = {
             "first_audio_s": round(float(np.median(first)), 4), "audio_sec_per_s": round(doc_sec / float(np.median(wall)), 2),
             "chunks_per_audio_sec": round(chunks / doc_sec, 3), "rows_bytes": a * cfg.max_steps_cap * 1920 * 4}
+    # the document with its own speed and / or output rate at ahead = 8, against this build's plain document at ahead = 8 measured here
+    legs = ([(args.speed, 0)] if args.speed else []) + ([(0, args.rate)] if args.rate else []) + ([(args.speed, args.rate)] if args.speed and args.rate else [])
+    if legs:
+        base = [run_document(eng, segs, px, sampler, 8)[0] for _ in range(args.steps)]
+        base_wall, base_chunks = float(np.median([b["wall_s"] for b in base])), base[-1]["chunks"]
+        out["session_document_rated"] = {"plain_ahead_8": {"wall_s": round(base_wall, 4), "chunks": base_chunks,
+                                                            "spread_s": round(max(b["wall_s"] for b in base) - min(b["wall_s"] for b in base), 4)}}
+        for s, r in legs:
+            ref = eng.generate_long(segs, prefix=px, seed=1000, speed_permille=s, output_rate=r, **sampler)
+            first, wall, chunks = [], [], 0
+            for _ in range(args.steps):
+                got, pcm = run_document(eng, segs, px, sampler, 8, speed=s, rate=r)
+                assert pcm.size == ref.n_samples and np.array_equal(pcm.view(np.uint32), ref.pcm.view(np.uint32)), "the rated document differs from generate_long's"
+                first.append(got["first_s"]); wall.append(got["wall_s"]); chunks = got["chunks"]
+            w = float(np.median(wall))
+            out["session_document_rated"]["speed_%d_rate_%d" % (s, r)] = {
+                "first_audio_s": round(float(np.median(first)), 4), "wall_s": round(w, 4), "source_audio_sec_per_s": round(doc_sec / w, 2),
+                "out_samples": int(ref.n_samples), "out_rate": int(ref.sample_rate), "chunks": chunks,
+                "added_ms_per_chunk_boundary": round(1e3 * (w - base_wall) / max(chunks, 1), 4)}
+    if args.skip_beside:
+        px.close()
+        eng.close()
+        print(json.dumps(out))
+        return
     alone, beside, doc_beside = [], [], []
     f_alone, f_beside = [], []
     for _ in range(args.steps):
