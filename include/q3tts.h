@@ -653,7 +653,8 @@ int q3tts_mel(q3tts_engine* e, const float* audio, int64_t n_samples, float* out
 /* ---- voice-clone encoders (replace AudioEncoder / SpeakerEncoder, src/models/onnx.rs:82-165, and the encoder half of
  * TtsEngine::create_voice_file, src/tts/engine.rs:324-387). The reference runs two ONNX graphs that are not in its
  * repository; the structure here is the model family's (ECAPA-TDNN speaker encoder; SEANet + transformer + split residual
- * VQ codec encoder), every dimension a field, weights seeded-synthetic. ------------------------------- */
+ * VQ codec encoder), every dimension a field, weights seeded-synthetic or read from two GGUF files
+ * (q3tts_clone_load below). ------------------------------------------------------------------------------ */
 typedef struct q3tts_clone_config {
     /* speaker encoder: log-mel [T][mel_dim] -> [se_dim] */
     int32_t mel_dim;                 /* 128 (fixed by q3tts_mel) */
@@ -679,6 +680,53 @@ void q3tts_clone_default_config(q3tts_clone_config* cfg);
 /* "load" both encoders into the engine (the reference does so when the two ONNX files exist, src/tts/engine.rs:105-119);
  * weights are generated from cfg.synth_seed of the engine. Calling it again replaces them. */
 int q3tts_clone_init(q3tts_engine* e, const q3tts_clone_config* cfg);
+/* ---- trained encoder weights from two GGUF files ----
+ * qwen3_tts_speaker_encoder.gguf and qwen3_tts_codec_encoder.gguf (the names mirror the reference's onnx/qwen3_tts_speaker_encoder.onnx
+ * and onnx/qwen3_tts_codec_encoder.onnx, src/tts/engine.rs:105-119). Each is looked up in weights_dir (the quant directory), else in its
+ * parent: one unquantised pair serves every quant directory. Tensor names and layouts are the state_dict keys and PyTorch layouts of the
+ * family's modules (transformers' ECAPA_TimeDelayNet; MimiModel's encoder, encoder_transformer, downsample and the two input_proj) plus
+ * quantizer.codebook.{q}.weight [codebook_size][vq_dim]; unknown tensors are ignored.
+ *
+ * q3tts_clone_config_from_dir (host only, no GPU): the encoders' shape from the two files. On entry *cfg holds a complete clone config; on
+ * success every field the metadata states is overwritten. Speaker file, A = "q3tts-speaker-encoder" (its general.architecture): A.mel_dim,
+ * A.channels / A.kernel_sizes / A.dilations (integer arrays of 5), A.attention_channels -> se_attn_channels, A.res2net_scale,
+ * A.se_channels -> se_se_channels, A.embedding_length -> se_dim. Codec file, A = "q3tts-codec-encoder": A.filters, A.kernel_size,
+ * A.residual_kernel_size, A.last_kernel_size, A.ratios (integer array of 1..4; its length -> ae_n_ratios), A.embedding_length -> ae_hidden,
+ * A.block_count -> ae_n_layer, A.attention.head_count, A.attention.key_length -> ae_head_dim, A.feed_forward_length,
+ * A.attention.sliding_window, A.rope.freq_base, A.attention.layer_norm_epsilon, A.down_stride, A.vq_dim, A.n_codebooks, A.codebook_size.
+ * Every key is required; ae_layer_scale parametrises only the synthetic generator and is left alone. Cross-checks: the numbers of
+ * transformer layers, SEANet stages, codebooks and Res2Net branches, and the shape of every tensor the metadata implies (every
+ * convolution's [n][cin][k], the stride convolutions' kernel 2 x ratio, q/k/v/o_proj, fc1, fc2, the codebooks). Errors go to err (err_cap
+ * bytes, NUL-terminated; err may be NULL) and leave *cfg unchanged: Q3TTS_ERR_IO for a missing or unreadable file, named (when exactly
+ * one of the two is missing the message names that one); Q3TTS_ERR_INVALID otherwise, naming the file and the key or tensor. */
+int q3tts_clone_config_from_dir(const char* weights_dir, q3tts_clone_config* cfg, char* err, int32_t err_cap);
+/* Where the two files are, by the rule above (host only): the path of each into its buffer of cap bytes, "" for one that is in neither
+ * directory. Returns how many were found (0, 1 or 2), or Q3TTS_ERR_INVALID (a NULL argument, a buffer that is too small; the message,
+ * with the size needed, goes to q3tts_last_error(NULL)). The one home of the lookup rule: TtsEngine.new decides with it whether to load. */
+int q3tts_clone_files_find(const char* weights_dir, char* speaker_path, char* codec_path, int32_t cap);
+/* Load both encoders from the two files. weights_dir NULL: the engine's own weights_path (Q3TTS_ERR_STATE if it was created without one).
+ * Both files are opened and checked in full on the host before the device is touched: the config comes from them
+ * (q3tts_clone_default_config, then q3tts_clone_config_from_dir), must pass the checks q3tts_clone_init applies, and every value must be
+ * finite. While it builds, a load holds one matrix's row-major staging copy on the device beside the encoders (freed per matrix), so its
+ * peak is that of q3tts_clone_init plus the largest matrix in bf16. A refusal (Q3TTS_ERR_IO for a file that is not found; Q3TTS_ERR_INVALID for a missing tensor, a shape that disagrees with the
+ * metadata, a missing or mistyped key, an unsupported tensor type, a value that is not finite, a file that ends early, a refused config)
+ * names the file and the tensor or key and leaves the engine and the encoders it had as they were. Then the encoders are built through
+ * the creation path of q3tts_clone_init, each array taken from the file instead of the generator: convolution and projection matrices
+ * rounded to bf16 (nearest even; a BF16 container passes bit for bit), biases, LayerNorm, LayerScale and codebooks f32 as stored.
+ * Calling it or q3tts_clone_init again replaces the encoders. Refused while a session is open, like q3tts_clone_init; a session clones
+ * with whatever was loaded before it opened. */
+int q3tts_clone_load(q3tts_engine* e, const char* weights_dir);
+/* Where the clone encoders' weights came from: 0 = not loaded, 1 = the seeded synthetic generator (q3tts_clone_init), 2 = the two files
+ * (q3tts_clone_load). Codes and embeddings of an engine that answers 1 are the output of random filters. */
+int q3tts_get_clone_source(const q3tts_engine* e, int32_t* source);
+/* Host-only test hook: the array q3tts_clone_load would upload from the pair found from weights_dir for the synthetic generator's tensor
+ * id (comp, which) of oracle/q3_oracle_clone.c, at the shape *cfg: in device layout, after rounding, as f32 (matrices [n][round512(k *
+ * cin)], zero in the padding). out may be NULL to query *n. Needs no GPU. */
+int q3tts_k_clone_file_tensor(const char* weights_dir, const q3tts_clone_config* cfg, int32_t comp, int32_t which, float* out, int64_t cap,
+                              int64_t* n);
+/* Host-only test hook: the host half of q3tts_clone_load on the pair found from weights_dir (open, shape, cross-checks, finite values, the
+ * config checks of q3tts_clone_init), with its status; the message goes to q3tts_last_error(NULL). Needs no GPU. */
+int q3tts_k_clone_load_check(const char* weights_dir);
 /* frames the audio encoder produces for n_samples (ceil division through every stride) */
 int32_t q3tts_clone_audio_frames(const q3tts_engine* e, int64_t n_samples);
 /* AudioEncoder::encode (src/models/onnx.rs:96-121): codes [n_frames][ae_n_codebooks] i64, row-major like "audio_codes".

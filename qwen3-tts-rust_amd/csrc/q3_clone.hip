@@ -18,14 +18,11 @@
 #include <vector>
 
 #include "q3_engine.h"
+#include "q3_gguf.h"
 
 namespace {
 
-#define Q3G_CLONE 5
-enum { SC_TDNN0 = 0, SC_BLOCK = 1, SC_MFA = 8, SC_ASP_TDNN = 9, SC_ASP_CONV = 10, SC_FC = 11, AC_CONV0 = 32, AC_STAGE = 33,
-       AC_LAST = 60, AC_TFM = 64, AC_DOWN = 100, AC_SEM_PROJ = 101, AC_AC_PROJ = 102, AC_CODEBOOK = 110 };
-enum { SW_TDNN1 = 0, SW_TDNN2 = 2, SW_SE1 = 4, SW_SE2 = 6, SW_RES2 = 16 };
-enum { TW_LN1_W = 0, TW_LN1_B, TW_QKV, TW_O, TW_LS1, TW_LN2_W, TW_LN2_B, TW_FC1, TW_FC2, TW_LS2 };
+#define Q3G_CLONE 5  // (the tensor ids SC_* / AC_* / SW_* / TW_* are in q3_gguf.h: the weights files' loader maps names onto them)
 enum { PAD_ZERO = 0, PAD_REFLECT = 1, PAD_REPLICATE = 2 };
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_ELU = 2, ACT_TANH = 3, ACT_SIGMOID = 4, ACT_GELU = 5, ACT_RELU_TANH = 6 };
 #define ROPE_MAX_T 16384
@@ -349,6 +346,7 @@ struct Q3Clone {
     Arena arena;
     float* pcm = nullptr; size_t pcm_cap = 0;
     float* mel_in = nullptr; size_t mel_cap = 0;
+    const Q3CloneFiles* file = nullptr;  // creation only: the opened and checked weights files (nullptr: the seeded generator)
 };
 
 namespace {
@@ -363,11 +361,37 @@ inline unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
 // that reading bounds K, but no depth above 8192 has ever run through it, under a test or otherwise, so the encoders refuse one on the host.
 bool depth_ok(int64_t k, int64_t cin) { return k >= 1 && cin >= 1 && k * cin <= 8192; }  // (k * cin <= 8192 <=> round512(k * cin) <= 8192)
 
+// a HIP status as an engine status (so that a creation step's failure goes through the caller's cleanup)
+int hip_rc(q3tts_engine* e, hipError_t err, const char* what) {
+    return err == hipSuccess ? Q3TTS_OK : q3_set_err(e, Q3TTS_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(err));
+}
 int dev_alloc(q3tts_engine* e, Q3Clone* c, void** p, size_t bytes) {
     Q3_HIP(e, hipMalloc(p, bytes));
     c->allocs.push_back(*p);
     return Q3TTS_OK;
 }
+// The weights' two sources. mk_conv, mk_vec and the codebook loop fill each device array either from the seeded generator (id (comp, which), as the
+// oracle's) or, with weights files, from q3_clone_file_array's host array for the same id: already in device layout and rounded like the
+// generator's, so the tiling, the fused QKV rows and k_cb_transpose are the same code for both.
+int file_array(q3tts_engine* e, Q3Clone* c, int comp, int which, size_t n, std::vector<float>& a) {
+    std::string err;
+    if (q3_clone_file_array(*c->file, c->cfg, comp, which, a, err)) return q3_set_err(e, Q3TTS_ERR_INVALID, err);
+    if (a.size() != n) return q3_set_err(e, Q3TTS_ERR_INVALID, "clone weights files: tensor id (" + std::to_string(comp) + ", " + std::to_string(which) + ") has " + std::to_string(a.size()) + " elements, the encoders need " + std::to_string(n));
+    return Q3TTS_OK;
+}
+int mk_vec(q3tts_engine* e, Q3Clone* c, float** p, int comp, int which, size_t n, float base, float std) {
+    int rc = dev_alloc(e, c, (void**)p, n * 4);
+    if (rc) return rc;
+    if (c->file) {
+        std::vector<float> a;
+        if ((rc = file_array(e, c, comp, which, n, a))) return rc;
+        Q3_HIP(e, hipMemcpy(*p, a.data(), n * 4, hipMemcpyHostToDevice));  // (a is a local: synchronous copy)
+        return Q3TTS_OK;
+    }
+    q3_launch_fill_f32(*p, n, e->cfg.synth_seed, Q3_TID(Q3G_CLONE, comp, which), base, std / Q3_IH4_STD, 0, e->stream);
+    return Q3TTS_OK;
+}
+int mk_bias(q3tts_engine* e, Q3Clone* c, float** p, int comp, int wb, size_t n) { return mk_vec(e, c, p, comp, wb, n, 0.0f, 0.02f); }
 int mk_conv(q3tts_engine* e, Q3Clone* c, CConv& cv, int comp, int ww, int wb, int cin, int n, int k, int stride, int dil, int padl, int mode) {
     if (!depth_ok(k, cin)) return q3_set_err(e, Q3TTS_ERR_INVALID, "clone config: a convolution's GEMM depth exceeds 8192");  // (validate() names it first)
     cv.cin = cin; cv.n = n; cv.k = k; cv.stride = stride; cv.dil = dil; cv.padl = padl; cv.mode = mode; cv.kp = round512(k * cin);
@@ -375,12 +399,27 @@ int mk_conv(q3tts_engine* e, Q3Clone* c, CConv& cv, int comp, int ww, int wb, in
     if ((rc = dev_alloc(e, c, (void**)&cv.w, (size_t)n * cv.kp * 2))) return rc;
     Q3Fill f{}; f.dst = cv.w; f.N = n; f.K = cv.kp; f.mode = 0; f.row0 = 0; f.rows = n; f.tid_a = Q3_TID(Q3G_CLONE, comp, ww);
     f.src_a = nullptr; f.src_b = nullptr; f.seed = e->cfg.synth_seed; f.scale = (1.0f / sqrtf((float)(k * cin))) / Q3_IH4_STD;
-    q3_launch_fill_tiled(f, e->stream);
+    if (c->file) {  // the file's rows arrive rounded to bf16 in f32: their upper halves are the bf16 bits
+        const size_t ne = (size_t)n * cv.kp;
+        std::vector<float> a;
+        if ((rc = file_array(e, c, comp, ww, ne, a))) return rc;
+        std::vector<uint16_t> h(ne);
+        for (size_t i = 0; i < ne; ++i) { uint32_t u; memcpy(&u, &a[i], 4); h[i] = (uint16_t)(u >> 16); }
+        // one row-major staging copy at a time: it is freed as soon as the fill that reads it has run, so a load never holds more than
+        // the encoders plus their largest matrix
+        void* stage = nullptr;
+        if ((rc = hip_rc(e, hipMalloc(&stage, ne * 2), "hipMalloc (weights staging)"))) return rc;
+        rc = hip_rc(e, hipMemcpy(stage, h.data(), ne * 2, hipMemcpyHostToDevice), "hipMemcpy (weights staging)");  // (h is a local: synchronous copy)
+        if (!rc) {
+            f.src_a = (const uint16_t*)stage;
+            q3_launch_fill_tiled(f, e->stream);
+            rc = hip_rc(e, hipStreamSynchronize(e->stream), "hipStreamSynchronize (weights staging)");
+        }
+        hipFree(stage);
+        if (rc) return rc;
+    } else q3_launch_fill_tiled(f, e->stream);
     cv.b = nullptr;
-    if (wb >= 0) {
-        if ((rc = dev_alloc(e, c, (void**)&cv.b, (size_t)n * 4))) return rc;
-        q3_launch_fill_f32(cv.b, (size_t)n, e->cfg.synth_seed, Q3_TID(Q3G_CLONE, comp, wb), 0.0f, 0.02f / Q3_IH4_STD, 0, e->stream);
-    }
+    if (wb >= 0) return mk_bias(e, c, &cv.b, comp, wb, (size_t)n);
     return Q3TTS_OK;
 }
 int mk_tdnn(q3tts_engine* e, Q3Clone* c, CConv& cv, int comp, int ww, int cin, int n, int k, int dil) {
@@ -388,12 +427,6 @@ int mk_tdnn(q3tts_engine* e, Q3Clone* c, CConv& cv, int comp, int ww, int cin, i
 }
 int mk_causal(q3tts_engine* e, Q3Clone* c, CConv& cv, int comp, int ww, int wb, int cin, int n, int k, int stride, int dil, int mode) {
     return mk_conv(e, c, cv, comp, ww, wb, cin, n, k, stride, dil, (k - 1) * dil + 1 - stride, mode);
-}
-int mk_vec(q3tts_engine* e, Q3Clone* c, float** p, int comp, int which, size_t n, float base, float std) {
-    int rc = dev_alloc(e, c, (void**)p, n * 4);
-    if (rc) return rc;
-    q3_launch_fill_f32(*p, n, e->cfg.synth_seed, Q3_TID(Q3G_CLONE, comp, which), base, std / Q3_IH4_STD, 0, e->stream);
-    return Q3TTS_OK;
 }
 
 // dst[t][0..n) (leading dimension ldd) = conv(src (+ src2)) through im2col + the exact GEMM
@@ -605,6 +638,7 @@ void q3_clone_destroy(q3tts_engine* e) {
     hipFree(c->arena.base); hipFree(c->pcm); hipFree(c->mel_in);
     delete c;
     e->clone = nullptr;
+    e->clone_source = 0;
 }
 
 extern "C" void q3tts_clone_default_config(q3tts_clone_config* c) {
@@ -621,16 +655,16 @@ extern "C" void q3tts_clone_default_config(q3tts_clone_config* c) {
     c->ae_down_stride = 2; c->ae_vq_dim = 256; c->ae_n_codebooks = 16; c->ae_codebook_size = 2048;
 }
 
-extern "C" int q3tts_clone_init(q3tts_engine* e, const q3tts_clone_config* cfg) {
-    Q3_NOT_IN_SESSION(e);
-    if (!e || !cfg) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
-    int rc = validate(e, *cfg);
-    if (rc) return rc;
+// The one creation path of the encoders: *cfg has passed validate(); files == nullptr takes every array from the seeded generator, else
+// from the opened and checked weights files. Replaces the encoders the engine had.
+static int clone_create(q3tts_engine* e, const q3tts_clone_config* cfg, const Q3CloneFiles* files) {
+    int rc;
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     q3_clone_destroy(e);
     Q3Clone* c = new Q3Clone();
     e->clone = c;
     c->cfg = *cfg;
+    c->file = files;
     const q3tts_clone_config& g = c->cfg;
 #define CK(x) do { if ((rc = (x))) { q3_clone_destroy(e); return rc; } } while (0)
     const int C = g.se_channels[0], C4 = g.se_channels[4], wp = C / g.se_res2net_scale;
@@ -678,16 +712,20 @@ extern "C" int q3tts_clone_init(q3tts_engine* e, const q3tts_clone_config* cfg) 
     for (int q = 0; q < g.ae_n_codebooks; ++q) {  // generated row-major [CS][D] (the logical tensor), kept transposed for k_rvq
         const size_t ne = (size_t)g.ae_codebook_size * g.ae_vq_dim;
         float* rowmajor = nullptr;
-        Q3_HIP(e, hipMalloc((void**)&rowmajor, ne * 4));
-        q3_launch_fill_f32(rowmajor, ne, e->cfg.synth_seed, Q3_TID(Q3G_CLONE, AC_CODEBOOK + q, 0), 0.0f, (1.0f / sqrtf((float)g.ae_vq_dim)) / Q3_IH4_STD, 0, e->stream);
-        rc = dev_alloc(e, c, (void**)&c->cb[q], ne * 4);
+        CK(hip_rc(e, hipMalloc((void**)&rowmajor, ne * 4), "hipMalloc (codebook)"));  // (rc == Q3TTS_OK from here)
+        if (files) {
+            std::vector<float> a;
+            rc = file_array(e, c, AC_CODEBOOK + q, 0, ne, a);
+            if (!rc) rc = hip_rc(e, hipMemcpy(rowmajor, a.data(), ne * 4, hipMemcpyHostToDevice), "hipMemcpy (codebook)");
+        } else q3_launch_fill_f32(rowmajor, ne, e->cfg.synth_seed, Q3_TID(Q3G_CLONE, AC_CODEBOOK + q, 0), 0.0f, (1.0f / sqrtf((float)g.ae_vq_dim)) / Q3_IH4_STD, 0, e->stream);
+        if (!rc) rc = dev_alloc(e, c, (void**)&c->cb[q], ne * 4);
         if (!rc) hipLaunchKernelGGL(k_cb_transpose, dim3(nblk(ne)), dim3(256), 0, e->stream, rowmajor, c->cb[q], g.ae_codebook_size, g.ae_vq_dim);
         hipStreamSynchronize(e->stream);
         hipFree(rowmajor);
         CK(rc);
     }
     CK(dev_alloc(e, c, (void**)&c->cb_dev, sizeof(float*) * g.ae_n_codebooks));
-    Q3_HIP(e, hipMemcpyAsync((void*)c->cb_dev, c->cb.data(), sizeof(float*) * g.ae_n_codebooks, hipMemcpyHostToDevice, e->stream));
+    CK(hip_rc(e, hipMemcpyAsync((void*)c->cb_dev, c->cb.data(), sizeof(float*) * g.ae_n_codebooks, hipMemcpyHostToDevice, e->stream), "hipMemcpyAsync (codebook table)"));
     // RoPE tables (evaluated in double on the host, like the decoder's)
     const int half = g.ae_head_dim / 2;
     std::vector<float> cs((size_t)ROPE_MAX_T * half), sn((size_t)ROPE_MAX_T * half);
@@ -697,11 +735,60 @@ extern "C" int q3tts_clone_init(q3tts_engine* e, const q3tts_clone_config* cfg) 
             cs[(size_t)t * half + i] = (float)cos(a); sn[(size_t)t * half + i] = (float)sin(a);
         }
     CK(dev_alloc(e, c, (void**)&c->cs, cs.size() * 4)); CK(dev_alloc(e, c, (void**)&c->sn, sn.size() * 4));
-    Q3_HIP(e, hipMemcpyAsync(c->cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, e->stream));
-    Q3_HIP(e, hipMemcpyAsync(c->sn, sn.data(), sn.size() * 4, hipMemcpyHostToDevice, e->stream));
-    Q3_HIP(e, hipStreamSynchronize(e->stream));
-    Q3_HIP(e, hipGetLastError());
+    // (cs / sn are locals: on a failure the stream is drained before they go)
+    rc = hip_rc(e, hipMemcpyAsync(c->cs, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, e->stream), "hipMemcpyAsync (RoPE table)");
+    if (!rc) rc = hip_rc(e, hipMemcpyAsync(c->sn, sn.data(), sn.size() * 4, hipMemcpyHostToDevice, e->stream), "hipMemcpyAsync (RoPE table)");
+    const int rc_sync = hip_rc(e, hipStreamSynchronize(e->stream), "hipStreamSynchronize (clone encoders)");
+    CK(rc ? rc : rc_sync);
+    CK(hip_rc(e, hipGetLastError(), "clone encoder creation"));
 #undef CK
+    c->file = nullptr;
+    e->clone_source = files ? 2 : 1;
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_clone_init(q3tts_engine* e, const q3tts_clone_config* cfg) {
+    Q3_NOT_IN_SESSION(e);
+    if (!e || !cfg) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
+    const int rc = validate(e, *cfg);
+    if (rc) return rc;
+    return clone_create(e, cfg, nullptr);
+}
+
+// The host half of q3tts_clone_load: everything a pair of files can get wrong is found here, before the device and the encoders the engine
+// has are touched. On success `files` are open and *cfg is their shape (e == nullptr: the message goes to the thread's error slot).
+static int files_host_check(q3tts_engine* e, const std::string& dir, Q3CloneFiles& files, q3tts_clone_config* cfg) {
+    std::string err;
+    const int st = q3_clone_files_open(dir, files, err);
+    if (st) return q3_set_err(e, st == 1 ? Q3TTS_ERR_IO : Q3TTS_ERR_INVALID, err);
+    q3tts_clone_default_config(cfg);
+    if (q3_clone_file_config(files, cfg, err) || q3_clone_file_check(files, *cfg, err)) return q3_set_err(e, Q3TTS_ERR_INVALID, err);
+    return validate(e, *cfg);
+}
+
+extern "C" int q3tts_clone_load(q3tts_engine* e, const char* weights_dir) {
+    Q3_NOT_IN_SESSION(e);
+    if (!e) return q3_set_err(e, Q3TTS_ERR_INVALID, "null argument");
+    if (!weights_dir && e->weights_dir.empty())
+        return q3_set_err(e, Q3TTS_ERR_STATE, "q3tts_clone_load: no directory given and the engine was created without a weights_path");
+    const std::string dir = weights_dir ? std::string(weights_dir) : e->weights_dir;
+    Q3CloneFiles files;
+    q3tts_clone_config cfg;
+    const int rc = files_host_check(e, dir, files, &cfg);
+    if (rc) return rc;
+    return clone_create(e, &cfg, &files);
+}
+
+extern "C" int q3tts_k_clone_load_check(const char* weights_dir) {
+    if (!weights_dir) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    Q3CloneFiles files;
+    q3tts_clone_config cfg;
+    return files_host_check(nullptr, weights_dir, files, &cfg);
+}
+
+extern "C" int q3tts_get_clone_source(const q3tts_engine* e, int32_t* source) {
+    if (!e || !source) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    *source = e->clone_source;
     return Q3TTS_OK;
 }
 

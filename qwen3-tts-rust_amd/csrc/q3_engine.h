@@ -143,7 +143,9 @@ struct q3tts_engine {
     Q3Voc* voc = nullptr;
     int voc_source = 0;                 // q3tts_get_vocoder_source: 0 no vocoder, 1 synthetic weights, 2 qwen3_tts_vocoder.gguf
     Q3Mel* mel = nullptr;               // created on first use
-    Q3Clone* clone = nullptr;           // q3tts_clone_init
+    Q3Clone* clone = nullptr;           // q3tts_clone_init / q3tts_clone_load
+    int clone_source = 0;               // q3tts_get_clone_source: 0 not loaded, 1 synthetic weights, 2 the two encoder files
+    std::string weights_dir;            // the config's weights_path ("" without one): where q3tts_clone_load(e, NULL) looks
     // q3tts_k_probe: eager frame steps, events around the Predictor gate/up GEMM (pass 1, layer 0) of every frame
     int probe = 0, probe_kind = 0;      // probe: 0 off, 1 Predictor (pass 1, block 0), 2 Talker (block 0); kind: 0 gate/up, 1 QKV, 2 attention, 3 O, 4 down
     std::vector<hipEvent_t> probe_ev;   // 2 per frame of a chunk

@@ -242,6 +242,7 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     if (cfg->device < 0 || cfg->device >= ndev) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "device ordinal out of range");
     q3tts_engine* e = new q3tts_engine();
     e->cfg = *cfg; e->cfg.weights_path = nullptr;
+    e->weights_dir = cfg->weights_path ? cfg->weights_path : "";
     e->max_steps = cfg->max_steps_cap < 512 ? cfg->max_steps_cap : 512;
     auto fail = [&](int rc) { std::string m = e->err; q3tts_engine_destroy(e); g_err = m; return rc; };
 #define TRYC(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return fail(rc__); } while (0)

@@ -674,16 +674,18 @@ int vf_check_tensors(const Q3Gguf& g, const std::string& file, const q3tts_vocod
 
 }  // namespace
 
-std::string q3_voc_file_find(const std::string& wdir) {
+// wdir/name (the quant directory), else the same name in wdir's parent (the model directory); "" when neither exists
+static std::string file_beside_model(const std::string& wdir, const char* name) {
     auto is_file = [](const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); };
     std::string d = wdir;
     while (d.size() > 1 && d.back() == '/') d.pop_back();
-    if (is_file(d + "/" + Q3_VOC_FILE_NAME)) return d + "/" + Q3_VOC_FILE_NAME;
+    if (is_file(d + "/" + name)) return d + "/" + name;
     const size_t sl = d.rfind('/');
     const std::string parent = sl == std::string::npos ? std::string(".") : sl == 0 ? std::string("/") : d.substr(0, sl);
-    const std::string p = (parent == "/" ? std::string() : parent) + "/" + Q3_VOC_FILE_NAME;
+    const std::string p = (parent == "/" ? std::string() : parent) + "/" + name;
     return is_file(p) ? p : std::string();
 }
+std::string q3_voc_file_find(const std::string& wdir) { return file_beside_model(wdir, Q3_VOC_FILE_NAME); }
 
 int q3_voc_file_config(const Q3Gguf& g, const std::string& file, q3tts_vocoder_config* vc, std::string& err) {
     q3tts_vocoder_config c = *vc;  // (*vc is written only on success; layer_scale_init is no file's to state)
@@ -835,6 +837,334 @@ extern "C" int q3tts_k_gguf_meta(const char* path, const char* key, int32_t* val
             else if (m.elem_type == Q3_GV_U64) values[j] = (double)load_int(p, m.elem_type);
             else values[j] = (double)(int64_t)load_int(p, m.elem_type);
         }
+    }
+    return Q3TTS_OK;
+}
+
+// ---- the clone encoders' weights files (q3_gguf.h; the table is DESIGN.md §29) ---------------------------------------------------------
+namespace {
+
+const char* const kSpkArch = "q3tts-speaker-encoder";
+const char* const kCodecArch = "q3tts-codec-encoder";
+
+// how the file's tensors (PyTorch layout) become the device's array
+enum CfKind {
+    CF_VEC,   // biases, LayerNorm, LayerScale: [n] as stored
+    CF_BOOK,  // codebook table [codebook_size][vq_dim]: as stored
+    CF_CONV,  // Conv1d [n][cin][k] -> rows W[n][tap * cin + ci], zero-padded to kp, bf16
+    CF_LIN,   // Linear [n][cin] -> rows W[n][ci], zero-padded to kp, bf16
+    CF_QKV    // three Linear [dq][cin] (q, k, v) -> the rows of the first under those of the second under those of the third, as CF_LIN
+};
+struct CfSpec { int file = 0; std::vector<std::string> names; std::vector<int64_t> shape; CfKind kind = CF_VEC; };  // file: 0 speaker, 1 codec
+
+inline int64_t cf_round512(int64_t k) { return (k + 511) / 512 * 512; }
+
+// generator id (comp, which) -> file tensor(s); false for an id the shape c does not have
+bool cf_spec(const q3tts_clone_config& c, int comp, int which, CfSpec* s) {
+    auto conv = [&](int file, const std::string& base, int w0, int64_t n, int64_t cin, int64_t k, bool bias) {
+        s->file = file;
+        if (which == w0) { s->names = {base + ".weight"}; s->shape = {n, cin, k}; s->kind = CF_CONV; return true; }
+        if (bias && which == w0 + 1) { s->names = {base + ".bias"}; s->shape = {n}; s->kind = CF_VEC; return true; }
+        return false;
+    };
+    const int64_t C = c.se_channels[0], C4 = c.se_channels[4], S = c.se_res2net_scale > 0 ? c.se_res2net_scale : 1, wp = C / S;
+    if (comp == SC_TDNN0) return conv(0, "blocks.0.conv", 0, C, c.mel_dim, c.se_kernels[0], true);
+    if (comp >= SC_BLOCK && comp < SC_BLOCK + 3) {
+        const int i = comp - SC_BLOCK + 1;
+        const std::string p = "blocks." + std::to_string(i) + ".";
+        if (which >= SW_RES2 + 2 && which < SW_RES2 + 2 * S) {
+            const int br = (which - SW_RES2) / 2;  // branch 1 .. S-1 is the family's blocks[br - 1]
+            return conv(0, p + "res2net_block.blocks." + std::to_string(br - 1) + ".conv", SW_RES2 + 2 * br, wp, wp, c.se_kernels[i], true);
+        }
+        switch (which & ~1) {
+            case SW_TDNN1: return conv(0, p + "tdnn1.conv", SW_TDNN1, C, C, 1, true);
+            case SW_TDNN2: return conv(0, p + "tdnn2.conv", SW_TDNN2, C, C, 1, true);
+            case SW_SE1: return conv(0, p + "se_block.conv1", SW_SE1, c.se_se_channels, C, 1, true);
+            case SW_SE2: return conv(0, p + "se_block.conv2", SW_SE2, C, c.se_se_channels, 1, true);
+            default: return false;
+        }
+    }
+    if (comp == SC_MFA) return conv(0, "mfa.conv", 0, C4, 3 * C, c.se_kernels[4], true);
+    if (comp == SC_ASP_TDNN) return conv(0, "asp.tdnn.conv", 0, c.se_attn_channels, 3 * C4, 1, true);
+    if (comp == SC_ASP_CONV) return conv(0, "asp.conv", 0, C4, c.se_attn_channels, 1, true);
+    if (comp == SC_FC) return conv(0, "fc", 0, c.se_dim, 2 * C4, 1, true);
+    // the audio encoder: SEANet layer indices are the family's (an ELU between the convolutions takes one index each)
+    const int nr = c.ae_n_ratios;
+    if (comp == AC_CONV0) return conv(1, "encoder.layers.0.conv", 0, c.ae_filters, 1, c.ae_kernel, true);
+    if (comp >= AC_STAGE && comp < AC_STAGE + 4 * nr && comp < AC_STAGE + 16) {
+        const int i = (comp - AC_STAGE) / 4, part = (comp - AC_STAGE) % 4, li = 1 + 3 * i;
+        int64_t Ca = c.ae_filters;
+        for (int j = 0; j < i; ++j) Ca *= 2;
+        const std::string p = "encoder.layers." + std::to_string(li);
+        if (part == 0) return conv(1, p + ".block.1.conv", 0, Ca / 2, Ca, c.ae_res_kernel, true);
+        if (part == 1) return conv(1, p + ".block.3.conv", 0, Ca, Ca / 2, 1, true);
+        if (part == 2) return conv(1, "encoder.layers." + std::to_string(li + 2) + ".conv", 0, 2 * Ca, Ca, 2 * (int64_t)c.ae_ratios[i], true);
+        return false;
+    }
+    const int64_t H = c.ae_hidden, dq = (int64_t)c.ae_n_head * c.ae_head_dim, F = c.ae_d_ffn;
+    if (comp == AC_LAST) {
+        int64_t Ca = c.ae_filters;
+        for (int j = 0; j < nr; ++j) Ca *= 2;
+        return conv(1, "encoder.layers." + std::to_string(3 * nr + 2) + ".conv", 0, H, Ca, c.ae_last_kernel, true);
+    }
+    if (comp >= AC_TFM && comp < AC_TFM + c.ae_n_layer && comp < AC_DOWN) {
+        const std::string p = "encoder_transformer.layers." + std::to_string(comp - AC_TFM) + ".";
+        s->file = 1;
+        auto vec = [&](const std::string& name) { s->names = {p + name}; s->shape = {H}; s->kind = CF_VEC; return true; };
+        auto lin = [&](const std::string& name, int64_t n, int64_t cin) { s->names = {p + name}; s->shape = {n, cin}; s->kind = CF_LIN; return true; };
+        switch (which) {
+            case TW_LN1_W: return vec("input_layernorm.weight");
+            case TW_LN1_B: return vec("input_layernorm.bias");
+            case TW_LN2_W: return vec("post_attention_layernorm.weight");
+            case TW_LN2_B: return vec("post_attention_layernorm.bias");
+            case TW_LS1: return vec("self_attn_layer_scale.scale");
+            case TW_LS2: return vec("mlp_layer_scale.scale");
+            case TW_QKV:
+                s->names = {p + "self_attn.q_proj.weight", p + "self_attn.k_proj.weight", p + "self_attn.v_proj.weight"};
+                s->shape = {dq, H}; s->kind = CF_QKV;
+                return true;
+            case TW_O: return lin("self_attn.o_proj.weight", H, dq);
+            case TW_FC1: return lin("mlp.fc1.weight", F, H);
+            case TW_FC2: return lin("mlp.fc2.weight", H, F);
+            default: return false;
+        }
+    }
+    if (comp == AC_DOWN) return conv(1, "downsample.conv", 0, H, H, 2 * (int64_t)c.ae_down_stride, false);
+    if (comp == AC_SEM_PROJ) return conv(1, "quantizer.semantic_residual_vector_quantizer.input_proj", 0, c.ae_vq_dim, H, 1, false);
+    if (comp == AC_AC_PROJ) return conv(1, "quantizer.acoustic_residual_vector_quantizer.input_proj", 0, c.ae_vq_dim, H, 1, false);
+    if (comp >= AC_CODEBOOK && comp < AC_CODEBOOK + c.ae_n_codebooks && which == 0) {
+        s->file = 1; s->names = {"quantizer.codebook." + std::to_string(comp - AC_CODEBOOK) + ".weight"};
+        s->shape = {c.ae_codebook_size, c.ae_vq_dim}; s->kind = CF_BOOK;
+        return true;
+    }
+    return false;
+}
+
+// every id the shape c has, in the order q3_clone.hip creates them
+std::vector<std::pair<int, int>> cf_ids(const q3tts_clone_config& c) {
+    std::vector<std::pair<int, int>> ids;
+    auto wb = [&](int comp, int w) { ids.push_back({comp, w}); ids.push_back({comp, w + 1}); };
+    wb(SC_TDNN0, 0);
+    for (int i = 0; i < 3; ++i) {
+        wb(SC_BLOCK + i, SW_TDNN1);
+        for (int p = 1; p < c.se_res2net_scale; ++p) wb(SC_BLOCK + i, SW_RES2 + 2 * p);
+        wb(SC_BLOCK + i, SW_TDNN2); wb(SC_BLOCK + i, SW_SE1); wb(SC_BLOCK + i, SW_SE2);
+    }
+    wb(SC_MFA, 0); wb(SC_ASP_TDNN, 0); wb(SC_ASP_CONV, 0); wb(SC_FC, 0);
+    wb(AC_CONV0, 0);
+    for (int i = 0; i < c.ae_n_ratios; ++i) for (int part = 0; part < 3; ++part) wb(AC_STAGE + 4 * i + part, 0);
+    wb(AC_LAST, 0);
+    for (int l = 0; l < c.ae_n_layer; ++l)
+        for (int w : {TW_LN1_W, TW_LN1_B, TW_LN2_W, TW_LN2_B, TW_LS1, TW_LS2, TW_QKV, TW_O, TW_FC1, TW_FC2}) ids.push_back({AC_TFM + l, w});
+    ids.push_back({AC_DOWN, 0}); ids.push_back({AC_SEM_PROJ, 0}); ids.push_back({AC_AC_PROJ, 0});
+    for (int q = 0; q < c.ae_n_codebooks; ++q) ids.push_back({AC_CODEBOOK + q, 0});
+    return ids;
+}
+
+const Q3Gguf& cf_gguf(const Q3CloneFiles& f, const CfSpec& s) { return s.file ? f.codec : f.spk; }
+const std::string& cf_path(const Q3CloneFiles& f, const CfSpec& s) { return s.file ? f.codec_path : f.spk_path; }
+
+// the file's tensors of `s`: present, of the PyTorch shape, of a type the reader reads
+int cf_tensors(const Q3CloneFiles& f, const CfSpec& s, const char* whence, const Q3GgufTensor** out, std::string& err) {
+    for (size_t i = 0; i < s.names.size(); ++i) {
+        VfSpec v; v.name = s.names[i]; v.shape = s.shape;
+        const Q3GgufTensor* t = vf_tensor(cf_gguf(f, s), cf_path(f, s), v, whence, err);
+        if (!t) return -1;
+        if (!t->data) { err = cf_path(f, s) + ": tensor '" + v.name + "': unsupported ggml type " + std::to_string(t->type) + " (supported: F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K)"; return -1; }
+        out[i] = t;
+    }
+    return 0;
+}
+
+struct CfMeta {
+    const Q3Gguf& g; const std::string& file; const char* arch; std::string& err;
+    int bad(const std::string& m) { err = file + ": " + m; return -1; }
+    std::string key(const char* k) const { return std::string(arch) + "." + k; }
+    int check_arch() {
+        std::string a;
+        const int st = g.meta_str("general.architecture", &a);
+        if (st == Q3_META_MISSING) return bad("metadata key 'general.architecture' is missing");
+        if (st == Q3_META_TYPE) return bad("metadata key 'general.architecture' is not a string");
+        if (a != arch) return bad("metadata key 'general.architecture' = '" + a + "', this file has '" + arch + "'");
+        return 0;
+    }
+    int integer(const char* k0, int64_t lo, int32_t* out) {
+        const std::string k = key(k0);
+        int64_t v = 0;
+        const int s = g.meta_int(k, &v);
+        if (s == Q3_META_MISSING) return bad("metadata key '" + k + "' is missing");
+        if (s == Q3_META_TYPE) return bad("metadata key '" + k + "' is not an integer");
+        if (v < lo || v > (1 << 24)) return bad("metadata key '" + k + "' = " + std::to_string(v) + " is out of range");
+        *out = (int32_t)v;
+        return 0;
+    }
+    int real(const char* k0, float* out) {
+        const std::string k = key(k0);
+        double v = 0;
+        const int s = g.meta_float(k, &v);
+        if (s == Q3_META_MISSING) return bad("metadata key '" + k + "' is missing");
+        if (s == Q3_META_TYPE) return bad("metadata key '" + k + "' is not a float");
+        if (!std::isfinite(v)) return bad("metadata key '" + k + "' is not finite");
+        *out = (float)v;
+        return 0;
+    }
+    // an integer array of lo_n .. cap entries, each 1 .. 4096; entries past its length are 0
+    int ints(const char* k0, int lo_n, int cap, int32_t* n, int32_t* out) {
+        const std::string k = key(k0);
+        std::vector<int64_t> v;
+        const int s = g.meta_int_array(k, &v);
+        if (s == Q3_META_MISSING) return bad("metadata key '" + k + "' is missing");
+        if (s == Q3_META_TYPE) return bad("metadata key '" + k + "' is not an integer array");
+        if ((int64_t)v.size() < lo_n || (int64_t)v.size() > cap)
+            return bad("metadata key '" + k + "' has " + std::to_string(v.size()) + " entries, " + (lo_n == cap ? std::to_string(cap) : std::to_string(lo_n) + " .. " + std::to_string(cap)) + " are needed");
+        for (int i = 0; i < cap; ++i) out[i] = 0;
+        for (size_t i = 0; i < v.size(); ++i) {
+            if (v[i] < 1 || v[i] > 4096) return bad("metadata key '" + k + "' entry " + std::to_string(i) + " = " + std::to_string(v[i]) + " is out of range");
+            out[i] = (int32_t)v[i];
+        }
+        if (n) *n = (int32_t)v.size();
+        return 0;
+    }
+};
+
+int cf_read_meta(const Q3CloneFiles& f, q3tts_clone_config* c, std::string& err) {
+    CfMeta s{f.spk, f.spk_path, kSpkArch, err};
+    if (s.check_arch() || s.integer("mel_dim", 1, &c->mel_dim) || s.ints("channels", 5, 5, nullptr, c->se_channels) ||
+        s.ints("kernel_sizes", 5, 5, nullptr, c->se_kernels) || s.ints("dilations", 5, 5, nullptr, c->se_dilations) ||
+        s.integer("attention_channels", 1, &c->se_attn_channels) || s.integer("res2net_scale", 1, &c->se_res2net_scale) ||
+        s.integer("se_channels", 1, &c->se_se_channels) || s.integer("embedding_length", 1, &c->se_dim)) return -1;
+    CfMeta a{f.codec, f.codec_path, kCodecArch, err};
+    if (a.check_arch() || a.integer("filters", 1, &c->ae_filters) || a.integer("kernel_size", 1, &c->ae_kernel) ||
+        a.integer("residual_kernel_size", 1, &c->ae_res_kernel) || a.integer("last_kernel_size", 1, &c->ae_last_kernel) ||
+        a.ints("ratios", 1, 4, &c->ae_n_ratios, c->ae_ratios) || a.integer("embedding_length", 1, &c->ae_hidden) ||
+        a.integer("block_count", 0, &c->ae_n_layer) || a.integer("attention.head_count", 1, &c->ae_n_head) ||
+        a.integer("attention.key_length", 1, &c->ae_head_dim) || a.integer("feed_forward_length", 1, &c->ae_d_ffn) ||
+        a.integer("attention.sliding_window", 1, &c->ae_window) || a.real("rope.freq_base", &c->ae_rope_theta) ||
+        a.real("attention.layer_norm_epsilon", &c->ae_ln_eps) || a.integer("down_stride", 1, &c->ae_down_stride) ||
+        a.integer("vq_dim", 1, &c->ae_vq_dim) || a.integer("n_codebooks", 1, &c->ae_n_codebooks) || a.integer("codebook_size", 1, &c->ae_codebook_size)) return -1;
+    // the generator's ids leave AC_DOWN - AC_TFM layers and 256 - AC_CODEBOOK tables their own numbers
+    if (c->ae_n_layer > AC_DOWN - AC_TFM) return a.bad("metadata key '" + a.key("block_count") + "' = " + std::to_string(c->ae_n_layer) + " is out of range");
+    if (c->ae_n_codebooks > 256 - AC_CODEBOOK) return a.bad("metadata key '" + a.key("n_codebooks") + "' = " + std::to_string(c->ae_n_codebooks) + " is out of range");
+    if (c->ae_filters > (1 << 16)) return a.bad("metadata key '" + a.key("filters") + "' = " + std::to_string(c->ae_filters) + " is out of range");
+    return 0;
+}
+
+// one id as the device's array (see q3_clone_file_array)
+int cf_array(const Q3CloneFiles& f, const CfSpec& s, const Q3GgufTensor* const* t, std::vector<float>& tmp, std::vector<float>& out, std::string& err) {
+    auto fail = [&]() { err = cf_path(f, s) + ": " + err; return -1; };
+    if (s.kind == CF_VEC || s.kind == CF_BOOK) {
+        out.resize(t[0]->nelem);
+        return q3_gguf_to_f32(*t[0], out.data(), err) ? fail() : 0;
+    }
+    const size_t N = (size_t)s.shape[0], CI = (size_t)s.shape[1], K = s.kind == CF_CONV ? (size_t)s.shape[2] : 1, kp = (size_t)cf_round512((int64_t)(K * CI));
+    out.assign(s.names.size() * N * kp, 0.0f);
+    for (size_t part = 0; part < s.names.size(); ++part) {
+        tmp.resize(t[part]->nelem);
+        if (q3_gguf_to_f32(*t[part], tmp.data(), err)) return fail();
+        float* o = out.data() + part * N * kp;
+        for (size_t n = 0; n < N; ++n) for (size_t ci = 0; ci < CI; ++ci) for (size_t k = 0; k < K; ++k) {
+            const uint32_t u = (uint32_t)f32_to_bf16_rne(tmp[(n * CI + ci) * K + k]) << 16;
+            memcpy(&o[n * kp + k * CI + ci], &u, 4);
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+int q3_clone_files_open(const std::string& wdir, Q3CloneFiles& f, std::string& err) {
+    f.spk_path = file_beside_model(wdir, Q3_SPK_FILE_NAME); f.codec_path = file_beside_model(wdir, Q3_CODEC_FILE_NAME);
+    if (f.spk_path.empty() || f.codec_path.empty()) {
+        const std::string where = " in " + wdir + " or its parent directory";
+        if (f.spk_path.empty() && f.codec_path.empty()) err = std::string(Q3_SPK_FILE_NAME) + " and " + Q3_CODEC_FILE_NAME + " not found" + where;
+        else if (f.spk_path.empty()) err = std::string(Q3_SPK_FILE_NAME) + " not found" + where + " (its partner is " + f.codec_path + "; the clone encoders need both files)";
+        else err = std::string(Q3_CODEC_FILE_NAME) + " not found" + where + " (its partner is " + f.spk_path + "; the clone encoders need both files)";
+        return 1;
+    }
+    if (f.spk.open(f.spk_path, err) || f.codec.open(f.codec_path, err)) return 2;
+    return 0;
+}
+
+int q3_clone_file_config(const Q3CloneFiles& f, q3tts_clone_config* cc, std::string& err) {
+    q3tts_clone_config c = *cc;  // (*cc is written only on success; ae_layer_scale is no file's to state)
+    if (cf_read_meta(f, &c, err)) return -1;
+    auto count = [&](bool codec, const char* key, int64_t want, const std::string& prefix, const std::string& suffix) {
+        const int64_t have = vf_count(codec ? f.codec : f.spk, prefix, suffix);
+        if (have == want) return 0;
+        err = (codec ? f.codec_path : f.spk_path) + ": metadata key '" + (codec ? kCodecArch : kSpkArch) + "." + key + "' implies " + std::to_string(want) + " tensors '" + prefix + "N" + suffix + "...', the file has " + std::to_string(have);
+        return -1;
+    };
+    for (int i = 1; i <= 3; ++i)
+        if (count(false, "res2net_scale", c.se_res2net_scale - 1, "blocks." + std::to_string(i) + ".res2net_block.blocks.", ".conv.weight")) return -1;
+    if (count(true, "ratios", c.ae_n_ratios, "encoder.layers.", ".block.1.conv.weight") || count(true, "block_count", c.ae_n_layer, "encoder_transformer.layers.", ".") ||
+        count(true, "n_codebooks", c.ae_n_codebooks, "quantizer.codebook.", ".weight")) return -1;
+    for (const auto& id : cf_ids(c)) {
+        CfSpec s; const Q3GgufTensor* t[3];
+        if (!cf_spec(c, id.first, id.second, &s)) { err = "no tensor for id (" + std::to_string(id.first) + ", " + std::to_string(id.second) + ")"; return -1; }
+        if (cf_tensors(f, s, "the file's metadata implies", t, err)) return -1;
+    }
+    *cc = c;
+    return 0;
+}
+
+int q3_clone_file_check(const Q3CloneFiles& f, const q3tts_clone_config& cc, std::string& err) {
+    std::vector<float> buf;
+    for (const auto& id : cf_ids(cc)) {
+        CfSpec s; const Q3GgufTensor* t[3];
+        if (!cf_spec(cc, id.first, id.second, &s)) { err = "no tensor for id (" + std::to_string(id.first) + ", " + std::to_string(id.second) + ")"; return -1; }
+        if (cf_tensors(f, s, "the configuration needs", t, err)) return -1;
+        for (size_t p = 0; p < s.names.size(); ++p) {
+            buf.resize(t[p]->nelem);
+            if (q3_gguf_to_f32(*t[p], buf.data(), err)) { err = cf_path(f, s) + ": " + err; return -1; }
+            for (size_t i = 0; i < buf.size(); ++i)
+                if (!std::isfinite(buf[i])) { err = cf_path(f, s) + ": tensor '" + s.names[p] + "' holds a value that is not finite (element " + std::to_string(i) + ")"; return -1; }
+        }
+    }
+    return 0;
+}
+
+int q3_clone_file_array(const Q3CloneFiles& f, const q3tts_clone_config& cc, int comp, int which, std::vector<float>& out, std::string& err) {
+    CfSpec s; const Q3GgufTensor* t[3];
+    if (!cf_spec(cc, comp, which, &s)) { err = "the clone encoders' shape has no tensor of id (" + std::to_string(comp) + ", " + std::to_string(which) + ")"; return -1; }
+    if (cf_tensors(f, s, "the configuration needs", t, err)) return -1;
+    std::vector<float> tmp;
+    return cf_array(f, s, t, tmp, out, err);
+}
+
+static void cf_copy_err(const std::string& msg, char* err, int32_t err_cap) {
+    if (err && err_cap > 0) { const size_t n = msg.size() < (size_t)err_cap - 1 ? msg.size() : (size_t)err_cap - 1; memcpy(err, msg.data(), n); err[n] = '\0'; }
+}
+
+extern "C" int q3tts_clone_files_find(const char* weights_dir, char* speaker_path, char* codec_path, int32_t cap) {
+    if (!weights_dir || !speaker_path || !codec_path || cap < 1) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    const std::string found[2] = {file_beside_model(weights_dir, Q3_SPK_FILE_NAME), file_beside_model(weights_dir, Q3_CODEC_FILE_NAME)};
+    char* const out[2] = {speaker_path, codec_path};
+    for (int i = 0; i < 2; ++i)
+        if (found[i].size() + 1 > (size_t)cap) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "path buffer too small: " + std::to_string(found[i].size() + 1) + " bytes are needed");
+    for (int i = 0; i < 2; ++i) memcpy(out[i], found[i].c_str(), found[i].size() + 1);
+    return (found[0].empty() ? 0 : 1) + (found[1].empty() ? 0 : 1);
+}
+
+extern "C" int q3tts_clone_config_from_dir(const char* weights_dir, q3tts_clone_config* cfg, char* err, int32_t err_cap) {
+    std::string msg;
+    auto done = [&](int rc) { cf_copy_err(msg, err, err_cap); return rc; };
+    if (!weights_dir || !cfg) { msg = "null argument"; return done(Q3TTS_ERR_INVALID); }
+    Q3CloneFiles f;
+    if (q3_clone_files_open(weights_dir, f, msg)) return done(Q3TTS_ERR_IO);
+    return done(q3_clone_file_config(f, cfg, msg) ? Q3TTS_ERR_INVALID : Q3TTS_OK);
+}
+
+extern "C" int q3tts_k_clone_file_tensor(const char* weights_dir, const q3tts_clone_config* cfg, int32_t comp, int32_t which, float* out, int64_t cap, int64_t* n) {
+    if (!weights_dir || !cfg || !n) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    std::string err;
+    Q3CloneFiles f;
+    if (q3_clone_files_open(weights_dir, f, err)) return q3_set_err(nullptr, Q3TTS_ERR_IO, err);
+    std::vector<float> a;
+    if (q3_clone_file_array(f, *cfg, comp, which, a, err)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, err);
+    *n = (int64_t)a.size();
+    if (out) {
+        if (cap < *n) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "output buffer too small");
+        memcpy(out, a.data(), a.size() * 4);
     }
     return Q3TTS_OK;
 }

@@ -105,3 +105,32 @@ int q3_voc_file_check(const Q3Gguf& g, const std::string& file, const q3tts_voco
 // nearest-even bf16 (a BF16 source passes bit for bit), vectors as stored, a SnakeBeta id evaluated in double (exp(alpha),
 // 1 / (exp(beta) + 1e-9)) like the generator's
 int q3_voc_file_array(const Q3Gguf& g, const std::string& file, const q3tts_vocoder_config& vc, int comp, int which, std::vector<float>& out, std::string& err);
+
+// ---- the clone encoders' weights files -------------------------------------------------------------------------------------
+// Two files beside the model, found like the vocoder's: qwen3_tts_speaker_encoder.gguf (ECAPA speaker encoder) and
+// qwen3_tts_codec_encoder.gguf (Mimi-style audio encoder). Tensor names and layouts are the state_dict keys and PyTorch layouts of the family's
+// modules (transformers' ECAPA_TimeDelayNet and MimiModel) plus quantizer.codebook.{q}.weight; every relayout to the device's arrays happens
+// here, on the host, and the encoders' one creation path (q3_clone.hip) takes each array either from the seeded generator or from
+// q3_clone_file_array.
+struct q3tts_clone_config;
+// tensor ids of the encoders' synthetic generator (oracle/q3_oracle_clone.c): component, tensor of the component
+enum { SC_TDNN0 = 0, SC_BLOCK = 1, SC_MFA = 8, SC_ASP_TDNN = 9, SC_ASP_CONV = 10, SC_FC = 11, AC_CONV0 = 32, AC_STAGE = 33,
+       AC_LAST = 60, AC_TFM = 64, AC_DOWN = 100, AC_SEM_PROJ = 101, AC_AC_PROJ = 102, AC_CODEBOOK = 110 };
+enum { SW_TDNN1 = 0, SW_TDNN2 = 2, SW_SE1 = 4, SW_SE2 = 6, SW_RES2 = 16 };
+enum { TW_LN1_W = 0, TW_LN1_B, TW_QKV, TW_O, TW_LS1, TW_LN2_W, TW_LN2_B, TW_FC1, TW_FC2, TW_LS2 };
+#define Q3_SPK_FILE_NAME "qwen3_tts_speaker_encoder.gguf"
+#define Q3_CODEC_FILE_NAME "qwen3_tts_codec_encoder.gguf"
+struct Q3CloneFiles { Q3Gguf spk, codec; std::string spk_path, codec_path; };
+// Finds each file in wdir (the quant directory), else in wdir's parent, and opens both. 0; 1 when a file is not found (err names it, and
+// says which of the two was there); 2 when a file that was found cannot be opened or ends early.
+int q3_clone_files_open(const std::string& wdir, Q3CloneFiles& f, std::string& err);
+// The three calls below return 0, or -1 with the reason in err (it names the file and the tensor or key).
+// every field of *cc the metadata states (ae_layer_scale is left alone), cross-checked against the shapes of every tensor; *cc is
+// written only on success
+int q3_clone_file_config(const Q3CloneFiles& f, q3tts_clone_config* cc, std::string& err);
+// what q3tts_clone_load refuses beyond that before it touches the device: a value that is not finite
+int q3_clone_file_check(const Q3CloneFiles& f, const q3tts_clone_config& cc, std::string& err);
+// the array the device holds for generator id (comp, which), as f32 in device layout: a convolution or projection [n][cin][k] as the rows
+// W[n][tap * cin + ci], zero-padded to round512(k * cin) and rounded to nearest-even bf16 (a BF16 source passes bit for bit), q / k / v
+// fused into the QKV rows in that order; biases, LayerNorm, LayerScale and codebooks as stored
+int q3_clone_file_array(const Q3CloneFiles& f, const q3tts_clone_config& cc, int comp, int which, std::vector<float>& out, std::string& err);

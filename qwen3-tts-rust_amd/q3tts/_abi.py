@@ -198,6 +198,7 @@ SYMBOLS = [
     "q3tts_k_session_doc_mem_cap", "q3tts_doc_default_opts", "q3tts_k_doc_rules", "q3tts_k_doc_plan", "q3tts_k_doc_stream",
     "q3tts_k_doc_stream_rate", "q3tts_k_doc_ring_plan", "q3tts_k_doc_out_pos",
     "q3tts_vocoder_config_from_file", "q3tts_get_vocoder_source", "q3tts_k_voc_file_tensor",
+    "q3tts_clone_config_from_dir", "q3tts_clone_load", "q3tts_get_clone_source", "q3tts_k_clone_file_tensor", "q3tts_k_clone_load_check", "q3tts_clone_files_find",
 ]
 
 # long documents (include/q3tts.h, "long documents"): break kinds, the join's block length, and the structs field for field
@@ -413,6 +414,12 @@ def load_library(path=None):
     lib.q3tts_clone_default_config.argtypes = [C.POINTER(CloneConfig)]
     lib.q3tts_clone_default_config.restype = None
     lib.q3tts_clone_init.argtypes = [vp, C.POINTER(CloneConfig)]
+    lib.q3tts_clone_config_from_dir.argtypes = [C.c_char_p, C.POINTER(CloneConfig), C.c_char_p, C.c_int32]
+    lib.q3tts_clone_load.argtypes = [vp, C.c_char_p]
+    lib.q3tts_get_clone_source.argtypes = [vp, i32p]
+    lib.q3tts_k_clone_load_check.argtypes = [C.c_char_p]
+    lib.q3tts_clone_files_find.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int32]
+    lib.q3tts_k_clone_file_tensor.argtypes = [C.c_char_p, C.POINTER(CloneConfig), C.c_int32, C.c_int32, f32p, C.c_int64, C.POINTER(C.c_int64)]
     lib.q3tts_clone_audio_frames.argtypes = [vp, C.c_int64]
     lib.q3tts_clone_audio_frames.restype = C.c_int32
     lib.q3tts_clone_audio_encode.argtypes = [vp, f32p, C.c_int64, C.POINTER(C.c_int64), C.c_int32, i32p]

@@ -138,7 +138,10 @@ class TtsEngine:
         """TtsEngine::new(model_dir, quant) (src/tts/engine.rs:84-169). With no config the model's shape comes from the GGUF files of the
         quant directory (q3tts_config_from_model_dir), whatever member of the family it holds; a config given by the caller is used as it
         is (its shapes must match the files) and is not modified. The vocoder's trained weights and shape come the same way from
-        qwen3_tts_vocoder.gguf in the quant directory or in model_dir (vocoder_is_synthetic tells whether there was one). There is no network here: with no weight container under model_dir the
+        qwen3_tts_vocoder.gguf in the quant directory or in model_dir (vocoder_is_synthetic tells whether there was one). The voice-clone
+        encoders are loaded when qwen3_tts_speaker_encoder.gguf and qwen3_tts_codec_encoder.gguf are both found the same way, as the
+        reference loads its ONNX pair (src/tts/engine.rs:105-119); with neither nothing is loaded (load_clone_encoders gives the synthetic
+        ones), with exactly one, or a pair whose embedding width or codebooks are not the model's, this raises. There is no network here: with no weight container under model_dir the
         engine uses seeded synthetic weights of the configured (default: 1.7B) shape. max_batch (1..256): the engine's slot count, in
         place of the config's (include/q3tts.h states the memory per slot; 256 slots of the 1.7B shape need n_ctx <= 1024 or so).
         kv_cache: None — a given config's own kv_q8_0 is kept (0, bf16, everywhere else); "bf16" — the Talker's K/V cache in bf16, whatever
@@ -167,7 +170,24 @@ class TtsEngine:
         if max_batch is not None:
             cfg.max_batch = int(max_batch)
         tok = load_tokenizer(model_dir) if model_dir else None
+        clone_files = native.clone_files_found(wdir) if wdir else (None, None)
+        if (clone_files[0] is None) != (clone_files[1] is None):
+            missing = native.CLONE_FILES[0 if clone_files[0] is None else 1]
+            raise _abi.Q3Error(f"{missing} not found in {wdir} or in {model_dir}: the clone encoders need both files "
+                               f"(found {clone_files[0] or clone_files[1]})")
         eng = cls(cfg, tok)
+        if clone_files[0] is not None:
+            try:
+                eng._native.clone_load(wdir)
+                cc, m = eng._native.clone_cfg, cfg.model
+                for what, have, want in (("speaker embedding width (embedding_length)", cc.se_dim, m.d_embed),
+                                         ("n_codebooks", cc.ae_n_codebooks, m.n_codebooks),
+                                         ("codebook_size", cc.ae_codebook_size, m.codebook_size)):
+                    if have != want:
+                        raise _abi.Q3Error(f"clone encoder files {clone_files[0]}, {clone_files[1]}: {what} = {have}, the model has {want}")
+            except Exception:
+                eng.close()
+                raise
         for d in ([os.path.join(model_dir, "preset_speakers")] if model_dir else []) + ["speakers"]:  # :156-166
             if os.path.isdir(d):
                 eng.load_speakers(d)
@@ -182,6 +202,12 @@ class TtsEngine:
         """True when the vocoder's weights are the seeded synthetic ones (no qwen3_tts_vocoder.gguf beside the model): the PCM is then the
         output of random filters, not speech. False with trained weights from the file. Meaningless without a vocoder (False)."""
         return self._native.vocoder_source == 1
+
+    @property
+    def clone_is_synthetic(self) -> bool:
+        """True when the clone encoders' weights are the seeded synthetic ones (load_clone_encoders): cloned voices are then the output of
+        random filters. False with trained weights from the two encoder files, and before any encoders are loaded."""
+        return self._native.clone_source == 1
 
     def set_max_steps(self, steps: int):
         self.max_steps = steps

@@ -387,6 +387,22 @@ class NativeEngine:
         self._check(self.lib.q3tts_clone_init(self.h, C.byref(ccfg)), "q3tts_clone_init")
         self.clone_cfg = ccfg
 
+    def clone_load(self, dir=None):
+        """q3tts_clone_load: both encoders from qwen3_tts_speaker_encoder.gguf and qwen3_tts_codec_encoder.gguf, found in `dir` or its
+        parent (None: the engine's own weights_path). clone_cfg becomes the shape the files state."""
+        wdir = None if dir is None else os.fsencode(dir)
+        self._check(self.lib.q3tts_clone_load(self.h, wdir), "q3tts_clone_load")
+        if wdir is None:
+            wdir = self.cfg.weights_path
+        self.clone_cfg = clone_config_from_dir(wdir)
+
+    @property
+    def clone_source(self):
+        """q3tts_get_clone_source: 0 = encoders not loaded, 1 = seeded synthetic weights (clone_init), 2 = the two files (clone_load)."""
+        s = C.c_int32(0)
+        self._check(self.lib.q3tts_get_clone_source(self.h, C.byref(s)), "q3tts_get_clone_source")
+        return int(s.value)
+
     def clone_audio_frames(self, n_samples):
         return int(self.lib.q3tts_clone_audio_frames(self.h, int(n_samples)))
 
@@ -1391,6 +1407,61 @@ def vocoder_config_from_file(path, base=None):
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_vocoder_config_from_file failed ({rc}): {err.value.decode('utf-8', 'replace')}")
     return vc
+
+
+CLONE_FILES = ("qwen3_tts_speaker_encoder.gguf", "qwen3_tts_codec_encoder.gguf")
+
+
+def clone_files_found(weights_dir):
+    """q3tts_clone_files_find: (speaker file, codec file) as q3tts_clone_load would find them — in weights_dir (the quant directory), else
+    in its parent; None for one that is in neither. Host only."""
+    lib = _abi.load_library()
+    d = os.fsencode(weights_dir)
+    cap = len(d) + 64
+    spk, codec = C.create_string_buffer(cap), C.create_string_buffer(cap)
+    rc = lib.q3tts_clone_files_find(d, spk, codec, cap)
+    if rc < 0:
+        raise _abi.Q3Error(f"q3tts_clone_files_find failed ({rc}): {lib.q3tts_last_error(None).decode('utf-8', 'replace')}")
+    return tuple(os.fsdecode(b.value) if b.value else None for b in (spk, codec))
+
+
+def clone_config_from_dir(weights_dir, base=None):
+    """q3tts_clone_config_from_dir: a copy of the clone config `base` (default: q3tts_clone_default_config's) with every field the two
+    encoder files found from weights_dir state, cross-checked against their tensor shapes. Host only."""
+    lib = _abi.load_library()
+    if base is not None:
+        cc = _abi.CloneConfig.from_buffer_copy(base)
+    else:
+        cc = _abi.CloneConfig()
+        lib.q3tts_clone_default_config(cc)
+    err = C.create_string_buffer(1024)
+    rc = lib.q3tts_clone_config_from_dir(os.fsencode(weights_dir), C.byref(cc), err, len(err))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_clone_config_from_dir failed ({rc}): {err.value.decode('utf-8', 'replace')}")
+    return cc
+
+
+def k_clone_load_check(weights_dir):
+    """q3tts_k_clone_load_check: (status, message) of the host half of q3tts_clone_load on the pair found from weights_dir. Host only."""
+    lib = _abi.load_library()
+    rc = lib.q3tts_k_clone_load_check(os.fsencode(weights_dir))
+    return rc, ("" if rc == 0 else lib.q3tts_last_error(None).decode("utf-8", "replace"))
+
+
+def k_clone_file_tensor(weights_dir, cc, comp, which):
+    """q3tts_k_clone_file_tensor: the f32 array (device layout, after rounding) q3tts_clone_load would upload from the pair found from
+    weights_dir for the synthetic generator's tensor id (comp, which) at the shape `cc`. Host only."""
+    lib = _abi.load_library()
+    n = C.c_int64(0)
+    p = os.fsencode(weights_dir)
+    rc = lib.q3tts_k_clone_file_tensor(p, C.byref(cc), comp, which, None, 0, C.byref(n))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_clone_file_tensor failed ({rc}): {lib.q3tts_last_error(None).decode('utf-8', 'replace')}")
+    out = np.zeros(n.value, dtype=np.float32)
+    rc = lib.q3tts_k_clone_file_tensor(p, C.byref(cc), comp, which, _ptr(out, f32p), out.size, C.byref(n))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_clone_file_tensor failed ({rc}): {lib.q3tts_last_error(None).decode('utf-8', 'replace')}")
+    return out
 
 
 def k_voc_file_tensor(path, vc, comp, which):

@@ -162,6 +162,17 @@ extern "C" {
     // voice-clone encoders (replace AudioEncoder / SpeakerEncoder, src/models/onnx.rs:82-160)
     pub fn q3tts_clone_default_config(cfg: *mut q3tts_clone_config);
     pub fn q3tts_clone_init(e: *mut q3tts_engine, cfg: *const q3tts_clone_config) -> c_int;
+    // trained encoder weights from qwen3_tts_speaker_encoder.gguf / qwen3_tts_codec_encoder.gguf, found in weights_dir or its parent
+    // (NULL: the engine's own weights_path); host-only shape query, loader, source (0 not loaded, 1 synthetic, 2 files), host-only test hook
+    pub fn q3tts_clone_config_from_dir(weights_dir: *const c_char, cfg: *mut q3tts_clone_config, err: *mut c_char, err_cap: i32) -> c_int;
+    pub fn q3tts_clone_load(e: *mut q3tts_engine, weights_dir: *const c_char) -> c_int;
+    pub fn q3tts_get_clone_source(e: *const q3tts_engine, source: *mut i32) -> c_int;
+    // where the two files are (each path into its buffer of cap bytes, "" when absent): returns how many were found, or a negative status
+    pub fn q3tts_clone_files_find(weights_dir: *const c_char, speaker_path: *mut c_char, codec_path: *mut c_char, cap: i32) -> c_int;
+    // host-only test hook: the host half of q3tts_clone_load (open, shape, cross-checks, finite values, config rules) with its status
+    pub fn q3tts_k_clone_load_check(weights_dir: *const c_char) -> c_int;
+    pub fn q3tts_k_clone_file_tensor(weights_dir: *const c_char, cfg: *const q3tts_clone_config, comp: i32, which: i32, out: *mut c_float, cap: i64,
+                                     n: *mut i64) -> c_int;
     pub fn q3tts_clone_audio_frames(e: *const q3tts_engine, n_samples: i64) -> i32;
     pub fn q3tts_clone_audio_encode(e: *mut q3tts_engine, audio: *const c_float, n_samples: i64, codes: *mut i64, cap_frames: i32, n_frames: *mut i32) -> c_int;
     pub fn q3tts_clone_speaker_encode(e: *mut q3tts_engine, audio: *const c_float, n_samples: i64, spk_emb: *mut c_float) -> c_int;
@@ -221,6 +232,13 @@ impl TtsEngine {
         let rc = unsafe { q3tts_get_vocoder_source(self.raw, &mut src) };
         self.check(rc, "q3tts_get_vocoder_source")?;
         Ok(src == 1)
+    }
+    /// where the clone encoders' weights came from: 0 not loaded, 1 seeded synthetic (q3tts_clone_init), 2 the two encoder files (q3tts_clone_load)
+    pub fn clone_source(&self) -> Result<i32, String> {
+        let mut src = 0i32;
+        let rc = unsafe { q3tts_get_clone_source(self.raw, &mut src) };
+        self.check(rc, "q3tts_get_clone_source")?;
+        Ok(src)
     }
     pub fn set_max_steps(&mut self, steps: usize) { self.max_steps = steps; }
     pub fn set_sampler_config(&mut self, c: SamplerConfig) { self.sampler = c; }
