@@ -932,6 +932,11 @@ int q3tts_k_mfma_bf16(int32_t device, const uint16_t* a, const uint16_t* b, cons
 int q3tts_k_bgemm(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const uint16_t* w_bf16, int32_t N, const float* ssp, int32_t ntiles,
                   int32_t d_norm, float eps, int32_t epilogue, const float* nw_next, float* y, uint16_t* yb, float* ssp_out, uint64_t* keys,
                   int32_t iters, float* mean_kernel_ms);
+/* The same launch on rows [a_row0, a_row0 + B) of an operand buffer xb [a_row0 + B][K] (how the engine launches a row range of a shared
+ * buffer); ssp, y, yb, ssp_out and keys belong to those B rows. Same bits as q3tts_k_bgemm on the B rows alone. */
+int q3tts_k_bgemm_rows(int32_t device, const uint16_t* xb, int32_t a_row0, int32_t B, int32_t K, const uint16_t* w_bf16, int32_t N, const float* ssp,
+                       int32_t ntiles, int32_t d_norm, float eps, int32_t epilogue, const float* nw_next, float* y, uint16_t* yb, float* ssp_out,
+                       uint64_t* keys);
 /* Which kernel serves launches of >= 256 rows: 1 = the many-row kernel (k_bgemm_big) whenever eligible, -1 = never, 0 = when it fills the
  * chip (default; the environment variable Q3TTS_BG_BIG sets the initial value once per process). The results are the same bits. */
 int q3tts_k_bgemm_policy(int32_t big);
@@ -966,6 +971,12 @@ int q3tts_k_swap_phase_ms(const q3tts_session* s, double out[3]);
 /* The k_bgemm instance the launcher takes for a shape, without launching: out5 = {row tiles, column tiles, ring depth, non-temporal weight
  * loads, 1 if k_bgemm_big}. bench.py names the kernel symbol of a probed launch from it. */
 int q3tts_k_bgemm_pick(int32_t B, int32_t K, int32_t N, int32_t epilogue, int32_t w_once, int32_t q8, int32_t* out5);
+/* Tests and tuning: every following launch of up to 255 rows whose N / 16 is a multiple of nt runs the (rt, nt) tile instance instead of the
+ * cost model's choice; (0, 0) restores the cost model. Process-wide: not for use beside a running engine. The results are the same bits. */
+int q3tts_k_bgemm_force(int32_t rt, int32_t nt);
+/* The instance the newest q3tts_k_bgemm* / engine launch of the decoder's GEMM ran: out6 = q3tts_k_bgemm_pick's five numbers, then the
+ * epilogue compiled into it (epilogue | 8: row scales from ssp | 16: nw_next), -1 = the kernel that decides the epilogue at run time. */
+int q3tts_k_bgemm_last(int32_t* out6);
 /* The same launch with ggml Q8_0 weights kept in block form on the device: q int8 [N][K] row-major (epilogue 2: the
  * N/2 gate rows, then the N/2 up rows), d_f16 the blocks' f16 scales as bit patterns [N][K/32]; K % 512 == 0. Equals oracle q3o_bgemm_q8
  * bit for bit. */

@@ -16,6 +16,7 @@
 // Workgroup = 8 waves = the 8 K-slices of one (RT*16) x (NT*16) output tile; a wave keeps D steps of operands in flight
 // (register ring, refilled right after the MFMAs that consumed a slot); slice partials meet in LDS and are added in order.
 #include "q3_kernels.h"
+#include <atomic>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -47,11 +48,26 @@ __device__ __forceinline__ float bg_f16(uint32_t bits) { return (float)__builtin
 // Q8: the weights are ggml Q8_0 blocks in the tiled Q8 layout (q3_kernels.h): 1.06 bytes per weight instead of 2 through
 // the same ring; every 32-wide K step is one block: P = MFMA from a zero accumulator, acc = fmaf(f32(d), P, acc).
 #define BG_PH(RT_, NT_) ((8 * (RT_) * (NT_) > 64 && ((RT_) * (NT_)) % 2 == 0) ? 2 : 1)  // slice-reduction phases (k_bgemm, BgInst::lds)
-template <int RT, int NT, int D, bool NTW, bool Q8>
-__global__ __launch_bounds__(512) void k_bgemm(Q3BGemm g) {
+// EK: the epilogue as a compile-time constant. BG_EK_ANY = everything the struct can ask for, decided at run time (k_bgemm); otherwise
+// epilogue | BG_EK_SSP (row scales from ssp) | BG_EK_NW (RESID with nw_next), nothing else set (k_bgemm_epi: bg_ek below names the launches).
+// Same loads in the same order, same arithmetic: what a fixed EK removes is the run-time branches around the partials' reduction and the
+// epilogue operands — every one of them a join at which the compiler's load counters wait for more than the code behind it needs —
+// and the registers of operands the epilogue never reads (0.2 - 0.8 us per launch by the in-kernel stamps).
+#define BG_EK_ANY (-1)
+#define BG_EK_SSP 8
+#define BG_EK_NW 16
+template <int RT, int NT, int D, bool NTW, bool Q8, int EK>
+__device__ __forceinline__ void bg_body(const Q3BGemm& g) {
     extern __shared__ float part[];  // [8 waves][RT*NT*4 regs][64 lanes]
     __shared__ float srow[64];
     Q3_STAMP(g, 0);
+    constexpr bool ANY = EK < 0;
+    const int epi = ANY ? g.epi : (EK & 7);
+    const bool h_ssp = ANY ? g.ssp != nullptr : (EK & BG_EK_SSP) != 0;
+    const bool h_nw = ANY ? g.nw_next != nullptr : (EK & BG_EK_NW) != 0;
+    const bool h_cs = ANY ? g.col_scale != nullptr : false, h_bias = ANY ? g.bias != nullptr : false, h_seg = ANY ? g.seg_rows != 0 : false;
+    const bool h_ybcopy = ANY ? (g.yb && !g.nw_next) : false;  // RESID without nw_next: yb = bf16(y)
+#define BG_YOFF(row_) (h_seg ? bg_yoff(g, row_) : (size_t)(row_) * g.ldy)
     constexpr int TR = RT * NT * 4;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, kq = lane >> 4, r = lane & 15;
     // workgroups are dealt round-robin to the 8 XCDs in linear-id order: the row chunks of one column group get ids 8 apart
@@ -77,11 +93,16 @@ __global__ __launch_bounds__(512) void k_bgemm(Q3BGemm g) {
     // tools/chain_stamps.hip: done after the main loop it cost ~1 us of every norm GEMM); then the weights (HBM / Infinity Cache: the
     // long latency) and the rows (L2), D steps of both; last what only the epilogue reads (residual, next norm weight, bias, scale).
     // Every load below is unconditional (out-of-range steps re-read step per - 1): straight-line code, so the counted waits are exact.
+    // Measured again with the ring covering the whole K slice (profiles/r07/bgemm_prologue_stamps.txt): the weights in FRONT of the
+    // partials shorten the Predictor's launches by 0 - 0.35 us and lengthen the Talker's gate/up and down by 1.1 and 0.35 us (the
+    // reduction then waits behind D weight steps from HBM): the order stays. Of the 1.5 - 2.4 us up to "loads issued" 0.1 - 0.4 us were
+    // the run-time epilogue branches (gone with a fixed EK), at most 0.6 us the kernel-argument loads and the address arithmetic, the
+    // rest the CU's vector-memory path taking in the ring itself (14 - 24 KiB per wave, eight waves): not removable here.
     // norm GEMMs: wave w owns the row scales of rows w, w + 8, ...: lane j adds its tiles j, j + 64, ... in ascending order, then the
     // 64-lane butterfly
     constexpr int NR = 2 * RT;
     float sp0[NR], sp1[NR];
-    if (g.ssp) {
+    if (h_ssp) {
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
             const float* sp = g.ssp + (size_t)min(row0 + wave + 8 * i, B - 1) * g.ld_ssp;
@@ -131,19 +152,19 @@ __global__ __launch_bounds__(512) void k_bgemm(Q3BGemm g) {
     float yres[NOUT], nwv[NOUT], bsv[NOUT], csv[NOUT];
 #pragma unroll
     for (int it = 0; it < NOUT; ++it) { yres[it] = 0.0f; nwv[it] = 0.0f; bsv[it] = 0.0f; csv[it] = 1.0f; }
-    if (g.epi == Q3_EPI_RESID) {
+    if (epi == Q3_EPI_RESID) {
 #pragma unroll
         for (int it = 0; it < NOUT; ++it) {
             const int o = threadIdx.x + it * 512;
             const int l = o & 63, e = (o >> 6) & 3, t = o >> 8, i = t / NT, j = t - i * NT;
             const int row = row0 + 16 * i + 4 * (l >> 4) + e, col = (nb0 + min(j, NT - 1)) * 16 + (l & 15);
             const bool in = o < TR * 64;
-            yres[it] = (in && row < B) ? g.y[bg_yoff(g, row) + col] : 0.0f;
-            if (g.nw_next) nwv[it] = in ? g.nw_next[col] : 0.0f;
-            if (g.col_scale) csv[it] = in ? g.col_scale[col] : 1.0f;
+            yres[it] = (in && row < B) ? g.y[BG_YOFF(row) + col] : 0.0f;
+            if (h_nw) nwv[it] = in ? g.nw_next[col] : 0.0f;
+            if (h_cs) csv[it] = in ? g.col_scale[col] : 1.0f;
         }
     }
-    if (g.bias && g.epi != Q3_EPI_SWIGLU) {
+    if (h_bias && epi != Q3_EPI_SWIGLU) {
 #pragma unroll
         for (int it = 0; it < NOUT; ++it) {
             const int o = threadIdx.x + it * 512;
@@ -154,7 +175,7 @@ __global__ __launch_bounds__(512) void k_bgemm(Q3BGemm g) {
     }
     __builtin_amdgcn_sched_barrier(0);
     Q3_STAMP(g, 1);
-    if (g.ssp) {  // the NR butterflies are independent chains: interleaved; they wait for the partials only (the first loads issued)
+    if (h_ssp) {  // the NR butterflies are independent chains: interleaved; they wait for the partials only (the first loads issued)
         float av[NR];
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
@@ -257,7 +278,6 @@ __global__ __launch_bounds__(512) void k_bgemm(Q3BGemm g) {
     // workgroup. Same sums in the same slice order per element; a thread's elements keep their places (o = tid + 512 it).
     constexpr int PH = BG_PH(RT, NT), TP = RT * NT / PH, TRP = TR / PH, NOUTP = NOUT / PH;
     static_assert(PH == 1 || ((RT * NT) % 2 == 0 && (TRP * 64) % 512 == 0), "two phases need an even tile count and whole items per phase");
-    const int epi = g.epi;
 #pragma unroll
     for (int ph = 0; ph < PH; ++ph) {
         if (ph) __syncthreads();  // every wave is done reading the previous phase's partials
@@ -284,7 +304,7 @@ __global__ __launch_bounds__(512) void k_bgemm(Q3BGemm g) {
                 const int q = p & 31, l = ((q >> 3) << 4) + (q & 7), o = ((p >> 5) << 6) + l;
                 const int e = (o >> 6) & 3, t = ph * TP + (o >> 8), i = t / NT, j = t - i * NT;
                 const int rl = 16 * i + 4 * (l >> 4) + e, row = row0 + rl, c = l & 15;
-                const float sc = g.ssp ? srow[rl] : 1.0f;
+                const float sc = h_ssp ? srow[rl] : 1.0f;
                 float gt = part[o], up = part[o + 8];
 #pragma unroll
                 for (int wv = 1; wv < 8; ++wv) { gt = gt + part[(size_t)wv * (TRP * 64) + o]; up = up + part[(size_t)wv * (TRP * 64) + o + 8]; }
@@ -300,20 +320,20 @@ __global__ __launch_bounds__(512) void k_bgemm(Q3BGemm g) {
             const int rl = 16 * i + 4 * (l >> 4) + e, row = row0 + rl, c = l & 15;
             const int col = (nb0 + j) * 16 + c;
             const bool live = row < B;
-            const float sc = g.ssp ? srow[rl] : 1.0f;
+            const float sc = h_ssp ? srow[rl] : 1.0f;
             float v = part[o];
 #pragma unroll
             for (int wv = 1; wv < 8; ++wv) v = v + part[(size_t)wv * (TRP * 64) + o];
-            if (g.bias) v = v + bsv[it];
+            if (h_bias) v = v + bsv[it];
             if (epi == Q3_EPI_STORE) {
-                if (live) g.y[bg_yoff(g, row) + col] = g.ssp ? sc * v : v;
+                if (live) g.y[BG_YOFF(row) + col] = h_ssp ? sc * v : v;
             } else if (epi == Q3_EPI_GELU) {
                 if (live) g.yb[q3_atile_off(row, col, g.N >> 5)] = q3_bf16(bg_gelu_erf(v));
             } else if (epi == Q3_EPI_RESID) {
-                const float xv = g.col_scale ? yres[it] + csv[it] * v : yres[it] + v;
-                if (live) g.y[bg_yoff(g, row) + col] = xv;
-                if (g.yb && !g.nw_next && live) g.yb[q3_atile_off(row, col, g.N >> 5)] = q3_bf16(xv);
-                if (g.nw_next) {  // the consumer's norm inputs: bf16(x * nw) and the tile's sum of squares (16-lane butterfly)
+                const float xv = h_cs ? yres[it] + csv[it] * v : yres[it] + v;
+                if (live) g.y[BG_YOFF(row) + col] = xv;
+                if (h_ybcopy && live) g.yb[q3_atile_off(row, col, g.N >> 5)] = q3_bf16(xv);
+                if (h_nw) {  // the consumer's norm inputs: bf16(x * nw) and the tile's sum of squares (16-lane butterfly)
                     if (live) g.yb[q3_atile_off(row, col, g.N >> 5)] = q3_bf16(xv * nwv[it]);
                     float sq = xv * xv;
                     sq = sq + __shfl_xor(sq, 1); sq = sq + __shfl_xor(sq, 2); sq = sq + __shfl_xor(sq, 4); sq = sq + __shfl_xor(sq, 8);
@@ -321,7 +341,7 @@ __global__ __launch_bounds__(512) void k_bgemm(Q3BGemm g) {
                 }
             } else {  // Q3_EPI_ARGMAX: the largest key of the tile's 16 columns goes to keys[row][column tile]; the consumer takes the maximum
                       // over the row's N/16 entries (an atomicMax per (row, tile) on one word per row cost ~8 us of the launch)
-                unsigned long long key = q3_argmax_key(g.ssp ? sc * v : v, (uint32_t)col);
+                unsigned long long key = q3_argmax_key(h_ssp ? sc * v : v, (uint32_t)col);
 #pragma unroll
                 for (int m = 1; m <= 8; m <<= 1) { const unsigned long long ok = __shfl_xor(key, m); key = ok > key ? ok : key; }
                 if (live && c == 0) g.keys[(size_t)row * g.key_stride + (nb0 + j)] = key;
@@ -333,6 +353,23 @@ __global__ __launch_bounds__(512) void k_bgemm(Q3BGemm g) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     Q3_STAMP(g, 6);
 #endif
+#undef BG_YOFF
+}
+// k_bgemm: any Q3BGemm (its five-argument name is what q3tts_k_bgemm_pick reports: the tile instance). k_bgemm_epi: the same instance with
+// the epilogue fixed, for the launches bg_ek names — the decoder's STORE / RESID + nw_next / SWIGLU / ARGMAX on bf16 weights.
+template <int RT, int NT, int D, bool NTW, bool Q8>
+__global__ __launch_bounds__(512) void k_bgemm(Q3BGemm g) { bg_body<RT, NT, D, NTW, Q8, BG_EK_ANY>(g); }
+template <int RT, int NT, int D, bool NTW, int EK>
+__global__ __launch_bounds__(512) void k_bgemm_epi(Q3BGemm g) { bg_body<RT, NT, D, NTW, false, EK>(g); }
+#define BG_EK_EACH(X) X(Q3_EPI_STORE) X(Q3_EPI_STORE | BG_EK_SSP) X(Q3_EPI_RESID | BG_EK_NW) X(Q3_EPI_SWIGLU | BG_EK_SSP) X(Q3_EPI_ARGMAX | BG_EK_SSP)
+// the fixed epilogue of a launch, BG_EK_ANY when it asks for anything else (Q8_0 weights, the vocoder's extras, GELU, RESID without nw_next, ...)
+static int bg_ek(const Q3BGemm& g) {
+    if (g.wscale || g.bias || g.col_scale || g.seg_rows) return BG_EK_ANY;
+    if (g.epi == Q3_EPI_STORE) return g.ssp ? (Q3_EPI_STORE | BG_EK_SSP) : Q3_EPI_STORE;
+    if (g.epi == Q3_EPI_RESID && g.nw_next && !g.ssp) return Q3_EPI_RESID | BG_EK_NW;
+    if (g.epi == Q3_EPI_SWIGLU && g.ssp) return Q3_EPI_SWIGLU | BG_EK_SSP;
+    if (g.epi == Q3_EPI_ARGMAX && g.ssp) return Q3_EPI_ARGMAX | BG_EK_SSP;
+    return BG_EK_ANY;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -497,6 +534,17 @@ static void bg_launch_big(const Q3BGemm& g, hipStream_t s) {
     hipLaunchKernelGGL(k_bgemm_big, grid, dim3(256), BB_NS * 16384, s, g);
 }
 
+// The instance of the newest launch from any thread (test hook q3tts_k_bgemm_last: the picker's answer against what ran), one word:
+// rt | nt << 4 | d << 8 | ntw << 12 | big << 13 | (ek + 1) << 14.
+static std::atomic<uint32_t> g_last_launch{0};
+static void bg_note_launch(int rt, int nt, int d, bool ntw, int big, int ek) {
+    g_last_launch.store((uint32_t)rt | (uint32_t)nt << 4 | (uint32_t)d << 8 | (uint32_t)ntw << 12 | (uint32_t)big << 13 | (uint32_t)(ek + 1) << 14, std::memory_order_relaxed);
+}
+void q3_bgemm_last(int* rt, int* nt, int* d, int* ntw, int* big, int* ek) {
+    const uint32_t v = g_last_launch.load(std::memory_order_relaxed);
+    *rt = v & 15; *nt = (v >> 4) & 15; *d = (v >> 8) & 15; *ntw = (v >> 12) & 1; *big = (v >> 13) & 1; *ek = (int)(v >> 14) - 1;
+}
+
 // Operand steps in flight per wave (a step = 4 (RT + NT) registers; a K slice of 256 is 8 steps): 8, 5, 4, 3, 2 for RT + NT = <= 3, 4, 5, 6, 7,
 // which keeps every instance at <= ~146 registers per wave. Round 2 first ran 5-8 steps everywhere (160-230 registers): the shallow
 // depths are 3 % faster on the Talker's gate/up GEMM and 20 % on launches with more than one workgroup per CU (tools/bgemm_tune.hip), and
@@ -514,11 +562,23 @@ struct BgInst {
             hipFuncSetAttribute((const void*)k_bgemm<RT, NT, D, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipFuncSetAttribute((const void*)k_bgemm<RT, NT, D, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             hipFuncSetAttribute((const void*)k_bgemm<RT, NT, D, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+#define A(EK_) hipFuncSetAttribute((const void*)k_bgemm_epi<RT, NT, D, false, (EK_)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+               hipFuncSetAttribute((const void*)k_bgemm_epi<RT, NT, D, true, (EK_)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            BG_EK_EACH(A)
+#undef A
         }
     }
     static void launch(const Q3BGemm& g, dim3 grid, hipStream_t s) {
         // once-read weight streams (the Talker at decode: every tile goes to exactly one workgroup) take non-temporal loads
         const bool nt = g.w_once && grid.y == 1;
+        const int ek = bg_ek(g);
+        bg_note_launch(RT, NT, D, nt, 0, ek);
+#define L(EK_) if (ek == (EK_)) { \
+            if (nt) hipLaunchKernelGGL((k_bgemm_epi<RT, NT, D, true, (EK_)>), grid, dim3(512), lds, s, g); \
+            else hipLaunchKernelGGL((k_bgemm_epi<RT, NT, D, false, (EK_)>), grid, dim3(512), lds, s, g); \
+            return; }
+        BG_EK_EACH(L)
+#undef L
         if (g.wscale) {  // Q8_0 weights
             if (nt) hipLaunchKernelGGL((k_bgemm<RT, NT, D, true, true>), grid, dim3(512), lds, s, g);
             else hipLaunchKernelGGL((k_bgemm<RT, NT, D, false, true>), grid, dim3(512), lds, s, g);
@@ -615,7 +675,7 @@ int q3_launch_bgemm(const Q3BGemm& g, hipStream_t s) {
     q3_bgemm_prepare();
     int bestRT, bestNT, big;
     bg_pick(g, &bestRT, &bestNT, &big);
-    if (big) { bg_launch_big(g, s); return 0; }
+    if (big) { bg_note_launch(8, 8, 0, false, 1, BG_EK_ANY); bg_launch_big(g, s); return 0; }
     const dim3 grid(g.N / 16 / bestNT, (g.B + 16 * bestRT - 1) / (16 * bestRT));
 #define L(RT_, NT_) if (bestRT == RT_ && bestNT == NT_) { BgInst<RT_, NT_>::launch(g, grid, s); return 0; }
     BG_EACH(L)

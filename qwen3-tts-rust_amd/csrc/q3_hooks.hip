@@ -610,17 +610,18 @@ extern "C" int q3tts_k_sample(int32_t device, const float* logits, int32_t n, in
 // The decoder's GEMM on bf16 rows through its launcher (q3_bgemm.hip), behind q3tts_k_bgemm (w: bf16 bits row-major [N][K]) and
 // q3tts_k_bgemm_q8 (q8: w holds block_q8_0 rows). The entry points have checked the arguments.
 static int bgemm_hook(const char* name, int device, const uint16_t* xb, int B, int K, const void* w, bool q8, int N, const float* ssp, int ntiles, int d_norm,
-                      float eps, int epi, const float* nw_next, float* y, uint16_t* yb, float* ssp_out, uint64_t* keys, int iters, float* mean_ms) {
+                      float eps, int epi, const float* nw_next, float* y, uint16_t* yb, float* ssp_out, uint64_t* keys, int iters, float* mean_ms,
+                      int a_row0 = 0) {  // a_row0 > 0: xb holds a_row0 + B rows, the launch reads the last B of them (Q3BGemm.a_row0)
     HK(hipSetDevice(device));
     const int F = N / 2, nt = N / 16;
     DevBuf dx, dw, dwt, dsc, ds, dn, dy, dyb, dso, dk;
-    { const std::vector<uint16_t> xt = atile_host(xb, B, K); TRY(dx.put(xt.data(), xt.size() * 2)); }
+    { const std::vector<uint16_t> xt = atile_host(xb, a_row0 + B, K); TRY(dx.put(xt.data(), xt.size() * 2)); }
     TRY(dw.put(w, q8 ? (size_t)N * (K / 32) * 34 : (size_t)N * K * 2)); TRY(dwt.alloc(q8 ? (size_t)N * K : (size_t)N * K * 2));
     if (q8) TRY(dsc.alloc((size_t)N * (K / 32) * 2));
     TRY(ds.put(ntiles > 0 ? ssp : nullptr, (size_t)B * std::max(ntiles, 1) * 4)); TRY(dn.put(nw_next, (size_t)N * 4));
     TRY(dy.put(epi == Q3_EPI_RESID ? y : nullptr, (size_t)B * N * 4)); TRY(dyb.alloc(pad16(B) * N * 2)); TRY(dso.alloc((size_t)B * nt * 4)); TRY(dk.alloc((size_t)B * nt * 8));
     tile_weight(dw, dwt, q8 ? &dsc : nullptr, N, K, epi == Q3_EPI_SWIGLU);
-    Q3BGemm g{}; g.a = dx; g.a_row0 = 0; g.B = B; g.w = dwt; g.K = K; g.N = N;
+    Q3BGemm g{}; g.a = dx; g.a_row0 = a_row0; g.B = B; g.w = dwt; g.K = K; g.N = N;
     if (q8) g.wscale = dsc;
     if (ssp) g.ssp = ds;
     g.ld_ssp = ntiles; g.ntiles = ntiles; g.d_norm = d_norm; g.eps = eps; g.epi = epi;
@@ -653,6 +654,20 @@ extern "C" int q3tts_k_bgemm(int32_t device, const uint16_t* xb, int32_t B, int3
     if (epi == Q3_EPI_ARGMAX && !keys) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: keys missing");
     if (epi == Q3_EPI_RESID && nw_next && (!yb || !ssp_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm hook: norm outputs missing");
     return bgemm_hook("bgemm", device, xb, B, K, w, false, N, ssp, ntiles, d_norm, eps, epi, nw_next, y, yb, ssp_out, keys, iters, mean_ms);
+}
+
+// q3tts_k_bgemm on rows [a_row0, a_row0 + B) of an operand buffer of a_row0 + B rows (the engine's launches of a row range: Q3BGemm.a_row0);
+// ssp, y, yb, ssp_out and keys are those B rows'. Same bits as q3tts_k_bgemm on the B rows alone.
+extern "C" int q3tts_k_bgemm_rows(int32_t device, const uint16_t* xb, int32_t a_row0, int32_t B, int32_t K, const uint16_t* w, int32_t N, const float* ssp,
+                                  int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb, float* ssp_out,
+                                  uint64_t* keys) {
+    if (!xb || !w || a_row0 < 0 || a_row0 > (1 << 20) || B <= 0 || K % 256 || K < 256 || N % 16 || epi < 0 || epi > 3) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm rows hook: K % 256 == 0, N % 16 == 0");
+    if (epi == Q3_EPI_SWIGLU && (N % 64 || !yb)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm rows hook: swiglu needs N % 64 == 0 and yb");
+    if (epi == Q3_EPI_RESID && nw_next && (N % 32 || !yb || !ssp_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm rows hook: norm outputs");
+    if ((epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) && !y) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm rows hook: y missing");
+    if (epi == Q3_EPI_ARGMAX && !keys) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm rows hook: keys missing");
+    float ms = 0.0f;
+    return bgemm_hook("bgemm rows", device, xb, B, K, w, false, N, ssp, ntiles, d_norm, eps, epi, nw_next, y, yb, ssp_out, keys, 0, &ms, a_row0);
 }
 
 // the same launch with ggml Q8_0 weights kept in block form: q int8 [N][K], d_f16 [N][K/32]. Mirrors oracle q3o_bgemm_q8.
@@ -972,6 +987,20 @@ extern "C" int q3tts_k_bgemm_pick(int32_t B, int32_t K, int32_t N, int32_t epilo
     int rt, nt, d, ntw, big;
     q3_bgemm_pick(g, &rt, &nt, &d, &ntw, &big);
     out5[0] = rt; out5[1] = nt; out5[2] = d; out5[3] = ntw; out5[4] = big;
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_bgemm_force(int32_t rt, int32_t nt) {
+    if (!((rt == 0 && nt == 0) || (rt >= 1 && rt <= 4 && nt >= 1 && nt <= 3))) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm force: (0, 0) or row tiles 1..4, column tiles 1..3");
+    q3_bgemm_force(rt, nt);
+    return Q3TTS_OK;
+}
+
+extern "C" int q3tts_k_bgemm_last(int32_t* out6) {
+    if (!out6) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm last: null");
+    int v[6];
+    q3_bgemm_last(&v[0], &v[1], &v[2], &v[3], &v[4], &v[5]);
+    for (int i = 0; i < 6; ++i) out6[i] = v[i];
     return Q3TTS_OK;
 }
 

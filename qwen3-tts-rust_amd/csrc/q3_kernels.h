@@ -117,6 +117,7 @@ int q3_launch_bgemm8(const Q3BGemm& g, hipStream_t s);   // the same launch in g
 void q3_bgemm8_prepare();  // its kernel attributes, once per device; call outside stream capture
 void q3_bgemm8_pick(const Q3BGemm& g, int* rt, int* nt);
 void q3_bgemm_pick(const Q3BGemm& g, int* rt, int* nt, int* d, int* ntw, int* big);  // the instance q3_launch_bgemm takes for g (no launch)
+void q3_bgemm_last(int* rt, int* nt, int* d, int* ntw, int* big, int* ek);  // the instance q3_launch_bgemm launched last, as q3_bgemm_pick names it; ek: its fixed epilogue (epilogue | 8 row scales | 16 nw_next), -1 = decided at run time
 void q3_bgemm_force(int rt, int nt);  // tuning only: force a tile instance (0, 0: back to the cost model)
 void q3_bgemm_prepare();  // kernel attributes + the Q3TTS_BG_BIG policy (read once); call once outside stream capture
 void q3_bgemm_big_policy(int policy);  // 1 / -1 / 0: k_bgemm_big always / never / when it fills the chip (tests, A/B runs)

@@ -913,11 +913,14 @@ def k_gemm_exact(x, w_bf16, norm_w=None, eps=1e-6, bias=None, epilogue=0, y_in=N
     return y, keys, ms.value
 
 
-def k_bgemm(xb, wb, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=0, iters=0):
-    """The decoder's GEMM through its launcher (q3tts_k_bgemm): natural-order bf16 bit arrays in, the epilogue's outputs out."""
+def k_bgemm(xb, wb, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=0, iters=0, a_row0=0):
+    """The decoder's GEMM through its launcher (q3tts_k_bgemm): natural-order bf16 bit arrays in, the epilogue's outputs out.
+    a_row0 > 0 (q3tts_k_bgemm_rows): xb holds a_row0 more rows in front, the launch reads the rows behind them; ssp, y0 and the outputs are
+    those rows'."""
     lib = _abi.load_library()
     xb = np.ascontiguousarray(xb, dtype=np.uint16); wb = np.ascontiguousarray(wb, dtype=np.uint16)
     B, K = xb.shape
+    B -= a_row0
     N = wb.shape[0]
     y = np.zeros((B, N), dtype=np.float32) if y0 is None else np.ascontiguousarray(y0, dtype=np.float32).copy()
     yb = np.zeros((B, N // 2 if epi == 2 else N), dtype=np.uint16)
@@ -926,9 +929,13 @@ def k_bgemm(xb, wb, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=0, iter
     sp = None if ssp is None else np.ascontiguousarray(ssp, dtype=np.float32)
     nw = None if nw_next is None else np.ascontiguousarray(nw_next, dtype=np.float32)
     ms = C.c_float(0)
-    rc = lib.q3tts_k_bgemm(device, xb.ctypes.data, B, K, wb.ctypes.data, N, None if sp is None else sp.ctypes.data, 0 if sp is None else sp.shape[1],
-                           d_norm, eps, epi, None if nw is None else nw.ctypes.data, y.ctypes.data, yb.ctypes.data, sso.ctypes.data, keys.ctypes.data,
-                           iters, C.byref(ms))
+    if a_row0:
+        rc = lib.q3tts_k_bgemm_rows(device, xb.ctypes.data, a_row0, B, K, wb.ctypes.data, N, None if sp is None else sp.ctypes.data, 0 if sp is None else sp.shape[1],
+                                    d_norm, eps, epi, None if nw is None else nw.ctypes.data, y.ctypes.data, yb.ctypes.data, sso.ctypes.data, keys.ctypes.data)
+    else:
+        rc = lib.q3tts_k_bgemm(device, xb.ctypes.data, B, K, wb.ctypes.data, N, None if sp is None else sp.ctypes.data, 0 if sp is None else sp.shape[1],
+                               d_norm, eps, epi, None if nw is None else nw.ctypes.data, y.ctypes.data, yb.ctypes.data, sso.ctypes.data, keys.ctypes.data,
+                               iters, C.byref(ms))
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_bgemm failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return dict(y=y, yb=yb, ssp_out=sso, keys=keys, ms=ms.value)
