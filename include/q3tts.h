@@ -107,7 +107,9 @@ typedef struct q3tts_engine_config {
     const char* weights_path; /* NULL -> synthetic. Else the reference's quant directory (src/tts/engine.rs:91-131):
                                * qwen3_tts_talker.gguf + qwen3_tts_predictor.gguf (llama.cpp qwen3 tensor names; F32, F16,
                                * BF16, Q8_0 or the K-quants Q4_K / Q5_K / Q6_K of the gguf_q5_k_m directory, converted to
-                               * bf16 at load) and qwen3_assets.gguf or its NPY fallback
+                               * bf16 at load — unless talker_q8_0 / predictor_q8_0 keep Q8_0 blocks, or
+                               * q3tts_engine_options.kquant_resident (q3tts_engine_create_opts) keeps the K-quants, as
+                               * stored) and qwen3_assets.gguf or its NPY fallback
                                * (src/assets_manager.rs:14-26). Shapes must match `model`: q3tts_config_from_model_dir below
                                * fills `model` and this field from the files themselves. The table row counts
                                * (text_vocab, codec0_rows, codecq_rows) are taken from the files. The vocoder
@@ -226,6 +228,20 @@ int q3tts_vocoder_config_from_file(const char* path, q3tts_vocoder_config* vc, c
 /* TtsEngine::new (reference: src/tts/engine.rs:84-169): allocates weights, KV slabs, vocoder state on the
  * device and builds the replayable frame-step graphs. */
 int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine** out);
+/* Options beyond the q3tts_engine_config struct, whose size is fixed. A zeroed struct with struct_size set = q3tts_engine_create.
+ * kquant_resident = 1: every Talker and Predictor matrix (the blocks' QKV, O, gate/up and down, output.weight / the Predictor's heads)
+ * whose tensors in weights_path are ggml Q4_K / Q5_K / Q6_K stays in that form ON THE DEVICE (4.63 / 5.63 / 6.56 bits per weight
+ * instead of 16) and is decoded in registers inside the decoder's GEMM (csrc/q3_bgemmk.hip). A decoded weight is
+ * the bf16 value the default loader uploads and enters the same MFMA chain: ids, logits, hidden rows and PCM are bit for bit those of
+ * q3tts_engine_create on the same files; what changes is device memory, bytes per frame step and load time. A matrix stays bf16,
+ * silently, when a tensor of it has another type, when ffn_gate and ffn_up differ in type (their columns share a tile), and always with
+ * synthetic weights. Q3TTS_ERR_INVALID: kquant_resident together with talker_q8_0 != 0 or predictor_q8_0 != 0 (the message names both
+ * settings), a value other than 0 / 1, and a struct_size this library does not know. opts == NULL: q3tts_engine_create. */
+typedef struct { uint32_t struct_size; int32_t kquant_resident; } q3tts_engine_options;
+int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3tts_engine_options* opts, q3tts_engine** out);
+/* The decoder matrices' bytes on the device by the form they are held in: out[0] bf16 (or Q8_0 blocks with talker_q8_0 /
+ * predictor_q8_0), out[1] Q4_K, out[2] Q5_K, out[3] Q6_K (the tiled sizes of q3tts_k_kq_bytes). */
+int q3tts_get_weight_formats(const q3tts_engine* e, int64_t out[4]);
 /* Where the engine's vocoder weights came from: 0 = no vocoder (with_vocoder = 0), 1 = the seeded synthetic generator, 2 = the file
  * qwen3_tts_vocoder.gguf (q3tts_engine_config.weights_path). Audio of an engine that answers 1 is the output of random filters. */
 int q3tts_get_vocoder_source(const q3tts_engine* e, int32_t* source);
@@ -983,6 +999,16 @@ int q3tts_k_bgemm_last(int32_t* out6);
 int q3tts_k_bgemm_q8(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N, const float* ssp,
                      int32_t ntiles, int32_t d_norm, float eps, int32_t epilogue, const float* nw_next, float* y, uint16_t* yb, float* ssp_out,
                      uint64_t* keys, int32_t iters, float* mean_kernel_ms);
+/* The same launch with ggml K-quant weights kept quantised on the device (csrc/q3_bgemmk.hip; q3tts_engine_options.
+ * kquant_resident): raw = the super-blocks of the N rows [N][K/256] in file order, in n_seg row segments of one ggml type each
+ * (seg_type 12 = Q4_K, 13 = Q5_K, 14 = Q6_K; seg_rows multiples of 16 that add up to N; epilogue 2: one segment, the N/2 gate rows, then
+ * the N/2 up rows). Runs the device relayout and one launch through the engine's launcher. K % 512 == 0. Equals q3tts_k_bgemm on the
+ * bf16-rounded dequantised weights bit for bit. */
+int q3tts_k_bgemm_kq(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const uint8_t* raw, const int32_t* seg_rows, const int32_t* seg_type,
+                     int32_t n_seg, int32_t N, const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epilogue, const float* nw_next,
+                     float* y, uint16_t* yb, float* ssp_out, uint64_t* keys);
+/* Host only: the bytes an [N][K] matrix of ggml type 12 / 13 / 14 takes on the device in that form (592 / 720 / 840 per 16 columns x 64 k). */
+int q3tts_k_kq_bytes(int32_t type, int32_t N, int32_t K, int64_t* bytes);
 /* The same launch in ggml's Q8_0 x Q8_0 arithmetic (W8A8: csrc/q3_bgemm8.hip; q3tts_engine_config.talker_q8_0 = 2): the
  * ACTIVATIONS are Q8_0 blocks too — aq int8 [B][K], ad their block scales as f32 [B][K/32] (the producers store d = amax / 127 rounded to
  * f16's 11-bit significand but kept in f32; any f32 is accepted) — a block's product is its exact int32 sum times f32(d_w) * d_x. epilogue 0: y = s_r * RAW; 1: y += RAW, then the consumer's operand v = y * nw_next quantised per 32

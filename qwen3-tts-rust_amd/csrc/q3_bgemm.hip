@@ -16,345 +16,9 @@
 // Workgroup = 8 waves = the 8 K-slices of one (RT*16) x (NT*16) output tile; a wave keeps D steps of operands in flight
 // (register ring, refilled right after the MFMAs that consumed a slot); slice partials meet in LDS and are added in order.
 #include "q3_kernels.h"
+#include "q3_bgemm_body.h"
 #include <atomic>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float bg_wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m);
-    return v;
-}
-
-__device__ __forceinline__ size_t bg_yoff(const Q3BGemm& g, int row) {
-    return g.seg_rows ? (size_t)(row / g.seg_rows) * g.seg_stride + (size_t)(row % g.seg_rows) * g.ldy : (size_t)row * g.ldy;
-}
-__device__ __forceinline__ float bg_gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-
-__device__ __forceinline__ u32x4 bg_ldw(const u32x4* p, bool nt) { return nt ? __builtin_nontemporal_load(p) : *p; }
-
-// 8 int8 quants (lo = elements 0..3, hi = 4..7 of the lane's fragment) as a bf16 MFMA operand: f32(int8) has an exact bf16 in its upper half
-__device__ __forceinline__ bf16x8 bg_q8_frag(uint32_t lo, uint32_t hi) {
-    union { u32x4 u; bf16x8 v; } r;
-#define Q8F(w_, b_) __float_as_uint((float)(int)(signed char)((w_) >> (8 * (b_))))
-    r.u.x = (Q8F(lo, 0) >> 16) | (Q8F(lo, 1) & 0xffff0000u); r.u.y = (Q8F(lo, 2) >> 16) | (Q8F(lo, 3) & 0xffff0000u);
-    r.u.z = (Q8F(hi, 0) >> 16) | (Q8F(hi, 1) & 0xffff0000u); r.u.w = (Q8F(hi, 2) >> 16) | (Q8F(hi, 3) & 0xffff0000u);
-#undef Q8F
-    return r.v;
-}
-__device__ __forceinline__ float bg_f16(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (unsigned short)bits); }
-
-// Q8: the weights are ggml Q8_0 blocks in the tiled Q8 layout (q3_kernels.h): 1.06 bytes per weight instead of 2 through
-// the same ring; every 32-wide K step is one block: P = MFMA from a zero accumulator, acc = fmaf(f32(d), P, acc).
-#define BG_PH(RT_, NT_) ((8 * (RT_) * (NT_) > 64 && ((RT_) * (NT_)) % 2 == 0) ? 2 : 1)  // slice-reduction phases (k_bgemm, BgInst::lds)
-// EK: the epilogue as a compile-time constant. BG_EK_ANY = everything the struct can ask for, decided at run time (k_bgemm); otherwise
-// epilogue | BG_EK_SSP (row scales from ssp) | BG_EK_NW (RESID with nw_next), nothing else set (k_bgemm_epi: bg_ek below names the launches).
-// Same loads in the same order, same arithmetic: what a fixed EK removes is the run-time branches around the partials' reduction and the
-// epilogue operands — every one of them a join at which the compiler's load counters wait for more than the code behind it needs —
-// and the registers of operands the epilogue never reads (0.2 - 0.8 us per launch by the in-kernel stamps).
-#define BG_EK_ANY (-1)
-#define BG_EK_SSP 8
-#define BG_EK_NW 16
-template <int RT, int NT, int D, bool NTW, bool Q8, int EK>
-__device__ __forceinline__ void bg_body(const Q3BGemm& g) {
-    extern __shared__ float part[];  // [8 waves][RT*NT*4 regs][64 lanes]
-    __shared__ float srow[64];
-    Q3_STAMP(g, 0);
-    constexpr bool ANY = EK < 0;
-    const int epi = ANY ? g.epi : (EK & 7);
-    const bool h_ssp = ANY ? g.ssp != nullptr : (EK & BG_EK_SSP) != 0;
-    const bool h_nw = ANY ? g.nw_next != nullptr : (EK & BG_EK_NW) != 0;
-    const bool h_cs = ANY ? g.col_scale != nullptr : false, h_bias = ANY ? g.bias != nullptr : false, h_seg = ANY ? g.seg_rows != 0 : false;
-    const bool h_ybcopy = ANY ? (g.yb && !g.nw_next) : false;  // RESID without nw_next: yb = bf16(y)
-#define BG_YOFF(row_) (h_seg ? bg_yoff(g, row_) : (size_t)(row_) * g.ldy)
-    constexpr int TR = RT * NT * 4;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, kq = lane >> 4, r = lane & 15;
-    // workgroups are dealt round-robin to the 8 XCDs in linear-id order: the row chunks of one column group get ids 8 apart
-    // (same XCD, neighbours in time), so the group's weight tiles are fetched into that L2 once
-    int cg = blockIdx.x, rc = blockIdx.y;
-    if (gridDim.y > 1 && (gridDim.x & 7) == 0) {
-        const int id = blockIdx.x + gridDim.x * blockIdx.y, G = gridDim.y;
-        rc = (id >> 3) % G; cg = (id & 7) + (id / (8 * G)) * 8;
-    }
-    const int nb0 = cg * NT, row0 = rc * RT * 16, kblocks = g.K >> 5, per = g.K >> 8, kb0 = wave * per;
-    const int B = g.B;
-    const u32x4* ap[RT];  // A-tiled rows: one contiguous KiB per (row tile, k block) when the row tile is aligned, 16 B per lane always
-#pragma unroll
-    for (int i = 0; i < RT; ++i) {
-        const int R = g.a_row0 + min(row0 + 16 * i + r, B - 1);
-        ap[i] = (const u32x4*)g.a + ((size_t)(R >> 4) * kblocks + kb0) * 64 + kq * 16 + (R & 15);
-    }
-    const u32x4* wp[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) wp[j] = (const u32x4*)g.w + ((size_t)(nb0 + j) * kblocks + kb0) * 64 + lane;
-    // Load order = the order the results are needed in (vmcnt retires in order): first the norm GEMMs' tile partials (a few hundred
-    // bytes per wave from L2), whose reduction to the row scales then runs WHILE the operands are in flight (in-kernel timestamps,
-    // tools/chain_stamps.hip: done after the main loop it cost ~1 us of every norm GEMM); then the weights (HBM / Infinity Cache: the
-    // long latency) and the rows (L2), D steps of both; last what only the epilogue reads (residual, next norm weight, bias, scale).
-    // Every load below is unconditional (out-of-range steps re-read step per - 1): straight-line code, so the counted waits are exact.
-    // Measured again with the ring covering the whole K slice (profiles/r07/bgemm_prologue_stamps.txt): the weights in FRONT of the
-    // partials shorten the Predictor's launches by 0 - 0.35 us and lengthen the Talker's gate/up and down by 1.1 and 0.35 us (the
-    // reduction then waits behind D weight steps from HBM): the order stays. Of the 1.5 - 2.4 us up to "loads issued" 0.1 - 0.4 us were
-    // the run-time epilogue branches (gone with a fixed EK), at most 0.6 us the kernel-argument loads and the address arithmetic, the
-    // rest the CU's vector-memory path taking in the ring itself (14 - 24 KiB per wave, eight waves): not removable here.
-    // norm GEMMs: wave w owns the row scales of rows w, w + 8, ...: lane j adds its tiles j, j + 64, ... in ascending order, then the
-    // 64-lane butterfly
-    constexpr int NR = 2 * RT;
-    float sp0[NR], sp1[NR];
-    if (h_ssp) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            const float* sp = g.ssp + (size_t)min(row0 + wave + 8 * i, B - 1) * g.ld_ssp;
-            sp0[i] = lane < g.ntiles ? sp[lane] : 0.0f;
-            sp1[i] = lane + 64 < g.ntiles ? sp[lane + 64] : 0.0f;
-        }
-    }
-    constexpr int DQ = (D + 1) & ~1, DP = DQ / 2;  // Q8: an even number of steps in flight = DP block pairs (one 16-byte weight load covers two steps)
-    u32x4 aq[Q8 ? DQ : D][RT], bq[Q8 ? DP : D][NT];
-    uint32_t sc8[Q8 ? DP : 1][NT];                 // Q8: the two f16 block scales of a pair
-    const u32x4* wq[NT]; const uint32_t* sq[NT];
-    const int npair = per >> 1;
-    if constexpr (Q8) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            wq[j] = (const u32x4*)g.w + ((size_t)(nb0 + j) * (kblocks >> 1) + (kb0 >> 1)) * 64 + lane;
-            sq[j] = (const uint32_t*)(g.wscale + (size_t)((nb0 + j) * 16 + r) * kblocks + kb0);
-        }
-#pragma unroll
-        for (int p = 0; p < DP; ++p) {
-            const int pc = min(p, npair - 1);
-#pragma unroll
-            for (int j = 0; j < NT; ++j) { bq[p][j] = bg_ldw(wq[j] + (size_t)pc * 64, NTW); sc8[p][j] = sq[j][pc]; }
-        }
-#pragma unroll
-        for (int s = 0; s < DQ; ++s) {
-            const size_t so = (size_t)min(s, per - 1) * 64;
-#pragma unroll
-            for (int i = 0; i < RT; ++i) aq[s][i] = ap[i][so];
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < D; ++s) {
-            const size_t so = (size_t)min(s, per - 1) * 64;
-#pragma unroll
-            for (int j = 0; j < NT; ++j) bq[s][j] = bg_ldw(wp[j] + so, NTW);
-        }
-#pragma unroll
-        for (int s = 0; s < D; ++s) {
-            const size_t so = (size_t)min(s, per - 1) * 64;
-#pragma unroll
-            for (int i = 0; i < RT; ++i) aq[s][i] = ap[i][so];
-        }
-    }
-    // epilogue operands, fetched up front instead of at the very end (each was a dependent round trip behind the slice reduction)
-    constexpr int NOUT = (TR * 64 + 511) / 512;
-    float yres[NOUT], nwv[NOUT], bsv[NOUT], csv[NOUT];
-#pragma unroll
-    for (int it = 0; it < NOUT; ++it) { yres[it] = 0.0f; nwv[it] = 0.0f; bsv[it] = 0.0f; csv[it] = 1.0f; }
-    if (epi == Q3_EPI_RESID) {
-#pragma unroll
-        for (int it = 0; it < NOUT; ++it) {
-            const int o = threadIdx.x + it * 512;
-            const int l = o & 63, e = (o >> 6) & 3, t = o >> 8, i = t / NT, j = t - i * NT;
-            const int row = row0 + 16 * i + 4 * (l >> 4) + e, col = (nb0 + min(j, NT - 1)) * 16 + (l & 15);
-            const bool in = o < TR * 64;
-            yres[it] = (in && row < B) ? g.y[BG_YOFF(row) + col] : 0.0f;
-            if (h_nw) nwv[it] = in ? g.nw_next[col] : 0.0f;
-            if (h_cs) csv[it] = in ? g.col_scale[col] : 1.0f;
-        }
-    }
-    if (h_bias && epi != Q3_EPI_SWIGLU) {
-#pragma unroll
-        for (int it = 0; it < NOUT; ++it) {
-            const int o = threadIdx.x + it * 512;
-            const int l = o & 63, t = o >> 8, i = t / NT, j = t - i * NT;
-            const int col = (nb0 + min(j, NT - 1)) * 16 + (l & 15);
-            bsv[it] = o < TR * 64 ? g.bias[col % g.bias_n] : 0.0f;
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    Q3_STAMP(g, 1);
-    if (h_ssp) {  // the NR butterflies are independent chains: interleaved; they wait for the partials only (the first loads issued)
-        float av[NR];
-#pragma unroll
-        for (int i = 0; i < NR; ++i) {
-            float a = sp0[i];
-            if (lane + 64 < g.ntiles) a = a + sp1[i];
-            if (g.ntiles > 128) {
-                const float* sp = g.ssp + (size_t)min(row0 + wave + 8 * i, B - 1) * g.ld_ssp;
-                for (int t = lane + 128; t < g.ntiles; t += 64) a = a + sp[t];
-            }
-            av[i] = a;
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1)
-#pragma unroll
-            for (int i = 0; i < NR; ++i) av[i] = av[i] + __shfl_xor(av[i], m);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < NR; ++i) srow[wave + 8 * i] = 1.0f / sqrtf(av[i] / (float)g.d_norm + g.eps);
-        }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    f32x4 acc[RT][NT];
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if constexpr (Q8) {
-        const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int p0 = 0; p0 < npair; p0 += DP) {
-#pragma unroll
-            for (int dp = 0; dp < DP; ++dp) {
-                const int p = p0 + dp;
-                if (p < npair) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        float dsc[NT]; bf16x8 bf[NT];
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) {
-                            dsc[j] = bg_f16(h ? sc8[dp][j] >> 16 : sc8[dp][j] & 0xffffu);
-                            bf[j] = h ? bg_q8_frag(bq[dp][j].z, bq[dp][j].w) : bg_q8_frag(bq[dp][j].x, bq[dp][j].y);
-                        }
-#pragma unroll
-                        for (int i = 0; i < RT; ++i) {
-                            union { u32x4 u; bf16x8 v; } a; a.u = aq[2 * dp + h][i];
-#pragma unroll
-                            for (int j = 0; j < NT; ++j) {
-                                const f32x4 P = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, bf[j], zero4, 0, 0, 0);
-                                acc[i][j][0] = fmaf(dsc[j], P[0], acc[i][j][0]); acc[i][j][1] = fmaf(dsc[j], P[1], acc[i][j][1]);
-                                acc[i][j][2] = fmaf(dsc[j], P[2], acc[i][j][2]); acc[i][j][3] = fmaf(dsc[j], P[3], acc[i][j][3]);
-                            }
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (p + DP < npair) {
-#pragma unroll
-                        for (int j = 0; j < NT; ++j) { bq[dp][j] = bg_ldw(wq[j] + (size_t)(p + DP) * 64, NTW); sc8[dp][j] = sq[j][p + DP]; }
-#pragma unroll
-                        for (int h = 0; h < 2; ++h)
-#pragma unroll
-                            for (int i = 0; i < RT; ++i) aq[2 * dp + h][i] = ap[i][(size_t)(2 * (p + DP) + h) * 64];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-    } else
-    for (int s0 = 0; s0 < per; s0 += D) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const int s = s0 + d;
-            if (s < per) {
-#pragma unroll
-                for (int i = 0; i < RT; ++i) {
-                    union { u32x4 u; bf16x8 v; } a; a.u = aq[d][i];
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        union { u32x4 u; bf16x8 v; } b; b.u = bq[d][j];
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, acc[i][j], 0, 0, 0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#ifdef Q3_STAMPS
-                if (s == 0) { asm volatile("" :: "v"(acc[0][0][0])); Q3_STAMP(g, 2); }
-#endif
-                if (s + D < per) {
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) bq[d][j] = bg_ldw(wp[j] + (size_t)(s + D) * 64, NTW);
-#pragma unroll
-                    for (int i = 0; i < RT; ++i) aq[d][i] = ap[i][(size_t)(s + D) * 64];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-#ifdef Q3_STAMPS
-    asm volatile("" :: "v"(acc[0][0][0])); Q3_STAMP(g, 3);
-#endif
-    // The slice buffer holds TRP = TR / PH registers per wave: instances whose 8 x TR x 256 bytes exceed 64 KiB ((4,3): 96) reduce in PH = 2
-    // phases of half their tiles, so that no decode workgroup needs more than 64 KiB of LDS — what is left beside one resident vocoder
-    // workgroup. Same sums in the same slice order per element; a thread's elements keep their places (o = tid + 512 it).
-    constexpr int PH = BG_PH(RT, NT), TP = RT * NT / PH, TRP = TR / PH, NOUTP = NOUT / PH;
-    static_assert(PH == 1 || ((RT * NT) % 2 == 0 && (TRP * 64) % 512 == 0), "two phases need an even tile count and whole items per phase");
-#pragma unroll
-    for (int ph = 0; ph < PH; ++ph) {
-        if (ph) __syncthreads();  // every wave is done reading the previous phase's partials
-#pragma unroll
-        for (int i = 0; i < RT; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                if ((i * NT + j) / TP != ph) continue;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) part[((size_t)wave * TRP + ((i * NT + j) - ph * TP) * 4 + e) * 64 + lane] = acc[i][j][e];
-            }
-        __syncthreads();
-        if (ph == 0) Q3_STAMP(g, 4);
-        // slice partials combined in slice order; element (tile t, reg e, lane l) -> row 16 i + 4 (l >> 4) + e, col 16 j + (l & 15)
-        if (epi == Q3_EPI_SWIGLU) {
-            // one thread per (gate, up) pair: pair p of the 32 in a (tile, register) block of 64 lanes sits in lanes l = 16 (p / 8) + p % 8 (gate,
-            // column c = p % 8 < 8 of the tile) and l + 8 (up, the same row 8 columns further); every thread has work (a loop over all
-            // TR * 64 elements left the up lanes idle: half of the epilogue's issue slots)
-            constexpr int NP = (TRP * 32 + 511) / 512;
-#pragma unroll
-            for (int it = 0; it < NP; ++it) {
-                const int p = threadIdx.x + it * 512;
-                if (p >= TRP * 32) break;  // (TRP * 32 is a multiple of 128: whole waves leave together)
-                const int q = p & 31, l = ((q >> 3) << 4) + (q & 7), o = ((p >> 5) << 6) + l;
-                const int e = (o >> 6) & 3, t = ph * TP + (o >> 8), i = t / NT, j = t - i * NT;
-                const int rl = 16 * i + 4 * (l >> 4) + e, row = row0 + rl, c = l & 15;
-                const float sc = h_ssp ? srow[rl] : 1.0f;
-                float gt = part[o], up = part[o + 8];
-#pragma unroll
-                for (int wv = 1; wv < 8; ++wv) { gt = gt + part[(size_t)wv * (TRP * 64) + o]; up = up + part[(size_t)wv * (TRP * 64) + o + 8]; }
-                if (row < B) g.yb[q3_atile_off(row, (nb0 + j) * 8 + c, g.N >> 6)] = q3_bf16(q3_swiglu(sc * gt, sc * up));
-            }
-            continue;
-        }
-#pragma unroll
-        for (int itp = 0; itp < NOUTP; ++itp) {
-            const int it = ph * NOUTP + itp, o = threadIdx.x + itp * 512;  // o: place in this phase's buffer; tid + 512 it in the whole tile set
-            if (o >= TRP * 64) break;  // whole waves leave together (TRP * 64 is a multiple of 256)
-            const int l = o & 63, e = (o >> 6) & 3, t = ph * TP + (o >> 8), i = t / NT, j = t - i * NT;
-            const int rl = 16 * i + 4 * (l >> 4) + e, row = row0 + rl, c = l & 15;
-            const int col = (nb0 + j) * 16 + c;
-            const bool live = row < B;
-            const float sc = h_ssp ? srow[rl] : 1.0f;
-            float v = part[o];
-#pragma unroll
-            for (int wv = 1; wv < 8; ++wv) v = v + part[(size_t)wv * (TRP * 64) + o];
-            if (h_bias) v = v + bsv[it];
-            if (epi == Q3_EPI_STORE) {
-                if (live) g.y[BG_YOFF(row) + col] = h_ssp ? sc * v : v;
-            } else if (epi == Q3_EPI_GELU) {
-                if (live) g.yb[q3_atile_off(row, col, g.N >> 5)] = q3_bf16(bg_gelu_erf(v));
-            } else if (epi == Q3_EPI_RESID) {
-                const float xv = h_cs ? yres[it] + csv[it] * v : yres[it] + v;
-                if (live) g.y[BG_YOFF(row) + col] = xv;
-                if (h_ybcopy && live) g.yb[q3_atile_off(row, col, g.N >> 5)] = q3_bf16(xv);
-                if (h_nw) {  // the consumer's norm inputs: bf16(x * nw) and the tile's sum of squares (16-lane butterfly)
-                    if (live) g.yb[q3_atile_off(row, col, g.N >> 5)] = q3_bf16(xv * nwv[it]);
-                    float sq = xv * xv;
-                    sq = sq + __shfl_xor(sq, 1); sq = sq + __shfl_xor(sq, 2); sq = sq + __shfl_xor(sq, 4); sq = sq + __shfl_xor(sq, 8);
-                    if (live && c == 0) g.ssp_out[(size_t)row * g.ld_ssp_out + (nb0 + j)] = sq;
-                }
-            } else {  // Q3_EPI_ARGMAX: the largest key of the tile's 16 columns goes to keys[row][column tile]; the consumer takes the maximum
-                      // over the row's N/16 entries (an atomicMax per (row, tile) on one word per row cost ~8 us of the launch)
-                unsigned long long key = q3_argmax_key(h_ssp ? sc * v : v, (uint32_t)col);
-#pragma unroll
-                for (int m = 1; m <= 8; m <<= 1) { const unsigned long long ok = __shfl_xor(key, m); key = ok > key ? ok : key; }
-                if (live && c == 0) g.keys[(size_t)row * g.key_stride + (nb0 + j)] = key;
-            }
-        }
-    }
-#ifdef Q3_STAMPS
-    Q3_STAMP(g, 5);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    Q3_STAMP(g, 6);
-#endif
-#undef BG_YOFF
-}
 // k_bgemm: any Q3BGemm (its five-argument name is what q3tts_k_bgemm_pick reports: the tile instance). k_bgemm_epi: the same instance with
 // the epilogue fixed, for the launches bg_ek names — the decoder's STORE / RESID + nw_next / SWIGLU / ARGMAX on bf16 weights.
 template <int RT, int NT, int D, bool NTW, bool Q8>
@@ -526,7 +190,7 @@ __global__ __launch_bounds__(256) void k_bgemm_big(Q3BGemm g) {
         }
 }
 static bool bg_big_ok(const Q3BGemm& g) {
-    return g.B >= 256 && !g.wscale && (g.epi == Q3_EPI_STORE || g.epi == Q3_EPI_RESID || g.epi == Q3_EPI_SWIGLU) && g.N % 128 == 0 && g.a_row0 % 16 == 0 &&
+    return g.B >= 256 && !g.wscale && !g.kq && (g.epi == Q3_EPI_STORE || g.epi == Q3_EPI_RESID || g.epi == Q3_EPI_SWIGLU) && g.N % 128 == 0 && g.a_row0 % 16 == 0 &&
            !g.bias && !g.col_scale && !g.seg_rows && !(g.epi == Q3_EPI_RESID && g.yb && !g.nw_next);
 }
 static void bg_launch_big(const Q3BGemm& g, hipStream_t s) {
@@ -602,6 +266,7 @@ void q3_bgemm_prepare() {  // once per DEVICE (function attributes are per devic
 #define P(RT_, NT_) BgInst<RT_, NT_>::prepare();
         BG_EACH(P)
 #undef P
+        q3_bgemmk_prepare();
     });
 }
 
@@ -640,7 +305,9 @@ static void bg_pick(const Q3BGemm& g, int* rt, int* nt, int* big) {
             const long chunks = (g.B + 16 * RT - 1) / (16 * RT);
             if (g.B <= 64 && RT > 1 && 16 * (RT - 1) * chunks >= g.B) continue;  // a smaller RT covers the rows with the same chunk count
             const long wgs = (long)(tiles / NT) * chunks, rounds = (wgs + 255) / 256;
-            const long cost = rounds * ((g.wscale ? 32L * RT + 17L * NT : 32L * (RT + NT)) * g.K + 24000L);  // + a fixed cost per round (ramp, reduction); Q8_0 weights: 17 bytes per k per column tile
+            // + a fixed cost per round (ramp, reduction); Q8_0 weights: 17 bytes per k per column tile; K-quants: the tile rows' own bytes (kq_bpp per 64 k)
+            const long wk = g.kq ? (long)g.kq_bpp * NT * (g.K >> 6) : (g.wscale ? 17L : 32L) * NT * g.K;
+            const long cost = rounds * (32L * RT * g.K + wk + 24000L);
             // equal cost: more workgroups, then the wider column tile; at 65 .. 512 rows the wider column tile first (the sweep: (2,2) over (3,1))
             const bool tie = mid ? (NT > bestNT || (NT == bestNT && wgs > bestWgs)) : (wgs > bestWgs || (wgs == bestWgs && NT > bestNT));
             if (bestCost < 0 || cost < bestCost || (cost == bestCost && tie)) { bestCost = cost; bestRT = RT; bestNT = NT; bestWgs = wgs; }
@@ -654,6 +321,7 @@ void q3_bgemm_pick(const Q3BGemm& g, int* rt, int* nt, int* d, int* ntw, int* bi
     bg_pick(g, rt, nt, big);
     *d = 0; *ntw = 0;
     if (*big) return;
+    if (g.kq) { *d = q3_bgemmk_depth(*rt, *nt); *ntw = (g.w_once && (g.B + 16 * *rt - 1) / (16 * *rt) == 1) ? 1 : 0; return; }
 #define X(RT_, NT_) if (*rt == RT_ && *nt == NT_) *d = BgInst<RT_, NT_>::D;
     BG_EACH(X)
 #undef X
@@ -663,6 +331,7 @@ void q3_bgemm_pick(const Q3BGemm& g, int* rt, int* nt, int* d, int* ntw, int* bi
 static int bg_check(const Q3BGemm& g) {
     if (g.B < 1 || g.N % 16 || g.K % 256 || g.K < 256 || !g.a || !g.w || g.a_row0 < 0) return -1;
     if (g.wscale && g.K % 512) return -1;  // Q8_0: two blocks per 16-byte weight load, an even number of blocks per K slice
+    if (g.kq && (g.K % 512 || g.wscale || g.kq_bpp < 1)) return -1;  // K-quants: whole tile pairs per K slice
     if (g.yb && (((g.epi == Q3_EPI_RESID || g.epi == Q3_EPI_GELU) && g.N % 32) || (g.epi == Q3_EPI_SWIGLU && g.N % 64))) return -1;  // the A-tiled output has N (N/2) columns in 32-blocks
     if ((g.epi == Q3_EPI_SWIGLU || g.epi == Q3_EPI_GELU) && (!g.yb)) return -1;
     if (g.bias && g.bias_n < 1) return -1;
@@ -676,6 +345,12 @@ int q3_launch_bgemm(const Q3BGemm& g, hipStream_t s) {
     int bestRT, bestNT, big;
     bg_pick(g, &bestRT, &bestNT, &big);
     if (big) { bg_note_launch(8, 8, 0, false, 1, BG_EK_ANY); bg_launch_big(g, s); return 0; }
+    if (g.kq) {
+        int d = 0, ntw = 0;
+        if (q3_bgemmk_launch(g, bestRT, bestNT, s, &d, &ntw)) return -1;
+        bg_note_launch(bestRT, bestNT, d, ntw != 0, 0, BG_EK_ANY);
+        return 0;
+    }
     const dim3 grid(g.N / 16 / bestNT, (g.B + 16 * bestRT - 1) / (16 * bestRT));
 #define L(RT_, NT_) if (bestRT == RT_ && bestNT == NT_) { BgInst<RT_, NT_>::launch(g, grid, s); return 0; }
     BG_EACH(L)

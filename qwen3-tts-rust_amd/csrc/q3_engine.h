@@ -38,9 +38,16 @@ struct Q3Tfm {
     // these the f16 block scales [N][K/32]; empty / null = bf16 weights
     std::vector<uint16_t*> sqkv, so, sgu, sd; uint16_t* shead = nullptr; bool q8 = false;
     bool a8 = false;  // cfg.talker_q8_0 = 2 / cfg.predictor_q8_0 = 2: the GEMMs' ACTIVATIONS are Q8_0 blocks as well (W8A8, q3_bgemm8.hip): every operand buffer then holds int8 quants + f32 block scales (11-bit significand: q3_q8_sig11)
+    // K-quant resident matrices (q3tts_engine_options.kquant_resident; q3_bgemmk.hip): where tab is set, the matrix pointer above
+    // holds the tiled K layout and tab its tile-row table (Q3BGemm::kq / kq_bpp); a matrix that did not qualify has tab == nullptr and is bf16.
+    // The tables (8 bytes per 16 rows) are small hipMallocs owned by the engine and not counted in dev_bytes.
+    struct Kq { const uint2* tab = nullptr; int bpp = 0; };
+    std::vector<Kq> kqkv, ko, kgu, kdn; Kq khead;
     Q3KvCache cache;
     float *cs = nullptr, *sn = nullptr;  // RoPE tables [cache.n_ctx][hd/2]
-    size_t weight_bytes = 0;              // bf16 matrix bytes of all layers + head
+    size_t weight_bytes = 0;              // matrix bytes of all layers + head in the form they have on the device
+    size_t head_bytes = 0, qkv0_bytes = 0;  // of these: the head matrix, block 0's QKV
+    size_t fmt_bytes[4] = {0, 0, 0, 0};   // q3tts_get_weight_formats: matrix bytes held as bf16 (or Q8_0), Q4_K, Q5_K, Q6_K
 };
 
 struct Q3Scratch {
@@ -84,6 +91,7 @@ struct q3tts_engine {
     std::string err;
     hipStream_t stream = nullptr, vstream = nullptr;
     std::vector<void*> allocs;          // every q3_dalloc of this engine, freed by q3tts_engine_destroy
+    int kquant_resident = 0;            // q3tts_engine_options.kquant_resident
     size_t dev_bytes = 0;               // bytes handed out by q3_dev_alloc_zeroed so far (q3tts_k_device_bytes)
     Q3Tfm T, P;
     // assets
@@ -237,7 +245,10 @@ inline Q3KvPrefix q3_kv_prefix_of(const Q3Tfm& t) {
 }
 // the transformer's weights, KV cache and RoPE tables. g: the opened GGUF `file` (null: seeded synthetic weights);
 // q8mode: cfg.talker_q8_0 / cfg.predictor_q8_0
-int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode);
+int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode, int kq = 0);
+// the bytes a K-quant resident engine saves on this transformer's matrices against bf16: sum of 2 N K - tiled K bytes over the matrices
+// q3_tfm_init (kq = 1) will keep quantised, from the file's tensor headers alone
+size_t q3_tfm_kq_saving(const Q3TfmShape& sh, const Q3Gguf& g);
 // text / codec tables, codec_dev, proj_w / proj_b, tts_pad and the pre-projected codec tables, from the files of wdir (empty: synthetic)
 int q3_assets_init(q3tts_engine* e, const std::string& wdir);
 // e->qkv0 (after both of the above), or nothing where the switches or the model say so; a refused launch is an error

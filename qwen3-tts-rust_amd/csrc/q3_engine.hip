@@ -207,10 +207,35 @@ static int alloc_rows(q3tts_engine* e, Q3Rows& r, size_t rows, int d, bool scale
     return Q3TTS_OK;
 }
 
-extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine** out) {
+static Q3TfmShape talker_shape(const q3tts_engine_config& c) {
+    const q3tts_model_config& m = c.model;
+    return {.grp = Q3G_TALKER, .L = m.t_n_layer, .d = m.t_d_model, .Hq = m.t_n_head, .Hkv = m.t_n_kv_head, .hd = m.t_head_dim, .F = m.t_d_ffn,
+            .head_n = m.t_vocab, .theta = m.t_rope_theta, .sections = m.t_mrope_sections, .n_ctx = c.n_ctx, .n_slots = c.max_batch, .kv8 = c.kv_q8_0};
+}
+static Q3TfmShape predictor_shape(const q3tts_engine_config& c) {
+    const q3tts_model_config& m = c.model;
+    return {.grp = Q3G_PRED, .L = m.p_n_layer, .d = m.p_d_model, .Hq = m.p_n_head, .Hkv = m.p_n_kv_head, .hd = m.p_head_dim, .F = m.p_d_ffn,
+            .head_n = (m.n_codebooks - 1) * m.codebook_size, .theta = m.p_rope_theta, .sections = nullptr, .n_ctx = 64, .n_slots = c.max_batch, .kv8 = 0};
+}
+extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine** out) { return q3tts_engine_create_opts(cfg, nullptr, out); }
+extern "C" int q3tts_get_weight_formats(const q3tts_engine* e, int64_t out[4]) {
+    if (!e || !out) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    for (int i = 0; i < 4; ++i) out[i] = (int64_t)(e->T.fmt_bytes[i] + e->P.fmt_bytes[i]);
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3tts_engine_options* opts, q3tts_engine** out) {
     if (!cfg || !out) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
     std::string why;
     if (validate(*cfg, why) != Q3TTS_OK) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, why);
+    int kquant = 0;
+    if (opts) {
+        if (opts->struct_size != sizeof(q3tts_engine_options)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.struct_size = " + std::to_string(opts->struct_size) + ", this library knows " + std::to_string(sizeof(q3tts_engine_options)));
+        if (opts->kquant_resident != 0 && opts->kquant_resident != 1) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.kquant_resident must be 0 or 1");
+        kquant = opts->kquant_resident;
+        if (kquant && (cfg->talker_q8_0 != 0 || cfg->predictor_q8_0 != 0))
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "kquant_resident = 1 keeps K-quant tensors as stored; it cannot be combined with talker_q8_0 = " + std::to_string(cfg->talker_q8_0) +
+                              " / predictor_q8_0 = " + std::to_string(cfg->predictor_q8_0) + " (Q8_0 weights): set one or the other");
+    }
     if (cfg->predictor_q8_0 == 1)
         return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, "predictor_q8_0 = 1 (Q8_0 weights x bf16 activations) is not implemented for the Predictor: use 0 (bf16) or 2 (Q8_0 x Q8_0)");
     // what the Q8_0-cache kernels (q3_attend_kv8.hip) cannot run is refused here, not at the first launch. (Today validate() above admits
@@ -247,11 +272,19 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     auto fail = [&](int rc) { std::string m = e->err; q3tts_engine_destroy(e); g_err = m; return rc; };
 #define TRYC(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return fail(rc__); } while (0)
 #define HIPC(call) do { hipError_t er__ = (call); if (er__ != hipSuccess) { q3_set_err(e, Q3TTS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(er__)); return fail(Q3TTS_ERR_DEVICE); } } while (0)
+    e->kquant_resident = kquant;
     HIPC(hipSetDevice(cfg->device));
+    // weights_path: the reference's quant directory (q3_weights.hip); NULL: seeded synthetic weights. The headers are read
+    // before the memory check: a K-quant resident engine counts each matrix at the bytes of the form it will take.
+    const std::string wdir = cfg->weights_path ? cfg->weights_path : "";
+    Q3Gguf gt, gp;
+    std::string er;
+    if (!wdir.empty() && (gt.open(wdir + "/qwen3_tts_talker.gguf", er) || gp.open(wdir + "/qwen3_tts_predictor.gguf", er))) { q3_set_err(e, Q3TTS_ERR_INVALID, er); return fail(Q3TTS_ERR_INVALID); }
+    const unsigned long long kq_saved = (kquant && !wdir.empty()) ? q3_tfm_kq_saving(talker_shape(*cfg), gt) + q3_tfm_kq_saving(predictor_shape(*cfg), gp) : 0;
     {   // before the first allocation: what the config sizes against the device's free memory (not a failure half-way through q3_dalloc)
         size_t free_b = 0, total_b = 0;
         HIPC(hipMemGetInfo(&free_b, &total_b));
-        const unsigned long long need = engine_footprint(*cfg);
+        const unsigned long long need = engine_footprint(*cfg) - kq_saved;
         if (need > (unsigned long long)free_b) {
             q3_set_err(e, Q3TTS_ERR_OOM, "engine needs at least " + std::to_string(need) + " bytes of device memory for max_batch = " + std::to_string(cfg->max_batch) +
                        ", n_ctx = " + std::to_string(cfg->n_ctx) + (cfg->kv_q8_0 ? " (Q8_0 cache)" : "") + "; the device has " + std::to_string((unsigned long long)free_b) +
@@ -279,17 +312,8 @@ extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine*
     const int B = cfg->max_batch;
     e->B = B;
     hipStream_t s = e->stream;
-    // weights_path: the reference's quant directory (q3_weights.hip); NULL: seeded synthetic weights
-    const std::string wdir = cfg->weights_path ? cfg->weights_path : "";
-    Q3Gguf gt, gp;
-    std::string er;
-    if (!wdir.empty() && (gt.open(wdir + "/qwen3_tts_talker.gguf", er) || gp.open(wdir + "/qwen3_tts_predictor.gguf", er))) { q3_set_err(e, Q3TTS_ERR_INVALID, er); return fail(Q3TTS_ERR_INVALID); }
-    TRYC(q3_tfm_init(e, e->T, {.grp = Q3G_TALKER, .L = m.t_n_layer, .d = m.t_d_model, .Hq = m.t_n_head, .Hkv = m.t_n_kv_head, .hd = m.t_head_dim, .F = m.t_d_ffn,
-                               .head_n = m.t_vocab, .theta = m.t_rope_theta, .sections = m.t_mrope_sections, .n_ctx = cfg->n_ctx, .n_slots = B, .kv8 = cfg->kv_q8_0},
-                     wdir.empty() ? nullptr : &gt, "qwen3_tts_talker.gguf", cfg->talker_q8_0));
-    TRYC(q3_tfm_init(e, e->P, {.grp = Q3G_PRED, .L = m.p_n_layer, .d = m.p_d_model, .Hq = m.p_n_head, .Hkv = m.p_n_kv_head, .hd = m.p_head_dim, .F = m.p_d_ffn,
-                               .head_n = (m.n_codebooks - 1) * m.codebook_size, .theta = m.p_rope_theta, .sections = nullptr, .n_ctx = 64, .n_slots = B, .kv8 = 0},
-                     wdir.empty() ? nullptr : &gp, "qwen3_tts_predictor.gguf", cfg->predictor_q8_0));
+    TRYC(q3_tfm_init(e, e->T, talker_shape(*cfg), wdir.empty() ? nullptr : &gt, "qwen3_tts_talker.gguf", cfg->talker_q8_0, kquant));
+    TRYC(q3_tfm_init(e, e->P, predictor_shape(*cfg), wdir.empty() ? nullptr : &gp, "qwen3_tts_predictor.gguf", cfg->predictor_q8_0, kquant));
     TRYC(q3_assets_init(e, wdir));
     TRYC(q3_pred_table_init(e));
     // decode state

@@ -362,15 +362,15 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
     {
         const q3tts_model_config& m = e->cfg.model;
         const long long wt = (long long)e->T.weight_bytes;  // includes lm_head
-        const double bpw_p = e->P.q8 ? 1.0625 : 2.0;  // the Predictor's bytes per weight (predictor_q8_0 = 2: Q8_0 blocks)
-        const long long wp_layers = (long long)e->P.weight_bytes - (long long)(bpw_p * (double)((size_t)e->P.head_n * m.p_d_model));
-        const long long head1 = (long long)(bpw_p * (double)((size_t)m.codebook_size * m.p_d_model)), pj = 2ll * m.p_d_model * m.d_embed;
+        // (the matrices' real bytes: a K-quant resident matrix counts at its quantised size)
+        const long long wp_layers = (long long)e->P.weight_bytes - (long long)e->P.head_bytes;
+        const long long head1 = (long long)(e->P.head_bytes / (size_t)(m.n_codebooks - 1)), pj = 2ll * m.p_d_model * m.d_embed;
         const long long kv_per_tok = 2ll * m.t_n_layer * 2 * m.t_n_kv_head * m.t_head_dim;
         long long fixed = wt + (m.n_codebooks - 1) * (wp_layers + head1) + pj;  // one projection GEMM per frame (hidden rows); codes come pre-projected
         e->tm.mean_live_slots = steps ? (float)((double)live_slot_steps / (double)steps) : 0.0f;
         long long gathered = 0;  // with the layer-0 QKV table, passes 1 .. n_codebooks - 2 do not stream wqkv[0]: every live row reads its table row instead
         if (q3_pred_table_on(e)) {
-            fixed -= (long long)(m.n_codebooks - 2) * (long long)(bpw_p * (double)((size_t)e->P.nqkv * m.p_d_model));
+            fixed -= (long long)(m.n_codebooks - 2) * (long long)e->P.qkv0_bytes;
             gathered = (long long)((double)(m.n_codebooks - 2) * (double)e->tm.mean_live_slots * (double)e->P.nqkv * 4.0);
         }
         e->tm.algo_bytes_per_step = fixed + gathered + (steps ? kv_per_tok * (ctx_tokens / steps) : 0);

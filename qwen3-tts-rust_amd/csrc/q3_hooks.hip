@@ -683,6 +683,71 @@ extern "C" int q3tts_k_bgemm_q8(int32_t device, const uint16_t* xb, int32_t B, i
     return bgemm_hook("bgemm_q8", device, xb, B, K, blocks.data(), true, N, ssp, ntiles, d_norm, eps, epi, nw_next, y, yb, ssp_out, keys, iters, mean_ms);
 }
 
+// K-quant weights kept quantised (q3_bgemmk.hip). ggml type -> Q3_KQ_*, -1 for any other type.
+static int kq_type(int ggml_type) { return ggml_type == 12 ? Q3_KQ_Q4 : ggml_type == 13 ? Q3_KQ_Q5 : ggml_type == 14 ? Q3_KQ_Q6 : -1; }
+extern "C" int q3tts_k_kq_bytes(int32_t type, int32_t N, int32_t K, int64_t* bytes) {
+    if (kq_type(type) < 0 || N < 16 || N % 16 || K < 512 || K % 512 || !bytes) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "kq_bytes: type 12 / 13 / 14, N % 16 == 0, K % 512 == 0");
+    *bytes = (int64_t)(N / 16) * (int64_t)q3_kq_row_bytes(kq_type(type), K);
+    return Q3TTS_OK;
+}
+// raw: the super-blocks of the N rows in file order, row segments of one ggml type each (seg_rows[i] rows of seg_type[i], multiples of 16;
+// epilogue 2: one segment, the N/2 gate rows, then the N/2 up rows). The device relayout, then one launch through q3_launch_bgemm.
+extern "C" int q3tts_k_bgemm_kq(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const uint8_t* raw, const int32_t* seg_rows, const int32_t* seg_type,
+                                int32_t n_seg, int32_t N, const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next,
+                                float* y, uint16_t* yb, float* ssp_out, uint64_t* keys) {
+    if (!xb || !raw || !seg_rows || !seg_type || n_seg < 1 || B <= 0 || K % 512 || K < 512 || N % 16 || N < 16 || epi < 0 || epi > 3)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_kq hook: K % 512 == 0, N % 16 == 0, epilogue 0..3");
+    if (epi == Q3_EPI_SWIGLU && (N % 64 || !yb || n_seg != 1)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_kq hook: swiglu needs N % 64 == 0, yb and one segment");
+    if (epi == Q3_EPI_RESID && nw_next && (N % 32 || !yb || !ssp_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_kq hook: norm outputs");
+    if ((epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) && !y) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_kq hook: y missing");
+    if (epi == Q3_EPI_ARGMAX && !keys) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_kq hook: keys missing");
+    size_t raw_bytes = 0, tiled_bytes = 0; int rows = 0;
+    for (int i = 0; i < n_seg; ++i) {
+        if (kq_type(seg_type[i]) < 0 || seg_rows[i] < 16 || seg_rows[i] % 16) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_kq hook: segments of type 12 / 13 / 14, rows % 16 == 0");
+        rows += seg_rows[i];
+        raw_bytes += (size_t)seg_rows[i] * (K / 256) * q3_kq_block_bytes(kq_type(seg_type[i]));
+        tiled_bytes += (size_t)(seg_rows[i] / 16) * q3_kq_row_bytes(kq_type(seg_type[i]), K);
+    }
+    if (rows != N) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_kq hook: the segments do not add up to N rows");
+    HK(hipSetDevice(device));
+    const int nt = N / 16;
+    DevBuf dx, dw, dwt, dtab, ds, dn, dy, dyb, dso, dk;
+    { const std::vector<uint16_t> xt = atile_host(xb, B, K); TRY(dx.put(xt.data(), xt.size() * 2)); }
+    TRY(dw.put(raw, raw_bytes)); TRY(dwt.alloc(tiled_bytes));
+    std::vector<uint2> tab;
+    {
+        size_t src = 0, dst = 0;
+        for (int i = 0; i < n_seg; ++i) {
+            const int ty = kq_type(seg_type[i]), ntr = seg_rows[i] / 16;
+            Q3FillKq f{}; f.dst = (uint8_t*)dwt.p + dst; f.K = K; f.type = ty; f.ntr = ntr; f.src_a = (const uint8_t*)dw.p + src;
+            if (epi == Q3_EPI_SWIGLU) { f.mode = 1; f.src_b = f.src_a + (size_t)(N / 2) * (K / 256) * q3_kq_block_bytes(ty); }
+            q3_launch_fill_tiled_kq(f, nullptr);
+            for (int t = 0; t < ntr; ++t) tab.push_back(make_uint2((uint32_t)((dst + (size_t)t * q3_kq_row_bytes(ty, K)) / 16), (uint32_t)ty));
+            src += (size_t)seg_rows[i] * (K / 256) * q3_kq_block_bytes(ty); dst += (size_t)ntr * q3_kq_row_bytes(ty, K);
+        }
+    }
+    TRY(dtab.put(tab.data(), tab.size() * sizeof(uint2)));
+    TRY(ds.put(ntiles > 0 ? ssp : nullptr, (size_t)B * std::max(ntiles, 1) * 4)); TRY(dn.put(nw_next, (size_t)N * 4));
+    TRY(dy.put(epi == Q3_EPI_RESID ? y : nullptr, (size_t)B * N * 4)); TRY(dyb.alloc(pad16(B) * N * 2)); TRY(dso.alloc((size_t)B * nt * 4)); TRY(dk.alloc((size_t)B * nt * 8));
+    Q3BGemm g{}; g.a = dx; g.B = B; g.w = dwt; g.K = K; g.N = N; g.kq = dtab; g.kq_bpp = (int)(tiled_bytes / ((size_t)nt * (K / 64)));
+    if (ssp) g.ssp = ds;
+    g.ld_ssp = ntiles; g.ntiles = ntiles; g.d_norm = d_norm; g.eps = eps; g.epi = epi;
+    g.y = dy; g.ldy = N; g.yb = dyb;
+    if (nw_next) g.nw_next = dn;
+    g.ssp_out = dso; g.ld_ssp_out = nt; g.keys = dk; g.key_stride = nt;
+    if (q3_launch_bgemm(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_kq hook: shape");
+    HK(hipDeviceSynchronize());
+    if (epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) TRY(dy.get(y, (size_t)B * N * 4));
+    if (epi == Q3_EPI_SWIGLU) TRY(untile_host(dyb, B, N / 2, yb));
+    if (epi == Q3_EPI_RESID && nw_next) { TRY(untile_host(dyb, B, N, yb)); TRY(dso.get(ssp_out, (size_t)B * nt * 4)); }
+    if (epi == Q3_EPI_ARGMAX) {
+        std::vector<uint64_t> parts((size_t)B * nt);
+        TRY(dk.get(parts.data(), parts.size() * 8));
+        for (int b = 0; b < B; ++b) { uint64_t m = 0; for (int t = 0; t < nt; ++t) m = std::max(m, parts[(size_t)b * nt + t]); keys[b] = m; }
+    }
+    return Q3TTS_OK;
+}
+
 // W8A8 (q3_bgemm8.hip): activations and weights as ggml Q8_0 blocks in natural order in / out; the hook tiles them for the device
 extern "C" int q3tts_k_bgemm_q8a8(int32_t device, const int8_t* aq, const float* ad, int32_t B, int32_t K, const int8_t* q, const uint16_t* d_f16, int32_t N,
                                   const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, int8_t* yq, float* yd,

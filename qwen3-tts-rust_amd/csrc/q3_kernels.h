@@ -110,8 +110,34 @@ struct Q3BGemm {
     // W8A8 (q3_launch_bgemm8; the Talker with talker_q8_0 = 2): `a` then holds the rows' int8 quants (q3_q8_off) and ascale their block scales
     // (q3_q8_scale_idx, a_rt16 row tiles); RESID / SWIGLU write the consumer's operand the same way: yb = int8 quants, yscale / y_rt16.
     const float* ascale; int a_rt16; float* yscale; int y_rt16;
+    // K-quant weights (q3_bgemmk.hip): w then is the base of a matrix whose 16-column tile rows are ggml Q4_K / Q5_K / Q6_K
+    // super-blocks in the tiled K layout below, and kq its table [N/16] of (x: byte offset of the tile row / 16, y: Q3_KQ_*). The weights
+    // are decoded in registers to the bf16 values the host loader produces and enter the bf16 MFMA chain: same RAW bits. K % 512 == 0.
+    // kq_bpp: mean bytes per (tile row, 64 k) of the matrix, for the launcher's cost model.
+    const uint2* kq; int kq_bpp;
     Q3_STAMP_FIELD
 };
+// The tiled K layout of one 16-column tile row over K columns (P = K/64 tile pairs, S = K/256 super-blocks); lane l = (kq, n) of a pair owns
+// the 16 weights its two bf16 fragments would hold: k = 4kq..4kq+3, 16+4kq..16+4kq+3 of 32-block 2p, then of 2p+1 (element e = 0..7 each).
+//   [0, 512 P)            nibbles  uint2 [P][64 lanes]: x = block 2p, y = block 2p+1, element e in bits 4e..4e+3 (the quant's low 4 bits)
+//   [512 P, +64 HB P)     high bits [P][64 lanes], HB bytes per lane: Q4_K none; Q5_K u16, bit 8h+e of block 2p+h; Q6_K u32, bits 16h+2e, +1
+//   then 64 P             scales   u32 [P][16 columns]: Q4_K / Q5_K bytes (sc, m) of block 2p, (sc, m) of 2p+1; Q6_K the four int8
+//                                  16-element scales of blocks 2p, 2p+1 in element order
+//   then 64 S / 32 S      Q4_K / Q5_K u32 [S][16]: f16 d | f16 dmin << 16; Q6_K u16 [S][16]: f16 d
+// = 592 / 720 / 840 bytes per pair (4.63 / 5.63 / 6.56 bits per weight); every plane starts at a multiple of 64 bytes (P % 8 == 0).
+enum { Q3_KQ_Q4 = 0, Q3_KQ_Q5 = 1, Q3_KQ_Q6 = 2 };
+Q3_HD int q3_kq_hb(int type) { return type == Q3_KQ_Q4 ? 0 : (type == Q3_KQ_Q5 ? 2 : 4); }                  // high-bit bytes per lane and pair
+Q3_HD int q3_kq_pair_bytes(int type) { return type == Q3_KQ_Q4 ? 592 : (type == Q3_KQ_Q5 ? 720 : 840); }
+Q3_HD int q3_kq_block_bytes(int type) { return type == Q3_KQ_Q4 ? 144 : (type == Q3_KQ_Q5 ? 176 : 210); }  // ggml's super-block in the file
+Q3_HD size_t q3_kq_row_bytes(int type, int K) { return (size_t)(K >> 6) * q3_kq_pair_bytes(type); }       // one tile row
+// Relayout: ntr tile rows of one type, contiguous at dst, from raw super-block rows [.][K/256] on the device. mode 0: tile row t, column c
+// <- row 16 t + c of src_a; mode 1 (gate / up): c < 8 <- row 8 t + c of src_a, else row 8 t + c - 8 of src_b.
+struct Q3FillKq { uint8_t* dst; int K, type, ntr, mode; const uint8_t* src_a; const uint8_t* src_b; };
+void q3_launch_fill_tiled_kq(const Q3FillKq& f, hipStream_t s);
+// the K-quant side of q3_launch_bgemm (q3_bgemm.hip picks the tile instance and calls these)
+int q3_bgemmk_launch(const Q3BGemm& g, int rt, int nt, hipStream_t s, int* d, int* ntw);
+int q3_bgemmk_depth(int rt, int nt);
+void q3_bgemmk_prepare();
 int q3_launch_bgemm(const Q3BGemm& g, hipStream_t s);
 int q3_launch_bgemm8(const Q3BGemm& g, hipStream_t s);   // the same launch in ggml's Q8_0 x Q8_0 arithmetic (STORE / RESID / SWIGLU / ARGMAX)
 void q3_bgemm8_prepare();  // its kernel attributes, once per device; call outside stream capture

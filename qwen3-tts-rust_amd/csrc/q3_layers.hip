@@ -8,8 +8,9 @@
 // depends on the operand format is set here, never at a call site.
 // Common arguments: block l of t over the first `rows` rows of r, scratch sc; once: Q3BGemm::w_once (the Talker's 2.8 GB stream once per
 // frame step; the Predictor's weights are re-read 15 times: Infinity Cache).
-static Q3BGemm gemm_w(const uint4* w, const uint16_t* wscale, int K, int N, int rows, int once) {
+static Q3BGemm gemm_w(const uint4* w, const uint16_t* wscale, const Q3Tfm::Kq& kq, int K, int N, int rows, int once) {
     Q3BGemm g{}; g.w_once = once; g.B = rows; g.w = w; g.wscale = wscale; g.K = K; g.N = N;
+    g.kq = kq.tab; g.kq_bpp = kq.bpp;  // a matrix kept as K-quants: w is its tiled K layout, kq the tile-row table
     return g;
 }
 // A = the rows' norm inputs r.xb, each row scaled from its tile partials r.ssp (the fused RMSNorm)
@@ -28,26 +29,26 @@ static void y_rows(Q3BGemm& g, const Q3Tfm& t, const Q3Rows& r, const float* nw_
     if (t.a8) { g.yscale = r.ascale; g.y_rt16 = r.rt16; }
 }
 Q3BGemm q3_gemm_qkv(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, float eps, int once) {
-    Q3BGemm g = gemm_w(t.wqkv[l], t.q8 ? t.sqkv[l] : nullptr, t.d, t.nqkv, rows, once);
+    Q3BGemm g = gemm_w(t.wqkv[l], t.q8 ? t.sqkv[l] : nullptr, t.kqkv[l], t.d, t.nqkv, rows, once);
     a_rows(g, t, r, eps);
     g.epi = Q3_EPI_STORE; g.y = sc.qkv; g.ldy = t.nqkv;
     return g;
 }
 static Q3BGemm gemm_o(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, int once) {
-    Q3BGemm g = gemm_w(t.wo[l], t.q8 ? t.so[l] : nullptr, t.nq, t.d, rows, once);
+    Q3BGemm g = gemm_w(t.wo[l], t.q8 ? t.so[l] : nullptr, t.ko[l], t.nq, t.d, rows, once);
     a_scratch(g, t, sc, sc.att, sc.asc_att);
     y_rows(g, t, r, t.ffn_norm[l]);
     return g;
 }
 static Q3BGemm gemm_gate_up(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, float eps, int once) {
-    Q3BGemm g = gemm_w(t.wgu[l], t.q8 ? t.sgu[l] : nullptr, t.d, 2 * t.F, rows, once);
+    Q3BGemm g = gemm_w(t.wgu[l], t.q8 ? t.sgu[l] : nullptr, t.kgu[l], t.d, 2 * t.F, rows, once);
     a_rows(g, t, r, eps);
     g.epi = Q3_EPI_SWIGLU; g.yb = sc.h;
     if (t.a8) { g.yscale = sc.asc_h; g.y_rt16 = sc.rt16; }
     return g;
 }
 static Q3BGemm gemm_down(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, int once) {
-    Q3BGemm g = gemm_w(t.wd[l], t.q8 ? t.sd[l] : nullptr, t.F, t.d, rows, once);
+    Q3BGemm g = gemm_w(t.wd[l], t.q8 ? t.sd[l] : nullptr, t.kdn[l], t.F, t.d, rows, once);
     a_scratch(g, t, sc, sc.h, sc.asc_h);
     y_rows(g, t, r, l + 1 < t.L ? t.attn_norm[l + 1] : t.out_norm);  // the next block's norm, or the head's
     return g;
@@ -57,7 +58,10 @@ static Q3BGemm gemm_down(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch
 Q3BGemm q3_gemm_head(const Q3Tfm& t, int q, int N, const Q3Rows& r, int row0, int rows, float eps, int once, float* y) {
     // uint4 per head (bf16 tiles of 32 k, Q8 tile pairs of 64 k) and its f16 block scales
     const size_t tile_stride = (size_t)(N / 16) * (t.d / (t.q8 ? 64 : 32)) * 64, scale_stride = (size_t)N * (t.d / 32);
-    Q3BGemm g = gemm_w(t.head + tile_stride * q, t.q8 ? t.shead + scale_stride * q : nullptr, t.d, N, rows, once);
+    // (a head kept as K-quants: the same matrix base, head q = the tile rows from q N / 16 on of its table)
+    Q3Tfm::Kq kh = t.khead;
+    if (kh.tab) kh.tab += (size_t)q * (N / 16);
+    Q3BGemm g = gemm_w(kh.tab ? t.head : t.head + tile_stride * q, t.q8 ? t.shead + scale_stride * q : nullptr, kh, t.d, N, rows, once);
     a_rows(g, t, r, eps);
     g.a_row0 = row0; g.ssp += (size_t)row0 * (t.d / 16);
     if (y) { g.epi = Q3_EPI_STORE; g.y = y; g.ldy = N; }

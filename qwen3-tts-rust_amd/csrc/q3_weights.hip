@@ -71,6 +71,18 @@ struct GgSrc {
         raw[which] = true;
         return Q3TTS_OK;
     }
+    // K-quant resident mode: the tensor's super-blocks as stored into staging buffer `which` (the caller has checked type and shape)
+    int raw_k(const Q3GgufTensor& t, int which) {
+        if (dev8_cap[which] < t.nbytes) {
+            if (dev8[which]) hipFree(dev8[which]);
+            dev8[which] = nullptr; dev8_cap[which] = 0;
+            void* p = nullptr;
+            if (hipMalloc(&p, t.nbytes) != hipSuccess) return q3_set_err(e, Q3TTS_ERR_OOM, "hipMalloc (K-quant staging)");
+            dev8[which] = (uint8_t*)p; dev8_cap[which] = t.nbytes;
+        }
+        Q3_HIP(e, hipMemcpy(dev8[which], t.data, t.nbytes, hipMemcpyHostToDevice));
+        return Q3TTS_OK;
+    }
     // [N][K] matrix -> bf16 row-major staging buffer `which` on the device
     int mat(const std::string& name, size_t N, size_t K, int which) {
         int rc; const Q3GgufTensor* t = need(name, K, N, &rc);
@@ -91,7 +103,55 @@ struct GgSrc {
     void source(int i, const uint16_t** src, const uint8_t** src8) const { *src = raw[i] ? nullptr : dev[i]; *src8 = raw[i] ? dev8[i] : nullptr; }
 };
 
-int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode) {
+// ---- K-quant resident matrices (q3tts_engine_options.kquant_resident; q3_bgemmk.hip) -----------------------------------
+// A matrix of the engine is one or more file tensors stacked by rows (q | k | v), or two interleaved 8 + 8 inside every tile (gate / up).
+// It stays quantised when every part is Q4_K / Q5_K / Q6_K with whole tile rows and K % 512 == 0 — interleaved parts of one type, since a
+// tile row has one type. Anything else is bf16 as before, silently. which: 0 QKV, 1 O, 2 gate / up, 3 down, 4 the head(s).
+struct KqPart { std::string name; int rows; };
+struct KqSpec { std::vector<KqPart> parts; int K; bool interleave; };
+static KqSpec kq_spec(const Q3TfmShape& sh, int l, int which) {
+    const std::string b = "blk." + std::to_string(l) + ".";
+    const int nq = sh.Hq * sh.hd, nkv = sh.Hkv * sh.hd;
+    switch (which) {
+        case 0: return {{{b + "attn_q.weight", nq}, {b + "attn_k.weight", nkv}, {b + "attn_v.weight", nkv}}, sh.d, false};
+        case 1: return {{{b + "attn_output.weight", sh.d}}, nq, false};
+        case 2: return {{{b + "ffn_gate.weight", sh.F}, {b + "ffn_up.weight", sh.F}}, sh.d, true};
+        case 3: return {{{b + "ffn_down.weight", sh.d}}, sh.F, false};
+        default: return {{{"output.weight", sh.head_n}}, sh.d, false};
+    }
+}
+static int kq_type_of(uint32_t ggml) { return ggml == Q3_GGML_Q4_K ? Q3_KQ_Q4 : ggml == Q3_GGML_Q5_K ? Q3_KQ_Q5 : ggml == Q3_GGML_Q6_K ? Q3_KQ_Q6 : -1; }
+// the parts' types and the matrix's tiled bytes when it qualifies
+static bool kq_plan(const Q3Gguf& g, const KqSpec& sp, std::vector<int>* types, size_t* bytes) {
+    types->clear(); *bytes = 0;
+    if (sp.K < 512 || sp.K % 512) return false;
+    for (const KqPart& p : sp.parts) {
+        const Q3GgufTensor* t = g.find(p.name);
+        const int ty = t ? kq_type_of(t->type) : -1;
+        if (ty < 0 || !t->data || t->dims.size() != 2 || t->dims[0] != (uint64_t)sp.K || t->dims[1] != (uint64_t)p.rows) return false;
+        if (p.rows % (sp.interleave ? 8 : 16)) return false;
+        if (sp.interleave && !types->empty() && ty != (*types)[0]) return false;
+        types->push_back(ty);
+        *bytes += (size_t)p.rows * (sp.K >> 6) * q3_kq_pair_bytes(ty) / 16;
+    }
+    return true;
+}
+size_t q3_tfm_kq_saving(const Q3TfmShape& sh, const Q3Gguf& g) {
+    size_t saved = 0;
+    std::vector<int> types; size_t bytes;
+    auto one = [&](int l, int which) {
+        const KqSpec sp = kq_spec(sh, l, which);
+        if (!kq_plan(g, sp, &types, &bytes)) return;
+        size_t n = 0;
+        for (const KqPart& p : sp.parts) n += (size_t)p.rows;
+        saved += 2 * n * sp.K - bytes;
+    };
+    for (int l = 0; l < sh.L; ++l) for (int w = 0; w < 4; ++w) one(l, w);
+    one(0, 4);
+    return saved;
+}
+
+int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode, int kq) {
     const bool q8 = q8mode != 0;
     const int grp = sh.grp, L = sh.L, d = sh.d, hd = sh.hd, F = sh.F;
     t.L = L; t.d = d; t.Hq = sh.Hq; t.Hkv = sh.Hkv; t.hd = hd; t.F = F; t.nq = sh.Hq * hd; t.nkv = sh.Hkv * hd; t.nqkv = t.nq + 2 * t.nkv;
@@ -123,30 +183,85 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
         return Q3TTS_OK;
     };
     const double bpw = q8 ? 1.0625 : 2.0;  // bytes per weight streamed by a GEMM
+    t.kqkv.assign(L, {}); t.ko.assign(L, {}); t.kgu.assign(L, {}); t.kdn.assign(L, {});
+    // Matrix `which` of block l: kept quantised when it qualifies (*w = the tiled K layout, *k its table; returns its bytes through *res),
+    // else *res = 0 and nothing is done. The relayout runs on the device from the file's super-blocks (staging slots 0 / 1).
+    auto resident = [&](int l, int which, uint4** w, Q3Tfm::Kq* k, size_t* res) -> int {
+        *res = 0;
+        if (!kq || !gg || q8) return Q3TTS_OK;
+        const KqSpec sp = kq_spec(sh, l, which);
+        std::vector<int> types; size_t bytes;
+        if (!kq_plan(*g, sp, &types, &bytes)) return Q3TTS_OK;
+        uint8_t* dst = nullptr;
+        TRY(q3_dalloc(e, &dst, bytes));
+        std::vector<uint2> tab;
+        size_t off = 0;
+        if (sp.interleave) {
+            TRY(gg->raw_k(*g->find(sp.parts[0].name), 0)); TRY(gg->raw_k(*g->find(sp.parts[1].name), 1));
+            Q3FillKq f{}; f.dst = dst; f.K = sp.K; f.type = types[0]; f.ntr = (sp.parts[0].rows + sp.parts[1].rows) / 16; f.mode = 1;
+            f.src_a = gg->dev8[0]; f.src_b = gg->dev8[1];
+            q3_launch_fill_tiled_kq(f, s);
+            for (int r = 0; r < f.ntr; ++r) tab.push_back(make_uint2((uint32_t)((size_t)r * q3_kq_row_bytes(types[0], sp.K) / 16), (uint32_t)types[0]));
+            Q3_HIP(e, hipStreamSynchronize(s));
+            t.fmt_bytes[1 + types[0]] += bytes;
+        } else
+            for (size_t i = 0; i < sp.parts.size(); ++i) {
+                TRY(gg->raw_k(*g->find(sp.parts[i].name), 0));
+                Q3FillKq f{}; f.dst = dst + off; f.K = sp.K; f.type = types[i]; f.ntr = sp.parts[i].rows / 16; f.src_a = gg->dev8[0];
+                q3_launch_fill_tiled_kq(f, s);
+                const size_t rb = q3_kq_row_bytes(types[i], sp.K);
+                for (int r = 0; r < f.ntr; ++r) tab.push_back(make_uint2((uint32_t)((off + (size_t)r * rb) / 16), (uint32_t)types[i]));
+                Q3_HIP(e, hipStreamSynchronize(s));  // (the staging slot is reused by the next part)
+                off += (size_t)f.ntr * rb; t.fmt_bytes[1 + types[i]] += (size_t)f.ntr * rb;
+            }
+        void* dtab = nullptr;
+        if (hipMalloc(&dtab, tab.size() * sizeof(uint2)) != hipSuccess) return q3_set_err(e, Q3TTS_ERR_OOM, "hipMalloc (K-quant tile-row table)");
+        e->allocs.push_back(dtab);
+        Q3_HIP(e, hipMemcpy(dtab, tab.data(), tab.size() * sizeof(uint2), hipMemcpyHostToDevice));
+        *w = (uint4*)dst; k->tab = (const uint2*)dtab; k->bpp = (int)(bytes / (tab.size() * (size_t)(sp.K >> 6)));
+        *res = bytes;
+        return Q3TTS_OK;
+    };
     for (int l = 0; l < L; ++l) {
         TRY(q3_dalloc(e, &t.attn_norm[l], (size_t)d)); TRY(q3_dalloc(e, &t.ffn_norm[l], (size_t)d));
         TRY(q3_dalloc(e, &t.qn[l], (size_t)hd)); TRY(q3_dalloc(e, &t.kn[l], (size_t)hd));
         uint16_t *sc_qkv = nullptr, *sc_o = nullptr, *sc_gu = nullptr, *sc_d = nullptr;
-        TRY(alloc_mat(&t.wqkv[l], &sc_qkv, t.nqkv, d)); TRY(alloc_mat(&t.wo[l], &sc_o, d, t.nq));
-        TRY(alloc_mat(&t.wgu[l], &sc_gu, (size_t)2 * F, d)); TRY(alloc_mat(&t.wd[l], &sc_d, d, F));
+        size_t r_qkv, r_o, r_gu, r_d;  // bytes of the matrices kept as K-quants (0: bf16 / Q8_0 as before)
+        if (gg) Q3_HIP(e, hipStreamSynchronize(s));
+        TRY(resident(l, 0, &t.wqkv[l], &t.kqkv[l], &r_qkv)); TRY(resident(l, 1, &t.wo[l], &t.ko[l], &r_o));
+        TRY(resident(l, 2, &t.wgu[l], &t.kgu[l], &r_gu)); TRY(resident(l, 3, &t.wd[l], &t.kdn[l], &r_d));
+        if (!r_qkv) TRY(alloc_mat(&t.wqkv[l], &sc_qkv, t.nqkv, d));
+        if (!r_o) TRY(alloc_mat(&t.wo[l], &sc_o, d, t.nq));
+        if (!r_gu) TRY(alloc_mat(&t.wgu[l], &sc_gu, (size_t)2 * F, d));
+        if (!r_d) TRY(alloc_mat(&t.wd[l], &sc_d, d, F));
         if (q8) { t.sqkv[l] = sc_qkv; t.so[l] = sc_o; t.sgu[l] = sc_gu; t.sd[l] = sc_d; }
-        t.weight_bytes += (size_t)(bpw * (double)((size_t)t.nqkv * d + (size_t)d * t.nq + 3ull * F * d));
+        {
+            const size_t b_qkv = r_qkv ? r_qkv : (size_t)(bpw * (double)((size_t)t.nqkv * d)), b_o = r_o ? r_o : (size_t)(bpw * (double)((size_t)d * t.nq));
+            const size_t b_gu = r_gu ? r_gu : (size_t)(bpw * (double)(2ull * F * d)), b_d = r_d ? r_d : (size_t)(bpw * (double)((size_t)F * d));
+            t.weight_bytes += b_qkv + b_o + b_gu + b_d;
+            t.fmt_bytes[0] += (r_qkv ? 0 : b_qkv) + (r_o ? 0 : b_o) + (r_gu ? 0 : b_gu) + (r_d ? 0 : b_d);
+            if (l == 0) t.qkv0_bytes = b_qkv;
+        }
         if (gg) {  // blk.N.* of a llama.cpp qwen3 GGUF (weights [out][in], NeoX RoPE: no q/k permutation)
             const std::string b = "blk." + std::to_string(l) + ".";
             Q3_HIP(e, hipStreamSynchronize(s));
             TRY(gg->vec(b + "attn_norm.weight", d, t.attn_norm[l])); TRY(gg->vec(b + "ffn_norm.weight", d, t.ffn_norm[l]));
             TRY(gg->vec(b + "attn_q_norm.weight", hd, t.qn[l])); TRY(gg->vec(b + "attn_k_norm.weight", hd, t.kn[l]));
+            if (!r_qkv) {
             TRY(put(b + "attn_q.weight", t.wqkv[l], sc_qkv, t.nqkv, d, 0, t.nq));
             TRY(put(b + "attn_k.weight", t.wqkv[l], sc_qkv, t.nqkv, d, t.nq, t.nkv));
             TRY(put(b + "attn_v.weight", t.wqkv[l], sc_qkv, t.nqkv, d, t.nq + t.nkv, t.nkv));
-            TRY(put(b + "attn_output.weight", t.wo[l], sc_o, d, t.nq, 0, d));
+            }
+            if (!r_o) TRY(put(b + "attn_output.weight", t.wo[l], sc_o, d, t.nq, 0, d));
+            if (!r_gu) {
             TRY(stage(b + "ffn_gate.weight", F, d, 0)); TRY(stage(b + "ffn_up.weight", F, d, 1));
             Q3Fill f{}; f.dst = t.wgu[l]; f.N = 2 * F; f.K = d; f.mode = 1; f.row0 = 0; f.rows = d;
             gg->source(0, &f.src_a, &f.src8_a); gg->source(1, &f.src_b, &f.src8_b);
             if (gg->raw[0] != gg->raw[1]) return gg->fail("ffn_gate / ffn_up of block " + std::to_string(l) + " differ in type (one Q8_0, one not)");
             fill(f, sc_gu);
             Q3_HIP(e, hipStreamSynchronize(s));
-            TRY(put(b + "ffn_down.weight", t.wd[l], sc_d, d, F, 0, d));
+            }
+            if (!r_d) TRY(put(b + "ffn_down.weight", t.wd[l], sc_d, d, F, 0, d));
             continue;
         }
         q3_launch_fill_f32(t.attn_norm[l], d, seed, Q3_TID(grp, l, Q3W_ATTN_NORM), 1.0f, ns, 0, s);
@@ -164,12 +279,17 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
         f.dst = t.wd[l]; f.N = d; f.K = F; f.mode = 0; f.row0 = 0; f.rows = d; f.tid_a = Q3_TID(grp, l, Q3W_DOWN); fill(f, sc_d);
     }
     TRY(q3_dalloc(e, &t.out_norm, (size_t)d));
-    TRY(alloc_mat(&t.head, &t.shead, (size_t)t.head_n, d));
-    t.weight_bytes += (size_t)(bpw * (double)((size_t)t.head_n * d));
+    size_t r_head;
+    if (gg) Q3_HIP(e, hipStreamSynchronize(s));
+    TRY(resident(0, 4, &t.head, &t.khead, &r_head));
+    if (!r_head) TRY(alloc_mat(&t.head, &t.shead, (size_t)t.head_n, d));
+    t.head_bytes = r_head ? r_head : (size_t)(bpw * (double)((size_t)t.head_n * d));
+    t.weight_bytes += t.head_bytes;
+    if (!r_head) t.fmt_bytes[0] += t.head_bytes;
     if (gg) {
         Q3_HIP(e, hipStreamSynchronize(s));
         TRY(gg->vec("output_norm.weight", d, t.out_norm));
-        TRY(put("output.weight", t.head, t.shead, t.head_n, d, 0, t.head_n));
+        if (!r_head) TRY(put("output.weight", t.head, t.shead, t.head_n, d, 0, t.head_n));
     } else {
         q3_launch_fill_f32(t.out_norm, d, seed, Q3_TID(grp, Q3_L_MODEL, Q3WM_OUT_NORM), 1.0f, ns, 0, s);
         Q3Fill f{}; f.seed = seed; f.scale = ms; f.dst = t.head; f.N = t.head_n; f.K = d; f.mode = 0; f.row0 = 0; f.rows = t.head_n;

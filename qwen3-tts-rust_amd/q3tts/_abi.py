@@ -165,6 +165,11 @@ class CloneConfig(C.Structure):
 
 
 # every symbol include/q3tts.h declares (tests check the export list against the header text)
+class EngineOptions(C.Structure):
+    """q3tts_engine_options: what q3tts_engine_create_opts takes beyond the config (zero = q3tts_engine_create)."""
+    _fields_ = [("struct_size", C.c_uint32), ("kquant_resident", C.c_int32)]
+
+
 SYMBOLS = [
     "q3tts_default_config", "q3tts_engine_create", "q3tts_engine_destroy", "q3tts_last_error", "q3tts_set_sampler",
     "q3tts_set_max_steps", "q3tts_build_prompt", "q3tts_free", "q3tts_generate", "q3tts_generate_batch",
@@ -199,6 +204,7 @@ SYMBOLS = [
     "q3tts_k_doc_stream_rate", "q3tts_k_doc_ring_plan", "q3tts_k_doc_out_pos",
     "q3tts_vocoder_config_from_file", "q3tts_get_vocoder_source", "q3tts_k_voc_file_tensor",
     "q3tts_clone_config_from_dir", "q3tts_clone_load", "q3tts_get_clone_source", "q3tts_k_clone_file_tensor", "q3tts_k_clone_load_check", "q3tts_clone_files_find",
+    "q3tts_k_bgemm_kq", "q3tts_k_kq_bytes", "q3tts_engine_create_opts", "q3tts_get_weight_formats",
 ]
 
 # long documents (include/q3tts.h, "long documents"): break kinds, the join's block length, and the structs field for field
@@ -277,6 +283,10 @@ def load_library(path=None):
     lib.q3tts_default_config.argtypes = [C.POINTER(EngineConfig)]
     lib.q3tts_default_config.restype = None
     lib.q3tts_engine_create.argtypes = [C.POINTER(EngineConfig), C.POINTER(vp)]
+    lib.q3tts_engine_create_opts.argtypes = [C.POINTER(EngineConfig), C.POINTER(EngineOptions), C.POINTER(vp)]
+    lib.q3tts_engine_create_opts.restype = C.c_int
+    lib.q3tts_get_weight_formats.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.q3tts_get_weight_formats.restype = C.c_int
     lib.q3tts_engine_destroy.argtypes = [vp]
     lib.q3tts_engine_destroy.restype = None
     lib.q3tts_last_error.argtypes = [vp]
@@ -451,6 +461,11 @@ def load_library(path=None):
     lib.q3tts_node_shard.restype = C.c_int32
     lib.q3tts_k_bgemm_q8.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, f32p]
+    lib.q3tts_k_bgemm_kq.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, i32p, i32p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.q3tts_k_bgemm_kq.restype = C.c_int
+    lib.q3tts_k_kq_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
+    lib.q3tts_k_kq_bytes.restype = C.c_int
     lib.q3tts_k_bgemm_q8a8_argmax.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
     lib.q3tts_k_bgemm_q8a8_argmax.restype = C.c_int
     lib.q3tts_k_bgemm_q8a8.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float,

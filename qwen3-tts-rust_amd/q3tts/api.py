@@ -124,8 +124,8 @@ class TtsEngine:
     """src/tts/engine.rs:53-72 — the engine owns weights, contexts and speakers; one utterance at a time per call
     (`&mut self`), or a list through `generate_batch_with_voice` (continuous batching, an extension)."""
 
-    def __init__(self, cfg, tokenizer=None):
-        self._native = native.NativeEngine(cfg)
+    def __init__(self, cfg, tokenizer=None, kquant_resident=False):
+        self._native = native.NativeEngine(cfg, kquant_resident=True) if kquant_resident else native.NativeEngine(cfg)
         self.cfg = cfg
         self.tokenizer = tokenizer
         self.speakers = {}
@@ -134,7 +134,7 @@ class TtsEngine:
 
     @classmethod
     def new(cls, model_dir: Optional[str] = None, quant: str = "none", config=None, max_batch: Optional[int] = None,
-            kv_cache: Optional[str] = None):
+            kv_cache: Optional[str] = None, kquant_resident: bool = False):
         """TtsEngine::new(model_dir, quant) (src/tts/engine.rs:84-169). With no config the model's shape comes from the GGUF files of the
         quant directory (q3tts_config_from_model_dir), whatever member of the family it holds; a config given by the caller is used as it
         is (its shapes must match the files) and is not modified. The vocoder's trained weights and shape come the same way from
@@ -146,7 +146,10 @@ class TtsEngine:
         place of the config's (include/q3tts.h states the memory per slot; 256 slots of the 1.7B shape need n_ctx <= 1024 or so).
         kv_cache: None — a given config's own kv_q8_0 is kept (0, bf16, everywhere else); "bf16" — the Talker's K/V cache in bf16, whatever
         the config says; "q8_0" — ggml Q8_0 blocks
-        (q3tts_engine_config.kv_q8_0 = 1: 0.53 of the memory; the results are not the bf16 cache's). Anything else: ValueError."""
+        (q3tts_engine_config.kv_q8_0 = 1: 0.53 of the memory; the results are not the bf16 cache's). Anything else: ValueError.
+        kquant_resident: Q4_K / Q5_K / Q6_K tensors of the quant directory (quant = "q5_k_m") stay quantised on the device and are decoded
+        inside the GEMM (q3tts_engine_options.kquant_resident): the same results bit for bit in about a third of the weight bytes;
+        weight_formats says what each form holds. Opt-in: the default converts them to bf16 at load."""
         if kv_cache not in (None, "bf16", "q8_0"):
             raise ValueError(f"kv_cache must be None, 'bf16' or 'q8_0', not {kv_cache!r}")
         wdir = None
@@ -175,7 +178,7 @@ class TtsEngine:
             missing = native.CLONE_FILES[0 if clone_files[0] is None else 1]
             raise _abi.Q3Error(f"{missing} not found in {wdir} or in {model_dir}: the clone encoders need both files "
                                f"(found {clone_files[0] or clone_files[1]})")
-        eng = cls(cfg, tok)
+        eng = cls(cfg, tok, kquant_resident=kquant_resident)
         if clone_files[0] is not None:
             try:
                 eng._native.clone_load(wdir)
@@ -196,6 +199,11 @@ class TtsEngine:
 
     def close(self):
         self._native.close()
+
+    @property
+    def weight_formats(self):
+        """The decoder matrices' device bytes by the form they are held in: {"bf16", "q4_k", "q5_k", "q6_k"}."""
+        return self._native.weight_formats
 
     @property
     def vocoder_is_synthetic(self) -> bool:

@@ -80,14 +80,27 @@ class GenResult:
 class NativeEngine:
     """q3tts_engine handle. One engine per GPU; not re-entrant (same contract as `&mut self`)."""
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, kquant_resident=False):
+        """kquant_resident: q3tts_engine_options.kquant_resident — Q4_K / Q5_K / Q6_K tensors of cfg.weights_path stay quantised on the
+        device and are decoded inside the GEMM (same bits as the default; fewer bytes)."""
         self.lib = _abi.load_library()
         self.cfg = cfg
         self.h = C.c_void_p()
         self._prefixes = weakref.WeakSet()  # destroyed before the engine
-        rc = self.lib.q3tts_engine_create(C.byref(cfg), C.byref(self.h))
+        if kquant_resident:
+            opts = _abi.EngineOptions(C.sizeof(_abi.EngineOptions), 1)
+            rc = self.lib.q3tts_engine_create_opts(C.byref(cfg), C.byref(opts), C.byref(self.h))
+        else:
+            rc = self.lib.q3tts_engine_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
             raise _abi.Q3Error(f"q3tts_engine_create failed ({rc}): {self.lib.q3tts_last_error(None).decode()}")
+
+    @property
+    def weight_formats(self):
+        """q3tts_get_weight_formats: the decoder matrices' device bytes held as {"bf16", "q4_k", "q5_k", "q6_k"}."""
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.q3tts_get_weight_formats(self.h, out), "q3tts_get_weight_formats")
+        return dict(zip(("bf16", "q4_k", "q5_k", "q6_k"), (int(v) for v in out)))
 
     def close(self):
         if getattr(self, "h", None):
@@ -960,6 +973,39 @@ def k_bgemm_q8(xb, q, d16, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_bgemm_q8 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return dict(y=y, yb=yb, ssp_out=sso, keys=keys, ms=ms.value)
+
+
+def k_bgemm_kq(xb, raw, segs, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=0):
+    """The same launch with K-quant weights kept quantised on the device (q3tts_k_bgemm_kq): raw = the rows' super-blocks in file order
+    (uint8), segs = [(rows, ggml type), ...] (one segment for epi 2: gate rows, then up rows)."""
+    lib = _abi.load_library()
+    xb = np.ascontiguousarray(xb, dtype=np.uint16); raw = np.ascontiguousarray(raw, dtype=np.uint8)
+    B, K = xb.shape
+    rows = np.array([s[0] for s in segs], dtype=np.int32); types = np.array([s[1] for s in segs], dtype=np.int32)
+    N = int(rows.sum())
+    y = np.zeros((B, N), dtype=np.float32) if y0 is None else np.ascontiguousarray(y0, dtype=np.float32).copy()
+    yb = np.zeros((B, N // 2 if epi == 2 else N), dtype=np.uint16)
+    sso = np.zeros((B, N // 16), dtype=np.float32)
+    keys = np.zeros(B, dtype=np.uint64)
+    sp = None if ssp is None else np.ascontiguousarray(ssp, dtype=np.float32)
+    nw = None if nw_next is None else np.ascontiguousarray(nw_next, dtype=np.float32)
+    i32p = C.POINTER(C.c_int32)
+    rc = lib.q3tts_k_bgemm_kq(device, xb.ctypes.data, B, K, raw.ctypes.data, rows.ctypes.data_as(i32p), types.ctypes.data_as(i32p), len(segs), N,
+                              None if sp is None else sp.ctypes.data, 0 if sp is None else sp.shape[1], d_norm, eps, epi,
+                              None if nw is None else nw.ctypes.data, y.ctypes.data, yb.ctypes.data, sso.ctypes.data, keys.ctypes.data)
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_bgemm_kq failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return dict(y=y, yb=yb, ssp_out=sso, keys=keys)
+
+
+def k_kq_bytes(ggml_type, N, K):
+    """q3tts_k_kq_bytes: the device bytes of an [N][K] matrix kept as Q4_K (12) / Q5_K (13) / Q6_K (14)."""
+    lib = _abi.load_library()
+    out = C.c_int64(0)
+    rc = lib.q3tts_k_kq_bytes(ggml_type, N, K, C.byref(out))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_kq_bytes failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return out.value
 
 
 def k_bgemm_q8a8_argmax(aq, ad, q, d16, ssp, d_norm, eps, device=0):

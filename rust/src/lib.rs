@@ -23,6 +23,8 @@ pub struct q3tts_vocoder_config {
     pub lookahead_frames: i32, pub sample_rate: i32,
 }
 #[repr(C)]
+pub struct q3tts_engine_options { pub struct_size: u32, pub kquant_resident: i32 }
+#[repr(C)]
 pub struct q3tts_engine_config {
     pub model: q3tts_model_config, pub vocoder: q3tts_vocoder_config,
     pub device: i32, pub max_batch: i32, pub n_ctx: i32, pub max_steps_cap: i32, pub with_vocoder: i32,
@@ -108,6 +110,10 @@ extern "C" {
     pub fn q3tts_config_from_model_dir(model_dir: *const c_char, quant: *const c_char, cfg: *mut q3tts_engine_config, path_buf: *mut c_char, path_cap: i32,
                                        err: *mut c_char, err_cap: i32) -> c_int;
     pub fn q3tts_engine_create(cfg: *const q3tts_engine_config, out: *mut *mut q3tts_engine) -> c_int;
+    // q3tts_engine_create with options ({struct_size, kquant_resident}: K-quant tensors stay quantised on the device; NULL = q3tts_engine_create)
+    pub fn q3tts_engine_create_opts(cfg: *const q3tts_engine_config, opts: *const q3tts_engine_options, out: *mut *mut q3tts_engine) -> c_int;
+    // the decoder matrices' device bytes held as bf16, Q4_K, Q5_K, Q6_K
+    pub fn q3tts_get_weight_formats(e: *const q3tts_engine, out: *mut i64) -> c_int;
     pub fn q3tts_engine_destroy(e: *mut q3tts_engine);
     // where the vocoder's weights came from: 0 none, 1 seeded synthetic, 2 qwen3_tts_vocoder.gguf beside the model
     pub fn q3tts_get_vocoder_source(e: *const q3tts_engine, source: *mut i32) -> c_int;
