@@ -236,9 +236,22 @@ int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine** out);
  * q3tts_engine_create on the same files; what changes is device memory, bytes per frame step and load time. A matrix stays bf16,
  * silently, when a tensor of it has another type, when ffn_gate and ffn_up differ in type (their columns share a tile), and always with
  * synthetic weights. Q3TTS_ERR_INVALID: kquant_resident together with talker_q8_0 != 0 or predictor_q8_0 != 0 (the message names both
- * settings), a value other than 0 / 1, and a struct_size this library does not know. opts == NULL: q3tts_engine_create. */
-typedef struct { uint32_t struct_size; int32_t kquant_resident; } q3tts_engine_options;
+ * settings), a value other than 0 / 1, and a struct_size this library does not know. opts == NULL: q3tts_engine_create.
+ * kv_pages = N >= 1 (0: off): the Talker's bf16 K/V cache is PAGED (csrc/q3_attend_paged.hip). Instead of n_ctx
+ * positions per slot the engine holds one pool of N pages of 64 positions (plus a zero page nobody owns) that all slots share, and a
+ * device table int32 [max_batch][n_ctx / 64] of each slot's pages: (N + 1) * 2 * t_n_layer * t_n_kv_head * 64 * t_head_dim * 2 bytes in
+ * place of max_batch * n_ctx * 2 * t_n_layer * t_n_kv_head * t_head_dim * 2, so n_ctx can stay a large logical limit. A request takes
+ * ceil((prefix rows + prompt rows + its own max_steps) / 64) pages with its slot and gives them back with it (done, EOS, cancel, error);
+ * while the pool cannot cover the request at the head of a queue it waits, as it waits for a free slot, and nothing overtakes it
+ * (q3tts_generate_batch, sessions, a session's prefix jobs). Ids, logits and PCM are those of the contiguous cache bit for bit.
+ * Q3TTS_ERR_INVALID (the message names both settings): kv_pages with kv_q8_0 = 1; kv_pages < n_ctx / 64 (every request the engine
+ * accepts fits the pool: what would need more pages exceeds n_ctx and is refused as such). q3tts_session_set_swap on a paged engine:
+ * Q3TTS_ERR_UNSUPPORTED. The Predictor's per-frame cache is never paged. struct_size may be that of the struct without kv_pages. */
+typedef struct { uint32_t struct_size; int32_t kquant_resident; int32_t kv_pages; } q3tts_engine_options;
 int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3tts_engine_options* opts, q3tts_engine** out);
+/* The paged cache's pool: out[0] pages it can hand out (kv_pages; 0 = the cache is contiguous), out[1] free now, out[2] the most in use at
+ * once since creation, out[3] bytes of one page over every layer and KV head, K and V. Call from the thread that drives the engine. */
+int q3tts_get_kv_pages(const q3tts_engine* e, int64_t out[4]);
 /* The decoder matrices' bytes on the device by the form they are held in: out[0] bf16 (or Q8_0 blocks with talker_q8_0 /
  * predictor_q8_0), out[1] Q4_K, out[2] Q5_K, out[3] Q6_K (the tiled sizes of q3tts_k_kq_bytes). */
 int q3tts_get_weight_formats(const q3tts_engine* e, int64_t out[4]);
@@ -837,6 +850,30 @@ int q3tts_k_attention_decode_kv8(int32_t device, const float* qkv, int32_t n_slo
                                  int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
                                  float rope_theta, const int32_t* mrope_sections, int32_t policy, int32_t out_form, void* out,
                                  float* out_scale, int8_t* k_q, int8_t* v_q, uint16_t* k_d, uint16_t* v_d);
+/* q3tts_k_attention_runs / q3tts_k_attention_decode_ex (without row_indexed) over a PAGED cache (csrc/q3_attend_paged.hip): a pool of
+ * n_pages + 1 pages and the caller's table tbl [n_runs or n_slots][n_ctx / 64] (entries 0 .. n_pages, 0 = the zero page). Page 0 and the
+ * pages the table names start as zeros, every other page filled with the bf16 pattern `fill`. Outputs as the contiguous hooks'; the
+ * cache comes back in their logical order, read through the table. q3tts_k_kv_prefix_roundtrip: a prefix store ([L][n_kv_head]
+ * [ceil(P / 64) * 64 * 128] bf16, K and V) copied into slot 0 of a cache of n_ctx positions and the slot's first P positions saved into
+ * zero-filled stores k_out / v_out; tbl NULL = the contiguous cache, else the slot's table [n_ctx / 64] as above. */
+int q3tts_k_attention_runs_paged(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx,
+                                 int32_t n_head, int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
+                                 float rope_theta, const int32_t* sections, int32_t policy, int32_t out_form, void* out, float* out_scale,
+                                 uint16_t* k_cache, uint16_t* v_cache, int32_t n_pages, const int32_t* tbl, uint16_t fill);
+int q3tts_k_attention_decode_paged(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t n_head,
+                                   int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
+                                   float rope_theta, const int32_t* sections, int32_t policy, int32_t out_form, void* out, float* out_scale,
+                                   uint16_t* k_cache, uint16_t* v_cache, int32_t n_pages, const int32_t* tbl, uint16_t fill);
+int q3tts_k_kv_prefix_roundtrip(int32_t device, const uint16_t* k_store, const uint16_t* v_store, int32_t n_layer, int32_t n_kv_head, int32_t P,
+                                int32_t n_ctx, int32_t n_pages, const int32_t* tbl, uint16_t fill, uint16_t* k_out, uint16_t* v_out);
+/* Host only: q3tts_k_attend_pick for a launch over a paged cache. *kernel = 15 / 16 / 17: k_attend_paged<1 / 2 / 4, false>; 18 / 19:
+ * k_attend_paged<2 / 4, true>; 20: k_attend_gqa2_paged; 21: k_attend_prefill_paged; -1: refused (fused = 2 and short fused caches, the
+ * Predictor's launches, among them). The choice is q3tts_k_attend_pick's for the same shape under the same policies. */
+int q3tts_k_attend_pick_paged(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t,
+                              int32_t n_kv_head, int32_t* kernel);
+/* Test hook: permute the free list of a paged engine's pool (seeded), so that requests take pages that are neither ascending nor
+ * adjacent. Q3TTS_ERR_STATE while any page is out, or on an engine whose cache is contiguous. */
+int q3tts_k_kv_pages_shuffle(q3tts_engine* e, uint64_t seed);
 /* Host only: q3tts_k_attend_pick for a launch over a Q8_0 cache. *kernel = 9 / 10 / 11: k_attend_kv8<1 / 2 / 4, false>; 12 / 13:
  * k_attend_kv8<2 / 4, true>; 14: k_attend_gqa2_kv8 (decode policy 0; policy 1 gives 12); -1: the launcher refuses (fused = 2, a fused
  * launch with one query head per KV head, a GQA ratio outside 1, 2, 4). Never 0 .. 8: there is no Q8 form of k_attend_prefill. */

@@ -28,6 +28,55 @@ static int voice_job_check(q3tts_engine* e, const q3tts_prompt_desc* p, const fl
     return Q3TTS_OK;
 }
 
+// ---- the paged cache's allocator (q3tts_engine_options.kv_pages): plain host state of the thread that drives the engine ----
+static int kvp_pages_for(int positions) { return (positions + 63) >> 6; }
+int q3_kvp_need(const q3tts_engine* e, const q3tts_request* r, const q3tts_prompt_desc* voice, int n_tok) {
+    if (!e->kvp_total) return 0;
+    if (!r) { const int n = voice ? q3_prompt_rows(voice, PROMPT_VOICE, false) : n_tok; return n >= 1 ? kvp_pages_for(n) : -1; }
+    const q3tts_prefix* x = r->prefix;
+    if (x && (x->e != e || x->state.load(std::memory_order_acquire) != 1)) return -1;
+    const int P = x ? x->P : 0;
+    const int n = r->prompt_embd ? r->n_tok : (r->prompt ? q3_prompt_rows(r->prompt, x ? PROMPT_TEXT : PROMPT_WHOLE, r->text_stream == 1) : 0);
+    const int max_steps = r->max_steps > 0 ? r->max_steps : e->max_steps;
+    return n >= 1 ? kvp_pages_for(P + n + max_steps) : -1;
+}
+bool q3_kvp_fits(const q3tts_engine* e, int need, int* avail) {
+    if (!e->kvp_total || need < 0 || need > e->kvp_total) return true;  // (not paged; or admission refuses it at once and takes nothing)
+    if (need > *avail) return false;
+    *avail -= need;
+    return true;
+}
+// slot b's table row as the host holds it, to the device on the engine's stream (in front of the slot's prefill / behind its last frame)
+static int kvp_upload_row(q3tts_engine* e, int b) {
+    const Q3KvCache& c = e->T.cache;
+    const size_t off = (size_t)b * c.tbl_stride;
+    Q3_HIP(e, hipMemcpyAsync(c.tbl + off, e->kvp_host + off, sizeof(int) * (size_t)c.tbl_stride, hipMemcpyHostToDevice, e->stream));
+    return Q3TTS_OK;
+}
+void q3_kvp_release(q3tts_engine* e, int b) {
+    if (!e->kvp_total || e->kvp_slot[b].empty()) return;
+    std::vector<int>& mine = e->kvp_slot[b];
+    for (size_t i = mine.size(); i-- > 0;) e->kvp_free.push_back(mine[i]);  // (LIFO: the slot's first page is the next one handed out)
+    mine.clear();
+    const Q3KvCache& c = e->T.cache;
+    memset(e->kvp_host + (size_t)b * c.tbl_stride, 0, sizeof(int) * (size_t)c.tbl_stride);  // every entry the slot does not own holds 0
+    kvp_upload_row(e, b);
+}
+// `need` pages for slot b, fixed until the slot lets go: blocks 0 .. need - 1 of its row. what: the positions the count comes from.
+static int kvp_take(q3tts_engine* e, int b, int need, int positions) {
+    if (!e->kvp_total) return Q3TTS_OK;
+    q3_kvp_release(e, b);  // (whatever an occupant that ended in an error left behind)
+    if (need > e->kvp_total)
+        return q3_set_err(e, Q3TTS_ERR_INVALID, "kv_pages: the request needs " + std::to_string(need) + " pages of 64 positions (prefix + prompt + max_steps = " +
+                          std::to_string(positions) + "), the pool has " + std::to_string(e->kvp_total));
+    if (need > (int)e->kvp_free.size())
+        return q3_set_err(e, Q3TTS_ERR_STATE, "kv_pages: " + std::to_string(need) + " pages wanted, " + std::to_string(e->kvp_free.size()) + " free (the caller admits only what q3_kvp_fits lets through)");
+    int* rowp = e->kvp_host + (size_t)b * e->T.cache.tbl_stride;
+    for (int i = 0; i < need; ++i) { rowp[i] = e->kvp_free.back(); e->kvp_slot[b].push_back(rowp[i]); e->kvp_free.pop_back(); }
+    e->kvp_peak = std::max(e->kvp_peak, e->kvp_total - (int)e->kvp_free.size());
+    return kvp_upload_row(e, b);
+}
+
 static uint64_t wall_seed() {
     return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::system_clock::now().time_since_epoch()).count();
 }
@@ -205,7 +254,14 @@ static int seed_slot(q3tts_engine* e, const Adm& a) {
     if (e->voc) TRY(q3_voc_reset(e, b));
     return Q3TTS_OK;
 }
+static int admit_group_run(q3tts_engine* e, std::vector<Adm>& grp, int total);
+// (paged cache: a prefix job's slot gives its pages back behind the group's launches — the save is ahead of any later user on the stream)
 static int admit_group(q3tts_engine* e, std::vector<Adm>& grp, int total) {
+    const int rc = admit_group_run(e, grp, total);
+    for (const Adm& a : grp) if (!a.r) q3_kvp_release(e, a.b);
+    return rc;
+}
+static int admit_group_run(q3tts_engine* e, std::vector<Adm>& grp, int total) {
     if (grp.empty()) return Q3TTS_OK;
     const GroupMaps m = group_maps(grp, total);
     Q3KvPrefix kp = q3_kv_prefix_of(e->T);
@@ -277,7 +333,9 @@ static int admit_job(q3tts_engine* e, std::vector<Adm>& grp, int& total, const Q
     if ((*fatal = place_rows(e, grp, total, e->cfg.n_ctx - 1, it.embd, it.n_tok, it.voice, PROMPT_VOICE, false, &n)) != Q3TTS_OK) return *fatal;
     if (n < 0) return n;
     if (n < 1) return q3_set_err(e, Q3TTS_ERR_INVALID, "prefix: the voice part has no rows");
-    TRY(prefix_store_alloc(e, it.keep, n));
+    TRY(kvp_take(e, it.slot, kvp_pages_for(n), n));
+    const int src = prefix_store_alloc(e, it.keep, n);
+    if (src != Q3TTS_OK) { q3_kvp_release(e, it.slot); return src; }
     grp.push_back(Adm{it.slot, nullptr, n, total, 0, 0, it.keep, n});
     total += n;
     return Q3TTS_OK;
@@ -306,6 +364,7 @@ static int admit_request(q3tts_engine* e, std::vector<Adm>& grp, int& total, con
         if (keep_rows < 1 || keep_rows >= n) return q3_set_err(e, Q3TTS_ERR_INVALID, "keep-voice: voice_rows outside 1 .. n - 1");
         TRY(prefix_store_alloc(e, it.keep, keep_rows));
     }
+    TRY(kvp_take(e, it.slot, kvp_pages_for(P + n + max_steps), P + n + max_steps));  // (last: nothing behind it refuses the request)
     grp.push_back(Adm{it.slot, r, n, total, max_steps, P, it.keep, keep_rows});
     total += n;
     return Q3TTS_OK;

@@ -8,15 +8,7 @@
 // K cache layout: per (slot, kv head) blocks of 64 keys, [block][hd/8 chunks][64 keys][8] bf16,
 // so that the score kernel reads 1 KiB contiguous per wave-load with one key per lane. V is row-major [t][hd].
 // ---------------------------------------------------------------------------------------------------
-// four floats as two bf16 pairs (element i in the low half of word i / 2): 8 bytes of a K / V cache row
-__device__ __forceinline__ uint2 pack_bf16x4(float a, float b, float c, float d) {
-    return make_uint2((uint32_t)q3_bf16(a) | ((uint32_t)q3_bf16(b) << 16), (uint32_t)q3_bf16(c) | ((uint32_t)q3_bf16(d) << 16));
-}
-// where dims 4 lane .. 4 lane + 3 of the key at `pos` live in a head's K cache (khead = kc + hb * hd): chunk lane / 2, half lane & 1
-__device__ __forceinline__ uint16_t* k_cache_elem(uint16_t* khead, int pos, int lane) {
-    const int blk = pos >> 6, kl = pos & 63, c = lane >> 1, e0 = 4 * (lane & 1);
-    return khead + ((size_t)(blk * (Q3_ATT_HD >> 3) + c) * 64 + kl) * 8 + e0;
-}
+// (pack_bf16x4 / k_cache_elem — a cache row's 8 bytes and where they live — are in q3_kernels.h: q3_attend_paged.hip uses them too)
 // (prep_rinv / prep_norm / prep_rope / prep_arith / prep_head — RMSNorm + RoPE of one head by one wave — are in q3_kernels.h: the Q8_0-cache
 // kernels of q3_attend_kv8.hip run the same statements)
 // bf16 K (key-interleaved blocks; k_cache_elem's address for a run-time hd) and V (row-major) append of one kv head by lanes [0, hd/4)
@@ -29,30 +21,7 @@ __device__ __forceinline__ void kv_append(uint16_t* kc, uint16_t* vc, size_t hb,
 // The two chains of the canonical order. Hand copies remain only where calling the helper changed the compiled schedule
 // of a decode-path kernel: prep_rope's loop in k_attend_gqa2 and k_attend_small's query wave, the output choice in k_attend_gqa2,
 // k_attend_prefill and k_attend_pair, the K address in k_attend_pair (whose chains read float operands from LDS).
-// Score: one 16-byte chunk of a key (8 bf16 dims, d ascending) onto the chain s; qa / qb = the query's 8 dims.
-__device__ __forceinline__ float att_dot8(const float4 qa, const float4 qb, const uint4 k, float s) {
-    s = fmaf(qa.x, q3_u2f(k.x << 16), s); s = fmaf(qa.y, q3_u2f(k.x & 0xffff0000u), s);
-    s = fmaf(qa.z, q3_u2f(k.y << 16), s); s = fmaf(qa.w, q3_u2f(k.y & 0xffff0000u), s);
-    s = fmaf(qb.x, q3_u2f(k.z << 16), s); s = fmaf(qb.y, q3_u2f(k.z & 0xffff0000u), s);
-    s = fmaf(qb.z, q3_u2f(k.w << 16), s); s = fmaf(qb.w, q3_u2f(k.w & 0xffff0000u), s);
-    return s;
-}
-// Value: 8 dims of one value row (16 bytes, bf16) times the key's weight pt onto the lane's 8 partial sums.
-__device__ __forceinline__ void att_pv8(float pt, const uint4 v, float o[8]) {
-    o[0] = fmaf(pt, q3_u2f(v.x << 16), o[0]); o[1] = fmaf(pt, q3_u2f(v.x & 0xffff0000u), o[1]);
-    o[2] = fmaf(pt, q3_u2f(v.y << 16), o[2]); o[3] = fmaf(pt, q3_u2f(v.y & 0xffff0000u), o[3]);
-    o[4] = fmaf(pt, q3_u2f(v.z << 16), o[4]); o[5] = fmaf(pt, q3_u2f(v.z & 0xffff0000u), o[5]);
-    o[6] = fmaf(pt, q3_u2f(v.w << 16), o[6]); o[7] = fmaf(pt, q3_u2f(v.w & 0xffff0000u), o[7]);
-}
-// The value step for two heads that share the row (k_attend_gqa2): the row is decoded once, head 0's sums first, then head 1's.
-__device__ __forceinline__ void att_pv8x2(float pa, float pb, const uint4 w, float o0[8], float o1[8]) {
-    const float v0 = q3_u2f(w.x << 16), v1 = q3_u2f(w.x & 0xffff0000u), v2 = q3_u2f(w.y << 16), v3 = q3_u2f(w.y & 0xffff0000u);
-    const float v4 = q3_u2f(w.z << 16), v5 = q3_u2f(w.z & 0xffff0000u), v6 = q3_u2f(w.w << 16), v7 = q3_u2f(w.w & 0xffff0000u);
-    o0[0] = fmaf(pa, v0, o0[0]); o0[1] = fmaf(pa, v1, o0[1]); o0[2] = fmaf(pa, v2, o0[2]); o0[3] = fmaf(pa, v3, o0[3]);
-    o0[4] = fmaf(pa, v4, o0[4]); o0[5] = fmaf(pa, v5, o0[5]); o0[6] = fmaf(pa, v6, o0[6]); o0[7] = fmaf(pa, v7, o0[7]);
-    o1[0] = fmaf(pb, v0, o1[0]); o1[1] = fmaf(pb, v1, o1[1]); o1[2] = fmaf(pb, v2, o1[2]); o1[3] = fmaf(pb, v3, o1[3]);
-    o1[4] = fmaf(pb, v4, o1[4]); o1[5] = fmaf(pb, v5, o1[5]); o1[6] = fmaf(pb, v6, o1[6]); o1[7] = fmaf(pb, v7, o1[7]);
-}
+// (att_dot8 / att_pv8 / att_pv8x2 — the score chain and the value step — are in q3_kernels.h, shared with q3_attend_paged.hip)
 // (att_out1 / att_out2 — the attention output in the form Q3Attend.out_bf16 names — are in q3_kernels.h)
 
 // hd stays the run-time a.hd here (the launcher admits only Q3_ATT_HD): with the constant folded in, the kernel traced 80-140 ns per launch
@@ -78,6 +47,7 @@ __global__ __launch_bounds__(64) void k_qk_prep(Q3QkPrep a) {
 }
 int q3_launch_qk_prep(const Q3QkPrep& a, hipStream_t s) {
     if (a.kv8) return q3_launch_qk_prep_kv8(a, s);  // Q8_0 cache: the quantising append of q3_attend_kv8.hip
+    if (a.tbl) return q3_launch_qk_prep_paged(a, s);  // paged cache: the append of q3_attend_paged.hip
     if (a.hd != Q3_ATT_HD) return 1;
     hipLaunchKernelGGL(k_qk_prep, dim3(a.rows, a.Hq + a.Hkv), dim3(64), 0, s, a);
     return 0;
@@ -835,6 +805,7 @@ static hipError_t att_allow_lds(const void* kernel, size_t lds) { return hipFunc
 int q3_attend_pick(const Q3Attend& a) {
     att_policy_init();
     if (a.kv8) return q3_attend_pick_kv8(a);  // Q8_0 cache: one of the six kernels of q3_attend_kv8.hip, never one of the nine below
+    if (a.tbl) return q3_attend_pick_paged(a);  // paged cache: one of the seven of q3_attend_paged.hip
     if (a.hd != Q3_ATT_HD || a.Hkv <= 0 || a.Hq % a.Hkv) return Q3_ATT_REFUSED;
     const int R = a.Hq / a.Hkv;
     if ((R != 1 && R != 2 && R != 4) || (a.fused && R == 1) || (a.fused == 2 && R != 2)) return Q3_ATT_REFUSED;
@@ -856,6 +827,7 @@ int q3_attend_pick(const Q3Attend& a) {
 // 0: launched. Nonzero: refused, nothing launched — a shape q3_attend_pick refuses, or a device that refuses the LDS size.
 int q3_launch_attend(const Q3Attend& a, hipStream_t s) {
     if (a.kv8) return q3_launch_attend_kv8(a, s);
+    if (a.tbl) return q3_launch_attend_paged(a, s);
     const int pick = q3_attend_pick(a);
     if (pick == Q3_ATT_REFUSED) return 1;
     const int R = a.Hq / a.Hkv;
@@ -929,6 +901,7 @@ __global__ __launch_bounds__(256) void k_kv_prefix(Q3KvPrefix a) {
 void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s) {
     if (a.n <= 0) return;
     if (a.kv8) { q3_launch_kv_prefix_kv8(a, s); return; }
+    if (a.tbl) { q3_launch_kv_prefix_paged(a, s); return; }
     hipLaunchKernelGGL(k_kv_prefix, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
 }
 
@@ -960,6 +933,7 @@ int q3_launch_kv_prefix_save(const Q3KvPrefix& a, hipStream_t s) {
     if (a.n <= 0) return 0;
     if (a.hd != Q3_ATT_HD || a.n > Q3_KVP_MAX) return 1;
     if (a.kv8) return q3_launch_kv_prefix_save_kv8(a, s);
+    if (a.tbl) return q3_launch_kv_prefix_save_paged(a, s);
     hipLaunchKernelGGL(k_kv_prefix_save, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
     return 0;
 }

@@ -26,6 +26,9 @@ struct Q3KvCache {
     // kd / vd the f16 block scales [L][slots][Hkv][n_ctx*hd/32], which follow the quants in the same allocation. q3_layer_cache does the arithmetic.
     bool kv8 = false; uint16_t *kd = nullptr, *vd = nullptr;
     int n_ctx = 0, n_slots = 0;
+    // q3tts_engine_options.kv_pages (the Talker only): kc / vc are page pools [L][n_pages + 1][Hkv][64 * hd] (layer_stride
+    // = one layer's pool) and tbl [n_slots][tbl_stride = n_ctx / 64] names each slot's pages (device; page 0 = the zero page). Null: contiguous.
+    int* tbl = nullptr; int tbl_stride = 0, n_pages = 0;
 };
 
 struct Q3Tfm {
@@ -175,6 +178,12 @@ struct q3tts_engine {
     float *park_logits = nullptr, *park_x = nullptr;  // [B][t_vocab], [B][t_d_model]: a parked slot's rows (q3_park_rows)
     float* first_chunk_host = nullptr;  // pinned landing buffer of the first 4-frame PCM chunk (first-chunk latency)
     std::atomic<q3tts_session*> session{nullptr};  // an open session owns the engine (q3_session.hip)
+    // The paged Talker cache's allocator (q3tts_engine_options.kv_pages; q3_admit.hip): a LIFO free list of page numbers
+    // 1 .. kvp_total, the pages each slot holds, and the pinned image of the device table (a slot's row is uploaded on e->stream in front of
+    // its prefill and zeroed when the slot lets go). kvp_total = 0: the cache is contiguous and none of this is touched.
+    int kvp_total = 0, kvp_peak = 0;
+    std::vector<int> kvp_free; std::vector<std::vector<int>> kvp_slot;
+    int* kvp_host = nullptr;
     std::mutex err_mu;                  // err is written by the session worker too
 };
 
@@ -229,6 +238,7 @@ struct Q3TfmShape {
     float theta; const int* sections;  // RoPE base; M-RoPE sections (null: every dimension rotates)
     int n_ctx, n_slots;       // KV cache: positions per slot, slots
     int kv8;                  // cfg.kv_q8_0: the cache as Q8_0 blocks
+    int kv_pages;             // q3tts_engine_options.kv_pages: > 0 = a pool of that many 64-position pages (+ the zero page) and a table, not n_slots * n_ctx positions
 };
 // layer l's part of the cache t: bf16 elements, or (t.kv8) int8 quants and their scales
 inline void q3_layer_cache(const Q3KvCache& t, int l, uint16_t** kc, uint16_t** vc, uint16_t** kd, uint16_t** vd) {
@@ -241,6 +251,7 @@ inline void q3_layer_cache(const Q3KvCache& t, int l, uint16_t** kc, uint16_t** 
 inline Q3KvPrefix q3_kv_prefix_of(const Q3Tfm& t) {
     const Q3KvCache& c = t.cache;
     Q3KvPrefix kp{c.kc, c.vc, c.layer_stride, c.n_ctx, t.L, t.Hkv, t.hd}; kp.kv8 = c.kv8 ? 1 : 0; kp.kd = c.kd; kp.vd = c.vd;
+    kp.tbl = c.tbl; kp.tbl_stride = c.tbl_stride;
     return kp;
 }
 // the transformer's weights, KV cache and RoPE tables. g: the opened GGUF `file` (null: seeded synthetic weights);
@@ -439,6 +450,17 @@ int build_prompt_dev(q3tts_engine* e, const q3tts_prompt_desc* p, float* out, in
 int q3_plan_rows(q3tts_engine* e, const std::vector<int>& live);
 int q3_admit_many(q3tts_engine* e, const int* slots, const q3tts_request* const* reqs, int count, int* rc);
 int q3_admit(q3tts_engine* e, int b, const q3tts_request* r);
+// Paged cache (all of them no-ops / "fits" on a contiguous engine). q3_kvp_need: the pages a request takes with its slot,
+// ceil((P + prompt rows + max_steps) / 64), from the request alone (host arithmetic: the prompt builder's row count); of a prefix job
+// (r == null) ceil(rows / 64). -1: the request is malformed in a way admission will name. q3_kvp_fits: whether the head of a queue may be
+// handed a slot now — it needs no more than *avail pages (then *avail shrinks by them), or more than the whole pool (admission refuses it
+// at once; nothing to wait for). q3_kvp_release: slot b's pages go back (done, EOS, cancel, error).
+int q3_kvp_need(const q3tts_engine* e, const q3tts_request* r, const q3tts_prompt_desc* voice, int n_tok);
+bool q3_kvp_fits(const q3tts_engine* e, int need, int* avail);
+inline int q3_kvp_avail(const q3tts_engine* e) { return (int)e->kvp_free.size(); }
+void q3_kvp_release(q3tts_engine* e, int b);
+// the prompt builder's row count for `part` of p (what build_prompt_dev will report), without building anything
+int q3_prompt_rows(const q3tts_prompt_desc* p, int part, bool text_stream);
 // What a well-formed request / voice job is, as far as no engine is needed to say: the rules every entry refuses alike (pure host code).
 // keep: the request's voice part is to be kept as a prefix, keep_rows rows of it (0: taken from r->prompt). Q3TTS_OK, or Q3TTS_ERR_INVALID
 // with *msg naming the rule; the session sites put their "submit: " / "prefix: " in front (q3tts_k_request_rules is the first as a test hook).

@@ -121,13 +121,15 @@ static unsigned long long tfm_weight_bytes(int L, int d, int Hq, int Hkv, int hd
     const unsigned long long n = per * L + (unsigned long long)head_n * d;
     return q8 ? n + n / 16 : 2 * n;  // Q8_0: 34 bytes per 32 weights
 }
-static unsigned long long engine_footprint(const q3tts_engine_config& c) {
+static unsigned long long engine_footprint(const q3tts_engine_config& c, int kv_pages = 0) {
     const q3tts_model_config& m = c.model;
     const unsigned long long B = c.max_batch, nctx = c.n_ctx, cap = c.max_steps_cap;
     unsigned long long t = tfm_weight_bytes(m.t_n_layer, m.t_d_model, m.t_n_head, m.t_n_kv_head, m.t_head_dim, m.t_d_ffn, m.t_vocab, c.talker_q8_0) +
                            tfm_weight_bytes(m.p_n_layer, m.p_d_model, m.p_n_head, m.p_n_kv_head, m.p_head_dim, m.p_d_ffn, (m.n_codebooks - 1) * m.codebook_size, c.predictor_q8_0);
     // Talker KV: bf16, or (kv_q8_0) Q8_0 blocks — 2 * t_n_layer * t_n_kv_head * n_ctx * (t_head_dim + 2 * t_head_dim / 32) bytes per slot
-    if (c.kv_q8_0) t += B * 2ull * m.t_n_layer * m.t_n_kv_head * nctx * (m.t_head_dim + 2ull * m.t_head_dim / 32);
+    // paged (kv_pages, bf16 only): the pool of kv_pages + 1 pages of 64 positions, and the table — not max_batch * n_ctx positions
+    if (kv_pages > 0) t += (kv_pages + 1ull) * 2 * m.t_n_layer * m.t_n_kv_head * 64 * m.t_head_dim * 2 + B * (nctx / 64) * 4;
+    else if (c.kv_q8_0) t += B * 2ull * m.t_n_layer * m.t_n_kv_head * nctx * (m.t_head_dim + 2ull * m.t_head_dim / 32);
     else t += B * 2ull * m.t_n_layer * m.t_n_kv_head * m.t_head_dim * nctx * 2;
     t += B * 2ull * m.p_n_layer * m.p_n_kv_head * m.p_head_dim * 64 * 2;    // Predictor cache (64 positions, one frame)
     t += B * cap * 4ull * (m.n_codebooks + 1 + (m.n_codebooks - 1));        // codes, rng, prng
@@ -189,6 +191,27 @@ extern "C" int q3tts_k_device_bytes(const q3tts_engine* e, int64_t* bytes) {
     *bytes = (int64_t)e->dev_bytes;
     return Q3TTS_OK;
 }
+// paged cache: {pages the pool can hand out, free now, the most in use at once, bytes of one page over all layers, heads, K and V}
+extern "C" int q3tts_get_kv_pages(const q3tts_engine* e, int64_t out[4]) {
+    if (!e || !out) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    out[0] = e->kvp_total; out[1] = (int64_t)e->kvp_free.size(); out[2] = e->kvp_peak;
+    out[3] = e->kvp_total ? 2ll * e->T.L * e->T.Hkv * 64 * e->T.hd * 2 : 0;
+    return Q3TTS_OK;
+}
+// test hook: the free list in a seeded pseudo-random order (a 64-bit LCG driving Fisher-Yates), so that the pages requests take next
+// are neither ascending nor adjacent
+extern "C" int q3tts_k_kv_pages_shuffle(q3tts_engine* e, uint64_t seed) {
+    if (!e) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null engine");
+    Q3_NOT_IN_SESSION(e);
+    if (!e->kvp_total) return q3_set_err(e, Q3TTS_ERR_STATE, "kv pages shuffle: this engine's cache is not paged (q3tts_engine_options.kv_pages = 0)");
+    if ((int)e->kvp_free.size() != e->kvp_total) return q3_set_err(e, Q3TTS_ERR_STATE, "kv pages shuffle: " + std::to_string(e->kvp_total - (int)e->kvp_free.size()) + " pages are out");
+    uint64_t x = seed * 6364136223846793005ull + 1442695040888963407ull;
+    for (size_t i = e->kvp_free.size(); i > 1; --i) {
+        x = x * 6364136223846793005ull + 1442695040888963407ull;
+        std::swap(e->kvp_free[i - 1], e->kvp_free[(size_t)((x >> 33) % i)]);
+    }
+    return Q3TTS_OK;
+}
 static int alloc_scratch(q3tts_engine* e, Q3Scratch& sc, int rows, int nqkv, int nq, int F) {
     sc.rows = rows;
     const size_t r16 = ((size_t)rows + 15) & ~(size_t)15;  // A-tiled buffers hold whole 16-row tiles
@@ -207,15 +230,15 @@ static int alloc_rows(q3tts_engine* e, Q3Rows& r, size_t rows, int d, bool scale
     return Q3TTS_OK;
 }
 
-static Q3TfmShape talker_shape(const q3tts_engine_config& c) {
+static Q3TfmShape talker_shape(const q3tts_engine_config& c, int kv_pages = 0) {
     const q3tts_model_config& m = c.model;
     return {.grp = Q3G_TALKER, .L = m.t_n_layer, .d = m.t_d_model, .Hq = m.t_n_head, .Hkv = m.t_n_kv_head, .hd = m.t_head_dim, .F = m.t_d_ffn,
-            .head_n = m.t_vocab, .theta = m.t_rope_theta, .sections = m.t_mrope_sections, .n_ctx = c.n_ctx, .n_slots = c.max_batch, .kv8 = c.kv_q8_0};
+            .head_n = m.t_vocab, .theta = m.t_rope_theta, .sections = m.t_mrope_sections, .n_ctx = c.n_ctx, .n_slots = c.max_batch, .kv8 = c.kv_q8_0, .kv_pages = kv_pages};
 }
 static Q3TfmShape predictor_shape(const q3tts_engine_config& c) {
     const q3tts_model_config& m = c.model;
     return {.grp = Q3G_PRED, .L = m.p_n_layer, .d = m.p_d_model, .Hq = m.p_n_head, .Hkv = m.p_n_kv_head, .hd = m.p_head_dim, .F = m.p_d_ffn,
-            .head_n = (m.n_codebooks - 1) * m.codebook_size, .theta = m.p_rope_theta, .sections = nullptr, .n_ctx = 64, .n_slots = c.max_batch, .kv8 = 0};
+            .head_n = (m.n_codebooks - 1) * m.codebook_size, .theta = m.p_rope_theta, .sections = nullptr, .n_ctx = 64, .n_slots = c.max_batch, .kv8 = 0, .kv_pages = 0};
 }
 extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine** out) { return q3tts_engine_create_opts(cfg, nullptr, out); }
 extern "C" int q3tts_get_weight_formats(const q3tts_engine* e, int64_t out[4]) {
@@ -227,14 +250,24 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     if (!cfg || !out) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
     std::string why;
     if (validate(*cfg, why) != Q3TTS_OK) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, why);
-    int kquant = 0;
+    int kquant = 0, kv_pages = 0;
     if (opts) {
-        if (opts->struct_size != sizeof(q3tts_engine_options)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.struct_size = " + std::to_string(opts->struct_size) + ", this library knows " + std::to_string(sizeof(q3tts_engine_options)));
+        // (a caller built against the struct without kv_pages passes the shorter size: everything behind it is off)
+        const bool has_pages = opts->struct_size >= offsetof(q3tts_engine_options, kv_pages) + sizeof(int32_t);
+        if (opts->struct_size != sizeof(q3tts_engine_options) && opts->struct_size != offsetof(q3tts_engine_options, kv_pages)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.struct_size = " + std::to_string(opts->struct_size) + ", this library knows " + std::to_string(sizeof(q3tts_engine_options)));
         if (opts->kquant_resident != 0 && opts->kquant_resident != 1) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.kquant_resident must be 0 or 1");
         kquant = opts->kquant_resident;
         if (kquant && (cfg->talker_q8_0 != 0 || cfg->predictor_q8_0 != 0))
             return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "kquant_resident = 1 keeps K-quant tensors as stored; it cannot be combined with talker_q8_0 = " + std::to_string(cfg->talker_q8_0) +
                               " / predictor_q8_0 = " + std::to_string(cfg->predictor_q8_0) + " (Q8_0 weights): set one or the other");
+        kv_pages = has_pages ? opts->kv_pages : 0;
+        if (kv_pages < 0) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.kv_pages must be >= 0 (0: the contiguous cache)");
+        if (kv_pages && cfg->kv_q8_0)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "kv_pages = " + std::to_string(kv_pages) + " pages the bf16 cache; it cannot be combined with kv_q8_0 = " +
+                              std::to_string(cfg->kv_q8_0) + " (the Q8_0 cache is contiguous): set one or the other");
+        if (kv_pages && cfg->n_ctx / 64 > kv_pages)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "kv_pages = " + std::to_string(kv_pages) + " cannot hold one request of n_ctx = " + std::to_string(cfg->n_ctx) +
+                              " (" + std::to_string(cfg->n_ctx / 64) + " pages of 64 positions): a larger kv_pages or a smaller n_ctx");
     }
     if (cfg->predictor_q8_0 == 1)
         return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, "predictor_q8_0 = 1 (Q8_0 weights x bf16 activations) is not implemented for the Predictor: use 0 (bf16) or 2 (Q8_0 x Q8_0)");
@@ -284,10 +317,10 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     {   // before the first allocation: what the config sizes against the device's free memory (not a failure half-way through q3_dalloc)
         size_t free_b = 0, total_b = 0;
         HIPC(hipMemGetInfo(&free_b, &total_b));
-        const unsigned long long need = engine_footprint(*cfg) - kq_saved;
+        const unsigned long long need = engine_footprint(*cfg, kv_pages) - kq_saved;
         if (need > (unsigned long long)free_b) {
             q3_set_err(e, Q3TTS_ERR_OOM, "engine needs at least " + std::to_string(need) + " bytes of device memory for max_batch = " + std::to_string(cfg->max_batch) +
-                       ", n_ctx = " + std::to_string(cfg->n_ctx) + (cfg->kv_q8_0 ? " (Q8_0 cache)" : "") + "; the device has " + std::to_string((unsigned long long)free_b) +
+                       ", n_ctx = " + std::to_string(cfg->n_ctx) + (cfg->kv_q8_0 ? " (Q8_0 cache)" : "") + (kv_pages ? " (kv_pages = " + std::to_string(kv_pages) + ")" : std::string()) + "; the device has " + std::to_string((unsigned long long)free_b) +
                        (cfg->kv_q8_0 ? " bytes free (fewer slots or a smaller n_ctx)" : " bytes free (fewer slots, a smaller n_ctx, or kv_q8_0 = 1: the cache in 0.53 of the bytes)"));
             return fail(Q3TTS_ERR_OOM);
         }
@@ -312,8 +345,15 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     const int B = cfg->max_batch;
     e->B = B;
     hipStream_t s = e->stream;
-    TRYC(q3_tfm_init(e, e->T, talker_shape(*cfg), wdir.empty() ? nullptr : &gt, "qwen3_tts_talker.gguf", cfg->talker_q8_0, kquant));
+    TRYC(q3_tfm_init(e, e->T, talker_shape(*cfg, kv_pages), wdir.empty() ? nullptr : &gt, "qwen3_tts_talker.gguf", cfg->talker_q8_0, kquant));
     TRYC(q3_tfm_init(e, e->P, predictor_shape(*cfg), wdir.empty() ? nullptr : &gp, "qwen3_tts_predictor.gguf", cfg->predictor_q8_0, kquant));
+    if (kv_pages) {  // the page allocator: LIFO, page 1 on top; the table's pinned image (all zero, like the device's)
+        e->kvp_total = kv_pages; e->kvp_slot.assign(B, {});
+        for (int p = kv_pages; p >= 1; --p) e->kvp_free.push_back(p);
+        const size_t tb = sizeof(int) * (size_t)B * e->T.cache.tbl_stride;
+        HIPC(hipHostMalloc((void**)&e->kvp_host, tb, hipHostMallocDefault));
+        memset(e->kvp_host, 0, tb);
+    }
     TRYC(q3_assets_init(e, wdir));
     TRYC(q3_pred_table_init(e));
     // decode state
@@ -410,6 +450,7 @@ extern "C" void q3tts_engine_destroy(q3tts_engine* e) {
     hipFree(e->rs_stage);                  // regrows with the output rate: its own pair (q3tts_set_output_rate)
     hipFree(e->tp_row);                    // regrows with the speed: its own pair (q3tts_set_speed)
     if (e->slots_host) hipHostFree(e->slots_host);
+    if (e->kvp_host) hipHostFree(e->kvp_host);
     for (auto ev : e->fin_ev) if (ev) hipEventDestroy(ev);
     for (auto ev : e->probe_ev) if (ev) hipEventDestroy(ev);
     if (e->ev0) hipEventDestroy(e->ev0); if (e->ev1) hipEventDestroy(e->ev1); if (e->ev2) hipEventDestroy(e->ev2); if (e->ev3) hipEventDestroy(e->ev3);
@@ -524,6 +565,17 @@ enum { PAD = 2148, BOS = 2149, THINK = 2154, NOTHINK = 2155, THINK_BOS = 2156, T
 // EOS, activation row) last, so PROMPT_VOICE ++ PROMPT_TEXT is PROMPT_WHOLE row for row (voice prefixes: include/q3tts.h).
 // text_stream: the text part in the streamed layout (include/q3tts.h, "streaming text input"): BOS, then text[x[0]] + codec0[BOS] in place of
 // the activation row; x[1 ..) and EOS join the feedback rows (q3_text_trailing, Q3TextRows). The voice part is the same either way.
+// the row count of the list below, from the desc alone (q3_kvp_need sizes a request's pages with it before anything is built)
+int q3_prompt_rows(const q3tts_prompt_desc* p, int part, bool text_stream) {
+    int n = 0;
+    if (part != PROMPT_TEXT) {
+        if (p->instruct_ids) n += 5 + std::max(p->n_instruct, 0);
+        n += 3 + (p->lang_id >= 0 ? 4 : 3) + ((p->spk_id >= 0 || p->spk_emb) ? 1 : 0);
+        if (p->ref_codes) n += 4 + std::max(p->n_ref_text, 0) + std::max(p->n_ref_frames, 0);
+    }
+    if (part != PROMPT_VOICE) n += text_stream ? 2 : std::max(p->n_text, 0) + 3;
+    return n;
+}
 int build_prompt_dev(q3tts_engine* e, const q3tts_prompt_desc* p, float* out, int max_rows, int* n_out, int part, bool text_stream) {
     const q3tts_model_config& m = e->cfg.model;
     if (!p || (p->n_text > 0 && !p->text_ids)) return q3_set_err(e, Q3TTS_ERR_INVALID, "prompt: text_ids missing");

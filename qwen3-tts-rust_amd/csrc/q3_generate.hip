@@ -182,6 +182,7 @@ int q3_retire_slot(q3tts_engine* e, int b, hipStream_t evs) {
     memset(st, 0, sizeof(*st));
     Q3_HIP(e, hipMemcpyAsync(e->slots + b, st, sizeof(Q3Slot), hipMemcpyHostToDevice, e->stream));
     Q3_HIP(e, hipEventRecord(e->fin_ev[b], evs));
+    q3_kvp_release(e, b);  // (paged cache: the slot's pages go back with it)
     return Q3TTS_OK;
 }
 int q3_emit_count(const q3tts_engine* e, int ns, bool done, long long delivered) {
@@ -253,6 +254,7 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
         if (reqs[i].text_open == 1) return q3_set_err(e, Q3TTS_ERR_INVALID, "text_open = 1 is for sessions (q3tts_session_append_text): this call takes closed text and never waits");
     }
     std::fill(e->ts_slot.begin(), e->ts_slot.end(), 0);  // nothing is in flight
+    for (int b = 0; b < e->B; ++b) q3_kvp_release(e, b);   // (... and no page is out: what a call that ended in an error left)
     if (e->dev_pcm_on && e->voc) {  // one row of max_steps_cap frames per request of this call
         const size_t stride = (size_t)e->cfg.max_steps_cap * q3_voc_samples_per_frame(e);
         if (e->dev_pcm_n < n || e->dev_pcm_stride != stride) {
@@ -285,8 +287,10 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
         bool admitted = false;
         {
             std::vector<int> as, ai; std::vector<const q3tts_request*> ar;
+            int pages = q3_kvp_avail(e);  // paged cache: the next request waits for pages as it waits for a slot, and nothing overtakes it
             for (int b = 0; b < B && next < n; ++b)
-                if (run[b].req < 0) { TRY(drain(b)); as.push_back(b); ar.push_back(&reqs[next]); ai.push_back(next++); }
+                if (run[b].req < 0) { if (!q3_kvp_fits(e, q3_kvp_need(e, &reqs[next], nullptr, 0), &pages)) break;
+                                      TRY(drain(b)); as.push_back(b); ar.push_back(&reqs[next]); ai.push_back(next++); }
             {
                 std::vector<int> live(as);
                 for (int b = 0; b < B; ++b) if (run[b].req >= 0) live.push_back(b);
@@ -346,6 +350,7 @@ extern "C" int q3tts_generate_batch(q3tts_engine* e, const q3tts_request* reqs, 
             pending[b] = run[b].req;
             run[b].req = -1; ++done;
             e->ts_slot[b] = 0;
+            q3_kvp_release(e, b);
         }
         hp_lap(hp_fin);
     }
@@ -443,6 +448,7 @@ extern "C" int q3tts_stream_begin(q3tts_engine* e, const q3tts_request* req, q3t
     if (req->text_open == 1) return q3_set_err(e, Q3TTS_ERR_INVALID, "text_open = 1 is for sessions (q3tts_session_append_text): a stream takes closed text and never waits");
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     std::fill(e->ts_slot.begin(), e->ts_slot.end(), 0);  // nothing else is in flight
+    for (int b = 0; b < e->B; ++b) q3_kvp_release(e, b);
     q3tts_stream* st = new q3tts_stream();
     st->e = e; st->req = *req; st->t0 = q3_now_ms();
     int rc = q3_plan_rows(e, std::vector<int>{0});

@@ -219,6 +219,22 @@ struct AttHook {
     int n_slots = 0, n_ctx = 0, Hq = 0, Hkv = 0, ld = 0, nq = 0, form = 0, out_rows = 0, rt16 = 0;
     int kv8 = 0;  // the cache as Q8_0 blocks (the _kv8 hooks; set before init): kc / vc then hold int8 quants, kd / vd their f16 scales
     DevBuf qn, kn, cs, sn, kc, vc, kd, vd, out, osc;
+    // the cache paged (the _paged hooks; set before init): kc / vc then are pools of n_pages + 1 pages [page][Hkv][64 * hd], tbl_host the
+    // caller's table [n_slots][n_ctx / 64]; page 0 and every page the table names start as zeros, every other page holds `fill`
+    int n_pages = 0; const int32_t* tbl_host = nullptr; uint16_t fill = 0; DevBuf tbl;
+    static const char* check_table(const int32_t* t, int n_slots, int n_ctx, int n_pages) {
+        if (!t || n_pages < 1 || n_pages > (1 << 20)) return "a table and 1 .. 2^20 pages";
+        for (size_t i = 0; i < (size_t)n_slots * (n_ctx / 64); ++i) if (t[i] < 0 || t[i] > n_pages) return "a table entry outside 0 .. n_pages";
+        return nullptr;
+    }
+    int init_pool() {
+        const size_t pg = (size_t)Hkv * 64 * Q3_ATT_HD;
+        std::vector<uint16_t> img((size_t)(n_pages + 1) * pg, fill);
+        std::fill(img.begin(), img.begin() + pg, (uint16_t)0);
+        for (size_t i = 0; i < (size_t)n_slots * (n_ctx / 64); ++i) std::fill(img.begin() + tbl_host[i] * pg, img.begin() + (tbl_host[i] + 1) * pg, (uint16_t)0);
+        TRY(kc.put(img.data(), img.size() * 2)); TRY(vc.put(img.data(), img.size() * 2));
+        return tbl.put(tbl_host, (size_t)n_slots * (n_ctx / 64) * 4);
+    }
     // the arguments every attention hook checks before anything is allocated or launched
     static const char* check(const float* qkv, int n_slots, int n_ctx, int Hq, int Hkv, int hd, const float* qnw, const float* knw, int form, const void* out,
                              const float* out_scale) {
@@ -240,7 +256,8 @@ struct AttHook {
         q3_rope_tables(n_ctx, Q3_ATT_HD, theta, sections, c, s);
         TRY(qn.put(qnw, Q3_ATT_HD * 4)); TRY(kn.put(knw, Q3_ATT_HD * 4)); TRY(cs.put(c.data(), c.size() * 4)); TRY(sn.put(s.data(), s.size() * 4));
         const size_t cache = (size_t)n_slots * Hkv * n_ctx * Q3_ATT_HD * (kv8 ? 1 : 2);
-        TRY(kc.alloc(cache)); TRY(vc.alloc(cache));
+        if (n_pages) TRY(init_pool());
+        else { TRY(kc.alloc(cache)); TRY(vc.alloc(cache)); }
         if (kv8) { TRY(kd.alloc(cache / 16)); TRY(vd.alloc(cache / 16)); }
         TRY(out.alloc(form == 0 ? (size_t)rows * nq * 4 : pad16(rows) * nq * (form == 1 ? 2 : 1)));
         if (form == 2) TRY(osc.alloc((size_t)(nq / 32 + 2) * pad16(rows) * 4));
@@ -250,12 +267,14 @@ struct AttHook {
         Q3QkPrep qp{}; qp.qkv = rows_dev; qp.ld = ld; qp.rows = rows; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = Q3_ATT_HD; qp.qnw = qn; qp.knw = kn; qp.eps = eps;
         qp.cs = cs; qp.sn = sn; qp.kc = kc; qp.vc = vc; qp.n_ctx = n_ctx;
         if (kv8) { qp.kv8 = 1; qp.kd = kd; qp.vd = vd; }
+        if (n_pages) { qp.tbl = tbl; qp.tbl_stride = n_ctx / 64; }
         return qp;
     }
     Q3Attend attend(const float* rows_dev, int rows) const {
         Q3Attend at{}; at.qkv = rows_dev; at.ld = ld; at.rows = rows; at.out = out; at.ldo = nq; at.out_bf16 = form; at.Hq = Hq; at.Hkv = Hkv; at.hd = Q3_ATT_HD;
         at.kc = kc; at.vc = vc; at.n_ctx = n_ctx;
         if (kv8) { at.kv8 = 1; at.kd = kd; at.vd = vd; }
+        if (n_pages) { at.tbl = tbl; at.tbl_stride = n_ctx / 64; }
         if (form == 2) { at.out_scale = osc; at.out_rt16 = rt16; }
         return at;
     }
@@ -273,8 +292,26 @@ struct AttHook {
         return Q3TTS_OK;
     }
     // the cache of every slot as bf16 bits [slot][Hkv][n_ctx][hd]: keys out of their 64-key blocks (k_cache_elem), values as stored
+    // ... of a paged cache: the same logical order, every position through the table
+    int read_cache_paged(uint16_t* k_host, uint16_t* v_host) const {
+        constexpr int hd = Q3_ATT_HD;
+        const size_t pg = (size_t)64 * hd, np = (size_t)(n_pages + 1) * Hkv * pg;
+        std::vector<uint16_t> tk(np), tv(np);
+        TRY(kc.get(tk.data(), np * 2)); TRY(vc.get(tv.data(), np * 2));
+        for (int s = 0; s < n_slots; ++s)
+            for (int g = 0; g < Hkv; ++g)
+                for (int pos = 0; pos < n_ctx; ++pos) {
+                    const size_t po = ((size_t)tbl_host[(size_t)s * (n_ctx / 64) + (pos >> 6)] * Hkv + g) * pg, o = (((size_t)s * Hkv + g) * n_ctx + pos) * hd;
+                    for (int d = 0; d < hd; ++d) {
+                        if (k_host) k_host[o + d] = tk[po + ((size_t)(d >> 3) * 64 + (pos & 63)) * 8 + (d & 7)];
+                        if (v_host) v_host[o + d] = tv[po + (size_t)(pos & 63) * hd + d];
+                    }
+                }
+        return Q3TTS_OK;
+    }
     int read_cache(uint16_t* k_host, uint16_t* v_host) const {
         constexpr int hd = Q3_ATT_HD;
+        if (n_pages) return read_cache_paged(k_host, v_host);
         const size_t n = (size_t)n_slots * Hkv * n_ctx * hd;
         if (v_host) TRY(vc.get(v_host, n * 2));
         if (!k_host) return Q3TTS_OK;
@@ -310,7 +347,9 @@ struct AttHook {
     }
 };
 // what a hook hands back of the cache: bf16 bits (k16 / v16), or with kv8 the quants and scales
-struct AttCacheOut { int kv8 = 0; uint16_t *k16 = nullptr, *v16 = nullptr; int8_t *kq = nullptr, *vq = nullptr; uint16_t *kd = nullptr, *vd = nullptr; };
+struct AttCacheOut { int kv8 = 0; uint16_t *k16 = nullptr, *v16 = nullptr; int8_t *kq = nullptr, *vq = nullptr; uint16_t *kd = nullptr, *vd = nullptr;
+                     int n_pages = 0; const int32_t* tbl = nullptr; uint16_t fill = 0; };  // (the _paged hooks: the pool's size, the caller's table, the fill pattern)
+static void att_hook_paged(AttHook& h, const AttCacheOut& c) { h.n_pages = c.n_pages; h.tbl_host = c.tbl; h.fill = c.fill; }
 static int att_read_cache(const AttHook& h, const AttCacheOut& c) {
     return c.kv8 ? h.read_cache_kv8(c.kq, c.vq, c.kd, c.vd) : h.read_cache(c.k16, c.v16);
 }
@@ -334,9 +373,10 @@ static int att_hook_launch(const char* name, const Q3Attend& at, int decode, int
 static int attention_runs(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx, int32_t Hq,
                           int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections,
                           int32_t policy, int32_t out_form, void* out, float* out_scale, const AttCacheOut& cache) {
-    const std::string hook = cache.kv8 ? "attention runs_kv8 hook" : "attention runs hook";   // (the exported entry that was called)
+    const std::string hook = cache.kv8 ? "attention runs_kv8 hook" : cache.tbl ? "attention runs_paged hook" : "attention runs hook";   // (the exported entry that was called)
     if (const char* why = AttHook::check(qkv, n_runs, n_ctx, Hq, Hkv, hd, qnw, knw, out_form, out, out_scale))
         return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": " + why);
+    if (const char* why = cache.tbl ? AttHook::check_table(cache.tbl, n_runs, n_ctx, cache.n_pages) : nullptr) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": " + why);
     if (!run_n || !run_pos0 || policy < -1 || policy > 2) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": run tables, prefill policy -1 .. 2");
     long long n_pre = 0, n_run = 0;
     int seg_max_n = 0, seg_max_t = 0;
@@ -347,7 +387,7 @@ static int attention_runs(int32_t device, const float* qkv, int32_t n_runs, cons
         seg_max_n = std::max(seg_max_n, run_n[i]); seg_max_t = std::max(seg_max_t, run_pos0[i] + run_n[i]);
     }
     HK(hipSetDevice(device));
-    AttHook h; h.kv8 = cache.kv8;
+    AttHook h; h.kv8 = cache.kv8; att_hook_paged(h, cache);
     TRY(h.init(n_runs, n_ctx, Hq, Hkv, qnw, knw, theta, sections, out_form, (int)n_run));
     const int ld = h.ld;
     std::vector<float> pre((size_t)std::max<long long>(n_pre, 1) * ld), run((size_t)n_run * ld);
@@ -395,9 +435,10 @@ extern "C" int q3tts_k_attention_runs_kv8(int32_t device, const float* qkv, int3
 static int attention_decode_ex(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq, int32_t Hkv,
                                int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, int32_t policy,
                                int32_t row_indexed, int32_t out_form, void* out, float* out_scale, const AttCacheOut& cache) {
-    const std::string hook = cache.kv8 ? "attention decode_kv8 hook" : "attention decode_ex hook";
+    const std::string hook = cache.kv8 ? "attention decode_kv8 hook" : cache.tbl ? "attention decode_paged hook" : "attention decode_ex hook";
     if (const char* why = AttHook::check(qkv, n_slots, n_ctx, Hq, Hkv, hd, qnw, knw, out_form, out, out_scale))
         return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": " + why);
+    if (const char* why = cache.tbl ? AttHook::check_table(cache.tbl, n_slots, n_ctx, cache.n_pages) : nullptr) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": " + why);
     if (!lens || Hq / Hkv < 2 || policy < -1 || policy > 1 || row_indexed < 0 || row_indexed > 1)
         return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": lens, a GQA ratio of 2 or 4, decode policy -1 .. 1, row_indexed 0 / 1");
     long long total = 0;
@@ -407,7 +448,7 @@ static int attention_decode_ex(int32_t device, const float* qkv, int32_t n_slots
         total += lens[s];
     }
     HK(hipSetDevice(device));
-    AttHook h; h.kv8 = cache.kv8;
+    AttHook h; h.kv8 = cache.kv8; att_hook_paged(h, cache);
     TRY(h.init(n_slots, n_ctx, Hq, Hkv, qnw, knw, theta, sections, out_form, n_slots));
     const int ld = h.ld, npre = (int)(total - n_slots);
     std::vector<float> pre((size_t)std::max(npre, 1) * ld), last((size_t)n_slots * ld);
@@ -449,6 +490,60 @@ extern "C" int q3tts_k_attention_decode_kv8(int32_t device, const float* qkv, in
     return attention_decode_ex(device, qkv, n_slots, lens, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, 0, out_form, out, out_scale, c);
 }
 
+// ... over a paged cache (q3_attend_paged.hip): the same rows through a pool of n_pages + 1 pages and the caller's table
+// tbl [n_runs or n_slots][n_ctx / 64] (entries 0 .. n_pages; 0 = the zero page); every page the table does not name, other than page 0,
+// starts filled with the bf16 pattern `fill`. The cache comes back in the contiguous hooks' logical order, read through the table.
+extern "C" int q3tts_k_attention_runs_paged(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx, int32_t Hq,
+                                            int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections,
+                                            int32_t policy, int32_t out_form, void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache,
+                                            int32_t n_pages, const int32_t* tbl, uint16_t fill) {
+    if (!tbl) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention runs_paged hook: a null table");
+    AttCacheOut c; c.k16 = k_cache; c.v16 = v_cache; c.n_pages = n_pages; c.tbl = tbl; c.fill = fill;
+    return attention_runs(device, qkv, n_runs, run_n, run_pos0, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, out_form, out, out_scale, c);
+}
+extern "C" int q3tts_k_attention_decode_paged(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq, int32_t Hkv,
+                                              int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, int32_t policy,
+                                              int32_t out_form, void* out, float* out_scale, uint16_t* k_cache, uint16_t* v_cache,
+                                              int32_t n_pages, const int32_t* tbl, uint16_t fill) {
+    if (!tbl) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attention decode_paged hook: a null table");
+    AttCacheOut c; c.k16 = k_cache; c.v16 = v_cache; c.n_pages = n_pages; c.tbl = tbl; c.fill = fill;
+    return attention_decode_ex(device, qkv, n_slots, lens, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, 0, out_form, out, out_scale, c);
+}
+// A voice prefix into a slot and out again: the store k_store / v_store ([L][Hkv][np * 128] bf16 bits, np = ceil(P / 64) * 64) is copied into
+// slot 0 of a cache of n_ctx positions (q3_launch_kv_prefix) and the slot's first P positions saved into a zero-filled store
+// (q3_launch_kv_prefix_save), which comes back in k_out / v_out. tbl == NULL: the contiguous cache; else a pool of n_pages + 1 pages, the
+// slot's table [n_ctx / 64] and the fill pattern as above.
+extern "C" int q3tts_k_kv_prefix_roundtrip(int32_t device, const uint16_t* k_store, const uint16_t* v_store, int32_t L, int32_t Hkv, int32_t P, int32_t n_ctx,
+                                           int32_t n_pages, const int32_t* tbl, uint16_t fill, uint16_t* k_out, uint16_t* v_out) {
+    if (!k_store || !v_store || !k_out || !v_out || L < 1 || L > 64 || Hkv < 1 || Hkv > 64 || P < 1 || n_ctx < 64 || n_ctx % 64 || n_ctx > 8192 || P > n_ctx)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "kv prefix roundtrip hook: null argument, or L / Hkv outside 1 .. 64, or P outside 1 .. n_ctx, or n_ctx not whole blocks");
+    if (const char* why = tbl ? AttHook::check_table(tbl, 1, n_ctx, n_pages) : nullptr) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string("kv prefix roundtrip hook: ") + why);
+    HK(hipSetDevice(device));
+    constexpr int hd = Q3_ATT_HD;
+    const int np = (P + 63) & ~63;
+    const size_t store = (size_t)L * Hkv * np * hd, pg = (size_t)Hkv * 64 * hd;
+    const size_t layer = tbl ? (size_t)(n_pages + 1) * pg : (size_t)Hkv * n_ctx * hd;
+    DevBuf dk, dv, ck, cv, ok, ov, dt;
+    TRY(dk.put(k_store, store * 2)); TRY(dv.put(v_store, store * 2)); TRY(ok.alloc(store * 2)); TRY(ov.alloc(store * 2));
+    if (tbl) {
+        std::vector<uint16_t> img(layer * L, fill);
+        for (int l = 0; l < L; ++l) {
+            std::fill(img.begin() + l * layer, img.begin() + l * layer + pg, (uint16_t)0);
+            for (int i = 0; i < n_ctx / 64; ++i) std::fill(img.begin() + l * layer + tbl[i] * pg, img.begin() + l * layer + (tbl[i] + 1) * pg, (uint16_t)0);
+        }
+        TRY(ck.put(img.data(), img.size() * 2)); TRY(cv.put(img.data(), img.size() * 2)); TRY(dt.put(tbl, (size_t)(n_ctx / 64) * 4));
+    } else { TRY(ck.alloc(layer * L * 2)); TRY(cv.alloc(layer * L * 2)); }
+    Q3KvPrefix kp{ck, cv, layer, n_ctx, L, Hkv, hd}; kp.n = 1; kp.P[0] = P; kp.slot[0] = 0;
+    if (tbl) { kp.tbl = dt; kp.tbl_stride = n_ctx / 64; }
+    kp.pk[0] = dk; kp.pv[0] = dv;
+    q3_launch_kv_prefix(kp, nullptr);
+    kp.pk[0] = ok; kp.pv[0] = ov;
+    if (q3_launch_kv_prefix_save(kp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "kv prefix roundtrip hook: the save launch was refused");
+    HK(hipGetLastError()); HK(hipDeviceSynchronize());
+    TRY(ok.get(k_out, store * 2));
+    return ov.get(v_out, store * 2);
+}
+
 // The Predictor's pass A: 2 * n_slots rows — row b at position 0, row n_slots + b at position 1 of slot b — in ONE launch with fused = 2 on an
 // empty cache (k_attend_pair); out rows in the same order
 extern "C" int q3tts_k_attention_pair(int32_t device, const float* qkv, int32_t n_slots, int32_t n_ctx, int32_t Hq, int32_t Hkv, int32_t hd, const float* qnw,
@@ -479,6 +574,19 @@ extern "C" int q3tts_k_attend_pick(int32_t fused, int32_t gqa_ratio, int32_t n_c
         return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attend pick: bad shape");
     Q3Attend a{}; a.hd = Q3_ATT_HD; a.Hkv = n_kv_head; a.Hq = n_kv_head * gqa_ratio; a.fused = fused; a.n_ctx = n_ctx;
     if (n_seg > 0) { a.seg = (const int*)16; a.n_seg = n_seg; a.seg_max_n = seg_max_n; a.seg_max_t = seg_max_t; }  // (never dereferenced: nothing is launched)
+    *kernel = q3_attend_pick(a);
+    return Q3TTS_OK;
+}
+// ... for a launch over a paged cache: *kernel = 15 / 16 / 17 k_attend_paged<1 / 2 / 4, false>, 18 / 19 k_attend_paged<2 / 4, true>,
+// 20 k_attend_gqa2_paged, 21 k_attend_prefill_paged, -1 refused (the Predictor's short-cache and pair launches among them)
+extern "C" int q3tts_k_attend_pick_paged(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t, int32_t n_kv_head,
+                                         int32_t* kernel) {
+    if (!kernel || fused < 0 || fused > 2 || gqa_ratio <= 0 || gqa_ratio > 64 || n_ctx <= 0 || n_seg < 0 || seg_max_n < 0 || seg_max_t < 0 || n_kv_head <= 0 ||
+        n_kv_head > 4096)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attend pick (paged cache): bad shape");
+    Q3Attend a{}; a.hd = Q3_ATT_HD; a.Hkv = n_kv_head; a.Hq = n_kv_head * gqa_ratio; a.fused = fused; a.n_ctx = n_ctx;
+    a.tbl = (const int*)16; a.tbl_stride = (n_ctx + 63) / 64;  // (never dereferenced: nothing is launched)
+    if (n_seg > 0) { a.seg = (const int*)16; a.n_seg = n_seg; a.seg_max_n = seg_max_n; a.seg_max_t = seg_max_t; }
     *kernel = q3_attend_pick(a);
     return Q3TTS_OK;
 }

@@ -270,6 +270,9 @@ struct Q3QkPrep {
     // Q8_0 cache (kv8 = 1; q3_attend_kv8.hip): kc / vc then hold the int8 quants (one byte per element, layouts at q3_kv8_k_off)
     // and kd / vd the f16 block scales, per (slot, kv head) n_ctx * hd / 32 of them
     int kv8; uint16_t* kd; uint16_t* vd;
+    // Paged cache (tbl != null; q3_attend_paged.hip): kc / vc are the layer's page pool [pages][Hkv][64 * hd] bf16 and
+    // tbl[slot * tbl_stride + (pos >> 6)] the page that holds pos. Null: the contiguous cache above, every launch and bit as before.
+    const int* tbl; int tbl_stride;
 };
 int q3_launch_qk_prep(const Q3QkPrep& a, hipStream_t s);  // 0: launched; nonzero: refused (hd != Q3_ATT_HD), nothing launched
 
@@ -293,6 +296,7 @@ struct Q3Attend {
     // seg_max_t = max (pos0 + n). With it (and two query heads per KV head, every n <= 128, every pos0 + n <= 256) one workgroup
     // serves a whole run from LDS: k_attend_prefill
     const int* seg; int n_seg; int seg_max_n; int seg_max_t;
+    const int* tbl; int tbl_stride;  // paged cache, as in Q3QkPrep: q3_launch_attend then takes the kernels of q3_attend_paged.hip
     Q3_STAMP_FIELD
 };
 int q3_launch_attend(const Q3Attend& a, hipStream_t s);  // 0: launched; nonzero: refused (see its definition), nothing launched
@@ -352,6 +356,40 @@ __device__ __forceinline__ void prep_head(const float* src, const float* nw, flo
     if (lane < nl) { c4 = *(const float4*)(cs + i0); s4 = *(const float4*)(sn + i0); }
     prep_rope(y, c4, s4, hl, lane, o);
 }
+// four floats as two bf16 pairs (element i in the low half of word i / 2): 8 bytes of a K / V cache row
+__device__ __forceinline__ uint2 pack_bf16x4(float a, float b, float c, float d) {
+    return make_uint2((uint32_t)q3_bf16(a) | ((uint32_t)q3_bf16(b) << 16), (uint32_t)q3_bf16(c) | ((uint32_t)q3_bf16(d) << 16));
+}
+// where dims 4 lane .. 4 lane + 3 of the key at `pos` live in a head's K cache (khead = kc + hb * hd): chunk lane / 2, half lane & 1
+__device__ __forceinline__ uint16_t* k_cache_elem(uint16_t* khead, int pos, int lane) {
+    const int blk = pos >> 6, kl = pos & 63, c = lane >> 1, e0 = 4 * (lane & 1);
+    return khead + ((size_t)(blk * (Q3_ATT_HD >> 3) + c) * 64 + kl) * 8 + e0;
+}
+// The two chains of the canonical order, one copy for q3_attend.hip and q3_attend_paged.hip.
+// Score: one 16-byte chunk of a key (8 bf16 dims, d ascending) onto the chain s; qa / qb = the query's 8 dims.
+__device__ __forceinline__ float att_dot8(const float4 qa, const float4 qb, const uint4 k, float s) {
+    s = fmaf(qa.x, q3_u2f(k.x << 16), s); s = fmaf(qa.y, q3_u2f(k.x & 0xffff0000u), s);
+    s = fmaf(qa.z, q3_u2f(k.y << 16), s); s = fmaf(qa.w, q3_u2f(k.y & 0xffff0000u), s);
+    s = fmaf(qb.x, q3_u2f(k.z << 16), s); s = fmaf(qb.y, q3_u2f(k.z & 0xffff0000u), s);
+    s = fmaf(qb.z, q3_u2f(k.w << 16), s); s = fmaf(qb.w, q3_u2f(k.w & 0xffff0000u), s);
+    return s;
+}
+// Value: 8 dims of one value row (16 bytes, bf16) times the key's weight pt onto the lane's 8 partial sums.
+__device__ __forceinline__ void att_pv8(float pt, const uint4 v, float o[8]) {
+    o[0] = fmaf(pt, q3_u2f(v.x << 16), o[0]); o[1] = fmaf(pt, q3_u2f(v.x & 0xffff0000u), o[1]);
+    o[2] = fmaf(pt, q3_u2f(v.y << 16), o[2]); o[3] = fmaf(pt, q3_u2f(v.y & 0xffff0000u), o[3]);
+    o[4] = fmaf(pt, q3_u2f(v.z << 16), o[4]); o[5] = fmaf(pt, q3_u2f(v.z & 0xffff0000u), o[5]);
+    o[6] = fmaf(pt, q3_u2f(v.w << 16), o[6]); o[7] = fmaf(pt, q3_u2f(v.w & 0xffff0000u), o[7]);
+}
+// The value step for two heads that share the row (k_attend_gqa2): the row is decoded once, head 0's sums first, then head 1's.
+__device__ __forceinline__ void att_pv8x2(float pa, float pb, const uint4 w, float o0[8], float o1[8]) {
+    const float v0 = q3_u2f(w.x << 16), v1 = q3_u2f(w.x & 0xffff0000u), v2 = q3_u2f(w.y << 16), v3 = q3_u2f(w.y & 0xffff0000u);
+    const float v4 = q3_u2f(w.z << 16), v5 = q3_u2f(w.z & 0xffff0000u), v6 = q3_u2f(w.w << 16), v7 = q3_u2f(w.w & 0xffff0000u);
+    o0[0] = fmaf(pa, v0, o0[0]); o0[1] = fmaf(pa, v1, o0[1]); o0[2] = fmaf(pa, v2, o0[2]); o0[3] = fmaf(pa, v3, o0[3]);
+    o0[4] = fmaf(pa, v4, o0[4]); o0[5] = fmaf(pa, v5, o0[5]); o0[6] = fmaf(pa, v6, o0[6]); o0[7] = fmaf(pa, v7, o0[7]);
+    o1[0] = fmaf(pb, v0, o1[0]); o1[1] = fmaf(pb, v1, o1[1]); o1[2] = fmaf(pb, v2, o1[2]); o1[3] = fmaf(pb, v3, o1[3]);
+    o1[4] = fmaf(pb, v4, o1[4]); o1[5] = fmaf(pb, v5, o1[5]); o1[6] = fmaf(pb, v6, o1[6]); o1[7] = fmaf(pb, v7, o1[7]);
+}
 // The attention output in the form Q3Attend.out_bf16 names, for a lane that holds 1 or 2 consecutive dims of `row` from dim `d` of query
 // head `head` on: f32 rows (0), the O projection's A-tiled bf16 operand (1), W8A8 Q8_0 blocks (2: 32 lanes x 1 / 16 lanes x 2, all active).
 __device__ __forceinline__ void att_out1(const Q3Attend& a, int row, int head, int d, float v) {
@@ -399,7 +437,14 @@ enum { Q3_ATT_REFUSED = -1, Q3_ATT_N1 = 0, Q3_ATT_N2 = 1, Q3_ATT_N4 = 2,   // k_
        Q3_ATT_F2 = 3, Q3_ATT_F4 = 4,                                       // k_attend<2 / 4, true>
        Q3_ATT_GQA2 = 5, Q3_ATT_SMALL2 = 6, Q3_ATT_PAIR = 7, Q3_ATT_PREFILL = 8,
        // the six of q3_attend_kv8.hip (Q3Attend.kv8; q3tts_k_attend_pick_kv8): k_attend_kv8<1 / 2 / 4, false>, k_attend_kv8<2 / 4, true>, k_attend_gqa2_kv8
-       Q3_ATT8_N1 = 9, Q3_ATT8_N2 = 10, Q3_ATT8_N4 = 11, Q3_ATT8_F2 = 12, Q3_ATT8_F4 = 13, Q3_ATT8_GQA2 = 14 };
+       Q3_ATT8_N1 = 9, Q3_ATT8_N2 = 10, Q3_ATT8_N4 = 11, Q3_ATT8_F2 = 12, Q3_ATT8_F4 = 13, Q3_ATT8_GQA2 = 14,
+       // the seven of q3_attend_paged.hip (Q3Attend.tbl; q3tts_k_attend_pick_paged): k_attend_paged<1 / 2 / 4, false>, <2 / 4, true>,
+       // k_attend_gqa2_paged, k_attend_prefill_paged
+       Q3_ATTP_N1 = 15, Q3_ATTP_N2 = 16, Q3_ATTP_N4 = 17, Q3_ATTP_F2 = 18, Q3_ATTP_F4 = 19, Q3_ATTP_GQA2 = 20, Q3_ATTP_PREFILL = 21 };
+// the launches of q3_attend_paged.hip: q3_launch_qk_prep / q3_attend_pick / q3_launch_attend / q3_launch_kv_prefix(_save) hand over when tbl is set
+int q3_launch_qk_prep_paged(const Q3QkPrep& a, hipStream_t s);
+int q3_attend_pick_paged(const Q3Attend& a);
+int q3_launch_attend_paged(const Q3Attend& a, hipStream_t s);
 int q3_attend_pick(const Q3Attend& a);  // the kernel q3_launch_attend takes for a under the current policies (no launch); reads hd, Hq, Hkv,
                                         // fused, n_ctx and the seg fields only
 // Voice prefixes (q3tts_prefix): copy a prefix store into slots before their prefill. A store is laid out as one slot's cache of
@@ -414,8 +459,13 @@ struct Q3KvPrefix {
     // store then is k / v [L][Hkv][np * hd] int8 followed by its scales [L][Hkv][np * hd / 32] f16 in the same allocation: pk / pv name the
     // quants. Whole key blocks (quants and scales) are copied for K, positions < P for V.
     int kv8; uint16_t* kd; uint16_t* vd;
+    // Paged cache (tbl != null): kc / vc are the page pool, layer_stride its per-layer elements, and slot[j]'s positions go through
+    // tbl[slot[j] * tbl_stride + block]. The store keeps its contiguous form.
+    const int* tbl; int tbl_stride;
 };
 void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s);
+int q3_launch_kv_prefix_paged(const Q3KvPrefix& a, hipStream_t s);       // (q3_attend_paged.hip; nonzero: refused — bf16 only, hd = Q3_ATT_HD)
+int q3_launch_kv_prefix_save_paged(const Q3KvPrefix& a, hipStream_t s);
 void q3_launch_kv_prefix_kv8(const Q3KvPrefix& a, hipStream_t s);  // (q3_attend_kv8.hip; q3_launch_kv_prefix hands over when kv8 is set)
 // The other direction (k_kv_prefix_save / k_kv_prefix_save_kv8): positions < P[j] of slot[j] into the store pk[j] / pv[j] (written, though
 // the struct names them const), which must come zero-filled: the result is byte for byte the store q3tts_prefix_create makes of the same

@@ -101,6 +101,7 @@ int q3_run_layers(q3tts_engine* e, const Q3Tfm& t, const Q3Rows& r, const Q3Laye
         qp.qnw = t.qn[l]; qp.knw = t.kn[l]; qp.eps = eps; qp.cs = t.cs; qp.sn = t.sn;
         q3_layer_cache(c, l, &qp.kc, &qp.vc, &qp.kd, &qp.vd); qp.kv8 = c.kv8 ? 1 : 0;  // (kv_q8_0: quants + scales, and the kernels of q3_attend_kv8.hip)
         qp.n_ctx = c.n_ctx; qp.row_pos = a.row_pos; qp.row_slot = a.row_slot;
+        qp.tbl = c.tbl; qp.tbl_stride = c.tbl_stride;  // (kv_pages: the page table, and the kernels of q3_attend_paged.hip)
         qp.slot_mod = a.slot_mod; qp.pos_const = a.pos_const;
         const bool fused = a.one_row_per_slot && t.Hq / t.Hkv >= 2;
         // the Predictor's pass A: rows [0, B) at position 0 and [B, 2B) at position 1 of an empty per-frame cache: one fused launch
@@ -108,6 +109,7 @@ int q3_run_layers(q3tts_engine* e, const Q3Tfm& t, const Q3Rows& r, const Q3Laye
         if (!fused && !pair) bad += q3_launch_qk_prep(qp, s) ? 1 : 0;
         Q3Attend at{}; at.qkv = sc.qkv; at.ld = t.nqkv; at.rows = a.rows; at.out = (float*)sc.att; at.ldo = t.nq; at.Hq = t.Hq; at.Hkv = t.Hkv; at.hd = t.hd;
         at.kc = qp.kc; at.vc = qp.vc; at.kv8 = qp.kv8; at.kd = qp.kd; at.vd = qp.vd; at.n_ctx = c.n_ctx; at.row_pos = a.row_pos; at.row_slot = a.row_slot;
+        at.tbl = c.tbl; at.tbl_stride = c.tbl_stride;
         at.fused = pair ? 2 : (fused ? 1 : 0); at.prep = qp; at.out_bf16 = 1; at.slot_mod = a.slot_mod; at.pos_const = a.pos_const;
         if (t.a8) { at.out_bf16 = 2; at.out_scale = sc.asc_att; at.out_rt16 = sc.rt16; }
         if (!fused && !pair && a.n_seg > 0) { at.seg = a.seg; at.n_seg = a.n_seg; at.seg_max_n = a.seg_max_n; at.seg_max_t = a.seg_max_t; }  // prefill of whole prompts (prefill_layers): the launch's rows as per-slot runs

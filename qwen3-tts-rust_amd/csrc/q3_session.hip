@@ -373,6 +373,7 @@ void free_slot(q3tts_session* s, int b) {
     SSlot& sl = s->slots[b];
     sl.req.reset(); sl.ts = false; sl.parked = false; sl.paced = false;
     s->e->ts_slot[b] = 0;
+    q3_kvp_release(s->e, b);  // (paged cache: done, EOS, cancel or error — the pages go back with the slot)
     s->evict_stuck = false;
 }
 
@@ -460,7 +461,7 @@ void text_now(q3tts_session* s, uint64_t id, int t_up, TextNow& t) {
 void collect(q3tts_session* s, Boundary& bd) {
     q3tts_engine* e = s->e;
     const int B = e->B;
-    int nfree = 0;
+    int nfree = 0, pages = q3_kvp_avail(e);
     for (int b = 0; b < B; ++b) if (!s->slots[b].req) ++nfree;
     std::lock_guard<std::mutex> lk(s->mu);
     // credits first: a swapped-out request whose rule holds again takes a free slot ahead of the queue's head
@@ -491,6 +492,8 @@ void collect(q3tts_session* s, Boundary& bd) {
         const int xs = x && x->e == e ? x->state.load(std::memory_order_acquire) : 1;
         if (xs == 0) break;
         if (xs == 1 && nfree <= 0) break;
+        // paged cache: the head waits for its pages as it waits for a slot (a prefix job for those of its voice rows)
+        if (xs == 1 && !q3_kvp_fits(e, f.kind == 1 ? q3_kvp_need(e, nullptr, f.embd.empty() ? &f.desc : nullptr, f.n_tok) : q3_kvp_need(e, &f.r, nullptr, 0), &pages)) break;
         const bool own = f.doc == nullptr;  // (a document's entries are internal: no IdState)
         if (own) s->ids[f.id].queued = false;
         unref_prefix(s, x);
@@ -1467,6 +1470,7 @@ extern "C" int q3tts_session_set_swap(q3tts_session* s, int64_t arena_bytes) {
     if (s->next_id != 1) return serr(s, Q3TTS_ERR_STATE, "set_swap: valid before the first submission only");
     if (s->stop || s->dead) return serr(s, Q3TTS_ERR_STATE, "set_swap: the session is closing, or its worker failed");
     if (arena_bytes < 0) return serr(s, Q3TTS_ERR_INVALID, "set_swap: arena_bytes is negative (0 turns swapping off)");
+    if (s->e->kvp_total) return serr(s, Q3TTS_ERR_UNSUPPORTED, "set_swap: this engine's cache is paged (q3tts_engine_options.kv_pages); swap blocks are laid out for the contiguous cache");
     q3tts_engine* e = s->e;
     if (Q3Swap* old = s->swap.exchange(nullptr)) q3_swap_destroy(e, old);
     if (arena_bytes == 0) return Q3TTS_OK;

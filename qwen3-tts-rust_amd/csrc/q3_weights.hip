@@ -298,6 +298,11 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
     Q3KvCache& c = t.cache; c.n_ctx = sh.n_ctx; c.n_slots = sh.n_slots;
     c.layer_stride = (size_t)c.n_slots * t.Hkv * c.n_ctx * hd;
     c.kv8 = sh.kv8 != 0;
+    if (sh.kv_pages > 0) {  // paged: a pool of kv_pages + 1 pages per layer (page 0 stays zero) and the slots' table, all zero = nothing owned
+        c.n_pages = sh.kv_pages; c.tbl_stride = c.n_ctx / 64;
+        c.layer_stride = (size_t)(c.n_pages + 1) * t.Hkv * 64 * hd;
+        TRY(q3_dalloc(e, &c.tbl, (size_t)c.n_slots * c.tbl_stride));
+    }
     if (c.kv8) {  // Q8_0 cache: per element one byte of quants + 1/16 byte of f16 block scales, the scales behind the quants in one allocation
         int8_t *kq = nullptr, *vq = nullptr;
         const size_t nq = c.layer_stride * L;

@@ -167,7 +167,7 @@ class CloneConfig(C.Structure):
 # every symbol include/q3tts.h declares (tests check the export list against the header text)
 class EngineOptions(C.Structure):
     """q3tts_engine_options: what q3tts_engine_create_opts takes beyond the config (zero = q3tts_engine_create)."""
-    _fields_ = [("struct_size", C.c_uint32), ("kquant_resident", C.c_int32)]
+    _fields_ = [("struct_size", C.c_uint32), ("kquant_resident", C.c_int32), ("kv_pages", C.c_int32)]
 
 
 SYMBOLS = [
@@ -189,6 +189,8 @@ SYMBOLS = [
     "q3tts_session_append_text", "q3tts_k_text_ready",
     "q3tts_k_attention_runs", "q3tts_k_attention_decode_ex", "q3tts_k_attention_pair", "q3tts_k_attend_pick",
     "q3tts_k_attention_runs_kv8", "q3tts_k_attention_decode_kv8", "q3tts_k_attend_pick_kv8",
+    "q3tts_k_attention_runs_paged", "q3tts_k_attention_decode_paged", "q3tts_k_attend_pick_paged", "q3tts_k_kv_prefix_roundtrip",
+    "q3tts_get_kv_pages", "q3tts_k_kv_pages_shuffle",
     "q3tts_k_pred_table_row", "q3tts_k_pred_next", "q3tts_k_attention_gather",
     "q3tts_k_row_buckets", "q3tts_k_bucket_steps", "q3tts_k_device_bytes", "q3tts_k_engine_footprint", "q3tts_k_prefix_stats",
     "q3tts_session_prefix_create", "q3tts_session_submit_keep_voice", "q3tts_session_prefix_release", "q3tts_session_clone",
@@ -391,6 +393,15 @@ def load_library(path=None):
     lib.q3tts_k_attention_decode_kv8.argtypes = [C.c_int32, f32p, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float,
                                                  C.c_float, i32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.q3tts_k_attend_pick_kv8.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
+    lib.q3tts_k_attention_runs_paged.argtypes = lib.q3tts_k_attention_runs.argtypes + [C.c_int32, i32p, C.c_uint16]
+    lib.q3tts_k_attention_decode_paged.argtypes = [C.c_int32, f32p, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float,
+                                                   C.c_float, i32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_int32, i32p, C.c_uint16]
+    lib.q3tts_k_attend_pick_paged.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
+    lib.q3tts_k_kv_prefix_roundtrip.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, C.c_uint16,
+                                                C.c_void_p, C.c_void_p]
+    lib.q3tts_get_kv_pages.argtypes = [vp, C.POINTER(C.c_int64)]
+    lib.q3tts_k_kv_pages_shuffle.argtypes = [vp, C.c_uint64]
     lib.q3tts_k_pred_table_row.argtypes = [vp, C.c_int32, C.c_int32, f32p]
     lib.q3tts_k_pred_next.argtypes = [C.c_int32, C.POINTER(PredStep), C.c_void_p, C.c_void_p, C.c_void_p]
     lib.q3tts_k_attention_gather.argtypes = [C.c_int32, C.POINTER(PredStep), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

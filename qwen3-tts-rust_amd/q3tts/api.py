@@ -124,8 +124,11 @@ class TtsEngine:
     """src/tts/engine.rs:53-72 — the engine owns weights, contexts and speakers; one utterance at a time per call
     (`&mut self`), or a list through `generate_batch_with_voice` (continuous batching, an extension)."""
 
-    def __init__(self, cfg, tokenizer=None, kquant_resident=False):
-        self._native = native.NativeEngine(cfg, kquant_resident=True) if kquant_resident else native.NativeEngine(cfg)
+    def __init__(self, cfg, tokenizer=None, kquant_resident=False, kv_pages=0):
+        if kv_pages:
+            self._native = native.NativeEngine(cfg, kquant_resident=bool(kquant_resident), kv_pages=kv_pages)
+        else:
+            self._native = native.NativeEngine(cfg, kquant_resident=True) if kquant_resident else native.NativeEngine(cfg)
         self.cfg = cfg
         self.tokenizer = tokenizer
         self.speakers = {}
@@ -134,7 +137,7 @@ class TtsEngine:
 
     @classmethod
     def new(cls, model_dir: Optional[str] = None, quant: str = "none", config=None, max_batch: Optional[int] = None,
-            kv_cache: Optional[str] = None, kquant_resident: bool = False):
+            kv_cache: Optional[str] = None, kquant_resident: bool = False, kv_pages: int = 0):
         """TtsEngine::new(model_dir, quant) (src/tts/engine.rs:84-169). With no config the model's shape comes from the GGUF files of the
         quant directory (q3tts_config_from_model_dir), whatever member of the family it holds; a config given by the caller is used as it
         is (its shapes must match the files) and is not modified. The vocoder's trained weights and shape come the same way from
@@ -149,7 +152,10 @@ class TtsEngine:
         (q3tts_engine_config.kv_q8_0 = 1: 0.53 of the memory; the results are not the bf16 cache's). Anything else: ValueError.
         kquant_resident: Q4_K / Q5_K / Q6_K tensors of the quant directory (quant = "q5_k_m") stay quantised on the device and are decoded
         inside the GEMM (q3tts_engine_options.kquant_resident): the same results bit for bit in about a third of the weight bytes;
-        weight_formats says what each form holds. Opt-in: the default converts them to bf16 at load."""
+        weight_formats says what each form holds. Opt-in: the default converts them to bf16 at load.
+        kv_pages: N >= 1 pages the Talker's bf16 K/V cache (q3tts_engine_options.kv_pages): one pool of N pages of 64 positions for all
+        slots — (N + 1) * 2 * t_n_layer * t_n_kv_head * 64 * head_dim * 2 bytes — in place of n_ctx positions per slot; the results are the
+        contiguous cache's bit for bit, a request waits while the pool cannot cover its prompt + max_steps. Not with kv_cache = "q8_0"."""
         if kv_cache not in (None, "bf16", "q8_0"):
             raise ValueError(f"kv_cache must be None, 'bf16' or 'q8_0', not {kv_cache!r}")
         wdir = None
@@ -178,7 +184,7 @@ class TtsEngine:
             missing = native.CLONE_FILES[0 if clone_files[0] is None else 1]
             raise _abi.Q3Error(f"{missing} not found in {wdir} or in {model_dir}: the clone encoders need both files "
                                f"(found {clone_files[0] or clone_files[1]})")
-        eng = cls(cfg, tok, kquant_resident=kquant_resident)
+        eng = cls(cfg, tok, kquant_resident=kquant_resident, kv_pages=kv_pages)
         if clone_files[0] is not None:
             try:
                 eng._native.clone_load(wdir)
@@ -204,6 +210,11 @@ class TtsEngine:
     def weight_formats(self):
         """The decoder matrices' device bytes by the form they are held in: {"bf16", "q4_k", "q5_k", "q6_k"}."""
         return self._native.weight_formats
+
+    @property
+    def kv_pages(self):
+        """(total, free, peak in use) pages of the paged K/V pool (kv_pages=N at creation); (0, 0, 0) with the contiguous cache."""
+        return self._native.kv_pages
 
     @property
     def vocoder_is_synthetic(self) -> bool:

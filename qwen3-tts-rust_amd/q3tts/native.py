@@ -80,20 +80,37 @@ class GenResult:
 class NativeEngine:
     """q3tts_engine handle. One engine per GPU; not re-entrant (same contract as `&mut self`)."""
 
-    def __init__(self, cfg, kquant_resident=False):
+    def __init__(self, cfg, kquant_resident=False, kv_pages=0):
         """kquant_resident: q3tts_engine_options.kquant_resident — Q4_K / Q5_K / Q6_K tensors of cfg.weights_path stay quantised on the
-        device and are decoded inside the GEMM (same bits as the default; fewer bytes)."""
+        device and are decoded inside the GEMM (same bits as the default; fewer bytes).
+        kv_pages: q3tts_engine_options.kv_pages — N >= 1 pages the Talker's K/V cache: a pool of N pages of 64 positions shared by all
+        slots instead of n_ctx positions per slot (same bits; requests wait for pages as they wait for a slot)."""
         self.lib = _abi.load_library()
         self.cfg = cfg
         self.h = C.c_void_p()
         self._prefixes = weakref.WeakSet()  # destroyed before the engine
-        if kquant_resident:
-            opts = _abi.EngineOptions(C.sizeof(_abi.EngineOptions), 1)
+        if kquant_resident or kv_pages:
+            opts = _abi.EngineOptions(C.sizeof(_abi.EngineOptions), 1 if kquant_resident else 0, int(kv_pages))
             rc = self.lib.q3tts_engine_create_opts(C.byref(cfg), C.byref(opts), C.byref(self.h))
         else:
             rc = self.lib.q3tts_engine_create(C.byref(cfg), C.byref(self.h))
         if rc != 0:
             raise _abi.Q3Error(f"q3tts_engine_create failed ({rc}): {self.lib.q3tts_last_error(None).decode()}")
+
+    @property
+    def kv_pages(self):
+        """q3tts_get_kv_pages: (total, free, peak in use) pages of a paged engine's pool; (0, 0, 0) on a contiguous one."""
+        return self.kv_pages_stats()[:3]
+
+    def kv_pages_stats(self):
+        """q3tts_get_kv_pages, all four: (total, free, peak in use, bytes of one page over every layer and head, K and V)."""
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.q3tts_get_kv_pages(self.h, out), "q3tts_get_kv_pages")
+        return tuple(int(v) for v in out)
+
+    def kv_pages_shuffle(self, seed):
+        """q3tts_k_kv_pages_shuffle (test hook): permute the free list; refused while any page is out."""
+        self._check(self.lib.q3tts_k_kv_pages_shuffle(self.h, int(seed)), "q3tts_k_kv_pages_shuffle")
 
     @property
     def weight_formats(self):
@@ -1236,8 +1253,16 @@ def _dp(a):
     return None if a is None else a.ctypes.data
 
 
+def _paged_args(paged, n_slots, n_ctx):
+    """(n_pages, tbl [n_slots][n_ctx / 64], fill) as the _paged hooks take them; the table array is returned too (it must outlive the call)."""
+    n_pages, tbl, fill = paged
+    tbl = np.ascontiguousarray(tbl, dtype=np.int32)
+    assert tbl.shape == (n_slots, n_ctx // 64)
+    return tbl, (int(n_pages), _ptr(tbl, i32p), int(fill))
+
+
 def k_attention_runs(qkv, runs, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, policy=-1, out_form=0,
-                     want_cache=True, device=0):
+                     want_cache=True, device=0, paged=None):
     """q3tts_k_attention_runs: runs = [(pos0, n), ...], one slot each; qkv holds every run's pos0 + n rows back to back. Returns a dict:
     out [sum n][n_head * head_dim] in the form asked for (f32 / bf16 bits / int8 with `scale`), k_cache / v_cache bf16 bits
     [run][n_kv_head][n_ctx][head_dim]."""
@@ -1250,16 +1275,19 @@ def k_attention_runs(qkv, runs, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_
     kn = np.ascontiguousarray(k_norm_w, dtype=np.float32)
     sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
     out, sc, kc, vc = _att_hook_out(max(int(nn.sum()), 1), n_head * head_dim, out_form, len(runs), n_kv_head, n_ctx, head_dim, want_cache)
-    rc = lib.q3tts_k_attention_runs(device, _ptr(qkv, f32p), len(runs), _ptr(nn, i32p), _ptr(p0, i32p), n_ctx, n_head, n_kv_head, head_dim,
-                                    _ptr(qn, f32p), _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, out_form,
-                                    _dp(out), _dp(sc), _dp(kc), _dp(vc))
+    # paged = (n_pages, tbl, fill): q3tts_k_attention_runs_paged — the same launch over a page pool and the caller's table
+    tbl, extra = _paged_args(paged, len(runs), n_ctx) if paged else (None, ())
+    fn = lib.q3tts_k_attention_runs_paged if paged else lib.q3tts_k_attention_runs
+    rc = fn(device, _ptr(qkv, f32p), len(runs), _ptr(nn, i32p), _ptr(p0, i32p), n_ctx, n_head, n_kv_head, head_dim,
+            _ptr(qn, f32p), _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, out_form,
+            _dp(out), _dp(sc), _dp(kc), _dp(vc), *extra)
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_attention_runs failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return _att_hook_ret(out, sc, kc, vc)
 
 
 def k_attention_decode_ex(qkv, lens, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, policy=-1,
-                          row_indexed=False, out_form=0, want_cache=True, device=0):
+                          row_indexed=False, out_form=0, want_cache=True, device=0, paged=None):
     """q3tts_k_attention_decode_ex: k_attention_decode with one output form per call, the cache, and the Predictor's row-indexed addressing.
     Returns the dict of k_attention_runs with out [n_slots][n_head * head_dim]."""
     lib = _abi.load_library()
@@ -1270,12 +1298,45 @@ def k_attention_decode_ex(qkv, lens, n_ctx, n_head, n_kv_head, head_dim, q_norm_
     kn = np.ascontiguousarray(k_norm_w, dtype=np.float32)
     sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
     out, sc, kc, vc = _att_hook_out(max(ln.size, 1), n_head * head_dim, out_form, ln.size, n_kv_head, n_ctx, head_dim, want_cache)
-    rc = lib.q3tts_k_attention_decode_ex(device, _ptr(qkv, f32p), ln.size, _ptr(ln, i32p), n_ctx, n_head, n_kv_head, head_dim, _ptr(qn, f32p),
-                                         _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy,
-                                         1 if row_indexed else 0, out_form, _dp(out), _dp(sc), _dp(kc), _dp(vc))
+    if paged:  # (n_pages, tbl, fill): q3tts_k_attention_decode_paged (no row-indexed form: the Predictor's cache is not paged)
+        tbl, extra = _paged_args(paged, ln.size, n_ctx)
+        rc = lib.q3tts_k_attention_decode_paged(device, _ptr(qkv, f32p), ln.size, _ptr(ln, i32p), n_ctx, n_head, n_kv_head, head_dim, _ptr(qn, f32p),
+                                                _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, out_form,
+                                                _dp(out), _dp(sc), _dp(kc), _dp(vc), *extra)
+    else:
+        rc = lib.q3tts_k_attention_decode_ex(device, _ptr(qkv, f32p), ln.size, _ptr(ln, i32p), n_ctx, n_head, n_kv_head, head_dim, _ptr(qn, f32p),
+                                             _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy,
+                                             1 if row_indexed else 0, out_form, _dp(out), _dp(sc), _dp(kc), _dp(vc))
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_attention_decode_ex failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return _att_hook_ret(out, sc, kc, vc)
+
+
+def k_kv_prefix_roundtrip(k_store, v_store, P, n_ctx, paged=None, device=0):
+    """q3tts_k_kv_prefix_roundtrip: the stores [L][n_kv_head][ceil(P / 64) * 64 * 128] (bf16 bits) into slot 0 of a cache of n_ctx positions
+    and the slot's first P positions back into zero-filled stores, which are returned. paged = (n_pages, tbl [n_ctx / 64], fill) or None."""
+    lib = _abi.load_library()
+    ks = np.ascontiguousarray(k_store, dtype=np.uint16)
+    vs = np.ascontiguousarray(v_store, dtype=np.uint16)
+    L, Hkv = ks.shape[0], ks.shape[1]
+    assert ks.shape == vs.shape == (L, Hkv, ((P + 63) // 64) * 64 * 128)
+    ko, vo = np.zeros_like(ks), np.zeros_like(vs)
+    tbl, extra = _paged_args((paged[0], np.asarray(paged[1]).reshape(1, -1), paged[2]), 1, n_ctx) if paged else (None, (0, None, 0))
+    rc = lib.q3tts_k_kv_prefix_roundtrip(device, _dp(ks), _dp(vs), L, Hkv, P, n_ctx, *extra, _dp(ko), _dp(vo))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_kv_prefix_roundtrip failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return ko, vo
+
+
+def k_attend_pick_paged(fused, gqa_ratio, n_ctx, n_seg=0, seg_max_n=0, seg_max_t=0, n_kv_head=8):
+    """q3tts_k_attend_pick_paged (host only): the number of the kernel of csrc/q3_attend_paged.hip the launcher takes for a launch over a
+    paged cache under the current policies (15 .. 21), or -1 for a launch it refuses."""
+    lib = _abi.load_library()
+    k = C.c_int32(-2)
+    rc = lib.q3tts_k_attend_pick_paged(fused, gqa_ratio, n_ctx, n_seg, seg_max_n, seg_max_t, n_kv_head, C.byref(k))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_attend_pick_paged failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return int(k.value)
 
 
 def k_attention_pair(qkv, n_slots, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, out_form=0,

@@ -23,7 +23,7 @@ pub struct q3tts_vocoder_config {
     pub lookahead_frames: i32, pub sample_rate: i32,
 }
 #[repr(C)]
-pub struct q3tts_engine_options { pub struct_size: u32, pub kquant_resident: i32 }
+pub struct q3tts_engine_options { pub struct_size: u32, pub kquant_resident: i32, pub kv_pages: i32 }
 #[repr(C)]
 pub struct q3tts_engine_config {
     pub model: q3tts_model_config, pub vocoder: q3tts_vocoder_config,
@@ -112,6 +112,8 @@ extern "C" {
     pub fn q3tts_engine_create(cfg: *const q3tts_engine_config, out: *mut *mut q3tts_engine) -> c_int;
     // q3tts_engine_create with options ({struct_size, kquant_resident}: K-quant tensors stay quantised on the device; NULL = q3tts_engine_create)
     pub fn q3tts_engine_create_opts(cfg: *const q3tts_engine_config, opts: *const q3tts_engine_options, out: *mut *mut q3tts_engine) -> c_int;
+    // paged Talker K/V cache (q3tts_engine_options.kv_pages >= 1): out = [pages in the pool, free, peak in use, bytes per page]
+    pub fn q3tts_get_kv_pages(e: *const q3tts_engine, out: *mut i64) -> c_int;
     // the decoder matrices' device bytes held as bf16, Q4_K, Q5_K, Q6_K
     pub fn q3tts_get_weight_formats(e: *const q3tts_engine, out: *mut i64) -> c_int;
     pub fn q3tts_engine_destroy(e: *mut q3tts_engine);
