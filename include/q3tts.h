@@ -92,7 +92,10 @@ typedef struct q3tts_engine_config {
     int32_t max_batch;     /* concurrent utterance slots, 1..Q3TTS_MAX_BATCH (256). Results do not depend on it. Device memory per slot:
                             *   Talker KV  2 * t_n_layer * t_n_kv_head * t_head_dim * n_ctx * 2 B  (470 MB at the 1.7B shape with n_ctx = 4096:
                             *              256 slots need a smaller n_ctx, e.g. 1024: 117 MB per slot, 30 GB); with kv_q8_0 = 1
-                            *              2 * t_n_layer * t_n_kv_head * n_ctx * (t_head_dim + 2 * t_head_dim / 32) B (250 MB at n_ctx = 4096)
+                            *              2 * t_n_layer * t_n_kv_head * n_ctx * (t_head_dim + 2 * t_head_dim / 32) B (250 MB at n_ctx = 4096);
+                            *              with q3tts_engine_options.kv_type_k / kv_type_v t_n_layer * t_n_kv_head * n_ctx * (bytes(k) + bytes(v)) B,
+                            *              bytes(Q8_0) = t_head_dim + 2 * t_head_dim / 32, bytes(Q4_0) = t_head_dim / 2 + 2 * t_head_dim / 32
+                            *              (Q8_0 / Q4_0: 191 MB, Q4_0 / Q4_0: 132 MB at n_ctx = 4096)
                             *   Predictor cache  2 * p_n_layer * p_n_kv_head * p_head_dim * 64 * 2 B
                             *   codes, Talker draws  max_steps_cap * (n_codebooks + 1) * 4 B;  Predictor draws (prng)  max_steps_cap *
                             *              (n_codebooks - 1) * 4 B;  seen codes  ceil(sample_limit / 32) * 4 B
@@ -246,8 +249,25 @@ int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine** out);
  * (q3tts_generate_batch, sessions, a session's prefix jobs). Ids, logits and PCM are those of the contiguous cache bit for bit.
  * Q3TTS_ERR_INVALID (the message names both settings): kv_pages with kv_q8_0 = 1; kv_pages < n_ctx / 64 (every request the engine
  * accepts fits the pool: what would need more pages exceeds n_ctx and is refused as such). q3tts_session_set_swap on a paged engine:
- * Q3TTS_ERR_UNSUPPORTED. The Predictor's per-frame cache is never paged. struct_size may be that of the struct without kv_pages. */
-typedef struct { uint32_t struct_size; int32_t kquant_resident; int32_t kv_pages; } q3tts_engine_options;
+ * Q3TTS_ERR_UNSUPPORTED. The Predictor's per-frame cache is never paged. struct_size may be that of the struct without kv_pages.
+ * kv_type_k / kv_type_v (0, 0: what q3tts_engine_config.kv_q8_0 says): the Talker's K/V cache with ggml Q4_0 blocks (csrc/q3_attend_kv4.hip,
+ * DESIGN.md section 32). Accepted pairs: (Q3TTS_KV_Q8_0, Q3TTS_KV_Q4_0) — llama.cpp's --cache-type-k q8_0 --cache-type-v q4_0, values
+ * tolerate four bits better than keys — and (Q3TTS_KV_Q4_0, Q3TTS_KV_Q4_0). Per-slot memory becomes
+ *   t_n_layer * t_n_kv_head * n_ctx * (bytes(kv_type_k) + bytes(kv_type_v)), bytes(Q8_0) = t_head_dim + 2 * t_head_dim / 32,
+ *   bytes(Q4_0) = t_head_dim / 2 + 2 * t_head_dim / 32: 0.41 and 0.28 of bf16 (kv_q8_0 = 1: 0.53).
+ * Blocks are those of kv_q8_0 (32 consecutive dims of one (position, KV head) vector; keys after q/k-norm and RoPE, values from the raw
+ * f32 row). Quantiser of a Q4_0 block: ggml's quantize_row_q4_0 in f32 — max = the element of largest magnitude with its sign (the first
+ * such in dim order), d = max / -8, id = d ? 1 / d : 0, q = min(15, (int)(x * id + 8.5f)), d stored as f16; a zero block has d = -0 (what
+ * 0 / -8 is) and every q = 8. The cached value is x^ = f32(d) * float(q - 8), exact in f32, and everything kv_q8_0 says of its arithmetic
+ * rule holds with this x^: the canonical order of DESIGN.md section 4.4, the newest key and value taking part as x^, the same bits from
+ * every kernel variant, for every batch, slot count, session and voice prefix. The Q8_0 K beside a Q4_0 V is kv_q8_0's K bit for bit. The
+ * results are those of neither the bf16 nor the Q8_0 cache, and parity with llama.cpp's flash-attention order is not pinned. Voice
+ * prefixes are stored in the cache's form. Q3TTS_ERR_INVALID (the message names the fields): any other pair; together with kv_pages;
+ * together with kv_q8_0 = 1 (ambiguous). q3tts_session_set_swap on such an engine: Q3TTS_ERR_UNSUPPORTED (swap blocks are laid out for
+ * bf16 and Q8_0). struct_size may be that of the struct without these two. */
+#define Q3TTS_KV_Q4_0 2   /* (ggml's type numbers) */
+#define Q3TTS_KV_Q8_0 8
+typedef struct { uint32_t struct_size; int32_t kquant_resident; int32_t kv_pages; int32_t kv_type_k; int32_t kv_type_v; } q3tts_engine_options;
 int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3tts_engine_options* opts, q3tts_engine** out);
 /* The paged cache's pool: out[0] pages it can hand out (kv_pages; 0 = the cache is contiguous), out[1] free now, out[2] the most in use at
  * once since creation, out[3] bytes of one page over every layer and KV head, K and V. Call from the thread that drives the engine. */
@@ -850,6 +870,26 @@ int q3tts_k_attention_decode_kv8(int32_t device, const float* qkv, int32_t n_slo
                                  int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
                                  float rope_theta, const int32_t* mrope_sections, int32_t policy, int32_t out_form, void* out,
                                  float* out_scale, int8_t* k_q, int8_t* v_q, uint16_t* k_d, uint16_t* v_d);
+/* ---- the same over a cache with Q4_0 blocks (q3tts_engine_options.kv_type_k / kv_type_v; csrc/q3_attend_kv4.hip) ----
+ * The two _kv8 hooks with the cache's types named: (Q3TTS_KV_Q8_0, Q3TTS_KV_Q4_0) or (Q3TTS_KV_Q4_0, Q3TTS_KV_Q4_0), anything else is
+ * Q3TTS_ERR_INVALID. The cache comes back un-blocked in the same shapes, one int8 per element: a Q8_0 quant as it is, a Q4_0 quant as
+ * its nibble 0 .. 15 (the cached value is f16(d) * (q - 8)). q3tts_k_attend_pick_kv4 (host only): *kernel = 22 / 23 / 24:
+ * k_attend_kv4<1 / 2 / 4, false>; 25 / 26: k_attend_kv4<2 / 4, true>; 27: k_attend_gqa2_kv4 (each in the instance of kv_type_k); -1: refused
+ * (fused = 2, a fused launch with one query head per KV head). q3tts_k_kv_prefix_roundtrip_kv4: q3tts_k_kv_prefix_roundtrip for such a
+ * cache — the stores are bytes, [L][n_kv_head][np * bytes per position] quants then [L][n_kv_head][np * 4] f16 scales, np = ceil(P / 64)
+ * * 64, head_dim 128; k_bytes / v_bytes must be their exact sizes. */
+int q3tts_k_attention_runs_kv4(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx,
+                               int32_t n_head, int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
+                               float rope_theta, const int32_t* mrope_sections, int32_t policy, int32_t out_form, void* out, float* out_scale,
+                               int32_t kv_type_k, int32_t kv_type_v, int8_t* k_q, int8_t* v_q, uint16_t* k_d, uint16_t* v_d);
+int q3tts_k_attention_decode_kv4(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t n_head,
+                                 int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
+                                 float rope_theta, const int32_t* mrope_sections, int32_t policy, int32_t out_form, void* out,
+                                 float* out_scale, int32_t kv_type_k, int32_t kv_type_v, int8_t* k_q, int8_t* v_q, uint16_t* k_d, uint16_t* v_d);
+int q3tts_k_attend_pick_kv4(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t,
+                            int32_t n_kv_head, int32_t kv_type_k, int32_t kv_type_v, int32_t* kernel);
+int q3tts_k_kv_prefix_roundtrip_kv4(int32_t device, const void* k_store, const void* v_store, int64_t k_bytes, int64_t v_bytes, int32_t n_layer,
+                                    int32_t n_kv_head, int32_t P, int32_t n_ctx, int32_t kv_type_k, int32_t kv_type_v, void* k_out, void* v_out);
 /* q3tts_k_attention_runs / q3tts_k_attention_decode_ex (without row_indexed) over a PAGED cache (csrc/q3_attend_paged.hip): a pool of
  * n_pages + 1 pages and the caller's table tbl [n_runs or n_slots][n_ctx / 64] (entries 0 .. n_pages, 0 = the zero page). Page 0 and the
  * pages the table names start as zeros, every other page filled with the bf16 pattern `fill`. Outputs as the contiguous hooks'; the

@@ -276,15 +276,15 @@ static int admit_group_run(q3tts_engine* e, std::vector<Adm>& grp, int total) {
 }
 
 // bytes of one of a prefix's two stores of np positions, in the slots' format: bf16, or Q8_0 quants with their f16 scales behind them
-size_t q3_prefix_store_bytes(const q3tts_engine* e, int np) {
+size_t q3_prefix_store_bytes(const q3tts_engine* e, int np, int v) {
     const size_t per = (size_t)e->T.L * e->T.Hkv * np * e->T.hd;
-    return e->T.cache.kv8 ? per + per / 16 : per * 2;
+    return e->T.cache.kv8 ? q3_kv4_bytes(e->T.cache.kv4, v, per) + per / 16 : per * 2;
 }
 // x's store seen as a K/V cache: one slot of np positions; Q8_0: the scales follow the L layers of quants in the same allocation
 static Q3KvCache prefix_cache_view(const Q3Tfm& t, const q3tts_prefix* x) {
     Q3KvCache c;
-    c.kc = x->k; c.vc = x->v; c.layer_stride = (size_t)t.Hkv * x->np * t.hd; c.n_ctx = x->np; c.n_slots = 1; c.kv8 = t.cache.kv8;
-    if (c.kv8) { const size_t quants = t.L * c.layer_stride; c.kd = (uint16_t*)((int8_t*)x->k + quants); c.vd = (uint16_t*)((int8_t*)x->v + quants); }
+    c.kc = x->k; c.vc = x->v; c.layer_stride = (size_t)t.Hkv * x->np * t.hd; c.n_ctx = x->np; c.n_slots = 1; c.kv8 = t.cache.kv8; c.kv4 = t.cache.kv4;
+    if (c.kv8) { const size_t quants = t.L * c.layer_stride; c.kd = (uint16_t*)((int8_t*)x->k + q3_kv4_bytes(c.kv4, 0, quants)); c.vd = (uint16_t*)((int8_t*)x->v + q3_kv4_bytes(c.kv4, 1, quants)); }
     return c;
 }
 // the zero-filled store of a prefix that a slot's first `rows` positions will be saved into (k_kv_prefix_save)
@@ -294,13 +294,13 @@ static int prefix_store_alloc(q3tts_engine* e, q3tts_prefix* x, int rows) {
     const int np = (rows + 63) & ~63;
     const size_t store = q3_prefix_store_bytes(e, np);
     int rc = q3_dev_alloc_zeroed(e, (void**)&x->k, store);
-    if (rc == Q3TTS_OK) { rc = q3_dev_alloc_zeroed(e, (void**)&x->v, store); if (rc != Q3TTS_OK) e->dev_bytes -= store; }
+    if (rc == Q3TTS_OK) { rc = q3_dev_alloc_zeroed(e, (void**)&x->v, q3_prefix_store_bytes(e, np, 1)); if (rc != Q3TTS_OK) e->dev_bytes -= store; }
     if (rc != Q3TTS_OK) { hipFree(x->k); x->k = x->v = nullptr; return rc; }
     x->P = rows; x->np = np;
     return Q3TTS_OK;
 }
 void q3_prefix_free(q3tts_prefix* x) {
-    for (uint16_t* p : {x->k, x->v}) if (p) { x->e->dev_bytes -= q3_prefix_store_bytes(x->e, x->np); hipFree(p); }
+    for (int v = 0; v < 2; ++v) if (uint16_t* p = v ? x->v : x->k) { x->e->dev_bytes -= q3_prefix_store_bytes(x->e, x->np, v); hipFree(p); }
     delete x;
 }
 

@@ -46,6 +46,7 @@ __global__ __launch_bounds__(64) void k_qk_prep(Q3QkPrep a) {
     }
 }
 int q3_launch_qk_prep(const Q3QkPrep& a, hipStream_t s) {
+    if (a.kv4) return q3_launch_qk_prep_kv4(a, s);  // Q4_0 blocks in the cache: q3_attend_kv4.hip
     if (a.kv8) return q3_launch_qk_prep_kv8(a, s);  // Q8_0 cache: the quantising append of q3_attend_kv8.hip
     if (a.tbl) return q3_launch_qk_prep_paged(a, s);  // paged cache: the append of q3_attend_paged.hip
     if (a.hd != Q3_ATT_HD) return 1;
@@ -804,6 +805,7 @@ static hipError_t att_allow_lds(const void* kernel, size_t lds) { return hipFunc
 // or the pair kernel for another ratio than 2.
 int q3_attend_pick(const Q3Attend& a) {
     att_policy_init();
+    if (a.kv4) return q3_attend_pick_kv4(a);  // Q4_0 blocks: one of the six kernels of q3_attend_kv4.hip
     if (a.kv8) return q3_attend_pick_kv8(a);  // Q8_0 cache: one of the six kernels of q3_attend_kv8.hip, never one of the nine below
     if (a.tbl) return q3_attend_pick_paged(a);  // paged cache: one of the seven of q3_attend_paged.hip
     if (a.hd != Q3_ATT_HD || a.Hkv <= 0 || a.Hq % a.Hkv) return Q3_ATT_REFUSED;
@@ -826,6 +828,7 @@ int q3_attend_pick(const Q3Attend& a) {
 
 // 0: launched. Nonzero: refused, nothing launched — a shape q3_attend_pick refuses, or a device that refuses the LDS size.
 int q3_launch_attend(const Q3Attend& a, hipStream_t s) {
+    if (a.kv4) return q3_launch_attend_kv4(a, s);
     if (a.kv8) return q3_launch_attend_kv8(a, s);
     if (a.tbl) return q3_launch_attend_paged(a, s);
     const int pick = q3_attend_pick(a);
@@ -900,6 +903,7 @@ __global__ __launch_bounds__(256) void k_kv_prefix(Q3KvPrefix a) {
 }
 void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s) {
     if (a.n <= 0) return;
+    if (a.kv4) { q3_launch_kv_prefix_kv4(a, s); return; }
     if (a.kv8) { q3_launch_kv_prefix_kv8(a, s); return; }
     if (a.tbl) { q3_launch_kv_prefix_paged(a, s); return; }
     hipLaunchKernelGGL(k_kv_prefix, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
@@ -932,6 +936,7 @@ __global__ __launch_bounds__(256) void k_kv_prefix_save(Q3KvPrefix a) {
 int q3_launch_kv_prefix_save(const Q3KvPrefix& a, hipStream_t s) {
     if (a.n <= 0) return 0;
     if (a.hd != Q3_ATT_HD || a.n > Q3_KVP_MAX) return 1;
+    if (a.kv4) return q3_launch_kv_prefix_save_kv4(a, s);
     if (a.kv8) return q3_launch_kv_prefix_save_kv8(a, s);
     if (a.tbl) return q3_launch_kv_prefix_save_paged(a, s);
     hipLaunchKernelGGL(k_kv_prefix_save, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);

@@ -15,59 +15,11 @@
 namespace {
 constexpr int HD = Q3_ATT_HD;
 
-__device__ __forceinline__ float kv8_d(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ float kv8_q(uint32_t w, int i) { return (float)(int8_t)(w >> (8 * i)); }
-
-// ggml's quantize_row_q8_0 (f32) on one block held by 8 consecutive lanes x 4 elements: d = amax / 127, id = d ? 1 / d : 0,
-// q = roundf(x * id), d kept as f16. *qw: the lane's four quants, element e in byte e; *d16: the block's scale (the same in all 8 lanes).
-__device__ __forceinline__ void kv8_quant4(const float x[4], uint32_t* qw, uint16_t* d16) {
-    float amax = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
-    amax = fmaxf(amax, __shfl_xor(amax, 1)); amax = fmaxf(amax, __shfl_xor(amax, 2)); amax = fmaxf(amax, __shfl_xor(amax, 4));
-    const float d = amax / 127.0f, id = d != 0.0f ? 1.0f / d : 0.0f;
-    uint32_t w = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) w |= (uint32_t)(uint8_t)(int8_t)(int)roundf(x[e] * id) << (8 * e);
-    *qw = w;
-    *d16 = __builtin_bit_cast(unsigned short, (_Float16)d);
-}
-// dims 4 lane .. 4 lane + 3 of position pos into a head's K / V cache (kq / vq: the head's quants, kd / vd: its scales), lanes [0, hd/4)
-__device__ __forceinline__ void kv8_put_k(int8_t* kq, uint16_t* kd, int pos, int lane, uint32_t w, uint16_t d16) {
-    *(uint32_t*)(kq + q3_kv8_k_off(pos, 4 * lane)) = w;
-    if ((lane & 7) == 0) kd[q3_kv8_kd_idx(pos, lane >> 3)] = d16;
-}
+// dims 4 lane .. 4 lane + 3 of position pos into a head's V cache (vq: the head's quants, vd: its scales), lanes [0, hd/4); kv8_put_k, the
+// packed LDS form, kv8_opaque and the score chain att8_dot16 are in q3_kernels.h (q3_attend_kv4.hip runs them for a Q8_0 K beside a Q4_0 V)
 __device__ __forceinline__ void kv8_put_v(int8_t* vq, uint16_t* vd, int pos, int lane, uint32_t w, uint16_t d16) {
     *(uint32_t*)(vq + (size_t)pos * HD + 4 * lane) = w;
     if ((lane & 7) == 0) vd[(size_t)pos * (HD >> 5) + (lane >> 3)] = d16;
-}
-// ... and into LDS in the packed form: words [0, 32) the quants in dim order (key chunk c = 16 bytes at l + 4 c), then the 4 scales
-__device__ __forceinline__ void kv8_put_lds(uint32_t* l, int lane, uint32_t w, uint16_t d16) {
-    l[lane] = w;
-    if ((lane & 7) == 0) ((uint16_t*)(l + 32))[lane >> 3] = d16;
-}
-__device__ __forceinline__ uint16_t kv8_lds_d(const uint32_t* l, int j) { return ((const uint16_t*)(l + 32))[j]; }
-// A key as its lane holds it, made opaque to the optimiser once the newest key has been put in place of the cached one. Without it the
-// compiler dequantises the newest key ahead of the key-block loop (it is loop-invariant) and keeps all 128 floats live beside the cached key's
-// registers: k_attend_kv8<2, true> took 180 VGPRs instead of 63, k_attend_gqa2_kv8 ran out of its 256 and spilled.
-// Nothing enforces this: after a compiler upgrade, or a change to these kernels, compile this file with
-// -Rpass-analysis=kernel-resource-usage (plus the Makefile's FLAGS) and look for 79 VGPRs in k_attend_kv8<2, true> / <4, true>, about 170
-// in k_attend_gqa2_kv8, and ScratchSize 0 in every kernel here.
-__device__ __forceinline__ void kv8_opaque(uint4 kv[8], uint16_t ks[4]) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) asm volatile("" : "+v"(kv[c].x), "+v"(kv[c].y), "+v"(kv[c].z), "+v"(kv[c].w));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { uint32_t t = ks[j]; asm volatile("" : "+v"(t)); ks[j] = (uint16_t)t; }
-}
-
-// The two chains of the canonical order on x^ = d * q. Score: 16 dims of a key (one chunk, d ascending; one block scale).
-__device__ __forceinline__ float att8_dot4(const float4 q, uint32_t w, float d, float s) {
-    s = fmaf(q.x, d * kv8_q(w, 0), s); s = fmaf(q.y, d * kv8_q(w, 1), s);
-    s = fmaf(q.z, d * kv8_q(w, 2), s); s = fmaf(q.w, d * kv8_q(w, 3), s);
-    return s;
-}
-__device__ __forceinline__ float att8_dot16(const float* q, const uint4 k, float d, float s) {
-    s = att8_dot4(*(const float4*)q, k.x, d, s); s = att8_dot4(*(const float4*)(q + 4), k.y, d, s);
-    s = att8_dot4(*(const float4*)(q + 8), k.z, d, s); s = att8_dot4(*(const float4*)(q + 12), k.w, d, s);
-    return s;
 }
 // Value: 8 dims of one value row (8 bytes inside one block) times the key's weight pt onto the lane's 8 partial sums.
 __device__ __forceinline__ void att8_pv8(float pt, const uint2 v, float d, float o[8]) {

@@ -25,6 +25,9 @@ struct Q3KvCache {
     // cfg.kv_q8_0 (the Talker only): the cache is ggml Q8_0 blocks — kc / vc hold int8 quants (layer_stride BYTES per layer) and
     // kd / vd the f16 block scales [L][slots][Hkv][n_ctx*hd/32], which follow the quants in the same allocation. q3_layer_cache does the arithmetic.
     bool kv8 = false; uint16_t *kd = nullptr, *vd = nullptr;
+    // q3tts_engine_options.kv_type_k / kv_type_v: with kv8, the Q3_KV4_K / Q3_KV4_V side holds Q4_0 blocks — half a byte per
+    // element, so layer l of that side starts q3_kv4_bytes(kv4, side, l * layer_stride) bytes in; the scales are as for Q8_0.
+    int kv4 = 0;
     int n_ctx = 0, n_slots = 0;
     // q3tts_engine_options.kv_pages (the Talker only): kc / vc are page pools [L][n_pages + 1][Hkv][64 * hd] (layer_stride
     // = one layer's pool) and tbl [n_slots][tbl_stride = n_ctx / 64] names each slot's pages (device; page 0 = the zero page). Null: contiguous.
@@ -192,14 +195,14 @@ struct q3tts_engine {
 struct q3tts_prefix {
     q3tts_engine* e = nullptr;          // the engine that made it (and whose slots it may enter)
     int P = 0, np = 0;
-    uint16_t *k = nullptr, *v = nullptr;  // (kv_q8_0: int8 quants [L][Hkv][np * hd], then their f16 scales [L][Hkv][np * hd / 32])
+    uint16_t *k = nullptr, *v = nullptr;  // (kv_q8_0: int8 quants [L][Hkv][np * hd], then their f16 scales [L][Hkv][np * hd / 32]; a Q4_0 side: np * hd / 2 bytes of quants)
     // A prefix made through a session (q3_session.hip) exists before its store does. state: 0 pending, 1 ready, < 0 the
     // status it failed with; the worker writes P / np / k / v and then state (release), any thread reads state first (acquire).
     // released / qrefs (the session's mutex): q3tts_session_prefix_release was called; queued requests of the session that name it.
     std::atomic<int> state{1};
     bool released = false; int qrefs = 0;
 };
-size_t q3_prefix_store_bytes(const q3tts_engine* e, int np);  // bytes of ONE of a prefix's two stores (k or v) of np positions
+size_t q3_prefix_store_bytes(const q3tts_engine* e, int np, int v = 0);  // bytes of ONE of a prefix's two stores of np positions: k, or (v = 1) v — they differ only with a Q8_0 K beside a Q4_0 V
 
 // helpers shared with q3_vocoder.hip and the kernel-level test hooks (q3_hooks.hip)
 int q3_set_err(q3tts_engine* e, int code, const std::string& msg);
@@ -239,18 +242,19 @@ struct Q3TfmShape {
     int n_ctx, n_slots;       // KV cache: positions per slot, slots
     int kv8;                  // cfg.kv_q8_0: the cache as Q8_0 blocks
     int kv_pages;             // q3tts_engine_options.kv_pages: > 0 = a pool of that many 64-position pages (+ the zero page) and a table, not n_slots * n_ctx positions
+    int kv4;                  // q3tts_engine_options.kv_type_k / kv_type_v as a Q3_KV4_* mask (with kv8 = 1): Q4_0 blocks on that side
 };
 // layer l's part of the cache t: bf16 elements, or (t.kv8) int8 quants and their scales
 inline void q3_layer_cache(const Q3KvCache& t, int l, uint16_t** kc, uint16_t** vc, uint16_t** kd, uint16_t** vd) {
     if (t.kv8) {
-        *kc = (uint16_t*)((int8_t*)t.kc + l * t.layer_stride); *vc = (uint16_t*)((int8_t*)t.vc + l * t.layer_stride);
+        *kc = (uint16_t*)((int8_t*)t.kc + q3_kv4_bytes(t.kv4, 0, l * t.layer_stride)); *vc = (uint16_t*)((int8_t*)t.vc + q3_kv4_bytes(t.kv4, 1, l * t.layer_stride));
         *kd = t.kd + l * (t.layer_stride >> 5); *vd = t.vd + l * (t.layer_stride >> 5);
     } else { *kc = t.kc + l * t.layer_stride; *vc = t.vc + l * t.layer_stride; *kd = *vd = nullptr; }
 }
 // the descriptor of K/V copies between t's cache and stores (voice prefixes, swap blocks): everything but the entries
 inline Q3KvPrefix q3_kv_prefix_of(const Q3Tfm& t) {
     const Q3KvCache& c = t.cache;
-    Q3KvPrefix kp{c.kc, c.vc, c.layer_stride, c.n_ctx, t.L, t.Hkv, t.hd}; kp.kv8 = c.kv8 ? 1 : 0; kp.kd = c.kd; kp.vd = c.vd;
+    Q3KvPrefix kp{c.kc, c.vc, c.layer_stride, c.n_ctx, t.L, t.Hkv, t.hd}; kp.kv8 = c.kv8 ? 1 : 0; kp.kd = c.kd; kp.vd = c.vd; kp.kv4 = c.kv4;
     kp.tbl = c.tbl; kp.tbl_stride = c.tbl_stride;
     return kp;
 }

@@ -121,7 +121,7 @@ static unsigned long long tfm_weight_bytes(int L, int d, int Hq, int Hkv, int hd
     const unsigned long long n = per * L + (unsigned long long)head_n * d;
     return q8 ? n + n / 16 : 2 * n;  // Q8_0: 34 bytes per 32 weights
 }
-static unsigned long long engine_footprint(const q3tts_engine_config& c, int kv_pages = 0) {
+static unsigned long long engine_footprint(const q3tts_engine_config& c, int kv_pages = 0, int kv4 = 0) {
     const q3tts_model_config& m = c.model;
     const unsigned long long B = c.max_batch, nctx = c.n_ctx, cap = c.max_steps_cap;
     unsigned long long t = tfm_weight_bytes(m.t_n_layer, m.t_d_model, m.t_n_head, m.t_n_kv_head, m.t_head_dim, m.t_d_ffn, m.t_vocab, c.talker_q8_0) +
@@ -129,6 +129,7 @@ static unsigned long long engine_footprint(const q3tts_engine_config& c, int kv_
     // Talker KV: bf16, or (kv_q8_0) Q8_0 blocks — 2 * t_n_layer * t_n_kv_head * n_ctx * (t_head_dim + 2 * t_head_dim / 32) bytes per slot
     // paged (kv_pages, bf16 only): the pool of kv_pages + 1 pages of 64 positions, and the table — not max_batch * n_ctx positions
     if (kv_pages > 0) t += (kv_pages + 1ull) * 2 * m.t_n_layer * m.t_n_kv_head * 64 * m.t_head_dim * 2 + B * (nctx / 64) * 4;
+    else if (kv4) t += B * 1ull * m.t_n_layer * m.t_n_kv_head * nctx * (q3_kv4_bytes(kv4, 0, m.t_head_dim) + q3_kv4_bytes(kv4, 1, m.t_head_dim) + 4ull * m.t_head_dim / 32);  // (kv_type_k / kv_type_v: a Q4_0 side at half a byte per element)
     else if (c.kv_q8_0) t += B * 2ull * m.t_n_layer * m.t_n_kv_head * nctx * (m.t_head_dim + 2ull * m.t_head_dim / 32);
     else t += B * 2ull * m.t_n_layer * m.t_n_kv_head * m.t_head_dim * nctx * 2;
     t += B * 2ull * m.p_n_layer * m.p_n_kv_head * m.p_head_dim * 64 * 2;    // Predictor cache (64 positions, one frame)
@@ -230,15 +231,15 @@ static int alloc_rows(q3tts_engine* e, Q3Rows& r, size_t rows, int d, bool scale
     return Q3TTS_OK;
 }
 
-static Q3TfmShape talker_shape(const q3tts_engine_config& c, int kv_pages = 0) {
+static Q3TfmShape talker_shape(const q3tts_engine_config& c, int kv_pages = 0, int kv4 = 0) {
     const q3tts_model_config& m = c.model;
     return {.grp = Q3G_TALKER, .L = m.t_n_layer, .d = m.t_d_model, .Hq = m.t_n_head, .Hkv = m.t_n_kv_head, .hd = m.t_head_dim, .F = m.t_d_ffn,
-            .head_n = m.t_vocab, .theta = m.t_rope_theta, .sections = m.t_mrope_sections, .n_ctx = c.n_ctx, .n_slots = c.max_batch, .kv8 = c.kv_q8_0, .kv_pages = kv_pages};
+            .head_n = m.t_vocab, .theta = m.t_rope_theta, .sections = m.t_mrope_sections, .n_ctx = c.n_ctx, .n_slots = c.max_batch, .kv8 = (c.kv_q8_0 || kv4) ? 1 : 0, .kv_pages = kv_pages, .kv4 = kv4};
 }
 static Q3TfmShape predictor_shape(const q3tts_engine_config& c) {
     const q3tts_model_config& m = c.model;
     return {.grp = Q3G_PRED, .L = m.p_n_layer, .d = m.p_d_model, .Hq = m.p_n_head, .Hkv = m.p_n_kv_head, .hd = m.p_head_dim, .F = m.p_d_ffn,
-            .head_n = (m.n_codebooks - 1) * m.codebook_size, .theta = m.p_rope_theta, .sections = nullptr, .n_ctx = 64, .n_slots = c.max_batch, .kv8 = 0, .kv_pages = 0};
+            .head_n = (m.n_codebooks - 1) * m.codebook_size, .theta = m.p_rope_theta, .sections = nullptr, .n_ctx = 64, .n_slots = c.max_batch, .kv8 = 0, .kv_pages = 0, .kv4 = 0};
 }
 extern "C" int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine** out) { return q3tts_engine_create_opts(cfg, nullptr, out); }
 extern "C" int q3tts_get_weight_formats(const q3tts_engine* e, int64_t out[4]) {
@@ -250,11 +251,13 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     if (!cfg || !out) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
     std::string why;
     if (validate(*cfg, why) != Q3TTS_OK) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, why);
-    int kquant = 0, kv_pages = 0;
+    int kquant = 0, kv_pages = 0, kv4 = 0;
     if (opts) {
         // (a caller built against the struct without kv_pages passes the shorter size: everything behind it is off)
         const bool has_pages = opts->struct_size >= offsetof(q3tts_engine_options, kv_pages) + sizeof(int32_t);
-        if (opts->struct_size != sizeof(q3tts_engine_options) && opts->struct_size != offsetof(q3tts_engine_options, kv_pages)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.struct_size = " + std::to_string(opts->struct_size) + ", this library knows " + std::to_string(sizeof(q3tts_engine_options)));
+        // (... and one built against the struct without kv_type_k / kv_type_v the size that ends behind kv_pages)
+        const bool has_types = opts->struct_size >= sizeof(q3tts_engine_options);
+        if (opts->struct_size != sizeof(q3tts_engine_options) && opts->struct_size != offsetof(q3tts_engine_options, kv_type_k) && opts->struct_size != offsetof(q3tts_engine_options, kv_pages)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.struct_size = " + std::to_string(opts->struct_size) + ", this library knows " + std::to_string(sizeof(q3tts_engine_options)));
         if (opts->kquant_resident != 0 && opts->kquant_resident != 1) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.kquant_resident must be 0 or 1");
         kquant = opts->kquant_resident;
         if (kquant && (cfg->talker_q8_0 != 0 || cfg->predictor_q8_0 != 0))
@@ -265,6 +268,18 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
         if (kv_pages && cfg->kv_q8_0)
             return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "kv_pages = " + std::to_string(kv_pages) + " pages the bf16 cache; it cannot be combined with kv_q8_0 = " +
                               std::to_string(cfg->kv_q8_0) + " (the Q8_0 cache is contiguous): set one or the other");
+        // kv_type_k / kv_type_v: (0, 0) what the config says; Q8_0 K with Q4_0 V; Q4_0 both
+        const int tk = has_types ? opts->kv_type_k : 0, tv = has_types ? opts->kv_type_v : 0;
+        const std::string types = "kv_type_k = " + std::to_string(tk) + ", kv_type_v = " + std::to_string(tv);
+        if (tk == Q3TTS_KV_Q8_0 && tv == Q3TTS_KV_Q4_0) kv4 = Q3_KV4_V;
+        else if (tk == Q3TTS_KV_Q4_0 && tv == Q3TTS_KV_Q4_0) kv4 = Q3_KV4_K | Q3_KV4_V;
+        else if (tk != 0 || tv != 0)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options: " + types + " is not an accepted pair; kv_type_k / kv_type_v take (0, 0), (Q3TTS_KV_Q8_0 = " +
+                              std::to_string(Q3TTS_KV_Q8_0) + ", Q3TTS_KV_Q4_0 = " + std::to_string(Q3TTS_KV_Q4_0) + ") or (Q3TTS_KV_Q4_0, Q3TTS_KV_Q4_0)");
+        if (kv4 && kv_pages)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "kv_pages = " + std::to_string(kv_pages) + " pages the bf16 cache; it cannot be combined with " + types + " (a quantised cache is contiguous): set one or the other");
+        if (kv4 && cfg->kv_q8_0)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, types + " together with kv_q8_0 = " + std::to_string(cfg->kv_q8_0) + " is ambiguous: name the cache's types in one place (kv_type_k = Q3TTS_KV_Q8_0 with kv_type_v = Q3TTS_KV_Q8_0 is kv_q8_0 = 1 alone)");
         if (kv_pages && cfg->n_ctx / 64 > kv_pages)
             return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "kv_pages = " + std::to_string(kv_pages) + " cannot hold one request of n_ctx = " + std::to_string(cfg->n_ctx) +
                               " (" + std::to_string(cfg->n_ctx / 64) + " pages of 64 positions): a larger kv_pages or a smaller n_ctx");
@@ -275,14 +290,14 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     // no such shape — it already holds t_head_dim to 128, the GQA ratio to 1, 2, 4 and n_ctx to whole key blocks for every engine — so this
     // cannot be reached through the ABI yet; it is the place a wider validate() falls back on. The launcher's own refusals are tested
     // through q3tts_k_attend_pick_kv8.)
-    if (cfg->kv_q8_0) {
+    if (cfg->kv_q8_0 || kv4) {  // (the Q4_0 kernels of q3_attend_kv4.hip take the same shapes: q3_attend_pick hands over on kv4)
         const q3tts_model_config& mm = cfg->model;
-        Q3Attend pa{}; pa.kv8 = 1; pa.hd = mm.t_head_dim; pa.Hq = mm.t_n_head; pa.Hkv = mm.t_n_kv_head; pa.n_ctx = cfg->n_ctx;
+        Q3Attend pa{}; pa.kv8 = 1; pa.kv4 = kv4; pa.hd = mm.t_head_dim; pa.Hq = mm.t_n_head; pa.Hkv = mm.t_n_kv_head; pa.n_ctx = cfg->n_ctx;
         const int R = mm.t_n_head / mm.t_n_kv_head;
-        const bool prefill_ok = q3_attend_pick_kv8(pa) != Q3_ATT_REFUSED;
+        const bool prefill_ok = q3_attend_pick(pa) != Q3_ATT_REFUSED;
         pa.fused = R >= 2 ? 1 : 0;
-        if (!prefill_ok || q3_attend_pick_kv8(pa) == Q3_ATT_REFUSED || mm.t_head_dim % 32 || cfg->n_ctx % 64)
-            return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, "kv_q8_0 = 1: the Q8_0-cache attention kernels need t_head_dim = 128, a GQA ratio of 1, 2 or 4 and n_ctx in whole 64-key blocks; this model has t_head_dim = " +
+        if (!prefill_ok || q3_attend_pick(pa) == Q3_ATT_REFUSED || mm.t_head_dim % 32 || cfg->n_ctx % 64)
+            return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, std::string(kv4 ? "kv_type_k / kv_type_v" : "kv_q8_0 = 1") + ": the quantised-cache attention kernels need t_head_dim = 128, a GQA ratio of 1, 2 or 4 and n_ctx in whole 64-key blocks; this model has t_head_dim = " +
                               std::to_string(mm.t_head_dim) + ", ratio " + std::to_string(R) + ", n_ctx = " + std::to_string(cfg->n_ctx));
     }
     // The vocoder's weights file, found beside the model (q3_voc_file_find), is opened and checked in full here, on the host, before the
@@ -317,11 +332,11 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     {   // before the first allocation: what the config sizes against the device's free memory (not a failure half-way through q3_dalloc)
         size_t free_b = 0, total_b = 0;
         HIPC(hipMemGetInfo(&free_b, &total_b));
-        const unsigned long long need = engine_footprint(*cfg, kv_pages) - kq_saved;
+        const unsigned long long need = engine_footprint(*cfg, kv_pages, kv4) - kq_saved;
         if (need > (unsigned long long)free_b) {
             q3_set_err(e, Q3TTS_ERR_OOM, "engine needs at least " + std::to_string(need) + " bytes of device memory for max_batch = " + std::to_string(cfg->max_batch) +
-                       ", n_ctx = " + std::to_string(cfg->n_ctx) + (cfg->kv_q8_0 ? " (Q8_0 cache)" : "") + (kv_pages ? " (kv_pages = " + std::to_string(kv_pages) + ")" : std::string()) + "; the device has " + std::to_string((unsigned long long)free_b) +
-                       (cfg->kv_q8_0 ? " bytes free (fewer slots or a smaller n_ctx)" : " bytes free (fewer slots, a smaller n_ctx, or kv_q8_0 = 1: the cache in 0.53 of the bytes)"));
+                       ", n_ctx = " + std::to_string(cfg->n_ctx) + (kv4 ? " (Q4_0 cache)" : cfg->kv_q8_0 ? " (Q8_0 cache)" : "") + (kv_pages ? " (kv_pages = " + std::to_string(kv_pages) + ")" : std::string()) + "; the device has " + std::to_string((unsigned long long)free_b) +
+                       ((cfg->kv_q8_0 || kv4) ? " bytes free (fewer slots or a smaller n_ctx)" : " bytes free (fewer slots, a smaller n_ctx, or kv_q8_0 = 1: the cache in 0.53 of the bytes)"));
             return fail(Q3TTS_ERR_OOM);
         }
     }
@@ -345,7 +360,7 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     const int B = cfg->max_batch;
     e->B = B;
     hipStream_t s = e->stream;
-    TRYC(q3_tfm_init(e, e->T, talker_shape(*cfg, kv_pages), wdir.empty() ? nullptr : &gt, "qwen3_tts_talker.gguf", cfg->talker_q8_0, kquant));
+    TRYC(q3_tfm_init(e, e->T, talker_shape(*cfg, kv_pages, kv4), wdir.empty() ? nullptr : &gt, "qwen3_tts_talker.gguf", cfg->talker_q8_0, kquant));
     TRYC(q3_tfm_init(e, e->P, predictor_shape(*cfg), wdir.empty() ? nullptr : &gp, "qwen3_tts_predictor.gguf", cfg->predictor_q8_0, kquant));
     if (kv_pages) {  // the page allocator: LIFO, page 1 on top; the table's pinned image (all zero, like the device's)
         e->kvp_total = kv_pages; e->kvp_slot.assign(B, {});

@@ -218,6 +218,7 @@ extern "C" int q3tts_k_attention_decode(int32_t device, const float* qkv, int32_
 struct AttHook {
     int n_slots = 0, n_ctx = 0, Hq = 0, Hkv = 0, ld = 0, nq = 0, form = 0, out_rows = 0, rt16 = 0;
     int kv8 = 0;  // the cache as Q8_0 blocks (the _kv8 hooks; set before init): kc / vc then hold int8 quants, kd / vd their f16 scales
+    int kv4 = 0;  // ... with Q4_0 blocks on the Q3_KV4_K / Q3_KV4_V side (the _kv4 hooks; with kv8 = 1): half a byte of quants per element there
     DevBuf qn, kn, cs, sn, kc, vc, kd, vd, out, osc;
     // the cache paged (the _paged hooks; set before init): kc / vc then are pools of n_pages + 1 pages [page][Hkv][64 * hd], tbl_host the
     // caller's table [n_slots][n_ctx / 64]; page 0 and every page the table names start as zeros, every other page holds `fill`
@@ -257,7 +258,7 @@ struct AttHook {
         TRY(qn.put(qnw, Q3_ATT_HD * 4)); TRY(kn.put(knw, Q3_ATT_HD * 4)); TRY(cs.put(c.data(), c.size() * 4)); TRY(sn.put(s.data(), s.size() * 4));
         const size_t cache = (size_t)n_slots * Hkv * n_ctx * Q3_ATT_HD * (kv8 ? 1 : 2);
         if (n_pages) TRY(init_pool());
-        else { TRY(kc.alloc(cache)); TRY(vc.alloc(cache)); }
+        else { TRY(kc.alloc(q3_kv4_bytes(kv4, 0, cache))); TRY(vc.alloc(q3_kv4_bytes(kv4, 1, cache))); }
         if (kv8) { TRY(kd.alloc(cache / 16)); TRY(vd.alloc(cache / 16)); }
         TRY(out.alloc(form == 0 ? (size_t)rows * nq * 4 : pad16(rows) * nq * (form == 1 ? 2 : 1)));
         if (form == 2) TRY(osc.alloc((size_t)(nq / 32 + 2) * pad16(rows) * 4));
@@ -266,14 +267,14 @@ struct AttHook {
     Q3QkPrep prep(float* rows_dev, int rows, float eps) const {
         Q3QkPrep qp{}; qp.qkv = rows_dev; qp.ld = ld; qp.rows = rows; qp.Hq = Hq; qp.Hkv = Hkv; qp.hd = Q3_ATT_HD; qp.qnw = qn; qp.knw = kn; qp.eps = eps;
         qp.cs = cs; qp.sn = sn; qp.kc = kc; qp.vc = vc; qp.n_ctx = n_ctx;
-        if (kv8) { qp.kv8 = 1; qp.kd = kd; qp.vd = vd; }
+        if (kv8) { qp.kv8 = 1; qp.kv4 = kv4; qp.kd = kd; qp.vd = vd; }
         if (n_pages) { qp.tbl = tbl; qp.tbl_stride = n_ctx / 64; }
         return qp;
     }
     Q3Attend attend(const float* rows_dev, int rows) const {
         Q3Attend at{}; at.qkv = rows_dev; at.ld = ld; at.rows = rows; at.out = out; at.ldo = nq; at.out_bf16 = form; at.Hq = Hq; at.Hkv = Hkv; at.hd = Q3_ATT_HD;
         at.kc = kc; at.vc = vc; at.n_ctx = n_ctx;
-        if (kv8) { at.kv8 = 1; at.kd = kd; at.vd = vd; }
+        if (kv8) { at.kv8 = 1; at.kv4 = kv4; at.kd = kd; at.vd = vd; }
         if (n_pages) { at.tbl = tbl; at.tbl_stride = n_ctx / 64; }
         if (form == 2) { at.out_scale = osc; at.out_rt16 = rt16; }
         return at;
@@ -326,6 +327,24 @@ struct AttHook {
     // the Q8_0 cache of every slot, un-blocked: quants int8 [slot][Hkv][n_ctx][hd], scales f16 bits [slot][Hkv][n_ctx][hd / 32] (each optional)
     int read_cache_kv8(int8_t* kq_host, int8_t* vq_host, uint16_t* kd_host, uint16_t* vd_host) const {
         constexpr int hd = Q3_ATT_HD, nb = hd / 32;
+        if (kv4) {  // the quants of a Q4_0 side as their nibbles 0 .. 15, one per element; the scales (below) are laid out as Q8_0's
+            const size_t heads = (size_t)n_slots * Hkv, per = (size_t)n_ctx * hd;
+            for (int v = 0; v < 2; ++v) {
+                int8_t* dst = v ? vq_host : kq_host;
+                if (!dst) continue;
+                const bool q4 = (kv4 & (v ? Q3_KV4_V : Q3_KV4_K)) != 0;
+                const size_t hb = q3_kv4_bytes(kv4, v, per);
+                std::vector<uint8_t> t(heads * hb);
+                TRY((v ? vc : kc).get(t.data(), t.size()));
+                for (size_t h = 0; h < heads; ++h)
+                    for (int pos = 0; pos < n_ctx; ++pos)
+                        for (int d = 0; d < hd; ++d) {
+                            const uint8_t b = t[h * hb + (!q4 ? q3_kv8_k_off(pos, d) : v ? q3_kv4_v_off(pos, d) : q3_kv4_k_off(pos, d))];
+                            dst[(h * n_ctx + pos) * hd + d] = (int8_t)(!q4 ? b : (d & 1) ? b >> 4 : b & 15);
+                        }
+            }
+            kq_host = vq_host = nullptr;
+        }
         const size_t n = (size_t)n_slots * Hkv * n_ctx * hd, heads = (size_t)n_slots * Hkv;
         if (vq_host) TRY(vc.get(vq_host, n));
         if (vd_host) TRY(vd.get(vd_host, n / 16));
@@ -347,7 +366,7 @@ struct AttHook {
     }
 };
 // what a hook hands back of the cache: bf16 bits (k16 / v16), or with kv8 the quants and scales
-struct AttCacheOut { int kv8 = 0; uint16_t *k16 = nullptr, *v16 = nullptr; int8_t *kq = nullptr, *vq = nullptr; uint16_t *kd = nullptr, *vd = nullptr;
+struct AttCacheOut { int kv8 = 0, kv4 = 0; uint16_t *k16 = nullptr, *v16 = nullptr; int8_t *kq = nullptr, *vq = nullptr; uint16_t *kd = nullptr, *vd = nullptr;
                      int n_pages = 0; const int32_t* tbl = nullptr; uint16_t fill = 0; };  // (the _paged hooks: the pool's size, the caller's table, the fill pattern)
 static void att_hook_paged(AttHook& h, const AttCacheOut& c) { h.n_pages = c.n_pages; h.tbl_host = c.tbl; h.fill = c.fill; }
 static int att_read_cache(const AttHook& h, const AttCacheOut& c) {
@@ -373,7 +392,7 @@ static int att_hook_launch(const char* name, const Q3Attend& at, int decode, int
 static int attention_runs(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx, int32_t Hq,
                           int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections,
                           int32_t policy, int32_t out_form, void* out, float* out_scale, const AttCacheOut& cache) {
-    const std::string hook = cache.kv8 ? "attention runs_kv8 hook" : cache.tbl ? "attention runs_paged hook" : "attention runs hook";   // (the exported entry that was called)
+    const std::string hook = cache.kv4 ? "attention runs_kv4 hook" : cache.kv8 ? "attention runs_kv8 hook" : cache.tbl ? "attention runs_paged hook" : "attention runs hook";   // (the exported entry that was called)
     if (const char* why = AttHook::check(qkv, n_runs, n_ctx, Hq, Hkv, hd, qnw, knw, out_form, out, out_scale))
         return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": " + why);
     if (const char* why = cache.tbl ? AttHook::check_table(cache.tbl, n_runs, n_ctx, cache.n_pages) : nullptr) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": " + why);
@@ -387,7 +406,7 @@ static int attention_runs(int32_t device, const float* qkv, int32_t n_runs, cons
         seg_max_n = std::max(seg_max_n, run_n[i]); seg_max_t = std::max(seg_max_t, run_pos0[i] + run_n[i]);
     }
     HK(hipSetDevice(device));
-    AttHook h; h.kv8 = cache.kv8; att_hook_paged(h, cache);
+    AttHook h; h.kv8 = cache.kv8; h.kv4 = cache.kv4; att_hook_paged(h, cache);
     TRY(h.init(n_runs, n_ctx, Hq, Hkv, qnw, knw, theta, sections, out_form, (int)n_run));
     const int ld = h.ld;
     std::vector<float> pre((size_t)std::max<long long>(n_pre, 1) * ld), run((size_t)n_run * ld);
@@ -435,7 +454,7 @@ extern "C" int q3tts_k_attention_runs_kv8(int32_t device, const float* qkv, int3
 static int attention_decode_ex(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq, int32_t Hkv,
                                int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, int32_t policy,
                                int32_t row_indexed, int32_t out_form, void* out, float* out_scale, const AttCacheOut& cache) {
-    const std::string hook = cache.kv8 ? "attention decode_kv8 hook" : cache.tbl ? "attention decode_paged hook" : "attention decode_ex hook";
+    const std::string hook = cache.kv4 ? "attention decode_kv4 hook" : cache.kv8 ? "attention decode_kv8 hook" : cache.tbl ? "attention decode_paged hook" : "attention decode_ex hook";
     if (const char* why = AttHook::check(qkv, n_slots, n_ctx, Hq, Hkv, hd, qnw, knw, out_form, out, out_scale))
         return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": " + why);
     if (const char* why = cache.tbl ? AttHook::check_table(cache.tbl, n_slots, n_ctx, cache.n_pages) : nullptr) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, hook + ": " + why);
@@ -448,7 +467,7 @@ static int attention_decode_ex(int32_t device, const float* qkv, int32_t n_slots
         total += lens[s];
     }
     HK(hipSetDevice(device));
-    AttHook h; h.kv8 = cache.kv8; att_hook_paged(h, cache);
+    AttHook h; h.kv8 = cache.kv8; h.kv4 = cache.kv4; att_hook_paged(h, cache);
     TRY(h.init(n_slots, n_ctx, Hq, Hkv, qnw, knw, theta, sections, out_form, n_slots));
     const int ld = h.ld, npre = (int)(total - n_slots);
     std::vector<float> pre((size_t)std::max(npre, 1) * ld), last((size_t)n_slots * ld);
@@ -488,6 +507,58 @@ extern "C" int q3tts_k_attention_decode_kv8(int32_t device, const float* qkv, in
                                             int32_t out_form, void* out, float* out_scale, int8_t* k_q, int8_t* v_q, uint16_t* k_d, uint16_t* v_d) {
     AttCacheOut c; c.kv8 = 1; c.kq = k_q; c.vq = v_q; c.kd = k_d; c.vd = v_d;
     return attention_decode_ex(device, qkv, n_slots, lens, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, 0, out_form, out, out_scale, c);
+}
+
+// ... over a cache with Q4_0 blocks (q3_attend_kv4.hip): the _kv8 hooks with the types named; quants come back one per element
+static int kv4_mask(int32_t tk, int32_t tv, const char* hook) {  // the Q3_KV4_* mask of an accepted pair; -1 (error text set) for any other
+    if (tk == Q3TTS_KV_Q8_0 && tv == Q3TTS_KV_Q4_0) return Q3_KV4_V;
+    if (tk == Q3TTS_KV_Q4_0 && tv == Q3TTS_KV_Q4_0) return Q3_KV4_K | Q3_KV4_V;
+    q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string(hook) + ": kv_type_k / kv_type_v must be (Q8_0, Q4_0) or (Q4_0, Q4_0)");
+    return -1;
+}
+extern "C" int q3tts_k_attention_runs_kv4(int32_t device, const float* qkv, int32_t n_runs, const int32_t* run_n, const int32_t* run_pos0, int32_t n_ctx, int32_t Hq,
+                                          int32_t Hkv, int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections,
+                                          int32_t policy, int32_t out_form, void* out, float* out_scale, int32_t kv_type_k, int32_t kv_type_v, int8_t* k_q,
+                                          int8_t* v_q, uint16_t* k_d, uint16_t* v_d) {
+    AttCacheOut c; c.kv8 = 1; c.kv4 = kv4_mask(kv_type_k, kv_type_v, "attention runs_kv4 hook"); c.kq = k_q; c.vq = v_q; c.kd = k_d; c.vd = v_d;
+    if (c.kv4 < 0) return Q3TTS_ERR_INVALID;
+    return attention_runs(device, qkv, n_runs, run_n, run_pos0, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, out_form, out, out_scale, c);
+}
+extern "C" int q3tts_k_attention_decode_kv4(int32_t device, const float* qkv, int32_t n_slots, const int32_t* lens, int32_t n_ctx, int32_t Hq, int32_t Hkv,
+                                            int32_t hd, const float* qnw, const float* knw, float eps, float theta, const int32_t* sections, int32_t policy,
+                                            int32_t out_form, void* out, float* out_scale, int32_t kv_type_k, int32_t kv_type_v, int8_t* k_q, int8_t* v_q,
+                                            uint16_t* k_d, uint16_t* v_d) {
+    AttCacheOut c; c.kv8 = 1; c.kv4 = kv4_mask(kv_type_k, kv_type_v, "attention decode_kv4 hook"); c.kq = k_q; c.vq = v_q; c.kd = k_d; c.vd = v_d;
+    if (c.kv4 < 0) return Q3TTS_ERR_INVALID;
+    return attention_decode_ex(device, qkv, n_slots, lens, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, 0, out_form, out, out_scale, c);
+}
+// A voice prefix into a slot and out again, as q3tts_k_kv_prefix_roundtrip, for such a cache: the stores are bytes (quants, then f16 scales)
+extern "C" int q3tts_k_kv_prefix_roundtrip_kv4(int32_t device, const void* k_store, const void* v_store, int64_t k_bytes, int64_t v_bytes, int32_t L, int32_t Hkv,
+                                               int32_t P, int32_t n_ctx, int32_t kv_type_k, int32_t kv_type_v, void* k_out, void* v_out) {
+    const char* hook = "kv prefix roundtrip_kv4 hook";
+    const int kv4 = kv4_mask(kv_type_k, kv_type_v, hook);
+    if (kv4 < 0) return Q3TTS_ERR_INVALID;
+    if (!k_store || !v_store || !k_out || !v_out || L < 1 || L > 64 || Hkv < 1 || Hkv > 64 || P < 1 || n_ctx < 64 || n_ctx % 64 || n_ctx > 8192 || P > n_ctx)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string(hook) + ": null argument, or L / Hkv outside 1 .. 64, or P outside 1 .. n_ctx, or n_ctx not whole blocks");
+    constexpr int hd = Q3_ATT_HD;
+    const int np = (P + 63) & ~63;
+    const size_t se = (size_t)L * Hkv * np * hd, layer = (size_t)Hkv * n_ctx * hd;   // elements of a store / of the cache's one slot per layer
+    const size_t sk = q3_kv4_bytes(kv4, 0, se), sv = q3_kv4_bytes(kv4, 1, se), ck_q = q3_kv4_bytes(kv4, 0, layer * L), cv_q = q3_kv4_bytes(kv4, 1, layer * L);
+    if (k_bytes != (int64_t)(sk + se / 16) || v_bytes != (int64_t)(sv + se / 16))
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string(hook) + ": k_bytes / v_bytes must be " + std::to_string(sk + se / 16) + " / " + std::to_string(sv + se / 16));
+    HK(hipSetDevice(device));
+    DevBuf dk, dv, ck, cv, ok, ov;
+    TRY(dk.put(k_store, sk + se / 16)); TRY(dv.put(v_store, sv + se / 16)); TRY(ok.alloc(sk + se / 16)); TRY(ov.alloc(sv + se / 16));
+    TRY(ck.alloc(ck_q + layer * L / 16)); TRY(cv.alloc(cv_q + layer * L / 16));
+    Q3KvPrefix kp{ck, cv, layer, n_ctx, L, Hkv, hd}; kp.n = 1; kp.P[0] = P; kp.slot[0] = 0; kp.kv8 = 1; kp.kv4 = kv4;
+    kp.kd = (uint16_t*)((uint8_t*)ck.p + ck_q); kp.vd = (uint16_t*)((uint8_t*)cv.p + cv_q);
+    kp.pk[0] = dk; kp.pv[0] = dv;
+    q3_launch_kv_prefix(kp, nullptr);
+    kp.pk[0] = ok; kp.pv[0] = ov;
+    if (q3_launch_kv_prefix_save(kp, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, std::string(hook) + ": the save launch was refused");
+    HK(hipGetLastError()); HK(hipDeviceSynchronize());
+    TRY(ok.get(k_out, sk + se / 16));
+    return ov.get(v_out, sv + se / 16);
 }
 
 // ... over a paged cache (q3_attend_paged.hip): the same rows through a pool of n_pages + 1 pages and the caller's table
@@ -587,6 +658,18 @@ extern "C" int q3tts_k_attend_pick_paged(int32_t fused, int32_t gqa_ratio, int32
     Q3Attend a{}; a.hd = Q3_ATT_HD; a.Hkv = n_kv_head; a.Hq = n_kv_head * gqa_ratio; a.fused = fused; a.n_ctx = n_ctx;
     a.tbl = (const int*)16; a.tbl_stride = (n_ctx + 63) / 64;  // (never dereferenced: nothing is launched)
     if (n_seg > 0) { a.seg = (const int*)16; a.n_seg = n_seg; a.seg_max_n = seg_max_n; a.seg_max_t = seg_max_t; }
+    *kernel = q3_attend_pick(a);
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_k_attend_pick_kv4(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t, int32_t n_kv_head,
+                                       int32_t kv_type_k, int32_t kv_type_v, int32_t* kernel) {
+    if (!kernel || fused < 0 || fused > 2 || gqa_ratio <= 0 || gqa_ratio > 64 || n_ctx <= 0 || n_seg < 0 || seg_max_n < 0 || seg_max_t < 0 || n_kv_head <= 0 ||
+        n_kv_head > 4096)
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "attend pick (Q4_0 cache): bad shape");
+    Q3Attend a{}; a.hd = Q3_ATT_HD; a.Hkv = n_kv_head; a.Hq = n_kv_head * gqa_ratio; a.fused = fused; a.n_ctx = n_ctx; a.kv8 = 1;
+    a.kv4 = kv4_mask(kv_type_k, kv_type_v, "attend pick (Q4_0 cache)");
+    if (a.kv4 < 0) return Q3TTS_ERR_INVALID;
+    if (n_seg > 0) { a.seg = (const int*)16; a.n_seg = n_seg; a.seg_max_n = seg_max_n; a.seg_max_t = seg_max_t; }  // (never dereferenced: nothing is launched)
     *kernel = q3_attend_pick(a);
     return Q3TTS_OK;
 }
@@ -1089,7 +1172,7 @@ extern "C" int q3tts_k_prefix_read(const q3tts_prefix* x, void* k, void* v, int6
     Q3_HIP(e, hipSetDevice(e->cfg.device));
     Q3_HIP(e, hipStreamSynchronize(e->stream));
     if (k) Q3_HIP(e, hipMemcpy(k, x->k, n, hipMemcpyDeviceToHost));
-    if (v) Q3_HIP(e, hipMemcpy(v, x->v, n, hipMemcpyDeviceToHost));
+    if (v) Q3_HIP(e, hipMemcpy(v, x->v, q3_prefix_store_bytes(e, x->np, 1), hipMemcpyDeviceToHost));  // (shorter than n only beside a Q8_0 K: a Q4_0 V)
     return Q3TTS_OK;
 }
 

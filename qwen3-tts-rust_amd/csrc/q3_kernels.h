@@ -270,6 +270,9 @@ struct Q3QkPrep {
     // Q8_0 cache (kv8 = 1; q3_attend_kv8.hip): kc / vc then hold the int8 quants (one byte per element, layouts at q3_kv8_k_off)
     // and kd / vd the f16 block scales, per (slot, kv head) n_ctx * hd / 32 of them
     int kv8; uint16_t* kd; uint16_t* vd;
+    // Q4_0 blocks in that cache (kv4 != 0, with kv8 = 1; q3_attend_kv4.hip): Q3_KV4_V — V is Q4_0, K stays Q8_0;
+    // Q3_KV4_K | Q3_KV4_V — both. A Q4_0 side holds half a byte per element (layouts at q3_kv4_k_off); the scales are where Q8_0's are.
+    int kv4;
     // Paged cache (tbl != null; q3_attend_paged.hip): kc / vc are the layer's page pool [pages][Hkv][64 * hd] bf16 and
     // tbl[slot * tbl_stride + (pos >> 6)] the page that holds pos. Null: the contiguous cache above, every launch and bit as before.
     const int* tbl; int tbl_stride;
@@ -288,6 +291,7 @@ struct Q3Attend {
     const int* row_pos; const int* row_slot;
     int slot_mod, pos_const;  // as in Q3QkPrep
     int kv8; const uint16_t* kd; const uint16_t* vd;  // Q8_0 cache, as in Q3QkPrep: q3_launch_attend then takes the kernels of q3_attend_kv8.hip
+    int kv4;          // Q4_0 blocks in it, as in Q3QkPrep: q3_launch_attend then takes the kernels of q3_attend_kv4.hip
     int fused;        // 1: every slot has exactly one row in this launch -> q/k prep + KV append done in-kernel (R >= 2)
                       // 2: rows b (position 0) and slot_mod + b (position 1) of every slot, nothing cached yet (R == 2): k_attend_pair
     Q3QkPrep prep;    // used when fused
@@ -411,10 +415,81 @@ __device__ __forceinline__ void att_out2(const Q3Attend& a, int row, int head, i
 // Byte offset of key element (pos, d) / f16 index of the scale of (pos, block j) inside a head's K cache:
 Q3_HD size_t q3_kv8_k_off(int pos, int d) { return ((size_t)((pos >> 6) * (Q3_ATT_HD >> 4) + (d >> 4)) * 64 + (pos & 63)) * 16 + (d & 15); }
 Q3_HD size_t q3_kv8_kd_idx(int pos, int j) { return ((size_t)(pos >> 6) * (Q3_ATT_HD >> 5) + j) * 64 + (pos & 63); }
+#ifdef __HIPCC__
+// The Q8_0 cache's device helpers that q3_attend_kv8.hip and q3_attend_kv4.hip (a Q8_0 K beside a Q4_0 V) share: one copy of each.
+__device__ __forceinline__ float kv8_d(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+__device__ __forceinline__ float kv8_q(uint32_t w, int i) { return (float)(int8_t)(w >> (8 * i)); }
+
+// ggml's quantize_row_q8_0 (f32) on one block held by 8 consecutive lanes x 4 elements: d = amax / 127, id = d ? 1 / d : 0,
+// q = roundf(x * id), d kept as f16. *qw: the lane's four quants, element e in byte e; *d16: the block's scale (the same in all 8 lanes).
+__device__ __forceinline__ void kv8_quant4(const float x[4], uint32_t* qw, uint16_t* d16) {
+    float amax = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
+    amax = fmaxf(amax, __shfl_xor(amax, 1)); amax = fmaxf(amax, __shfl_xor(amax, 2)); amax = fmaxf(amax, __shfl_xor(amax, 4));
+    const float d = amax / 127.0f, id = d != 0.0f ? 1.0f / d : 0.0f;
+    uint32_t w = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w |= (uint32_t)(uint8_t)(int8_t)(int)roundf(x[e] * id) << (8 * e);
+    *qw = w;
+    *d16 = __builtin_bit_cast(unsigned short, (_Float16)d);
+}
+// dims 4 lane .. 4 lane + 3 of position pos into a head's K cache (kq: the head's quants, kd: its scales), lanes [0, hd/4)
+__device__ __forceinline__ void kv8_put_k(int8_t* kq, uint16_t* kd, int pos, int lane, uint32_t w, uint16_t d16) {
+    *(uint32_t*)(kq + q3_kv8_k_off(pos, 4 * lane)) = w;
+    if ((lane & 7) == 0) kd[q3_kv8_kd_idx(pos, lane >> 3)] = d16;
+}
+// ... and into LDS in the packed form: words [0, 32) the quants in dim order (key chunk c = 16 bytes at l + 4 c), then the 4 scales
+__device__ __forceinline__ void kv8_put_lds(uint32_t* l, int lane, uint32_t w, uint16_t d16) {
+    l[lane] = w;
+    if ((lane & 7) == 0) ((uint16_t*)(l + 32))[lane >> 3] = d16;
+}
+__device__ __forceinline__ uint16_t kv8_lds_d(const uint32_t* l, int j) { return ((const uint16_t*)(l + 32))[j]; }
+// A key as its lane holds it, made opaque to the optimiser once the newest key has been put in place of the cached one. Without it the
+// compiler dequantises the newest key ahead of the key-block loop (it is loop-invariant) and keeps all 128 floats live beside the cached key's
+// registers: k_attend_kv8<2, true> took 180 VGPRs instead of 63, k_attend_gqa2_kv8 ran out of its 256 and spilled.
+// (N chunks: 8 of a Q8_0 key, 4 of a Q4_0 key.) Nothing enforces this: after a compiler upgrade, or a change to these kernels, compile q3_attend_kv8.hip with
+// -Rpass-analysis=kernel-resource-usage (plus the Makefile's FLAGS) and look for 79 VGPRs in k_attend_kv8<2, true> / <4, true>, about 170
+// in k_attend_gqa2_kv8, and ScratchSize 0 in every kernel here.
+template <int N> __device__ __forceinline__ void kv8_opaque(uint4 (&kv)[N], uint16_t (&ks)[4]) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) asm volatile("" : "+v"(kv[c].x), "+v"(kv[c].y), "+v"(kv[c].z), "+v"(kv[c].w));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { uint32_t t = ks[j]; asm volatile("" : "+v"(t)); ks[j] = (uint16_t)t; }
+}
+
+// The two chains of the canonical order on x^ = d * q. Score: 16 dims of a key (one chunk, d ascending; one block scale).
+__device__ __forceinline__ float att8_dot4(const float4 q, uint32_t w, float d, float s) {
+    s = fmaf(q.x, d * kv8_q(w, 0), s); s = fmaf(q.y, d * kv8_q(w, 1), s);
+    s = fmaf(q.z, d * kv8_q(w, 2), s); s = fmaf(q.w, d * kv8_q(w, 3), s);
+    return s;
+}
+__device__ __forceinline__ float att8_dot16(const float* q, const uint4 k, float d, float s) {
+    s = att8_dot4(*(const float4*)q, k.x, d, s); s = att8_dot4(*(const float4*)(q + 4), k.y, d, s);
+    s = att8_dot4(*(const float4*)(q + 8), k.z, d, s); s = att8_dot4(*(const float4*)(q + 12), k.w, d, s);
+    return s;
+}
+#endif
 // the launches of q3_attend_kv8.hip: q3_launch_qk_prep / q3_attend_pick / q3_launch_attend / q3_launch_kv_prefix hand over when kv8 is set
 int q3_launch_qk_prep_kv8(const Q3QkPrep& a, hipStream_t s);
 int q3_attend_pick_kv8(const Q3Attend& a);
 int q3_launch_attend_kv8(const Q3Attend& a, hipStream_t s);
+// ggml Q4_0 blocks in that cache (q3_attend_kv4.hip; q3tts_engine_options.kv_type_k / kv_type_v): V alone (K stays Q8_0, its
+// layout and kernels' key path as above) or K and V. A block is the same 32 dims; its 32 four-bit quants are 16 bytes, its scale one f16.
+// Per (slot, KV head):
+//   K quants [64-key block][hd / 32 blocks][64 keys][16 bytes] — one block of one key per 16-byte load, one key per lane, 1 KiB per wave-load,
+//            four loads per key (Q8_0: eight); K scales exactly as Q8_0's (q3_kv8_kd_idx)
+//   V quants [t][hd / 2 bytes] row-major — the 8 dims of a value-pass lane are one 4-byte word; V scales [t][hd / 32] f16
+// Dim d of a block sits in nibble d & 7 (bits 4 (d & 7) ..) of word (d & 31) >> 3: shifting a word right by 4 walks the dims upwards, so the
+// d-ascending chains read it without a permute. (ggml's file order, j | j + 16 per byte, is not kept: only the values are contractual.)
+// Byte offset of the byte that holds key element (pos, d) inside a head's K quants; the element is its low nibble for even d:
+enum { Q3_KV4_K = 1, Q3_KV4_V = 2 };
+Q3_HD size_t q3_kv4_k_off(int pos, int d) { return ((size_t)((pos >> 6) * (Q3_ATT_HD >> 5) + (d >> 5)) * 64 + (pos & 63)) * 16 + ((d & 31) >> 1); }
+Q3_HD size_t q3_kv4_v_off(int pos, int d) { return (size_t)pos * (Q3_ATT_HD >> 1) + (d >> 1); }
+// bytes that n cache elements take as quants on the K (v = 0) or V (v = 1) side of a cache with Q4_0 mask kv4
+Q3_HD size_t q3_kv4_bytes(int kv4, int v, size_t n) { return (kv4 & (v ? Q3_KV4_V : Q3_KV4_K)) ? n >> 1 : n; }
+// the launches of q3_attend_kv4.hip: the same launchers hand over when kv4 is set (accepted: Q3_KV4_V and Q3_KV4_K | Q3_KV4_V, with kv8 = 1)
+int q3_launch_qk_prep_kv4(const Q3QkPrep& a, hipStream_t s);
+int q3_attend_pick_kv4(const Q3Attend& a);
+int q3_launch_attend_kv4(const Q3Attend& a, hipStream_t s);
 // The gathering form of k_attend_small (block 0 of passes q >= 1 of the greedy bf16 Predictor): the row's q / k / v are not
 // read from a.qkv but from a table of every possible input row's layer-0 QKV, tab[code], where code is the argmax k_pred_next<false>(q)
 // takes from the same per-tile keys (largest key of the row, q3_argmax_idx); a code outside [0, tab_rows) reads the fallback row tab_rows.
@@ -440,7 +515,10 @@ enum { Q3_ATT_REFUSED = -1, Q3_ATT_N1 = 0, Q3_ATT_N2 = 1, Q3_ATT_N4 = 2,   // k_
        Q3_ATT8_N1 = 9, Q3_ATT8_N2 = 10, Q3_ATT8_N4 = 11, Q3_ATT8_F2 = 12, Q3_ATT8_F4 = 13, Q3_ATT8_GQA2 = 14,
        // the seven of q3_attend_paged.hip (Q3Attend.tbl; q3tts_k_attend_pick_paged): k_attend_paged<1 / 2 / 4, false>, <2 / 4, true>,
        // k_attend_gqa2_paged, k_attend_prefill_paged
-       Q3_ATTP_N1 = 15, Q3_ATTP_N2 = 16, Q3_ATTP_N4 = 17, Q3_ATTP_F2 = 18, Q3_ATTP_F4 = 19, Q3_ATTP_GQA2 = 20, Q3_ATTP_PREFILL = 21 };
+       Q3_ATTP_N1 = 15, Q3_ATTP_N2 = 16, Q3_ATTP_N4 = 17, Q3_ATTP_F2 = 18, Q3_ATTP_F4 = 19, Q3_ATTP_GQA2 = 20, Q3_ATTP_PREFILL = 21,
+       // the six of q3_attend_kv4.hip (Q3Attend.kv4; q3tts_k_attend_pick_kv4), each in two instances (K Q8_0 / K Q4_0): k_attend_kv4<1 / 2 / 4, false>,
+       // k_attend_kv4<2 / 4, true>, k_attend_gqa2_kv4
+       Q3_ATT4_N1 = 22, Q3_ATT4_N2 = 23, Q3_ATT4_N4 = 24, Q3_ATT4_F2 = 25, Q3_ATT4_F4 = 26, Q3_ATT4_GQA2 = 27 };
 // the launches of q3_attend_paged.hip: q3_launch_qk_prep / q3_attend_pick / q3_launch_attend / q3_launch_kv_prefix(_save) hand over when tbl is set
 int q3_launch_qk_prep_paged(const Q3QkPrep& a, hipStream_t s);
 int q3_attend_pick_paged(const Q3Attend& a);
@@ -459,6 +537,9 @@ struct Q3KvPrefix {
     // store then is k / v [L][Hkv][np * hd] int8 followed by its scales [L][Hkv][np * hd / 32] f16 in the same allocation: pk / pv name the
     // quants. Whole key blocks (quants and scales) are copied for K, positions < P for V.
     int kv8; uint16_t* kd; uint16_t* vd;
+    // Q4_0 blocks (kv4 != 0, with kv8 = 1; as in Q3QkPrep): layer_stride then counts ELEMENTS, a Q4_0 side takes half a byte of each in the
+    // cache and in its store; the scales stay [..][hd / 32] f16 behind the store's quants.
+    int kv4;
     // Paged cache (tbl != null): kc / vc are the page pool, layer_stride its per-layer elements, and slot[j]'s positions go through
     // tbl[slot[j] * tbl_stride + block]. The store keeps its contiguous form.
     const int* tbl; int tbl_stride;
@@ -473,6 +554,9 @@ void q3_launch_kv_prefix_kv8(const Q3KvPrefix& a, hipStream_t s);  // (q3_attend
 // 0: launched (or n == 0); nonzero: refused, nothing launched (hd != Q3_ATT_HD, more than Q3_KVP_MAX entries, a Q8_0 cache without scales)
 int q3_launch_kv_prefix_save(const Q3KvPrefix& a, hipStream_t s);
 int q3_launch_kv_prefix_save_kv8(const Q3KvPrefix& a, hipStream_t s);
+// (q3_attend_kv4.hip; both hand over when kv4 is set. Nonzero: refused, nothing launched)
+int q3_launch_kv_prefix_kv4(const Q3KvPrefix& a, hipStream_t s);
+int q3_launch_kv_prefix_save_kv4(const Q3KvPrefix& a, hipStream_t s);
 void q3_attend_policy(int decode, int prefill);  // test hook (q3tts_k_attend_policy): which kernel variant serves decode / prefill attention (same bits)
 void q3_attend_policy_get(int* decode, int* prefill);
 

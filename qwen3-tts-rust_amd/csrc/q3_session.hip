@@ -1470,6 +1470,7 @@ extern "C" int q3tts_session_set_swap(q3tts_session* s, int64_t arena_bytes) {
     if (s->next_id != 1) return serr(s, Q3TTS_ERR_STATE, "set_swap: valid before the first submission only");
     if (s->stop || s->dead) return serr(s, Q3TTS_ERR_STATE, "set_swap: the session is closing, or its worker failed");
     if (arena_bytes < 0) return serr(s, Q3TTS_ERR_INVALID, "set_swap: arena_bytes is negative (0 turns swapping off)");
+    if (s->e->T.cache.kv4) return serr(s, Q3TTS_ERR_UNSUPPORTED, "set_swap: this engine's cache holds Q4_0 blocks (q3tts_engine_options.kv_type_k / kv_type_v); swap blocks are laid out for the bf16 and the Q8_0 cache");
     if (s->e->kvp_total) return serr(s, Q3TTS_ERR_UNSUPPORTED, "set_swap: this engine's cache is paged (q3tts_engine_options.kv_pages); swap blocks are laid out for the contiguous cache");
     q3tts_engine* e = s->e;
     if (Q3Swap* old = s->swap.exchange(nullptr)) q3_swap_destroy(e, old);

@@ -297,7 +297,7 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
     }
     Q3KvCache& c = t.cache; c.n_ctx = sh.n_ctx; c.n_slots = sh.n_slots;
     c.layer_stride = (size_t)c.n_slots * t.Hkv * c.n_ctx * hd;
-    c.kv8 = sh.kv8 != 0;
+    c.kv8 = sh.kv8 != 0; c.kv4 = sh.kv4;
     if (sh.kv_pages > 0) {  // paged: a pool of kv_pages + 1 pages per layer (page 0 stays zero) and the slots' table, all zero = nothing owned
         c.n_pages = sh.kv_pages; c.tbl_stride = c.n_ctx / 64;
         c.layer_stride = (size_t)(c.n_pages + 1) * t.Hkv * 64 * hd;
@@ -306,8 +306,9 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
     if (c.kv8) {  // Q8_0 cache: per element one byte of quants + 1/16 byte of f16 block scales, the scales behind the quants in one allocation
         int8_t *kq = nullptr, *vq = nullptr;
         const size_t nq = c.layer_stride * L;
-        TRY(q3_dalloc(e, &kq, nq + nq / 16)); TRY(q3_dalloc(e, &vq, nq + nq / 16));
-        c.kc = (uint16_t*)kq; c.vc = (uint16_t*)vq; c.kd = (uint16_t*)(kq + nq); c.vd = (uint16_t*)(vq + nq);
+        const size_t nk = q3_kv4_bytes(c.kv4, 0, nq), nv = q3_kv4_bytes(c.kv4, 1, nq);  // (a Q4_0 side: half a byte of quants per element)
+        TRY(q3_dalloc(e, &kq, nk + nq / 16)); TRY(q3_dalloc(e, &vq, nv + nq / 16));
+        c.kc = (uint16_t*)kq; c.vc = (uint16_t*)vq; c.kd = (uint16_t*)(kq + nk); c.vd = (uint16_t*)(vq + nv);
     } else {
     TRY(q3_dalloc(e, &c.kc, c.layer_stride * L)); TRY(q3_dalloc(e, &c.vc, c.layer_stride * L));
     }

@@ -164,10 +164,13 @@ class CloneConfig(C.Structure):
     ]
 
 
+KV_Q4_0, KV_Q8_0 = 2, 8   # Q3TTS_KV_Q4_0 / Q3TTS_KV_Q8_0: q3tts_engine_options.kv_type_k / kv_type_v
+
+
 # every symbol include/q3tts.h declares (tests check the export list against the header text)
 class EngineOptions(C.Structure):
     """q3tts_engine_options: what q3tts_engine_create_opts takes beyond the config (zero = q3tts_engine_create)."""
-    _fields_ = [("struct_size", C.c_uint32), ("kquant_resident", C.c_int32), ("kv_pages", C.c_int32)]
+    _fields_ = [("struct_size", C.c_uint32), ("kquant_resident", C.c_int32), ("kv_pages", C.c_int32), ("kv_type_k", C.c_int32), ("kv_type_v", C.c_int32)]
 
 
 SYMBOLS = [
@@ -189,6 +192,7 @@ SYMBOLS = [
     "q3tts_session_append_text", "q3tts_k_text_ready",
     "q3tts_k_attention_runs", "q3tts_k_attention_decode_ex", "q3tts_k_attention_pair", "q3tts_k_attend_pick",
     "q3tts_k_attention_runs_kv8", "q3tts_k_attention_decode_kv8", "q3tts_k_attend_pick_kv8",
+    "q3tts_k_attention_runs_kv4", "q3tts_k_attention_decode_kv4", "q3tts_k_attend_pick_kv4", "q3tts_k_kv_prefix_roundtrip_kv4",
     "q3tts_k_attention_runs_paged", "q3tts_k_attention_decode_paged", "q3tts_k_attend_pick_paged", "q3tts_k_kv_prefix_roundtrip",
     "q3tts_get_kv_pages", "q3tts_k_kv_pages_shuffle",
     "q3tts_k_pred_table_row", "q3tts_k_pred_next", "q3tts_k_attention_gather",
@@ -393,6 +397,12 @@ def load_library(path=None):
     lib.q3tts_k_attention_decode_kv8.argtypes = [C.c_int32, f32p, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float,
                                                  C.c_float, i32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.q3tts_k_attend_pick_kv8.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p]
+    # the same with the cache's types named (Q4_0 blocks): two int32 in front of the cache pointers / of the result
+    for name in ("q3tts_k_attention_runs_kv8", "q3tts_k_attention_decode_kv8", "q3tts_k_attend_pick_kv8"):
+        at = list(getattr(lib, name).argtypes)
+        cut = len(at) - (1 if name.endswith("pick_kv8") else 4)
+        getattr(lib, name.replace("kv8", "kv4")).argtypes = at[:cut] + [C.c_int32, C.c_int32] + at[cut:]
+    lib.q3tts_k_kv_prefix_roundtrip_kv4.argtypes = [C.c_int32, vp, vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp]
     lib.q3tts_k_attention_runs_paged.argtypes = lib.q3tts_k_attention_runs.argtypes + [C.c_int32, i32p, C.c_uint16]
     lib.q3tts_k_attention_decode_paged.argtypes = [C.c_int32, f32p, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f32p, f32p, C.c_float,
                                                    C.c_float, i32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -124,9 +124,9 @@ class TtsEngine:
     """src/tts/engine.rs:53-72 — the engine owns weights, contexts and speakers; one utterance at a time per call
     (`&mut self`), or a list through `generate_batch_with_voice` (continuous batching, an extension)."""
 
-    def __init__(self, cfg, tokenizer=None, kquant_resident=False, kv_pages=0):
-        if kv_pages:
-            self._native = native.NativeEngine(cfg, kquant_resident=bool(kquant_resident), kv_pages=kv_pages)
+    def __init__(self, cfg, tokenizer=None, kquant_resident=False, kv_pages=0, kv_types=None):
+        if kv_pages or kv_types:
+            self._native = native.NativeEngine(cfg, kquant_resident=bool(kquant_resident), kv_pages=kv_pages, kv_types=kv_types)
         else:
             self._native = native.NativeEngine(cfg, kquant_resident=True) if kquant_resident else native.NativeEngine(cfg)
         self.cfg = cfg
@@ -149,15 +149,19 @@ class TtsEngine:
         place of the config's (include/q3tts.h states the memory per slot; 256 slots of the 1.7B shape need n_ctx <= 1024 or so).
         kv_cache: None — a given config's own kv_q8_0 is kept (0, bf16, everywhere else); "bf16" — the Talker's K/V cache in bf16, whatever
         the config says; "q8_0" — ggml Q8_0 blocks
-        (q3tts_engine_config.kv_q8_0 = 1: 0.53 of the memory; the results are not the bf16 cache's). Anything else: ValueError.
+        (q3tts_engine_config.kv_q8_0 = 1: 0.53 of the memory; the results are not the bf16 cache's); "q8_0/q4_0" — K in Q8_0, V in ggml
+        Q4_0 blocks (llama.cpp's --cache-type-k q8_0 --cache-type-v q4_0; 0.41 of the memory) and "q4_0" — both in Q4_0 (0.28)
+        (q3tts_engine_options.kv_type_k / kv_type_v; results of their own again; not with kv_pages, and a given config's
+        kv_q8_0 must be 0). Anything else: ValueError.
         kquant_resident: Q4_K / Q5_K / Q6_K tensors of the quant directory (quant = "q5_k_m") stay quantised on the device and are decoded
         inside the GEMM (q3tts_engine_options.kquant_resident): the same results bit for bit in about a third of the weight bytes;
         weight_formats says what each form holds. Opt-in: the default converts them to bf16 at load.
         kv_pages: N >= 1 pages the Talker's bf16 K/V cache (q3tts_engine_options.kv_pages): one pool of N pages of 64 positions for all
         slots — (N + 1) * 2 * t_n_layer * t_n_kv_head * 64 * head_dim * 2 bytes — in place of n_ctx positions per slot; the results are the
         contiguous cache's bit for bit, a request waits while the pool cannot cover its prompt + max_steps. Not with kv_cache = "q8_0"."""
-        if kv_cache not in (None, "bf16", "q8_0"):
-            raise ValueError(f"kv_cache must be None, 'bf16' or 'q8_0', not {kv_cache!r}")
+        kv_types = {"q8_0/q4_0": (_abi.KV_Q8_0, _abi.KV_Q4_0), "q4_0": (_abi.KV_Q4_0, _abi.KV_Q4_0)}.get(kv_cache)
+        if kv_cache not in (None, "bf16", "q8_0") and kv_types is None:
+            raise ValueError(f"kv_cache must be None, 'bf16', 'q8_0', 'q8_0/q4_0' or 'q4_0', not {kv_cache!r}")
         wdir = None
         if model_dir:
             quant_dir = {"q5_k_m": "gguf_q5_k_m", "q8_0": "gguf_q8_0"}.get(quant, "gguf")  # src/tts/engine.rs:91-95
@@ -174,7 +178,7 @@ class TtsEngine:
             cfg = _abi.default_config()
         if quant == "q8_0" and not cfg.talker_q8_0:
             cfg.talker_q8_0 = 2   # the gguf_q8_0 directory is multiplied as llama.cpp multiplies it: Q8_0 x Q8_0 (W8A8)
-        if kv_cache is not None:
+        if kv_cache in ("bf16", "q8_0"):
             cfg.kv_q8_0 = 1 if kv_cache == "q8_0" else 0
         if max_batch is not None:
             cfg.max_batch = int(max_batch)
@@ -184,7 +188,7 @@ class TtsEngine:
             missing = native.CLONE_FILES[0 if clone_files[0] is None else 1]
             raise _abi.Q3Error(f"{missing} not found in {wdir} or in {model_dir}: the clone encoders need both files "
                                f"(found {clone_files[0] or clone_files[1]})")
-        eng = cls(cfg, tok, kquant_resident=kquant_resident, kv_pages=kv_pages)
+        eng = cls(cfg, tok, kquant_resident=kquant_resident, kv_pages=kv_pages, kv_types=kv_types)
         if clone_files[0] is not None:
             try:
                 eng._native.clone_load(wdir)

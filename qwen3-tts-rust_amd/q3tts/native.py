@@ -80,17 +80,20 @@ class GenResult:
 class NativeEngine:
     """q3tts_engine handle. One engine per GPU; not re-entrant (same contract as `&mut self`)."""
 
-    def __init__(self, cfg, kquant_resident=False, kv_pages=0):
+    def __init__(self, cfg, kquant_resident=False, kv_pages=0, kv_types=None):
         """kquant_resident: q3tts_engine_options.kquant_resident — Q4_K / Q5_K / Q6_K tensors of cfg.weights_path stay quantised on the
         device and are decoded inside the GEMM (same bits as the default; fewer bytes).
         kv_pages: q3tts_engine_options.kv_pages — N >= 1 pages the Talker's K/V cache: a pool of N pages of 64 positions shared by all
-        slots instead of n_ctx positions per slot (same bits; requests wait for pages as they wait for a slot)."""
+        slots instead of n_ctx positions per slot (same bits; requests wait for pages as they wait for a slot).
+        kv_types: q3tts_engine_options.kv_type_k / kv_type_v — (_abi.KV_Q8_0, _abi.KV_Q4_0) or (_abi.KV_Q4_0, _abi.KV_Q4_0): the Talker's
+        K/V cache with ggml Q4_0 blocks (0.41 / 0.28 of the bf16 cache's bytes; other results than the bf16 and the Q8_0 cache)."""
         self.lib = _abi.load_library()
         self.cfg = cfg
         self.h = C.c_void_p()
         self._prefixes = weakref.WeakSet()  # destroyed before the engine
-        if kquant_resident or kv_pages:
-            opts = _abi.EngineOptions(C.sizeof(_abi.EngineOptions), 1 if kquant_resident else 0, int(kv_pages))
+        if kquant_resident or kv_pages or kv_types:
+            tk, tv = kv_types or (0, 0)
+            opts = _abi.EngineOptions(C.sizeof(_abi.EngineOptions), 1 if kquant_resident else 0, int(kv_pages), int(tk), int(tv))
             rc = self.lib.q3tts_engine_create_opts(C.byref(cfg), C.byref(opts), C.byref(self.h))
         else:
             rc = self.lib.q3tts_engine_create(C.byref(cfg), C.byref(self.h))
@@ -1173,17 +1176,25 @@ ATTEND_KERNELS_KV8 = {9: "k_attend_kv8<1, false>", 10: "k_attend_kv8<2, false>",
                       13: "k_attend_kv8<4, true>", 14: "k_attend_gqa2_kv8"}
 
 
-def k_attend_pick_kv8(fused, gqa_ratio, n_ctx, n_kv_head, n_seg=0, seg_max_n=0, seg_max_t=0, want_code=False):
+ATTEND_KERNELS_KV4 = {22: "k_attend_kv4<1, false>", 23: "k_attend_kv4<2, false>", 24: "k_attend_kv4<4, false>", 25: "k_attend_kv4<2, true>",
+                      26: "k_attend_kv4<4, true>", 27: "k_attend_gqa2_kv4"}
+
+
+def k_attend_pick_kv8(fused, gqa_ratio, n_ctx, n_kv_head, n_seg=0, seg_max_n=0, seg_max_t=0, want_code=False, kv_types=None):
     """q3tts_k_attend_pick_kv8 (host only): the kernel of csrc/q3_attend_kv8.hip the launcher takes for a launch over a Q8_0 cache under the
-    current policies — its name (want_code: its number 9 .. 14) — or None when the launcher refuses."""
+    current policies — its name (want_code: its number 9 .. 14) — or None when the launcher refuses. kv_types = (k, v): q3tts_k_attend_pick_kv4,
+    a cache with Q4_0 blocks and the kernels 22 .. 27 of csrc/q3_attend_kv4.hip."""
     lib = _abi.load_library()
     k = C.c_int32(-2)
-    rc = lib.q3tts_k_attend_pick_kv8(fused, gqa_ratio, n_ctx, n_seg, seg_max_n, seg_max_t, n_kv_head, C.byref(k))
+    if kv_types:
+        rc = lib.q3tts_k_attend_pick_kv4(fused, gqa_ratio, n_ctx, n_seg, seg_max_n, seg_max_t, n_kv_head, *kv_types, C.byref(k))
+    else:
+        rc = lib.q3tts_k_attend_pick_kv8(fused, gqa_ratio, n_ctx, n_seg, seg_max_n, seg_max_t, n_kv_head, C.byref(k))
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_attend_pick_kv8 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     if k.value < 0:
         return None
-    return k.value if want_code else ATTEND_KERNELS_KV8[k.value]
+    return k.value if want_code else (ATTEND_KERNELS_KV4 if kv_types else ATTEND_KERNELS_KV8)[k.value]
 
 
 def _att_hook_cache_kv8(n_slots, n_kv_head, n_ctx, head_dim, want_cache):
@@ -1195,9 +1206,10 @@ def _att_hook_cache_kv8(n_slots, n_kv_head, n_ctx, head_dim, want_cache):
 
 
 def k_attention_runs_kv8(qkv, runs, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, policy=-1, out_form=0,
-                         want_cache=True, device=0):
+                         want_cache=True, device=0, kv_types=None):
     """q3tts_k_attention_runs_kv8: k_attention_runs over a Q8_0 cache. Returns a dict: out / scale as there, and the cache un-blocked:
-    k_q / v_q int8 [run][n_kv_head][n_ctx][head_dim], k_d / v_d f16 bits [run][n_kv_head][n_ctx][head_dim / 32]."""
+    k_q / v_q int8 [run][n_kv_head][n_ctx][head_dim], k_d / v_d f16 bits [run][n_kv_head][n_ctx][head_dim / 32].
+    kv_types = (k, v): q3tts_k_attention_runs_kv4 — a cache with Q4_0 blocks; a Q4_0 quant comes back as its nibble 0 .. 15."""
     lib = _abi.load_library()
     qkv = np.ascontiguousarray(qkv, dtype=np.float32)
     p0 = np.ascontiguousarray([r[0] for r in runs], dtype=np.int32)
@@ -1208,18 +1220,19 @@ def k_attention_runs_kv8(qkv, runs, n_ctx, n_head, n_kv_head, head_dim, q_norm_w
     sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
     out, sc, _, _ = _att_hook_out(max(int(nn.sum()), 1), n_head * head_dim, out_form, len(runs), n_kv_head, n_ctx, head_dim, False)
     kq, vq, kd, vd = _att_hook_cache_kv8(len(runs), n_kv_head, n_ctx, head_dim, want_cache)
-    rc = lib.q3tts_k_attention_runs_kv8(device, _ptr(qkv, f32p), len(runs), _ptr(nn, i32p), _ptr(p0, i32p), n_ctx, n_head, n_kv_head, head_dim,
-                                        _ptr(qn, f32p), _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, out_form,
-                                        _dp(out), _dp(sc), _dp(kq), _dp(vq), _dp(kd), _dp(vd))
+    fn = lib.q3tts_k_attention_runs_kv4 if kv_types else lib.q3tts_k_attention_runs_kv8
+    rc = fn(device, _ptr(qkv, f32p), len(runs), _ptr(nn, i32p), _ptr(p0, i32p), n_ctx, n_head, n_kv_head, head_dim,
+            _ptr(qn, f32p), _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, out_form,
+            _dp(out), _dp(sc), *(kv_types or ()), _dp(kq), _dp(vq), _dp(kd), _dp(vd))
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_attention_runs_kv8 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return dict(out=out, scale=sc, k_q=kq, v_q=vq, k_d=kd, v_d=vd)
 
 
 def k_attention_decode_kv8(qkv, lens, n_ctx, n_head, n_kv_head, head_dim, q_norm_w, k_norm_w, eps, rope_theta, sections, policy=-1, out_form=0,
-                           want_cache=True, device=0):
+                           want_cache=True, device=0, kv_types=None):
     """q3tts_k_attention_decode_kv8: k_attention_decode_ex (without row_indexed) over a Q8_0 cache. Returns the dict of k_attention_runs_kv8
-    with out [n_slots][n_head * head_dim]."""
+    with out [n_slots][n_head * head_dim]. kv_types = (k, v): q3tts_k_attention_decode_kv4."""
     lib = _abi.load_library()
     qkv = np.ascontiguousarray(qkv, dtype=np.float32)
     ln = np.ascontiguousarray(lens, dtype=np.int32)
@@ -1229,9 +1242,10 @@ def k_attention_decode_kv8(qkv, lens, n_ctx, n_head, n_kv_head, head_dim, q_norm
     sec = None if sections is None else np.ascontiguousarray(sections, dtype=np.int32)
     out, sc, _, _ = _att_hook_out(max(ln.size, 1), n_head * head_dim, out_form, ln.size, n_kv_head, n_ctx, head_dim, False)
     kq, vq, kd, vd = _att_hook_cache_kv8(ln.size, n_kv_head, n_ctx, head_dim, want_cache)
-    rc = lib.q3tts_k_attention_decode_kv8(device, _ptr(qkv, f32p), ln.size, _ptr(ln, i32p), n_ctx, n_head, n_kv_head, head_dim, _ptr(qn, f32p),
-                                          _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, out_form,
-                                          _dp(out), _dp(sc), _dp(kq), _dp(vq), _dp(kd), _dp(vd))
+    fn = lib.q3tts_k_attention_decode_kv4 if kv_types else lib.q3tts_k_attention_decode_kv8
+    rc = fn(device, _ptr(qkv, f32p), ln.size, _ptr(ln, i32p), n_ctx, n_head, n_kv_head, head_dim, _ptr(qn, f32p),
+            _ptr(kn, f32p), eps, rope_theta, None if sec is None else _ptr(sec, i32p), policy, out_form,
+            _dp(out), _dp(sc), *(kv_types or ()), _dp(kq), _dp(vq), _dp(kd), _dp(vd))
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_attention_decode_kv8 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return dict(out=out, scale=sc, k_q=kq, v_q=vq, k_d=kd, v_d=vd)
@@ -1310,6 +1324,18 @@ def k_attention_decode_ex(qkv, lens, n_ctx, n_head, n_kv_head, head_dim, q_norm_
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_attention_decode_ex failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return _att_hook_ret(out, sc, kc, vc)
+
+
+def k_kv_prefix_roundtrip_kv4(k_store, v_store, n_layer, n_kv_head, P, n_ctx, kv_types, device=0):
+    """q3tts_k_kv_prefix_roundtrip_kv4: the stores (uint8: quants, then f16 scales; a cache with Q4_0 blocks of types kv_types) into slot 0
+    of a cache of n_ctx positions and the slot's first P positions saved into zero-filled stores, which come back."""
+    lib = _abi.load_library()
+    ks, vs = (np.ascontiguousarray(a, dtype=np.uint8) for a in (k_store, v_store))
+    ko, vo = np.zeros_like(ks), np.zeros_like(vs)
+    rc = lib.q3tts_k_kv_prefix_roundtrip_kv4(device, _dp(ks), _dp(vs), ks.size, vs.size, n_layer, n_kv_head, P, n_ctx, *kv_types, _dp(ko), _dp(vo))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_kv_prefix_roundtrip_kv4 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return ko, vo
 
 
 def k_kv_prefix_roundtrip(k_store, v_store, P, n_ctx, paged=None, device=0):

@@ -23,7 +23,7 @@ pub struct q3tts_vocoder_config {
     pub lookahead_frames: i32, pub sample_rate: i32,
 }
 #[repr(C)]
-pub struct q3tts_engine_options { pub struct_size: u32, pub kquant_resident: i32, pub kv_pages: i32 }
+pub struct q3tts_engine_options { pub struct_size: u32, pub kquant_resident: i32, pub kv_pages: i32, pub kv_type_k: i32, pub kv_type_v: i32 }
 #[repr(C)]
 pub struct q3tts_engine_config {
     pub model: q3tts_model_config, pub vocoder: q3tts_vocoder_config,

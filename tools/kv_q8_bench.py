@@ -9,6 +9,12 @@ or hung child ends the run there) builds the bf16-cache engine, then the Q8_0-ca
 and q3tts_timings' mean_ctx_tokens / mean_rows is about c — twice, reporting the second call's frame_step_ms. Also per engine:
 q3tts_k_device_bytes, and the logits of q3tts_k_talker_prefill on one 64-row prompt; the child prints the largest |dlogit| / max |logit|
 between the two formats. One JSON line per slot count. Ids with the Q8_0 cache may differ from the bf16 cache's: nothing here is asserted.
+
+--q4 adds the two caches with ggml Q4_0 blocks (q3tts_engine_options.kv_type_k / kv_type_v): "q8_0/q4_0" (K Q8_0, V Q4_0) and
+"q4_0" (both). All engines of a child then live side by side and the timed calls alternate over them, `--rounds` times (bf16, q8_0, q8_0/q4_0,
+q4_0, bf16, ...): each format's frame_step_ms is the median of its rounds and the spread (min .. max) is printed with it. Closeness: the
+first 8 requests of every context once more with temperature 0 on every engine; greedy_code0_differs is the share of their code-0 ids
+(frames x requests) that are not the bf16 cache's. On synthetic weights that says how far the logits move, not how it sounds.
 """
 import argparse
 import json
@@ -23,6 +29,41 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "qwen3-tts-rust_amd"))
 
 N_CTX = 1024
+
+
+MODES_Q4 = {"q8_0/q4_0": (8, 2), "q4_0": (2, 2)}   # (kv_type_k, kv_type_v): Q3TTS_KV_Q8_0 = 8, Q3TTS_KV_Q4_0 = 2
+
+
+def child_q4(slots, ctxs, frames, rounds):
+    from q3tts import _abi, native
+    rng = np.random.default_rng(7)
+    d = _abi.full_config_py().model.d_embed
+    rows = {c: (rng.standard_normal((c - frames // 2, d)) * 0.05).astype(np.float32) for c in ctxs}
+    engs = {}
+    for name in ("bf16", "q8_0", "q8_0/q4_0", "q4_0"):
+        cfg = _abi.full_config_py()
+        cfg.device, cfg.max_batch, cfg.n_ctx, cfg.max_steps_cap, cfg.with_vocoder, cfg.kv_q8_0 = 0, slots, N_CTX, 64, 0, int(name == "q8_0")
+        engs[name] = native.NativeEngine(cfg, kv_types=MODES_Q4.get(name))
+    out = {"max_batch": slots, "n_ctx": N_CTX, "frames": frames, "rounds": rounds}
+    res = {name: {"device_bytes": e.device_bytes()} for name, e in engs.items()}
+    for c in ctxs:
+        kw = dict(embd=rows[c], top_k=40, top_p=0.9, max_steps=frames, min_frames=frames, force_eos_at=frames, want_pcm=0)
+        reqs = [dict(kw, temperature=0.7, seed=i) for i in range(slots)]
+        ms = {name: [] for name in engs}
+        for r in range(rounds + 1):            # round 0 warms every engine up and is not kept
+            for name, e in engs.items():
+                outs = e.generate_batch(reqs)
+                assert all(o.status == 0 and o.n_frames == frames for o in outs)
+                if r:
+                    ms[name].append(e.timings().frame_step_ms)
+        code0 = {name: np.stack([o.codes[:, 0] for o in e.generate_batch([dict(kw, temperature=0.0, seed=i) for i in range(8)])]) for name, e in engs.items()}
+        for name in engs:
+            res[name]["ctx_%d" % c] = {"frame_step_ms": round(float(np.median(ms[name])), 4), "min": round(min(ms[name]), 4), "max": round(max(ms[name]), 4),
+                                       "greedy_code0_differs": round(float((code0[name] != code0["bf16"]).mean()), 4)}
+    for e in engs.values():
+        e.close()
+    out.update(res)
+    print(json.dumps(out))
 
 
 def child(slots, ctxs, frames):
@@ -65,14 +106,16 @@ def main():
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--timeout", type=int, default=900, help="seconds per slot count (its own child process)")
     ap.add_argument("--child", type=int, default=0)
+    ap.add_argument("--q4", action="store_true", help="all four cache formats side by side, alternating (see the module docstring)")
+    ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
     ctxs = [int(x) for x in args.ctx.split(",")]
     if args.child:
-        child(args.child, ctxs, args.frames)
+        child_q4(args.child, ctxs, args.frames, args.rounds) if args.q4 else child(args.child, ctxs, args.frames)
         return 0
     for slots in [int(x) for x in args.slots.split(",")]:
         cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", str(slots), "--ctx", args.ctx,
-               "--frames", str(args.frames)]
+               "--frames", str(args.frames)] + (["--q4", "--rounds", str(args.rounds)] if args.q4 else [])
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         if p.returncode != 0:   # a fault, an abort or a time limit: nothing more is started on the GPU
             print(json.dumps({"max_batch": slots, "failed": p.returncode}))
