@@ -267,14 +267,36 @@ int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine** out);
  * bf16 and Q8_0). struct_size may be that of the struct without these two. */
 #define Q3TTS_KV_Q4_0 2   /* (ggml's type numbers) */
 #define Q3TTS_KV_Q8_0 8
-typedef struct { uint32_t struct_size; int32_t kquant_resident; int32_t kv_pages; int32_t kv_type_k; int32_t kv_type_v; } q3tts_engine_options;
+typedef struct {
+    uint32_t struct_size; int32_t kquant_resident; int32_t kv_pages; int32_t kv_type_k; int32_t kv_type_v;
+    int32_t talker_mxfp4;   /* 1: the Talker's four block matrices (fused QKV, O, gate/up, down) are held ON THE DEVICE as ggml MXFP4 blocks — 32 E2M1
+                             * elements and one E8M0 scale, value 2^(e - 127) * {0, 0.5, 1, 1.5, 2, 3, 4, 6} with a sign — and multiplied on gfx950's
+                             * block-scaled v_mfma_scale_f32_16x16x128_f8f6f4 (csrc/q3_bgemm4.hip). A tensor stored as
+                             * MXFP4 (GGUF type 39) is taken as stored; bf16 / f32 / synthetic weights are quantised on the device at creation
+                             * by ggml's quantize_row_mxfp4 rule in f32, with two stated deviations: floor(log2(amax)) is read from the
+                             * float's exponent field (ggml calls log2f, which can round up to the next integer just below a power of
+                             * two), and e is held at 0 from below where ggml's cast to uint8 wraps. The bf16 row operand
+                             * of each GEMM is converted inside the kernel to MXFP8 (E4M3, one scale 2^(floor(log2 amax) - 8) per 32 columns,
+                             * round to nearest even, saturating); the f32 sums chain k ascending in steps of 128 per K slice, and row scales
+                             * and epilogues are the bf16 path's. A matrix is MXFP4 when its input width is a multiple of 128, else it stays
+                             * bf16; device bytes of an MXFP4 matrix [N][K]: N * K / 32 * 17, no padding (q3tts_get_mxfp4_bytes sums them;
+                             * q3tts_get_weight_formats out[0] then counts only what stayed bf16). The Predictor, lm_head and every table stay
+                             * as they are. Ids are those of neither bf16 nor Q8_0, identical for every batch, slot count, session and prefix;
+                             * parity with llama.cpp's MXFP4 kernels is not pinned. Q3TTS_ERR_INVALID (the message names both settings):
+                             * together with talker_q8_0 != 0, together with kquant_resident. 0 (and a struct_size without the field):
+                             * every launch, allocation and bit as before. */
+} q3tts_engine_options;
 int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3tts_engine_options* opts, q3tts_engine** out);
 /* The paged cache's pool: out[0] pages it can hand out (kv_pages; 0 = the cache is contiguous), out[1] free now, out[2] the most in use at
  * once since creation, out[3] bytes of one page over every layer and KV head, K and V. Call from the thread that drives the engine. */
 int q3tts_get_kv_pages(const q3tts_engine* e, int64_t out[4]);
 /* The decoder matrices' bytes on the device by the form they are held in: out[0] bf16 (or Q8_0 blocks with talker_q8_0 /
- * predictor_q8_0), out[1] Q4_K, out[2] Q5_K, out[3] Q6_K (the tiled sizes of q3tts_k_kq_bytes). */
+ * predictor_q8_0), out[1] Q4_K, out[2] Q5_K, out[3] Q6_K (the tiled sizes of q3tts_k_kq_bytes). With talker_mxfp4 the matrices held
+ * as MXFP4 are NOT in out[0]: out stays four entries long for the callers that exist, and q3tts_get_mxfp4_bytes below reports the fifth
+ * form (the Python eng.weight_formats joins the two). */
 int q3tts_get_weight_formats(const q3tts_engine* e, int64_t out[4]);
+/* The device bytes of the Talker matrices held as MXFP4 (q3tts_engine_options.talker_mxfp4): the sum of N * K / 32 * 17; 0 without the option. */
+int q3tts_get_mxfp4_bytes(const q3tts_engine* e, int64_t* bytes);
 /* Where the engine's vocoder weights came from: 0 = no vocoder (with_vocoder = 0), 1 = the seeded synthetic generator, 2 = the file
  * qwen3_tts_vocoder.gguf (q3tts_engine_config.weights_path). Audio of an engine that answers 1 is the output of random filters. */
 int q3tts_get_vocoder_source(const q3tts_engine* e, int32_t* source);
@@ -1081,6 +1103,15 @@ int q3tts_k_bgemm_q8(int32_t device, const uint16_t* xb, int32_t B, int32_t K, c
  * (seg_type 12 = Q4_K, 13 = Q5_K, 14 = Q6_K; seg_rows multiples of 16 that add up to N; epilogue 2: one segment, the N/2 gate rows, then
  * the N/2 up rows). Runs the device relayout and one launch through the engine's launcher. K % 512 == 0. Equals q3tts_k_bgemm on the
  * bf16-rounded dequantised weights bit for bit. */
+/* The decoder's GEMM on MXFP4 weights (csrc/q3_bgemm4.hip; q3tts_engine_options.talker_mxfp4): xb bf16 bits [B][K],
+ * K % 128 == 0; exactly one of w_f32 [N][K] (quantised on the device by ggml's quantize_row_mxfp4 rule) and w_blocks (ggml block_mxfp4 rows
+ * [N][K/32] x 17 bytes, kept as stored); epilogue 2: the N/2 gate rows, then the N/2 up rows. One launch through the engine's launcher;
+ * outputs as q3tts_k_bgemm. Optional: blocks_out [N][K/32][17] = the weights the device holds, in ggml's block order; a8_out [B][K] /
+ * ae_out [B][K/32] (both or neither) = the rows as the kernel converts them, E4M3 bytes and their E8M0 scales. iters > 0: *mean_ms = the
+ * mean time of that many further launches (epilogue 1 timed as 0), as q3tts_k_bgemm. */
+int q3tts_k_bgemm_mxfp4(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const float* w_f32, const uint8_t* w_blocks, int32_t N,
+                        const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb,
+                        float* ssp_out, uint64_t* keys, uint8_t* blocks_out, uint8_t* a8_out, uint8_t* ae_out, int32_t iters, float* mean_ms);
 int q3tts_k_bgemm_kq(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const uint8_t* raw, const int32_t* seg_rows, const int32_t* seg_type,
                      int32_t n_seg, int32_t N, const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epilogue, const float* nw_next,
                      float* y, uint16_t* yb, float* ssp_out, uint64_t* keys);

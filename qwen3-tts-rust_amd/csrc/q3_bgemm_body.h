@@ -2,6 +2,7 @@
 // kernels of q3_bgemm.hip and the K-quant kernels of q3_bgemmk.hip.
 #pragma once
 #include "q3_kernels.h"
+#include <type_traits>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -92,10 +93,15 @@ struct BgKqRow {
         s_ = sc[(size_t)p * 16];
     }
 };
-template <int RT, int NT, int D, bool NTW, bool Q8, int EK, bool KQ = false>
+// MX: the weights are ggml MXFP4 blocks and the K loop runs on the block-scaled MFMA: BgMx (q3_bgemm4.hip, the only file that instantiates
+// MX = true, defines it before it does) owns the loop's operands; open() issues its first loads, run() is the loop. Every other
+// instantiation holds the empty BgNoMx.
+template <int RT, int NT, int D, bool NTW> struct BgMx;
+struct BgNoMx {};
+template <int RT, int NT, int D, bool NTW, bool Q8, int EK, bool KQ = false, bool MX = false>
 __device__ __forceinline__ void bg_body(const Q3BGemm& g) {
-    static_assert(!(Q8 && KQ), "one weight format");
-    extern __shared__ float part[];  // [8 waves][RT*NT*4 regs][64 lanes]
+    static_assert(!(Q8 && KQ) && !(MX && (Q8 || KQ)), "one weight format");
+    extern __shared__ float part[];  // [8 waves][RT*NT*4 regs][64 lanes]; MX: then [8 waves][RT][128] x 16 bytes of FP8 exchange
     __shared__ float srow[64];
     Q3_STAMP(g, 0);
     constexpr bool ANY = EK < 0;
@@ -155,7 +161,10 @@ __device__ __forceinline__ void bg_body(const Q3BGemm& g) {
     BgKqRow kr[KQ ? NT : 1];                        // KQ: DP pairs in flight, as Q8
     u32x2 kn[KQ ? DP : 1][NT]; uint32_t kh[KQ ? DP : 1][NT], ks[KQ ? DP : 1][NT], kd[KQ ? DP : 1][NT];
     const int kp0 = kb0 >> 1;                       // the slice's first pair in the tile row
-    if constexpr (KQ) {
+    std::conditional_t<MX, BgMx<RT, NT, D, NTW>, BgNoMx> mx;
+    if constexpr (MX) {
+        mx.open(g, nb0, row0, wave, lane);
+    } else if constexpr (KQ) {
 #pragma unroll
         for (int j = 0; j < NT; ++j) kr[j].open(g, nb0 + j, lane);
 #pragma unroll
@@ -257,7 +266,9 @@ __device__ __forceinline__ void bg_body(const Q3BGemm& g) {
     for (int i = 0; i < RT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if constexpr (KQ) {
+    if constexpr (MX) {
+        mx.run(acc, (u32x4*)(part + (size_t)8 * (RT * NT * 4 / BG_PH(RT, NT)) * 64) + (size_t)wave * RT * 128, lane);
+    } else if constexpr (KQ) {
         for (int p0 = 0; p0 < npair; p0 += DP) {
 #pragma unroll
             for (int dp = 0; dp < DP; ++dp) {

@@ -49,6 +49,9 @@ struct Q3Tfm {
     // The tables (8 bytes per 16 rows) are small hipMallocs owned by the engine and not counted in dev_bytes.
     struct Kq { const uint2* tab = nullptr; int bpp = 0; };
     std::vector<Kq> kqkv, ko, kgu, kdn; Kq khead;
+    // q3tts_engine_options.talker_mxfp4 (q3_bgemm4.hip): the block matrices whose K is whole 128-steps hold ggml MXFP4 blocks
+    // in the tiled MX layout (Q3BGemm::mx); per kind (QKV / gate-up: K = d, O: K = nq, down: K = F), the same in every block
+    bool mx_d = false, mx_nq = false, mx_F = false; size_t mx_bytes = 0;
     Q3KvCache cache;
     float *cs = nullptr, *sn = nullptr;  // RoPE tables [cache.n_ctx][hd/2]
     size_t weight_bytes = 0;              // matrix bytes of all layers + head in the form they have on the device
@@ -98,6 +101,7 @@ struct q3tts_engine {
     hipStream_t stream = nullptr, vstream = nullptr;
     std::vector<void*> allocs;          // every q3_dalloc of this engine, freed by q3tts_engine_destroy
     int kquant_resident = 0;            // q3tts_engine_options.kquant_resident
+    int talker_mxfp4 = 0;               // q3tts_engine_options.talker_mxfp4
     size_t dev_bytes = 0;               // bytes handed out by q3_dev_alloc_zeroed so far (q3tts_k_device_bytes)
     Q3Tfm T, P;
     // assets
@@ -260,7 +264,11 @@ inline Q3KvPrefix q3_kv_prefix_of(const Q3Tfm& t) {
 }
 // the transformer's weights, KV cache and RoPE tables. g: the opened GGUF `file` (null: seeded synthetic weights);
 // q8mode: cfg.talker_q8_0 / cfg.predictor_q8_0
-int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode, int kq = 0);
+int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode, int kq = 0, int mx = 0);
+// q3tts_engine_options.talker_mxfp4: whether a block matrix with K input columns is held as MXFP4 (whole 128-steps), and the device bytes
+// the option saves against bf16 on this shape's block matrices (the memory check before allocation)
+inline bool q3_mx4_ok(int K) { return K >= 128 && K % 128 == 0; }
+size_t q3_tfm_mx4_saving(const Q3TfmShape& sh);
 // the bytes a K-quant resident engine saves on this transformer's matrices against bf16: sum of 2 N K - tiled K bytes over the matrices
 // q3_tfm_init (kq = 1) will keep quantised, from the file's tensor headers alone
 size_t q3_tfm_kq_saving(const Q3TfmShape& sh, const Q3Gguf& g);

@@ -87,6 +87,7 @@ size_t type_bytes(uint32_t type, size_t nelem, uint64_t ne0, bool* ok) {
         case Q3_GGML_Q4_K: if (ne0 % 256) { *ok = false; return 0; } return nelem / 256 * 144;
         case Q3_GGML_Q5_K: if (ne0 % 256) { *ok = false; return 0; } return nelem / 256 * 176;
         case Q3_GGML_Q6_K: if (ne0 % 256) { *ok = false; return 0; } return nelem / 256 * 210;
+        case Q3_GGML_MXFP4: if (ne0 % 32) { *ok = false; return 0; } return nelem / 32 * 17;
         default: *ok = false; return 0;
     }
 }
@@ -307,10 +308,19 @@ int Q3Gguf::meta_float_array(const std::string& key, std::vector<double>* v) con
     return Q3_META_OK;
 }
 
+// ggml block_mxfp4 { u8 e; u8 qs[16] }: y[j] = kvalues[qs[j] & 15] * d, y[j + 16] = kvalues[qs[j] >> 4] * d, d = 2^(e - 128) (kvalues: the doubled E2M1 values)
+static void deq_mxfp4(const uint8_t* blk, float* y) {
+    static const float kv[16] = {0.f, 1.f, 2.f, 3.f, 4.f, 6.f, 8.f, 12.f, 0.f, -1.f, -2.f, -3.f, -4.f, -6.f, -8.f, -12.f};
+    const uint32_t e = blk[0], bits = e < 2 ? 0x00200000u << e : (e - 1) << 23;
+    float d; memcpy(&d, &bits, 4);
+    for (int j = 0; j < 16; ++j) { y[j] = kv[blk[1 + j] & 15] * d; y[j + 16] = kv[blk[1 + j] >> 4] * d; }
+}
+
 int q3_gguf_to_f32(const Q3GgufTensor& t, float* dst, std::string& err) {
-    if (!t.data) { err = "tensor '" + t.name + "': unsupported ggml type " + std::to_string(t.type) + " (supported: F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K)"; return -1; }
+    if (!t.data) { err = "tensor '" + t.name + "': unsupported ggml type " + std::to_string(t.type) + " (supported: F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K, MXFP4)"; return -1; }
     const size_t n = t.nelem;
     if (t.type == Q3_GGML_Q4_K || t.type == Q3_GGML_Q5_K || t.type == Q3_GGML_Q6_K) { for (size_t kb = 0; kb < n / 256; ++kb) deq_k_block(t, kb, dst + kb * 256); return 0; }
+    if (t.type == Q3_GGML_MXFP4) { for (size_t b = 0; b < n / 32; ++b) deq_mxfp4(t.data + b * 17, dst + b * 32); return 0; }
     if (t.type == Q3_GGML_F32) memcpy(dst, t.data, n * 4);
     else if (t.type == Q3_GGML_F16) { for (size_t i = 0; i < n; ++i) { uint16_t h; memcpy(&h, t.data + 2 * i, 2); dst[i] = f16_to_f32(h); } }
     else if (t.type == Q3_GGML_BF16) { for (size_t i = 0; i < n; ++i) { uint16_t h; memcpy(&h, t.data + 2 * i, 2); const uint32_t u = (uint32_t)h << 16; memcpy(&dst[i], &u, 4); } }
@@ -326,11 +336,16 @@ int q3_gguf_to_f32(const Q3GgufTensor& t, float* dst, std::string& err) {
 }
 
 int q3_gguf_to_bf16(const Q3GgufTensor& t, uint16_t* dst, std::string& err) {
-    if (!t.data) { err = "tensor '" + t.name + "': unsupported ggml type " + std::to_string(t.type) + " (supported: F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K)"; return -1; }
+    if (!t.data) { err = "tensor '" + t.name + "': unsupported ggml type " + std::to_string(t.type) + " (supported: F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K, MXFP4)"; return -1; }
     if (t.type == Q3_GGML_BF16) { memcpy(dst, t.data, t.nelem * 2); return 0; }
     if (t.type == Q3_GGML_Q4_K || t.type == Q3_GGML_Q5_K || t.type == Q3_GGML_Q6_K) {
         float y[256];
         for (size_t kb = 0; kb < t.nelem / 256; ++kb) { deq_k_block(t, kb, y); for (int j = 0; j < 256; ++j) dst[kb * 256 + j] = f32_to_bf16_rne(y[j]); }
+        return 0;
+    }
+    if (t.type == Q3_GGML_MXFP4) {
+        float y[32];
+        for (size_t b = 0; b < t.nelem / 32; ++b) { deq_mxfp4(t.data + b * 17, y); for (int j = 0; j < 32; ++j) dst[b * 32 + j] = f32_to_bf16_rne(y[j]); }
         return 0;
     }
     const size_t chunk = 1 << 16;
@@ -667,7 +682,7 @@ int vf_check_tensors(const Q3Gguf& g, const std::string& file, const q3tts_vocod
         if (!vf_spec(vc, id.first, id.second, &s)) { err = file + ": no tensor for id (" + std::to_string(id.first) + ", " + std::to_string(id.second) + ")"; return -1; }
         const Q3GgufTensor* t = vf_tensor(g, file, s, whence, err);
         if (!t) return -1;
-        if (!t->data) { err = file + ": tensor '" + s.name + "': unsupported ggml type " + std::to_string(t->type) + " (supported: F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K)"; return -1; }
+        if (!t->data) { err = file + ": tensor '" + s.name + "': unsupported ggml type " + std::to_string(t->type) + " (supported: F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K, MXFP4)"; return -1; }
     }
     return 0;
 }
@@ -970,7 +985,7 @@ int cf_tensors(const Q3CloneFiles& f, const CfSpec& s, const char* whence, const
         VfSpec v; v.name = s.names[i]; v.shape = s.shape;
         const Q3GgufTensor* t = vf_tensor(cf_gguf(f, s), cf_path(f, s), v, whence, err);
         if (!t) return -1;
-        if (!t->data) { err = cf_path(f, s) + ": tensor '" + v.name + "': unsupported ggml type " + std::to_string(t->type) + " (supported: F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K)"; return -1; }
+        if (!t->data) { err = cf_path(f, s) + ": tensor '" + v.name + "': unsupported ggml type " + std::to_string(t->type) + " (supported: F32, F16, BF16, Q8_0, Q4_K, Q5_K, Q6_K, MXFP4)"; return -1; }
         out[i] = t;
     }
     return 0;

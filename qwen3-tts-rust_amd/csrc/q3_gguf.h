@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 
-enum { Q3_GGML_F32 = 0, Q3_GGML_F16 = 1, Q3_GGML_Q8_0 = 8, Q3_GGML_Q4_K = 12, Q3_GGML_Q5_K = 13, Q3_GGML_Q6_K = 14, Q3_GGML_BF16 = 30 };
+enum { Q3_GGML_F32 = 0, Q3_GGML_F16 = 1, Q3_GGML_Q8_0 = 8, Q3_GGML_Q4_K = 12, Q3_GGML_Q5_K = 13, Q3_GGML_Q6_K = 14, Q3_GGML_BF16 = 30, Q3_GGML_MXFP4 = 39 };
 
 struct Q3GgufTensor {
     std::string name;

@@ -91,6 +91,7 @@ struct Q3BGemm {
     const uint16_t* a; int a_row0; int B;       // A-tiled bf16 rows [a_row0, a_row0 + B) of a buffer with K columns
     const uint4* w; int K, N;                   // tiled bf16
     int w_once;                                 // 1: the weights are read once per long interval (Talker decode): non-temporal loads when one workgroup owns a tile
+    int mx;                                     // 1: w holds ggml MXFP4 blocks in the tiled MX layout below (q3_bgemm4.hip); K % 128 == 0. (In the struct's padding: no other field moves.)
     const float* ssp; int ld_ssp; int ntiles; int d_norm; float eps;  // row scale: s_r = 1 / sqrtf(SS(ssp[row][0..ntiles)) / d_norm + eps)
     int epi;
     float* y; int ldy;
@@ -117,6 +118,28 @@ struct Q3BGemm {
     const uint2* kq; int kq_bpp;
     Q3_STAMP_FIELD
 };
+// The tiled MX layout of an [N][K] matrix of ggml MXFP4 blocks (32 x E2M1 + one E8M0 byte), S = K / 128 steps — what one
+// v_mfma_scale_f32_16x16x128_f8f6f4 takes per column tile, as probed on the hardware: lane l = (g, c) of (column tile nb, step s) owns
+// column 16 nb + c, k = 128 s + 32 g .. + 31, i.e. ggml block 4 s + g of that row, and the block's scale.
+//   [0, N K / 2)            elements  [N/16][S][64 lanes] x 16 bytes: element p of the block in nibble p (bits 4 (p & 7) .. of word p >> 3),
+//                                     the E2M1 code ggml stores (ggml's byte order, p | p + 16 per byte, is not kept)
+//   [N K / 2, + N K / 32)   scales    [N/16][S][64 lanes] x 1 byte: the block's E8M0 e as stored; value = 2^(e - 127) * E2M1(q)
+// = 17 bytes per 32 weights, no padding: q3_mx4_bytes. A wave-load of a step is one contiguous KiB + 64 contiguous bytes, naturally aligned.
+Q3_HD size_t q3_mx4_bytes(size_t N, size_t K) { return N * K / 32 * 17; }
+// Fill: rows [row0, row0 + rows) of the physical matrix (mode 1: gate / up interleave 8 + 8 per tile, as Q3Fill) from ONE of: raw ggml
+// block_mxfp4 rows as stored (src4: [rows][K/32] x 17 bytes, e first), f32 rows (srcf), bf16 rows (src), else the synthetic tensor — the last
+// three quantised on the device by ggml's quantize_row_mxfp4 restated in f32.
+struct Q3FillMx {
+    uint8_t* dst; int N, K, mode, row0, rows;
+    uint32_t tid_a, tid_b; uint64_t seed; float scale;
+    const uint16_t* src_a; const uint16_t* src_b; const float* srcf_a; const float* srcf_b; const uint8_t* src4_a; const uint8_t* src4_b;
+};
+void q3_launch_fill_tiled_mx4(const Q3FillMx& f, hipStream_t s);
+// the MXFP4 side of q3_launch_bgemm (q3_bgemm.hip picks the tile instance and calls these)
+int q3_bgemm4_launch(const struct Q3BGemm& g, int rt, int nt, hipStream_t s, int* d, int* ntw);
+int q3_bgemm4_depth(int rt, int nt);
+void q3_bgemm4_prepare();
+void q3_launch_mx_rows(const uint16_t* a, int rows, int K, uint8_t* q8, uint8_t* e8, hipStream_t s);  // test hook: the rows' MXFP8 form, natural order, whole 16-row tiles
 // The tiled K layout of one 16-column tile row over K columns (P = K/64 tile pairs, S = K/256 super-blocks); lane l = (kq, n) of a pair owns
 // the 16 weights its two bf16 fragments would hold: k = 4kq..4kq+3, 16+4kq..16+4kq+3 of 32-block 2p, then of 2p+1 (element e = 0..7 each).
 //   [0, 512 P)            nibbles  uint2 [P][64 lanes]: x = block 2p, y = block 2p+1, element e in bits 4e..4e+3 (the quant's low 4 bits)

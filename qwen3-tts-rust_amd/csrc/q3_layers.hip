@@ -30,18 +30,21 @@ static void y_rows(Q3BGemm& g, const Q3Tfm& t, const Q3Rows& r, const float* nw_
 }
 Q3BGemm q3_gemm_qkv(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, float eps, int once) {
     Q3BGemm g = gemm_w(t.wqkv[l], t.q8 ? t.sqkv[l] : nullptr, t.kqkv[l], t.d, t.nqkv, rows, once);
+    g.mx = t.mx_d;
     a_rows(g, t, r, eps);
     g.epi = Q3_EPI_STORE; g.y = sc.qkv; g.ldy = t.nqkv;
     return g;
 }
 static Q3BGemm gemm_o(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, int once) {
     Q3BGemm g = gemm_w(t.wo[l], t.q8 ? t.so[l] : nullptr, t.ko[l], t.nq, t.d, rows, once);
+    g.mx = t.mx_nq;
     a_scratch(g, t, sc, sc.att, sc.asc_att);
     y_rows(g, t, r, t.ffn_norm[l]);
     return g;
 }
 static Q3BGemm gemm_gate_up(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, float eps, int once) {
     Q3BGemm g = gemm_w(t.wgu[l], t.q8 ? t.sgu[l] : nullptr, t.kgu[l], t.d, 2 * t.F, rows, once);
+    g.mx = t.mx_d;
     a_rows(g, t, r, eps);
     g.epi = Q3_EPI_SWIGLU; g.yb = sc.h;
     if (t.a8) { g.yscale = sc.asc_h; g.y_rt16 = sc.rt16; }
@@ -49,6 +52,7 @@ static Q3BGemm gemm_gate_up(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scra
 }
 static Q3BGemm gemm_down(const Q3Tfm& t, int l, const Q3Rows& r, const Q3Scratch& sc, int rows, int once) {
     Q3BGemm g = gemm_w(t.wd[l], t.q8 ? t.sd[l] : nullptr, t.kdn[l], t.F, t.d, rows, once);
+    g.mx = t.mx_F;
     a_scratch(g, t, sc, sc.h, sc.asc_h);
     y_rows(g, t, r, l + 1 < t.L ? t.attn_norm[l + 1] : t.out_norm);  // the next block's norm, or the head's
     return g;

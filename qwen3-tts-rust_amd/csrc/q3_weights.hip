@@ -53,13 +53,16 @@ struct GgSrc {
     // Q8_0 mode: a tensor stored as Q8_0 goes to the device as it is ([N][K/32] blocks of 34 bytes) into staging buffer `which`
     // (raw[which] = true); any other type is widened to bf16 as below and quantised on the device
     uint8_t* dev8[2] = {nullptr, nullptr}; size_t dev8_cap[2] = {0, 0}; bool raw[2] = {false, false};
-    int mat_q8(const std::string& name, size_t N, size_t K, int which) {
+    int mat_q8(const std::string& name, size_t N, size_t K, int which) { return mat_blocks(name, N, K, which, Q3_GGML_Q8_0, 34); }
+    // MXFP4 mode: the same for a tensor stored as MXFP4 (ggml type 39: [N][K/32] blocks of 17 bytes)
+    int mat_mx4(const std::string& name, size_t N, size_t K, int which) { return mat_blocks(name, N, K, which, Q3_GGML_MXFP4, 17); }
+    int mat_blocks(const std::string& name, size_t N, size_t K, int which, uint32_t type, size_t block_bytes) {
         int rc; const Q3GgufTensor* t = need(name, K, N, &rc);
         if (!t) return rc;
         raw[which] = false;
-        if (t->type != Q3_GGML_Q8_0) return mat(name, N, K, which);
-        const size_t bytes = N * (K / 32) * 34;
-        if (t->nbytes < bytes) return fail("tensor '" + name + "' is shorter than its Q8_0 shape");
+        if (t->type != type) return mat(name, N, K, which);
+        const size_t bytes = N * (K / 32) * block_bytes;
+        if (t->nbytes < bytes) return fail("tensor '" + name + "' is shorter than its block shape");
         if (dev8_cap[which] < bytes) {
             if (dev8[which]) hipFree(dev8[which]);
             dev8[which] = nullptr; dev8_cap[which] = 0;
@@ -87,6 +90,7 @@ struct GgSrc {
     int mat(const std::string& name, size_t N, size_t K, int which) {
         int rc; const Q3GgufTensor* t = need(name, K, N, &rc);
         if (!t) return rc;
+        raw[which] = false;  // (the slot may have held a tensor's blocks: with talker_mxfp4 the head follows MXFP4 matrices through slot 0)
         host.resize(N * K); std::string err;
         if (q3_gguf_to_bf16(*t, host.data(), err)) return fail(err);
         if (dev_cap[which] < N * K) {
@@ -151,7 +155,16 @@ size_t q3_tfm_kq_saving(const Q3TfmShape& sh, const Q3Gguf& g) {
     return saved;
 }
 
-int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode, int kq) {
+size_t q3_tfm_mx4_saving(const Q3TfmShape& sh) {
+    const size_t nq = (size_t)sh.Hq * sh.hd, nqkv = nq + 2 * (size_t)sh.Hkv * sh.hd;
+    size_t n = 0;  // weights that leave bf16
+    if (q3_mx4_ok(sh.d)) n += (nqkv + 2 * (size_t)sh.F) * sh.d;
+    if (q3_mx4_ok((int)nq)) n += (size_t)sh.d * nq;
+    if (q3_mx4_ok(sh.F)) n += (size_t)sh.d * sh.F;
+    return (size_t)sh.L * (2 * n - q3_mx4_bytes(n, 1));
+}
+
+int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode, int kq, int mx) {
     const bool q8 = q8mode != 0;
     const int grp = sh.grp, L = sh.L, d = sh.d, hd = sh.hd, F = sh.F;
     t.L = L; t.d = d; t.Hq = sh.Hq; t.Hkv = sh.Hkv; t.hd = hd; t.F = F; t.nq = sh.Hq * hd; t.nkv = sh.Hkv * hd; t.nqkv = t.nq + 2 * t.nkv;
@@ -166,16 +179,28 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
     if (q8) { t.sqkv.assign(L, nullptr); t.so.assign(L, nullptr); t.sgu.assign(L, nullptr); t.sd.assign(L, nullptr); }
     // a matrix [N][K]: bf16 tiles (2 bytes per weight), or in Q8_0 mode block quants (1 byte) + f16 block scales [N][K/32]
     const size_t wdiv = q8 ? 16 : 8;  // weights per uint4
+    // talker_mxfp4: a block matrix with whole 128-steps is 17 bytes per 32 weights in the tiled MX layout; the others stay bf16
+    if (mx) { t.mx_d = q3_mx4_ok(d); t.mx_nq = q3_mx4_ok(sh.Hq * hd); t.mx_F = q3_mx4_ok(F); }
+    auto is_mx = [&](size_t K) { return mx && q3_mx4_ok((int)K); };
     auto alloc_mat = [&](uint4** w, uint16_t** sc, size_t N, size_t K) -> int {
+        if (is_mx(K) && w != &t.head) { uint8_t* p = nullptr; TRY(q3_dalloc(e, &p, q3_mx4_bytes(N, K))); *w = (uint4*)p; return Q3TTS_OK; }
         TRY(q3_dalloc(e, w, N * K / wdiv));
         if (q8) TRY(q3_dalloc(e, sc, N * K / 32));
         return Q3TTS_OK;
     };
-    auto fill = [&](Q3Fill& f, uint16_t* sc) { if (q8) { f.dst_scale = sc; q3_launch_fill_tiled_q8(f, s); } else q3_launch_fill_tiled(f, s); };
-    auto stage = [&](const std::string& name, size_t N, size_t K, int which) -> int { return q8 ? gg->mat_q8(name, N, K, which) : gg->mat(name, N, K, which); };
+    auto fill = [&](Q3Fill& f, uint16_t* sc) {
+        if (is_mx(f.K) && f.dst != t.head) {  // quantised on the device from the bf16 rows / the synthetic tensor (ggml's quantize_row_mxfp4)
+            Q3FillMx m{}; m.dst = (uint8_t*)f.dst; m.N = f.N; m.K = f.K; m.mode = f.mode; m.row0 = f.row0; m.rows = f.rows; m.tid_a = f.tid_a; m.tid_b = f.tid_b;
+            m.seed = f.seed; m.scale = f.scale; m.src_a = f.src_a; m.src_b = f.src_b; m.src4_a = f.src8_a; m.src4_b = f.src8_b;  // (a type-39 tensor: its blocks as stored)
+            q3_launch_fill_tiled_mx4(m, s);
+        } else if (q8) { f.dst_scale = sc; q3_launch_fill_tiled_q8(f, s); } else q3_launch_fill_tiled(f, s);
+    };
+    auto stage = [&](const std::string& name, size_t N, size_t K, int which, bool mxdst) -> int {
+        return mxdst ? gg->mat_mx4(name, N, K, which) : (q8 ? gg->mat_q8(name, N, K, which) : gg->mat(name, N, K, which));
+    };
     // rows [row0, row0 + rows) of dst [Ntot][K] <- the file's tensor `name` (through staging slot 0, which the next tensor reuses)
     auto put = [&](const std::string& name, uint4* dst, uint16_t* sc, int Ntot, int K, int row0, int rows) -> int {
-        TRY(stage(name, rows, K, 0));
+        TRY(stage(name, rows, K, 0, is_mx(K) && dst != t.head));
         Q3Fill f{}; f.dst = dst; f.N = Ntot; f.K = K; f.mode = 0; f.row0 = row0; f.rows = rows;
         gg->source(0, &f.src_a, &f.src8_a);
         fill(f, sc);
@@ -236,8 +261,13 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
         if (!r_d) TRY(alloc_mat(&t.wd[l], &sc_d, d, F));
         if (q8) { t.sqkv[l] = sc_qkv; t.so[l] = sc_o; t.sgu[l] = sc_gu; t.sd[l] = sc_d; }
         {
-            const size_t b_qkv = r_qkv ? r_qkv : (size_t)(bpw * (double)((size_t)t.nqkv * d)), b_o = r_o ? r_o : (size_t)(bpw * (double)((size_t)d * t.nq));
-            const size_t b_gu = r_gu ? r_gu : (size_t)(bpw * (double)(2ull * F * d)), b_d = r_d ? r_d : (size_t)(bpw * (double)((size_t)F * d));
+            auto mb = [&](size_t N, size_t K) { return is_mx(K) ? q3_mx4_bytes(N, K) : (size_t)(bpw * (double)(N * K)); };
+            const size_t b_qkv = r_qkv ? r_qkv : mb(t.nqkv, d), b_o = r_o ? r_o : mb(d, t.nq);
+            const size_t b_gu = r_gu ? r_gu : mb(2ull * F, d), b_d = r_d ? r_d : mb(d, F);
+            if (mx) {  // (never together with Q8_0 or K-quants) the MXFP4 matrices are counted apart from the bf16 ones
+                const size_t m4 = (t.mx_d ? b_qkv + b_gu : 0) + (t.mx_nq ? b_o : 0) + (t.mx_F ? b_d : 0);
+                t.mx_bytes += m4; t.fmt_bytes[0] -= m4;
+            }
             t.weight_bytes += b_qkv + b_o + b_gu + b_d;
             t.fmt_bytes[0] += (r_qkv ? 0 : b_qkv) + (r_o ? 0 : b_o) + (r_gu ? 0 : b_gu) + (r_d ? 0 : b_d);
             if (l == 0) t.qkv0_bytes = b_qkv;
@@ -254,10 +284,10 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
             }
             if (!r_o) TRY(put(b + "attn_output.weight", t.wo[l], sc_o, d, t.nq, 0, d));
             if (!r_gu) {
-            TRY(stage(b + "ffn_gate.weight", F, d, 0)); TRY(stage(b + "ffn_up.weight", F, d, 1));
+            TRY(stage(b + "ffn_gate.weight", F, d, 0, is_mx(d))); TRY(stage(b + "ffn_up.weight", F, d, 1, is_mx(d)));
             Q3Fill f{}; f.dst = t.wgu[l]; f.N = 2 * F; f.K = d; f.mode = 1; f.row0 = 0; f.rows = d;
             gg->source(0, &f.src_a, &f.src8_a); gg->source(1, &f.src_b, &f.src8_b);
-            if (gg->raw[0] != gg->raw[1]) return gg->fail("ffn_gate / ffn_up of block " + std::to_string(l) + " differ in type (one Q8_0, one not)");
+            if (gg->raw[0] != gg->raw[1]) return gg->fail("ffn_gate / ffn_up of block " + std::to_string(l) + " differ in type (one kept as blocks, one not)");
             fill(f, sc_gu);
             Q3_HIP(e, hipStreamSynchronize(s));
             }
