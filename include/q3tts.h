@@ -285,6 +285,22 @@ typedef struct {
                              * parity with llama.cpp's MXFP4 kernels is not pinned. Q3TTS_ERR_INVALID (the message names both settings):
                              * together with talker_q8_0 != 0, together with kquant_resident. 0 (and a struct_size without the field):
                              * every launch, allocation and bit as before. */
+    int32_t talker_mxfp8;   /* 1: the same four matrices are held ON THE DEVICE as MXFP8 blocks — 32 E4M3 elements and one E8M0 scale, value
+                             * 2^(E - 127) * E4M3(q) — and multiplied on the same instruction with FP8 on both sides (k_bgemm_mx8 in
+                             * csrc/q3_bgemm4.hip): half of bf16's bytes, no vector work per block, three mantissa bits more
+                             * than MXFP4. ggml has no MXFP8 tensor type, so nothing is taken as stored: every file type (Q8_0 and K-quant
+                             * files included, which are thereby rounded twice) goes through the bf16 values the default loader uploads, and
+                             * those are quantised on the device at creation by the OCP MX v1.0 rule the row operand gets: per 32 columns of
+                             * one output row E = max(exponent field of the largest magnitude - 8, 0), 0 for a zero block; elements
+                             * x * 2^(127 - E) to E4M3, round to nearest even, saturating at 448. Row operand, sums, row scales and epilogues are
+                             * talker_mxfp4's. A matrix is MXFP8 when its input width is a multiple of 128, else it stays bf16; device bytes
+                             * of an MXFP8 matrix [N][K]: N * K / 32 * 33, no padding (q3tts_get_mxfp8_bytes sums them;
+                             * q3tts_get_weight_formats out[0] then counts only what stayed bf16). The Predictor, lm_head, every table and
+                             * every K/V cache mode stay as they are and combine with it. Ids are those of neither bf16, Q8_0 nor MXFP4,
+                             * identical for every batch, slot count, session and prefix; parity with anything outside this library is not
+                             * pinned. Q3TTS_ERR_INVALID (the message names both settings): together with talker_mxfp4, with
+                             * talker_q8_0 != 0, with kquant_resident. 0 (and a struct_size that ends behind talker_mxfp4): every launch,
+                             * allocation and bit as before. */
 } q3tts_engine_options;
 int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3tts_engine_options* opts, q3tts_engine** out);
 /* The paged cache's pool: out[0] pages it can hand out (kv_pages; 0 = the cache is contiguous), out[1] free now, out[2] the most in use at
@@ -297,6 +313,9 @@ int q3tts_get_kv_pages(const q3tts_engine* e, int64_t out[4]);
 int q3tts_get_weight_formats(const q3tts_engine* e, int64_t out[4]);
 /* The device bytes of the Talker matrices held as MXFP4 (q3tts_engine_options.talker_mxfp4): the sum of N * K / 32 * 17; 0 without the option. */
 int q3tts_get_mxfp4_bytes(const q3tts_engine* e, int64_t* bytes);
+/* The device bytes of the Talker matrices held as MXFP8 (q3tts_engine_options.talker_mxfp8): the sum of N * K / 32 * 33; 0 without the option
+ * (and q3tts_get_mxfp4_bytes answers 0 on such an engine). */
+int q3tts_get_mxfp8_bytes(const q3tts_engine* e, int64_t* bytes);
 /* Where the engine's vocoder weights came from: 0 = no vocoder (with_vocoder = 0), 1 = the seeded synthetic generator, 2 = the file
  * qwen3_tts_vocoder.gguf (q3tts_engine_config.weights_path). Audio of an engine that answers 1 is the output of random filters. */
 int q3tts_get_vocoder_source(const q3tts_engine* e, int32_t* source);
@@ -1112,6 +1131,13 @@ int q3tts_k_bgemm_q8(int32_t device, const uint16_t* xb, int32_t B, int32_t K, c
 int q3tts_k_bgemm_mxfp4(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const float* w_f32, const uint8_t* w_blocks, int32_t N,
                         const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb,
                         float* ssp_out, uint64_t* keys, uint8_t* blocks_out, uint8_t* a8_out, uint8_t* ae_out, int32_t iters, float* mean_ms);
+/* The same on MXFP8 weights (k_bgemm_mx8; q3tts_engine_options.talker_mxfp8): w_f32 [N][K] only — rounded to bf16
+ * (nearest even) and quantised on the device by the rows' rule; there is no raw-blocks input. Outputs as q3tts_k_bgemm_mxfp4; q_out [N][K]
+ * E4M3 bytes and e_out [N][K/32] E8M0 bytes (optional, both or neither) = the weights the device holds, in plain row order (epilogue 2: the
+ * N/2 gate rows, then the N/2 up rows); a8_out / ae_out and iters / mean_ms as there. q3tts_k_bgemm_force applies. */
+int q3tts_k_bgemm_mxfp8(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const float* w_f32, int32_t N,
+                        const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb,
+                        float* ssp_out, uint64_t* keys, uint8_t* q_out, uint8_t* e_out, uint8_t* a8_out, uint8_t* ae_out, int32_t iters, float* mean_ms);
 int q3tts_k_bgemm_kq(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const uint8_t* raw, const int32_t* seg_rows, const int32_t* seg_type,
                      int32_t n_seg, int32_t N, const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epilogue, const float* nw_next,
                      float* y, uint16_t* yb, float* ssp_out, uint64_t* keys);

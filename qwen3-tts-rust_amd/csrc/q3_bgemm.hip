@@ -268,6 +268,7 @@ void q3_bgemm_prepare() {  // once per DEVICE (function attributes are per devic
 #undef P
         q3_bgemmk_prepare();
         q3_bgemm4_prepare();
+        q3_bgemm_mx8_prepare();
     });
 }
 
@@ -307,7 +308,7 @@ static void bg_pick(const Q3BGemm& g, int* rt, int* nt, int* big) {
             if (g.B <= 64 && RT > 1 && 16 * (RT - 1) * chunks >= g.B) continue;  // a smaller RT covers the rows with the same chunk count
             const long wgs = (long)(tiles / NT) * chunks, rounds = (wgs + 255) / 256;
             // + a fixed cost per round (ramp, reduction); Q8_0 weights: 17 bytes per k per column tile; K-quants: the tile rows' own bytes (kq_bpp per 64 k)
-            const long wk = g.kq ? (long)g.kq_bpp * NT * (g.K >> 6) : (g.mx ? 17L * NT * g.K / 2 : (g.wscale ? 17L : 32L) * NT * g.K);  // (MXFP4: 8.5 bytes per k per column tile)
+            const long wk = g.kq ? (long)g.kq_bpp * NT * (g.K >> 6) : (g.mx ? (g.mx == 2 ? 33L : 17L) * NT * g.K / 2 : (g.wscale ? 17L : 32L) * NT * g.K);  // (MXFP4: 8.5 bytes per k per column tile, MXFP8: 16.5)
             const long cost = rounds * (32L * RT * g.K + wk + 24000L);
             // equal cost: more workgroups, then the wider column tile; at 65 .. 512 rows the wider column tile first (the sweep: (2,2) over (3,1))
             const bool tie = mid ? (NT > bestNT || (NT == bestNT && wgs > bestWgs)) : (wgs > bestWgs || (wgs == bestWgs && NT > bestNT));
@@ -322,7 +323,7 @@ void q3_bgemm_pick(const Q3BGemm& g, int* rt, int* nt, int* d, int* ntw, int* bi
     bg_pick(g, rt, nt, big);
     *d = 0; *ntw = 0;
     if (*big) return;
-    if (g.mx) { *d = q3_bgemm4_depth(*rt, *nt); *ntw = (g.w_once && (g.B + 16 * *rt - 1) / (16 * *rt) == 1) ? 1 : 0; return; }
+    if (g.mx) { *d = g.mx == 2 ? q3_bgemm_mx8_depth(*rt, *nt) : q3_bgemm4_depth(*rt, *nt); *ntw = (g.w_once && (g.B + 16 * *rt - 1) / (16 * *rt) == 1) ? 1 : 0; return; }
     if (g.kq) { *d = q3_bgemmk_depth(*rt, *nt); *ntw = (g.w_once && (g.B + 16 * *rt - 1) / (16 * *rt) == 1) ? 1 : 0; return; }
 #define X(RT_, NT_) if (*rt == RT_ && *nt == NT_) *d = BgInst<RT_, NT_>::D;
     BG_EACH(X)
@@ -331,8 +332,8 @@ void q3_bgemm_pick(const Q3BGemm& g, int* rt, int* nt, int* d, int* ntw, int* bi
 }
 
 static int bg_check(const Q3BGemm& g) {
-    if (g.mx) {  // MXFP4 weights: whole 128-steps; STORE / RESID / SWIGLU / ARGMAX as below
-        if (g.B < 1 || g.N % 16 || g.K % 128 || g.K < 128 || !g.a || !g.w || g.a_row0 < 0 || g.wscale || g.kq || g.ascale) return -1;
+    if (g.mx) {  // MXFP4 / MXFP8 weights: whole 128-steps; STORE / RESID / SWIGLU / ARGMAX as below
+        if (g.B < 1 || g.N % 16 || g.K % 128 || g.K < 128 || !g.a || !g.w || g.a_row0 < 0 || g.wscale || g.kq || g.ascale || g.mx > 2) return -1;
     } else
     if (g.B < 1 || g.N % 16 || g.K % 256 || g.K < 256 || !g.a || !g.w || g.a_row0 < 0) return -1;
     if (g.wscale && g.K % 512) return -1;  // Q8_0: two blocks per 16-byte weight load, an even number of blocks per K slice
@@ -352,7 +353,7 @@ int q3_launch_bgemm(const Q3BGemm& g, hipStream_t s) {
     if (big) { bg_note_launch(8, 8, 0, false, 1, BG_EK_ANY); bg_launch_big(g, s); return 0; }
     if (g.mx) {
         int d = 0, ntw = 0;
-        if (q3_bgemm4_launch(g, bestRT, bestNT, s, &d, &ntw)) return -1;
+        if (g.mx == 2 ? q3_bgemm_mx8_launch(g, bestRT, bestNT, s, &d, &ntw) : q3_bgemm4_launch(g, bestRT, bestNT, s, &d, &ntw)) return -1;
         bg_note_launch(bestRT, bestNT, d, ntw != 0, 0, BG_EK_ANY);
         return 0;
     }

@@ -4,12 +4,17 @@
 // vector work behind the MFMA (Q8_0, §4.1c) and no decode in front of it (K-quants, §30).
 //
 // Split of the work: k_bgemm's — a workgroup = 8 waves = 8 K-slices of one (RT*16) x (NT*16) output tile, partials meet in LDS and are
-// added in wave order, every epilogue is bg_body's own code. The K loop is bg_body<..., MX = true> (q3_bgemm_body.h): a wave's slice is
+// added in wave order, every epilogue is bg_body's own code. The K loop is bg_body<..., MX = 1> (q3_bgemm_body.h): a wave's slice is
 // whole 128-steps, ceil(K / 1024) of them, so the split depends on K alone; per step the wave converts its RT row tiles once (lane = one
 // 32-block of one row: amax, scale, 16 packed conversions, all in the lane), passes the bytes through 2 KiB of its own LDS into the
 // instruction's operand order, and reuses them for the NT column tiles. Weights stream through a register ring D steps deep (5 registers
 // per column tile and 128 k against the bf16 ring's 16), with non-temporal loads when a tile is read by one workgroup.
 // Here: the kernels, their launch (the tile instance is q3_bgemm.hip's choice) and the quantising / relayout kernel.
+//
+// Second half of the file: the same instruction with FP8 on BOTH sides (talker_mxfp8) — the weights are MXFP8 blocks (32 x
+// E4M3 + one E8M0 scale: 8.25 bits per weight), made at load from the bf16 weights by the very conversion the rows get (bg_mx_block: one
+// copy). k_bgemm_mx8 = bg_body<..., MX = 2>; its K loop is BgMx8, a sibling of BgMx that shares the row side (BgMxRows) and differs in the
+// weight ring: two 16-byte loads and a scale byte per column tile and step (9 registers against 5), so the rings are shallower.
 #include "q3_bgemm_body.h"
 
 // MX: the weights are ggml MXFP4 blocks in the tiled MX layout (q3_kernels.h) and the K loop runs on the block-scaled
@@ -36,9 +41,11 @@ __device__ __forceinline__ uint32_t bg_mx_cvt4(uint32_t w0, uint32_t w1, uint32_
     hi = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(hi, __builtin_bit_cast(bf16x2, c1), sc, false);
     return ((uint32_t)__builtin_bit_cast(uint32_t, lo) & 0xffffu) | ((uint32_t)__builtin_bit_cast(uint32_t, hi) << 16);
 }
-// raw: the lane's block as the A-tiled layout holds it (raw[j].x, .y = k 4j .. 4j + 3, .z, .w = k 16 + 4j .. 16 + 4j + 3); xw: the wave's
-// exchange area for this row tile, 128 x 16 bytes. Returns the operand registers and the scale byte of the lane.
-__device__ __forceinline__ void bg_mx_rows(const u32x4 (&raw)[4], u32x4* xw, int lane, i32x8* a8, uint32_t* e8) {
+// raw: the lane's block as the A-tiled layout holds it (raw[j].x, .y = k 4j .. 4j + 3, .z, .w = k 16 + 4j .. 16 + 4j + 3).
+// bg_mx_block: one 32-block of bf16 bits -> its E8M0 scale (returned) and its E4M3 bytes, k 0 .. 15 in lo and 16 .. 31 in hi (the rows of
+// both kernels and the MXFP8 weights at load go through this one copy). bg_mx_rows: xw = the wave's exchange area for this row tile,
+// 128 x 16 bytes; returns the operand registers and the scale byte of the lane.
+__device__ __forceinline__ uint32_t bg_mx_block(const u32x4 (&raw)[4], u32x4& lo, u32x4& hi) {
     uint32_t m = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -47,11 +54,15 @@ __device__ __forceinline__ void bg_mx_rows(const u32x4 (&raw)[4], u32x4* xw, int
     }
     const uint32_t E = bg_mx_e(max(m & 0xffffu, m >> 16)), lim = (((E + 8u) << 7) | 0x60u) * 0x10001u;
     const float sc = __uint_as_float(E << 23);
-    u32x4 lo, hi;  // k 0 .. 15 and 16 .. 31 of the block
     lo.x = bg_mx_cvt4(raw[0].x, raw[0].y, lim, sc); lo.y = bg_mx_cvt4(raw[1].x, raw[1].y, lim, sc);
     lo.z = bg_mx_cvt4(raw[2].x, raw[2].y, lim, sc); lo.w = bg_mx_cvt4(raw[3].x, raw[3].y, lim, sc);
     hi.x = bg_mx_cvt4(raw[0].z, raw[0].w, lim, sc); hi.y = bg_mx_cvt4(raw[1].z, raw[1].w, lim, sc);
     hi.z = bg_mx_cvt4(raw[2].z, raw[2].w, lim, sc); hi.w = bg_mx_cvt4(raw[3].z, raw[3].w, lim, sc);
+    return E;
+}
+__device__ __forceinline__ void bg_mx_rows(const u32x4 (&raw)[4], u32x4* xw, int lane, i32x8* a8, uint32_t* e8) {
+    u32x4 lo, hi;
+    const uint32_t E = bg_mx_block(raw, lo, hi);
     const int b = lane >> 4, r = lane & 15, g0 = 2 * (b & 1), vg = b >> 1;  // block b: lanes (g0, r) and (g0 + 1, r), registers 4 vg .. 4 vg + 3
     // a wave-synchronous exchange: nothing may move across the two barriers (the area is the wave's own; LDS operations of a wave complete in order)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();  // the last step's loads are behind us
@@ -62,12 +73,35 @@ __device__ __forceinline__ void bg_mx_rows(const u32x4 (&raw)[4], u32x4* xw, int
     *a8 = (i32x8){(int)p0.x, (int)p0.y, (int)p0.z, (int)p0.w, (int)p1.x, (int)p1.y, (int)p1.z, (int)p1.w};
     *e8 = E;
 }
+// The row side of both MX K loops (BgMx, BgMx8): one step of bf16 rows in registers, converted per step.
+template <int RT>
+struct BgMxRows {
+    u32x4 mraw[RT][4]; const u32x4* map[RT];
+    // lane (kq, r): block kq of the step, row r of the tile: 4 x 16 bytes, 256 apart; s40: the wave's first step; kblocks = K / 32
+    __device__ __forceinline__ void rows_open(const Q3BGemm& g, int row0, int s40, int kblocks, int kq, int r) {
+#pragma unroll
+        for (int i = 0; i < RT; ++i) {
+            const int R = g.a_row0 + min(row0 + 16 * i + r, g.B - 1);
+            map[i] = (const u32x4*)g.a + ((size_t)(R >> 4) * kblocks + 4 * s40 + kq) * 64 + (R & 15);
+        }
+    }
+    __device__ __forceinline__ void rows_load(int s) {  // step s of the wave's slice
+#pragma unroll
+        for (int i = 0; i < RT; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mraw[i][q] = map[i][(size_t)s * 256 + q * 16];
+    }
+    __device__ __forceinline__ void rows_convert(u32x4* xw, int lane, i32x8 (&a8)[RT], uint32_t (&e8)[RT]) {
+#pragma unroll
+        for (int i = 0; i < RT; ++i) bg_mx_rows(mraw[i], xw + i * 128, lane, &a8[i], &e8[i]);
+    }
+};
 // The MX K loop's operands (bg_body holds one as `mx`): D steps of weights in a register ring (16 bytes of FP4 + a scale byte per column
-// tile and step) and one step of bf16 rows.
+// tile and step) and, in BgMxRows, one step of bf16 rows.
 template <int RT, int NT, int D, bool NTW>
-struct BgMx {
-    u32x4 mw[D][NT], mraw[RT][4]; uint32_t ms[D][NT];
-    const u32x4* mwp[NT]; const uint8_t* msp[NT]; const u32x4* map[RT];
+struct BgMx : BgMxRows<RT> {
+    u32x4 mw[D][NT]; uint32_t ms[D][NT];
+    const u32x4* mwp[NT]; const uint8_t* msp[NT];
     int n4;  // the wave's steps
     __device__ __forceinline__ void open(const Q3BGemm& g, int nb0, int row0, int wave, int lane) {
         const int S4 = g.K >> 7, per4 = (S4 + 7) >> 3, s40 = wave * per4, kblocks = g.K >> 5, kq = lane >> 4, r = lane & 15;
@@ -78,11 +112,7 @@ struct BgMx {
             mwp[j] = (const u32x4*)g.w + ((size_t)(nb0 + j) * S4 + s40) * 64 + lane;
             msp[j] = splane + ((size_t)(nb0 + j) * S4 + s40) * 64 + lane;
         }
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {  // lane (b, r): block b of the step, row r of the tile: 4 x 16 bytes, 256 apart
-            const int R = g.a_row0 + min(row0 + 16 * i + r, g.B - 1);
-            map[i] = (const u32x4*)g.a + ((size_t)(R >> 4) * kblocks + 4 * s40 + kq) * 64 + (R & 15);
-        }
+        this->rows_open(g, row0, s40, kblocks, kq, r);
         if (n4 > 0) {  // (a K of fewer than 8 steps leaves the last waves without work: they add zeros)
 #pragma unroll
             for (int d = 0; d < D; ++d) {
@@ -90,10 +120,7 @@ struct BgMx {
 #pragma unroll
                 for (int j = 0; j < NT; ++j) { mw[d][j] = bg_ldw(mwp[j] + so, NTW); ms[d][j] = msp[j][so]; }
             }
-#pragma unroll
-            for (int i = 0; i < RT; ++i)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) mraw[i][q] = map[i][q * 16];
+            this->rows_load(0);
         }
     }
     // xw: the wave's exchange area, RT x 2 KiB
@@ -104,15 +131,9 @@ struct BgMx {
                 const int s = s0 + d;
                 if (s < n4) {
                     i32x8 a8[RT]; uint32_t e8[RT];
-#pragma unroll
-                    for (int i = 0; i < RT; ++i) bg_mx_rows(mraw[i], xw + i * 128, lane, &a8[i], &e8[i]);
+                    this->rows_convert(xw, lane, a8, e8);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (s + 1 < n4) {  // the next step's rows travel while this step's MFMAs run
-#pragma unroll
-                        for (int i = 0; i < RT; ++i)
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) mraw[i][q] = map[i][(size_t)(s + 1) * 256 + q * 16];
-                    }
+                    if (s + 1 < n4) this->rows_load(s + 1);  // the next step's rows travel while this step's MFMAs run
 #pragma unroll
                     for (int j = 0; j < NT; ++j) {
                         const i32x8 b4 = (i32x8){(int)mw[d][j].x, (int)mw[d][j].y, (int)mw[d][j].z, (int)mw[d][j].w, 0, 0, 0, 0};
@@ -191,17 +212,21 @@ __device__ __forceinline__ uint32_t mx4_best(float x, float d) {
     }
     return best;
 }
+// where row c of column tile nb of a fill comes from: the tensor, the row's index in it, and that tensor's sources (Q3FillMx)
+__device__ __forceinline__ void mx_fill_src(const Q3FillMx& f, int nb, int c, uint32_t& tid, size_t& lr, const uint16_t*& src, const float*& srcf, const uint8_t*& src4) {
+    if (f.mode == 0) { tid = f.tid_a; lr = (size_t)(nb * 16 + c - f.row0); src = f.src_a; srcf = f.srcf_a; src4 = f.src4_a; }
+    else if (c < 8) { tid = f.tid_a; lr = (size_t)nb * 8 + c; src = f.src_a; srcf = f.srcf_a; src4 = f.src4_a; }
+    else { tid = f.tid_b; lr = (size_t)nb * 8 + c - 8; src = f.src_b; srcf = f.srcf_b; src4 = f.src4_b; }
+}
 __global__ __launch_bounds__(256) void k_fill_tiled_mx4(Q3FillMx f, int nb0, int nb_count) {
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int S = f.K >> 7, kblocks = f.K >> 5;
     if (gid >= (size_t)nb_count * S * 64) return;
     const int lane = (int)(gid & 63), g = lane >> 4, c = lane & 15;
     const int s = (int)((gid >> 6) % S), nb = nb0 + (int)((gid >> 6) / S);
-    const int n = nb * 16 + c, kb = 4 * s + g;
+    const int kb = 4 * s + g;
     uint32_t tid; size_t lr; const uint16_t* src; const float* srcf; const uint8_t* src4;
-    if (f.mode == 0) { tid = f.tid_a; lr = (size_t)(n - f.row0); src = f.src_a; srcf = f.srcf_a; src4 = f.src4_a; }
-    else if (c < 8) { tid = f.tid_a; lr = (size_t)nb * 8 + c; src = f.src_a; srcf = f.srcf_a; src4 = f.src4_a; }
-    else { tid = f.tid_b; lr = (size_t)nb * 8 + c - 8; src = f.src_b; srcf = f.srcf_b; src4 = f.src4_b; }
+    mx_fill_src(f, nb, c, tid, lr, src, srcf, src4);
     uint32_t q[4] = {0u, 0u, 0u, 0u}, e;
     if (src4) {  // a block_mxfp4 as stored: e, then qs[j] = element j | element j + 16 << 4
         const uint8_t* blk = src4 + (lr * kblocks + kb) * 17;
@@ -253,4 +278,140 @@ __global__ __launch_bounds__(64) void k_mx_rows(const uint16_t* a, int K, uint8_
 }
 void q3_launch_mx_rows(const uint16_t* a, int rows, int K, uint8_t* q8, uint8_t* e8, hipStream_t s) {
     hipLaunchKernelGGL(k_mx_rows, dim3(K >> 7, (rows + 15) / 16), dim3(64), 0, s, a, K, q8, e8);
+}
+
+// =====================================================================================================================
+// MXFP8 weights: FP8 x FP8 on the same instruction.
+// The FP8 operand of lane (g, c) is 32 bytes = two 16-byte halves, half h = k 64 h + 16 g .. + 15 of the step, and the lane's scale byte
+// is block g's (k = 32 g .. 32 g + 31): the weight side mirrors the row side with columns for rows (pinned by the exact-grid test). The
+// tiled MX8 layout (q3_kernels.h) stores exactly that: per (column tile, step) two wave-loads of one contiguous KiB, then 64 scale bytes.
+// BgMx8: the ring holds D steps of 8 + 1 registers per column tile; everything on the row side is BgMxRows, as in BgMx.
+// =====================================================================================================================
+template <int RT, int NT, int D, bool NTW>
+struct BgMx8 : BgMxRows<RT> {
+    u32x4 mw[D][NT][2]; uint32_t ms[D][NT];
+    const u32x4* mwp[NT]; const uint8_t* msp[NT];
+    int n4;  // the wave's steps
+    __device__ __forceinline__ void load_w(int d, int s) {  // step s of the slice into ring slot d
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            mw[d][j][0] = bg_ldw(mwp[j] + (size_t)s * 128, NTW); mw[d][j][1] = bg_ldw(mwp[j] + (size_t)s * 128 + 64, NTW);
+            ms[d][j] = msp[j][(size_t)s * 64];
+        }
+    }
+    __device__ __forceinline__ void open(const Q3BGemm& g, int nb0, int row0, int wave, int lane) {
+        const int S4 = g.K >> 7, per4 = (S4 + 7) >> 3, s40 = wave * per4, kblocks = g.K >> 5, kq = lane >> 4, r = lane & 15;
+        n4 = max(0, min(per4, S4 - s40));
+        const uint8_t* splane = (const uint8_t*)g.w + (size_t)g.N * g.K;
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            mwp[j] = (const u32x4*)g.w + ((size_t)(nb0 + j) * S4 + s40) * 128 + lane;
+            msp[j] = splane + ((size_t)(nb0 + j) * S4 + s40) * 64 + lane;
+        }
+        this->rows_open(g, row0, s40, kblocks, kq, r);
+        if (n4 > 0) {  // (as BgMx: waves past the last step load nothing and add zeros; a short slice re-reads its last step)
+#pragma unroll
+            for (int d = 0; d < D; ++d) load_w(d, min(d, n4 - 1));
+            this->rows_load(0);
+        }
+    }
+    // xw: the wave's exchange area, RT x 2 KiB
+    __device__ __forceinline__ void run(f32x4 (&acc)[RT][NT], u32x4* xw, int lane) {
+        for (int s0 = 0; s0 < n4; s0 += D) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                const int s = s0 + d;
+                if (s < n4) {
+                    i32x8 a8[RT]; uint32_t e8[RT];
+                    this->rows_convert(xw, lane, a8, e8);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (s + 1 < n4) this->rows_load(s + 1);  // the next step's rows travel while this step's MFMAs run
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) {
+                        const u32x4 w0 = mw[d][j][0], w1 = mw[d][j][1];
+                        const i32x8 b8 = (i32x8){(int)w0.x, (int)w0.y, (int)w0.z, (int)w0.w, (int)w1.x, (int)w1.y, (int)w1.z, (int)w1.w};
+#pragma unroll
+                        for (int i = 0; i < RT; ++i)  // cbsz = blgp = 0: E4M3 on both sides
+                            acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8[i], b8, acc[i][j], 0, 0, 0, (int)e8[i], 0, (int)ms[d][j]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (s + D < n4) load_w(d, s + D);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    }
+};
+
+template <int RT, int NT, int D, bool NTW>
+__global__ __launch_bounds__(512) void k_bgemm_mx8(Q3BGemm g) { bg_body<RT, NT, D, NTW, false, BG_EK_ANY, false, 2>(g); }
+
+template <int RT, int NT>
+struct BgInstMx8 {
+    static constexpr int D = NT == 1 ? 4 : (NT == 2 ? 3 : (RT == 4 ? 1 : 2));  // steps of weights in flight, 9 NT registers each
+    static constexpr size_t lds = BgInst4<RT, NT>::lds;  // the slice partials, then the FP8 exchange of the rows
+    static void prepare() {
+        if (lds > 65536) {
+            hipFuncSetAttribute((const void*)k_bgemm_mx8<RT, NT, D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipFuncSetAttribute((const void*)k_bgemm_mx8<RT, NT, D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        }
+    }
+    static void launch(const Q3BGemm& g, dim3 grid, bool nt, hipStream_t s) {
+        if (nt) hipLaunchKernelGGL((k_bgemm_mx8<RT, NT, D, true>), grid, dim3(512), lds, s, g);
+        else hipLaunchKernelGGL((k_bgemm_mx8<RT, NT, D, false>), grid, dim3(512), lds, s, g);
+    }
+};
+void q3_bgemm_mx8_prepare() {
+#define P(RT_, NT_) BgInstMx8<RT_, NT_>::prepare();
+    BG4_EACH(P)
+#undef P
+}
+int q3_bgemm_mx8_depth(int rt, int nt) {
+#define X(RT_, NT_) if (rt == RT_ && nt == NT_) return BgInstMx8<RT_, NT_>::D;
+    BG4_EACH(X)
+#undef X
+    return 0;
+}
+int q3_bgemm_mx8_launch(const Q3BGemm& g, int rt, int nt, hipStream_t s, int* d, int* ntw) {
+    const dim3 grid(g.N / 16 / nt, (g.B + 16 * rt - 1) / (16 * rt));
+    const bool once = g.w_once && grid.y == 1;
+    *d = q3_bgemm_mx8_depth(rt, nt); *ntw = once ? 1 : 0;
+#define L(RT_, NT_) if (rt == RT_ && nt == NT_) { BgInstMx8<RT_, NT_>::launch(g, grid, once, s); return 0; }
+    BG4_EACH(L)
+#undef L
+    return -1;
+}
+
+// Quantiser + relayout: one thread per (column tile, step, lane (g, c)) = 32-block 4 s + g of one matrix row -> its 32 E4M3 bytes, which
+// go to halves of lanes (2 (g & 1), c) and (2 (g & 1) + 1, c) of half-plane g >> 1, and its scale byte, which stays with lane (g, c).
+// The values are the bf16 weights the default loader uploads (f32 sources rounded to nearest even first); the rule is bg_mx_block's.
+__global__ __launch_bounds__(256) void k_fill_tiled_mx8(Q3FillMx f, int nb0, int nb_count) {
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int S = f.K >> 7;
+    if (gid >= (size_t)nb_count * S * 64) return;
+    const int lane = (int)(gid & 63), g = lane >> 4, c = lane & 15;
+    const int s = (int)((gid >> 6) % S), nb = nb0 + (int)((gid >> 6) / S);
+    uint32_t tid; size_t lr; const uint16_t* src; const float* srcf; const uint8_t* src4;
+    mx_fill_src(f, nb, c, tid, lr, src, srcf, src4);
+    const size_t idx0 = lr * f.K + (size_t)(4 * s + g) * 32;
+    auto two = [&](int p) {  // k = p, p + 1 of the block as one word of bf16 bits
+        uint32_t b[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) b[t] = srcf ? q3_bf16(srcf[idx0 + p + t]) : (src ? src[idx0 + p + t] : q3_bf16(q3_synth(f.seed, tid, idx0 + p + t, f.scale)));
+        return b[0] | (b[1] << 16);
+    };
+    u32x4 raw[4], lo, hi;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) raw[j] = (u32x4){two(4 * j), two(4 * j + 2), two(16 + 4 * j), two(18 + 4 * j)};
+    const uint32_t E = bg_mx_block(raw, lo, hi);
+    u32x4* el = (u32x4*)f.dst + (((size_t)nb * S + s) * 2 + (g >> 1)) * 64 + 2 * (g & 1) * 16 + c;
+    el[0] = lo; el[16] = hi;
+    f.dst[(size_t)f.N * f.K + ((size_t)nb * S + s) * 64 + lane] = (uint8_t)E;
+}
+void q3_launch_fill_tiled_mx8(const Q3FillMx& f, hipStream_t s) {
+    int nb0, nbc;
+    if (f.mode == 0) { nb0 = f.row0 / 16; nbc = f.rows / 16; } else { nb0 = 0; nbc = f.N / 16; }
+    const size_t total = (size_t)nbc * (f.K >> 7) * 64;
+    if (!total) return;
+    hipLaunchKernelGGL(k_fill_tiled_mx8, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, f, nb0, nbc);
 }

@@ -93,14 +93,15 @@ struct BgKqRow {
         s_ = sc[(size_t)p * 16];
     }
 };
-// MX: the weights are ggml MXFP4 blocks and the K loop runs on the block-scaled MFMA: BgMx (q3_bgemm4.hip, the only file that instantiates
-// MX = true, defines it before it does) owns the loop's operands; open() issues its first loads, run() is the loop. Every other
-// instantiation holds the empty BgNoMx.
+// MX: the weights are MX blocks and the K loop runs on the block-scaled MFMA — 1: ggml MXFP4 blocks, BgMx; 2: MXFP8 (E4M3) blocks, BgMx8
+// (both in q3_bgemm4.hip, the only file that instantiates MX != 0, which defines them before it does). The struct owns the loop's
+// operands; open() issues its first loads, run() is the loop. Every other instantiation holds the empty BgNoMx.
 template <int RT, int NT, int D, bool NTW> struct BgMx;
+template <int RT, int NT, int D, bool NTW> struct BgMx8;
 struct BgNoMx {};
-template <int RT, int NT, int D, bool NTW, bool Q8, int EK, bool KQ = false, bool MX = false>
+template <int RT, int NT, int D, bool NTW, bool Q8, int EK, bool KQ = false, int MX = 0>
 __device__ __forceinline__ void bg_body(const Q3BGemm& g) {
-    static_assert(!(Q8 && KQ) && !(MX && (Q8 || KQ)), "one weight format");
+    static_assert(!(Q8 && KQ) && !(MX && (Q8 || KQ)) && MX >= 0 && MX <= 2, "one weight format");
     extern __shared__ float part[];  // [8 waves][RT*NT*4 regs][64 lanes]; MX: then [8 waves][RT][128] x 16 bytes of FP8 exchange
     __shared__ float srow[64];
     Q3_STAMP(g, 0);
@@ -161,7 +162,7 @@ __device__ __forceinline__ void bg_body(const Q3BGemm& g) {
     BgKqRow kr[KQ ? NT : 1];                        // KQ: DP pairs in flight, as Q8
     u32x2 kn[KQ ? DP : 1][NT]; uint32_t kh[KQ ? DP : 1][NT], ks[KQ ? DP : 1][NT], kd[KQ ? DP : 1][NT];
     const int kp0 = kb0 >> 1;                       // the slice's first pair in the tile row
-    std::conditional_t<MX, BgMx<RT, NT, D, NTW>, BgNoMx> mx;
+    std::conditional_t<MX == 2, BgMx8<RT, NT, D, NTW>, std::conditional_t<MX == 1, BgMx<RT, NT, D, NTW>, BgNoMx>> mx;
     if constexpr (MX) {
         mx.open(g, nb0, row0, wave, lane);
     } else if constexpr (KQ) {

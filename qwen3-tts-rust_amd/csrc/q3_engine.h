@@ -50,8 +50,9 @@ struct Q3Tfm {
     struct Kq { const uint2* tab = nullptr; int bpp = 0; };
     std::vector<Kq> kqkv, ko, kgu, kdn; Kq khead;
     // q3tts_engine_options.talker_mxfp4 (q3_bgemm4.hip): the block matrices whose K is whole 128-steps hold ggml MXFP4 blocks
-    // in the tiled MX layout (Q3BGemm::mx); per kind (QKV / gate-up: K = d, O: K = nq, down: K = F), the same in every block
-    bool mx_d = false, mx_nq = false, mx_F = false; size_t mx_bytes = 0;
+    // in the tiled MX layout (Q3BGemm::mx); per kind (QKV / gate-up: K = d, O: K = nq, down: K = F), the same in every block.
+    // talker_mxfp8: the same matrices as MXFP8 blocks. The value is Q3BGemm::mx's: 0 bf16, 1 MXFP4, 2 MXFP8.
+    int mx_d = 0, mx_nq = 0, mx_F = 0; size_t mx_bytes = 0;
     Q3KvCache cache;
     float *cs = nullptr, *sn = nullptr;  // RoPE tables [cache.n_ctx][hd/2]
     size_t weight_bytes = 0;              // matrix bytes of all layers + head in the form they have on the device
@@ -102,6 +103,7 @@ struct q3tts_engine {
     std::vector<void*> allocs;          // every q3_dalloc of this engine, freed by q3tts_engine_destroy
     int kquant_resident = 0;            // q3tts_engine_options.kquant_resident
     int talker_mxfp4 = 0;               // q3tts_engine_options.talker_mxfp4
+    int talker_mxfp8 = 0;               // q3tts_engine_options.talker_mxfp8
     size_t dev_bytes = 0;               // bytes handed out by q3_dev_alloc_zeroed so far (q3tts_k_device_bytes)
     Q3Tfm T, P;
     // assets
@@ -265,10 +267,11 @@ inline Q3KvPrefix q3_kv_prefix_of(const Q3Tfm& t) {
 // the transformer's weights, KV cache and RoPE tables. g: the opened GGUF `file` (null: seeded synthetic weights);
 // q8mode: cfg.talker_q8_0 / cfg.predictor_q8_0
 int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode, int kq = 0, int mx = 0);
-// q3tts_engine_options.talker_mxfp4: whether a block matrix with K input columns is held as MXFP4 (whole 128-steps), and the device bytes
-// the option saves against bf16 on this shape's block matrices (the memory check before allocation)
+// q3tts_engine_options.talker_mxfp4 / talker_mxfp8 (q3_tfm_init's mx = 1 / 2): whether a block matrix with K input columns is held as MX
+// blocks (whole 128-steps), and the device bytes the option saves against bf16 on this shape's block matrices (the memory check before
+// allocation): per matrix 2 N K - N K / 32 * 17 (mx = 1) or 2 N K - N K / 32 * 33 (mx = 2)
 inline bool q3_mx4_ok(int K) { return K >= 128 && K % 128 == 0; }
-size_t q3_tfm_mx4_saving(const Q3TfmShape& sh);
+size_t q3_tfm_mx_saving(const Q3TfmShape& sh, int mx);
 // the bytes a K-quant resident engine saves on this transformer's matrices against bf16: sum of 2 N K - tiled K bytes over the matrices
 // q3_tfm_init (kq = 1) will keep quantised, from the file's tensor headers alone
 size_t q3_tfm_kq_saving(const Q3TfmShape& sh, const Q3Gguf& g);

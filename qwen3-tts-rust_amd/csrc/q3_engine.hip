@@ -249,24 +249,38 @@ extern "C" int q3tts_get_weight_formats(const q3tts_engine* e, int64_t out[4]) {
 }
 extern "C" int q3tts_get_mxfp4_bytes(const q3tts_engine* e, int64_t* bytes) {
     if (!e || !bytes) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
-    *bytes = (int64_t)e->T.mx_bytes;
+    *bytes = e->talker_mxfp4 ? (int64_t)e->T.mx_bytes : 0;
+    return Q3TTS_OK;
+}
+extern "C" int q3tts_get_mxfp8_bytes(const q3tts_engine* e, int64_t* bytes) {
+    if (!e || !bytes) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
+    *bytes = e->talker_mxfp8 ? (int64_t)e->T.mx_bytes : 0;
     return Q3TTS_OK;
 }
 extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3tts_engine_options* opts, q3tts_engine** out) {
     if (!cfg || !out) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "null argument");
     std::string why;
     if (validate(*cfg, why) != Q3TTS_OK) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, why);
-    int kquant = 0, kv_pages = 0, kv4 = 0, mx4 = 0;
+    int kquant = 0, kv_pages = 0, kv4 = 0, mx4 = 0, mx8 = 0;
     if (opts) {
         // (a caller built against the struct without kv_pages passes the shorter size: everything behind it is off)
         const bool has_pages = opts->struct_size >= offsetof(q3tts_engine_options, kv_pages) + sizeof(int32_t);
         // (... and one built against the struct without kv_type_k / kv_type_v the size that ends behind kv_pages)
         const bool has_types = opts->struct_size >= offsetof(q3tts_engine_options, talker_mxfp4);
-        if (opts->struct_size != sizeof(q3tts_engine_options) && opts->struct_size != offsetof(q3tts_engine_options, talker_mxfp4) && opts->struct_size != offsetof(q3tts_engine_options, kv_type_k) && opts->struct_size != offsetof(q3tts_engine_options, kv_pages)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.struct_size = " + std::to_string(opts->struct_size) + ", this library knows " + std::to_string(sizeof(q3tts_engine_options)));
+        if (opts->struct_size != sizeof(q3tts_engine_options) && opts->struct_size != offsetof(q3tts_engine_options, talker_mxfp8) && opts->struct_size != offsetof(q3tts_engine_options, talker_mxfp4) && opts->struct_size != offsetof(q3tts_engine_options, kv_type_k) && opts->struct_size != offsetof(q3tts_engine_options, kv_pages)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.struct_size = " + std::to_string(opts->struct_size) + ", this library knows " + std::to_string(sizeof(q3tts_engine_options)));
         // (... and one built against the struct without talker_mxfp4 the size that ends behind kv_type_v)
-        const bool has_mx = opts->struct_size >= sizeof(q3tts_engine_options);
+        const bool has_mx = opts->struct_size >= offsetof(q3tts_engine_options, talker_mxfp8);
         mx4 = has_mx ? opts->talker_mxfp4 : 0;
         if (mx4 != 0 && mx4 != 1) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.talker_mxfp4 must be 0 or 1");
+        // (... and one built against the struct without talker_mxfp8 the size that ends behind talker_mxfp4)
+        mx8 = opts->struct_size >= sizeof(q3tts_engine_options) ? opts->talker_mxfp8 : 0;
+        if (mx8 != 0 && mx8 != 1) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "q3tts_engine_options.talker_mxfp8 must be 0 or 1");
+        if (mx8 && mx4)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "talker_mxfp8 = 1 holds the Talker's matrices as MXFP8 blocks; it cannot be combined with talker_mxfp4 = " + std::to_string(mx4) + " (MXFP4 blocks): set one or the other");
+        if (mx8 && cfg->talker_q8_0 != 0)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "talker_mxfp8 = 1 holds the Talker's matrices as MXFP8 blocks; it cannot be combined with talker_q8_0 = " + std::to_string(cfg->talker_q8_0) + " (Q8_0 blocks): set one or the other");
+        if (mx8 && opts->kquant_resident)
+            return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "talker_mxfp8 = 1 holds the Talker's matrices as MXFP8 blocks; it cannot be combined with kquant_resident = " + std::to_string(opts->kquant_resident) + " (K-quant tensors as stored): set one or the other");
         if (mx4 && cfg->talker_q8_0 != 0)
             return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "talker_mxfp4 = 1 holds the Talker's matrices as MXFP4 blocks; it cannot be combined with talker_q8_0 = " + std::to_string(cfg->talker_q8_0) + " (Q8_0 blocks): set one or the other");
         if (mx4 && opts->kquant_resident)
@@ -333,7 +347,8 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     auto fail = [&](int rc) { std::string m = e->err; q3tts_engine_destroy(e); g_err = m; return rc; };
 #define TRYC(x) do { int rc__ = (x); if (rc__ != Q3TTS_OK) return fail(rc__); } while (0)
 #define HIPC(call) do { hipError_t er__ = (call); if (er__ != hipSuccess) { q3_set_err(e, Q3TTS_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(er__)); return fail(Q3TTS_ERR_DEVICE); } } while (0)
-    e->kquant_resident = kquant; e->talker_mxfp4 = mx4;
+    e->kquant_resident = kquant; e->talker_mxfp4 = mx4; e->talker_mxfp8 = mx8;
+    const int mx = mx8 ? 2 : mx4;  // Q3BGemm::mx of the Talker's block matrices
     HIPC(hipSetDevice(cfg->device));
     // weights_path: the reference's quant directory (q3_weights.hip); NULL: seeded synthetic weights. The headers are read
     // before the memory check: a K-quant resident engine counts each matrix at the bytes of the form it will take.
@@ -345,7 +360,7 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     {   // before the first allocation: what the config sizes against the device's free memory (not a failure half-way through q3_dalloc)
         size_t free_b = 0, total_b = 0;
         HIPC(hipMemGetInfo(&free_b, &total_b));
-        const unsigned long long need = engine_footprint(*cfg, kv_pages, kv4) - kq_saved - (mx4 ? q3_tfm_mx4_saving(talker_shape(*cfg)) : 0);
+        const unsigned long long need = engine_footprint(*cfg, kv_pages, kv4) - kq_saved - (mx ? q3_tfm_mx_saving(talker_shape(*cfg), mx) : 0);
         if (need > (unsigned long long)free_b) {
             q3_set_err(e, Q3TTS_ERR_OOM, "engine needs at least " + std::to_string(need) + " bytes of device memory for max_batch = " + std::to_string(cfg->max_batch) +
                        ", n_ctx = " + std::to_string(cfg->n_ctx) + (kv4 ? " (Q4_0 cache)" : cfg->kv_q8_0 ? " (Q8_0 cache)" : "") + (kv_pages ? " (kv_pages = " + std::to_string(kv_pages) + ")" : std::string()) + "; the device has " + std::to_string((unsigned long long)free_b) +
@@ -373,7 +388,7 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     const int B = cfg->max_batch;
     e->B = B;
     hipStream_t s = e->stream;
-    TRYC(q3_tfm_init(e, e->T, talker_shape(*cfg, kv_pages, kv4), wdir.empty() ? nullptr : &gt, "qwen3_tts_talker.gguf", cfg->talker_q8_0, kquant, mx4));
+    TRYC(q3_tfm_init(e, e->T, talker_shape(*cfg, kv_pages, kv4), wdir.empty() ? nullptr : &gt, "qwen3_tts_talker.gguf", cfg->talker_q8_0, kquant, mx));
     TRYC(q3_tfm_init(e, e->P, predictor_shape(*cfg), wdir.empty() ? nullptr : &gp, "qwen3_tts_predictor.gguf", cfg->predictor_q8_0, kquant));
     if (kv_pages) {  // the page allocator: LIFO, page 1 on top; the table's pinned image (all zero, like the device's)
         e->kvp_total = kv_pages; e->kvp_slot.assign(B, {});

@@ -943,23 +943,26 @@ extern "C" int q3tts_k_bgemm_kq(int32_t device, const uint16_t* xb, int32_t B, i
 // = ggml block_mxfp4 rows [N][K/32] x 17 bytes kept as stored (exactly one of the two; epilogue 2: the N/2 gate rows, then the N/2 up rows).
 // One launch through q3_launch_bgemm. blocks_out (optional): the device's weights read back into ggml's block order [N][K/32][17];
 // a8_out / ae_out (optional, both): the rows as the kernel converts them, E4M3 bytes [B][K] and E8M0 bytes [B][K/32]. iters > 0: mean_ms as q3tts_k_bgemm.
-extern "C" int q3tts_k_bgemm_mxfp4(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const float* w_f32, const uint8_t* w_blocks, int32_t N,
-                                   const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb,
-                                   float* ssp_out, uint64_t* keys, uint8_t* blocks_out, uint8_t* a8_out, uint8_t* ae_out, int32_t iters,
-                                   float* mean_ms) {
+// form 2 = MXFP8 weights (q3tts_k_bgemm_mxfp8): w_f32 only, quantised by the rows' rule; q_out [N][K] / e_out [N][K/32]
+// (optional, both) = the device's weights in plain row order. Both hooks are this one function.
+static int bgemm_mx_hook(int form, int32_t device, const uint16_t* xb, int32_t B, int32_t K, const float* w_f32, const uint8_t* w_blocks, int32_t N,
+                         const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb,
+                         float* ssp_out, uint64_t* keys, uint8_t* blocks_out, uint8_t* q_out, uint8_t* e_out, uint8_t* a8_out, uint8_t* ae_out,
+                         int32_t iters, float* mean_ms) {
+    if ((!q_out) != (!e_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm MX hook: q_out and e_out go together");
     if (!xb || (!w_f32) == (!w_blocks) || B <= 0 || K % 128 || K < 128 || N % 16 || N < 16 || epi < 0 || epi > 3)
-        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_mxfp4 hook: K % 128 == 0, N % 16 == 0, epilogue 0..3, one of w_f32 / w_blocks");
-    if (epi == Q3_EPI_SWIGLU && (N % 64 || !yb)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_mxfp4 hook: swiglu needs N % 64 == 0 and yb");
-    if (epi == Q3_EPI_RESID && nw_next && (N % 32 || !yb || !ssp_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_mxfp4 hook: norm outputs");
-    if ((epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) && !y) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_mxfp4 hook: y missing");
-    if (epi == Q3_EPI_ARGMAX && !keys) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_mxfp4 hook: keys missing");
-    if ((!a8_out) != (!ae_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_mxfp4 hook: a8_out and ae_out go together");
+        return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm MX hook: K % 128 == 0, N % 16 == 0, epilogue 0..3, one of w_f32 / w_blocks");
+    if (epi == Q3_EPI_SWIGLU && (N % 64 || !yb)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm MX hook: swiglu needs N % 64 == 0 and yb");
+    if (epi == Q3_EPI_RESID && nw_next && (N % 32 || !yb || !ssp_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm MX hook: norm outputs");
+    if ((epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) && !y) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm MX hook: y missing");
+    if (epi == Q3_EPI_ARGMAX && !keys) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm MX hook: keys missing");
+    if ((!a8_out) != (!ae_out)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm MX hook: a8_out and ae_out go together");
     HK(hipSetDevice(device));
     const int nt = N / 16, kb = K / 32, S = K / 128;
     const size_t src_bytes = w_f32 ? (size_t)N * K * 4 : (size_t)N * kb * 17;
     DevBuf dx, dw, dwt, ds, dn, dy, dyb, dso, dk;
     { const std::vector<uint16_t> xt = atile_host(xb, B, K); TRY(dx.put(xt.data(), xt.size() * 2)); }
-    TRY(dw.put(w_f32 ? (const void*)w_f32 : (const void*)w_blocks, src_bytes)); TRY(dwt.alloc(q3_mx4_bytes(N, K)));
+    TRY(dw.put(w_f32 ? (const void*)w_f32 : (const void*)w_blocks, src_bytes)); TRY(dwt.alloc(form == 2 ? q3_mx8_bytes(N, K) : q3_mx4_bytes(N, K)));
     TRY(ds.put(ntiles > 0 ? ssp : nullptr, (size_t)B * std::max(ntiles, 1) * 4)); TRY(dn.put(nw_next, (size_t)N * 4));
     TRY(dy.put(epi == Q3_EPI_RESID ? y : nullptr, (size_t)B * N * 4)); TRY(dyb.alloc(pad16(B) * N * 2)); TRY(dso.alloc((size_t)B * nt * 4)); TRY(dk.alloc((size_t)B * nt * 8));
     const bool swiglu = epi == Q3_EPI_SWIGLU;
@@ -967,16 +970,16 @@ extern "C" int q3tts_k_bgemm_mxfp4(int32_t device, const uint16_t* xb, int32_t B
         Q3FillMx f{}; f.dst = dwt; f.N = N; f.K = K; f.mode = swiglu ? 1 : 0; f.row0 = 0; f.rows = N;
         if (w_f32) { f.srcf_a = dw; if (swiglu) f.srcf_b = f.srcf_a + (size_t)(N / 2) * K; }
         else { f.src4_a = dw; if (swiglu) f.src4_b = f.src4_a + (size_t)(N / 2) * kb * 17; }
-        q3_launch_fill_tiled_mx4(f, nullptr);
+        if (form == 2) q3_launch_fill_tiled_mx8(f, nullptr); else q3_launch_fill_tiled_mx4(f, nullptr);
     }
-    Q3BGemm g{}; g.a = dx; g.B = B; g.w = dwt; g.K = K; g.N = N; g.mx = 1;
+    Q3BGemm g{}; g.a = dx; g.B = B; g.w = dwt; g.K = K; g.N = N; g.mx = form;
     if (ssp) g.ssp = ds;
     g.ld_ssp = ntiles; g.ntiles = ntiles; g.d_norm = d_norm; g.eps = eps; g.epi = epi;
     g.y = dy; g.ldy = N;
     if (swiglu || nw_next) g.yb = dyb;  // (RESID without nw_next and with yb would also ask for yb = bf16(y): N % 32)
     if (nw_next) g.nw_next = dn;
     g.ssp_out = dso; g.ld_ssp_out = nt; g.keys = dk; g.key_stride = nt;
-    if (q3_launch_bgemm(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm_mxfp4 hook: shape");
+    if (q3_launch_bgemm(g, nullptr)) return q3_set_err(nullptr, Q3TTS_ERR_INVALID, "bgemm MX hook: shape");
     HK(hipDeviceSynchronize());
     if (epi == Q3_EPI_STORE || epi == Q3_EPI_RESID) TRY(dy.get(y, (size_t)B * N * 4));
     if (epi == Q3_EPI_SWIGLU) TRY(untile_host(dyb, B, N / 2, yb));
@@ -1002,6 +1005,18 @@ extern "C" int q3tts_k_bgemm_mxfp4(int32_t device, const uint16_t* xb, int32_t B
             }
         }
     }
+    if (q_out) {  // half h of lane (g, c) of tile (nb, s): k = 128 s + 64 h + 16 g .. + 15 of the lane's logical row; scale byte: block 4 s + g
+        std::vector<uint8_t> t(q3_mx8_bytes(N, K));
+        TRY(dwt.get(t.data(), t.size()));
+        const uint8_t* sp = t.data() + (size_t)N * K;
+        for (int nb = 0; nb < nt; ++nb) for (int s = 0; s < S; ++s) for (int l = 0; l < 64; ++l) {
+            const int gq = l >> 4, c = l & 15;
+            const size_t row = swiglu ? (c < 8 ? (size_t)nb * 8 + c : (size_t)N / 2 + nb * 8 + c - 8) : (size_t)nb * 16 + c;
+            const size_t ti = (size_t)nb * S + s;
+            for (int h = 0; h < 2; ++h) memcpy(q_out + row * K + 128 * s + 64 * h + 16 * gq, t.data() + ((ti * 2 + h) * 64 + l) * 16, 16);
+            e_out[row * kb + 4 * s + gq] = sp[ti * 64 + l];
+        }
+    }
     if (a8_out) {
         DevBuf dq, de;
         TRY(dq.alloc(pad16(B) * K)); TRY(de.alloc(pad16(B) * kb));
@@ -1011,6 +1026,20 @@ extern "C" int q3tts_k_bgemm_mxfp4(int32_t device, const uint16_t* xb, int32_t B
     }
     if (epi == Q3_EPI_RESID) { g.epi = Q3_EPI_STORE; g.nw_next = nullptr; }  // (timed launches must not keep adding into y)
     return time_launches(iters, [&] { q3_launch_bgemm(g, nullptr); }, mean_ms);
+}
+extern "C" int q3tts_k_bgemm_mxfp4(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const float* w_f32, const uint8_t* w_blocks, int32_t N,
+                                   const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb,
+                                   float* ssp_out, uint64_t* keys, uint8_t* blocks_out, uint8_t* a8_out, uint8_t* ae_out, int32_t iters,
+                                   float* mean_ms) {
+    return bgemm_mx_hook(1, device, xb, B, K, w_f32, w_blocks, N, ssp, ntiles, d_norm, eps, epi, nw_next, y, yb, ssp_out, keys, blocks_out, nullptr, nullptr,
+                         a8_out, ae_out, iters, mean_ms);
+}
+extern "C" int q3tts_k_bgemm_mxfp8(int32_t device, const uint16_t* xb, int32_t B, int32_t K, const float* w_f32, int32_t N,
+                                   const float* ssp, int32_t ntiles, int32_t d_norm, float eps, int32_t epi, const float* nw_next, float* y, uint16_t* yb,
+                                   float* ssp_out, uint64_t* keys, uint8_t* q_out, uint8_t* e_out, uint8_t* a8_out, uint8_t* ae_out, int32_t iters,
+                                   float* mean_ms) {
+    return bgemm_mx_hook(2, device, xb, B, K, w_f32, nullptr, N, ssp, ntiles, d_norm, eps, epi, nw_next, y, yb, ssp_out, keys, nullptr, q_out, e_out,
+                         a8_out, ae_out, iters, mean_ms);
 }
 
 // W8A8 (q3_bgemm8.hip): activations and weights as ggml Q8_0 blocks in natural order in / out; the hook tiles them for the device

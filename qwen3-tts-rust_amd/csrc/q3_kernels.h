@@ -91,7 +91,7 @@ struct Q3BGemm {
     const uint16_t* a; int a_row0; int B;       // A-tiled bf16 rows [a_row0, a_row0 + B) of a buffer with K columns
     const uint4* w; int K, N;                   // tiled bf16
     int w_once;                                 // 1: the weights are read once per long interval (Talker decode): non-temporal loads when one workgroup owns a tile
-    int mx;                                     // 1: w holds ggml MXFP4 blocks in the tiled MX layout below (q3_bgemm4.hip); K % 128 == 0. (In the struct's padding: no other field moves.)
+    int mx;                                     // 1: w holds ggml MXFP4 blocks in the tiled MX layout below (q3_bgemm4.hip); 2: MXFP8 blocks in the tiled MX8 layout (§34); K % 128 == 0. (In the struct's padding: no other field moves.)
     const float* ssp; int ld_ssp; int ntiles; int d_norm; float eps;  // row scale: s_r = 1 / sqrtf(SS(ssp[row][0..ntiles)) / d_norm + eps)
     int epi;
     float* y; int ldy;
@@ -140,6 +140,18 @@ int q3_bgemm4_launch(const struct Q3BGemm& g, int rt, int nt, hipStream_t s, int
 int q3_bgemm4_depth(int rt, int nt);
 void q3_bgemm4_prepare();
 void q3_launch_mx_rows(const uint16_t* a, int rows, int K, uint8_t* q8, uint8_t* e8, hipStream_t s);  // test hook: the rows' MXFP8 form, natural order, whole 16-row tiles
+// The tiled MX8 layout of an [N][K] matrix of MXFP8 blocks (32 x E4M3 + one E8M0 byte; Q3BGemm::mx = 2), S = K / 128 — the FP8
+// operand of the same instruction: lane (g, c) of (column tile nb, step s) holds row 16 nb + c, k = 128 s + 64 h + 16 g .. + 15 in half
+// h = 0, 1 of its 32 bytes, and the scale of block 4 s + g of that row (k = 128 s + 32 g .. + 31: not the lane's own data).
+//   [0, N K)              elements  [N/16][S][2 halves][64 lanes] x 16 bytes, byte p of half h = k 128 s + 64 h + 16 g + p
+//   [N K, + N K / 32)     scales    [N/16][S][64 lanes] x 1 byte: E of block 4 s + g; value = 2^(E - 127) * E4M3(q)
+// = 33 bytes per 32 weights, no padding: q3_mx8_bytes. A step of a column tile is two contiguous, naturally aligned KiB + 64 bytes.
+// q3_launch_fill_tiled_mx8 fills it from a Q3FillMx's f32 / bf16 / synthetic source (src4 is not read) by the rows' own conversion.
+Q3_HD size_t q3_mx8_bytes(size_t N, size_t K) { return N * K / 32 * 33; }
+void q3_launch_fill_tiled_mx8(const Q3FillMx& f, hipStream_t s);
+int q3_bgemm_mx8_launch(const struct Q3BGemm& g, int rt, int nt, hipStream_t s, int* d, int* ntw);
+int q3_bgemm_mx8_depth(int rt, int nt);
+void q3_bgemm_mx8_prepare();
 // The tiled K layout of one 16-column tile row over K columns (P = K/64 tile pairs, S = K/256 super-blocks); lane l = (kq, n) of a pair owns
 // the 16 weights its two bf16 fragments would hold: k = 4kq..4kq+3, 16+4kq..16+4kq+3 of 32-block 2p, then of 2p+1 (element e = 0..7 each).
 //   [0, 512 P)            nibbles  uint2 [P][64 lanes]: x = block 2p, y = block 2p+1, element e in bits 4e..4e+3 (the quant's low 4 bits)

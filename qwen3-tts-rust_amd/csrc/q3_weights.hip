@@ -155,13 +155,13 @@ size_t q3_tfm_kq_saving(const Q3TfmShape& sh, const Q3Gguf& g) {
     return saved;
 }
 
-size_t q3_tfm_mx4_saving(const Q3TfmShape& sh) {
+size_t q3_tfm_mx_saving(const Q3TfmShape& sh, int mx) {
     const size_t nq = (size_t)sh.Hq * sh.hd, nqkv = nq + 2 * (size_t)sh.Hkv * sh.hd;
     size_t n = 0;  // weights that leave bf16
     if (q3_mx4_ok(sh.d)) n += (nqkv + 2 * (size_t)sh.F) * sh.d;
     if (q3_mx4_ok((int)nq)) n += (size_t)sh.d * nq;
     if (q3_mx4_ok(sh.F)) n += (size_t)sh.d * sh.F;
-    return (size_t)sh.L * (2 * n - q3_mx4_bytes(n, 1));
+    return (size_t)sh.L * (2 * n - (mx == 2 ? q3_mx8_bytes(n, 1) : q3_mx4_bytes(n, 1)));
 }
 
 int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g, const char* file, int q8mode, int kq, int mx) {
@@ -179,11 +179,13 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
     if (q8) { t.sqkv.assign(L, nullptr); t.so.assign(L, nullptr); t.sgu.assign(L, nullptr); t.sd.assign(L, nullptr); }
     // a matrix [N][K]: bf16 tiles (2 bytes per weight), or in Q8_0 mode block quants (1 byte) + f16 block scales [N][K/32]
     const size_t wdiv = q8 ? 16 : 8;  // weights per uint4
-    // talker_mxfp4: a block matrix with whole 128-steps is 17 bytes per 32 weights in the tiled MX layout; the others stay bf16
-    if (mx) { t.mx_d = q3_mx4_ok(d); t.mx_nq = q3_mx4_ok(sh.Hq * hd); t.mx_F = q3_mx4_ok(F); }
+    // talker_mxfp4 (mx = 1) / talker_mxfp8 (mx = 2): a block matrix with whole 128-steps is 17 / 33 bytes per 32 weights in the tiled MX /
+    // MX8 layout; the others stay bf16
+    if (mx) { t.mx_d = q3_mx4_ok(d) ? mx : 0; t.mx_nq = q3_mx4_ok(sh.Hq * hd) ? mx : 0; t.mx_F = q3_mx4_ok(F) ? mx : 0; }
     auto is_mx = [&](size_t K) { return mx && q3_mx4_ok((int)K); };
+    auto mx_bytes = [&](size_t N, size_t K) { return mx == 2 ? q3_mx8_bytes(N, K) : q3_mx4_bytes(N, K); };
     auto alloc_mat = [&](uint4** w, uint16_t** sc, size_t N, size_t K) -> int {
-        if (is_mx(K) && w != &t.head) { uint8_t* p = nullptr; TRY(q3_dalloc(e, &p, q3_mx4_bytes(N, K))); *w = (uint4*)p; return Q3TTS_OK; }
+        if (is_mx(K) && w != &t.head) { uint8_t* p = nullptr; TRY(q3_dalloc(e, &p, mx_bytes(N, K))); *w = (uint4*)p; return Q3TTS_OK; }
         TRY(q3_dalloc(e, w, N * K / wdiv));
         if (q8) TRY(q3_dalloc(e, sc, N * K / 32));
         return Q3TTS_OK;
@@ -192,11 +194,12 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
         if (is_mx(f.K) && f.dst != t.head) {  // quantised on the device from the bf16 rows / the synthetic tensor (ggml's quantize_row_mxfp4)
             Q3FillMx m{}; m.dst = (uint8_t*)f.dst; m.N = f.N; m.K = f.K; m.mode = f.mode; m.row0 = f.row0; m.rows = f.rows; m.tid_a = f.tid_a; m.tid_b = f.tid_b;
             m.seed = f.seed; m.scale = f.scale; m.src_a = f.src_a; m.src_b = f.src_b; m.src4_a = f.src8_a; m.src4_b = f.src8_b;  // (a type-39 tensor: its blocks as stored)
-            q3_launch_fill_tiled_mx4(m, s);
+            if (mx == 2) q3_launch_fill_tiled_mx8(m, s);  // (MXFP8: always from the bf16 staging rows; no tensor type is taken as stored)
+            else q3_launch_fill_tiled_mx4(m, s);
         } else if (q8) { f.dst_scale = sc; q3_launch_fill_tiled_q8(f, s); } else q3_launch_fill_tiled(f, s);
     };
     auto stage = [&](const std::string& name, size_t N, size_t K, int which, bool mxdst) -> int {
-        return mxdst ? gg->mat_mx4(name, N, K, which) : (q8 ? gg->mat_q8(name, N, K, which) : gg->mat(name, N, K, which));
+        return mxdst && mx == 1 ? gg->mat_mx4(name, N, K, which) : (q8 ? gg->mat_q8(name, N, K, which) : gg->mat(name, N, K, which));
     };
     // rows [row0, row0 + rows) of dst [Ntot][K] <- the file's tensor `name` (through staging slot 0, which the next tensor reuses)
     auto put = [&](const std::string& name, uint4* dst, uint16_t* sc, int Ntot, int K, int row0, int rows) -> int {
@@ -261,10 +264,10 @@ int q3_tfm_init(q3tts_engine* e, Q3Tfm& t, const Q3TfmShape& sh, const Q3Gguf* g
         if (!r_d) TRY(alloc_mat(&t.wd[l], &sc_d, d, F));
         if (q8) { t.sqkv[l] = sc_qkv; t.so[l] = sc_o; t.sgu[l] = sc_gu; t.sd[l] = sc_d; }
         {
-            auto mb = [&](size_t N, size_t K) { return is_mx(K) ? q3_mx4_bytes(N, K) : (size_t)(bpw * (double)(N * K)); };
+            auto mb = [&](size_t N, size_t K) { return is_mx(K) ? mx_bytes(N, K) : (size_t)(bpw * (double)(N * K)); };
             const size_t b_qkv = r_qkv ? r_qkv : mb(t.nqkv, d), b_o = r_o ? r_o : mb(d, t.nq);
             const size_t b_gu = r_gu ? r_gu : mb(2ull * F, d), b_d = r_d ? r_d : mb(d, F);
-            if (mx) {  // (never together with Q8_0 or K-quants) the MXFP4 matrices are counted apart from the bf16 ones
+            if (mx) {  // (never together with Q8_0 or K-quants) the MXFP4 / MXFP8 matrices are counted apart from the bf16 ones
                 const size_t m4 = (t.mx_d ? b_qkv + b_gu : 0) + (t.mx_nq ? b_o : 0) + (t.mx_F ? b_d : 0);
                 t.mx_bytes += m4; t.fmt_bytes[0] -= m4;
             }

@@ -170,7 +170,7 @@ KV_Q4_0, KV_Q8_0 = 2, 8   # Q3TTS_KV_Q4_0 / Q3TTS_KV_Q8_0: q3tts_engine_options.
 # every symbol include/q3tts.h declares (tests check the export list against the header text)
 class EngineOptions(C.Structure):
     """q3tts_engine_options: what q3tts_engine_create_opts takes beyond the config (zero = q3tts_engine_create)."""
-    _fields_ = [("struct_size", C.c_uint32), ("kquant_resident", C.c_int32), ("kv_pages", C.c_int32), ("kv_type_k", C.c_int32), ("kv_type_v", C.c_int32), ("talker_mxfp4", C.c_int32)]
+    _fields_ = [("struct_size", C.c_uint32), ("kquant_resident", C.c_int32), ("kv_pages", C.c_int32), ("kv_type_k", C.c_int32), ("kv_type_v", C.c_int32), ("talker_mxfp4", C.c_int32), ("talker_mxfp8", C.c_int32)]
 
 
 SYMBOLS = [
@@ -210,7 +210,7 @@ SYMBOLS = [
     "q3tts_k_doc_stream_rate", "q3tts_k_doc_ring_plan", "q3tts_k_doc_out_pos",
     "q3tts_vocoder_config_from_file", "q3tts_get_vocoder_source", "q3tts_k_voc_file_tensor",
     "q3tts_clone_config_from_dir", "q3tts_clone_load", "q3tts_get_clone_source", "q3tts_k_clone_file_tensor", "q3tts_k_clone_load_check", "q3tts_clone_files_find",
-    "q3tts_k_bgemm_kq", "q3tts_k_bgemm_mxfp4", "q3tts_get_mxfp4_bytes", "q3tts_k_kq_bytes", "q3tts_engine_create_opts", "q3tts_get_weight_formats",
+    "q3tts_k_bgemm_kq", "q3tts_k_bgemm_mxfp4", "q3tts_get_mxfp4_bytes", "q3tts_k_bgemm_mxfp8", "q3tts_get_mxfp8_bytes", "q3tts_k_kq_bytes", "q3tts_engine_create_opts", "q3tts_get_weight_formats",
 ]
 
 # long documents (include/q3tts.h, "long documents"): break kinds, the join's block length, and the structs field for field
@@ -491,6 +491,12 @@ def load_library(path=None):
     lib.q3tts_k_bgemm_mxfp4.restype = C.c_int
     lib.q3tts_get_mxfp4_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
     lib.q3tts_get_mxfp4_bytes.restype = C.c_int
+    lib.q3tts_k_bgemm_mxfp8.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                        C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.POINTER(C.c_float)]
+    lib.q3tts_k_bgemm_mxfp8.restype = C.c_int
+    lib.q3tts_get_mxfp8_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.q3tts_get_mxfp8_bytes.restype = C.c_int
     lib.q3tts_k_kq_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]
     lib.q3tts_k_kq_bytes.restype = C.c_int
     lib.q3tts_k_bgemm_q8a8_argmax.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]

@@ -124,9 +124,10 @@ class TtsEngine:
     """src/tts/engine.rs:53-72 — the engine owns weights, contexts and speakers; one utterance at a time per call
     (`&mut self`), or a list through `generate_batch_with_voice` (continuous batching, an extension)."""
 
-    def __init__(self, cfg, tokenizer=None, kquant_resident=False, kv_pages=0, kv_types=None, talker_mxfp4=False):
-        if kv_pages or kv_types or talker_mxfp4:
-            self._native = native.NativeEngine(cfg, kquant_resident=bool(kquant_resident), kv_pages=kv_pages, kv_types=kv_types, talker_mxfp4=bool(talker_mxfp4))
+    def __init__(self, cfg, tokenizer=None, kquant_resident=False, kv_pages=0, kv_types=None, talker_mxfp4=False, talker_mxfp8=False):
+        if kv_pages or kv_types or talker_mxfp4 or talker_mxfp8:
+            self._native = native.NativeEngine(cfg, kquant_resident=bool(kquant_resident), kv_pages=kv_pages, kv_types=kv_types, talker_mxfp4=bool(talker_mxfp4),
+                                               talker_mxfp8=bool(talker_mxfp8))
         else:
             self._native = native.NativeEngine(cfg, kquant_resident=True) if kquant_resident else native.NativeEngine(cfg)
         self.cfg = cfg
@@ -137,7 +138,7 @@ class TtsEngine:
 
     @classmethod
     def new(cls, model_dir: Optional[str] = None, quant: str = "none", config=None, max_batch: Optional[int] = None,
-            kv_cache: Optional[str] = None, kquant_resident: bool = False, kv_pages: int = 0, talker_mxfp4: bool = False):
+            kv_cache: Optional[str] = None, kquant_resident: bool = False, kv_pages: int = 0, talker_mxfp4: bool = False, talker_mxfp8: bool = False):
         """TtsEngine::new(model_dir, quant) (src/tts/engine.rs:84-169). With no config the model's shape comes from the GGUF files of the
         quant directory (q3tts_config_from_model_dir), whatever member of the family it holds; a config given by the caller is used as it
         is (its shapes must match the files) and is not modified. The vocoder's trained weights and shape come the same way from
@@ -155,6 +156,9 @@ class TtsEngine:
         kv_q8_0 must be 0). Anything else: ValueError.
         talker_mxfp4: the Talker's block matrices are quantised on the device to ggml MXFP4 blocks and multiplied on the block-scaled
         MFMA (q3tts_engine_options.talker_mxfp4): 4.25 bits per weight, other results than bf16 and Q8_0; not with quant = "q8_0" or kquant_resident.
+        talker_mxfp8: the same matrices as MXFP8 blocks, quantised on the device from the bf16 values of whatever the files hold, FP8 x FP8 on
+        that instruction (q3tts_engine_options.talker_mxfp8): 8.25 bits per weight, results of its own; not with talker_mxfp4, quant = "q8_0"
+        or kquant_resident.
         kquant_resident: Q4_K / Q5_K / Q6_K tensors of the quant directory (quant = "q5_k_m") stay quantised on the device and are decoded
         inside the GEMM (q3tts_engine_options.kquant_resident): the same results bit for bit in about a third of the weight bytes;
         weight_formats says what each form holds. Opt-in: the default converts them to bf16 at load.
@@ -190,7 +194,7 @@ class TtsEngine:
             missing = native.CLONE_FILES[0 if clone_files[0] is None else 1]
             raise _abi.Q3Error(f"{missing} not found in {wdir} or in {model_dir}: the clone encoders need both files "
                                f"(found {clone_files[0] or clone_files[1]})")
-        eng = cls(cfg, tok, kquant_resident=kquant_resident, kv_pages=kv_pages, kv_types=kv_types, talker_mxfp4=talker_mxfp4)
+        eng = cls(cfg, tok, kquant_resident=kquant_resident, kv_pages=kv_pages, kv_types=kv_types, talker_mxfp4=talker_mxfp4, talker_mxfp8=talker_mxfp8)
         if clone_files[0] is not None:
             try:
                 eng._native.clone_load(wdir)

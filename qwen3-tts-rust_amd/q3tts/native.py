@@ -80,7 +80,7 @@ class GenResult:
 class NativeEngine:
     """q3tts_engine handle. One engine per GPU; not re-entrant (same contract as `&mut self`)."""
 
-    def __init__(self, cfg, kquant_resident=False, kv_pages=0, kv_types=None, talker_mxfp4=False):
+    def __init__(self, cfg, kquant_resident=False, kv_pages=0, kv_types=None, talker_mxfp4=False, talker_mxfp8=False):
         """kquant_resident: q3tts_engine_options.kquant_resident — Q4_K / Q5_K / Q6_K tensors of cfg.weights_path stay quantised on the
         device and are decoded inside the GEMM (same bits as the default; fewer bytes).
         kv_pages: q3tts_engine_options.kv_pages — N >= 1 pages the Talker's K/V cache: a pool of N pages of 64 positions shared by all
@@ -88,14 +88,16 @@ class NativeEngine:
         kv_types: q3tts_engine_options.kv_type_k / kv_type_v — (_abi.KV_Q8_0, _abi.KV_Q4_0) or (_abi.KV_Q4_0, _abi.KV_Q4_0): the Talker's
         K/V cache with ggml Q4_0 blocks (0.41 / 0.28 of the bf16 cache's bytes; other results than the bf16 and the Q8_0 cache).
         talker_mxfp4: q3tts_engine_options.talker_mxfp4 — the Talker's block matrices as ggml MXFP4 blocks on the block-scaled MFMA (4.25
-        bits per weight; other results than bf16 and Q8_0)."""
+        bits per weight; other results than bf16 and Q8_0).
+        talker_mxfp8: q3tts_engine_options.talker_mxfp8 — the same matrices as MXFP8 blocks (E4M3 elements, E8M0 block scales), FP8 x FP8 on
+        the same instruction (8.25 bits per weight; results of its own again; not together with talker_mxfp4)."""
         self.lib = _abi.load_library()
         self.cfg = cfg
         self.h = C.c_void_p()
         self._prefixes = weakref.WeakSet()  # destroyed before the engine
-        if kquant_resident or kv_pages or kv_types or talker_mxfp4:
+        if kquant_resident or kv_pages or kv_types or talker_mxfp4 or talker_mxfp8:
             tk, tv = kv_types or (0, 0)
-            opts = _abi.EngineOptions(C.sizeof(_abi.EngineOptions), 1 if kquant_resident else 0, int(kv_pages), int(tk), int(tv), 1 if talker_mxfp4 else 0)
+            opts = _abi.EngineOptions(C.sizeof(_abi.EngineOptions), 1 if kquant_resident else 0, int(kv_pages), int(tk), int(tv), 1 if talker_mxfp4 else 0, 1 if talker_mxfp8 else 0)
             rc = self.lib.q3tts_engine_create_opts(C.byref(cfg), C.byref(opts), C.byref(self.h))
         else:
             rc = self.lib.q3tts_engine_create(C.byref(cfg), C.byref(self.h))
@@ -127,6 +129,9 @@ class NativeEngine:
         fm = dict(zip(("bf16", "q4_k", "q5_k", "q6_k"), (int(v) for v in out)))
         if mx.value:
             fm["mxfp4"] = int(mx.value)  # (only engines with talker_mxfp4 carry the key)
+        self._check(self.lib.q3tts_get_mxfp8_bytes(self.h, C.byref(mx)), "q3tts_get_mxfp8_bytes")
+        if mx.value:
+            fm["mxfp8"] = int(mx.value)  # (... and only engines with talker_mxfp8 this one)
         return fm
 
     def close(self):
@@ -1051,6 +1056,33 @@ def k_bgemm_mxfp4(xb, w, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=0,
     if rc != 0:
         raise _abi.Q3Error(f"q3tts_k_bgemm_mxfp4 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
     return dict(y=y, yb=yb, ssp_out=sso, keys=keys, blocks=blocks, a8=a8, ae=ae, ms=ms.value)
+
+
+def k_bgemm_mxfp8(xb, w, ssp, d_norm, eps, epi, nw_next=None, y0=None, device=0, rows_out=False, iters=0):
+    """The same launch with MXFP8 weights, FP8 x FP8 on the block-scaled MFMA (q3tts_k_bgemm_mxfp8): w = f32 [N][K], rounded to bf16 and
+    quantised on the device. Also returns q / e = the device's weights in plain row order (E4M3 bytes [N][K], E8M0 bytes [N][K/32]) and, with
+    rows_out, a8 / ae as k_bgemm_mxfp4."""
+    lib = _abi.load_library()
+    xb = np.ascontiguousarray(xb, dtype=np.uint16)
+    B, K = xb.shape
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    N = w.shape[0]
+    y = np.zeros((B, N), dtype=np.float32) if y0 is None else np.ascontiguousarray(y0, dtype=np.float32).copy()
+    yb = np.zeros((B, N // 2 if epi == 2 else N), dtype=np.uint16)
+    sso = np.zeros((B, N // 16), dtype=np.float32)
+    keys = np.zeros(B, dtype=np.uint64)
+    q = np.zeros((N, K), dtype=np.uint8); e = np.zeros((N, K // 32), dtype=np.uint8)
+    a8 = np.zeros((B, K), dtype=np.uint8); ae = np.zeros((B, K // 32), dtype=np.uint8)
+    ms = C.c_float(0)
+    sp = None if ssp is None else np.ascontiguousarray(ssp, dtype=np.float32)
+    nw = None if nw_next is None else np.ascontiguousarray(nw_next, dtype=np.float32)
+    rc = lib.q3tts_k_bgemm_mxfp8(device, xb.ctypes.data, B, K, w.ctypes.data, N, None if sp is None else sp.ctypes.data,
+                                 0 if sp is None else sp.shape[1], d_norm, eps, epi, None if nw is None else nw.ctypes.data, y.ctypes.data,
+                                 yb.ctypes.data, sso.ctypes.data, keys.ctypes.data, q.ctypes.data, e.ctypes.data,
+                                 a8.ctypes.data if rows_out else None, ae.ctypes.data if rows_out else None, iters, C.byref(ms))
+    if rc != 0:
+        raise _abi.Q3Error(f"q3tts_k_bgemm_mxfp8 failed ({rc}): {lib.q3tts_last_error(None).decode()}")
+    return dict(y=y, yb=yb, ssp_out=sso, keys=keys, q=q, e=e, a8=a8, ae=ae, ms=ms.value)
 
 
 def k_kq_bytes(ggml_type, N, K):
