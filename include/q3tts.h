@@ -250,7 +250,7 @@ int q3tts_engine_create(const q3tts_engine_config* cfg, q3tts_engine** out);
  * Q3TTS_ERR_INVALID (the message names both settings): kv_pages with kv_q8_0 = 1; kv_pages < n_ctx / 64 (every request the engine
  * accepts fits the pool: what would need more pages exceeds n_ctx and is refused as such). q3tts_session_set_swap on a paged engine:
  * Q3TTS_ERR_UNSUPPORTED. The Predictor's per-frame cache is never paged. struct_size may be that of the struct without kv_pages.
- * kv_type_k / kv_type_v (0, 0: what q3tts_engine_config.kv_q8_0 says): the Talker's K/V cache with ggml Q4_0 blocks (csrc/q3_attend_kv4.hip,
+ * kv_type_k / kv_type_v (0, 0: what q3tts_engine_config.kv_q8_0 says): the Talker's K/V cache with ggml Q4_0 blocks (csrc/q3_attend_kvq.hip,
  * DESIGN.md section 32). Accepted pairs: (Q3TTS_KV_Q8_0, Q3TTS_KV_Q4_0) — llama.cpp's --cache-type-k q8_0 --cache-type-v q4_0, values
  * tolerate four bits better than keys — and (Q3TTS_KV_Q4_0, Q3TTS_KV_Q4_0). Per-slot memory becomes
  *   t_n_layer * t_n_kv_head * n_ctx * (bytes(kv_type_k) + bytes(kv_type_v)), bytes(Q8_0) = t_head_dim + 2 * t_head_dim / 32,
@@ -898,7 +898,7 @@ int q3tts_k_attention_pair(int32_t device, const float* qkv, int32_t n_slots, in
  * k_attend<2 / 4, true>; 5: k_attend_gqa2; 6: k_attend_small<2>; 7: k_attend_pair; 8: k_attend_prefill; -1: the launcher refuses. */
 int q3tts_k_attend_pick(int32_t fused, int32_t gqa_ratio, int32_t n_ctx, int32_t n_seg, int32_t seg_max_n, int32_t seg_max_t,
                         int32_t n_kv_head, int32_t* kernel);
-/* ---- the same over a Q8_0 cache (q3tts_engine_config.kv_q8_0; csrc/q3_attend_kv8.hip) ----
+/* ---- the same over a Q8_0 cache (q3tts_engine_config.kv_q8_0; csrc/q3_attend_kvq.hip in its Q8_0 / Q8_0 instance) ----
  * q3tts_k_attention_runs / q3tts_k_attention_decode_ex (without row_indexed) with the launch's cache in Q8_0 blocks: the quantising append
  * k_qk_prep_kv8 for the rows that are only cached, then ONE launch through the engine's launcher. The cache comes back un-blocked:
  * k_q / v_q int8 [slot][n_kv_head][n_ctx][hd], k_d / v_d f16 bits [slot][n_kv_head][n_ctx][hd / 32] (each optional). Arguments are
@@ -911,7 +911,7 @@ int q3tts_k_attention_decode_kv8(int32_t device, const float* qkv, int32_t n_slo
                                  int32_t n_kv_head, int32_t head_dim, const float* q_norm_w, const float* k_norm_w, float eps,
                                  float rope_theta, const int32_t* mrope_sections, int32_t policy, int32_t out_form, void* out,
                                  float* out_scale, int8_t* k_q, int8_t* v_q, uint16_t* k_d, uint16_t* v_d);
-/* ---- the same over a cache with Q4_0 blocks (q3tts_engine_options.kv_type_k / kv_type_v; csrc/q3_attend_kv4.hip) ----
+/* ---- the same over a cache with Q4_0 blocks (q3tts_engine_options.kv_type_k / kv_type_v; the same file's instances with a Q4_0 V) ----
  * The two _kv8 hooks with the cache's types named: (Q3TTS_KV_Q8_0, Q3TTS_KV_Q4_0) or (Q3TTS_KV_Q4_0, Q3TTS_KV_Q4_0), anything else is
  * Q3TTS_ERR_INVALID. The cache comes back un-blocked in the same shapes, one int8 per element: a Q8_0 quant as it is, a Q4_0 quant as
  * its nibble 0 .. 15 (the cached value is f16(d) * (q - 8)). q3tts_k_attend_pick_kv4 (host only): *kernel = 22 / 23 / 24:

@@ -10,7 +10,7 @@
 // ---------------------------------------------------------------------------------------------------
 // (pack_bf16x4 / k_cache_elem — a cache row's 8 bytes and where they live — are in q3_kernels.h: q3_attend_paged.hip uses them too)
 // (prep_rinv / prep_norm / prep_rope / prep_arith / prep_head — RMSNorm + RoPE of one head by one wave — are in q3_kernels.h: the Q8_0-cache
-// kernels of q3_attend_kv8.hip run the same statements)
+// kernels of q3_attend_kvq.hip run the same statements)
 // bf16 K (key-interleaved blocks; k_cache_elem's address for a run-time hd) and V (row-major) append of one kv head by lanes [0, hd/4)
 __device__ __forceinline__ void kv_append(uint16_t* kc, uint16_t* vc, size_t hb, int hd, int pos, int lane, const float o[4], const float4 vv) {
     const int blk = pos >> 6, kl = pos & 63, c = lane >> 1, e0 = 4 * (lane & 1);
@@ -46,8 +46,7 @@ __global__ __launch_bounds__(64) void k_qk_prep(Q3QkPrep a) {
     }
 }
 int q3_launch_qk_prep(const Q3QkPrep& a, hipStream_t s) {
-    if (a.kv4) return q3_launch_qk_prep_kv4(a, s);  // Q4_0 blocks in the cache: q3_attend_kv4.hip
-    if (a.kv8) return q3_launch_qk_prep_kv8(a, s);  // Q8_0 cache: the quantising append of q3_attend_kv8.hip
+    if (a.kv8 || a.kv4) return q3_launch_qk_prep_kvq(a, s);  // Q8_0 / Q4_0 blocks in the cache: the quantising append of q3_attend_kvq.hip
     if (a.tbl) return q3_launch_qk_prep_paged(a, s);  // paged cache: the append of q3_attend_paged.hip
     if (a.hd != Q3_ATT_HD) return 1;
     hipLaunchKernelGGL(k_qk_prep, dim3(a.rows, a.Hq + a.Hkv), dim3(64), 0, s, a);
@@ -797,16 +796,12 @@ static void att_policy_init() {
 void q3_attend_policy(int decode, int prefill) { att_policy_init(); g_att_decode = decode; g_att_prefill = prefill; }
 void q3_attend_policy_get(int* decode, int* prefill) { att_policy_init(); *decode = g_att_decode; *prefill = g_att_prefill; }
 
-// dynamic LDS above 64 KiB has to be allowed per kernel (and per device); a refused attribute is a refused launch
-static hipError_t att_allow_lds(const void* kernel, size_t lds) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
-
 // The kernel q3_launch_attend takes for a launch, under the current policies (the one place that decides; q3tts_k_attend_pick asks here too).
 // Q3_ATT_REFUSED: a head size other than Q3_ATT_HD, a GQA ratio outside {1, 2, 4}, a fused launch without a second wave for k / v (R == 1),
 // or the pair kernel for another ratio than 2.
 int q3_attend_pick(const Q3Attend& a) {
     att_policy_init();
-    if (a.kv4) return q3_attend_pick_kv4(a);  // Q4_0 blocks: one of the six kernels of q3_attend_kv4.hip
-    if (a.kv8) return q3_attend_pick_kv8(a);  // Q8_0 cache: one of the six kernels of q3_attend_kv8.hip, never one of the nine below
+    if (a.kv8 || a.kv4) return q3_attend_pick_kvq(a);  // Q8_0 / Q4_0 blocks: one of the six kernels of q3_attend_kvq.hip, never one of the nine below
     if (a.tbl) return q3_attend_pick_paged(a);  // paged cache: one of the seven of q3_attend_paged.hip
     if (a.hd != Q3_ATT_HD || a.Hkv <= 0 || a.Hq % a.Hkv) return Q3_ATT_REFUSED;
     const int R = a.Hq / a.Hkv;
@@ -828,8 +823,7 @@ int q3_attend_pick(const Q3Attend& a) {
 
 // 0: launched. Nonzero: refused, nothing launched — a shape q3_attend_pick refuses, or a device that refuses the LDS size.
 int q3_launch_attend(const Q3Attend& a, hipStream_t s) {
-    if (a.kv4) return q3_launch_attend_kv4(a, s);
-    if (a.kv8) return q3_launch_attend_kv8(a, s);
+    if (a.kv8 || a.kv4) return q3_launch_attend_kvq(a, s);
     if (a.tbl) return q3_launch_attend_paged(a, s);
     const int pick = q3_attend_pick(a);
     if (pick == Q3_ATT_REFUSED) return 1;
@@ -844,7 +838,7 @@ int q3_launch_attend(const Q3Attend& a, hipStream_t s) {
         return 0;
     }
     if (pick == Q3_ATT_GQA2) {
-        const size_t lds2 = ((size_t)2 * a.n_ctx + 2 * Q3_ATT_HD + 8 * Q3_ATT_HD + 16 + 128) * sizeof(float);  // as k_attend_gqa2 lays it out
+        const size_t lds2 = att_lds_gqa2(a.n_ctx).bytes;
         static Q3PerDevice pd2;
         if (lds2 > 65536 && !pd2.ensure(lds2, [&]() { return att_allow_lds((const void*)k_attend_gqa2, lds2); })) return 1;
         hipLaunchKernelGGL(k_attend_gqa2, grid, dim3(256), lds2, s, a);
@@ -903,8 +897,7 @@ __global__ __launch_bounds__(256) void k_kv_prefix(Q3KvPrefix a) {
 }
 void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s) {
     if (a.n <= 0) return;
-    if (a.kv4) { q3_launch_kv_prefix_kv4(a, s); return; }
-    if (a.kv8) { q3_launch_kv_prefix_kv8(a, s); return; }
+    if (a.kv8 || a.kv4) { q3_launch_kv_prefix_kvq(a, s); return; }
     if (a.tbl) { q3_launch_kv_prefix_paged(a, s); return; }
     hipLaunchKernelGGL(k_kv_prefix, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
 }
@@ -936,8 +929,7 @@ __global__ __launch_bounds__(256) void k_kv_prefix_save(Q3KvPrefix a) {
 int q3_launch_kv_prefix_save(const Q3KvPrefix& a, hipStream_t s) {
     if (a.n <= 0) return 0;
     if (a.hd != Q3_ATT_HD || a.n > Q3_KVP_MAX) return 1;
-    if (a.kv4) return q3_launch_kv_prefix_save_kv4(a, s);
-    if (a.kv8) return q3_launch_kv_prefix_save_kv8(a, s);
+    if (a.kv8 || a.kv4) return q3_launch_kv_prefix_save_kvq(a, s);
     if (a.tbl) return q3_launch_kv_prefix_save_paged(a, s);
     hipLaunchKernelGGL(k_kv_prefix_save, dim3(a.L * 2 * a.Hkv, a.n), dim3(256), 0, s, a);
     return 0;

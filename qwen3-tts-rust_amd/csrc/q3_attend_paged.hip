@@ -491,7 +491,6 @@ __global__ __launch_bounds__(256) void k_kv_prefix_save_paged(Q3KvPrefix a) {
     }
 }
 
-hipError_t attp_allow_lds(const void* kernel, size_t lds) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
 // what every paged launch needs beyond its contiguous form's checks: a bf16 cache in whole blocks and a row stride that covers n_ctx
 bool attp_table_ok(const int* tbl, int tbl_stride, int n_ctx, int kv8) { return tbl && !kv8 && n_ctx > 0 && n_ctx % 64 == 0 && tbl_stride >= n_ctx / 64; }
 }  // namespace
@@ -527,9 +526,9 @@ int q3_launch_attend_paged(const Q3Attend& a, hipStream_t s) {
     const int R = a.Hq / a.Hkv;
     const dim3 grid(a.Hkv, a.rows);
     if (pick == Q3_ATTP_GQA2) {
-        const size_t lds2 = ((size_t)2 * a.n_ctx + 2 * Q3_ATT_HD + 8 * Q3_ATT_HD + 16 + 128) * sizeof(float);  // as k_attend_gqa2_paged lays it out
+        const size_t lds2 = att_lds_gqa2(a.n_ctx).bytes;
         static Q3PerDevice pd2;
-        if (lds2 > 65536 && !pd2.ensure(lds2, [&]() { return attp_allow_lds((const void*)k_attend_gqa2_paged, lds2); })) return 1;
+        if (lds2 > 65536 && !pd2.ensure(lds2, [&]() { return att_allow_lds((const void*)k_attend_gqa2_paged, lds2); })) return 1;
         hipLaunchKernelGGL(k_attend_gqa2_paged, grid, dim3(256), lds2, s, a);
         return 0;
     }
@@ -538,7 +537,7 @@ int q3_launch_attend_paged(const Q3Attend& a, hipStream_t s) {
         const int pw = a.seg_max_t > 128 ? (a.seg_max_t + 63) & ~63 : 128;  // as k_attend_prefill_paged computes it
         const size_t lds3 = (size_t)nblk * 16384 + (size_t)a.seg_max_t * 256 + (size_t)8 * (pw + 128) * sizeof(float);
         static Q3PerDevice pd3;
-        if (lds3 > 65536 && !pd3.ensure(lds3, [&]() { return attp_allow_lds((const void*)k_attend_prefill_paged, lds3); })) return 1;
+        if (lds3 > 65536 && !pd3.ensure(lds3, [&]() { return att_allow_lds((const void*)k_attend_prefill_paged, lds3); })) return 1;
         hipLaunchKernelGGL(k_attend_prefill_paged, dim3(a.Hkv, a.n_seg), dim3(512), lds3, s, a);
         return 0;
     }
@@ -548,7 +547,7 @@ int q3_launch_attend_paged(const Q3Attend& a, hipStream_t s) {
             hipError_t e = hipSuccess;
             for (const void* k : {(const void*)k_attend_paged<2, true>, (const void*)k_attend_paged<4, true>, (const void*)k_attend_paged<1, false>,
                                   (const void*)k_attend_paged<2, false>, (const void*)k_attend_paged<4, false>})
-                if (e == hipSuccess) e = attp_allow_lds(k, lds);
+                if (e == hipSuccess) e = att_allow_lds(k, lds);
             return e;
         })) return 1;
     if (pick == Q3_ATTP_F2) hipLaunchKernelGGL((k_attend_paged<2, true>), grid, dim3(512), lds, s, a);

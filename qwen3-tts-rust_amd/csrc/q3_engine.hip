@@ -313,11 +313,11 @@ extern "C" int q3tts_engine_create_opts(const q3tts_engine_config* cfg, const q3
     }
     if (cfg->predictor_q8_0 == 1)
         return q3_set_err(nullptr, Q3TTS_ERR_UNSUPPORTED, "predictor_q8_0 = 1 (Q8_0 weights x bf16 activations) is not implemented for the Predictor: use 0 (bf16) or 2 (Q8_0 x Q8_0)");
-    // what the Q8_0-cache kernels (q3_attend_kv8.hip) cannot run is refused here, not at the first launch. (Today validate() above admits
+    // what the Q8_0-cache kernels (q3_attend_kvq.hip) cannot run is refused here, not at the first launch. (Today validate() above admits
     // no such shape — it already holds t_head_dim to 128, the GQA ratio to 1, 2, 4 and n_ctx to whole key blocks for every engine — so this
     // cannot be reached through the ABI yet; it is the place a wider validate() falls back on. The launcher's own refusals are tested
     // through q3tts_k_attend_pick_kv8.)
-    if (cfg->kv_q8_0 || kv4) {  // (the Q4_0 kernels of q3_attend_kv4.hip take the same shapes: q3_attend_pick hands over on kv4)
+    if (cfg->kv_q8_0 || kv4) {  // (the instances with Q4_0 blocks take the same shapes: q3_attend_pick hands over on kv4)
         const q3tts_model_config& mm = cfg->model;
         Q3Attend pa{}; pa.kv8 = 1; pa.kv4 = kv4; pa.hd = mm.t_head_dim; pa.Hq = mm.t_n_head; pa.Hkv = mm.t_n_kv_head; pa.n_ctx = cfg->n_ctx;
         const int R = mm.t_n_head / mm.t_n_kv_head;

@@ -509,7 +509,7 @@ extern "C" int q3tts_k_attention_decode_kv8(int32_t device, const float* qkv, in
     return attention_decode_ex(device, qkv, n_slots, lens, n_ctx, Hq, Hkv, hd, qnw, knw, eps, theta, sections, policy, 0, out_form, out, out_scale, c);
 }
 
-// ... over a cache with Q4_0 blocks (q3_attend_kv4.hip): the _kv8 hooks with the types named; quants come back one per element
+// ... over a cache with Q4_0 blocks (q3_attend_kvq.hip): the _kv8 hooks with the types named; quants come back one per element
 static int kv4_mask(int32_t tk, int32_t tv, const char* hook) {  // the Q3_KV4_* mask of an accepted pair; -1 (error text set) for any other
     if (tk == Q3TTS_KV_Q8_0 && tv == Q3TTS_KV_Q4_0) return Q3_KV4_V;
     if (tk == Q3TTS_KV_Q4_0 && tv == Q3TTS_KV_Q4_0) return Q3_KV4_K | Q3_KV4_V;

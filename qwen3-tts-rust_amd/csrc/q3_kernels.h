@@ -302,10 +302,10 @@ struct Q3QkPrep {
     uint16_t* kc; uint16_t* vc; int n_ctx;  // layer base; per (slot, kv head): n_ctx*hd elements
     const int* row_pos; const int* row_slot;
     int slot_mod, pos_const;  // slot_mod > 0: slot = row % slot_mod, pos = pos_const + row / slot_mod (no loads: the Predictor's per-frame cache is indexed by row)
-    // Q8_0 cache (kv8 = 1; q3_attend_kv8.hip): kc / vc then hold the int8 quants (one byte per element, layouts at q3_kv8_k_off)
+    // Q8_0 cache (kv8 = 1; q3_attend_kvq.hip): kc / vc then hold the int8 quants (one byte per element, layouts at q3_kv8_k_off)
     // and kd / vd the f16 block scales, per (slot, kv head) n_ctx * hd / 32 of them
     int kv8; uint16_t* kd; uint16_t* vd;
-    // Q4_0 blocks in that cache (kv4 != 0, with kv8 = 1; q3_attend_kv4.hip): Q3_KV4_V — V is Q4_0, K stays Q8_0;
+    // Q4_0 blocks in that cache (kv4 != 0, with kv8 = 1): Q3_KV4_V — V is Q4_0, K stays Q8_0;
     // Q3_KV4_K | Q3_KV4_V — both. A Q4_0 side holds half a byte per element (layouts at q3_kv4_k_off); the scales are where Q8_0's are.
     int kv4;
     // Paged cache (tbl != null; q3_attend_paged.hip): kc / vc are the layer's page pool [pages][Hkv][64 * hd] bf16 and
@@ -325,8 +325,8 @@ struct Q3Attend {
     const uint16_t* kc; const uint16_t* vc; int n_ctx;
     const int* row_pos; const int* row_slot;
     int slot_mod, pos_const;  // as in Q3QkPrep
-    int kv8; const uint16_t* kd; const uint16_t* vd;  // Q8_0 cache, as in Q3QkPrep: q3_launch_attend then takes the kernels of q3_attend_kv8.hip
-    int kv4;          // Q4_0 blocks in it, as in Q3QkPrep: q3_launch_attend then takes the kernels of q3_attend_kv4.hip
+    int kv8; const uint16_t* kd; const uint16_t* vd;  // Q8_0 cache, as in Q3QkPrep: q3_launch_attend then takes the kernels of q3_attend_kvq.hip
+    int kv4;          // Q4_0 blocks in it, as in Q3QkPrep: the instance of those kernels for the pair
     int fused;        // 1: every slot has exactly one row in this launch -> q/k prep + KV append done in-kernel (R >= 2)
                       // 2: rows b (position 0) and slot_mod + b (position 1) of every slot, nothing cached yet (R == 2): k_attend_pair
     Q3QkPrep prep;    // used when fused
@@ -339,7 +339,7 @@ struct Q3Attend {
     Q3_STAMP_FIELD
 };
 int q3_launch_attend(const Q3Attend& a, hipStream_t s);  // 0: launched; nonzero: refused (see its definition), nothing launched
-// k_attend's dynamic LDS (and k_attend_kv8's), offsets in floats: the kernels and their launchers both ask here
+// k_attend's dynamic LDS (and k_attend_kvq's), offsets in floats: the kernels and their launchers both ask here
 struct AttLds { size_t qh, ow, lw, mw, kh, vh, bytes; };
 Q3_HD AttLds att_lds(int R, int n_ctx) {
     constexpr int hd = Q3_ATT_HD;
@@ -353,6 +353,16 @@ Q3_HD AttLds att_lds(int R, int n_ctx) {
     L.bytes = (L.vh + hd) * sizeof(float);
     return L;
 }
+// ... and of the four-wave kernels for two query heads (k_attend_gqa2, _paged, _kvq): the same order with R = 2 and 64 words for each of
+// the newest key and value, (2 n_ctx + 2 hd + 8 hd + 16 + 128) floats in all
+Q3_HD AttLds att_lds_gqa2(int n_ctx) {
+    AttLds L = att_lds(2, n_ctx);
+    L.vh = L.kh + 64;
+    L.bytes = (L.vh + 64) * sizeof(float);
+    return L;
+}
+// dynamic LDS above 64 KiB has to be allowed per kernel (and per device, Q3PerDevice); a refused attribute is a refused launch
+inline hipError_t att_allow_lds(const void* kernel, size_t lds) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }
 #ifdef __HIPCC__
 // RMSNorm(hd) + RoPE of one head by one wave, the arithmetic in its three steps. Lane (< hd/4) holds its 4 consecutive elements x4, their
 // norm weights w4 and RoPE entries c4 / s4; every other lane holds x4 = 0 (+0 to the sum of squares).
@@ -443,73 +453,15 @@ __device__ __forceinline__ void att_out2(const Q3Attend& a, int row, int head, i
     else *(float2*)(a.out + (size_t)row * a.ldo + (size_t)head * Q3_ATT_HD + d) = make_float2(v0, v1);
 }
 #endif
-// The Talker's cache as ggml Q8_0 blocks (q3_attend_kv8.hip; q3tts_engine_config.kv_q8_0). A block is 32 consecutive dims of
+// The Talker's cache as ggml Q8_0 blocks (q3_attend_kvq.hip; q3tts_engine_config.kv_q8_0). A block is 32 consecutive dims of
 // one (position, KV head) vector: four per key (after q/k-norm and RoPE), four per value (the raw f32 row). Per (slot, KV head):
 //   K quants [64-key block][hd / 16 chunks][64 keys][16] int8 — one key per lane, one 16-byte load per chunk, 1 KiB contiguous per wave-load
 //   K scales [64-key block][hd / 32][64 keys] f16;  V quants [t][hd] int8 row-major;  V scales [t][hd / 32] f16
 // Byte offset of key element (pos, d) / f16 index of the scale of (pos, block j) inside a head's K cache:
 Q3_HD size_t q3_kv8_k_off(int pos, int d) { return ((size_t)((pos >> 6) * (Q3_ATT_HD >> 4) + (d >> 4)) * 64 + (pos & 63)) * 16 + (d & 15); }
 Q3_HD size_t q3_kv8_kd_idx(int pos, int j) { return ((size_t)(pos >> 6) * (Q3_ATT_HD >> 5) + j) * 64 + (pos & 63); }
-#ifdef __HIPCC__
-// The Q8_0 cache's device helpers that q3_attend_kv8.hip and q3_attend_kv4.hip (a Q8_0 K beside a Q4_0 V) share: one copy of each.
-__device__ __forceinline__ float kv8_d(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ float kv8_q(uint32_t w, int i) { return (float)(int8_t)(w >> (8 * i)); }
-
-// ggml's quantize_row_q8_0 (f32) on one block held by 8 consecutive lanes x 4 elements: d = amax / 127, id = d ? 1 / d : 0,
-// q = roundf(x * id), d kept as f16. *qw: the lane's four quants, element e in byte e; *d16: the block's scale (the same in all 8 lanes).
-__device__ __forceinline__ void kv8_quant4(const float x[4], uint32_t* qw, uint16_t* d16) {
-    float amax = fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])));
-    amax = fmaxf(amax, __shfl_xor(amax, 1)); amax = fmaxf(amax, __shfl_xor(amax, 2)); amax = fmaxf(amax, __shfl_xor(amax, 4));
-    const float d = amax / 127.0f, id = d != 0.0f ? 1.0f / d : 0.0f;
-    uint32_t w = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) w |= (uint32_t)(uint8_t)(int8_t)(int)roundf(x[e] * id) << (8 * e);
-    *qw = w;
-    *d16 = __builtin_bit_cast(unsigned short, (_Float16)d);
-}
-// dims 4 lane .. 4 lane + 3 of position pos into a head's K cache (kq: the head's quants, kd: its scales), lanes [0, hd/4)
-__device__ __forceinline__ void kv8_put_k(int8_t* kq, uint16_t* kd, int pos, int lane, uint32_t w, uint16_t d16) {
-    *(uint32_t*)(kq + q3_kv8_k_off(pos, 4 * lane)) = w;
-    if ((lane & 7) == 0) kd[q3_kv8_kd_idx(pos, lane >> 3)] = d16;
-}
-// ... and into LDS in the packed form: words [0, 32) the quants in dim order (key chunk c = 16 bytes at l + 4 c), then the 4 scales
-__device__ __forceinline__ void kv8_put_lds(uint32_t* l, int lane, uint32_t w, uint16_t d16) {
-    l[lane] = w;
-    if ((lane & 7) == 0) ((uint16_t*)(l + 32))[lane >> 3] = d16;
-}
-__device__ __forceinline__ uint16_t kv8_lds_d(const uint32_t* l, int j) { return ((const uint16_t*)(l + 32))[j]; }
-// A key as its lane holds it, made opaque to the optimiser once the newest key has been put in place of the cached one. Without it the
-// compiler dequantises the newest key ahead of the key-block loop (it is loop-invariant) and keeps all 128 floats live beside the cached key's
-// registers: k_attend_kv8<2, true> took 180 VGPRs instead of 63, k_attend_gqa2_kv8 ran out of its 256 and spilled.
-// (N chunks: 8 of a Q8_0 key, 4 of a Q4_0 key.) Nothing enforces this: after a compiler upgrade, or a change to these kernels, compile q3_attend_kv8.hip with
-// -Rpass-analysis=kernel-resource-usage (plus the Makefile's FLAGS) and look for 79 VGPRs in k_attend_kv8<2, true> / <4, true>, about 170
-// in k_attend_gqa2_kv8, and ScratchSize 0 in every kernel here.
-template <int N> __device__ __forceinline__ void kv8_opaque(uint4 (&kv)[N], uint16_t (&ks)[4]) {
-#pragma unroll
-    for (int c = 0; c < N; ++c) asm volatile("" : "+v"(kv[c].x), "+v"(kv[c].y), "+v"(kv[c].z), "+v"(kv[c].w));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { uint32_t t = ks[j]; asm volatile("" : "+v"(t)); ks[j] = (uint16_t)t; }
-}
-
-// The two chains of the canonical order on x^ = d * q. Score: 16 dims of a key (one chunk, d ascending; one block scale).
-__device__ __forceinline__ float att8_dot4(const float4 q, uint32_t w, float d, float s) {
-    s = fmaf(q.x, d * kv8_q(w, 0), s); s = fmaf(q.y, d * kv8_q(w, 1), s);
-    s = fmaf(q.z, d * kv8_q(w, 2), s); s = fmaf(q.w, d * kv8_q(w, 3), s);
-    return s;
-}
-__device__ __forceinline__ float att8_dot16(const float* q, const uint4 k, float d, float s) {
-    s = att8_dot4(*(const float4*)q, k.x, d, s); s = att8_dot4(*(const float4*)(q + 4), k.y, d, s);
-    s = att8_dot4(*(const float4*)(q + 8), k.z, d, s); s = att8_dot4(*(const float4*)(q + 12), k.w, d, s);
-    return s;
-}
-#endif
-// the launches of q3_attend_kv8.hip: q3_launch_qk_prep / q3_attend_pick / q3_launch_attend / q3_launch_kv_prefix hand over when kv8 is set
-int q3_launch_qk_prep_kv8(const Q3QkPrep& a, hipStream_t s);
-int q3_attend_pick_kv8(const Q3Attend& a);
-int q3_launch_attend_kv8(const Q3Attend& a, hipStream_t s);
-// ggml Q4_0 blocks in that cache (q3_attend_kv4.hip; q3tts_engine_options.kv_type_k / kv_type_v): V alone (K stays Q8_0, its
-// layout and kernels' key path as above) or K and V. A block is the same 32 dims; its 32 four-bit quants are 16 bytes, its scale one f16.
-// Per (slot, KV head):
+// ggml Q4_0 blocks in that cache (q3tts_engine_options.kv_type_k / kv_type_v): V alone (K stays Q8_0, layout as above) or
+// K and V. A block is the same 32 dims; its 32 four-bit quants are 16 bytes, its scale one f16. Per (slot, KV head):
 //   K quants [64-key block][hd / 32 blocks][64 keys][16 bytes] — one block of one key per 16-byte load, one key per lane, 1 KiB per wave-load,
 //            four loads per key (Q8_0: eight); K scales exactly as Q8_0's (q3_kv8_kd_idx)
 //   V quants [t][hd / 2 bytes] row-major — the 8 dims of a value-pass lane are one 4-byte word; V scales [t][hd / 32] f16
@@ -521,10 +473,11 @@ Q3_HD size_t q3_kv4_k_off(int pos, int d) { return ((size_t)((pos >> 6) * (Q3_AT
 Q3_HD size_t q3_kv4_v_off(int pos, int d) { return (size_t)pos * (Q3_ATT_HD >> 1) + (d >> 1); }
 // bytes that n cache elements take as quants on the K (v = 0) or V (v = 1) side of a cache with Q4_0 mask kv4
 Q3_HD size_t q3_kv4_bytes(int kv4, int v, size_t n) { return (kv4 & (v ? Q3_KV4_V : Q3_KV4_K)) ? n >> 1 : n; }
-// the launches of q3_attend_kv4.hip: the same launchers hand over when kv4 is set (accepted: Q3_KV4_V and Q3_KV4_K | Q3_KV4_V, with kv8 = 1)
-int q3_launch_qk_prep_kv4(const Q3QkPrep& a, hipStream_t s);
-int q3_attend_pick_kv4(const Q3Attend& a);
-int q3_launch_attend_kv4(const Q3Attend& a, hipStream_t s);
+// the launches of q3_attend_kvq.hip: q3_launch_qk_prep / q3_attend_pick / q3_launch_attend / q3_launch_kv_prefix(_save) hand over when kv8
+// is set (accepted: kv4 = 0, Q3_KV4_V and Q3_KV4_K | Q3_KV4_V)
+int q3_launch_qk_prep_kvq(const Q3QkPrep& a, hipStream_t s);
+int q3_attend_pick_kvq(const Q3Attend& a);
+int q3_launch_attend_kvq(const Q3Attend& a, hipStream_t s);
 // The gathering form of k_attend_small (block 0 of passes q >= 1 of the greedy bf16 Predictor): the row's q / k / v are not
 // read from a.qkv but from a table of every possible input row's layer-0 QKV, tab[code], where code is the argmax k_pred_next<false>(q)
 // takes from the same per-tile keys (largest key of the row, q3_argmax_idx); a code outside [0, tab_rows) reads the fallback row tab_rows.
@@ -546,13 +499,13 @@ int q3_launch_attend_gather(const Q3Attend& a, const Q3AttGather& t, hipStream_t
 enum { Q3_ATT_REFUSED = -1, Q3_ATT_N1 = 0, Q3_ATT_N2 = 1, Q3_ATT_N4 = 2,   // k_attend<1 / 2 / 4, false>
        Q3_ATT_F2 = 3, Q3_ATT_F4 = 4,                                       // k_attend<2 / 4, true>
        Q3_ATT_GQA2 = 5, Q3_ATT_SMALL2 = 6, Q3_ATT_PAIR = 7, Q3_ATT_PREFILL = 8,
-       // the six of q3_attend_kv8.hip (Q3Attend.kv8; q3tts_k_attend_pick_kv8): k_attend_kv8<1 / 2 / 4, false>, k_attend_kv8<2 / 4, true>, k_attend_gqa2_kv8
+       // the six of q3_attend_kvq.hip in the instance Key<false>, Val<false> (Q3Attend.kv8; q3tts_k_attend_pick_kv8): k_attend_kvq<1 / 2 / 4, false>,
+       // k_attend_kvq<2 / 4, true>, k_attend_gqa2_kvq. (The test labels "k_attend_kv8<..>" / "k_attend_kv4<..>" name these instances.)
        Q3_ATT8_N1 = 9, Q3_ATT8_N2 = 10, Q3_ATT8_N4 = 11, Q3_ATT8_F2 = 12, Q3_ATT8_F4 = 13, Q3_ATT8_GQA2 = 14,
        // the seven of q3_attend_paged.hip (Q3Attend.tbl; q3tts_k_attend_pick_paged): k_attend_paged<1 / 2 / 4, false>, <2 / 4, true>,
        // k_attend_gqa2_paged, k_attend_prefill_paged
        Q3_ATTP_N1 = 15, Q3_ATTP_N2 = 16, Q3_ATTP_N4 = 17, Q3_ATTP_F2 = 18, Q3_ATTP_F4 = 19, Q3_ATTP_GQA2 = 20, Q3_ATTP_PREFILL = 21,
-       // the six of q3_attend_kv4.hip (Q3Attend.kv4; q3tts_k_attend_pick_kv4), each in two instances (K Q8_0 / K Q4_0): k_attend_kv4<1 / 2 / 4, false>,
-       // k_attend_kv4<2 / 4, true>, k_attend_gqa2_kv4
+       // the same six in the instances with Q4_0 blocks (Q3Attend.kv4; q3tts_k_attend_pick_kv4): Key<false>, Val<true> and Key<true>, Val<true>
        Q3_ATT4_N1 = 22, Q3_ATT4_N2 = 23, Q3_ATT4_N4 = 24, Q3_ATT4_F2 = 25, Q3_ATT4_F4 = 26, Q3_ATT4_GQA2 = 27 };
 // the launches of q3_attend_paged.hip: q3_launch_qk_prep / q3_attend_pick / q3_launch_attend / q3_launch_kv_prefix(_save) hand over when tbl is set
 int q3_launch_qk_prep_paged(const Q3QkPrep& a, hipStream_t s);
@@ -582,16 +535,14 @@ struct Q3KvPrefix {
 void q3_launch_kv_prefix(const Q3KvPrefix& a, hipStream_t s);
 int q3_launch_kv_prefix_paged(const Q3KvPrefix& a, hipStream_t s);       // (q3_attend_paged.hip; nonzero: refused — bf16 only, hd = Q3_ATT_HD)
 int q3_launch_kv_prefix_save_paged(const Q3KvPrefix& a, hipStream_t s);
-void q3_launch_kv_prefix_kv8(const Q3KvPrefix& a, hipStream_t s);  // (q3_attend_kv8.hip; q3_launch_kv_prefix hands over when kv8 is set)
-// The other direction (k_kv_prefix_save / k_kv_prefix_save_kv8): positions < P[j] of slot[j] into the store pk[j] / pv[j] (written, though
+// The other direction (k_kv_prefix_save / k_kv_prefix_save_kvq): positions < P[j] of slot[j] into the store pk[j] / pv[j] (written, though
 // the struct names them const), which must come zero-filled: the result is byte for byte the store q3tts_prefix_create makes of the same
 // rows — the keys P[j] .. np - 1 of the last block are written as zeros, values and (Q8_0) scales likewise stop at P[j].
 // 0: launched (or n == 0); nonzero: refused, nothing launched (hd != Q3_ATT_HD, more than Q3_KVP_MAX entries, a Q8_0 cache without scales)
 int q3_launch_kv_prefix_save(const Q3KvPrefix& a, hipStream_t s);
-int q3_launch_kv_prefix_save_kv8(const Q3KvPrefix& a, hipStream_t s);
-// (q3_attend_kv4.hip; both hand over when kv4 is set. Nonzero: refused, nothing launched)
-int q3_launch_kv_prefix_kv4(const Q3KvPrefix& a, hipStream_t s);
-int q3_launch_kv_prefix_save_kv4(const Q3KvPrefix& a, hipStream_t s);
+// (q3_attend_kvq.hip; both hand over when kv8 is set. Nonzero: refused, nothing launched)
+int q3_launch_kv_prefix_kvq(const Q3KvPrefix& a, hipStream_t s);
+int q3_launch_kv_prefix_save_kvq(const Q3KvPrefix& a, hipStream_t s);
 void q3_attend_policy(int decode, int prefill);  // test hook (q3tts_k_attend_policy): which kernel variant serves decode / prefill attention (same bits)
 void q3_attend_policy_get(int* decode, int* prefill);
 

@@ -103,7 +103,7 @@ int q3_run_layers(q3tts_engine* e, const Q3Tfm& t, const Q3Rows& r, const Q3Laye
         if (!gather) bad += q3_launch_gemm(e, t, q3_gemm_qkv(t, l, r, sc, a.rows, eps, once), s, l == (a.gather ? 1 : 0) ? a.probe : nullptr, 1);
         Q3QkPrep qp{}; qp.qkv = sc.qkv; qp.ld = t.nqkv; qp.rows = a.rows; qp.Hq = t.Hq; qp.Hkv = t.Hkv; qp.hd = t.hd;
         qp.qnw = t.qn[l]; qp.knw = t.kn[l]; qp.eps = eps; qp.cs = t.cs; qp.sn = t.sn;
-        q3_layer_cache(c, l, &qp.kc, &qp.vc, &qp.kd, &qp.vd); qp.kv8 = c.kv8 ? 1 : 0; qp.kv4 = c.kv4;  // (kv_q8_0: quants + scales, and the kernels of q3_attend_kv8.hip)
+        q3_layer_cache(c, l, &qp.kc, &qp.vc, &qp.kd, &qp.vd); qp.kv8 = c.kv8 ? 1 : 0; qp.kv4 = c.kv4;  // (kv_q8_0: quants + scales, and the kernels of q3_attend_kvq.hip)
         qp.n_ctx = c.n_ctx; qp.row_pos = a.row_pos; qp.row_slot = a.row_slot;
         qp.tbl = c.tbl; qp.tbl_stride = c.tbl_stride;  // (kv_pages: the page table, and the kernels of q3_attend_paged.hip)
         qp.slot_mod = a.slot_mod; qp.pos_const = a.pos_const;

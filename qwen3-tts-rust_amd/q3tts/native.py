@@ -1248,9 +1248,9 @@ ATTEND_KERNELS_KV4 = {22: "k_attend_kv4<1, false>", 23: "k_attend_kv4<2, false>"
 
 
 def k_attend_pick_kv8(fused, gqa_ratio, n_ctx, n_kv_head, n_seg=0, seg_max_n=0, seg_max_t=0, want_code=False, kv_types=None):
-    """q3tts_k_attend_pick_kv8 (host only): the kernel of csrc/q3_attend_kv8.hip the launcher takes for a launch over a Q8_0 cache under the
+    """q3tts_k_attend_pick_kv8 (host only): the kernel of csrc/q3_attend_kvq.hip (its Q8_0 / Q8_0 instance) the launcher takes for a launch over a Q8_0 cache under the
     current policies — its name (want_code: its number 9 .. 14) — or None when the launcher refuses. kv_types = (k, v): q3tts_k_attend_pick_kv4,
-    a cache with Q4_0 blocks and the kernels 22 .. 27 of csrc/q3_attend_kv4.hip."""
+    a cache with Q4_0 blocks and the kernels 22 .. 27, the same file's instances with a Q4_0 V."""
     lib = _abi.load_library()
     k = C.c_int32(-2)
     if kv_types:

@@ -1,4 +1,4 @@
-"""The Talker's K/V cache as ggml Q8_0 blocks (q3tts_engine_config.kv_q8_0, csrc/q3_attend_kv8.hip): the cases and the
+"""The Talker's K/V cache as ggml Q8_0 blocks (q3tts_engine_config.kv_q8_0, csrc/q3_attend_kvq.hip): the cases and the
 two-stage float64 checks that tests/test_kv_q8_cpu.py (numpy alone) and tests/test_kv_q8_gpu.py (the device) share. The reference is the
 one of tests/_attend_ref.py, split at the cache:
   stage 1, K: with k64 = prep64(...) (RMSNorm + M-RoPE in float64) and a64 = max |k64| of a block of 32 dims, the cached scale must be
@@ -23,7 +23,7 @@ SCALE_WINDOW = 2.0 ** -20
 QUANT_WINDOW = 2.0 ** -10
 SHARE_CAP = 5e-3
 
-# the kernels of csrc/q3_attend_kv8.hip as q3tts_k_attend_pick_kv8 numbers them
+# the kernels of csrc/q3_attend_kvq.hip (labels: its Q8_0 / Q8_0 instances) as q3tts_k_attend_pick_kv8 numbers them
 KERNELS = {9: "k_attend_kv8<1, false>", 10: "k_attend_kv8<2, false>", 11: "k_attend_kv8<4, false>", 12: "k_attend_kv8<2, true>",
            13: "k_attend_kv8<4, true>", 14: "k_attend_gqa2_kv8"}
 

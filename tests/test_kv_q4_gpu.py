@@ -1,4 +1,4 @@
-"""The Talker's K/V cache with ggml Q4_0 blocks (q3tts_engine_options.kv_type_k / kv_type_v, csrc/q3_attend_kv4.hip) on the
+"""The Talker's K/V cache with ggml Q4_0 blocks (q3tts_engine_options.kv_type_k / kv_type_v, csrc/q3_attend_kvq.hip) on the
 device, in both accepted modes: K Q8_0 with V Q4_0, and both Q4_0.
 Kernel level (q3tts_k_attention_runs_kv4 / _decode_kv4; the quants come back one per element, a Q4_0 quant as its nibble 0 .. 15):
   1. stage 1 — V equals the numpy-f32 restatement of quantize_row_q4_0 below bit for bit; K is held to the quantiser applied to the
@@ -111,6 +111,33 @@ def test_kv4_kernels(oracle, mode, Hkv, R, T):
         lib.q3tts_k_attend_policy(0, 0)
     print(counts.line(spec["name"]))
     counts.check_caps(spec["name"])
+
+
+def test_kv4_policies_are_independent():
+    """What lets one key policy and one value policy serve three caches: on the same rows a Q8_0 K holds the same quants and scales beside a
+    Q8_0 V and beside a Q4_0 V, and a Q4_0 V the same beside a Q8_0 K and beside a Q4_0 K — from the run kernel and from the decode step
+    under both policies (the gqa2 kernel and the fused one). Slots of 65 and 257 keys: past one key block, past 256 keys, at a block edge."""
+    from q3tts import _abi, native
+    lib = _abi.load_library()
+    Hkv, R, lens = 2, 2, [65, 257]
+    Hq = Hkv * R
+    spec = dict(name="kv4_pairs", hook="runs", heads=(Hq, Hkv), seqs=[(0, n) for n in lens])
+    shape = (N_CTX, Hq, Hkv, A.HD)
+    xs, qn, kn = A.make_inputs(spec, "normal")
+    rows = np.concatenate(xs)
+    pairs = (None, MODES["q8_q4"], MODES["q4_q4"])
+    calls = [("runs", lambda kt: native.k_attention_runs_kv8(rows, spec["seqs"], *shape, qn, kn, *TAIL, policy=2, kv_types=kt))]
+    for policy in (0, 1):
+        calls.append((f"decode policy {policy}", lambda kt, p=policy: native.k_attention_decode_kv8(rows, lens, *shape, qn, kn, *TAIL, policy=p, kv_types=kt)))
+    try:
+        for what, call in calls:
+            q8_q8, q8_q4, q4_q4 = (call(kt) for kt in pairs)
+            for k in ("k_q", "k_d"):
+                assert np.array_equal(q8_q8[k], q8_q4[k]), (what, k, "a Q8_0 K depends on the V beside it")
+            for k in ("v_q", "v_d"):
+                assert np.array_equal(q8_q4[k], q4_q4[k]), (what, k, "a Q4_0 V depends on the K beside it")
+    finally:
+        lib.q3tts_k_attend_policy(0, 0)
 
 
 @pytest.mark.parametrize("Hkv,R", [(1, 1), (2, 2), (1, 4)])

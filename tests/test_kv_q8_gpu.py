@@ -1,4 +1,4 @@
-"""The Q8_0 K/V cache (q3tts_engine_config.kv_q8_0, csrc/q3_attend_kv8.hip) on the device.
+"""The Q8_0 K/V cache (q3tts_engine_config.kv_q8_0, csrc/q3_attend_kvq.hip) on the device.
 Kernel level, one launch at a time through q3tts_k_attention_runs_kv8 / _decode_kv8 (the cases of tests/_kv_q8.py, every input kind):
   1. stage 1 (the cache: K within the windows of tests/_kv_q8.py, V equal to q3o_quantize_q8_0) and stage 2 (the output against float64
      over the cache as returned, ATT_STAGE2_TOL of tests/_oracle.py);
